@@ -2,6 +2,7 @@
 """bench.py - gridcell-timesteps/sec of the full water+energy timestep (all 7 kernels) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cols C] [--tier A|B] [--workload timestep7|soil_temperature] [--fused]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  `python bench.py --gpus N` without a launcher starts the N rank processes itself (the parent never
@@ -419,6 +420,31 @@ def timed_steps(D, workload, steps, warmup, sync_all, dist, torch, red_device="c
     return elapsed
 
 
+DUMP_COLUMNS = 8192  # x 6 216 B of state per column (every field as float64) = 51 MB
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 0xD0E5
+
+
+def dump_outputs(D, out_dir):
+    """What the timed path left in the state after its last step, as a caller of that path would download it: every state
+    field at a fixed, seeded sample of DUMP_COLUMNS columns (all columns when there are fewer), as float64 (integer fields
+    converted exactly), one DIR/<field>.npy each, and the sampled column indices as DIR/sample_columns.npy."""
+    import numpy as np
+
+    n = D.ncols
+    cols = np.arange(n) if n <= DUMP_COLUMNS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_COLUMNS, replace=False))
+    lo, hi = int(cols[0]), int(cols[-1]) + 1
+    arrays = {"sample_columns": cols.astype(np.float64)}
+    for name in sorted(D.fields):
+        arrays[name] = D.download(name, col0=lo, n=hi - lo)[cols - lo].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "columns": len(cols), "arrays": len(arrays), "bytes": total}
+
+
 def event_time_soil(D, nsteps):
     """Mean device time of the soil_temperature launch: HIP events on the context's stream (elmk_profile_wrapper), the
     snapshot restored before every launch outside the event brackets."""
@@ -634,7 +660,12 @@ def main(argv=None):
     ap.add_argument("--state-f32", action="store_true",
                     help="also measure BASELINE config 5's fp32-state variant (libelmk_f32.so: fp64 fields stored as fp32, fp64 arithmetic, "
                          "fused step) as a separate object fp32_state_10M - reported beside the fp64 numbers, never as `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (every field at a fixed sample of rank 0's columns, "
+                         "float64) as DIR/<field>.npy, for comparing the outputs of two builds")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "RANK" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, argv)
@@ -644,10 +675,6 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     args.gpus = world  # under a launcher the launcher decides
 
-    # every HIP stream its own hardware queue (the runtime's default is 4 queues shared by all streams of the process): kernels of two
-    # contexts' streams can then be resident together (two_block_pipeline); no effect on the one-context measurements (A/B in
-    # profiles/r04_two_block_overlap.txt).  Read by the runtime when it initialises, hence before torch is imported.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     if world == 1 and not args.no_cpu_baseline:
         # the CPU-baseline leg: OpenMP threads bound to neighbouring cores and sleeping between parallel regions instead of
         # spinning on a shared host.  libgomp reads these once, when it is loaded (import torch loads it), hence here.  Not at
@@ -713,8 +740,11 @@ def main(argv=None):
             D.sync()
         return D, host_state
 
-    def measure(D, steps, warmup, with_dist, fused=None):
+    dumped = None
+
+    def measure(D, steps, warmup, with_dist, fused=None, dump=False):
         """-> (seconds of the timed region, per-launch-group ms, ms of the whole step by HIP events)."""
+        nonlocal dumped
         fused = args.fused if fused is None else fused
         def sync_all():
             D.sync()
@@ -724,6 +754,8 @@ def main(argv=None):
                 dist.barrier()
 
         el = timed_steps(D, args.workload, steps, warmup, sync_all, dist if with_dist else None, torch, red_device, fused)
+        if dump:  # before the profiling steps below advance the state further
+            dumped = dump_outputs(D, args.dump_outputs)
         if rehearsal is not None:
             return el, [], 0.0
         if soil:
@@ -756,7 +788,8 @@ def main(argv=None):
     sun_frac = float((D["coszen"] > 0).mean())
     if args.graph and not soil and rehearsal is None:
         D.set_graph(True)
-    elapsed, ms, ms_total = measure(D, args.steps, args.warmup, True)
+    elapsed, ms, ms_total = measure(D, args.steps, args.warmup, True,
+                                    dump=args.dump_outputs is not None and rank == 0 and rehearsal is None)
     flags, first_bad = D.error_summary()
     state_gb = round(D.device_bytes / 1e9, 3)
     step_time = None
@@ -863,8 +896,7 @@ def main(argv=None):
             D.close()
             D = None
         blocks2 = {"what": "fused step, the columns as two contexts of cols / 2 on two streams, k_cf_iterate in 256-thread workgroups "
-                           "(elmk_set_option ELMK_OPT_CF_HALF_WORKGROUPS); needs GPU_MAX_HW_QUEUES above the runtime's default of 4",
-                   "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")}
+                           "(elmk_set_option ELMK_OPT_CF_HALF_WORKGROUPS); the streams share the process's hardware queues"}
         for tier in ("A", "B"):
             half = args.cols // 2
             ctxs = [build_state(half, device_index, tier, args.seed + i)[0] for i in range(2)]
@@ -1026,6 +1058,8 @@ def main(argv=None):
             out["two_block_pipeline"] = blocks2
         if f32 is not None:
             out["fp32_state_10M"] = f32
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1 and rehearsal is None:  # reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(host_state, workload=args.workload)
         print(json.dumps(out), flush=True)

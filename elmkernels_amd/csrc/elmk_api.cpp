@@ -954,7 +954,8 @@ int enqueue_stages(elmk_ctx* ctx, stage_fn fn, int nstage, double dt, hipEvent_t
   return ELMK_OK;
 }
 
-// the stages captured once as a HIP graph (kernel nodes + the side-stream fork / join inside albedo_snicar) and replayed
+// the stages captured once as a HIP graph (kernel nodes in one chain: the side-stream forks are issued in order on the
+// capturing stream) and replayed
 int run_graph(elmk_ctx* ctx, GraphSlot& g, stage_fn fn, int nstage, double dt)
 {
   if (!g.exec || g.dt != dt || g.stream != ctx->stream) {
@@ -967,7 +968,9 @@ int run_graph(elmk_ctx* ctx, GraphSlot& g, stage_fn fn, int nstage, double dt)
     }
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    ctx->side.one_stream = true;  // one chain of nodes: no fork onto the side streams (elmk_kernels.h: SideStreams)
     for (int k = 0; k < nstage; k++) fn(ctx, k, dt);
+    ctx->side.one_stream = false;
     // a launch that failed during capture leaves its error in the runtime and may have invalidated the capture: read it,
     // and ALWAYS end the capture so that neither the stream nor the forked side streams stay in capture mode
     const hipError_t launch_err = hipGetLastError();

@@ -151,6 +151,12 @@ void launch_albedo_snicar(const DevState* S, int64_t n, hipStream_t st, const Si
   if (n >= 262144) {
     launch_snicar_deep_all(S, capped, n, st);
     hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, st, S);
+  } else if (side->one_stream) {  // (graph capture: the same five queues one after another on the caller's stream)
+    launch_snicar_deep<5>(S, capped, n, st);
+    launch_snicar_deep<4>(S, capped, n, st);
+    launch_snicar_deep<3>(S, capped, n, st);
+    launch_snicar_deep<2>(S, capped, n, st);
+    hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, st, S);
   } else {
     (void)hipEventRecord(side->fork, st);
     for (int i = 0; i < 4; i++) (void)hipStreamWaitEvent(side->s[i], side->fork, 0);

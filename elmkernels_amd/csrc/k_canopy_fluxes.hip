@@ -1988,6 +1988,8 @@ void launch_fused_stage(const DevState* S, int64_t n, double dt, hipStream_t st,
 {
   if (n <= 0) return;
   const unsigned nblk = (unsigned)((n + 255) / 256);
+  const bool use_side = n >= 262144 && !side->one_stream;  // (one_stream: graph capture, every launch on st)
+  const bool bg_side = FZ_BG_OVERLAP && use_side;
   switch (stage) {
     case 0: hipLaunchKernelGGL(k_fz_prep, dim3((nblk + FZ_PREP_TILES - 1) / FZ_PREP_TILES), dim3(256), 0, st, S); break;
     case 1:
@@ -2003,7 +2005,7 @@ void launch_fused_stage(const DevState* S, int64_t n, double dt, hipStream_t st,
         if (FZ_SNICAR_GRID_BY_TILES && gs < nblk) gs = nblk;
         hipLaunchKernelGGL(k_fz_snicar_pre, dim3(gs + nblk), dim3(256), 0, st, S, gs, nblk);
         if (!FZ_ALB_FWD) launch_albedo_snicar_part(S, n, st, 1, nullptr);  // (else k_fz_stream runs stage 3 itself)
-      } else if (n >= 262144) {
+      } else if (use_side) {
         // k_fz_pre (memory-bound) beside the albedo stage (fp64-issue-bound) on a side stream; joined before k_fz_stream
         (void)hipEventRecord(side->fork, st);
         (void)hipStreamWaitEvent(side->s[0], side->fork, 0);
@@ -2026,7 +2028,7 @@ void launch_fused_stage(const DevState* S, int64_t n, double dt, hipStream_t st,
       // With FZ_BG_OVERLAP the list kernel goes to a side stream behind k_cf_iterate's launch (case 4): a few hundred workgroups
       // of long dependent chains that cannot fill the machine on their own (VALU busy 0.31 on the branch-mix tier) run in the
       // CUs the persistent iteration kernel frees during its tail, instead of in front of it.
-      if (FZ_BG_OVERLAP && n >= 262144) {
+      if (bg_side) {
         (void)hipEventRecord(side->fork, st);
       } else {
         launch_bareground_list(S, n, st);
@@ -2034,13 +2036,13 @@ void launch_fused_stage(const DevState* S, int64_t n, double dt, hipStream_t st,
       break;
     default: {
       launch_cf_iterate(S, nblk, dt, st, side, 0);
-      if (FZ_BG_OVERLAP && n >= 262144) {
+      if (bg_side) {
         (void)hipStreamWaitEvent(side->s[0], side->fork, 0);
         launch_bareground_list(S, n, side->s[0]);
         (void)hipEventRecord(side->join[0], side->s[0]);
       }
       hipLaunchKernelGGL(k_cf_finish, dim3(nblk), dim3(256), 0, st, S, dt, 0);
-      if (FZ_BG_OVERLAP && n >= 262144) (void)hipStreamWaitEvent(st, side->join[0], 0);
+      if (bg_side) (void)hipStreamWaitEvent(st, side->join[0], 0);
     }
   }
 }

@@ -247,3 +247,35 @@ def test_bench_cpu_budget_and_floor(tmp_path, monkeypatch):
     assert bench.step_floor("A", 10_000_000, 2.5, 5000.0) is None                  # another column count: no claim
     monkeypatch.setattr(bench, "kernel_source_hash", lambda: "another build")
     assert bench.step_floor("A", 1_000_000, 2.5, 5000.0) is None                   # another build: no claim
+
+
+def test_bench_dump_outputs_is_a_fixed_float64_sample(tmp_path):
+    """bench.py --dump-outputs on a stand-in for the device state (the real field table, host arrays behind download): every field
+    at the same seeded columns from run to run, float64, integer fields exact, under 64 MB in all."""
+    import bench
+
+    class Stand:
+        def __init__(self, n):
+            rng = np.random.default_rng(5)
+            self.ncols, self.fields = n, st.field_table()
+            self.arr = {k: (rng.integers(-9, 1 << 20, size=(n, nl)) if np.dtype(dt).kind in "iu" else rng.random((n, nl))).astype(dt)
+                        for k, (_, nl, dt) in self.fields.items()}
+
+        def download(self, name, col0=0, n=None):
+            a = self.arr[name][col0:col0 + n]
+            return a[:, 0].copy() if self.fields[name][1] == 1 else a.copy()
+
+    D = Stand(bench.DUMP_COLUMNS * 3 + 1)
+    info = bench.dump_outputs(D, str(tmp_path / "a"))
+    bench.dump_outputs(D, str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted([k + ".npy" for k in D.fields] + ["sample_columns.npy"]) == sorted(os.listdir(tmp_path / "b"))
+    assert info["bytes"] == sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= 64 << 20
+    cols = np.load(tmp_path / "a" / "sample_columns.npy").astype(np.int64)
+    assert len(cols) == bench.DUMP_COLUMNS and len(np.unique(cols)) == len(cols) and cols.max() < D.ncols
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        if f != "sample_columns.npy":
+            src = D.arr[f[:-4]][cols]
+            assert np.array_equal(a, (src[:, 0] if src.shape[1] == 1 else src).astype(np.float64))

@@ -1,7 +1,9 @@
 """elmkernels_amd/testinput.py - the reader of the reference's NSTEP-block text format (ELM::IO::ELMtestinput,
-src/utils/read_test_input.hh / .cc) - on a file written here in that format, and, where the reference tree is mounted
-(build container only), on one of its own fixture files against the committed golden conversion."""
+src/utils/read_test_input.hh / .cc) - on a file written here in that format, and on one of the reference's own fixture files
+(a verbatim, gzipped copy under tests/golden/text/) against the committed golden conversion."""
+import gzip
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -65,9 +67,11 @@ def test_compare_output_is_almost_equal(path):
     assert not TI.is_almost_equal(np.nan, np.nan).any()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/test/data/CanopyHydrology_IN.txt"), reason="reference tree not mounted")
-def test_reads_a_reference_fixture_like_the_golden_conversion():
-    inp = TI.ELMtestinput("/root/reference/test/data/CanopyHydrology_IN.txt")
+def test_reads_a_reference_fixture_like_the_golden_conversion(tmp_path):
+    p = tmp_path / "CanopyHydrology_IN.txt"
+    with gzip.open(os.path.join(F.GOLDEN, "text", "CanopyHydrology_IN.txt.gz"), "rb") as src, open(p, "wb") as dst:
+        shutil.copyfileobj(src, dst)
+    inp = TI.ELMtestinput(str(p))
     d = F.load("CanopyHydrology")
     steps = [int(s) for s in d["steps"]]
     assert inp.steps() == steps
