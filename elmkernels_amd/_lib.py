@@ -73,6 +73,10 @@ SIGNATURES = {
     "elmk_copy_bandwidth": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
     "elmk_copy_bandwidth_shape": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "elmk_math_eval": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64]),
+    "elmk_set_column_geography": (C.c_int, [_P, _P, _P]),
+    "elmk_solar_geometry": (C.c_int, [_P, C.c_double, C.c_double, C.c_int]),
+    "elmk_download_day_length": (C.c_int, [_P, _P, _P]),
+    "elmk_clear_column_geography": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

@@ -91,6 +91,10 @@ struct elmk_ctx {
   bool lists_stale = false;
   char* counters_raw = nullptr;
   size_t counters_bytes = 0;
+  // per-column solar geometry: DevState::geo and DevState::col_dayl in one allocation (elmk_set_column_geography); the mode flag
+  // itself is side.col_dayl (elmk_solar_geometry sets it, elmk_clear_column_geography clears it)
+  double* geo = nullptr;
+  bool geo_set = false;
   std::string err;
 };
 
@@ -321,6 +325,7 @@ int elmk_destroy(elmk_ctx* ctx)
   if (ctx->snowage) (void)hipFree(ctx->snowage);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->d) (void)hipFree(ctx->d);
+  if (ctx->geo) (void)hipFree(ctx->geo);
   for (GraphSlot& g : ctx->graph)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (ctx->red_or) (void)hipFree(ctx->red_or);
@@ -363,6 +368,19 @@ int elmk_set_graph(elmk_ctx* ctx, int on)
   return ELMK_OK;
 }
 
+namespace {
+// a captured graph holds the launch shape and the kernels of the moment it was captured (elmk_set_option, the day-length mode)
+int drop_graphs(elmk_ctx* ctx)
+{
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (GraphSlot& g : ctx->graph) {
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    g.exec = nullptr;
+  }
+  return ELMK_OK;
+}
+}  // namespace
+
 int elmk_set_option(elmk_ctx* ctx, int option, int value)
 {
   if (int rc = enter(ctx)) return rc;
@@ -371,12 +389,7 @@ int elmk_set_option(elmk_ctx* ctx, int option, int value)
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->dev));
   const int want = value ? (cus > 0 ? cus : 256) : 0;
   if (want != ctx->side.cf_half_groups) {
-    // a captured graph holds the old launch shape
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (GraphSlot& g : ctx->graph) {
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
-      g.exec = nullptr;
-    }
+    if (int rc = drop_graphs(ctx)) return rc;
     ctx->side.cf_half_groups = want;
   }
   return ELMK_OK;
@@ -618,6 +631,90 @@ int elmk_set_scalars(elmk_ctx* ctx, double dewmx, int oldfflag, double dayl, dou
   ctx->h.dayl = dayl;
   ctx->h.max_dayl = max_dayl;
   ctx->dirty = true;
+  return ELMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// per-column solar geometry (elmk_solar.h, k_solar.hip)
+// ---------------------------------------------------------------------------------------------------
+int elmk_set_column_geography(elmk_ctx* ctx, const double* lat_r, const double* lon_r)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!lat_r || !lon_r) return invalid(ctx, "elmk_set_column_geography: null pointer");
+  const int64_t ld = ctx->ld;
+  // the time-invariant terms of every column, with the host libm (the reference's bits by construction)
+  std::vector<double> g((size_t)ELMK_GEO_N * (size_t)ld, 0.0);
+  for (int64_t c = 0; c < ctx->ncols; c++) {
+    if (!elmk_solar_geography_ok(lat_r[c], lon_r[c])) {
+      char buf[200];
+      snprintf(buf, sizeof buf, "elmk_set_column_geography: column %lld: lat %g / lon %g (need |lat| <= pi/2 + 10 eps, finite lon)",
+               (long long)c, lat_r[c], lon_r[c]);
+      return invalid(ctx, buf);
+    }
+    double row[ELMK_GEO_N];
+    elmk_solar_column_consts(lat_r[c], lon_r[c], row);
+    for (int k = 0; k < ELMK_GEO_N; k++) g[(size_t)k * ld + c] = row[k];
+  }
+  if (!ctx->geo) {
+    const size_t bytes = (size_t)(ELMK_GEO_N + COL_DAYL_N) * (size_t)ld * 8;
+    HIPCHK(hipMalloc((void**)&ctx->geo, bytes));
+    HIPCHK(hipMemsetAsync(ctx->geo, 0, bytes, ctx->stream));
+    ctx->h.geo = (gptr<const double>)ctx->geo;
+    ctx->h.col_dayl = (gptr<double>)(ctx->geo + (size_t)ELMK_GEO_N * ld);
+    ctx->dirty = true;
+  }
+  HIPCHK(hipMemcpyAsync(ctx->geo, g.data(), g.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // (g goes out of scope)
+  ctx->geo_set = true;
+  return ELMK_OK;
+}
+
+int elmk_solar_geometry(elmk_ctx* ctx, double dt_seconds, double decday, int doy)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->geo_set) return invalid(ctx, "elmk_solar_geometry: no column geography (elmk_set_column_geography)");
+  if (!(dt_seconds > 0.0 && dt_seconds <= 1.0e9) || !(decday >= 0.0 && decday < 1.0e9) || doy < -1 || doy > 1000000000)
+    return invalid(ctx, "elmk_solar_geometry: bad dt / decday / doy");
+  if (!ctx->side.col_dayl) {  // canopy_fluxes switches to the per-column kernels: graphs captured so far hold the scalar ones
+    if (int rc = drop_graphs(ctx)) return rc;
+    ctx->side.col_dayl = true;
+  }
+  if (int rc = push_params(ctx)) return rc;
+  launch_solar_geometry(ctx->d, ctx->ncols, elmk_solar_step_consts(dt_seconds, decday, doy), ctx->stream);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_download_day_length(elmk_ctx* ctx, double* dayl, double* max_dayl)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->side.col_dayl) return invalid(ctx, "elmk_download_day_length: no elmk_solar_geometry since the geography was set");
+  const size_t bytes = (size_t)ctx->ncols * 8;
+  if (dayl && bytes)
+    HIPCHK(hipMemcpyAsync(dayl, ctx->geo + (size_t)(ELMK_GEO_N + COL_DAYL) * ctx->ld, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (max_dayl && bytes)
+    HIPCHK(hipMemcpyAsync(max_dayl, ctx->geo + (size_t)ELMK_GEO_MAX_DAYL * ctx->ld, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+int elmk_clear_column_geography(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (ctx->side.col_dayl) {
+    if (int rc = drop_graphs(ctx)) return rc;
+    ctx->side.col_dayl = false;
+  }
+  if (ctx->geo) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const hipError_t e = hipFree(ctx->geo);
+    ctx->geo = nullptr;
+    ctx->h.geo = nullptr;
+    ctx->h.col_dayl = nullptr;
+    ctx->dirty = true;
+    HIPCHK(e);
+  }
+  ctx->geo_set = false;
   return ELMK_OK;
 }
 
@@ -1230,14 +1327,15 @@ int elmk_copy_bandwidth_shape(elmk_ctx* ctx, int64_t bytes, int iters, int shape
 int elmk_math_eval(elmk_ctx* ctx, int fn, const double* x, const double* y, double* out, int64_t n)
 {
   if (int rc = enter(ctx)) return rc;
-  if (fn < ELMK_MATH_EXP || fn > ELMK_MATH_POW || !x || !out || n < 0 || (fn >= ELMK_MATH_DIV && !y))
+  const bool binary = fn == ELMK_MATH_DIV || fn == ELMK_MATH_POW;
+  if (fn < ELMK_MATH_EXP || fn > ELMK_MATH_SIN || !x || !out || n < 0 || (binary && !y))
     return invalid(ctx, "elmk_math_eval: bad arguments");
   if (n == 0) return ELMK_OK;
   double* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, (size_t)n * 8 * 3));
   int rc = ELMK_OK;
   if (hip_fail(ctx, hipMemcpyAsync(d, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync")) rc = ELMK_E_HIP;
-  if (!rc && fn >= ELMK_MATH_DIV &&
+  if (!rc && binary &&
       hip_fail(ctx, hipMemcpyAsync(d + n, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))
     rc = ELMK_E_HIP;
   if (!rc) {

@@ -291,7 +291,13 @@ struct DevState {
   // cold-start initialisation (k_init_state.hip): organic_max of the parameter file, PFTData::roota_par / rootb_par
   double organic_max;
   double roota_par[ELMK_MXPFT], rootb_par[ELMK_MXPFT];
+  // per-column solar geometry (elmk_set_column_geography / elmk_solar_geometry, k_solar.hip); null until a geography is set
+  gptr<const double> geo;  // ELMK_GEO_N x ld: the time-invariant terms of each column (elmk_solar.h)
+  gptr<double> col_dayl;   // COL_DAYL_N x ld (below)
 };
+// rows of DevState::col_dayl: what the last elmk_solar_geometry left per column, and the leaf-nitrogen term of canopy_fluxes in
+// per-column mode by queue position (k_cf_dayl -> k_cf_iterate<true>)
+enum : int { COL_DAYL = 0, COL_DAYL_FACTOR, COL_CF_VCMAX25TOP, COL_DAYL_N };
 
 // std::min / std::max of the reference (<algorithm>): first argument wins ties and NaNs
 __device__ __forceinline__ double dmin(double a, double b) { return (b < a) ? b : a; }

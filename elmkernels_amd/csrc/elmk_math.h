@@ -933,10 +933,32 @@ ELMK_MFN double elmk_sc_do_sin(double x, double dx)
   cor = ELMK_FMA(s, cs, cor);
   return elmk_atan_signed(sn + cor, xold);  // copysign
 }
+// reduce_sincos (|x| < 105414350): x = n * pi/2 + (b + db), returns n & 3 (the quadrant)
+ELMK_MFN int elmk_sc_reduce(double x, double* b_out, double* db_out)
+{
+  const double hpinv = 0x1.45f306dc9c883p-1, toint = 0x1.8p+52, mp1 = 0x1.921fb58p+0, mp2 = -0x1.dde973cp-27,
+               pp3 = -0x1.cb3b398p-55, pp4 = -0x1.d747f23e32ed7p-83;
+  const double t = ELMK_FMA(x, hpinv, toint);
+  const double xn = t - toint;
+  double y = ELMK_FMA(-xn, mp1, x);
+  y = ELMK_FMA(-xn, mp2, y);
+  const double t2 = ELMK_FMA(-xn, pp3, y);
+  double db = ELMK_FMA(-pp3, xn, y - t2);
+  const double b = ELMK_FMA(-xn, pp4, t2);
+  db = db + ELMK_FMA(-xn, pp4, t2 - b);
+  *b_out = b;
+  *db_out = db;
+  return (int)(uint32_t)elmk_asu64(t) & 3;
+}
+// do_sincos
+ELMK_MFN double elmk_sc_do_sincos(double b, double db, int n)
+{
+  const double r = (n & 1) ? elmk_sc_do_cos(b, db) : elmk_sc_do_sin(b, db);
+  return (n & 2) ? -r : r;
+}
 ELMK_MFN double elmk_cos(double x)
 {
-  const double hp0 = 0x1.921fb54442d18p+0, hp1 = 0x1.1a62633145c07p-54, hpinv = 0x1.45f306dc9c883p-1, toint = 0x1.8p+52,
-               mp1 = 0x1.921fb58p+0, mp2 = -0x1.dde973cp-27, pp3 = -0x1.cb3b398p-55, pp4 = -0x1.d747f23e32ed7p-83;
+  const double hp0 = 0x1.921fb54442d18p+0, hp1 = 0x1.1a62633145c07p-54;
   const uint32_t k = (uint32_t)(elmk_asu64(x) >> 32) & 0x7fffffffu;
   if (k < 0x3e400000u) return 1.0;                      // |x| < 2^-27
   if (k < 0x3feb6000u) return elmk_sc_do_cos(x, 0.0);  // |x| < 0.855469
@@ -947,17 +969,29 @@ ELMK_MFN double elmk_cos(double x)
     return elmk_sc_do_sin(a, da);
   }
   if (k < 0x419921FBu) {  // |x| < 105414350: reduce_sincos, then do_sincos(a, da, n + 1)
-    const double t = ELMK_FMA(x, hpinv, toint);
-    const double xn = t - toint;
-    const int n = ((int)(uint32_t)elmk_asu64(t) & 3) + 1;
-    double y = ELMK_FMA(-xn, mp1, x);
-    y = ELMK_FMA(-xn, mp2, y);
-    const double t2 = ELMK_FMA(-xn, pp3, y);
-    double db = ELMK_FMA(-pp3, xn, y - t2);
-    const double b = ELMK_FMA(-xn, pp4, t2);
-    db = db + ELMK_FMA(-xn, pp4, t2 - b);
-    const double r = (n & 1) ? elmk_sc_do_cos(b, db) : elmk_sc_do_sin(b, db);
-    return (n & 2) ? -r : r;
+    double b, db;
+    const int n = elmk_sc_reduce(x, &b, &db) + 1;
+    return elmk_sc_do_sincos(b, db, n);
+  }
+  if (k < 0x7ff00000u) return ELMK_NAN;  // outside the restated range (see above)
+  return x / x;                          // inf, nan
+}
+// ---- sin: glibc 2.35 s_sin.c (__sin_fma), the same ranges and the same restated range as cos.  The physics takes it of hour
+// angles (incident_shortwave.cc:113-114, |x| <= 3 pi; k_solar.hip) -----------------------------------------------------------
+ELMK_MFN double elmk_sin(double x)
+{
+  const double hp0 = 0x1.921fb54442d18p+0, hp1 = 0x1.1a62633145c07p-54;
+  const uint32_t k = (uint32_t)(elmk_asu64(x) >> 32) & 0x7fffffffu;
+  if (k < 0x3e500000u) return x;                        // |x| < 2^-26
+  if (k < 0x3feb6000u) return elmk_sc_do_sin(x, 0.0);  // |x| < 0.855469
+  if (k < 0x400368fdu) {                                // |x| < 2.426265: copysign(do_cos(hp0 - |x|, hp1), x)
+    const double t = hp0 - __builtin_fabs(x);
+    return elmk_atan_signed(elmk_sc_do_cos(t, hp1), x);
+  }
+  if (k < 0x419921FBu) {  // |x| < 105414350: reduce_sincos, then do_sincos(a, da, n)
+    double b, db;
+    const int n = elmk_sc_reduce(x, &b, &db);
+    return elmk_sc_do_sincos(b, db, n);
   }
   if (k < 0x7ff00000u) return ELMK_NAN;  // outside the restated range (see above)
   return x / x;                          // inf, nan

@@ -77,6 +77,14 @@ enum : int {
   PFT_N,
   PFT_STRIDE = PFT_N + 1  // odd: rows of different plant types start in different LDS banks
 };
+// vcmax25top (:28-44) is lnc * flnr * fnr * act25 * dayl_factor, then * fnitr: this is the product up to the day-length factor, the
+// part that depends on the plant type alone (in per-column mode, k_cf_dayl completes it per column)
+__device__ __forceinline__ double cf_vcmax25_base(const double* __restrict__ P)
+{
+  const double lnc = 1.0 / (P[P_slatop] * P[P_leafcn]);
+  const double act25 = P[P_act25] * 1000.0 / 60.0;
+  return lnc * P[P_flnr] * P[P_fnr] * act25;
+}
 __device__ __forceinline__ void cf_pft_row(const DevState* __restrict__ S, int v, double* __restrict__ row)
 {
   const double* __restrict__ P = S->pft_psn[v];
@@ -98,12 +106,10 @@ __device__ __forceinline__ void cf_pft_row(const DevState* __restrict__ S, int v
   row[PFT_bbbopt] = P[P_bbbopt];
   row[PFT_mbbopt] = P[P_mbbopt];
   row[PFT_c3] = (round(P[P_c3psn]) == 1) ? 1.0 : 0.0;
-  // vcmax25top (:28-44): leaf nitrogen, the day-length factor and the nitrogen limitation
+  // vcmax25top (:28-44): leaf nitrogen, the day-length factor and the nitrogen limitation (scalar mode: the context's dayl / max_dayl)
   const double dl = S->dayl, mdl = S->max_dayl;
   const double dayl_factor = dmin(1.0, dmax(0.01, (dl * dl) / (mdl * mdl)));
-  const double lnc = 1.0 / (P[P_slatop] * P[P_leafcn]);
-  const double act25 = P[P_act25] * 1000.0 / 60.0;
-  double vcmax25top = lnc * P[P_flnr] * P[P_fnr] * act25 * dayl_factor;
+  double vcmax25top = cf_vcmax25_base(P) * dayl_factor;
   vcmax25top *= P[P_fnitr];
   row[PFT_vcmax25top] = vcmax25top;
   row[PFT_lmrc] = psn_fth25(P[P_lmrhd], P[P_lmrse]);
@@ -1026,8 +1032,9 @@ CF_LDS_FIELDS(X)
 #define C(n) cf_get_##n(R, s_col, tid)
 #define CSET(n, v) cf_set_##n(R, s_col, tid, (v))
 
-// (the body as a template over the workgroup size: the per-lane LDS slots are [field][thread of the workgroup])
-template <int THREADS>
+// (the body as a template over the workgroup size: the per-lane LDS slots are [field][thread of the workgroup]; COL_DAYL_MODE: per-column
+// day length - vcmax25top of the column comes from k_cf_dayl, by queue position, instead of from the plant type's row)
+template <int THREADS, bool COL_DAYL_MODE>
 __device__ __forceinline__ void cf_iterate_body(const DevState* __restrict__ S, double dtime, const int given)
 {
   elmk_math_lds_init<true>();
@@ -1275,8 +1282,9 @@ __device__ __forceinline__ void cf_iterate_body(const DevState* __restrict__ S, 
                                      (404.9 / 1.e06) * C(forc_pbot), (278.4 / 1.e03) * C(forc_pbot), C(cp25), t_veg, day);
           PsnCol I;
           I.c3flag = c3flag;
-          I.vcmax25top = PR[PFT_vcmax25top];
-          I.jmax25top = (2.59 - 0.035 * tc) * PR[PFT_vcmax25top];
+          const double vcmax25top = COL_DAYL_MODE ? S->col_dayl[(int64_t)COL_CF_VCMAX25TOP * ld + pos] : PR[PFT_vcmax25top];
+          I.vcmax25top = vcmax25top;
+          I.jmax25top = (2.59 - 0.035 * tc) * vcmax25top;
           I.cf = 0.0;  // (not read by psn_phase_inputs)
           I.qe = I.theta_cj = I.bbbopt = I.mbbopt = 0.0;
           // the soybean adjustment of btran runs once in front of each phase (:282-292), so the shaded phase sees it twice
@@ -1600,7 +1608,7 @@ __device__ __forceinline__ void cf_iterate_body(const DevState* __restrict__ S, 
 #undef CSET
 __global__ __launch_bounds__(CF_ITER_THREADS, 2) void k_cf_iterate(const DevState* __restrict__ S, double dtime, const int given)
 {
-  cf_iterate_body<CF_ITER_THREADS>(S, dtime, given);
+  cf_iterate_body<CF_ITER_THREADS, false>(S, dtime, given);
 }
 // The same iteration in 256-thread workgroups: one wave per SIMD and 92 KB of LDS, one workgroup per CU - slower on its own (the
 // second wave per SIMD is what fills the fp64 pipe, 1.29 against 0.87 ms per million columns) but it leaves half the register file
@@ -1609,7 +1617,31 @@ __global__ __launch_bounds__(CF_ITER_THREADS, 2) void k_cf_iterate(const DevStat
 // profiles/r04_two_block_overlap.txt).
 __global__ __launch_bounds__(CF_ITER_THREADS_HALF, 2) void k_cf_iterate_half(const DevState* __restrict__ S, double dtime, const int given)
 {
-  cf_iterate_body<CF_ITER_THREADS_HALF>(S, dtime, given);
+  cf_iterate_body<CF_ITER_THREADS_HALF, false>(S, dtime, given);
+}
+// Per-column day length (elmk_solar_geometry until elmk_clear_column_geography): the same two launch shapes as separate kernels, so
+// that the scalar-mode kernels above stay exactly what they were.  k_cf_dayl runs in front of them: for every queued column
+// (vcmax25 base of its plant type * its dayl_factor) * fnitr, the reference's product split where the row ends
+// (photosynthesis_impl.hh:41-44), stored by queue position.
+__global__ __launch_bounds__(256) void k_cf_dayl(const DevState* __restrict__ S)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (S->land.lakpoi || c >= S->ncols) return;
+  const int32_t pos = S->cf_pos[c];
+  if (pos < 0) return;
+  const int64_t ld = S->ld;
+  const double* __restrict__ P = S->pft_psn[S->vtype[c]];
+  double vcmax25top = cf_vcmax25_base(P) * S->col_dayl[(int64_t)COL_DAYL_FACTOR * ld + c];
+  vcmax25top *= P[P_fnitr];
+  S->col_dayl[(int64_t)COL_CF_VCMAX25TOP * ld + pos] = vcmax25top;
+}
+__global__ __launch_bounds__(CF_ITER_THREADS, 2) void k_cf_iterate_col_dayl(const DevState* __restrict__ S, double dtime, const int given)
+{
+  cf_iterate_body<CF_ITER_THREADS, true>(S, dtime, given);
+}
+__global__ __launch_bounds__(CF_ITER_THREADS_HALF, 2) void k_cf_iterate_half_col_dayl(const DevState* __restrict__ S, double dtime, const int given)
+{
+  cf_iterate_body<CF_ITER_THREADS_HALF, true>(S, dtime, given);
 }
 
 // =====================================================================================================
@@ -1976,12 +2008,14 @@ static unsigned cf_iterate_groups(unsigned nblk)
 
 static void launch_cf_iterate(const DevState* S, unsigned nblk, double dt, hipStream_t st, const SideStreams* side, int given)
 {
+  const bool col_dayl = side && side->col_dayl;
+  if (col_dayl) hipLaunchKernelGGL(k_cf_dayl, dim3(nblk), dim3(256), 0, st, S);
   if (side && side->cf_half_groups > 0) {  // (one workgroup per CU and no more: what is launched is resident)
     const unsigned g = nblk * 256u / CF_ITER_THREADS_HALF < (unsigned)side->cf_half_groups ? nblk * 256u / CF_ITER_THREADS_HALF : (unsigned)side->cf_half_groups;
-    hipLaunchKernelGGL(k_cf_iterate_half, dim3(g ? g : 1u), dim3(CF_ITER_THREADS_HALF), 0, st, S, dt, given);
+    hipLaunchKernelGGL(col_dayl ? k_cf_iterate_half_col_dayl : k_cf_iterate_half, dim3(g ? g : 1u), dim3(CF_ITER_THREADS_HALF), 0, st, S, dt, given);
     return;
   }
-  hipLaunchKernelGGL(k_cf_iterate, dim3(cf_iterate_groups(nblk)), dim3(CF_ITER_THREADS), 0, st, S, dt, given);
+  hipLaunchKernelGGL(col_dayl ? k_cf_iterate_col_dayl : k_cf_iterate, dim3(cf_iterate_groups(nblk)), dim3(CF_ITER_THREADS), 0, st, S, dt, given);
 }
 
 void launch_fused_stage(const DevState* S, int64_t n, double dt, hipStream_t st, const SideStreams* side, int stage)

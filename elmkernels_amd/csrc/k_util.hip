@@ -304,6 +304,7 @@ __global__ __launch_bounds__(256) void k_math_eval(int fn, const double* __restr
     case ELMK_MATH_ACOS: r = elmk_acos(a); break;
     case ELMK_MATH_EXPM1: r = elmk_expm1(a); break;
     case ELMK_MATH_DIV: r = a / y[i]; break;
+    case ELMK_MATH_SIN: r = elmk_sin(a); break;
     default: r = elmk_pow(a, y[i]); break;
   }
   out[i] = r;

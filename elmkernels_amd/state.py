@@ -272,6 +272,32 @@ class ELMState:
         return g.value
 
 
+    # -- per-column solar geometry (include/elmk.h: elmk_set_column_geography ...) -------------------
+    def set_column_geography(self, lat, lon):
+        """Latitude and longitude of every column, radians ([ncols] each; |lat| <= pi/2 + 10 eps).  Changes nothing until
+        solar_geometry() runs."""
+        lat = np.ascontiguousarray(lat, dtype=np.float64).reshape(-1)
+        lon = np.ascontiguousarray(lon, dtype=np.float64).reshape(-1)
+        assert lat.size == self.ncols and lon.size == self.ncols
+        self._chk(self.lib.elmk_set_column_geography(self.ctx, lat.ctypes.data_as(C.c_void_p), lon.ctypes.data_as(C.c_void_p)),
+                  "set_column_geography")
+
+    def solar_geometry(self, dt, decday, doy):
+        """kokkos_init_timestep's solar lines for every column at its own location: coszen, and per-column day length for
+        canopy_fluxes from now on (decday = decimal_doy(date) + 1.0, doy = date.doy)."""
+        self._chk(self.lib.elmk_solar_geometry(self.ctx, float(dt), float(decday), int(doy)), "solar_geometry")
+
+    def day_length(self):
+        """(dayl, max_dayl) of every column from the last solar_geometry()."""
+        dayl, max_dayl = np.empty(self.ncols), np.empty(self.ncols)
+        self._chk(self.lib.elmk_download_day_length(self.ctx, dayl.ctypes.data_as(C.c_void_p), max_dayl.ctypes.data_as(C.c_void_p)),
+                  "day_length")
+        return dayl, max_dayl
+
+    def clear_column_geography(self):
+        """Back to one day length for all columns (set_scalars' dayl / max_dayl)."""
+        self._chk(self.lib.elmk_clear_column_geography(self.ctx), "clear_column_geography")
+
     def math_eval(self, fn, x, y=None):
         """elmk_math.h on the device: fn in MATH_FNS; returns fn(x), x / y or pow(x, y)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -286,7 +312,7 @@ class ELMState:
         return out
 
 
-MATH_FNS = ["exp", "log", "log10", "atan", "sqrt", "tanh", "cos", "erf", "acos", "expm1", "div", "pow"]
+MATH_FNS = ["exp", "log", "log10", "atan", "sqrt", "tanh", "cos", "erf", "acos", "expm1", "div", "pow", "sin"]
 WRAPPER_NAMES = ["frac_wet", "albedo_snicar", "canopy_hydrology", "surface_radiation", "canopy_temperature",
                  "bareground_fluxes", "canopy_fluxes", "soil_temperature", "surface_fluxes", "snow_hydrology", "advance_physics"]
 KERNEL_NAMES = [

@@ -351,3 +351,16 @@ def forcing_streams(cols, seed):
     out["mhtop"] = two(top, 0.05)
     out["mhbot"] = two(0.1 * top, 0.05)
     return out
+
+
+def global_grid(n, seed=0x6E0):
+    """Latitudes and longitudes (radians) of n columns spread over the globe, for per-column solar geometry
+    (elmk_set_column_geography): both hemispheres, both poles, the equator and the dateline among them, the rest uniform
+    in sin(latitude) (equal area) and in longitude on [-pi, pi).  Returns (lat_r, lon_r), float64 [n] each."""
+    rng = np.random.default_rng(seed)
+    lat = np.arcsin(2.0 * rng.random(n) - 1.0)
+    lon = (rng.random(n) - 0.5) * 2.0 * np.pi
+    fixed = [(np.pi / 2, 0.0), (-np.pi / 2, 0.0), (0.0, 0.0), (0.0, np.pi), (0.0, -np.pi), (1.2, np.pi), (-1.2, -np.pi)]
+    for i, (a, b) in enumerate(fixed[: min(n, len(fixed))]):
+        lat[i], lon[i] = a, b
+    return lat, lon

@@ -15,6 +15,8 @@
  *                                                                     elmk_device_ptr  (ids: elmk_fields.def)
  *   S.Land                          src/data/land_data.h:36-44        elmk_set_land
  *   S.dewmx/oldfflag/dayl/max_dayl  src/data/elm_state.h:221-224      elmk_set_scalars
+ *   kokkos_init_timestep's coszen / dayl / max_dayl (per column)
+ *                                   init_timestep_kokkos.cc:26-34     elmk_set_column_geography, elmk_solar_geometry
  *   S.pft_data (PFTData)            src/data/pft_data.h:20-31,35-90   elmk_set_pft
  *   S.albsat / S.albdry             src/data/elm_state.h:82           elmk_set_soilcolor
  *   S.snicar_data (SnicarData)      src/data/snicar_data.h:29-71      elmk_set_snicar
@@ -213,6 +215,32 @@ int elmk_set_snicar(elmk_ctx *ctx, const elmk_snicar_tables *t);
  * snowage_drdt0 [um/hour], each [11][31][8] = [temperature][temperature gradient][density] index, row-major */
 int elmk_set_snow_age_tables(elmk_ctx *ctx, const double *tau, const double *kappa, const double *drdt0);
 
+/* ---- per-column solar geometry ----------------------------------------------------------------
+ * kokkos_init_timestep computes ONE step-averaged cos(zenith), day length and maximum day length for the whole domain on the
+ * host, at S.lat_r / S.lon_r (init_timestep_kokkos.cc:26-34: "only one value currently"), and elmk_interface.hpp's
+ * ELMInterface::set_solar_geometry does the same.  These entries do it for every column at its own location, on the device, with
+ * the reference's bits for that column:
+ *   elmk_set_column_geography  lat_r, lon_r: [ncols] radians, |lat_r| <= pi/2 + 10 eps (day_length.cc:22), finite lon_r; copied,
+ *                              not retained.  The time-invariant terms (tan / sin / cos of the latitude, max_daylength) are
+ *                              computed here once, with the host libm.  Setting a geography alone changes nothing.
+ *   elmk_solar_geometry        for every column c: coszen[c] = average_cosz(lat_c, lon_c, dt, decday), the day length
+ *                              daylength(lat_c, declination_angle_sin(doy + 1)) and max_daylength(lat_c) - decday =
+ *                              decimal_doy(date) + 1.0 and doy = date.doy, the arguments ELMInterface::set_solar_geometry takes.
+ *                              Enqueued on the context's stream.  From the first call on, the context is in per-column mode:
+ *                              canopy_fluxes (every path to it - elmk_canopy_fluxes, _given, elmk_timestep7(_fused),
+ *                              elmk_advance_physics, their graphs, ELMK_OPT_CF_HALF_WORKGROUPS) takes the day-length factor of
+ *                              photosynthesis from each column's own dayl / max_dayl instead of elmk_set_scalars' two scalars;
+ *                              a column gives the bits a scalar-mode context with elmk_set_scalars(dayl_c, max_dayl_c) gives.
+ *                              ELMK_E_INVALID without a geography.
+ *   elmk_download_day_length   [ncols] each (either may be NULL) of the last elmk_solar_geometry; synchronises.
+ *   elmk_clear_column_geography  back to scalar mode (elmk_set_scalars' dayl / max_dayl); the geography is forgotten, coszen keeps
+ *                              its values.
+ * A multi-rank driver passes each rank its own slice of the grid (elmkernels_amd/decomp.py). */
+int elmk_set_column_geography(elmk_ctx *ctx, const double *lat_r, const double *lon_r);
+int elmk_solar_geometry(elmk_ctx *ctx, double dt_seconds, double decday, int doy);
+int elmk_download_day_length(elmk_ctx *ctx, double *dayl, double *max_dayl);
+int elmk_clear_column_geography(elmk_ctx *ctx);
+
 /* ---- the physics wrappers (same names, order and arguments as driver/kokkos) ---------------- */
 int elmk_frac_wet(elmk_ctx *ctx);
 int elmk_albedo_snicar(elmk_ctx *ctx);
@@ -345,12 +373,13 @@ int elmk_copy_bandwidth(elmk_ctx *ctx, int64_t bytes, int iters, double *gbytes_
  * and shape 4 as the line of a many-field streaming kernel. */
 int elmk_copy_bandwidth_shape(elmk_ctx *ctx, int64_t bytes, int iters, int shape, double *gbytes_per_s);
 /* Evaluate one function of elmkernels_amd/csrc/elmk_math.h - the device restatement of the host libm's exp / log / log10 /
- * pow / atan / tanh / cos / erf / acos / expm1 (the <cmath> calls of src/physics headers) - on n host values: out[i] = fn(x[i]) or pow(x[i], y[i]).
+ * pow / atan / tanh / cos / erf / acos / expm1 / sin (the <cmath> calls of src/physics headers and of incident_shortwave.cc) - on n host values: out[i] = fn(x[i]) or pow(x[i], y[i]).
  * ELMK_MATH_SQRT and ELMK_MATH_DIV (x[i] / y[i]) are the device's own IEEE operations, included so that the tests can
  * confirm they round correctly.  y is read only for ELMK_MATH_POW / ELMK_MATH_DIV.  Used by the parity tests to compare the device bits with the host libm's. */
 typedef enum {
   ELMK_MATH_EXP = 0, ELMK_MATH_LOG, ELMK_MATH_LOG10, ELMK_MATH_ATAN, ELMK_MATH_SQRT, ELMK_MATH_TANH, ELMK_MATH_COS, ELMK_MATH_ERF,
-  ELMK_MATH_ACOS, ELMK_MATH_EXPM1, ELMK_MATH_DIV, ELMK_MATH_POW
+  ELMK_MATH_ACOS, ELMK_MATH_EXPM1, ELMK_MATH_DIV, ELMK_MATH_POW,
+  ELMK_MATH_SIN /* (appended: the ids above do not move) */
 } elmk_math_fn;
 int elmk_math_eval(elmk_ctx *ctx, int fn, const double *x, const double *y, double *out, int64_t n);
 

@@ -193,6 +193,22 @@ class ELMInterface {
                         solar::max_daylength(lat_r)));
   }
 
+  /* A domain whose columns do not share one sun (a regional or global grid): the latitude and longitude of every column, radians
+   * ([ncols] each), once.  From then on solar_geometry() - or the advance() overload below - does kokkos_init_timestep's solar
+   * lines for each column at its own location, on the device, and canopy_fluxes takes each column's own day length.
+   * clear_column_geography() goes back to set_solar_geometry's single location. */
+  void set_column_geography(const double* lat_r, const double* lon_r) { ok(elmk_set_column_geography(ctx_, lat_r, lon_r)); }
+  void solar_geometry(double dt_seconds, double decday, int doy) { ok(elmk_solar_geometry(ctx_, dt_seconds, decday, doy)); }
+  void clear_column_geography() { ok(elmk_clear_column_geography(ctx_)); }
+  /* advance() for a grid with a geography: the solar lines first, then phenology and forcing (coszen feeds get_forcing's
+   * direct / diffuse split, atm_physics_impl.hh), in kokkos_init_timestep's order (init_timestep_kokkos.cc:26-50).
+   * decday = Utils::decimal_doy(date) + 1.0, doy = date.doy of the step's start. */
+  bool advance(double dt_seconds, const StepWeights& w, double decday, int doy)
+  {
+    solar_geometry(dt_seconds, decday, doy);
+    return advance(dt_seconds, w);
+  }
+
   /* ELMInterface::copyPrimaryVars / getPrimaryVars (elm_kokkos_interface.cc:324-356) */
   void copyPrimaryVars(PrimaryVars& pv)
   {
