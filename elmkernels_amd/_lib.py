@@ -77,6 +77,12 @@ SIGNATURES = {
     "elmk_solar_geometry": (C.c_int, [_P, C.c_double, C.c_double, C.c_int]),
     "elmk_download_day_length": (C.c_int, [_P, _P, _P]),
     "elmk_clear_column_geography": (C.c_int, [_P]),
+    "elmk_history_add": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "elmk_history_accumulate": (C.c_int, [_P]),
+    "elmk_history_reset": (C.c_int, [_P, C.c_int]),
+    "elmk_history_count": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
+    "elmk_history_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int]),
+    "elmk_history_clear": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

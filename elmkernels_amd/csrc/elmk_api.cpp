@@ -95,6 +95,16 @@ struct elmk_ctx {
   // itself is side.col_dayl (elmk_solar_geometry sets it, elmk_clear_column_geography clears it)
   double* geo = nullptr;
   bool geo_set = false;
+  // history (elmk_history_*): the entries, their rows as the device table k_hist_accumulate reads (hist_table: the rows, then one
+  // count per tape), and per tape whether it has accumulated since its last reset (elmk_history_add refuses such a tape)
+  struct HistEntry {
+    int tape, field, op, nlev, row0;
+    double* acc;
+  };
+  std::vector<HistEntry> hist;
+  std::vector<HistRow> hist_rows;
+  char* hist_table = nullptr;
+  bool hist_dirty[ELMK_HIST_MAX_TAPES] = {};
   std::string err;
 };
 
@@ -326,6 +336,8 @@ int elmk_destroy(elmk_ctx* ctx)
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->d) (void)hipFree(ctx->d);
   if (ctx->geo) (void)hipFree(ctx->geo);
+  for (const elmk_ctx::HistEntry& e : ctx->hist) (void)hipFree(e.acc);
+  if (ctx->hist_table) (void)hipFree(ctx->hist_table);
   for (GraphSlot& g : ctx->graph)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (ctx->red_or) (void)hipFree(ctx->red_or);
@@ -793,6 +805,149 @@ int elmk_set_snow_age_tables(elmk_ctx* ctx, const double* tau, const double* kap
   for (int k = 0; k < 3; k++)
     HIPCHK(hipMemcpyAsync(ctx->snowage + (size_t)k * ELMK_SNOWAGE_N, src[k], ELMK_SNOWAGE_N * sizeof(double), hipMemcpyHostToDevice,
                           ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// history (k_history.hip)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+constexpr int HIST_MAX_ROWS = ELMK_HIST_MAX_ENTRIES * MAXLEV_STAGE;
+constexpr size_t HIST_COUNTS_OFF = ((size_t)HIST_MAX_ROWS * sizeof(HistRow) + 255) / 256 * 256;
+
+unsigned long long* hist_counts(elmk_ctx* ctx) { return (unsigned long long*)(ctx->hist_table + HIST_COUNTS_OFF); }
+
+unsigned hist_tape_mask(const elmk_ctx* ctx)
+{
+  unsigned m = 0;
+  for (const elmk_ctx::HistEntry& e : ctx->hist) m |= 1u << e.tape;
+  return m;
+}
+
+bool tape_ok(int tape) { return tape >= 0 && tape < ELMK_HIST_MAX_TAPES; }
+}  // namespace
+
+int elmk_history_add(elmk_ctx* ctx, int tape, int field, int op)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!tape_ok(tape)) return invalid(ctx, "elmk_history_add: unknown tape");
+  if (!field_ok(field)) return invalid(ctx, "elmk_history_add: unknown field");
+  if (op < ELMK_HIST_AVG || op > ELMK_HIST_INST) return invalid(ctx, "elmk_history_add: unknown op");
+  if ((int)ctx->hist.size() >= ELMK_HIST_MAX_ENTRIES) return invalid(ctx, "elmk_history_add: the history table is full");
+  if (ctx->hist_dirty[tape]) return invalid(ctx, "elmk_history_add: the tape holds samples; reset it first");
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIPCHK(hipStreamIsCapturing(ctx->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone) return invalid(ctx, "elmk_history_add: the stream is being captured");
+  if (!ctx->hist_table) {
+    HIPCHK(hipMalloc((void**)&ctx->hist_table, HIST_COUNTS_OFF + ELMK_HIST_MAX_TAPES * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(ctx->hist_table, 0, HIST_COUNTS_OFF + ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
+  }
+  const int nlev = g_fields[field].nlev;
+  double* acc = nullptr;
+  if (hip_fail(ctx, hipMalloc((void**)&acc, (size_t)nlev * (size_t)ctx->ld * sizeof(double)), "hipMalloc(history)")) return ELMK_E_NOMEM;
+  launch_fill(acc, ELMK_F64, nlev, ctx->ld, ctx->ld, hist_init_value(op), ctx->stream);
+  const int row0 = (int)ctx->hist_rows.size();
+  const int es = store_size(g_fields[field].dtype);
+  for (int l = 0; l < nlev; l++)
+    ctx->hist_rows.push_back(HistRow{(const char*)ctx->fptr[field] + (size_t)l * (size_t)ctx->ld * es, acc + (size_t)l * (size_t)ctx->ld,
+                                     store_dtype(g_fields[field].dtype), op, tape, 0});
+  // the stream may still run an accumulate that reads the table: the copy is ordered after it; pageable source, so wait
+  const hipError_t e1 = hipGetLastError();
+  const hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(ctx->hist_table + (size_t)row0 * sizeof(HistRow), &ctx->hist_rows[row0],
+                                                          (size_t)nlev * sizeof(HistRow), hipMemcpyHostToDevice, ctx->stream)
+                                         : e1;
+  const hipError_t e3 = e2 == hipSuccess ? hipStreamSynchronize(ctx->stream) : e2;
+  if (hip_fail(ctx, e3, "elmk_history_add")) {
+    ctx->hist_rows.resize(row0);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(acc);
+    return ELMK_E_HIP;
+  }
+  ctx->hist.push_back(elmk_ctx::HistEntry{tape, field, op, nlev, row0, acc});
+  return (int)ctx->hist.size() - 1;
+}
+
+int elmk_history_accumulate(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (ctx->hist.empty()) return ELMK_OK;
+  const unsigned mask = hist_tape_mask(ctx);
+  launch_hist_accumulate((const HistRow*)ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
+  HIPCHK(hipGetLastError());
+  for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
+    if (mask & (1u << t)) ctx->hist_dirty[t] = true;
+  return ELMK_OK;
+}
+
+int elmk_history_reset(elmk_ctx* ctx, int tape)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!tape_ok(tape)) return invalid(ctx, "elmk_history_reset: unknown tape");
+  if (ctx->hist_table) {
+    launch_hist_reset((const HistRow*)ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, tape, ctx->stream);
+    HIPCHK(hipGetLastError());
+  }
+  ctx->hist_dirty[tape] = false;
+  return ELMK_OK;
+}
+
+int elmk_history_count(elmk_ctx* ctx, int tape, int64_t* nsamples)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!tape_ok(tape) || !nsamples) return invalid(ctx, "elmk_history_count: bad arguments");
+  unsigned long long c = 0;
+  if (ctx->hist_table)
+    HIPCHK(hipMemcpyAsync(&c, hist_counts(ctx) + tape, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *nsamples = (int64_t)c;
+  return ELMK_OK;
+}
+
+int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int64_t n, int layout)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (entry < 0 || entry >= (int)ctx->hist.size()) return invalid(ctx, "elmk_history_read: unknown entry");
+  if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols) return invalid(ctx, "elmk_history_read: bad column range");
+  if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_history_read: unknown layout");
+  const elmk_ctx::HistEntry e = ctx->hist[entry];
+  int64_t count = 0;
+  if (int rc = elmk_history_count(ctx, e.tape, &count)) return rc;
+  if (count <= 0) return invalid(ctx, "elmk_history_read: the tape holds no samples");
+  if (n == 0) return ELMK_OK;
+  // chunks of m columns: the finalize kernel writes them as dense SoA [lev][m] into the upper half of the staging buffer, and the
+  // transpose of elmk_download takes them to [col][lev] in the lower half where the caller wants the reference layout
+  const size_t half = ctx->staging_bytes / 2 / sizeof(double) * sizeof(double);
+  const int64_t chunk = (int64_t)(half / ((size_t)e.nlev * sizeof(double)));
+  if (chunk <= 0) return invalid(ctx, "staging buffer too small");
+  double* soa = (double*)(ctx->staging + half);
+  for (int64_t done = 0; done < n; done += chunk) {
+    const int64_t m = (n - done) < chunk ? (n - done) : chunk;
+    launch_hist_finalize(e.acc, ctx->ld, e.nlev, e.op, count, col0 + done, m, soa, ctx->stream);
+    if (layout == ELMK_LAYOUT_SOA || e.nlev == 1) {
+      HIPCHK(hipMemcpy2DAsync(host + done, (size_t)n * sizeof(double), soa, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
+                              e.nlev, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+      launch_soa_to_cols(soa, ctx->staging, 8, e.nlev, m, 0, m, ctx->stream);
+      HIPCHK(hipMemcpyAsync(host + (size_t)done * e.nlev, ctx->staging, (size_t)m * e.nlev * sizeof(double), hipMemcpyDeviceToHost,
+                            ctx->stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));  // staging is reused by the next chunk
+  }
+  return ELMK_OK;
+}
+
+int elmk_history_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (const elmk_ctx::HistEntry& e : ctx->hist) (void)hipFree(e.acc);
+  ctx->hist.clear();
+  ctx->hist_rows.clear();
+  if (ctx->hist_table)
+    HIPCHK(hipMemsetAsync(hist_counts(ctx), 0, ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
+  for (bool& d : ctx->hist_dirty) d = false;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return ELMK_OK;
 }

@@ -92,4 +92,32 @@ void launch_math_eval(int fn, const double* x, const double* y, double* out, int
 // the per-column solar geometry of elmk_solar_geometry (k_solar.hip): coszen and DevState::col_dayl from DevState::geo
 void launch_solar_geometry(const DevState* S, int64_t n, const elmk_solar_step& step, hipStream_t st);
 
+// history accumulation (k_history.hip, elmk_history_*): one row = one level of one registered entry.  src: the level's row of the
+// state field (stored element type `dtype`: an elmk_dtype or ELMK_F32_STORED); acc: its fp64 accumulator row (ld elements)
+struct HistRow {
+  const void* src;
+  double* acc;
+  int32_t dtype;
+  int32_t op;  // ELMK_HIST_*
+  int32_t tape;
+  int32_t pad;
+};
+// the value a reset leaves in an accumulator of `op`
+__host__ __device__ inline double hist_init_value(int op)
+{
+  switch (op) {
+    case ELMK_HIST_AVG:
+    case ELMK_HIST_SUM: return -0.0;  // IEEE's exact additive identity: -0.0 + x == x for every x, -0.0 included
+    case ELMK_HIST_MAX: return -__builtin_inf();
+    case ELMK_HIST_MIN: return __builtin_inf();
+    default: return __builtin_nan("");  // ELMK_HIST_INST: never read before a sample
+  }
+}
+// every row of every tape in one launch; counts[t] += 1 for each tape t in tape_mask
+void launch_hist_accumulate(const HistRow* rows, int nrows, unsigned long long* counts, int64_t ncols, unsigned tape_mask, hipStream_t st);
+void launch_hist_reset(const HistRow* rows, int nrows, unsigned long long* counts, int64_t ncols, int tape, hipStream_t st);
+// columns [col0, col0 + m) of one entry's result into out[lev * m + i]: acc / count for ELMK_HIST_AVG, acc otherwise
+void launch_hist_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, int64_t col0, int64_t m, double* out,
+                          hipStream_t st);
+
 }  // namespace elmk

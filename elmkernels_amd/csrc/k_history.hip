@@ -1,0 +1,142 @@
+// k_history.hip - history accumulation on the device (elmk_history_*): running sums, extremes and last values of registered state
+// fields, folded in once per step by ONE launch, so a driver downloads a time average once per output interval instead of the
+// state after every step.
+//
+// The unit of work is a row: one level of one registered entry (HistRow, built on the host by elmk_history_add).  The grid is
+// column blocks x rows, so the op and the stored dtype are uniform across a workgroup (no divergence) and every access is a
+// coalesced SoA stream over the columns of one row.  Every thread takes two adjacent columns: a 16-byte load / store of the fp64
+// accumulator and an 8-, 4- or 2-byte load of the source.  Rows of state fields and accumulators start at multiples of the level
+// stride ld (a multiple of 64 columns) from 256-byte aligned bases, so the vector accesses are aligned, and ncols <= ld keeps the
+// second column of a pair inside the row.  Bytes per column and row: source element + 16 (accumulator read + write).
+//
+// Semantics (include/elmk.h, "history"): each sample is the stored value widened to fp64; SUM / AVG acc = acc + v from -0.0;
+// MAX acc = (v > acc || v != v) ? v : acc from -inf (a NaN sticks), MIN the mirror from +inf; INST acc = v.  AVG is divided by
+// the count when it is read (k_hist_finalize), one correctly rounded division.
+#include "elmk_dev.h"
+#include "elmk_kernels.h"
+
+// Nontemporal hints (bit 1: source loads, bit 2: accumulator loads and stores).  Both on: interleaved A/B runs of
+// tests/tools/history_cost.py --ab (profiles/r06_history_nt_ab.jsonl) took the 19-field PrimaryVars tape from 0.64 to 0.59 ms at
+// 1 M columns and from 6.25 to 5.84 ms at 10 M, the 12-flux tape from 0.49 to 0.46 ms at 10 M.  Only a tape small enough to stay
+// in the on-die caches between two launches back to back lost (12 fluxes at 1 M: 0.039 -> 0.046 ms), and a physics step between
+// two accumulates leaves nothing of it there.
+#ifndef ELMK_HIST_NT
+#define ELMK_HIST_NT 3
+#endif
+
+namespace elmk {
+
+namespace {
+typedef double hd2 __attribute__((ext_vector_type(2)));
+typedef float hf2 __attribute__((ext_vector_type(2)));
+typedef int32_t hi2 __attribute__((ext_vector_type(2)));
+typedef uint32_t hu2 __attribute__((ext_vector_type(2)));
+typedef uint8_t hb2 __attribute__((ext_vector_type(2)));
+
+template <int BIT, typename V> __device__ __forceinline__ V h_ld(const ELMK_GLOBAL V* p)
+{
+  if (ELMK_HIST_NT & BIT) return __builtin_nontemporal_load(p);
+  return *p;
+}
+template <int BIT, typename V> __device__ __forceinline__ void h_st(ELMK_GLOBAL V* p, V v)
+{
+  if (ELMK_HIST_NT & BIT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
+// two adjacent columns of a source row, widened to fp64 (exact for every stored type)
+__device__ __forceinline__ hd2 load_pair(const void* src, int dtype, int64_t c)
+{
+  hd2 v;
+  switch (dtype) {
+    case ELMK_F64: v = h_ld<1>((const ELMK_GLOBAL hd2*)src + c / 2); break;
+    case ELMK_F32_STORED: { const hf2 f = h_ld<1>((const ELMK_GLOBAL hf2*)src + c / 2); v = hd2{(double)f.x, (double)f.y}; break; }
+    case ELMK_I32: { const hi2 i = h_ld<1>((const ELMK_GLOBAL hi2*)src + c / 2); v = hd2{(double)i.x, (double)i.y}; break; }
+    case ELMK_U32: { const hu2 u = h_ld<1>((const ELMK_GLOBAL hu2*)src + c / 2); v = hd2{(double)u.x, (double)u.y}; break; }
+    default: { const hb2 b = h_ld<1>((const ELMK_GLOBAL hb2*)src + c / 2); v = hd2{(double)b.x, (double)b.y}; break; }
+  }
+  return v;
+}
+
+__device__ __forceinline__ double fold(int op, double acc, double v)
+{
+  switch (op) {
+    case ELMK_HIST_AVG:
+    case ELMK_HIST_SUM: return acc + v;
+    case ELMK_HIST_MAX: return (v > acc || v != v) ? v : acc;
+    case ELMK_HIST_MIN: return (v < acc || v != v) ? v : acc;
+    default: return v;  // ELMK_HIST_INST
+  }
+}
+}  // namespace
+
+// grid (column pairs / 256, rows); rows[blockIdx.y] is uniform across the workgroup
+__global__ __launch_bounds__(256) void k_hist_accumulate(const HistRow* __restrict__ rows, unsigned long long* __restrict__ counts,
+                                                         int64_t npairs, unsigned tape_mask)
+{
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
+      if (tape_mask & (1u << t)) atomicAdd(&counts[t], 1ull);
+  }
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npairs) return;
+  const HistRow r = rows[blockIdx.y];
+  const int64_t c = 2 * p;
+  const hd2 v = load_pair(r.src, r.dtype, c);
+  ELMK_GLOBAL hd2* a = (ELMK_GLOBAL hd2*)r.acc + p;
+  hd2 acc = h_ld<2>(a);
+  acc.x = fold(r.op, acc.x, v.x);
+  acc.y = fold(r.op, acc.y, v.y);
+  h_st<2>(a, acc);
+}
+
+// the rows of one tape back to their initial value, the tape's count to 0 (rows of other tapes: nothing)
+__global__ __launch_bounds__(256) void k_hist_reset(const HistRow* __restrict__ rows, int nrows, unsigned long long* __restrict__ counts,
+                                                    int64_t npairs, int tape)
+{
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) counts[tape] = 0ull;
+  if ((int)blockIdx.y >= nrows) return;
+  const HistRow r = rows[blockIdx.y];
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r.tape != tape || p >= npairs) return;
+  const double v = hist_init_value(r.op);
+  ((ELMK_GLOBAL hd2*)r.acc)[p] = hd2{v, v};
+}
+
+// result of one entry for columns [col0, col0 + m): acc / count for AVG, acc otherwise, into out[lev * m + i] (dense SoA)
+__global__ __launch_bounds__(256) void k_hist_finalize(const double* __restrict__ acc, int64_t ld, int op, int64_t count, int64_t col0,
+                                                       int64_t m, double* __restrict__ out)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const int lev = blockIdx.y;
+  const double a = acc[(int64_t)lev * ld + col0 + i];
+  out[(int64_t)lev * m + i] = op == ELMK_HIST_AVG ? a / (double)count : a;
+}
+
+static unsigned pair_blocks(int64_t npairs) { return (unsigned)(npairs > 0 ? (npairs + 255) / 256 : 1); }
+
+void launch_hist_accumulate(const HistRow* rows, int nrows, unsigned long long* counts, int64_t ncols, unsigned tape_mask,
+                            hipStream_t st)
+{
+  if (nrows <= 0) return;
+  const int64_t npairs = (ncols + 1) / 2;
+  hipLaunchKernelGGL(k_hist_accumulate, dim3(pair_blocks(npairs), (unsigned)nrows), dim3(256), 0, st, rows, counts, npairs, tape_mask);
+}
+
+void launch_hist_reset(const HistRow* rows, int nrows, unsigned long long* counts, int64_t ncols, int tape, hipStream_t st)
+{
+  const int64_t npairs = (ncols + 1) / 2;
+  hipLaunchKernelGGL(k_hist_reset, dim3(pair_blocks(npairs), (unsigned)(nrows > 0 ? nrows : 1)), dim3(256), 0, st, rows, nrows, counts,
+                     npairs, tape);
+}
+
+void launch_hist_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, int64_t col0, int64_t m, double* out,
+                          hipStream_t st)
+{
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_hist_finalize, dim3((unsigned)((m + 255) / 256), (unsigned)nlev), dim3(256), 0, st, acc, ld, op, count, col0, m,
+                     out);
+}
+
+}  // namespace elmk

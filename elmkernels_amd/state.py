@@ -18,6 +18,9 @@ from . import _lib as L
 DTYPES = {0: np.float64, 1: np.int32, 2: np.uint8, 3: np.uint32}
 LAYOUT_COL_MAJOR, LAYOUT_SOA = 0, 1
 OPT_CF_HALF_WORKGROUPS = 1  # elmk_set_option
+HIST_AVG, HIST_SUM, HIST_MAX, HIST_MIN, HIST_INST = range(5)  # elmk_history_add
+HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, "inst": HIST_INST}
+HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
 
 # member order of ELM::PFTDataPSN (src/data/pft_data.h:20-24)
 PSN_FIELDS = (
@@ -64,6 +67,7 @@ class ELMState:
         self.fields = field_table()
         self.scalars = dict(dewmx=0.1, oldfflag=1, dayl=0.0, max_dayl=0.0)
         self.land = dict(ltype=1, ctype=0, vtype=2, urbpoi=0, lakpoi=0)
+        self._hist_nlev = {}  # history entry id -> levels of its field
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -298,6 +302,47 @@ class ELMState:
         """Back to one day length for all columns (set_scalars' dayl / max_dayl)."""
         self._chk(self.lib.elmk_clear_column_geography(self.ctx), "clear_column_geography")
 
+    # -- history (include/elmk.h: elmk_history_add ...) ---------------------------------------------
+    def history_add(self, tape, name, op):
+        """Register every level of field `name` on `tape` with op ("avg", "sum", "max", "min", "inst" or HIST_*); returns the
+        entry id.  Refused (ElmkError) for an unknown field / op / tape, a full table, a tape holding samples, a stream in capture."""
+        fid = self.fields[name][0] if isinstance(name, str) else int(name)
+        code = HIST_OPS[op] if isinstance(op, str) else int(op)
+        entry = self._chk(self.lib.elmk_history_add(self.ctx, int(tape), fid, code), f"history_add({name})")
+        nlev = C.c_int()
+        self.lib.elmk_field_info(fid, C.byref(nlev), None)
+        self._hist_nlev[entry] = nlev.value
+        return entry
+
+    def history_accumulate(self):
+        """Fold the current state into every tape's accumulators and count one sample per tape with entries: one launch, no sync."""
+        self._chk(self.lib.elmk_history_accumulate(self.ctx), "history_accumulate")
+
+    def history_reset(self, tape):
+        """The tape's accumulators back to their initial values, its count to 0 (stream-ordered)."""
+        self._chk(self.lib.elmk_history_reset(self.ctx, int(tape)), "history_reset")
+
+    def history_count(self, tape):
+        n = C.c_int64()
+        self._chk(self.lib.elmk_history_count(self.ctx, int(tape), C.byref(n)), "history_count")
+        return n.value
+
+    def history_read(self, entry, col0=0, n=None, layout=LAYOUT_COL_MAJOR, nlev=None):
+        """The entry's result as float64: [n] for a one-level field, else [n, nlev] (COL_MAJOR) or [nlev, n] (SOA)."""
+        n = self.ncols - col0 if n is None else int(n)
+        if nlev is None:
+            nlev = self._hist_nlev.get(int(entry), 1)
+        shape = (n,) if nlev == 1 else ((n, nlev) if layout == LAYOUT_COL_MAJOR else (nlev, n))
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self.lib.elmk_history_read(self.ctx, int(entry), out.ctypes.data_as(C.c_void_p), int(col0), n, int(layout)),
+                  "history_read")
+        return out
+
+    def history_clear(self):
+        """Drop every entry of every tape and free its device buffers."""
+        self._chk(self.lib.elmk_history_clear(self.ctx), "history_clear")
+        self._hist_nlev.clear()
+
     def math_eval(self, fn, x, y=None):
         """elmk_math.h on the device: fn in MATH_FNS; returns fn(x), x / y or pow(x, y)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -491,6 +536,10 @@ class ELMInterface:
         if flags & 0xC7FF:  # ELMK_ERR_FATAL_MASK
             raise RuntimeError(f"ELM physics error flags {flags:#x}, first at column {col}")
         return False
+
+    def accumulate_history(self):
+        """Fold this step's state into the history tapes registered on self.S (ELMState.history_add): call after advance()."""
+        self.S.history_accumulate()
 
     def getPrimaryVars(self):
         """ELMInterface::getPrimaryVars / copyPrimaryVars (:324-356): the PrimaryVars members as host arrays."""

@@ -38,6 +38,7 @@
  *   S.snw_rds_table (SnwRdsTable)   src/data/snicar_data.h:75-84      elmk_set_snow_age_tables
  *   kokkos_surface_fluxes(S,dt)     surface_fluxes_kokkos.hh          elmk_surface_fluxes
  *   kokkos_evaluate_conservation    conserved_quantity_kokkos.hh      elmk_evaluate_conservation
+ *   (ELM's history tapes: time averages, extremes, last values)       elmk_history_add / _accumulate / _read
  *   throw / assert inside physics   (list: SURVEY.md section 5)       per-column flag word, elmk_error_summary
  *
  * Conventions
@@ -240,6 +241,37 @@ int elmk_set_column_geography(elmk_ctx *ctx, const double *lat_r, const double *
 int elmk_solar_geometry(elmk_ctx *ctx, double dt_seconds, double decday, int doy);
 int elmk_download_day_length(elmk_ctx *ctx, double *dayl, double *max_dayl);
 int elmk_clear_column_geography(elmk_ctx *ctx);
+
+/* ---- history --------------------------------------------------------------------------------
+ * Output averaged over time without a download per step (ELM's history tapes): a driver registers fields once, folds the
+ * current state into device-resident accumulators with one launch per step, and downloads only at the end of an output interval.
+ *   elmk_history_add         register every level of `field` on `tape` (0 .. ELMK_HIST_MAX_TAPES-1) with `op`; returns the entry
+ *                            id (>= 0, in order of registration) or a negative ELMK_E_* code.  Refused: an unknown field, op or
+ *                            tape, a full table (ELMK_HIST_MAX_ENTRIES over all tapes), a tape that has accumulated samples since
+ *                            its last reset, a stream that is being captured.  Allocates nlev x level-stride fp64 on the device.
+ *   elmk_history_accumulate  fold the current value of every registered field of every tape into its accumulator and count one
+ *                            sample for each tape that has entries: ONE kernel launch on the context's stream, no host memory, no
+ *                            synchronisation - a caller may capture it into a graph of its own.  Nothing without entries.  A
+ *                            captured graph holds the entry table of the moment of capture: capture again after add / clear.
+ *   elmk_history_reset       stream-ordered and capturable: the tape's accumulators back to their initial values, its count to 0
+ *   elmk_history_count       the tape's sample count, kept on the device (a replayed graph counts every replay); synchronises
+ *   elmk_history_read        the entry's result as doubles, [nlev] per column, columns [col0, col0+n), layout as elmk_download;
+ *                            ELMK_E_INVALID while its tape holds 0 samples; synchronises
+ *   elmk_history_clear       drop every entry of every tape and free its buffers; counts to 0
+ * Semantics, bit for bit: a sample is the stored value widened to fp64 (F64 as stored - fp32 widened in libelmk_f32.so -, I32 /
+ * U8 / U32 exactly); accumulators are fp64.  SUM / AVG: -0.0 after a reset, then acc = acc + v in step order; SUM reads acc, AVG
+ * reads acc / (double)count (one correctly rounded division when read, not a running mean).  MAX: -inf after a reset, then
+ * acc = (v > acc || v != v) ? v : acc, so a NaN sticks; MIN the mirror image from +inf.  INST: the last sample.
+ * Accumulating writes no state field and no physics scratch and changes no other call, graph or launch shape. */
+enum { ELMK_HIST_AVG = 0, ELMK_HIST_SUM = 1, ELMK_HIST_MAX = 2, ELMK_HIST_MIN = 3, ELMK_HIST_INST = 4 };
+#define ELMK_HIST_MAX_TAPES 4
+#define ELMK_HIST_MAX_ENTRIES 64 /* per context, over all tapes */
+int elmk_history_add(elmk_ctx *ctx, int tape, int field, int op);
+int elmk_history_accumulate(elmk_ctx *ctx);
+int elmk_history_reset(elmk_ctx *ctx, int tape);
+int elmk_history_count(elmk_ctx *ctx, int tape, int64_t *nsamples);
+int elmk_history_read(elmk_ctx *ctx, int entry, double *host, int64_t col0, int64_t n, int layout);
+int elmk_history_clear(elmk_ctx *ctx);
 
 /* ---- the physics wrappers (same names, order and arguments as driver/kokkos) ---------------- */
 int elmk_frac_wet(elmk_ctx *ctx);

@@ -209,6 +209,26 @@ class ELMInterface {
     return advance(dt_seconds, w);
   }
 
+  /* History tapes (ELM's time-averaged output) kept on the device: register fields once, call accumulate_history() after every
+   * advance(), read at the end of an output interval and reset the tape.  op: ELMK_HIST_AVG / _SUM / _MAX / _MIN / _INST;
+   * history_add returns the entry id history_read takes.  history_read fills [ncols][nlev] doubles, the host layout of upload. */
+  int history_add(int tape, const char* field, int op)
+  {
+    const int e = elmk_history_add(ctx_, tape, id(field), op);
+    ok(e < 0 ? e : ELMK_OK);
+    return e;
+  }
+  void accumulate_history() { ok(elmk_history_accumulate(ctx_)); }
+  void history_reset(int tape) { ok(elmk_history_reset(ctx_, tape)); }
+  int64_t history_count(int tape)
+  {
+    int64_t n = 0;
+    ok(elmk_history_count(ctx_, tape, &n));
+    return n;
+  }
+  void history_read(int entry, double* host) { ok(elmk_history_read(ctx_, entry, host, 0, ncols_, ELMK_LAYOUT_COL_MAJOR)); }
+  void history_clear() { ok(elmk_history_clear(ctx_)); }
+
   /* ELMInterface::copyPrimaryVars / getPrimaryVars (elm_kokkos_interface.cc:324-356) */
   void copyPrimaryVars(PrimaryVars& pv)
   {
