@@ -83,6 +83,10 @@ SIGNATURES = {
     "elmk_history_count": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     "elmk_history_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int]),
     "elmk_history_clear": (C.c_int, [_P]),
+    "elmk_run_reserve": (C.c_int, [_P, C.c_int, C.c_int]),
+    "elmk_series_upload": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_run": (C.c_int, [_P, C.c_double, _P, C.c_int, C.c_int]),
+    "elmk_run_diagnostics": (C.c_int, [_P, _P, _P, _P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

@@ -10,6 +10,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <dlfcn.h>
 #include <string>
@@ -56,6 +57,7 @@ struct GraphSlot {
   hipGraphExec_t exec = nullptr;
   double dt = 0.0;
   hipStream_t stream = nullptr;
+  uint64_t tag = 0;  // what else the captured launches depend on (elmk_run: its flags and the history table's version)
 };
 
 struct elmk_ctx {
@@ -85,7 +87,7 @@ struct elmk_ctx {
   // fork / join of albedo_snicar) and replayed; key = (dt, stream)
   bool use_graph = false;
   bool have_init_params = false;
-  GraphSlot graph[3];  // [0] elmk_timestep7, [1] elmk_timestep7_fused, [2] elmk_advance_physics
+  GraphSlot graph[4];  // [0] elmk_timestep7, [1] elmk_timestep7_fused, [2] elmk_advance_physics, [3] one step of elmk_run
   // A HIP error may have cut a step short between the kernel that fills a work list and the one that drains it and leaves it
   // empty (the lists have no reset launch of their own): the next physics call zeroes every list counter first.
   bool lists_stale = false;
@@ -105,6 +107,33 @@ struct elmk_ctx {
   std::vector<HistRow> hist_rows;
   char* hist_table = nullptr;
   bool hist_dirty[ELMK_HIST_MAX_TAPES] = {};
+  uint64_t hist_version = 0;  // counts elmk_history_add / _clear: a captured step of elmk_run holds the table of its moment
+  bool snowage_set = false;
+  // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
+  // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
+  // is the pinned host copy of the step tables.  Per buffer, what the run last enqueued on it reads and the event of its end: a
+  // buffer is reused only after that run has finished, so the read set of every unfinished run is known to elmk_series_upload.
+  struct Run {
+    int slots = 0, max_steps = 0;
+    char* mem = nullptr;
+    size_t bytes = 0;
+    char* forc = nullptr;
+    char* phen = nullptr;
+    RunRow* table = nullptr;
+    int32_t* cursor = nullptr;
+    double* cons = nullptr;
+    uint32_t* flag_or = nullptr;
+    long long* flag_first = nullptr;
+    RunRow* rows = nullptr;
+    hipStream_t upload = nullptr;
+    hipEvent_t done[2] = {};
+    bool live[2] = {};
+    int slot_lo[2] = {}, slot_hi[2] = {};
+    unsigned months[2] = {};
+    uint64_t count = 0;  // runs enqueued since the reserve
+    int last_buf = -1, last_nsteps = 0;
+    int flags = 0;  // of the run being enqueued (launch_stage_run)
+  } run;
   std::string err;
 };
 
@@ -181,6 +210,22 @@ int enter(elmk_ctx* ctx)
 }
 
 bool field_ok(int f) { return f >= 0 && f < ELMK_NUM_FIELDS; }
+
+// the device and pinned memory of elmk_run_reserve (the caller has synchronised every stream that may use it)
+void run_release(elmk_ctx* ctx)
+{
+  elmk_ctx::Run& R = ctx->run;
+  if (R.mem) (void)hipFree(R.mem);
+  if (R.rows) (void)hipHostFree(R.rows);
+  R.mem = nullptr;
+  R.rows = nullptr;
+  R.bytes = 0;
+  R.slots = R.max_steps = 0;
+  R.live[0] = R.live[1] = false;
+  R.count = 0;
+  R.last_buf = -1;
+  R.last_nsteps = 0;
+}
 
 }  // namespace
 
@@ -340,6 +385,14 @@ int elmk_destroy(elmk_ctx* ctx)
   if (ctx->hist_table) (void)hipFree(ctx->hist_table);
   for (GraphSlot& g : ctx->graph)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  run_release(ctx);
+  if (ctx->run.upload) {
+    (void)hipStreamSynchronize(ctx->run.upload);
+    (void)hipStreamDestroy(ctx->run.upload);
+  }
+  for (int b = 0; b < 2; b++) {
+    if (ctx->run.done[b]) (void)hipEventDestroy(ctx->run.done[b]);
+  }
   if (ctx->red_or) (void)hipFree(ctx->red_or);
   if (ctx->staging) (void)hipFree(ctx->staging);
   for (char* b : ctx->snap_bufs) (void)hipFree(b);
@@ -418,7 +471,9 @@ int64_t elmk_ncols(const elmk_ctx* ctx) { return ctx ? ctx->ncols : -1; }
 int64_t elmk_level_stride(const elmk_ctx* ctx) { return ctx ? ctx->ld : -1; }
 int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
-  return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState)) : -1;
+  return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
+                         ctx->run.bytes)
+             : -1;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -806,6 +861,7 @@ int elmk_set_snow_age_tables(elmk_ctx* ctx, const double* tau, const double* kap
     HIPCHK(hipMemcpyAsync(ctx->snowage + (size_t)k * ELMK_SNOWAGE_N, src[k], ELMK_SNOWAGE_N * sizeof(double), hipMemcpyHostToDevice,
                           ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->snowage_set = true;
   return ELMK_OK;
 }
 
@@ -865,6 +921,7 @@ int elmk_history_add(elmk_ctx* ctx, int tape, int field, int op)
     return ELMK_E_HIP;
   }
   ctx->hist.push_back(elmk_ctx::HistEntry{tape, field, op, nlev, row0, acc});
+  ctx->hist_version++;
   return (int)ctx->hist.size() - 1;
 }
 
@@ -948,6 +1005,7 @@ int elmk_history_clear(elmk_ctx* ctx)
   if (ctx->hist_table)
     HIPCHK(hipMemsetAsync(hist_counts(ctx), 0, ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
   for (bool& d : ctx->hist_dirty) d = false;
+  ctx->hist_version++;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return ELMK_OK;
 }
@@ -1208,9 +1266,9 @@ int enqueue_stages(elmk_ctx* ctx, stage_fn fn, int nstage, double dt, hipEvent_t
 
 // the stages captured once as a HIP graph (kernel nodes in one chain: the side-stream forks are issued in order on the
 // capturing stream) and replayed
-int run_graph(elmk_ctx* ctx, GraphSlot& g, stage_fn fn, int nstage, double dt)
+int run_graph(elmk_ctx* ctx, GraphSlot& g, stage_fn fn, int nstage, double dt, uint64_t tag = 0)
 {
-  if (!g.exec || g.dt != dt || g.stream != ctx->stream) {
+  if (!g.exec || g.dt != dt || g.stream != ctx->stream || g.tag != tag) {
     if (g.exec) {
       // dt or the stream changed: the old executable may still be running its last launch.  (Best effort: a caller that
       // destroyed the old stream has synchronised it itself, and the error of waiting on it is not this call's.)
@@ -1242,6 +1300,7 @@ int run_graph(elmk_ctx* ctx, GraphSlot& g, stage_fn fn, int nstage, double dt)
     }
     g.dt = dt;
     g.stream = ctx->stream;
+    g.tag = tag;
   }
   HIPCHK(hipGraphLaunch(g.exec, ctx->stream));
   return ELMK_OK;
@@ -1319,6 +1378,247 @@ int elmk_advance_physics(elmk_ctx* ctx, double dt)
   PHYSICS_PROLOGUE();
   if (ctx->use_graph) return run_graph(ctx, ctx->graph[2], launch_stage_advance, ADV_NSTAGE, dt);
   return enqueue_stages(ctx, launch_stage_advance, ADV_NSTAGE, dt, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// multi-step runs: the driver's time loop (kokkos_driver.cc:54-85) on the device
+// ---------------------------------------------------------------------------------------------------
+namespace {
+bool capturing(elmk_ctx* ctx, hipStream_t s, bool* out)
+{
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hip_fail(ctx, hipStreamIsCapturing(s, &cap), "hipStreamIsCapturing")) return false;
+  *out = cap != hipStreamCaptureStatusNone;
+  return true;
+}
+
+// one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
+// forcing, init_timestep, advance_physics' stages, conservation -> ring row, flag summary -> ring row, history, next row
+constexpr int RUN_NSTAGE = 4 + ADV_NSTAGE + 4;
+void launch_stage_run(elmk_ctx* ctx, int k, double dt)
+{
+  const elmk_ctx::Run& R = ctx->run;
+  if (k >= 4 && k < 4 + ADV_NSTAGE) {
+    launch_stage_advance(ctx, k - 4, dt);
+    return;
+  }
+  switch (k < 4 ? k : k - ADV_NSTAGE) {
+    case 0: launch_solar_geometry_run(ctx->d, ctx->ncols, R.table, R.cursor, ctx->stream); break;
+    case 1: launch_phenology_run(ctx->d, ctx->ncols, R.table, R.cursor, R.phen, ctx->stream); break;
+    case 2: launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream); break;
+    case 3: launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); break;
+    case 4: {
+      double* diag = ELMK_GENERIC(ctx->h.cons_diag);
+      double* part = diag + (size_t)8 * ctx->ld;
+      launch_conservation_run(ctx->d, ctx->ncols, ctx->ld, dt, diag, part, R.cons, R.flag_or, R.flag_first, R.cursor, ctx->stream);
+      break;
+    }
+    case 5:
+      launch_flag_reduce_run((const uint32_t*)ctx->fptr[ELMK_FIELD_err_flags], ctx->ncols, R.flag_or, R.flag_first, R.cursor, ctx->stream);
+      break;
+    case 6:
+      if ((R.flags & ELMK_RUN_HISTORY) && !ctx->hist.empty())
+        launch_hist_accumulate((const HistRow*)ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, hist_tape_mask(ctx),
+                               ctx->stream);
+      break;
+    default: launch_run_next(R.cursor, ctx->stream); break;
+  }
+}
+}  // namespace
+
+int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (forcing_slots < 2 || forcing_slots > (1 << 20) || max_steps < 1 || max_steps > (1 << 24))
+    return invalid(ctx, "elmk_run_reserve: need 2 <= forcing_slots <= 2^20 and 1 <= max_steps <= 2^24");
+  bool cap = false;
+  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
+  if (cap) return invalid(ctx, "elmk_run_reserve: the stream is being captured");
+  elmk_ctx::Run& R = ctx->run;
+  // the runs in flight read the old buffers, an upload may still write them: wait for both, then drop the captured step (it holds
+  // the old addresses)
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (R.upload) HIPCHK(hipStreamSynchronize(R.upload));
+  if (ctx->graph[3].exec) (void)hipGraphExecDestroy(ctx->graph[3].exec);
+  ctx->graph[3].exec = nullptr;
+  run_release(ctx);
+  if (!R.upload) {
+    HIPCHK(hipStreamCreateWithFlags(&R.upload, hipStreamNonBlocking));
+    for (int b = 0; b < 2; b++) {
+      HIPCHK(hipEventCreateWithFlags(&R.done[b], hipEventDisableTiming));
+    }
+  }
+  const size_t es = (size_t)store_size(ELMK_F64), ld = (size_t)ctx->ld, nrow = 2 * (size_t)max_steps;
+  const size_t forc_b = align_up((size_t)RUN_NFORC * forcing_slots * ld * es, 256);
+  const size_t phen_b = align_up((size_t)RUN_NPHEN * RUN_NMONTH * ld * es, 256);
+  const size_t tab_b = align_up(nrow * sizeof(RunRow), 256);
+  const size_t cur_b = 256;
+  const size_t cons_b = align_up(nrow * 24 * sizeof(double), 256);
+  const size_t or_b = align_up(nrow * sizeof(uint32_t), 256);
+  const size_t first_b = align_up(nrow * sizeof(long long), 256);
+  const size_t bytes = forc_b + phen_b + tab_b + cur_b + cons_b + or_b + first_b;
+  if (hip_fail(ctx, hipMalloc((void**)&R.mem, bytes), "hipMalloc(run)")) {
+    R.mem = nullptr;
+    return ELMK_E_NOMEM;
+  }
+  if (hip_fail(ctx, hipHostMalloc((void**)&R.rows, nrow * sizeof(RunRow), hipHostMallocDefault), "hipHostMalloc(run steps)")) {
+    R.rows = nullptr;
+    run_release(ctx);
+    return ELMK_E_NOMEM;
+  }
+  char* q = R.mem;
+  R.forc = q;
+  q += forc_b;
+  R.phen = q;
+  q += phen_b;
+  R.table = (RunRow*)q;
+  q += tab_b;
+  R.cursor = (int32_t*)q;
+  q += cur_b;
+  R.cons = (double*)q;
+  q += cons_b;
+  R.flag_or = (uint32_t*)q;
+  q += or_b;
+  R.flag_first = (long long*)q;
+  R.bytes = bytes;
+  R.slots = forcing_slots;
+  R.max_steps = max_steps;
+  if (hip_fail(ctx, hipMemsetAsync(R.mem, 0, bytes, ctx->stream), "hipMemset(run)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    run_release(ctx);
+    return ELMK_E_HIP;
+  }
+  return ELMK_OK;
+}
+
+int elmk_series_upload(elmk_ctx* ctx, int field, int slot0, int nslots, const double* host, int64_t col0, int64_t n)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Run& R = ctx->run;
+  if (!R.mem) return invalid(ctx, "elmk_series_upload: elmk_run_reserve has not been called");
+  const bool forcing = field >= ELMK_FIELD_atm_tbot && field <= ELMK_FIELD_atm_wind;
+  const bool phen = field >= ELMK_FIELD_mlai && field <= ELMK_FIELD_mhbot;
+  static_assert(ELMK_FIELD_atm_wind - ELMK_FIELD_atm_tbot + 1 == RUN_NFORC && ELMK_FIELD_mhbot - ELMK_FIELD_mlai + 1 == RUN_NPHEN,
+                "series fields");
+  if (!forcing && !phen) return invalid(ctx, "elmk_series_upload: not a series field (atm_tbot .. atm_wind, mlai .. mhbot)");
+  const int k = forcing ? field - ELMK_FIELD_atm_tbot : field - ELMK_FIELD_mlai;
+  const int nsl = forcing ? R.slots : RUN_NMONTH;
+  if (slot0 < 0 || nslots < 0 || slot0 + (int64_t)nslots > nsl) return invalid(ctx, "elmk_series_upload: slots out of range");
+  if ((!host && n > 0 && nslots > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols)
+    return invalid(ctx, "elmk_series_upload: bad column range");
+  if (n == 0 || nslots == 0) return ELMK_OK;
+  // never write under a run that reads these records: wait for the end of each enqueued run that does
+  for (int b = 0; b < 2; b++) {
+    if (!R.live[b]) continue;
+    const bool hit = forcing ? (slot0 <= R.slot_hi[b] && slot0 + nslots - 1 >= R.slot_lo[b])
+                             : ((R.months[b] >> slot0) & ((1u << nslots) - 1u)) != 0;
+    if (hit) HIPCHK(hipEventSynchronize(R.done[b]));
+  }
+  const size_t es = (size_t)store_size(ELMK_F64);
+  char* dst = (forcing ? R.forc : R.phen) + (((size_t)k * nsl + slot0) * (size_t)ctx->ld + (size_t)col0) * es;
+  const void* src = host;
+  std::vector<float> tmp;
+  if (kStateF32) {  // rounded to the stored fp32 as xfer rounds an upload
+    const size_t cnt = (size_t)nslots * (size_t)n;
+    tmp.resize(cnt);
+    for (size_t i = 0; i < cnt; i++) tmp[i] = (float)host[i];
+    src = tmp.data();
+  }
+  HIPCHK(hipMemcpy2DAsync(dst, (size_t)ctx->ld * es, src, (size_t)n * es, (size_t)n * es, (size_t)nslots, hipMemcpyHostToDevice, R.upload));
+  HIPCHK(hipStreamSynchronize(R.upload));  // (caller's pageable source; a run enqueued after this call sees the records)
+  return ELMK_OK;
+}
+
+int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, int flags)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Run& R = ctx->run;
+  // every refusal before anything is enqueued
+  if (!R.mem) return invalid(ctx, "elmk_run: elmk_run_reserve has not been called");
+  if (!ctx->geo_set) return invalid(ctx, "elmk_run: no column geography (elmk_set_column_geography)");
+  if (!ctx->snowage_set) return invalid(ctx, "elmk_run: the snow-age tables are not set (elmk_set_snow_age_tables)");
+  if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
+  if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
+  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY)) return invalid(ctx, "elmk_run: unknown flags");
+  int lo = R.slots, hi = -1;
+  unsigned months = 0;
+  for (int s = 0; s < nsteps; s++) {
+    const elmk_run_step& p = steps[s];
+    if (p.forc_slot < 0 || p.forc_slot > R.slots - 2) return invalid(ctx, "elmk_run: forc_slot outside 0 .. forcing_slots - 2");
+    if (p.month1 < 0 || p.month1 >= RUN_NMONTH || p.month2 < 0 || p.month2 >= RUN_NMONTH) return invalid(ctx, "elmk_run: month outside 0 .. 11");
+    if (!(p.decday >= 0.0 && p.decday < 1.0e9) || p.doy < -1 || p.doy > 1000000000) return invalid(ctx, "elmk_run: bad decday / doy");
+    lo = std::min(lo, (int)p.forc_slot);
+    hi = std::max(hi, (int)p.forc_slot + 1);
+    months |= (1u << p.month1) | (1u << p.month2);
+  }
+  bool cap = false;
+  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
+  if (cap) return invalid(ctx, "elmk_run: the stream is being captured");
+
+  if (!ctx->side.col_dayl) {  // per-column mode, as the first elmk_solar_geometry enters it
+    if (int rc = drop_graphs(ctx)) return rc;
+    ctx->side.col_dayl = true;
+  }
+  if (int rc = heal_lists(ctx)) return rc;
+  if (int rc = push_params(ctx)) return rc;
+  // this buffer was last used by run count - 2: wait for its end before its pinned rows, device table, ring rows and read set are
+  // reused (otherwise an upload after this call would no longer know that run's read set and could write under it)
+  const int buf = (int)(R.count & 1);
+  if (R.live[buf]) HIPCHK(hipEventSynchronize(R.done[buf]));
+  RunRow* rows = R.rows + (size_t)buf * R.max_steps;
+  for (int s = 0; s < nsteps; s++) {
+    const elmk_run_step& p = steps[s];
+    RunRow& r = rows[s];
+    r.sol = elmk_solar_step_consts(dt, p.decday, p.doy);
+    memcpy(r.forc_wt1, p.forc_wt1, sizeof r.forc_wt1);
+    memcpy(r.forc_wt2, p.forc_wt2, sizeof r.forc_wt2);
+    r.month_wt1 = p.month_wt1;
+    r.month_wt2 = p.month_wt2;
+    r.forc_slot = p.forc_slot;
+    r.month1 = p.month1;
+    r.month2 = p.month2;
+    r.pad = 0;
+  }
+  const int row0 = buf * R.max_steps;
+  HIPCHK(hipMemcpyAsync(R.table + row0, rows, (size_t)nsteps * sizeof(RunRow), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)R.cursor, row0, 1, ctx->stream));
+  R.flags = flags;
+  R.live[buf] = true;  // (from here on an upload of these records waits for the run's end event)
+  R.slot_lo[buf] = lo;
+  R.slot_hi[buf] = hi;
+  R.months[buf] = months;
+  R.count++;
+  R.last_buf = buf;
+  R.last_nsteps = nsteps;
+  const uint64_t tag = (uint64_t)flags | (ctx->hist_version << 8);
+  int rc = ELMK_OK;
+  for (int s = 0; s < nsteps && rc == ELMK_OK; s++)
+    rc = ctx->use_graph ? run_graph(ctx, ctx->graph[3], launch_stage_run, RUN_NSTAGE, dt, tag)
+                        : enqueue_stages(ctx, launch_stage_run, RUN_NSTAGE, dt, nullptr);
+  HIPCHK(hipEventRecord(R.done[buf], ctx->stream));
+  if (rc) return rc;
+  if ((flags & ELMK_RUN_HISTORY) && !ctx->hist.empty()) {
+    const unsigned mask = hist_tape_mask(ctx);
+    for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
+      if (mask & (1u << t)) ctx->hist_dirty[t] = true;
+  }
+  return ELMK_OK;
+}
+
+int elmk_run_diagnostics(elmk_ctx* ctx, double* min_max_sum, uint32_t* flags_or, int64_t* first_bad_col)
+{
+  if (int rc = enter(ctx)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const elmk_ctx::Run& R = ctx->run;
+  if (R.last_buf < 0) return 0;
+  const size_t row0 = (size_t)R.last_buf * R.max_steps, n = (size_t)R.last_nsteps;
+  std::vector<long long> f(first_bad_col ? n : 0);
+  if (min_max_sum) HIPCHK(hipMemcpyAsync(min_max_sum, R.cons + row0 * 24, n * 24 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (flags_or) HIPCHK(hipMemcpyAsync(flags_or, R.flag_or + row0, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (first_bad_col) HIPCHK(hipMemcpyAsync(f.data(), R.flag_first + row0, n * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < f.size(); i++) first_bad_col[i] = (f[i] == 0x7fffffffffffffffll) ? -1 : (int64_t)f[i];
+  return (int)n;
 }
 
 // ---------------------------------------------------------------------------------------------------

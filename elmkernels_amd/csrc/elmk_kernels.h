@@ -92,6 +92,28 @@ void launch_math_eval(int fn, const double* x, const double* y, double* out, int
 // the per-column solar geometry of elmk_solar_geometry (k_solar.hip): coszen and DevState::col_dayl from DevState::geo
 void launch_solar_geometry(const DevState* S, int64_t n, const elmk_solar_step& step, hipStream_t st);
 
+// multi-step runs (elmk_run): one row of the device step table per step, read through the device step cursor (an int32: the
+// table row of the step now executing; elmk_run sets it before the first step, k_run_next advances it at the end of each)
+struct RunRow {
+  elmk_solar_step sol;  // elmk_solar_step_consts of the step, computed on the host
+  double forc_wt1[8], forc_wt2[8];
+  double month_wt1, month_wt2;
+  int32_t forc_slot, month1, month2, pad;
+};
+// series: the forcing records [RUN_NFORC][slots][ld] and the months [RUN_NPHEN][12][ld], stored element type of the state
+constexpr int RUN_NFORC = 7, RUN_NPHEN = 4, RUN_NMONTH = 12;
+void launch_solar_geometry_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, hipStream_t st);
+void launch_phenology_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* phen, hipStream_t st);
+void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
+                            int qbot_is_rh, hipStream_t st);
+// launch_conservation with the (min, max, sum) triples written to ring row *cursor (cons_ring: [row][8][3]); also opens the flag
+// row of the step (flag_or 0, flag_first "none") for launch_flag_reduce_run
+void launch_conservation_run(const DevState* S, int64_t n, int64_t ld, double dt, const double* diag, double* part, double* cons_ring,
+                             uint32_t* flag_or, long long* flag_first, const int32_t* cursor, hipStream_t st);
+void launch_flag_reduce_run(const uint32_t* flags, int64_t n, uint32_t* flag_or, long long* flag_first, const int32_t* cursor,
+                            hipStream_t st);
+void launch_run_next(int32_t* cursor, hipStream_t st);
+
 // history accumulation (k_history.hip, elmk_history_*): one row = one level of one registered entry.  src: the level's row of the
 // state field (stored element type `dtype`: an elmk_dtype or ELMK_F32_STORED); acc: its fp64 accumulator row (ld elements)
 struct HistRow {

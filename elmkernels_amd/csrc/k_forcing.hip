@@ -42,20 +42,26 @@ struct ForcingWeights {
   int qbot_is_rh;
 };
 
-__global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict__ S, const ForcingWeights W)
+// where a column reads its two records of each raw stream (TBOT PBOT QBOT FLDS FSDS PREC WIND): record t_idx at l0[k] + c,
+// t_idx + 1 at l1[k] + c - the levels of atm_* for elmk_get_forcing, two slots of the forcing series for elmk_run
+struct ForcingSrc {
+  dfield l0[RUN_NFORC], l1[RUN_NFORC];
+};
+#define SV(k, lev) src.l##lev[k][c]
+
+// one column: the body of k_get_forcing and of its run-mode variant
+__device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, int64_t c, const ForcingWeights& W, const ForcingSrc& src)
 {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ld = S->ld;
-  if (c >= S->ncols) return;
   // ProcessTBOT :38-42
-  const double tbot = dmin(interp_forcing(W.wt1[0], W.wt2[0], LV(atm_tbot, 0), LV(atm_tbot, 1)), 323.0);
+  const double tbot = dmin(interp_forcing(W.wt1[0], W.wt2[0], SV(0, 0), SV(0, 1)), 323.0);
   S->forc_tbot[c] = tbot;
   S->forc_thbot[c] = tbot;
   // ProcessPBOT :55-58
-  const double pbot = dmax(interp_forcing(W.wt1[1], W.wt2[1], LV(atm_pbot, 0), LV(atm_pbot, 1)), 4.0e4);
+  const double pbot = dmax(interp_forcing(W.wt1[1], W.wt2[1], SV(1, 0), SV(1, 1)), 4.0e4);
   S->forc_pbot[c] = pbot;
   // ProcessQBOT :73-81
-  double qbot = dmax(interp_forcing(W.wt1[2], W.wt2[2], LV(atm_qbot, 0), LV(atm_qbot, 1)), 1.0e-9);
+  double qbot = dmax(interp_forcing(W.wt1[2], W.wt2[2], SV(2, 0), SV(2, 1)), 1.0e-9);
   if (W.qbot_is_rh) {
     const double e = (tbot > TFRZ) ? esatw(tdc(tbot)) : esati(tdc(tbot));
     const double qsat = 0.622 * e / (pbot - 0.378 * e);
@@ -63,7 +69,7 @@ __global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict_
   }
   S->forc_qbot[c] = qbot;
   // ProcessFLDS :97-107
-  const double flds = interp_forcing(W.wt1[3], W.wt2[3], LV(atm_flds, 0), LV(atm_flds, 1));
+  const double flds = interp_forcing(W.wt1[3], W.wt2[3], SV(3, 0), SV(3, 1));
   double lwrad = flds;
   if (flds <= 50.0 || flds >= 600.0) {
     const double e = pbot * qbot / (0.622 + 0.378 * qbot);
@@ -73,7 +79,7 @@ __global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict_
   S->forc_lwrad[c] = lwrad;
   // ProcessFSDS :122-142 (record t_idx only); pow(x, 2.0) is x * x in the reference's optimised builds (elmk_math.h)
   {
-    const double swndr = dmax(LV(atm_fsds, 0) * S->coszen[c] * 0.5, 0.0);
+    const double swndr = dmax(SV(4, 0) * S->coszen[c] * 0.5, 0.0);
     const double swndf = swndr, swvdr = swndr, swvdf = swndr;
     const double ratio_rvrf_vis =
         dmin(0.99, dmax(0.17639 + 0.00380 * swvdr - 9.0039e-06 * elmk_sq(swvdr) + 8.1351e-09 * elmk_pow(swvdr, 3.0), 0.01));
@@ -88,12 +94,12 @@ __global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict_
   {
     const double frac1 = (tbot - TFRZ) * 0.5;
     const double frac2 = dmin(1.0, dmax(0.0, frac1));
-    const double prec = dmax(LV(atm_prec, 0), 0.0);
+    const double prec = dmax(SV(5, 0), 0.0);
     S->forc_rain[c] = frac2 * prec;
     S->forc_snow[c] = (1.0 - frac2) * prec;
   }
   // ProcessWIND :177-181
-  S->forc_u[c] = interp_forcing(W.wt1[6], W.wt2[6], LV(atm_wind, 0), LV(atm_wind, 1));
+  S->forc_u[c] = interp_forcing(W.wt1[6], W.wt2[6], SV(6, 0), SV(6, 1));
   S->forc_v[c] = 0.0;
   // ProcessZBOT :195-203 (hardwired 30 m)
   S->forc_hgt[c] = 30.0;
@@ -102,20 +108,23 @@ __global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict_
   S->forc_hgt_q_patch[c] = 30.0;
 }
 
-// phenology_physics_impl.hh:22-69
-__global__ __launch_bounds__(256) void k_phenology(const DevState* __restrict__ S, double wt1, double wt2)
+// the two months a column reads of mlai, msai, mhtop, mhbot (in this order): month start_idx at l0[k] + c, start_idx + 1 at
+// l1[k] + c - the levels of the fields for elmk_phenology, two months of the phenology series for elmk_run
+struct PhenologySrc {
+  dfield l0[RUN_NPHEN], l1[RUN_NPHEN];
+};
+
+// phenology_physics_impl.hh:22-69, one column: the body of k_phenology and of its run-mode variant
+__device__ __forceinline__ void phenology_col(const DevState* __restrict__ S, int64_t c, double wt1, double wt2, const PhenologySrc& src)
 {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t ld = S->ld;
-  if (c >= S->ncols) return;
   constexpr int noveg = 0, nbrdlf_dcd_brl_shrub = 11;  // elm_constants.h:56,67
   const int vtype = S->vtype[c];
   double tlai = 0.0, tsai = 0.0, htop = 0.0, hbot = 0.0;
   if (vtype != noveg) {
-    tlai = wt1 * LV(mlai, 0) + wt2 * LV(mlai, 1);
-    tsai = wt1 * LV(msai, 0) + wt2 * LV(msai, 1);
-    htop = wt1 * LV(mhtop, 0) + wt2 * LV(mhtop, 1);
-    hbot = wt1 * LV(mhbot, 0) + wt2 * LV(mhbot, 1);
+    tlai = wt1 * SV(0, 0) + wt2 * SV(0, 1);
+    tsai = wt1 * SV(1, 0) + wt2 * SV(1, 1);
+    htop = wt1 * SV(2, 0) + wt2 * SV(2, 1);
+    hbot = wt1 * SV(3, 0) + wt2 * SV(3, 1);
   }
   S->tlai[c] = tlai;
   S->tsai[c] = tsai;
@@ -138,6 +147,68 @@ __global__ __launch_bounds__(256) void k_phenology(const DevState* __restrict__ 
   S->frac_veg_nosno_alb[c] = ((elai + esai) >= 0.05) ? 1 : 0;
 }
 
+__global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict__ S, const ForcingWeights W)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const ForcingSrc src{{S->atm_tbot, S->atm_pbot, S->atm_qbot, S->atm_flds, S->atm_fsds, S->atm_prec, S->atm_wind},
+                       {S->atm_tbot + ld, S->atm_pbot + ld, S->atm_qbot + ld, S->atm_flds + ld, S->atm_fsds + ld, S->atm_prec + ld,
+                        S->atm_wind + ld}};
+  get_forcing_col(S, c, W, src);
+}
+
+__global__ __launch_bounds__(256) void k_phenology(const DevState* __restrict__ S, double wt1, double wt2)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const PhenologySrc src{{S->mlai, S->msai, S->mhtop, S->mhbot}, {S->mlai + ld, S->msai + ld, S->mhtop + ld, S->mhbot + ld}};
+  phenology_col(S, c, wt1, wt2, src);
+}
+
+// elmk_run: the weights and the records of the step's row of the step table, from the series (elmk_api.cpp: elmk_run_reserve)
+__global__ __launch_bounds__(256) void k_get_forcing_run(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                         const int32_t* __restrict__ cursor, const dfield forc, int slots, int qbot_is_rh)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const RunRow* __restrict__ r = rows + *cursor;
+  ForcingWeights W;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    W.wt1[i] = r->forc_wt1[i];
+    W.wt2[i] = r->forc_wt2[i];
+  }
+  W.qbot_is_rh = qbot_is_rh;
+  const int64_t slot = r->forc_slot;
+  ForcingSrc src;
+#pragma unroll
+  for (int k = 0; k < RUN_NFORC; k++) {
+    src.l0[k] = forc + ((int64_t)k * slots + slot) * ld;
+    src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ld;
+  }
+  get_forcing_col(S, c, W, src);
+}
+
+__global__ __launch_bounds__(256) void k_phenology_run(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                       const int32_t* __restrict__ cursor, const dfield phen)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const RunRow* __restrict__ r = rows + *cursor;
+  const int64_t m1 = r->month1, m2 = r->month2;
+  PhenologySrc src;
+#pragma unroll
+  for (int k = 0; k < RUN_NPHEN; k++) {
+    src.l0[k] = phen + ((int64_t)k * RUN_NMONTH + m1) * ld;
+    src.l1[k] = phen + ((int64_t)k * RUN_NMONTH + m2) * ld;
+  }
+  phenology_col(S, c, r->month_wt1, r->month_wt2, src);
+}
+
 void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const double* wt2, int qbot_is_rh, hipStream_t st)
 {
   if (n <= 0) return;
@@ -154,6 +225,21 @@ void launch_phenology(const DevState* S, int64_t n, double wt1, double wt2, hipS
 {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_phenology, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, wt1, wt2);
+}
+
+void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
+                            int qbot_is_rh, hipStream_t st)
+{
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_get_forcing_run, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, rows, cursor,
+                     field_of<ELMK_F64>::from(const_cast<void*>(forc)), slots, qbot_is_rh);
+}
+
+void launch_phenology_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* phen, hipStream_t st)
+{
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_phenology_run, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, rows, cursor,
+                     field_of<ELMK_F64>::from(const_cast<void*>(phen)));
 }
 
 }  // namespace elmk

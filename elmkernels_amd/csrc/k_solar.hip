@@ -10,10 +10,9 @@
 
 namespace elmk {
 
-__global__ __launch_bounds__(256) void k_solar_geometry(const DevState* __restrict__ S, const elmk_solar_step p)
+// one column of one step: the body of k_solar_geometry and of its run-mode variant
+__device__ __forceinline__ void solar_geometry_col(const DevState* __restrict__ S, int64_t c, const elmk_solar_step& p)
 {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= S->ncols) return;
   const int64_t ld = S->ld;
   double g[ELMK_GEO_N];
 #pragma unroll
@@ -25,9 +24,31 @@ __global__ __launch_bounds__(256) void k_solar_geometry(const DevState* __restri
   S->col_dayl[(int64_t)COL_DAYL_FACTOR * ld + c] = dayl_factor;
 }
 
+__global__ __launch_bounds__(256) void k_solar_geometry(const DevState* __restrict__ S, const elmk_solar_step p)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= S->ncols) return;
+  solar_geometry_col(S, c, p);
+}
+
+// elmk_run: the step's scalars from its row of the step table
+__global__ __launch_bounds__(256) void k_solar_geometry_run(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                            const int32_t* __restrict__ cursor)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= S->ncols) return;
+  const elmk_solar_step p = rows[*cursor].sol;
+  solar_geometry_col(S, c, p);
+}
+
 void launch_solar_geometry(const DevState* S, int64_t n, const elmk_solar_step& p, hipStream_t st)
 {
   if (n > 0) hipLaunchKernelGGL(k_solar_geometry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, p);
+}
+
+void launch_solar_geometry_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, hipStream_t st)
+{
+  if (n > 0) hipLaunchKernelGGL(k_solar_geometry_run, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, rows, cursor);
 }
 
 }  // namespace elmk

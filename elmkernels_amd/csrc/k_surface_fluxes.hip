@@ -234,7 +234,8 @@ __global__ __launch_bounds__(256) void k_cons_reduce1(const double* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void k_cons_reduce2(const double* __restrict__ part, int nblk, double* __restrict__ out)
+// stage 2 in one workgroup of 256 threads per diagnostic: the body of k_cons_reduce2 and of its run-mode variant
+__device__ __forceinline__ void cons_reduce2_block(const double* __restrict__ part, int nblk, double* __restrict__ out)
 {
   __shared__ double s_min[256], s_max[256], s_sum[256];
   const int k = blockIdx.x;
@@ -262,6 +263,25 @@ __global__ __launch_bounds__(256) void k_cons_reduce2(const double* __restrict__
     out[k * 3 + 1] = s_max[0];
     out[k * 3 + 2] = s_sum[0];
   }
+}
+
+__global__ __launch_bounds__(256) void k_cons_reduce2(const double* __restrict__ part, int nblk, double* __restrict__ out)
+{
+  cons_reduce2_block(part, nblk, out);
+}
+
+// elmk_run: the triples to ring row *cursor ([row][8][3]); the first thread also opens the step's row of the flag rings, which
+// k_flag_reduce_run (launched after this kernel) ORs / mins into
+__global__ __launch_bounds__(256) void k_cons_reduce2_run(const double* __restrict__ part, int nblk, double* __restrict__ ring,
+                                                          uint32_t* __restrict__ flag_or, long long* __restrict__ flag_first,
+                                                          const int32_t* __restrict__ cursor)
+{
+  const int64_t row = *cursor;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    flag_or[row] = 0u;
+    flag_first[row] = 0x7fffffffffffffffll;
+  }
+  cons_reduce2_block(part, nblk, ring + row * (NDIAG * 3));
 }
 
 // ---- the per-column kernel of kokkos_init_timestep (init_timestep_kokkos.cc:55-75): h2osno_old, the column water
@@ -311,6 +331,15 @@ void launch_conservation(const DevState* S, int64_t n, int64_t ld, double dt, co
   hipLaunchKernelGGL(k_conservation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, dt);
   hipLaunchKernelGGL(k_cons_reduce1, dim3(ELMK_CONS_NPART, NDIAG), dim3(256), 0, st, diag, ld, n, part);
   hipLaunchKernelGGL(k_cons_reduce2, dim3(NDIAG), dim3(256), 0, st, part, ELMK_CONS_NPART, out);
+}
+
+void launch_conservation_run(const DevState* S, int64_t n, int64_t ld, double dt, const double* diag, double* part, double* cons_ring,
+                             uint32_t* flag_or, long long* flag_first, const int32_t* cursor, hipStream_t st)
+{
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_conservation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, dt);
+  hipLaunchKernelGGL(k_cons_reduce1, dim3(ELMK_CONS_NPART, NDIAG), dim3(256), 0, st, diag, ld, n, part);
+  hipLaunchKernelGGL(k_cons_reduce2_run, dim3(NDIAG), dim3(256), 0, st, part, ELMK_CONS_NPART, cons_ring, flag_or, flag_first, cursor);
 }
 
 }  // namespace elmk

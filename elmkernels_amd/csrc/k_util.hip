@@ -158,8 +158,9 @@ void launch_tile(void* field, int dtype, int nlev, int64_t ld, int64_t ncols, in
 // ---------------------------------------------------------------------------------------------------
 // OR of all flag words + first column carrying a fatal bit
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_flag_reduce(const uint32_t* __restrict__ flags, int64_t n, uint32_t* or_out,
-                                                     long long* first_bad)
+// OR of the flag words and the first column with a fatal bit, into *or_out / *first_bad: the body of k_flag_reduce and of its
+// run-mode variant
+__device__ __forceinline__ void flag_reduce_grid(const uint32_t* __restrict__ flags, int64_t n, uint32_t* or_out, long long* first_bad)
 {
   uint32_t acc = 0;
   long long first = 0x7fffffffffffffffll;
@@ -180,6 +181,23 @@ __global__ __launch_bounds__(256) void k_flag_reduce(const uint32_t* __restrict_
   }
 }
 
+__global__ __launch_bounds__(256) void k_flag_reduce(const uint32_t* __restrict__ flags, int64_t n, uint32_t* or_out,
+                                                     long long* first_bad)
+{
+  flag_reduce_grid(flags, n, or_out, first_bad);
+}
+
+// elmk_run: into ring row *cursor (opened by k_cons_reduce2_run earlier in the step)
+__global__ __launch_bounds__(256) void k_flag_reduce_run(const uint32_t* __restrict__ flags, int64_t n, uint32_t* flag_or,
+                                                         long long* flag_first, const int32_t* __restrict__ cursor)
+{
+  const int64_t row = *cursor;
+  flag_reduce_grid(flags, n, flag_or + row, flag_first + row);
+}
+
+// elmk_run: the last node of every step moves the step cursor to the next row of the step table
+__global__ void k_run_next(int32_t* cursor) { *cursor += 1; }
+
 void launch_flag_reduce(const uint32_t* flags, int64_t n, uint32_t* or_out, long long* first_bad, hipStream_t st)
 {
   if (n <= 0) return;
@@ -187,6 +205,17 @@ void launch_flag_reduce(const uint32_t* flags, int64_t n, uint32_t* or_out, long
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(k_flag_reduce, dim3((unsigned)blocks), dim3(256), 0, st, flags, n, or_out, first_bad);
 }
+
+void launch_flag_reduce_run(const uint32_t* flags, int64_t n, uint32_t* flag_or, long long* flag_first, const int32_t* cursor,
+                            hipStream_t st)
+{
+  if (n <= 0) return;
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_flag_reduce_run, dim3((unsigned)blocks), dim3(256), 0, st, flags, n, flag_or, flag_first, cursor);
+}
+
+void launch_run_next(int32_t* cursor, hipStream_t st) { hipLaunchKernelGGL(k_run_next, dim3(1), dim3(1), 0, st, cursor); }
 
 // ---------------------------------------------------------------------------------------------------
 // streaming copy with the same access shape as the physics kernels (8 bytes per lane): empirical HBM line

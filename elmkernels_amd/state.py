@@ -21,6 +21,13 @@ OPT_CF_HALF_WORKGROUPS = 1  # elmk_set_option
 HIST_AVG, HIST_SUM, HIST_MAX, HIST_MIN, HIST_INST = range(5)  # elmk_history_add
 HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, "inst": HIST_INST}
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
+RUN_QBOT_IS_RH, RUN_HISTORY = 1, 2  # elmk_run flags
+# elmk_run_step of include/elmk.h, field for field (natural C alignment: tests/test_run_host.py checks it against gcc)
+RUN_STEP_DTYPE = np.dtype([("decday", np.float64), ("doy", np.int32), ("forc_slot", np.int32), ("forc_wt1", np.float64, (8,)),
+                           ("forc_wt2", np.float64, (8,)), ("month1", np.int32), ("month2", np.int32), ("month_wt1", np.float64),
+                           ("month_wt2", np.float64)], align=True)
+SERIES_FORCING = ("atm_tbot", "atm_pbot", "atm_qbot", "atm_flds", "atm_fsds", "atm_prec", "atm_wind")
+SERIES_PHENOLOGY = ("mlai", "msai", "mhtop", "mhbot")
 
 # member order of ELM::PFTDataPSN (src/data/pft_data.h:20-24)
 PSN_FIELDS = (
@@ -343,6 +350,34 @@ class ELMState:
         self._chk(self.lib.elmk_history_clear(self.ctx), "history_clear")
         self._hist_nlev.clear()
 
+    # -- multi-step runs (include/elmk.h: elmk_run ...) ---------------------------------------------
+    def run_reserve(self, forcing_slots, max_steps):
+        """Device series of `forcing_slots` forcing records and 12 months, and step tables / diagnostics rings of `max_steps` rows."""
+        self._chk(self.lib.elmk_run_reserve(self.ctx, int(forcing_slots), int(max_steps)), "run_reserve")
+        self._run_max = int(max_steps)
+
+    def series_upload(self, name, slot0, records, col0=0):
+        """Records [slot0, slot0 + nslots) of one series field (SERIES_FORCING: forcing slots, SERIES_PHENOLOGY: months 0..11) from
+        records [nslots, n] (record-major), columns [col0, col0 + n).  Waits for a run in flight only if it reads those records."""
+        a = np.ascontiguousarray(records, dtype=np.float64)
+        if a.ndim == 1:
+            a = a[None, :]
+        self._chk(self.lib.elmk_series_upload(self.ctx, self.fields[name][0], int(slot0), a.shape[0], a.ctypes.data_as(C.c_void_p),
+                                              int(col0), a.shape[1]), f"series_upload({name})")
+
+    def run(self, dt, steps, flags=0):
+        """elmk_run: len(steps) model steps on the device, steps a RUN_STEP_DTYPE array; stream-ordered, no synchronisation."""
+        a = np.ascontiguousarray(steps, dtype=RUN_STEP_DTYPE)
+        self._chk(self.lib.elmk_run(self.ctx, float(dt), a.ctypes.data_as(C.c_void_p), int(a.size), int(flags)), "run")
+
+    def run_diagnostics(self):
+        """Of the last run (synchronises): conservation (min, max, sum) [nsteps, 8, 3], flag OR [nsteps], first fatal column [nsteps]."""
+        m = max(getattr(self, "_run_max", 0), 1)
+        mms, fo, fb = np.zeros((m, 8, 3)), np.zeros(m, np.uint32), np.zeros(m, np.int64)
+        n = self._chk(self.lib.elmk_run_diagnostics(self.ctx, mms.ctypes.data_as(C.c_void_p), fo.ctypes.data_as(C.c_void_p),
+                                                    fb.ctypes.data_as(C.c_void_p)), "run_diagnostics")
+        return mms[:n].copy(), fo[:n].copy(), fb[:n].copy()
+
     def math_eval(self, fn, x, y=None):
         """elmk_math.h on the device: fn in MATH_FNS; returns fn(x), x / y or pow(x, y)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -535,6 +570,22 @@ class ELMInterface:
         flags, col = S.error_summary()
         if flags & 0xC7FF:  # ELMK_ERR_FATAL_MASK
             raise RuntimeError(f"ELM physics error flags {flags:#x}, first at column {col}")
+        return False
+
+    def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False):
+        """ELMInterface::advance for every row of steps (RUN_STEP_DTYPE) in one call (elmk_run; needs S.run_reserve and the series
+        uploaded); self.conservation = the last step's triples, self.run_conservation = all of them.  Raises after the run if a step
+        raised a fatal flag, naming the first such step and column."""
+        S = self.S
+        flags = (RUN_HISTORY if accumulate_history else 0) | (RUN_QBOT_IS_RH if qbot_is_rh else 0)
+        S.run(dt_seconds, steps, flags)
+        mms, fo, fb = S.run_diagnostics()
+        self.run_conservation = mms
+        self.conservation = mms[-1]
+        bad = np.nonzero(fo & 0xC7FF)[0]  # ELMK_ERR_FATAL_MASK
+        if bad.size:
+            s = int(bad[0])
+            raise RuntimeError(f"ELM physics error flags {int(fo[s]):#x} in step {s} of the run, first at column {int(fb[s])}")
         return False
 
     def accumulate_history(self):

@@ -39,6 +39,7 @@
  *   kokkos_surface_fluxes(S,dt)     surface_fluxes_kokkos.hh          elmk_surface_fluxes
  *   kokkos_evaluate_conservation    conserved_quantity_kokkos.hh      elmk_evaluate_conservation
  *   (ELM's history tapes: time averages, extremes, last values)       elmk_history_add / _accumulate / _read
+ *   kokkos_driver.cc:54-85 time loop                                  elmk_run (elmk_run_reserve, elmk_series_upload)
  *   throw / assert inside physics   (list: SURVEY.md section 5)       per-column flag word, elmk_error_summary
  *
  * Conventions
@@ -272,6 +273,50 @@ int elmk_history_reset(elmk_ctx *ctx, int tape);
 int elmk_history_count(elmk_ctx *ctx, int tape, int64_t *nsamples);
 int elmk_history_read(elmk_ctx *ctx, int entry, double *host, int64_t col0, int64_t n, int layout);
 int elmk_history_clear(elmk_ctx *ctx);
+
+/* ---- multi-step runs ------------------------------------------------------------------------
+ * The reference's driver time loop (kokkos_driver.cc:54-85: one ELMInterface::advance per step) as one call: the forcing and
+ * phenology records stay on the device as series, the host sends the schedule of N steps in one copy, and nothing in the run
+ * synchronises with the host.
+ *   elmk_run_reserve     allocates everything a run needs (counted in elmk_device_bytes): the forcing series (atm_tbot .. atm_wind x
+ *                        forcing_slots records), the phenology series (mlai, msai, mhtop, mhbot x 12 months), two step tables of
+ *                        max_steps rows and two diagnostics rings.  Series start at 0.  Calling it again waits for the runs in
+ *                        flight and re-reserves (the series contents are lost).  forcing_slots >= 2, max_steps >= 1.
+ *   elmk_series_upload   records [slot0, slot0 + nslots) of one series field - ELMK_FIELD_atm_tbot .. ELMK_FIELD_atm_wind (slots
+ *                        0 .. forcing_slots-1) or ELMK_FIELD_mlai .. ELMK_FIELD_mhbot (slots = months 0 .. 11) - columns [col0, col0+n)
+ *                        from host[nslots][n] (record-major: AtmDataManager::data(ntimes, ncells)); stored at state precision
+ *                        (rounded as elmk_upload rounds in libelmk_f32.so).  The copy runs on an internal stream, so it overlaps a
+ *                        run in flight; it first waits for any enqueued, unfinished run that reads one of the slots it writes.
+ *                        Returns when the copy is done.
+ *   elmk_run             for each step s, the bits of the calls
+ *                          elmk_solar_geometry(dt, decday, doy); elmk_phenology(month_wt1, month_wt2) over months month1 / month2;
+ *                          elmk_get_forcing(forc_wt1, forc_wt2, flags & ELMK_RUN_QBOT_IS_RH) over slots forc_slot / forc_slot + 1;
+ *                          elmk_init_timestep; elmk_advance_physics(dt); elmk_evaluate_conservation -> ring row s;
+ *                          elmk_error_summary -> ring row s (flags sticky, as that call sees them after the step);
+ *                          with ELMK_RUN_HISTORY: elmk_history_accumulate.
+ *                        Stream-ordered, returns without synchronising; with elmk_set_graph one step is captured once (one chain of
+ *                        nodes) and replayed nsteps times.  Enters per-column solar mode (as elmk_solar_geometry does).  Needs a
+ *                        column geography, the snow-age tables and elmk_run_reserve.  ELMK_E_INVALID, before anything is enqueued,
+ *                        for nsteps outside 1 .. max_steps, dt not finite and positive, a forc_slot outside 0 .. forcing_slots-2,
+ *                        a month outside 0 .. 11, unknown flags, a stream being captured.  A run reads neither atm_* nor
+ *                        mlai .. mhbot.  The step tables are double-buffered: run k+1 may be enqueued while run k executes;
+ *                        enqueuing run k+2 waits until run k has finished.
+ *   elmk_run_diagnostics synchronises, then copies the rows of the most recently enqueued run (any pointer may be NULL):
+ *                        min_max_sum[nsteps][8][3] as elmk_evaluate_conservation, flags_or[nsteps] and first_bad_col[nsteps] (-1: none)
+ *                        as elmk_error_summary.  Returns that run's nsteps (0 before the first run). */
+typedef struct {
+  double decday;                    /* decimal_doy(step start) + 1.0, as elmk_solar_geometry */
+  int32_t doy;                      /* date.doy of the step start */
+  int32_t forc_slot;                /* series slot of forcing record t_idx; slot forc_slot + 1 holds t_idx + 1 */
+  double forc_wt1[8], forc_wt2[8];  /* as elmk_get_forcing (TBOT PBOT QBOT|RH FLDS FSDS PREC WIND ZBOT) */
+  int32_t month1, month2;           /* phenology months 0 .. 11 bracketing the step (monthly_data.cc:29-37) */
+  double month_wt1, month_wt2;      /* monthly_data.cc:56-62 */
+} elmk_run_step;
+enum { ELMK_RUN_QBOT_IS_RH = 1, ELMK_RUN_HISTORY = 2 };
+int elmk_run_reserve(elmk_ctx *ctx, int forcing_slots, int max_steps);
+int elmk_series_upload(elmk_ctx *ctx, int field, int slot0, int nslots, const double *host, int64_t col0, int64_t n);
+int elmk_run(elmk_ctx *ctx, double dt, const elmk_run_step *steps, int nsteps, int flags);
+int elmk_run_diagnostics(elmk_ctx *ctx, double *min_max_sum, uint32_t *flags_or, int64_t *first_bad_col);
 
 /* ---- the physics wrappers (same names, order and arguments as driver/kokkos) ---------------- */
 int elmk_frac_wet(elmk_ctx *ctx);

@@ -229,6 +229,50 @@ class ELMInterface {
   void history_read(int entry, double* host) { ok(elmk_history_read(ctx_, entry, host, 0, ncols_, ELMK_LAYOUT_COL_MAJOR)); }
   void history_clear() { ok(elmk_history_clear(ctx_)); }
 
+  /* Multi-step runs (elmk_run): the driver's time loop on the device.  reserve_run() once; the forcing records (atm_* fields, slots
+   * 0 .. forcing_slots-1) and the 12 months of mlai .. mhbot go up as series, host[nslots][ncols], record-major; run() then does
+   * advance() (the overload with solar geometry) for every row of the schedule, with no host round trip between steps, and throws if
+   * a step raised a fatal flag.  enqueue_run() + finish_run() split run() in two: a series_upload() of records the run does not read
+   * overlaps the run in between.  conservation() is the last step's triples, run_conservation() all of them ([nsteps][8][3]). */
+  void reserve_run(int forcing_slots, int max_steps)
+  {
+    ok(elmk_run_reserve(ctx_, forcing_slots, max_steps));
+    max_steps_ = max_steps;
+  }
+  void series_upload(const char* field, int slot0, int nslots, const double* host)
+  {
+    ok(elmk_series_upload(ctx_, id(field), slot0, nslots, host, 0, ncols_));
+  }
+  void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false)
+  {
+    ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(), (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0)));
+  }
+  bool finish_run()
+  {
+    const size_t m = (size_t)std::max(max_steps_, 1);
+    std::vector<double> cons(m * 24);
+    std::vector<uint32_t> flags(m);
+    std::vector<int64_t> first(m);
+    const int n = elmk_run_diagnostics(ctx_, cons.data(), flags.data(), first.data());
+    ok(n < 0 ? n : ELMK_OK);
+    run_conservation_.assign(cons.begin(), cons.begin() + (size_t)n * 24);
+    if (n > 0) {  // (kept even when a step failed, as the Python mirror keeps them)
+      std::copy(run_conservation_.end() - 24, run_conservation_.end(), &conservation_[0][0]);
+      last_flags_ = flags[(size_t)n - 1];
+    }
+    for (int s = 0; s < n; s++)
+      if (flags[(size_t)s] & ELMK_ERR_FATAL_MASK)
+        throw std::runtime_error("ELM physics error flags " + std::to_string(flags[(size_t)s]) + " in step " + std::to_string(s) +
+                                 " of the run, first at column " + std::to_string(first[(size_t)s]));
+    return false;
+  }
+  bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false)
+  {
+    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh);
+    return finish_run();
+  }
+  const std::vector<double>& run_conservation() const { return run_conservation_; }
+
   /* ELMInterface::copyPrimaryVars / getPrimaryVars (elm_kokkos_interface.cc:324-356) */
   void copyPrimaryVars(PrimaryVars& pv)
   {
@@ -280,6 +324,8 @@ class ELMInterface {
   int64_t ncols_{0};
   double conservation_[8][3]{};
   uint32_t last_flags_{0};
+  int max_steps_{0};
+  std::vector<double> run_conservation_;
 };
 
 }  // namespace elmk

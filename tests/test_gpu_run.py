@@ -1,0 +1,441 @@
+"""Multi-step runs on the device (elmk_run, include/elmk.h "multi-step runs"): every run is compared bit for bit with the same steps
+driven through the existing calls ("stepwise": the atm_* and mlai .. mhbot fields uploaded from the same host records before every
+step, elmk_solar_geometry, elmk_phenology, elmk_get_forcing, elmk_init_timestep, elmk_advance_physics, then
+elmk_evaluate_conservation and elmk_error_summary after every step)."""
+import ctypes as C
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from elmkernels_amd import _lib as L
+from elmkernels_amd import state as st
+from elmkernels_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+DT = 1800.0
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SERIES = st.SERIES_FORCING + st.SERIES_PHENOLOGY
+NREC = 10  # hourly forcing records
+NSTEPS = 12  # half-hour steps: forcing slots 0 .. 6
+
+
+def same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def _inputs(n, seed, nrec=NREC):
+    """State, geography, nrec hourly records per forcing stream and 12 months per phenology field, all [records, n]."""
+    ft = st.field_table()
+    cols, scal, soil = synth.make_state(ft, n, tier="B", seed=seed)
+    lat, lon = synth.global_grid(n, seed=seed + 1)
+    rng = np.random.default_rng(seed + 2)
+    rec = {}
+    for k in st.SERIES_FORCING:
+        a, b = cols[k][:, 0], cols[k][:, 1]
+        t = np.linspace(0.0, 1.0, nrec)[:, None]
+        rec[k] = (1.0 - t) * a[None, :] + t * b[None, :] + 0.01 * np.abs(a)[None, :] * rng.standard_normal((nrec, n))
+    # long-wave: both branches of ProcessFLDS (<= 50, >= 600) in some columns of some records
+    m = rng.random((nrec, n))
+    rec["atm_flds"] = np.where(m < 0.05, 30.0, np.where(m > 0.95, 700.0, rec["atm_flds"]))
+    rec["atm_prec"] = np.where(rng.random((nrec, n)) < 0.3, 0.0, np.abs(rec["atm_prec"]))  # some dry records
+    rec["atm_fsds"] = np.abs(rec["atm_fsds"])
+    for k in st.SERIES_PHENOLOGY:
+        base = cols[k][:, 0]
+        rec[k] = np.abs(base[None, :] * (1.0 + 0.1 * rng.standard_normal((12, n))))
+    return cols, scal, soil, lat, lon, rec
+
+
+def schedule(nsteps=NSTEPS, slot0=0):
+    """Half-hour steps from 21:00 of day 13: crosses midnight; the month bracket moves from (11, 0) to (0, 1) half way; distinct
+    weights for every stream."""
+    S = np.zeros(nsteps, st.RUN_STEP_DTYPE)
+    for s in range(nsteps):
+        ddoy = 13.875 + s * DT / 86400.0
+        S[s]["decday"] = ddoy + 1.0
+        S[s]["doy"] = int(ddoy)
+        S[s]["forc_slot"] = slot0 + s // 2
+        e = (s % 2) * 0.5 + 0.25
+        w2 = np.clip(e + 0.03 * np.arange(8) - 0.1, 0.0, 1.0)
+        S[s]["forc_wt2"] = w2
+        S[s]["forc_wt1"] = 1.0 - w2
+        if s < nsteps // 2:
+            S[s]["month1"], S[s]["month2"], S[s]["month_wt1"] = 11, 0, 0.3 - 0.01 * s
+        else:
+            S[s]["month1"], S[s]["month2"], S[s]["month_wt1"] = 0, 1, 0.9 - 0.01 * s
+        S[s]["month_wt2"] = 1.0 - S[s]["month_wt1"]
+    return S
+
+
+def _device(cols, scal, soil, lat, lon, lib_path=None):
+    n = next(iter(cols.values())).shape[0]
+    D = st.ELMState(n, lib_path=lib_path)
+    pft, optics = synth.load_params()
+    D.set_pft(pft)
+    D.set_snicar(optics)
+    D.set_soilcolor(soil["albsat"], soil["albdry"])
+    D.set_land(**synth.TEST_LAND)
+    D.set_scalars(**scal)
+    D.set_snow_age_tables(synth.snow_age_tables())
+    for k, v in cols.items():
+        D.upload(k, v)
+    D.set_column_geography(lat, lon)
+    return D
+
+
+def stepwise(D, rec, steps, qbot_is_rh=False, history=False, rec_late=None, late_from=None):
+    """The existing calls; returns conservation [nsteps, 8, 3], flags [nsteps], first [nsteps].  rec_late: the records from step
+    late_from on."""
+    cons, fo, fb = [], [], []
+    for s, p in enumerate(steps):
+        R = rec_late if (rec_late is not None and s >= late_from) else rec
+        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
+        f = int(p["forc_slot"])
+        for k in st.SERIES_FORCING:
+            D.upload(k, np.stack([R[k][f], R[k][f + 1]], axis=1))
+        for k in st.SERIES_PHENOLOGY:
+            D.upload(k, np.stack([R[k][p["month1"]], R[k][p["month2"]]], axis=1))
+        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
+        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], qbot_is_rh)
+        st.kokkos_init_timestep(D)
+        st.advance_physics(D, DT)
+        cons.append(st.kokkos_evaluate_conservation(D, DT))
+        flags, first = D.error_summary()
+        fo.append(flags)
+        fb.append(first)
+        if history:
+            D.history_accumulate()
+    return np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)
+
+
+def upload_series(D, rec, forc_slots=None):
+    for k in st.SERIES_FORCING:
+        sl = range(rec[k].shape[0]) if forc_slots is None else forc_slots
+        D.series_upload(k, sl[0], rec[k][sl[0]:sl[-1] + 1])
+    for k in st.SERIES_PHENOLOGY:
+        D.series_upload(k, 0, rec[k])
+
+
+def assert_same_state(A, B, cols):
+    """Every field but the series inputs bit for bit; the series inputs of the run context (B) untouched."""
+    for name in A.fields:
+        if name in SERIES:
+            assert same(B[name], np.ascontiguousarray(cols[name], dtype=B[name].dtype)), name
+        else:
+            assert same(A[name], B[name]), name
+
+
+def assert_same_rows(got, want):
+    for g, w in zip(got, want):
+        assert same(g, w)
+
+
+@pytest.fixture(scope="module")
+def base():
+    return _inputs(5003, 71)
+
+
+def _pair(base, graph=True, lib_path=None):
+    cols, scal, soil, lat, lon, rec = base
+    A = _device(cols, scal, soil, lat, lon, lib_path)
+    B = _device(cols, scal, soil, lat, lon, lib_path)
+    A.set_graph(graph)
+    B.set_graph(graph)
+    assert A.level_stride != A.ncols
+    return A, B
+
+
+def test_run_equals_stepwise_graph_on(base):
+    """Twelve steps as one elmk_run replayed from one captured step: state, err_flags, conservation and flag rows bit for bit."""
+    cols, _, _, _, _, rec = base
+    A, B = _pair(base)
+    steps = schedule()
+    want = stepwise(A, rec, steps)
+    B.run_reserve(NREC, NSTEPS)
+    upload_series(B, rec)
+    B.run(DT, steps)
+    got = B.run_diagnostics()
+    assert_same_rows(got, want)
+    assert_same_state(A, B, cols)
+    assert len(np.unique(want[0][:, 6, 2])) > 1  # the steps differ
+    A.close()
+    B.close()
+
+
+def test_graph_off_equals_graph_on(base):
+    cols, _, _, _, _, rec = base
+    A, B = _pair(base, graph=False)
+    B.set_graph(True)
+    steps = schedule()
+    for D in (A, B):
+        D.run_reserve(NREC, NSTEPS)
+        upload_series(D, rec)
+        D.run(DT, steps)
+    assert_same_rows(A.run_diagnostics(), B.run_diagnostics())
+    for name in A.fields:
+        assert same(A[name], B[name]), name
+    A.close()
+    B.close()
+
+
+def test_two_runs_with_an_upload_between_equal_one_run(base):
+    """Runs of 5 + 7 steps enqueued back to back: between them the second window is uploaded, and slot 3 - which the first run
+    reads - is replaced by new values.  The upload must wait for the first run, so that the first run sees the old record and the
+    second the new one, as the stepwise reference does.  (An upload that did not wait would most likely land before the first run's
+    last steps read slot 3 and change their bits; the check relies on that timing, it cannot force it.)"""
+    cols, _, _, _, _, rec = base
+    A, B = _pair(base)
+    steps = schedule()
+    late = {k: v.copy() for k, v in rec.items()}
+    for k in st.SERIES_FORCING:
+        late[k][3] = rec[k][3] * 1.001 + (30.0 if k == "atm_flds" else 0.0)
+    want = stepwise(A, rec, steps, rec_late=late, late_from=5)
+    B.run_reserve(NREC, 8)
+    upload_series(B, rec, forc_slots=range(0, 4))  # steps 0..4 read slots 0..3
+    B.run(DT, steps[:5])
+    for k in st.SERIES_FORCING:
+        B.series_upload(k, 3, late[k][3:NREC])  # slot 3 (read by the run in flight) and the second window
+    B.run(DT, steps[5:])
+    got = B.run_diagnostics()
+    assert_same_rows(got, tuple(w[5:] for w in want))
+    assert_same_state(A, B, cols)
+    A.close()
+    B.close()
+
+
+def test_third_run_keeps_the_first_runs_records(base):
+    """Three runs of 4 steps enqueued back to back without a sync (the third reuses the first one's step table), then slots 0 and
+    1 - read by the first run only - are replaced by other values: the upload may not write under the first run, so all twelve
+    steps give the stepwise bits of the original records."""
+    cols, _, _, _, _, rec = base
+    A, B = _pair(base)
+    steps = schedule()
+    want = stepwise(A, rec, steps)
+    B.run_reserve(NREC, 4)
+    upload_series(B, rec)
+    for r in range(3):
+        B.run(DT, steps[4 * r:4 * r + 4])  # slots read: 0..2, 2..4, 4..6
+    for k in st.SERIES_FORCING:
+        B.series_upload(k, 0, rec[k][0:2] * 0.5 + (40.0 if k == "atm_flds" else 0.0))
+    got = B.run_diagnostics()
+    assert_same_rows(got, tuple(w[8:] for w in want))
+    assert_same_state(A, B, cols)
+    A.close()
+    B.close()
+
+
+ENTRIES = [(0, "t_grnd", "avg"), (0, "eflx_sh_tot", "sum"), (1, "t_grnd", "max"), (1, "h2osoi_liq", "min"), (2, "snl", "inst"),
+           (2, "t_soisno", "avg")]
+
+
+def test_history_option_equals_stepwise_accumulate(base):
+    cols, _, _, _, _, rec = base
+    A, B = _pair(base)
+    ids = [[D.history_add(t, f, op) for t, f, op in ENTRIES] for D in (A, B)]
+    steps = schedule()
+    stepwise(A, rec, steps, history=True)
+    B.run_reserve(NREC, NSTEPS)
+    upload_series(B, rec)
+    B.run(DT, steps, st.RUN_HISTORY)
+    for a, b in zip(*ids):
+        assert same(A.history_read(a), B.history_read(b))
+    for t in range(3):
+        assert A.history_count(t) == B.history_count(t) == NSTEPS
+    assert_same_state(A, B, cols)
+    A.close()
+    B.close()
+
+
+def test_qbot_is_rh_option_equals_stepwise(base):
+    cols, _, _, _, _, rec = base
+    rec = dict(rec)
+    rec["atm_qbot"] = np.clip(rec["atm_qbot"] * 5000.0, 5.0, 100.0)  # relative humidity, percent
+    A, B = _pair(base)
+    steps = schedule()
+    want = stepwise(A, rec, steps, qbot_is_rh=True)
+    B.run_reserve(NREC, NSTEPS)
+    upload_series(B, rec)
+    B.run(DT, steps, st.RUN_QBOT_IS_RH)
+    assert_same_rows(B.run_diagnostics(), want)
+    assert_same_state(A, B, cols)
+    A.close()
+    B.close()
+
+
+def _hip_runtime():
+    """The HIP runtime this process already uses (loaded by libelmk)."""
+    L.load()
+    path = next((ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64.so" in ln), None)
+    assert path, "libamdhip64 is not loaded"
+    hip = C.CDLL(path)
+    P = C.c_void_p
+    for name, args in (("hipStreamCreateWithFlags", [C.POINTER(P), C.c_uint]), ("hipStreamBeginCapture", [P, C.c_int]),
+                       ("hipStreamEndCapture", [P, C.POINTER(P)]), ("hipGraphDestroy", [P]), ("hipStreamDestroy", [P])):
+        getattr(hip, name).argtypes = args
+        getattr(hip, name).restype = C.c_int
+    return hip
+
+
+def test_refusals_enqueue_nothing(base):
+    """Every refusal of elmk_run returns ELMK_E_INVALID, and after each one a valid run from the same starting state (restored
+    from a snapshot of every field) still gives the bits of the stepwise run."""
+    cols, _, _, _, _, rec = base
+    A, B = _pair(base)
+    steps = schedule()
+    want = stepwise(A, rec, steps)
+    want_state = {name: A[name] for name in A.fields if name not in SERIES}
+    B.snapshot_fields(list(B.fields))
+
+    def refused(dt, s, flags=0):
+        a = np.ascontiguousarray(s, dtype=st.RUN_STEP_DTYPE)
+        return B.lib.elmk_run(B.ctx, float(dt), a.ctypes.data_as(C.c_void_p), int(a.size), int(flags)) == -1
+
+    def valid_run_still_gives_the_bits(what):
+        B.restore_fields()
+        B.run(DT, steps)
+        assert_same_rows(B.run_diagnostics(), want)
+        for name, v in want_state.items():
+            assert same(B[name], v), (what, name)
+        for name in SERIES:
+            assert same(B[name], np.ascontiguousarray(cols[name], dtype=B[name].dtype)), (what, name)
+
+    assert refused(DT, steps)  # not reserved
+    B.run_reserve(NREC, NSTEPS)
+    upload_series(B, rec)
+    assert B.run_diagnostics()[0].shape == (0, 8, 3)  # no run was ever enqueued
+    valid_run_still_gives_the_bits("not reserved")
+    cases = [("nsteps 0", DT, steps[:0], 0), ("nsteps > max_steps", DT, np.concatenate([steps, steps[:1]]), 0)]
+    cases += [(f"dt {dt}", dt, steps, 0) for dt in (0.0, -DT, float("nan"), float("inf"))]
+    for slot in (-1, NREC - 1):
+        s = steps.copy()
+        s[4]["forc_slot"] = slot
+        cases.append((f"forc_slot {slot}", DT, s, 0))
+    for f in ("month1", "month2"):
+        for m in (-1, 12):
+            s = steps.copy()
+            s[7][f] = m
+            cases.append((f"{f} {m}", DT, s, 0))
+    cases.append(("flags 4", DT, steps, 4))
+    for what, dt, s, flags in cases:
+        assert refused(dt, s, flags), what
+        valid_run_still_gives_the_bits(what)
+    hip = _hip_runtime()
+    strm, graph = C.c_void_p(), C.c_void_p()
+    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
+    B.set_stream(strm.value)
+    assert hip.hipStreamBeginCapture(strm, 1) == 0
+    rc = refused(DT, steps)
+    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    assert rc
+    if graph.value:
+        hip.hipGraphDestroy(graph)
+    B.set_stream(None)
+    hip.hipStreamDestroy(strm)
+    valid_run_still_gives_the_bits("stream being captured")
+    A.close()
+    B.close()
+
+
+@pytest.mark.parametrize("half", [False, True])
+def test_large_launch_run_equals_stepwise(half):
+    """262 144 columns (the benchmark's launch structure), three steps; ELMK_OPT_CF_HALF_WORKGROUPS off and on."""
+    cols, scal, soil, lat, lon, rec = _inputs(262144, 72)
+    A = _device(cols, scal, soil, lat, lon)
+    B = _device(cols, scal, soil, lat, lon)
+    for D in (A, B):
+        D.set_graph(True)
+        D.set_option(st.OPT_CF_HALF_WORKGROUPS, int(half))
+    steps = schedule(3)
+    want = stepwise(A, rec, steps)
+    B.run_reserve(NREC, 3)
+    upload_series(B, rec)
+    B.run(DT, steps)
+    assert_same_rows(B.run_diagnostics(), want)
+    assert_same_state(A, B, cols)
+    A.close()
+    B.close()
+
+
+def test_fp32_state_library():
+    cols, scal, soil, lat, lon, rec = _inputs(2053, 73)
+    A = _device(cols, scal, soil, lat, lon, L.F32_LIB_PATH)
+    B = _device(cols, scal, soil, lat, lon, L.F32_LIB_PATH)
+    assert B.lib.elmk_state_real_bytes() == 4
+    steps = schedule()
+    want = stepwise(A, rec, steps)
+    B.run_reserve(NREC, NSTEPS)
+    upload_series(B, rec)
+    B.run(DT, steps)
+    assert_same_rows(B.run_diagnostics(), want)
+    for name in A.fields:
+        if name in SERIES:
+            assert same(B[name], np.ascontiguousarray(cols[name], dtype=B[name].dtype).astype(np.float32).astype(B[name].dtype)), name
+        else:
+            assert same(A[name], B[name]), name
+    A.close()
+    B.close()
+
+
+def test_run_demo(tmp_path):
+    """examples/run_demo.cc (48 half-hour steps over 25 hourly records as two runs of 24, the second window uploaded during the
+    first run) writes the PrimaryVars and the 48 conservation rows of the stepwise run, bit for bit."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    n, nsteps = 3008, 48
+    cols, scal, soil, lat, lon, rec = _inputs(n, 74, nrec=25)
+    steps = schedule(nsteps)
+    libdir = os.path.dirname(L.LIB_PATH)
+    exe = str(tmp_path / "run_demo")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "run_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
+    from tests import helpers as H
+
+    S = H.oracle_state(cols, scal, soil)
+    blob = [struct.pack("<q", n)]
+
+    def put(name, kind, arr):
+        a = np.ascontiguousarray(arr)
+        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
+
+    for k, v in S.fields.items():
+        if k != "err_flags":
+            put(k, 0, v)
+    sc = S.scalars
+    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
+    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
+    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
+        put(k, 1, getattr(S, k))
+    for i, name in enumerate(L.SNICAR_NAMES):
+        put(f"snicar/{i}", 1, S.snicar[name])
+    put("age_tau", 1, S.snowage[0])
+    put("age_kappa", 1, S.snowage[1])
+    put("age_drdt0", 1, S.snowage[2])
+    put("lat", 1, lat)
+    put("lon", 1, lon)
+    for k in SERIES:
+        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
+    put("steps", 1, steps)
+    (tmp_path / "state.bin").write_bytes(b"".join(blob))
+    r = subprocess.run([exe, str(tmp_path / "state.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "48 steps" in r.stdout, r.stdout
+    # the same steps through the Python layer, stepwise
+    D = _device(cols, scal, soil, lat, lon)
+    D.set_graph(True)
+    cons, _, _ = stepwise(D, rec, steps)
+    raw = (tmp_path / "out.bin").read_bytes()
+    off = 0
+    for name in st.ELMInterface.PRIMARY_VARS:
+        want = D[name]
+        got = np.frombuffer(raw, want.dtype, want.size, off).reshape(want.shape)
+        off += want.nbytes
+        assert same(got, want), name
+    got = np.frombuffer(raw, np.float64, nsteps * 24, off).reshape(nsteps, 8, 3)
+    assert same(got, cons)
+    assert off + nsteps * 24 * 8 == len(raw)
+    D.close()
