@@ -295,12 +295,13 @@ __device__ __forceinline__ AlbIn alb_final_inputs(const DevState* __restrict__ S
     x.albsoi[0] = LV(albsoi, 0);
     x.albsoi[1] = LV(albsoi, 1);
     if (h2osno_in > SN_MIN_SNW) {
+      // the SNICAR products are read once, by column: nontemporal loads (k_alb_final -5 %, profiles/r04_scratch_nt_ab.txt)
       const gptr<const double> o = S->alb_snow + c;
       x.snicar = true;
-      x.sd_alb[0] = sc_ld<1>(o);
-      x.sd_alb[1] = sc_ld<1>(o + ld);
-      x.si_alb[0] = sc_ld<1>(o + (int64_t)14 * ld);
-      x.si_alb[1] = sc_ld<1>(o + (int64_t)15 * ld);
+      x.sd_alb[0] = __builtin_nontemporal_load(o);
+      x.sd_alb[1] = __builtin_nontemporal_load(o + ld);
+      x.si_alb[0] = __builtin_nontemporal_load(o + (int64_t)14 * ld);
+      x.si_alb[1] = __builtin_nontemporal_load(o + (int64_t)15 * ld);
     } else if (h2osno_in < SN_MIN_SNW && h2osno_in > 0.0) {
       // no snow radiative transfer: snow_albedo_radiation_factor's remaining branches (snow_snicar_impl.hh:758-765)
       x.sd_alb[0] = x.si_alb[0] = x.albsoi[0];
@@ -314,15 +315,15 @@ __device__ __forceinline__ AlbIn alb_final_inputs(const DevState* __restrict__ S
 __device__ __forceinline__ void alb_flux_abs_all(const DevState* __restrict__ S, const int64_t c, const int64_t ld, const Land& L,
                                                  const AlbIn& x, double (&flx)[6][4])
 {
-  const gptr<const double> o = S->alb_snow + c;
+  const gptr<const double> o = S->alb_snow + c;  // (nontemporal loads: see alb_final_inputs)
 #pragma unroll
   for (int i = 0; i < 6; i++) {
     double sdf[2] = {0.0, 0.0}, sif[2] = {0.0, 0.0};
     if (x.snicar) {
-      sdf[0] = sc_ld<1>(o + (int64_t)(2 + 2 * i) * ld);
-      sdf[1] = sc_ld<1>(o + (int64_t)(3 + 2 * i) * ld);
-      sif[0] = sc_ld<1>(o + (int64_t)(16 + 2 * i) * ld);
-      sif[1] = sc_ld<1>(o + (int64_t)(17 + 2 * i) * ld);
+      sdf[0] = __builtin_nontemporal_load(o + (int64_t)(2 + 2 * i) * ld);
+      sdf[1] = __builtin_nontemporal_load(o + (int64_t)(3 + 2 * i) * ld);
+      sif[0] = __builtin_nontemporal_load(o + (int64_t)(16 + 2 * i) * ld);
+      sif[1] = __builtin_nontemporal_load(o + (int64_t)(17 + 2 * i) * ld);
     }
     alb_flux_abs_level(L, x.day, x.frac_sno, x.albsod, x.albsoi, x.sd_alb, x.si_alb, sdf, sif, flx[i][0], flx[i][1], flx[i][2], flx[i][3]);
     LV(flx_absdv, i) = flx[i][0];

@@ -33,14 +33,16 @@ struct SideStreams {
 
 // the seven physics launches (one per reference L3 wrapper)
 void launch_frac_wet(const DevState* S, int64_t n, hipStream_t st);
-// classify = false: the caller has run stage 1 (soil albedo, SNICAR queues) itself (the fused step does it in k_fz_prep)
-// final = false: the caller runs stage 3 (k_alb_final's body) itself (the fused step's k_fz_stream)
-void launch_albedo_snicar(const DevState* S, int64_t n, hipStream_t st, const SideStreams* side, bool classify = true, bool final = true);
-void launch_albedo_snicar_part(const DevState* S, int64_t n, hipStream_t st, int part, unsigned* snicar_grid);
+// fused: stage 2 only - the fused step runs stage 1 (soil albedo, SNICAR queues) in k_fz_prep and stage 3 (k_alb_final's body)
+// in k_fz_stream
+void launch_albedo_snicar(const DevState* S, int64_t n, hipStream_t st, const SideStreams* side, bool fused = false);
+unsigned launch_albedo_snicar_part(const DevState* S, int64_t n, hipStream_t st);
 void launch_canopy_hydrology(const DevState* S, int64_t n, double dt, hipStream_t st);
 void launch_surface_radiation(const DevState* S, int64_t n, hipStream_t st);
 void launch_canopy_temperature(const DevState* S, int64_t n, hipStream_t st);
-// given (bit 0 forc_rho, bit 1 forc_po2, bit 2 forc_pco2): the L2-level entries elmk_*_given take these from DevState::cf_given
+// given (bit 0 forc_rho, bit 1 forc_po2, bit 2 forc_pco2): the L2-level entries elmk_*_given take these from DevState::cf_given.
+// GIVEN_FUSED, outside the mask, tells k_bg_flux that it runs in the fused step (launch_bareground_list; see k_water_energy.hip)
+constexpr int GIVEN_FUSED = 1 << 8;
 void launch_bareground_fluxes(const DevState* S, int64_t n, hipStream_t st, int given = 0);
 void launch_canopy_fluxes(const DevState* S, int64_t n, double dt, hipStream_t st, int given = 0, const SideStreams* side = nullptr);
 // elmk_timestep7_fused: the same seven wrappers as five launch groups (k_canopy_fluxes.hip):

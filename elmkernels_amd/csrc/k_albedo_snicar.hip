@@ -38,10 +38,9 @@ namespace elmk {
 // stage 1 (coalesced, every column): canopy_layer_lai, soil albedo of the sunlit columns, and the classification of
 // the sunlit snow-covered columns by their number of snow layers (lists LIST_ALB_1..5)
 // =====================================================================================================
-#ifndef ALB_CLASSIFY_THREADS
-#define ALB_CLASSIFY_THREADS 1024  // one atomic per workgroup and non-empty queue: with 256-thread workgroups the 3 907 atomics on
-                                   // ONE counter (the fixture-tiled tier fills a single queue) were the kernel's whole time (57 us)
-#endif
+// one atomic per workgroup and non-empty queue: with 256-thread workgroups the 3 907 atomics on ONE counter (the fixture-tiled
+// tier fills a single queue) were the kernel's whole time (57 us; profiles/r03_classify_atomics_ab.txt)
+constexpr int ALB_CLASSIFY_THREADS = 1024;
 __global__ __launch_bounds__(ALB_CLASSIFY_THREADS) void k_alb_classify(const DevState* __restrict__ S)
 {
   const Land L = S->land;
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(256, 2) void k_alb_snicar(const DevState* __restric
 {
   snicar_workgroup<NL>(S, blockIdx.x, gridDim.x);
 }
-// the queue of NL >= 2 layers
+// the queue of NL >= 2 layers (fewer than 262 144 columns: see launch_albedo_snicar)
 template <int NL>
 static void launch_snicar_deep(const DevState* S, const unsigned capped, const int64_t n, hipStream_t st)
 {
@@ -76,13 +75,9 @@ static void launch_snicar_deep(const DevState* S, const unsigned capped, const i
 // The four queues of 5..2 layers as ONE launch: the first `per_queue` workgroups take the five-layer queue, the next the
 // four-layer queue, ...; every launch costs ~4.5 us whether its queue holds columns or not (four empty queues on a snow-free
 // region were 18 us of the wrapper), and a queue's tail overlaps the next queue's start.  The price: one register allocation
-// for all (the five-layer body's), which takes the two-layer queue from three waves per SIMD to two.
-#ifndef ALB_DEEP_MERGED
-#define ALB_DEEP_MERGED 1
-#endif
-#ifndef ALB_DEEP_PER_QUEUE
-#define ALB_DEEP_PER_QUEUE 1024
-#endif
+// for all (the five-layer body's), which takes the two-layer queue from three waves per SIMD to two
+// (merged launch: profiles/r03_snicar_deep_merged_ab.txt).
+constexpr int ALB_DEEP_PER_QUEUE = 1024;
 __global__ __launch_bounds__(256, 2) void k_alb_snicar_deep(const DevState* __restrict__ S, const unsigned per_queue)
 {
   const unsigned q = blockIdx.x / per_queue, b = blockIdx.x - q * per_queue;
@@ -93,19 +88,12 @@ __global__ __launch_bounds__(256, 2) void k_alb_snicar_deep(const DevState* __re
     default: snicar_workgroup<2>(S, b, per_queue);
   }
 }
-static void launch_snicar_deep_all(const DevState* S, const unsigned capped, const int64_t n, hipStream_t st)
+static void launch_snicar_deep_all(const DevState* S, const unsigned capped, hipStream_t st)
 {
-  if (ALB_DEEP_MERGED) {
-    // (workgroups walk their queue with a stride, so fewer of them do the same work; an empty queue costs what its workgroups
-    //  cost to dispatch - 16 384 of them 14 us, 4 096 the 4.7 us of any launch)
-    const unsigned per_queue = capped < (unsigned)ALB_DEEP_PER_QUEUE ? capped : (unsigned)ALB_DEEP_PER_QUEUE;
-    hipLaunchKernelGGL(k_alb_snicar_deep, dim3(4u * per_queue), dim3(256), 0, st, S, per_queue);
-  } else {
-    launch_snicar_deep<5>(S, capped, n, st);
-    launch_snicar_deep<4>(S, capped, n, st);
-    launch_snicar_deep<3>(S, capped, n, st);
-    launch_snicar_deep<2>(S, capped, n, st);
-  }
+  // (workgroups walk their queue with a stride, so fewer of them do the same work; an empty queue costs what its workgroups
+  //  cost to dispatch - 16 384 of them 14 us, 4 096 the 4.7 us of any launch)
+  const unsigned per_queue = capped < (unsigned)ALB_DEEP_PER_QUEUE ? capped : (unsigned)ALB_DEEP_PER_QUEUE;
+  hipLaunchKernelGGL(k_alb_snicar_deep, dim3(4u * per_queue), dim3(256), 0, st, S, per_queue);
 }
 
 // =====================================================================================================
@@ -133,7 +121,7 @@ __global__ __launch_bounds__(256) void k_alb_final(const DevState* __restrict__ 
   alb_two_stream(S, c, ld, L, x.day, x.coszen, x.elai, x.esai, x.vcmaxcintsun, x.vcmaxcintsha, a);
 }
 
-void launch_albedo_snicar(const DevState* S, int64_t n, hipStream_t st, const SideStreams* side, bool classify, bool final)
+void launch_albedo_snicar(const DevState* S, int64_t n, hipStream_t st, const SideStreams* side, bool fused)
 {
   if (n <= 0) return;
   const dim3 block(256);
@@ -141,52 +129,49 @@ void launch_albedo_snicar(const DevState* S, int64_t n, hipStream_t st, const Si
   // stage 2 is grid-stride over a device-side count: 24 columns per workgroup
   const unsigned want = (unsigned)((n + 23) / 24);
   const unsigned capped = want < 4096u ? want : 4096u;
-  if (classify)
+  if (!fused)
     hipLaunchKernelGGL(k_alb_classify, dim3((unsigned)((n + ALB_CLASSIFY_THREADS - 1) / ALB_CLASSIFY_THREADS)), dim3(ALB_CLASSIFY_THREADS), 0, st, S);
   // The five layer-count queues are independent.  (One persistent launch draining all five lists through a chunk counter
   // was measured 30 % slower: every wave then pays the deepest list's register footprint, and the five unrolled bodies
   // compete for the instruction cache.)  With many columns every non-empty queue fills the GPU by itself and an empty one
   // costs a few microseconds, so the launches simply follow each other; the fork and join through side streams cost
   // ~35 us of dependency latency per call and only pay when the queues are too short to fill the machine.
-  if (n >= 262144) {
-    launch_snicar_deep_all(S, capped, n, st);
-    hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, st, S);
-  } else if (side->one_stream) {  // (graph capture: the same five queues one after another on the caller's stream)
-    launch_snicar_deep<5>(S, capped, n, st);
-    launch_snicar_deep<4>(S, capped, n, st);
-    launch_snicar_deep<3>(S, capped, n, st);
-    launch_snicar_deep<2>(S, capped, n, st);
-    hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, st, S);
-  } else {
-    (void)hipEventRecord(side->fork, st);
-    for (int i = 0; i < 4; i++) (void)hipStreamWaitEvent(side->s[i], side->fork, 0);
-    launch_snicar_deep<5>(S, capped, n, st);  // longest work on the caller's stream
-    launch_snicar_deep<4>(S, capped, n, side->s[0]);
-    launch_snicar_deep<3>(S, capped, n, side->s[1]);
-    launch_snicar_deep<2>(S, capped, n, side->s[2]);
-    hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, side->s[3], S);
-    for (int i = 0; i < 4; i++) {
-      (void)hipEventRecord(side->join[i], side->s[i]);
-      (void)hipStreamWaitEvent(st, side->join[i], 0);
+  if (n < 262144) {
+    if (side->one_stream) {  // (graph capture: the same five queues one after another on the caller's stream)
+      launch_snicar_deep<5>(S, capped, n, st);
+      launch_snicar_deep<4>(S, capped, n, st);
+      launch_snicar_deep<3>(S, capped, n, st);
+      launch_snicar_deep<2>(S, capped, n, st);
+      hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, st, S);
+    } else {
+      (void)hipEventRecord(side->fork, st);
+      for (int i = 0; i < 4; i++) (void)hipStreamWaitEvent(side->s[i], side->fork, 0);
+      launch_snicar_deep<5>(S, capped, n, st);  // longest work on the caller's stream
+      launch_snicar_deep<4>(S, capped, n, side->s[0]);
+      launch_snicar_deep<3>(S, capped, n, side->s[1]);
+      launch_snicar_deep<2>(S, capped, n, side->s[2]);
+      hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, side->s[3], S);
+      for (int i = 0; i < 4; i++) {
+        (void)hipEventRecord(side->join[i], side->s[i]);
+        (void)hipStreamWaitEvent(st, side->join[i], 0);
+      }
     }
+  } else {
+    launch_snicar_deep_all(S, capped, st);
+    hipLaunchKernelGGL(k_alb_snicar<1>, dim3(capped), block, 0, st, S);
   }
-  if (final) hipLaunchKernelGGL(k_alb_final, dim3(full), block, 0, st, S);
+  if (!fused) hipLaunchKernelGGL(k_alb_final, dim3(full), block, 0, st, S);
 }
 
-// The same stage in two parts around a kernel of the caller's that does the single-layer SNICAR queue itself (the fused step's
-// k_fz_snicar_pre): part 0 = the queues of 5..2 layers, part 1 = k_alb_final.  *snicar_grid: the grid k_alb_snicar<1> would get.
-void launch_albedo_snicar_part(const DevState* S, int64_t n, hipStream_t st, int part, unsigned* snicar_grid)
+// Stage 2 for a fused step of 262 144 columns or more, whose k_fz_snicar_pre does the single-layer SNICAR queue itself: the
+// queues of 5..2 layers.  Returns the grid k_alb_snicar<1> would get.
+unsigned launch_albedo_snicar_part(const DevState* S, int64_t n, hipStream_t st)
 {
-  if (n <= 0) return;
-  const dim3 block(256);
+  if (n <= 0) return 0u;
   const unsigned want = (unsigned)((n + 23) / 24);
   const unsigned capped = want < 4096u ? want : 4096u;
-  if (snicar_grid) *snicar_grid = capped;
-  if (part == 0) {
-    launch_snicar_deep_all(S, capped, n, st);
-  } else {
-    hipLaunchKernelGGL(k_alb_final, dim3((unsigned)((n + 255) / 256)), block, 0, st, S);
-  }
+  launch_snicar_deep_all(S, capped, st);
+  return capped;
 }
 
 }  // namespace elmk

@@ -180,11 +180,8 @@ __device__ __forceinline__ double ci_func(double ci, CiCtx& k)
   return ci - k.cair + k.an * k.forc_pbot * (1.4 * k.gs_mol + 1.6 * k.gb_mol) / (k.gb_mol * k.gs_mol);
 }
 
-// photosynthesis_impl.hh:396-511
-#ifndef CF_BRENT_ATTR
-#define CF_BRENT_ATTR __forceinline__  // not a call: see the note at psn_hybrid
-#endif
-__device__ CF_BRENT_ATTR double psn_brent(double x1, double x2, double f1, double f2, double tol, CiCtx& k)
+// photosynthesis_impl.hh:396-511 (inlined, not a call: see the note at psn_hybrid)
+__device__ __forceinline__ double psn_brent(double x1, double x2, double f1, double f2, double tol, CiCtx& k)
 {
   const int ITMAX = 20;
   const double EPS = 1.0e-2;
@@ -509,9 +506,6 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long m, int r)
   }
   return idx;
 }
-#ifndef CF_PAIR_PHASES
-#define CF_PAIR_PHASES 1  // 0: every lane runs both solves of its column itself, whatever the wave holds (development A/B)
-#endif
 
 // =====================================================================================================
 // Launch structure.  The leaf-temperature iteration has data-dependent trip counts (3..41) and is fp64-compute
@@ -527,16 +521,9 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long m, int r)
 //                it converges, stores the converged state at the queue position and takes the next position
 //   k_cf_finish  coalesced, one thread per column: compute_flux (:456-540), the 2 m profile, state writes
 // =====================================================================================================
-#ifndef CF_REFILL_MIN_N
-#define CF_REFILL_MIN_N 8  // (12 / 16 / 24 measured in round 4: profiles/r04_cf_refill_min_ab.txt)
-#endif
-constexpr int CF_REFILL_MIN = CF_REFILL_MIN_N;
-#ifndef CF_PRIO_LEVEL
-#define CF_PRIO_LEVEL 2  // s_setprio of a wave that carries a column past CF_PRIO_TRIPS trips (3 measured: profiles/r04_cf_phase_pairing_ab.txt)
-#endif
-#ifndef CF_PRIO_TRIPS
-#define CF_PRIO_TRIPS 10  // trips after which a column makes its wave a priority wave (k_cf_iterate)
-#endif
+constexpr int CF_REFILL_MIN = 8;   // (12 / 16 / 24 measured in round 4: profiles/r04_cf_refill_min_ab.txt)
+constexpr int CF_PRIO_LEVEL = 2;   // s_setprio of a wave that carries a column past CF_PRIO_TRIPS trips (3 measured: profiles/r04_cf_phase_pairing_ab.txt)
+constexpr int CF_PRIO_TRIPS = 10;  // trips after which a column makes its wave a priority wave (k_cf_iterate)
 constexpr int CF_BLOCK_EXTRA = 24;  // queue positions a wave claims beyond what a refill needs (its private block)
 // Measured and dropped in round 3 (profiles/r03_cf_probe_two_*_queue_tier*.txt): separating day from night waves.  With one
 // head, day before night, every wave crosses from day to night columns mid-kernel and runs a dozen trips at the price of a day
@@ -587,36 +574,17 @@ enum : int {
 #undef X
   FIN_COUNT
 };
-// Records are stored in blocks of 8 consecutive queue positions: block b holds field k of positions 8b..8b+7 at
-// [b][k][0..7] (64 contiguous bytes), so all fields of neighbouring positions share a few DRAM pages, a refill batch
-// of consecutive positions reads 64-byte runs, and the writers' partial runs merge in L2.
-// CF_REC_AOS / CF_FIN_AOS (profiles/r04_record_layout_ab.txt): a record as CF_*_N consecutive doubles at its position - every
-// lane reads or writes ONE contiguous run (16-byte accesses), whatever positions its neighbours hold.  The FINISH record is
-// written by single lanes as they converge, trips apart from their neighbours: in blocks of 8 positions its 8-byte stores
-// left half-written 64-byte runs behind (PMC: 403 bytes written per column for 192 of payload); per position the kernel writes
-// 199 and the step moves 286 bytes per column less at the same time (k_cf_iterate -0.5 %, k_cf_finish +0.5 %): the product.
-// The INPUT record is written by k_cf_init / k_fz_stream, whose neighbouring threads hold neighbouring positions: per position
-// every wave store would go to 64 different lines (k_cf_init x 2) - it stays in blocks of 8.
-#ifndef CF_REC_AOS
-#define CF_REC_AOS 0
-#endif
-#ifndef CF_FIN_AOS
-#define CF_FIN_AOS 1
-#endif
-#if CF_REC_AOS
-#define CF_REC_BASE(pos) ((pos) * (int64_t)CF_REC_N)
-#define CF_REC_K(k) (k)
-#else
+// The INPUT record is written by k_cf_init / k_fz_stream, whose neighbouring threads hold neighbouring positions, so it is
+// stored in blocks of 8 consecutive queue positions: block b holds field k of positions 8b..8b+7 at [b][k][0..7] (64
+// contiguous bytes), so all fields of neighbouring positions share a few DRAM pages, a refill batch of consecutive positions
+// reads 64-byte runs, and the writers' partial runs merge in L2 (per position: k_cf_init x 2, profiles/r04_record_layout_ab.txt).
+// The FINISH record is written by single lanes as they converge, trips apart from their neighbours, so it is stored as CF_FIN_N
+// consecutive doubles at its position: ONE contiguous run per lane (in blocks of 8: 403 bytes written per column for 192 of
+// payload, per position 199, at the same time: profiles/r04_record_layout_ab.txt).
+// Both are plain loads and stores: with the nontemporal hint k_cf_init +65 %, k_cf_finish +70 % (profiles/r04_scratch_nt_ab.txt).
 #define CF_REC_BASE(pos) (((pos) >> 3) * (int64_t)(CF_REC_N * 8) + ((pos)&7))
 #define CF_REC_K(k) ((k)*8)
-#endif
-#if CF_FIN_AOS
 #define CF_FIN_BASE(pos) ((pos) * (int64_t)CF_FIN_N)
-#define CF_FIN_K(k) (k)
-#else
-#define CF_FIN_BASE(pos) (((pos) >> 3) * (int64_t)(CF_FIN_N * 8) + ((pos)&7))
-#define CF_FIN_K(k) ((k)*8)
-#endif
 static_assert(REC_COUNT == CF_REC_N && FIN_COUNT == CF_FIN_N, "record sizes in elmk_dev.h out of date");
 enum : int { IREC_vtype = 0, IREC_nrad, IREC_fvn };
 constexpr int IREC_FVN_SAME_TQ = 1 << 8;  // in the IREC_fvn word: forc_hgt_q_patch == forc_hgt_t_patch (friction_velocity_humidity's short-cut)
@@ -660,10 +628,7 @@ __device__ __forceinline__ int cf_class(const DevState* __restrict__ S, const La
 
 // One workgroup counts CF_COUNT_TILES tiles of 256 columns (a tile = one workgroup of k_cf_init) and takes the
 // slices of all of them with ONE atomic per class: the class totals are 12 addresses, every atomic on them serialises.
-#ifndef CF_COUNT_TILES_N
-#define CF_COUNT_TILES_N 4
-#endif
-constexpr int CF_COUNT_TILES = CF_COUNT_TILES_N;
+constexpr int CF_COUNT_TILES = 4;
 // (256 x CF_COUNT_TILES threads: the tiles of a workgroup are counted side by side, four waves each - one after the other
 //  their loads were four dependent round trips)
 __global__ __launch_bounds__(256 * CF_COUNT_TILES) void k_cf_count(const DevState* __restrict__ S)
@@ -787,11 +752,11 @@ __device__ __forceinline__ void cf_root_stress_col(const DevState* __restrict__ 
     LV(rootr, i) = q;
   }
   S->btran[c] = btran;
-  sc_st<4>(S->cf_rec + CF_REC_BASE(pos) + CF_REC_K(REC_btran), btran);
+  S->cf_rec[CF_REC_BASE(pos) + CF_REC_K(REC_btran)] = btran;
 }
 
-// ROOT_DONE: the fused step's early kernel (k_fz_pre) has already done cf_root_stress_col and the bare branch's rootr / btran
-template <bool FUSED, bool ROOT_DONE = false>
+// FUSED: the fused step's early kernel (k_fz_pre) has already done cf_root_stress_col and the bare branch's rootr / btran
+template <bool FUSED>
 __device__ __forceinline__ void cf_init_col(const DevState* __restrict__ S, const int64_t c, const int64_t ld, const Land& L,
                                             const int64_t pos, const ColFwd& w, const int given = 0)
 {
@@ -800,7 +765,7 @@ __device__ __forceinline__ void cf_init_col(const DevState* __restrict__ S, cons
     S->cf_niter[c] &= (int32_t)0xFFFF0000;  // trips of this call: 0 (not vegetated); the scheduling hint stays
     if (!L.urbpoi) {
       S->t_veg[c] = FW(forc_tbot, S->forc_tbot[c]);
-      if (!ROOT_DONE) {
+      if (!FUSED) {
         S->btran[c] = 0.0;
 #pragma unroll
         for (int i = 0; i < NLEVGRND; i++) LV(rootr, i) = 0.0;
@@ -814,11 +779,11 @@ __device__ __forceinline__ void cf_init_col(const DevState* __restrict__ S, cons
   // record fields are stored as soon as they are final (PUT), so few of them are live at any time
   CfRec r;
   const gptr<double> rec = S->cf_rec + CF_REC_BASE(pos);
-#define PUT(n) sc_st<4>(rec + CF_REC_K(REC_##n), r.n);
+#define PUT(n) rec[CF_REC_K(REC_##n)] = r.n;
   const int snl = FW(snl, S->snl[c]);
   const int vtype = S->vtype[c];
   const double* __restrict__ P = S->pft_psn[vtype];
-  if (!ROOT_DONE) cf_root_stress_col(S, c, ld, pos, LV(h2osoi_liq, NLEVSNO));
+  if (!FUSED) cf_root_stress_col(S, c, ld, pos, LV(h2osoi_liq, NLEVSNO));
   const double t_soi0 = LV(t_soisno, NLEVSNO);
   const double t_top = (snl > 0) ? LV(t_soisno, NLEVSNO - snl) : t_soi0;
 
@@ -1014,11 +979,8 @@ enum : int {
 #undef X
   CF_NLDS
 };
-#ifndef CF_ITER_THREADS_N
-#define CF_ITER_THREADS_N 512  // (256: one wave per SIMD, half the LDS - development, tests/tools/two_ctx_overlap.py)
-#endif
-constexpr int CF_ITER_THREADS = CF_ITER_THREADS_N;  // 8 waves = two per SIMD; one workgroup per CU shares one copy of the math tables
-constexpr int CF_ITER_THREADS_HALF = 256;           // k_cf_iterate_half: one wave per SIMD, 92 KB of LDS - room for other kernels beside it
+constexpr int CF_ITER_THREADS = 512;  // 8 waves = two per SIMD; one workgroup per CU shares one copy of the math tables
+constexpr int CF_ITER_THREADS_HALF = 256;  // k_cf_iterate_half: one wave per SIMD, 92 KB of LDS - room for other kernels beside it
 #define X(n)                                                                                              \
   template <class L> __device__ __forceinline__ double cf_get_##n(const CfRegs& R, const L* s, int t) { return R.n; } \
   template <class L> __device__ __forceinline__ void cf_set_##n(CfRegs& R, L* s, int t, double v) { R.n = v; }
@@ -1146,7 +1108,7 @@ __device__ __forceinline__ void cf_iterate_body(const DevState* __restrict__ S, 
     if (fresh) {
       fresh = false;
       const gptr<const double> rec = S->cf_rec + CF_REC_BASE(pos);
-#define LD(n) sc_ld<4>(rec + CF_REC_K(REC_##n))
+#define LD(n) rec[CF_REC_K(REC_##n)]
       const gptr<const int32_t> irec = S->cf_irec + pos;
       const int vtype = irec[(int64_t)IREC_vtype * ld];
       nrad = irec[(int64_t)IREC_nrad * ld];
@@ -1340,7 +1302,7 @@ __device__ __forceinline__ void cf_iterate_body(const DevState* __restrict__ S, 
       const unsigned long long md = __ballot(dayl);
       const int nd = __popcll(md);
       if (nd != 0) {  // (wave-uniform)
-        const bool paired = CF_PAIR_PHASES && nd <= 32;
+        const bool paired = nd <= 32;  // (profiles/r04_cf_phase_pairing_ab.txt)
         // what the solve reads beside J / qsun, as this lane will hand it in: its own sunlit phase first
         double pb = has ? C(forc_pbot) : 0.0, rbi = rb, bt = btran_sun;
         double par = has ? C(parsun) : 0.0, lai = has ? C(lai_sun_z) : 0.0;
@@ -1541,30 +1503,30 @@ __device__ __forceinline__ void cf_iterate_body(const DevState* __restrict__ S, 
       // ---------------- converged: hand the state to k_cf_finish, release the lane ----------------
       if (stop) {
         const gptr<double> fin = S->cf_fin + CF_FIN_BASE(pos);
-        sc_st<4>(fin + CF_FIN_K(FIN_t_veg), t_veg);
-        sc_st<4>(fin + CF_FIN_K(FIN_btran), btran);
-        sc_st<4>(fin + CF_FIN_K(FIN_qflx_tran_veg), qflx_tran_veg);
-        sc_st<4>(fin + CF_FIN_K(FIN_qflx_evap_veg), qflx_evap_veg);
-        sc_st<4>(fin + CF_FIN_K(FIN_eflx_sh_veg), eflx_sh_veg);
-        sc_st<4>(fin + CF_FIN_K(FIN_wtg), wtg);
-        sc_st<4>(fin + CF_FIN_K(FIN_wtl0), wtl0);
-        sc_st<4>(fin + CF_FIN_K(FIN_wta0), wta0);
-        sc_st<4>(fin + CF_FIN_K(FIN_wtal), wtal);
-        sc_st<4>(fin + CF_FIN_K(FIN_wtgq), wtgq);
-        sc_st<4>(fin + CF_FIN_K(FIN_wtalq), wtalq);
-        sc_st<4>(fin + CF_FIN_K(FIN_wtlq0), wtlq0);
-        sc_st<4>(fin + CF_FIN_K(FIN_wtaq0), wtaq0);
-        sc_st<4>(fin + CF_FIN_K(FIN_delq), delq);
-        sc_st<4>(fin + CF_FIN_K(FIN_qsatl), qsatl);
-        sc_st<4>(fin + CF_FIN_K(FIN_temp1), temp1);
-        sc_st<4>(fin + CF_FIN_K(FIN_temp2), temp2);
-        sc_st<4>(fin + CF_FIN_K(FIN_dth), dth);
-        sc_st<4>(fin + CF_FIN_K(FIN_dqh), dqh);
-        sc_st<4>(fin + CF_FIN_K(FIN_tlbef), tlbef);
-        sc_st<4>(fin + CF_FIN_K(FIN_dt_veg), dt_veg);
-        sc_st<4>(fin + CF_FIN_K(FIN_obu_trip), obu_trip);
-        sc_st<4>(fin + CF_FIN_K(FIN_trips), (double)itlef);
-        sc_st<4>(fin + CF_FIN_K(FIN_err), (double)err);
+        fin[FIN_t_veg] = t_veg;
+        fin[FIN_btran] = btran;
+        fin[FIN_qflx_tran_veg] = qflx_tran_veg;
+        fin[FIN_qflx_evap_veg] = qflx_evap_veg;
+        fin[FIN_eflx_sh_veg] = eflx_sh_veg;
+        fin[FIN_wtg] = wtg;
+        fin[FIN_wtl0] = wtl0;
+        fin[FIN_wta0] = wta0;
+        fin[FIN_wtal] = wtal;
+        fin[FIN_wtgq] = wtgq;
+        fin[FIN_wtalq] = wtalq;
+        fin[FIN_wtlq0] = wtlq0;
+        fin[FIN_wtaq0] = wtaq0;
+        fin[FIN_delq] = delq;
+        fin[FIN_qsatl] = qsatl;
+        fin[FIN_temp1] = temp1;
+        fin[FIN_temp2] = temp2;
+        fin[FIN_dth] = dth;
+        fin[FIN_dqh] = dqh;
+        fin[FIN_tlbef] = tlbef;
+        fin[FIN_dt_veg] = dt_veg;
+        fin[FIN_obu_trip] = obu_trip;
+        fin[FIN_trips] = (double)itlef;
+        fin[FIN_err] = (double)err;
         pos = -1;
       }
       PR_T(8)
@@ -1664,7 +1626,7 @@ __global__ __launch_bounds__(256) void k_cf_finish(const DevState* __restrict__ 
   }
   CfFin f;
   const gptr<const double> fin = S->cf_fin + CF_FIN_BASE((int64_t)pos);
-#define X(n) f.n = sc_ld<4>(fin + CF_FIN_K(FIN_##n));
+#define X(n) f.n = fin[FIN_##n];
   CF_FIN_FIELDS(X)
 #undef X
   const double t_veg = f.t_veg;
@@ -1743,19 +1705,19 @@ __global__ __launch_bounds__(256) void k_cf_finish(const DevState* __restrict__ 
 //                is computed from inputs of the step (frac_veg_nosno, coszen, the incident visible flux, last call's trip
 //                hint), because the queue slices must exist before the streaming pass places its records, and it is
 //                stored per column so that count and placement agree by construction (a class only orders the queue: any
-//                consistent choice gives the same results)
-//   albedo       k_alb_classify -> k_alb_snicar<1..5> -> k_alb_final, unchanged: it reads snl / h2osno / frac_sno as they
-//                are BEFORE canopy_hydrology, so it cannot join the pass
-//   k_fz_stream  canopy_hydrology -> surface_radiation -> canopy_temperature -> bareground_fluxes' streaming stage (cgrnd*
-//                reset, list of bare columns) -> canopy_fluxes' initialize_flux + queue record, in the reference's order, by
-//                the bodies the separate kernels use (elmk_stream.h, cf_init_col); each later body takes what an earlier
-//                one produced from registers: t_soisno[20] and some 45 scalars per column are neither re-read nor waited for
+//                consistent choice gives the same results); and stage 1 of albedo (k_alb_classify's work)
+//   k_fz_pre     what of the pass depends on nothing albedo or canopy_hydrology produce (below); from 262 144 columns its
+//                tiles run inside k_fz_snicar_pre, beside the single-layer SNICAR queue
+//   albedo       k_alb_snicar<1..5>: SNICAR reads snl / h2osno / frac_sno as they are BEFORE canopy_hydrology, so it cannot
+//                join the pass
+//   k_fz_stream  canopy_hydrology -> albedo's stage 3 (k_alb_final's body) -> surface_radiation -> canopy_temperature ->
+//                bareground_fluxes' streaming stage (cgrnd* reset, list of bare columns) -> canopy_fluxes' initialize_flux +
+//                queue record, in the reference's order, by the bodies the separate kernels use (elmk_stream.h, cf_init_col);
+//                each later body takes what an earlier one produced from registers: t_soisno[20] and some 45 scalars per
+//                column are neither re-read nor waited for
 //   k_bg_flux, k_cf_iterate, k_cf_finish   as in the unfused step
 // =====================================================================================================
-#ifndef FZ_PREP_TILES_N
-#define FZ_PREP_TILES_N 4
-#endif
-constexpr int FZ_PREP_TILES = FZ_PREP_TILES_N;  // tiles of 256 columns per workgroup of k_fz_prep
+constexpr int FZ_PREP_TILES = 4;  // tiles of 256 columns per workgroup of k_fz_prep
 __global__ __launch_bounds__(256) void k_fz_prep(const DevState* __restrict__ S)
 {
   elmk_math_lds_init<false>();  // (frac_wet: one pow per column)
@@ -1837,9 +1799,10 @@ __global__ __launch_bounds__(256) void k_fz_prep(const DevState* __restrict__ S)
   }
 }
 
-// k_fz_pre - the part of the streaming pass that depends on nothing the albedo stage or canopy_hydrology produce, as a kernel
-// of its own that runs BESIDE the albedo stage on a side stream: SNICAR and the two-stream solution are bound by fp64 issue,
-// this kernel by HBM, and the two kinds of work share the CUs.  Per column: the queue position of the canopy_fluxes record,
+// k_fz_pre - the part of the streaming pass that depends on nothing the albedo stage or canopy_hydrology produce, taken out of
+// k_fz_stream so that it can share the CUs with SNICAR: SNICAR is bound by fp64 issue, this work by HBM.  From 262 144 columns
+// its tiles run inside k_fz_snicar_pre (below; profiles/r03_fused_split_ab.txt), under that as a kernel of its own in front of
+// the albedo stage.  Per column: the queue position of the canopy_fluxes record,
 // the root moisture stress of the 15 soil levels (soil_moist_stress: 105 level values read, rootr / eff_porosity written,
 // fifteen pow) and old_ground_temp's copy of the soil levels of t_soisno into tssbef - 1.4 KB of the 3.1 KB per column that
 // k_fz_stream used to move.  What lies between this kernel and k_fz_stream in the reference's call order touches none of it
@@ -1914,16 +1877,6 @@ __global__ __launch_bounds__(256, 2) void k_fz_snicar_pre(const DevState* __rest
   fz_pre_tile(S, (int64_t)idx);
 }
 
-#ifndef FZ_SNICAR_GRID_BY_TILES
-#define FZ_SNICAR_GRID_BY_TILES 1  // 0: k_alb_snicar<1>'s own grid for the SNICAR part of k_fz_snicar_pre (development A/B)
-#endif
-#ifndef FZ_SPLIT
-#define FZ_SPLIT 2  // 2: k_fz_pre's tiles share a kernel with the single-layer SNICAR queue (k_fz_snicar_pre); 1: k_fz_pre beside
-                    // the albedo stage on a side stream; 0: k_fz_stream does that work itself, as in round 2 (1, 0: development A/B)
-#endif
-#ifndef FZ_ALB_FWD
-#define FZ_ALB_FWD 1  // 0: k_alb_final as its own launch in front of k_fz_stream, as in round 3 (development A/B)
-#endif
 __global__ __launch_bounds__(256, 3) void k_fz_stream(const DevState* __restrict__ S, double dtime)
 {
   elmk_math_lds_init<false>();
@@ -1931,33 +1884,21 @@ __global__ __launch_bounds__(256, 3) void k_fz_stream(const DevState* __restrict
   const int64_t ld = S->ld;
   const Land L = S->land;
   const bool inside = c < S->ncols;
-#if !FZ_SPLIT
-  int64_t pos0 = -1;
-  if (!L.lakpoi) {
-    pos0 = cf_queue_position(S, inside ? (int)S->cf_cls[c] : -1);
-    if (inside) S->cf_pos[c] = (int32_t)pos0;
-  } else if (blockIdx.x == 0 && threadIdx.x == 0) {
-    ELMK_LIST_COUNT(S, LIST_CF_QUEUE) = 0u;
-  }
-#endif
   ColFwd w;
-#if FZ_ALB_FWD
   // Stage 3 of albedo_snicar (k_alb_final's body, elmk_albedo_fin.h) runs HERE, between canopy_hydrology and surface_radiation,
   // so that surface_radiation takes the 56 doubles it reads of that stage's outputs from registers instead of from the state
   // (-496 bytes per column and one launch less).  The reference runs albedo BEFORE canopy_hydrology (elm_kokkos_interface.cc:
   // 292-295), which changes two of its inputs - frac_sno and h2osno (snow_init, fraction_h2osfc) - so their values of before are
   // taken first; nothing else the stage reads (coszen, elai, esai, t_veg, fwet, the soil albedos, the SNICAR products) is written
-  // by canopy_hydrology, and nothing canopy_hydrology reads is written by the stage.
+  // by canopy_hydrology, and nothing canopy_hydrology reads is written by the stage (profiles/r04_albedo_forwarding_ab.txt).
   const bool alb_here = inside && !L.urbpoi;  // (kokkos_albedo_snicar does nothing on urban land units)
   const double frac_sno_before = alb_here ? (double)S->frac_sno[c] : 0.0, h2osno_before = alb_here ? (double)S->h2osno[c] : 0.0;
   if (blockIdx.x == 0 && threadIdx.x < 6) {  // (k_alb_final's job: the SNICAR queues are drained by now, leave them empty)
     ELMK_LIST_COUNT(S, LIST_ALB_0 + threadIdx.x) = 0u;
     ELMK_LIST_HEAD(S, LIST_ALB_0 + threadIdx.x) = 0u;
   }
-#endif
   canopy_hydrology_col<true>(S, c, ld, L, dtime, w, inside);  // (every thread: the pond solves are pooled per workgroup)
   if (inside) {
-#if FZ_ALB_FWD
     AlbFwd a;
     double flx[6][4];
     if (alb_here) {
@@ -1969,12 +1910,7 @@ __global__ __launch_bounds__(256, 3) void k_fz_stream(const DevState* __restrict
     } else {
       surface_radiation_col<true, false>(S, c, ld, L, w, a, flx);
     }
-#else
-    const AlbFwd a{};
-    const double flx[6][4] = {};
-    surface_radiation_col<true>(S, c, ld, L, w, a, flx);
-#endif
-    canopy_temperature_col<true, FZ_SPLIT != 0>(S, c, ld, L, w);
+    canopy_temperature_col<true>(S, c, ld, L, w);
   }
   // bareground_fluxes, streaming stage (k_bg_main): compute_flux's unconditional cgrnd reset and the list of bare columns
   if (!L.lakpoi) {
@@ -1986,24 +1922,8 @@ __global__ __launch_bounds__(256, 3) void k_fz_stream(const DevState* __restrict
     const bool bare = inside && !L.urbpoi && w.fvn == 0;
     block_classify_append<1>(S->lists, ld, S->counters, LIST_BG, bare ? 0 : -1, (int32_t)c);
     // canopy_fluxes up to the iteration (queue position and root moisture stress: k_fz_pre)
-    if (inside) cf_init_col<true, FZ_SPLIT != 0>(S, c, ld, L, (int64_t)S->cf_pos[c], w);
+    if (inside) cf_init_col<true>(S, c, ld, L, (int64_t)S->cf_pos[c], w);
   }
-}
-
-#ifndef FZ_BG_OVERLAP
-#define FZ_BG_OVERLAP 1
-#endif
-// Workgroups of the persistent k_cf_iterate: two per CU are launched (one is resident at its LDS footprint; the ones that start
-// later find the queue empty).  ELMK_CF_GROUPS (development, read once) overrides the 512: a smaller grid leaves CUs to kernels
-// of another context's stream (tests/tools/two_ctx_overlap.py).
-static unsigned cf_iterate_groups(unsigned nblk)
-{
-  static const unsigned cap = [] {
-    const char* e = getenv("ELMK_CF_GROUPS");
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? (unsigned)v : 512u;
-  }();
-  return nblk < cap ? nblk : cap;
 }
 
 static void launch_cf_iterate(const DevState* S, unsigned nblk, double dt, hipStream_t st, const SideStreams* side, int given)
@@ -2015,41 +1935,29 @@ static void launch_cf_iterate(const DevState* S, unsigned nblk, double dt, hipSt
     hipLaunchKernelGGL(col_dayl ? k_cf_iterate_half_col_dayl : k_cf_iterate_half, dim3(g ? g : 1u), dim3(CF_ITER_THREADS_HALF), 0, st, S, dt, given);
     return;
   }
-  hipLaunchKernelGGL(col_dayl ? k_cf_iterate_col_dayl : k_cf_iterate, dim3(cf_iterate_groups(nblk)), dim3(CF_ITER_THREADS), 0, st, S, dt, given);
+  // two workgroups per CU (one is resident at its LDS footprint; the ones that start later find the queue empty)
+  hipLaunchKernelGGL(col_dayl ? k_cf_iterate_col_dayl : k_cf_iterate, dim3(nblk < 512u ? nblk : 512u), dim3(CF_ITER_THREADS), 0, st, S, dt, given);
 }
 
 void launch_fused_stage(const DevState* S, int64_t n, double dt, hipStream_t st, const SideStreams* side, int stage)
 {
   if (n <= 0) return;
   const unsigned nblk = (unsigned)((n + 255) / 256);
-  const bool use_side = n >= 262144 && !side->one_stream;  // (one_stream: graph capture, every launch on st)
-  const bool bg_side = FZ_BG_OVERLAP && use_side;
+  const bool bg_side = n >= 262144 && !side->one_stream;  // (one_stream: graph capture, every launch on st)
   switch (stage) {
     case 0: hipLaunchKernelGGL(k_fz_prep, dim3((nblk + FZ_PREP_TILES - 1) / FZ_PREP_TILES), dim3(256), 0, st, S); break;
-    case 1:
-      if (!FZ_SPLIT) {
-        launch_albedo_snicar(S, n, st, side, false, !FZ_ALB_FWD);
-      } else if (FZ_SPLIT == 2 && n >= 262144) {
-        // the SNICAR queues of 5..2 layers, then the single-layer queue and k_fz_pre's tiles as ONE kernel, then k_alb_final
-        unsigned gs = 0;
-        launch_albedo_snicar_part(S, n, st, 0, &gs);
+    case 1:  // (the albedo stage without k_alb_final, whose body k_fz_stream runs)
+      if (n >= 262144) {
+        // the SNICAR queues of 5..2 layers, then the single-layer queue and k_fz_pre's tiles as ONE kernel
+        unsigned gs = launch_albedo_snicar_part(S, n, st);
         // as many SNICAR workgroups as tiles (each walks the queue with that stride: two or three entries per wave), so that the
         // two kinds alternate for the whole length of the kernel; with k_alb_snicar<1>'s grid of 4 096 long-lived workgroups
-        // the SNICAR part filled the machine first at 10 M columns and the tiles ran behind it
-        if (FZ_SNICAR_GRID_BY_TILES && gs < nblk) gs = nblk;
+        // the SNICAR part filled the machine first at 10 M columns and the tiles ran behind it (profiles/r03_fused_split_ab.txt)
+        if (gs < nblk) gs = nblk;
         hipLaunchKernelGGL(k_fz_snicar_pre, dim3(gs + nblk), dim3(256), 0, st, S, gs, nblk);
-        if (!FZ_ALB_FWD) launch_albedo_snicar_part(S, n, st, 1, nullptr);  // (else k_fz_stream runs stage 3 itself)
-      } else if (use_side) {
-        // k_fz_pre (memory-bound) beside the albedo stage (fp64-issue-bound) on a side stream; joined before k_fz_stream
-        (void)hipEventRecord(side->fork, st);
-        (void)hipStreamWaitEvent(side->s[0], side->fork, 0);
-        hipLaunchKernelGGL(k_fz_pre, dim3(nblk), dim3(256), 0, side->s[0], S);
-        (void)hipEventRecord(side->join[0], side->s[0]);
-        launch_albedo_snicar(S, n, st, side, false, !FZ_ALB_FWD);
-        (void)hipStreamWaitEvent(st, side->join[0], 0);
       } else {  // (few columns: the SNICAR queues themselves fork onto the side streams)
         hipLaunchKernelGGL(k_fz_pre, dim3(nblk), dim3(256), 0, st, S);
-        launch_albedo_snicar(S, n, st, side, false, !FZ_ALB_FWD);
+        launch_albedo_snicar(S, n, st, side, true);
       }
       break;
     case 2: hipLaunchKernelGGL(k_fz_stream, dim3(nblk), dim3(256), 0, st, S, dt); break;
@@ -2057,11 +1965,11 @@ void launch_fused_stage(const DevState* S, int64_t n, double dt, hipStream_t st,
       // The bare-ground Monin-Obukhov loop works on bare columns only and the canopy iteration on vegetated ones.  The one field
       // group both k_bg_flux and k_cf_finish would store to on a bare column is cgrnd / cgrnds / cgrndl (compute_flux of
       // canopy_fluxes resets them on every column after bareground_fluxes has set them, canopy_fluxes_impl.hh:474-479): in the
-      // fused step k_bg_flux therefore leaves them alone (launch_bareground_list passes given = 4; k_fz_stream has stored the
+      // fused step k_bg_flux therefore leaves them alone (launch_bareground_list passes GIVEN_FUSED; k_fz_stream has stored the
       // zeros that are their final value), so the two kernels have no store in common and may run side by side.
-      // With FZ_BG_OVERLAP the list kernel goes to a side stream behind k_cf_iterate's launch (case 4): a few hundred workgroups
+      // From 262 144 columns the list kernel goes to a side stream behind k_cf_iterate's launch (case 4): a few hundred workgroups
       // of long dependent chains that cannot fill the machine on their own (VALU busy 0.31 on the branch-mix tier) run in the
-      // CUs the persistent iteration kernel frees during its tail, instead of in front of it.
+      // CUs the persistent iteration kernel frees during its tail, instead of in front of it (profiles/r03_bg_overlap_ab.txt).
       if (bg_side) {
         (void)hipEventRecord(side->fork, st);
       } else {

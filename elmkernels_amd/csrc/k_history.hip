@@ -15,14 +15,11 @@
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
 
-// Nontemporal hints (bit 1: source loads, bit 2: accumulator loads and stores).  Both on: interleaved A/B runs of
+// Every source load and every accumulator load and store carries the nontemporal hint: interleaved A/B runs of
 // tests/tools/history_cost.py --ab (profiles/r06_history_nt_ab.jsonl) took the 19-field PrimaryVars tape from 0.64 to 0.59 ms at
 // 1 M columns and from 6.25 to 5.84 ms at 10 M, the 12-flux tape from 0.49 to 0.46 ms at 10 M.  Only a tape small enough to stay
 // in the on-die caches between two launches back to back lost (12 fluxes at 1 M: 0.039 -> 0.046 ms), and a physics step between
 // two accumulates leaves nothing of it there.
-#ifndef ELMK_HIST_NT
-#define ELMK_HIST_NT 3
-#endif
 
 namespace elmk {
 
@@ -33,27 +30,19 @@ typedef int32_t hi2 __attribute__((ext_vector_type(2)));
 typedef uint32_t hu2 __attribute__((ext_vector_type(2)));
 typedef uint8_t hb2 __attribute__((ext_vector_type(2)));
 
-template <int BIT, typename V> __device__ __forceinline__ V h_ld(const ELMK_GLOBAL V* p)
-{
-  if (ELMK_HIST_NT & BIT) return __builtin_nontemporal_load(p);
-  return *p;
-}
-template <int BIT, typename V> __device__ __forceinline__ void h_st(ELMK_GLOBAL V* p, V v)
-{
-  if (ELMK_HIST_NT & BIT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
+template <typename V> __device__ __forceinline__ V h_ld(const ELMK_GLOBAL V* p) { return __builtin_nontemporal_load(p); }
+template <typename V> __device__ __forceinline__ void h_st(ELMK_GLOBAL V* p, V v) { __builtin_nontemporal_store(v, p); }
 
 // two adjacent columns of a source row, widened to fp64 (exact for every stored type)
 __device__ __forceinline__ hd2 load_pair(const void* src, int dtype, int64_t c)
 {
   hd2 v;
   switch (dtype) {
-    case ELMK_F64: v = h_ld<1>((const ELMK_GLOBAL hd2*)src + c / 2); break;
-    case ELMK_F32_STORED: { const hf2 f = h_ld<1>((const ELMK_GLOBAL hf2*)src + c / 2); v = hd2{(double)f.x, (double)f.y}; break; }
-    case ELMK_I32: { const hi2 i = h_ld<1>((const ELMK_GLOBAL hi2*)src + c / 2); v = hd2{(double)i.x, (double)i.y}; break; }
-    case ELMK_U32: { const hu2 u = h_ld<1>((const ELMK_GLOBAL hu2*)src + c / 2); v = hd2{(double)u.x, (double)u.y}; break; }
-    default: { const hb2 b = h_ld<1>((const ELMK_GLOBAL hb2*)src + c / 2); v = hd2{(double)b.x, (double)b.y}; break; }
+    case ELMK_F64: v = h_ld((const ELMK_GLOBAL hd2*)src + c / 2); break;
+    case ELMK_F32_STORED: { const hf2 f = h_ld((const ELMK_GLOBAL hf2*)src + c / 2); v = hd2{(double)f.x, (double)f.y}; break; }
+    case ELMK_I32: { const hi2 i = h_ld((const ELMK_GLOBAL hi2*)src + c / 2); v = hd2{(double)i.x, (double)i.y}; break; }
+    case ELMK_U32: { const hu2 u = h_ld((const ELMK_GLOBAL hu2*)src + c / 2); v = hd2{(double)u.x, (double)u.y}; break; }
+    default: { const hb2 b = h_ld((const ELMK_GLOBAL hb2*)src + c / 2); v = hd2{(double)b.x, (double)b.y}; break; }
   }
   return v;
 }
@@ -84,10 +73,10 @@ __global__ __launch_bounds__(256) void k_hist_accumulate(const HistRow* __restri
   const int64_t c = 2 * p;
   const hd2 v = load_pair(r.src, r.dtype, c);
   ELMK_GLOBAL hd2* a = (ELMK_GLOBAL hd2*)r.acc + p;
-  hd2 acc = h_ld<2>(a);
+  hd2 acc = h_ld(a);
   acc.x = fold(r.op, acc.x, v.x);
   acc.y = fold(r.op, acc.y, v.y);
-  h_st<2>(a, acc);
+  h_st(a, acc);
 }
 
 // the rows of one tape back to their initial value, the tape's count to 0 (rows of other tapes: nothing)

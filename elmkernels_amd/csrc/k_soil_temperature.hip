@@ -35,17 +35,8 @@
 
 namespace elmk {
 
+// plain loads: the nontemporal hint costs this solve 16-30 % (profiles/r04_nontemporal_ab.txt), 2-5 % on its read-once levels alone
 #define LV(f, lev) S->f[(int64_t)(lev) * ld + c]
-// a level value this kernel reads exactly once (ST_NT_ONCE: with the nontemporal hint; the values phase change reads a second
-// time - liquid, ice, thickness, porosity - must stay cached: with the hint on every load the solve is 16-30 % slower)
-#ifndef ST_NT_ONCE
-#define ST_NT_ONCE 0
-#endif
-#if ST_NT_ONCE && !defined(ELMK_STATE_F32)
-#define LVN(f, lev) __builtin_nontemporal_load(&S->f[(int64_t)(lev) * ld + c])
-#else
-#define LVN(f, lev) LV(f, lev)
-#endif
 
 constexpr int NLEVBED = 15;               // elm_constants.h:91
 constexpr double ST_TKICE = 2.290;        // soil_thermal_properties.h:15-18
@@ -89,14 +80,14 @@ __device__ __forceinline__ StLevIn st_load_level(const DevState* __restrict__ S,
   L.liq = LV(h2osoi_liq, li);
   L.ice = LV(h2osoi_ice, li);
   L.dz = LV(dz, li);
-  L.t = LVN(t_soisno, li);
-  L.z = LVN(zsoi, li);
-  L.zi = LVN(zisoi, li);
-  L.sabg = LVN(sabg_lyr, lsab);
+  L.t = LV(t_soisno, li);
+  L.z = LV(zsoi, li);
+  L.zi = LV(zisoi, li);
+  L.sabg = LV(sabg_lyr, lsab);
   L.watsat = LV(watsat, js);
-  L.tkdry = LVN(tkdry, js);
-  L.tkmg = LVN(tkmg, js);
-  L.csol = LVN(csol, lcs);
+  L.tkdry = LV(tkdry, js);
+  L.tkmg = LV(tkmg, js);
+  L.csol = LV(csol, lcs);
   return L;
 }
 
@@ -151,10 +142,7 @@ __device__ __forceinline__ void st_level_props(const StLevIn& L, const int i, co
 // ground has a second superdiagonal entry (l0, get_matrix_snow_soil) - so that one value stays in a register and the
 // back substitution multiplies by a literal zero elsewhere (the same arithmetic as the reference's 0 * U1 product for
 // every finite solution).  The recurrence itself only needs the last two rows, kept here.
-#ifndef ST_WG_N
-#define ST_WG_N 512  // (64 / 128 / 192 measured in round 4: profiles/r04_soil_workgroup_ab.txt)
-#endif
-constexpr int ST_WG = ST_WG_N;
+constexpr int ST_WG = 512;  // (64 / 128 / 192 measured in round 4: profiles/r04_soil_workgroup_ab.txt)
 constexpr int ST_LDS_ROWS = NROW - 2;
 typedef double StLds[ST_LDS_ROWS][ST_WG];
 struct StSweep {

@@ -68,9 +68,7 @@ __global__ __launch_bounds__(256) void k_canopy_temperature(const DevState* __re
 // (1024-thread workgroups: one global atomic per workgroup on the bare-ground list's counter, and same-address atomics retire
 //  one after the other at ~14 ns each - with 256-thread workgroups they were most of this kernel's time on a mixed tile,
 //  profiles/r03_classify_atomics_ab.txt)
-#ifndef BG_MAIN_THREADS
-#define BG_MAIN_THREADS 1024
-#endif
+constexpr int BG_MAIN_THREADS = 1024;
 __global__ __launch_bounds__(BG_MAIN_THREADS) void k_bg_main(const DevState* __restrict__ S)
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -157,10 +155,10 @@ __global__ __launch_bounds__(256) void k_bg_flux(const DevState* __restrict__ S,
   }
   const double cgrnds = raih;
   const double cgrndl = raiw * S->dqgdT[c];
-  // (given & 4: the fused step.  There canopy_fluxes' compute_flux follows in the same call and resets cgrnd* on every column
+  // (GIVEN_FUSED: the fused step.  There canopy_fluxes' compute_flux follows in the same call and resets cgrnd* on every column
   //  (canopy_fluxes_impl.hh:474-479) - k_fz_stream has already stored those zeros - and this kernel may run beside
   //  k_cf_finish on a side stream: it must not store to a field that kernel stores to.)
-  if (!(given & 4)) {
+  if (!(given & GIVEN_FUSED)) {
     S->cgrnds[c] = cgrnds;
     S->cgrndl[c] = cgrndl;
     S->cgrnd[c] = cgrnds + S->htvp[c] * cgrndl;
@@ -226,7 +224,7 @@ void launch_bareground_list(const DevState* S, int64_t n, hipStream_t st)
 {
   if (n <= 0) return;
   const unsigned full = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(k_bg_flux, dim3(full < 2048u ? full : 2048u), dim3(256), 0, st, S, 4);
+  hipLaunchKernelGGL(k_bg_flux, dim3(full < 2048u ? full : 2048u), dim3(256), 0, st, S, GIVEN_FUSED);
 }
 
 void launch_bareground_fluxes(const DevState* S, int64_t n, hipStream_t st, int given)
@@ -234,7 +232,7 @@ void launch_bareground_fluxes(const DevState* S, int64_t n, hipStream_t st, int 
   if (n <= 0) return;
   const unsigned full = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(k_bg_main, dim3((unsigned)((n + BG_MAIN_THREADS - 1) / BG_MAIN_THREADS)), dim3(BG_MAIN_THREADS), 0, st, S);
-  hipLaunchKernelGGL(k_bg_flux, dim3(full < 2048u ? full : 2048u), dim3(256), 0, st, S, given);
+  hipLaunchKernelGGL(k_bg_flux, dim3(full < 2048u ? full : 2048u), dim3(256), 0, st, S, given & 1);  // (only forc_rho is staged for bare ground)
 }
 
 }  // namespace elmk

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""GPU box, development: trip-count histogram of canopy_fluxes and, with a CF_PROBE=4 build selected through
-ELMK_LIBRARY, the per-wave timeline of k_cf_iterate.  python tests/tools/cf_timeline.py [cols]"""
+"""GPU box, development: trip-count histogram of canopy_fluxes and, with a CF_PROBE=4 or 5 build selected through
+ELMK_LIBRARY, the per-wave timeline of k_cf_iterate.  python tests/tools/cf_timeline.py [cols]
+(build: bash tests/tools/build_variant.sh <out.so> k_canopy_fluxes.hip -DCF_PROBE=5)"""
 import os
 import sys
 

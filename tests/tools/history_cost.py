@@ -9,8 +9,7 @@ For each column count, interleaved over `rounds` repeats (the modes take turns i
   acc_a, acc_b    elmk_history_accumulate alone, back to back: ms per launch and bytes moved per second
                   (bytes = per row and column: the stored source element + 16 B of fp64 accumulator read and write)
 and elmk_copy_bandwidth (shape 0, and the best of shapes 0..3) from the same process.
---ab LIB: accumulate alone, interleaved between the product library and LIB (a build of the same ABI, e.g. with
--DELMK_HIST_NT=3), for the nontemporal A/B.
+--ab LIB: accumulate alone, interleaved between the product library and LIB (a build of the same ABI), for an A/B.
 python tests/tools/history_cost.py [--cols 1000000,10000000] [--rounds 5] [--ab path/to/libelmk_variant.so]"""
 import argparse
 import json
