@@ -11,6 +11,10 @@ carries a field wins, so every field has its start-of-timestep value).
                              with a consistent snowpack, 5 % capped snow, 10 % ponded surface water,
                              10 % C4 grass (vtype 14), aerosols in snow, cold/warm forcing for all three
                              snowfall-density regimes.
+  tier "W" (wide)            tier B's snow packs, ponds and capped snow, every other input drawn over its physical
+                             range (LAI / SAI 0..10, every leafed PFT, veg_active 0 / 1, wind from every direction,
+                             sun from grazing to zenith, soil from frozen to hot and dry to saturated, thin air), then
+                             hand-built edge rows for the paths the draw reaches only by chance (wide_edge_rows).
 
 Larger states tile the base block (column c <- base column c mod nbase) with small multiplicative / additive
 perturbations of forcing-like fields; the same rule runs on the device (elmk_tile_columns) for big N.
@@ -197,6 +201,256 @@ def branch_mix(cols, seed=0x5EEDE1A0):
     return c
 
 
+DENH2O, DENICE = 1000.0, 917.0
+LEAFED_PFTS = np.arange(1, 25)  # every vegetated PFT of the parameter table (0 is bare ground)
+
+
+def _snow_mesh(c):
+    """Node depths and interfaces of the snow levels from dz and snl, and the pack totals from the layers' water
+    (h2osno = ice + liquid of the active layers, snow_depth = their thickness)."""
+    snl = c["snl"]
+    n = snl.shape[0]
+    act = np.arange(5)[None, :] >= 5 - snl[:, None]
+    for k in ("dz", "h2osoi_ice", "h2osoi_liq", "t_soisno", "snw_rds", "frac_iceold"):
+        c[k][:, :5] = np.where(act, c[k][:, :5], 0.0)
+    zi_run = np.zeros(n)
+    for lev in range(4, -1, -1):
+        c["zsoi"][:, lev] = np.where(act[:, lev], zi_run - 0.5 * c["dz"][:, lev], 0.0)
+        zi_run = np.where(act[:, lev], zi_run - c["dz"][:, lev], zi_run)
+        c["zisoi"][:, lev] = np.where(act[:, lev], zi_run, 0.0)
+    layered = snl > 0
+    c["h2osno"] = np.where(layered, (c["h2osoi_ice"][:, :5] + c["h2osoi_liq"][:, :5]).sum(axis=1), c["h2osno"])
+    c["snow_depth"] = np.where(layered, c["dz"][:, :5].sum(axis=1), c["snow_depth"])
+
+
+def wide_mix(cols, seed=0x5EEDE1A0):
+    """Tier W: tier B's snow packs, ponds and capped snow, with every other input drawn over its physical range instead
+    of near the fixtures (vegetation, sun, soil temperature and water, forcing), followed by hand-built edge rows
+    (wide_edge_rows).  Keeps what the reference assumes of a state: a consistent snow mesh, h2osno equal to the layers'
+    water, water within the pore space, grain radii inside the Mie table."""
+    c = branch_mix(cols, seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 0x57))
+    n = c["snl"].shape[0]
+    u = lambda: rng.random(n)  # noqa: E731
+
+    # --- vegetation: every leafed PFT, LAI / SAI 0..10, exposed <= total, canopy heights from shrubs to trees
+    c["vtype"] = rng.choice(LEAFED_PFTS, n).astype(np.int32)
+    tlai = 10.0 * u() ** 1.5
+    tlai[u() < 0.05] = 0.0
+    c["tlai"] = tlai
+    c["elai"] = np.where(u() < 0.3, tlai, tlai * u())
+    c["tsai"] = 3.0 * u() ** 2
+    c["esai"] = np.where(u() < 0.3, c["tsai"], c["tsai"] * u())
+    c["tlai_z"] = c["elai"].copy()
+    htop = np.where(u() < 0.5, 0.1 + 1.9 * u(), 2.0 + 33.0 * u())
+    c["htop"] = htop
+    c["hbot"] = htop * (0.02 + 0.5 * u())
+    leafy = c["elai"] + c["esai"] >= 0.05
+    c["frac_veg_nosno"] = np.where(leafy & (c["frac_veg_nosno"] == 1), 1, 0).astype(np.int32)
+    c["veg_active"] = (u() < 0.8).astype(c["veg_active"].dtype)
+
+    # --- wind from every direction, sun from the horizon to the zenith (night columns kept)
+    speed = 0.3 + 14.0 * u()
+    ang = 2 * np.pi * u()
+    c["forc_u"], c["forc_v"] = speed * np.cos(ang), speed * np.sin(ang)
+    day = c["coszen"] > 0
+    mu = np.where(u() < 0.2, 1e-3 + 0.05 * u(), u())
+    mu[u() < 0.02] = 1.0
+    c["coszen"] = np.where(day, mu, c["coszen"])
+    light = np.where(u() < 0.1, 0.5 * u(), 900.0 * mu * u())  # some barely lit columns
+    c["forc_solad"] = np.where(day[:, None], light[:, None] * np.array([[0.55, 0.45]]), 0.0)
+    c["forc_solai"] = np.where(day[:, None], 0.3 * light[:, None] * np.array([[0.5, 0.5]]), 0.0)
+
+    # --- air and leaves: 240..318 K (snowfall regimes of tier B kept where there is a pack), humid to very dry
+    snowy = (c["snl"] > 0) | (c["h2osno"] > 0)
+    forc_t = np.where(snowy, c["forc_tbot"], 240.0 + 78.0 * u())
+    dT = forc_t - c["forc_tbot"]
+    c["forc_tbot"] = forc_t
+    c["forc_thbot"] = c["forc_thbot"] + dT
+    qs = 0.622 * 611.0 * np.exp(17.3 * (forc_t - TFRZ) / (forc_t - 35.86)) / c["forc_pbot"]
+    c["forc_qbot"] = qs * (0.02 + 0.93 * u())
+    c["forc_pbot"] = c["forc_pbot"] * (0.6 + 0.4 * u())  # high ground: thin air, low CO2 partial pressure
+    warm = forc_t > TFRZ
+    c["forc_snow"] = np.where(warm, 0.0, c["forc_snow"])
+    c["t_veg"] = forc_t + 6.0 * (u() - 0.5)
+    c["t10"] = forc_t + 4.0 * (u() - 0.5)
+    c["h2ocan"] = np.where(u() < 0.3, 0.0, 0.1 * (c["elai"] + c["esai"]) * u())
+
+    # --- soil: temperatures from deep frost to hot ground, water from dry to saturated, ice only below freezing
+    tsurf = np.where(snowy, np.minimum(c["t_grnd"], TFRZ + 1.0), 245.0 + 65.0 * u())
+    tdeep = 262.0 + 24.0 * u()
+    dzs = c["dz"][:, 5:]
+    frac = np.where(u()[:, None] < 0.15, 0.01 + 0.05 * rng.random((n, 15)), 0.05 + 0.95 * rng.random((n, 15)))
+    frac[u() < 0.05] = 1.0
+    for j in range(15):
+        lev = 5 + j
+        w = np.exp(-j / 3.0)
+        t = w * tsurf + (1 - w) * tdeep
+        c["t_soisno"][:, lev] = t
+        vol = frac[:, j] * c["watsat"][:, j]
+        fice = np.where(t < TFRZ, np.minimum(1.0, (TFRZ - t) / 3.0) * rng.random(n), 0.0)
+        c["h2osoi_liq"][:, lev] = (1 - fice) * vol * dzs[:, j] * DENH2O
+        c["h2osoi_ice"][:, lev] = fice * vol * dzs[:, j] * DENICE
+        c["h2osoi_vol"][:, j] = vol
+    c["t_grnd"] = np.where(c["snl"] > 0, c["t_soisno"][np.arange(n), np.maximum(5 - c["snl"], 0)], tsurf)
+    c["t_h2osfc"] = np.where(c["h2osfc"] > 0, np.where(snowy, np.minimum(c["t_h2osfc"], TFRZ + 0.5), tsurf), c["t_h2osfc"])
+    _snow_mesh(c)
+    return _append(c, wide_edge_rows(c, rng))
+
+
+def _append(c, rows):
+    return {k: np.concatenate([v, rows[k]]) for k, v in c.items()}
+
+
+def wide_edge_rows(c, rng):
+    """Hand-built rows, one or a few per path the wide draw reaches only by chance.  Each starts from a copy of a wide row
+    and changes what the path needs, keeping the mesh and the water consistent (_snow_mesh)."""
+    n = c["snl"].shape[0]
+    rows = []
+
+    def row(src=None, snl=None, depth=0.15, t_snow=TFRZ - 5.0):
+        i = src if src is not None else int(rng.integers(0, n))
+        r = {k: v[i : i + 1].copy() for k, v in c.items()}
+        if snl is not None:  # a fresh pack: snl equal layers, 250 kg/m3, cold, mid-table grains
+            r["snl"][:] = snl
+            for lev in range(5):
+                on = lev >= 5 - snl
+                r["dz"][:, lev] = depth / max(snl, 1) if on else 0.0
+                r["h2osoi_ice"][:, lev] = 250.0 * r["dz"][:, lev]
+                r["h2osoi_liq"][:, lev] = 0.0
+                r["t_soisno"][:, lev] = t_snow if on else 0.0
+                r["snw_rds"][:, lev] = 200.0 if on else 0.0
+                r["frac_iceold"][:, lev] = 1.0 if on else 0.0
+            r["frac_sno"][:] = r["frac_sno_eff"][:] = 1.0 if snl > 0 else r["frac_sno"]
+            r["do_capsnow"][:] = 0
+            r["frac_h2osfc"][:] = 0.0
+        rows.append(r)
+        return r
+
+    def cold(r):
+        r["forc_tbot"][:] = TFRZ - 8.0
+        r["forc_thbot"][:] = TFRZ - 7.0
+        r["forc_rain"][:] = 0.0
+        r["forc_qbot"][:] = 1e-3
+        for lev in range(5, 20):
+            r["t_soisno"][:, lev] = np.minimum(r["t_soisno"][:, lev], TFRZ - 0.5)
+            r["h2osoi_ice"][:, lev] += r["h2osoi_liq"][:, lev] * 0.9
+            r["h2osoi_liq"][:, lev] *= 0.1
+
+    # temperatures exactly at freezing: snow layers, soil, ground, pond
+    for snl in (0, 1, 3):
+        r = row(snl=snl, t_snow=TFRZ)
+        r["t_soisno"][:, 5:8] = TFRZ
+        r["t_grnd"][:] = TFRZ
+        r["t_h2osfc"][:] = TFRZ
+    # snow without layers: none, a trace (< 1 kg/m2, the oldfflag clamp), a few kg/m2
+    for w in (0.0, 1e-31, 0.02, 0.4, 0.999, 6.0):
+        r = row(snl=0)
+        r["h2osno"][:] = w
+        r["snow_depth"][:] = w / 250.0
+        r["frac_sno"][:] = r["frac_sno_eff"][:] = 0.0 if w == 0 else min(1.0, 0.2 + w)
+        r["forc_snow"][:] = 4e-4 if 1e-20 < w < 1 else 0.0
+        cold(r)
+        if w < 1e-20:  # a trace below SNICAR's minimum, in daylight
+            r["coszen"][:] = 0.5
+    # a layer with <= 0.01 kg/m2 of ice at every depth of every pack: combine_layers removes it
+    for snl in range(1, 6):
+        for j in range(snl):
+            for liq in (0.0, 0.004):
+                r = row(snl=snl, depth=0.08 * snl)
+                lev = 5 - snl + j
+                r["h2osoi_ice"][:, lev] = 0.006
+                r["h2osoi_liq"][:, lev] = liq
+                r["dz"][:, lev] = 0.006 / 250.0
+                cold(r)
+    # a deep pack over ponded water that freezes into it (one and several layers), and a pond without snow
+    # (a thin pond freezes whole, a deep one in part)
+    for k, snl in enumerate((0, 1, 1, 2, 4)):
+        for pond, tp, sigma, night in ((12.0, TFRZ - 3.0, None, False), (0.05, TFRZ - 10.0, None, False),
+                                       (0.5, TFRZ - 20.0, None, False), (0.01, TFRZ - 30.0, None, False),
+                                       (0.05, TFRZ - 25.0, 1e-3, False), (0.2, TFRZ - 30.0, 1e-3, False),
+                                       (0.05, TFRZ - 25.0, 1e-3, True), (0.2, TFRZ - 30.0, 1e-3, True)):
+            # (a one-layer pack thin enough that divide_layers keeps it one layer through the chain)
+            r = row(snl=snl, depth=0.015 if (k == 2 and sigma is not None) else 0.1 * max(snl, 1))
+            cold(r)
+            if sigma is not None:  # smooth ground: a thin pond covers much of the column (fraction_h2osfc)
+                r["micro_sigma"][:] = sigma
+            if night:  # ... and on a clear cold night freezes whole
+                r["coszen"][:] = -0.3
+                r["forc_solad"][:] = 0.0
+                r["forc_solai"][:] = 0.0
+                r["forc_lwrad"][:] = 100.0
+                r["forc_tbot"][:] = TFRZ - 25.0
+                r["forc_thbot"][:] = TFRZ - 24.0
+                r["forc_qbot"][:] = 2e-4
+            r["h2osfc"][:] = pond
+            r["frac_h2osfc"][:] = 0.3
+            r["frac_sno"][:] = r["frac_sno_eff"][:] = 0.7 if snl > 0 else 0.0
+            r["t_h2osfc"][:] = tp
+    # humidity measured at another height than temperature (the profile of friction_velocity_humidity)
+    for dh in (-3.0, 5.0):
+        r = row()
+        r["forc_hgt_q_patch"][:] = r["forc_hgt_t_patch"] + dh
+    # frac_h2osfc at both ends
+    for f in (0.0, 1.0):
+        r = row(snl=0)
+        r["h2osfc"][:] = 30.0 if f > 0 else 0.0
+        r["frac_h2osfc"][:] = f
+        r["frac_sno"][:] = r["frac_sno_eff"][:] = 0.0
+        r["h2osno"][:] = 0.0
+        r["snow_depth"][:] = 0.0
+    # capped snow whose top layer sublimation empties
+    for top_ice in (1e-4, 0.05):
+        r = row(snl=5, depth=5.5)  # still > 1000 kg/m2 without the top layer: init_timestep keeps do_capsnow
+        r["do_capsnow"][:] = 1
+        r["h2osoi_ice"][:, 0] = top_ice
+        r["dz"][:, 0] = 0.02
+        r["qflx_sub_snow"][:] = 5e-5
+        r["forc_qbot"][:] = 1e-5
+        r["forc_tbot"][:] = TFRZ - 2.0
+        r["forc_thbot"][:] = TFRZ - 1.0
+    # bare dry soil under hot dry wind: evaporation the top layer cannot supply (with and without a thin pack)
+    for snl in (0, 0, 1):
+        r = row(snl=snl, depth=0.01, t_snow=TFRZ - 0.5)
+        r["frac_veg_nosno"][:] = 0
+        r["h2osoi_liq"][:, 5] = 1e-4
+        r["h2osoi_ice"][:, 5] = 0.0
+        if snl:
+            r["h2osoi_ice"][:, 4] = 2e-3
+            r["dz"][:, 4] = 2e-3 / 250.0
+            r["forc_tbot"][:] = TFRZ - 1.0
+        else:
+            r["forc_tbot"][:] = 312.0
+            r["t_grnd"][:] = 318.0
+            r["t_soisno"][:, 5] = 318.0
+        r["forc_thbot"][:] = r["forc_tbot"] + 1.0
+        r["forc_qbot"][:] = 2e-4
+        r["forc_u"][:] = 12.0
+        r["forc_v"][:] = -7.0
+        r["forc_solad"][:] = [[500.0, 400.0]]
+        r["coszen"][:] = 0.9
+    # photosynthesis on the edge of its domain: dim light, thin air (low CO2), hot leaves, very dry soil
+    for k in range(24):
+        r = row()
+        r["vtype"][:] = LEAFED_PFTS[k]
+        r["frac_veg_nosno"][:] = 1
+        r["veg_active"][:] = 1
+        r["tlai"][:] = r["elai"][:] = r["tlai_z"][:] = (0.2, 3.0, 9.0)[k % 3]
+        r["coszen"][:] = (0.02, 0.4, 1.0)[k % 3]
+        r["forc_solad"][:] = [[(0.05, 2.0, 900.0, 20.0)[k % 4]] * 2]
+        r["forc_solai"][:] = r["forc_solad"] * 0.3
+        r["forc_pbot"][:] = (4.2e4, 6.0e4, 1.0e5)[k % 3]
+        hot = k % 2 == 1
+        r["forc_tbot"][:] = 316.0 if hot else 290.0
+        r["forc_thbot"][:] = r["forc_tbot"] + 1.0
+        r["t_veg"][:] = 320.0 if hot else 289.0
+        r["t10"][:] = 315.0 if hot else 288.0
+        r["forc_qbot"][:] = 2e-3
+    out = {k: np.concatenate([r[k] for r in rows]) for k in c}
+    _snow_mesh(out)
+    return out
+
+
 def soil_color_tables(seed=7):
     """20 plausible soil colour classes (saturated / dry albedo, VIS and NIR) for tier B."""
     rng = np.random.Generator(np.random.PCG64(seed))
@@ -227,6 +481,11 @@ def make_state(field_table, n, tier="A", seed=0x5EEDE1A0, perturb=True):
         reps = max(1, min(64, (n + 46) // 47))
         base = tile(base, 47 * reps, seed=seed, perturb=False)
         base = branch_mix(base, seed=seed)
+        sat, dry = soil_color_tables()
+        soil = dict(albsat=sat, albdry=dry)
+    elif tier == "W":
+        base = tile(base, 47 * 16, seed=seed, perturb=False)
+        base = wide_mix(base, seed=seed)
         sat, dry = soil_color_tables()
         soil = dict(albsat=sat, albdry=dry)
     cols = tile(base, n, seed=seed, perturb=perturb) if n != next(iter(base.values())).shape[0] else base

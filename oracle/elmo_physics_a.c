@@ -407,8 +407,8 @@ unsigned elmo_sr_layer_absorbed_radiation(const elmo_land *L, int snl, double sa
     }
     if (fabs(sabg_snl_sum - sabg_snow) > 0.00001) {
       if (snl == 0) {
-        for (int j = 0; j < nlevsno; j++) sabg_lyr[j] = 0.0;
-        sabg_lyr[nlevsno] = sabg;
+        for (int j = 0; j < nlevsno; j++) sabg_lyr[j] = 0.0; /* unreached: snl > 0 in this branch, snl == 0 is handled above (kept as the reference writes it) */
+        sabg_lyr[nlevsno] = sabg; /* unreached: snl > 0 in this branch, snl == 0 is handled above (kept as the reference writes it) */
       } else if (snl == 1) {
         for (int j = 0; j < nlevsno - 1; j++) sabg_lyr[j] = 0.0;
         sabg_lyr[nlevsno - 1] = sabg_snow * 0.6;
@@ -530,11 +530,11 @@ void elmo_ct_calc_soilbeta(const elmo_land *L, double frac_sno, double frac_h2os
         *soilbeta = 1.0;
       }
     } else if (L->ltype == icol_road_perv) {
-      *soilbeta = 0.0;
+      *soilbeta = 0.0; /* unreached: compares ltype with a column-type code (71-75) that no land type equals (kept as the reference writes it) */
     } else if (L->ltype == icol_sunwall || L->ltype == icol_shadewall) {
-      *soilbeta = 0.0;
+      *soilbeta = 0.0; /* unreached: compares ltype with a column-type code (71-75) that no land type equals (kept as the reference writes it) */
     } else if (L->ltype == icol_roof || L->ltype == icol_road_imperv) {
-      *soilbeta = 0.0;
+      *soilbeta = 0.0; /* unreached: compares ltype with a column-type code (71-75) that no land type equals (kept as the reference writes it) */
     }
   } else {
     *soilbeta = 1.0;
@@ -552,7 +552,7 @@ void elmo_ct_humidities(const elmo_land *L, int snl, double forc_q, double forc_
   double eg, qsatg, degdT, qsatgdT;
   if (L->ltype == istsoil || L->ltype == istcrop) {
     elmo_qsat(t_soisno[nlevsno - snl], forc_pbot, &eg, &degdT, &qsatg, &qsatgdT);
-    if (qsatg > forc_q && forc_q > qsatg) {
+    if (qsatg > forc_q && forc_q > qsatg) { /* unreached: the condition is always false (kept as the reference writes it) */
       qsatg = forc_q;
       qsatgdT = 0.0;
     }
@@ -570,7 +570,7 @@ void elmo_ct_humidities(const elmo_land *L, int snl, double forc_q, double forc_
       *dqgdT = (1.0 - frac_h2osfc) * hr * *dqgdT;
     }
     elmo_qsat(t_h2osfc, forc_pbot, &eg, &degdT, &qsatg, &qsatgdT);
-    if (qsatg > forc_q && forc_q > qsatg) {
+    if (qsatg > forc_q && forc_q > qsatg) { /* unreached: the condition is always false (kept as the reference writes it) */
       qsatg = forc_q;
       qsatgdT = 0.0;
     }
@@ -776,7 +776,7 @@ void elmo_fv_humidity2m(double obu, double z0h, double z0q, double temp12m, doub
 {
   if (z0q == z0h) {
     *temp22m = temp12m;
-  } else {
+  } else { /* unreached: z0qg / z0hg and z0qv / z0hv are set equal together (canopy_temperature), so z0q == z0h always */
     *temp22m = profile_t(2.0 + z0q, obu, z0q, 0);
   }
 }

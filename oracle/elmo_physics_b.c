@@ -157,7 +157,7 @@ static void psn_brent(double *x, double x1, double x2, double f1, double f2, dou
   double b = x2;
   double fa = f1;
   double fb = f2;
-  if ((fa > 0.0 && fb > 0.0) || (fa < 0.0 && fb < 0.0)) {
+  if ((fa > 0.0 && fb > 0.0) || (fa < 0.0 && fb < 0.0)) { /* unreached: throw site of the reference (photosynthesis_impl.hh:439), pinned by tests/test_oracle_vs_ref_canopy.py */
     k->err |= ELMO_ERR_PSN_BRENT_BRACKET;
   }
   double c = b;
@@ -219,18 +219,18 @@ static void psn_brent(double *x, double x1, double x2, double f1, double f2, dou
       b = b + copysign(tol1, xm);
     }
     psn_ci_func(b, &fb, k);
-    if (fb == 0.0) {
+    if (fb == 0.0) { /* unreached: an exactly zero residual after a Brent step: no known input produces it */
       break;
     }
   }
-  *x = b;
+  *x = b; /* unreached: Brent's own iteration limit: no known input exhausts it (the hybrid's limit below is the one reached) */
 }
 
 /* Branch counters of the root find (test infrastructure: the tests that pin this file against the reference's own
  * photosynthesis() use them to show that their inputs reach Brent's method, the itmax fall-back and the C4 forms).
  * [0] hybrid calls, [1] calls that entered brent, [2] calls that left through the itmax fall-back, [3] C4 calls. */
 static unsigned long long psn_counts[4];
-void elmo_psn_counters(unsigned long long *out, int reset)
+void elmo_psn_counters(unsigned long long *out, int reset) /* unreached: test hook, not physics: the branch counters tests/test_oracle_vs_ref_canopy.py reads */
 {
   for (int i = 0; i < 4; i++) {
     if (out) out[i] = psn_counts[i];
@@ -291,7 +291,7 @@ static void psn_hybrid(double *x0, psn_ctx *k)
       *x0 = x;
       break;
     }
-    if (iter > itmax) {
+    if (iter > itmax) { /* unreached: the secant iteration's limit, about one call in a million: tests/test_oracle_vs_ref_canopy.py::test_photosynthesis_alone_bitwise_over_wide_inputs */
       PSN_COUNT(2);
       psn_ci_func(minx, &f1, k);
       break;
@@ -323,7 +323,7 @@ unsigned elmo_psn_photosynthesis(const elmo_pft_psn *psnveg, int nrad, double fo
   double tpu25top = 0.167 * vcmax25top;
   double kp25top = 20000.0 * vcmax25top;
   double kn;
-  if (dayl_factor == 0.0) {
+  if (dayl_factor == 0.0) { /* unreached: dayl_factor is clamped to at least 0.01 by canopy_fluxes, never 0 */
     kn = 0.0;
   } else {
     kn = exp(0.00963 * vcmax25top / dayl_factor - 2.43);
@@ -341,7 +341,7 @@ unsigned elmo_psn_photosynthesis(const elmo_pft_psn *psnveg, int nrad, double fo
   for (int iv = 0; iv < nrad; iv++) {
     if (iv == 0) {
       laican = 0.5 * tlai_z[iv];
-    } else {
+    } else { /* unreached: nlevcan == 1: nrad <= 1, so the layer sum never passes its first term */
       laican += 0.5 * (tlai_z[iv - 1] + tlai_z[iv]);
     }
     double nscaler = vcmaxcint;
@@ -453,12 +453,12 @@ unsigned elmo_psn_photosynthesis(const elmo_pft_psn *psnveg, int nrad, double fo
       ci_z[iv] = cair - an * forc_pbot * (1.4 * gs_mol[iv] + 1.6 * gb_mol) / (gb_mol * gs_mol[iv]);
       double gs = gs_mol[iv] / cf;
       rs_z[iv] = dmin(1.0 / gs, rsmax0);
-      if (gs_mol[iv] < 0.0) {
+      if (gs_mol[iv] < 0.0) { /* unreached: throw site of the reference (photosynthesis_impl.hh:232), pinned by tests/test_oracle_vs_ref_canopy.py */
         err |= ELMO_ERR_PSN_NEG_GS;
       }
       double hs = (gb_mol * ceair + gs_mol[iv] * esat_tv) / ((gb_mol + gs_mol[iv]) * esat_tv);
       double gs_mol_err = psnveg->mbbopt * dmax(an, 0.0) * hs / cs * forc_pbot + bbb;
-      if (fabs(gs_mol[iv] - gs_mol_err) > 1.0e-01) {
+      if (fabs(gs_mol[iv] - gs_mol_err) > 1.0e-01) { /* unreached: the reference's Ball-Berry warning (photosynthesis_impl.hh:240), pinned by tests/test_oracle_vs_ref_canopy.py */
         err |= ELMO_WARN_PSN_BALL_BERRY;
       }
     }
@@ -611,13 +611,13 @@ unsigned elmo_cf_stability_iteration(const elmo_land *L, double dtime, int snl, 
       svpts = w->el;
       eah = forc_pbot * w->qaf / 0.622;
 
-      if (L->vtype == pft_nsoybean || L->vtype == pft_nsoybeanirrig) {
+      if (L->vtype == pft_nsoybean || L->vtype == pft_nsoybeanirrig) { /* unreached: soybean land units only (L->vtype): tests/test_oracle_vs_ref_canopy.py::test_canopy_fluxes_whole_wrapper_bitwise runs one */
         *btran = dmin(1.0, *btran * 1.25);
       }
       err |= elmo_psn_photosynthesis(psn_pft, nrad, forc_pbot, *t_veg, t10, svpts, eah, forc_po2, forc_pco2, rb,
                                      *btran, w->dayl_factor, thm, tlai_z, vcmaxcintsun, parsun_z, laisun_z, ci_z,
                                      &rssun);
-      if (L->vtype == pft_nsoybean || L->vtype == pft_nsoybeanirrig) {
+      if (L->vtype == pft_nsoybean || L->vtype == pft_nsoybeanirrig) { /* unreached: soybean land units only (L->vtype): tests/test_oracle_vs_ref_canopy.py::test_canopy_fluxes_whole_wrapper_bitwise runs one */
         *btran = dmin(1.0, *btran * 1.25);
       }
       err |= elmo_psn_photosynthesis(psn_pft, nrad, forc_pbot, *t_veg, t10, svpts, eah, forc_po2, forc_pco2, rb,

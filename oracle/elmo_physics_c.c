@@ -183,7 +183,7 @@ unsigned elmo_sa_canopy_layer_lai(int urbpoi, double elai, double esai, double t
       laisum += tlai_z[iv];
       saisum += tsai_z[iv];
     }
-    if (fabs(laisum - elai) > SA_MPE || fabs(saisum - esai) > SA_MPE) {
+    if (fabs(laisum - elai) > SA_MPE || fabs(saisum - esai) > SA_MPE) { /* unreached: throw site of the reference (surface_albedo_impl.hh:270): tests/test_gpu_parity.py::test_error_flags_match_the_reference_throw_sites */
       err |= ELMO_ERR_ALB_CANOPY_LAYERS;
     }
     for (int iv = 0; iv < *nrad; ++iv) {
@@ -407,7 +407,7 @@ unsigned elmo_sn_init_timestep(int urbpoi, int flg_slr_in, double coszen, double
     *snl_btm = nlevsno - 1;
     *snl_top = nlevsno - snl_lcl;
     for (int i = *snl_top; i <= *snl_btm; ++i) {
-      if ((snw_rds_lcl[i] < SN_RDS_MIN_TBL) || (snw_rds_lcl[i] > SN_RDS_MAX_TBL)) {
+      if ((snw_rds_lcl[i] < SN_RDS_MIN_TBL) || (snw_rds_lcl[i] > SN_RDS_MAX_TBL)) { /* unreached: throw site of the reference (snow_snicar_impl.hh:76): tests/test_gpu_parity.py::test_error_flags_match_the_reference_throw_sites */
         err |= ELMO_ERR_SNICAR_RDS;
         /* the reference throws; keep the table index in range so a flagged column cannot read out of bounds */
         snw_rds_lcl[i] = snw_rds_lcl[i] < SN_RDS_MIN_TBL ? SN_RDS_MIN_TBL : SN_RDS_MAX_TBL;
@@ -424,7 +424,7 @@ unsigned elmo_sn_init_timestep(int urbpoi, int flg_slr_in, double coszen, double
         flx_slrd_lcl[b] = 0.0;
         flx_slri_lcl[b] = 1.0;
       }
-    } else {
+    } else { /* unreached: flg_slr_in is 1 or 2: the wrapper runs the direct and the diffuse pass only */
       err |= ELMO_ERR_SNICAR_FLAG;
     }
   }

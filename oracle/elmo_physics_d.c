@@ -67,10 +67,10 @@ void elmo_st_calc_soil_tk(int ltype, const double *h2osoi_liq, const double *h2o
         thk[i] = tkdry[i - NSNO];
       }
       if (i >= NSNO + NLEVBED) thk[i] = TKBDRK;
-    } else if (ltype == istice || ltype == istice_mec) {
+    } else if (ltype == istice || ltype == istice_mec) { /* unreached: the soil temperature wrapper passes ltype = 1 for every column (its dummy ltype, soil_temperature_kokkos.cc:77-79) */
       thk[i] = TKWAT;
       if (t_soisno[i] < TFRZ) thk[i] = TKICE;
-    } else if (ltype == istwet) {
+    } else if (ltype == istwet) { /* unreached: the soil temperature wrapper passes ltype = 1 for every column (its dummy ltype, soil_temperature_kokkos.cc:77-79) */
       if (i >= NSNO + NLEVBED) {
         thk[i] = TKBDRK;
       } else {
@@ -112,10 +112,10 @@ void elmo_st_calc_soil_heat_capacity(int ltype, int snl, double h2osno, const do
   for (int i = NSNO; i < NGRND + NSNO; ++i) {
     if (ltype != istwet && ltype != istice && ltype != istice_mec) {
       cv[i] = csol[i] * (1.0 - watsat[i - NSNO]) * dz[i] + (h2osoi_ice[i] * CPICE + h2osoi_liq[i] * CPWAT);
-    } else if (ltype == istwet) {
+    } else if (ltype == istwet) { /* unreached: the soil temperature wrapper passes ltype = 1 for every column (its dummy ltype, soil_temperature_kokkos.cc:77-79) */
       cv[i] = (h2osoi_ice[i] * CPICE + h2osoi_liq[i] * CPWAT);
       if (i >= NSNO + NLEVBED) cv[i] = csol[i] * dz[i];
-    } else if (ltype == istice || ltype == istice_mec) {
+    } else if (ltype == istice || ltype == istice_mec) { /* unreached: the soil temperature wrapper passes ltype = 1 for every column (its dummy ltype, soil_temperature_kokkos.cc:77-79) */
       cv[i] = (h2osoi_ice[i] * CPICE + h2osoi_liq[i] * CPWAT);
     }
     if (i == NSNO && snl == 0 && h2osno > 0.0) cv[i] += CPICE * h2osno;
@@ -463,7 +463,7 @@ void elmo_st_phase_change_h2osfc(int snl, double dtime, double frac_sno, double 
         }
         if (frac_h2osfc != 0.0) {
           c2 = (-CPWAT * xm - frac_h2osfc * dhsdT * dtime);
-        } else {
+        } else { /* unreached: frac_h2osfc > 0 in this branch */
           c2 = 0.0;
         }
         *t_soisno_sl1 = (c1 * *t_soisno_sl1 + c2 * *t_h2osfc) / (c1 + c2);
@@ -484,7 +484,7 @@ void elmo_st_phase_change_h2osfc(int snl, double dtime, double frac_sno, double 
         c1 = frac_sno * (dtime / fact_sl1 - dhsdT * dtime);
         if (frac_h2osfc != 0.0) {
           c2 = frac_h2osfc * (c_h2osfc - dtime * dhsdT);
-        } else {
+        } else { /* unreached: frac_h2osfc > 0 in this branch */
           c2 = 0.0;
         }
         *t_soisno_sl1 = (c1 * *t_soisno_sl1 + c2 * *t_h2osfc) / (c1 + c2);
@@ -493,7 +493,7 @@ void elmo_st_phase_change_h2osfc(int snl, double dtime, double frac_sno, double 
         c1 = frac_sno / fact_sl1 * dtime;
         if (frac_h2osfc != 0.0) {
           c2 = frac_h2osfc * (c_h2osfc - dtime * dhsdT);
-        } else {
+        } else { /* unreached: frac_h2osfc > 0 in this branch */
           c2 = 0.0;
         }
         *t_soisno_sl1 = (c1 * *t_soisno_sl1 + c2 * *t_h2osfc) / (c1 + c2);
@@ -627,7 +627,7 @@ void elmo_st_phase_change_soisno(int snl, int ltype, double dtime, double dhsdT,
         if (i < NSNO) {
           h2osoi_ice[i] = dmin(wmass0, wice0 - xm);
         } else {
-          if (wmass0 < supercool[i - NSNO]) {
+          if (wmass0 < supercool[i - NSNO]) { /* unreached: xm < 0 only for imelt == 2, which needs liquid above supercool, so wmass0 >= supercool */
             h2osoi_ice[i] = 0.0;
           } else {
             h2osoi_ice[i] = dmin(wmass0 - supercool[i - NSNO], wice0 - xm);

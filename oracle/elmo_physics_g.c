@@ -91,7 +91,7 @@ void elmo_snow_aging(int do_capsnow, int snl, double frac_sno, double dtime, dou
       double dr_fresh = snw_rds[i] - SNW_RDS_MIN;
       if (fabs(dr_fresh) < 1.0e-8) {
         dr_fresh = 0.0;
-      } else if (dr_fresh < 0.0) {
+      } else if (dr_fresh < 0.0) { /* unreached: throw site of the reference (snow_hydrology_impl.hh:152): tests/test_oracle_vs_ref.py::test_snow_hydrology_stages_bitwise_vs_reference */
         *err |= ELMO_ERR_SNOW_AGE_DRFRESH; /* throw at :152 */
       }
       double dr = (bst_drdt0 * pow(bst_tau / (dr_fresh + bst_tau), 1.0 / bst_kappa)) * (dtime / 3600.0);

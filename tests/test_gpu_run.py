@@ -29,10 +29,10 @@ def same(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
-def _inputs(n, seed, nrec=NREC):
+def _inputs(n, seed, nrec=NREC, tier="B"):
     """State, geography, nrec hourly records per forcing stream and 12 months per phenology field, all [records, n]."""
     ft = st.field_table()
-    cols, scal, soil = synth.make_state(ft, n, tier="B", seed=seed)
+    cols, scal, soil = synth.make_state(ft, n, tier=tier, seed=seed)
     lat, lon = synth.global_grid(n, seed=seed + 1)
     rng = np.random.default_rng(seed + 2)
     rec = {}

@@ -100,9 +100,9 @@ def test_solar_geometry_matches_the_reference_over_the_globe(tmp_path):
     D.close()
 
 
-def _global_pair(n, seed, lat=None, lon=None):
+def _global_pair(n, seed, lat=None, lon=None, tier="B"):
     ft = st.field_table()
-    cols, scal, soil = synth.make_state(ft, n, tier="B", seed=seed)
+    cols, scal, soil = synth.make_state(ft, n, tier=tier, seed=seed)
     D = H.device_state(cols, scal, soil)
     if lat is None:
         lat, lon = synth.global_grid(n, seed=seed)
