@@ -87,6 +87,9 @@ SIGNATURES = {
     "elmk_series_upload": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int64]),
     "elmk_run": (C.c_int, [_P, C.c_double, _P, C.c_int, C.c_int]),
     "elmk_run_diagnostics": (C.c_int, [_P, _P, _P, _P]),
+    "elmk_set_forcing_grid": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
+    "elmk_clear_forcing_grid": (C.c_int, [_P]),
+    "elmk_upload_gridded": (C.c_int, [_P, C.c_int, C.c_int, _P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -115,6 +116,7 @@ struct elmk_ctx {
   // buffer is reused only after that run has finished, so the read set of every unfinished run is known to elmk_series_upload.
   struct Run {
     int slots = 0, max_steps = 0;
+    int64_t fcols = 0, fstride = 0;  // forcing series: entries per record (columns, or cells in grid mode) and the record stride
     char* mem = nullptr;
     size_t bytes = 0;
     char* forc = nullptr;
@@ -134,6 +136,17 @@ struct elmk_ctx {
     int last_buf = -1, last_nsteps = 0;
     int flags = 0;  // of the run being enqueued (launch_stage_run)
   } run;
+  // forcing on a coarser grid (elmk_set_forcing_grid): one allocation `mem` holds the ELL map [npad][ld] - idx (int32), w (fp64);
+  // npts rounded up to npad = 1, 2, 4 or 8 with padding rows idx = -1 - and the fp64 staging of elmk_upload_gridded (ncells values)
+  struct Grid {
+    int64_t ncells = 0;
+    int npts = 0, npad = 0;
+    char* mem = nullptr;
+    size_t bytes = 0;
+    int32_t* idx = nullptr;
+    double* w = nullptr;
+    double* cells = nullptr;
+  } grid;
   std::string err;
 };
 
@@ -221,6 +234,7 @@ void run_release(elmk_ctx* ctx)
   R.rows = nullptr;
   R.bytes = 0;
   R.slots = R.max_steps = 0;
+  R.fcols = R.fstride = 0;
   R.live[0] = R.live[1] = false;
   R.count = 0;
   R.last_buf = -1;
@@ -386,6 +400,7 @@ int elmk_destroy(elmk_ctx* ctx)
   for (GraphSlot& g : ctx->graph)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   run_release(ctx);
+  if (ctx->grid.mem) (void)hipFree(ctx->grid.mem);
   if (ctx->run.upload) {
     (void)hipStreamSynchronize(ctx->run.upload);
     (void)hipStreamDestroy(ctx->run.upload);
@@ -472,7 +487,7 @@ int64_t elmk_level_stride(const elmk_ctx* ctx) { return ctx ? ctx->ld : -1; }
 int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
   return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
-                         ctx->run.bytes)
+                         ctx->run.bytes + ctx->grid.bytes)
              : -1;
 }
 
@@ -1392,6 +1407,20 @@ bool capturing(elmk_ctx* ctx, hipStream_t s, bool* out)
   return true;
 }
 
+// wait for the runs in flight (they read the run buffers) and for the upload stream (it may still write them), drop the captured
+// step (it holds the old addresses and launch shape) and release the reservation: elmk_run_reserve, elmk_set_forcing_grid and
+// elmk_clear_forcing_grid
+int run_drop(elmk_ctx* ctx)
+{
+  elmk_ctx::Run& R = ctx->run;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (R.upload) HIPCHK(hipStreamSynchronize(R.upload));
+  if (ctx->graph[3].exec) (void)hipGraphExecDestroy(ctx->graph[3].exec);
+  ctx->graph[3].exec = nullptr;
+  run_release(ctx);
+  return ELMK_OK;
+}
+
 // one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
 // forcing, init_timestep, advance_physics' stages, conservation -> ring row, flag summary -> ring row, history, next row
 constexpr int RUN_NSTAGE = 4 + ADV_NSTAGE + 4;
@@ -1405,7 +1434,13 @@ void launch_stage_run(elmk_ctx* ctx, int k, double dt)
   switch (k < 4 ? k : k - ADV_NSTAGE) {
     case 0: launch_solar_geometry_run(ctx->d, ctx->ncols, R.table, R.cursor, ctx->stream); break;
     case 1: launch_phenology_run(ctx->d, ctx->ncols, R.table, R.cursor, R.phen, ctx->stream); break;
-    case 2: launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream); break;
+    case 2:
+      if (ctx->grid.mem)
+        launch_get_forcing_run_grid(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, R.fstride, ctx->grid.npad, ctx->grid.idx,
+                                    ctx->grid.w, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
+      else
+        launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
+      break;
     case 3: launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); break;
     case 4: {
       double* diag = ELMK_GENERIC(ctx->h.cons_diag);
@@ -1435,13 +1470,7 @@ int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
   if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
   if (cap) return invalid(ctx, "elmk_run_reserve: the stream is being captured");
   elmk_ctx::Run& R = ctx->run;
-  // the runs in flight read the old buffers, an upload may still write them: wait for both, then drop the captured step (it holds
-  // the old addresses)
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (R.upload) HIPCHK(hipStreamSynchronize(R.upload));
-  if (ctx->graph[3].exec) (void)hipGraphExecDestroy(ctx->graph[3].exec);
-  ctx->graph[3].exec = nullptr;
-  run_release(ctx);
+  if (int rc = run_drop(ctx)) return rc;
   if (!R.upload) {
     HIPCHK(hipStreamCreateWithFlags(&R.upload, hipStreamNonBlocking));
     for (int b = 0; b < 2; b++) {
@@ -1449,7 +1478,9 @@ int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
     }
   }
   const size_t es = (size_t)store_size(ELMK_F64), ld = (size_t)ctx->ld, nrow = 2 * (size_t)max_steps;
-  const size_t forc_b = align_up((size_t)RUN_NFORC * forcing_slots * ld * es, 256);
+  // with a forcing grid the forcing records are cell records, [RUN_NFORC][slots][ncells] without padding
+  const int64_t fstride = ctx->grid.mem ? ctx->grid.ncells : ctx->ld;
+  const size_t forc_b = align_up((size_t)RUN_NFORC * forcing_slots * (size_t)fstride * es, 256);
   const size_t phen_b = align_up((size_t)RUN_NPHEN * RUN_NMONTH * ld * es, 256);
   const size_t tab_b = align_up(nrow * sizeof(RunRow), 256);
   const size_t cur_b = 256;
@@ -1483,6 +1514,8 @@ int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
   R.bytes = bytes;
   R.slots = forcing_slots;
   R.max_steps = max_steps;
+  R.fcols = ctx->grid.mem ? ctx->grid.ncells : ctx->ncols;
+  R.fstride = fstride;
   if (hip_fail(ctx, hipMemsetAsync(R.mem, 0, bytes, ctx->stream), "hipMemset(run)") ||
       hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
     run_release(ctx);
@@ -1504,8 +1537,9 @@ int elmk_series_upload(elmk_ctx* ctx, int field, int slot0, int nslots, const do
   const int k = forcing ? field - ELMK_FIELD_atm_tbot : field - ELMK_FIELD_mlai;
   const int nsl = forcing ? R.slots : RUN_NMONTH;
   if (slot0 < 0 || nslots < 0 || slot0 + (int64_t)nslots > nsl) return invalid(ctx, "elmk_series_upload: slots out of range");
-  if ((!host && n > 0 && nslots > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols)
-    return invalid(ctx, "elmk_series_upload: bad column range");
+  const int64_t ncol = forcing ? R.fcols : ctx->ncols, stride = forcing ? R.fstride : ctx->ld;  // (cells in grid mode)
+  if ((!host && n > 0 && nslots > 0) || col0 < 0 || n < 0 || col0 + n > ncol)
+    return invalid(ctx, "elmk_series_upload: bad column (grid mode: cell) range");
   if (n == 0 || nslots == 0) return ELMK_OK;
   // never write under a run that reads these records: wait for the end of each enqueued run that does
   for (int b = 0; b < 2; b++) {
@@ -1515,7 +1549,7 @@ int elmk_series_upload(elmk_ctx* ctx, int field, int slot0, int nslots, const do
     if (hit) HIPCHK(hipEventSynchronize(R.done[b]));
   }
   const size_t es = (size_t)store_size(ELMK_F64);
-  char* dst = (forcing ? R.forc : R.phen) + (((size_t)k * nsl + slot0) * (size_t)ctx->ld + (size_t)col0) * es;
+  char* dst = (forcing ? R.forc : R.phen) + (((size_t)k * nsl + slot0) * (size_t)stride + (size_t)col0) * es;
   const void* src = host;
   std::vector<float> tmp;
   if (kStateF32) {  // rounded to the stored fp32 as xfer rounds an upload
@@ -1524,7 +1558,7 @@ int elmk_series_upload(elmk_ctx* ctx, int field, int slot0, int nslots, const do
     for (size_t i = 0; i < cnt; i++) tmp[i] = (float)host[i];
     src = tmp.data();
   }
-  HIPCHK(hipMemcpy2DAsync(dst, (size_t)ctx->ld * es, src, (size_t)n * es, (size_t)n * es, (size_t)nslots, hipMemcpyHostToDevice, R.upload));
+  HIPCHK(hipMemcpy2DAsync(dst, (size_t)stride * es, src, (size_t)n * es, (size_t)n * es, (size_t)nslots, hipMemcpyHostToDevice, R.upload));
   HIPCHK(hipStreamSynchronize(R.upload));  // (caller's pageable source; a run enqueued after this call sees the records)
   return ELMK_OK;
 }
@@ -1619,6 +1653,105 @@ int elmk_run_diagnostics(elmk_ctx* ctx, double* min_max_sum, uint32_t* flags_or,
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < f.size(); i++) first_bad_col[i] = (f[i] == 0x7fffffffffffffffll) ? -1 : (int64_t)f[i];
   return (int)n;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// forcing on a coarser grid: a per-column ELL remap map on the device (include/elmk.h "forcing grid")
+// ---------------------------------------------------------------------------------------------------
+namespace {
+void grid_release(elmk_ctx* ctx)
+{
+  elmk_ctx::Grid& G = ctx->grid;
+  if (G.mem) (void)hipFree(G.mem);
+  G = elmk_ctx::Grid{};
+}
+}  // namespace
+
+int elmk_set_forcing_grid(elmk_ctx* ctx, int64_t ncells, int npts, const int32_t* idx, const double* w)
+{
+  if (int rc = enter(ctx)) return rc;
+  const int64_t n = ctx->ncols;
+  if (npts < 1 || npts > 8) return invalid(ctx, "elmk_set_forcing_grid: npts outside 1 .. 8");
+  if (ncells < 1 || ncells > INT32_MAX) return invalid(ctx, "elmk_set_forcing_grid: ncells outside 1 .. 2^31-1");
+  if (n > 0 && (!idx || !w)) return invalid(ctx, "elmk_set_forcing_grid: null map");
+  // every gather of the remap kernels stays inside a cell record because of these checks
+  for (int k = 0; k < npts; k++) {
+    const int32_t* ik = idx + (size_t)k * n;
+    const double* wk = w + (size_t)k * n;
+    const int32_t lo = k == 0 ? 0 : -1;
+    for (int64_t c = 0; c < n; c++) {
+      if (ik[c] < lo || ik[c] >= ncells)
+        return invalid(ctx, k == 0 ? "elmk_set_forcing_grid: idx[0] outside [0, ncells)" : "elmk_set_forcing_grid: idx outside [-1, ncells)");
+      if (ik[c] >= 0 && !std::isfinite(wk[c])) return invalid(ctx, "elmk_set_forcing_grid: non-finite weight");
+    }
+  }
+  bool cap = false;
+  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
+  if (cap) return invalid(ctx, "elmk_set_forcing_grid: the stream is being captured");
+  if (int rc = run_drop(ctx)) return rc;
+  grid_release(ctx);
+  elmk_ctx::Grid& G = ctx->grid;
+  const int npad = npts <= 1 ? 1 : npts <= 2 ? 2 : npts <= 4 ? 4 : 8;
+  const size_t ld = (size_t)ctx->ld;
+  const size_t idx_b = align_up((size_t)npad * ld * sizeof(int32_t), 256), w_b = align_up((size_t)npad * ld * sizeof(double), 256);
+  const size_t cell_b = align_up((size_t)ncells * sizeof(double), 256);
+  if (hip_fail(ctx, hipMalloc((void**)&G.mem, idx_b + w_b + cell_b), "hipMalloc(forcing grid)")) {
+    G.mem = nullptr;
+    return ELMK_E_NOMEM;
+  }
+  G.bytes = idx_b + w_b + cell_b;
+  G.idx = (int32_t*)G.mem;
+  G.w = (double*)(G.mem + idx_b);
+  G.cells = (double*)(G.mem + idx_b + w_b);
+  G.ncells = ncells;
+  G.npts = npts;
+  G.npad = npad;
+  // padding rows and the columns past ncols: idx -1 (all bits set), w 0
+  int rc = ELMK_OK;
+  if (hip_fail(ctx, hipMemsetAsync(G.idx, 0xFF, idx_b, ctx->stream), "hipMemset(grid idx)") ||
+      hip_fail(ctx, hipMemsetAsync(G.w, 0, w_b + cell_b, ctx->stream), "hipMemset(grid w)"))
+    rc = ELMK_E_HIP;
+  else if (n > 0 &&
+           (hip_fail(ctx, hipMemcpy2DAsync(G.idx, ld * sizeof(int32_t), idx, (size_t)n * sizeof(int32_t), (size_t)n * sizeof(int32_t),
+                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(grid idx)") ||
+            hip_fail(ctx, hipMemcpy2DAsync(G.w, ld * sizeof(double), w, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
+                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(grid w)")))
+    rc = ELMK_E_HIP;
+  if (rc == ELMK_OK && hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) rc = ELMK_E_HIP;
+  if (rc != ELMK_OK) grid_release(ctx);
+  return rc;
+}
+
+int elmk_clear_forcing_grid(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  bool cap = false;
+  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
+  if (cap) return invalid(ctx, "elmk_clear_forcing_grid: the stream is being captured");
+  if (int rc = run_drop(ctx)) return rc;
+  grid_release(ctx);
+  return ELMK_OK;
+}
+
+int elmk_upload_gridded(elmk_ctx* ctx, int field, int level, const double* cells)
+{
+  if (int rc = enter(ctx)) return rc;
+  const elmk_ctx::Grid& G = ctx->grid;
+  if (!G.mem) return invalid(ctx, "elmk_upload_gridded: no forcing grid (elmk_set_forcing_grid)");
+  if (!field_ok(field) || g_fields[field].dtype != ELMK_F64) return invalid(ctx, "elmk_upload_gridded: not an fp64 field");
+  if (level < 0 || level >= g_fields[field].nlev) return invalid(ctx, "elmk_upload_gridded: level out of range");
+  if (!cells) return invalid(ctx, "elmk_upload_gridded: null cells");
+  bool cap = false;
+  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
+  if (cap) return invalid(ctx, "elmk_upload_gridded: the stream is being captured");
+  if (ctx->ncols == 0) return ELMK_OK;
+  char* dst = (char*)ctx->fptr[field] + (size_t)level * (size_t)ctx->ld * (size_t)store_size(ELMK_F64);
+  // staging is reused by the next call: the copy and the remap are done when this returns, as elmk_upload's copy is
+  HIPCHK(hipMemcpyAsync(G.cells, cells, (size_t)G.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  launch_remap_field(dst, G.cells, ctx->ncols, ctx->ld, G.npad, G.idx, G.w, ctx->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -108,6 +108,12 @@ void launch_solar_geometry_run(const DevState* S, int64_t n, const RunRow* rows,
 void launch_phenology_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* phen, hipStream_t st);
 void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
                             int qbot_is_rh, hipStream_t st);
+// forcing on a coarser grid (elmk_set_forcing_grid): the map idx / w is [npts][ld] (npts = 1, 2, 4 or 8, padding idx = -1).
+// launch_get_forcing_run_grid: launch_get_forcing_run over cell series [RUN_NFORC][slots][ncells], remapped per column.
+// launch_remap_field: dst[c] = the remap of cells (fp64, ncells values) for columns [0, n); dst is one level of an fp64 state field.
+void launch_get_forcing_run_grid(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
+                                 int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st);
+void launch_remap_field(void* dst, const double* cells, int64_t n, int64_t ld, int npts, const int32_t* idx, const double* w, hipStream_t st);
 // launch_conservation with the (min, max, sum) triples written to ring row *cursor (cons_ring: [row][8][3]); also opens the flag
 // row of the step (flag_or 0, flag_first "none") for launch_flag_reduce_run
 void launch_conservation_run(const DevState* S, int64_t n, int64_t ld, double dt, const double* diag, double* part, double* cons_ring,

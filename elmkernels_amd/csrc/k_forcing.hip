@@ -46,22 +46,26 @@ struct ForcingWeights {
 // t_idx + 1 at l1[k] + c - the levels of atm_* for elmk_get_forcing, two slots of the forcing series for elmk_run
 struct ForcingSrc {
   dfield l0[RUN_NFORC], l1[RUN_NFORC];
+  __device__ __forceinline__ double get(int k, int lev, int64_t c) const { return lev ? (double)l1[k][c] : (double)l0[k][c]; }
 };
 #define SV(k, lev) src.l##lev[k][c]
+#define FV(k, lev) src.get(k, lev, c)
 
-// one column: the body of k_get_forcing and of its run-mode variant
-__device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, int64_t c, const ForcingWeights& W, const ForcingSrc& src)
+// one column: the body of k_get_forcing and of its run-mode variants; Src::get(k, lev, c) is record t_idx + lev of stream k at
+// column c (ForcingSrc: per-column records; GridForcingSrc: cell records remapped through the forcing grid)
+template <class Src>
+__device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, int64_t c, const ForcingWeights& W, const Src& src)
 {
   const int64_t ld = S->ld;
   // ProcessTBOT :38-42
-  const double tbot = dmin(interp_forcing(W.wt1[0], W.wt2[0], SV(0, 0), SV(0, 1)), 323.0);
+  const double tbot = dmin(interp_forcing(W.wt1[0], W.wt2[0], FV(0, 0), FV(0, 1)), 323.0);
   S->forc_tbot[c] = tbot;
   S->forc_thbot[c] = tbot;
   // ProcessPBOT :55-58
-  const double pbot = dmax(interp_forcing(W.wt1[1], W.wt2[1], SV(1, 0), SV(1, 1)), 4.0e4);
+  const double pbot = dmax(interp_forcing(W.wt1[1], W.wt2[1], FV(1, 0), FV(1, 1)), 4.0e4);
   S->forc_pbot[c] = pbot;
   // ProcessQBOT :73-81
-  double qbot = dmax(interp_forcing(W.wt1[2], W.wt2[2], SV(2, 0), SV(2, 1)), 1.0e-9);
+  double qbot = dmax(interp_forcing(W.wt1[2], W.wt2[2], FV(2, 0), FV(2, 1)), 1.0e-9);
   if (W.qbot_is_rh) {
     const double e = (tbot > TFRZ) ? esatw(tdc(tbot)) : esati(tdc(tbot));
     const double qsat = 0.622 * e / (pbot - 0.378 * e);
@@ -69,7 +73,7 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
   }
   S->forc_qbot[c] = qbot;
   // ProcessFLDS :97-107
-  const double flds = interp_forcing(W.wt1[3], W.wt2[3], SV(3, 0), SV(3, 1));
+  const double flds = interp_forcing(W.wt1[3], W.wt2[3], FV(3, 0), FV(3, 1));
   double lwrad = flds;
   if (flds <= 50.0 || flds >= 600.0) {
     const double e = pbot * qbot / (0.622 + 0.378 * qbot);
@@ -79,7 +83,7 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
   S->forc_lwrad[c] = lwrad;
   // ProcessFSDS :122-142 (record t_idx only); pow(x, 2.0) is x * x in the reference's optimised builds (elmk_math.h)
   {
-    const double swndr = dmax(SV(4, 0) * S->coszen[c] * 0.5, 0.0);
+    const double swndr = dmax(FV(4, 0) * S->coszen[c] * 0.5, 0.0);
     const double swndf = swndr, swvdr = swndr, swvdf = swndr;
     const double ratio_rvrf_vis =
         dmin(0.99, dmax(0.17639 + 0.00380 * swvdr - 9.0039e-06 * elmk_sq(swvdr) + 8.1351e-09 * elmk_pow(swvdr, 3.0), 0.01));
@@ -94,12 +98,12 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
   {
     const double frac1 = (tbot - TFRZ) * 0.5;
     const double frac2 = dmin(1.0, dmax(0.0, frac1));
-    const double prec = dmax(SV(5, 0), 0.0);
+    const double prec = dmax(FV(5, 0), 0.0);
     S->forc_rain[c] = frac2 * prec;
     S->forc_snow[c] = (1.0 - frac2) * prec;
   }
   // ProcessWIND :177-181
-  S->forc_u[c] = interp_forcing(W.wt1[6], W.wt2[6], SV(6, 0), SV(6, 1));
+  S->forc_u[c] = interp_forcing(W.wt1[6], W.wt2[6], FV(6, 0), FV(6, 1));
   S->forc_v[c] = 0.0;
   // ProcessZBOT :195-203 (hardwired 30 m)
   S->forc_hgt[c] = 30.0;
@@ -107,6 +111,54 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
   S->forc_hgt_t_patch[c] = 30.0;
   S->forc_hgt_q_patch[c] = 30.0;
 }
+
+// ---- forcing on a coarser grid (elmk_set_forcing_grid) -------------------------------------------------------------------------
+// The map is ELL: NPTS rows idx[k][column] (int32) and w[k][column] (fp64), SoA with the state's level stride; idx = -1 is padding
+// (every row k >= 1 may hold it, row 0 never does - elmk_api.cpp checks both on the host, so every gather is inside the cell
+// record).  The value of column c is defined by this operation order (include/elmk.h), which regrid.apply_map restates on the host:
+//   v = w[0] * a[idx[0]];  then for k = 1 .. NPTS-1: if idx[k] >= 0: v = v + w[k] * a[idx[k]]
+// Padding is skipped, not multiplied by zero: -0.0 stays -0.0 and a non-finite cell behind a padding slot is never read.
+// NPTS is wave-uniform (the map's width, rounded up to 1, 2, 4 or 8 with padding rows), so the loop is unrolled per width.
+#ifndef ELMK_GRID_MAP_NT
+// 1: nontemporal hint on the map loads.  Not taken: in an interleaved A/B at 1 M columns (profiles/r08_forcing_grid_cost.jsonl, the
+// rows with "ab_lib") the hint made 6 of 8 grid configurations 1-4 % slower per step and 2 (nearest, ncols / 150 cells) 4-5 % faster.
+#define ELMK_GRID_MAP_NT 0
+#endif
+template <typename T> __device__ __forceinline__ T map_load(gptr<const T> p)
+{
+  if (ELMK_GRID_MAP_NT) return __builtin_nontemporal_load(p);
+  return *p;
+}
+
+template <int NPTS, class A>
+__device__ __forceinline__ double remap_cells(const int32_t (&idx)[NPTS], const double (&w)[NPTS], const A& a)
+{
+  double v = w[0] * (double)a[idx[0]];
+#pragma unroll
+  for (int k = 1; k < NPTS; k++)
+    if (idx[k] >= 0) v = v + w[k] * (double)a[idx[k]];
+  return v;
+}
+
+// the map row of column c, loaded once (coalesced) and reused by every stream and record that column reads
+template <int NPTS>
+__device__ __forceinline__ void load_map_row(gptr<const int32_t> midx, gptr<const double> mw, int64_t ld, int64_t c, int32_t (&idx)[NPTS],
+                                             double (&w)[NPTS])
+{
+#pragma unroll
+  for (int k = 0; k < NPTS; k++) {
+    idx[k] = map_load(midx + (int64_t)k * ld + c);
+    w[k] = map_load(mw + (int64_t)k * ld + c);
+  }
+}
+
+// the source of get_forcing_col in grid mode: record t_idx + lev of stream k is the cell record l0[k] / l1[k] remapped to column c
+template <int NPTS> struct GridForcingSrc {
+  dfield l0[RUN_NFORC], l1[RUN_NFORC];
+  int32_t idx[NPTS];
+  double w[NPTS];
+  __device__ __forceinline__ double get(int k, int lev, int64_t) const { return remap_cells<NPTS>(idx, w, lev ? l1[k] : l0[k]); }
+};
 
 // the two months a column reads of mlai, msai, mhtop, mhbot (in this order): month start_idx at l0[k] + c, start_idx + 1 at
 // l1[k] + c - the levels of the fields for elmk_phenology, two months of the phenology series for elmk_run
@@ -192,6 +244,48 @@ __global__ __launch_bounds__(256) void k_get_forcing_run(const DevState* __restr
   get_forcing_col(S, c, W, src);
 }
 
+// elmk_run with a forcing grid: the series hold cell records [RUN_NFORC][slots][ncells]; the body is k_get_forcing_run's, fed the
+// remapped records (FSDS and PREC read record t_idx only, as there)
+template <int NPTS>
+__global__ __launch_bounds__(256) void k_get_forcing_run_grid(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                              const int32_t* __restrict__ cursor, const dfield forc, int slots,
+                                                              int64_t ncells, gptr<const int32_t> midx, gptr<const double> mw, int qbot_is_rh)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const RunRow* __restrict__ r = rows + *cursor;
+  ForcingWeights W;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    W.wt1[i] = r->forc_wt1[i];
+    W.wt2[i] = r->forc_wt2[i];
+  }
+  W.qbot_is_rh = qbot_is_rh;
+  const int64_t slot = r->forc_slot;
+  GridForcingSrc<NPTS> src;
+#pragma unroll
+  for (int k = 0; k < RUN_NFORC; k++) {
+    src.l0[k] = forc + ((int64_t)k * slots + slot) * ncells;
+    src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ncells;
+  }
+  load_map_row<NPTS>(midx, mw, ld, c, src.idx, src.w);
+  get_forcing_col(S, c, W, src);
+}
+
+// elmk_upload_gridded: one level of an fp64 field from fp64 cell values (stored at state precision: fp32 in libelmk_f32.so)
+template <int NPTS>
+__global__ __launch_bounds__(256) void k_remap_field(dfield dst, gptr<const double> cells, int64_t n, int64_t ld, gptr<const int32_t> midx,
+                                                     gptr<const double> mw)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  int32_t idx[NPTS];
+  double w[NPTS];
+  load_map_row<NPTS>(midx, mw, ld, c, idx, w);
+  dst[c] = remap_cells<NPTS>(idx, w, cells);
+}
+
 __global__ __launch_bounds__(256) void k_phenology_run(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
                                                        const int32_t* __restrict__ cursor, const dfield phen)
 {
@@ -233,6 +327,38 @@ void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, co
   if (n <= 0) return;
   hipLaunchKernelGGL(k_get_forcing_run, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, rows, cursor,
                      field_of<ELMK_F64>::from(const_cast<void*>(forc)), slots, qbot_is_rh);
+}
+
+void launch_get_forcing_run_grid(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
+                                 int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st)
+{
+  if (n <= 0) return;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const dfield f = field_of<ELMK_F64>::from(const_cast<void*>(forc));
+  const gptr<const int32_t> mi = (gptr<const int32_t>)idx;
+  const gptr<const double> mw = (gptr<const double>)w;
+  switch (npts) {
+    case 1: hipLaunchKernelGGL(k_get_forcing_run_grid<1>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh); break;
+    case 2: hipLaunchKernelGGL(k_get_forcing_run_grid<2>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh); break;
+    case 4: hipLaunchKernelGGL(k_get_forcing_run_grid<4>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh); break;
+    default: hipLaunchKernelGGL(k_get_forcing_run_grid<8>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh); break;
+  }
+}
+
+void launch_remap_field(void* dst, const double* cells, int64_t n, int64_t ld, int npts, const int32_t* idx, const double* w, hipStream_t st)
+{
+  if (n <= 0) return;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const dfield d = field_of<ELMK_F64>::from(dst);
+  const gptr<const double> a = (gptr<const double>)cells;
+  const gptr<const int32_t> mi = (gptr<const int32_t>)idx;
+  const gptr<const double> mw = (gptr<const double>)w;
+  switch (npts) {
+    case 1: hipLaunchKernelGGL(k_remap_field<1>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+    case 2: hipLaunchKernelGGL(k_remap_field<2>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+    case 4: hipLaunchKernelGGL(k_remap_field<4>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+    default: hipLaunchKernelGGL(k_remap_field<8>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+  }
 }
 
 void launch_phenology_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* phen, hipStream_t st)

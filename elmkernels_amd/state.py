@@ -358,7 +358,8 @@ class ELMState:
 
     def series_upload(self, name, slot0, records, col0=0):
         """Records [slot0, slot0 + nslots) of one series field (SERIES_FORCING: forcing slots, SERIES_PHENOLOGY: months 0..11) from
-        records [nslots, n] (record-major), columns [col0, col0 + n).  Waits for a run in flight only if it reads those records."""
+        records [nslots, n] (record-major), columns [col0, col0 + n).  Waits for a run in flight only if it reads those records.
+        With a forcing grid set at run_reserve, SERIES_FORCING records are cell records: [nslots, n] cells [col0, col0 + n)."""
         a = np.ascontiguousarray(records, dtype=np.float64)
         if a.ndim == 1:
             a = a[None, :]
@@ -377,6 +378,33 @@ class ELMState:
         n = self._chk(self.lib.elmk_run_diagnostics(self.ctx, mms.ctypes.data_as(C.c_void_p), fo.ctypes.data_as(C.c_void_p),
                                                     fb.ctypes.data_as(C.c_void_p)), "run_diagnostics")
         return mms[:n].copy(), fo[:n].copy(), fb[:n].copy()
+
+    # -- forcing on a coarser grid (include/elmk.h: elmk_set_forcing_grid ...) -----------------------
+    def set_forcing_grid(self, idx, w, ncells):
+        """The per-column remap map (elmkernels_amd/regrid.py): idx int32 [npts, ncols] (-1 = padding, never in row 0), w float64
+        [npts, ncols], ncells source cells.  Releases the run reservation (run_reserve again before run)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if idx.ndim == 1:
+            idx, w = idx[None, :], w.reshape(1, -1)
+        if idx.shape != w.shape or idx.shape[1] != self.ncols:
+            raise ValueError(f"idx and w must both be [npts, {self.ncols}]")
+        self._chk(self.lib.elmk_set_forcing_grid(self.ctx, int(ncells), idx.shape[0], idx.ctypes.data_as(C.c_void_p),
+                                                 w.ctypes.data_as(C.c_void_p)), "set_forcing_grid")
+        self.grid_ncells = int(ncells)
+
+    def clear_forcing_grid(self):
+        """Per-column forcing again; releases the run reservation."""
+        self._chk(self.lib.elmk_clear_forcing_grid(self.ctx), "clear_forcing_grid")
+        self.grid_ncells = None
+
+    def upload_gridded(self, name, cells, level=0):
+        """One level of an fp64 field from cell values [ncells], remapped to every column on the device."""
+        a = np.ascontiguousarray(cells, dtype=np.float64).reshape(-1)
+        if getattr(self, "grid_ncells", None) is not None and a.size != self.grid_ncells:
+            raise ValueError(f"{name}: {a.size} cell values, the grid has {self.grid_ncells}")
+        self._chk(self.lib.elmk_upload_gridded(self.ctx, self.fields[name][0], int(level), a.ctypes.data_as(C.c_void_p)),
+                  f"upload_gridded({name})")
 
     def math_eval(self, fn, x, y=None):
         """elmk_math.h on the device: fn in MATH_FNS; returns fn(x), x / y or pow(x, y)."""
@@ -587,6 +615,17 @@ class ELMInterface:
             s = int(bad[0])
             raise RuntimeError(f"ELM physics error flags {int(fo[s]):#x} in step {s} of the run, first at column {int(fb[s])}")
         return False
+
+    def set_forcing_grid(self, idx, w, ncells):
+        """Forcing on the data set's own grid (ELMState.set_forcing_grid): then upload_gridded() per record, or reserve a run and
+        upload cell records with S.series_upload."""
+        self.S.set_forcing_grid(idx, w, ncells)
+
+    def clear_forcing_grid(self):
+        self.S.clear_forcing_grid()
+
+    def upload_gridded(self, name, cells, level=0):
+        self.S.upload_gridded(name, cells, level)
 
     def accumulate_history(self):
         """Fold this step's state into the history tapes registered on self.S (ELMState.history_add): call after advance()."""

@@ -40,6 +40,8 @@
  *   kokkos_evaluate_conservation    conserved_quantity_kokkos.hh      elmk_evaluate_conservation
  *   (ELM's history tapes: time averages, extremes, last values)       elmk_history_add / _accumulate / _read
  *   kokkos_driver.cc:54-85 time loop                                  elmk_run (elmk_run_reserve, elmk_series_upload)
+ *   AtmDataManager::data(ntimes, ncells) on the data set's own grid   elmk_set_forcing_grid, elmk_upload_gridded,
+ *     (src/data/atm_data.h:168-172; ELM's coupler maps it to land)     elmk_series_upload of cell records
  *   throw / assert inside physics   (list: SURVEY.md section 5)       per-column flag word, elmk_error_summary
  *
  * Conventions
@@ -317,6 +319,38 @@ int elmk_run_reserve(elmk_ctx *ctx, int forcing_slots, int max_steps);
 int elmk_series_upload(elmk_ctx *ctx, int field, int slot0, int nslots, const double *host, int64_t col0, int64_t n);
 int elmk_run(elmk_ctx *ctx, double dt, const elmk_run_step *steps, int nsteps, int flags);
 int elmk_run_diagnostics(elmk_ctx *ctx, double *min_max_sum, uint32_t *flags_or, int64_t *first_bad_col);
+
+/* ---- forcing grid ----------------------------------------------------------------------------
+ * Forcing on the data set's own grid (GSWP3 / CRUNCEP at 0.5 deg, ERA5 at 0.25 deg, an atmosphere's grid), remapped to the columns on
+ * the device through a per-column map: the host sends ncells values per record instead of ncols.
+ *   elmk_set_forcing_grid  the map, padded sparse rows in ELL form: up to npts source cells per column, idx[npts][ncols] and
+ *                          w[npts][ncols] (SoA, column fastest; copied, not retained).  The value of column c of cell values a[ncells]
+ *                          is, in this operation order and without contraction:
+ *                            v = w[0][c] * a[idx[0][c]];  then for k = 1 .. npts-1:  if idx[k][c] >= 0:  v = v + w[k][c] * a[idx[k][c]]
+ *                          idx = -1 is padding and is skipped, never multiplied by zero (-0.0 stays -0.0, a non-finite cell is not
+ *                          read).  elmkernels_amd/regrid.py: apply_map is this operation on the host; nearest_map, bilinear_map and
+ *                          from_sparse (a map file's row / col / S triplets) build maps, slice_map one rank's block.
+ *                          ELMK_E_INVALID, nothing enqueued: npts outside 1 .. 8, ncells outside 1 .. 2^31-1, idx[0][c] outside
+ *                          [0, ncells), idx[k][c] outside [-1, ncells) for k >= 1, a non-finite weight where idx >= 0, a stream being
+ *                          captured.  Replaces an earlier map.
+ *   elmk_clear_forcing_grid  forget the map: per-column forcing series again.
+ *   Both wait for the runs in flight and release the run reservation as a new elmk_run_reserve does (series contents lost, the
+ *   captured run step dropped); elmk_run refuses until the next elmk_run_reserve.
+ *   elmk_upload_gridded    level `level` of any fp64 per-column field (atm_*, aer_*, mlai .. mhbot, surface data ...) from cells[ncells]:
+ *                          the cells go to a staging buffer of the context, a kernel writes the remap of every column (stored at
+ *                          state precision: rounded to fp32 in libelmk_f32.so, as elmk_upload rounds).  Synchronises as elmk_upload.
+ *                          ELMK_E_INVALID without a map, for a field that is not fp64, a level out of range, a stream being captured.
+ *   Run mode: elmk_run_reserve while a map is set sizes the seven forcing series slots x ncells (cell records; the phenology series
+ *   stay per column); elmk_series_upload of atm_tbot .. atm_wind then takes cells [col0, col0 + n) of ncells, record-major
+ *   host[nslots][n].  elmk_run remaps both records of every stream per step inside its forcing kernel.  For every column a run gives
+ *   the bits of the same run over per-column series equal to the remap of each record (graph on and off).  In libelmk_f32.so the
+ *   cell records are stored as fp32 and the remap is done in fp64 before the forcing arithmetic, so that holds bitwise only for maps
+ *   with one term of weight 1.0 per column.
+ *   Device memory (elmk_device_bytes): the map, npad x (4 + 8) bytes x elmk_level_stride with npad = npts rounded up to 1, 2, 4 or 8
+ *   (padding rows), and ncells x 8 bytes of staging, each rounded up to 256 bytes. */
+int elmk_set_forcing_grid(elmk_ctx *ctx, int64_t ncells, int npts, const int32_t *idx /*[npts][ncols]*/, const double *w /*[npts][ncols]*/);
+int elmk_clear_forcing_grid(elmk_ctx *ctx);
+int elmk_upload_gridded(elmk_ctx *ctx, int field, int level, const double *cells /*[ncells]*/);
 
 /* ---- the physics wrappers (same names, order and arguments as driver/kokkos) ---------------- */
 int elmk_frac_wet(elmk_ctx *ctx);

@@ -273,6 +273,27 @@ class ELMInterface {
   }
   const std::vector<double>& run_conservation() const { return run_conservation_; }
 
+  /* Forcing on a coarser grid (elmk_set_forcing_grid): the per-column map idx[npts][ncols] / w[npts][ncols] over ncells source
+   * cells.  upload_gridded() remaps one level of an fp64 field from cells[ncells] on the device (the stepwise driver's path);
+   * after reserve_run() the forcing series hold cell records, filled by series_upload_cells(), host[nslots][ncells].  Setting or
+   * clearing the map releases the run reservation: reserve_run() again. */
+  void set_forcing_grid(int64_t ncells, int npts, const int32_t* idx, const double* w)
+  {
+    ok(elmk_set_forcing_grid(ctx_, ncells, npts, idx, w));
+    grid_ncells_ = ncells;
+  }
+  void clear_forcing_grid()
+  {
+    ok(elmk_clear_forcing_grid(ctx_));
+    grid_ncells_ = 0;
+  }
+  void upload_gridded(const char* field, int level, const double* cells) { ok(elmk_upload_gridded(ctx_, id(field), level, cells)); }
+  void series_upload_cells(const char* field, int slot0, int nslots, const double* host)
+  {
+    ok(elmk_series_upload(ctx_, id(field), slot0, nslots, host, 0, grid_ncells_));
+  }
+  int64_t grid_ncells() const { return grid_ncells_; }
+
   /* ELMInterface::copyPrimaryVars / getPrimaryVars (elm_kokkos_interface.cc:324-356) */
   void copyPrimaryVars(PrimaryVars& pv)
   {
@@ -325,6 +346,7 @@ class ELMInterface {
   double conservation_[8][3]{};
   uint32_t last_flags_{0};
   int max_steps_{0};
+  int64_t grid_ncells_{0};
   std::vector<double> run_conservation_;
 };
 
