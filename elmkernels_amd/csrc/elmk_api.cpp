@@ -52,6 +52,70 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 thread_local std::string g_create_error;
 constexpr int MAXLEV_STAGE = 21;  // widest field (zisoi)
 
+// The owner of one device allocation (hipMalloc), or with Pinned of one pinned host allocation (hipHostMalloc): freed by reset()
+// and by its destructor (a move assignment hands the old block to the moved-from owner).  Whoever frees has synchronised every
+// stream that may still use the memory (hipFree also synchronises the device, but nothing here relies on that).
+template <class T, bool Pinned = false>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { std::swap(p_, o.p_); }
+  DevBuf& operator=(DevBuf&& o) noexcept
+  {
+    std::swap(p_, o.p_);
+    return *this;
+  }
+  ~DevBuf() { (void)reset(); }
+  hipError_t alloc(size_t bytes)
+  {
+    (void)reset();
+    void* v = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&v, bytes, hipHostMallocDefault) : hipMalloc(&v, bytes);
+    p_ = e == hipSuccess ? (T*)v : nullptr;
+    return e;
+  }
+  hipError_t reset()
+  {
+    const hipError_t e = !p_ ? hipSuccess : Pinned ? hipHostFree(p_) : hipFree(p_);
+    p_ = nullptr;
+    return e;
+  }
+  operator T*() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
+
+// Lays regions out one after another in one block, each on a 256-byte boundary.  carve() runs a layout twice: over no block to
+// size it, then over the allocated block to hand each region's address to its pointer; *bytes is set once the block exists.
+struct Carve {
+  char* base;
+  size_t bytes = 0;
+  template <class P>
+  void take(P& dst, size_t n)
+  {
+    if (base) dst = (P)(base + bytes);
+    bytes += align_up(n, 256);
+  }
+};
+template <class Layout>
+hipError_t carve(DevBuf<char>& block, size_t* bytes, Layout layout)
+{
+  Carve sizing{nullptr};
+  layout(sizing);
+  if (const hipError_t e = block.alloc(sizing.bytes)) return e;
+  Carve place{block};
+  layout(place);
+  *bytes = sizing.bytes;
+  return hipSuccess;
+}
+
+// the list counters of the compacted kernels (ELMK_LIST_COUNT / ELMK_LIST_HEAD, one per CPAD words) and the classes of canopy_fluxes
+constexpr size_t COUNTERS_BYTES = ((size_t)(2 * NLISTS + CF_NCLS) * CPAD * 4 + 255) / 256 * 256;
+
+// the captured launch sequences of elmk_set_graph
+enum GraphId { GRAPH_TS7, GRAPH_FUSED, GRAPH_ADVANCE, GRAPH_RUN_STEP, GRAPH_N };
+
 }  // namespace
 
 struct GraphSlot {
@@ -59,6 +123,11 @@ struct GraphSlot {
   double dt = 0.0;
   hipStream_t stream = nullptr;
   uint64_t tag = 0;  // what else the captured launches depend on (elmk_run: its flags and the history table's version)
+  void drop()  // (nothing may still run it)
+  {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    exec = nullptr;
+  }
 };
 
 struct elmk_ctx {
@@ -69,55 +138,59 @@ struct elmk_ctx {
   int64_t ncols = 0;
   int64_t ld = 0;
   DevState h;            // host mirror of the device parameter block
-  DevState* d = nullptr; // device copy handed to kernels
+  DevBuf<DevState> d;    // device copy handed to kernels
   bool dirty = true;
-  char* arena = nullptr;
+  // every device allocation of the context is one of these DevBuf owners
+  DevBuf<char> arena;
   size_t arena_bytes = 0;
   void* fptr[ELMK_NUM_FIELDS] = {};
-  double* snicar = nullptr;
-  double* snowage = nullptr;  // SnwRdsTable (elmk_set_snow_age_tables)
-  char* scratch = nullptr;  // work arrays + work lists + queue counters of the compacted kernels
+  DevBuf<double> snicar;
+  DevBuf<double> snowage;  // SnwRdsTable (elmk_set_snow_age_tables)
+  DevBuf<char> scratch;  // work arrays + work lists + queue counters of the compacted kernels
   size_t scratch_bytes = 0;
-  char* staging = nullptr;  // device staging for layout conversion
+  // in scratch after DevState::cons_diag (diag [8][ld]): the stage-1 partials [8][ELMK_CONS_NPART][3] and the (min, max, sum)
+  // triples [8][3] of launch_conservation
+  double* cons_part = nullptr;
+  double* cons_out = nullptr;
+  DevBuf<char> staging;  // device staging for layout conversion
   size_t staging_bytes = 0;
   std::vector<int> snap_fields;  // elmk_snapshot_fields
-  std::vector<char*> snap_bufs;
-  uint32_t* red_or = nullptr;  // device scalars for elmk_error_summary
+  std::vector<DevBuf<double>> snap_bufs;
+  DevBuf<uint32_t> red_or;  // device scalars for elmk_error_summary
   long long* red_first = nullptr;
   // elmk_set_graph: the seven wrappers of elmk_timestep7 captured once as a HIP graph (kernel nodes + the side-stream
   // fork / join of albedo_snicar) and replayed; key = (dt, stream)
   bool use_graph = false;
   bool have_init_params = false;
-  GraphSlot graph[4];  // [0] elmk_timestep7, [1] elmk_timestep7_fused, [2] elmk_advance_physics, [3] one step of elmk_run
+  GraphSlot graph[GRAPH_N];
   // A HIP error may have cut a step short between the kernel that fills a work list and the one that drains it and leaves it
   // empty (the lists have no reset launch of their own): the next physics call zeroes every list counter first.
   bool lists_stale = false;
-  char* counters_raw = nullptr;
-  size_t counters_bytes = 0;
   // per-column solar geometry: DevState::geo and DevState::col_dayl in one allocation (elmk_set_column_geography); the mode flag
   // itself is side.col_dayl (elmk_solar_geometry sets it, elmk_clear_column_geography clears it)
-  double* geo = nullptr;
+  DevBuf<double> geo;
   bool geo_set = false;
   // history (elmk_history_*): the entries, their rows as the device table k_hist_accumulate reads (hist_table: the rows, then one
   // count per tape), and per tape whether it has accumulated since its last reset (elmk_history_add refuses such a tape)
   struct HistEntry {
     int tape, field, op, nlev, row0;
-    double* acc;
+    DevBuf<double> acc;
   };
   std::vector<HistEntry> hist;
   std::vector<HistRow> hist_rows;
-  char* hist_table = nullptr;
+  DevBuf<HistRow> hist_table;
   bool hist_dirty[ELMK_HIST_MAX_TAPES] = {};
   uint64_t hist_version = 0;  // counts elmk_history_add / _clear: a captured step of elmk_run holds the table of its moment
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
-  // is the pinned host copy of the step tables.  Per buffer, what the run last enqueued on it reads and the event of its end: a
-  // buffer is reused only after that run has finished, so the read set of every unfinished run is known to elmk_series_upload.
+  // is the pinned host copy of the step tables.  Per buffer, what the run last enqueued on it reads and the event of its end
+  // (run_done): a buffer is reused only after that run has finished, so the read set of every unfinished run is known to
+  // elmk_series_upload.  A new reservation starts from Run{}.
   struct Run {
     int slots = 0, max_steps = 0;
     int64_t fcols = 0, fstride = 0;  // forcing series: entries per record (columns, or cells in grid mode) and the record stride
-    char* mem = nullptr;
+    DevBuf<char> mem;
     size_t bytes = 0;
     char* forc = nullptr;
     char* phen = nullptr;
@@ -126,22 +199,22 @@ struct elmk_ctx {
     double* cons = nullptr;
     uint32_t* flag_or = nullptr;
     long long* flag_first = nullptr;
-    RunRow* rows = nullptr;
-    hipStream_t upload = nullptr;
-    hipEvent_t done[2] = {};
+    DevBuf<RunRow, true> rows;
     bool live[2] = {};
     int slot_lo[2] = {}, slot_hi[2] = {};
     unsigned months[2] = {};
     uint64_t count = 0;  // runs enqueued since the reserve
     int last_buf = -1, last_nsteps = 0;
-    int flags = 0;  // of the run being enqueued (launch_stage_run)
+    int flags = 0;  // of the run being enqueued (the run step's stages)
   } run;
+  hipStream_t upload = nullptr;  // of elmk_series_upload, with run_done created by the first elmk_run_reserve
+  hipEvent_t run_done[2] = {};
   // forcing on a coarser grid (elmk_set_forcing_grid): one allocation `mem` holds the ELL map [npad][ld] - idx (int32), w (fp64);
   // npts rounded up to npad = 1, 2, 4 or 8 with padding rows idx = -1 - and the fp64 staging of elmk_upload_gridded (ncells values)
   struct Grid {
     int64_t ncells = 0;
     int npts = 0, npad = 0;
-    char* mem = nullptr;
+    DevBuf<char> mem;
     size_t bytes = 0;
     int32_t* idx = nullptr;
     double* w = nullptr;
@@ -170,7 +243,7 @@ bool hip_fail(elmk_ctx* ctx, hipError_t e, const char* what)
     if (hip_fail(ctx, (call), #call)) return ELMK_E_HIP;  \
   } while (0)
 
-// Owners for the temporaries of the diagnostic entry points: released on every return path
+// Owner of the events of the diagnostic entry points: released on every return path
 struct EventList {
   std::vector<hipEvent_t> ev;
   hipError_t create(size_t n)
@@ -188,14 +261,6 @@ struct EventList {
   ~EventList()
   {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-};
-struct DevBuf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-  ~DevBuf()
-  {
-    if (p) (void)hipFree(p);
   }
 };
 
@@ -223,23 +288,6 @@ int enter(elmk_ctx* ctx)
 }
 
 bool field_ok(int f) { return f >= 0 && f < ELMK_NUM_FIELDS; }
-
-// the device and pinned memory of elmk_run_reserve (the caller has synchronised every stream that may use it)
-void run_release(elmk_ctx* ctx)
-{
-  elmk_ctx::Run& R = ctx->run;
-  if (R.mem) (void)hipFree(R.mem);
-  if (R.rows) (void)hipHostFree(R.rows);
-  R.mem = nullptr;
-  R.rows = nullptr;
-  R.bytes = 0;
-  R.slots = R.max_steps = 0;
-  R.fcols = R.fstride = 0;
-  R.live[0] = R.live[1] = false;
-  R.count = 0;
-  R.last_buf = -1;
-  R.last_nsteps = 0;
-}
 
 }  // namespace
 
@@ -284,57 +332,8 @@ int elmk_create(int64_t ncols, int device_id, elmk_ctx** out)
   }
   if (hip_fail(ctx, hipEventCreateWithFlags(&ctx->side.fork, hipEventDisableTiming), "hipEventCreate")) return fail(ELMK_E_HIP);
 
-  // arena layout
-  size_t off = 0;
-  size_t foff[ELMK_NUM_FIELDS];
-  for (int f = 0; f < ELMK_NUM_FIELDS; f++) {
-    foff[f] = off;
-    off += align_up((size_t)g_fields[f].nlev * (size_t)ctx->ld * store_size(g_fields[f].dtype), 256);
-  }
-  ctx->arena_bytes = off;
-  if (hip_fail(ctx, hipMalloc((void**)&ctx->arena, off), "hipMalloc(state arena)")) return fail(ELMK_E_NOMEM);
-  if (hip_fail(ctx, hipMemsetAsync(ctx->arena, 0, off, ctx->stream), "hipMemset(state arena)")) return fail(ELMK_E_HIP);
-  for (int f = 0; f < ELMK_NUM_FIELDS; f++) ctx->fptr[f] = ctx->arena + foff[f];
-
-  if (hip_fail(ctx, hipMalloc((void**)&ctx->snicar, SN_TOTAL * sizeof(double)), "hipMalloc(snicar)"))
-    return fail(ELMK_E_NOMEM);
-  if (hip_fail(ctx, hipMemsetAsync(ctx->snicar, 0, SN_TOTAL * sizeof(double), ctx->stream), "hipMemset(snicar)"))
-    return fail(ELMK_E_HIP);
-  if (hip_fail(ctx, hipMalloc((void**)&ctx->snowage, 3 * ELMK_SNOWAGE_N * sizeof(double)), "hipMalloc(snowage)"))
-    return fail(ELMK_E_NOMEM);
-  if (hip_fail(ctx, hipMemsetAsync(ctx->snowage, 0, 3 * ELMK_SNOWAGE_N * sizeof(double), ctx->stream), "hipMemset(snowage)"))
-    return fail(ELMK_E_HIP);
-  if (hip_fail(ctx, hipMalloc((void**)&ctx->d, sizeof(DevState)), "hipMalloc(params)")) return fail(ELMK_E_NOMEM);
-  const size_t wk_bytes = align_up((size_t)WK_N * (size_t)ctx->ld * 8, 256);
-  const size_t list_bytes = align_up((size_t)NLISTS * (size_t)ctx->ld * 4, 256);
-  const size_t cnt_bytes = align_up((size_t)(2 * NLISTS + CF_NCLS) * CPAD * 4, 256);
-  const size_t hint_bytes = align_up((size_t)ctx->ld * 4, 256);
-  // canopy_fluxes queue records (k_canopy_fluxes.hip), by queue position
-  const int64_t cf_nblk = (ncols + 255) / 256 > 0 ? (ncols + 255) / 256 : 1;
-  const size_t rec_bytes = align_up((size_t)CF_REC_N * (size_t)(ctx->ld + 8) * 8, 256);
-  const size_t fin_bytes = align_up((size_t)CF_FIN_N * (size_t)(ctx->ld + 8) * 8, 256);
-  const size_t irec_bytes = align_up((size_t)CF_IREC_N * (size_t)ctx->ld * 4, 256);
-  const size_t pos_bytes = align_up((size_t)ctx->ld * 4, 256);
-  const size_t blk_bytes = align_up((size_t)CF_NCLS * (size_t)cf_nblk * 4, 256);
-  const size_t cls_bytes = align_up((size_t)ctx->ld, 256);
-  const size_t given_bytes = align_up((size_t)3 * (size_t)ctx->ld * 8, 256);
-  const size_t snow_bytes = align_up((size_t)28 * (size_t)ctx->ld * 8, 256);
-  const size_t cons_bytes = align_up((size_t)8 * (size_t)ctx->ld * 8 + (size_t)8 * ELMK_CONS_NPART * 3 * 8 + 8 * 3 * 8, 256);
-  ctx->scratch_bytes = wk_bytes + list_bytes + cnt_bytes + hint_bytes + rec_bytes + fin_bytes + irec_bytes + pos_bytes + blk_bytes + cls_bytes + given_bytes + snow_bytes + cons_bytes;
-  if (hip_fail(ctx, hipMalloc((void**)&ctx->scratch, ctx->scratch_bytes), "hipMalloc(scratch)")) return fail(ELMK_E_NOMEM);
-  if (hip_fail(ctx, hipMemsetAsync(ctx->scratch, 0, ctx->scratch_bytes, ctx->stream), "hipMemset(scratch)"))
-    return fail(ELMK_E_HIP);
-  if (hip_fail(ctx, hipMalloc((void**)&ctx->red_or, 16), "hipMalloc(reduce)")) return fail(ELMK_E_NOMEM);
-  ctx->red_first = (long long*)((char*)ctx->red_or + 8);
-
-  // staging: up to 32 MiB, at least one 64-column tile of the widest field
-  size_t want = (size_t)MAXLEV_STAGE * 8 * (size_t)(ncols > 0 ? ncols : 1);
-  if (want > ((size_t)32 << 20)) want = (size_t)32 << 20;
-  if (want < (size_t)MAXLEV_STAGE * 8 * 64) want = (size_t)MAXLEV_STAGE * 8 * 64;
-  ctx->staging_bytes = want;
-  if (hip_fail(ctx, hipMalloc((void**)&ctx->staging, want), "hipMalloc(staging)")) return fail(ELMK_E_NOMEM);
-
-  // parameter block defaults: LandType() (land_data.h:38) and ELMState scalars (elm_state.h:221-224)
+  // parameter block defaults: LandType() (land_data.h:38) and ELMState scalars (elm_state.h:221-224); the allocations below set
+  // its device pointers
   DevState& h = ctx->h;
   memset(&h, 0, sizeof h);
   h.ncols = ncols;
@@ -342,35 +341,56 @@ int elmk_create(int64_t ncols, int device_id, elmk_ctx** out)
   h.land = Land{1, 0, 2, 0, 0};
   h.dewmx = 0.1;
   h.oldfflag = 1;
-  h.snicar = (gptr<const double>)ctx->snicar;
-  h.snowage = (gptr<const double>)ctx->snowage;
-  h.wk = (gptr<double>)ctx->scratch;
-  h.lists = (gptr<int32_t>)(ctx->scratch + wk_bytes);
-  h.counters = (gptr<uint32_t>)(ctx->scratch + wk_bytes + list_bytes);
-  ctx->counters_raw = ctx->scratch + wk_bytes + list_bytes;
-  ctx->counters_bytes = cnt_bytes;
-  h.cf_niter = (gptr<int32_t>)(ctx->scratch + wk_bytes + list_bytes + cnt_bytes);
-  {
-    char* q = ctx->scratch + wk_bytes + list_bytes + cnt_bytes + hint_bytes;
-    h.cf_rec = (gptr<double>)q;
-    q += rec_bytes;
-    h.cf_fin = (gptr<double>)q;
-    q += fin_bytes;
-    h.cf_irec = (gptr<int32_t>)q;
-    q += irec_bytes;
-    h.cf_pos = (gptr<int32_t>)q;
-    q += pos_bytes;
-    h.cf_blk = (gptr<uint32_t>)q;
-    q += blk_bytes;
-    h.cf_cls = (gptr<int8_t>)q;
-    q += cls_bytes;
-    h.cf_given = (gptr<double>)q;
-    q += given_bytes;
-    h.alb_snow = (gptr<double>)q;
-    q += snow_bytes;
-    h.cons_diag = (gptr<double>)q;
-    h.cf_nblk = cf_nblk;
-  }
+
+  const size_t ld = (size_t)ctx->ld;
+  if (hip_fail(ctx, carve(ctx->arena, &ctx->arena_bytes, [&](Carve& L) {
+                 for (int f = 0; f < ELMK_NUM_FIELDS; f++) L.take(ctx->fptr[f], (size_t)g_fields[f].nlev * ld * store_size(g_fields[f].dtype));
+               }), "hipMalloc(state arena)"))
+    return fail(ELMK_E_NOMEM);
+  if (hip_fail(ctx, hipMemsetAsync(ctx->arena, 0, ctx->arena_bytes, ctx->stream), "hipMemset(state arena)")) return fail(ELMK_E_HIP);
+
+  if (hip_fail(ctx, ctx->snicar.alloc(SN_TOTAL * sizeof(double)), "hipMalloc(snicar)")) return fail(ELMK_E_NOMEM);
+  if (hip_fail(ctx, hipMemsetAsync(ctx->snicar, 0, SN_TOTAL * sizeof(double), ctx->stream), "hipMemset(snicar)"))
+    return fail(ELMK_E_HIP);
+  if (hip_fail(ctx, ctx->snowage.alloc(3 * ELMK_SNOWAGE_N * sizeof(double)), "hipMalloc(snowage)")) return fail(ELMK_E_NOMEM);
+  if (hip_fail(ctx, hipMemsetAsync(ctx->snowage, 0, 3 * ELMK_SNOWAGE_N * sizeof(double), ctx->stream), "hipMemset(snowage)"))
+    return fail(ELMK_E_HIP);
+  if (hip_fail(ctx, ctx->d.alloc(sizeof(DevState)), "hipMalloc(params)")) return fail(ELMK_E_NOMEM);
+  // canopy_fluxes queue records (k_canopy_fluxes.hip), by queue position
+  const int64_t cf_nblk = (ncols + 255) / 256 > 0 ? (ncols + 255) / 256 : 1;
+  h.cf_nblk = cf_nblk;
+  if (hip_fail(ctx, carve(ctx->scratch, &ctx->scratch_bytes, [&](Carve& L) {
+                 L.take(h.wk, (size_t)WK_N * ld * 8);
+                 L.take(h.lists, (size_t)NLISTS * ld * 4);
+                 L.take(h.counters, COUNTERS_BYTES);
+                 L.take(h.cf_niter, ld * 4);
+                 L.take(h.cf_rec, (size_t)CF_REC_N * (ld + 8) * 8);
+                 L.take(h.cf_fin, (size_t)CF_FIN_N * (ld + 8) * 8);
+                 L.take(h.cf_irec, (size_t)CF_IREC_N * ld * 4);
+                 L.take(h.cf_pos, ld * 4);
+                 L.take(h.cf_blk, (size_t)CF_NCLS * (size_t)cf_nblk * 4);
+                 L.take(h.cf_cls, ld);
+                 L.take(h.cf_given, 3 * ld * 8);
+                 L.take(h.alb_snow, 28 * ld * 8);
+                 L.take(h.cons_diag, 8 * ld * 8);
+                 L.take(ctx->cons_part, (size_t)8 * ELMK_CONS_NPART * 3 * 8);
+                 L.take(ctx->cons_out, 8 * 3 * 8);
+               }), "hipMalloc(scratch)"))
+    return fail(ELMK_E_NOMEM);
+  if (hip_fail(ctx, hipMemsetAsync(ctx->scratch, 0, ctx->scratch_bytes, ctx->stream), "hipMemset(scratch)"))
+    return fail(ELMK_E_HIP);
+  if (hip_fail(ctx, ctx->red_or.alloc(16), "hipMalloc(reduce)")) return fail(ELMK_E_NOMEM);
+  ctx->red_first = (long long*)(ctx->red_or + 2);
+
+  // staging: up to 32 MiB, at least one 64-column tile of the widest field
+  size_t want = (size_t)MAXLEV_STAGE * 8 * (size_t)(ncols > 0 ? ncols : 1);
+  if (want > ((size_t)32 << 20)) want = (size_t)32 << 20;
+  if (want < (size_t)MAXLEV_STAGE * 8 * 64) want = (size_t)MAXLEV_STAGE * 8 * 64;
+  ctx->staging_bytes = want;
+  if (hip_fail(ctx, ctx->staging.alloc(want), "hipMalloc(staging)")) return fail(ELMK_E_NOMEM);
+
+  h.snicar = (gptr<const double>)(double*)ctx->snicar;
+  h.snowage = (gptr<const double>)(double*)ctx->snowage;
   {
     int f = 0;
 #define ELMK_FIELD(name, T, nlev) h.name = field_of<ELMK_##T>::from(ctx->fptr[f++]);
@@ -388,39 +408,28 @@ int elmk_destroy(elmk_ctx* ctx)
 {
   if (!ctx) return ELMK_OK;
   (void)hipSetDevice(ctx->dev);
-  if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-  if (ctx->arena) (void)hipFree(ctx->arena);
-  if (ctx->snicar) (void)hipFree(ctx->snicar);
-  if (ctx->snowage) (void)hipFree(ctx->snowage);
-  if (ctx->scratch) (void)hipFree(ctx->scratch);
-  if (ctx->d) (void)hipFree(ctx->d);
-  if (ctx->geo) (void)hipFree(ctx->geo);
-  for (const elmk_ctx::HistEntry& e : ctx->hist) (void)hipFree(e.acc);
-  if (ctx->hist_table) (void)hipFree(ctx->hist_table);
-  for (GraphSlot& g : ctx->graph)
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  run_release(ctx);
-  if (ctx->grid.mem) (void)hipFree(ctx->grid.mem);
-  if (ctx->run.upload) {
-    (void)hipStreamSynchronize(ctx->run.upload);
-    (void)hipStreamDestroy(ctx->run.upload);
-  }
-  for (int b = 0; b < 2; b++) {
-    if (ctx->run.done[b]) (void)hipEventDestroy(ctx->run.done[b]);
-  }
-  if (ctx->red_or) (void)hipFree(ctx->red_or);
-  if (ctx->staging) (void)hipFree(ctx->staging);
-  for (char* b : ctx->snap_bufs) (void)hipFree(b);
-  for (int i = 0; i < ELMK_NSIDE; i++) {
-    if (ctx->side.s[i]) {
-      (void)hipStreamSynchronize(ctx->side.s[i]);
-      (void)hipStreamDestroy(ctx->side.s[i]);
-    }
-    if (ctx->side.join[i]) (void)hipEventDestroy(ctx->side.join[i]);
-  }
-  if (ctx->side.fork) (void)hipEventDestroy(ctx->side.fork);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+  // 1. nothing may still use the context's memory: its stream (the caller's, once set), the side streams and the upload stream
+  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  for (hipStream_t s : ctx->side.s)
+    if (s) (void)hipStreamSynchronize(s);
+  if (ctx->upload) (void)hipStreamSynchronize(ctx->upload);
+  // 2. the graph executables
+  for (GraphSlot& g : ctx->graph) g.drop();
+  // 3. the memory: every allocation is a DevBuf member of the context
+  const SideStreams side = ctx->side;
+  const hipStream_t own = ctx->own_stream, upload = ctx->upload;
+  const hipEvent_t done[2] = {ctx->run_done[0], ctx->run_done[1]};
   delete ctx;
+  // 4. the events and streams
+  for (int i = 0; i < ELMK_NSIDE; i++) {
+    if (side.s[i]) (void)hipStreamDestroy(side.s[i]);
+    if (side.join[i]) (void)hipEventDestroy(side.join[i]);
+  }
+  if (side.fork) (void)hipEventDestroy(side.fork);
+  for (hipEvent_t e : done)
+    if (e) (void)hipEventDestroy(e);
+  if (upload) (void)hipStreamDestroy(upload);
+  if (own) (void)hipStreamDestroy(own);
   return ELMK_OK;
 }
 
@@ -434,32 +443,39 @@ int elmk_set_stream(elmk_ctx* ctx, void* hip_stream)
   return ELMK_OK;
 }
 
-int elmk_set_graph(elmk_ctx* ctx, int on)
-{
-  if (int rc = enter(ctx)) return rc;
-  ctx->use_graph = on != 0;
-  if (!ctx->use_graph) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (GraphSlot& g : ctx->graph) {
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
-      g.exec = nullptr;
-    }
-  }
-  return ELMK_OK;
-}
-
 namespace {
 // a captured graph holds the launch shape and the kernels of the moment it was captured (elmk_set_option, the day-length mode)
 int drop_graphs(elmk_ctx* ctx)
 {
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (GraphSlot& g : ctx->graph) {
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    g.exec = nullptr;
-  }
+  for (GraphSlot& g : ctx->graph) g.drop();
   return ELMK_OK;
 }
+
+// per-column day length on or off (DevState::col_dayl, elmk_kernels.h: SideStreams::col_dayl)
+int set_col_dayl(elmk_ctx* ctx, bool on)
+{
+  if (ctx->side.col_dayl == on) return ELMK_OK;
+  if (int rc = drop_graphs(ctx)) return rc;
+  ctx->side.col_dayl = on;
+  return ELMK_OK;
+}
+
+// the calls that allocate, free or wait cannot be part of a caller's captured graph
+int refuse_capture(elmk_ctx* ctx, const char* msg)
+{
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hip_fail(ctx, hipStreamIsCapturing(ctx->stream, &cap), "hipStreamIsCapturing")) return ELMK_E_HIP;
+  return cap != hipStreamCaptureStatusNone ? invalid(ctx, msg) : ELMK_OK;
+}
 }  // namespace
+
+int elmk_set_graph(elmk_ctx* ctx, int on)
+{
+  if (int rc = enter(ctx)) return rc;
+  ctx->use_graph = on != 0;
+  return ctx->use_graph ? ELMK_OK : drop_graphs(ctx);
+}
 
 int elmk_set_option(elmk_ctx* ctx, int option, int value)
 {
@@ -633,38 +649,31 @@ int elmk_snapshot_fields(elmk_ctx* ctx, const int* fields, int nfields)
   for (int i = 0; i < nfields; i++)
     if (!field_ok(fields[i])) return invalid(ctx, "elmk_snapshot_fields: unknown field");
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (char* b : ctx->snap_bufs) (void)hipFree(b);
   ctx->snap_bufs.clear();
   ctx->snap_fields.clear();
   // a field enters the snapshot only once its buffer exists and its copy has been enqueued; any failure drops the whole
   // snapshot, so that a later elmk_restore_fields never restores from a partly filled set
-  auto drop = [&]() {
-    (void)hipStreamSynchronize(ctx->stream);
-    for (char* b : ctx->snap_bufs) (void)hipFree(b);
-    ctx->snap_bufs.clear();
-    ctx->snap_fields.clear();
-  };
-  for (int i = 0; i < nfields; i++) {
+  int rc = ELMK_OK;
+  for (int i = 0; i < nfields && rc == ELMK_OK; i++) {
     const int f = fields[i];
     const size_t bytes = (size_t)g_fields[f].nlev * (size_t)ctx->ld * store_size(g_fields[f].dtype);
-    char* b = nullptr;
-    if (hip_fail(ctx, hipMalloc((void**)&b, bytes), "hipMalloc(snapshot)")) {
-      drop();
-      return ELMK_E_NOMEM;
+    DevBuf<double> b;
+    if (hip_fail(ctx, b.alloc(bytes), "hipMalloc(snapshot)"))
+      rc = ELMK_E_NOMEM;
+    else if (hip_fail(ctx, hipMemcpyAsync(b, ctx->fptr[f], bytes, hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync(snapshot)"))
+      rc = ELMK_E_HIP;
+    else {
+      ctx->snap_bufs.push_back(std::move(b));
+      ctx->snap_fields.push_back(f);
     }
-    if (hip_fail(ctx, hipMemcpyAsync(b, ctx->fptr[f], bytes, hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpyAsync(snapshot)")) {
-      (void)hipFree(b);
-      drop();
-      return ELMK_E_HIP;
-    }
-    ctx->snap_bufs.push_back(b);
-    ctx->snap_fields.push_back(f);
   }
-  if (hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(snapshot)")) {
-    drop();
-    return ELMK_E_HIP;
+  if (rc == ELMK_OK && hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(snapshot)")) rc = ELMK_E_HIP;
+  if (rc != ELMK_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->snap_bufs.clear();
+    ctx->snap_fields.clear();
   }
-  return ELMK_OK;
+  return rc;
 }
 
 int elmk_restore_fields(elmk_ctx* ctx)
@@ -679,7 +688,7 @@ int elmk_restore_fields(elmk_ctx* ctx)
     const int f = ctx->snap_fields[i];
     const size_t bytes = (size_t)g_fields[f].nlev * (size_t)ctx->ld * store_size(g_fields[f].dtype);
     words += (int64_t)(bytes / 8);
-    J.src[J.n] = (const double*)ctx->snap_bufs[i];
+    J.src[J.n] = ctx->snap_bufs[i];
     J.dst[J.n] = (double*)ctx->fptr[f];
     J.end[J.n] = words;
     J.n++;
@@ -739,9 +748,9 @@ int elmk_set_column_geography(elmk_ctx* ctx, const double* lat_r, const double* 
   }
   if (!ctx->geo) {
     const size_t bytes = (size_t)(ELMK_GEO_N + COL_DAYL_N) * (size_t)ld * 8;
-    HIPCHK(hipMalloc((void**)&ctx->geo, bytes));
+    HIPCHK(ctx->geo.alloc(bytes));
     HIPCHK(hipMemsetAsync(ctx->geo, 0, bytes, ctx->stream));
-    ctx->h.geo = (gptr<const double>)ctx->geo;
+    ctx->h.geo = (gptr<const double>)(double*)ctx->geo;
     ctx->h.col_dayl = (gptr<double>)(ctx->geo + (size_t)ELMK_GEO_N * ld);
     ctx->dirty = true;
   }
@@ -757,10 +766,8 @@ int elmk_solar_geometry(elmk_ctx* ctx, double dt_seconds, double decday, int doy
   if (!ctx->geo_set) return invalid(ctx, "elmk_solar_geometry: no column geography (elmk_set_column_geography)");
   if (!(dt_seconds > 0.0 && dt_seconds <= 1.0e9) || !(decday >= 0.0 && decday < 1.0e9) || doy < -1 || doy > 1000000000)
     return invalid(ctx, "elmk_solar_geometry: bad dt / decday / doy");
-  if (!ctx->side.col_dayl) {  // canopy_fluxes switches to the per-column kernels: graphs captured so far hold the scalar ones
-    if (int rc = drop_graphs(ctx)) return rc;
-    ctx->side.col_dayl = true;
-  }
+  // canopy_fluxes switches to the per-column kernels: graphs captured so far hold the scalar ones
+  if (int rc = set_col_dayl(ctx, true)) return rc;
   if (int rc = push_params(ctx)) return rc;
   launch_solar_geometry(ctx->d, ctx->ncols, elmk_solar_step_consts(dt_seconds, decday, doy), ctx->stream);
   HIPCHK(hipGetLastError());
@@ -783,14 +790,10 @@ int elmk_download_day_length(elmk_ctx* ctx, double* dayl, double* max_dayl)
 int elmk_clear_column_geography(elmk_ctx* ctx)
 {
   if (int rc = enter(ctx)) return rc;
-  if (ctx->side.col_dayl) {
-    if (int rc = drop_graphs(ctx)) return rc;
-    ctx->side.col_dayl = false;
-  }
+  if (int rc = set_col_dayl(ctx, false)) return rc;
   if (ctx->geo) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    const hipError_t e = hipFree(ctx->geo);
-    ctx->geo = nullptr;
+    const hipError_t e = ctx->geo.reset();
     ctx->h.geo = nullptr;
     ctx->h.col_dayl = nullptr;
     ctx->dirty = true;
@@ -887,13 +890,20 @@ namespace {
 constexpr int HIST_MAX_ROWS = ELMK_HIST_MAX_ENTRIES * MAXLEV_STAGE;
 constexpr size_t HIST_COUNTS_OFF = ((size_t)HIST_MAX_ROWS * sizeof(HistRow) + 255) / 256 * 256;
 
-unsigned long long* hist_counts(elmk_ctx* ctx) { return (unsigned long long*)(ctx->hist_table + HIST_COUNTS_OFF); }
+unsigned long long* hist_counts(elmk_ctx* ctx) { return (unsigned long long*)((char*)(HistRow*)ctx->hist_table + HIST_COUNTS_OFF); }
 
 unsigned hist_tape_mask(const elmk_ctx* ctx)
 {
   unsigned m = 0;
   for (const elmk_ctx::HistEntry& e : ctx->hist) m |= 1u << e.tape;
   return m;
+}
+
+// the tapes of mask hold samples: elmk_history_add refuses them until their reset
+void mark_sampled(elmk_ctx* ctx, unsigned mask)
+{
+  for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
+    if (mask & (1u << t)) ctx->hist_dirty[t] = true;
 }
 
 bool tape_ok(int tape) { return tape >= 0 && tape < ELMK_HIST_MAX_TAPES; }
@@ -907,16 +917,14 @@ int elmk_history_add(elmk_ctx* ctx, int tape, int field, int op)
   if (op < ELMK_HIST_AVG || op > ELMK_HIST_INST) return invalid(ctx, "elmk_history_add: unknown op");
   if ((int)ctx->hist.size() >= ELMK_HIST_MAX_ENTRIES) return invalid(ctx, "elmk_history_add: the history table is full");
   if (ctx->hist_dirty[tape]) return invalid(ctx, "elmk_history_add: the tape holds samples; reset it first");
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  HIPCHK(hipStreamIsCapturing(ctx->stream, &cap));
-  if (cap != hipStreamCaptureStatusNone) return invalid(ctx, "elmk_history_add: the stream is being captured");
+  if (int rc = refuse_capture(ctx, "elmk_history_add: the stream is being captured")) return rc;
   if (!ctx->hist_table) {
-    HIPCHK(hipMalloc((void**)&ctx->hist_table, HIST_COUNTS_OFF + ELMK_HIST_MAX_TAPES * sizeof(unsigned long long)));
+    HIPCHK(ctx->hist_table.alloc(HIST_COUNTS_OFF + ELMK_HIST_MAX_TAPES * sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(ctx->hist_table, 0, HIST_COUNTS_OFF + ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
   }
   const int nlev = g_fields[field].nlev;
-  double* acc = nullptr;
-  if (hip_fail(ctx, hipMalloc((void**)&acc, (size_t)nlev * (size_t)ctx->ld * sizeof(double)), "hipMalloc(history)")) return ELMK_E_NOMEM;
+  DevBuf<double> acc;
+  if (hip_fail(ctx, acc.alloc((size_t)nlev * (size_t)ctx->ld * sizeof(double)), "hipMalloc(history)")) return ELMK_E_NOMEM;
   launch_fill(acc, ELMK_F64, nlev, ctx->ld, ctx->ld, hist_init_value(op), ctx->stream);
   const int row0 = (int)ctx->hist_rows.size();
   const int es = store_size(g_fields[field].dtype);
@@ -925,17 +933,16 @@ int elmk_history_add(elmk_ctx* ctx, int tape, int field, int op)
                                      store_dtype(g_fields[field].dtype), op, tape, 0});
   // the stream may still run an accumulate that reads the table: the copy is ordered after it; pageable source, so wait
   const hipError_t e1 = hipGetLastError();
-  const hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(ctx->hist_table + (size_t)row0 * sizeof(HistRow), &ctx->hist_rows[row0],
+  const hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(ctx->hist_table + row0, &ctx->hist_rows[row0],
                                                           (size_t)nlev * sizeof(HistRow), hipMemcpyHostToDevice, ctx->stream)
                                          : e1;
   const hipError_t e3 = e2 == hipSuccess ? hipStreamSynchronize(ctx->stream) : e2;
   if (hip_fail(ctx, e3, "elmk_history_add")) {
     ctx->hist_rows.resize(row0);
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(acc);
-    return ELMK_E_HIP;
+    return ELMK_E_HIP;  // (frees acc)
   }
-  ctx->hist.push_back(elmk_ctx::HistEntry{tape, field, op, nlev, row0, acc});
+  ctx->hist.push_back(elmk_ctx::HistEntry{tape, field, op, nlev, row0, std::move(acc)});
   ctx->hist_version++;
   return (int)ctx->hist.size() - 1;
 }
@@ -945,10 +952,9 @@ int elmk_history_accumulate(elmk_ctx* ctx)
   if (int rc = enter(ctx)) return rc;
   if (ctx->hist.empty()) return ELMK_OK;
   const unsigned mask = hist_tape_mask(ctx);
-  launch_hist_accumulate((const HistRow*)ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
+  launch_hist_accumulate(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
   HIPCHK(hipGetLastError());
-  for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
-    if (mask & (1u << t)) ctx->hist_dirty[t] = true;
+  mark_sampled(ctx, mask);
   return ELMK_OK;
 }
 
@@ -957,7 +963,7 @@ int elmk_history_reset(elmk_ctx* ctx, int tape)
   if (int rc = enter(ctx)) return rc;
   if (!tape_ok(tape)) return invalid(ctx, "elmk_history_reset: unknown tape");
   if (ctx->hist_table) {
-    launch_hist_reset((const HistRow*)ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, tape, ctx->stream);
+    launch_hist_reset(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, tape, ctx->stream);
     HIPCHK(hipGetLastError());
   }
   ctx->hist_dirty[tape] = false;
@@ -982,7 +988,7 @@ int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int6
   if (entry < 0 || entry >= (int)ctx->hist.size()) return invalid(ctx, "elmk_history_read: unknown entry");
   if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols) return invalid(ctx, "elmk_history_read: bad column range");
   if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_history_read: unknown layout");
-  const elmk_ctx::HistEntry e = ctx->hist[entry];
+  const elmk_ctx::HistEntry& e = ctx->hist[entry];
   int64_t count = 0;
   if (int rc = elmk_history_count(ctx, e.tape, &count)) return rc;
   if (count <= 0) return invalid(ctx, "elmk_history_read: the tape holds no samples");
@@ -1014,7 +1020,6 @@ int elmk_history_clear(elmk_ctx* ctx)
 {
   if (int rc = enter(ctx)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (const elmk_ctx::HistEntry& e : ctx->hist) (void)hipFree(e.acc);
   ctx->hist.clear();
   ctx->hist_rows.clear();
   if (ctx->hist_table)
@@ -1028,188 +1033,25 @@ int elmk_history_clear(elmk_ctx* ctx)
 // ---------------------------------------------------------------------------------------------------
 // physics wrappers: one launch each, same order/arguments as driver/kokkos
 // ---------------------------------------------------------------------------------------------------
+}  // extern "C" (the launch machinery below has templates)
+
 namespace {
 int heal_lists(elmk_ctx* ctx)
 {
   if (!ctx->lists_stale) return ELMK_OK;
   ctx->lists_stale = false;
-  HIPCHK(hipMemsetAsync(ctx->counters_raw, 0, ctx->counters_bytes, ctx->stream));
-  return ELMK_OK;
-}
-}  // namespace
-#define PHYSICS_PROLOGUE()                 \
-  if (int rc = enter(ctx)) return rc;      \
-  if (int rc = heal_lists(ctx)) return rc; \
-  if (int rc = push_params(ctx)) return rc
-
-int elmk_frac_wet(elmk_ctx* ctx)
-{
-  PHYSICS_PROLOGUE();
-  launch_frac_wet(ctx->d, ctx->ncols, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-int elmk_albedo_snicar(elmk_ctx* ctx)
-{
-  PHYSICS_PROLOGUE();
-  launch_albedo_snicar(ctx->d, ctx->ncols, ctx->stream, &ctx->side);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-int elmk_canopy_hydrology(elmk_ctx* ctx, double dt)
-{
-  PHYSICS_PROLOGUE();
-  launch_canopy_hydrology(ctx->d, ctx->ncols, dt, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-int elmk_surface_radiation(elmk_ctx* ctx)
-{
-  PHYSICS_PROLOGUE();
-  launch_surface_radiation(ctx->d, ctx->ncols, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-int elmk_canopy_temperature(elmk_ctx* ctx)
-{
-  PHYSICS_PROLOGUE();
-  launch_canopy_temperature(ctx->d, ctx->ncols, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-int elmk_bareground_fluxes(elmk_ctx* ctx)
-{
-  PHYSICS_PROLOGUE();
-  launch_bareground_fluxes(ctx->d, ctx->ncols, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-int elmk_canopy_fluxes(elmk_ctx* ctx, double dt)
-{
-  PHYSICS_PROLOGUE();
-  launch_canopy_fluxes(ctx->d, ctx->ncols, dt, ctx->stream, 0, &ctx->side);
-  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(ELMK_GENERIC(ctx->h.counters), 0, COUNTERS_BYTES, ctx->stream));
   return ELMK_OK;
 }
 
-// L2-level entries: the forcing-derived scalars handed in, as the reference's unit tests call the physics
-// (test/test_CanFlux.cc:285-340, test/test_BGFlux.cc:200-260) instead of the wrapper's derive_forc_* (atm_physics_impl.hh:246-272)
-namespace {
-int stage_given(elmk_ctx* ctx, const double* rho, const double* po2, const double* pco2, int* mask)
+// what every physics entry point does before it launches
+int enter_physics(elmk_ctx* ctx)
 {
-  const double* src[3] = {rho, po2, pco2};
-  *mask = 0;
-  for (int k = 0; k < 3; k++) {
-    if (!src[k] || ctx->ncols == 0) continue;
-    HIPCHK(hipMemcpyAsync(ELMK_GENERIC(ctx->h.cf_given) + (size_t)k * ctx->ld, src[k], (size_t)ctx->ncols * 8, hipMemcpyHostToDevice,
-                          ctx->stream));
-    *mask |= 1 << k;
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));  // the sources are caller-owned pageable host arrays
-  return ELMK_OK;
-}
-}  // namespace
-
-int elmk_canopy_fluxes_given(elmk_ctx* ctx, double dt, const double* forc_rho, const double* forc_po2, const double* forc_pco2)
-{
-  PHYSICS_PROLOGUE();
-  int mask = 0;
-  if (int rc = stage_given(ctx, forc_rho, forc_po2, forc_pco2, &mask)) return rc;
-  launch_canopy_fluxes(ctx->d, ctx->ncols, dt, ctx->stream, mask, &ctx->side);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = heal_lists(ctx)) return rc;
+  return push_params(ctx);
 }
 
-int elmk_bareground_fluxes_given(elmk_ctx* ctx, const double* forc_rho)
-{
-  PHYSICS_PROLOGUE();
-  int mask = 0;
-  if (int rc = stage_given(ctx, forc_rho, nullptr, nullptr, &mask)) return rc;
-  launch_bareground_fluxes(ctx->d, ctx->ncols, ctx->stream, mask);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_soil_temperature(elmk_ctx* ctx, double dt)
-{
-  PHYSICS_PROLOGUE();
-  launch_soil_temperature(ctx->d, ctx->ncols, dt, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_snow_hydrology(elmk_ctx* ctx, double dt)
-{
-  PHYSICS_PROLOGUE();
-  launch_snow_hydrology(ctx->d, ctx->ncols, dt, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_init_timestep(elmk_ctx* ctx)
-{
-  PHYSICS_PROLOGUE();
-  launch_init_timestep(ctx->d, ctx->ncols, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_get_forcing(elmk_ctx* ctx, const double* wt1, const double* wt2, int qbot_is_rh)
-{
-  PHYSICS_PROLOGUE();
-  if (!wt1 || !wt2) return invalid(ctx, "elmk_get_forcing: null weights");
-  launch_get_forcing(ctx->d, ctx->ncols, wt1, wt2, qbot_is_rh != 0, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_phenology(elmk_ctx* ctx, double wt1, double wt2)
-{
-  PHYSICS_PROLOGUE();
-  launch_phenology(ctx->d, ctx->ncols, wt1, wt2, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_initialize_state(elmk_ctx* ctx)
-{
-  PHYSICS_PROLOGUE();
-  if (!ctx->have_init_params) return invalid(ctx, "elmk_initialize_state: elmk_set_init_params has not been called");
-  launch_initialize_state(ctx->d, ctx->ncols, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_surface_fluxes(elmk_ctx* ctx, double dt)
-{
-  PHYSICS_PROLOGUE();
-  launch_surface_fluxes(ctx->d, ctx->ncols, dt, ctx->stream);
-  HIPCHK(hipGetLastError());
-  return ELMK_OK;
-}
-
-int elmk_evaluate_conservation(elmk_ctx* ctx, double dt, double* min_max_sum, double* per_column)
-{
-  PHYSICS_PROLOGUE();
-  if (!min_max_sum) return invalid(ctx, "elmk_evaluate_conservation: min_max_sum is NULL");
-  double* diag = ELMK_GENERIC(ctx->h.cons_diag);
-  double* part = diag + (size_t)8 * ctx->ld;
-  double* out = part + (size_t)8 * ELMK_CONS_NPART * 3;
-  launch_conservation(ctx->d, ctx->ncols, ctx->ld, dt, diag, part, out, ctx->stream);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(min_max_sum, out, 8 * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (per_column) {  // [8][ncols], diagnostic-major
-    for (int k = 0; k < 8; k++)
-      HIPCHK(hipMemcpyAsync(per_column + (size_t)k * ctx->ncols, diag + (size_t)k * ctx->ld, (size_t)ctx->ncols * 8,
-                            hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return ELMK_OK;
-}
-
-// ELMInterface::advance order (elm_kokkos_interface.cc:289-307).  ONE stage table per launch structure drives the plain
-// path, the graph capture and the profiled path, so the three cannot drift apart.
-namespace {
 // roctx ranges named after the labels the reference gives its parallel_for launches (driver/kokkos/*_kokkos.cc:
 // "kokkos_canhydro_fracwet_kernel", "kokkos_albedo_and_snicar", ...), so that a marker trace of this library reads like one of
 // the reference (tracing).  Off unless ELMK_ROCTX=1 is set when the first context is created; the marker
@@ -1237,64 +1079,98 @@ const Roctx* roctx()
   static const Roctx r;
   return &r;
 }
+// label nullptr: no range
 struct RoctxRange {
-  explicit RoctxRange(const char* label)
+  const bool on;
+  explicit RoctxRange(const char* label) : on(label && roctx()->push)
   {
-    if (roctx()->push) roctx()->push(label);
+    if (on) roctx()->push(label);
   }
   ~RoctxRange()
   {
-    if (roctx()->pop) roctx()->pop();
+    if (on) roctx()->pop();
   }
 };
-const char* const TS7_LABELS[7] = {"kokkos_canhydro_fracwet_kernel", "kokkos_albedo_and_snicar", "kokkos_canopy_hydrology", "kokkos_surface_radiation",
-                                   "kokkos_canopy_temperature",     "kokkos_bareground_fluxes", "kokkos_canopy_fluxes"};
-constexpr int TS7_NSTAGE = 7;
-void launch_stage7(elmk_ctx* ctx, int k, double dt)
-{
-  const RoctxRange range(TS7_LABELS[k < 7 ? k : 6]);
-  switch (k) {
-    case 0: launch_frac_wet(ctx->d, ctx->ncols, ctx->stream); break;
-    case 1: launch_albedo_snicar(ctx->d, ctx->ncols, ctx->stream, &ctx->side); break;
-    case 2: launch_canopy_hydrology(ctx->d, ctx->ncols, dt, ctx->stream); break;
-    case 3: launch_surface_radiation(ctx->d, ctx->ncols, ctx->stream); break;
-    case 4: launch_canopy_temperature(ctx->d, ctx->ncols, ctx->stream); break;
-    case 5: launch_bareground_fluxes(ctx->d, ctx->ncols, ctx->stream); break;
-    default: launch_canopy_fluxes(ctx->d, ctx->ncols, dt, ctx->stream, 0, &ctx->side); break;
-  }
-}
-// elmk_timestep7_fused: the same seven wrappers as ELMK_FUSED_NSTAGE launch groups (k_canopy_fluxes.hip)
-void launch_stage_fused(elmk_ctx* ctx, int k, double dt) { launch_fused_stage(ctx->d, ctx->ncols, dt, ctx->stream, &ctx->side, k); }
-typedef void (*stage_fn)(elmk_ctx*, int, double);
 
-// all stages in order; marks (may be null): nstage + 1 events recorded around the stages on the context's stream
-int enqueue_stages(elmk_ctx* ctx, stage_fn fn, int nstage, double dt, hipEvent_t* marks)
+// ELMInterface::advance order (elm_kokkos_interface.cc:289-307).  ONE stage list per launch sequence drives the plain path, the
+// graph capture, the profiled path and the entry points of a single stage, so that they cannot drift apart.
+struct Stage {
+  void (*launch)(elmk_ctx* ctx, double dt);
+  const char* label;  // of its roctx range (nullptr: none)
+};
+// consecutive stages of one list
+struct Stages {
+  const Stage* s;
+  int n;
+  template <int N>
+  constexpr Stages(const Stage (&a)[N]) : s(a), n(N) {}
+  constexpr Stages(const Stage& one) : s(&one), n(1) {}
+};
+
+void stage_frac_wet(elmk_ctx* ctx, double) { launch_frac_wet(ctx->d, ctx->ncols, ctx->stream); }
+void stage_albedo_snicar(elmk_ctx* ctx, double) { launch_albedo_snicar(ctx->d, ctx->ncols, ctx->stream, &ctx->side); }
+void stage_canopy_hydrology(elmk_ctx* ctx, double dt) { launch_canopy_hydrology(ctx->d, ctx->ncols, dt, ctx->stream); }
+void stage_surface_radiation(elmk_ctx* ctx, double) { launch_surface_radiation(ctx->d, ctx->ncols, ctx->stream); }
+void stage_canopy_temperature(elmk_ctx* ctx, double) { launch_canopy_temperature(ctx->d, ctx->ncols, ctx->stream); }
+void stage_bareground_fluxes(elmk_ctx* ctx, double) { launch_bareground_fluxes(ctx->d, ctx->ncols, ctx->stream); }
+void stage_canopy_fluxes(elmk_ctx* ctx, double dt) { launch_canopy_fluxes(ctx->d, ctx->ncols, dt, ctx->stream, 0, &ctx->side); }
+template <int K>
+void stage_fused(elmk_ctx* ctx, double dt)
 {
-  for (int k = 0; k < nstage; k++) {
-    if (marks) HIPCHK(hipEventRecord(marks[k], ctx->stream));
-    fn(ctx, k, dt);
+  launch_fused_stage(ctx->d, ctx->ncols, dt, ctx->stream, &ctx->side, K);
+}
+void stage_soil_temperature(elmk_ctx* ctx, double dt) { launch_soil_temperature(ctx->d, ctx->ncols, dt, ctx->stream); }
+void stage_snow_hydrology(elmk_ctx* ctx, double dt) { launch_snow_hydrology(ctx->d, ctx->ncols, dt, ctx->stream); }
+void stage_surface_fluxes(elmk_ctx* ctx, double dt) { launch_surface_fluxes(ctx->d, ctx->ncols, dt, ctx->stream); }
+
+// elmk_timestep7, in the order of ELMK_WRAPPER_FRAC_WET .. ELMK_WRAPPER_CANOPY_FLUXES
+constexpr Stage TS7[] = {{stage_frac_wet, "kokkos_canhydro_fracwet_kernel"},   {stage_albedo_snicar, "kokkos_albedo_and_snicar"},
+                         {stage_canopy_hydrology, "kokkos_canopy_hydrology"},   {stage_surface_radiation, "kokkos_surface_radiation"},
+                         {stage_canopy_temperature, "kokkos_canopy_temperature"}, {stage_bareground_fluxes, "kokkos_bareground_fluxes"},
+                         {stage_canopy_fluxes, "kokkos_canopy_fluxes"}};
+// elmk_timestep7_fused: the same seven wrappers as ELMK_FUSED_NSTAGE launch groups (k_canopy_fluxes.hip)
+constexpr Stage FUSED[] = {{stage_fused<0>, nullptr}, {stage_fused<1>, nullptr}, {stage_fused<2>, nullptr}, {stage_fused<3>, nullptr},
+                           {stage_fused<4>, nullptr}};
+static_assert(sizeof FUSED / sizeof FUSED[0] == ELMK_FUSED_NSTAGE, "fused stages");
+// elmk_advance_physics: the fused seven, then the rest of ELMInterface::advance's per-column calls in its order
+constexpr Stage SOIL_TEMPERATURE{stage_soil_temperature, nullptr}, SNOW_HYDROLOGY{stage_snow_hydrology, nullptr},
+    SURFACE_FLUXES{stage_surface_fluxes, nullptr};
+constexpr Stage ADVANCE[] = {FUSED[0], FUSED[1], FUSED[2], FUSED[3], FUSED[4], SOIL_TEMPERATURE, SNOW_HYDROLOGY, SURFACE_FLUXES};
+
+void launch(elmk_ctx* ctx, const Stage& st, double dt)
+{
+  const RoctxRange range(st.label);
+  st.launch(ctx, dt);
+}
+
+// the stages in order; marks (may be null): events recorded on the context's stream before the first stage and after the last,
+// and with per_stage before every stage (marks[k] before stage k)
+int enqueue_stages(elmk_ctx* ctx, Stages L, double dt, hipEvent_t* marks = nullptr, bool per_stage = true)
+{
+  for (int k = 0; k < L.n; k++) {
+    if (marks && (per_stage || k == 0)) HIPCHK(hipEventRecord(marks[k], ctx->stream));
+    launch(ctx, L.s[k], dt);
   }
-  if (marks) HIPCHK(hipEventRecord(marks[nstage], ctx->stream));
+  if (marks) HIPCHK(hipEventRecord(marks[per_stage ? L.n : 1], ctx->stream));
   HIPCHK(hipGetLastError());
   return ELMK_OK;
 }
 
 // the stages captured once as a HIP graph (kernel nodes in one chain: the side-stream forks are issued in order on the
 // capturing stream) and replayed
-int run_graph(elmk_ctx* ctx, GraphSlot& g, stage_fn fn, int nstage, double dt, uint64_t tag = 0)
+int run_graph(elmk_ctx* ctx, GraphSlot& g, Stages L, double dt, uint64_t tag)
 {
   if (!g.exec || g.dt != dt || g.stream != ctx->stream || g.tag != tag) {
     if (g.exec) {
       // dt or the stream changed: the old executable may still be running its last launch.  (Best effort: a caller that
       // destroyed the old stream has synchronised it itself, and the error of waiting on it is not this call's.)
       if (g.stream && hipStreamSynchronize(g.stream) != hipSuccess) (void)hipGetLastError();
-      (void)hipGraphExecDestroy(g.exec);
-      g.exec = nullptr;
+      g.drop();
     }
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     ctx->side.one_stream = true;  // one chain of nodes: no fork onto the side streams (elmk_kernels.h: SideStreams)
-    for (int k = 0; k < nstage; k++) fn(ctx, k, dt);
+    for (int k = 0; k < L.n; k++) launch(ctx, L.s[k], dt);
     ctx->side.one_stream = false;
     // a launch that failed during capture leaves its error in the runtime and may have invalidated the capture: read it,
     // and ALWAYS end the capture so that neither the stream nor the forked side streams stay in capture mode
@@ -1321,144 +1197,233 @@ int run_graph(elmk_ctx* ctx, GraphSlot& g, stage_fn fn, int nstage, double dt, u
   return ELMK_OK;
 }
 
-// nsteps profiled steps: HIP events between the stages on the context's stream; the snapshot (if any) is restored before
-// every step outside the event brackets, so each profiled step does the same work as the caller's timed loop
-int profile_stages(elmk_ctx* ctx, stage_fn fn, int nstage, double dt, int nsteps, float* ms_per_stage, float* ms_total,
-                   float* ms_each_step = nullptr)
+// a sequence elmk_set_graph applies to: replayed from its captured graph, or enqueued stage by stage
+int launch_sequence(elmk_ctx* ctx, GraphId id, Stages L, double dt, uint64_t tag = 0)
 {
+  if (ctx->use_graph) return run_graph(ctx, ctx->graph[id], L, dt, tag);
+  return enqueue_stages(ctx, L, dt);
+}
+
+// the entry points of one stage
+int launch_stage(elmk_ctx* ctx, const Stage& st, double dt)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  return enqueue_stages(ctx, st, dt);
+}
+
+// nsteps profiled steps: HIP events around each step and, with per_stage, between its stages, on the context's stream
+// (step_label: a roctx range around each step); the snapshot (if any) is restored before every step outside the event
+// brackets, so each profiled step does the same work as the caller's timed loop
+int profile_stages(elmk_ctx* ctx, Stages L, double dt, int nsteps, bool per_stage, const char* step_label, float* ms_per_stage,
+                   float* ms_total, float* ms_each_step)
+{
+  const int nev = per_stage ? L.n + 1 : 2;  // events per step
   EventList ev;
-  HIPCHK(ev.create((size_t)nsteps * (nstage + 1)));
+  HIPCHK(ev.create((size_t)nsteps * nev));
   for (int s = 0; s < nsteps; s++) {
     if (!ctx->snap_fields.empty())
       if (int rc = elmk_restore_fields(ctx)) return rc;
-    if (int rc = enqueue_stages(ctx, fn, nstage, dt, &ev[(size_t)s * (nstage + 1)])) return rc;
+    const RoctxRange range(step_label);
+    if (int rc = enqueue_stages(ctx, L, dt, &ev[(size_t)s * nev], per_stage)) return rc;
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  std::vector<double> acc((size_t)nstage, 0.0);
+  std::vector<double> acc((size_t)L.n, 0.0);
   double tot = 0.0;
   for (int s = 0; s < nsteps; s++) {
-    hipEvent_t* e = &ev[(size_t)s * (nstage + 1)];
-    for (int k = 0; k < nstage; k++) {
+    hipEvent_t* e = &ev[(size_t)s * nev];
+    for (int k = 0; per_stage && k < L.n; k++) {
       float ms = 0.f;
       HIPCHK(hipEventElapsedTime(&ms, e[k], e[k + 1]));
       acc[k] += ms;
     }
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e[0], e[nstage]));
+    HIPCHK(hipEventElapsedTime(&ms, e[0], e[nev - 1]));
     tot += ms;
     if (ms_each_step) ms_each_step[s] = ms;
   }
   if (ms_per_stage)
-    for (int k = 0; k < nstage; k++) ms_per_stage[k] = (float)(acc[k] / nsteps);
+    for (int k = 0; k < L.n; k++) ms_per_stage[k] = (float)(acc[k] / nsteps);
   if (ms_total) *ms_total = (float)(tot / nsteps);
   return ELMK_OK;
 }
 }  // namespace
 
+extern "C" {
+
+int elmk_frac_wet(elmk_ctx* ctx) { return launch_stage(ctx, TS7[ELMK_WRAPPER_FRAC_WET], 0.0); }
+int elmk_albedo_snicar(elmk_ctx* ctx) { return launch_stage(ctx, TS7[ELMK_WRAPPER_ALBEDO_SNICAR], 0.0); }
+int elmk_canopy_hydrology(elmk_ctx* ctx, double dt) { return launch_stage(ctx, TS7[ELMK_WRAPPER_CANOPY_HYDROLOGY], dt); }
+int elmk_surface_radiation(elmk_ctx* ctx) { return launch_stage(ctx, TS7[ELMK_WRAPPER_SURFACE_RADIATION], 0.0); }
+int elmk_canopy_temperature(elmk_ctx* ctx) { return launch_stage(ctx, TS7[ELMK_WRAPPER_CANOPY_TEMPERATURE], 0.0); }
+int elmk_bareground_fluxes(elmk_ctx* ctx) { return launch_stage(ctx, TS7[ELMK_WRAPPER_BAREGROUND_FLUXES], 0.0); }
+int elmk_canopy_fluxes(elmk_ctx* ctx, double dt) { return launch_stage(ctx, TS7[ELMK_WRAPPER_CANOPY_FLUXES], dt); }
+int elmk_soil_temperature(elmk_ctx* ctx, double dt) { return launch_stage(ctx, SOIL_TEMPERATURE, dt); }
+int elmk_snow_hydrology(elmk_ctx* ctx, double dt) { return launch_stage(ctx, SNOW_HYDROLOGY, dt); }
+int elmk_surface_fluxes(elmk_ctx* ctx, double dt) { return launch_stage(ctx, SURFACE_FLUXES, dt); }
+
+// L2-level entries: the forcing-derived scalars handed in, as the reference's unit tests call the physics
+// (test/test_CanFlux.cc:285-340, test/test_BGFlux.cc:200-260) instead of the wrapper's derive_forc_* (atm_physics_impl.hh:246-272)
+namespace {
+int stage_given(elmk_ctx* ctx, const double* rho, const double* po2, const double* pco2, int* mask)
+{
+  const double* src[3] = {rho, po2, pco2};
+  *mask = 0;
+  for (int k = 0; k < 3; k++) {
+    if (!src[k] || ctx->ncols == 0) continue;
+    HIPCHK(hipMemcpyAsync(ELMK_GENERIC(ctx->h.cf_given) + (size_t)k * ctx->ld, src[k], (size_t)ctx->ncols * 8, hipMemcpyHostToDevice,
+                          ctx->stream));
+    *mask |= 1 << k;
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // the sources are caller-owned pageable host arrays
+  return ELMK_OK;
+}
+}  // namespace
+
+int elmk_canopy_fluxes_given(elmk_ctx* ctx, double dt, const double* forc_rho, const double* forc_po2, const double* forc_pco2)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  int mask = 0;
+  if (int rc = stage_given(ctx, forc_rho, forc_po2, forc_pco2, &mask)) return rc;
+  launch_canopy_fluxes(ctx->d, ctx->ncols, dt, ctx->stream, mask, &ctx->side);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_bareground_fluxes_given(elmk_ctx* ctx, const double* forc_rho)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  int mask = 0;
+  if (int rc = stage_given(ctx, forc_rho, nullptr, nullptr, &mask)) return rc;
+  launch_bareground_fluxes(ctx->d, ctx->ncols, ctx->stream, mask);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_init_timestep(elmk_ctx* ctx)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  launch_init_timestep(ctx->d, ctx->ncols, ctx->stream);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_get_forcing(elmk_ctx* ctx, const double* wt1, const double* wt2, int qbot_is_rh)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  if (!wt1 || !wt2) return invalid(ctx, "elmk_get_forcing: null weights");
+  launch_get_forcing(ctx->d, ctx->ncols, wt1, wt2, qbot_is_rh != 0, ctx->stream);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_phenology(elmk_ctx* ctx, double wt1, double wt2)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  launch_phenology(ctx->d, ctx->ncols, wt1, wt2, ctx->stream);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_initialize_state(elmk_ctx* ctx)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  if (!ctx->have_init_params) return invalid(ctx, "elmk_initialize_state: elmk_set_init_params has not been called");
+  launch_initialize_state(ctx->d, ctx->ncols, ctx->stream);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_evaluate_conservation(elmk_ctx* ctx, double dt, double* min_max_sum, double* per_column)
+{
+  if (int rc = enter_physics(ctx)) return rc;
+  if (!min_max_sum) return invalid(ctx, "elmk_evaluate_conservation: min_max_sum is NULL");
+  const double* diag = ELMK_GENERIC(ctx->h.cons_diag);
+  launch_conservation(ctx->d, ctx->ncols, ctx->ld, dt, diag, ctx->cons_part, ctx->cons_out, ctx->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(min_max_sum, ctx->cons_out, 8 * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (per_column) {  // [8][ncols], diagnostic-major
+    for (int k = 0; k < 8; k++)
+      HIPCHK(hipMemcpyAsync(per_column + (size_t)k * ctx->ncols, diag + (size_t)k * ctx->ld, (size_t)ctx->ncols * 8,
+                            hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
 int elmk_timestep7(elmk_ctx* ctx, double dt)
 {
-  PHYSICS_PROLOGUE();
+  if (int rc = enter_physics(ctx)) return rc;
   // ~22 dependent launches cost ~0.5 ms of launch latency however few columns there are; replaying them as one graph
   // removes the host side of that.  Kernel arguments are the device parameter block (fixed address) and dt.
-  if (ctx->use_graph) return run_graph(ctx, ctx->graph[0], launch_stage7, TS7_NSTAGE, dt);
-  return enqueue_stages(ctx, launch_stage7, TS7_NSTAGE, dt, nullptr);
+  return launch_sequence(ctx, GRAPH_TS7, TS7, dt);
 }
 
 int elmk_timestep7_fused(elmk_ctx* ctx, double dt)
 {
-  PHYSICS_PROLOGUE();
-  if (ctx->use_graph) return run_graph(ctx, ctx->graph[1], launch_stage_fused, ELMK_FUSED_NSTAGE, dt);
-  return enqueue_stages(ctx, launch_stage_fused, ELMK_FUSED_NSTAGE, dt, nullptr);
+  if (int rc = enter_physics(ctx)) return rc;
+  return launch_sequence(ctx, GRAPH_FUSED, FUSED, dt);
 }
-
-namespace {
-// elmk_advance_physics: the fused seven, then the rest of ELMInterface::advance's per-column calls in its order
-constexpr int ADV_NSTAGE = ELMK_FUSED_NSTAGE + 3;
-void launch_stage_advance(elmk_ctx* ctx, int k, double dt)
-{
-  if (k < ELMK_FUSED_NSTAGE) {
-    launch_stage_fused(ctx, k, dt);
-    return;
-  }
-  switch (k - ELMK_FUSED_NSTAGE) {
-    case 0: launch_soil_temperature(ctx->d, ctx->ncols, dt, ctx->stream); break;
-    case 1: launch_snow_hydrology(ctx->d, ctx->ncols, dt, ctx->stream); break;
-    default: launch_surface_fluxes(ctx->d, ctx->ncols, dt, ctx->stream); break;
-  }
-}
-}  // namespace
 
 int elmk_advance_physics(elmk_ctx* ctx, double dt)
 {
-  PHYSICS_PROLOGUE();
-  if (ctx->use_graph) return run_graph(ctx, ctx->graph[2], launch_stage_advance, ADV_NSTAGE, dt);
-  return enqueue_stages(ctx, launch_stage_advance, ADV_NSTAGE, dt, nullptr);
+  if (int rc = enter_physics(ctx)) return rc;
+  return launch_sequence(ctx, GRAPH_ADVANCE, ADVANCE, dt);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // multi-step runs: the driver's time loop (kokkos_driver.cc:54-85) on the device
 // ---------------------------------------------------------------------------------------------------
 namespace {
-bool capturing(elmk_ctx* ctx, hipStream_t s, bool* out)
-{
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hip_fail(ctx, hipStreamIsCapturing(s, &cap), "hipStreamIsCapturing")) return false;
-  *out = cap != hipStreamCaptureStatusNone;
-  return true;
-}
-
 // wait for the runs in flight (they read the run buffers) and for the upload stream (it may still write them), drop the captured
 // step (it holds the old addresses and launch shape) and release the reservation: elmk_run_reserve, elmk_set_forcing_grid and
 // elmk_clear_forcing_grid
 int run_drop(elmk_ctx* ctx)
 {
-  elmk_ctx::Run& R = ctx->run;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (R.upload) HIPCHK(hipStreamSynchronize(R.upload));
-  if (ctx->graph[3].exec) (void)hipGraphExecDestroy(ctx->graph[3].exec);
-  ctx->graph[3].exec = nullptr;
-  run_release(ctx);
+  if (ctx->upload) HIPCHK(hipStreamSynchronize(ctx->upload));
+  ctx->graph[GRAPH_RUN_STEP].drop();
+  ctx->run = elmk_ctx::Run{};
   return ELMK_OK;
 }
 
-// one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
-// forcing, init_timestep, advance_physics' stages, conservation -> ring row, flag summary -> ring row, history, next row
-constexpr int RUN_NSTAGE = 4 + ADV_NSTAGE + 4;
-void launch_stage_run(elmk_ctx* ctx, int k, double dt)
+void run_solar_geometry(elmk_ctx* ctx, double) { launch_solar_geometry_run(ctx->d, ctx->ncols, ctx->run.table, ctx->run.cursor, ctx->stream); }
+void run_phenology(elmk_ctx* ctx, double) { launch_phenology_run(ctx->d, ctx->ncols, ctx->run.table, ctx->run.cursor, ctx->run.phen, ctx->stream); }
+void run_forcing(elmk_ctx* ctx, double)
 {
   const elmk_ctx::Run& R = ctx->run;
-  if (k >= 4 && k < 4 + ADV_NSTAGE) {
-    launch_stage_advance(ctx, k - 4, dt);
-    return;
-  }
-  switch (k < 4 ? k : k - ADV_NSTAGE) {
-    case 0: launch_solar_geometry_run(ctx->d, ctx->ncols, R.table, R.cursor, ctx->stream); break;
-    case 1: launch_phenology_run(ctx->d, ctx->ncols, R.table, R.cursor, R.phen, ctx->stream); break;
-    case 2:
-      if (ctx->grid.mem)
-        launch_get_forcing_run_grid(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, R.fstride, ctx->grid.npad, ctx->grid.idx,
-                                    ctx->grid.w, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
-      else
-        launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
-      break;
-    case 3: launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); break;
-    case 4: {
-      double* diag = ELMK_GENERIC(ctx->h.cons_diag);
-      double* part = diag + (size_t)8 * ctx->ld;
-      launch_conservation_run(ctx->d, ctx->ncols, ctx->ld, dt, diag, part, R.cons, R.flag_or, R.flag_first, R.cursor, ctx->stream);
-      break;
-    }
-    case 5:
-      launch_flag_reduce_run((const uint32_t*)ctx->fptr[ELMK_FIELD_err_flags], ctx->ncols, R.flag_or, R.flag_first, R.cursor, ctx->stream);
-      break;
-    case 6:
-      if ((R.flags & ELMK_RUN_HISTORY) && !ctx->hist.empty())
-        launch_hist_accumulate((const HistRow*)ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, hist_tape_mask(ctx),
-                               ctx->stream);
-      break;
-    default: launch_run_next(R.cursor, ctx->stream); break;
-  }
+  const elmk_ctx::Grid& G = ctx->grid;
+  if (G.mem)
+    launch_get_forcing_run_grid(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, R.fstride, G.npad, G.idx, G.w,
+                                (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
+  else
+    launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
 }
+void run_init_timestep(elmk_ctx* ctx, double) { launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); }
+void run_conservation(elmk_ctx* ctx, double dt)
+{
+  const elmk_ctx::Run& R = ctx->run;
+  launch_conservation_run(ctx->d, ctx->ncols, ctx->ld, dt, ELMK_GENERIC(ctx->h.cons_diag), ctx->cons_part, R.cons, R.flag_or,
+                          R.flag_first, R.cursor, ctx->stream);
+}
+void run_flag_reduce(elmk_ctx* ctx, double)
+{
+  const elmk_ctx::Run& R = ctx->run;
+  launch_flag_reduce_run((const uint32_t*)ctx->fptr[ELMK_FIELD_err_flags], ctx->ncols, R.flag_or, R.flag_first, R.cursor, ctx->stream);
+}
+void run_history(elmk_ctx* ctx, double)
+{
+  if ((ctx->run.flags & ELMK_RUN_HISTORY) && !ctx->hist.empty())
+    launch_hist_accumulate(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, hist_tape_mask(ctx),
+                           ctx->stream);
+}
+void run_next(elmk_ctx* ctx, double) { launch_run_next(ctx->run.cursor, ctx->stream); }
+
+// one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
+// forcing, init_timestep, advance_physics' stages, conservation -> ring row, flag summary -> ring row, history, next row
+constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},   {run_forcing, nullptr}, {run_init_timestep, nullptr},
+                              ADVANCE[0], ADVANCE[1], ADVANCE[2], ADVANCE[3], ADVANCE[4], ADVANCE[5], ADVANCE[6], ADVANCE[7],
+                              {run_conservation, nullptr},   {run_flag_reduce, nullptr}, {run_history, nullptr}, {run_next, nullptr}};
+static_assert(sizeof ADVANCE / sizeof ADVANCE[0] == 8, "RUN_STEP holds every stage of ADVANCE");
 }  // namespace
 
 int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
@@ -1466,59 +1431,39 @@ int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
   if (int rc = enter(ctx)) return rc;
   if (forcing_slots < 2 || forcing_slots > (1 << 20) || max_steps < 1 || max_steps > (1 << 24))
     return invalid(ctx, "elmk_run_reserve: need 2 <= forcing_slots <= 2^20 and 1 <= max_steps <= 2^24");
-  bool cap = false;
-  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
-  if (cap) return invalid(ctx, "elmk_run_reserve: the stream is being captured");
+  if (int rc = refuse_capture(ctx, "elmk_run_reserve: the stream is being captured")) return rc;
   elmk_ctx::Run& R = ctx->run;
   if (int rc = run_drop(ctx)) return rc;
-  if (!R.upload) {
-    HIPCHK(hipStreamCreateWithFlags(&R.upload, hipStreamNonBlocking));
+  if (!ctx->upload) {
+    HIPCHK(hipStreamCreateWithFlags(&ctx->upload, hipStreamNonBlocking));
     for (int b = 0; b < 2; b++) {
-      HIPCHK(hipEventCreateWithFlags(&R.done[b], hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ctx->run_done[b], hipEventDisableTiming));
     }
   }
   const size_t es = (size_t)store_size(ELMK_F64), ld = (size_t)ctx->ld, nrow = 2 * (size_t)max_steps;
   // with a forcing grid the forcing records are cell records, [RUN_NFORC][slots][ncells] without padding
   const int64_t fstride = ctx->grid.mem ? ctx->grid.ncells : ctx->ld;
-  const size_t forc_b = align_up((size_t)RUN_NFORC * forcing_slots * (size_t)fstride * es, 256);
-  const size_t phen_b = align_up((size_t)RUN_NPHEN * RUN_NMONTH * ld * es, 256);
-  const size_t tab_b = align_up(nrow * sizeof(RunRow), 256);
-  const size_t cur_b = 256;
-  const size_t cons_b = align_up(nrow * 24 * sizeof(double), 256);
-  const size_t or_b = align_up(nrow * sizeof(uint32_t), 256);
-  const size_t first_b = align_up(nrow * sizeof(long long), 256);
-  const size_t bytes = forc_b + phen_b + tab_b + cur_b + cons_b + or_b + first_b;
-  if (hip_fail(ctx, hipMalloc((void**)&R.mem, bytes), "hipMalloc(run)")) {
-    R.mem = nullptr;
+  if (hip_fail(ctx, carve(R.mem, &R.bytes, [&](Carve& L) {
+                 L.take(R.forc, (size_t)RUN_NFORC * forcing_slots * (size_t)fstride * es);
+                 L.take(R.phen, (size_t)RUN_NPHEN * RUN_NMONTH * ld * es);
+                 L.take(R.table, nrow * sizeof(RunRow));
+                 L.take(R.cursor, 256);
+                 L.take(R.cons, nrow * 24 * sizeof(double));
+                 L.take(R.flag_or, nrow * sizeof(uint32_t));
+                 L.take(R.flag_first, nrow * sizeof(long long));
+               }), "hipMalloc(run)"))
+    return ELMK_E_NOMEM;
+  if (hip_fail(ctx, R.rows.alloc(nrow * sizeof(RunRow)), "hipHostMalloc(run steps)")) {
+    R = elmk_ctx::Run{};
     return ELMK_E_NOMEM;
   }
-  if (hip_fail(ctx, hipHostMalloc((void**)&R.rows, nrow * sizeof(RunRow), hipHostMallocDefault), "hipHostMalloc(run steps)")) {
-    R.rows = nullptr;
-    run_release(ctx);
-    return ELMK_E_NOMEM;
-  }
-  char* q = R.mem;
-  R.forc = q;
-  q += forc_b;
-  R.phen = q;
-  q += phen_b;
-  R.table = (RunRow*)q;
-  q += tab_b;
-  R.cursor = (int32_t*)q;
-  q += cur_b;
-  R.cons = (double*)q;
-  q += cons_b;
-  R.flag_or = (uint32_t*)q;
-  q += or_b;
-  R.flag_first = (long long*)q;
-  R.bytes = bytes;
   R.slots = forcing_slots;
   R.max_steps = max_steps;
   R.fcols = ctx->grid.mem ? ctx->grid.ncells : ctx->ncols;
   R.fstride = fstride;
-  if (hip_fail(ctx, hipMemsetAsync(R.mem, 0, bytes, ctx->stream), "hipMemset(run)") ||
+  if (hip_fail(ctx, hipMemsetAsync(R.mem, 0, R.bytes, ctx->stream), "hipMemset(run)") ||
       hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
-    run_release(ctx);
+    R = elmk_ctx::Run{};
     return ELMK_E_HIP;
   }
   return ELMK_OK;
@@ -1546,7 +1491,7 @@ int elmk_series_upload(elmk_ctx* ctx, int field, int slot0, int nslots, const do
     if (!R.live[b]) continue;
     const bool hit = forcing ? (slot0 <= R.slot_hi[b] && slot0 + nslots - 1 >= R.slot_lo[b])
                              : ((R.months[b] >> slot0) & ((1u << nslots) - 1u)) != 0;
-    if (hit) HIPCHK(hipEventSynchronize(R.done[b]));
+    if (hit) HIPCHK(hipEventSynchronize(ctx->run_done[b]));
   }
   const size_t es = (size_t)store_size(ELMK_F64);
   char* dst = (forcing ? R.forc : R.phen) + (((size_t)k * nsl + slot0) * (size_t)stride + (size_t)col0) * es;
@@ -1558,8 +1503,8 @@ int elmk_series_upload(elmk_ctx* ctx, int field, int slot0, int nslots, const do
     for (size_t i = 0; i < cnt; i++) tmp[i] = (float)host[i];
     src = tmp.data();
   }
-  HIPCHK(hipMemcpy2DAsync(dst, (size_t)stride * es, src, (size_t)n * es, (size_t)n * es, (size_t)nslots, hipMemcpyHostToDevice, R.upload));
-  HIPCHK(hipStreamSynchronize(R.upload));  // (caller's pageable source; a run enqueued after this call sees the records)
+  HIPCHK(hipMemcpy2DAsync(dst, (size_t)stride * es, src, (size_t)n * es, (size_t)n * es, (size_t)nslots, hipMemcpyHostToDevice, ctx->upload));
+  HIPCHK(hipStreamSynchronize(ctx->upload));  // (caller's pageable source; a run enqueued after this call sees the records)
   return ELMK_OK;
 }
 
@@ -1585,20 +1530,15 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
     hi = std::max(hi, (int)p.forc_slot + 1);
     months |= (1u << p.month1) | (1u << p.month2);
   }
-  bool cap = false;
-  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
-  if (cap) return invalid(ctx, "elmk_run: the stream is being captured");
+  if (int rc = refuse_capture(ctx, "elmk_run: the stream is being captured")) return rc;
 
-  if (!ctx->side.col_dayl) {  // per-column mode, as the first elmk_solar_geometry enters it
-    if (int rc = drop_graphs(ctx)) return rc;
-    ctx->side.col_dayl = true;
-  }
+  if (int rc = set_col_dayl(ctx, true)) return rc;  // per-column mode, as the first elmk_solar_geometry enters it
   if (int rc = heal_lists(ctx)) return rc;
   if (int rc = push_params(ctx)) return rc;
   // this buffer was last used by run count - 2: wait for its end before its pinned rows, device table, ring rows and read set are
   // reused (otherwise an upload after this call would no longer know that run's read set and could write under it)
   const int buf = (int)(R.count & 1);
-  if (R.live[buf]) HIPCHK(hipEventSynchronize(R.done[buf]));
+  if (R.live[buf]) HIPCHK(hipEventSynchronize(ctx->run_done[buf]));
   RunRow* rows = R.rows + (size_t)buf * R.max_steps;
   for (int s = 0; s < nsteps; s++) {
     const elmk_run_step& p = steps[s];
@@ -1626,16 +1566,10 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.last_nsteps = nsteps;
   const uint64_t tag = (uint64_t)flags | (ctx->hist_version << 8);
   int rc = ELMK_OK;
-  for (int s = 0; s < nsteps && rc == ELMK_OK; s++)
-    rc = ctx->use_graph ? run_graph(ctx, ctx->graph[3], launch_stage_run, RUN_NSTAGE, dt, tag)
-                        : enqueue_stages(ctx, launch_stage_run, RUN_NSTAGE, dt, nullptr);
-  HIPCHK(hipEventRecord(R.done[buf], ctx->stream));
+  for (int s = 0; s < nsteps && rc == ELMK_OK; s++) rc = launch_sequence(ctx, GRAPH_RUN_STEP, RUN_STEP, dt, tag);
+  HIPCHK(hipEventRecord(ctx->run_done[buf], ctx->stream));
   if (rc) return rc;
-  if ((flags & ELMK_RUN_HISTORY) && !ctx->hist.empty()) {
-    const unsigned mask = hist_tape_mask(ctx);
-    for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
-      if (mask & (1u << t)) ctx->hist_dirty[t] = true;
-  }
+  if ((flags & ELMK_RUN_HISTORY) && !ctx->hist.empty()) mark_sampled(ctx, hist_tape_mask(ctx));
   return ELMK_OK;
 }
 
@@ -1658,15 +1592,6 @@ int elmk_run_diagnostics(elmk_ctx* ctx, double* min_max_sum, uint32_t* flags_or,
 // ---------------------------------------------------------------------------------------------------
 // forcing on a coarser grid: a per-column ELL remap map on the device (include/elmk.h "forcing grid")
 // ---------------------------------------------------------------------------------------------------
-namespace {
-void grid_release(elmk_ctx* ctx)
-{
-  elmk_ctx::Grid& G = ctx->grid;
-  if (G.mem) (void)hipFree(G.mem);
-  G = elmk_ctx::Grid{};
-}
-}  // namespace
-
 int elmk_set_forcing_grid(elmk_ctx* ctx, int64_t ncells, int npts, const int32_t* idx, const double* w)
 {
   if (int rc = enter(ctx)) return rc;
@@ -1685,31 +1610,25 @@ int elmk_set_forcing_grid(elmk_ctx* ctx, int64_t ncells, int npts, const int32_t
       if (ik[c] >= 0 && !std::isfinite(wk[c])) return invalid(ctx, "elmk_set_forcing_grid: non-finite weight");
     }
   }
-  bool cap = false;
-  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
-  if (cap) return invalid(ctx, "elmk_set_forcing_grid: the stream is being captured");
+  if (int rc = refuse_capture(ctx, "elmk_set_forcing_grid: the stream is being captured")) return rc;
   if (int rc = run_drop(ctx)) return rc;
-  grid_release(ctx);
   elmk_ctx::Grid& G = ctx->grid;
+  G = elmk_ctx::Grid{};
   const int npad = npts <= 1 ? 1 : npts <= 2 ? 2 : npts <= 4 ? 4 : 8;
   const size_t ld = (size_t)ctx->ld;
-  const size_t idx_b = align_up((size_t)npad * ld * sizeof(int32_t), 256), w_b = align_up((size_t)npad * ld * sizeof(double), 256);
-  const size_t cell_b = align_up((size_t)ncells * sizeof(double), 256);
-  if (hip_fail(ctx, hipMalloc((void**)&G.mem, idx_b + w_b + cell_b), "hipMalloc(forcing grid)")) {
-    G.mem = nullptr;
+  if (hip_fail(ctx, carve(G.mem, &G.bytes, [&](Carve& L) {
+                 L.take(G.idx, (size_t)npad * ld * sizeof(int32_t));
+                 L.take(G.w, (size_t)npad * ld * sizeof(double));
+                 L.take(G.cells, (size_t)ncells * sizeof(double));
+               }), "hipMalloc(forcing grid)"))
     return ELMK_E_NOMEM;
-  }
-  G.bytes = idx_b + w_b + cell_b;
-  G.idx = (int32_t*)G.mem;
-  G.w = (double*)(G.mem + idx_b);
-  G.cells = (double*)(G.mem + idx_b + w_b);
   G.ncells = ncells;
   G.npts = npts;
   G.npad = npad;
-  // padding rows and the columns past ncols: idx -1 (all bits set), w 0
+  // padding rows and the columns past ncols: idx -1 (all bits set), w 0 (and the cells after it)
   int rc = ELMK_OK;
-  if (hip_fail(ctx, hipMemsetAsync(G.idx, 0xFF, idx_b, ctx->stream), "hipMemset(grid idx)") ||
-      hip_fail(ctx, hipMemsetAsync(G.w, 0, w_b + cell_b, ctx->stream), "hipMemset(grid w)"))
+  if (hip_fail(ctx, hipMemsetAsync(G.idx, 0xFF, (char*)G.w - (char*)G.idx, ctx->stream), "hipMemset(grid idx)") ||
+      hip_fail(ctx, hipMemsetAsync(G.w, 0, G.mem + G.bytes - (char*)G.w, ctx->stream), "hipMemset(grid w)"))
     rc = ELMK_E_HIP;
   else if (n > 0 &&
            (hip_fail(ctx, hipMemcpy2DAsync(G.idx, ld * sizeof(int32_t), idx, (size_t)n * sizeof(int32_t), (size_t)n * sizeof(int32_t),
@@ -1718,18 +1637,16 @@ int elmk_set_forcing_grid(elmk_ctx* ctx, int64_t ncells, int npts, const int32_t
                                            (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(grid w)")))
     rc = ELMK_E_HIP;
   if (rc == ELMK_OK && hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) rc = ELMK_E_HIP;
-  if (rc != ELMK_OK) grid_release(ctx);
+  if (rc != ELMK_OK) G = elmk_ctx::Grid{};
   return rc;
 }
 
 int elmk_clear_forcing_grid(elmk_ctx* ctx)
 {
   if (int rc = enter(ctx)) return rc;
-  bool cap = false;
-  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
-  if (cap) return invalid(ctx, "elmk_clear_forcing_grid: the stream is being captured");
+  if (int rc = refuse_capture(ctx, "elmk_clear_forcing_grid: the stream is being captured")) return rc;
   if (int rc = run_drop(ctx)) return rc;
-  grid_release(ctx);
+  ctx->grid = elmk_ctx::Grid{};
   return ELMK_OK;
 }
 
@@ -1741,9 +1658,7 @@ int elmk_upload_gridded(elmk_ctx* ctx, int field, int level, const double* cells
   if (!field_ok(field) || g_fields[field].dtype != ELMK_F64) return invalid(ctx, "elmk_upload_gridded: not an fp64 field");
   if (level < 0 || level >= g_fields[field].nlev) return invalid(ctx, "elmk_upload_gridded: level out of range");
   if (!cells) return invalid(ctx, "elmk_upload_gridded: null cells");
-  bool cap = false;
-  if (!capturing(ctx, ctx->stream, &cap)) return ELMK_E_HIP;
-  if (cap) return invalid(ctx, "elmk_upload_gridded: the stream is being captured");
+  if (int rc = refuse_capture(ctx, "elmk_upload_gridded: the stream is being captured")) return rc;
   if (ctx->ncols == 0) return ELMK_OK;
   char* dst = (char*)ctx->fptr[field] + (size_t)level * (size_t)ctx->ld * (size_t)store_size(ELMK_F64);
   // staging is reused by the next call: the copy and the remap are done when this returns, as elmk_upload's copy is
@@ -1780,69 +1695,42 @@ int elmk_clear_errors(elmk_ctx* ctx) { return elmk_fill(ctx, ELMK_FIELD_err_flag
 
 int elmk_profile_timestep7(elmk_ctx* ctx, double dt, int nsteps, float* ms_per_kernel, float* ms_total)
 {
-  PHYSICS_PROLOGUE();
+  if (int rc = enter_physics(ctx)) return rc;
   if (nsteps <= 0) return invalid(ctx, "elmk_profile_timestep7: nsteps <= 0");
-  return profile_stages(ctx, launch_stage7, TS7_NSTAGE, dt, nsteps, ms_per_kernel, ms_total);
+  return profile_stages(ctx, TS7, dt, nsteps, true, nullptr, ms_per_kernel, ms_total, nullptr);
 }
 
 int elmk_profile_timestep7_fused(elmk_ctx* ctx, double dt, int nsteps, float* ms_per_stage, float* ms_total)
 {
-  PHYSICS_PROLOGUE();
+  if (int rc = enter_physics(ctx)) return rc;
   if (nsteps <= 0) return invalid(ctx, "elmk_profile_timestep7_fused: nsteps <= 0");
-  return profile_stages(ctx, launch_stage_fused, ELMK_FUSED_NSTAGE, dt, nsteps, ms_per_stage, ms_total);
+  return profile_stages(ctx, FUSED, dt, nsteps, true, nullptr, ms_per_stage, ms_total, nullptr);
 }
 
 int elmk_profile_steps(elmk_ctx* ctx, int fused, double dt, int nsteps, float* ms_each_step)
 {
-  PHYSICS_PROLOGUE();
+  if (int rc = enter_physics(ctx)) return rc;
   if (nsteps <= 0 || !ms_each_step) return invalid(ctx, "elmk_profile_steps: bad arguments");
-  return fused ? profile_stages(ctx, launch_stage_fused, ELMK_FUSED_NSTAGE, dt, nsteps, nullptr, nullptr, ms_each_step)
-               : profile_stages(ctx, launch_stage7, TS7_NSTAGE, dt, nsteps, nullptr, nullptr, ms_each_step);
+  return profile_stages(ctx, fused ? Stages(FUSED) : Stages(TS7), dt, nsteps, true, nullptr, nullptr, nullptr, ms_each_step);
 }
-
-namespace {
-void launch_one_wrapper(elmk_ctx* ctx, int wrapper, double dt)
-{
-  const RoctxRange range(wrapper == ELMK_WRAPPER_SOIL_TEMPERATURE ? "kokkos_soil_temperature"
-                         : wrapper == ELMK_WRAPPER_SNOW_HYDROLOGY ? "kokkos_snow_hydrology"
-                         : wrapper == ELMK_WRAPPER_SURFACE_FLUXES ? "kokkos_surface_fluxes" : "elmk_wrapper");
-  if (wrapper <= ELMK_WRAPPER_CANOPY_FLUXES)
-    launch_stage7(ctx, wrapper, dt);
-  else if (wrapper == ELMK_WRAPPER_SOIL_TEMPERATURE)
-    launch_soil_temperature(ctx->d, ctx->ncols, dt, ctx->stream);
-  else if (wrapper == ELMK_WRAPPER_SNOW_HYDROLOGY)
-    launch_snow_hydrology(ctx->d, ctx->ncols, dt, ctx->stream);
-  else if (wrapper == ELMK_WRAPPER_ADVANCE_PHYSICS)
-    for (int k = 0; k < ADV_NSTAGE; k++) launch_stage_advance(ctx, k, dt);
-  else
-    launch_surface_fluxes(ctx->d, ctx->ncols, dt, ctx->stream);
-}
-}  // namespace
 
 int elmk_profile_wrapper(elmk_ctx* ctx, int wrapper, double dt, int nsteps, float* ms_mean)
 {
-  PHYSICS_PROLOGUE();
+  if (int rc = enter_physics(ctx)) return rc;
   if (nsteps <= 0 || !ms_mean) return invalid(ctx, "elmk_profile_wrapper: bad arguments");
   if (wrapper < 0 || wrapper > ELMK_WRAPPER_ADVANCE_PHYSICS) return invalid(ctx, "elmk_profile_wrapper: unknown wrapper");
-  EventList ev;
-  HIPCHK(ev.create((size_t)nsteps * 2));
-  for (int s = 0; s < nsteps; s++) {
-    if (!ctx->snap_fields.empty())
-      if (int rc = elmk_restore_fields(ctx)) return rc;
-    HIPCHK(hipEventRecord(ev[(size_t)s * 2], ctx->stream));
-    launch_one_wrapper(ctx, wrapper, dt);
-    HIPCHK(hipEventRecord(ev[(size_t)s * 2 + 1], ctx->stream));
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  double acc = 0.0;
-  for (int s = 0; s < nsteps; s++) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[(size_t)s * 2], ev[(size_t)s * 2 + 1]));
-    acc += ms;
-  }
-  *ms_mean = (float)(acc / nsteps);
-  return ELMK_OK;
+  const Stages L = wrapper <= ELMK_WRAPPER_CANOPY_FLUXES       ? Stages(TS7[wrapper])
+                   : wrapper == ELMK_WRAPPER_SOIL_TEMPERATURE ? Stages(SOIL_TEMPERATURE)
+                   : wrapper == ELMK_WRAPPER_SNOW_HYDROLOGY   ? Stages(SNOW_HYDROLOGY)
+                   : wrapper == ELMK_WRAPPER_SURFACE_FLUXES   ? Stages(SURFACE_FLUXES)
+                                                              : Stages(ADVANCE);
+  const char* label = wrapper == ELMK_WRAPPER_SOIL_TEMPERATURE ? "kokkos_soil_temperature"
+                      : wrapper == ELMK_WRAPPER_SNOW_HYDROLOGY ? "kokkos_snow_hydrology"
+                      : wrapper == ELMK_WRAPPER_SURFACE_FLUXES ? "kokkos_surface_fluxes"
+                                                               : "elmk_wrapper";
+  // one event pair per step around the whole wrapper: bench.py times advance_physics with it, and events between its stages
+  // would change what it measures
+  return profile_stages(ctx, L, dt, nsteps, false, label, nullptr, ms_mean, nullptr);
 }
 
 int elmk_read_scratch(elmk_ctx* ctx, int kind, void* host, int64_t offset, int64_t count)
@@ -1896,14 +1784,14 @@ int elmk_copy_bandwidth_shape(elmk_ctx* ctx, int64_t bytes, int iters, int shape
   if (int rc = enter(ctx)) return rc;
   if (bytes < 512 || iters <= 0 || shape < 0 || shape > 4 || !gbytes_per_s) return invalid(ctx, "elmk_copy_bandwidth: bad arguments");
   const int64_t n = (bytes / 512) * 64;  // whole 512-byte runs: every shape copies the same bytes
-  DevBuf a, b;
+  DevBuf<double> a, b;
   if (hip_fail(ctx, a.alloc((size_t)n * 8), "hipMalloc") || hip_fail(ctx, b.alloc((size_t)n * 8), "hipMalloc")) return ELMK_E_NOMEM;
   EventList ev;
   HIPCHK(ev.create(2));
-  HIPCHK(hipMemsetAsync(a.p, 0, (size_t)n * 8, ctx->stream));
-  launch_copy((const double*)a.p, (double*)b.p, n, ctx->stream, shape);  // warm-up
+  HIPCHK(hipMemsetAsync(a, 0, (size_t)n * 8, ctx->stream));
+  launch_copy(a, b, n, ctx->stream, shape);  // warm-up
   HIPCHK(hipEventRecord(ev[0], ctx->stream));
-  for (int i = 0; i < iters; i++) launch_copy((const double*)a.p, (double*)b.p, n, ctx->stream, shape);
+  for (int i = 0; i < iters; i++) launch_copy(a, b, n, ctx->stream, shape);
   HIPCHK(hipEventRecord(ev[1], ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   float ms = 0.f;
@@ -1919,21 +1807,16 @@ int elmk_math_eval(elmk_ctx* ctx, int fn, const double* x, const double* y, doub
   if (fn < ELMK_MATH_EXP || fn > ELMK_MATH_SIN || !x || !out || n < 0 || (binary && !y))
     return invalid(ctx, "elmk_math_eval: bad arguments");
   if (n == 0) return ELMK_OK;
-  double* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, (size_t)n * 8 * 3));
-  int rc = ELMK_OK;
-  if (hip_fail(ctx, hipMemcpyAsync(d, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync")) rc = ELMK_E_HIP;
-  if (!rc && binary &&
-      hip_fail(ctx, hipMemcpyAsync(d + n, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))
-    rc = ELMK_E_HIP;
-  if (!rc) {
-    launch_math_eval(fn, d, d + n, d + 2 * n, n, ctx->stream);
-    if (hip_fail(ctx, hipMemcpyAsync(out, d + 2 * n, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync") ||
-        hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
-      rc = ELMK_E_HIP;
-  }
-  (void)hipFree(d);
-  return rc;
+  DevBuf<double> d;
+  if (hip_fail(ctx, d.alloc((size_t)n * 8 * 3), "hipMalloc")) return ELMK_E_HIP;
+  if (hip_fail(ctx, hipMemcpyAsync(d, x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync")) return ELMK_E_HIP;
+  if (binary && hip_fail(ctx, hipMemcpyAsync(d + n, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))
+    return ELMK_E_HIP;
+  launch_math_eval(fn, d, d + n, d + 2 * n, n, ctx->stream);
+  if (hip_fail(ctx, hipMemcpyAsync(out, d + 2 * n, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+    return ELMK_E_HIP;
+  return ELMK_OK;
 }
 
 }  // extern "C"
