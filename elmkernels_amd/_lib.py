@@ -90,6 +90,10 @@ SIGNATURES = {
     "elmk_set_forcing_grid": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "elmk_clear_forcing_grid": (C.c_int, [_P]),
     "elmk_upload_gridded": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "elmk_set_output_grid": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_double]),
+    "elmk_clear_output_grid": (C.c_int, [_P]),
+    "elmk_download_gridded": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "elmk_gridded_history_add": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

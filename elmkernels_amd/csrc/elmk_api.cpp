@@ -170,14 +170,20 @@ struct elmk_ctx {
   // itself is side.col_dayl (elmk_solar_geometry sets it, elmk_clear_column_geography clears it)
   DevBuf<double> geo;
   bool geo_set = false;
-  // history (elmk_history_*): the entries, their rows as the device table k_hist_accumulate reads (hist_table: the rows, then one
-  // count per tape), and per tape whether it has accumulated since its last reset (elmk_history_add refuses such a tape)
+  // history (elmk_history_*): the entries, their rows as the device table k_hist_accumulate reads (hist_table: the column rows, one
+  // count per tape, then the cell rows of gridded entries), and per tape whether it has accumulated since its last reset
+  // (elmk_history_add refuses such a tape).  A gridded entry (elmk_gridded_history_add) has cell rows: nlev x cld accumulators over
+  // the output grid's cells, cld = ncells rounded up to 64; their bytes are counted in elmk_device_bytes (hist_cell_bytes).
   struct HistEntry {
     int tape, field, op, nlev, row0;
     DevBuf<double> acc;
+    bool cells = false;
+    int64_t cld = 0;
   };
   std::vector<HistEntry> hist;
   std::vector<HistRow> hist_rows;
+  std::vector<HistRow> hist_crows;
+  size_t hist_cell_bytes = 0;
   DevBuf<HistRow> hist_table;
   bool hist_dirty[ELMK_HIST_MAX_TAPES] = {};
   uint64_t hist_version = 0;  // counts elmk_history_add / _clear: a captured step of elmk_run holds the table of its moment
@@ -220,6 +226,17 @@ struct elmk_ctx {
     double* w = nullptr;
     double* cells = nullptr;
   } grid;
+  // output grid (elmk_set_output_grid): one allocation `mem` holds the CSR map by output cell - ptr (int64, ncells + 1 entries), col
+  // (int32, nnz), w (fp64, nnz) - each region rounded up to 256 bytes
+  struct OGrid {
+    int64_t ncells = 0, nnz = 0;
+    double fill = 0.0;
+    DevBuf<char> mem;
+    size_t bytes = 0;
+    int64_t* ptr = nullptr;
+    int32_t* col = nullptr;
+    double* w = nullptr;
+  } ogrid;
   std::string err;
 };
 
@@ -503,7 +520,7 @@ int64_t elmk_level_stride(const elmk_ctx* ctx) { return ctx ? ctx->ld : -1; }
 int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
   return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
-                         ctx->run.bytes + ctx->grid.bytes)
+                         ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes)
              : -1;
 }
 
@@ -889,8 +906,20 @@ int elmk_set_snow_age_tables(elmk_ctx* ctx, const double* tau, const double* kap
 namespace {
 constexpr int HIST_MAX_ROWS = ELMK_HIST_MAX_ENTRIES * MAXLEV_STAGE;
 constexpr size_t HIST_COUNTS_OFF = ((size_t)HIST_MAX_ROWS * sizeof(HistRow) + 255) / 256 * 256;
+constexpr size_t HIST_CROWS_OFF = HIST_COUNTS_OFF + 256;  // the cell rows of gridded entries
+constexpr size_t HIST_TABLE_BYTES = HIST_CROWS_OFF + (size_t)HIST_MAX_ROWS * sizeof(HistRow);
+static_assert(ELMK_HIST_MAX_TAPES * sizeof(unsigned long long) <= 256, "the counts fit before the cell rows");
 
 unsigned long long* hist_counts(elmk_ctx* ctx) { return (unsigned long long*)((char*)(HistRow*)ctx->hist_table + HIST_COUNTS_OFF); }
+HistRow* hist_cell_rows(elmk_ctx* ctx) { return (HistRow*)((char*)(HistRow*)ctx->hist_table + HIST_CROWS_OFF); }
+
+OGridMap ogrid_map(const elmk_ctx* ctx)
+{
+  const elmk_ctx::OGrid& O = ctx->ogrid;
+  return OGridMap{O.ptr, O.col, O.w, O.ncells, O.fill};
+}
+
+bool has_gridded_entries(const elmk_ctx* ctx) { return !ctx->hist_crows.empty(); }
 
 unsigned hist_tape_mask(const elmk_ctx* ctx)
 {
@@ -909,52 +938,80 @@ void mark_sampled(elmk_ctx* ctx, unsigned mask)
 bool tape_ok(int tape) { return tape >= 0 && tape < ELMK_HIST_MAX_TAPES; }
 }  // namespace
 
-int elmk_history_add(elmk_ctx* ctx, int tape, int field, int op)
+}  // extern "C"
+
+namespace {
+// elmk_history_add (cells = false: accumulators over the columns) and elmk_gridded_history_add (cells = true: over the output grid's
+// cells); `who` names the entry point in the messages
+int hist_add(elmk_ctx* ctx, int tape, int field, int op, bool cells, const char* who)
 {
   if (int rc = enter(ctx)) return rc;
-  if (!tape_ok(tape)) return invalid(ctx, "elmk_history_add: unknown tape");
-  if (!field_ok(field)) return invalid(ctx, "elmk_history_add: unknown field");
-  if (op < ELMK_HIST_AVG || op > ELMK_HIST_INST) return invalid(ctx, "elmk_history_add: unknown op");
-  if ((int)ctx->hist.size() >= ELMK_HIST_MAX_ENTRIES) return invalid(ctx, "elmk_history_add: the history table is full");
-  if (ctx->hist_dirty[tape]) return invalid(ctx, "elmk_history_add: the tape holds samples; reset it first");
-  if (int rc = refuse_capture(ctx, "elmk_history_add: the stream is being captured")) return rc;
+  const std::string w = who;
+  if (!tape_ok(tape)) return invalid(ctx, (w + ": unknown tape").c_str());
+  if (!field_ok(field)) return invalid(ctx, (w + ": unknown field").c_str());
+  if (op < ELMK_HIST_AVG || op > ELMK_HIST_INST) return invalid(ctx, (w + ": unknown op").c_str());
+  if (cells && !ctx->ogrid.mem) return invalid(ctx, (w + ": no output grid (elmk_set_output_grid)").c_str());
+  if ((int)ctx->hist.size() >= ELMK_HIST_MAX_ENTRIES) return invalid(ctx, (w + ": the history table is full").c_str());
+  if (ctx->hist_dirty[tape]) return invalid(ctx, (w + ": the tape holds samples; reset it first").c_str());
+  if (int rc = refuse_capture(ctx, (w + ": the stream is being captured").c_str())) return rc;
   if (!ctx->hist_table) {
-    HIPCHK(ctx->hist_table.alloc(HIST_COUNTS_OFF + ELMK_HIST_MAX_TAPES * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(ctx->hist_table, 0, HIST_COUNTS_OFF + ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx->hist_table.alloc(HIST_TABLE_BYTES));
+    HIPCHK(hipMemsetAsync(ctx->hist_table, 0, HIST_TABLE_BYTES, ctx->stream));
   }
   const int nlev = g_fields[field].nlev;
+  // a column row spans the level stride; a cell row the cell count rounded up to 64 (16-byte aligned rows for k_hist_reset's pairs)
+  const int64_t ld = cells ? (ctx->ogrid.ncells + 63) / 64 * 64 : ctx->ld;
+  const size_t bytes = (size_t)nlev * (size_t)ld * sizeof(double);
   DevBuf<double> acc;
-  if (hip_fail(ctx, acc.alloc((size_t)nlev * (size_t)ctx->ld * sizeof(double)), "hipMalloc(history)")) return ELMK_E_NOMEM;
-  launch_fill(acc, ELMK_F64, nlev, ctx->ld, ctx->ld, hist_init_value(op), ctx->stream);
-  const int row0 = (int)ctx->hist_rows.size();
+  if (hip_fail(ctx, acc.alloc(bytes), "hipMalloc(history)")) return ELMK_E_NOMEM;
+  launch_fill(acc, ELMK_F64, nlev, ld, ld, hist_init_value(op), ctx->stream);
+  std::vector<HistRow>& rows = cells ? ctx->hist_crows : ctx->hist_rows;
+  HistRow* table = cells ? hist_cell_rows(ctx) : (HistRow*)ctx->hist_table;
+  const int row0 = (int)rows.size();
   const int es = store_size(g_fields[field].dtype);
   for (int l = 0; l < nlev; l++)
-    ctx->hist_rows.push_back(HistRow{(const char*)ctx->fptr[field] + (size_t)l * (size_t)ctx->ld * es, acc + (size_t)l * (size_t)ctx->ld,
-                                     store_dtype(g_fields[field].dtype), op, tape, 0});
+    rows.push_back(HistRow{(const char*)ctx->fptr[field] + (size_t)l * (size_t)ctx->ld * es, acc + (size_t)l * (size_t)ld,
+                           store_dtype(g_fields[field].dtype), op, tape, 0});
   // the stream may still run an accumulate that reads the table: the copy is ordered after it; pageable source, so wait
   const hipError_t e1 = hipGetLastError();
-  const hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(ctx->hist_table + row0, &ctx->hist_rows[row0],
-                                                          (size_t)nlev * sizeof(HistRow), hipMemcpyHostToDevice, ctx->stream)
+  const hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(table + row0, &rows[row0], (size_t)nlev * sizeof(HistRow), hipMemcpyHostToDevice,
+                                                          ctx->stream)
                                          : e1;
   const hipError_t e3 = e2 == hipSuccess ? hipStreamSynchronize(ctx->stream) : e2;
-  if (hip_fail(ctx, e3, "elmk_history_add")) {
-    ctx->hist_rows.resize(row0);
+  if (hip_fail(ctx, e3, who)) {
+    rows.resize(row0);
     (void)hipStreamSynchronize(ctx->stream);
     return ELMK_E_HIP;  // (frees acc)
   }
-  ctx->hist.push_back(elmk_ctx::HistEntry{tape, field, op, nlev, row0, std::move(acc)});
+  ctx->hist.push_back(elmk_ctx::HistEntry{tape, field, op, nlev, row0, std::move(acc), cells, ld});
+  if (cells) ctx->hist_cell_bytes += align_up(bytes, 256);
   ctx->hist_version++;
   return (int)ctx->hist.size() - 1;
 }
+
+// every row of every tape, one launch: the column rows alone as before any gridded entry existed, else with the cell rows after them
+void hist_accumulate_launch(elmk_ctx* ctx)
+{
+  const unsigned mask = hist_tape_mask(ctx);
+  if (!has_gridded_entries(ctx))
+    launch_hist_accumulate(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
+  else
+    launch_hist_accumulate_cells(ctx->hist_table, (int)ctx->hist_rows.size(), hist_cell_rows(ctx), (int)ctx->hist_crows.size(),
+                                 ogrid_map(ctx), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
+}
+}  // namespace
+
+extern "C" {
+
+int elmk_history_add(elmk_ctx* ctx, int tape, int field, int op) { return hist_add(ctx, tape, field, op, false, "elmk_history_add"); }
 
 int elmk_history_accumulate(elmk_ctx* ctx)
 {
   if (int rc = enter(ctx)) return rc;
   if (ctx->hist.empty()) return ELMK_OK;
-  const unsigned mask = hist_tape_mask(ctx);
-  launch_hist_accumulate(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
+  hist_accumulate_launch(ctx);
   HIPCHK(hipGetLastError());
-  mark_sampled(ctx, mask);
+  mark_sampled(ctx, hist_tape_mask(ctx));
   return ELMK_OK;
 }
 
@@ -964,6 +1021,11 @@ int elmk_history_reset(elmk_ctx* ctx, int tape)
   if (!tape_ok(tape)) return invalid(ctx, "elmk_history_reset: unknown tape");
   if (ctx->hist_table) {
     launch_hist_reset(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, tape, ctx->stream);
+    HIPCHK(hipGetLastError());
+  }
+  if (has_gridded_entries(ctx)) {  // (resets the tape's count a second time)
+    launch_hist_reset(hist_cell_rows(ctx), (int)ctx->hist_crows.size(), hist_counts(ctx), (ctx->ogrid.ncells + 63) / 64 * 64, tape,
+                      ctx->stream);
     HIPCHK(hipGetLastError());
   }
   ctx->hist_dirty[tape] = false;
@@ -986,9 +1048,11 @@ int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int6
 {
   if (int rc = enter(ctx)) return rc;
   if (entry < 0 || entry >= (int)ctx->hist.size()) return invalid(ctx, "elmk_history_read: unknown entry");
-  if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols) return invalid(ctx, "elmk_history_read: bad column range");
-  if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_history_read: unknown layout");
   const elmk_ctx::HistEntry& e = ctx->hist[entry];
+  const int64_t lim = e.cells ? ctx->ogrid.ncells : ctx->ncols;  // a gridded entry's col0, n index cells
+  if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > lim)
+    return invalid(ctx, e.cells ? "elmk_history_read: bad cell range" : "elmk_history_read: bad column range");
+  if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_history_read: unknown layout");
   int64_t count = 0;
   if (int rc = elmk_history_count(ctx, e.tape, &count)) return rc;
   if (count <= 0) return invalid(ctx, "elmk_history_read: the tape holds no samples");
@@ -1001,7 +1065,10 @@ int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int6
   double* soa = (double*)(ctx->staging + half);
   for (int64_t done = 0; done < n; done += chunk) {
     const int64_t m = (n - done) < chunk ? (n - done) : chunk;
-    launch_hist_finalize(e.acc, ctx->ld, e.nlev, e.op, count, col0 + done, m, soa, ctx->stream);
+    if (e.cells)
+      launch_ogrid_finalize(e.acc, e.cld, e.nlev, e.op, count, ctx->ogrid.ptr, ctx->ogrid.fill, col0 + done, m, soa, ctx->stream);
+    else
+      launch_hist_finalize(e.acc, ctx->ld, e.nlev, e.op, count, col0 + done, m, soa, ctx->stream);
     if (layout == ELMK_LAYOUT_SOA || e.nlev == 1) {
       HIPCHK(hipMemcpy2DAsync(host + done, (size_t)n * sizeof(double), soa, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
                               e.nlev, hipMemcpyDeviceToHost, ctx->stream));
@@ -1022,6 +1089,8 @@ int elmk_history_clear(elmk_ctx* ctx)
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->hist.clear();
   ctx->hist_rows.clear();
+  ctx->hist_crows.clear();
+  ctx->hist_cell_bytes = 0;
   if (ctx->hist_table)
     HIPCHK(hipMemsetAsync(hist_counts(ctx), 0, ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
   for (bool& d : ctx->hist_dirty) d = false;
@@ -1412,9 +1481,7 @@ void run_flag_reduce(elmk_ctx* ctx, double)
 }
 void run_history(elmk_ctx* ctx, double)
 {
-  if ((ctx->run.flags & ELMK_RUN_HISTORY) && !ctx->hist.empty())
-    launch_hist_accumulate(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, hist_tape_mask(ctx),
-                           ctx->stream);
+  if ((ctx->run.flags & ELMK_RUN_HISTORY) && !ctx->hist.empty()) hist_accumulate_launch(ctx);
 }
 void run_next(elmk_ctx* ctx, double) { launch_run_next(ctx->run.cursor, ctx->stream); }
 
@@ -1667,6 +1734,87 @@ int elmk_upload_gridded(elmk_ctx* ctx, int field, int level, const double* cells
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return ELMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// output grid: columns aggregated onto cells on the device through a CSR map (include/elmk.h "output grid")
+// ---------------------------------------------------------------------------------------------------
+int elmk_set_output_grid(elmk_ctx* ctx, int64_t ncells, const int64_t* ptr, const int32_t* col, const double* w, double fill)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (ncells < 1 || ncells > INT32_MAX) return invalid(ctx, "elmk_set_output_grid: ncells outside 1 .. 2^31-1");
+  if (!ptr) return invalid(ctx, "elmk_set_output_grid: null ptr");
+  if (ptr[0] != 0) return invalid(ctx, "elmk_set_output_grid: ptr[0] != 0");
+  for (int64_t i = 0; i < ncells; i++)
+    if (ptr[i + 1] < ptr[i]) return invalid(ctx, "elmk_set_output_grid: ptr decreasing");
+  const int64_t nnz = ptr[ncells];
+  if (nnz > INT32_MAX) return invalid(ctx, "elmk_set_output_grid: nnz outside 0 .. 2^31-1");
+  if (nnz > 0 && (!col || !w)) return invalid(ctx, "elmk_set_output_grid: null map");
+  // every gather of the aggregate kernels stays inside a source row because of these checks
+  for (int64_t p = 0; p < nnz; p++) {
+    if (col[p] < 0 || col[p] >= ctx->ncols) return invalid(ctx, "elmk_set_output_grid: col outside [0, ncols)");
+    if (!std::isfinite(w[p])) return invalid(ctx, "elmk_set_output_grid: non-finite weight");
+  }
+  if (int rc = refuse_capture(ctx, "elmk_set_output_grid: the stream is being captured")) return rc;
+  if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_set_output_grid: gridded history entries exist (elmk_history_clear first)");
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // (a gridded download may still read the old map)
+  elmk_ctx::OGrid& O = ctx->ogrid;
+  O = elmk_ctx::OGrid{};
+  if (hip_fail(ctx, carve(O.mem, &O.bytes, [&](Carve& L) {
+                 L.take(O.ptr, (size_t)(ncells + 1) * sizeof(int64_t));
+                 L.take(O.col, (size_t)nnz * sizeof(int32_t));
+                 L.take(O.w, (size_t)nnz * sizeof(double));
+               }), "hipMalloc(output grid)"))
+    return ELMK_E_NOMEM;
+  O.ncells = ncells;
+  O.nnz = nnz;
+  O.fill = fill;
+  int rc = ELMK_OK;
+  if (hip_fail(ctx, hipMemcpyAsync(O.ptr, ptr, (size_t)(ncells + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(ptr)") ||
+      (nnz > 0 && (hip_fail(ctx, hipMemcpyAsync(O.col, col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(col)") ||
+                   hip_fail(ctx, hipMemcpyAsync(O.w, w, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(w)"))) ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+    rc = ELMK_E_HIP;
+  if (rc != ELMK_OK) O = elmk_ctx::OGrid{};
+  return rc;
+}
+
+int elmk_clear_output_grid(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_clear_output_grid: the stream is being captured")) return rc;
+  if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_clear_output_grid: gridded history entries exist (elmk_history_clear first)");
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->ogrid = elmk_ctx::OGrid{};
+  return ELMK_OK;
+}
+
+int elmk_download_gridded(elmk_ctx* ctx, int field, int level, double* cells)
+{
+  if (int rc = enter(ctx)) return rc;
+  const elmk_ctx::OGrid& O = ctx->ogrid;
+  if (!O.mem) return invalid(ctx, "elmk_download_gridded: no output grid (elmk_set_output_grid)");
+  if (!field_ok(field)) return invalid(ctx, "elmk_download_gridded: unknown field");
+  if (level < 0 || level >= g_fields[field].nlev) return invalid(ctx, "elmk_download_gridded: level out of range");
+  if (!cells) return invalid(ctx, "elmk_download_gridded: null cells");
+  if (int rc = refuse_capture(ctx, "elmk_download_gridded: the stream is being captured")) return rc;
+  const int es = store_size(g_fields[field].dtype);
+  const char* src = (const char*)ctx->fptr[field] + (size_t)level * (size_t)ctx->ld * es;
+  // chunks of cells through the staging buffer, which the next chunk reuses
+  const int64_t chunk = (int64_t)(ctx->staging_bytes / sizeof(double));
+  for (int64_t done = 0; done < O.ncells; done += chunk) {
+    const int64_t m = (O.ncells - done) < chunk ? (O.ncells - done) : chunk;
+    launch_ogrid_aggregate(src, store_dtype(g_fields[field].dtype), ogrid_map(ctx), done, m, (double*)(char*)ctx->staging, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cells + done, ctx->staging, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return ELMK_OK;
+}
+
+int elmk_gridded_history_add(elmk_ctx* ctx, int tape, int field, int op)
+{
+  return hist_add(ctx, tape, field, op, true, "elmk_gridded_history_add");
 }
 
 // ---------------------------------------------------------------------------------------------------

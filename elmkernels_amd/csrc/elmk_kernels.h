@@ -150,4 +150,23 @@ void launch_hist_reset(const HistRow* rows, int nrows, unsigned long long* count
 void launch_hist_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, int64_t col0, int64_t m, double* out,
                           hipStream_t st);
 
+// output grid (k_history.hip, elmk_set_output_grid): the CSR map by output cell on the device - cell i owns terms ptr[i] .. ptr[i+1]-1,
+// each a source column col[p] in [0, ncols) and a weight w[p]; a cell with no terms reads fill
+struct OGridMap {
+  const int64_t* ptr;
+  const int32_t* col;
+  const double* w;
+  int64_t ncells;
+  double fill;
+};
+// cells [cell0, cell0 + m) of the source row src (stored element type dtype, as HistRow::dtype) into out[0 .. m)
+void launch_ogrid_aggregate(const void* src, int dtype, const OGridMap& M, int64_t cell0, int64_t m, double* out, hipStream_t st);
+// launch_hist_accumulate over the column rows and, in the same launch, the cell rows crows[ncrows] (acc: cells of one level, fp64)
+void launch_hist_accumulate_cells(const HistRow* rows, int nrows, const HistRow* crows, int ncrows, const OGridMap& M,
+                                  unsigned long long* counts, int64_t ncols, unsigned tape_mask, hipStream_t st);
+// cells [cell0, cell0 + m) of one gridded entry's result (level stride ld) into out[lev * m + i]: fill for an empty cell, else as
+// launch_hist_finalize
+void launch_ogrid_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, const int64_t* ptr, double fill, int64_t cell0,
+                           int64_t m, double* out, hipStream_t st);
+
 }  // namespace elmk

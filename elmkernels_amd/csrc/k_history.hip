@@ -47,6 +47,18 @@ __device__ __forceinline__ hd2 load_pair(const void* src, int dtype, int64_t c)
   return v;
 }
 
+// one column of a source row, widened to fp64 as load_pair widens it (a gather: no nontemporal hint, neighbouring cells re-read lines)
+__device__ __forceinline__ double load_one(const void* src, int dtype, int64_t c)
+{
+  switch (dtype) {
+    case ELMK_F64: return ((const ELMK_GLOBAL double*)src)[c];
+    case ELMK_F32_STORED: return (double)((const ELMK_GLOBAL float*)src)[c];
+    case ELMK_I32: return (double)((const ELMK_GLOBAL int32_t*)src)[c];
+    case ELMK_U32: return (double)((const ELMK_GLOBAL uint32_t*)src)[c];
+    default: return (double)((const ELMK_GLOBAL uint8_t*)src)[c];
+  }
+}
+
 __device__ __forceinline__ double fold(int op, double acc, double v)
 {
   switch (op) {
@@ -56,6 +68,17 @@ __device__ __forceinline__ double fold(int op, double acc, double v)
     case ELMK_HIST_MIN: return (v < acc || v != v) ? v : acc;
     default: return v;  // ELMK_HIST_INST
   }
+}
+// column pair p of a column row
+__device__ __forceinline__ void fold_pair(const HistRow& r, int64_t p)
+{
+  const int64_t c = 2 * p;
+  const hd2 v = load_pair(r.src, r.dtype, c);
+  ELMK_GLOBAL hd2* a = (ELMK_GLOBAL hd2*)r.acc + p;
+  hd2 acc = h_ld(a);
+  acc.x = fold(r.op, acc.x, v.x);
+  acc.y = fold(r.op, acc.y, v.y);
+  h_st(a, acc);
 }
 }  // namespace
 
@@ -70,13 +93,7 @@ __global__ __launch_bounds__(256) void k_hist_accumulate(const HistRow* __restri
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npairs) return;
   const HistRow r = rows[blockIdx.y];
-  const int64_t c = 2 * p;
-  const hd2 v = load_pair(r.src, r.dtype, c);
-  ELMK_GLOBAL hd2* a = (ELMK_GLOBAL hd2*)r.acc + p;
-  hd2 acc = h_ld(a);
-  acc.x = fold(r.op, acc.x, v.x);
-  acc.y = fold(r.op, acc.y, v.y);
-  h_st(a, acc);
+  fold_pair(r, p);
 }
 
 // the rows of one tape back to their initial value, the tape's count to 0 (rows of other tapes: nothing)
@@ -126,6 +143,132 @@ void launch_hist_finalize(const double* acc, int64_t ld, int nlev, int op, int64
   if (m <= 0) return;
   hipLaunchKernelGGL(k_hist_finalize, dim3((unsigned)((m + 255) / 256), (unsigned)nlev), dim3(256), 0, st, acc, ld, op, count, col0, m,
                      out);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// output grid (elmk_set_output_grid, elmk_download_gridded, elmk_gridded_history_add): columns averaged onto cells through a CSR map.
+// The value of cell i of a source row x is w[p0] * x[col[p0]], then + w[p] * x[col[p]] for p = p0+1 .. p1-1 in that order, with no
+// contraction; a cell with no terms is `fill`.  One workgroup takes AGG_CELLS consecutive cells of one row, and the terms of those
+// cells are one contiguous span of the map: the workgroup walks it in tiles of AGG_TILE terms, every thread forming the products of
+// its share of a tile with coalesced loads of col and w (and of x, when a cell's columns are contiguous) into LDS, then thread t
+// adds the products of cell t out of LDS in CSR order.  A product is one rounding whichever lane forms it, and every sum is taken
+// by one lane in term order, so the result is the host's (regrid.apply_aggregate) bit for bit; no atomics.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+constexpr int AGG_THREADS = 256, AGG_CELLS = 64, AGG_TILE = 2048;
+
+// cells [c0, min(c0 + AGG_CELLS, cend)) of the source row src; called by every thread of the workgroup (it has barriers, and c0 is
+// uniform).  Thread t < AGG_CELLS returns the value of cell c0 + t (fill for an empty cell or a thread past the end) and in *empty
+// whether that cell has no terms.
+__device__ __forceinline__ double agg_cells(const void* src, int dtype, const OGridMap& M, int64_t c0, int64_t cend, double* tile,
+                                            bool* empty)
+{
+  const int t = threadIdx.x;
+  const int64_t c1 = c0 + AGG_CELLS < cend ? c0 + AGG_CELLS : cend;
+  const int64_t P0 = M.ptr[c0], P1 = M.ptr[c1];
+  int64_t p0 = 0, p1 = 0;
+  if (t < AGG_CELLS && c0 + t < c1) {
+    p0 = M.ptr[c0 + t];
+    p1 = M.ptr[c0 + t + 1];
+  }
+  double v = M.fill;
+  for (int64_t base = P0; base < P1; base += AGG_TILE) {
+    const int m = (int)(P1 - base < AGG_TILE ? P1 - base : AGG_TILE);
+#pragma unroll
+    for (int k = 0; k < AGG_TILE / AGG_THREADS; k++) {
+      const int q = k * AGG_THREADS + t;
+      if (q < m) tile[q] = M.w[base + q] * load_one(src, dtype, M.col[base + q]);
+    }
+    __syncthreads();
+    const int64_t lo = p0 > base ? p0 : base, hi = p1 < base + m ? p1 : base + m;
+    for (int64_t p = lo; p < hi; p++) {
+      const double x = tile[p - base];
+      v = p == p0 ? x : v + x;
+    }
+    __syncthreads();
+  }
+  *empty = p0 == p1;
+  return v;
+}
+}  // namespace
+
+// cells [cell0, cell0 + m) of one source row into out[0 .. m); grid (ceil(m / AGG_CELLS))
+__global__ __launch_bounds__(AGG_THREADS) void k_ogrid_aggregate(const void* __restrict__ src, int dtype, OGridMap M, int64_t cell0,
+                                                                 int64_t m, double* __restrict__ out)
+{
+  __shared__ double tile[AGG_TILE];
+  const int64_t c0 = cell0 + (int64_t)blockIdx.x * AGG_CELLS;
+  bool empty;
+  const double v = agg_cells(src, dtype, M, c0, cell0 + m, tile, &empty);
+  if (threadIdx.x < AGG_CELLS && c0 + threadIdx.x < cell0 + m) out[c0 - cell0 + threadIdx.x] = v;
+}
+
+// k_hist_accumulate with cell rows after the column rows: grid (max(column pair blocks, cell blocks), nrows + ncrows).  Row y < nrows
+// is a column row, folded as k_hist_accumulate folds it; row nrows + k is cell row crows[k]: acc[c] = fold(op, acc[c], aggregate of
+// cell c of the current value), skipped for an empty cell (it reads fill).
+__global__ __launch_bounds__(256) void k_hist_accumulate_cells(const HistRow* __restrict__ rows, int nrows, const HistRow* __restrict__ crows,
+                                                               OGridMap M, unsigned long long* __restrict__ counts, int64_t npairs,
+                                                               unsigned tape_mask)
+{
+  static_assert(AGG_THREADS == 256, "one block shape for both kinds of rows");
+  __shared__ double tile[AGG_TILE];
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
+      if (tape_mask & (1u << t)) atomicAdd(&counts[t], 1ull);
+  }
+  if ((int)blockIdx.y < nrows) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npairs) return;
+    const HistRow r = rows[blockIdx.y];
+    fold_pair(r, p);
+    return;
+  }
+  const int64_t c0 = (int64_t)blockIdx.x * AGG_CELLS;
+  if (c0 >= M.ncells) return;
+  const HistRow r = crows[blockIdx.y - nrows];
+  bool empty;
+  const double g = agg_cells(r.src, r.dtype, M, c0, M.ncells, tile, &empty);
+  const int64_t c = c0 + threadIdx.x;
+  if (threadIdx.x < AGG_CELLS && c < M.ncells && !empty) r.acc[c] = fold(r.op, r.acc[c], g);
+}
+
+// cells [cell0, cell0 + m) of one gridded entry's result into out[lev * m + i]: fill for an empty cell, else as k_hist_finalize
+__global__ __launch_bounds__(256) void k_ogrid_finalize(const double* __restrict__ acc, int64_t ld, int op, int64_t count,
+                                                        const int64_t* __restrict__ ptr, double fill, int64_t cell0, int64_t m,
+                                                        double* __restrict__ out)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const int lev = blockIdx.y;
+  const int64_t c = cell0 + i;
+  const double a = acc[(int64_t)lev * ld + c];
+  out[(int64_t)lev * m + i] = ptr[c] == ptr[c + 1] ? fill : op == ELMK_HIST_AVG ? a / (double)count : a;
+}
+
+static unsigned cell_blocks(int64_t ncells) { return (unsigned)(ncells > 0 ? (ncells + AGG_CELLS - 1) / AGG_CELLS : 1); }
+
+void launch_ogrid_aggregate(const void* src, int dtype, const OGridMap& M, int64_t cell0, int64_t m, double* out, hipStream_t st)
+{
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_ogrid_aggregate, dim3(cell_blocks(m)), dim3(AGG_THREADS), 0, st, src, dtype, M, cell0, m, out);
+}
+
+void launch_hist_accumulate_cells(const HistRow* rows, int nrows, const HistRow* crows, int ncrows, const OGridMap& M,
+                                  unsigned long long* counts, int64_t ncols, unsigned tape_mask, hipStream_t st)
+{
+  const int64_t npairs = (ncols + 1) / 2;
+  const unsigned pb = nrows > 0 ? pair_blocks(npairs) : 1u, cb = cell_blocks(M.ncells);
+  const unsigned bx = pb > cb ? pb : cb;
+  hipLaunchKernelGGL(k_hist_accumulate_cells, dim3(bx, (unsigned)(nrows + ncrows)), dim3(256), 0, st, rows, nrows, crows, M, counts, npairs,
+                     tape_mask);
+}
+
+void launch_ogrid_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, const int64_t* ptr, double fill, int64_t cell0,
+                           int64_t m, double* out, hipStream_t st)
+{
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_ogrid_finalize, dim3((unsigned)((m + 255) / 256), (unsigned)nlev), dim3(256), 0, st, acc, ld, op, count, ptr, fill,
+                     cell0, m, out);
 }
 
 }  // namespace elmk

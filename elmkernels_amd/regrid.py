@@ -1,5 +1,6 @@
-"""Forcing on a coarser grid, host side (numpy only): build the per-column remap maps that elmk_set_forcing_grid takes, and apply
-them exactly as the device does.
+"""Forcing on a coarser grid and output on a grid, host side (numpy only): build the per-column remap maps that
+elmk_set_forcing_grid takes and the per-cell aggregation maps that elmk_set_output_grid takes, and apply both exactly as the device
+does.
 
 A map is ELL ("padded sparse rows"): idx int32 [npts, ncols] and w float64 [npts, ncols], up to npts source cells per column,
 row k of every column in SoA order.  idx = -1 is padding; row 0 never holds it.  The value of column c of cell values a is
@@ -132,3 +133,108 @@ def slice_map(idx, w, col0, n):
     cells = np.unique(idx[idx >= 0]).astype(np.int64)
     local = np.where(idx >= 0, np.searchsorted(cells, np.where(idx >= 0, idx, 0)), -1).astype(np.int32)
     return local, w, cells
+
+
+# ---- output grid (elmk_set_output_grid): columns aggregated onto cells ----------------------------------------------------------
+# A map is CSR by output cell: ptr int64 [ncells + 1] (ptr[0] = 0, non-decreasing), col int32 [nnz] (source columns) and w float64
+# [nnz]; cell i owns terms ptr[i] .. ptr[i+1]-1.  The value of cell i of a column row x is fill for a cell without terms, else
+#
+#     v = w[p0] * x[col[p0]];   then for p = p0+1 .. p1-1:  v = v + w[p] * x[col[p]]
+#
+# in that order, without fused multiply-adds (include/elmk.h, "output grid").
+
+
+def _csr(ptr, col, w):
+    ptr = np.asarray(ptr, dtype=np.int64).reshape(-1)
+    col = np.asarray(col).reshape(-1)
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if ptr.size < 2 or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != col.size or col.size != w.size:
+        raise ValueError("not a CSR map: ptr [ncells + 1] from 0, non-decreasing, ptr[-1] == len(col) == len(w)")
+    return ptr, col, w
+
+
+def apply_aggregate(ptr, col, w, x, fill):
+    """Cell values of column values `x` ([ncols], or [nrec, ncols] for several rows at once) through the CSR map ptr / col / w, in
+    the device's operation order: one rounded product per term, summed in term order from the first product.  Returns float64
+    [ncells] (or [nrec, ncells]); a cell without terms is `fill`."""
+    ptr, col, w = _csr(ptr, col, w)
+    x = np.asarray(x, dtype=np.float64)
+    ncells = ptr.size - 1
+    cnt = np.diff(ptr)
+    v = np.full(x.shape[:-1] + (ncells,), float(fill))
+    if col.size == 0:
+        return v
+    t = w * x[..., col]  # every product, rounded once
+    live = np.nonzero(cnt > 0)[0]
+    v[..., live] = t[..., ptr[live]]
+    # term k of every cell that has one, while many cells are still adding; then the few long cells one by one (add.accumulate
+    # adds strictly left to right, so prepending the running value continues the same chain of roundings)
+    k = 1
+    while True:
+        live = live[cnt[live] > k]
+        if live.size <= 32:
+            break
+        v[..., live] = v[..., live] + t[..., ptr[live] + k]
+        k += 1
+    for c in live:
+        seq = np.concatenate([v[..., c:c + 1], t[..., ptr[c] + k:ptr[c + 1]]], axis=-1)
+        v[..., c] = np.add.accumulate(seq, axis=-1)[..., -1]
+    return v
+
+
+def owner_map(cell_of_col, area, ncells):
+    """ELM's c2g: every column belongs to one cell (cell_of_col [ncols]; a negative entry belongs to none) and the cell value is the
+    area-weighted mean of its columns, w = area_c / (sum of area over the cell's columns).  Terms are in ascending column order; a
+    cell without columns has no terms.  Returns (ptr int64 [ncells + 1], col int32 [nnz], w float64 [nnz])."""
+    cell = np.asarray(cell_of_col, dtype=np.int64).reshape(-1)
+    area = np.asarray(area, dtype=np.float64).reshape(-1)
+    if cell.size != area.size:
+        raise ValueError("cell_of_col and area must both be [ncols]")
+    if cell.size and cell.max() >= ncells:
+        raise ValueError("cell_of_col out of range")
+    cols = np.nonzero(cell >= 0)[0]
+    order = cols[np.argsort(cell[cols], kind="stable")]  # by cell, ascending column inside a cell
+    cnt = np.bincount(cell[cols], minlength=ncells)
+    tot = np.bincount(cell[cols], weights=area[cols], minlength=ncells)
+    if np.any((cnt > 0) & ~(tot > 0.0)) or not np.all(np.isfinite(tot)):
+        raise ValueError("a cell's columns must have a finite, positive total area")
+    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    return ptr, order.astype(np.int32), area[order] / tot[cell[order]]
+
+
+def from_sparse_cells(row, col, S, ncells, ncols, one_based=False):
+    """A land -> atmosphere map file's triplets - row = destination cell, col = source column, S = weight (the row / col / S variables
+    of an ESMF or TempestRemap file; one_based=True for their 1-based indices) - as a CSR map by cell.  Each cell's terms are in
+    ascending column order, stable for a repeated column; a cell without triplets has no terms.  Returns (ptr, col, w)."""
+    row = np.asarray(row, dtype=np.int64).reshape(-1)
+    col = np.asarray(col, dtype=np.int64).reshape(-1)
+    S = np.asarray(S, dtype=np.float64).reshape(-1)
+    if not (row.size == col.size == S.size):
+        raise ValueError("row, col and S must have the same length")
+    if one_based:
+        row, col = row - 1, col - 1
+    if row.size and (row.min() < 0 or row.max() >= ncells or col.min() < 0 or col.max() >= ncols):
+        raise ValueError("row or col out of range")
+    order = np.lexsort((col, row))  # by cell, then by column (stable)
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=ncells))]).astype(np.int64)
+    return ptr, col[order].astype(np.int32), S[order]
+
+
+def slice_output_map(ptr, col, w, col0, n):
+    """One rank's part of an output map when it holds columns [col0, col0 + n) (decomp.block_range).  Returns (ptr_l, col_l, w_l,
+    cells, straddling): the local map of the cells whose every term lies in the block, with columns renumbered from col0; `cells`
+    (int64, ascending) their global ids, so apply_aggregate(ptr_l, col_l, w_l, x[col0:col0 + n], fill) is
+    apply_aggregate(ptr, col, w, x, fill)[cells] bit for bit; and `straddling` (int64, ascending) the cells with terms both inside
+    and outside the block.  Cells without terms are in no rank's list (they are fill everywhere).  Combining a straddling cell across
+    ranks is left to the driver."""
+    ptr, col, w = _csr(ptr, col, w)
+    ncells = ptr.size - 1
+    cell_of_term = np.repeat(np.arange(ncells), np.diff(ptr))
+    inside = (col >= col0) & (col < col0 + n)
+    nin = np.bincount(cell_of_term, weights=inside, minlength=ncells).astype(np.int64)
+    cnt = np.diff(ptr)
+    cells = np.nonzero((cnt > 0) & (nin == cnt))[0].astype(np.int64)
+    straddling = np.nonzero((nin > 0) & (nin < cnt))[0].astype(np.int64)
+    take = np.isin(cell_of_term, cells)
+    ptr_l = np.concatenate([[0], np.cumsum(cnt[cells])]).astype(np.int64)
+    return ptr_l, (col[take] - col0).astype(np.int32), w[take].copy(), cells, straddling

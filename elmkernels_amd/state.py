@@ -75,6 +75,8 @@ class ELMState:
         self.scalars = dict(dewmx=0.1, oldfflag=1, dayl=0.0, max_dayl=0.0)
         self.land = dict(ltype=1, ctype=0, vtype=2, urbpoi=0, lakpoi=0)
         self._hist_nlev = {}  # history entry id -> levels of its field
+        self._hist_cells = set()  # ids of gridded history entries (their results are cell-shaped)
+        self.output_ncells = None  # cells of the output grid (set_output_grid)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -335,8 +337,11 @@ class ELMState:
         return n.value
 
     def history_read(self, entry, col0=0, n=None, layout=LAYOUT_COL_MAJOR, nlev=None):
-        """The entry's result as float64: [n] for a one-level field, else [n, nlev] (COL_MAJOR) or [nlev, n] (SOA)."""
-        n = self.ncols - col0 if n is None else int(n)
+        """The entry's result as float64: [n] for a one-level field, else [n, nlev] (COL_MAJOR) or [nlev, n] (SOA).  For a gridded
+        entry (gridded_history_add) col0 and n index cells of the output grid (n defaults to the cells from col0 on)."""
+        if n is None:
+            n = (self.output_ncells if int(entry) in self._hist_cells else self.ncols) - col0
+        n = int(n)
         if nlev is None:
             nlev = self._hist_nlev.get(int(entry), 1)
         shape = (n,) if nlev == 1 else ((n, nlev) if layout == LAYOUT_COL_MAJOR else (nlev, n))
@@ -349,6 +354,7 @@ class ELMState:
         """Drop every entry of every tape and free its device buffers."""
         self._chk(self.lib.elmk_history_clear(self.ctx), "history_clear")
         self._hist_nlev.clear()
+        self._hist_cells.clear()
 
     # -- multi-step runs (include/elmk.h: elmk_run ...) ---------------------------------------------
     def run_reserve(self, forcing_slots, max_steps):
@@ -405,6 +411,45 @@ class ELMState:
             raise ValueError(f"{name}: {a.size} cell values, the grid has {self.grid_ncells}")
         self._chk(self.lib.elmk_upload_gridded(self.ctx, self.fields[name][0], int(level), a.ctypes.data_as(C.c_void_p)),
                   f"upload_gridded({name})")
+
+    # -- output grid (include/elmk.h: elmk_set_output_grid ...) ----------------------------------------
+    def set_output_grid(self, ptr, col, w, fill=np.nan):
+        """The CSR aggregation map by output cell (elmkernels_amd/regrid.py: owner_map, from_sparse_cells): ptr int64 [ncells + 1],
+        col int32 [nnz] (columns), w float64 [nnz]; a cell without terms reads `fill`.  Refused while gridded history entries exist."""
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+        col = np.ascontiguousarray(col, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if ptr.size < 2 or col.size != w.size or ptr[-1] != col.size:
+            raise ValueError("ptr must be [ncells + 1] with ptr[-1] == len(col) == len(w)")
+        self._chk(self.lib.elmk_set_output_grid(self.ctx, ptr.size - 1, ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                                w.ctypes.data_as(C.c_void_p), float(fill)), "set_output_grid")
+        self.output_ncells = ptr.size - 1
+
+    def clear_output_grid(self):
+        """Forget the output map (refused while gridded history entries exist)."""
+        self._chk(self.lib.elmk_clear_output_grid(self.ctx), "clear_output_grid")
+        self.output_ncells = None
+
+    def download_gridded(self, name, level=0):
+        """One level of field `name` aggregated onto the output cells on the device: float64 [ncells]."""
+        if self.output_ncells is None:
+            raise L.ElmkError("download_gridded: no output grid (set_output_grid)")
+        out = np.empty(self.output_ncells, dtype=np.float64)
+        self._chk(self.lib.elmk_download_gridded(self.ctx, self.fields[name][0], int(level), out.ctypes.data_as(C.c_void_p)),
+                  f"download_gridded({name})")
+        return out
+
+    def gridded_history_add(self, tape, name, op):
+        """As history_add, with the accumulators on the output cells: every accumulate folds the aggregate of each level.  Returns
+        the entry id; history_read of it is cell-shaped."""
+        fid = self.fields[name][0] if isinstance(name, str) else int(name)
+        code = HIST_OPS[op] if isinstance(op, str) else int(op)
+        entry = self._chk(self.lib.elmk_gridded_history_add(self.ctx, int(tape), fid, code), f"gridded_history_add({name})")
+        nlev = C.c_int()
+        self.lib.elmk_field_info(fid, C.byref(nlev), None)
+        self._hist_nlev[entry] = nlev.value
+        self._hist_cells.add(entry)
+        return entry
 
     def math_eval(self, fn, x, y=None):
         """elmk_math.h on the device: fn in MATH_FNS; returns fn(x), x / y or pow(x, y)."""

@@ -42,6 +42,8 @@
  *   kokkos_driver.cc:54-85 time loop                                  elmk_run (elmk_run_reserve, elmk_series_upload)
  *   AtmDataManager::data(ntimes, ncells) on the data set's own grid   elmk_set_forcing_grid, elmk_upload_gridded,
  *     (src/data/atm_data.h:168-172; ELM's coupler maps it to land)     elmk_series_upload of cell records
+ *   ELM's c2g: columns averaged onto grid cells by area for history  elmk_set_output_grid, elmk_download_gridded,
+ *     and for the fluxes a coupled run returns to the atmosphere       elmk_gridded_history_add
  *   throw / assert inside physics   (list: SURVEY.md section 5)       per-column flag word, elmk_error_summary
  *
  * Conventions
@@ -351,6 +353,45 @@ int elmk_run_diagnostics(elmk_ctx *ctx, double *min_max_sum, uint32_t *flags_or,
 int elmk_set_forcing_grid(elmk_ctx *ctx, int64_t ncells, int npts, const int32_t *idx /*[npts][ncols]*/, const double *w /*[npts][ncols]*/);
 int elmk_clear_forcing_grid(elmk_ctx *ctx);
 int elmk_upload_gridded(elmk_ctx *ctx, int field, int level, const double *cells /*[ncells]*/);
+
+/* ---- output grid -----------------------------------------------------------------------------
+ * The other direction: columns aggregated onto an output grid on the device (ELM's c2g, area-weighted means of the columns of each
+ * grid cell; the land -> atmosphere map of a coupled run), so a driver downloads ncells values per field level instead of ncols.
+ *   elmk_set_output_grid   the map, CSR by output cell: nnz = ptr[ncells], cell i owns terms ptr[i] .. ptr[i+1]-1, each a column
+ *                          col[p] and a weight w[p] (copied, not retained).  The value of cell i of a source row x (one level of a
+ *                          field, each element widened to fp64 as history widens it) is, in this operation order and without
+ *                          contraction:
+ *                            ptr[i] == ptr[i+1]:  v = fill
+ *                            otherwise:           v = w[p0] * x[col[p0]];  then for p = p0+1 .. p1-1:  v = v + w[p] * x[col[p]]
+ *                          Weights are used as given (normalising them is the map builder's job).  elmkernels_amd/regrid.py:
+ *                          apply_aggregate is this operation on the host; owner_map (area-weighted ownership) and from_sparse_cells
+ *                          (a map file's row / col / S triplets) build maps, slice_output_map one rank's block.
+ *                          ELMK_E_INVALID, nothing enqueued: ncells outside 1 .. 2^31-1, ptr[0] != 0 or ptr decreasing, nnz outside
+ *                          0 .. 2^31-1, a col outside [0, ncols), a non-finite weight, a stream being captured, any gridded history
+ *                          entry existing (elmk_history_clear first).  Replaces an earlier map.
+ *   elmk_clear_output_grid forget the map; ELMK_E_INVALID while gridded history entries exist or the stream is being captured.
+ *   The output grid is independent of the forcing grid and of the run reservation: setting or clearing it releases neither.
+ *   elmk_download_gridded  level `level` of any field (F64 - stored as fp32 in libelmk_f32.so -, I32, U8, U32) aggregated into
+ *                          cells[ncells] on the device; only those doubles are copied back.  Synchronises as elmk_download.
+ *                          ELMK_E_INVALID without a map, for an unknown field, a level out of range, a stream being captured.
+ *   elmk_gridded_history_add  as elmk_history_add (the same entry ids, table and limits, the same refusals, and without an output
+ *                          grid), but the entry's accumulators live on the output cells, nlev x ncells: each elmk_history_accumulate
+ *                          takes g = the aggregate of the current value of each level and folds it, acc = fold(op, acc, g), by the
+ *                          rules of "history" (ELM's order: c2g, then the time fold).  A cell with no terms reads fill under every op.
+ *                          elmk_history_read, _reset, _count and _clear work on gridded entries unchanged; for a gridded entry
+ *                          elmk_history_read's col0, n index cells.  A tape with only gridded entries counts one sample per
+ *                          accumulate.  With gridded entries elmk_history_accumulate stays one launch (the cell rows after the
+ *                          column rows), stream-ordered, host-free and capturable, and elmk_run with ELMK_RUN_HISTORY folds them every
+ *                          step; column entries give the same bits with or without gridded entries beside them.  Without gridded
+ *                          entries nothing changes.
+ *   Device memory (elmk_device_bytes): the map's ptr ((ncells + 1) x 8 bytes), col (nnz x 4) and w (nnz x 8), and each gridded
+ *   entry's accumulators (nlev x ncells rounded up to 64 x 8 bytes), each rounded up to 256 bytes; elmk_clear_output_grid and
+ *   elmk_history_clear return them. */
+int elmk_set_output_grid(elmk_ctx *ctx, int64_t ncells, const int64_t *ptr /*[ncells+1]*/, const int32_t *col /*[nnz]*/,
+                         const double *w /*[nnz]*/, double fill);
+int elmk_clear_output_grid(elmk_ctx *ctx);
+int elmk_download_gridded(elmk_ctx *ctx, int field, int level, double *cells /*[ncells]*/);
+int elmk_gridded_history_add(elmk_ctx *ctx, int tape, int field, int op);
 
 /* ---- the physics wrappers (same names, order and arguments as driver/kokkos) ---------------- */
 int elmk_frac_wet(elmk_ctx *ctx);

@@ -294,6 +294,33 @@ class ELMInterface {
   }
   int64_t grid_ncells() const { return grid_ncells_; }
 
+  /* Output on a grid (elmk_set_output_grid): the CSR map by output cell - cell i averages columns col[ptr[i] .. ptr[i+1]-1] with
+   * weights w (ELM's c2g, elmkernels_amd/regrid.py owner_map) - and fill for a cell without columns.  download_gridded() gives one
+   * level of a field on the cells, [ncells]; gridded_history_add() registers a field on a tape with its accumulators on the cells,
+   * folded by accumulate_history() and by run(..., accumulate_history = true); gridded_history_read() fills [ncells][nlev]. */
+  void set_output_grid(int64_t ncells, const int64_t* ptr, const int32_t* col, const double* w, double fill)
+  {
+    ok(elmk_set_output_grid(ctx_, ncells, ptr, col, w, fill));
+    output_ncells_ = ncells;
+  }
+  void clear_output_grid()
+  {
+    ok(elmk_clear_output_grid(ctx_));
+    output_ncells_ = 0;
+  }
+  void download_gridded(const char* field, int level, double* cells) { ok(elmk_download_gridded(ctx_, id(field), level, cells)); }
+  int gridded_history_add(int tape, const char* field, int op)
+  {
+    const int e = elmk_gridded_history_add(ctx_, tape, id(field), op);
+    ok(e < 0 ? e : ELMK_OK);
+    return e;
+  }
+  void gridded_history_read(int entry, double* host)
+  {
+    ok(elmk_history_read(ctx_, entry, host, 0, output_ncells_, ELMK_LAYOUT_COL_MAJOR));
+  }
+  int64_t output_ncells() const { return output_ncells_; }
+
   /* ELMInterface::copyPrimaryVars / getPrimaryVars (elm_kokkos_interface.cc:324-356) */
   void copyPrimaryVars(PrimaryVars& pv)
   {
@@ -347,6 +374,7 @@ class ELMInterface {
   uint32_t last_flags_{0};
   int max_steps_{0};
   int64_t grid_ncells_{0};
+  int64_t output_ncells_{0};
   std::vector<double> run_conservation_;
 };
 
