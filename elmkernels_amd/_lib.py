@@ -94,6 +94,10 @@ SIGNATURES = {
     "elmk_clear_output_grid": (C.c_int, [_P]),
     "elmk_download_gridded": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "elmk_gridded_history_add": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "elmk_field_class": (C.c_int, [C.c_int]),
+    "elmk_restart_size": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "elmk_restart_save": (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
+    "elmk_restart_load": (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

@@ -169,4 +169,21 @@ void launch_hist_accumulate_cells(const HistRow* rows, int nrows, const HistRow*
 void launch_ogrid_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, const int64_t* ptr, double fill, int64_t cell0,
                            int64_t m, double* out, hipStream_t st);
 
+// restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
+// HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element
+struct RstPiece {
+  void* dev;
+  int64_t img_off;
+  int64_t n;
+  int64_t g0;
+  int32_t lev;
+  int32_t sdtype;
+  int32_t adtype;
+  int32_t snl;  // 1: count elements outside 0..nlevsno (verify)
+};
+// mode 0: rows -> chunk, checksums; 1: checksums and snl range of the chunk; 2: chunk -> rows.  part: [npieces][nbx][2] partials,
+// sums: [npieces][2] (checksum, out-of-range count), modes 0 and 1
+void launch_restart_pieces(int mode, const RstPiece* pieces, int npieces, int nbx, char* chunk, uint64_t* part, uint64_t* sums,
+                           hipStream_t st);
+
 }  // namespace elmk

@@ -1,0 +1,210 @@
+"""Host codec of restart images (include/elmk.h "restart"), in numpy only: read, check, merge and cut the images that
+elmk_restart_save writes, so that a run can restart with another column decomposition.
+
+    img = S.restart_save(gcol0)              # one rank's columns
+    full = restart.merge([img0, img1])       # adjacent column ranges -> one image; checksums add
+    part = restart.slice(full, gcol0, n)     # columns [gcol0, gcol0 + n) for another rank; checksums recomputed
+    restart.write(path, part); restart.read(path)
+
+merge and slice refuse images with gridded history entries: per-rank partial cell accumulators do not survive a change of
+decomposition under MAX and MIN.
+"""
+import numpy as np
+
+MAGIC = b"ELMKRST\0"
+VERSION = 1
+FIELD, HISTORY, GRIDDED = 0, 1, 2  # ELMK_RESTART_*
+ALIGN = 256
+HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), ("schema_hash", "<u8"), ("gcol0", "<i8"),
+                   ("ncols", "<i8"), ("tape_count", "<u8", (4,)), ("nentries", "<u4"), ("nsections", "<u4"),
+                   ("header_bytes", "<u8"), ("total_bytes", "<u8"), ("header_checksum", "<u8")])
+ENTRY = np.dtype([("tape", "<i4"), ("field", "<i4"), ("op", "<i4"), ("gridded", "<i4"), ("ncells", "<i8")])
+SECTION = np.dtype([("kind", "<i4"), ("id", "<i4"), ("nlev", "<i4"), ("dtype", "<i4"), ("extent", "<i8"), ("offset", "<u8"),
+                    ("checksum", "<u8")])
+assert HEADER.itemsize == 104 and ENTRY.itemsize == 24 and SECTION.itemsize == 40
+ELEM = {0: np.dtype("<f8"), 1: np.dtype("<i4"), 2: np.dtype("u1"), 3: np.dtype("<u4")}  # elmk_dtype -> image element
+_CK_OFF = HEADER.fields["header_checksum"][1]
+
+
+class RestartError(ValueError):
+    pass
+
+
+def _align(v):
+    return (v + ALIGN - 1) // ALIGN * ALIGN
+
+
+def fmix64(k):
+    """murmur3's 64-bit finalizer, elementwise on uint64 (wrapping)."""
+    k = np.asarray(k, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        k = k ^ (k >> np.uint64(33))
+        k = k * np.uint64(0xFF51AFD7ED558CCD)
+        k = k ^ (k >> np.uint64(33))
+        k = k * np.uint64(0xC4CEB9FE1A85EC53)
+        k = k ^ (k >> np.uint64(33))
+    return k
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    if a.dtype.itemsize == 8:
+        return a.view(np.uint64)
+    if a.dtype.itemsize == 4:
+        return a.view(np.uint32).astype(np.uint64)
+    return a.astype(np.uint64)
+
+
+def checksum(data, g0=0):
+    """Checksum of a section [nlev, extent]: sum mod 2^64 of fmix64(bits ^ fmix64(g * 64 + lev + 1)), g = g0 + element index."""
+    data = np.asarray(data)
+    if data.ndim == 1:
+        data = data[None, :]
+    nlev, ext = data.shape
+    pos = (np.uint64(g0) + np.arange(ext, dtype=np.uint64))[None, :] * np.uint64(64) + np.arange(nlev, dtype=np.uint64)[:, None] + np.uint64(1)
+    return int(np.sum(fmix64(_bits(data) ^ fmix64(pos)), dtype=np.uint64))
+
+
+def header_checksum(img, header_bytes):
+    w = np.frombuffer(bytes(img[:header_bytes]), dtype="<u8").copy()
+    w[_CK_OFF // 8] = 0
+    return int(np.sum(fmix64(w ^ fmix64(np.arange(w.size, dtype=np.uint64) * np.uint64(64) + np.uint64(1))), dtype=np.uint64))
+
+
+def parse(image):
+    """-> dict(header=, entries=, sections=, data=[nlev, extent] array per section).  Checks the structure, not the checksums."""
+    img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+    if img.size < HEADER.itemsize:
+        raise RestartError("truncated image")
+    h = np.frombuffer(img[:HEADER.itemsize].tobytes(), HEADER)[0]
+    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) != VERSION:
+        raise RestartError("not a restart image of this format version")
+    hb, tb, ne, ns = int(h["header_bytes"]), int(h["total_bytes"]), int(h["nentries"]), int(h["nsections"])
+    if hb > img.size or tb > img.size or hb < HEADER.itemsize + ne * ENTRY.itemsize + ns * SECTION.itemsize:
+        raise RestartError("truncated image")
+    o = HEADER.itemsize
+    ent = np.frombuffer(img[o:o + ne * ENTRY.itemsize].tobytes(), ENTRY).copy()
+    o += ne * ENTRY.itemsize
+    sec = np.frombuffer(img[o:o + ns * SECTION.itemsize].tobytes(), SECTION).copy()
+    data = []
+    for s in sec:
+        dt = ELEM[int(s["dtype"])]
+        n = int(s["nlev"]) * int(s["extent"])
+        off = int(s["offset"])
+        if off + n * dt.itemsize > tb:
+            raise RestartError("truncated image")
+        data.append(np.frombuffer(img[off:off + n * dt.itemsize].tobytes(), dt).reshape(int(s["nlev"]), int(s["extent"])))
+    return dict(header=h, entries=ent, sections=sec, data=data)
+
+
+def verify(image):
+    """parse() and check the header checksum and every section checksum; raises RestartError."""
+    img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+    p = parse(img)
+    h = p["header"]
+    if header_checksum(img, int(h["header_bytes"])) != int(h["header_checksum"]):
+        raise RestartError("header checksum mismatch")
+    for s, d in zip(p["sections"], p["data"]):
+        g0 = 0 if int(s["kind"]) == GRIDDED else int(h["gcol0"])
+        if checksum(d, g0) != int(s["checksum"]):
+            raise RestartError(f"section checksum mismatch (kind {int(s['kind'])}, id {int(s['id'])})")
+    return p
+
+
+def build(header, entries, sections, data):
+    """An image from its parts: offsets, header_bytes, total_bytes and the header checksum are computed; section checksums are
+    taken from sections['checksum']."""
+    h = np.array(header, HEADER).reshape(())
+    ent = np.asarray(entries, ENTRY)
+    sec = np.array(sections, SECTION)
+    hb = _align(HEADER.itemsize + ent.size * ENTRY.itemsize + sec.size * SECTION.itemsize)
+    off = hb
+    for i, d in enumerate(data):
+        sec[i]["offset"] = off
+        off = _align(off + d.nbytes)
+    h["nentries"], h["nsections"], h["header_bytes"], h["total_bytes"], h["header_checksum"] = ent.size, sec.size, hb, off, 0
+    img = np.zeros(off, np.uint8)
+    img[:HEADER.itemsize] = np.frombuffer(h.tobytes(), np.uint8)
+    o = HEADER.itemsize
+    img[o:o + ent.nbytes] = np.frombuffer(ent.tobytes(), np.uint8)
+    o += ent.nbytes
+    img[o:o + sec.nbytes] = np.frombuffer(sec.tobytes(), np.uint8)
+    for s, d in zip(sec, data):
+        b = np.frombuffer(np.ascontiguousarray(d, ELEM[int(s["dtype"])]).tobytes(), np.uint8)
+        img[int(s["offset"]):int(s["offset"]) + b.size] = b
+    img[_CK_OFF:_CK_OFF + 8] = np.frombuffer(np.uint64(header_checksum(img, hb)).tobytes(), np.uint8)
+    return img
+
+
+def _no_gridded(p, what):
+    if np.any(p["entries"]["gridded"] != 0):
+        raise RestartError(f"{what}: the image holds gridded history entries, which do not survive a change of decomposition")
+
+
+def merge(images):
+    """Images of adjacent column ranges (any order) -> one image of their union.  Section checksums add."""
+    ps = sorted((verify(i) for i in images), key=lambda p: int(p["header"]["gcol0"]))
+    if not ps:
+        raise RestartError("merge: no images")
+    first = ps[0]
+    for p in ps:
+        _no_gridded(p, "merge")
+    end = int(first["header"]["gcol0"])
+    for p in ps:
+        h = p["header"]
+        if int(h["gcol0"]) != end:
+            raise RestartError("merge: the column ranges are not adjacent")
+        end += int(h["ncols"])
+        for k in ("schema_hash", "real_bytes", "nentries", "nsections"):
+            if h[k] != first["header"][k]:
+                raise RestartError(f"merge: the images differ in {k}")
+        if not np.array_equal(h["tape_count"], first["header"]["tape_count"]) or p["entries"].tobytes() != first["entries"].tobytes():
+            raise RestartError("merge: the images hold different history tapes")
+        a, b = p["sections"], first["sections"]
+        if not all(np.array_equal(a[k], b[k]) for k in ("kind", "id", "nlev", "dtype")):
+            raise RestartError("merge: the images hold different sections")
+    h = first["header"].copy()
+    h["ncols"] = end - int(first["header"]["gcol0"])
+    sec = first["sections"].copy()
+    data = []
+    for i in range(sec.size):
+        data.append(np.concatenate([p["data"][i] for p in ps], axis=1))
+        sec[i]["extent"] = h["ncols"]
+        sec[i]["checksum"] = int(np.sum(np.array([int(p["sections"][i]["checksum"]) for p in ps], np.uint64), dtype=np.uint64))
+    return build(h, first["entries"], sec, data)
+
+
+def slice(image, gcol0, n):  # noqa: A001 - the name of the operation
+    """Global columns [gcol0, gcol0 + n) of an image, as an image of its own; checksums recomputed."""
+    p = verify(image)
+    _no_gridded(p, "slice")
+    h = p["header"].copy()
+    lo = int(gcol0) - int(h["gcol0"])
+    if lo < 0 or n < 0 or lo + n > int(h["ncols"]):
+        raise RestartError("slice: the columns are outside the image")
+    h["gcol0"], h["ncols"] = gcol0, n
+    sec = p["sections"].copy()
+    data = []
+    for i in range(sec.size):
+        d = np.ascontiguousarray(p["data"][i][:, lo:lo + n])
+        data.append(d)
+        sec[i]["extent"] = n
+        sec[i]["checksum"] = checksum(d, gcol0)
+    return build(h, p["entries"], sec, data)
+
+
+def write(path, image):
+    np.ascontiguousarray(image, dtype=np.uint8).tofile(path)
+
+
+def read(path):
+    """The image in a file, verified."""
+    img = np.fromfile(path, dtype=np.uint8)
+    verify(img)
+    return img
+
+
+def field_sections(image):
+    """{field id: [nlev, ncols] array} of an image's field sections."""
+    p = parse(image)
+    return {int(s["id"]): d for s, d in zip(p["sections"], p["data"]) if int(s["kind"]) == FIELD}

@@ -21,6 +21,8 @@ OPT_CF_HALF_WORKGROUPS = 1  # elmk_set_option
 HIST_AVG, HIST_SUM, HIST_MAX, HIST_MIN, HIST_INST = range(5)  # elmk_history_add
 HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, "inst": HIST_INST}
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
+CLASS_PROGNOSTIC, CLASS_SURFACE, CLASS_FORCING, CLASS_DIAGNOSTIC = range(4)  # elmk_field_class
+CLASS_NAMES = ("prognostic", "surface", "forcing", "diagnostic")
 RUN_QBOT_IS_RH, RUN_HISTORY = 1, 2  # elmk_run flags
 # elmk_run_step of include/elmk.h, field for field (natural C alignment: tests/test_run_host.py checks it against gcc)
 RUN_STEP_DTYPE = np.dtype([("decday", np.float64), ("doy", np.int32), ("forc_slot", np.int32), ("forc_wt1", np.float64, (8,)),
@@ -45,6 +47,16 @@ def field_table():
         lib.elmk_field_info(i, C.byref(nlev), C.byref(dt))
         out[lib.elmk_field_name(i).decode()] = (i, nlev.value, DTYPES[dt.value])
     return out
+
+
+def field_class(name, lib_path=None):
+    """Restart class of a field (name or id), from the library's table."""
+    lib = L.load(lib_path)
+    fid = lib.elmk_field_id(name.encode()) if isinstance(name, str) else int(name)
+    c = lib.elmk_field_class(fid)
+    if c < 0:
+        raise KeyError(name)
+    return c
 
 
 def pack_pft(pft):
@@ -451,6 +463,28 @@ class ELMState:
         self._hist_cells.add(entry)
         return entry
 
+    # -- restart images (include/elmk.h "restart"; elmkernels_amd/restart.py reads and rewrites them on the host) -------------
+    def field_class(self, name):
+        """CLASS_PROGNOSTIC, CLASS_SURFACE, CLASS_FORCING or CLASS_DIAGNOSTIC (include/elmk_restart.def)."""
+        return field_class(name)
+
+    def restart_size(self):
+        n = C.c_int64()
+        self._chk(self.lib.elmk_restart_size(self.ctx, C.byref(n)), "restart_size")
+        return n.value
+
+    def restart_save(self, gcol0=0):
+        """The image of this context's columns, global columns [gcol0, gcol0 + ncols): np.ndarray of uint8."""
+        img = np.empty(self.restart_size(), np.uint8)
+        self._chk(self.lib.elmk_restart_save(self.ctx, int(gcol0), img.ctypes.data, img.size), "restart_save")
+        return img
+
+    def restart_load(self, image, gcol0=0):
+        """Verify the whole image, then load its fields, history accumulators and tape counts; the history entries must have been
+        registered as when it was saved."""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        self._chk(self.lib.elmk_restart_load(self.ctx, int(gcol0), img.ctypes.data, img.size), "restart_load")
+
     def math_eval(self, fn, x, y=None):
         """elmk_math.h on the device: fn in MATH_FNS; returns fn(x), x / y or pow(x, y)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -675,6 +709,20 @@ class ELMInterface:
     def accumulate_history(self):
         """Fold this step's state into the history tapes registered on self.S (ELMState.history_add): call after advance()."""
         self.S.history_accumulate()
+
+    def restart_save(self, gcol0=0):
+        """The restart image of the columns (ELMState.restart_save)."""
+        return self.S.restart_save(gcol0)
+
+    def restart_load(self, image, gcol0=0):
+        """After setup(), the geography and maps and the same history entries: load an image instead of initialize()."""
+        self.S.restart_load(image, gcol0)
+
+    def restart_size(self):
+        return self.S.restart_size()
+
+    def field_class(self, name):
+        return self.S.field_class(name)
 
     def getPrimaryVars(self):
         """ELMInterface::getPrimaryVars / copyPrimaryVars (:324-356): the PrimaryVars members as host arrays."""

@@ -393,6 +393,76 @@ int elmk_clear_output_grid(elmk_ctx *ctx);
 int elmk_download_gridded(elmk_ctx *ctx, int field, int level, double *cells /*[ncells]*/);
 int elmk_gridded_history_add(elmk_ctx *ctx, int tape, int field, int op);
 
+/* ---- restart ---------------------------------------------------------------------------------
+ * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state
+ * and history into a self-describing byte buffer, the image, and another context - in another process, or with another column
+ * decomposition through elmkernels_amd/restart.py - loads it.  Continuing from the load gives the bits of the run that never stopped.
+ *
+ * Which fields an image holds comes from one table, include/elmk_restart.def, read through elmk_field_class.  Classes are relative to
+ * one model step (the per-step sequence of elmk_run): PROGNOSTIC - some element may be read before the step writes it, or survive the
+ * step unwritten (err_flags included: its bits are sticky); SURFACE - read and never written by the step (soil hydraulics, geometry,
+ * what elmk_initialize_state derives, land and plant-type indices); FORCING - the series fields atm_tbot .. atm_wind and mlai .. mhbot,
+ * which the driver supplies every step; DIAGNOSTIC - every element is overwritten by the step before any read.  The image holds the
+ * PROGNOSTIC and SURFACE fields.
+ *
+ * Image format, version 1.  Little-endian; all offsets from the start of the image.
+ *   elmk_restart_header at 0, then nentries elmk_restart_entry (the history entries in registration order), then nsections
+ *   elmk_restart_section; zero padding up to header_bytes (a multiple of 256).  Then the sections, in table order, each at a
+ *   256-byte aligned offset, dense [nlev][extent] in its element type, zero padding up to the next multiple of 256:
+ *     ELMK_RESTART_FIELD    id = field id, extent = ncols, the field's ABI element type: F64 fields as doubles in both builds
+ *                           (libelmk_f32.so widens its fp32 values exactly as elmk_download does); one per PROGNOSTIC or
+ *                           SURFACE field, in field id order
+ *     ELMK_RESTART_HISTORY  id = entry index, extent = ncols, F64: the raw accumulators (not acc / count)
+ *     ELMK_RESTART_GRIDDED  id = entry index, extent = ncells of the output grid, F64: the cell accumulators
+ *   Checksum of a section: the sum modulo 2^64 of term = fmix64(bits ^ fmix64(g * 64 + lev + 1)) over its elements, fmix64 the
+ *   murmur3 finalizer, bits the element zero-extended to 64 bits, g the global column (gcol0 + column; the cell for GRIDDED), lev
+ *   its level.  A sum, so it is the same in any reduction order, and images of adjacent column ranges merge by adding checksums.
+ *   Checksum of the header: the same sum over the 8-byte words w_i of [0, header_bytes), header_checksum read as 0, with g = i,
+ *   lev = 0.  schema_hash: FNV-1a 64 over, for every field in id order, its name, a 0 byte, its dtype byte and its nlev byte.
+ *
+ * elmk_restart_size: bytes of this context's image.  elmk_restart_save: the image of the context's columns, which are global
+ * columns [gcol0, gcol0 + ncols) of the run.  elmk_restart_load: verifies the whole image on the device (every checksum, snl in
+ * 0..nlevsno, as elmk_upload) before it writes anything, then writes the fields, the accumulators and the tape counts; a tape with
+ * count > 0 counts as accumulated (elmk_history_add refuses it until its reset).  Both synchronise with the context's stream and
+ * any elmk_run in flight; staging memory is allocated for the call and freed before it returns.  ELMK_E_INVALID, with state,
+ * history and counts untouched and the context usable, for: a stream being captured, a too small or truncated buffer, a bad magic
+ * or version, another schema, another ncols or gcol0, a history entry table other than the context's (same entries, same order,
+ * gridded entries with the same ncells), any checksum mismatch, snl out of range.
+ *
+ * The image holds column data and history only.  Parameters, SNICAR and snow-age tables, geography, forcing and output maps, run
+ * reservations and series, options and graphs stay with the driver, which sets them up as at start-up.  Restart order: create,
+ * parameters and tables, geography and maps, history entries, elmk_restart_load, then the current forcing records or run series.
+ * Graphs captured before a load stay valid (the arena and the history table do not move). */
+enum { ELMK_CLASS_PROGNOSTIC = 0, ELMK_CLASS_SURFACE = 1, ELMK_CLASS_FORCING = 2, ELMK_CLASS_DIAGNOSTIC = 3 };
+enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2 };
+#define ELMK_RESTART_MAGIC "ELMKRST\0"
+#define ELMK_RESTART_VERSION 1u
+typedef struct {
+  char magic[8];              /* ELMK_RESTART_MAGIC */
+  uint32_t version;           /* ELMK_RESTART_VERSION */
+  uint32_t real_bytes;        /* elmk_state_real_bytes of the build that saved it */
+  uint64_t schema_hash;
+  int64_t gcol0, ncols;       /* global columns [gcol0, gcol0 + ncols) */
+  uint64_t tape_count[4];     /* samples of each tape (ELMK_HIST_MAX_TAPES) */
+  uint32_t nentries, nsections;
+  uint64_t header_bytes;      /* offset of the first section */
+  uint64_t total_bytes;       /* = elmk_restart_size */
+  uint64_t header_checksum;
+} elmk_restart_header;        /* 104 bytes */
+typedef struct {
+  int32_t tape, field, op, gridded; /* gridded: 1 for elmk_gridded_history_add */
+  int64_t ncells;                   /* the output grid's cells for a gridded entry, else 0 */
+} elmk_restart_entry;               /* 24 bytes */
+typedef struct {
+  int32_t kind, id, nlev, dtype;    /* ELMK_RESTART_*, field id or entry index, levels, elmk_dtype */
+  int64_t extent;                   /* elements per level */
+  uint64_t offset, checksum;
+} elmk_restart_section;             /* 40 bytes */
+int elmk_field_class(int field);
+int elmk_restart_size(elmk_ctx *ctx, int64_t *bytes);
+int elmk_restart_save(elmk_ctx *ctx, int64_t gcol0, void *image, int64_t bytes);
+int elmk_restart_load(elmk_ctx *ctx, int64_t gcol0, const void *image, int64_t bytes);
+
 /* ---- the physics wrappers (same names, order and arguments as driver/kokkos) ---------------- */
 int elmk_frac_wet(elmk_ctx *ctx);
 int elmk_albedo_snicar(elmk_ctx *ctx);

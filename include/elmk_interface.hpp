@@ -229,6 +229,22 @@ class ELMInterface {
   void history_read(int entry, double* host) { ok(elmk_history_read(ctx_, entry, host, 0, ncols_, ELMK_LAYOUT_COL_MAJOR)); }
   void history_clear() { ok(elmk_history_clear(ctx_)); }
 
+  /* Restart images (elmk.h "restart"): saveRestart() returns the image of the columns, global columns [gcol0, gcol0 + ncols);
+   * loadRestart() takes one after setup, geography, maps and the same history entries, in place of initialize().  Both throw on a
+   * refusal; the state is then untouched. */
+  std::vector<unsigned char> saveRestart(int64_t gcol0 = 0)
+  {
+    int64_t bytes = 0;
+    ok(elmk_restart_size(ctx_, &bytes));
+    std::vector<unsigned char> image((size_t)bytes);
+    ok(elmk_restart_save(ctx_, gcol0, image.data(), bytes));
+    return image;
+  }
+  void loadRestart(const std::vector<unsigned char>& image, int64_t gcol0 = 0)
+  {
+    ok(elmk_restart_load(ctx_, gcol0, image.data(), (int64_t)image.size()));
+  }
+
   /* Multi-step runs (elmk_run): the driver's time loop on the device.  reserve_run() once; the forcing records (atm_* fields, slots
    * 0 .. forcing_slots-1) and the 12 months of mlai .. mhbot go up as series, host[nslots][ncols], record-major; run() then does
    * advance() (the overload with solar geometry) for every row of the schedule, with no host round trip between steps, and throws if

@@ -1,0 +1,309 @@
+"""Exact restarts on the device (include/elmk.h "restart"): E3SM's ERS test - 2N steps against N steps, a save, a fresh context
+whose every field outside the image is poisoned, a load and N more steps - bit for bit in every field, every history result,
+the tape counts and the error summary; a change of column decomposition through restart.merge / restart.slice; the image's
+contents against elmk_download; and every refusal of elmk_restart_load, each leaving the context as it was."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from elmkernels_amd import _lib as L
+from elmkernels_amd import restart as R
+from elmkernels_amd import state as st
+from tests.test_gpu_history import _hip_runtime
+from tests.test_gpu_run import DT, NREC, NSTEPS, _device, _inputs, same, schedule, stepwise, upload_series
+
+pytestmark = pytest.mark.gpu
+
+N = NSTEPS // 2
+IMAGE_CLASSES = (st.CLASS_PROGNOSTIC, st.CLASS_SURFACE)
+
+
+@pytest.fixture(scope="module")
+def base():
+    return _inputs(3001, 97)
+
+
+def _sub(base, c0, n):
+    cols, scal, soil, lat, lon, rec = base
+    return ({k: v[c0:c0 + n] for k, v in cols.items()}, scal, soil, lat[c0:c0 + n], lon[c0:c0 + n],
+            {k: v[:, c0:c0 + n] for k, v in rec.items()})
+
+
+def _poison(D):
+    """Every field the image does not hold: NaN, or an out-of-the-way integer."""
+    for name, (fid, nlev, dt) in D.fields.items():
+        if st.field_class(name) not in IMAGE_CLASSES:
+            D.fill(name, np.nan if dt == np.float64 else 3.0)
+
+
+def _output_map(n, per=7):
+    cells = np.arange(n) // per
+    ncells = int(cells[-1]) + 1
+    ptr = np.searchsorted(cells, np.arange(ncells + 1)).astype(np.int64)
+    w = 1.0 + 0.01 * (np.arange(n) % 5)
+    return ptr, np.arange(n, dtype=np.int32), w
+
+
+def _history(D, gridded=True):
+    """Entries on two tapes with every op (and gridded ones); returns their ids."""
+    ids = [D.history_add(0, "t_grnd", "avg"), D.history_add(0, "t_soisno", "max"), D.history_add(0, "h2osno", "min"),
+           D.history_add(0, "eflx_sh_tot", "sum"), D.history_add(1, "snl", "inst"), D.history_add(1, "h2osoi_liq", "avg")]
+    if gridded:
+        D.set_output_grid(*_output_map(D.ncols))
+        ids += [D.gridded_history_add(1, "t_grnd", "avg"), D.gridded_history_add(1, "eflx_lh_tot", "max")]
+    return ids
+
+
+def _snapshot(D, ids):
+    out = {k: D[k] for k in D.fields}
+    out["hist"] = [D.history_read(e) if D.history_count(0 if e < 4 else 1) > 0 else None for e in ids]
+    out["counts"] = [D.history_count(t) for t in range(st.HIST_MAX_TAPES)]
+    out["errors"] = D.error_summary()
+    return out
+
+
+def _assert_same(a, b, skip=()):
+    for k in a:
+        if k in skip:
+            continue
+        if k == "hist":
+            for x, y in zip(a[k], b[k]):
+                assert (x is None and y is None) or same(x, y), "history"
+        elif k in ("counts", "errors"):
+            assert a[k] == b[k], k
+        else:
+            assert same(a[k], b[k]), k
+
+
+def _fresh(base, gridded=True, graph=False, lib_path=None):
+    D = _device(*base[:5], lib_path=lib_path)
+    D.set_graph(graph)
+    ids = _history(D, gridded)
+    _poison(D)
+    return D, ids
+
+
+@pytest.mark.parametrize("lib_path", [None, L.F32_LIB_PATH], ids=["f64", "f32"])
+def test_ers_stepwise(base, lib_path):
+    """ERS through the stepwise calls, history with every op on two tapes and gridded entries."""
+    rec = base[5]
+    sch = schedule()
+    A = _device(*base[:5], lib_path=lib_path)
+    ids = _history(A)
+    stepwise(A, rec, sch, history=True)
+    B = _device(*base[:5], lib_path=lib_path)
+    _history(B)
+    stepwise(B, rec, sch[:N], history=True)
+    img = B.restart_save()
+    B.close()
+    R.verify(img)
+    Cx, ids_c = _fresh(base, lib_path=lib_path)
+    Cx.restart_load(img)
+    assert [Cx.history_count(t) for t in range(4)] == [N, N, 0, 0]
+    stepwise(Cx, rec, sch[N:], history=True)
+    # the series inputs hold the last step's records in both
+    _assert_same(_snapshot(A, ids), _snapshot(Cx, ids_c))
+    A.close()
+    Cx.close()
+
+
+def test_ers_run_with_graph(base):
+    """ERS through elmk_run with graphs on: N steps in one run, save, a fresh poisoned context, load, the other N in one run."""
+    rec = base[5]
+    sch = schedule()
+    A = _device(*base[:5])
+    A.set_graph(True)
+    ids = _history(A)
+    A.run_reserve(NREC, NSTEPS)
+    upload_series(A, rec)
+    A.run(DT, sch, st.RUN_HISTORY)
+    B = _device(*base[:5])
+    B.set_graph(True)
+    _history(B)
+    B.run_reserve(NREC, NSTEPS)
+    upload_series(B, rec)
+    B.run(DT, sch[:N], st.RUN_HISTORY)
+    img = B.restart_save()
+    B.close()
+    Cx, ids_c = _fresh(base, graph=True)
+    Cx.run_reserve(NREC, NSTEPS)
+    Cx.restart_load(img)
+    upload_series(Cx, rec)
+    Cx.run(DT, sch[N:], st.RUN_HISTORY)
+    _assert_same(_snapshot(A, ids), _snapshot(Cx, ids_c), skip=st.SERIES_FORCING + st.SERIES_PHENOLOGY)
+    A.close()
+    Cx.close()
+
+
+def test_decomposition_change(base):
+    """Two halves save with their gcol0; merged, then cut into three uneven blocks, each loaded and continued: the one-context
+    run, column for column (fields and column history)."""
+    n = base[0]["snl"].shape[0]
+    rec = base[5]
+    sch = schedule()
+    A = _device(*base[:5])
+    ids = _history(A, gridded=False)
+    stepwise(A, rec, sch, history=True)
+    want = _snapshot(A, ids)
+    A.close()
+    halves = [(0, 1400), (1400, n - 1400)]
+    imgs = []
+    for c0, m in halves:
+        H = _device(*_sub(base, c0, m)[:5])
+        _history(H, gridded=False)
+        stepwise(H, _sub(base, c0, m)[5], sch[:N], history=True)
+        imgs.append(H.restart_save(c0))
+        H.close()
+    full = R.merge(imgs[::-1])
+    for c0, m in [(0, 517), (517, 1999), (2516, n - 2516)]:
+        part = R.slice(full, c0, m)
+        sub = _sub(base, c0, m)
+        D, ids_d = _fresh(sub, gridded=False)
+        D.restart_load(part, c0)
+        stepwise(D, sub[5], sch[N:], history=True)
+        got = _snapshot(D, ids_d)
+        for k in D.fields:
+            assert same(got[k], want[k][c0:c0 + m]), k
+        for x, y in zip(got["hist"], want["hist"]):
+            assert same(x, y[c0:c0 + m])
+        assert got["counts"] == want["counts"]
+        D.close()
+
+
+def test_image_contents(base):
+    """Field sections equal elmk_download bit for bit; the device's checksums equal restart.py's; the image holds exactly the
+    PROGNOSTIC and SURFACE fields."""
+    D = _device(*base[:5])
+    stepwise(D, base[5], schedule()[:2])
+    img = D.restart_save(gcol0=12345)
+    assert img.size == D.restart_size()
+    R.verify(img)
+    secs = R.field_sections(img)
+    want = {fid for name, (fid, _, _) in D.fields.items() if st.field_class(name) in IMAGE_CLASSES}
+    assert set(secs) == want
+    for name, (fid, nlev, dt) in D.fields.items():
+        if fid in secs:
+            got = secs[fid]
+            ref = D[name].reshape(D.ncols, nlev).T
+            assert same(got, np.ascontiguousarray(ref, dtype=got.dtype)), name
+    D.close()
+
+
+def test_refusals_leave_the_context_as_it_was(base):
+    rec = base[5]
+    sch = schedule()
+    B = _device(*base[:5])
+    _history(B)
+    stepwise(B, rec, sch[:N], history=True)
+    img = B.restart_save()
+    B.close()
+    D, ids = _fresh(base)
+    D.restart_load(img)
+    before = _snapshot(D, ids)
+    p = R.parse(img)
+    snl_id = D.fields["snl"][0]
+    snl_sec = [s for s in p["sections"] if int(s["kind"]) == R.FIELD and int(s["id"]) == snl_id][0]
+
+    bad = {}
+    b = img.copy()
+    b[int(p["sections"][3]["offset"]) + 17] ^= 0x10
+    bad["data byte"] = (b, 0)
+    bad["truncated"] = (img[:img.size - 300].copy(), 0)
+    bad["gcol0"] = (img, 5)
+    h = p["header"].copy()
+    h["schema_hash"] ^= 1
+    bad["schema"] = (R.build(h, p["entries"], p["sections"], p["data"]), 0)
+    bad["magic"] = (np.concatenate([np.frombuffer(b"XXXXXXXX", np.uint8), img[8:]]), 0)
+    data = [d.copy() for d in p["data"]]
+    sec = p["sections"].copy()
+    i = list(p["sections"]["offset"]).index(snl_sec["offset"])
+    data[i][0, 10] = 6
+    sec[i]["checksum"] = R.checksum(data[i], 0)
+    bad["snl range"] = (R.build(p["header"], p["entries"], sec, data), 0)
+    for what, (b, g0) in bad.items():
+        with pytest.raises(L.ElmkError):
+            D.restart_load(b, g0)
+        _assert_same(before, _snapshot(D, ids))
+    # another ncols
+    E = _device(*_sub(base, 0, 2000)[:5])
+    _history(E)
+    with pytest.raises(L.ElmkError):
+        E.restart_load(img)
+    E.close()
+    # another history table
+    E = _device(*base[:5])
+    E.history_add(0, "t_grnd", "avg")
+    with pytest.raises(L.ElmkError):
+        E.restart_load(img)
+    E.close()
+    # a load while the stream is being captured
+    hip = _hip_runtime()
+    s, graph = C.c_void_p(), C.c_void_p()
+    assert hip.hipStreamCreateWithFlags(C.byref(s), 1) == 0
+    D.set_stream(s.value)
+    assert hip.hipStreamBeginCapture(s, 1) == 0
+    rc = D.lib.elmk_restart_load(D.ctx, 0, img.ctypes.data, img.size)
+    assert hip.hipStreamEndCapture(s, C.byref(graph)) == 0
+    assert rc == -1
+    hip.hipGraphDestroy(graph)
+    D.set_stream(None)
+    hip.hipStreamDestroy(s)
+    _assert_same(before, _snapshot(D, ids))
+    # the context still gives the bits of a clean one
+    Cx, ids_c = _fresh(base)
+    Cx.restart_load(img)
+    stepwise(D, rec, sch[N:N + 1], history=True)
+    stepwise(Cx, rec, sch[N:N + 1], history=True)
+    _assert_same(_snapshot(D, ids), _snapshot(Cx, ids_c))
+    D.close()
+    Cx.close()
+
+
+def test_restart_demo(tmp_path):
+    """examples/restart_demo.cc builds, restarts half way through 48 steps and prints bit-identical."""
+    import os
+    import shutil
+    import struct
+    import subprocess
+
+    from tests import helpers as H
+    from tests.test_gpu_run import ROOT, SERIES
+
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    n = 3008
+    cols, scal, soil, lat, lon, rec = _inputs(n, 74, nrec=25)
+    libdir = os.path.dirname(L.LIB_PATH)
+    exe = str(tmp_path / "restart_demo")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "restart_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
+    S = H.oracle_state(cols, scal, soil)
+    blob = [struct.pack("<q", n)]
+
+    def put(name, kind, arr):
+        a = np.ascontiguousarray(arr)
+        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
+
+    for k, v in S.fields.items():
+        if k != "err_flags":
+            put(k, 0, v)
+    sc = S.scalars
+    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
+    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
+    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
+        put(k, 1, getattr(S, k))
+    for i, name in enumerate(L.SNICAR_NAMES):
+        put(f"snicar/{i}", 1, S.snicar[name])
+    for i, k in enumerate(("age_tau", "age_kappa", "age_drdt0")):
+        put(k, 1, S.snowage[i])
+    put("lat", 1, lat)
+    put("lon", 1, lon)
+    for k in SERIES:
+        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
+    put("steps", 1, schedule(48))
+    (tmp_path / "state.bin").write_bytes(b"".join(blob))
+    r = subprocess.run([exe, str(tmp_path / "state.bin"), str(tmp_path / "restart.img")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "bit-identical" in r.stdout
+    R.verify(R.read(tmp_path / "restart.img"))
