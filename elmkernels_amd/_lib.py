@@ -90,6 +90,10 @@ SIGNATURES = {
     "elmk_set_forcing_grid": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "elmk_clear_forcing_grid": (C.c_int, [_P]),
     "elmk_upload_gridded": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "elmk_set_shortwave_mode": (C.c_int, [_P, C.c_int, C.c_double]),
+    "elmk_set_forcing_record_time": (C.c_int, [_P, C.c_double]),
+    "elmk_series_record_times": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "elmk_download_forcing_cosz": (C.c_int, [_P, _P]),
     "elmk_set_output_grid": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_double]),
     "elmk_clear_output_grid": (C.c_int, [_P]),
     "elmk_download_gridded": (C.c_int, [_P, C.c_int, C.c_int, _P]),

@@ -213,6 +213,11 @@ struct elmk_ctx {
     uint64_t count = 0;  // runs enqueued since the reserve
     int last_buf = -1, last_nsteps = 0;
     int flags = 0;  // of the run being enqueued (the run step's stages)
+    // shortwave COSZEN mode (elmk_series_record_times): the record-time scalars of every forcing slot (elmk_solar_step_consts at
+    // forc_dt and the slot's record start), allocated by the first call after a reservation, and which slots have one
+    DevBuf<elmk_solar_step> rec;
+    size_t rec_bytes = 0;
+    std::vector<char> rec_set;
   } run;
   hipStream_t upload = nullptr;  // of elmk_series_upload, with run_done created by the first elmk_run_reserve
   hipEvent_t run_done[2] = {};
@@ -238,6 +243,17 @@ struct elmk_ctx {
     int32_t* col = nullptr;
     double* w = nullptr;
   } ogrid;
+  // shortwave (elmk_set_shortwave_mode): the mode, the forcing records' interval, and in COSZEN mode czf - every column's mean
+  // cos(zenith) over the current forcing record's interval ([ld] doubles, allocated when the context first enters COSZEN mode).
+  // step_time: elmk_set_forcing_record_time has written czf for elmk_get_forcing (an elmk_run overwrites it); czf_ready: czf holds the
+  // values of the last record time or run step (elmk_download_forcing_cosz)
+  struct Shortwave {
+    int mode = ELMK_SW_REFERENCE;
+    double forc_dt = 0.0;
+    DevBuf<double> czf;
+    size_t czf_bytes = 0;
+    bool step_time = false, czf_ready = false;
+  } sw;
   std::string err;
 };
 
@@ -521,7 +537,7 @@ int64_t elmk_level_stride(const elmk_ctx* ctx) { return ctx ? ctx->ld : -1; }
 int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
   return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
-                         ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes)
+                         ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes + ctx->sw.czf_bytes + ctx->run.rec_bytes)
              : -1;
 }
 
@@ -805,10 +821,16 @@ int elmk_download_day_length(elmk_ctx* ctx, double* dayl, double* max_dayl)
   return ELMK_OK;
 }
 
+namespace {
+int sw_reset(elmk_ctx* ctx, int mode, double forc_dt);
+}
+
 int elmk_clear_column_geography(elmk_ctx* ctx)
 {
   if (int rc = enter(ctx)) return rc;
   if (int rc = set_col_dayl(ctx, false)) return rc;
+  if (ctx->sw.mode != ELMK_SW_REFERENCE)  // COSZEN needs the geography
+    if (int rc = sw_reset(ctx, ELMK_SW_REFERENCE, 0.0)) return rc;
   if (ctx->geo) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const hipError_t e = ctx->geo.reset();
@@ -1381,7 +1403,10 @@ int elmk_get_forcing(elmk_ctx* ctx, const double* wt1, const double* wt2, int qb
 {
   if (int rc = enter_physics(ctx)) return rc;
   if (!wt1 || !wt2) return invalid(ctx, "elmk_get_forcing: null weights");
-  launch_get_forcing(ctx->d, ctx->ncols, wt1, wt2, qbot_is_rh != 0, ctx->stream);
+  const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
+  if (cz && !ctx->sw.step_time)
+    return invalid(ctx, "elmk_get_forcing: shortwave COSZEN mode needs the record's time (elmk_set_forcing_record_time)");
+  launch_get_forcing(ctx->d, ctx->ncols, wt1, wt2, qbot_is_rh != 0, ctx->stream, cz ? (const double*)ctx->sw.czf : nullptr);
   HIPCHK(hipGetLastError());
   return ELMK_OK;
 }
@@ -1456,17 +1481,24 @@ int run_drop(elmk_ctx* ctx)
   return ELMK_OK;
 }
 
-void run_solar_geometry(elmk_ctx* ctx, double) { launch_solar_geometry_run(ctx->d, ctx->ncols, ctx->run.table, ctx->run.cursor, ctx->stream); }
+void run_solar_geometry(elmk_ctx* ctx, double)
+{
+  if (ctx->sw.mode == ELMK_SW_COSZEN)
+    launch_solar_geometry_run_cz(ctx->d, ctx->ncols, ctx->run.table, ctx->run.cursor, ctx->run.rec, ctx->sw.czf, ctx->stream);
+  else
+    launch_solar_geometry_run(ctx->d, ctx->ncols, ctx->run.table, ctx->run.cursor, ctx->stream);
+}
 void run_phenology(elmk_ctx* ctx, double) { launch_phenology_run(ctx->d, ctx->ncols, ctx->run.table, ctx->run.cursor, ctx->run.phen, ctx->stream); }
 void run_forcing(elmk_ctx* ctx, double)
 {
   const elmk_ctx::Run& R = ctx->run;
   const elmk_ctx::Grid& G = ctx->grid;
+  const double* czf = ctx->sw.mode == ELMK_SW_COSZEN ? (const double*)ctx->sw.czf : nullptr;
   if (G.mem)
     launch_get_forcing_run_grid(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, R.fstride, G.npad, G.idx, G.w,
-                                (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
+                                (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf);
   else
-    launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream);
+    launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf);
 }
 void run_init_timestep(elmk_ctx* ctx, double) { launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); }
 void run_conservation(elmk_ctx* ctx, double dt)
@@ -1587,11 +1619,14 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
   if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
   if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY)) return invalid(ctx, "elmk_run: unknown flags");
+  const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   int lo = R.slots, hi = -1;
   unsigned months = 0;
   for (int s = 0; s < nsteps; s++) {
     const elmk_run_step& p = steps[s];
     if (p.forc_slot < 0 || p.forc_slot > R.slots - 2) return invalid(ctx, "elmk_run: forc_slot outside 0 .. forcing_slots - 2");
+    if (cz && !(R.rec && R.rec_set[p.forc_slot]))
+      return invalid(ctx, "elmk_run: shortwave COSZEN mode: a step's forc_slot has no record time (elmk_series_record_times)");
     if (p.month1 < 0 || p.month1 >= RUN_NMONTH || p.month2 < 0 || p.month2 >= RUN_NMONTH) return invalid(ctx, "elmk_run: month outside 0 .. 11");
     if (!(p.decday >= 0.0 && p.decday < 1.0e9) || p.doy < -1 || p.doy > 1000000000) return invalid(ctx, "elmk_run: bad decday / doy");
     lo = std::min(lo, (int)p.forc_slot);
@@ -1632,7 +1667,11 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.count++;
   R.last_buf = buf;
   R.last_nsteps = nsteps;
-  const uint64_t tag = (uint64_t)flags | (ctx->hist_version << 8);
+  const uint64_t tag = (uint64_t)flags | ((uint64_t)cz << 7) | (ctx->hist_version << 8);
+  if (cz) {  // the run's czf replaces the stepwise record time's
+    ctx->sw.step_time = false;
+    ctx->sw.czf_ready = true;
+  }
   int rc = ELMK_OK;
   for (int s = 0; s < nsteps && rc == ELMK_OK; s++) rc = launch_sequence(ctx, GRAPH_RUN_STEP, RUN_STEP, dt, tag);
   HIPCHK(hipEventRecord(ctx->run_done[buf], ctx->stream));
@@ -1715,6 +1754,100 @@ int elmk_clear_forcing_grid(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, "elmk_clear_forcing_grid: the stream is being captured")) return rc;
   if (int rc = run_drop(ctx)) return rc;
   ctx->grid = elmk_ctx::Grid{};
+  return ELMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// shortwave: interval-mean FSDS weighted by cos(zenith) (include/elmk.h "shortwave")
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// set the mode and forget every record time: wait for the runs in flight, drop the captured run step (it holds the mode's kernels)
+int sw_reset(elmk_ctx* ctx, int mode, double forc_dt)
+{
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->graph[GRAPH_RUN_STEP].drop();
+  elmk_ctx::Shortwave& W = ctx->sw;
+  W.mode = mode;
+  W.forc_dt = mode == ELMK_SW_COSZEN ? forc_dt : 0.0;
+  W.step_time = W.czf_ready = false;
+  std::fill(ctx->run.rec_set.begin(), ctx->run.rec_set.end(), 0);
+  return ELMK_OK;
+}
+bool rec_decday_ok(double d) { return d >= 0.0 && d < 1.0e9; }
+}  // namespace
+
+int elmk_set_shortwave_mode(elmk_ctx* ctx, int mode, double forc_dt_seconds)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Shortwave& W = ctx->sw;
+  if (mode != ELMK_SW_REFERENCE && mode != ELMK_SW_COSZEN) return invalid(ctx, "elmk_set_shortwave_mode: unknown mode");
+  if (mode == ELMK_SW_COSZEN) {
+    if (!ctx->geo_set) return invalid(ctx, "elmk_set_shortwave_mode: COSZEN needs a column geography (elmk_set_column_geography)");
+    if (!(forc_dt_seconds > 0.0 && forc_dt_seconds <= 86400.0 * 366.0))
+      return invalid(ctx, "elmk_set_shortwave_mode: forc_dt must be finite and in (0, 366 days]");
+  }
+  if (int rc = refuse_capture(ctx, "elmk_set_shortwave_mode: the stream is being captured")) return rc;
+  if (mode == W.mode && (mode == ELMK_SW_REFERENCE || forc_dt_seconds == W.forc_dt)) return ELMK_OK;  // no change
+  if (mode == ELMK_SW_COSZEN && !W.czf) {
+    const size_t bytes = (size_t)ctx->ld * sizeof(double);
+    if (hip_fail(ctx, W.czf.alloc(bytes), "hipMalloc(shortwave czf)")) return ELMK_E_NOMEM;
+    W.czf_bytes = bytes;
+    HIPCHK(hipMemsetAsync(W.czf, 0, bytes, ctx->stream));
+  }
+  return sw_reset(ctx, mode, forc_dt_seconds);
+}
+
+int elmk_set_forcing_record_time(elmk_ctx* ctx, double rec_decday)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Shortwave& W = ctx->sw;
+  if (W.mode != ELMK_SW_COSZEN) return invalid(ctx, "elmk_set_forcing_record_time: not in shortwave COSZEN mode");
+  if (!rec_decday_ok(rec_decday)) return invalid(ctx, "elmk_set_forcing_record_time: bad rec_decday");
+  if (int rc = push_params(ctx)) return rc;
+  // the record's scalars with the host libm, as elmk_solar_step_consts does for a step (the day-length terms are not read)
+  launch_forcing_cosz(ctx->d, ctx->ncols, elmk_solar_step_consts(W.forc_dt, rec_decday, 0), W.czf, ctx->stream);
+  HIPCHK(hipGetLastError());
+  W.step_time = W.czf_ready = true;
+  return ELMK_OK;
+}
+
+int elmk_series_record_times(elmk_ctx* ctx, int slot0, int nslots, const double* rec_decday)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Run& R = ctx->run;
+  if (!R.mem) return invalid(ctx, "elmk_series_record_times: elmk_run_reserve has not been called");
+  if (ctx->sw.mode != ELMK_SW_COSZEN) return invalid(ctx, "elmk_series_record_times: not in shortwave COSZEN mode");
+  if (slot0 < 0 || nslots < 0 || slot0 + (int64_t)nslots > R.slots) return invalid(ctx, "elmk_series_record_times: slots out of range");
+  if (nslots > 0 && !rec_decday) return invalid(ctx, "elmk_series_record_times: null rec_decday");
+  for (int i = 0; i < nslots; i++)
+    if (!rec_decday_ok(rec_decday[i])) return invalid(ctx, "elmk_series_record_times: bad rec_decday");
+  if (int rc = refuse_capture(ctx, "elmk_series_record_times: the stream is being captured")) return rc;
+  if (nslots == 0) return ELMK_OK;
+  if (!R.rec) {
+    const size_t bytes = (size_t)R.slots * sizeof(elmk_solar_step);
+    if (hip_fail(ctx, R.rec.alloc(bytes), "hipMalloc(record times)")) return ELMK_E_NOMEM;
+    R.rec_bytes = bytes;
+    R.rec_set.assign((size_t)R.slots, 0);
+  }
+  // never write under a run that reads these slots (as elmk_series_upload)
+  for (int b = 0; b < 2; b++)
+    if (R.live[b] && slot0 <= R.slot_hi[b] && slot0 + nslots - 1 >= R.slot_lo[b]) HIPCHK(hipEventSynchronize(ctx->run_done[b]));
+  std::vector<elmk_solar_step> q((size_t)nslots);
+  for (int i = 0; i < nslots; i++) q[(size_t)i] = elmk_solar_step_consts(ctx->sw.forc_dt, rec_decday[i], 0);
+  HIPCHK(hipMemcpyAsync(R.rec + slot0, q.data(), q.size() * sizeof(elmk_solar_step), hipMemcpyHostToDevice, ctx->upload));
+  HIPCHK(hipStreamSynchronize(ctx->upload));  // (q goes out of scope; a run enqueued after this call sees the times)
+  std::fill(R.rec_set.begin() + slot0, R.rec_set.begin() + slot0 + nslots, 1);
+  return ELMK_OK;
+}
+
+int elmk_download_forcing_cosz(elmk_ctx* ctx, double* czf)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!czf) return invalid(ctx, "elmk_download_forcing_cosz: null pointer");
+  if (!ctx->sw.czf_ready) return invalid(ctx, "elmk_download_forcing_cosz: no record time or COSZEN run step since the mode was set");
+  if (int rc = refuse_capture(ctx, "elmk_download_forcing_cosz: the stream is being captured")) return rc;
+  if (ctx->ncols > 0) HIPCHK(hipMemcpyAsync(czf, ctx->sw.czf, (size_t)ctx->ncols * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return ELMK_OK;
 }
 

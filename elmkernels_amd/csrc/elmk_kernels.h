@@ -63,7 +63,10 @@ void launch_init_timestep(const DevState* S, int64_t n, hipStream_t st);
 // the per-column init functions of ELM::initialize_kokkos_elm (initialize_elm_kokkos.cc:373-428), k_init_state.hip
 void launch_initialize_state(const DevState* S, int64_t n, hipStream_t st);
 // the forcing and phenology functors kokkos_init_timestep runs first (k_forcing.hip)
-void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const double* wt2, int qbot_is_rh, hipStream_t st);
+// czf (shortwave COSZEN mode, elmk_set_shortwave_mode): the forcing interval's mean cos(zenith) per column; with czf the COSZEN variant
+// of each forcing kernel runs (ProcessFSDS weighted by coszen_factor(coszen, czf)), without it the reference's kernel as it was
+void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const double* wt2, int qbot_is_rh, hipStream_t st,
+                        const double* czf = nullptr);
 void launch_phenology(const DevState* S, int64_t n, double wt1, double wt2, hipStream_t st);
 void launch_conservation(const DevState* S, int64_t n, int64_t ld, double dt, const double* diag, double* part, double* out,
                          hipStream_t st);
@@ -93,6 +96,8 @@ void launch_copy_multi(const CopyJobs& J, hipStream_t st);
 void launch_math_eval(int fn, const double* x, const double* y, double* out, int64_t n, hipStream_t st);
 // the per-column solar geometry of elmk_solar_geometry (k_solar.hip): coszen and DevState::col_dayl from DevState::geo
 void launch_solar_geometry(const DevState* S, int64_t n, const elmk_solar_step& step, hipStream_t st);
+// czf[c] = elmk_solar_avg_cosz of column c at the forcing record's scalars q (elmk_set_forcing_record_time)
+void launch_forcing_cosz(const DevState* S, int64_t n, const elmk_solar_step& q, double* czf, hipStream_t st);
 
 // multi-step runs (elmk_run): one row of the device step table per step, read through the device step cursor (an int32: the
 // table row of the step now executing; elmk_run sets it before the first step, k_run_next advances it at the end of each)
@@ -105,14 +110,18 @@ struct RunRow {
 // series: the forcing records [RUN_NFORC][slots][ld] and the months [RUN_NPHEN][12][ld], stored element type of the state
 constexpr int RUN_NFORC = 7, RUN_NPHEN = 4, RUN_NMONTH = 12;
 void launch_solar_geometry_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, hipStream_t st);
+// COSZEN mode: also czf[c] at the scalars rec[forc_slot] of the step's forcing record (rec: one row per forcing slot)
+void launch_solar_geometry_run_cz(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const elmk_solar_step* rec,
+                                  double* czf, hipStream_t st);
 void launch_phenology_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* phen, hipStream_t st);
 void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
-                            int qbot_is_rh, hipStream_t st);
+                            int qbot_is_rh, hipStream_t st, const double* czf = nullptr);
 // forcing on a coarser grid (elmk_set_forcing_grid): the map idx / w is [npts][ld] (npts = 1, 2, 4 or 8, padding idx = -1).
 // launch_get_forcing_run_grid: launch_get_forcing_run over cell series [RUN_NFORC][slots][ncells], remapped per column.
 // launch_remap_field: dst[c] = the remap of cells (fp64, ncells values) for columns [0, n); dst is one level of an fp64 state field.
 void launch_get_forcing_run_grid(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
-                                 int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st);
+                                 int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st,
+                                 const double* czf = nullptr);
 void launch_remap_field(void* dst, const double* cells, int64_t n, int64_t ld, int npts, const int32_t* idx, const double* w, hipStream_t st);
 // launch_conservation with the (min, max, sum) triples written to ring row *cursor (cons_ring: [row][8][3]); also opens the flag
 // row of the step (flag_or 0, flag_first "none") for launch_flag_reduce_run

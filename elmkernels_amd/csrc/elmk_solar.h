@@ -115,17 +115,14 @@ static inline elmk_solar_step elmk_solar_step_consts(double dt, double decday, i
   return p;
 }
 
-/* The per-step, per-column part: average_cosz (incident_shortwave.cc:114-121 with :37-94, :99-110) and daylength
- * (day_length.cc:29-33) from the column's row g and the step's scalars; the day-length factor of canopy_fluxes
- * (photosynthesis_impl.hh:33: min(1, max(0.01, dayl^2 / max_dayl^2))) */
-ELMK_MFN void elmk_solar_column(const double g[ELMK_GEO_N], const elmk_solar_step* p, double* cosz_out, double* dayl_out,
-                                double* dayl_factor_out)
+/* average_cosz (incident_shortwave.cc:114-121 with :37-94, :99-110) of one column from its row g and the step's scalars: the
+ * cos(zenith) part of elmk_solar_column, on its own for the forcing interval's mean (elmk_set_forcing_record_time, k_solar.hip).
+ * Reads g[ELMK_GEO_LON .. ELMK_GEO_COS_LAT] and p->s, dtrad, tan_decl, sin_decl, cos_decl. */
+ELMK_MFN double elmk_solar_avg_cosz(const double g[ELMK_GEO_N], const elmk_solar_step* p)
 {
   const double PI = ELMK_SOLAR_PI, TWO_PI = ELMK_SOLAR_TWO_PI;
   const double lon = g[ELMK_GEO_LON], tan_lat = g[ELMK_GEO_TAN_LAT];
   const double sin_lat = g[ELMK_GEO_SIN_LAT], cos_lat = g[ELMK_GEO_COS_LAT];
-  const double sin_my = g[ELMK_GEO_SIN_MYLAT], cos_my = g[ELMK_GEO_COS_MYLAT];
-  const double mdl = g[ELMK_GEO_MAX_DAYL];
   const double dtrad = p->dtrad;
   // dt_start_rad / dt_end_rad (:37-48)
   double t_start = (p->s + lon) - PI;
@@ -160,6 +157,17 @@ ELMK_MFN void elmk_solar_column(const double g[ELMK_GEO_N], const elmk_solar_ste
   double cosz = 0.0;
   if (h1 > h0 || h3 > h2)
     cosz = (aa * (h1 - h0) + bb * (elmk_sin(h1) - elmk_sin(h0))) / dtrad + (aa * (h3 - h2) + bb * (elmk_sin(h3) - elmk_sin(h2))) / dtrad;
+  return cosz;
+}
+
+/* The per-step, per-column part: average_cosz (elmk_solar_avg_cosz) and daylength (day_length.cc:29-33) from the column's row g
+ * and the step's scalars; the day-length factor of canopy_fluxes (photosynthesis_impl.hh:33: min(1, max(0.01, dayl^2 / max_dayl^2))) */
+ELMK_MFN void elmk_solar_column(const double g[ELMK_GEO_N], const elmk_solar_step* p, double* cosz_out, double* dayl_out,
+                                double* dayl_factor_out)
+{
+  const double sin_my = g[ELMK_GEO_SIN_MYLAT], cos_my = g[ELMK_GEO_COS_MYLAT];
+  const double mdl = g[ELMK_GEO_MAX_DAYL];
+  const double cosz = elmk_solar_avg_cosz(g, p);
   // daylength (day_length.cc:29-33) of declination_angle_sin(doy + 1)
   double temp = -(sin_my * p->sin_decl_dl) / (cos_my * p->cos_decl_dl);
   temp = elmk_sol_min(1.0, elmk_sol_max(-1.0, temp));

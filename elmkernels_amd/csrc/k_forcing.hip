@@ -14,6 +14,9 @@
 // atm_data_impl.hh:147-199) works on dates on the host and stays with the caller; the readers are file I/O.
 // Algorithmic bytes per column: get_forcing 7 x 16 + 8 (coszen) read, 17 x 8 written = 256; phenology 4 x 16 + 20 read,
 // 6 x 8 + 4 written = 136.
+//
+// Shortwave (elmk_set_shortwave_mode): every forcing kernel has a COSZEN variant (the CZ switch of get_forcing_col, 8 bytes more read
+// per column: czf, the forcing interval's mean cos(zenith), k_solar.hip).  The REFERENCE kernels are the reference's as before.
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
 
@@ -52,9 +55,11 @@ struct ForcingSrc {
 #define FV(k, lev) src.get(k, lev, c)
 
 // one column: the body of k_get_forcing and of its run-mode variants; Src::get(k, lev, c) is record t_idx + lev of stream k at
-// column c (ForcingSrc: per-column records; GridForcingSrc: cell records remapped through the forcing grid)
-template <class Src>
-__device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, int64_t c, const ForcingWeights& W, const Src& src)
+// column c (ForcingSrc: per-column records; GridForcingSrc: cell records remapped through the forcing grid).  CZ: shortwave COSZEN
+// mode, czf[c] the mean cos(zenith) of the column over the forcing record's interval.
+template <bool CZ, class Src>
+__device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, int64_t c, const ForcingWeights& W, const Src& src,
+                                                const double* __restrict__ czf = nullptr)
 {
   const int64_t ld = S->ld;
   // ProcessTBOT :38-42
@@ -81,9 +86,17 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
     lwrad = ea * STEBOL * elmk_pow(tbot, 4.0);
   }
   S->forc_lwrad[c] = lwrad;
-  // ProcessFSDS :122-142 (record t_idx only); pow(x, 2.0) is x * x in the reference's optimised builds (elmk_math.h)
+  // ProcessFSDS :122-142 (record t_idx only); pow(x, 2.0) is x * x in the reference's optimised builds (elmk_math.h).  COSZEN:
+  // the record (an interval mean) weighted by ELM's fac = (cosz > 0.001) ? min(cosz / avg_forc_cosz, 10) : 0 (:126-130)
   {
-    const double swndr = dmax(FV(4, 0) * S->coszen[c] * 0.5, 0.0);
+    double swndr;
+    if constexpr (CZ) {
+      const double cz = S->coszen[c];
+      const double fac = (cz > 0.001) ? dmin(cz / czf[c], 10.0) : 0.0;
+      swndr = dmax(FV(4, 0) * fac * 0.5, 0.0);
+    } else {
+      swndr = dmax(FV(4, 0) * S->coszen[c] * 0.5, 0.0);
+    }
     const double swndf = swndr, swvdr = swndr, swvdf = swndr;
     const double ratio_rvrf_vis =
         dmin(0.99, dmax(0.17639 + 0.00380 * swvdr - 9.0039e-06 * elmk_sq(swvdr) + 8.1351e-09 * elmk_pow(swvdr, 3.0), 0.01));
@@ -199,7 +212,8 @@ __device__ __forceinline__ void phenology_col(const DevState* __restrict__ S, in
   S->frac_veg_nosno_alb[c] = ((elai + esai) >= 0.05) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict__ S, const ForcingWeights W)
+template <bool CZ>
+__device__ __forceinline__ void get_forcing_levels(const DevState* __restrict__ S, const ForcingWeights& W, const double* __restrict__ czf)
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ld = S->ld;
@@ -207,7 +221,17 @@ __global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict_
   const ForcingSrc src{{S->atm_tbot, S->atm_pbot, S->atm_qbot, S->atm_flds, S->atm_fsds, S->atm_prec, S->atm_wind},
                        {S->atm_tbot + ld, S->atm_pbot + ld, S->atm_qbot + ld, S->atm_flds + ld, S->atm_fsds + ld, S->atm_prec + ld,
                         S->atm_wind + ld}};
-  get_forcing_col(S, c, W, src);
+  get_forcing_col<CZ>(S, c, W, src, czf);
+}
+
+__global__ __launch_bounds__(256) void k_get_forcing(const DevState* __restrict__ S, const ForcingWeights W)
+{
+  get_forcing_levels<false>(S, W, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_get_forcing_cz(const DevState* __restrict__ S, const ForcingWeights W, const double* __restrict__ czf)
+{
+  get_forcing_levels<true>(S, W, czf);
 }
 
 __global__ __launch_bounds__(256) void k_phenology(const DevState* __restrict__ S, double wt1, double wt2)
@@ -220,6 +244,16 @@ __global__ __launch_bounds__(256) void k_phenology(const DevState* __restrict__ 
 }
 
 // elmk_run: the weights and the records of the step's row of the step table, from the series (elmk_api.cpp: elmk_run_reserve)
+__device__ __forceinline__ void run_weights(const RunRow* __restrict__ r, int qbot_is_rh, ForcingWeights& W)
+{
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    W.wt1[i] = r->forc_wt1[i];
+    W.wt2[i] = r->forc_wt2[i];
+  }
+  W.qbot_is_rh = qbot_is_rh;
+}
+
 __global__ __launch_bounds__(256) void k_get_forcing_run(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
                                                          const int32_t* __restrict__ cursor, const dfield forc, int slots, int qbot_is_rh)
 {
@@ -228,12 +262,7 @@ __global__ __launch_bounds__(256) void k_get_forcing_run(const DevState* __restr
   if (c >= S->ncols) return;
   const RunRow* __restrict__ r = rows + *cursor;
   ForcingWeights W;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    W.wt1[i] = r->forc_wt1[i];
-    W.wt2[i] = r->forc_wt2[i];
-  }
-  W.qbot_is_rh = qbot_is_rh;
+  run_weights(r, qbot_is_rh, W);
   const int64_t slot = r->forc_slot;
   ForcingSrc src;
 #pragma unroll
@@ -241,7 +270,29 @@ __global__ __launch_bounds__(256) void k_get_forcing_run(const DevState* __restr
     src.l0[k] = forc + ((int64_t)k * slots + slot) * ld;
     src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ld;
   }
-  get_forcing_col(S, c, W, src);
+  get_forcing_col<false>(S, c, W, src);
+}
+
+// (the COSZEN kernels repeat the bodies of the REFERENCE ones instead of sharing them through a helper: inlined through a helper, the
+// REFERENCE kernels' code changed, if only in the operand order of an address add)
+__global__ __launch_bounds__(256) void k_get_forcing_run_cz(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                            const int32_t* __restrict__ cursor, const dfield forc, int slots, int qbot_is_rh,
+                                                            const double* __restrict__ czf)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const RunRow* __restrict__ r = rows + *cursor;
+  ForcingWeights W;
+  run_weights(r, qbot_is_rh, W);
+  const int64_t slot = r->forc_slot;
+  ForcingSrc src;
+#pragma unroll
+  for (int k = 0; k < RUN_NFORC; k++) {
+    src.l0[k] = forc + ((int64_t)k * slots + slot) * ld;
+    src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ld;
+  }
+  get_forcing_col<true>(S, c, W, src, czf);
 }
 
 // elmk_run with a forcing grid: the series hold cell records [RUN_NFORC][slots][ncells]; the body is k_get_forcing_run's, fed the
@@ -256,12 +307,7 @@ __global__ __launch_bounds__(256) void k_get_forcing_run_grid(const DevState* __
   if (c >= S->ncols) return;
   const RunRow* __restrict__ r = rows + *cursor;
   ForcingWeights W;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    W.wt1[i] = r->forc_wt1[i];
-    W.wt2[i] = r->forc_wt2[i];
-  }
-  W.qbot_is_rh = qbot_is_rh;
+  run_weights(r, qbot_is_rh, W);
   const int64_t slot = r->forc_slot;
   GridForcingSrc<NPTS> src;
 #pragma unroll
@@ -270,7 +316,30 @@ __global__ __launch_bounds__(256) void k_get_forcing_run_grid(const DevState* __
     src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ncells;
   }
   load_map_row<NPTS>(midx, mw, ld, c, src.idx, src.w);
-  get_forcing_col(S, c, W, src);
+  get_forcing_col<false>(S, c, W, src);
+}
+
+template <int NPTS>
+__global__ __launch_bounds__(256) void k_get_forcing_run_grid_cz(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                                 const int32_t* __restrict__ cursor, const dfield forc, int slots,
+                                                                 int64_t ncells, gptr<const int32_t> midx, gptr<const double> mw,
+                                                                 int qbot_is_rh, const double* __restrict__ czf)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const RunRow* __restrict__ r = rows + *cursor;
+  ForcingWeights W;
+  run_weights(r, qbot_is_rh, W);
+  const int64_t slot = r->forc_slot;
+  GridForcingSrc<NPTS> src;
+#pragma unroll
+  for (int k = 0; k < RUN_NFORC; k++) {
+    src.l0[k] = forc + ((int64_t)k * slots + slot) * ncells;
+    src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ncells;
+  }
+  load_map_row<NPTS>(midx, mw, ld, c, src.idx, src.w);
+  get_forcing_col<true>(S, c, W, src, czf);
 }
 
 // elmk_upload_gridded: one level of an fp64 field from fp64 cell values (stored at state precision: fp32 in libelmk_f32.so)
@@ -303,7 +372,8 @@ __global__ __launch_bounds__(256) void k_phenology_run(const DevState* __restric
   phenology_col(S, c, r->month_wt1, r->month_wt2, src);
 }
 
-void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const double* wt2, int qbot_is_rh, hipStream_t st)
+void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const double* wt2, int qbot_is_rh, hipStream_t st,
+                        const double* czf)
 {
   if (n <= 0) return;
   ForcingWeights W;
@@ -312,7 +382,10 @@ void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const d
     W.wt2[i] = wt2[i];
   }
   W.qbot_is_rh = qbot_is_rh;
-  hipLaunchKernelGGL(k_get_forcing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, W);
+  if (czf)
+    hipLaunchKernelGGL(k_get_forcing_cz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, W, czf);
+  else
+    hipLaunchKernelGGL(k_get_forcing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, W);
 }
 
 void launch_phenology(const DevState* S, int64_t n, double wt1, double wt2, hipStream_t st)
@@ -322,21 +395,35 @@ void launch_phenology(const DevState* S, int64_t n, double wt1, double wt2, hipS
 }
 
 void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
-                            int qbot_is_rh, hipStream_t st)
+                            int qbot_is_rh, hipStream_t st, const double* czf)
 {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_get_forcing_run, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, rows, cursor,
-                     field_of<ELMK_F64>::from(const_cast<void*>(forc)), slots, qbot_is_rh);
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const dfield f = field_of<ELMK_F64>::from(const_cast<void*>(forc));
+  if (czf)
+    hipLaunchKernelGGL(k_get_forcing_run_cz, grid, block, 0, st, S, rows, cursor, f, slots, qbot_is_rh, czf);
+  else
+    hipLaunchKernelGGL(k_get_forcing_run, grid, block, 0, st, S, rows, cursor, f, slots, qbot_is_rh);
 }
 
 void launch_get_forcing_run_grid(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
-                                 int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st)
+                                 int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st,
+                                 const double* czf)
 {
   if (n <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   const dfield f = field_of<ELMK_F64>::from(const_cast<void*>(forc));
   const gptr<const int32_t> mi = (gptr<const int32_t>)idx;
   const gptr<const double> mw = (gptr<const double>)w;
+  if (czf) {
+    switch (npts) {
+      case 1: hipLaunchKernelGGL(k_get_forcing_run_grid_cz<1>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh, czf); break;
+      case 2: hipLaunchKernelGGL(k_get_forcing_run_grid_cz<2>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh, czf); break;
+      case 4: hipLaunchKernelGGL(k_get_forcing_run_grid_cz<4>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh, czf); break;
+      default: hipLaunchKernelGGL(k_get_forcing_run_grid_cz<8>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh, czf); break;
+    }
+    return;
+  }
   switch (npts) {
     case 1: hipLaunchKernelGGL(k_get_forcing_run_grid<1>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh); break;
     case 2: hipLaunchKernelGGL(k_get_forcing_run_grid<2>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh); break;

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .shortwave import SW_COSZEN, SW_MODES, SW_REFERENCE  # noqa: F401
 
 DTYPES = {0: np.float64, 1: np.int32, 2: np.uint8, 3: np.uint32}
 LAYOUT_COL_MAJOR, LAYOUT_SOA = 0, 1
@@ -397,6 +398,28 @@ class ELMState:
                                                     fb.ctypes.data_as(C.c_void_p)), "run_diagnostics")
         return mms[:n].copy(), fo[:n].copy(), fb[:n].copy()
 
+    # -- shortwave (include/elmk.h: elmk_set_shortwave_mode ...) -------------------------------------
+    def set_shortwave_mode(self, mode, forc_dt=0.0):
+        """"reference" (the default, the reference's ProcessFSDS) or "coszen" (ELM's cos(zenith) factor over forcing records that are
+        means over forc_dt seconds; needs a column geography).  A change forgets every record time."""
+        code = SW_MODES[mode] if isinstance(mode, str) else int(mode)
+        self._chk(self.lib.elmk_set_shortwave_mode(self.ctx, code, float(forc_dt)), "set_shortwave_mode")
+
+    def set_forcing_record_time(self, rec_decday):
+        """COSZEN, stepwise: the start of the record in level 0 of atm_* (decimal_doy + 1.0); enqueues the czf kernel."""
+        self._chk(self.lib.elmk_set_forcing_record_time(self.ctx, float(rec_decday)), "set_forcing_record_time")
+
+    def series_record_times(self, slot0, rec_decday):
+        """COSZEN, runs: the record start (decimal_doy + 1.0) of forcing slots slot0 .. slot0 + len(rec_decday) - 1."""
+        a = np.ascontiguousarray(rec_decday, dtype=np.float64).reshape(-1)
+        self._chk(self.lib.elmk_series_record_times(self.ctx, int(slot0), a.size, a.ctypes.data_as(C.c_void_p)), "series_record_times")
+
+    def forcing_cosz(self):
+        """czf [ncols]: the forcing interval's mean cos(zenith) of the last record time or COSZEN run step (synchronises)."""
+        out = np.empty(self.ncols)
+        self._chk(self.lib.elmk_download_forcing_cosz(self.ctx, out.ctypes.data_as(C.c_void_p)), "forcing_cosz")
+        return out
+
     # -- forcing on a coarser grid (include/elmk.h: elmk_set_forcing_grid ...) -----------------------
     def set_forcing_grid(self, idx, w, ncells):
         """The per-column remap map (elmkernels_amd/regrid.py): idx int32 [npts, ncols] (-1 = padding, never in row 0), w float64
@@ -694,6 +717,16 @@ class ELMInterface:
             s = int(bad[0])
             raise RuntimeError(f"ELM physics error flags {int(fo[s]):#x} in step {s} of the run, first at column {int(fb[s])}")
         return False
+
+    def set_shortwave_mode(self, mode, forc_dt=0.0):
+        """ELMState.set_shortwave_mode: "coszen" spreads interval-mean FSDS records over their steps (after the geography is set)."""
+        self.S.set_shortwave_mode(mode, forc_dt)
+
+    def set_forcing_record_time(self, rec_decday):
+        self.S.set_forcing_record_time(rec_decday)
+
+    def series_record_times(self, slot0, rec_decday):
+        self.S.series_record_times(slot0, rec_decday)
 
     def set_forcing_grid(self, idx, w, ncells):
         """Forcing on the data set's own grid (ELMState.set_forcing_grid): then upload_gridded() per record, or reserve a run and

@@ -354,6 +354,45 @@ int elmk_set_forcing_grid(elmk_ctx *ctx, int64_t ncells, int npts, const int32_t
 int elmk_clear_forcing_grid(elmk_ctx *ctx);
 int elmk_upload_gridded(elmk_ctx *ctx, int field, int level, const double *cells /*[ncells]*/);
 
+/* ---- shortwave --------------------------------------------------------------------------------
+ * ProcessFSDS (atm_physics_impl.hh:122-143) sets swndr = max(fsds * coszen * 0.5, 0) with a placeholder for ELM's cos(zenith) factor
+ * (:126-130).  The FSDS records of the usual data sets (GSWP3: 3 h, CRUNCEP: 6 h) are means over the record's interval, so with the
+ * placeholder a column receives the record times the step's mean cos(zenith) - less than the data set's sunlight, by an amount that
+ * depends on the sun's height.  COSZEN mode applies ELM's factor, which spreads each record over the steps of its interval:
+ *   cz  = coszen[c] (the step's mean: elmk_solar_geometry, elmk_run, or whatever the caller uploaded)
+ *   czf = average_cosz(lat_c, lon_c, forc_dt, rec_decday) (incident_shortwave.cc:113-121), the mean over the record's interval;
+ *         rec_decday = decimal_doy(start of record t_idx) + 1.0, the convention of elmk_solar_geometry's decday
+ *   fac   = (cz > 0.001) ? min(cz / czf, 10.0) : 0.0       (min: the first argument wins ties and NaN)
+ *   swndr = max(fsds * fac * 0.5, 0.0)                     (in this order, without contraction; the rest of get_forcing unchanged)
+ * Both cosines are the reference's analytic means, so over one interval the steps' factors average to one (up to rounding) wherever
+ * neither the 0.001 threshold nor the cap applies, and the record's energy is kept.  (ELM's offline driver averages cos(zenith)
+ * sampled at the model steps instead; this is not imitated.)
+ *   elmk_set_shortwave_mode     ELMK_SW_REFERENCE (the default: the reference's formula, bit for bit; forc_dt ignored) or
+ *                               ELMK_SW_COSZEN with forc_dt_seconds the data set's record interval.  ELMK_E_INVALID: an unknown
+ *                               mode; COSZEN without a column geography or with forc_dt not finite or outside (0, 86400 x 366]; a
+ *                               stream being captured.  Waits for the runs in flight.  A change of mode or forc_dt forgets every
+ *                               record time and drops the captured run step.  elmk_clear_column_geography puts a COSZEN context
+ *                               back to REFERENCE.
+ *   elmk_set_forcing_record_time  stepwise path: rec_decday of the record held in level 0 of atm_*.  Enqueues one kernel writing czf
+ *                               of every column into a context buffer.  COSZEN mode only; in COSZEN mode elmk_get_forcing without a
+ *                               record time is ELMK_E_INVALID.  An elmk_run overwrites the buffer: set the time again after it.
+ *   elmk_series_record_times    run path: rec_decday of forcing slots [slot0, slot0 + nslots) (the record start of each slot).  COSZEN
+ *                               mode and elmk_run_reserve needed; waits for a run that reads those slots, as elmk_series_upload.
+ *                               elmk_run_reserve and elmk_set_forcing_grid / elmk_clear_forcing_grid forget the times; in COSZEN
+ *                               mode elmk_run refuses, before anything is enqueued, any step whose forc_slot has no time.  Each step
+ *                               of a COSZEN run computes czf beside coszen in its solar kernel.
+ *   elmk_download_forcing_cosz  [ncols]: czf of the last record time or of the last run step; synchronises (tests, diagnostics).
+ *                               ELMK_E_INVALID before either since the mode was set.
+ * A context that never leaves REFERENCE mode runs the kernels, launch sequences and graphs it ran before and allocates nothing more.
+ * COSZEN allocates ncols x 8 bytes (czf) on entering the mode and forcing_slots x 56 bytes (the record times) per reservation, both
+ * counted in elmk_device_bytes.  The restart image does not change: mode and times are driver setup, like geography and maps.
+ * libelmk_f32.so keeps czf and fac in fp64; its bits are report-only, as for the rest of that build. */
+enum { ELMK_SW_REFERENCE = 0, ELMK_SW_COSZEN = 1 };
+int elmk_set_shortwave_mode(elmk_ctx *ctx, int mode, double forc_dt_seconds);
+int elmk_set_forcing_record_time(elmk_ctx *ctx, double rec_decday);
+int elmk_series_record_times(elmk_ctx *ctx, int slot0, int nslots, const double *rec_decday /*[nslots]*/);
+int elmk_download_forcing_cosz(elmk_ctx *ctx, double *czf /*[ncols]*/);
+
 /* ---- output grid -----------------------------------------------------------------------------
  * The other direction: columns aggregated onto an output grid on the device (ELM's c2g, area-weighted means of the columns of each
  * grid cell; the land -> atmosphere map of a coupled run), so a driver downloads ncells values per field level instead of ncols.
@@ -430,8 +469,9 @@ int elmk_gridded_history_add(elmk_ctx *ctx, int tape, int field, int op);
  * gridded entries with the same ncells), any checksum mismatch, snl out of range.
  *
  * The image holds column data and history only.  Parameters, SNICAR and snow-age tables, geography, forcing and output maps, run
- * reservations and series, options and graphs stay with the driver, which sets them up as at start-up.  Restart order: create,
- * parameters and tables, geography and maps, history entries, elmk_restart_load, then the current forcing records or run series.
+ * reservations and series, shortwave mode and record times, options and graphs stay with the driver, which sets them up as at
+ * start-up.  Restart order: create, parameters and tables, geography and maps, shortwave mode, history entries, elmk_restart_load,
+ * then the current forcing records or run series and their record times.
  * Graphs captured before a load stay valid (the arena and the history table do not move). */
 enum { ELMK_CLASS_PROGNOSTIC = 0, ELMK_CLASS_SURFACE = 1, ELMK_CLASS_FORCING = 2, ELMK_CLASS_DIAGNOSTIC = 3 };
 enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2 };

@@ -209,6 +209,14 @@ class ELMInterface {
     return advance(dt_seconds, w);
   }
 
+  /* Shortwave (elmk_set_shortwave_mode): ELMK_SW_COSZEN spreads interval-mean FSDS records (forc_dt seconds each) over the steps of
+   * their interval with ELM's cos(zenith) factor; needs the column geography.  The record start of each record, as decimal_doy + 1.0:
+   * set_forcing_record_time() before a stepwise advance() for the record in level 0 of atm_*, series_record_times() for the forcing
+   * slots of a run. */
+  void set_shortwave_mode(int mode, double forc_dt_seconds) { ok(elmk_set_shortwave_mode(ctx_, mode, forc_dt_seconds)); }
+  void set_forcing_record_time(double rec_decday) { ok(elmk_set_forcing_record_time(ctx_, rec_decday)); }
+  void series_record_times(int slot0, int nslots, const double* rec_decday) { ok(elmk_series_record_times(ctx_, slot0, nslots, rec_decday)); }
+
   /* History tapes (ELM's time-averaged output) kept on the device: register fields once, call accumulate_history() after every
    * advance(), read at the end of an output interval and reset the tape.  op: ELMK_HIST_AVG / _SUM / _MAX / _MIN / _INST;
    * history_add returns the entry id history_read takes.  history_read fills [ncols][nlev] doubles, the host layout of upload. */
