@@ -7,6 +7,7 @@ reference) as hand-written HIP kernels behind the C ABI of include/elmk.h.  This
 mirror of that interface; see DESIGN.md.
 """
 from .decomp import all_ranges, block_range  # noqa: F401
+from .downscale import DS_OFF, DS_TOPO  # noqa: F401
 from .shortwave import SW_COSZEN, SW_REFERENCE, coszen_factor  # noqa: F401
 from .state import (  # noqa: F401
     KERNEL_NAMES,

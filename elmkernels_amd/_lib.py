@@ -90,6 +90,12 @@ SIGNATURES = {
     "elmk_set_forcing_grid": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "elmk_clear_forcing_grid": (C.c_int, [_P]),
     "elmk_upload_gridded": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "elmk_set_column_elevation": (C.c_int, [_P, _P, _P]),
+    "elmk_set_forcing_elevation_gridded": (C.c_int, [_P, _P]),
+    "elmk_set_downscaling": (C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "elmk_set_downscaling_groups": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "elmk_clear_downscaling_groups": (C.c_int, [_P]),
+    "elmk_download_column_elevation": (C.c_int, [_P, _P, _P]),
     "elmk_set_shortwave_mode": (C.c_int, [_P, C.c_int, C.c_double]),
     "elmk_set_forcing_record_time": (C.c_int, [_P, C.c_double]),
     "elmk_series_record_times": (C.c_int, [_P, C.c_int, C.c_int, _P]),

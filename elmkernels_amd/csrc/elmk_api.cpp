@@ -254,6 +254,25 @@ struct elmk_ctx {
     size_t czf_bytes = 0;
     bool step_time = false, czf_ready = false;
   } sw;
+  // downscaling (elmk_set_downscaling): the mode and its parameters; topo = the elevations [2][ld] (row 0 the columns', row 1 the
+  // forcing's surface height), allocated by the first call that sets either, and which rows hold values.  Longwave groups
+  // (elmk_set_downscaling_groups): one allocation `gmem` holds the CSR map (ptr, col, w), each group's weight sum wsum (the host's sum
+  // in term order) and the Lg row [ld] the TOPO forcing kernels write for launch_ds_lw_norm.
+  struct Downscale {
+    int mode = ELMK_DS_OFF;
+    double lapse = 0.006, lapse_lw = 0.032, lw_limit = 0.5;
+    DevBuf<double> topo;
+    size_t topo_bytes = 0;
+    bool col_set = false, forc_set = false;
+    DevBuf<char> gmem;
+    size_t gbytes = 0;
+    int64_t ngroups = 0, nnz = 0;
+    int64_t* ptr = nullptr;
+    int32_t* col = nullptr;
+    double* w = nullptr;
+    double* wsum = nullptr;
+    double* lg = nullptr;
+  } ds;
   std::string err;
 };
 
@@ -537,7 +556,8 @@ int64_t elmk_level_stride(const elmk_ctx* ctx) { return ctx ? ctx->ld : -1; }
 int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
   return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
-                         ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes + ctx->sw.czf_bytes + ctx->run.rec_bytes)
+                         ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes + ctx->sw.czf_bytes + ctx->run.rec_bytes +
+                         ctx->ds.topo_bytes + ctx->ds.gbytes)
              : -1;
 }
 
@@ -1399,6 +1419,28 @@ int elmk_init_timestep(elmk_ctx* ctx)
   return ELMK_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// downscaling TOPO mode: the forcing kernels' parameters (ds_topo false: OFF, the kernels as they were)
+bool ds_topo(const elmk_ctx* ctx) { return ctx->ds.mode == ELMK_DS_TOPO; }
+DsParams ds_params(const elmk_ctx* ctx)
+{
+  const elmk_ctx::Downscale& D = ctx->ds;
+  return DsParams{D.topo, D.topo + ctx->ld, D.gmem ? D.lg : nullptr, D.lapse, D.lapse_lw, D.lw_limit};
+}
+// after a TOPO forcing kernel while groups are set: the longwave renormalisation over the groups
+void ds_lw_norm(elmk_ctx* ctx)
+{
+  const elmk_ctx::Downscale& D = ctx->ds;
+  if (!ds_topo(ctx) || !D.gmem) return;
+  launch_ds_lw_norm(ctx->fptr[ELMK_FIELD_forc_lwrad], store_dtype(ELMK_F64), D.lg, OGridMap{D.ptr, D.col, D.w, D.ngroups, 0.0}, D.wsum,
+                    ctx->stream);
+}
+}  // namespace
+
+extern "C" {
+
 int elmk_get_forcing(elmk_ctx* ctx, const double* wt1, const double* wt2, int qbot_is_rh)
 {
   if (int rc = enter_physics(ctx)) return rc;
@@ -1406,7 +1448,10 @@ int elmk_get_forcing(elmk_ctx* ctx, const double* wt1, const double* wt2, int qb
   const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   if (cz && !ctx->sw.step_time)
     return invalid(ctx, "elmk_get_forcing: shortwave COSZEN mode needs the record's time (elmk_set_forcing_record_time)");
-  launch_get_forcing(ctx->d, ctx->ncols, wt1, wt2, qbot_is_rh != 0, ctx->stream, cz ? (const double*)ctx->sw.czf : nullptr);
+  const DsParams P = ds_params(ctx);
+  launch_get_forcing(ctx->d, ctx->ncols, wt1, wt2, qbot_is_rh != 0, ctx->stream, cz ? (const double*)ctx->sw.czf : nullptr,
+                     ds_topo(ctx) ? &P : nullptr);
+  ds_lw_norm(ctx);
   HIPCHK(hipGetLastError());
   return ELMK_OK;
 }
@@ -1494,11 +1539,14 @@ void run_forcing(elmk_ctx* ctx, double)
   const elmk_ctx::Run& R = ctx->run;
   const elmk_ctx::Grid& G = ctx->grid;
   const double* czf = ctx->sw.mode == ELMK_SW_COSZEN ? (const double*)ctx->sw.czf : nullptr;
+  const DsParams P = ds_params(ctx);
+  const DsParams* ds = ds_topo(ctx) ? &P : nullptr;
   if (G.mem)
     launch_get_forcing_run_grid(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, R.fstride, G.npad, G.idx, G.w,
-                                (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf);
+                                (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf, ds);
   else
-    launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf);
+    launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf, ds);
+  ds_lw_norm(ctx);
 }
 void run_init_timestep(elmk_ctx* ctx, double) { launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); }
 void run_conservation(elmk_ctx* ctx, double dt)
@@ -1667,7 +1715,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.count++;
   R.last_buf = buf;
   R.last_nsteps = nsteps;
-  const uint64_t tag = (uint64_t)flags | ((uint64_t)cz << 7) | (ctx->hist_version << 8);
+  const uint64_t tag = (uint64_t)flags | ((uint64_t)(ds_topo(ctx) && ctx->ds.gmem) << 5) | ((uint64_t)ds_topo(ctx) << 6) |
+                       ((uint64_t)cz << 7) | (ctx->hist_version << 8);
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;
@@ -1847,6 +1896,179 @@ int elmk_download_forcing_cosz(elmk_ctx* ctx, double* czf)
   if (!ctx->sw.czf_ready) return invalid(ctx, "elmk_download_forcing_cosz: no record time or COSZEN run step since the mode was set");
   if (int rc = refuse_capture(ctx, "elmk_download_forcing_cosz: the stream is being captured")) return rc;
   if (ctx->ncols > 0) HIPCHK(hipMemcpyAsync(czf, ctx->sw.czf, (size_t)ctx->ncols * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// downscaling: forcing adjusted to each column's elevation (include/elmk.h "downscaling")
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// every downscaling setter: wait for the runs in flight (they read the elevations and groups), drop the captured run step (it holds
+// the mode's kernels and the groups' addresses)
+int ds_quiesce(elmk_ctx* ctx)
+{
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->graph[GRAPH_RUN_STEP].drop();
+  return ELMK_OK;
+}
+int ds_alloc_topo(elmk_ctx* ctx)
+{
+  elmk_ctx::Downscale& D = ctx->ds;
+  if (D.topo) return ELMK_OK;
+  const size_t bytes = 2 * (size_t)ctx->ld * sizeof(double);
+  if (hip_fail(ctx, D.topo.alloc(bytes), "hipMalloc(elevations)")) return ELMK_E_NOMEM;
+  D.topo_bytes = bytes;
+  HIPCHK(hipMemsetAsync(D.topo, 0, bytes, ctx->stream));
+  return ELMK_OK;
+}
+bool all_finite(const double* a, int64_t n)
+{
+  for (int64_t i = 0; i < n; i++)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
+}  // namespace
+
+int elmk_set_column_elevation(elmk_ctx* ctx, const double* topo_col, const double* topo_forc)
+{
+  if (int rc = enter(ctx)) return rc;
+  const int64_t n = ctx->ncols;
+  if (!topo_col && n > 0) return invalid(ctx, "elmk_set_column_elevation: null topo_col");
+  if (n > 0 && (!all_finite(topo_col, n) || (topo_forc && !all_finite(topo_forc, n))))
+    return invalid(ctx, "elmk_set_column_elevation: non-finite elevation");
+  if (int rc = refuse_capture(ctx, "elmk_set_column_elevation: the stream is being captured")) return rc;
+  if (int rc = ds_quiesce(ctx)) return rc;
+  if (int rc = ds_alloc_topo(ctx)) return rc;
+  elmk_ctx::Downscale& D = ctx->ds;
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(D.topo, topo_col, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (topo_forc) HIPCHK(hipMemcpyAsync(D.topo + ctx->ld, topo_forc, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // (the caller's pageable arrays)
+  D.col_set = true;
+  if (topo_forc) D.forc_set = true;
+  return ELMK_OK;
+}
+
+int elmk_set_forcing_elevation_gridded(elmk_ctx* ctx, const double* cells)
+{
+  if (int rc = enter(ctx)) return rc;
+  const elmk_ctx::Grid& G = ctx->grid;
+  if (!G.mem) return invalid(ctx, "elmk_set_forcing_elevation_gridded: no forcing grid (elmk_set_forcing_grid)");
+  if (!cells) return invalid(ctx, "elmk_set_forcing_elevation_gridded: null cells");
+  if (!all_finite(cells, G.ncells)) return invalid(ctx, "elmk_set_forcing_elevation_gridded: non-finite elevation");
+  if (int rc = refuse_capture(ctx, "elmk_set_forcing_elevation_gridded: the stream is being captured")) return rc;
+  if (int rc = ds_quiesce(ctx)) return rc;
+  if (int rc = ds_alloc_topo(ctx)) return rc;
+  elmk_ctx::Downscale& D = ctx->ds;
+  if (ctx->ncols > 0) {
+    HIPCHK(hipMemcpyAsync(G.cells, cells, (size_t)G.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_remap_field_f64(D.topo + ctx->ld, G.cells, ctx->ncols, ctx->ld, G.npad, G.idx, G.w, ctx->stream);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // (the staging is reused by the next call)
+  D.forc_set = true;
+  return ELMK_OK;
+}
+
+int elmk_set_downscaling(elmk_ctx* ctx, int mode, double lapse, double lapse_lw, double lw_limit)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Downscale& D = ctx->ds;
+  if (mode != ELMK_DS_OFF && mode != ELMK_DS_TOPO) return invalid(ctx, "elmk_set_downscaling: unknown mode");
+  if (!(std::isfinite(lapse) && std::isfinite(lapse_lw) && std::isfinite(lw_limit)))
+    return invalid(ctx, "elmk_set_downscaling: non-finite parameter");
+  if (lapse < 0.0 || lapse_lw < 0.0) return invalid(ctx, "elmk_set_downscaling: negative lapse rate");
+  if (!(lw_limit >= 0.0 && lw_limit < 1.0)) return invalid(ctx, "elmk_set_downscaling: lw_limit outside [0, 1)");
+  if (mode == ELMK_DS_TOPO && !(D.col_set && D.forc_set))
+    return invalid(ctx, "elmk_set_downscaling: TOPO needs both elevations (elmk_set_column_elevation, elmk_set_forcing_elevation_gridded)");
+  if (int rc = refuse_capture(ctx, "elmk_set_downscaling: the stream is being captured")) return rc;
+  if (int rc = ds_quiesce(ctx)) return rc;
+  D.mode = mode;
+  D.lapse = lapse;
+  D.lapse_lw = lapse_lw;
+  D.lw_limit = lw_limit;
+  return ELMK_OK;
+}
+
+int elmk_set_downscaling_groups(elmk_ctx* ctx, int64_t ngroups, const int64_t* ptr, const int32_t* col, const double* w)
+{
+  if (int rc = enter(ctx)) return rc;
+  const char* bad = nullptr;
+  if (ngroups < 1 || ngroups > INT32_MAX) bad = "ngroups outside 1 .. 2^31-1";
+  else if (!ptr) bad = "null ptr";
+  else if (ptr[0] != 0) bad = "ptr[0] != 0";
+  for (int64_t i = 0; !bad && i < ngroups; i++)
+    if (ptr[i + 1] < ptr[i]) bad = "ptr decreasing";
+  const int64_t nnz = bad ? 0 : ptr[ngroups];
+  if (!bad && nnz > INT32_MAX) bad = "nnz outside 0 .. 2^31-1";
+  if (!bad && nnz > 0 && (!col || !w)) bad = "null map";
+  // every gather and scatter of the renormalisation stays inside the longwave row, and a column is scaled once, because of these
+  std::vector<char> seen(bad ? 0 : (size_t)ctx->ncols, 0);
+  for (int64_t p = 0; !bad && p < nnz; p++) {
+    if (col[p] < 0 || col[p] >= ctx->ncols) bad = "col outside [0, ncols)";
+    else if (seen[(size_t)col[p]]++) bad = "a column in more than one group (or twice in one)";
+    else if (!(std::isfinite(w[p]) && w[p] >= 0.0)) bad = "weight not finite and >= 0";
+  }
+  if (bad) return invalid(ctx, (std::string("elmk_set_downscaling_groups: ") + bad).c_str());
+  if (int rc = refuse_capture(ctx, "elmk_set_downscaling_groups: the stream is being captured")) return rc;
+  if (int rc = ds_quiesce(ctx)) return rc;
+  elmk_ctx::Downscale& D = ctx->ds;
+  (void)D.gmem.reset();
+  D.gbytes = 0;
+  std::vector<double> wsum((size_t)ngroups, 0.0);  // W = w[p0], then W = W + w[p]: the order of agg_cells
+  for (int64_t g = 0; g < ngroups; g++)
+    for (int64_t p = ptr[g]; p < ptr[g + 1]; p++) wsum[(size_t)g] = p == ptr[g] ? w[p] : wsum[(size_t)g] + w[p];
+  if (hip_fail(ctx, carve(D.gmem, &D.gbytes, [&](Carve& L) {
+                 L.take(D.ptr, (size_t)(ngroups + 1) * sizeof(int64_t));
+                 L.take(D.col, (size_t)nnz * sizeof(int32_t));
+                 L.take(D.w, (size_t)nnz * sizeof(double));
+                 L.take(D.wsum, (size_t)ngroups * sizeof(double));
+                 L.take(D.lg, (size_t)ctx->ld * sizeof(double));
+               }), "hipMalloc(downscaling groups)")) {
+    D.gbytes = 0;
+    return ELMK_E_NOMEM;
+  }
+  D.ngroups = ngroups;
+  D.nnz = nnz;
+  int rc = ELMK_OK;
+  if (hip_fail(ctx, hipMemsetAsync(D.lg, 0, (size_t)ctx->ld * sizeof(double), ctx->stream), "hipMemset(lg)") ||
+      hip_fail(ctx, hipMemcpyAsync(D.ptr, ptr, (size_t)(ngroups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(ptr)") ||
+      hip_fail(ctx, hipMemcpyAsync(D.wsum, wsum.data(), (size_t)ngroups * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(wsum)") ||
+      (nnz > 0 && (hip_fail(ctx, hipMemcpyAsync(D.col, col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(col)") ||
+                   hip_fail(ctx, hipMemcpyAsync(D.w, w, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(w)"))) ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+    rc = ELMK_E_HIP;
+  if (rc != ELMK_OK) {
+    (void)D.gmem.reset();
+    D.gbytes = 0;
+    D.ngroups = D.nnz = 0;
+  }
+  return rc;
+}
+
+int elmk_clear_downscaling_groups(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_clear_downscaling_groups: the stream is being captured")) return rc;
+  if (int rc = ds_quiesce(ctx)) return rc;
+  elmk_ctx::Downscale& D = ctx->ds;
+  HIPCHK(D.gmem.reset());
+  D.gbytes = 0;
+  D.ngroups = D.nnz = 0;
+  return ELMK_OK;
+}
+
+int elmk_download_column_elevation(elmk_ctx* ctx, double* topo_col, double* topo_forc)
+{
+  if (int rc = enter(ctx)) return rc;
+  const elmk_ctx::Downscale& D = ctx->ds;
+  if ((topo_col && !D.col_set) || (topo_forc && !D.forc_set)) return invalid(ctx, "elmk_download_column_elevation: not set");
+  if (int rc = refuse_capture(ctx, "elmk_download_column_elevation: the stream is being captured")) return rc;
+  const size_t bytes = (size_t)ctx->ncols * sizeof(double);
+  if (topo_col && bytes) HIPCHK(hipMemcpyAsync(topo_col, D.topo, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (topo_forc && bytes) HIPCHK(hipMemcpyAsync(topo_forc, D.topo + ctx->ld, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return ELMK_OK;
 }

@@ -64,9 +64,16 @@ void launch_init_timestep(const DevState* S, int64_t n, hipStream_t st);
 void launch_initialize_state(const DevState* S, int64_t n, hipStream_t st);
 // the forcing and phenology functors kokkos_init_timestep runs first (k_forcing.hip)
 // czf (shortwave COSZEN mode, elmk_set_shortwave_mode): the forcing interval's mean cos(zenith) per column; with czf the COSZEN variant
-// of each forcing kernel runs (ProcessFSDS weighted by coszen_factor(coszen, czf)), without it the reference's kernel as it was
+// of each forcing kernel runs (ProcessFSDS weighted by coszen_factor(coszen, czf)), without it the reference's kernel as it was.
+// ds (downscaling TOPO mode, elmk_set_downscaling): with it the downscaling variant runs (k_forcing.hip: downscale_col).
+struct DsParams {
+  const double* hc;  // [ld] the column's elevation (m)
+  const double* hf;  // [ld] the forcing's surface height as the column sees it (m)
+  double* lg;        // [ld] Lg, the longwave before downscaling, for launch_ds_lw_norm; null while no groups are set
+  double lapse, lapse_lw, lw_limit;
+};
 void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const double* wt2, int qbot_is_rh, hipStream_t st,
-                        const double* czf = nullptr);
+                        const double* czf = nullptr, const DsParams* ds = nullptr);
 void launch_phenology(const DevState* S, int64_t n, double wt1, double wt2, hipStream_t st);
 void launch_conservation(const DevState* S, int64_t n, int64_t ld, double dt, const double* diag, double* part, double* out,
                          hipStream_t st);
@@ -115,14 +122,17 @@ void launch_solar_geometry_run_cz(const DevState* S, int64_t n, const RunRow* ro
                                   double* czf, hipStream_t st);
 void launch_phenology_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* phen, hipStream_t st);
 void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
-                            int qbot_is_rh, hipStream_t st, const double* czf = nullptr);
+                            int qbot_is_rh, hipStream_t st, const double* czf = nullptr, const DsParams* ds = nullptr);
 // forcing on a coarser grid (elmk_set_forcing_grid): the map idx / w is [npts][ld] (npts = 1, 2, 4 or 8, padding idx = -1).
 // launch_get_forcing_run_grid: launch_get_forcing_run over cell series [RUN_NFORC][slots][ncells], remapped per column.
 // launch_remap_field: dst[c] = the remap of cells (fp64, ncells values) for columns [0, n); dst is one level of an fp64 state field.
 void launch_get_forcing_run_grid(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
                                  int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st,
-                                 const double* czf = nullptr);
+                                 const double* czf = nullptr, const DsParams* ds = nullptr);
 void launch_remap_field(void* dst, const double* cells, int64_t n, int64_t ld, int npts, const int32_t* idx, const double* w, hipStream_t st);
+// launch_remap_field into an fp64 row dst[0 .. n) in every build (elmk_set_forcing_elevation_gridded)
+void launch_remap_field_f64(double* dst, const double* cells, int64_t n, int64_t ld, int npts, const int32_t* idx, const double* w,
+                            hipStream_t st);
 // launch_conservation with the (min, max, sum) triples written to ring row *cursor (cons_ring: [row][8][3]); also opens the flag
 // row of the step (flag_or 0, flag_first "none") for launch_flag_reduce_run
 void launch_conservation_run(const DevState* S, int64_t n, int64_t ld, double dt, const double* diag, double* part, double* cons_ring,
@@ -173,6 +183,10 @@ void launch_ogrid_aggregate(const void* src, int dtype, const OGridMap& M, int64
 // launch_hist_accumulate over the column rows and, in the same launch, the cell rows crows[ncrows] (acc: cells of one level, fp64)
 void launch_hist_accumulate_cells(const HistRow* rows, int nrows, const HistRow* crows, int ncrows, const OGridMap& M,
                                   unsigned long long* counts, int64_t ncols, unsigned tape_mask, hipStream_t st);
+// downscaling's longwave renormalisation (k_history.hip, elmk_set_downscaling_groups): M is the CSR map of the groups (fill 0), wsum[g]
+// the sum of group g's weights in term order.  Per group A = aggregate of lg, S = aggregate of lw (stored element type lw_dtype), then
+// norm = (W == 0 || A == 0) ? 1 : (A / W) / (S / W) and lw[col] = lw[col] * norm for every column of the group
+void launch_ds_lw_norm(void* lw, int lw_dtype, const double* lg, const OGridMap& M, const double* wsum, hipStream_t st);
 // cells [cell0, cell0 + m) of one gridded entry's result (level stride ld) into out[lev * m + i]: fill for an empty cell, else as
 // launch_hist_finalize
 void launch_ogrid_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, const int64_t* ptr, double fill, int64_t cell0,

@@ -17,6 +17,10 @@
 //
 // Shortwave (elmk_set_shortwave_mode): every forcing kernel has a COSZEN variant (the CZ switch of get_forcing_col, 8 bytes more read
 // per column: czf, the forcing interval's mean cos(zenith), k_solar.hip).  The REFERENCE kernels are the reference's as before.
+//
+// Downscaling (elmk_set_downscaling): every forcing kernel, COSZEN or not, has a TOPO variant (the DS switch of get_forcing_col: 16
+// bytes more read per column, the column's elevation and the forcing's surface height, and 8 written while longwave groups are set,
+// Lg) that adjusts the near-surface air from the forcing's height to the column's (downscale_col).  The OFF kernels are as before.
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
 
@@ -54,21 +58,47 @@ struct ForcingSrc {
 #define SV(k, lev) src.l##lev[k][c]
 #define FV(k, lev) src.get(k, lev, c)
 
+// ---- downscaling to the column's elevation (include/elmk.h "downscaling"; ELM's downscale_forcings) -------------------------------
+// tg, pg, qg, Lg: tbot, pbot, qbot, lwrad as get_forcing computes them at the forcing's surface height hf; the values at the column's
+// elevation hc, in this operation order, without contraction (elmkernels_amd/downscale.py restates it on the host)
+constexpr double DS_ZBOT = 30.0;  // ProcessZBOT's forc_hgt
+struct DsCol {
+  double tc, thc, pc, qc, lc;
+};
+__device__ __forceinline__ DsCol downscale_col(double tg, double pg, double qg, double lg, double hc, double hf, const DsParams& P)
+{
+  DsCol o;
+  const double dz = hc - hf;
+  o.tc = tg - P.lapse * dz;
+  const double hbot = RAIR * 0.5 * (tg + o.tc) / GRAV;
+  o.pc = pg * elmk_exp(-dz / hbot);
+  o.thc = tg + (o.tc - tg) * elmk_exp((DS_ZBOT / hbot) * (RAIR / CPAIR));  // thg = tg (ProcessTBOT: forc_thbot = tbot)
+  double es, esdT, qs_g, qs_c, qsdT;
+  qsat(tg, pg, es, esdT, qs_g, qsdT);
+  qsat(o.tc, o.pc, es, esdT, qs_c, qsdT);
+  o.qc = qg * (qs_c / qs_g);
+  o.lc = dmax(dmin(lg - P.lapse_lw * dz, lg * (1.0 + P.lw_limit)), lg * (1.0 - P.lw_limit));
+  return o;
+}
+
 // one column: the body of k_get_forcing and of its run-mode variants; Src::get(k, lev, c) is record t_idx + lev of stream k at
 // column c (ForcingSrc: per-column records; GridForcingSrc: cell records remapped through the forcing grid).  CZ: shortwave COSZEN
-// mode, czf[c] the mean cos(zenith) of the column over the forcing record's interval.
-template <bool CZ, class Src>
+// mode, czf[c] the mean cos(zenith) of the column over the forcing record's interval.  DS: downscaling TOPO mode (*ds): tbot, thbot,
+// pbot, qbot and lwrad at the column's elevation, rain and snow split by the downscaled temperature, Lg to ds->lg while groups are set.
+template <bool CZ, class Src, bool DS = false>
 __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, int64_t c, const ForcingWeights& W, const Src& src,
-                                                const double* __restrict__ czf = nullptr)
+                                                const double* __restrict__ czf = nullptr, const DsParams* ds = nullptr)
 {
   const int64_t ld = S->ld;
   // ProcessTBOT :38-42
   const double tbot = dmin(interp_forcing(W.wt1[0], W.wt2[0], FV(0, 0), FV(0, 1)), 323.0);
-  S->forc_tbot[c] = tbot;
-  S->forc_thbot[c] = tbot;
+  if constexpr (!DS) {
+    S->forc_tbot[c] = tbot;
+    S->forc_thbot[c] = tbot;
+  }
   // ProcessPBOT :55-58
   const double pbot = dmax(interp_forcing(W.wt1[1], W.wt2[1], FV(1, 0), FV(1, 1)), 4.0e4);
-  S->forc_pbot[c] = pbot;
+  if constexpr (!DS) S->forc_pbot[c] = pbot;
   // ProcessQBOT :73-81
   double qbot = dmax(interp_forcing(W.wt1[2], W.wt2[2], FV(2, 0), FV(2, 1)), 1.0e-9);
   if (W.qbot_is_rh) {
@@ -76,7 +106,7 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
     const double qsat = 0.622 * e / (pbot - 0.378 * e);
     qbot *= qsat / 100.0;
   }
-  S->forc_qbot[c] = qbot;
+  if constexpr (!DS) S->forc_qbot[c] = qbot;
   // ProcessFLDS :97-107
   const double flds = interp_forcing(W.wt1[3], W.wt2[3], FV(3, 0), FV(3, 1));
   double lwrad = flds;
@@ -85,7 +115,19 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
     const double ea = 0.70 + 5.95e-5 * 0.01 * e * elmk_exp(1500.0 / tbot);
     lwrad = ea * STEBOL * elmk_pow(tbot, 4.0);
   }
-  S->forc_lwrad[c] = lwrad;
+  double tprec = tbot;  // the temperature that splits precipitation
+  if constexpr (DS) {
+    const DsCol d = downscale_col(tbot, pbot, qbot, lwrad, ds->hc[c], ds->hf[c], *ds);
+    S->forc_tbot[c] = d.tc;
+    S->forc_thbot[c] = d.thc;
+    S->forc_pbot[c] = d.pc;
+    S->forc_qbot[c] = d.qc;
+    S->forc_lwrad[c] = d.lc;
+    if (ds->lg) ds->lg[c] = lwrad;
+    tprec = d.tc;
+  } else {
+    S->forc_lwrad[c] = lwrad;
+  }
   // ProcessFSDS :122-142 (record t_idx only); pow(x, 2.0) is x * x in the reference's optimised builds (elmk_math.h).  COSZEN:
   // the record (an interval mean) weighted by ELM's fac = (cosz > 0.001) ? min(cosz / avg_forc_cosz, 10) : 0 (:126-130)
   {
@@ -109,7 +151,7 @@ __device__ __forceinline__ void get_forcing_col(const DevState* __restrict__ S, 
   }
   // ProcessPREC :157-163 (record t_idx only)
   {
-    const double frac1 = (tbot - TFRZ) * 0.5;
+    const double frac1 = (tprec - TFRZ) * 0.5;
     const double frac2 = dmin(1.0, dmax(0.0, frac1));
     const double prec = dmax(FV(5, 0), 0.0);
     S->forc_rain[c] = frac2 * prec;
@@ -234,6 +276,21 @@ __global__ __launch_bounds__(256) void k_get_forcing_cz(const DevState* __restri
   get_forcing_levels<true>(S, W, czf);
 }
 
+// TOPO mode (elmk_set_downscaling): the downscaling variants of the kernels around them, COSZEN through CZ (czf null without it).
+// New kernels, so each shares one template; the OFF kernels keep their own bodies (see the note above k_get_forcing_run_cz).
+template <bool CZ>
+__global__ __launch_bounds__(256) void k_get_forcing_ds(const DevState* __restrict__ S, const ForcingWeights W, const double* __restrict__ czf,
+                                                        const DsParams P)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const ForcingSrc src{{S->atm_tbot, S->atm_pbot, S->atm_qbot, S->atm_flds, S->atm_fsds, S->atm_prec, S->atm_wind},
+                       {S->atm_tbot + ld, S->atm_pbot + ld, S->atm_qbot + ld, S->atm_flds + ld, S->atm_fsds + ld, S->atm_prec + ld,
+                        S->atm_wind + ld}};
+  get_forcing_col<CZ, ForcingSrc, true>(S, c, W, src, czf, &P);
+}
+
 __global__ __launch_bounds__(256) void k_phenology(const DevState* __restrict__ S, double wt1, double wt2)
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -295,6 +352,27 @@ __global__ __launch_bounds__(256) void k_get_forcing_run_cz(const DevState* __re
   get_forcing_col<true>(S, c, W, src, czf);
 }
 
+template <bool CZ>
+__global__ __launch_bounds__(256) void k_get_forcing_run_ds(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                            const int32_t* __restrict__ cursor, const dfield forc, int slots, int qbot_is_rh,
+                                                            const double* __restrict__ czf, const DsParams P)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const RunRow* __restrict__ r = rows + *cursor;
+  ForcingWeights W;
+  run_weights(r, qbot_is_rh, W);
+  const int64_t slot = r->forc_slot;
+  ForcingSrc src;
+#pragma unroll
+  for (int k = 0; k < RUN_NFORC; k++) {
+    src.l0[k] = forc + ((int64_t)k * slots + slot) * ld;
+    src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ld;
+  }
+  get_forcing_col<CZ, ForcingSrc, true>(S, c, W, src, czf, &P);
+}
+
 // elmk_run with a forcing grid: the series hold cell records [RUN_NFORC][slots][ncells]; the body is k_get_forcing_run's, fed the
 // remapped records (FSDS and PREC read record t_idx only, as there)
 template <int NPTS>
@@ -342,10 +420,46 @@ __global__ __launch_bounds__(256) void k_get_forcing_run_grid_cz(const DevState*
   get_forcing_col<true>(S, c, W, src, czf);
 }
 
+template <int NPTS, bool CZ>
+__global__ __launch_bounds__(256) void k_get_forcing_run_grid_ds(const DevState* __restrict__ S, const RunRow* __restrict__ rows,
+                                                                 const int32_t* __restrict__ cursor, const dfield forc, int slots,
+                                                                 int64_t ncells, gptr<const int32_t> midx, gptr<const double> mw,
+                                                                 int qbot_is_rh, const double* __restrict__ czf, const DsParams P)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t ld = S->ld;
+  if (c >= S->ncols) return;
+  const RunRow* __restrict__ r = rows + *cursor;
+  ForcingWeights W;
+  run_weights(r, qbot_is_rh, W);
+  const int64_t slot = r->forc_slot;
+  GridForcingSrc<NPTS> src;
+#pragma unroll
+  for (int k = 0; k < RUN_NFORC; k++) {
+    src.l0[k] = forc + ((int64_t)k * slots + slot) * ncells;
+    src.l1[k] = forc + ((int64_t)k * slots + slot + 1) * ncells;
+  }
+  load_map_row<NPTS>(midx, mw, ld, c, src.idx, src.w);
+  get_forcing_col<CZ, GridForcingSrc<NPTS>, true>(S, c, W, src, czf, &P);
+}
+
 // elmk_upload_gridded: one level of an fp64 field from fp64 cell values (stored at state precision: fp32 in libelmk_f32.so)
 template <int NPTS>
 __global__ __launch_bounds__(256) void k_remap_field(dfield dst, gptr<const double> cells, int64_t n, int64_t ld, gptr<const int32_t> midx,
                                                      gptr<const double> mw)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  int32_t idx[NPTS];
+  double w[NPTS];
+  load_map_row<NPTS>(midx, mw, ld, c, idx, w);
+  dst[c] = remap_cells<NPTS>(idx, w, cells);
+}
+
+// elmk_set_forcing_elevation_gridded: k_remap_field into an fp64 row in every build (the elevations stay fp64 in libelmk_f32.so)
+template <int NPTS>
+__global__ __launch_bounds__(256) void k_remap_field_f64(gptr<double> dst, gptr<const double> cells, int64_t n, int64_t ld,
+                                                         gptr<const int32_t> midx, gptr<const double> mw)
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n) return;
@@ -373,7 +487,7 @@ __global__ __launch_bounds__(256) void k_phenology_run(const DevState* __restric
 }
 
 void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const double* wt2, int qbot_is_rh, hipStream_t st,
-                        const double* czf)
+                        const double* czf, const DsParams* ds)
 {
   if (n <= 0) return;
   ForcingWeights W;
@@ -382,6 +496,13 @@ void launch_get_forcing(const DevState* S, int64_t n, const double* wt1, const d
     W.wt2[i] = wt2[i];
   }
   W.qbot_is_rh = qbot_is_rh;
+  if (ds) {
+    if (czf)
+      hipLaunchKernelGGL(k_get_forcing_ds<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, W, czf, *ds);
+    else
+      hipLaunchKernelGGL(k_get_forcing_ds<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, W, czf, *ds);
+    return;
+  }
   if (czf)
     hipLaunchKernelGGL(k_get_forcing_cz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, W, czf);
   else
@@ -395,11 +516,18 @@ void launch_phenology(const DevState* S, int64_t n, double wt1, double wt2, hipS
 }
 
 void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
-                            int qbot_is_rh, hipStream_t st, const double* czf)
+                            int qbot_is_rh, hipStream_t st, const double* czf, const DsParams* ds)
 {
   if (n <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   const dfield f = field_of<ELMK_F64>::from(const_cast<void*>(forc));
+  if (ds) {
+    if (czf)
+      hipLaunchKernelGGL(k_get_forcing_run_ds<true>, grid, block, 0, st, S, rows, cursor, f, slots, qbot_is_rh, czf, *ds);
+    else
+      hipLaunchKernelGGL(k_get_forcing_run_ds<false>, grid, block, 0, st, S, rows, cursor, f, slots, qbot_is_rh, czf, *ds);
+    return;
+  }
   if (czf)
     hipLaunchKernelGGL(k_get_forcing_run_cz, grid, block, 0, st, S, rows, cursor, f, slots, qbot_is_rh, czf);
   else
@@ -408,13 +536,24 @@ void launch_get_forcing_run(const DevState* S, int64_t n, const RunRow* rows, co
 
 void launch_get_forcing_run_grid(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, const void* forc, int slots,
                                  int64_t ncells, int npts, const int32_t* idx, const double* w, int qbot_is_rh, hipStream_t st,
-                                 const double* czf)
+                                 const double* czf, const DsParams* ds)
 {
   if (n <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   const dfield f = field_of<ELMK_F64>::from(const_cast<void*>(forc));
   const gptr<const int32_t> mi = (gptr<const int32_t>)idx;
   const gptr<const double> mw = (gptr<const double>)w;
+  if (ds) {
+#define ELMK_DS_GRID(N, CZ) hipLaunchKernelGGL((k_get_forcing_run_grid_ds<N, CZ>), grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh, czf, *ds)
+    switch (npts) {
+      case 1: if (czf) ELMK_DS_GRID(1, true); else ELMK_DS_GRID(1, false); break;
+      case 2: if (czf) ELMK_DS_GRID(2, true); else ELMK_DS_GRID(2, false); break;
+      case 4: if (czf) ELMK_DS_GRID(4, true); else ELMK_DS_GRID(4, false); break;
+      default: if (czf) ELMK_DS_GRID(8, true); else ELMK_DS_GRID(8, false); break;
+    }
+#undef ELMK_DS_GRID
+    return;
+  }
   if (czf) {
     switch (npts) {
       case 1: hipLaunchKernelGGL(k_get_forcing_run_grid_cz<1>, grid, block, 0, st, S, rows, cursor, f, slots, ncells, mi, mw, qbot_is_rh, czf); break;
@@ -445,6 +584,23 @@ void launch_remap_field(void* dst, const double* cells, int64_t n, int64_t ld, i
     case 2: hipLaunchKernelGGL(k_remap_field<2>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
     case 4: hipLaunchKernelGGL(k_remap_field<4>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
     default: hipLaunchKernelGGL(k_remap_field<8>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+  }
+}
+
+void launch_remap_field_f64(double* dst, const double* cells, int64_t n, int64_t ld, int npts, const int32_t* idx, const double* w,
+                            hipStream_t st)
+{
+  if (n <= 0) return;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const gptr<double> d = (gptr<double>)dst;
+  const gptr<const double> a = (gptr<const double>)cells;
+  const gptr<const int32_t> mi = (gptr<const int32_t>)idx;
+  const gptr<const double> mw = (gptr<const double>)w;
+  switch (npts) {
+    case 1: hipLaunchKernelGGL(k_remap_field_f64<1>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+    case 2: hipLaunchKernelGGL(k_remap_field_f64<2>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+    case 4: hipLaunchKernelGGL(k_remap_field_f64<4>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
+    default: hipLaunchKernelGGL(k_remap_field_f64<8>, grid, block, 0, st, d, a, n, ld, mi, mw); break;
   }
 }
 

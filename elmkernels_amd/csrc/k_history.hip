@@ -157,17 +157,18 @@ void launch_hist_finalize(const double* acc, int64_t ld, int nlev, int op, int64
 namespace {
 constexpr int AGG_THREADS = 256, AGG_CELLS = 64, AGG_TILE = 2048;
 
-// cells [c0, min(c0 + AGG_CELLS, cend)) of the source row src; called by every thread of the workgroup (it has barriers, and c0 is
-// uniform).  Thread t < AGG_CELLS returns the value of cell c0 + t (fill for an empty cell or a thread past the end) and in *empty
+// cells [c0, min(c0 + CELLS, cend)) of the source row src; called by every thread of the workgroup (it has barriers, and c0 is
+// uniform).  Thread t < CELLS returns the value of cell c0 + t (fill for an empty cell or a thread past the end) and in *empty
 // whether that cell has no terms.
+template <int CELLS = AGG_CELLS>
 __device__ __forceinline__ double agg_cells(const void* src, int dtype, const OGridMap& M, int64_t c0, int64_t cend, double* tile,
                                             bool* empty)
 {
   const int t = threadIdx.x;
-  const int64_t c1 = c0 + AGG_CELLS < cend ? c0 + AGG_CELLS : cend;
+  const int64_t c1 = c0 + CELLS < cend ? c0 + CELLS : cend;
   const int64_t P0 = M.ptr[c0], P1 = M.ptr[c1];
   int64_t p0 = 0, p1 = 0;
-  if (t < AGG_CELLS && c0 + t < c1) {
+  if (t < CELLS && c0 + t < c1) {
     p0 = M.ptr[c0 + t];
     p1 = M.ptr[c0 + t + 1];
   }
@@ -246,6 +247,57 @@ __global__ __launch_bounds__(256) void k_ogrid_finalize(const double* __restrict
 }
 
 static unsigned cell_blocks(int64_t ncells) { return (unsigned)(ncells > 0 ? (ncells + AGG_CELLS - 1) / AGG_CELLS : 1); }
+
+// downscaling's longwave renormalisation (elmk_set_downscaling_groups; ELM's downscale_longwave): the groups are an output-grid map
+// (fill 0, a column in at most one group), so agg_cells gives each group's A = sum w * Lg and S = sum w * Lc in term order.  Then, for
+// the cells of this workgroup, norm = (W == 0 || A == 0) ? 1 : (A / W) / (S / W), and every thread scales its share of the span's
+// terms: term q belongs to the cell k with ptr[c0 + k] <= q < ptr[c0 + k + 1] (a search over the span's ptr in LDS).  A column is
+// read and written only by the workgroup of its one group, after that workgroup's sums, so one launch needs no atomics.  A gridcell
+// holds far more columns than an output cell holds terms on average, so a workgroup takes DS_CELLS groups, not AGG_CELLS: at 1 M
+// columns in groups of 150 that is 417 workgroups instead of 105, and each lane's serial sum is the only long chain left.
+constexpr int DS_CELLS = 16;
+__global__ __launch_bounds__(AGG_THREADS) void k_ds_lw_norm(void* __restrict__ lw, int lw_dtype, const double* __restrict__ lg, OGridMap M,
+                                                            const double* __restrict__ wsum)
+{
+  __shared__ double tile[AGG_TILE];
+  __shared__ double norm[DS_CELLS];
+  __shared__ int64_t sp[DS_CELLS + 1];
+  const int t = threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * DS_CELLS;
+  const int64_t c1 = c0 + DS_CELLS < M.ncells ? c0 + DS_CELLS : M.ncells;
+  bool empty;
+  const double A = agg_cells<DS_CELLS>(lg, ELMK_F64, M, c0, M.ncells, tile, &empty);
+  const double S = agg_cells<DS_CELLS>(lw, lw_dtype, M, c0, M.ncells, tile, &empty);
+  if (t < DS_CELLS && c0 + t < c1) {
+    const double W = wsum[c0 + t];
+    norm[t] = (W == 0.0 || A == 0.0) ? 1.0 : (A / W) / (S / W);
+  }
+  if (t <= DS_CELLS && c0 + t <= c1) sp[t] = M.ptr[c0 + t];
+  __syncthreads();
+  const int ncl = (int)(c1 - c0);
+  for (int64_t q = sp[0] + t; q < sp[ncl]; q += AGG_THREADS) {
+    int lo = 0, hi = ncl;  // sp[lo] <= q < sp[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (sp[mid] <= q) lo = mid;
+      else hi = mid;
+    }
+    const int64_t c = M.col[q];
+    if (lw_dtype == ELMK_F64) {
+      ELMK_GLOBAL double* p = (ELMK_GLOBAL double*)lw + c;
+      *p = *p * norm[lo];
+    } else {  // ELMK_F32_STORED: widened, scaled in fp64, rounded on store
+      ELMK_GLOBAL float* p = (ELMK_GLOBAL float*)lw + c;
+      *p = (float)((double)*p * norm[lo]);
+    }
+  }
+}
+
+void launch_ds_lw_norm(void* lw, int lw_dtype, const double* lg, const OGridMap& M, const double* wsum, hipStream_t st)
+{
+  if (M.ncells <= 0) return;
+  hipLaunchKernelGGL(k_ds_lw_norm, dim3((unsigned)((M.ncells + DS_CELLS - 1) / DS_CELLS)), dim3(AGG_THREADS), 0, st, lw, lw_dtype, lg, M, wsum);
+}
 
 void launch_ogrid_aggregate(const void* src, int dtype, const OGridMap& M, int64_t cell0, int64_t m, double* out, hipStream_t st)
 {

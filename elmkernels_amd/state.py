@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .downscale import DS_MODES, LAPSE, LAPSE_LW, LW_LIMIT
 from .shortwave import SW_COSZEN, SW_MODES, SW_REFERENCE  # noqa: F401
 
 DTYPES = {0: np.float64, 1: np.int32, 2: np.uint8, 3: np.uint32}
@@ -420,6 +421,54 @@ class ELMState:
         self._chk(self.lib.elmk_download_forcing_cosz(self.ctx, out.ctypes.data_as(C.c_void_p)), "forcing_cosz")
         return out
 
+    # -- downscaling (include/elmk.h: elmk_set_downscaling ...) ---------------------------------------
+    def _cols(self, a, what):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if a.size != self.ncols:
+            raise ValueError(f"{what} must be [{self.ncols}]")
+        return a
+
+    def set_column_elevation(self, topo_col, topo_forc=None):
+        """The column elevations and the forcing's surface height as each column sees it (m, [ncols] each); topo_forc None sets only
+        the columns' (the forcing's then comes from set_forcing_elevation_gridded)."""
+        hc = self._cols(topo_col, "topo_col")
+        hf = None if topo_forc is None else self._cols(topo_forc, "topo_forc")
+        self._chk(self.lib.elmk_set_column_elevation(self.ctx, hc.ctypes.data_as(C.c_void_p), None if hf is None else hf.ctypes.data_as(C.c_void_p)),
+                  "set_column_elevation")
+
+    def set_forcing_elevation_gridded(self, cells):
+        """The forcing's surface height from its grid's cells [ncells], remapped through the forcing map (regrid.apply_map)."""
+        a = np.ascontiguousarray(cells, dtype=np.float64).reshape(-1)
+        if getattr(self, "grid_ncells", None) is not None and a.size != self.grid_ncells:
+            raise ValueError(f"{a.size} cell values, the grid has {self.grid_ncells}")
+        self._chk(self.lib.elmk_set_forcing_elevation_gridded(self.ctx, a.ctypes.data_as(C.c_void_p)), "set_forcing_elevation_gridded")
+
+    def set_downscaling(self, mode, lapse=LAPSE, lapse_lw=LAPSE_LW, lw_limit=LW_LIMIT):
+        """"off" (the default) or "topo": forcing adjusted from the forcing's surface height to each column's elevation."""
+        code = DS_MODES[mode] if isinstance(mode, str) else int(mode)
+        self._chk(self.lib.elmk_set_downscaling(self.ctx, code, float(lapse), float(lapse_lw), float(lw_limit)), "set_downscaling")
+
+    def set_downscaling_groups(self, ptr, col, w):
+        """Longwave renormalisation groups, CSR by gridcell (regrid.owner_map builds one): ptr int64 [ngroups + 1], col int32 [nnz],
+        w float64 [nnz]; a column in at most one group, weights finite and >= 0."""
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+        col = np.ascontiguousarray(col, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if ptr.size < 2 or col.size != w.size or ptr[-1] != col.size:
+            raise ValueError("ptr must be [ngroups + 1] with ptr[-1] == len(col) == len(w)")
+        self._chk(self.lib.elmk_set_downscaling_groups(self.ctx, ptr.size - 1, ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                                       w.ctypes.data_as(C.c_void_p)), "set_downscaling_groups")
+
+    def clear_downscaling_groups(self):
+        self._chk(self.lib.elmk_clear_downscaling_groups(self.ctx), "clear_downscaling_groups")
+
+    def column_elevation(self):
+        """(topo_col, topo_forc) as held on the device (synchronises)."""
+        hc, hf = np.empty(self.ncols), np.empty(self.ncols)
+        self._chk(self.lib.elmk_download_column_elevation(self.ctx, hc.ctypes.data_as(C.c_void_p), hf.ctypes.data_as(C.c_void_p)),
+                  "column_elevation")
+        return hc, hf
+
     # -- forcing on a coarser grid (include/elmk.h: elmk_set_forcing_grid ...) -----------------------
     def set_forcing_grid(self, idx, w, ncells):
         """The per-column remap map (elmkernels_amd/regrid.py): idx int32 [npts, ncols] (-1 = padding, never in row 0), w float64
@@ -727,6 +776,23 @@ class ELMInterface:
 
     def series_record_times(self, slot0, rec_decday):
         self.S.series_record_times(slot0, rec_decday)
+
+    def set_column_elevation(self, topo_col, topo_forc=None):
+        """ELMState.set_column_elevation: each column's elevation and the forcing's surface height as it sees it (m)."""
+        self.S.set_column_elevation(topo_col, topo_forc)
+
+    def set_forcing_elevation_gridded(self, cells):
+        self.S.set_forcing_elevation_gridded(cells)
+
+    def set_downscaling(self, mode, lapse=LAPSE, lapse_lw=LAPSE_LW, lw_limit=LW_LIMIT):
+        """ELMState.set_downscaling: "topo" adjusts every step's forcing to the column elevations (after they are set)."""
+        self.S.set_downscaling(mode, lapse, lapse_lw, lw_limit)
+
+    def set_downscaling_groups(self, ptr, col, w):
+        self.S.set_downscaling_groups(ptr, col, w)
+
+    def clear_downscaling_groups(self):
+        self.S.clear_downscaling_groups()
 
     def set_forcing_grid(self, idx, w, ncells):
         """Forcing on the data set's own grid (ELMState.set_forcing_grid): then upload_gridded() per record, or reserve a run and

@@ -393,6 +393,60 @@ int elmk_set_forcing_record_time(elmk_ctx *ctx, double rec_decday);
 int elmk_series_record_times(elmk_ctx *ctx, int slot0, int nslots, const double *rec_decday /*[nslots]*/);
 int elmk_download_forcing_cosz(elmk_ctx *ctx, double *czf /*[ncols]*/);
 
+/* ---- downscaling -----------------------------------------------------------------------------
+ * Forcing from a coarse grid carries the near-surface air at the forcing's surface height.  TOPO mode adjusts it to each column's own
+ * elevation, as ELM's downscale_forcings (atm2lndMod) does.  With tg, pg, qg, Lg = tbot, pbot, qbot, lwrad exactly as get_forcing
+ * computes them (clamps, the RH conversion and the FLDS fallback included), prec the PREC record ProcessPREC reads, hc the column's
+ * elevation and hf the forcing's surface height as the column sees it (both in m), and RAIR, GRAV, CPAIR, TFRZ the constants of
+ * elm_constants.h, the forcing kernel evaluates, left to right and without contraction (exp: the host libm's bits, qsat: the
+ * reference's qsat_impl.hh; ZBOT = 30.0, ProcessZBOT's forc_hgt):
+ *   dz   = hc - hf
+ *   tc   = tg - lapse * dz
+ *   Hbot = RAIR * 0.5 * (tg + tc) / GRAV
+ *   pc   = pg * exp(-dz / Hbot)
+ *   thc  = tg + (tc - tg) * exp((ZBOT / Hbot) * (RAIR / CPAIR))        (the forcing's potential temperature is tg)
+ *   qc   = qg * (qs_c / qs_g)                                          (qs_g = qsat(tg, pg), qs_c = qsat(tc, pc): RH is kept)
+ *   Lc   = max(min(Lg - lapse_lw * dz, Lg * (1.0 + lw_limit)), Lg * (1.0 - lw_limit))    (std::min / std::max)
+ *   frac = min(1.0, max(0.0, (tc - TFRZ) * 0.5));  rain = frac * prec;  snow = (1.0 - frac) * prec
+ * and writes forc_tbot = tc, forc_thbot = thc, forc_pbot = pc, forc_qbot = qc, forc_lwrad = Lc, forc_rain, forc_snow.  Shortwave,
+ * wind and heights are unchanged (a COSZEN factor applies as it does without downscaling); forc_rho, po2, pco2 and vp are derived
+ * from these fields downstream, as always.  hc == hf gives exactly the bits of OFF (exp(-0.0) = 1, qs / qs = 1, and the group
+ * normalisation below is exactly 1): that is how a column is exempted.
+ * Longwave groups (optional; ELM's downscale_longwave): a CSR map by gridcell, group g owns terms ptr[g] .. ptr[g+1]-1, each a column
+ * col[p] with weight w[p].  Per group, with sums of one rounded product per term added in term order (as the output grid aggregates,
+ * regrid.apply_aggregate): W = sum w, A = sum w * Lg, S = sum w * Lc; norm = (W == 0 || A == 0) ? 1.0 : (A / W) / (S / W); then
+ * Lc = Lc * norm for every column of the group, so the group keeps its weighted mean longwave.  Columns of no group are not
+ * renormalised.  Groups lie inside one context: a decomposition must keep a gridcell's columns on one rank (not checked).
+ *   elmk_set_column_elevation   hc and hf, [ncols] each (copied).  topo_forc may be NULL: only hc is set (hf then comes from
+ *                               elmk_set_forcing_elevation_gridded).  ELMK_E_INVALID for a non-finite value.
+ *   elmk_set_forcing_elevation_gridded  hf from the forcing grid's surface height cells[ncells], remapped through the stored forcing
+ *                               map exactly as elmk_upload_gridded remaps (regrid.apply_map), kept in fp64.  ELMK_E_INVALID without
+ *                               a map or for a non-finite cell.  Clearing or replacing the map later leaves hf as it is.
+ *   elmk_set_downscaling        ELMK_DS_OFF (the default) or ELMK_DS_TOPO, with lapse (K/m), lapse_lw (W m-2 per m) and lw_limit;
+ *                               CLM5 / ELM's namelist values are 0.006, 0.032 and 0.5.  ELMK_E_INVALID: an unknown mode, TOPO before
+ *                               both hc and hf are set, a non-finite parameter, lapse < 0, lapse_lw < 0, lw_limit outside [0, 1).
+ *   elmk_set_downscaling_groups the groups (copied).  ELMK_E_INVALID as elmk_set_output_grid (ngroups outside 1 .. 2^31-1, ptr[0] != 0
+ *                               or decreasing, nnz outside 0 .. 2^31-1, col outside [0, ncols)), and for a column in more than one
+ *                               term, a weight not finite or negative.  Replaces earlier groups.
+ *   elmk_clear_downscaling_groups  no groups.
+ *   elmk_download_column_elevation  hc and / or hf (either pointer may be NULL); ELMK_E_INVALID for one not set.  Synchronises.
+ * Every setter refuses while the stream is being captured, waits for the runs in flight and drops the captured run step; a refusal
+ * enqueues nothing.  In TOPO mode elmk_get_forcing and every forcing kernel of elmk_run use the downscaling variant (per-column
+ * series or a forcing grid, REFERENCE or COSZEN shortwave), followed by one renormalisation launch while groups are set; a run gives
+ * the bits of the stepwise calls.  A context that never calls these runs the kernels, launch sequences and graphs it ran before and
+ * allocates nothing more.  Device memory (elmk_device_bytes): 2 x 8 bytes x elmk_level_stride for the elevations (first setter), and
+ * for groups 8 x (ngroups + 1) + 12 x nnz + 8 x ngroups + 8 x elmk_level_stride bytes (each region rounded up to 256).  The restart
+ * image does not change: elevations, mode and groups are driver setup.  libelmk_f32.so keeps the elevations and the downscaling
+ * arithmetic in fp64 and stores the results at state precision (report-only). */
+enum { ELMK_DS_OFF = 0, ELMK_DS_TOPO = 1 };
+int elmk_set_column_elevation(elmk_ctx *ctx, const double *topo_col /*[ncols]*/, const double *topo_forc /*[ncols] or NULL*/);
+int elmk_set_forcing_elevation_gridded(elmk_ctx *ctx, const double *cells /*[ncells]*/);
+int elmk_set_downscaling(elmk_ctx *ctx, int mode, double lapse, double lapse_lw, double lw_limit);
+int elmk_set_downscaling_groups(elmk_ctx *ctx, int64_t ngroups, const int64_t *ptr /*[ngroups+1]*/, const int32_t *col /*[nnz]*/,
+                                const double *w /*[nnz]*/);
+int elmk_clear_downscaling_groups(elmk_ctx *ctx);
+int elmk_download_column_elevation(elmk_ctx *ctx, double *topo_col /*[ncols] or NULL*/, double *topo_forc /*[ncols] or NULL*/);
+
 /* ---- output grid -----------------------------------------------------------------------------
  * The other direction: columns aggregated onto an output grid on the device (ELM's c2g, area-weighted means of the columns of each
  * grid cell; the land -> atmosphere map of a coupled run), so a driver downloads ncells values per field level instead of ncols.

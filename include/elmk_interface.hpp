@@ -217,6 +217,22 @@ class ELMInterface {
   void set_forcing_record_time(double rec_decday) { ok(elmk_set_forcing_record_time(ctx_, rec_decday)); }
   void series_record_times(int slot0, int nslots, const double* rec_decday) { ok(elmk_series_record_times(ctx_, slot0, nslots, rec_decday)); }
 
+  /* Downscaling (elmk_set_downscaling): ELMK_DS_TOPO adjusts every step's forcing from the forcing's surface height to each column's
+   * elevation (lapse-rate temperature, hydrostatic pressure, kept relative humidity, longwave, rain / snow split).  The elevations
+   * first: set_column_elevation() with both arrays, or with topo_forc = nullptr and then set_forcing_elevation_gridded() over the
+   * forcing grid.  Optional longwave groups (CSR by gridcell) keep each gridcell's weighted mean longwave. */
+  void set_column_elevation(const double* topo_col, const double* topo_forc) { ok(elmk_set_column_elevation(ctx_, topo_col, topo_forc)); }
+  void set_forcing_elevation_gridded(const double* cells) { ok(elmk_set_forcing_elevation_gridded(ctx_, cells)); }
+  void set_downscaling(int mode, double lapse = 0.006, double lapse_lw = 0.032, double lw_limit = 0.5)
+  {
+    ok(elmk_set_downscaling(ctx_, mode, lapse, lapse_lw, lw_limit));
+  }
+  void set_downscaling_groups(int64_t ngroups, const int64_t* ptr, const int32_t* col, const double* w)
+  {
+    ok(elmk_set_downscaling_groups(ctx_, ngroups, ptr, col, w));
+  }
+  void clear_downscaling_groups() { ok(elmk_clear_downscaling_groups(ctx_)); }
+
   /* History tapes (ELM's time-averaged output) kept on the device: register fields once, call accumulate_history() after every
    * advance(), read at the end of an output interval and reset the tape.  op: ELMK_HIST_AVG / _SUM / _MAX / _MIN / _INST;
    * history_add returns the entry id history_read takes.  history_read fills [ncols][nlev] doubles, the host layout of upload. */

@@ -1,0 +1,486 @@
+"""Downscaling of coarse-grid forcing to column elevation on the device (include/elmk.h "downscaling"): equal elevations give the
+bits of OFF, elmk_get_forcing in TOPO mode against elmkernels_amd/downscale.py (with the reference's own qsat), elmk_run against the
+stepwise calls (per-column series and a forcing grid, graph on and off), the physical properties of the adjusted fields, the snow a
+mountain column keeps, the refusals, an exact restart and the demo."""
+import ctypes as C
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from elmkernels_amd import _lib as L
+from elmkernels_amd import downscale as DSC
+from elmkernels_amd import regrid as RG
+from elmkernels_amd import state as st
+from tests import helpers as H
+from tests import test_gpu_run as GR
+
+pytestmark = pytest.mark.gpu
+
+DT = GR.DT
+ROOT = GR.ROOT
+NSTEPS = 24
+NREC = NSTEPS // 2 + 1  # GR.schedule: slot s // 2
+same = GR.same
+DS_FIELDS = ("forc_tbot", "forc_thbot", "forc_pbot", "forc_qbot", "forc_lwrad", "forc_rain", "forc_snow")
+KEPT_FIELDS = ("forc_solad", "forc_solai", "forc_u", "forc_v", "forc_hgt", "forc_hgt_u_patch", "forc_hgt_t_patch", "forc_hgt_q_patch")
+NLON, NLAT = 64, 32
+
+
+@pytest.fixture(scope="module")
+def base():
+    return GR._inputs(5003, 211, nrec=NREC)
+
+
+def _qsat():
+    """The reference's qsat (qsat_impl.hh) through oracle/_ref: (T, p) -> qs."""
+    from oracle import oracle as O
+
+    if not O.have_ref():
+        pytest.skip("oracle/_ref/libelmref.so not built (build() makes it where the reference is mounted)")
+    R = O.Reference()
+    return lambda T, p: R.qsat(T, p)[2]
+
+
+def _elevations(n, seed):
+    """hf: a forcing surface height per column; hc within +-1500 m of it, equal to it on every tenth column."""
+    rng = np.random.default_rng(seed)
+    hf = 200.0 + 1500.0 * rng.random(n)
+    hc = hf + rng.uniform(-1500.0, 1500.0, n)
+    hc[::10] = hf[::10]
+    return hc, hf
+
+
+def _groups(n, seed):
+    """regrid.owner_map with ~150 columns per group, 19 columns in no group and the last column a group of its own."""
+    cell = np.arange(n) // 150
+    cell[n - 20:n - 1] = -1
+    cell[n - 1] = cell.max() + 1
+    area = 0.5 + np.random.default_rng(seed).random(n)
+    return RG.owner_map(cell, area, int(cell.max()) + 1)
+
+
+def _col(D, k):
+    return D[k].reshape(-1).copy()
+
+
+def _forcing(D):
+    return {k: D[k] for k in DS_FIELDS + KEPT_FIELDS}
+
+
+def _topo_device(base, hc, hf, groups=None, graph=False, mode="topo"):
+    cols, scal, soil, lat, lon, rec = base
+    D = GR._device(cols, scal, soil, lat, lon)
+    D.set_graph(graph)
+    D.set_column_elevation(hc, hf)
+    if groups is not None:
+        D.set_downscaling_groups(*groups)
+    D.set_downscaling(mode)
+    return D
+
+
+@pytest.mark.parametrize("path", ["stepwise", "run_graph", "run"])
+def test_equal_elevations_give_the_bits_of_off(base, path):
+    """TOPO with topo_col == topo_forc (random heights) and longwave groups: every field, conservation and flag row of 24 steps has
+    the bits of OFF."""
+    cols = base[0]
+    n = cols["t_grnd"].shape[0]
+    h = 100.0 + 3000.0 * np.random.default_rng(5).random(n)
+    steps = GR.schedule(NSTEPS)
+    graph = path == "run_graph"
+    A = _topo_device(base, h, h, graph=graph, mode="off")
+    B = _topo_device(base, h, h, groups=_groups(n, 6), graph=graph)
+    if path == "stepwise":
+        GR.assert_same_rows(GR.stepwise(B, base[5], steps), GR.stepwise(A, base[5], steps))
+    else:
+        for D in (A, B):
+            D.run_reserve(NREC, NSTEPS)
+            GR.upload_series(D, base[5])
+            D.run(DT, steps)
+        GR.assert_same_rows(B.run_diagnostics(), A.run_diagnostics())
+    for name in A.fields:
+        assert same(A[name], B[name]), name
+    A.close()
+    B.close()
+
+
+@pytest.mark.parametrize("grid,rh,sw,groups", [
+    (False, False, "reference", False),
+    (False, False, "reference", True),
+    (False, True, "coszen", True),
+    (False, True, "reference", False),
+    (True, False, "coszen", False),
+    (True, True, "reference", True),
+    (True, False, "reference", True),
+])
+def test_stepwise_matches_the_host_restatement(base, grid, rh, sw, groups):
+    """elmk_get_forcing in TOPO mode writes, bit for bit, downscale.py applied to the same step's OFF values; shortwave, wind and
+    heights keep the OFF bits.  Grid: the records and hf come through a bilinear forcing grid (hf by
+    elmk_set_forcing_elevation_gridded, bit for bit regrid.apply_map)."""
+    qsat = _qsat()
+    cols, scal, soil, lat, lon, rec = base
+    n = cols["t_grnd"].shape[0]
+    rng = np.random.default_rng(17)
+    hc, hf = _elevations(n, 18)
+    D = GR._device(cols, scal, soil, lat, lon)
+    if grid:
+        ncells = NLON * NLAT
+        idx, w = RG.bilinear_map(np.degrees(lat), np.degrees(lon), NLON, NLAT)
+        cells = GR._inputs(ncells, 112, nrec=2)[-1]
+        D.set_forcing_grid(idx, w, ncells)
+        for k in st.SERIES_FORCING:
+            D.upload_gridded(k, cells[k][0], level=0)
+            D.upload_gridded(k, cells[k][1], level=1)
+        hcells = 200.0 + 1500.0 * rng.random(ncells)
+        D.set_column_elevation(hc)
+        D.set_forcing_elevation_gridded(hcells)
+        hf = RG.apply_map(idx, w, hcells)
+    else:
+        D.set_column_elevation(hc, hf)
+        for k in st.SERIES_FORCING:
+            D.upload(k, np.stack([rec[k][0], rec[k][1]], axis=1))
+    got_hc, got_hf = D.column_elevation()
+    assert same(got_hc, hc) and same(got_hf, hf)
+    D.solar_geometry(DT, 172.3, 171)
+    if sw == "coszen":
+        D.set_shortwave_mode("coszen", 3 * 3600.0)
+        D.set_forcing_record_time(172.25)
+    wt = rng.random(8)
+    st.get_forcing(D, 1.0 - wt, wt, rh)
+    off = _forcing(D)
+    prec = D["atm_prec"][:, 0].copy()
+    G = _groups(n, 19) if groups else None
+    if G is not None:
+        D.set_downscaling_groups(*G)
+    D.set_downscaling("topo")
+    st.get_forcing(D, 1.0 - wt, wt, rh)
+    got = _forcing(D)
+    want = DSC.downscale_forcing(off, prec, hc, hf, qsat, groups=G)
+    for k in DS_FIELDS:
+        assert same(got[k], want[k]), k
+    for k in KEPT_FIELDS:
+        assert same(got[k], off[k]), k
+    moved = hc != hf
+    assert (got["forc_tbot"][moved] != off["forc_tbot"][moved]).all()
+    assert same(got["forc_tbot"][~moved], off["forc_tbot"][~moved])
+    if G is not None:  # the single-column group gives back Lg (to rounding)
+        c = n - 1
+        assert abs(got["forc_lwrad"][c] - off["forc_lwrad"][c]) <= 4 * np.spacing(off["forc_lwrad"][c])
+    D.close()
+
+
+@pytest.mark.parametrize("grid", [False, True])
+@pytest.mark.parametrize("graph", [True, False])
+def test_run_equals_stepwise(base, grid, graph):
+    """24 TOPO steps with longwave groups as one elmk_run against the stepwise calls: every field, conservation and flag row bit for
+    bit; over per-column series, and over cell series of a bilinear forcing grid with hf from the grid."""
+    cols, scal, soil, lat, lon, rec = base
+    n = cols["t_grnd"].shape[0]
+    hc, hf = _elevations(n, 21)
+    G = _groups(n, 22)
+    steps = GR.schedule(NSTEPS)
+    if not grid:
+        A = _topo_device(base, hc, hf, G, graph)
+        B = _topo_device(base, hc, hf, G, graph)
+        want = GR.stepwise(A, rec, steps)
+        B.run_reserve(NREC, NSTEPS)
+        GR.upload_series(B, rec)
+    else:
+        ncells = NLON * NLAT
+        idx, w = RG.bilinear_map(np.degrees(lat), np.degrees(lon), NLON, NLAT)
+        cells = {k: v for k, v in GR._inputs(ncells, 113, nrec=NREC)[-1].items() if k in st.SERIES_FORCING}
+        hcells = 200.0 + 1500.0 * np.random.default_rng(23).random(ncells)
+        rec_cols = dict(rec)
+        for k in st.SERIES_FORCING:
+            rec_cols[k] = RG.apply_map(idx, w, cells[k])
+        A = _topo_device(base, hc, RG.apply_map(idx, w, hcells), G, graph)
+        want = GR.stepwise(A, rec_cols, steps)
+        B = GR._device(cols, scal, soil, lat, lon)
+        B.set_graph(graph)
+        B.set_forcing_grid(idx, w, ncells)
+        B.set_column_elevation(hc)
+        B.set_forcing_elevation_gridded(hcells)
+        B.set_downscaling_groups(*G)
+        B.set_downscaling("topo")
+        B.run_reserve(NREC, NSTEPS)
+        for k in st.SERIES_FORCING:
+            B.series_upload(k, 0, cells[k])
+        for k in st.SERIES_PHENOLOGY:
+            B.series_upload(k, 0, rec[k])
+    B.run(DT, steps)
+    GR.assert_same_rows(B.run_diagnostics(), want)
+    for name in A.fields:
+        if name not in GR.SERIES:
+            assert same(A[name], B[name]), name
+    A.close()
+    B.close()
+
+
+def test_physical_properties(base):
+    """On the device's output: tc - tg = -lapse dz to rounding, relative humidity kept (qc / qs_c = qg / qs_g to 1e-15), rain + snow
+    = prec to 1 ulp (2 ulp at most, the split's roundings), Lc inside the lw_limit band without groups, and with groups each group's weighted mean of Lc that of Lg to 1e-13."""
+    qsat = _qsat()
+    cols, scal, soil, lat, lon, rec = base
+    n = cols["t_grnd"].shape[0]
+    hc, hf = _elevations(n, 31)
+    G = _groups(n, 32)
+    lapse, lapse_lw, lw_limit = 0.0065, 0.05, 0.3
+    D = GR._device(cols, scal, soil, lat, lon)
+    D.set_column_elevation(hc, hf)
+    for k in st.SERIES_FORCING:
+        D.upload(k, np.stack([rec[k][0], rec[k][1]], axis=1))
+    D.solar_geometry(DT, 172.3, 171)
+    wt = np.full(8, 0.4)
+    st.get_forcing(D, 1.0 - wt, wt, False)
+    off = _forcing(D)
+    prec = np.maximum(D["atm_prec"][:, 0], 0.0)
+    D.set_downscaling("topo", lapse, lapse_lw, lw_limit)
+    st.get_forcing(D, 1.0 - wt, wt, False)
+    got = _forcing(D)
+    dz = hc - hf
+    tg, tc = off["forc_tbot"], got["forc_tbot"]
+    assert (np.abs((tc - tg) + lapse * dz) <= 2 * np.spacing(tg)).all()
+    qg, qc = off["forc_qbot"], got["forc_qbot"]
+    rh_g = qg / qsat(tg, off["forc_pbot"])
+    rh_c = qc / qsat(tc, got["forc_pbot"])
+    assert (np.abs(rh_c - rh_g) <= 1e-15 * rh_g).all()
+    tot = got["forc_rain"] + got["forc_snow"]  # three roundings in the split and one in this sum
+    assert (np.abs(tot - prec) <= 2 * np.spacing(prec)).all()
+    assert (np.abs(tot - prec) <= np.spacing(prec)).mean() > 0.99
+    lg, lc = off["forc_lwrad"], got["forc_lwrad"]
+    assert (lc >= lg * (1.0 - lw_limit)).all() and (lc <= lg * (1.0 + lw_limit)).all()
+    assert (got["forc_pbot"][dz > 0] < off["forc_pbot"][dz > 0]).all() and (got["forc_pbot"][dz < 0] > off["forc_pbot"][dz < 0]).all()
+    D.set_downscaling_groups(*G)
+    st.get_forcing(D, 1.0 - wt, wt, False)
+    lcn = _col(D, "forc_lwrad")
+    ptr, col, w = G
+    ones = np.ones(n)
+    mean_g = RG.apply_aggregate(ptr, col, w, lg, 0.0) / RG.apply_aggregate(ptr, col, w, ones, 0.0)
+    mean_c = RG.apply_aggregate(ptr, col, w, lcn, 0.0) / RG.apply_aggregate(ptr, col, w, ones, 0.0)
+    assert (np.abs(mean_c - mean_g) <= 1e-13 * mean_g).all()
+    free = np.setdiff1d(np.arange(n), col)
+    assert free.size == 19 and same(lcn[free], lc[free])  # columns of no group are not renormalised
+    D.close()
+
+
+def _snow_case(n, seed, nrec=25):
+    """Identical columns (the state of one synthetic column, one position) under identical near-freezing records: 275 K, wet,
+    at night; even columns at the cell's surface height (800 m), odd columns 1 500 m above it."""
+    cols, scal, soil, lat, lon, rec = GR._inputs(n, seed, nrec=nrec)
+    cols = {k: np.repeat(v[:1], n, axis=0) for k, v in cols.items()}
+    lat, lon = np.full(n, lat[0]), np.full(n, lon[0])
+    const = {"atm_tbot": 275.0, "atm_pbot": 85000.0, "atm_qbot": 0.004, "atm_flds": 300.0, "atm_fsds": 0.0, "atm_prec": 1.0e-3,
+             "atm_wind": 3.0}
+    for k in st.SERIES_FORCING:
+        rec[k] = np.full((nrec, n), const[k])
+    for k in st.SERIES_PHENOLOGY:
+        rec[k] = np.repeat(rec[k][:, :1], n, axis=1)
+    hf = np.full(n, 800.0)
+    hc = np.where(np.arange(n) % 2 == 0, 800.0, 2300.0)
+    return (cols, scal, soil, lat, lon, rec), hc, hf
+
+
+def test_mountain_columns_keep_more_snow():
+    """48 steps of near-freezing forcing from one cell: columns 1 500 m above the cell's surface end with more h2osno than columns at
+    its height in TOPO mode (their precipitation falls as snow); with downscaling OFF every column ends alike."""
+    n = 256
+    case, hc, hf = _snow_case(n, 301)
+    out = {}
+    for mode in ("off", "topo"):
+        D = _topo_device(case, hc, hf, graph=True, mode=mode)
+        D.run_reserve(25, 48)
+        GR.upload_series(D, case[5])
+        D.run(DT, GR.schedule(48))
+        out[mode] = _col(D, "h2osno")
+        D.close()
+    valley, mountain = slice(0, None, 2), slice(1, None, 2)
+    h = out["off"]
+    assert (h == h[0]).all()
+    h = out["topo"]
+    assert (h[mountain] > h[valley]).all() and (h[mountain] > out["off"][mountain]).all(), (h[valley][:3], h[mountain][:3])
+
+
+def _hip():
+    return GR._hip_runtime()
+
+
+def test_refusals_enqueue_nothing(base):
+    """Every refusal is ELMK_E_INVALID and leaves the context as a twin that made only the valid calls: the same forcing bits after a
+    TOPO step and the same device bytes.  A context that never downscales allocates nothing more."""
+    cols, scal, soil, lat, lon, rec = base
+    n = cols["t_grnd"].shape[0]
+    hc, hf = _elevations(n, 41)
+    G = _groups(n, 42)
+    A = GR._device(cols, scal, soil, lat, lon)  # refusals
+    B = GR._device(cols, scal, soil, lat, lon)  # twin
+    bytes0 = A.device_bytes
+
+    def P(a):
+        return np.ascontiguousarray(a).ctypes.data_as(C.c_void_p)
+
+    def rc(f, *a):
+        return getattr(A.lib, f)(A.ctx, *a)
+
+    good = (0.006, 0.032, 0.5)
+    assert rc("elmk_set_downscaling", 1, *good) == -1  # no elevations
+    assert rc("elmk_set_forcing_elevation_gridded", P(np.zeros(8))) == -1  # no forcing map
+    bad_hc = hc.copy()
+    bad_hc[7] = np.nan
+    assert rc("elmk_set_column_elevation", P(bad_hc), P(hf)) == -1
+    bad_hf = hf.copy()
+    bad_hf[3] = np.inf
+    assert rc("elmk_set_column_elevation", P(hc), P(bad_hf)) == -1
+    assert rc("elmk_set_column_elevation", None, P(hf)) == -1
+    assert A.device_bytes == bytes0
+    A.set_column_elevation(hc)  # hc only: TOPO still refused
+    assert rc("elmk_set_downscaling", 1, *good) == -1
+    A.set_column_elevation(hc, hf)
+    for mode, p in [(2, good), (-1, good), (1, (np.nan, 0.032, 0.5)), (1, (0.006, np.inf, 0.5)), (1, (0.006, 0.032, np.nan)),
+                    (1, (-1e-3, 0.032, 0.5)), (1, (0.006, -1e-3, 0.5)), (1, (0.006, 0.032, -0.1)), (1, (0.006, 0.032, 1.0))]:
+        assert rc("elmk_set_downscaling", mode, *p) == -1, (mode, p)
+    ptr, col, w = G
+    ptr = np.ascontiguousarray(ptr, np.int64)
+    col = np.ascontiguousarray(col, np.int32)
+    w = np.ascontiguousarray(w, np.float64)
+
+    def groups_rc(p, c, ww, ng=None):
+        return rc("elmk_set_downscaling_groups", C.c_int64(p.size - 1 if ng is None else ng), P(p), P(c), P(ww))
+
+    c2 = col.copy()
+    c2[200] = c2[10]  # a column in two groups
+    assert groups_rc(ptr, c2, w) == -1
+    for v in (-0.1, np.nan, np.inf):
+        w2 = w.copy()
+        w2[5] = v
+        assert groups_rc(ptr, col, w2) == -1, v
+    for v in (-1, n):
+        c3 = col.copy()
+        c3[3] = v
+        assert groups_rc(ptr, c3, w) == -1, v
+    p2 = ptr.copy()
+    p2[0] = 1
+    assert groups_rc(p2, col, w) == -1
+    p3 = ptr.copy()
+    p3[2] = p3[1] - 1
+    assert groups_rc(p3, col, w) == -1
+    assert groups_rc(ptr, col, w, ng=0) == -1
+    # valid calls, then refusals under capture of each setter
+    A.set_downscaling_groups(*G)
+    A.set_downscaling("topo", 0.0065, 0.04, 0.4)
+    hip = _hip()
+    strm, graph = C.c_void_p(), C.c_void_p()
+    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
+    A.set_stream(strm.value)
+    assert hip.hipStreamBeginCapture(strm, 1) == 0
+    refused = [rc("elmk_set_column_elevation", P(hf), P(hc)) == -1,
+               rc("elmk_set_downscaling", 0, *good) == -1,
+               rc("elmk_set_downscaling_groups", C.c_int64(1), P(np.array([0, 1], np.int64)), P(np.array([0], np.int32)), P(np.ones(1))) == -1,
+               rc("elmk_clear_downscaling_groups") == -1,
+               rc("elmk_download_column_elevation", P(np.zeros(n)), None) == -1]
+    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    assert all(refused), refused
+    if graph.value:
+        hip.hipGraphDestroy(graph)
+    A.set_stream(None)
+    hip.hipStreamDestroy(strm)
+    # the twin
+    B.set_column_elevation(hc, hf)
+    B.set_downscaling_groups(*G)
+    B.set_downscaling("topo", 0.0065, 0.04, 0.4)
+    assert A.device_bytes == B.device_bytes > bytes0
+    for D in (A, B):
+        for k in st.SERIES_FORCING:
+            D.upload(k, np.stack([rec[k][0], rec[k][1]], axis=1))
+        D.solar_geometry(DT, 172.3, 171)
+        st.get_forcing(D, np.full(8, 0.5), np.full(8, 0.5), False)
+    for name in A.fields:
+        assert same(A[name], B[name]), name
+    A.close()
+    B.close()
+
+
+def test_exact_restart_in_topo_mode(base):
+    """N steps, save, load into a fresh context with the same downscaling setup, N steps: the bits of 2N steps."""
+    from elmkernels_amd import restart as RS
+    from tests.test_gpu_restart import _poison
+
+    cols, scal, soil, lat, lon, rec = base
+    n = cols["t_grnd"].shape[0]
+    hc, hf = _elevations(n, 51)
+    G = _groups(n, 52)
+    steps = GR.schedule(NSTEPS)
+    half = NSTEPS // 2
+    A = _topo_device(base, hc, hf, G, graph=True)
+    A.run_reserve(NREC, NSTEPS)
+    GR.upload_series(A, rec)
+    A.run(DT, steps)
+    B = _topo_device(base, hc, hf, G, graph=True)
+    B.run_reserve(NREC, NSTEPS)
+    GR.upload_series(B, rec)
+    B.run(DT, steps[:half])
+    img = B.restart_save()
+    B.close()
+    RS.verify(img)
+    Cx = GR._device(cols, scal, soil, lat, lon)
+    Cx.set_graph(True)
+    _poison(Cx)
+    Cx.set_column_elevation(hc, hf)
+    Cx.set_downscaling_groups(*G)
+    Cx.set_downscaling("topo")
+    Cx.run_reserve(NREC, NSTEPS)
+    Cx.restart_load(img)
+    GR.upload_series(Cx, rec)
+    Cx.run(DT, steps[half:])
+    for name in A.fields:
+        if name not in GR.SERIES:
+            assert same(A[name], Cx[name]), name
+    A.close()
+    Cx.close()
+
+
+def test_downscaling_demo(tmp_path):
+    """examples/downscaling_demo.cc compiles with g++ against the C ABI and runs a day of valley and mountain columns in one forcing
+    cell: with downscaling OFF they end alike, in TOPO mode the mountain is colder and keeps more snow."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    libdir = os.path.dirname(L.LIB_PATH)
+    exe = str(tmp_path / "downscaling_demo")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "downscaling_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
+    n = 512
+    (cols, scal, soil, lat, lon, rec), hc, hf = _snow_case(n, 311)
+    S = H.oracle_state(cols, scal, soil)
+    blob = [struct.pack("<q", n)]
+
+    def put(name, kind, arr):
+        a = np.ascontiguousarray(arr)
+        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
+
+    for k, v in S.fields.items():
+        if k != "err_flags":
+            put(k, 0, v)
+    sc = S.scalars
+    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
+    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
+    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
+        put(k, 1, getattr(S, k))
+    for i, name in enumerate(L.SNICAR_NAMES):
+        put(f"snicar/{i}", 1, S.snicar[name])
+    put("age_tau", 1, S.snowage[0])
+    put("age_kappa", 1, S.snowage[1])
+    put("age_drdt0", 1, S.snowage[2])
+    put("lat", 1, lat)
+    put("lon", 1, lon)
+    for k in GR.SERIES:
+        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
+    put("topo", 1, hc)
+    put("hf", 1, hf[:1])
+    put("steps", 1, GR.schedule(48))
+    (tmp_path / "state.bin").write_bytes(b"".join(blob))
+    out = subprocess.run([exe, str(tmp_path / "state.bin")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout + out.stderr
+    print(out.stdout)
+    assert "off: valley and mountain alike" in out.stdout and "topo: more snow on the mountain" in out.stdout, out.stdout
