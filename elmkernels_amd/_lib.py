@@ -108,6 +108,11 @@ SIGNATURES = {
     "elmk_restart_size": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "elmk_restart_save": (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
     "elmk_restart_load": (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
+    "elmk_accum_add": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "elmk_accum_init": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
+    "elmk_accum_update": (C.c_int, [_P]),
+    "elmk_accum_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    "elmk_accum_clear": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

@@ -123,7 +123,7 @@ struct GraphSlot {
   hipGraphExec_t exec = nullptr;
   double dt = 0.0;
   hipStream_t stream = nullptr;
-  uint64_t tag = 0;  // what else the captured launches depend on (elmk_run: its flags and the history table's version)
+  uint64_t tag = 0;  // what else the captured launches depend on (elmk_run: its flags and the history and accumulator tables' versions)
   void drop()  // (nothing may still run it)
   {
     if (exec) (void)hipGraphExecDestroy(exec);
@@ -188,6 +188,18 @@ struct elmk_ctx {
   DevBuf<HistRow> hist_table;
   bool hist_dirty[ELMK_HIST_MAX_TAPES] = {};
   uint64_t hist_version = 0;  // counts elmk_history_add / _clear: a captured step of elmk_run holds the table of its moment
+  // accumulated fields (elmk_accum_*): the entries, their rows as the device table k_accum_update reads (accum_table: the rows, then
+  // one step count per entry), and the bytes of the table and of every value buffer (elmk_device_bytes)
+  struct AccumEntry {
+    int src, kind, dst, nlev, row0;
+    int64_t period;
+    DevBuf<double> val;
+  };
+  std::vector<AccumEntry> accum;
+  std::vector<AccumRow> accum_rows;
+  DevBuf<char> accum_table;
+  size_t accum_bytes = 0;
+  uint64_t accum_version = 0;  // counts elmk_accum_add / _clear, as hist_version
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
@@ -341,6 +353,7 @@ int enter(elmk_ctx* ctx)
 }
 
 bool field_ok(int f) { return f >= 0 && f < ELMK_NUM_FIELDS; }
+int field_class(int f);  // include/elmk_restart.def (defined with the restart images)
 
 }  // namespace
 
@@ -557,7 +570,7 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
   return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
                          ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes + ctx->sw.czf_bytes + ctx->run.rec_bytes +
-                         ctx->ds.topo_bytes + ctx->ds.gbytes)
+                         ctx->ds.topo_bytes + ctx->ds.gbytes + ctx->accum_bytes)
              : -1;
 }
 
@@ -1142,10 +1155,177 @@ int elmk_history_clear(elmk_ctx* ctx)
   return ELMK_OK;
 }
 
+}  // extern "C" (the launch machinery below has templates)
+
+// ---------------------------------------------------------------------------------------------------
+// accumulated fields (k_accum.hip; include/elmk.h "accumulated fields")
+// ---------------------------------------------------------------------------------------------------
+namespace {
+constexpr int ACCUM_MAX_ROWS = ELMK_ACCUM_MAX_ENTRIES * MAXLEV_STAGE;
+constexpr size_t ACCUM_COUNTS_OFF = ((size_t)ACCUM_MAX_ROWS * sizeof(AccumRow) + 255) / 256 * 256;
+constexpr size_t ACCUM_TABLE_BYTES = ACCUM_COUNTS_OFF + 256;
+static_assert(ELMK_ACCUM_MAX_ENTRIES * sizeof(unsigned long long) <= 256, "the counts fit behind the rows");
+
+unsigned long long* accum_counts(elmk_ctx* ctx) { return (unsigned long long*)((char*)ctx->accum_table + ACCUM_COUNTS_OFF); }
+size_t accum_val_bytes(const elmk_ctx* ctx, int nlev) { return align_up((size_t)nlev * (size_t)ctx->ld * sizeof(double), 256); }
+
+// every row of every entry, then the counts (two launches; nothing without entries)
+void accum_update_launch(elmk_ctx* ctx)
+{
+  launch_accum_update((const AccumRow*)(char*)ctx->accum_table, (int)ctx->accum_rows.size(), accum_counts(ctx), (int)ctx->accum.size(),
+                      ctx->ncols, ctx->stream);
+}
+}  // namespace
+
+extern "C" {
+
+int elmk_accum_add(elmk_ctx* ctx, int src_field, int kind, int64_t period_steps, int dst_field)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!field_ok(src_field)) return invalid(ctx, "elmk_accum_add: unknown source field");
+  if (kind < ELMK_ACCUM_RUNMEAN || kind > ELMK_ACCUM_RUNACCUM) return invalid(ctx, "elmk_accum_add: unknown kind");
+  if (period_steps < 1) return invalid(ctx, "elmk_accum_add: the period must be at least one step");
+  const int nlev = g_fields[src_field].nlev;
+  if (dst_field != -1) {
+    if (!field_ok(dst_field)) return invalid(ctx, "elmk_accum_add: unknown destination field");
+    if (g_fields[dst_field].dtype != ELMK_F64 || g_fields[dst_field].nlev != nlev)
+      return invalid(ctx, "elmk_accum_add: the destination must be an F64 field of the source's levels");
+    if (field_class(dst_field) != ELMK_CLASS_SURFACE)
+      return invalid(ctx, "elmk_accum_add: the destination must be of class SURFACE (no kernel of the step may write it)");
+    if (dst_field == src_field) return invalid(ctx, "elmk_accum_add: the destination is the entry's own source");
+    for (const elmk_ctx::AccumEntry& e : ctx->accum) {
+      if (e.dst == dst_field) return invalid(ctx, "elmk_accum_add: the field is the destination of another entry");
+      // all rows run in one launch: a row reading what another row writes would see old or new values, element by element
+      if (e.src == dst_field) return invalid(ctx, "elmk_accum_add: the destination is the source of another entry");
+    }
+  }
+  for (const elmk_ctx::AccumEntry& e : ctx->accum)
+    if (e.dst == src_field) return invalid(ctx, "elmk_accum_add: the source is the destination of another entry");
+  if ((int)ctx->accum.size() >= ELMK_ACCUM_MAX_ENTRIES) return invalid(ctx, "elmk_accum_add: the accumulator table is full");
+  if (int rc = refuse_capture(ctx, "elmk_accum_add: the stream is being captured")) return rc;
+  const bool first = !ctx->accum_table;
+  if (first) {
+    if (hip_fail(ctx, ctx->accum_table.alloc(ACCUM_TABLE_BYTES), "hipMalloc(accumulator table)")) return ELMK_E_NOMEM;
+    if (hip_fail(ctx, hipMemsetAsync(ctx->accum_table, 0, ACCUM_TABLE_BYTES, ctx->stream), "hipMemset(accumulator table)")) {
+      (void)hipStreamSynchronize(ctx->stream);
+      (void)ctx->accum_table.reset();
+      return ELMK_E_HIP;
+    }
+  }
+  const size_t bytes = (size_t)nlev * (size_t)ctx->ld * sizeof(double);
+  DevBuf<double> val;
+  if (hip_fail(ctx, val.alloc(bytes), "hipMalloc(accumulator)")) {
+    if (first) (void)ctx->accum_table.reset();  // the table is held exactly while entries exist
+    return ELMK_E_NOMEM;
+  }
+  const int entry = (int)ctx->accum.size(), row0 = (int)ctx->accum_rows.size();
+  const int ses = store_size(g_fields[src_field].dtype);
+  for (int l = 0; l < nlev; l++) {
+    const size_t row = (size_t)l * (size_t)ctx->ld;
+    ctx->accum_rows.push_back(AccumRow{(const char*)ctx->fptr[src_field] + row * ses, val + row,
+                                       dst_field >= 0 ? (char*)ctx->fptr[dst_field] + row * store_size(ELMK_F64) : nullptr, period_steps,
+                                       store_dtype(g_fields[src_field].dtype), kind, entry, kStateF32 ? 1 : 0});
+  }
+  // the stream may still run an update that reads the table: the copies are ordered after it; pageable source, so wait
+  const unsigned long long zero = 0;
+  hipError_t e = hipMemsetAsync(val, 0, bytes, ctx->stream);
+  if (!e) e = hipMemcpyAsync((AccumRow*)(char*)ctx->accum_table + row0, &ctx->accum_rows[row0], (size_t)nlev * sizeof(AccumRow),
+                             hipMemcpyHostToDevice, ctx->stream);
+  if (!e) e = hipMemcpyAsync(accum_counts(ctx) + entry, &zero, sizeof zero, hipMemcpyHostToDevice, ctx->stream);
+  if (!e) e = hipStreamSynchronize(ctx->stream);
+  if (hip_fail(ctx, e, "elmk_accum_add")) {
+    ctx->accum_rows.resize(row0);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (first) (void)ctx->accum_table.reset();
+    return ELMK_E_HIP;  // (frees val)
+  }
+  ctx->accum.push_back(elmk_ctx::AccumEntry{src_field, kind, dst_field, nlev, row0, period_steps, std::move(val)});
+  ctx->accum_bytes += accum_val_bytes(ctx, nlev) + (first ? ACCUM_TABLE_BYTES : 0);
+  ctx->accum_version++;
+  return entry;
+}
+
+int elmk_accum_init(elmk_ctx* ctx, int entry, const double* host, int64_t nsteps)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (entry < 0 || entry >= (int)ctx->accum.size()) return invalid(ctx, "elmk_accum_init: unknown entry");
+  if (nsteps < 0) return invalid(ctx, "elmk_accum_init: nsteps must not be negative");
+  const elmk_ctx::AccumEntry& e = ctx->accum[entry];
+  if (!host && e.dst < 0) return invalid(ctx, "elmk_accum_init: no host values and no destination field to seed from");
+  if (int rc = refuse_capture(ctx, "elmk_accum_init: the stream is being captured")) return rc;
+  if (host) {
+    if (ctx->ncols > 0)
+      HIPCHK(hipMemcpy2DAsync(e.val, (size_t)ctx->ld * sizeof(double), host, (size_t)ctx->ncols * sizeof(double),
+                              (size_t)ctx->ncols * sizeof(double), (size_t)e.nlev, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    launch_accum_seed(ctx->fptr[e.dst], store_dtype(ELMK_F64), e.val, e.nlev, ctx->ld, ctx->ncols, ctx->stream);
+    HIPCHK(hipGetLastError());
+  }
+  const unsigned long long n = (unsigned long long)nsteps;
+  HIPCHK(hipMemcpyAsync(accum_counts(ctx) + entry, &n, sizeof n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+int elmk_accum_update(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (ctx->accum.empty()) return ELMK_OK;
+  accum_update_launch(ctx);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_accum_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int64_t n, int layout, int64_t* nsteps)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (entry < 0 || entry >= (int)ctx->accum.size()) return invalid(ctx, "elmk_accum_read: unknown entry");
+  if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols) return invalid(ctx, "elmk_accum_read: bad column range");
+  if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_accum_read: unknown layout");
+  if (int rc = refuse_capture(ctx, "elmk_accum_read: the stream is being captured")) return rc;
+  const elmk_ctx::AccumEntry& e = ctx->accum[entry];
+  unsigned long long cnt = 0;
+  HIPCHK(hipMemcpyAsync(&cnt, accum_counts(ctx) + entry, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+  if (n > 0 && (layout == ELMK_LAYOUT_SOA || e.nlev == 1)) {
+    HIPCHK(hipMemcpy2DAsync(host, (size_t)n * sizeof(double), e.val + col0, (size_t)ctx->ld * sizeof(double), (size_t)n * sizeof(double),
+                            (size_t)e.nlev, hipMemcpyDeviceToHost, ctx->stream));
+  } else if (n > 0) {
+    // reference layout [col][lev]: through the device staging buffer in chunks of whole 64-column tiles, as elmk_download
+    const int64_t chunk = (int64_t)(ctx->staging_bytes / ((size_t)e.nlev * sizeof(double))) / 64 * 64;
+    if (chunk <= 0) return invalid(ctx, "staging buffer too small");
+    for (int64_t done = 0; done < n; done += chunk) {
+      const int64_t m = (n - done) < chunk ? (n - done) : chunk;
+      launch_soa_to_cols(e.val, ctx->staging, 8, e.nlev, ctx->ld, col0 + done, m, ctx->stream);
+      HIPCHK(hipMemcpyAsync(host + (size_t)done * e.nlev, ctx->staging, (size_t)m * e.nlev * sizeof(double), hipMemcpyDeviceToHost,
+                            ctx->stream));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(ctx->stream));  // staging is reused by the next chunk
+    }
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (nsteps) *nsteps = (int64_t)cnt;
+  return ELMK_OK;
+}
+
+int elmk_accum_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_accum_clear: the stream is being captured")) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (ctx->accum.empty()) return ELMK_OK;
+  ctx->accum.clear();
+  ctx->accum_rows.clear();
+  HIPCHK(ctx->accum_table.reset());
+  ctx->accum_bytes = 0;
+  ctx->accum_version++;
+  return ELMK_OK;
+}
+
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------------
 // physics wrappers: one launch each, same order/arguments as driver/kokkos
 // ---------------------------------------------------------------------------------------------------
-}  // extern "C" (the launch machinery below has templates)
 
 namespace {
 int heal_lists(elmk_ctx* ctx)
@@ -1560,6 +1740,10 @@ void run_flag_reduce(elmk_ctx* ctx, double)
   const elmk_ctx::Run& R = ctx->run;
   launch_flag_reduce_run((const uint32_t*)ctx->fptr[ELMK_FIELD_err_flags], ctx->ncols, R.flag_or, R.flag_first, R.cursor, ctx->stream);
 }
+void run_accum(elmk_ctx* ctx, double)
+{
+  if (ctx->run.flags & ELMK_RUN_ACCUM) accum_update_launch(ctx);
+}
 void run_history(elmk_ctx* ctx, double)
 {
   if ((ctx->run.flags & ELMK_RUN_HISTORY) && !ctx->hist.empty()) hist_accumulate_launch(ctx);
@@ -1567,10 +1751,12 @@ void run_history(elmk_ctx* ctx, double)
 void run_next(elmk_ctx* ctx, double) { launch_run_next(ctx->run.cursor, ctx->stream); }
 
 // one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
-// forcing, init_timestep, advance_physics' stages, conservation -> ring row, flag summary -> ring row, history, next row
+// forcing, init_timestep, advance_physics' stages, conservation -> ring row, flag summary -> ring row, accumulated fields, history,
+// next row
 constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},   {run_forcing, nullptr}, {run_init_timestep, nullptr},
                               ADVANCE[0], ADVANCE[1], ADVANCE[2], ADVANCE[3], ADVANCE[4], ADVANCE[5], ADVANCE[6], ADVANCE[7],
-                              {run_conservation, nullptr},   {run_flag_reduce, nullptr}, {run_history, nullptr}, {run_next, nullptr}};
+                              {run_conservation, nullptr},   {run_flag_reduce, nullptr}, {run_accum, nullptr},   {run_history, nullptr},
+                              {run_next, nullptr}};
 static_assert(sizeof ADVANCE / sizeof ADVANCE[0] == 8, "RUN_STEP holds every stage of ADVANCE");
 }  // namespace
 
@@ -1666,7 +1852,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   if (!ctx->snowage_set) return invalid(ctx, "elmk_run: the snow-age tables are not set (elmk_set_snow_age_tables)");
   if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
   if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
-  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY)) return invalid(ctx, "elmk_run: unknown flags");
+  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM)) return invalid(ctx, "elmk_run: unknown flags");
+  if ((flags & ELMK_RUN_ACCUM) && ctx->accum.empty()) return invalid(ctx, "elmk_run: ELMK_RUN_ACCUM without an accumulator entry (elmk_accum_add)");
   const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   int lo = R.slots, hi = -1;
   unsigned months = 0;
@@ -1716,7 +1903,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.last_buf = buf;
   R.last_nsteps = nsteps;
   const uint64_t tag = (uint64_t)flags | ((uint64_t)(ds_topo(ctx) && ctx->ds.gmem) << 5) | ((uint64_t)ds_topo(ctx) << 6) |
-                       ((uint64_t)cz << 7) | (ctx->hist_version << 8);
+                       ((uint64_t)cz << 7) | ((ctx->hist_version & 0xFFFFFFFull) << 8) |  // bits 8..35 and 36..63: the tables'
+                       ((ctx->accum_version & 0xFFFFFFFull) << 36);                       // versions, 28 bits each
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;
@@ -2355,6 +2543,7 @@ constexpr bool every_field_classified()
   return g_class.listed == ELMK_NUM_FIELDS;
 }
 static_assert(every_field_classified(), "include/elmk_restart.def lists every field exactly once");
+int field_class(int f) { return g_class.c[f]; }
 
 constexpr size_t RST_ALIGN = 256;
 constexpr size_t RST_CHUNK = (size_t)64 << 20;  // bytes of image per staging chunk
@@ -2408,6 +2597,7 @@ struct RstSrc {
 // what an image of this context holds, in order: the section and entry tables and where each section's rows live
 struct RstLayout {
   std::vector<elmk_restart_entry> ent;
+  std::vector<elmk_restart_accum> acc;  // version 2: one per accumulator entry (nsteps filled in by the save)
   std::vector<elmk_restart_section> sec;
   std::vector<RstSrc> src;
   size_t header_bytes = 0, total = 0;
@@ -2430,8 +2620,15 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
     L.sec.push_back(elmk_restart_section{e.cells ? ELMK_RESTART_GRIDDED : ELMK_RESTART_HISTORY, (int32_t)i, e.nlev, ELMK_F64, ext, 0, 0});
     L.src.push_back(RstSrc{(char*)(double*)e.acc, e.cld, ELMK_F64, e.cells ? 0 : gcol0, false});
   }
-  L.header_bytes = align_up(sizeof(elmk_restart_header) + L.ent.size() * sizeof(elmk_restart_entry) +
-                                L.sec.size() * sizeof(elmk_restart_section),
+  for (size_t i = 0; i < ctx->accum.size(); i++) {
+    const elmk_ctx::AccumEntry& e = ctx->accum[i];
+    L.acc.push_back(elmk_restart_accum{e.src, e.kind, e.dst, 0, e.period, 0});
+    L.sec.push_back(elmk_restart_section{ELMK_RESTART_ACCUM, (int32_t)i, e.nlev, ELMK_F64, ctx->ncols, 0, 0});
+    L.src.push_back(RstSrc{(char*)(double*)e.val, ctx->ld, ELMK_F64, gcol0, false});
+  }
+  // version 2 (with accumulator entries): their number in the word after the header, their table after the history entries
+  L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.acc.empty() ? 0 : 8 + L.acc.size() * sizeof(elmk_restart_accum)) +
+                                L.ent.size() * sizeof(elmk_restart_entry) + L.sec.size() * sizeof(elmk_restart_section),
                             RST_ALIGN);
   size_t off = L.header_bytes;
   for (elmk_restart_section& s : L.sec) {
@@ -2606,6 +2803,9 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
   unsigned long long counts[ELMK_HIST_MAX_TAPES] = {};
   if (!sums.empty()) HIPCHK(hipMemcpyAsync(sums.data(), R.sums, sums.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (ctx->hist_table) HIPCHK(hipMemcpyAsync(counts, hist_counts(ctx), sizeof counts, hipMemcpyDeviceToHost, ctx->stream));
+  unsigned long long nacc[ELMK_ACCUM_MAX_ENTRIES] = {};
+  if (!L.acc.empty())
+    HIPCHK(hipMemcpyAsync(nacc, accum_counts(ctx), L.acc.size() * sizeof nacc[0], hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   std::vector<uint64_t> ck;
   uint64_t bad = 0;
@@ -2618,7 +2818,7 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
   }
   elmk_restart_header H{};
   memcpy(H.magic, ELMK_RESTART_MAGIC, 8);
-  H.version = ELMK_RESTART_VERSION;
+  H.version = L.acc.empty() ? ELMK_RESTART_VERSION : ELMK_RESTART_VERSION_ACCUM;
   H.real_bytes = (uint32_t)store_size(ELMK_F64);
   H.schema_hash = schema_hash();
   H.gcol0 = gcol0;
@@ -2630,8 +2830,19 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
   H.total_bytes = L.total;
   memcpy(out, &H, sizeof H);
   unsigned char* p = out + sizeof H;
+  if (!L.acc.empty()) {
+    const uint32_t word[2] = {(uint32_t)L.acc.size(), 0u};
+    memcpy(p, word, 8);
+    p += 8;
+  }
   if (!L.ent.empty()) memcpy(p, L.ent.data(), L.ent.size() * sizeof(elmk_restart_entry));
   p += L.ent.size() * sizeof(elmk_restart_entry);
+  for (size_t i = 0; i < L.acc.size(); i++) {
+    elmk_restart_accum A = L.acc[i];
+    A.nsteps = nacc[i];
+    memcpy(p, &A, sizeof A);
+    p += sizeof A;
+  }
   for (size_t s = 0; s < L.sec.size(); s++) {
     elmk_restart_section S = L.sec[s];
     S.checksum = ck[s];
@@ -2649,7 +2860,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   elmk_restart_header H;
   if (bytes < (int64_t)sizeof H) return invalid(ctx, "elmk_restart_load: truncated image");
   memcpy(&H, in, sizeof H);
-  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || H.version != ELMK_RESTART_VERSION)
+  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || (H.version != ELMK_RESTART_VERSION && H.version != ELMK_RESTART_VERSION_ACCUM))
     return invalid(ctx, "elmk_restart_load: not a restart image of this format version");
   if (H.header_bytes > (uint64_t)bytes || H.total_bytes > (uint64_t)bytes || H.header_bytes % 8 != 0)
     return invalid(ctx, "elmk_restart_load: truncated image");
@@ -2658,15 +2869,34 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   if (H.ncols != ctx->ncols) return invalid(ctx, "elmk_restart_load: the image holds another number of columns");
   if (H.gcol0 != gcol0) return invalid(ctx, "elmk_restart_load: the image starts at another global column");
   const RstLayout L = rst_layout(ctx, gcol0);
+  // the accumulator table first (version 2 holds one, and only a context with entries saves or loads version 2)
+  const unsigned char* p = in + sizeof H;
+  unsigned long long nacc[ELMK_ACCUM_MAX_ENTRIES] = {};
+  const char* const acc_differs = "elmk_restart_load: the image's accumulator entries differ from the context's";
+  if ((H.version == ELMK_RESTART_VERSION_ACCUM) != !L.acc.empty()) return invalid(ctx, acc_differs);
+  if (!L.acc.empty()) {
+    uint32_t word[2];
+    if (H.header_bytes < sizeof H + 8) return invalid(ctx, "elmk_restart_load: truncated image");
+    memcpy(word, p, 8);
+    if (word[0] != L.acc.size() || word[1] != 0u) return invalid(ctx, acc_differs);
+    p += 8;
+  }
   if (H.nentries != L.ent.size() || H.nsections != L.sec.size() || H.header_bytes != L.header_bytes || H.total_bytes != L.total)
     return invalid(ctx, "elmk_restart_load: the image's history entries differ from the context's");
-  const unsigned char* p = in + sizeof H;
   for (size_t i = 0; i < L.ent.size(); i++) {
     elmk_restart_entry E;
     memcpy(&E, p + i * sizeof E, sizeof E);
     if (memcmp(&E, &L.ent[i], sizeof E) != 0) return invalid(ctx, "elmk_restart_load: the image's history entries differ from the context's");
   }
   p += L.ent.size() * sizeof(elmk_restart_entry);
+  for (size_t i = 0; i < L.acc.size(); i++) {
+    elmk_restart_accum A;
+    memcpy(&A, p, sizeof A);
+    p += sizeof A;
+    nacc[i] = A.nsteps;
+    A.nsteps = 0;  // (loaded, not compared)
+    if (memcmp(&A, &L.acc[i], sizeof A) != 0) return invalid(ctx, acc_differs);
+  }
   std::vector<uint64_t> want(L.sec.size());
   for (size_t s = 0; s < L.sec.size(); s++) {
     elmk_restart_section S;
@@ -2709,6 +2939,8 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
     HIPCHK(hipMemcpyAsync(hist_counts(ctx), counts, sizeof counts, hipMemcpyHostToDevice, ctx->stream));
     for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++) ctx->hist_dirty[t] = counts[t] > 0;
   }
+  if (!L.acc.empty())
+    HIPCHK(hipMemcpyAsync(accum_counts(ctx), nacc, L.acc.size() * sizeof nacc[0], hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return ELMK_OK;
 }

@@ -192,6 +192,24 @@ void launch_ds_lw_norm(void* lw, int lw_dtype, const double* lg, const OGridMap&
 void launch_ogrid_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, const int64_t* ptr, double fill, int64_t cell0,
                            int64_t m, double* out, hipStream_t st);
 
+// accumulated fields (k_accum.hip, elmk_accum_*): one row = one level of one entry.  src: the level's row of the source field (stored
+// element type `dtype`, as HistRow::dtype); val: its fp64 value row (ld elements); dst: the level's row of the destination field at
+// state precision (dst_f32 != 0: stored as fp32), or null
+struct AccumRow {
+  const void* src;
+  double* val;
+  void* dst;
+  int64_t period;  // in steps, >= 1
+  int32_t dtype;
+  int32_t kind;  // ELMK_ACCUM_*
+  int32_t entry;
+  int32_t dst_f32;
+};
+// one update of every row from its entry's step count nsteps[entry], then (a second, one-thread launch) nsteps[e] += 1 for e < nentries
+void launch_accum_update(const AccumRow* rows, int nrows, unsigned long long* nsteps, int nentries, int64_t ncols, hipStream_t st);
+// val[lev][c] = the stored value of src[lev][c] widened to fp64, nlev rows of stride ld each (elmk_accum_init without host values)
+void launch_accum_seed(const void* src, int dtype, double* val, int nlev, int64_t ld, int64_t ncols, hipStream_t st);
+
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element
 struct RstPiece {

@@ -14,6 +14,7 @@
 // the count when it is read (k_hist_finalize), one correctly rounded division.
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
+#include "elmk_pair.h"
 
 // Every source load and every accumulator load and store carries the nontemporal hint: interleaved A/B runs of
 // tests/tools/history_cost.py --ab (profiles/r06_history_nt_ab.jsonl) took the 19-field PrimaryVars tape from 0.64 to 0.59 ms at
@@ -24,29 +25,6 @@
 namespace elmk {
 
 namespace {
-typedef double hd2 __attribute__((ext_vector_type(2)));
-typedef float hf2 __attribute__((ext_vector_type(2)));
-typedef int32_t hi2 __attribute__((ext_vector_type(2)));
-typedef uint32_t hu2 __attribute__((ext_vector_type(2)));
-typedef uint8_t hb2 __attribute__((ext_vector_type(2)));
-
-template <typename V> __device__ __forceinline__ V h_ld(const ELMK_GLOBAL V* p) { return __builtin_nontemporal_load(p); }
-template <typename V> __device__ __forceinline__ void h_st(ELMK_GLOBAL V* p, V v) { __builtin_nontemporal_store(v, p); }
-
-// two adjacent columns of a source row, widened to fp64 (exact for every stored type)
-__device__ __forceinline__ hd2 load_pair(const void* src, int dtype, int64_t c)
-{
-  hd2 v;
-  switch (dtype) {
-    case ELMK_F64: v = h_ld((const ELMK_GLOBAL hd2*)src + c / 2); break;
-    case ELMK_F32_STORED: { const hf2 f = h_ld((const ELMK_GLOBAL hf2*)src + c / 2); v = hd2{(double)f.x, (double)f.y}; break; }
-    case ELMK_I32: { const hi2 i = h_ld((const ELMK_GLOBAL hi2*)src + c / 2); v = hd2{(double)i.x, (double)i.y}; break; }
-    case ELMK_U32: { const hu2 u = h_ld((const ELMK_GLOBAL hu2*)src + c / 2); v = hd2{(double)u.x, (double)u.y}; break; }
-    default: { const hb2 b = h_ld((const ELMK_GLOBAL hb2*)src + c / 2); v = hd2{(double)b.x, (double)b.y}; break; }
-  }
-  return v;
-}
-
 // one column of a source row, widened to fp64 as load_pair widens it (a gather: no nontemporal hint, neighbouring cells re-read lines)
 __device__ __forceinline__ double load_one(const void* src, int dtype, int64_t c)
 {

@@ -8,12 +8,18 @@ elmk_restart_save writes, so that a run can restart with another column decompos
 
 merge and slice refuse images with gridded history entries: per-rank partial cell accumulators do not survive a change of
 decomposition under MAX and MIN.
+
+A context with accumulated fields (elmk_accum_add) saves a version-2 image: the word after the header counts the accumulator
+entries, their table (ACCUM: source, kind, destination, period, step count) follows the history entries, and their value rows are
+sections of kind ACCUM_SECTION.  parse returns the table under "accum" (empty for version 1), build takes it as `accum`, and merge
+requires equal tables and equal step counts.  An image without accumulator entries is version 1, byte for byte as before.
 """
 import numpy as np
 
 MAGIC = b"ELMKRST\0"
-VERSION = 1
-FIELD, HISTORY, GRIDDED = 0, 1, 2  # ELMK_RESTART_*
+VERSION = 1  # of an image without accumulator entries
+VERSION_ACCUM = 2  # of an image with accumulator entries
+FIELD, HISTORY, GRIDDED, ACCUM_SECTION = 0, 1, 2, 3  # ELMK_RESTART_*
 ALIGN = 256
 HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), ("schema_hash", "<u8"), ("gcol0", "<i8"),
                    ("ncols", "<i8"), ("tape_count", "<u8", (4,)), ("nentries", "<u4"), ("nsections", "<u4"),
@@ -21,7 +27,8 @@ HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), (
 ENTRY = np.dtype([("tape", "<i4"), ("field", "<i4"), ("op", "<i4"), ("gridded", "<i4"), ("ncells", "<i8")])
 SECTION = np.dtype([("kind", "<i4"), ("id", "<i4"), ("nlev", "<i4"), ("dtype", "<i4"), ("extent", "<i8"), ("offset", "<u8"),
                     ("checksum", "<u8")])
-assert HEADER.itemsize == 104 and ENTRY.itemsize == 24 and SECTION.itemsize == 40
+ACCUM = np.dtype([("src_field", "<i4"), ("kind", "<i4"), ("dst_field", "<i4"), ("pad", "<i4"), ("period", "<i8"), ("nsteps", "<u8")])
+assert HEADER.itemsize == 104 and ENTRY.itemsize == 24 and SECTION.itemsize == 40 and ACCUM.itemsize == 32
 ELEM = {0: np.dtype("<f8"), 1: np.dtype("<i4"), 2: np.dtype("u1"), 3: np.dtype("<u4")}  # elmk_dtype -> image element
 _CK_OFF = HEADER.fields["header_checksum"][1]
 
@@ -72,19 +79,30 @@ def header_checksum(img, header_bytes):
 
 
 def parse(image):
-    """-> dict(header=, entries=, sections=, data=[nlev, extent] array per section).  Checks the structure, not the checksums."""
+    """-> dict(header=, entries=, accum=, sections=, data=[nlev, extent] array per section).  Checks the structure, not the
+    checksums."""
     img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
     if img.size < HEADER.itemsize:
         raise RestartError("truncated image")
     h = np.frombuffer(img[:HEADER.itemsize].tobytes(), HEADER)[0]
-    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) != VERSION:
+    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) not in (VERSION, VERSION_ACCUM):
         raise RestartError("not a restart image of this format version")
     hb, tb, ne, ns = int(h["header_bytes"]), int(h["total_bytes"]), int(h["nentries"]), int(h["nsections"])
-    if hb > img.size or tb > img.size or hb < HEADER.itemsize + ne * ENTRY.itemsize + ns * SECTION.itemsize:
-        raise RestartError("truncated image")
     o = HEADER.itemsize
+    na = 0
+    if int(h["version"]) == VERSION_ACCUM:
+        if img.size < o + 8:
+            raise RestartError("truncated image")
+        na, zero = (int(x) for x in np.frombuffer(img[o:o + 8].tobytes(), "<u4"))
+        if na < 1 or zero != 0:
+            raise RestartError("a version-2 image holds at least one accumulator entry")
+        o += 8
+    if hb > img.size or tb > img.size or hb < o + ne * ENTRY.itemsize + na * ACCUM.itemsize + ns * SECTION.itemsize:
+        raise RestartError("truncated image")
     ent = np.frombuffer(img[o:o + ne * ENTRY.itemsize].tobytes(), ENTRY).copy()
     o += ne * ENTRY.itemsize
+    acc = np.frombuffer(img[o:o + na * ACCUM.itemsize].tobytes(), ACCUM).copy()
+    o += na * ACCUM.itemsize
     sec = np.frombuffer(img[o:o + ns * SECTION.itemsize].tobytes(), SECTION).copy()
     data = []
     for s in sec:
@@ -94,7 +112,7 @@ def parse(image):
         if off + n * dt.itemsize > tb:
             raise RestartError("truncated image")
         data.append(np.frombuffer(img[off:off + n * dt.itemsize].tobytes(), dt).reshape(int(s["nlev"]), int(s["extent"])))
-    return dict(header=h, entries=ent, sections=sec, data=data)
+    return dict(header=h, entries=ent, accum=acc, sections=sec, data=data)
 
 
 def verify(image):
@@ -111,13 +129,16 @@ def verify(image):
     return p
 
 
-def build(header, entries, sections, data):
-    """An image from its parts: offsets, header_bytes, total_bytes and the header checksum are computed; section checksums are
-    taken from sections['checksum']."""
+def build(header, entries, sections, data, accum=None):
+    """An image from its parts: offsets, header_bytes, total_bytes, the version (2 with accumulator entries `accum`, else 1) and the
+    header checksum are computed; section checksums are taken from sections['checksum']."""
     h = np.array(header, HEADER).reshape(())
     ent = np.asarray(entries, ENTRY)
+    acc = np.zeros(0, ACCUM) if accum is None else np.asarray(accum, ACCUM).reshape(-1)
     sec = np.array(sections, SECTION)
-    hb = _align(HEADER.itemsize + ent.size * ENTRY.itemsize + sec.size * SECTION.itemsize)
+    h["version"] = VERSION_ACCUM if acc.size else VERSION
+    pre = HEADER.itemsize + (8 if acc.size else 0)
+    hb = _align(pre + ent.size * ENTRY.itemsize + acc.size * ACCUM.itemsize + sec.size * SECTION.itemsize)
     off = hb
     for i, d in enumerate(data):
         sec[i]["offset"] = off
@@ -125,9 +146,13 @@ def build(header, entries, sections, data):
     h["nentries"], h["nsections"], h["header_bytes"], h["total_bytes"], h["header_checksum"] = ent.size, sec.size, hb, off, 0
     img = np.zeros(off, np.uint8)
     img[:HEADER.itemsize] = np.frombuffer(h.tobytes(), np.uint8)
-    o = HEADER.itemsize
+    if acc.size:
+        img[HEADER.itemsize:pre] = np.frombuffer(np.array([acc.size, 0], "<u4").tobytes(), np.uint8)
+    o = pre
     img[o:o + ent.nbytes] = np.frombuffer(ent.tobytes(), np.uint8)
     o += ent.nbytes
+    img[o:o + acc.nbytes] = np.frombuffer(acc.tobytes(), np.uint8)
+    o += acc.nbytes
     img[o:o + sec.nbytes] = np.frombuffer(sec.tobytes(), np.uint8)
     for s, d in zip(sec, data):
         b = np.frombuffer(np.ascontiguousarray(d, ELEM[int(s["dtype"])]).tobytes(), np.uint8)
@@ -155,11 +180,13 @@ def merge(images):
         if int(h["gcol0"]) != end:
             raise RestartError("merge: the column ranges are not adjacent")
         end += int(h["ncols"])
-        for k in ("schema_hash", "real_bytes", "nentries", "nsections"):
+        for k in ("version", "schema_hash", "real_bytes", "nentries", "nsections"):
             if h[k] != first["header"][k]:
                 raise RestartError(f"merge: the images differ in {k}")
         if not np.array_equal(h["tape_count"], first["header"]["tape_count"]) or p["entries"].tobytes() != first["entries"].tobytes():
             raise RestartError("merge: the images hold different history tapes")
+        if p["accum"].tobytes() != first["accum"].tobytes():
+            raise RestartError("merge: the images hold different accumulator entries or step counts")
         a, b = p["sections"], first["sections"]
         if not all(np.array_equal(a[k], b[k]) for k in ("kind", "id", "nlev", "dtype")):
             raise RestartError("merge: the images hold different sections")
@@ -171,7 +198,7 @@ def merge(images):
         data.append(np.concatenate([p["data"][i] for p in ps], axis=1))
         sec[i]["extent"] = h["ncols"]
         sec[i]["checksum"] = int(np.sum(np.array([int(p["sections"][i]["checksum"]) for p in ps], np.uint64), dtype=np.uint64))
-    return build(h, first["entries"], sec, data)
+    return build(h, first["entries"], sec, data, first["accum"])
 
 
 def slice(image, gcol0, n):  # noqa: A001 - the name of the operation
@@ -190,7 +217,7 @@ def slice(image, gcol0, n):  # noqa: A001 - the name of the operation
         data.append(d)
         sec[i]["extent"] = n
         sec[i]["checksum"] = checksum(d, gcol0)
-    return build(h, p["entries"], sec, data)
+    return build(h, p["entries"], sec, data, p["accum"])
 
 
 def write(path, image):

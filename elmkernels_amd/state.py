@@ -25,7 +25,10 @@ HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, 
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
 CLASS_PROGNOSTIC, CLASS_SURFACE, CLASS_FORCING, CLASS_DIAGNOSTIC = range(4)  # elmk_field_class
 CLASS_NAMES = ("prognostic", "surface", "forcing", "diagnostic")
-RUN_QBOT_IS_RH, RUN_HISTORY = 1, 2  # elmk_run flags
+RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM = 1, 2, 4  # elmk_run flags
+ACCUM_RUNMEAN, ACCUM_TIMEAVG, ACCUM_RUNACCUM = range(3)  # elmk_accum_add
+ACCUM_KINDS = {"runmean": ACCUM_RUNMEAN, "timeavg": ACCUM_TIMEAVG, "runaccum": ACCUM_RUNACCUM}
+ACCUM_MAX_ENTRIES = 16
 # elmk_run_step of include/elmk.h, field for field (natural C alignment: tests/test_run_host.py checks it against gcc)
 RUN_STEP_DTYPE = np.dtype([("decday", np.float64), ("doy", np.int32), ("forc_slot", np.int32), ("forc_wt1", np.float64, (8,)),
                            ("forc_wt2", np.float64, (8,)), ("month1", np.int32), ("month2", np.int32), ("month_wt1", np.float64),
@@ -91,6 +94,7 @@ class ELMState:
         self._hist_nlev = {}  # history entry id -> levels of its field
         self._hist_cells = set()  # ids of gridded history entries (their results are cell-shaped)
         self.output_ncells = None  # cells of the output grid (set_output_grid)
+        self._accum_nlev = {}  # accumulator entry id -> levels of its source field
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -370,6 +374,53 @@ class ELMState:
         self._hist_nlev.clear()
         self._hist_cells.clear()
 
+    # -- accumulated fields (include/elmk.h: elmk_accum_add ...; elmkernels_amd/accum.py restates the update) ------------------
+    def accum_add(self, src, kind, period_steps, dst=None):
+        """Register an accumulated field over every level of field `src`: kind "runmean", "timeavg", "runaccum" or ACCUM_*, the
+        period in steps, `dst` the field that receives the value (or None).  Returns the entry id.  Refused (ElmkError) for an unknown
+        field or kind, a period < 1, a destination that is not an F64 SURFACE field of the source's levels, that another entry writes
+        or that is the source, a full table, a stream in capture."""
+        sid = self.fields[src][0] if isinstance(src, str) else int(src)
+        did = -1 if dst is None else (self.fields[dst][0] if isinstance(dst, str) else int(dst))
+        code = ACCUM_KINDS[kind] if isinstance(kind, str) else int(kind)
+        entry = self._chk(self.lib.elmk_accum_add(self.ctx, sid, code, int(period_steps), did), f"accum_add({src})")
+        nlev = C.c_int()
+        self.lib.elmk_field_info(sid, C.byref(nlev), None)
+        self._accum_nlev[entry] = nlev.value
+        return entry
+
+    def accum_init(self, entry, values=None, nsteps=0):
+        """Set the entry's value from values ([ncols] or [nlev, ncols], SoA) and its step count (a restart file's T10 and nstep);
+        values None: seeded from the destination field's current contents.  Synchronises."""
+        p = None
+        if values is not None:
+            a = np.ascontiguousarray(values, dtype=np.float64)
+            if a.size != self._accum_nlev.get(int(entry), 1) * self.ncols:
+                raise ValueError(f"accum_init: {a.size} values for {self._accum_nlev.get(int(entry), 1)} x {self.ncols}")
+            p = a.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.elmk_accum_init(self.ctx, int(entry), p, int(nsteps)), "accum_init")
+
+    def accum_update(self):
+        """Fold the current state into every accumulated field and write the destinations: stream-ordered, no sync."""
+        self._chk(self.lib.elmk_accum_update(self.ctx), "accum_update")
+
+    def accum_read(self, entry, col0=0, n=None, layout=LAYOUT_SOA):
+        """(val, nsteps): the entry's fp64 value - [n] for a one-level source, else [nlev, n] (SOA) or [n, nlev] (COL_MAJOR) - and
+        the updates folded in so far.  Synchronises."""
+        n = int(self.ncols - col0 if n is None else n)
+        nlev = self._accum_nlev.get(int(entry), 1)
+        shape = (n,) if nlev == 1 else ((n, nlev) if layout == LAYOUT_COL_MAJOR else (nlev, n))
+        out = np.empty(shape, dtype=np.float64)
+        cnt = C.c_int64()
+        self._chk(self.lib.elmk_accum_read(self.ctx, int(entry), out.ctypes.data_as(C.c_void_p), int(col0), n, int(layout),
+                                           C.byref(cnt)), "accum_read")
+        return out, cnt.value
+
+    def accum_clear(self):
+        """Drop every accumulated field and free its device buffers (destination fields keep their values)."""
+        self._chk(self.lib.elmk_accum_clear(self.ctx), "accum_clear")
+        self._accum_nlev.clear()
+
     # -- multi-step runs (include/elmk.h: elmk_run ...) ---------------------------------------------
     def run_reserve(self, forcing_slots, max_steps):
         """Device series of `forcing_slots` forcing records and 12 months, and step tables / diagnostics rings of `max_steps` rows."""
@@ -552,8 +603,8 @@ class ELMState:
         return img
 
     def restart_load(self, image, gcol0=0):
-        """Verify the whole image, then load its fields, history accumulators and tape counts; the history entries must have been
-        registered as when it was saved."""
+        """Verify the whole image, then load its fields, history accumulators and tape counts and the accumulated fields' values and
+        step counts; the history and accumulator entries must have been registered as when it was saved."""
         img = np.ascontiguousarray(image, dtype=np.uint8)
         self._chk(self.lib.elmk_restart_load(self.ctx, int(gcol0), img.ctypes.data, img.size), "restart_load")
 
@@ -751,12 +802,13 @@ class ELMInterface:
             raise RuntimeError(f"ELM physics error flags {flags:#x}, first at column {col}")
         return False
 
-    def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False):
+    def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False, update_accum=False):
         """ELMInterface::advance for every row of steps (RUN_STEP_DTYPE) in one call (elmk_run; needs S.run_reserve and the series
-        uploaded); self.conservation = the last step's triples, self.run_conservation = all of them.  Raises after the run if a step
-        raised a fatal flag, naming the first such step and column."""
+        uploaded); self.conservation = the last step's triples, self.run_conservation = all of them.  update_accum: every step updates
+        the accumulated fields registered on self.S (ELM's UpdateAccVars: after the physics, before the history).  Raises after the
+        run if a step raised a fatal flag, naming the first such step and column."""
         S = self.S
-        flags = (RUN_HISTORY if accumulate_history else 0) | (RUN_QBOT_IS_RH if qbot_is_rh else 0)
+        flags = (RUN_HISTORY if accumulate_history else 0) | (RUN_QBOT_IS_RH if qbot_is_rh else 0) | (RUN_ACCUM if update_accum else 0)
         S.run(dt_seconds, steps, flags)
         mms, fo, fb = S.run_diagnostics()
         self.run_conservation = mms
@@ -808,6 +860,10 @@ class ELMInterface:
     def accumulate_history(self):
         """Fold this step's state into the history tapes registered on self.S (ELMState.history_add): call after advance()."""
         self.S.history_accumulate()
+
+    def update_accum(self):
+        """Update the accumulated fields registered on self.S (ELMState.accum_add): call after advance(), before accumulate_history()."""
+        self.S.accum_update()
 
     def restart_save(self, gcol0=0):
         """The restart image of the columns (ELMState.restart_save)."""

@@ -39,6 +39,7 @@
  *   kokkos_surface_fluxes(S,dt)     surface_fluxes_kokkos.hh          elmk_surface_fluxes
  *   kokkos_evaluate_conservation    conserved_quantity_kokkos.hh      elmk_evaluate_conservation
  *   (ELM's history tapes: time averages, extremes, last values)       elmk_history_add / _accumulate / _read
+ *   (ELM's accumulMod: T10, the running means behind photosynthesis)  elmk_accum_add / _init / _update / _read
  *   kokkos_driver.cc:54-85 time loop                                  elmk_run (elmk_run_reserve, elmk_series_upload)
  *   AtmDataManager::data(ntimes, ncells) on the data set's own grid   elmk_set_forcing_grid, elmk_upload_gridded,
  *     (src/data/atm_data.h:168-172; ELM's coupler maps it to land)     elmk_series_upload of cell records
@@ -297,6 +298,7 @@ int elmk_history_clear(elmk_ctx *ctx);
  *                          elmk_get_forcing(forc_wt1, forc_wt2, flags & ELMK_RUN_QBOT_IS_RH) over slots forc_slot / forc_slot + 1;
  *                          elmk_init_timestep; elmk_advance_physics(dt); elmk_evaluate_conservation -> ring row s;
  *                          elmk_error_summary -> ring row s (flags sticky, as that call sees them after the step);
+ *                          with ELMK_RUN_ACCUM: elmk_accum_update ("accumulated fields");
  *                          with ELMK_RUN_HISTORY: elmk_history_accumulate.
  *                        Stream-ordered, returns without synchronising; with elmk_set_graph one step is captured once (one chain of
  *                        nodes) and replayed nsteps times.  Enters per-column solar mode (as elmk_solar_geometry does).  Needs a
@@ -317,6 +319,7 @@ typedef struct {
   double month_wt1, month_wt2;      /* monthly_data.cc:56-62 */
 } elmk_run_step;
 enum { ELMK_RUN_QBOT_IS_RH = 1, ELMK_RUN_HISTORY = 2 };
+#define ELMK_RUN_ACCUM 4 /* the third flag bit: every step updates the accumulated fields ("accumulated fields" below) */
 int elmk_run_reserve(elmk_ctx *ctx, int forcing_slots, int max_steps);
 int elmk_series_upload(elmk_ctx *ctx, int field, int slot0, int nslots, const double *host, int64_t col0, int64_t n);
 int elmk_run(elmk_ctx *ctx, double dt, const elmk_run_step *steps, int nsteps, int flags);
@@ -486,6 +489,51 @@ int elmk_clear_output_grid(elmk_ctx *ctx);
 int elmk_download_gridded(elmk_ctx *ctx, int field, int level, double *cells /*[ncells]*/);
 int elmk_gridded_history_add(elmk_ctx *ctx, int tape, int field, int op);
 
+/* ---- accumulated fields -----------------------------------------------------------------------
+ * ELM's accumulMod on the device: named fields accumulated over time from a source field, updated once per step after the physics
+ * and before the history update (UpdateAccVars), and fed back into the state without a round trip through the host.  The one the hot
+ * path reads is t10, the 10-day running mean of t_ref2m behind photosynthesis' acclimation terms (vcmaxse, jmaxse, jmax25top in
+ * canopy_fluxes): no kernel of the step writes it, so without an entry it stays what was uploaded.
+ * An entry has a source field (every level, any dtype, each sample widened to fp64 as history widens it), a kind, a period P >= 1 in
+ * steps, an optional destination field, a value buffer val[nlev][level stride] in fp64 (in both builds) and a step count n kept on the
+ * device: the updates folded in so far.  One update uses nstep = n + 1 and the sample v, per element, in this operation order and
+ * without contraction (`/` is the correctly rounded fp64 division):
+ *   ELMK_ACCUM_RUNMEAN   a = min(nstep, P);  val = ((double)(a - 1) * val + v) / (double)a     (as written also for a == 1)
+ *   ELMK_ACCUM_TIMEAVG   if (nstep % P == 1 || P == 1) val = +0.0;  val = val + v;  if (nstep % P == 0) val = val / (double)P
+ *   ELMK_ACCUM_RUNACCUM  if (rint(v) == -99999.0) val = +0.0;
+ *                        else t = val + v;  t = t > 0.0 ? t : 0.0;  val = t < 99999.0 ? t : 99999.0
+ * then n = n + 1.  The destination receives val at state precision (rounded to fp32 in libelmk_f32.so) on every update; for TIMEAVG
+ * only on an update that completes a period, so that the field holds the last whole average.  elmkernels_amd/accum.py: update is
+ * this operation on the host.
+ *   elmk_accum_add     register an entry; returns its index (>= 0, in order of registration).  Allocates the value rows, zero-filled,
+ *                      with n = 0 (counted in elmk_device_bytes, with the 16 KiB row table of the first entry).  dst_field = -1: no
+ *                      destination.  A destination must be an F64 field of the source's nlev and of class SURFACE (nothing else may
+ *                      own it), not the destination of another entry and not the entry's own source.  No entry reads what another
+ *                      writes: a destination may not be the source of another entry, nor a source the destination of one (the rows
+ *                      of all entries run in one launch, in no order).  ELMK_E_INVALID, nothing changed: a bad field, kind or
+ *                      period, such a destination or source, a full table (ELMK_ACCUM_MAX_ENTRIES), a stream being captured.
+ *   elmk_accum_init    set val from host[nlev][ncols] (SoA) and n = nsteps >= 0: how a restart file's T10 and nstep come in.  host =
+ *                      NULL: val is seeded from the destination field's current contents (widened), ELMK_E_INVALID without a
+ *                      destination.  Synchronises, as elmk_upload does.
+ *   elmk_accum_update  fold the current state into every entry: stream-ordered and capturable, no host memory, no synchronisation;
+ *                      writes nothing but value rows, counts and destination fields.  Two launches (the update of every row of every
+ *                      entry, then a one-thread kernel that advances the counts); nothing without entries.  A captured graph holds
+ *                      the entry table of the moment of capture: capture again after add / clear.
+ *   elmk_accum_read    val of columns [col0, col0 + n) as doubles, layout as elmk_download (host may be NULL with n = 0), and the
+ *                      count (nsteps may be NULL); synchronises.
+ *   elmk_accum_clear   drop every entry and free its buffers; destination fields keep their values.
+ * elmk_run with ELMK_RUN_ACCUM runs the update in every step, after elmk_advance_physics and the step's conservation and flag rows and
+ * before elmk_history_accumulate (ELM's order: a tape of t10 sees the new value); graph on and off give the same bits.
+ * A context without entries runs the kernels, launch sequences and graphs it ran before, allocates nothing more and saves the
+ * restart image it saved before. */
+enum { ELMK_ACCUM_RUNMEAN = 0, ELMK_ACCUM_TIMEAVG = 1, ELMK_ACCUM_RUNACCUM = 2 };
+#define ELMK_ACCUM_MAX_ENTRIES 16
+int elmk_accum_add(elmk_ctx *ctx, int src_field, int kind, int64_t period_steps, int dst_field);
+int elmk_accum_init(elmk_ctx *ctx, int entry, const double *host /*[nlev][ncols] SoA, or NULL*/, int64_t nsteps);
+int elmk_accum_update(elmk_ctx *ctx);
+int elmk_accum_read(elmk_ctx *ctx, int entry, double *host, int64_t col0, int64_t n, int layout, int64_t *nsteps);
+int elmk_accum_clear(elmk_ctx *ctx);
+
 /* ---- restart ---------------------------------------------------------------------------------
  * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state
  * and history into a self-describing byte buffer, the image, and another context - in another process, or with another column
@@ -507,20 +555,29 @@ int elmk_gridded_history_add(elmk_ctx *ctx, int tape, int field, int op);
  *                           SURFACE field, in field id order
  *     ELMK_RESTART_HISTORY  id = entry index, extent = ncols, F64: the raw accumulators (not acc / count)
  *     ELMK_RESTART_GRIDDED  id = entry index, extent = ncells of the output grid, F64: the cell accumulators
+ *     ELMK_RESTART_ACCUM    (version 2) id = accumulator entry index, extent = ncols, F64: the value rows of elmk_accum_add
  *   Checksum of a section: the sum modulo 2^64 of term = fmix64(bits ^ fmix64(g * 64 + lev + 1)) over its elements, fmix64 the
  *   murmur3 finalizer, bits the element zero-extended to 64 bits, g the global column (gcol0 + column; the cell for GRIDDED), lev
  *   its level.  A sum, so it is the same in any reduction order, and images of adjacent column ranges merge by adding checksums.
  *   Checksum of the header: the same sum over the 8-byte words w_i of [0, header_bytes), header_checksum read as 0, with g = i,
  *   lev = 0.  schema_hash: FNV-1a 64 over, for every field in id order, its name, a 0 byte, its dtype byte and its nlev byte.
  *
+ * Image format, version 2: what a context WITH accumulator entries (elmk_accum_add) saves; one without saves version 1, byte for
+ * byte as before.  As version 1, except that header.version = 2, the 8-byte word after the header holds the number of accumulator
+ * entries (uint32, then a zero uint32), the history entries follow it, then one elmk_restart_accum per accumulator entry in
+ * registration order (source, kind, destination, period and the step count n), then the section table; the ELMK_RESTART_ACCUM
+ * sections come last, checksummed as the other column sections.  The header checksum covers all of it.
+ *
  * elmk_restart_size: bytes of this context's image.  elmk_restart_save: the image of the context's columns, which are global
  * columns [gcol0, gcol0 + ncols) of the run.  elmk_restart_load: verifies the whole image on the device (every checksum, snl in
- * 0..nlevsno, as elmk_upload) before it writes anything, then writes the fields, the accumulators and the tape counts; a tape with
- * count > 0 counts as accumulated (elmk_history_add refuses it until its reset).  Both synchronise with the context's stream and
- * any elmk_run in flight; staging memory is allocated for the call and freed before it returns.  ELMK_E_INVALID, with state,
- * history and counts untouched and the context usable, for: a stream being captured, a too small or truncated buffer, a bad magic
+ * 0..nlevsno, as elmk_upload) before it writes anything, then writes the fields, the accumulators, the tape counts and the
+ * accumulated fields' value rows and step counts; a tape with count > 0 counts as accumulated (elmk_history_add refuses it until
+ * its reset).  Both synchronise with the context's stream and any elmk_run in flight; staging memory is allocated for the call and
+ * freed before it returns.  ELMK_E_INVALID, with state, history and counts untouched and the context usable, for: a stream being
+ * captured, a too small or truncated buffer, a bad magic
  * or version, another schema, another ncols or gcol0, a history entry table other than the context's (same entries, same order,
- * gridded entries with the same ncells), any checksum mismatch, snl out of range.
+ * gridded entries with the same ncells), an accumulator table other than the context's (same source, kind, period and destination,
+ * same order; the counts are loaded, not compared), any checksum mismatch, snl out of range.
  *
  * The image holds column data and history only.  Parameters, SNICAR and snow-age tables, geography, forcing and output maps, run
  * reservations and series, shortwave mode and record times, options and graphs stay with the driver, which sets them up as at
@@ -528,9 +585,10 @@ int elmk_gridded_history_add(elmk_ctx *ctx, int tape, int field, int op);
  * then the current forcing records or run series and their record times.
  * Graphs captured before a load stay valid (the arena and the history table do not move). */
 enum { ELMK_CLASS_PROGNOSTIC = 0, ELMK_CLASS_SURFACE = 1, ELMK_CLASS_FORCING = 2, ELMK_CLASS_DIAGNOSTIC = 3 };
-enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2 };
+enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2, ELMK_RESTART_ACCUM = 3 };
 #define ELMK_RESTART_MAGIC "ELMKRST\0"
-#define ELMK_RESTART_VERSION 1u
+#define ELMK_RESTART_VERSION 1u       /* of a context without accumulator entries */
+#define ELMK_RESTART_VERSION_ACCUM 2u /* of a context with accumulator entries */
 typedef struct {
   char magic[8];              /* ELMK_RESTART_MAGIC */
   uint32_t version;           /* ELMK_RESTART_VERSION */
@@ -552,6 +610,11 @@ typedef struct {
   int64_t extent;                   /* elements per level */
   uint64_t offset, checksum;
 } elmk_restart_section;             /* 40 bytes */
+typedef struct {
+  int32_t src_field, kind, dst_field, pad; /* dst_field -1: none; pad 0 */
+  int64_t period;
+  uint64_t nsteps;                  /* the updates folded in so far */
+} elmk_restart_accum;               /* 32 bytes (version 2) */
 int elmk_field_class(int field);
 int elmk_restart_size(elmk_ctx *ctx, int64_t *bytes);
 int elmk_restart_save(elmk_ctx *ctx, int64_t gcol0, void *image, int64_t bytes);

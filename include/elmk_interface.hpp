@@ -253,9 +253,36 @@ class ELMInterface {
   void history_read(int entry, double* host) { ok(elmk_history_read(ctx_, entry, host, 0, ncols_, ELMK_LAYOUT_COL_MAJOR)); }
   void history_clear() { ok(elmk_history_clear(ctx_)); }
 
+  /* Accumulated fields (elmk.h "accumulated fields"; ELM's accumulMod): accum_add() registers a running mean / period average /
+   * running accumulation of `src` over period_steps steps, written to `dst` (nullptr: no destination) - accum_add_t10() is ELM's T10,
+   * the 10-day running mean of t_ref2m into t10, which photosynthesis reads.  update_accum() after every advance() and before
+   * accumulate_history(), or run(..., update_accum = true).  accum_init() sets the value ([nlev][ncols], SoA; nullptr: seeded from the
+   * destination field) and the step count, as from a restart file; accum_read() fills [nlev][ncols] and returns the count. */
+  int accum_add(const char* src, int kind, int64_t period_steps, const char* dst = nullptr)
+  {
+    const int e = elmk_accum_add(ctx_, id(src), kind, period_steps, dst ? id(dst) : -1);
+    ok(e < 0 ? e : ELMK_OK);
+    return e;
+  }
+  int accum_add_t10(double dt_seconds, int days = 10)
+  {
+    const double steps = days * 86400.0 / dt_seconds;
+    if (!(steps >= 1.0) || steps != std::floor(steps)) throw std::invalid_argument("accum_add_t10: the period is not a whole number of steps");
+    return accum_add("t_ref2m", ELMK_ACCUM_RUNMEAN, (int64_t)steps, "t10");
+  }
+  void accum_init(int entry, const double* host = nullptr, int64_t nsteps = 0) { ok(elmk_accum_init(ctx_, entry, host, nsteps)); }
+  void update_accum() { ok(elmk_accum_update(ctx_)); }
+  int64_t accum_read(int entry, double* host)
+  {
+    int64_t n = 0;
+    ok(elmk_accum_read(ctx_, entry, host, 0, host ? ncols_ : 0, ELMK_LAYOUT_SOA, &n));
+    return n;
+  }
+  void accum_clear() { ok(elmk_accum_clear(ctx_)); }
+
   /* Restart images (elmk.h "restart"): saveRestart() returns the image of the columns, global columns [gcol0, gcol0 + ncols);
-   * loadRestart() takes one after setup, geography, maps and the same history entries, in place of initialize().  Both throw on a
-   * refusal; the state is then untouched. */
+   * loadRestart() takes one after setup, geography, maps and the same history and accumulator entries, in place of initialize().
+   * Both throw on a refusal; the state is then untouched. */
   std::vector<unsigned char> saveRestart(int64_t gcol0 = 0)
   {
     int64_t bytes = 0;
@@ -283,9 +310,11 @@ class ELMInterface {
   {
     ok(elmk_series_upload(ctx_, id(field), slot0, nslots, host, 0, ncols_));
   }
-  void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false)
+  void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
+                   bool update_accum = false)
   {
-    ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(), (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0)));
+    ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(),
+                (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0) | (update_accum ? ELMK_RUN_ACCUM : 0)));
   }
   bool finish_run()
   {
@@ -306,9 +335,10 @@ class ELMInterface {
                                  " of the run, first at column " + std::to_string(first[(size_t)s]));
     return false;
   }
-  bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false)
+  bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
+           bool update_accum = false)
   {
-    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh);
+    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum);
     return finish_run();
   }
   const std::vector<double>& run_conservation() const { return run_conservation_; }

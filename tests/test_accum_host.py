@@ -1,0 +1,255 @@
+"""Accumulated fields on the host: accum.update (the numpy restatement of include/elmk.h "accumulated fields") against a scalar loop
+written straight from the spec, its edge values, period_steps, the version-2 restart image in the codec, and the declarations."""
+import math
+import os
+import re
+import struct
+
+import numpy as np
+import pytest
+
+from elmkernels_amd import _lib as L
+from elmkernels_amd import accum
+from elmkernels_amd import restart as R
+from elmkernels_amd import state as st
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("elmk_accum_add", "elmk_accum_init", "elmk_accum_update", "elmk_accum_read", "elmk_accum_clear")
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).tobytes()
+
+
+def scalar_update(val, v, kind, P, nstep):
+    """One element, straight from the spec; Python floats are IEEE fp64 and every line is one operation."""
+    v = float(v)
+    if kind == accum.RUNMEAN:
+        a = min(nstep, P)
+        x = float(a - 1) * val
+        x = x + v
+        return x / float(a)
+    if kind == accum.TIMEAVG:
+        if nstep % P == 1 or P == 1:
+            val = 0.0
+        val = val + v
+        if nstep % P == 0:
+            val = val / float(P)
+        return val
+    r = v if (math.isnan(v) or math.isinf(v)) else float(round(v))  # rint: Python's round is half-to-even
+    if r == -99999.0:
+        return 0.0
+    t = val + v
+    t = t if t > 0.0 else 0.0
+    return t if t < 99999.0 else 99999.0
+
+
+@pytest.mark.parametrize("kind", [accum.RUNMEAN, accum.TIMEAVG, accum.RUNACCUM])
+@pytest.mark.parametrize("P", [1, 4, 10])
+def test_update_equals_the_scalar_loop(kind, P):
+    """25 steps: nstep < P, nstep == P and more than two periods."""
+    rng = np.random.default_rng(100 * kind + P)
+    n = 37
+    val = np.zeros(n)
+    ref = [0.0] * n
+    for nstep in range(1, 26):
+        v = 280.0 + 15.0 * rng.standard_normal(n) if kind != accum.RUNACCUM else 4000.0 * rng.standard_normal(n)
+        if kind == accum.RUNACCUM and nstep in (7, 19):
+            v[::5] = -99999.0
+        val = accum.update(val, v, kind, P, nstep)
+        ref = [scalar_update(ref[i], v[i], kind, P, nstep) for i in range(n)]
+        assert bits(val) == bits(ref), (kind, P, nstep)
+    assert np.all(np.isfinite(val))
+
+
+def test_update_accepts_names_and_integer_samples():
+    v = np.array([-2, 0, 3], np.int32)
+    a = accum.update(np.zeros(3), v, "timeavg", 2, 1)
+    assert bits(a) == bits([-2.0, 0.0, 3.0])
+    assert bits(accum.update(a, v, "timeavg", 2, 2)) == bits([-2.0, 0.0, 3.0])
+    assert bits(accum.update(np.zeros(3), np.array([1, 2, 3], np.uint8), "runmean", 4, 1)) == bits([1.0, 2.0, 3.0])
+    with pytest.raises(ValueError):
+        accum.update(np.zeros(1), np.zeros(1), 3, 4, 1)
+    with pytest.raises(ValueError):
+        accum.update(np.zeros(1), np.zeros(1), accum.RUNMEAN, 0, 1)
+    with pytest.raises(ValueError):
+        accum.update(np.zeros(1), np.zeros(1), accum.RUNMEAN, 4, 0)
+
+
+def test_update_signed_zero_and_nan():
+    nz, nan = -0.0, float("nan")
+    # RUNMEAN as written for a == 1: (0.0 * val + v) / 1.0; +0.0 + -0.0 = +0.0
+    out = accum.update(np.array([0.0, -0.0, 5.0]), np.array([nz, nz, nz]), accum.RUNMEAN, 4, 1)
+    assert bits(out) == bits([0.0, -0.0, 0.0])
+    # ... and a NaN or infinite value before the first update is not masked by the zero factor
+    assert np.isnan(accum.update(np.array([np.inf]), np.array([1.0]), accum.RUNMEAN, 4, 1))[0]
+    # TIMEAVG: the period starts from +0.0, so a sample of -0.0 gives +0.0
+    assert bits(accum.update(np.array([7.0]), np.array([nz]), accum.TIMEAVG, 4, 1)) == bits([0.0])
+    assert bits(accum.update(np.array([nz]), np.array([nz]), accum.TIMEAVG, 4, 2)) == bits([nz])
+    # a NaN sample: sticks in the means, resets RUNACCUM (t > 0.0 is false for NaN)
+    assert np.isnan(accum.update(np.array([1.0]), np.array([nan]), accum.RUNMEAN, 4, 3))[0]
+    assert np.isnan(accum.update(np.array([1.0]), np.array([nan]), accum.TIMEAVG, 4, 3))[0]
+    assert bits(accum.update(np.array([1.0]), np.array([nan]), accum.RUNACCUM, 4, 3)) == bits([0.0])
+    # ... and a NaN value leaves the period with the next TIMEAVG reset, RUNMEAN never on its own
+    assert bits(accum.update(np.array([nan]), np.array([2.0]), accum.TIMEAVG, 4, 5)) == bits([2.0])
+    assert np.isnan(accum.update(np.array([nan]), np.array([2.0]), accum.RUNMEAN, 4, 5))[0]
+
+
+def test_runaccum_reset_value_and_clamps():
+    up = lambda val, v: accum.update(np.array(val, dtype=np.float64), np.array(v, dtype=np.float64), accum.RUNACCUM, 4, 9)  # noqa: E731
+    # the reset value is matched after rounding to the nearest integer, half to even; from a value above the clamp a reset (0.0)
+    # and a sum differ
+    big = 150000.0
+    assert bits(up([big, big, big], [-99999.0, -99999.4, -99998.6])) == bits([0.0, 0.0, 0.0])
+    assert bits(up([big, big, big], [-99999.5, -99998.5, -99998.4])) == bits([50000.5, 50001.5, big + -99998.4])  # -100000, -99998
+    # lower clamp gives +0.0, also from -0.0
+    assert bits(up([1.0, 0.0, -0.0], [-3.0, -0.0, -0.0])) == bits([0.0, 0.0, 0.0])
+    # upper clamp: t < 99999.0 keeps t, anything else (99999.0 itself, above, +inf) is 99999.0
+    below = np.nextafter(99999.0, 0.0)
+    assert bits(up([99998.0, 99998.0, 99998.0, 0.0], [below - 99998.0, 1.0, 2.0, np.inf])) == bits([below, 99999.0, 99999.0, 99999.0])
+    assert bits(up([1.5], [2.25])) == bits([3.75])
+
+
+def test_writes_destination():
+    assert all(accum.writes_destination(k, 4, s) for k in (accum.RUNMEAN, accum.RUNACCUM) for s in range(1, 10))
+    assert [s for s in range(1, 13) if accum.writes_destination("timeavg", 4, s)] == [4, 8, 12]
+    assert all(accum.writes_destination(accum.TIMEAVG, 1, s) for s in range(1, 5))
+
+
+def test_period_steps():
+    assert accum.period_steps(7, 1800.0) == 7
+    assert accum.period_steps(-10, 1800.0) == 480
+    assert accum.period_steps(-1, 86400.0) == 1
+    assert accum.period_steps(-10, 3600.0) == 240
+    for period, dt in ((-1, 7000.0), (-10, 1801.0), (-1, 172800.0), (0, 1800.0), (2.5, 1800.0), (-10, 0.0), (-10, float("nan")), (4, -1.0)):
+        with pytest.raises(ValueError):
+            accum.period_steps(period, dt)
+
+
+def test_add_t10_registers_the_running_mean():
+    class Recorder:
+        def accum_add(self, *a):
+            self.args = a
+            return 3
+
+    S = Recorder()
+    assert accum.add_t10(S, 1800.0) == 3 and S.args == ("t_ref2m", accum.RUNMEAN, 480, "t10")
+    assert accum.add_t10(S, 1800.0, period=4) == 3 and S.args == ("t_ref2m", accum.RUNMEAN, 4, "t10")
+    with pytest.raises(ValueError):
+        accum.add_t10(S, 1700.0)
+
+
+# ---- the codec: version 2 ---------------------------------------------------------------------------------------------------------
+def _image(gcol0=0, n=37, seed=3, accum_table=((29, accum.RUNMEAN, 30, 480, 6), (51, accum.TIMEAVG, -1, 4, 6))):
+    """As test_restart_host._image builds a version-1 image, with accumulator entries and their sections when accum_table has rows."""
+    rng = np.random.default_rng(seed)
+    h = np.zeros((), R.HEADER)
+    h["magic"], h["version"], h["real_bytes"], h["schema_hash"] = R.MAGIC, R.VERSION, 8, 0x1234
+    h["gcol0"], h["ncols"], h["tape_count"] = gcol0, n, [5, 2, 0, 0]
+    ent = np.zeros(2, R.ENTRY)
+    ent[0] = (0, 52, 0, 0, 0)
+    ent[1] = (1, 52, 2, 0, 0)
+    secs = [(R.FIELD, 29, 1, 1), (R.FIELD, 51, 20, 0), (R.FIELD, 167, 1, 2), (R.HISTORY, 0, 1, 0), (R.HISTORY, 1, 1, 0)]
+    acc = np.zeros(len(accum_table), R.ACCUM)
+    for i, (src, kind, dst, period, nsteps) in enumerate(accum_table):
+        acc[i] = (src, kind, dst, 0, period, nsteps)
+        secs.append((R.ACCUM_SECTION, i, 20 if src == 51 else 1, 0))
+    sec = np.zeros(len(secs), R.SECTION)
+    data = []
+    for i, (kind, fid, nlev, dt) in enumerate(secs):
+        d = (rng.integers(0, 6, (nlev, n)) if dt != 0 else rng.standard_normal((nlev, n))).astype(R.ELEM[dt])
+        sec[i] = (kind, fid, nlev, dt, n, 0, R.checksum(d, gcol0))
+        data.append(d)
+    return R.build(h, ent, sec, data, acc)
+
+
+def test_version_2_image_round_trips_through_slice_and_merge():
+    img = _image(gcol0=100, n=37)
+    p = R.verify(img)
+    assert int(p["header"]["version"]) == R.VERSION_ACCUM == 2 and p["accum"].size == 2
+    assert [int(x) for x in p["accum"]["nsteps"]] == [6, 6] and int(p["accum"][0]["period"]) == 480
+    assert struct.unpack("<II", img[R.HEADER.itemsize:R.HEADER.itemsize + 8].tobytes()) == (2, 0)
+    assert [int(s["kind"]) for s in p["sections"]][-2:] == [R.ACCUM_SECTION, R.ACCUM_SECTION]
+    parts = [R.slice(img, 100, 10), R.slice(img, 110, 1), R.slice(img, 111, 26)]
+    for q in parts:
+        v = R.verify(q)
+        assert v["accum"].tobytes() == p["accum"].tobytes()
+    assert R.merge(parts[::-1]).tobytes() == img.tobytes()
+    a, b = parts[0], R.slice(img, 110, 27)
+    for s, sa, sb in zip(p["sections"], R.parse(a)["sections"], R.parse(b)["sections"]):
+        assert int(s["checksum"]) == (int(sa["checksum"]) + int(sb["checksum"])) % (1 << 64)
+
+
+def test_merge_refuses_unequal_tables_and_counts():
+    a = _image(0, 10)
+    with pytest.raises(R.RestartError):  # another step count
+        R.merge([a, _image(10, 10, accum_table=((29, accum.RUNMEAN, 30, 480, 7), (51, accum.TIMEAVG, -1, 4, 6)))])
+    with pytest.raises(R.RestartError):  # another period
+        R.merge([a, _image(10, 10, accum_table=((29, accum.RUNMEAN, 30, 240, 6), (51, accum.TIMEAVG, -1, 4, 6)))])
+    with pytest.raises(R.RestartError):  # another destination
+        R.merge([a, _image(10, 10, accum_table=((29, accum.RUNMEAN, -1, 480, 6), (51, accum.TIMEAVG, -1, 4, 6)))])
+    with pytest.raises(R.RestartError):  # one entry fewer
+        R.merge([a, _image(10, 10, accum_table=((29, accum.RUNMEAN, 30, 480, 6),))])
+    with pytest.raises(R.RestartError):  # a version-1 image beside a version-2 image
+        R.merge([a, _image(10, 10, accum_table=())])
+    R.verify(R.merge([a, _image(10, 10)]))
+
+
+def test_damaged_version_2_images_are_refused():
+    img = _image()
+    tbl = R.HEADER.itemsize + 8 + 2 * R.ENTRY.itemsize  # the first accumulator entry
+    for off in (R.HEADER.itemsize, tbl + 4, tbl + 24, int(R.parse(img)["sections"][-1]["offset"]) + 3):
+        bad = img.copy()
+        bad[off] ^= 1
+        with pytest.raises(R.RestartError):
+            R.verify(bad)
+    with pytest.raises(R.RestartError):
+        R.verify(img[:R.HEADER.itemsize + 4])
+
+
+def test_version_1_image_still_parses_and_is_what_build_writes_without_entries():
+    """An image built as test_restart_host.py builds it (no accumulator entries): version 1, no count word, the old offsets."""
+    img = _image(gcol0=100, n=37, accum_table=())
+    p = R.verify(img)
+    assert int(p["header"]["version"]) == R.VERSION == 1 and p["accum"].size == 0
+    ne, ns = int(p["header"]["nentries"]), int(p["header"]["nsections"])
+    assert int(p["header"]["header_bytes"]) == (R.HEADER.itemsize + ne * R.ENTRY.itemsize + ns * R.SECTION.itemsize + 255) // 256 * 256
+    first = np.frombuffer(img[R.HEADER.itemsize:R.HEADER.itemsize + R.ENTRY.itemsize].tobytes(), R.ENTRY)[0]
+    assert first.tobytes() == p["entries"][0].tobytes()  # the history entries start right after the header
+    parts = [R.slice(img, 100, 10), R.slice(img, 110, 27)]
+    assert R.merge(parts).tobytes() == img.tobytes()
+    assert R.build(p["header"], p["entries"], p["sections"], p["data"]).tobytes() == img.tobytes()  # the four-argument form
+
+
+# ---- declarations -----------------------------------------------------------------------------------------------------------------
+def test_accum_abi_is_declared_and_mirrored():
+    hdr = open(os.path.join(ROOT, "include", "elmk.h")).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b" + name + r"\s*\(", hdr), name
+        assert name in L.SIGNATURES
+    for name, value in (("ELMK_ACCUM_RUNMEAN", accum.RUNMEAN), ("ELMK_ACCUM_TIMEAVG", accum.TIMEAVG), ("ELMK_ACCUM_RUNACCUM", accum.RUNACCUM),
+                        ("ELMK_RESTART_ACCUM", R.ACCUM_SECTION)):
+        assert re.search(r"\b" + name + r" = " + str(value) + r"\b", hdr), name
+    assert re.search(r"#define ELMK_RUN_ACCUM " + str(st.RUN_ACCUM) + r"\b", hdr) and st.RUN_ACCUM == 4
+    assert re.search(r"#define ELMK_ACCUM_MAX_ENTRIES " + str(accum.MAX_ENTRIES) + r"\b", hdr)
+    assert re.search(r"#define ELMK_RESTART_VERSION 1u", hdr) and re.search(r"#define ELMK_RESTART_VERSION_ACCUM 2u", hdr)
+    assert (st.ACCUM_RUNMEAN, st.ACCUM_TIMEAVG, st.ACCUM_RUNACCUM, st.ACCUM_MAX_ENTRIES) == (0, 1, 2, accum.MAX_ENTRIES)
+    assert st.ACCUM_KINDS == accum.KINDS
+    for m in ("accum_add", "accum_init", "accum_update", "accum_read", "accum_clear"):
+        assert callable(getattr(st.ELMState, m))
+    cpp = open(os.path.join(ROOT, "include", "elmk_interface.hpp")).read()
+    for name in NEW_SYMBOLS:
+        assert name in cpp, name
+
+
+def test_t10_is_a_surface_field_and_the_struct_matches_the_codec(tmp_path):
+    import subprocess
+
+    assert st.field_class("t10") == st.CLASS_SURFACE
+    src = tmp_path / "l.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "elmk.h"\nint main(void){printf("%zu %zu %zu\\n",'
+                   "sizeof(elmk_restart_accum), offsetof(elmk_restart_accum, period), offsetof(elmk_restart_accum, nsteps));return 0;}\n")
+    exe = tmp_path / "l"
+    subprocess.run(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [R.ACCUM.itemsize, R.ACCUM.fields["period"][1], R.ACCUM.fields["nsteps"][1]]
