@@ -113,6 +113,10 @@ SIGNATURES = {
     "elmk_accum_update": (C.c_int, [_P]),
     "elmk_accum_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     "elmk_accum_clear": (C.c_int, [_P]),
+    "elmk_aerosol_reserve": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
+    "elmk_aerosol_upload": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "elmk_aerosol_deposition": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "elmk_aerosol_clear": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

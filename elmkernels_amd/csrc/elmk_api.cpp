@@ -222,6 +222,7 @@ struct elmk_ctx {
     bool live[2] = {};
     int slot_lo[2] = {}, slot_hi[2] = {};
     unsigned months[2] = {};
+    unsigned aer_months[2] = {};  // the months of the aerosol series the run reads (ELMK_RUN_AEROSOL; 0 without the flag)
     uint64_t count = 0;  // runs enqueued since the reserve
     int last_buf = -1, last_nsteps = 0;
     int flags = 0;  // of the run being enqueued (the run step's stages)
@@ -285,6 +286,20 @@ struct elmk_ctx {
     double* wsum = nullptr;
     double* lg = nullptr;
   } ds;
+  // aerosol deposition (elmk_aerosol_reserve): one allocation `mem` holds the cell series [AER_NSTREAM][12][ncells] in fp64 and, unless
+  // the series is per column (npad 0), the ELL map of its grid [npad][ld] - idx (int32), w (fp64) - laid out as Grid's.  step_live: a
+  // stepwise elmk_aerosol_deposition has been enqueued since the last elmk_aerosol_upload waited for aer_step_done.
+  struct Aerosol {
+    int64_t ncells = 0;
+    int npts = 0, npad = 0;
+    DevBuf<char> mem;
+    size_t bytes = 0;
+    double* cells = nullptr;
+    int32_t* idx = nullptr;
+    double* w = nullptr;
+    bool step_live = false;
+  } aer;
+  hipEvent_t aer_step_done = nullptr;  // the end of the last stepwise elmk_aerosol_deposition (created by the first reservation)
   std::string err;
 };
 
@@ -484,7 +499,7 @@ int elmk_destroy(elmk_ctx* ctx)
   // 3. the memory: every allocation is a DevBuf member of the context
   const SideStreams side = ctx->side;
   const hipStream_t own = ctx->own_stream, upload = ctx->upload;
-  const hipEvent_t done[2] = {ctx->run_done[0], ctx->run_done[1]};
+  const hipEvent_t done[3] = {ctx->run_done[0], ctx->run_done[1], ctx->aer_step_done};
   delete ctx;
   // 4. the events and streams
   for (int i = 0; i < ELMK_NSIDE; i++) {
@@ -570,7 +585,7 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
   return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
                          ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes + ctx->sw.czf_bytes + ctx->run.rec_bytes +
-                         ctx->ds.topo_bytes + ctx->ds.gbytes + ctx->accum_bytes)
+                         ctx->ds.topo_bytes + ctx->ds.gbytes + ctx->accum_bytes + ctx->aer.bytes)
              : -1;
 }
 
@@ -1706,6 +1721,17 @@ int run_drop(elmk_ctx* ctx)
   return ELMK_OK;
 }
 
+// the internal copy stream of elmk_series_upload and elmk_aerosol_upload, with the events of the two run buffers
+int ensure_upload_stream(elmk_ctx* ctx)
+{
+  if (ctx->upload) return ELMK_OK;
+  HIPCHK(hipStreamCreateWithFlags(&ctx->upload, hipStreamNonBlocking));
+  for (int b = 0; b < 2; b++) {
+    HIPCHK(hipEventCreateWithFlags(&ctx->run_done[b], hipEventDisableTiming));
+  }
+  return ELMK_OK;
+}
+
 void run_solar_geometry(elmk_ctx* ctx, double)
 {
   if (ctx->sw.mode == ELMK_SW_COSZEN)
@@ -1727,6 +1753,16 @@ void run_forcing(elmk_ctx* ctx, double)
   else
     launch_get_forcing_run(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf, ds);
   ds_lw_norm(ctx);
+}
+AerSeries aer_series(const elmk_ctx* ctx)
+{
+  const elmk_ctx::Aerosol& A = ctx->aer;
+  return AerSeries{A.cells, A.ncells, A.npad, A.idx, A.w};
+}
+void run_aerosol(elmk_ctx* ctx, double)
+{
+  if (ctx->run.flags & ELMK_RUN_AEROSOL)
+    launch_aerosol_deposition_run(ctx->d, ctx->ncols, aer_series(ctx), ctx->run.table, ctx->run.cursor, ctx->stream);
 }
 void run_init_timestep(elmk_ctx* ctx, double) { launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); }
 void run_conservation(elmk_ctx* ctx, double dt)
@@ -1751,9 +1787,10 @@ void run_history(elmk_ctx* ctx, double)
 void run_next(elmk_ctx* ctx, double) { launch_run_next(ctx->run.cursor, ctx->stream); }
 
 // one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
-// forcing, init_timestep, advance_physics' stages, conservation -> ring row, flag summary -> ring row, accumulated fields, history,
-// next row
-constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},   {run_forcing, nullptr}, {run_init_timestep, nullptr},
+// forcing, aerosol deposition (ELMK_RUN_AEROSOL: where the reference's hook sits, init_timestep_kokkos.cc:48-49), init_timestep,
+// advance_physics' stages, conservation -> ring row, flag summary -> ring row, accumulated fields, history, next row
+constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},   {run_forcing, nullptr}, {run_aerosol, nullptr},
+                              {run_init_timestep, nullptr},
                               ADVANCE[0], ADVANCE[1], ADVANCE[2], ADVANCE[3], ADVANCE[4], ADVANCE[5], ADVANCE[6], ADVANCE[7],
                               {run_conservation, nullptr},   {run_flag_reduce, nullptr}, {run_accum, nullptr},   {run_history, nullptr},
                               {run_next, nullptr}};
@@ -1768,12 +1805,7 @@ int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
   if (int rc = refuse_capture(ctx, "elmk_run_reserve: the stream is being captured")) return rc;
   elmk_ctx::Run& R = ctx->run;
   if (int rc = run_drop(ctx)) return rc;
-  if (!ctx->upload) {
-    HIPCHK(hipStreamCreateWithFlags(&ctx->upload, hipStreamNonBlocking));
-    for (int b = 0; b < 2; b++) {
-      HIPCHK(hipEventCreateWithFlags(&ctx->run_done[b], hipEventDisableTiming));
-    }
-  }
+  if (int rc = ensure_upload_stream(ctx)) return rc;
   const size_t es = (size_t)store_size(ELMK_F64), ld = (size_t)ctx->ld, nrow = 2 * (size_t)max_steps;
   // with a forcing grid the forcing records are cell records, [RUN_NFORC][slots][ncells] without padding
   const int64_t fstride = ctx->grid.mem ? ctx->grid.ncells : ctx->ld;
@@ -1852,7 +1884,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   if (!ctx->snowage_set) return invalid(ctx, "elmk_run: the snow-age tables are not set (elmk_set_snow_age_tables)");
   if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
   if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
-  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM)) return invalid(ctx, "elmk_run: unknown flags");
+  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL)) return invalid(ctx, "elmk_run: unknown flags");
+  if ((flags & ELMK_RUN_AEROSOL) && !ctx->aer.mem) return invalid(ctx, "elmk_run: ELMK_RUN_AEROSOL without an aerosol series (elmk_aerosol_reserve)");
   if ((flags & ELMK_RUN_ACCUM) && ctx->accum.empty()) return invalid(ctx, "elmk_run: ELMK_RUN_ACCUM without an accumulator entry (elmk_accum_add)");
   const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   int lo = R.slots, hi = -1;
@@ -1899,6 +1932,7 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.slot_lo[buf] = lo;
   R.slot_hi[buf] = hi;
   R.months[buf] = months;
+  R.aer_months[buf] = (flags & ELMK_RUN_AEROSOL) ? months : 0u;
   R.count++;
   R.last_buf = buf;
   R.last_nsteps = nsteps;
@@ -1991,6 +2025,136 @@ int elmk_clear_forcing_grid(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, "elmk_clear_forcing_grid: the stream is being captured")) return rc;
   if (int rc = run_drop(ctx)) return rc;
   ctx->grid = elmk_ctx::Grid{};
+  return ELMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// aerosol deposition: a monthly climatology on a grid of its own, interpolated on the device (include/elmk.h "aerosol deposition")
+// ---------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+// wait for the runs in flight and the copy stream, and drop the captured run step (it holds the series' and the map's addresses and
+// the kernel of the map's width); the run reservation stays
+int aerosol_quiesce(elmk_ctx* ctx)
+{
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (ctx->upload) HIPCHK(hipStreamSynchronize(ctx->upload));
+  ctx->graph[GRAPH_RUN_STEP].drop();
+  return ELMK_OK;
+}
+bool aerosol_field(int f) { return f >= ELMK_FIELD_aer_bcphi && f <= ELMK_FIELD_aer_dst4_2; }
+}  // namespace
+
+extern "C" {
+
+int elmk_aerosol_reserve(elmk_ctx* ctx, int64_t ncells, int npts, const int32_t* idx, const double* w)
+{
+  if (int rc = enter(ctx)) return rc;
+  const int64_t n = ctx->ncols;
+  if ((idx == nullptr) != (w == nullptr)) return invalid(ctx, "elmk_aerosol_reserve: idx and w must both be given or both be NULL");
+  const bool mapped = idx != nullptr;
+  if (ncells < 1 || ncells > INT32_MAX) return invalid(ctx, "elmk_aerosol_reserve: ncells outside 1 .. 2^31-1");
+  if (!mapped && ncells != n) return invalid(ctx, "elmk_aerosol_reserve: without a map the series are per column: ncells must equal ncols");
+  if (mapped) {
+    if (npts < 1 || npts > 8) return invalid(ctx, "elmk_aerosol_reserve: npts outside 1 .. 8");
+    // every gather of k_aerosol_deposition stays inside a cell record because of these checks
+    for (int k = 0; k < npts; k++) {
+      const int32_t* ik = idx + (size_t)k * n;
+      const double* wk = w + (size_t)k * n;
+      const int32_t lo = k == 0 ? 0 : -1;
+      for (int64_t c = 0; c < n; c++) {
+        if (ik[c] < lo || ik[c] >= ncells)
+          return invalid(ctx, k == 0 ? "elmk_aerosol_reserve: idx[0] outside [0, ncells)" : "elmk_aerosol_reserve: idx outside [-1, ncells)");
+        if (ik[c] >= 0 && !std::isfinite(wk[c])) return invalid(ctx, "elmk_aerosol_reserve: non-finite weight");
+      }
+    }
+  }
+  if (int rc = refuse_capture(ctx, "elmk_aerosol_reserve: the stream is being captured")) return rc;
+  if (int rc = aerosol_quiesce(ctx)) return rc;
+  if (int rc = ensure_upload_stream(ctx)) return rc;
+  if (!ctx->aer_step_done) HIPCHK(hipEventCreateWithFlags(&ctx->aer_step_done, hipEventDisableTiming));
+  elmk_ctx::Aerosol& A = ctx->aer;
+  A = elmk_ctx::Aerosol{};
+  const int npad = !mapped ? 0 : npts <= 1 ? 1 : npts <= 2 ? 2 : npts <= 4 ? 4 : 8;
+  const size_t ld = (size_t)ctx->ld;
+  if (hip_fail(ctx, carve(A.mem, &A.bytes, [&](Carve& L) {
+                 L.take(A.cells, (size_t)AER_NSTREAM * RUN_NMONTH * (size_t)ncells * sizeof(double));
+                 if (npad) {
+                   L.take(A.idx, (size_t)npad * ld * sizeof(int32_t));
+                   L.take(A.w, (size_t)npad * ld * sizeof(double));
+                 }
+               }), "hipMalloc(aerosol series)"))
+    return ELMK_E_NOMEM;
+  A.ncells = ncells;
+  A.npts = mapped ? npts : 0;
+  A.npad = npad;
+  // the series start at 0; padding rows and the columns past ncols: idx -1 (all bits set), w 0
+  int rc = ELMK_OK;
+  const size_t series_bytes = npad ? (size_t)((char*)A.idx - (char*)A.cells) : A.bytes;
+  if (hip_fail(ctx, hipMemsetAsync(A.cells, 0, series_bytes, ctx->stream), "hipMemset(aerosol series)"))
+    rc = ELMK_E_HIP;
+  else if (npad && (hip_fail(ctx, hipMemsetAsync(A.idx, 0xFF, (char*)A.w - (char*)A.idx, ctx->stream), "hipMemset(aerosol idx)") ||
+                    hip_fail(ctx, hipMemsetAsync(A.w, 0, A.mem + A.bytes - (char*)A.w, ctx->stream), "hipMemset(aerosol w)")))
+    rc = ELMK_E_HIP;
+  else if (npad && n > 0 &&
+           (hip_fail(ctx, hipMemcpy2DAsync(A.idx, ld * sizeof(int32_t), idx, (size_t)n * sizeof(int32_t), (size_t)n * sizeof(int32_t),
+                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(aerosol idx)") ||
+            hip_fail(ctx, hipMemcpy2DAsync(A.w, ld * sizeof(double), w, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
+                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(aerosol w)")))
+    rc = ELMK_E_HIP;
+  if (rc == ELMK_OK && hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) rc = ELMK_E_HIP;
+  if (rc != ELMK_OK) A = elmk_ctx::Aerosol{};
+  return rc;
+}
+
+int elmk_aerosol_upload(elmk_ctx* ctx, int field, int month0, int nmonths, const double* host)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Aerosol& A = ctx->aer;
+  if (!A.mem) return invalid(ctx, "elmk_aerosol_upload: elmk_aerosol_reserve has not been called");
+  if (!aerosol_field(field)) return invalid(ctx, "elmk_aerosol_upload: not a deposition stream (aer_bcphi .. aer_dst4_2)");
+  if (month0 < 0 || nmonths < 1 || month0 + (int64_t)nmonths > RUN_NMONTH) return invalid(ctx, "elmk_aerosol_upload: months outside 0 .. 11");
+  if (!host) return invalid(ctx, "elmk_aerosol_upload: null host");
+  if (int rc = refuse_capture(ctx, "elmk_aerosol_upload: the stream is being captured")) return rc;  // (it waits)
+  // never write under a reader of these months: each enqueued, unfinished run that reads them, and the stepwise depositions
+  const elmk_ctx::Run& R = ctx->run;
+  for (int b = 0; b < 2; b++)
+    if (R.live[b] && ((R.aer_months[b] >> month0) & ((1u << nmonths) - 1u)) != 0) HIPCHK(hipEventSynchronize(ctx->run_done[b]));
+  if (A.step_live) {
+    HIPCHK(hipEventSynchronize(ctx->aer_step_done));
+    A.step_live = false;
+  }
+  const int k = field - ELMK_FIELD_aer_bcphi;
+  double* dst = A.cells + ((size_t)k * RUN_NMONTH + (size_t)month0) * (size_t)A.ncells;
+  HIPCHK(hipMemcpyAsync(dst, host, (size_t)nmonths * (size_t)A.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->upload));
+  HIPCHK(hipStreamSynchronize(ctx->upload));  // (caller's pageable source; a deposition or run enqueued after this call sees the months)
+  return ELMK_OK;
+}
+
+int elmk_aerosol_deposition(elmk_ctx* ctx, int month1, int month2, double wt1, double wt2)
+{
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Aerosol& A = ctx->aer;
+  if (!A.mem) return invalid(ctx, "elmk_aerosol_deposition: elmk_aerosol_reserve has not been called");
+  if (month1 < 0 || month1 >= RUN_NMONTH || month2 < 0 || month2 >= RUN_NMONTH) return invalid(ctx, "elmk_aerosol_deposition: month outside 0 .. 11");
+  if (!std::isfinite(wt1) || !std::isfinite(wt2)) return invalid(ctx, "elmk_aerosol_deposition: non-finite weight");
+  if (int rc = refuse_capture(ctx, "elmk_aerosol_deposition: the stream is being captured")) return rc;
+  if (int rc = heal_lists(ctx)) return rc;
+  if (int rc = push_params(ctx)) return rc;
+  launch_aerosol_deposition(ctx->d, ctx->ncols, aer_series(ctx), month1, month2, wt1, wt2, ctx->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->aer_step_done, ctx->stream));
+  A.step_live = true;
+  return ELMK_OK;
+}
+
+int elmk_aerosol_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_aerosol_clear: the stream is being captured")) return rc;
+  if (int rc = aerosol_quiesce(ctx)) return rc;
+  ctx->aer = elmk_ctx::Aerosol{};
   return ELMK_OK;
 }
 

@@ -210,6 +210,25 @@ void launch_accum_update(const AccumRow* rows, int nrows, unsigned long long* ns
 // val[lev][c] = the stored value of src[lev][c] widened to fp64, nlev rows of stride ld each (elmk_accum_init without host values)
 void launch_accum_seed(const void* src, int dtype, double* val, int nlev, int64_t ld, int64_t ncols, hipStream_t st);
 
+// aerosol deposition (k_aerosol.hip, elmk_aerosol_*): the series cells[AER_NSTREAM][RUN_NMONTH][ncells] (fp64 in both builds) and the
+// ELL map of its grid, idx / w [npad][ld] as the forcing grid's (npad = 1, 2, 4 or 8, padding idx = -1); npad = 0: per-column series
+// (ncells == ncols), idx and w null
+constexpr int AER_NSTREAM = 11;
+static_assert(ELMK_FIELD_aer_dst4_2 - ELMK_FIELD_aer_bcphi + 1 == AER_NSTREAM, "the eleven deposition streams are consecutive fields");
+struct AerSeries {
+  const double* cells;
+  int64_t ncells;
+  int npad;
+  const int32_t* idx;
+  const double* w;
+};
+// aer_s[c] = wt1 * remap(cells[s][month1]) + wt2 * remap(cells[s][month2]) for the eleven streams of columns [0, n)
+void launch_aerosol_deposition(const DevState* S, int64_t n, const AerSeries& A, int month1, int month2, double wt1, double wt2,
+                               hipStream_t st);
+// the same with month1, month2, month_wt1, month_wt2 of table row *cursor (elmk_run)
+void launch_aerosol_deposition_run(const DevState* S, int64_t n, const AerSeries& A, const RunRow* rows, const int32_t* cursor,
+                                   hipStream_t st);
+
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element
 struct RstPiece {

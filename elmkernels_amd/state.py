@@ -25,7 +25,7 @@ HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, 
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
 CLASS_PROGNOSTIC, CLASS_SURFACE, CLASS_FORCING, CLASS_DIAGNOSTIC = range(4)  # elmk_field_class
 CLASS_NAMES = ("prognostic", "surface", "forcing", "diagnostic")
-RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM = 1, 2, 4  # elmk_run flags
+RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM, RUN_AEROSOL = 1, 2, 4, 8  # elmk_run flags
 ACCUM_RUNMEAN, ACCUM_TIMEAVG, ACCUM_RUNACCUM = range(3)  # elmk_accum_add
 ACCUM_KINDS = {"runmean": ACCUM_RUNMEAN, "timeavg": ACCUM_TIMEAVG, "runaccum": ACCUM_RUNACCUM}
 ACCUM_MAX_ENTRIES = 16
@@ -421,6 +421,51 @@ class ELMState:
         self._chk(self.lib.elmk_accum_clear(self.ctx), "accum_clear")
         self._accum_nlev.clear()
 
+    # -- aerosol deposition (include/elmk.h: elmk_aerosol_reserve ...; elmkernels_amd/aerosol.py restates the kernel) ----------
+    def aerosol_reserve(self, ncells=None, idx=None, w=None):
+        """The device series of the eleven deposition streams x 12 months x ncells (fp64, zero-filled) and the map of the aerosol
+        grid: idx int32 [npts, ncols] (-1 = padding, never in row 0) and w float64 [npts, ncols] (regrid.nearest_map,
+        regrid.bilinear_map), or neither for per-column series (ncells = ncols).  Replaces an earlier reservation; the run reservation
+        and the forcing grid stay."""
+        if (idx is None) != (w is None):
+            raise ValueError("idx and w: both or neither")
+        if idx is None:
+            ncells = self.ncols if ncells is None else int(ncells)
+            self._chk(self.lib.elmk_aerosol_reserve(self.ctx, ncells, 0, None, None), "aerosol_reserve")
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if idx.ndim == 1:
+                idx, w = idx[None, :], w.reshape(1, -1)
+            if idx.shape != w.shape or idx.shape[1] != self.ncols:
+                raise ValueError(f"idx and w must both be [npts, {self.ncols}]")
+            if ncells is None:
+                raise ValueError("aerosol_reserve: ncells of the aerosol grid is needed with a map")
+            self._chk(self.lib.elmk_aerosol_reserve(self.ctx, int(ncells), idx.shape[0], idx.ctypes.data_as(C.c_void_p),
+                                                    w.ctypes.data_as(C.c_void_p)), "aerosol_reserve")
+        self.aerosol_ncells = int(ncells)
+
+    def aerosol_upload(self, name, month0, records):
+        """Months [month0, month0 + nmonths) of one stream ("aer_bcphi" .. "aer_dst4_2", or without the prefix) from records
+        [nmonths, ncells] (or [ncells] for one month).  Waits for a run or deposition in flight that reads them."""
+        a = np.ascontiguousarray(records, dtype=np.float64)
+        if a.ndim == 1:
+            a = a[None, :]
+        nc = getattr(self, "aerosol_ncells", None)
+        if nc is not None and a.shape[1] != nc:
+            raise ValueError(f"{name}: {a.shape[1]} cell values per month, the series has {nc}")
+        fid = self.fields[name if name in self.fields else "aer_" + name][0] if isinstance(name, str) else int(name)
+        self._chk(self.lib.elmk_aerosol_upload(self.ctx, fid, int(month0), a.shape[0], a.ctypes.data_as(C.c_void_p)), f"aerosol_upload({name})")
+
+    def aerosol_deposition(self, month1, month2, wt1, wt2):
+        """aer_* of every column = wt1 * (month1 remapped) + wt2 * (month2 remapped), one launch, stream-ordered, no sync."""
+        self._chk(self.lib.elmk_aerosol_deposition(self.ctx, int(month1), int(month2), float(wt1), float(wt2)), "aerosol_deposition")
+
+    def aerosol_clear(self):
+        """Free the aerosol series and map (aer_* keep their values)."""
+        self._chk(self.lib.elmk_aerosol_clear(self.ctx), "aerosol_clear")
+        self.aerosol_ncells = None
+
     # -- multi-step runs (include/elmk.h: elmk_run ...) ---------------------------------------------
     def run_reserve(self, forcing_slots, max_steps):
         """Device series of `forcing_slots` forcing records and 12 months, and step tables / diagnostics rings of `max_steps` rows."""
@@ -802,13 +847,15 @@ class ELMInterface:
             raise RuntimeError(f"ELM physics error flags {flags:#x}, first at column {col}")
         return False
 
-    def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False, update_accum=False):
+    def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False, update_accum=False, update_aerosol=False):
         """ELMInterface::advance for every row of steps (RUN_STEP_DTYPE) in one call (elmk_run; needs S.run_reserve and the series
         uploaded); self.conservation = the last step's triples, self.run_conservation = all of them.  update_accum: every step updates
-        the accumulated fields registered on self.S (ELM's UpdateAccVars: after the physics, before the history).  Raises after the
-        run if a step raised a fatal flag, naming the first such step and column."""
+        the accumulated fields registered on self.S (ELM's UpdateAccVars: after the physics, before the history).  update_aerosol: every
+        step interpolates aer_* from the aerosol series of self.S (S.aerosol_reserve / aerosol_upload) over the step's month bracket,
+        between the forcing and init_timestep.  Raises after the run if a step raised a fatal flag, naming the first such step and column."""
         S = self.S
         flags = (RUN_HISTORY if accumulate_history else 0) | (RUN_QBOT_IS_RH if qbot_is_rh else 0) | (RUN_ACCUM if update_accum else 0)
+        flags |= RUN_AEROSOL if update_aerosol else 0
         S.run(dt_seconds, steps, flags)
         mms, fo, fb = S.run_diagnostics()
         self.run_conservation = mms
@@ -860,6 +907,11 @@ class ELMInterface:
     def accumulate_history(self):
         """Fold this step's state into the history tapes registered on self.S (ELMState.history_add): call after advance()."""
         self.S.history_accumulate()
+
+    def update_aerosol(self, month1, month2, wt1, wt2):
+        """aer_* from the aerosol series of self.S (ELMState.aerosol_deposition): call before advance(), with the month bracket that
+        feeds advance()'s month_wt1 / month_wt2 (the reference's hook, init_timestep_kokkos.cc:48-49)."""
+        self.S.aerosol_deposition(month1, month2, wt1, wt2)
 
     def update_accum(self):
         """Update the accumulated fields registered on self.S (ELMState.accum_add): call after advance(), before accumulate_history()."""

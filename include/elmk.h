@@ -296,6 +296,7 @@ int elmk_history_clear(elmk_ctx *ctx);
  *   elmk_run             for each step s, the bits of the calls
  *                          elmk_solar_geometry(dt, decday, doy); elmk_phenology(month_wt1, month_wt2) over months month1 / month2;
  *                          elmk_get_forcing(forc_wt1, forc_wt2, flags & ELMK_RUN_QBOT_IS_RH) over slots forc_slot / forc_slot + 1;
+ *                          with ELMK_RUN_AEROSOL: elmk_aerosol_deposition(month1, month2, month_wt1, month_wt2) ("aerosol deposition");
  *                          elmk_init_timestep; elmk_advance_physics(dt); elmk_evaluate_conservation -> ring row s;
  *                          elmk_error_summary -> ring row s (flags sticky, as that call sees them after the step);
  *                          with ELMK_RUN_ACCUM: elmk_accum_update ("accumulated fields");
@@ -320,6 +321,7 @@ typedef struct {
 } elmk_run_step;
 enum { ELMK_RUN_QBOT_IS_RH = 1, ELMK_RUN_HISTORY = 2 };
 #define ELMK_RUN_ACCUM 4 /* the third flag bit: every step updates the accumulated fields ("accumulated fields" below) */
+#define ELMK_RUN_AEROSOL 8 /* the fourth flag bit: every step interpolates the aerosol deposition streams ("aerosol deposition" below) */
 int elmk_run_reserve(elmk_ctx *ctx, int forcing_slots, int max_steps);
 int elmk_series_upload(elmk_ctx *ctx, int field, int slot0, int nslots, const double *host, int64_t col0, int64_t n);
 int elmk_run(elmk_ctx *ctx, double dt, const elmk_run_step *steps, int nsteps, int flags);
@@ -533,6 +535,66 @@ int elmk_accum_init(elmk_ctx *ctx, int entry, const double *host /*[nlev][ncols]
 int elmk_accum_update(elmk_ctx *ctx);
 int elmk_accum_read(elmk_ctx *ctx, int entry, double *host, int64_t col0, int64_t n, int layout, int64_t *nsteps);
 int elmk_accum_clear(elmk_ctx *ctx);
+
+/* ---- aerosol deposition -----------------------------------------------------------------------
+ * The eleven deposition streams aer_bcphi .. aer_dst4_2 (aero_data::AerosolFileInput, src/data/aerosol_data.h:10-28; kg/m2/s) are
+ * what snow hydrology's compute_aerosol_deposition reads every step to grow the snow aerosol masses mss_*, which SNICAR turns into
+ * snow albedo.  No kernel of the step writes them: without these calls they keep whatever was uploaded, and a long elmk_run has no
+ * dust season.  ELM holds the input as twelve monthly records per stream on the aerosol file's own coarse grid (1.9 x 2.5 deg) and
+ * interpolates every stream in time every step (aerdepini / aerinterp); the reference has the hook commented out at
+ * init_timestep_kokkos.cc:48-49 (aerosol_data_old_impl.hh:32-55: the month bracket of monthly_data and a nearest-cell pick).  Here
+ * the twelve months of every stream live on the device, on a grid of their own, and one kernel writes the eleven fields.
+ * For every stream s (field ELMK_FIELD_aer_bcphi + s, AerosolFileInput's member order) and column c, without contraction:
+ *   r1 = remap of cells x[s][month1] to column c;  r2 = remap of cells x[s][month2] to column c
+ *   aer_s[c] = wt1 * r1 + wt2 * r2
+ * - two products and one sum, as written also when month1 == month2 or a weight is 0 or 1: weights (1, 0) give x * 1 + y * 0, not a
+ * copy, so a NaN or infinity in the other month propagates (NaN * 0 = NaN) and -0.0 * 1 + x * 0 is +0.0.  The remap is
+ * elmk_set_forcing_grid's, in its operation order (regrid.apply_map): v = w[0][c] * a[idx[0][c]], then for k = 1 .. npts-1, if
+ * idx[k][c] >= 0, v = v + w[k][c] * a[idx[k][c]]; idx = -1 is padding, skipped and never multiplied.  Without a map (per-column
+ * series) r = x[s][month][c] itself.  The result is stored at state precision (rounded to fp32 in libelmk_f32.so, as elmk_upload
+ * rounds).  Every stream is interpolated on its own, as aerinterp does; the sums bcpho + bcdep, dstX_1 + dstX_2 and the * dtime stay
+ * in snow hydrology (aerosol_physics_impl.hh:49-57).  elmkernels_amd/aerosol.py: interpolate is this operation on the host.
+ *   elmk_aerosol_reserve     allocates the cell series [11][12][ncells], fp64 in both builds (a few MB: one arithmetic for both),
+ *                            zero-filled, and keeps a map of the aerosol grid in the ELL form, padding and validation of
+ *                            elmk_set_forcing_grid: idx[npts][ncols] / w[npts][ncols] copied, npts 1 .. 8 stored as npad = 1, 2, 4
+ *                            or 8 rows (regrid.nearest_map: the reference's nearest-cell pick; regrid.bilinear_map: what ELM's
+ *                            stream mapping does).  idx == NULL and w == NULL: per-column series, ncells must equal ncols, npts is
+ *                            ignored and no map is stored.  Independent of the forcing grid and of the run reservation: setting or
+ *                            clearing it releases neither.  Waits for the runs in flight, drops the captured run step (the next
+ *                            elmk_run under elmk_set_graph captures again) and replaces an earlier reservation, series included.
+ *                            ELMK_E_INVALID, nothing enqueued: only one of idx, w NULL; ncells outside 1 .. 2^31-1; ncells != ncols
+ *                            without a map; npts outside 1 .. 8; idx[0][c] outside [0, ncells); idx[k][c] outside [-1, ncells) for
+ *                            k >= 1; a non-finite weight where idx >= 0; a stream being captured.
+ *                            Device memory (elmk_device_bytes): 11 x 12 x ncells x 8 bytes for the series and, with a map, npad x 4
+ *                            bytes x elmk_level_stride (idx) and npad x 8 bytes x elmk_level_stride (w), each of the three rounded
+ *                            up to 256 bytes.
+ *   elmk_aerosol_upload      months [month0, month0 + nmonths) of one stream from host[nmonths][ncells], record-major.  The copy runs
+ *                            on the internal copy stream, so it overlaps a run in flight; it first waits for every enqueued,
+ *                            unfinished reader of those months (an elmk_run with ELMK_RUN_AEROSOL whose steps name one of them, any
+ *                            elmk_aerosol_deposition) and returns when the copy is done: elmk_series_upload's contract.
+ *                            ELMK_E_INVALID: no reservation, a field that is not one of the eleven, month0 < 0, nmonths < 1,
+ *                            month0 + nmonths > 12, host NULL, a stream being captured.
+ *   elmk_aerosol_deposition  one kernel launch that writes all eleven fields of every column and touches nothing else; stream-ordered,
+ *                            no synchronisation.  Picking the months and weights is date arithmetic and stays with the caller, as
+ *                            for elmk_phenology (monthly_data.cc:29-62); the reference's commented call would pass the step-centred
+ *                            date.  ELMK_E_INVALID, nothing enqueued: no reservation, a month outside 0 .. 11, a non-finite weight,
+ *                            a stream being captured (it is captured only as part of elmk_run's own step).
+ *   elmk_aerosol_clear       free the series and the map; aer_* keep their values.  Waits and drops the captured step as the reserve.
+ * elmk_run with ELMK_RUN_AEROSOL runs the same kernel in every step between the forcing kernel and elmk_init_timestep, where the
+ * reference's hook sits, with month1, month2, month_wt1, month_wt2 of the step's row.  This is a decision: elmk_run_step does not grow,
+ * the aerosol interpolation uses the PHENOLOGY bracket of the step (the step-start date's), not a step-centred bracket of its own.  A
+ * run with the flag overwrites aer_* and gives, bit for bit and with the graph on or off, the stepwise calls with
+ * elmk_aerosol_deposition(month1, month2, month_wt1, month_wt2) before elmk_init_timestep; without the flag aer_* are read-only, as
+ * they were.  ELMK_E_INVALID before anything is enqueued for the flag without a reservation.
+ * Restart: aer_* are SURFACE fields, so an image carries them.  The series are an input like the forcing series and are not in the
+ * image: reserve and upload again after elmk_restart_load.  The image format does not change.
+ * A context that never calls these runs the kernels, launch sequences and graphs it ran before and allocates nothing more. */
+int elmk_aerosol_reserve(elmk_ctx *ctx, int64_t ncells, int npts, const int32_t *idx /*[npts][ncols] or NULL*/,
+                         const double *w /*[npts][ncols] or NULL*/);
+int elmk_aerosol_upload(elmk_ctx *ctx, int field /*ELMK_FIELD_aer_bcphi .. ELMK_FIELD_aer_dst4_2*/, int month0, int nmonths,
+                        const double *host /*[nmonths][ncells]*/);
+int elmk_aerosol_deposition(elmk_ctx *ctx, int month1, int month2, double wt1, double wt2);
+int elmk_aerosol_clear(elmk_ctx *ctx);
 
 /* ---- restart ---------------------------------------------------------------------------------
  * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state

@@ -311,10 +311,11 @@ class ELMInterface {
     ok(elmk_series_upload(ctx_, id(field), slot0, nslots, host, 0, ncols_));
   }
   void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
-                   bool update_accum = false)
+                   bool update_accum = false, bool update_aerosol = false)
   {
     ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(),
-                (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0) | (update_accum ? ELMK_RUN_ACCUM : 0)));
+                (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0) | (update_accum ? ELMK_RUN_ACCUM : 0) |
+                    (update_aerosol ? ELMK_RUN_AEROSOL : 0)));
   }
   bool finish_run()
   {
@@ -336,12 +337,26 @@ class ELMInterface {
     return false;
   }
   bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
-           bool update_accum = false)
+           bool update_accum = false, bool update_aerosol = false)
   {
-    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum);
+    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol);
     return finish_run();
   }
   const std::vector<double>& run_conservation() const { return run_conservation_; }
+
+  /* Aerosol deposition (elmk.h "aerosol deposition"; ELM's aerdepini / aerinterp, the hook the reference leaves commented out at
+   * init_timestep_kokkos.cc:48-49): aerosol_reserve() allocates the twelve months of the eleven streams aer_bcphi .. aer_dst4_2 on
+   * the aerosol file's own grid of ncells cells, with the map idx[npts][ncols] / w[npts][ncols] from that grid to the columns (both
+   * nullptr: per-column series, ncells = ncols); aerosol_upload() fills months [month0, month0 + nmonths) of one stream from
+   * host[nmonths][ncells].  update_aerosol() before advance() writes the eleven fields from the month bracket that also feeds
+   * advance()'s month weights; run(..., update_aerosol = true) does it in every step from the step's month1 / month2 / weights. */
+  void aerosol_reserve(int64_t ncells, int npts, const int32_t* idx, const double* w) { ok(elmk_aerosol_reserve(ctx_, ncells, npts, idx, w)); }
+  void aerosol_upload(const char* field, int month0, int nmonths, const double* host)
+  {
+    ok(elmk_aerosol_upload(ctx_, id(field), month0, nmonths, host));
+  }
+  void update_aerosol(int month1, int month2, double wt1, double wt2) { ok(elmk_aerosol_deposition(ctx_, month1, month2, wt1, wt2)); }
+  void aerosol_clear() { ok(elmk_aerosol_clear(ctx_)); }
 
   /* Forcing on a coarser grid (elmk_set_forcing_grid): the per-column map idx[npts][ncols] / w[npts][ncols] over ncells source
    * cells.  upload_gridded() remaps one level of an fp64 field from cells[ncells] on the device (the stepwise driver's path);
