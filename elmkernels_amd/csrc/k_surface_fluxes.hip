@@ -201,7 +201,12 @@ __global__ __launch_bounds__(256) void k_conservation(const DevState* __restrict
   d[(int64_t)7 * ld] = fsa - eflx_lwrad_net;
 }
 
-// (min, max, sum) of each diagnostic: stage 1 one partial triple per workgroup, stage 2 one workgroup per diagnostic
+// (min, max, sum) of each diagnostic: stage 1 one partial triple per workgroup, stage 2 one workgroup per diagnostic.
+// The order is part of the contract (include/elmk.h: elmk_evaluate_conservation; elmkernels_amd/diagnostics.py: reduce_min_max_sum
+// restates it): a thread folds its grid-stride elements in index order into (+inf, -inf, +0.0), the workgroup's tree takes
+// a[t] = op(a[t], a[t + s]) for s = 128 .. 1.  min / max are NaN-sticky (fmin / fmax would drop a NaN column from a health check).
+__device__ __forceinline__ double cons_min(double acc, double v) { return (v < acc || v != v) ? v : acc; }
+__device__ __forceinline__ double cons_max(double acc, double v) { return (v > acc || v != v) ? v : acc; }
 __global__ __launch_bounds__(256) void k_cons_reduce1(const double* __restrict__ diag, int64_t ld, int64_t n, double* __restrict__ part)
 {
   __shared__ double s_min[256], s_max[256], s_sum[256];
@@ -210,8 +215,8 @@ __global__ __launch_bounds__(256) void k_cons_reduce1(const double* __restrict__
   double mn = INFINITY, mx = -INFINITY, sm = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const double v = x[i];
-    mn = fmin(mn, v);
-    mx = fmax(mx, v);
+    mn = cons_min(mn, v);
+    mx = cons_max(mx, v);
     sm += v;
   }
   s_min[threadIdx.x] = mn;
@@ -220,8 +225,8 @@ __global__ __launch_bounds__(256) void k_cons_reduce1(const double* __restrict__
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
-      s_min[threadIdx.x] = fmin(s_min[threadIdx.x], s_min[threadIdx.x + s]);
-      s_max[threadIdx.x] = fmax(s_max[threadIdx.x], s_max[threadIdx.x + s]);
+      s_min[threadIdx.x] = cons_min(s_min[threadIdx.x], s_min[threadIdx.x + s]);
+      s_max[threadIdx.x] = cons_max(s_max[threadIdx.x], s_max[threadIdx.x + s]);
       s_sum[threadIdx.x] += s_sum[threadIdx.x + s];
     }
     __syncthreads();
@@ -242,8 +247,8 @@ __device__ __forceinline__ void cons_reduce2_block(const double* __restrict__ pa
   double mn = INFINITY, mx = -INFINITY, sm = 0.0;
   for (int i = threadIdx.x; i < nblk; i += blockDim.x) {
     const double* p = part + ((int64_t)k * nblk + i) * 3;
-    mn = fmin(mn, p[0]);
-    mx = fmax(mx, p[1]);
+    mn = cons_min(mn, p[0]);
+    mx = cons_max(mx, p[1]);
     sm += p[2];
   }
   s_min[threadIdx.x] = mn;
@@ -252,8 +257,8 @@ __device__ __forceinline__ void cons_reduce2_block(const double* __restrict__ pa
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
-      s_min[threadIdx.x] = fmin(s_min[threadIdx.x], s_min[threadIdx.x + s]);
-      s_max[threadIdx.x] = fmax(s_max[threadIdx.x], s_max[threadIdx.x + s]);
+      s_min[threadIdx.x] = cons_min(s_min[threadIdx.x], s_min[threadIdx.x + s]);
+      s_max[threadIdx.x] = cons_max(s_max[threadIdx.x], s_max[threadIdx.x + s]);
       s_sum[threadIdx.x] += s_sum[threadIdx.x + s];
     }
     __syncthreads();

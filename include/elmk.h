@@ -309,8 +309,8 @@ int elmk_history_clear(elmk_ctx *ctx);
  *                        mlai .. mhbot.  The step tables are double-buffered: run k+1 may be enqueued while run k executes;
  *                        enqueuing run k+2 waits until run k has finished.
  *   elmk_run_diagnostics synchronises, then copies the rows of the most recently enqueued run (any pointer may be NULL):
- *                        min_max_sum[nsteps][8][3] as elmk_evaluate_conservation, flags_or[nsteps] and first_bad_col[nsteps] (-1: none)
- *                        as elmk_error_summary.  Returns that run's nsteps (0 before the first run). */
+ *                        min_max_sum[nsteps][8][3] as elmk_evaluate_conservation (the same order of the sum, the same rule for
+ *                        NaN and infinities: see there), flags_or[nsteps] and first_bad_col[nsteps] (-1: none) as elmk_error_summary.  Returns that run's nsteps (0 before the first run). */
 typedef struct {
   double decday;                    /* decimal_doy(step start) + 1.0, as elmk_solar_geometry */
   int32_t doy;                      /* date.doy of the step start */
@@ -755,7 +755,15 @@ int elmk_phenology(elmk_ctx *ctx, double wt1, double wt2);
  * diagnostics in wrapper-local Views and prints column 0; here min_max_sum[8][3] receives (min, max, sum) over the
  * context's columns of dtend_column_h2o, errh2o, errh2osno, dwb, errsol, errlon, errseb, netrad - what a multi-GPU
  * run all-reduces with MIN / MAX / SUM (the reference's min_max_sum, src/utils/min_max_sum.hh:57-66) - and
- * per_column (may be NULL) the values themselves, [8][ncols].  Synchronises. */
+ * per_column (may be NULL) the values themselves, [8][ncols].  Synchronises.
+ *   Order of the sum.  The sum is a fixed function of the column values, as reduce_min_max_sum (elmkernels_amd/diagnostics.py)
+ *   restates it: T = 512 x 256 threads; thread g adds x[g], x[g + T], x[g + 2T], .. in that order to +0.0; each block of 256
+ *   consecutive threads then combines a[t] += a[t + s] for s = 128, 64, .., 1; one block does the same over the 512 block results
+ *   (thread j adds results j and j + 256 to +0.0, then the same tree).  The same columns give the same bits on every call, in a
+ *   run's rows, with and without a graph and after a restart; the bits depend on ncols (how a domain is split over contexts).
+ *   Non-finite values.  If any column's value of a diagnostic is NaN, that diagnostic's min, max and sum are all NaN: a NaN sticks,
+ *   as in the history tapes.  +inf and -inf are ordinary values (min = -inf, max = +inf; both among the columns give sum = NaN).
+ *   The sign of a min or max that is zero is unspecified. */
 int elmk_evaluate_conservation(elmk_ctx *ctx, double dt, double *min_max_sum, double *per_column);
 /* Everything ELMInterface::advance calls per column after kokkos_init_timestep, in its order
  * (elm_kokkos_interface.cc:289-316): the seven wrappers (as elmk_timestep7_fused), kokkos_soil_temperature,
