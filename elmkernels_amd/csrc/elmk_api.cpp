@@ -20,6 +20,7 @@
 
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
+#include "elmk_maps.h"
 
 using namespace elmk;
 
@@ -53,17 +54,19 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 thread_local std::string g_create_error;
 constexpr int MAXLEV_STAGE = 21;  // widest field (zisoi)
 
-// The owner of one device allocation (hipMalloc), or with Pinned of one pinned host allocation (hipHostMalloc): freed by reset()
-// and by its destructor (a move assignment hands the old block to the moved-from owner).  Whoever frees has synchronised every
-// stream that may still use the memory (hipFree also synchronises the device, but nothing here relies on that).
+// The owner of one device allocation (hipMalloc), or with Pinned of one pinned host allocation (hipHostMalloc), and of its size:
+// freed by reset() and by its destructor (a move assignment hands the old block to the moved-from owner).  bytes() is what alloc()
+// was asked for and 0 while nothing is held, so elmk_device_bytes adds up owners and no release path keeps a count.  Whoever frees
+// has synchronised every stream that may still use the memory (hipFree also synchronises the device, but nothing here relies on that).
 template <class T, bool Pinned = false>
 class DevBuf {
  public:
   DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept { std::swap(p_, o.p_); }
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
   DevBuf& operator=(DevBuf&& o) noexcept
   {
     std::swap(p_, o.p_);
+    std::swap(bytes_, o.bytes_);
     return *this;
   }
   ~DevBuf() { (void)reset(); }
@@ -72,23 +75,29 @@ class DevBuf {
     (void)reset();
     void* v = nullptr;
     const hipError_t e = Pinned ? hipHostMalloc(&v, bytes, hipHostMallocDefault) : hipMalloc(&v, bytes);
-    p_ = e == hipSuccess ? (T*)v : nullptr;
+    if (e == hipSuccess) {
+      p_ = (T*)v;
+      bytes_ = bytes;
+    }
     return e;
   }
   hipError_t reset()
   {
     const hipError_t e = !p_ ? hipSuccess : Pinned ? hipHostFree(p_) : hipFree(p_);
     p_ = nullptr;
+    bytes_ = 0;
     return e;
   }
   operator T*() const { return p_; }
+  size_t bytes() const { return bytes_; }
 
  private:
   T* p_ = nullptr;
+  size_t bytes_ = 0;
 };
 
 // Lays regions out one after another in one block, each on a 256-byte boundary.  carve() runs a layout twice: over no block to
-// size it, then over the allocated block to hand each region's address to its pointer; *bytes is set once the block exists.
+// size it, then over the allocated block to hand each region's address to its pointer (block.bytes() is the layout's size).
 struct Carve {
   char* base;
   size_t bytes = 0;
@@ -100,16 +109,48 @@ struct Carve {
   }
 };
 template <class Layout>
-hipError_t carve(DevBuf<char>& block, size_t* bytes, Layout layout)
+hipError_t carve(DevBuf<char>& block, Layout layout)
 {
   Carve sizing{nullptr};
   layout(sizing);
   if (const hipError_t e = block.alloc(sizing.bytes)) return e;
   Carve place{block};
   layout(place);
-  *bytes = sizing.bytes;
   return hipSuccess;
 }
+
+// The two map shapes of elmk_maps.h as they lie on the device, inside their owner's block: take() lays the arrays out, upload()
+// fills them from the caller's (checked) arrays and returns once the copies are done - the sources are pageable host memory.
+struct EllMap {
+  int64_t ncells = 0;
+  int npts = 0, npad = 0;  // (npad 0: no map)
+  int32_t* idx = nullptr;  // [npad][ld]; padding rows and the columns past ncols hold -1
+  double* w = nullptr;     // [npad][ld]
+  void take(Carve& L, int64_t ncells_, int npts_, size_t ld)
+  {
+    *this = EllMap{ncells_, npts_, ell_npad(npts_)};
+    L.take(idx, (size_t)npad * ld * sizeof(int32_t));
+    L.take(w, (size_t)npad * ld * sizeof(double));
+  }
+  // `what` names the owner in the text of a HIP error; zeroes from w to `end` (the owner's regions behind the map, or the block's end)
+  int upload(elmk_ctx* ctx, const char* what, const char* end, const int32_t* hidx, const double* hw) const;
+};
+struct CsrMap {
+  int64_t nrows = 0, nnz = 0;
+  int64_t* ptr = nullptr;  // [nrows + 1]
+  int32_t* col = nullptr;  // [nnz]
+  double* w = nullptr;     // [nnz]
+  void take(Carve& L, int64_t nrows_, int64_t nnz_)
+  {
+    *this = CsrMap{nrows_, nnz_};
+    L.take(ptr, (size_t)(nrows + 1) * sizeof(int64_t));
+    L.take(col, (size_t)nnz * sizeof(int32_t));
+    L.take(w, (size_t)nnz * sizeof(double));
+  }
+  // after_ptr(): the owner's further copies, enqueued behind ptr's; true if one failed
+  template <class More>
+  int upload(elmk_ctx* ctx, const int64_t* hptr, const int32_t* hcol, const double* hw, More after_ptr) const;
+};
 
 // the list counters of the compacted kernels (ELMK_LIST_COUNT / ELMK_LIST_HEAD, one per CPAD words) and the classes of canopy_fluxes
 constexpr size_t COUNTERS_BYTES = ((size_t)(2 * NLISTS + CF_NCLS) * CPAD * 4 + 255) / 256 * 256;
@@ -143,18 +184,15 @@ struct elmk_ctx {
   bool dirty = true;
   // every device allocation of the context is one of these DevBuf owners
   DevBuf<char> arena;
-  size_t arena_bytes = 0;
   void* fptr[ELMK_NUM_FIELDS] = {};
   DevBuf<double> snicar;
   DevBuf<double> snowage;  // SnwRdsTable (elmk_set_snow_age_tables)
   DevBuf<char> scratch;  // work arrays + work lists + queue counters of the compacted kernels
-  size_t scratch_bytes = 0;
   // in scratch after DevState::cons_diag (diag [8][ld]): the stage-1 partials [8][ELMK_CONS_NPART][3] and the (min, max, sum)
   // triples [8][3] of launch_conservation
   double* cons_part = nullptr;
   double* cons_out = nullptr;
   DevBuf<char> staging;  // device staging for layout conversion
-  size_t staging_bytes = 0;
   std::vector<int> snap_fields;  // elmk_snapshot_fields
   std::vector<DevBuf<double>> snap_bufs;
   DevBuf<uint32_t> red_or;  // device scalars for elmk_error_summary
@@ -174,7 +212,7 @@ struct elmk_ctx {
   // history (elmk_history_*): the entries, their rows as the device table k_hist_accumulate reads (hist_table: the column rows, one
   // count per tape, then the cell rows of gridded entries), and per tape whether it has accumulated since its last reset
   // (elmk_history_add refuses such a tape).  A gridded entry (elmk_gridded_history_add) has cell rows: nlev x cld accumulators over
-  // the output grid's cells, cld = ncells rounded up to 64; their bytes are counted in elmk_device_bytes (hist_cell_bytes).
+  // the output grid's cells, cld = ncells rounded up to 64; their bytes are counted in elmk_device_bytes.
   struct HistEntry {
     int tape, field, op, nlev, row0;
     DevBuf<double> acc;
@@ -184,12 +222,11 @@ struct elmk_ctx {
   std::vector<HistEntry> hist;
   std::vector<HistRow> hist_rows;
   std::vector<HistRow> hist_crows;
-  size_t hist_cell_bytes = 0;
   DevBuf<HistRow> hist_table;
   bool hist_dirty[ELMK_HIST_MAX_TAPES] = {};
   uint64_t hist_version = 0;  // counts elmk_history_add / _clear: a captured step of elmk_run holds the table of its moment
   // accumulated fields (elmk_accum_*): the entries, their rows as the device table k_accum_update reads (accum_table: the rows, then
-  // one step count per entry), and the bytes of the table and of every value buffer (elmk_device_bytes)
+  // one step count per entry); elmk_device_bytes counts the table and every value buffer
   struct AccumEntry {
     int src, kind, dst, nlev, row0;
     int64_t period;
@@ -198,7 +235,6 @@ struct elmk_ctx {
   std::vector<AccumEntry> accum;
   std::vector<AccumRow> accum_rows;
   DevBuf<char> accum_table;
-  size_t accum_bytes = 0;
   uint64_t accum_version = 0;  // counts elmk_accum_add / _clear, as hist_version
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
@@ -210,7 +246,6 @@ struct elmk_ctx {
     int slots = 0, max_steps = 0;
     int64_t fcols = 0, fstride = 0;  // forcing series: entries per record (columns, or cells in grid mode) and the record stride
     DevBuf<char> mem;
-    size_t bytes = 0;
     char* forc = nullptr;
     char* phen = nullptr;
     RunRow* table = nullptr;
@@ -229,32 +264,22 @@ struct elmk_ctx {
     // shortwave COSZEN mode (elmk_series_record_times): the record-time scalars of every forcing slot (elmk_solar_step_consts at
     // forc_dt and the slot's record start), allocated by the first call after a reservation, and which slots have one
     DevBuf<elmk_solar_step> rec;
-    size_t rec_bytes = 0;
     std::vector<char> rec_set;
   } run;
   hipStream_t upload = nullptr;  // of elmk_series_upload, with run_done created by the first elmk_run_reserve
   hipEvent_t run_done[2] = {};
-  // forcing on a coarser grid (elmk_set_forcing_grid): one allocation `mem` holds the ELL map [npad][ld] - idx (int32), w (fp64);
-  // npts rounded up to npad = 1, 2, 4 or 8 with padding rows idx = -1 - and the fp64 staging of elmk_upload_gridded (ncells values)
+  // forcing on a coarser grid (elmk_set_forcing_grid): one allocation `mem` holds the ELL map and the fp64 staging of
+  // elmk_upload_gridded (map.ncells values)
   struct Grid {
-    int64_t ncells = 0;
-    int npts = 0, npad = 0;
     DevBuf<char> mem;
-    size_t bytes = 0;
-    int32_t* idx = nullptr;
-    double* w = nullptr;
+    EllMap map;
     double* cells = nullptr;
   } grid;
-  // output grid (elmk_set_output_grid): one allocation `mem` holds the CSR map by output cell - ptr (int64, ncells + 1 entries), col
-  // (int32, nnz), w (fp64, nnz) - each region rounded up to 256 bytes
+  // output grid (elmk_set_output_grid): one allocation `mem` holds the CSR map by output cell (map.nrows cells)
   struct OGrid {
-    int64_t ncells = 0, nnz = 0;
     double fill = 0.0;
     DevBuf<char> mem;
-    size_t bytes = 0;
-    int64_t* ptr = nullptr;
-    int32_t* col = nullptr;
-    double* w = nullptr;
+    CsrMap map;
   } ogrid;
   // shortwave (elmk_set_shortwave_mode): the mode, the forcing records' interval, and in COSZEN mode czf - every column's mean
   // cos(zenith) over the current forcing record's interval ([ld] doubles, allocated when the context first enters COSZEN mode).
@@ -264,39 +289,29 @@ struct elmk_ctx {
     int mode = ELMK_SW_REFERENCE;
     double forc_dt = 0.0;
     DevBuf<double> czf;
-    size_t czf_bytes = 0;
     bool step_time = false, czf_ready = false;
   } sw;
   // downscaling (elmk_set_downscaling): the mode and its parameters; topo = the elevations [2][ld] (row 0 the columns', row 1 the
   // forcing's surface height), allocated by the first call that sets either, and which rows hold values.  Longwave groups
-  // (elmk_set_downscaling_groups): one allocation `gmem` holds the CSR map (ptr, col, w), each group's weight sum wsum (the host's sum
-  // in term order) and the Lg row [ld] the TOPO forcing kernels write for launch_ds_lw_norm.
+  // (elmk_set_downscaling_groups): one allocation `gmem` holds the CSR map by group, each group's weight sum wsum (the host's sum in
+  // term order) and the Lg row [ld] the TOPO forcing kernels write for launch_ds_lw_norm.
   struct Downscale {
     int mode = ELMK_DS_OFF;
     double lapse = 0.006, lapse_lw = 0.032, lw_limit = 0.5;
     DevBuf<double> topo;
-    size_t topo_bytes = 0;
     bool col_set = false, forc_set = false;
     DevBuf<char> gmem;
-    size_t gbytes = 0;
-    int64_t ngroups = 0, nnz = 0;
-    int64_t* ptr = nullptr;
-    int32_t* col = nullptr;
-    double* w = nullptr;
+    CsrMap groups;
     double* wsum = nullptr;
     double* lg = nullptr;
   } ds;
-  // aerosol deposition (elmk_aerosol_reserve): one allocation `mem` holds the cell series [AER_NSTREAM][12][ncells] in fp64 and, unless
-  // the series is per column (npad 0), the ELL map of its grid [npad][ld] - idx (int32), w (fp64) - laid out as Grid's.  step_live: a
+  // aerosol deposition (elmk_aerosol_reserve): one allocation `mem` holds the cell series [AER_NSTREAM][12][map.ncells] in fp64 and, unless
+  // the series is per column (map.npad 0), the ELL map of its grid.  step_live: a
   // stepwise elmk_aerosol_deposition has been enqueued since the last elmk_aerosol_upload waited for aer_step_done.
   struct Aerosol {
-    int64_t ncells = 0;
-    int npts = 0, npad = 0;
     DevBuf<char> mem;
-    size_t bytes = 0;
     double* cells = nullptr;
-    int32_t* idx = nullptr;
-    double* w = nullptr;
+    EllMap map;  // (per-column series: only its ncells, = ncols)
     bool step_live = false;
   } aer;
   hipEvent_t aer_step_done = nullptr;  // the end of the last stepwise elmk_aerosol_deposition (created by the first reservation)
@@ -351,6 +366,41 @@ int invalid(elmk_ctx* ctx, const char* msg)
   return ELMK_E_INVALID;
 }
 
+int EllMap::upload(elmk_ctx* ctx, const char* what, const char* end, const int32_t* hidx, const double* hw) const
+{
+  const std::string set = std::string("hipMemset(") + what, copy = std::string("hipMemcpy2D(") + what;
+  const size_t ld = (size_t)ctx->ld, n = (size_t)ctx->ncols;
+  // padding rows and the columns past ncols: idx -1 (all bits set), w 0; then the caller's npts rows
+  if (npad && (hip_fail(ctx, hipMemsetAsync(idx, 0xFF, (char*)w - (char*)idx, ctx->stream), (set + " idx)").c_str()) ||
+               hip_fail(ctx, hipMemsetAsync(w, 0, end - (char*)w, ctx->stream), (set + " w)").c_str())))
+    return ELMK_E_HIP;
+  if (npad && n > 0 &&
+      (hip_fail(ctx, hipMemcpy2DAsync(idx, ld * sizeof(int32_t), hidx, n * sizeof(int32_t), n * sizeof(int32_t), (size_t)npts,
+                                      hipMemcpyHostToDevice, ctx->stream), (copy + " idx)").c_str()) ||
+       hip_fail(ctx, hipMemcpy2DAsync(w, ld * sizeof(double), hw, n * sizeof(double), n * sizeof(double), (size_t)npts,
+                                      hipMemcpyHostToDevice, ctx->stream), (copy + " w)").c_str())))
+    return ELMK_E_HIP;
+  return hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize") ? ELMK_E_HIP : ELMK_OK;
+}
+
+template <class More>
+int CsrMap::upload(elmk_ctx* ctx, const int64_t* hptr, const int32_t* hcol, const double* hw, More after_ptr) const
+{
+  const bool failed =
+      hip_fail(ctx, hipMemcpyAsync(ptr, hptr, (size_t)(nrows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(ptr)") ||
+      after_ptr() ||
+      (nnz > 0 && (hip_fail(ctx, hipMemcpyAsync(col, hcol, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(col)") ||
+                   hip_fail(ctx, hipMemcpyAsync(w, hw, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(w)"))) ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+  return failed ? ELMK_E_HIP : ELMK_OK;
+}
+
+// a refusal of elmk_maps.h's checks (text, or nullptr for none) under the entry point's name
+int invalid_map(elmk_ctx* ctx, const char* who, const char* text)
+{
+  return text ? invalid(ctx, (std::string(who) + ": " + text).c_str()) : ELMK_OK;
+}
+
 int push_params(elmk_ctx* ctx)
 {
   if (!ctx->dirty) return ELMK_OK;
@@ -364,6 +414,26 @@ int enter(elmk_ctx* ctx)
 {
   if (!ctx) return ELMK_E_INVALID;
   HIPCHK(hipSetDevice(ctx->dev));
+  return ELMK_OK;
+}
+
+// wait for the runs in flight (they read the series, maps, elevations and tables the caller is about to change) and, with `uploads`,
+// for the copy stream (it may still write them), then drop the captured run step (it holds their addresses and the kernels of their
+// modes and widths)
+int quiesce(elmk_ctx* ctx, bool uploads)
+{
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (uploads && ctx->upload) HIPCHK(hipStreamSynchronize(ctx->upload));
+  ctx->graph[GRAPH_RUN_STEP].drop();
+  return ELMK_OK;
+}
+
+// never write under a run that reads it: wait for the end of every enqueued, unfinished run whose buffer b `reads` selects
+template <class Pred>
+int wait_for_runs(elmk_ctx* ctx, Pred reads)
+{
+  for (int b = 0; b < 2; b++)
+    if (ctx->run.live[b] && reads(b)) HIPCHK(hipEventSynchronize(ctx->run_done[b]));
   return ELMK_OK;
 }
 
@@ -424,11 +494,11 @@ int elmk_create(int64_t ncols, int device_id, elmk_ctx** out)
   h.oldfflag = 1;
 
   const size_t ld = (size_t)ctx->ld;
-  if (hip_fail(ctx, carve(ctx->arena, &ctx->arena_bytes, [&](Carve& L) {
+  if (hip_fail(ctx, carve(ctx->arena, [&](Carve& L) {
                  for (int f = 0; f < ELMK_NUM_FIELDS; f++) L.take(ctx->fptr[f], (size_t)g_fields[f].nlev * ld * store_size(g_fields[f].dtype));
                }), "hipMalloc(state arena)"))
     return fail(ELMK_E_NOMEM);
-  if (hip_fail(ctx, hipMemsetAsync(ctx->arena, 0, ctx->arena_bytes, ctx->stream), "hipMemset(state arena)")) return fail(ELMK_E_HIP);
+  if (hip_fail(ctx, hipMemsetAsync(ctx->arena, 0, ctx->arena.bytes(), ctx->stream), "hipMemset(state arena)")) return fail(ELMK_E_HIP);
 
   if (hip_fail(ctx, ctx->snicar.alloc(SN_TOTAL * sizeof(double)), "hipMalloc(snicar)")) return fail(ELMK_E_NOMEM);
   if (hip_fail(ctx, hipMemsetAsync(ctx->snicar, 0, SN_TOTAL * sizeof(double), ctx->stream), "hipMemset(snicar)"))
@@ -440,7 +510,7 @@ int elmk_create(int64_t ncols, int device_id, elmk_ctx** out)
   // canopy_fluxes queue records (k_canopy_fluxes.hip), by queue position
   const int64_t cf_nblk = (ncols + 255) / 256 > 0 ? (ncols + 255) / 256 : 1;
   h.cf_nblk = cf_nblk;
-  if (hip_fail(ctx, carve(ctx->scratch, &ctx->scratch_bytes, [&](Carve& L) {
+  if (hip_fail(ctx, carve(ctx->scratch, [&](Carve& L) {
                  L.take(h.wk, (size_t)WK_N * ld * 8);
                  L.take(h.lists, (size_t)NLISTS * ld * 4);
                  L.take(h.counters, COUNTERS_BYTES);
@@ -458,7 +528,7 @@ int elmk_create(int64_t ncols, int device_id, elmk_ctx** out)
                  L.take(ctx->cons_out, 8 * 3 * 8);
                }), "hipMalloc(scratch)"))
     return fail(ELMK_E_NOMEM);
-  if (hip_fail(ctx, hipMemsetAsync(ctx->scratch, 0, ctx->scratch_bytes, ctx->stream), "hipMemset(scratch)"))
+  if (hip_fail(ctx, hipMemsetAsync(ctx->scratch, 0, ctx->scratch.bytes(), ctx->stream), "hipMemset(scratch)"))
     return fail(ELMK_E_HIP);
   if (hip_fail(ctx, ctx->red_or.alloc(16), "hipMalloc(reduce)")) return fail(ELMK_E_NOMEM);
   ctx->red_first = (long long*)(ctx->red_or + 2);
@@ -467,7 +537,6 @@ int elmk_create(int64_t ncols, int device_id, elmk_ctx** out)
   size_t want = (size_t)MAXLEV_STAGE * 8 * (size_t)(ncols > 0 ? ncols : 1);
   if (want > ((size_t)32 << 20)) want = (size_t)32 << 20;
   if (want < (size_t)MAXLEV_STAGE * 8 * 64) want = (size_t)MAXLEV_STAGE * 8 * 64;
-  ctx->staging_bytes = want;
   if (hip_fail(ctx, ctx->staging.alloc(want), "hipMalloc(staging)")) return fail(ELMK_E_NOMEM);
 
   h.snicar = (gptr<const double>)(double*)ctx->snicar;
@@ -583,10 +652,15 @@ int64_t elmk_ncols(const elmk_ctx* ctx) { return ctx ? ctx->ncols : -1; }
 int64_t elmk_level_stride(const elmk_ctx* ctx) { return ctx ? ctx->ld : -1; }
 int64_t elmk_device_bytes(const elmk_ctx* ctx)
 {
-  return ctx ? (int64_t)(ctx->arena_bytes + ctx->staging_bytes + ctx->scratch_bytes + (SN_TOTAL + 3 * ELMK_SNOWAGE_N) * sizeof(double) + sizeof(DevState) +
-                         ctx->run.bytes + ctx->grid.bytes + ctx->ogrid.bytes + ctx->hist_cell_bytes + ctx->sw.czf_bytes + ctx->run.rec_bytes +
-                         ctx->ds.topo_bytes + ctx->ds.gbytes + ctx->accum_bytes + ctx->aer.bytes)
-             : -1;
+  if (!ctx) return -1;
+  size_t n = ctx->arena.bytes() + ctx->staging.bytes() + ctx->scratch.bytes() + ctx->snicar.bytes() + ctx->snowage.bytes() + ctx->d.bytes() +
+             ctx->run.mem.bytes() + ctx->grid.mem.bytes() + ctx->ogrid.mem.bytes() + ctx->sw.czf.bytes() + ctx->run.rec.bytes() +
+             ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes();
+  // the cell rows of gridded history entries (not the column rows) and the accumulators' values: whole rows of ld or cld doubles,
+  // both multiples of 64, so every size is a multiple of 256 already
+  for (const elmk_ctx::HistEntry& e : ctx->hist) n += e.cells ? e.acc.bytes() : 0;
+  for (const elmk_ctx::AccumEntry& e : ctx->accum) n += e.val.bytes();
+  return (int64_t)n;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -612,7 +686,48 @@ int elmk_field_info(int field, int* nlev, int* dtype)
 // ---------------------------------------------------------------------------------------------------
 // data movement
 // ---------------------------------------------------------------------------------------------------
-static int xfer_stored(elmk_ctx* ctx, int field, void* host, int64_t col0, int64_t n, int layout, bool up);
+// Columns [col0, col0 + n) of nlev device rows, ld elements of es bytes apart, from (up) or to the host's n > 0 columns: as rows of n
+// elements (ELMK_LAYOUT_SOA, or one level), else in the reference layout [col][lev] through the device staging buffer in chunks of
+// whole 64-column tiles.  Enqueued on the context's stream, which is waited for only where a chunk reuses the staging buffer: the
+// caller waits for the end (the host side is pageable memory).
+static int xfer_rows(elmk_ctx* ctx, char* dev, int64_t ld, int es, int nlev, void* host, int64_t col0, int64_t n, int layout, bool up)
+{
+  if (layout == ELMK_LAYOUT_SOA || nlev == 1) {
+    if (up)
+      HIPCHK(hipMemcpy2DAsync(dev + (size_t)col0 * es, (size_t)ld * es, host, (size_t)n * es, (size_t)n * es, nlev, hipMemcpyHostToDevice,
+                              ctx->stream));
+    else
+      HIPCHK(hipMemcpy2DAsync(host, (size_t)n * es, dev + (size_t)col0 * es, (size_t)ld * es, (size_t)n * es, nlev, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    return ELMK_OK;
+  }
+  const int64_t chunk = (int64_t)(ctx->staging.bytes() / ((size_t)nlev * es)) / 64 * 64;
+  if (chunk <= 0) return invalid(ctx, "staging buffer too small");
+  for (int64_t done = 0; done < n; done += chunk) {
+    if (done > 0) HIPCHK(hipStreamSynchronize(ctx->stream));  // staging is reused by this chunk
+    const int64_t m = (n - done) < chunk ? (n - done) : chunk;
+    char* hp = (char*)host + (size_t)done * nlev * es;
+    if (up) {
+      HIPCHK(hipMemcpyAsync(ctx->staging, hp, (size_t)m * nlev * es, hipMemcpyHostToDevice, ctx->stream));
+      launch_cols_to_soa(ctx->staging, dev, es, nlev, ld, col0 + done, m, ctx->stream);
+    } else {
+      launch_soa_to_cols(dev, ctx->staging, es, nlev, ld, col0 + done, m, ctx->stream);
+      HIPCHK(hipMemcpyAsync(hp, ctx->staging, (size_t)m * nlev * es, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipGetLastError());
+  }
+  return ELMK_OK;
+}
+
+// host elements already in the stored element type
+static int xfer_stored(elmk_ctx* ctx, int field, void* host, int64_t col0, int64_t n, int layout, bool up)
+{
+  const int nlev = g_fields[field].nlev;
+  if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR && nlev != 1) return invalid(ctx, "elmk_upload/download: unknown layout");
+  if (int rc = xfer_rows(ctx, (char*)ctx->fptr[field], ctx->ld, store_size(g_fields[field].dtype), nlev, host, col0, n, layout, up)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
 
 static int xfer(elmk_ctx* ctx, int field, void* host, int64_t col0, int64_t n, int layout, bool up)
 {
@@ -642,43 +757,6 @@ static int xfer(elmk_ctx* ctx, int field, void* host, int64_t col0, int64_t n, i
     return rc;
   }
   return xfer_stored(ctx, field, host, col0, n, layout, up);
-}
-
-// host elements already in the stored element type
-static int xfer_stored(elmk_ctx* ctx, int field, void* host, int64_t col0, int64_t n, int layout, bool up)
-{
-  const int es = store_size(g_fields[field].dtype), nlev = g_fields[field].nlev;
-  char* dev = (char*)ctx->fptr[field];
-  if (layout == ELMK_LAYOUT_SOA || nlev == 1) {
-    // rows of n elements <-> rows of ld elements
-    if (up)
-      HIPCHK(hipMemcpy2DAsync(dev + (size_t)col0 * es, (size_t)ctx->ld * es, host, (size_t)n * es, (size_t)n * es, nlev,
-                              hipMemcpyHostToDevice, ctx->stream));
-    else
-      HIPCHK(hipMemcpy2DAsync(host, (size_t)n * es, dev + (size_t)col0 * es, (size_t)ctx->ld * es, (size_t)n * es, nlev,
-                              hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return ELMK_OK;
-  }
-  if (layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_upload/download: unknown layout");
-  // reference layout [col][lev]: go through the device staging buffer in chunks of whole 64-column tiles
-  int64_t chunk = (int64_t)(ctx->staging_bytes / ((size_t)nlev * es));
-  chunk = chunk / 64 * 64;
-  if (chunk <= 0) return invalid(ctx, "staging buffer too small");
-  for (int64_t done = 0; done < n; done += chunk) {
-    const int64_t m = (n - done) < chunk ? (n - done) : chunk;
-    char* hp = (char*)host + (size_t)done * nlev * es;
-    if (up) {
-      HIPCHK(hipMemcpyAsync(ctx->staging, hp, (size_t)m * nlev * es, hipMemcpyHostToDevice, ctx->stream));
-      launch_cols_to_soa(ctx->staging, dev, es, nlev, ctx->ld, col0 + done, m, ctx->stream);
-    } else {
-      launch_soa_to_cols(dev, ctx->staging, es, nlev, ctx->ld, col0 + done, m, ctx->stream);
-      HIPCHK(hipMemcpyAsync(hp, ctx->staging, (size_t)m * nlev * es, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // staging is reused by the next chunk
-  }
-  return ELMK_OK;
 }
 
 int elmk_upload(elmk_ctx* ctx, int field, const void* host, int64_t col0, int64_t n, int layout)
@@ -986,8 +1064,8 @@ HistRow* hist_cell_rows(elmk_ctx* ctx) { return (HistRow*)((char*)(HistRow*)ctx-
 
 OGridMap ogrid_map(const elmk_ctx* ctx)
 {
-  const elmk_ctx::OGrid& O = ctx->ogrid;
-  return OGridMap{O.ptr, O.col, O.w, O.ncells, O.fill};
+  const CsrMap& M = ctx->ogrid.map;
+  return OGridMap{M.ptr, M.col, M.w, M.nrows, ctx->ogrid.fill};
 }
 
 bool has_gridded_entries(const elmk_ctx* ctx) { return !ctx->hist_crows.empty(); }
@@ -1031,7 +1109,7 @@ int hist_add(elmk_ctx* ctx, int tape, int field, int op, bool cells, const char*
   }
   const int nlev = g_fields[field].nlev;
   // a column row spans the level stride; a cell row the cell count rounded up to 64 (16-byte aligned rows for k_hist_reset's pairs)
-  const int64_t ld = cells ? (ctx->ogrid.ncells + 63) / 64 * 64 : ctx->ld;
+  const int64_t ld = cells ? (ctx->ogrid.map.nrows + 63) / 64 * 64 : ctx->ld;
   const size_t bytes = (size_t)nlev * (size_t)ld * sizeof(double);
   DevBuf<double> acc;
   if (hip_fail(ctx, acc.alloc(bytes), "hipMalloc(history)")) return ELMK_E_NOMEM;
@@ -1055,7 +1133,6 @@ int hist_add(elmk_ctx* ctx, int tape, int field, int op, bool cells, const char*
     return ELMK_E_HIP;  // (frees acc)
   }
   ctx->hist.push_back(elmk_ctx::HistEntry{tape, field, op, nlev, row0, std::move(acc), cells, ld});
-  if (cells) ctx->hist_cell_bytes += align_up(bytes, 256);
   ctx->hist_version++;
   return (int)ctx->hist.size() - 1;
 }
@@ -1095,7 +1172,7 @@ int elmk_history_reset(elmk_ctx* ctx, int tape)
     HIPCHK(hipGetLastError());
   }
   if (has_gridded_entries(ctx)) {  // (resets the tape's count a second time)
-    launch_hist_reset(hist_cell_rows(ctx), (int)ctx->hist_crows.size(), hist_counts(ctx), (ctx->ogrid.ncells + 63) / 64 * 64, tape,
+    launch_hist_reset(hist_cell_rows(ctx), (int)ctx->hist_crows.size(), hist_counts(ctx), (ctx->ogrid.map.nrows + 63) / 64 * 64, tape,
                       ctx->stream);
     HIPCHK(hipGetLastError());
   }
@@ -1120,7 +1197,7 @@ int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int6
   if (int rc = enter(ctx)) return rc;
   if (entry < 0 || entry >= (int)ctx->hist.size()) return invalid(ctx, "elmk_history_read: unknown entry");
   const elmk_ctx::HistEntry& e = ctx->hist[entry];
-  const int64_t lim = e.cells ? ctx->ogrid.ncells : ctx->ncols;  // a gridded entry's col0, n index cells
+  const int64_t lim = e.cells ? ctx->ogrid.map.nrows : ctx->ncols;  // a gridded entry's col0, n index cells
   if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > lim)
     return invalid(ctx, e.cells ? "elmk_history_read: bad cell range" : "elmk_history_read: bad column range");
   if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_history_read: unknown layout");
@@ -1130,14 +1207,14 @@ int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int6
   if (n == 0) return ELMK_OK;
   // chunks of m columns: the finalize kernel writes them as dense SoA [lev][m] into the upper half of the staging buffer, and the
   // transpose of elmk_download takes them to [col][lev] in the lower half where the caller wants the reference layout
-  const size_t half = ctx->staging_bytes / 2 / sizeof(double) * sizeof(double);
+  const size_t half = ctx->staging.bytes() / 2 / sizeof(double) * sizeof(double);
   const int64_t chunk = (int64_t)(half / ((size_t)e.nlev * sizeof(double)));
   if (chunk <= 0) return invalid(ctx, "staging buffer too small");
   double* soa = (double*)(ctx->staging + half);
   for (int64_t done = 0; done < n; done += chunk) {
     const int64_t m = (n - done) < chunk ? (n - done) : chunk;
     if (e.cells)
-      launch_ogrid_finalize(e.acc, e.cld, e.nlev, e.op, count, ctx->ogrid.ptr, ctx->ogrid.fill, col0 + done, m, soa, ctx->stream);
+      launch_ogrid_finalize(e.acc, e.cld, e.nlev, e.op, count, ctx->ogrid.map.ptr, ctx->ogrid.fill, col0 + done, m, soa, ctx->stream);
     else
       launch_hist_finalize(e.acc, ctx->ld, e.nlev, e.op, count, col0 + done, m, soa, ctx->stream);
     if (layout == ELMK_LAYOUT_SOA || e.nlev == 1) {
@@ -1161,7 +1238,6 @@ int elmk_history_clear(elmk_ctx* ctx)
   ctx->hist.clear();
   ctx->hist_rows.clear();
   ctx->hist_crows.clear();
-  ctx->hist_cell_bytes = 0;
   if (ctx->hist_table)
     HIPCHK(hipMemsetAsync(hist_counts(ctx), 0, ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
   for (bool& d : ctx->hist_dirty) d = false;
@@ -1182,7 +1258,6 @@ constexpr size_t ACCUM_TABLE_BYTES = ACCUM_COUNTS_OFF + 256;
 static_assert(ELMK_ACCUM_MAX_ENTRIES * sizeof(unsigned long long) <= 256, "the counts fit behind the rows");
 
 unsigned long long* accum_counts(elmk_ctx* ctx) { return (unsigned long long*)((char*)ctx->accum_table + ACCUM_COUNTS_OFF); }
-size_t accum_val_bytes(const elmk_ctx* ctx, int nlev) { return align_up((size_t)nlev * (size_t)ctx->ld * sizeof(double), 256); }
 
 // every row of every entry, then the counts (two launches; nothing without entries)
 void accum_update_launch(elmk_ctx* ctx)
@@ -1255,7 +1330,6 @@ int elmk_accum_add(elmk_ctx* ctx, int src_field, int kind, int64_t period_steps,
     return ELMK_E_HIP;  // (frees val)
   }
   ctx->accum.push_back(elmk_ctx::AccumEntry{src_field, kind, dst_field, nlev, row0, period_steps, std::move(val)});
-  ctx->accum_bytes += accum_val_bytes(ctx, nlev) + (first ? ACCUM_TABLE_BYTES : 0);
   ctx->accum_version++;
   return entry;
 }
@@ -1270,8 +1344,7 @@ int elmk_accum_init(elmk_ctx* ctx, int entry, const double* host, int64_t nsteps
   if (int rc = refuse_capture(ctx, "elmk_accum_init: the stream is being captured")) return rc;
   if (host) {
     if (ctx->ncols > 0)
-      HIPCHK(hipMemcpy2DAsync(e.val, (size_t)ctx->ld * sizeof(double), host, (size_t)ctx->ncols * sizeof(double),
-                              (size_t)ctx->ncols * sizeof(double), (size_t)e.nlev, hipMemcpyHostToDevice, ctx->stream));
+      if (int rc = xfer_rows(ctx, (char*)(double*)e.val, ctx->ld, 8, e.nlev, const_cast<double*>(host), 0, ctx->ncols, ELMK_LAYOUT_SOA, true)) return rc;
   } else {
     launch_accum_seed(ctx->fptr[e.dst], store_dtype(ELMK_F64), e.val, e.nlev, ctx->ld, ctx->ncols, ctx->stream);
     HIPCHK(hipGetLastError());
@@ -1301,23 +1374,9 @@ int elmk_accum_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int64_
   const elmk_ctx::AccumEntry& e = ctx->accum[entry];
   unsigned long long cnt = 0;
   HIPCHK(hipMemcpyAsync(&cnt, accum_counts(ctx) + entry, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-  if (n > 0 && (layout == ELMK_LAYOUT_SOA || e.nlev == 1)) {
-    HIPCHK(hipMemcpy2DAsync(host, (size_t)n * sizeof(double), e.val + col0, (size_t)ctx->ld * sizeof(double), (size_t)n * sizeof(double),
-                            (size_t)e.nlev, hipMemcpyDeviceToHost, ctx->stream));
-  } else if (n > 0) {
-    // reference layout [col][lev]: through the device staging buffer in chunks of whole 64-column tiles, as elmk_download
-    const int64_t chunk = (int64_t)(ctx->staging_bytes / ((size_t)e.nlev * sizeof(double))) / 64 * 64;
-    if (chunk <= 0) return invalid(ctx, "staging buffer too small");
-    for (int64_t done = 0; done < n; done += chunk) {
-      const int64_t m = (n - done) < chunk ? (n - done) : chunk;
-      launch_soa_to_cols(e.val, ctx->staging, 8, e.nlev, ctx->ld, col0 + done, m, ctx->stream);
-      HIPCHK(hipMemcpyAsync(host + (size_t)done * e.nlev, ctx->staging, (size_t)m * e.nlev * sizeof(double), hipMemcpyDeviceToHost,
-                            ctx->stream));
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(ctx->stream));  // staging is reused by the next chunk
-    }
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (n > 0)
+    if (int rc = xfer_rows(ctx, (char*)(double*)e.val, ctx->ld, 8, e.nlev, host, col0, n, layout, false)) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // (the count and the rows)
   if (nsteps) *nsteps = (int64_t)cnt;
   return ELMK_OK;
 }
@@ -1331,7 +1390,6 @@ int elmk_accum_clear(elmk_ctx* ctx)
   ctx->accum.clear();
   ctx->accum_rows.clear();
   HIPCHK(ctx->accum_table.reset());
-  ctx->accum_bytes = 0;
   ctx->accum_version++;
   return ELMK_OK;
 }
@@ -1628,9 +1686,9 @@ DsParams ds_params(const elmk_ctx* ctx)
 void ds_lw_norm(elmk_ctx* ctx)
 {
   const elmk_ctx::Downscale& D = ctx->ds;
+  const CsrMap& G = D.groups;
   if (!ds_topo(ctx) || !D.gmem) return;
-  launch_ds_lw_norm(ctx->fptr[ELMK_FIELD_forc_lwrad], store_dtype(ELMK_F64), D.lg, OGridMap{D.ptr, D.col, D.w, D.ngroups, 0.0}, D.wsum,
-                    ctx->stream);
+  launch_ds_lw_norm(ctx->fptr[ELMK_FIELD_forc_lwrad], store_dtype(ELMK_F64), D.lg, OGridMap{G.ptr, G.col, G.w, G.nrows, 0.0}, D.wsum, ctx->stream);
 }
 }  // namespace
 
@@ -1709,14 +1767,10 @@ int elmk_advance_physics(elmk_ctx* ctx, double dt)
 // multi-step runs: the driver's time loop (kokkos_driver.cc:54-85) on the device
 // ---------------------------------------------------------------------------------------------------
 namespace {
-// wait for the runs in flight (they read the run buffers) and for the upload stream (it may still write them), drop the captured
-// step (it holds the old addresses and launch shape) and release the reservation: elmk_run_reserve, elmk_set_forcing_grid and
-// elmk_clear_forcing_grid
+// quiesce and release the reservation: elmk_run_reserve, elmk_set_forcing_grid and elmk_clear_forcing_grid
 int run_drop(elmk_ctx* ctx)
 {
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->upload) HIPCHK(hipStreamSynchronize(ctx->upload));
-  ctx->graph[GRAPH_RUN_STEP].drop();
+  if (int rc = quiesce(ctx, true)) return rc;
   ctx->run = elmk_ctx::Run{};
   return ELMK_OK;
 }
@@ -1743,11 +1797,11 @@ void run_phenology(elmk_ctx* ctx, double) { launch_phenology_run(ctx->d, ctx->nc
 void run_forcing(elmk_ctx* ctx, double)
 {
   const elmk_ctx::Run& R = ctx->run;
-  const elmk_ctx::Grid& G = ctx->grid;
+  const EllMap& G = ctx->grid.map;
   const double* czf = ctx->sw.mode == ELMK_SW_COSZEN ? (const double*)ctx->sw.czf : nullptr;
   const DsParams P = ds_params(ctx);
   const DsParams* ds = ds_topo(ctx) ? &P : nullptr;
-  if (G.mem)
+  if (ctx->grid.mem)
     launch_get_forcing_run_grid(ctx->d, ctx->ncols, R.table, R.cursor, R.forc, R.slots, R.fstride, G.npad, G.idx, G.w,
                                 (R.flags & ELMK_RUN_QBOT_IS_RH) != 0, ctx->stream, czf, ds);
   else
@@ -1757,7 +1811,7 @@ void run_forcing(elmk_ctx* ctx, double)
 AerSeries aer_series(const elmk_ctx* ctx)
 {
   const elmk_ctx::Aerosol& A = ctx->aer;
-  return AerSeries{A.cells, A.ncells, A.npad, A.idx, A.w};
+  return AerSeries{A.cells, A.map.ncells, A.map.npad, A.map.idx, A.map.w};
 }
 void run_aerosol(elmk_ctx* ctx, double)
 {
@@ -1808,8 +1862,8 @@ int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
   if (int rc = ensure_upload_stream(ctx)) return rc;
   const size_t es = (size_t)store_size(ELMK_F64), ld = (size_t)ctx->ld, nrow = 2 * (size_t)max_steps;
   // with a forcing grid the forcing records are cell records, [RUN_NFORC][slots][ncells] without padding
-  const int64_t fstride = ctx->grid.mem ? ctx->grid.ncells : ctx->ld;
-  if (hip_fail(ctx, carve(R.mem, &R.bytes, [&](Carve& L) {
+  const int64_t fstride = ctx->grid.mem ? ctx->grid.map.ncells : ctx->ld;
+  if (hip_fail(ctx, carve(R.mem, [&](Carve& L) {
                  L.take(R.forc, (size_t)RUN_NFORC * forcing_slots * (size_t)fstride * es);
                  L.take(R.phen, (size_t)RUN_NPHEN * RUN_NMONTH * ld * es);
                  L.take(R.table, nrow * sizeof(RunRow));
@@ -1825,9 +1879,9 @@ int elmk_run_reserve(elmk_ctx* ctx, int forcing_slots, int max_steps)
   }
   R.slots = forcing_slots;
   R.max_steps = max_steps;
-  R.fcols = ctx->grid.mem ? ctx->grid.ncells : ctx->ncols;
+  R.fcols = ctx->grid.mem ? ctx->grid.map.ncells : ctx->ncols;
   R.fstride = fstride;
-  if (hip_fail(ctx, hipMemsetAsync(R.mem, 0, R.bytes, ctx->stream), "hipMemset(run)") ||
+  if (hip_fail(ctx, hipMemsetAsync(R.mem, 0, R.mem.bytes(), ctx->stream), "hipMemset(run)") ||
       hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
     R = elmk_ctx::Run{};
     return ELMK_E_HIP;
@@ -1852,13 +1906,10 @@ int elmk_series_upload(elmk_ctx* ctx, int field, int slot0, int nslots, const do
   if ((!host && n > 0 && nslots > 0) || col0 < 0 || n < 0 || col0 + n > ncol)
     return invalid(ctx, "elmk_series_upload: bad column (grid mode: cell) range");
   if (n == 0 || nslots == 0) return ELMK_OK;
-  // never write under a run that reads these records: wait for the end of each enqueued run that does
-  for (int b = 0; b < 2; b++) {
-    if (!R.live[b]) continue;
-    const bool hit = forcing ? (slot0 <= R.slot_hi[b] && slot0 + nslots - 1 >= R.slot_lo[b])
-                             : ((R.months[b] >> slot0) & ((1u << nslots) - 1u)) != 0;
-    if (hit) HIPCHK(hipEventSynchronize(ctx->run_done[b]));
-  }
+  const auto reads = [&](int b) {  // the run on buffer b reads some of these records
+    return forcing ? (slot0 <= R.slot_hi[b] && slot0 + nslots - 1 >= R.slot_lo[b]) : ((R.months[b] >> slot0) & ((1u << nslots) - 1u)) != 0;
+  };
+  if (int rc = wait_for_runs(ctx, reads)) return rc;
   const size_t es = (size_t)store_size(ELMK_F64);
   char* dst = (forcing ? R.forc : R.phen) + (((size_t)k * nsl + slot0) * (size_t)stride + (size_t)col0) * es;
   const void* src = host;
@@ -1973,48 +2024,18 @@ int elmk_run_diagnostics(elmk_ctx* ctx, double* min_max_sum, uint32_t* flags_or,
 int elmk_set_forcing_grid(elmk_ctx* ctx, int64_t ncells, int npts, const int32_t* idx, const double* w)
 {
   if (int rc = enter(ctx)) return rc;
-  const int64_t n = ctx->ncols;
-  if (npts < 1 || npts > 8) return invalid(ctx, "elmk_set_forcing_grid: npts outside 1 .. 8");
-  if (ncells < 1 || ncells > INT32_MAX) return invalid(ctx, "elmk_set_forcing_grid: ncells outside 1 .. 2^31-1");
-  if (n > 0 && (!idx || !w)) return invalid(ctx, "elmk_set_forcing_grid: null map");
-  // every gather of the remap kernels stays inside a cell record because of these checks
-  for (int k = 0; k < npts; k++) {
-    const int32_t* ik = idx + (size_t)k * n;
-    const double* wk = w + (size_t)k * n;
-    const int32_t lo = k == 0 ? 0 : -1;
-    for (int64_t c = 0; c < n; c++) {
-      if (ik[c] < lo || ik[c] >= ncells)
-        return invalid(ctx, k == 0 ? "elmk_set_forcing_grid: idx[0] outside [0, ncells)" : "elmk_set_forcing_grid: idx outside [-1, ncells)");
-      if (ik[c] >= 0 && !std::isfinite(wk[c])) return invalid(ctx, "elmk_set_forcing_grid: non-finite weight");
-    }
-  }
+  // (every gather of the remap kernels stays inside a cell record because of this check)
+  if (int rc = invalid_map(ctx, "elmk_set_forcing_grid", ell_check(ctx->ncols, ncells, npts, idx, w))) return rc;
   if (int rc = refuse_capture(ctx, "elmk_set_forcing_grid: the stream is being captured")) return rc;
   if (int rc = run_drop(ctx)) return rc;
   elmk_ctx::Grid& G = ctx->grid;
   G = elmk_ctx::Grid{};
-  const int npad = npts <= 1 ? 1 : npts <= 2 ? 2 : npts <= 4 ? 4 : 8;
-  const size_t ld = (size_t)ctx->ld;
-  if (hip_fail(ctx, carve(G.mem, &G.bytes, [&](Carve& L) {
-                 L.take(G.idx, (size_t)npad * ld * sizeof(int32_t));
-                 L.take(G.w, (size_t)npad * ld * sizeof(double));
-                 L.take(G.cells, (size_t)ncells * sizeof(double));
-               }), "hipMalloc(forcing grid)"))
-    return ELMK_E_NOMEM;
-  G.ncells = ncells;
-  G.npts = npts;
-  G.npad = npad;
-  // padding rows and the columns past ncols: idx -1 (all bits set), w 0 (and the cells after it)
-  int rc = ELMK_OK;
-  if (hip_fail(ctx, hipMemsetAsync(G.idx, 0xFF, (char*)G.w - (char*)G.idx, ctx->stream), "hipMemset(grid idx)") ||
-      hip_fail(ctx, hipMemsetAsync(G.w, 0, G.mem + G.bytes - (char*)G.w, ctx->stream), "hipMemset(grid w)"))
-    rc = ELMK_E_HIP;
-  else if (n > 0 &&
-           (hip_fail(ctx, hipMemcpy2DAsync(G.idx, ld * sizeof(int32_t), idx, (size_t)n * sizeof(int32_t), (size_t)n * sizeof(int32_t),
-                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(grid idx)") ||
-            hip_fail(ctx, hipMemcpy2DAsync(G.w, ld * sizeof(double), w, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
-                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(grid w)")))
-    rc = ELMK_E_HIP;
-  if (rc == ELMK_OK && hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) rc = ELMK_E_HIP;
+  const int rc = hip_fail(ctx, carve(G.mem, [&](Carve& L) {
+                            G.map.take(L, ncells, npts, (size_t)ctx->ld);
+                            L.take(G.cells, (size_t)ncells * sizeof(double));
+                          }), "hipMalloc(forcing grid)")
+                     ? ELMK_E_NOMEM
+                     : G.map.upload(ctx, "grid", G.mem + G.mem.bytes(), idx, w);  // (zeroes the cells behind w too)
   if (rc != ELMK_OK) G = elmk_ctx::Grid{};
   return rc;
 }
@@ -2034,15 +2055,6 @@ int elmk_clear_forcing_grid(elmk_ctx* ctx)
 }  // extern "C"
 
 namespace {
-// wait for the runs in flight and the copy stream, and drop the captured run step (it holds the series' and the map's addresses and
-// the kernel of the map's width); the run reservation stays
-int aerosol_quiesce(elmk_ctx* ctx)
-{
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->upload) HIPCHK(hipStreamSynchronize(ctx->upload));
-  ctx->graph[GRAPH_RUN_STEP].drop();
-  return ELMK_OK;
-}
 bool aerosol_field(int f) { return f >= ELMK_FIELD_aer_bcphi && f <= ELMK_FIELD_aer_dst4_2; }
 }  // namespace
 
@@ -2051,59 +2063,31 @@ extern "C" {
 int elmk_aerosol_reserve(elmk_ctx* ctx, int64_t ncells, int npts, const int32_t* idx, const double* w)
 {
   if (int rc = enter(ctx)) return rc;
-  const int64_t n = ctx->ncols;
   if ((idx == nullptr) != (w == nullptr)) return invalid(ctx, "elmk_aerosol_reserve: idx and w must both be given or both be NULL");
   const bool mapped = idx != nullptr;
   if (ncells < 1 || ncells > INT32_MAX) return invalid(ctx, "elmk_aerosol_reserve: ncells outside 1 .. 2^31-1");
-  if (!mapped && ncells != n) return invalid(ctx, "elmk_aerosol_reserve: without a map the series are per column: ncells must equal ncols");
-  if (mapped) {
-    if (npts < 1 || npts > 8) return invalid(ctx, "elmk_aerosol_reserve: npts outside 1 .. 8");
-    // every gather of k_aerosol_deposition stays inside a cell record because of these checks
-    for (int k = 0; k < npts; k++) {
-      const int32_t* ik = idx + (size_t)k * n;
-      const double* wk = w + (size_t)k * n;
-      const int32_t lo = k == 0 ? 0 : -1;
-      for (int64_t c = 0; c < n; c++) {
-        if (ik[c] < lo || ik[c] >= ncells)
-          return invalid(ctx, k == 0 ? "elmk_aerosol_reserve: idx[0] outside [0, ncells)" : "elmk_aerosol_reserve: idx outside [-1, ncells)");
-        if (ik[c] >= 0 && !std::isfinite(wk[c])) return invalid(ctx, "elmk_aerosol_reserve: non-finite weight");
-      }
-    }
-  }
+  if (!mapped && ncells != ctx->ncols) return invalid(ctx, "elmk_aerosol_reserve: without a map the series are per column: ncells must equal ncols");
+  // (every gather of k_aerosol_deposition stays inside a cell record because of this check)
+  if (mapped)
+    if (int rc = invalid_map(ctx, "elmk_aerosol_reserve", ell_check(ctx->ncols, ncells, npts, idx, w))) return rc;
   if (int rc = refuse_capture(ctx, "elmk_aerosol_reserve: the stream is being captured")) return rc;
-  if (int rc = aerosol_quiesce(ctx)) return rc;
+  if (int rc = quiesce(ctx, true)) return rc;  // (the run reservation stays)
   if (int rc = ensure_upload_stream(ctx)) return rc;
   if (!ctx->aer_step_done) HIPCHK(hipEventCreateWithFlags(&ctx->aer_step_done, hipEventDisableTiming));
   elmk_ctx::Aerosol& A = ctx->aer;
   A = elmk_ctx::Aerosol{};
-  const int npad = !mapped ? 0 : npts <= 1 ? 1 : npts <= 2 ? 2 : npts <= 4 ? 4 : 8;
-  const size_t ld = (size_t)ctx->ld;
-  if (hip_fail(ctx, carve(A.mem, &A.bytes, [&](Carve& L) {
-                 L.take(A.cells, (size_t)AER_NSTREAM * RUN_NMONTH * (size_t)ncells * sizeof(double));
-                 if (npad) {
-                   L.take(A.idx, (size_t)npad * ld * sizeof(int32_t));
-                   L.take(A.w, (size_t)npad * ld * sizeof(double));
-                 }
-               }), "hipMalloc(aerosol series)"))
-    return ELMK_E_NOMEM;
-  A.ncells = ncells;
-  A.npts = mapped ? npts : 0;
-  A.npad = npad;
-  // the series start at 0; padding rows and the columns past ncols: idx -1 (all bits set), w 0
+  A.map.ncells = ncells;
+  const size_t series_bytes = align_up((size_t)AER_NSTREAM * RUN_NMONTH * (size_t)ncells * sizeof(double), 256);
   int rc = ELMK_OK;
-  const size_t series_bytes = npad ? (size_t)((char*)A.idx - (char*)A.cells) : A.bytes;
-  if (hip_fail(ctx, hipMemsetAsync(A.cells, 0, series_bytes, ctx->stream), "hipMemset(aerosol series)"))
+  if (hip_fail(ctx, carve(A.mem, [&](Carve& L) {
+                 L.take(A.cells, series_bytes);
+                 if (mapped) A.map.take(L, ncells, npts, (size_t)ctx->ld);
+               }), "hipMalloc(aerosol series)"))
+    rc = ELMK_E_NOMEM;
+  else if (hip_fail(ctx, hipMemsetAsync(A.cells, 0, series_bytes, ctx->stream), "hipMemset(aerosol series)"))  // the series start at 0
     rc = ELMK_E_HIP;
-  else if (npad && (hip_fail(ctx, hipMemsetAsync(A.idx, 0xFF, (char*)A.w - (char*)A.idx, ctx->stream), "hipMemset(aerosol idx)") ||
-                    hip_fail(ctx, hipMemsetAsync(A.w, 0, A.mem + A.bytes - (char*)A.w, ctx->stream), "hipMemset(aerosol w)")))
-    rc = ELMK_E_HIP;
-  else if (npad && n > 0 &&
-           (hip_fail(ctx, hipMemcpy2DAsync(A.idx, ld * sizeof(int32_t), idx, (size_t)n * sizeof(int32_t), (size_t)n * sizeof(int32_t),
-                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(aerosol idx)") ||
-            hip_fail(ctx, hipMemcpy2DAsync(A.w, ld * sizeof(double), w, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
-                                           (size_t)npts, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy2D(aerosol w)")))
-    rc = ELMK_E_HIP;
-  if (rc == ELMK_OK && hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) rc = ELMK_E_HIP;
+  else
+    rc = A.map.upload(ctx, "aerosol", A.mem + A.mem.bytes(), idx, w);
   if (rc != ELMK_OK) A = elmk_ctx::Aerosol{};
   return rc;
 }
@@ -2117,17 +2101,15 @@ int elmk_aerosol_upload(elmk_ctx* ctx, int field, int month0, int nmonths, const
   if (month0 < 0 || nmonths < 1 || month0 + (int64_t)nmonths > RUN_NMONTH) return invalid(ctx, "elmk_aerosol_upload: months outside 0 .. 11");
   if (!host) return invalid(ctx, "elmk_aerosol_upload: null host");
   if (int rc = refuse_capture(ctx, "elmk_aerosol_upload: the stream is being captured")) return rc;  // (it waits)
-  // never write under a reader of these months: each enqueued, unfinished run that reads them, and the stepwise depositions
-  const elmk_ctx::Run& R = ctx->run;
-  for (int b = 0; b < 2; b++)
-    if (R.live[b] && ((R.aer_months[b] >> month0) & ((1u << nmonths) - 1u)) != 0) HIPCHK(hipEventSynchronize(ctx->run_done[b]));
+  // never write under a reader of these months: the runs that read them, and the stepwise depositions
+  if (int rc = wait_for_runs(ctx, [&](int b) { return ((ctx->run.aer_months[b] >> month0) & ((1u << nmonths) - 1u)) != 0; })) return rc;
   if (A.step_live) {
     HIPCHK(hipEventSynchronize(ctx->aer_step_done));
     A.step_live = false;
   }
   const int k = field - ELMK_FIELD_aer_bcphi;
-  double* dst = A.cells + ((size_t)k * RUN_NMONTH + (size_t)month0) * (size_t)A.ncells;
-  HIPCHK(hipMemcpyAsync(dst, host, (size_t)nmonths * (size_t)A.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->upload));
+  double* dst = A.cells + ((size_t)k * RUN_NMONTH + (size_t)month0) * (size_t)A.map.ncells;
+  HIPCHK(hipMemcpyAsync(dst, host, (size_t)nmonths * (size_t)A.map.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->upload));
   HIPCHK(hipStreamSynchronize(ctx->upload));  // (caller's pageable source; a deposition or run enqueued after this call sees the months)
   return ELMK_OK;
 }
@@ -2153,7 +2135,7 @@ int elmk_aerosol_clear(elmk_ctx* ctx)
 {
   if (int rc = enter(ctx)) return rc;
   if (int rc = refuse_capture(ctx, "elmk_aerosol_clear: the stream is being captured")) return rc;
-  if (int rc = aerosol_quiesce(ctx)) return rc;
+  if (int rc = quiesce(ctx, true)) return rc;
   ctx->aer = elmk_ctx::Aerosol{};
   return ELMK_OK;
 }
@@ -2162,11 +2144,10 @@ int elmk_aerosol_clear(elmk_ctx* ctx)
 // shortwave: interval-mean FSDS weighted by cos(zenith) (include/elmk.h "shortwave")
 // ---------------------------------------------------------------------------------------------------
 namespace {
-// set the mode and forget every record time: wait for the runs in flight, drop the captured run step (it holds the mode's kernels)
+// set the mode and forget every record time
 int sw_reset(elmk_ctx* ctx, int mode, double forc_dt)
 {
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->graph[GRAPH_RUN_STEP].drop();
+  if (int rc = quiesce(ctx, false)) return rc;
   elmk_ctx::Shortwave& W = ctx->sw;
   W.mode = mode;
   W.forc_dt = mode == ELMK_SW_COSZEN ? forc_dt : 0.0;
@@ -2192,7 +2173,6 @@ int elmk_set_shortwave_mode(elmk_ctx* ctx, int mode, double forc_dt_seconds)
   if (mode == ELMK_SW_COSZEN && !W.czf) {
     const size_t bytes = (size_t)ctx->ld * sizeof(double);
     if (hip_fail(ctx, W.czf.alloc(bytes), "hipMalloc(shortwave czf)")) return ELMK_E_NOMEM;
-    W.czf_bytes = bytes;
     HIPCHK(hipMemsetAsync(W.czf, 0, bytes, ctx->stream));
   }
   return sw_reset(ctx, mode, forc_dt_seconds);
@@ -2227,12 +2207,10 @@ int elmk_series_record_times(elmk_ctx* ctx, int slot0, int nslots, const double*
   if (!R.rec) {
     const size_t bytes = (size_t)R.slots * sizeof(elmk_solar_step);
     if (hip_fail(ctx, R.rec.alloc(bytes), "hipMalloc(record times)")) return ELMK_E_NOMEM;
-    R.rec_bytes = bytes;
     R.rec_set.assign((size_t)R.slots, 0);
   }
-  // never write under a run that reads these slots (as elmk_series_upload)
-  for (int b = 0; b < 2; b++)
-    if (R.live[b] && slot0 <= R.slot_hi[b] && slot0 + nslots - 1 >= R.slot_lo[b]) HIPCHK(hipEventSynchronize(ctx->run_done[b]));
+  // (the runs that read these slots, as elmk_series_upload)
+  if (int rc = wait_for_runs(ctx, [&](int b) { return slot0 <= R.slot_hi[b] && slot0 + nslots - 1 >= R.slot_lo[b]; })) return rc;
   std::vector<elmk_solar_step> q((size_t)nslots);
   for (int i = 0; i < nslots; i++) q[(size_t)i] = elmk_solar_step_consts(ctx->sw.forc_dt, rec_decday[i], 0);
   HIPCHK(hipMemcpyAsync(R.rec + slot0, q.data(), q.size() * sizeof(elmk_solar_step), hipMemcpyHostToDevice, ctx->upload));
@@ -2256,21 +2234,12 @@ int elmk_download_forcing_cosz(elmk_ctx* ctx, double* czf)
 // downscaling: forcing adjusted to each column's elevation (include/elmk.h "downscaling")
 // ---------------------------------------------------------------------------------------------------
 namespace {
-// every downscaling setter: wait for the runs in flight (they read the elevations and groups), drop the captured run step (it holds
-// the mode's kernels and the groups' addresses)
-int ds_quiesce(elmk_ctx* ctx)
-{
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->graph[GRAPH_RUN_STEP].drop();
-  return ELMK_OK;
-}
 int ds_alloc_topo(elmk_ctx* ctx)
 {
   elmk_ctx::Downscale& D = ctx->ds;
   if (D.topo) return ELMK_OK;
   const size_t bytes = 2 * (size_t)ctx->ld * sizeof(double);
   if (hip_fail(ctx, D.topo.alloc(bytes), "hipMalloc(elevations)")) return ELMK_E_NOMEM;
-  D.topo_bytes = bytes;
   HIPCHK(hipMemsetAsync(D.topo, 0, bytes, ctx->stream));
   return ELMK_OK;
 }
@@ -2290,7 +2259,7 @@ int elmk_set_column_elevation(elmk_ctx* ctx, const double* topo_col, const doubl
   if (n > 0 && (!all_finite(topo_col, n) || (topo_forc && !all_finite(topo_forc, n))))
     return invalid(ctx, "elmk_set_column_elevation: non-finite elevation");
   if (int rc = refuse_capture(ctx, "elmk_set_column_elevation: the stream is being captured")) return rc;
-  if (int rc = ds_quiesce(ctx)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;
   if (int rc = ds_alloc_topo(ctx)) return rc;
   elmk_ctx::Downscale& D = ctx->ds;
   if (n > 0) {
@@ -2309,14 +2278,14 @@ int elmk_set_forcing_elevation_gridded(elmk_ctx* ctx, const double* cells)
   const elmk_ctx::Grid& G = ctx->grid;
   if (!G.mem) return invalid(ctx, "elmk_set_forcing_elevation_gridded: no forcing grid (elmk_set_forcing_grid)");
   if (!cells) return invalid(ctx, "elmk_set_forcing_elevation_gridded: null cells");
-  if (!all_finite(cells, G.ncells)) return invalid(ctx, "elmk_set_forcing_elevation_gridded: non-finite elevation");
+  if (!all_finite(cells, G.map.ncells)) return invalid(ctx, "elmk_set_forcing_elevation_gridded: non-finite elevation");
   if (int rc = refuse_capture(ctx, "elmk_set_forcing_elevation_gridded: the stream is being captured")) return rc;
-  if (int rc = ds_quiesce(ctx)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;
   if (int rc = ds_alloc_topo(ctx)) return rc;
   elmk_ctx::Downscale& D = ctx->ds;
   if (ctx->ncols > 0) {
-    HIPCHK(hipMemcpyAsync(G.cells, cells, (size_t)G.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_remap_field_f64(D.topo + ctx->ld, G.cells, ctx->ncols, ctx->ld, G.npad, G.idx, G.w, ctx->stream);
+    HIPCHK(hipMemcpyAsync(G.cells, cells, (size_t)G.map.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_remap_field_f64(D.topo + ctx->ld, G.cells, ctx->ncols, ctx->ld, G.map.npad, G.map.idx, G.map.w, ctx->stream);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));  // (the staging is reused by the next call)
@@ -2336,7 +2305,7 @@ int elmk_set_downscaling(elmk_ctx* ctx, int mode, double lapse, double lapse_lw,
   if (mode == ELMK_DS_TOPO && !(D.col_set && D.forc_set))
     return invalid(ctx, "elmk_set_downscaling: TOPO needs both elevations (elmk_set_column_elevation, elmk_set_forcing_elevation_gridded)");
   if (int rc = refuse_capture(ctx, "elmk_set_downscaling: the stream is being captured")) return rc;
-  if (int rc = ds_quiesce(ctx)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;
   D.mode = mode;
   D.lapse = lapse;
   D.lapse_lw = lapse_lw;
@@ -2347,55 +2316,31 @@ int elmk_set_downscaling(elmk_ctx* ctx, int mode, double lapse, double lapse_lw,
 int elmk_set_downscaling_groups(elmk_ctx* ctx, int64_t ngroups, const int64_t* ptr, const int32_t* col, const double* w)
 {
   if (int rc = enter(ctx)) return rc;
-  const char* bad = nullptr;
-  if (ngroups < 1 || ngroups > INT32_MAX) bad = "ngroups outside 1 .. 2^31-1";
-  else if (!ptr) bad = "null ptr";
-  else if (ptr[0] != 0) bad = "ptr[0] != 0";
-  for (int64_t i = 0; !bad && i < ngroups; i++)
-    if (ptr[i + 1] < ptr[i]) bad = "ptr decreasing";
-  const int64_t nnz = bad ? 0 : ptr[ngroups];
-  if (!bad && nnz > INT32_MAX) bad = "nnz outside 0 .. 2^31-1";
-  if (!bad && nnz > 0 && (!col || !w)) bad = "null map";
-  // every gather and scatter of the renormalisation stays inside the longwave row, and a column is scaled once, because of these
-  std::vector<char> seen(bad ? 0 : (size_t)ctx->ncols, 0);
-  for (int64_t p = 0; !bad && p < nnz; p++) {
-    if (col[p] < 0 || col[p] >= ctx->ncols) bad = "col outside [0, ncols)";
-    else if (seen[(size_t)col[p]]++) bad = "a column in more than one group (or twice in one)";
-    else if (!(std::isfinite(w[p]) && w[p] >= 0.0)) bad = "weight not finite and >= 0";
-  }
-  if (bad) return invalid(ctx, (std::string("elmk_set_downscaling_groups: ") + bad).c_str());
+  // (every gather and scatter of the renormalisation stays inside the longwave row, and a column is scaled once, because of this check)
+  if (int rc = invalid_map(ctx, "elmk_set_downscaling_groups", csr_check(ngroups, ctx->ncols, ptr, col, w, "ngroups outside 1 .. 2^31-1", true, true))) return rc;
   if (int rc = refuse_capture(ctx, "elmk_set_downscaling_groups: the stream is being captured")) return rc;
-  if (int rc = ds_quiesce(ctx)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;
   elmk_ctx::Downscale& D = ctx->ds;
   (void)D.gmem.reset();
-  D.gbytes = 0;
   std::vector<double> wsum((size_t)ngroups, 0.0);  // W = w[p0], then W = W + w[p]: the order of agg_cells
   for (int64_t g = 0; g < ngroups; g++)
     for (int64_t p = ptr[g]; p < ptr[g + 1]; p++) wsum[(size_t)g] = p == ptr[g] ? w[p] : wsum[(size_t)g] + w[p];
-  if (hip_fail(ctx, carve(D.gmem, &D.gbytes, [&](Carve& L) {
-                 L.take(D.ptr, (size_t)(ngroups + 1) * sizeof(int64_t));
-                 L.take(D.col, (size_t)nnz * sizeof(int32_t));
-                 L.take(D.w, (size_t)nnz * sizeof(double));
+  int rc = ELMK_OK;
+  if (hip_fail(ctx, carve(D.gmem, [&](Carve& L) {
+                 D.groups.take(L, ngroups, ptr[ngroups]);
                  L.take(D.wsum, (size_t)ngroups * sizeof(double));
                  L.take(D.lg, (size_t)ctx->ld * sizeof(double));
-               }), "hipMalloc(downscaling groups)")) {
-    D.gbytes = 0;
-    return ELMK_E_NOMEM;
-  }
-  D.ngroups = ngroups;
-  D.nnz = nnz;
-  int rc = ELMK_OK;
-  if (hip_fail(ctx, hipMemsetAsync(D.lg, 0, (size_t)ctx->ld * sizeof(double), ctx->stream), "hipMemset(lg)") ||
-      hip_fail(ctx, hipMemcpyAsync(D.ptr, ptr, (size_t)(ngroups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(ptr)") ||
-      hip_fail(ctx, hipMemcpyAsync(D.wsum, wsum.data(), (size_t)ngroups * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(wsum)") ||
-      (nnz > 0 && (hip_fail(ctx, hipMemcpyAsync(D.col, col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(col)") ||
-                   hip_fail(ctx, hipMemcpyAsync(D.w, w, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(w)"))) ||
-      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+               }), "hipMalloc(downscaling groups)"))
+    rc = ELMK_E_NOMEM;
+  else if (hip_fail(ctx, hipMemsetAsync(D.lg, 0, (size_t)ctx->ld * sizeof(double), ctx->stream), "hipMemset(lg)"))
     rc = ELMK_E_HIP;
+  else
+    rc = D.groups.upload(ctx, ptr, col, w, [&] {
+      return hip_fail(ctx, hipMemcpyAsync(D.wsum, wsum.data(), (size_t)ngroups * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(wsum)");
+    });
   if (rc != ELMK_OK) {
     (void)D.gmem.reset();
-    D.gbytes = 0;
-    D.ngroups = D.nnz = 0;
+    D.groups = CsrMap{};
   }
   return rc;
 }
@@ -2404,11 +2349,10 @@ int elmk_clear_downscaling_groups(elmk_ctx* ctx)
 {
   if (int rc = enter(ctx)) return rc;
   if (int rc = refuse_capture(ctx, "elmk_clear_downscaling_groups: the stream is being captured")) return rc;
-  if (int rc = ds_quiesce(ctx)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;
   elmk_ctx::Downscale& D = ctx->ds;
+  D.groups = CsrMap{};
   HIPCHK(D.gmem.reset());
-  D.gbytes = 0;
-  D.ngroups = D.nnz = 0;
   return ELMK_OK;
 }
 
@@ -2437,8 +2381,8 @@ int elmk_upload_gridded(elmk_ctx* ctx, int field, int level, const double* cells
   if (ctx->ncols == 0) return ELMK_OK;
   char* dst = (char*)ctx->fptr[field] + (size_t)level * (size_t)ctx->ld * (size_t)store_size(ELMK_F64);
   // staging is reused by the next call: the copy and the remap are done when this returns, as elmk_upload's copy is
-  HIPCHK(hipMemcpyAsync(G.cells, cells, (size_t)G.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  launch_remap_field(dst, G.cells, ctx->ncols, ctx->ld, G.npad, G.idx, G.w, ctx->stream);
+  HIPCHK(hipMemcpyAsync(G.cells, cells, (size_t)G.map.ncells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  launch_remap_field(dst, G.cells, ctx->ncols, ctx->ld, G.map.npad, G.map.idx, G.map.w, ctx->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return ELMK_OK;
@@ -2450,39 +2394,17 @@ int elmk_upload_gridded(elmk_ctx* ctx, int field, int level, const double* cells
 int elmk_set_output_grid(elmk_ctx* ctx, int64_t ncells, const int64_t* ptr, const int32_t* col, const double* w, double fill)
 {
   if (int rc = enter(ctx)) return rc;
-  if (ncells < 1 || ncells > INT32_MAX) return invalid(ctx, "elmk_set_output_grid: ncells outside 1 .. 2^31-1");
-  if (!ptr) return invalid(ctx, "elmk_set_output_grid: null ptr");
-  if (ptr[0] != 0) return invalid(ctx, "elmk_set_output_grid: ptr[0] != 0");
-  for (int64_t i = 0; i < ncells; i++)
-    if (ptr[i + 1] < ptr[i]) return invalid(ctx, "elmk_set_output_grid: ptr decreasing");
-  const int64_t nnz = ptr[ncells];
-  if (nnz > INT32_MAX) return invalid(ctx, "elmk_set_output_grid: nnz outside 0 .. 2^31-1");
-  if (nnz > 0 && (!col || !w)) return invalid(ctx, "elmk_set_output_grid: null map");
-  // every gather of the aggregate kernels stays inside a source row because of these checks
-  for (int64_t p = 0; p < nnz; p++) {
-    if (col[p] < 0 || col[p] >= ctx->ncols) return invalid(ctx, "elmk_set_output_grid: col outside [0, ncols)");
-    if (!std::isfinite(w[p])) return invalid(ctx, "elmk_set_output_grid: non-finite weight");
-  }
+  // (every gather of the aggregate kernels stays inside a source row because of this check)
+  if (int rc = invalid_map(ctx, "elmk_set_output_grid", csr_check(ncells, ctx->ncols, ptr, col, w, "ncells outside 1 .. 2^31-1", false, false))) return rc;
   if (int rc = refuse_capture(ctx, "elmk_set_output_grid: the stream is being captured")) return rc;
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_set_output_grid: gridded history entries exist (elmk_history_clear first)");
   HIPCHK(hipStreamSynchronize(ctx->stream));  // (a gridded download may still read the old map)
   elmk_ctx::OGrid& O = ctx->ogrid;
   O = elmk_ctx::OGrid{};
-  if (hip_fail(ctx, carve(O.mem, &O.bytes, [&](Carve& L) {
-                 L.take(O.ptr, (size_t)(ncells + 1) * sizeof(int64_t));
-                 L.take(O.col, (size_t)nnz * sizeof(int32_t));
-                 L.take(O.w, (size_t)nnz * sizeof(double));
-               }), "hipMalloc(output grid)"))
-    return ELMK_E_NOMEM;
-  O.ncells = ncells;
-  O.nnz = nnz;
   O.fill = fill;
-  int rc = ELMK_OK;
-  if (hip_fail(ctx, hipMemcpyAsync(O.ptr, ptr, (size_t)(ncells + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(ptr)") ||
-      (nnz > 0 && (hip_fail(ctx, hipMemcpyAsync(O.col, col, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(col)") ||
-                   hip_fail(ctx, hipMemcpyAsync(O.w, w, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(w)"))) ||
-      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
-    rc = ELMK_E_HIP;
+  const int rc = hip_fail(ctx, carve(O.mem, [&](Carve& L) { O.map.take(L, ncells, ptr[ncells]); }), "hipMalloc(output grid)")
+                     ? ELMK_E_NOMEM
+                     : O.map.upload(ctx, ptr, col, w, [] { return false; });
   if (rc != ELMK_OK) O = elmk_ctx::OGrid{};
   return rc;
 }
@@ -2509,9 +2431,9 @@ int elmk_download_gridded(elmk_ctx* ctx, int field, int level, double* cells)
   const int es = store_size(g_fields[field].dtype);
   const char* src = (const char*)ctx->fptr[field] + (size_t)level * (size_t)ctx->ld * es;
   // chunks of cells through the staging buffer, which the next chunk reuses
-  const int64_t chunk = (int64_t)(ctx->staging_bytes / sizeof(double));
-  for (int64_t done = 0; done < O.ncells; done += chunk) {
-    const int64_t m = (O.ncells - done) < chunk ? (O.ncells - done) : chunk;
+  const int64_t chunk = (int64_t)(ctx->staging.bytes() / sizeof(double)), ncells = O.map.nrows;
+  for (int64_t done = 0; done < ncells; done += chunk) {
+    const int64_t m = (ncells - done) < chunk ? (ncells - done) : chunk;
     launch_ogrid_aggregate(src, store_dtype(g_fields[field].dtype), ogrid_map(ctx), done, m, (double*)(char*)ctx->staging, ctx->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(cells + done, ctx->staging, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -2779,8 +2701,8 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
   }
   for (size_t i = 0; i < ctx->hist.size(); i++) {
     const elmk_ctx::HistEntry& e = ctx->hist[i];
-    const int64_t ext = e.cells ? ctx->ogrid.ncells : ctx->ncols;
-    L.ent.push_back(elmk_restart_entry{e.tape, e.field, e.op, e.cells ? 1 : 0, e.cells ? ctx->ogrid.ncells : 0});
+    const int64_t ext = e.cells ? ctx->ogrid.map.nrows : ctx->ncols;
+    L.ent.push_back(elmk_restart_entry{e.tape, e.field, e.op, e.cells ? 1 : 0, e.cells ? ctx->ogrid.map.nrows : 0});
     L.sec.push_back(elmk_restart_section{e.cells ? ELMK_RESTART_GRIDDED : ELMK_RESTART_HISTORY, (int32_t)i, e.nlev, ELMK_F64, ext, 0, 0});
     L.src.push_back(RstSrc{(char*)(double*)e.acc, e.cld, ELMK_F64, e.cells ? 0 : gcol0, false});
   }

@@ -44,6 +44,21 @@ PSN_FIELDS = (
 ALB_SOURCES = ["rholvis", "rholnir", "rhosvis", "rhosnir", "taulvis", "taulnir", "tausvis", "tausnir", "xl"]
 
 
+def _p(a):
+    """The address of a numpy array's data as the ABI's void pointer."""
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _csr_args(ptr, col, w, rows_name):
+    """A CSR map as the ABI takes it: (nrows, ptr int64 [nrows + 1], col int32 [nnz], w float64 [nnz])."""
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+    col = np.ascontiguousarray(col, dtype=np.int32).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if ptr.size < 2 or col.size != w.size or ptr[-1] != col.size:
+        raise ValueError(f"ptr must be [{rows_name} + 1] with ptr[-1] == len(col) == len(w)")
+    return ptr.size - 1, ptr, col, w
+
+
 def field_table():
     lib = L.load()
     out = {}
@@ -112,6 +127,16 @@ class ELMState:
         if rc < 0:
             raise L.ElmkError(f"{what} failed ({rc}): {self.lib.elmk_last_error(self.ctx).decode()}")
         return rc
+
+    def _ell_args(self, idx, w):
+        """A per-column ELL map as the ABI takes it: (npts, idx int32 [npts, ncols], w float64 [npts, ncols])."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if idx.ndim == 1:
+            idx, w = idx[None, :], w.reshape(1, -1)
+        if idx.shape != w.shape or idx.shape[1] != self.ncols:
+            raise ValueError(f"idx and w must both be [npts, {self.ncols}]")
+        return idx.shape[0], idx, w
 
     # -- arrays -----------------------------------------------------------------------------------
     def upload(self, name, arr, col0=0, layout=LAYOUT_COL_MAJOR):
@@ -217,13 +242,13 @@ class ELMState:
         a = np.ascontiguousarray(roota_par, dtype=np.float64)
         b = np.ascontiguousarray(rootb_par, dtype=np.float64)
         assert a.shape == (25,) and b.shape == (25,)
-        self._chk(self.lib.elmk_set_init_params(self.ctx, float(organic_max), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)), "set_init_params")
+        self._chk(self.lib.elmk_set_init_params(self.ctx, float(organic_max), _p(a), _p(b)), "set_init_params")
 
     def set_snow_age_tables(self, tables):
         """SnwRdsTable: tables [3, 11, 31, 8] = snowage_tau, snowage_kappa, snowage_drdt0."""
         t = np.ascontiguousarray(tables, dtype=np.float64)
         assert t.shape == (3, 11, 31, 8)
-        self._chk(self.lib.elmk_set_snow_age_tables(self.ctx, *[t[k].ctypes.data_as(C.c_void_p) for k in range(3)]), "set_snow_age_tables")
+        self._chk(self.lib.elmk_set_snow_age_tables(self.ctx, *[_p(t[k]) for k in range(3)]), "set_snow_age_tables")
 
     # -- control ----------------------------------------------------------------------------------
     def sync(self):
@@ -261,25 +286,25 @@ class ELMState:
     def canopy_trip_counts(self):
         """Trips of the leaf-temperature iteration per column in the last canopy_fluxes call (0: not vegetated)."""
         out = np.zeros(self.ncols, dtype=np.int32)
-        self._chk(self.lib.elmk_read_scratch(self.ctx, 0, out.ctypes.data_as(C.c_void_p), 0, self.ncols), "read_scratch")
+        self._chk(self.lib.elmk_read_scratch(self.ctx, 0, _p(out), 0, self.ncols), "read_scratch")
         return out
 
     def canopy_schedule_hints(self):
         """The scheduler's hint per column: slowly decaying maximum of the trip count (development diagnostics)."""
         out = np.zeros(self.ncols, dtype=np.int32)
-        self._chk(self.lib.elmk_read_scratch(self.ctx, 2, out.ctypes.data_as(C.c_void_p), 0, self.ncols), "read_scratch")
+        self._chk(self.lib.elmk_read_scratch(self.ctx, 2, _p(out), 0, self.ncols), "read_scratch")
         return out
 
     def work_list_counters(self):
         """(entries, queue head) of every internal work list [nlists, 2]: all zero between two wrapper calls."""
         n = 8
         out = np.zeros(2 * n, dtype=np.uint32)
-        self._chk(self.lib.elmk_read_scratch(self.ctx, 3, out.ctypes.data_as(C.c_void_p), 0, 2 * n), "read_scratch")
+        self._chk(self.lib.elmk_read_scratch(self.ctx, 3, _p(out), 0, 2 * n), "read_scratch")
         return out.reshape(n, 2)
 
     def read_work(self, offset, count):
         out = np.zeros(int(count), dtype=np.float64)
-        self._chk(self.lib.elmk_read_scratch(self.ctx, 1, out.ctypes.data_as(C.c_void_p), int(offset), int(count)), "read_scratch")
+        self._chk(self.lib.elmk_read_scratch(self.ctx, 1, _p(out), int(offset), int(count)), "read_scratch")
         return out
 
     def profile_wrapper(self, wrapper, dt, nsteps=5):
@@ -310,8 +335,7 @@ class ELMState:
         lat = np.ascontiguousarray(lat, dtype=np.float64).reshape(-1)
         lon = np.ascontiguousarray(lon, dtype=np.float64).reshape(-1)
         assert lat.size == self.ncols and lon.size == self.ncols
-        self._chk(self.lib.elmk_set_column_geography(self.ctx, lat.ctypes.data_as(C.c_void_p), lon.ctypes.data_as(C.c_void_p)),
-                  "set_column_geography")
+        self._chk(self.lib.elmk_set_column_geography(self.ctx, _p(lat), _p(lon)), "set_column_geography")
 
     def solar_geometry(self, dt, decday, doy):
         """kokkos_init_timestep's solar lines for every column at its own location: coszen, and per-column day length for
@@ -321,8 +345,7 @@ class ELMState:
     def day_length(self):
         """(dayl, max_dayl) of every column from the last solar_geometry()."""
         dayl, max_dayl = np.empty(self.ncols), np.empty(self.ncols)
-        self._chk(self.lib.elmk_download_day_length(self.ctx, dayl.ctypes.data_as(C.c_void_p), max_dayl.ctypes.data_as(C.c_void_p)),
-                  "day_length")
+        self._chk(self.lib.elmk_download_day_length(self.ctx, _p(dayl), _p(max_dayl)), "day_length")
         return dayl, max_dayl
 
     def clear_column_geography(self):
@@ -364,8 +387,7 @@ class ELMState:
             nlev = self._hist_nlev.get(int(entry), 1)
         shape = (n,) if nlev == 1 else ((n, nlev) if layout == LAYOUT_COL_MAJOR else (nlev, n))
         out = np.empty(shape, dtype=np.float64)
-        self._chk(self.lib.elmk_history_read(self.ctx, int(entry), out.ctypes.data_as(C.c_void_p), int(col0), n, int(layout)),
-                  "history_read")
+        self._chk(self.lib.elmk_history_read(self.ctx, int(entry), _p(out), int(col0), n, int(layout)), "history_read")
         return out
 
     def history_clear(self):
@@ -397,7 +419,7 @@ class ELMState:
             a = np.ascontiguousarray(values, dtype=np.float64)
             if a.size != self._accum_nlev.get(int(entry), 1) * self.ncols:
                 raise ValueError(f"accum_init: {a.size} values for {self._accum_nlev.get(int(entry), 1)} x {self.ncols}")
-            p = a.ctypes.data_as(C.c_void_p)
+            p = _p(a)
         self._chk(self.lib.elmk_accum_init(self.ctx, int(entry), p, int(nsteps)), "accum_init")
 
     def accum_update(self):
@@ -412,8 +434,7 @@ class ELMState:
         shape = (n,) if nlev == 1 else ((n, nlev) if layout == LAYOUT_COL_MAJOR else (nlev, n))
         out = np.empty(shape, dtype=np.float64)
         cnt = C.c_int64()
-        self._chk(self.lib.elmk_accum_read(self.ctx, int(entry), out.ctypes.data_as(C.c_void_p), int(col0), n, int(layout),
-                                           C.byref(cnt)), "accum_read")
+        self._chk(self.lib.elmk_accum_read(self.ctx, int(entry), _p(out), int(col0), n, int(layout), C.byref(cnt)), "accum_read")
         return out, cnt.value
 
     def accum_clear(self):
@@ -433,16 +454,10 @@ class ELMState:
             ncells = self.ncols if ncells is None else int(ncells)
             self._chk(self.lib.elmk_aerosol_reserve(self.ctx, ncells, 0, None, None), "aerosol_reserve")
         else:
-            idx = np.ascontiguousarray(idx, dtype=np.int32)
-            w = np.ascontiguousarray(w, dtype=np.float64)
-            if idx.ndim == 1:
-                idx, w = idx[None, :], w.reshape(1, -1)
-            if idx.shape != w.shape or idx.shape[1] != self.ncols:
-                raise ValueError(f"idx and w must both be [npts, {self.ncols}]")
+            npts, idx, w = self._ell_args(idx, w)
             if ncells is None:
                 raise ValueError("aerosol_reserve: ncells of the aerosol grid is needed with a map")
-            self._chk(self.lib.elmk_aerosol_reserve(self.ctx, int(ncells), idx.shape[0], idx.ctypes.data_as(C.c_void_p),
-                                                    w.ctypes.data_as(C.c_void_p)), "aerosol_reserve")
+            self._chk(self.lib.elmk_aerosol_reserve(self.ctx, int(ncells), npts, _p(idx), _p(w)), "aerosol_reserve")
         self.aerosol_ncells = int(ncells)
 
     def aerosol_upload(self, name, month0, records):
@@ -455,7 +470,7 @@ class ELMState:
         if nc is not None and a.shape[1] != nc:
             raise ValueError(f"{name}: {a.shape[1]} cell values per month, the series has {nc}")
         fid = self.fields[name if name in self.fields else "aer_" + name][0] if isinstance(name, str) else int(name)
-        self._chk(self.lib.elmk_aerosol_upload(self.ctx, fid, int(month0), a.shape[0], a.ctypes.data_as(C.c_void_p)), f"aerosol_upload({name})")
+        self._chk(self.lib.elmk_aerosol_upload(self.ctx, fid, int(month0), a.shape[0], _p(a)), f"aerosol_upload({name})")
 
     def aerosol_deposition(self, month1, month2, wt1, wt2):
         """aer_* of every column = wt1 * (month1 remapped) + wt2 * (month2 remapped), one launch, stream-ordered, no sync."""
@@ -479,20 +494,19 @@ class ELMState:
         a = np.ascontiguousarray(records, dtype=np.float64)
         if a.ndim == 1:
             a = a[None, :]
-        self._chk(self.lib.elmk_series_upload(self.ctx, self.fields[name][0], int(slot0), a.shape[0], a.ctypes.data_as(C.c_void_p),
+        self._chk(self.lib.elmk_series_upload(self.ctx, self.fields[name][0], int(slot0), a.shape[0], _p(a),
                                               int(col0), a.shape[1]), f"series_upload({name})")
 
     def run(self, dt, steps, flags=0):
         """elmk_run: len(steps) model steps on the device, steps a RUN_STEP_DTYPE array; stream-ordered, no synchronisation."""
         a = np.ascontiguousarray(steps, dtype=RUN_STEP_DTYPE)
-        self._chk(self.lib.elmk_run(self.ctx, float(dt), a.ctypes.data_as(C.c_void_p), int(a.size), int(flags)), "run")
+        self._chk(self.lib.elmk_run(self.ctx, float(dt), _p(a), int(a.size), int(flags)), "run")
 
     def run_diagnostics(self):
         """Of the last run (synchronises): conservation (min, max, sum) [nsteps, 8, 3], flag OR [nsteps], first fatal column [nsteps]."""
         m = max(getattr(self, "_run_max", 0), 1)
         mms, fo, fb = np.zeros((m, 8, 3)), np.zeros(m, np.uint32), np.zeros(m, np.int64)
-        n = self._chk(self.lib.elmk_run_diagnostics(self.ctx, mms.ctypes.data_as(C.c_void_p), fo.ctypes.data_as(C.c_void_p),
-                                                    fb.ctypes.data_as(C.c_void_p)), "run_diagnostics")
+        n = self._chk(self.lib.elmk_run_diagnostics(self.ctx, _p(mms), _p(fo), _p(fb)), "run_diagnostics")
         return mms[:n].copy(), fo[:n].copy(), fb[:n].copy()
 
     # -- shortwave (include/elmk.h: elmk_set_shortwave_mode ...) -------------------------------------
@@ -509,12 +523,12 @@ class ELMState:
     def series_record_times(self, slot0, rec_decday):
         """COSZEN, runs: the record start (decimal_doy + 1.0) of forcing slots slot0 .. slot0 + len(rec_decday) - 1."""
         a = np.ascontiguousarray(rec_decday, dtype=np.float64).reshape(-1)
-        self._chk(self.lib.elmk_series_record_times(self.ctx, int(slot0), a.size, a.ctypes.data_as(C.c_void_p)), "series_record_times")
+        self._chk(self.lib.elmk_series_record_times(self.ctx, int(slot0), a.size, _p(a)), "series_record_times")
 
     def forcing_cosz(self):
         """czf [ncols]: the forcing interval's mean cos(zenith) of the last record time or COSZEN run step (synchronises)."""
         out = np.empty(self.ncols)
-        self._chk(self.lib.elmk_download_forcing_cosz(self.ctx, out.ctypes.data_as(C.c_void_p)), "forcing_cosz")
+        self._chk(self.lib.elmk_download_forcing_cosz(self.ctx, _p(out)), "forcing_cosz")
         return out
 
     # -- downscaling (include/elmk.h: elmk_set_downscaling ...) ---------------------------------------
@@ -529,15 +543,14 @@ class ELMState:
         the columns' (the forcing's then comes from set_forcing_elevation_gridded)."""
         hc = self._cols(topo_col, "topo_col")
         hf = None if topo_forc is None else self._cols(topo_forc, "topo_forc")
-        self._chk(self.lib.elmk_set_column_elevation(self.ctx, hc.ctypes.data_as(C.c_void_p), None if hf is None else hf.ctypes.data_as(C.c_void_p)),
-                  "set_column_elevation")
+        self._chk(self.lib.elmk_set_column_elevation(self.ctx, _p(hc), None if hf is None else _p(hf)), "set_column_elevation")
 
     def set_forcing_elevation_gridded(self, cells):
         """The forcing's surface height from its grid's cells [ncells], remapped through the forcing map (regrid.apply_map)."""
         a = np.ascontiguousarray(cells, dtype=np.float64).reshape(-1)
         if getattr(self, "grid_ncells", None) is not None and a.size != self.grid_ncells:
             raise ValueError(f"{a.size} cell values, the grid has {self.grid_ncells}")
-        self._chk(self.lib.elmk_set_forcing_elevation_gridded(self.ctx, a.ctypes.data_as(C.c_void_p)), "set_forcing_elevation_gridded")
+        self._chk(self.lib.elmk_set_forcing_elevation_gridded(self.ctx, _p(a)), "set_forcing_elevation_gridded")
 
     def set_downscaling(self, mode, lapse=LAPSE, lapse_lw=LAPSE_LW, lw_limit=LW_LIMIT):
         """"off" (the default) or "topo": forcing adjusted from the forcing's surface height to each column's elevation."""
@@ -547,13 +560,8 @@ class ELMState:
     def set_downscaling_groups(self, ptr, col, w):
         """Longwave renormalisation groups, CSR by gridcell (regrid.owner_map builds one): ptr int64 [ngroups + 1], col int32 [nnz],
         w float64 [nnz]; a column in at most one group, weights finite and >= 0."""
-        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
-        col = np.ascontiguousarray(col, dtype=np.int32).reshape(-1)
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        if ptr.size < 2 or col.size != w.size or ptr[-1] != col.size:
-            raise ValueError("ptr must be [ngroups + 1] with ptr[-1] == len(col) == len(w)")
-        self._chk(self.lib.elmk_set_downscaling_groups(self.ctx, ptr.size - 1, ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
-                                                       w.ctypes.data_as(C.c_void_p)), "set_downscaling_groups")
+        ngroups, ptr, col, w = _csr_args(ptr, col, w, "ngroups")
+        self._chk(self.lib.elmk_set_downscaling_groups(self.ctx, ngroups, _p(ptr), _p(col), _p(w)), "set_downscaling_groups")
 
     def clear_downscaling_groups(self):
         self._chk(self.lib.elmk_clear_downscaling_groups(self.ctx), "clear_downscaling_groups")
@@ -561,22 +569,15 @@ class ELMState:
     def column_elevation(self):
         """(topo_col, topo_forc) as held on the device (synchronises)."""
         hc, hf = np.empty(self.ncols), np.empty(self.ncols)
-        self._chk(self.lib.elmk_download_column_elevation(self.ctx, hc.ctypes.data_as(C.c_void_p), hf.ctypes.data_as(C.c_void_p)),
-                  "column_elevation")
+        self._chk(self.lib.elmk_download_column_elevation(self.ctx, _p(hc), _p(hf)), "column_elevation")
         return hc, hf
 
     # -- forcing on a coarser grid (include/elmk.h: elmk_set_forcing_grid ...) -----------------------
     def set_forcing_grid(self, idx, w, ncells):
         """The per-column remap map (elmkernels_amd/regrid.py): idx int32 [npts, ncols] (-1 = padding, never in row 0), w float64
         [npts, ncols], ncells source cells.  Releases the run reservation (run_reserve again before run)."""
-        idx = np.ascontiguousarray(idx, dtype=np.int32)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if idx.ndim == 1:
-            idx, w = idx[None, :], w.reshape(1, -1)
-        if idx.shape != w.shape or idx.shape[1] != self.ncols:
-            raise ValueError(f"idx and w must both be [npts, {self.ncols}]")
-        self._chk(self.lib.elmk_set_forcing_grid(self.ctx, int(ncells), idx.shape[0], idx.ctypes.data_as(C.c_void_p),
-                                                 w.ctypes.data_as(C.c_void_p)), "set_forcing_grid")
+        npts, idx, w = self._ell_args(idx, w)
+        self._chk(self.lib.elmk_set_forcing_grid(self.ctx, int(ncells), npts, _p(idx), _p(w)), "set_forcing_grid")
         self.grid_ncells = int(ncells)
 
     def clear_forcing_grid(self):
@@ -589,21 +590,15 @@ class ELMState:
         a = np.ascontiguousarray(cells, dtype=np.float64).reshape(-1)
         if getattr(self, "grid_ncells", None) is not None and a.size != self.grid_ncells:
             raise ValueError(f"{name}: {a.size} cell values, the grid has {self.grid_ncells}")
-        self._chk(self.lib.elmk_upload_gridded(self.ctx, self.fields[name][0], int(level), a.ctypes.data_as(C.c_void_p)),
-                  f"upload_gridded({name})")
+        self._chk(self.lib.elmk_upload_gridded(self.ctx, self.fields[name][0], int(level), _p(a)), f"upload_gridded({name})")
 
     # -- output grid (include/elmk.h: elmk_set_output_grid ...) ----------------------------------------
     def set_output_grid(self, ptr, col, w, fill=np.nan):
         """The CSR aggregation map by output cell (elmkernels_amd/regrid.py: owner_map, from_sparse_cells): ptr int64 [ncells + 1],
         col int32 [nnz] (columns), w float64 [nnz]; a cell without terms reads `fill`.  Refused while gridded history entries exist."""
-        ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
-        col = np.ascontiguousarray(col, dtype=np.int32).reshape(-1)
-        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-        if ptr.size < 2 or col.size != w.size or ptr[-1] != col.size:
-            raise ValueError("ptr must be [ncells + 1] with ptr[-1] == len(col) == len(w)")
-        self._chk(self.lib.elmk_set_output_grid(self.ctx, ptr.size - 1, ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
-                                                w.ctypes.data_as(C.c_void_p), float(fill)), "set_output_grid")
-        self.output_ncells = ptr.size - 1
+        ncells, ptr, col, w = _csr_args(ptr, col, w, "ncells")
+        self._chk(self.lib.elmk_set_output_grid(self.ctx, ncells, _p(ptr), _p(col), _p(w), float(fill)), "set_output_grid")
+        self.output_ncells = ncells
 
     def clear_output_grid(self):
         """Forget the output map (refused while gridded history entries exist)."""
@@ -615,8 +610,7 @@ class ELMState:
         if self.output_ncells is None:
             raise L.ElmkError("download_gridded: no output grid (set_output_grid)")
         out = np.empty(self.output_ncells, dtype=np.float64)
-        self._chk(self.lib.elmk_download_gridded(self.ctx, self.fields[name][0], int(level), out.ctypes.data_as(C.c_void_p)),
-                  f"download_gridded({name})")
+        self._chk(self.lib.elmk_download_gridded(self.ctx, self.fields[name][0], int(level), _p(out)), f"download_gridded({name})")
         return out
 
     def gridded_history_add(self, tape, name, op):
@@ -661,9 +655,8 @@ class ELMState:
         if y is not None:
             y = np.ascontiguousarray(y, dtype=np.float64)
             assert y.shape == x.shape
-            yp = y.ctypes.data_as(C.c_void_p)
-        self._chk(self.lib.elmk_math_eval(self.ctx, MATH_FNS.index(fn), x.ctypes.data_as(C.c_void_p), yp,
-                                          out.ctypes.data_as(C.c_void_p), x.size), "math_eval")
+            yp = _p(y)
+        self._chk(self.lib.elmk_math_eval(self.ctx, MATH_FNS.index(fn), _p(x), yp, _p(out), x.size), "math_eval")
         return out
 
 
@@ -715,15 +708,14 @@ def canopy_fluxes_given(S, dt, forc_rho=None, forc_po2=None, forc_pco2=None):
     """L2-level canopy_fluxes: forcing-derived scalars handed in (test/test_CanFlux.cc) instead of derived by the wrapper."""
     a = [_opt(x) for x in (forc_rho, forc_po2, forc_pco2)]
     assert all(x is None or x.shape == (S.ncols,) for x in a)
-    S._chk(S.lib.elmk_canopy_fluxes_given(S.ctx, float(dt), *[None if x is None else x.ctypes.data_as(C.c_void_p) for x in a]),
-           "canopy_fluxes_given")
+    S._chk(S.lib.elmk_canopy_fluxes_given(S.ctx, float(dt), *[None if x is None else _p(x) for x in a]), "canopy_fluxes_given")
 
 
 def bareground_fluxes_given(S, forc_rho):
     """L2-level bareground_fluxes with ELM's own air density (test/test_BGFlux.cc)."""
     a = _opt(forc_rho)
     assert a.shape == (S.ncols,)
-    S._chk(S.lib.elmk_bareground_fluxes_given(S.ctx, a.ctypes.data_as(C.c_void_p)), "bareground_fluxes_given")
+    S._chk(S.lib.elmk_bareground_fluxes_given(S.ctx, _p(a)), "bareground_fluxes_given")
 
 
 def kokkos_soil_temperature(S, dt):
@@ -741,7 +733,7 @@ def get_forcing(S, wt1, wt2, qbot_is_rh=False):
     w1 = np.ascontiguousarray(wt1, dtype=np.float64)
     w2 = np.ascontiguousarray(wt2, dtype=np.float64)
     assert w1.shape == (8,) and w2.shape == (8,)
-    S._chk(S.lib.elmk_get_forcing(S.ctx, w1.ctypes.data_as(C.c_void_p), w2.ctypes.data_as(C.c_void_p), int(bool(qbot_is_rh))), "get_forcing")
+    S._chk(S.lib.elmk_get_forcing(S.ctx, _p(w1), _p(w2), int(bool(qbot_is_rh))), "get_forcing")
 
 
 def compute_phenology(S, wt1, wt2):
@@ -781,8 +773,7 @@ def kokkos_evaluate_conservation(S, dt, per_column=False):
     per-column values [ncols, 8]."""
     mms = np.zeros((8, 3))
     cols = np.zeros((8, S.ncols)) if per_column else None
-    S._chk(S.lib.elmk_evaluate_conservation(S.ctx, float(dt), mms.ctypes.data_as(C.c_void_p),
-                                            cols.ctypes.data_as(C.c_void_p) if per_column else None), "evaluate_conservation")
+    S._chk(S.lib.elmk_evaluate_conservation(S.ctx, float(dt), _p(mms), _p(cols) if per_column else None), "evaluate_conservation")
     return (mms, np.ascontiguousarray(cols.T)) if per_column else mms
 
 

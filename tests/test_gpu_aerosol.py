@@ -338,6 +338,8 @@ def test_refusals_enqueue_nothing(base, mapped, flagged):
         assert lib.elmk_aerosol_reserve(ctx, *a[:4]) == -1, what
         assert B.device_bytes == bytes1, what
         valid_run_still_gives_the_bits(what)
+    assert lib.elmk_aerosol_reserve(ctx, *reserve_cases["idx[0] = ncells"][:4]) == -1
+    assert lib.elmk_last_error(ctx) == b"elmk_aerosol_reserve: idx[0] outside [0, ncells)"
     dep_cases = {"month1 -1": (-1, 0, 0.5, 0.5), "month1 12": (12, 0, 0.5, 0.5), "month2 -1": (0, -1, 0.5, 0.5), "month2 12": (0, 12, 0.5, 0.5),
                  "wt1 nan": (0, 1, np.nan, 0.5), "wt2 inf": (0, 1, 0.5, np.inf), "wt1 -inf": (0, 1, -np.inf, 0.5)}
     for what, a in dep_cases.items():

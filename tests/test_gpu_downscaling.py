@@ -352,6 +352,7 @@ def test_refusals_enqueue_nothing(base):
     c2 = col.copy()
     c2[200] = c2[10]  # a column in two groups
     assert groups_rc(ptr, c2, w) == -1
+    assert A.lib.elmk_last_error(A.ctx) == b"elmk_set_downscaling_groups: a column in more than one group (or twice in one)"
     for v in (-0.1, np.nan, np.inf):
         w2 = w.copy()
         w2[5] = v

@@ -252,6 +252,9 @@ def test_refusals_enqueue_nothing(base):
     for what, i, ww, nc, npts in cases:
         assert set_refused(i, ww, nc, npts), what
         still_gives_the_bits(what)
+    assert cases[-1][0] == "w inf" and lib.elmk_last_error(ctx) == b"elmk_set_forcing_grid: non-finite weight"
+    assert cases[6][0] == "idx[1] -2" and set_refused(*cases[6][1:])
+    assert lib.elmk_last_error(ctx) == b"elmk_set_forcing_grid: idx outside [-1, ncells)"
     for what, f, lev in (("int field", B.fields["snl"][0], 0), ("level 2", B.fields["atm_tbot"][0], 2), ("level -1", B.fields["atm_tbot"][0], -1),
                          ("unknown field", 100000, 0)):
         assert lib.elmk_upload_gridded(ctx, f, lev, cells["atm_tbot"][0].ctypes.data_as(C.c_void_p)) == -1, what

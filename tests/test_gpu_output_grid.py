@@ -281,6 +281,9 @@ def test_refusals_enqueue_nothing_and_leave_the_context_working():
     for k, (nc, p, c, ww) in enumerate(bad):
         assert _set(D, nc, p, c, ww) == -1, k
         assert same(D.download_gridded("t_grnd"), want), k  # the map in place is untouched
+    assert np.isinf(bad[-1][3][2]) and D.lib.elmk_last_error(D.ctx) == b"elmk_set_output_grid: non-finite weight"
+    assert list(bad[4][1]) == [0, 2, 1, 3, 5] and _set(D, *bad[4]) == -1
+    assert D.lib.elmk_last_error(D.ctx) == b"elmk_set_output_grid: ptr decreasing"
     big = np.array([0, (1 << 31)], np.int64)  # nnz outside 0 .. 2^31-1 (refused before col / w are read)
     assert D.lib.elmk_set_output_grid(D.ctx, 1, big.ctypes.data_as(C.c_void_p), None, None, 0.0) == -1
     nf = D.lib.elmk_num_fields()
@@ -330,6 +333,45 @@ def test_device_bytes_account_for_the_map_and_the_accumulators():
     assert D.device_bytes - b0 == al(501 * 8) + al(int(ptr[500]) * 4) + al(int(ptr[500]) * 8)
     D.clear_output_grid()
     assert D.device_bytes == b0
+    D.close()
+    # every counted owner at once - one full 64-column tile and a tail, 5-cell grids: the total is the sum of the layouts include/elmk.h
+    # documents (the run's from elmk_run_reserve's list: series, two tables of 216-byte rows, the cursor's 256 bytes, two rings of
+    # 24 doubles, a flag word and a first column per row), and every clear returns exactly its share
+    n, nc, slots, msteps = 70, 5, 3, 4
+    D = st.ELMState(n)
+    ld, nlev, rows = D.level_stride, _levels(D, "t_soisno"), 2 * msteps
+    assert ld == 128
+    D.set_column_geography(np.zeros(n), np.zeros(n))  # (not counted)
+    b0 = D.device_bytes
+    idx = np.stack([(np.arange(n) + k) % nc for k in range(3)])  # npts 3: stored as 4 rows
+    ptr, col, w = np.arange(0, n + 1, n // nc), np.arange(n), np.ones(n)
+    D.set_forcing_grid(idx, np.full((3, n), 1.0 / 3.0), nc)
+    D.run_reserve(slots, msteps)  # (cell records)
+    D.aerosol_reserve(nc, idx[:1], np.ones((1, n)))
+    D.set_output_grid(ptr, col, w, FILL)
+    D.gridded_history_add(0, "t_soisno", "avg")
+    D.set_shortwave_mode("coszen", 3600.0)
+    D.series_record_times(0, [1.0, 1.5, 2.0])
+    D.set_column_elevation(np.zeros(n), np.zeros(n))
+    D.set_downscaling_groups(ptr, col, w)
+    D.accum_add("t_ref2m", "runmean", 4)
+    D.accum_add("t_soisno", "timeavg", 10)
+    share = {"grid": al(4 * ld * 4) + al(4 * ld * 8) + al(nc * 8),
+             "run": al(7 * slots * nc * 8) + al(4 * 12 * ld * 8) + al(rows * 216) + 256 + al(rows * 24 * 8) + al(rows * 4) + al(rows * 8),
+             "aerosol": al(11 * 12 * nc * 8) + al(ld * 4) + al(ld * 8),
+             "ogrid": al((nc + 1) * 8) + al(n * 4) + al(n * 8), "gridded": al(nlev * 64 * 8),
+             "czf": ld * 8, "times": slots * 56, "topo": 2 * ld * 8,
+             "groups": al((nc + 1) * 8) + al(n * 4) + al(n * 8) + al(nc * 8) + al(ld * 8),
+             "accum": 16 * 21 * 48 + 256 + ld * 8 * (1 + nlev)}
+    held = b0 + sum(share.values())
+    assert D.device_bytes == held
+    for clear, back in ((D.accum_clear, ("accum",)), (D.history_clear, ("gridded",)), (D.clear_output_grid, ("ogrid",)),
+                        (D.clear_downscaling_groups, ("groups",)), (D.aerosol_clear, ("aerosol",)),
+                        (D.clear_forcing_grid, ("grid", "run", "times"))):  # (the reservation and its record times go with the grid)
+        clear()
+        held -= sum(share[k] for k in back)
+        assert D.device_bytes == held, back
+    assert held == b0 + share["czf"] + share["topo"]  # nothing frees these two before the context goes
     D.close()
 
 
