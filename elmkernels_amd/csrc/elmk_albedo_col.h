@@ -14,7 +14,18 @@ constexpr double SN_MIN_SNW = 1.0e-30;  // snow_snicar.h:27
 constexpr double SA_MPE = 1.e-06;       // surface_albedo.h:56
 constexpr double SA_EXTKN = 0.30;       // surface_albedo.h:57
 
-// per-column body of stage 1; returns the number of snow layers if the column must go through SNICAR, else 0
+// The SNICAR class of a column, one source for stage 1's queues and for k_alb_tile's selection (k_albedo_snicar.hip): a column
+// goes through SNICAR if it is sunlit and holds snow, with snl layers or - snl == 0, a pack too thin for a layer - with one
+// fictitious fresh-snow layer (flg_nosnl, snow_snicar_impl.hh:42-48).
+__device__ __forceinline__ bool alb_sunlit(const double coszen) { return coszen > 0.0; }
+// ... of a sunlit column: its number of SNICAR layers, 0 = no snow radiative transfer
+__device__ __forceinline__ int alb_snicar_layers(const double h2osno, const int snl)
+{
+  if (h2osno > SN_MIN_SNW) return snl == 0 ? 1 : snl;
+  return 0;
+}
+
+// per-column body of stage 1; returns the number of snow layers if the column must go through SNICAR, else 0 (-1: no sun)
 __device__ __forceinline__ int alb_main_column(const DevState* __restrict__ S, const int64_t c, const int64_t ld, const Land& L)
 {
   const double coszen = S->coszen[c];
@@ -25,7 +36,7 @@ __device__ __forceinline__ int alb_main_column(const DevState* __restrict__ S, c
   S->tlai_z[c] = elai;
   // (laisum/saisum of a single layer equal elai/esai exactly: the reference's consistency throw cannot fire)
 
-  if (!(coszen > 0.0)) return -1;  // night column: stage 3 writes the init_timestep defaults
+  if (!alb_sunlit(coszen)) return -1;  // night column: stage 3 writes the init_timestep defaults
 
   // =========================== sunlit column ===========================
   const double h2osno = S->h2osno[c];
@@ -74,8 +85,7 @@ __device__ __forceinline__ int alb_main_column(const DevState* __restrict__ S, c
   LV(albsod, 1) = albsod[1];
   LV(albsoi, 0) = albsoi[0];
   LV(albsoi, 1) = albsoi[1];
-  if (h2osno > SN_MIN_SNW) return snl == 0 ? 1 : snl;  // snl == 0: one fictitious fresh-snow layer (flg_nosnl, :42-48)
-  return 0;
+  return alb_snicar_layers(h2osno, snl);
 }
 
 }  // namespace elmk

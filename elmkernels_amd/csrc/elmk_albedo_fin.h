@@ -2,7 +2,7 @@
 // flux_absorption_factor :171-211, two_stream_solver :323-687 with nlevcan == 1; for a column without sun the values
 // surface_albedo::init_timestep leaves, :90-151, and snow_albedo_radiation_factor's "no sun" branch, snow_snicar_impl.hh:758-765),
 // in three pieces that are ONE piece of source for two users:
-//   * k_alb_final (k_albedo_snicar.hip) calls them in the reference's order and every output goes to the state;
+//   * k_alb_final and k_alb_tile (k_albedo_snicar.hip) call them in the reference's order and every output goes to the state;
 //   * the fused step's k_fz_stream (k_canopy_fluxes.hip) calls them around surface_radiation's body and ALSO keeps the outputs
 //     in registers (AlbFwd), so kokkos_surface_radiation reads none of the 56 doubles back that this stage has just written.
 // Every output is STORED BY ALL LANES TOGETHER: a wave that holds sunlit and dark columns would otherwise write every 128-byte
@@ -268,8 +268,11 @@ struct AlbIn {
   double coszen, elai, esai, frac_sno, vcmaxcintsun, vcmaxcintsha;
   double albsod[2], albsoi[2], sd_alb[2], si_alb[2];
 };
+// snow(k): product k of the column's 28 SNICAR products (pass x {alb[2], fabs_[6][2]}: the rows of alb_snow), read only where the
+// column went through SNICAR.  k_alb_final and k_fz_stream read alb_snow (alb_snow_reader); k_alb_tile reads LDS for its own columns.
+template <class FS>
 __device__ __forceinline__ AlbIn alb_final_inputs(const DevState* __restrict__ S, const int64_t c, const int64_t ld, const double frac_sno_in,
-                                                  const double h2osno_in)
+                                                  const double h2osno_in, const FS snow)
 {
   AlbIn x;
   x.coszen = S->coszen[c];
@@ -281,7 +284,7 @@ __device__ __forceinline__ AlbIn alb_final_inputs(const DevState* __restrict__ S
   } else {
     x.vcmaxcintsha = 0.0;
   }
-  x.day = x.coszen > 0.0;  // nothing after init_timestep runs without sun except snow_albedo_radiation_factor's "no sun" branch
+  x.day = alb_sunlit(x.coszen);  // nothing after init_timestep runs without sun except snow_albedo_radiation_factor's "no sun" branch
   x.snicar = false;
   x.esai = 0.0;
   x.frac_sno = 0.0;
@@ -295,13 +298,11 @@ __device__ __forceinline__ AlbIn alb_final_inputs(const DevState* __restrict__ S
     x.albsoi[0] = LV(albsoi, 0);
     x.albsoi[1] = LV(albsoi, 1);
     if (h2osno_in > SN_MIN_SNW) {
-      // the SNICAR products are read once, by column: nontemporal loads (k_alb_final -5 %, profiles/r04_scratch_nt_ab.txt)
-      const gptr<const double> o = S->alb_snow + c;
       x.snicar = true;
-      x.sd_alb[0] = __builtin_nontemporal_load(o);
-      x.sd_alb[1] = __builtin_nontemporal_load(o + ld);
-      x.si_alb[0] = __builtin_nontemporal_load(o + (int64_t)14 * ld);
-      x.si_alb[1] = __builtin_nontemporal_load(o + (int64_t)15 * ld);
+      x.sd_alb[0] = snow(0);
+      x.sd_alb[1] = snow(1);
+      x.si_alb[0] = snow(14);
+      x.si_alb[1] = snow(15);
     } else if (h2osno_in < SN_MIN_SNW && h2osno_in > 0.0) {
       // no snow radiative transfer: snow_albedo_radiation_factor's remaining branches (snow_snicar_impl.hh:758-765)
       x.sd_alb[0] = x.si_alb[0] = x.albsoi[0];
@@ -310,20 +311,20 @@ __device__ __forceinline__ AlbIn alb_final_inputs(const DevState* __restrict__ S
   }
   return x;
 }
-// flux_absorption_factor for all six levels: the SNICAR factors come from alb_snow (zeros for a column that did not go through
+// flux_absorption_factor for all six levels: the SNICAR factors come from snow(k) (zeros for a column that did not go through
 // SNICAR), the four arrays go to the state and to flx[i] = {dv, dn, iv, in}
+template <class FS>
 __device__ __forceinline__ void alb_flux_abs_all(const DevState* __restrict__ S, const int64_t c, const int64_t ld, const Land& L,
-                                                 const AlbIn& x, double (&flx)[6][4])
+                                                 const AlbIn& x, double (&flx)[6][4], const FS snow)
 {
-  const gptr<const double> o = S->alb_snow + c;  // (nontemporal loads: see alb_final_inputs)
 #pragma unroll
   for (int i = 0; i < 6; i++) {
     double sdf[2] = {0.0, 0.0}, sif[2] = {0.0, 0.0};
     if (x.snicar) {
-      sdf[0] = __builtin_nontemporal_load(o + (int64_t)(2 + 2 * i) * ld);
-      sdf[1] = __builtin_nontemporal_load(o + (int64_t)(3 + 2 * i) * ld);
-      sif[0] = __builtin_nontemporal_load(o + (int64_t)(16 + 2 * i) * ld);
-      sif[1] = __builtin_nontemporal_load(o + (int64_t)(17 + 2 * i) * ld);
+      sdf[0] = snow(2 + 2 * i);
+      sdf[1] = snow(3 + 2 * i);
+      sif[0] = snow(16 + 2 * i);
+      sif[1] = snow(17 + 2 * i);
     }
     alb_flux_abs_level(L, x.day, x.frac_sno, x.albsod, x.albsoi, x.sd_alb, x.si_alb, sdf, sif, flx[i][0], flx[i][1], flx[i][2], flx[i][3]);
     LV(flx_absdv, i) = flx[i][0];
@@ -331,6 +332,25 @@ __device__ __forceinline__ void alb_flux_abs_all(const DevState* __restrict__ S,
     LV(flx_absiv, i) = flx[i][2];
     LV(flx_absin, i) = flx[i][3];
   }
+}
+
+// ... with the products where k_alb_snicar<NL> left them, in the scratch array alb_snow.  They are read once, by column:
+// nontemporal loads (k_alb_final -5 %, profiles/r04_scratch_nt_ab.txt)
+struct alb_snow_reader {
+  gptr<const double> o;
+  int64_t ld;
+  __device__ __forceinline__ alb_snow_reader(const DevState* __restrict__ S, const int64_t c, const int64_t ld_) : o(S->alb_snow + c), ld(ld_) {}
+  __device__ __forceinline__ double operator()(const int k) const { return __builtin_nontemporal_load(o + (int64_t)k * ld); }
+};
+__device__ __forceinline__ AlbIn alb_final_inputs(const DevState* __restrict__ S, const int64_t c, const int64_t ld, const double frac_sno_in,
+                                                  const double h2osno_in)
+{
+  return alb_final_inputs(S, c, ld, frac_sno_in, h2osno_in, alb_snow_reader(S, c, ld));
+}
+__device__ __forceinline__ void alb_flux_abs_all(const DevState* __restrict__ S, const int64_t c, const int64_t ld, const Land& L,
+                                                 const AlbIn& x, double (&flx)[6][4])
+{
+  alb_flux_abs_all(S, c, ld, L, x, flx, alb_snow_reader(S, c, ld));
 }
 
 }  // namespace elmk

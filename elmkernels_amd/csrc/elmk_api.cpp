@@ -630,6 +630,14 @@ int elmk_set_graph(elmk_ctx* ctx, int on)
 int elmk_set_option(elmk_ctx* ctx, int option, int value)
 {
   if (int rc = enter(ctx)) return rc;
+  if (option == ELMK_OPT_ALB_STAGED) {
+    const bool want = value != 0;
+    if (want != ctx->side.alb_staged) {
+      if (int rc = drop_graphs(ctx)) return rc;  // (a captured graph holds the kernels of the structure it was captured in)
+      ctx->side.alb_staged = want;
+    }
+    return ELMK_OK;
+  }
   if (option != ELMK_OPT_CF_HALF_WORKGROUPS) return invalid(ctx, "elmk_set_option: unknown option");
   int cus = 0;
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->dev));

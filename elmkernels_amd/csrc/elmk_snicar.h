@@ -1,6 +1,6 @@
 // elmk_snicar.h - SNICAR for the sunlit snow-covered columns (snow_snicar_impl.hh): one (pass, band) solve per lane, the band
-// combination across lanes, and the work of one workgroup of the queue-driven kernel.  Shared by k_albedo_snicar.hip (the
-// kernels k_alb_snicar<NL>) and k_canopy_fluxes.hip (the fused step's k_fz_snicar_pre, which hosts streaming work beside it).
+// combination across lanes, the walk over a queue of columns and the work of one workgroup of the queue-driven kernel.  Shared by
+// k_albedo_snicar.hip (the kernels k_alb_snicar<NL>; k_alb_tile, whose queue and products live in LDS) and k_canopy_fluxes.hip (the fused step's k_fz_snicar_pre, which hosts streaming work beside it).
 #pragma once
 #include "elmk_dev.h"
 #include "elmk_albedo_col.h"
@@ -330,28 +330,23 @@ __device__ __forceinline__ void snicar_combine(const int g0, const int pass, con
       [&](const int b, const int i) { return __shfl(fl[i], g0 + b, 64); }, out);
 }
 
-// the work of one workgroup of k_alb_snicar<NL>: workgroup `block` of `nblocks` (a kernel that hosts other work beside SNICAR
-// numbers its SNICAR workgroups itself: k_fz_snicar_pre, k_canopy_fluxes.hip)
-template <int NL>
-__device__ __forceinline__ void snicar_workgroup(const DevState* __restrict__ S, const uint32_t block, const uint32_t nblocks)
+// The walk over a queue of `count` columns with NL layers: wave `wave0` of `nwaves` takes queue positions 6 w .. 6 w + 5 for
+// w = wave0, wave0 + nwaves, ..., ten lanes per column.  column_at(q): the column at queue position q; store(c, pass, out): where
+// the SnowOut of one pass of column c goes (called by the band-0 lane of the pass).  Error bits go to err_flags.
+template <int NL, class FC, class FO>
+__device__ __forceinline__ void snicar_queue(const DevState* __restrict__ S, const uint32_t count, const uint32_t wave0,
+                                             const uint32_t nwaves, const FC column_at, const FO store)
 {
-  uint32_t count = ELMK_LIST_COUNT(S, LIST_ALB_0 + NL);
-  if ((int64_t)count > S->ld) count = (uint32_t)S->ld;  // (a list never holds more than every column: block_classify_append)
-  // nothing in the queue for this workgroup (the whole launch, when no column has NL layers): leave before the table copy
-  if ((uint64_t)block * (blockDim.x >> 6) * 6u >= count) return;
-  elmk_math_lds_init<false>();
   const int64_t ld = S->ld;
-  const gptr<const int32_t> list = S->lists + (int64_t)(LIST_ALB_0 + NL) * ld;
   constexpr int snl_top = NLEVSNO - NL;
   const int lane = threadIdx.x & 63;
   const int slot = lane / 10, task = lane - slot * 10;  // slot 6 (lanes 60..63): no column
   const int pass = task / 5, bnd = task - pass * 5;
   const int g0 = lane - bnd;  // first lane of this (column, pass) group
-  const uint32_t nwaves = nblocks * (blockDim.x >> 6);
-  for (uint32_t w = block * (blockDim.x >> 6) + (threadIdx.x >> 6); (uint64_t)w * 6u < count; w += nwaves) {
+  for (uint32_t w = wave0; (uint64_t)w * 6u < count; w += nwaves) {
     const uint32_t q = w * 6u + (uint32_t)slot;
     const bool valid = slot < 6 && q < count;
-    const int64_t c = list[valid ? q : w * 6u];  // lanes without a column shadow the wave's first one and store nothing
+    const int64_t c = column_at(valid ? q : w * 6u);  // lanes without a column shadow the wave's first one and store nothing
     uint32_t err = 0;
     const double mu_not = dmax(S->coszen[c], 0.01);
     const int snl = S->snl[c];
@@ -363,19 +358,37 @@ __device__ __forceinline__ void snicar_workgroup(const DevState* __restrict__ S,
     rds_top = rds_top < SN_RDS_MIN_TBL ? SN_RDS_MIN_TBL : (rds_top > SN_RDS_MAX_TBL ? SN_RDS_MAX_TBL : rds_top);
     SnowOut out;
     snicar_combine<NL>(g0, pass, mu_not, rds_top, albedo, fl, out);
-    if (valid && bnd == 0) {
-      // plain stores: with the nontemporal hint the fused step took 1-3 % longer (profiles/r04_scratch_nt_ab.txt)
-      const gptr<double> o = S->alb_snow + (int64_t)(pass * 14) * ld + c;
-      o[0] = out.alb[0];
-      o[ld] = out.alb[1];
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        o[(int64_t)(2 + 2 * i) * ld] = out.fabs_[i][0];
-        o[(int64_t)(3 + 2 * i) * ld] = out.fabs_[i][1];
-      }
-    }
+    if (valid && bnd == 0) store(c, pass, out);
     if (valid && err) atomicOr(ELMK_GENERIC(&S->err_flags[c]), err);
   }
+}
+
+// the work of one workgroup of k_alb_snicar<NL>: workgroup `block` of `nblocks` (a kernel that hosts other work beside SNICAR
+// numbers its SNICAR workgroups itself: k_fz_snicar_pre, k_canopy_fluxes.hip).  The queue is work list LIST_ALB_0 + NL and the
+// products go to the scratch array alb_snow, by column.
+template <int NL>
+__device__ __forceinline__ void snicar_workgroup(const DevState* __restrict__ S, const uint32_t block, const uint32_t nblocks)
+{
+  uint32_t count = ELMK_LIST_COUNT(S, LIST_ALB_0 + NL);
+  if ((int64_t)count > S->ld) count = (uint32_t)S->ld;  // (a list never holds more than every column: block_classify_append)
+  // nothing in the queue for this workgroup (the whole launch, when no column has NL layers): leave before the table copy
+  if ((uint64_t)block * (blockDim.x >> 6) * 6u >= count) return;
+  elmk_math_lds_init<false>();
+  const int64_t ld = S->ld;
+  const gptr<const int32_t> list = S->lists + (int64_t)(LIST_ALB_0 + NL) * ld;
+  snicar_queue<NL>(
+      S, count, block * (blockDim.x >> 6) + (threadIdx.x >> 6), nblocks * (blockDim.x >> 6), [&](const uint32_t q) { return (int64_t)list[q]; },
+      [&](const int64_t c, const int pass, const SnowOut& out) {
+        // plain stores: with the nontemporal hint the fused step took 1-3 % longer (profiles/r04_scratch_nt_ab.txt)
+        const gptr<double> o = S->alb_snow + (int64_t)(pass * 14) * ld + c;
+        o[0] = out.alb[0];
+        o[ld] = out.alb[1];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+          o[(int64_t)(2 + 2 * i) * ld] = out.fabs_[i][0];
+          o[(int64_t)(3 + 2 * i) * ld] = out.fabs_[i][1];
+        }
+      });
 }
 
 // Measured and dropped in round 3 (profiles/r03_snicar_band_per_wave_ab.txt): one BAND per wave for the packs of two or more

@@ -20,6 +20,7 @@ from .shortwave import SW_COSZEN, SW_MODES, SW_REFERENCE  # noqa: F401
 DTYPES = {0: np.float64, 1: np.int32, 2: np.uint8, 3: np.uint32}
 LAYOUT_COL_MAJOR, LAYOUT_SOA = 0, 1
 OPT_CF_HALF_WORKGROUPS = 1  # elmk_set_option
+OPT_ALB_STAGED = 2  # elmk_set_option: albedo_snicar as three stages instead of k_alb_tile
 HIST_AVG, HIST_SUM, HIST_MAX, HIST_MIN, HIST_INST = range(5)  # elmk_history_add
 HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, "inst": HIST_INST}
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
@@ -314,7 +315,8 @@ class ELMState:
         return ms.value
 
     def set_option(self, option, value):
-        """Launch options (elmk_set_option); OPT_CF_HALF_WORKGROUPS: the leaf-temperature iteration in 256-thread workgroups, one per CU."""
+        """Launch options (elmk_set_option); OPT_CF_HALF_WORKGROUPS: the leaf-temperature iteration in 256-thread workgroups, one per CU;
+        OPT_ALB_STAGED: albedo_snicar's one-layer SNICAR and final stage as launches of their own instead of k_alb_tile."""
         self._chk(self.lib.elmk_set_option(self.ctx, int(option), int(value)), "set_option")
 
     def set_graph(self, on=True):

@@ -177,8 +177,11 @@ int elmk_set_graph(elmk_ctx *ctx, int on);
  *     workgroups, one per compute unit - half the registers and 68 KB of a CU's LDS stay free, so the kernels of ANOTHER context's
  *     stream are resident on the same CUs and use the memory pipeline this fp64-bound kernel leaves idle.  For a driver that steps two
  *     (or more) blocks of columns as separate contexts on separate streams; on its
- *     own the kernel is 1.5 x slower in this shape, which is why it is an option. */
-enum { ELMK_OPT_CF_HALF_WORKGROUPS = 1 };
+ *     own the kernel is 1.5 x slower in this shape, which is why it is an option.
+ *   ELMK_OPT_ALB_STAGED  value != 0: kokkos_albedo_snicar (and elmk_timestep7's) runs SNICAR of the one-layer snow packs and the final
+ *     stage as launches of their own (k_alb_snicar<1>, k_alb_final) that meet through device memory, instead of k_alb_tile, which does
+ *     both for a tile of 256 columns in one workgroup and is the default.  The structure an A/B or a test compares k_alb_tile with. */
+enum { ELMK_OPT_CF_HALF_WORKGROUPS = 1, ELMK_OPT_ALB_STAGED = 2 };
 int elmk_set_option(elmk_ctx *ctx, int option, int value);
 int64_t elmk_ncols(const elmk_ctx *ctx);
 int64_t elmk_level_stride(const elmk_ctx *ctx); /* elements between consecutive levels of a device field */
