@@ -117,6 +117,11 @@ SIGNATURES = {
     "elmk_aerosol_upload": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "elmk_aerosol_deposition": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double]),
     "elmk_aerosol_clear": (C.c_int, [_P]),
+    "elmk_active_layer_enable": (C.c_int, [_P]),
+    "elmk_active_layer_init": (C.c_int, [_P, _P, _P]),
+    "elmk_active_layer_update": (C.c_int, [_P, C.c_int]),
+    "elmk_active_layer_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_active_layer_clear": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

@@ -236,6 +236,9 @@ struct elmk_ctx {
   std::vector<AccumRow> accum_rows;
   DevBuf<char> accum_table;
   uint64_t accum_version = 0;  // counts elmk_accum_add / _clear, as hist_version
+  // active layer thickness (elmk_active_layer_*): the rows alt, altmax, altmax_lastyear [3][ld] in fp64, held exactly while the feature
+  // is enabled
+  DevBuf<double> alt_rows;
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
@@ -663,7 +666,7 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
   if (!ctx) return -1;
   size_t n = ctx->arena.bytes() + ctx->staging.bytes() + ctx->scratch.bytes() + ctx->snicar.bytes() + ctx->snowage.bytes() + ctx->d.bytes() +
              ctx->run.mem.bytes() + ctx->grid.mem.bytes() + ctx->ogrid.mem.bytes() + ctx->sw.czf.bytes() + ctx->run.rec.bytes() +
-             ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes();
+             ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes() + ctx->alt_rows.bytes();
   // the cell rows of gridded history entries (not the column rows) and the accumulators' values: whole rows of ld or cld doubles,
   // both multiples of 64, so every size is a multiple of 256 already
   for (const elmk_ctx::HistEntry& e : ctx->hist) n += e.cells ? e.acc.bytes() : 0;
@@ -1405,6 +1408,90 @@ int elmk_accum_clear(elmk_ctx* ctx)
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------
+// active layer thickness (k_active_layer.hip; include/elmk.h "active layer thickness")
+// ---------------------------------------------------------------------------------------------------
+namespace {
+ActiveLayerArgs alt_args(const elmk_ctx* ctx)
+{
+  return ActiveLayerArgs{ctx->fptr[ELMK_FIELD_t_soisno], ctx->fptr[ELMK_FIELD_zsoi], (int32_t*)ctx->fptr[ELMK_FIELD_altmax_indx],
+                         (int32_t*)ctx->fptr[ELMK_FIELD_altmax_lastyear_indx], ctx->alt_rows,
+                         ctx->geo + (size_t)ELMK_GEO_SIN_LAT * (size_t)ctx->ld, ctx->ld, ctx->ncols};
+}
+static_assert(ELMK_ALT_ALTMAX_LASTYEAR == 2, "three rows");
+constexpr int ALT_NROWS = 3;
+}  // namespace
+
+extern "C" {
+
+int elmk_active_layer_enable(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (ctx->alt_rows) return invalid(ctx, "elmk_active_layer_enable: already enabled");
+  if (int rc = refuse_capture(ctx, "elmk_active_layer_enable: the stream is being captured")) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the stages of its flags' moment)
+  const size_t bytes = (size_t)ALT_NROWS * (size_t)ctx->ld * sizeof(double);
+  if (hip_fail(ctx, ctx->alt_rows.alloc(bytes), "hipMalloc(active layer rows)")) return ELMK_E_NOMEM;
+  if (hip_fail(ctx, hipMemsetAsync(ctx->alt_rows, 0, bytes, ctx->stream), "hipMemset(active layer rows)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)ctx->alt_rows.reset();
+    return ELMK_E_HIP;
+  }
+  return ELMK_OK;
+}
+
+int elmk_active_layer_init(elmk_ctx* ctx, const double* altmax, const double* altmax_lastyear)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->alt_rows) return invalid(ctx, "elmk_active_layer_init: not enabled (elmk_active_layer_enable)");
+  if (int rc = refuse_capture(ctx, "elmk_active_layer_init: the stream is being captured")) return rc;
+  const size_t ld = (size_t)ctx->ld, n = (size_t)ctx->ncols;
+  HIPCHK(hipMemsetAsync(ctx->alt_rows, 0, ctx->alt_rows.bytes(), ctx->stream));
+  if (altmax && n) HIPCHK(hipMemcpyAsync(ctx->alt_rows + ELMK_ALT_ALTMAX * ld, altmax, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (altmax_lastyear && n)
+    HIPCHK(hipMemcpyAsync(ctx->alt_rows + ELMK_ALT_ALTMAX_LASTYEAR * ld, altmax_lastyear, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+int elmk_active_layer_update(elmk_ctx* ctx, int rollover)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->alt_rows) return invalid(ctx, "elmk_active_layer_update: not enabled (elmk_active_layer_enable)");
+  if (!ctx->geo_set) return invalid(ctx, "elmk_active_layer_update: no column geography (elmk_set_column_geography)");
+  if (rollover & ~(ELMK_ALT_ROLL_NORTH | ELMK_ALT_ROLL_SOUTH)) return invalid(ctx, "elmk_active_layer_update: unknown rollover bits");
+  launch_active_layer(alt_args(ctx), rollover, ctx->stream);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_active_layer_read(elmk_ctx* ctx, int which, double* host, int64_t col0, int64_t n)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->alt_rows) return invalid(ctx, "elmk_active_layer_read: not enabled (elmk_active_layer_enable)");
+  if (which < ELMK_ALT_ALT || which > ELMK_ALT_ALTMAX_LASTYEAR) return invalid(ctx, "elmk_active_layer_read: unknown row");
+  if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols) return invalid(ctx, "elmk_active_layer_read: bad column range");
+  if (int rc = refuse_capture(ctx, "elmk_active_layer_read: the stream is being captured")) return rc;
+  if (n > 0)
+    HIPCHK(hipMemcpyAsync(host, ctx->alt_rows + (size_t)which * (size_t)ctx->ld + (size_t)col0, (size_t)n * 8, hipMemcpyDeviceToHost,
+                          ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+int elmk_active_layer_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_active_layer_clear: the stream is being captured")) return rc;
+  if (!ctx->alt_rows) return ELMK_OK;
+  if (int rc = quiesce(ctx, false)) return rc;
+  HIPCHK(ctx->alt_rows.reset());
+  return ELMK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
 // physics wrappers: one launch each, same order/arguments as driver/kokkos
 // ---------------------------------------------------------------------------------------------------
 
@@ -1838,6 +1925,10 @@ void run_flag_reduce(elmk_ctx* ctx, double)
   const elmk_ctx::Run& R = ctx->run;
   launch_flag_reduce_run((const uint32_t*)ctx->fptr[ELMK_FIELD_err_flags], ctx->ncols, R.flag_or, R.flag_first, R.cursor, ctx->stream);
 }
+void run_active_layer(elmk_ctx* ctx, double)
+{
+  if (ctx->run.flags & ELMK_RUN_ALT) launch_active_layer_run(alt_args(ctx), ctx->run.table, ctx->run.cursor, ctx->stream);
+}
 void run_accum(elmk_ctx* ctx, double)
 {
   if (ctx->run.flags & ELMK_RUN_ACCUM) accum_update_launch(ctx);
@@ -1850,12 +1941,13 @@ void run_next(elmk_ctx* ctx, double) { launch_run_next(ctx->run.cursor, ctx->str
 
 // one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
 // forcing, aerosol deposition (ELMK_RUN_AEROSOL: where the reference's hook sits, init_timestep_kokkos.cc:48-49), init_timestep,
-// advance_physics' stages, conservation -> ring row, flag summary -> ring row, accumulated fields, history, next row
+// advance_physics' stages, conservation -> ring row, flag summary -> ring row, active layer thickness (ELMK_RUN_ALT), accumulated fields,
+// history, next row
 constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},   {run_forcing, nullptr}, {run_aerosol, nullptr},
                               {run_init_timestep, nullptr},
                               ADVANCE[0], ADVANCE[1], ADVANCE[2], ADVANCE[3], ADVANCE[4], ADVANCE[5], ADVANCE[6], ADVANCE[7],
-                              {run_conservation, nullptr},   {run_flag_reduce, nullptr}, {run_accum, nullptr},   {run_history, nullptr},
-                              {run_next, nullptr}};
+                              {run_conservation, nullptr},   {run_flag_reduce, nullptr}, {run_active_layer, nullptr},
+                              {run_accum, nullptr},          {run_history, nullptr},     {run_next, nullptr}};
 static_assert(sizeof ADVANCE / sizeof ADVANCE[0] == 8, "RUN_STEP holds every stage of ADVANCE");
 }  // namespace
 
@@ -1943,9 +2035,12 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   if (!ctx->snowage_set) return invalid(ctx, "elmk_run: the snow-age tables are not set (elmk_set_snow_age_tables)");
   if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
   if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
-  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL)) return invalid(ctx, "elmk_run: unknown flags");
+  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL | ELMK_RUN_ALT))
+    return invalid(ctx, "elmk_run: unknown flags");
   if ((flags & ELMK_RUN_AEROSOL) && !ctx->aer.mem) return invalid(ctx, "elmk_run: ELMK_RUN_AEROSOL without an aerosol series (elmk_aerosol_reserve)");
   if ((flags & ELMK_RUN_ACCUM) && ctx->accum.empty()) return invalid(ctx, "elmk_run: ELMK_RUN_ACCUM without an accumulator entry (elmk_accum_add)");
+  if ((flags & ELMK_RUN_ALT) && !ctx->alt_rows)
+    return invalid(ctx, "elmk_run: ELMK_RUN_ALT without the active layer thickness enabled (elmk_active_layer_enable)");
   const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   int lo = R.slots, hi = -1;
   unsigned months = 0;
@@ -1981,7 +2076,11 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
     r.forc_slot = p.forc_slot;
     r.month1 = p.month1;
     r.month2 = p.month2;
-    r.pad = 0;
+    // the annual rollover of the active layer thickness: the step that starts at 00:00 of 1 January (north) / 1 July (south) of the
+    // no-leap calendar, whose end-of-step date satisfies ELM's mon, day == 1 && sec / dtime == 1
+    r.pad = !(flags & ELMK_RUN_ALT) ? 0
+                                    : (p.doy == 0 && p.decday == 1.0 ? ELMK_ALT_ROLL_NORTH : 0) |
+                                          (p.doy == 181 && p.decday == 182.0 ? ELMK_ALT_ROLL_SOUTH : 0);
   }
   const int row0 = buf * R.max_steps;
   HIPCHK(hipMemcpyAsync(R.table + row0, rows, (size_t)nsteps * sizeof(RunRow), hipMemcpyHostToDevice, ctx->stream));
@@ -2694,6 +2793,7 @@ struct RstLayout {
   std::vector<elmk_restart_accum> acc;  // version 2: one per accumulator entry (nsteps filled in by the save)
   std::vector<elmk_restart_section> sec;
   std::vector<RstSrc> src;
+  bool alt = false;  // version 3: the active layer thickness is enabled (the accumulator-count word is present, three ALT sections last)
   size_t header_bytes = 0, total = 0;
 };
 
@@ -2720,8 +2820,13 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
     L.sec.push_back(elmk_restart_section{ELMK_RESTART_ACCUM, (int32_t)i, e.nlev, ELMK_F64, ctx->ncols, 0, 0});
     L.src.push_back(RstSrc{(char*)(double*)e.val, ctx->ld, ELMK_F64, gcol0, false});
   }
-  // version 2 (with accumulator entries): their number in the word after the header, their table after the history entries
-  L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.acc.empty() ? 0 : 8 + L.acc.size() * sizeof(elmk_restart_accum)) +
+  L.alt = (bool)ctx->alt_rows;
+  for (int which = 0; L.alt && which < ALT_NROWS; which++) {
+    L.sec.push_back(elmk_restart_section{ELMK_RESTART_ALT, which, 1, ELMK_F64, ctx->ncols, 0, 0});
+    L.src.push_back(RstSrc{(char*)(ctx->alt_rows + (size_t)which * (size_t)ctx->ld), ctx->ld, ELMK_F64, gcol0, false});
+  }
+  // version 2 (with accumulator entries) and 3: their number in the word after the header, their table after the history entries
+  L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.acc.empty() && !L.alt ? 0 : 8 + L.acc.size() * sizeof(elmk_restart_accum)) +
                                 L.ent.size() * sizeof(elmk_restart_entry) + L.sec.size() * sizeof(elmk_restart_section),
                             RST_ALIGN);
   size_t off = L.header_bytes;
@@ -2912,7 +3017,7 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
   }
   elmk_restart_header H{};
   memcpy(H.magic, ELMK_RESTART_MAGIC, 8);
-  H.version = L.acc.empty() ? ELMK_RESTART_VERSION : ELMK_RESTART_VERSION_ACCUM;
+  H.version = L.alt ? ELMK_RESTART_VERSION_ALT : L.acc.empty() ? ELMK_RESTART_VERSION : ELMK_RESTART_VERSION_ACCUM;
   H.real_bytes = (uint32_t)store_size(ELMK_F64);
   H.schema_hash = schema_hash();
   H.gcol0 = gcol0;
@@ -2924,7 +3029,7 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
   H.total_bytes = L.total;
   memcpy(out, &H, sizeof H);
   unsigned char* p = out + sizeof H;
-  if (!L.acc.empty()) {
+  if (!L.acc.empty() || L.alt) {
     const uint32_t word[2] = {(uint32_t)L.acc.size(), 0u};
     memcpy(p, word, 8);
     p += 8;
@@ -2954,7 +3059,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   elmk_restart_header H;
   if (bytes < (int64_t)sizeof H) return invalid(ctx, "elmk_restart_load: truncated image");
   memcpy(&H, in, sizeof H);
-  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || (H.version != ELMK_RESTART_VERSION && H.version != ELMK_RESTART_VERSION_ACCUM))
+  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || (H.version != ELMK_RESTART_VERSION && H.version != ELMK_RESTART_VERSION_ACCUM && H.version != ELMK_RESTART_VERSION_ALT))
     return invalid(ctx, "elmk_restart_load: not a restart image of this format version");
   if (H.header_bytes > (uint64_t)bytes || H.total_bytes > (uint64_t)bytes || H.header_bytes % 8 != 0)
     return invalid(ctx, "elmk_restart_load: truncated image");
@@ -2967,8 +3072,12 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   const unsigned char* p = in + sizeof H;
   unsigned long long nacc[ELMK_ACCUM_MAX_ENTRIES] = {};
   const char* const acc_differs = "elmk_restart_load: the image's accumulator entries differ from the context's";
-  if ((H.version == ELMK_RESTART_VERSION_ACCUM) != !L.acc.empty()) return invalid(ctx, acc_differs);
-  if (!L.acc.empty()) {
+  // (version 3 is what a context with the active layer thickness saves and loads, with or without accumulator entries)
+  if ((H.version == ELMK_RESTART_VERSION_ALT) != L.alt)
+    return invalid(ctx, L.alt ? "elmk_restart_load: the active layer thickness is enabled and the image holds none (version 1 or 2)"
+                              : "elmk_restart_load: a version-3 image needs the active layer thickness enabled (elmk_active_layer_enable)");
+  if (!L.alt && (H.version == ELMK_RESTART_VERSION_ACCUM) != !L.acc.empty()) return invalid(ctx, acc_differs);
+  if (!L.acc.empty() || L.alt) {
     uint32_t word[2];
     if (H.header_bytes < sizeof H + 8) return invalid(ctx, "elmk_restart_load: truncated image");
     memcpy(word, p, 8);

@@ -115,7 +115,7 @@ struct RunRow {
   elmk_solar_step sol;  // elmk_solar_step_consts of the step, computed on the host
   double forc_wt1[8], forc_wt2[8];
   double month_wt1, month_wt2;
-  int32_t forc_slot, month1, month2, pad;
+  int32_t forc_slot, month1, month2, pad;  // pad: the step's ELMK_ALT_ROLL_* bits (ELMK_RUN_ALT; 0 otherwise)
 };
 // series: the forcing records [RUN_NFORC][slots][ld] and the months [RUN_NPHEN][12][ld], stored element type of the state
 constexpr int RUN_NFORC = 7, RUN_NPHEN = 4, RUN_NMONTH = 12;
@@ -231,6 +231,23 @@ void launch_aerosol_deposition(const DevState* S, int64_t n, const AerSeries& A,
 // the same with month1, month2, month_wt1, month_wt2 of table row *cursor (elmk_run)
 void launch_aerosol_deposition_run(const DevState* S, int64_t n, const AerSeries& A, const RunRow* rows, const int32_t* cursor,
                                    hipStream_t st);
+
+// active layer thickness (k_active_layer.hip, elmk_active_layer_*): the state fields it reads (t_soisno, zsoi: level 0, stored element
+// type of the state) and writes (the two I32 index fields), the three fp64 rows alt / altmax / altmax_lastyear [3][ld] of the feature
+// and the geography's sin(lat) row
+struct ActiveLayerArgs {
+  void* t_soisno;
+  void* zsoi;
+  int32_t* altmax_indx;
+  int32_t* altmax_lastyear_indx;
+  double* rows;
+  const double* sin_lat;
+  int64_t ld, ncols;
+};
+// one update of every column with the rollover bits ELMK_ALT_ROLL_*
+void launch_active_layer(const ActiveLayerArgs& A, int rollover, hipStream_t st);
+// the same with the rollover bits of table row *cursor (RunRow::pad; elmk_run)
+void launch_active_layer_run(const ActiveLayerArgs& A, const RunRow* rows, const int32_t* cursor, hipStream_t st);
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

@@ -13,13 +13,19 @@ A context with accumulated fields (elmk_accum_add) saves a version-2 image: the 
 entries, their table (ACCUM: source, kind, destination, period, step count) follows the history entries, and their value rows are
 sections of kind ACCUM_SECTION.  parse returns the table under "accum" (empty for version 1), build takes it as `accum`, and merge
 requires equal tables and equal step counts.  An image without accumulator entries is version 1, byte for byte as before.
+
+A context with the active layer thickness enabled (elmk_active_layer_enable) saves a version-3 image: as version 2 with the
+accumulator-count word always present (0 without entries) and, last, three column sections of kind ALT_SECTION (id 0, 1, 2: alt,
+altmax, altmax_lastyear; one level, F64).  build writes version 3 exactly when it is given such sections; merge and slice carry them
+as they carry every column section.
 """
 import numpy as np
 
 MAGIC = b"ELMKRST\0"
 VERSION = 1  # of an image without accumulator entries
 VERSION_ACCUM = 2  # of an image with accumulator entries
-FIELD, HISTORY, GRIDDED, ACCUM_SECTION = 0, 1, 2, 3  # ELMK_RESTART_*
+VERSION_ALT = 3  # of an image with the active layer thickness rows
+FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION = 0, 1, 2, 3, 4  # ELMK_RESTART_*
 ALIGN = 256
 HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), ("schema_hash", "<u8"), ("gcol0", "<i8"),
                    ("ncols", "<i8"), ("tape_count", "<u8", (4,)), ("nentries", "<u4"), ("nsections", "<u4"),
@@ -85,16 +91,16 @@ def parse(image):
     if img.size < HEADER.itemsize:
         raise RestartError("truncated image")
     h = np.frombuffer(img[:HEADER.itemsize].tobytes(), HEADER)[0]
-    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) not in (VERSION, VERSION_ACCUM):
+    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) not in (VERSION, VERSION_ACCUM, VERSION_ALT):
         raise RestartError("not a restart image of this format version")
     hb, tb, ne, ns = int(h["header_bytes"]), int(h["total_bytes"]), int(h["nentries"]), int(h["nsections"])
     o = HEADER.itemsize
     na = 0
-    if int(h["version"]) == VERSION_ACCUM:
+    if int(h["version"]) in (VERSION_ACCUM, VERSION_ALT):
         if img.size < o + 8:
             raise RestartError("truncated image")
         na, zero = (int(x) for x in np.frombuffer(img[o:o + 8].tobytes(), "<u4"))
-        if na < 1 or zero != 0:
+        if zero != 0 or (na < 1 and int(h["version"]) == VERSION_ACCUM):
             raise RestartError("a version-2 image holds at least one accumulator entry")
         o += 8
     if hb > img.size or tb > img.size or hb < o + ne * ENTRY.itemsize + na * ACCUM.itemsize + ns * SECTION.itemsize:
@@ -104,6 +110,8 @@ def parse(image):
     acc = np.frombuffer(img[o:o + na * ACCUM.itemsize].tobytes(), ACCUM).copy()
     o += na * ACCUM.itemsize
     sec = np.frombuffer(img[o:o + ns * SECTION.itemsize].tobytes(), SECTION).copy()
+    if bool(np.any(sec["kind"] == ALT_SECTION)) != (int(h["version"]) == VERSION_ALT):
+        raise RestartError("active layer sections belong to version 3, and a version-3 image holds them")
     data = []
     for s in sec:
         dt = ELEM[int(s["dtype"])]
@@ -130,14 +138,15 @@ def verify(image):
 
 
 def build(header, entries, sections, data, accum=None):
-    """An image from its parts: offsets, header_bytes, total_bytes, the version (2 with accumulator entries `accum`, else 1) and the
+    """An image from its parts: offsets, header_bytes, total_bytes, the version (3 with sections of kind ALT_SECTION, else 2 with accumulator entries `accum`, else 1) and the
     header checksum are computed; section checksums are taken from sections['checksum']."""
     h = np.array(header, HEADER).reshape(())
     ent = np.asarray(entries, ENTRY)
     acc = np.zeros(0, ACCUM) if accum is None else np.asarray(accum, ACCUM).reshape(-1)
     sec = np.array(sections, SECTION)
-    h["version"] = VERSION_ACCUM if acc.size else VERSION
-    pre = HEADER.itemsize + (8 if acc.size else 0)
+    alt = bool(np.any(sec["kind"] == ALT_SECTION)) if sec.size else False
+    h["version"] = VERSION_ALT if alt else (VERSION_ACCUM if acc.size else VERSION)
+    pre = HEADER.itemsize + (8 if acc.size or alt else 0)
     hb = _align(pre + ent.size * ENTRY.itemsize + acc.size * ACCUM.itemsize + sec.size * SECTION.itemsize)
     off = hb
     for i, d in enumerate(data):
@@ -146,7 +155,7 @@ def build(header, entries, sections, data, accum=None):
     h["nentries"], h["nsections"], h["header_bytes"], h["total_bytes"], h["header_checksum"] = ent.size, sec.size, hb, off, 0
     img = np.zeros(off, np.uint8)
     img[:HEADER.itemsize] = np.frombuffer(h.tobytes(), np.uint8)
-    if acc.size:
+    if acc.size or alt:
         img[HEADER.itemsize:pre] = np.frombuffer(np.array([acc.size, 0], "<u4").tobytes(), np.uint8)
     o = pre
     img[o:o + ent.nbytes] = np.frombuffer(ent.tobytes(), np.uint8)

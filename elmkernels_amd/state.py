@@ -26,7 +26,9 @@ HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, 
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
 CLASS_PROGNOSTIC, CLASS_SURFACE, CLASS_FORCING, CLASS_DIAGNOSTIC = range(4)  # elmk_field_class
 CLASS_NAMES = ("prognostic", "surface", "forcing", "diagnostic")
-RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM, RUN_AEROSOL = 1, 2, 4, 8  # elmk_run flags
+RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM, RUN_AEROSOL, RUN_ALT = 1, 2, 4, 8, 16  # elmk_run flags
+ALT_ALT, ALT_ALTMAX, ALT_ALTMAX_LASTYEAR = range(3)  # elmk_active_layer_read
+ALT_ROLL_NORTH, ALT_ROLL_SOUTH = 1, 2  # elmk_active_layer_update
 ACCUM_RUNMEAN, ACCUM_TIMEAVG, ACCUM_RUNACCUM = range(3)  # elmk_accum_add
 ACCUM_KINDS = {"runmean": ACCUM_RUNMEAN, "timeavg": ACCUM_TIMEAVG, "runaccum": ACCUM_RUNACCUM}
 ACCUM_MAX_ENTRIES = 16
@@ -444,6 +446,36 @@ class ELMState:
         self._chk(self.lib.elmk_accum_clear(self.ctx), "accum_clear")
         self._accum_nlev.clear()
 
+    # -- active layer thickness (include/elmk.h: elmk_active_layer_enable ...; elmkernels_amd/active_layer.py restates the update) --
+    def active_layer_enable(self):
+        """Allocate the rows alt, altmax, altmax_lastyear (fp64, zero-filled); the index fields altmax_indx and
+        altmax_lastyear_indx keep what was uploaded.  Refused when already enabled or while the stream is captured."""
+        self._chk(self.lib.elmk_active_layer_enable(self.ctx), "active_layer_enable")
+
+    def active_layer_init(self, altmax=None, altmax_lastyear=None):
+        """altmax and altmax_lastyear from [ncols] each (None: zeros), alt = zeros: a restart file's ALTMAX.  Synchronises."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (altmax, altmax_lastyear)]
+        for v in a:
+            if v is not None and v.size != self.ncols:
+                raise ValueError(f"active_layer_init: {v.size} values for {self.ncols} columns")
+        self._chk(self.lib.elmk_active_layer_init(self.ctx, *(None if v is None else _p(v) for v in a)), "active_layer_init")
+
+    def active_layer_update(self, rollover=0):
+        """ELM's alt_calc for every column from the current t_soisno: one launch, stream-ordered, no sync.  rollover: ALT_ROLL_* bits
+        (active_layer.rollover gives the run's rule).  Needs the column geography."""
+        self._chk(self.lib.elmk_active_layer_update(self.ctx, int(rollover)), "active_layer_update")
+
+    def active_layer_read(self, which, col0=0, n=None):
+        """Row ALT_ALT, ALT_ALTMAX or ALT_ALTMAX_LASTYEAR of columns [col0, col0 + n): float64 [n].  Synchronises."""
+        n = int(self.ncols - col0 if n is None else n)
+        out = np.empty(n, dtype=np.float64)
+        self._chk(self.lib.elmk_active_layer_read(self.ctx, int(which), _p(out), int(col0), n), "active_layer_read")
+        return out
+
+    def active_layer_clear(self):
+        """Free the three rows (the index fields keep their values)."""
+        self._chk(self.lib.elmk_active_layer_clear(self.ctx), "active_layer_clear")
+
     # -- aerosol deposition (include/elmk.h: elmk_aerosol_reserve ...; elmkernels_amd/aerosol.py restates the kernel) ----------
     def aerosol_reserve(self, ncells=None, idx=None, w=None):
         """The device series of the eleven deposition streams x 12 months x ncells (fp64, zero-filled) and the map of the aerosol
@@ -840,15 +872,17 @@ class ELMInterface:
             raise RuntimeError(f"ELM physics error flags {flags:#x}, first at column {col}")
         return False
 
-    def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False, update_accum=False, update_aerosol=False):
+    def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False, update_accum=False, update_aerosol=False,
+            update_active_layer=False):
         """ELMInterface::advance for every row of steps (RUN_STEP_DTYPE) in one call (elmk_run; needs S.run_reserve and the series
         uploaded); self.conservation = the last step's triples, self.run_conservation = all of them.  update_accum: every step updates
         the accumulated fields registered on self.S (ELM's UpdateAccVars: after the physics, before the history).  update_aerosol: every
         step interpolates aer_* from the aerosol series of self.S (S.aerosol_reserve / aerosol_upload) over the step's month bracket,
-        between the forcing and init_timestep.  Raises after the run if a step raised a fatal flag, naming the first such step and column."""
+        between the forcing and init_timestep.  update_active_layer: every step runs ELM's alt_calc after the physics (S.active_layer_enable),
+        with the annual rollover on the steps that start at 00:00 of 1 January / 1 July.  Raises after the run if a step raised a fatal flag, naming the first such step and column."""
         S = self.S
         flags = (RUN_HISTORY if accumulate_history else 0) | (RUN_QBOT_IS_RH if qbot_is_rh else 0) | (RUN_ACCUM if update_accum else 0)
-        flags |= RUN_AEROSOL if update_aerosol else 0
+        flags |= (RUN_AEROSOL if update_aerosol else 0) | (RUN_ALT if update_active_layer else 0)
         S.run(dt_seconds, steps, flags)
         mms, fo, fb = S.run_diagnostics()
         self.run_conservation = mms
@@ -905,6 +939,10 @@ class ELMInterface:
         """aer_* from the aerosol series of self.S (ELMState.aerosol_deposition): call before advance(), with the month bracket that
         feeds advance()'s month_wt1 / month_wt2 (the reference's hook, init_timestep_kokkos.cc:48-49)."""
         self.S.aerosol_deposition(month1, month2, wt1, wt2)
+
+    def update_active_layer(self, rollover=0):
+        """ELM's alt_calc on self.S (ELMState.active_layer_update): call after advance(), before update_accum()."""
+        self.S.active_layer_update(rollover)
 
     def update_accum(self):
         """Update the accumulated fields registered on self.S (ELMState.accum_add): call after advance(), before accumulate_history()."""

@@ -302,6 +302,7 @@ int elmk_history_clear(elmk_ctx *ctx);
  *                          with ELMK_RUN_AEROSOL: elmk_aerosol_deposition(month1, month2, month_wt1, month_wt2) ("aerosol deposition");
  *                          elmk_init_timestep; elmk_advance_physics(dt); elmk_evaluate_conservation -> ring row s;
  *                          elmk_error_summary -> ring row s (flags sticky, as that call sees them after the step);
+ *                          with ELMK_RUN_ALT: elmk_active_layer_update(the step's rollover) ("active layer thickness");
  *                          with ELMK_RUN_ACCUM: elmk_accum_update ("accumulated fields");
  *                          with ELMK_RUN_HISTORY: elmk_history_accumulate.
  *                        Stream-ordered, returns without synchronising; with elmk_set_graph one step is captured once (one chain of
@@ -599,6 +600,57 @@ int elmk_aerosol_upload(elmk_ctx *ctx, int field /*ELMK_FIELD_aer_bcphi .. ELMK_
 int elmk_aerosol_deposition(elmk_ctx *ctx, int month1, int month2, double wt1, double wt2);
 int elmk_aerosol_clear(elmk_ctx *ctx);
 
+/* ---- active layer thickness --------------------------------------------------------------------
+ * ELM's ActiveLayerMod::alt_calc on the device: the depth of the thaw front (history fields ALT, ALTMAX, ALTMAX_LASTYEAR) and the
+ * two layer indices altmax_indx and altmax_lastyear_indx, which initialize_flux -> calc_root_moist_stress -> normalize_unfrozen_rootfr
+ * reads every step.  The reference marks both fields NEED!! (src/data/elm_state_impl.hh:274-276) and has no alt_calc; no kernel of the
+ * step writes them, so without these calls they keep what was uploaded (the reference driver's placeholders are 5 and 0).  ELM runs the
+ * routine once per step after the soil temperature solve.  The feature owns three fp64 rows [level stride] (in both builds): alt,
+ * altmax, altmax_lastyear (ELMK_ALT_*); the indices are the two I32 state fields.
+ * One update, per column c, with t[j] and z[j] the temperature and node depth of soil layer j = 0 .. 14 (level 5 + j of t_soisno / zsoi,
+ * widened to fp64), tfrz = 273.15, without contraction (`/` is the correctly rounded fp64 division):
+ *   if (roll_c) { altmax_lastyear = altmax;  altmax_lastyear_indx = altmax_indx;  altmax = +0.0;  altmax_indx = -1; }
+ *   if (t[14] > tfrz) { a = z[14];  k = 14; }
+ *   else { k = the largest j in 0 .. 13 with t[j] > tfrz, or -1 if there is none      (from the bottom upward: a talik counts)
+ *          if (k >= 0) a = z[k] + ((t[k] - tfrz) * (z[k+1] - z[k])) / (t[k] - t[k+1]);  else a = +0.0; }
+ *   if (a != a) a = the canonical quiet NaN, bits 0x7FF8000000000000;
+ *   alt = a;  if (a > altmax) { altmax = a;  altmax_indx = k; }
+ * Every comparison is the plain IEEE `>`: a NaN temperature is "not thawed", a NaN a is stored in alt and leaves altmax alone; no error
+ * bit is raised.  A NaN a (from a NaN or infinite t or z) is stored as that one NaN: IEEE 754 leaves the sign and payload of a NaN result
+ * to the implementation, and device and host arithmetic differ there, so the operation fixes them.  The indices are 0-BASED soil-layer numbers with -1 for "no thawed layer", that is ELM's index minus one: the only
+ * consumer reads them as i <= max(0, max(altmax_lastyear_indx, altmax_indx)) over 0-based i (soil_moist_stress_impl.hh:41), which is
+ * ELM's j <= max(indx, 1) over 1-based j.  The annual rollover (ELM: before the search) is per hemisphere:
+ *   roll_c = (rollover & ELMK_ALT_ROLL_NORTH) && north_c || (rollover & ELMK_ALT_ROLL_SOUTH) && !north_c,
+ *   north_c = geo[ELMK_GEO_SIN_LAT][c] > 0.0 - for |lat| <= pi/2 ELM's lat > 0, with lat == 0 going south.
+ * elmkernels_amd/active_layer.py: update is this operation on the host.
+ *   elmk_active_layer_enable  allocates the three rows, zero-filled (one owner of 3 x 8 bytes x elmk_level_stride, counted in
+ *                             elmk_device_bytes); writes no state field; drops the captured run step.  ELMK_E_INVALID, nothing
+ *                             changed: already enabled; a stream being captured.
+ *   elmk_active_layer_init    altmax and altmax_lastyear from host[ncols] each (NULL: zeros), alt = zeros: how a restart file's ALTMAX
+ *                             comes in (the indices come in through elmk_upload).  Synchronises.
+ *   elmk_active_layer_update  one launch; stream-ordered and capturable, no host memory, no synchronisation; writes nothing but the
+ *                             three rows and the two index fields.  ELMK_E_INVALID, nothing enqueued: not enabled; no column
+ *                             geography; unknown rollover bits.
+ *   elmk_active_layer_read    row `which` (ELMK_ALT_*) of columns [col0, col0 + n) as doubles; synchronises.
+ *   elmk_active_layer_clear   frees the rows and drops the captured run step; the state fields keep their values.
+ * elmk_run with ELMK_RUN_ALT runs the update in every step, after the step's conservation and flag rows and before the accumulated
+ * fields and the history (ELM's order: tapes and accumulators of the index fields see the new values); refused before anything is
+ * enqueued when not enabled.  The step's rollover is derived on the host from the step's start date, in the reference's no-leap
+ * calendar: NORTH iff doy == 0 && decday == 1.0 (the step that starts at 00:00 of 1 January), SOUTH iff doy == 181 && decday == 182.0
+ * (1 July) - the step whose end-of-step date satisfies ELM's mon, day == 1 && sec / dtime == 1 (active_layer.rollover).  Graph on and
+ * off give the same bits.
+ * Restart: a context with the feature enabled saves a version-3 image that carries the three rows ("restart" below).
+ * A context that never enables the feature runs the kernels, launch sequences and graphs it ran before, allocates nothing more and
+ * saves the image it saved before. */
+enum { ELMK_ALT_ALT = 0, ELMK_ALT_ALTMAX = 1, ELMK_ALT_ALTMAX_LASTYEAR = 2 };
+enum { ELMK_ALT_ROLL_NORTH = 1, ELMK_ALT_ROLL_SOUTH = 2 };
+#define ELMK_RUN_ALT 16 /* the fifth flag bit of elmk_run: every step updates the active layer thickness */
+int elmk_active_layer_enable(elmk_ctx *ctx);
+int elmk_active_layer_init(elmk_ctx *ctx, const double *altmax /*[ncols] or NULL*/, const double *altmax_lastyear /*[ncols] or NULL*/);
+int elmk_active_layer_update(elmk_ctx *ctx, int rollover /*ELMK_ALT_ROLL_* bits*/);
+int elmk_active_layer_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
+int elmk_active_layer_clear(elmk_ctx *ctx);
+
 /* ---- restart ---------------------------------------------------------------------------------
  * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state
  * and history into a self-describing byte buffer, the image, and another context - in another process, or with another column
@@ -633,6 +685,12 @@ int elmk_aerosol_clear(elmk_ctx *ctx);
  * registration order (source, kind, destination, period and the step count n), then the section table; the ELMK_RESTART_ACCUM
  * sections come last, checksummed as the other column sections.  The header checksum covers all of it.
  *
+ * Image format, version 3: what a context with the active layer thickness enabled (elmk_active_layer_enable) saves.  As version 2,
+ * with the accumulator-count word always present (0 without entries), and after the ELMK_RESTART_ACCUM sections three sections of kind
+ * ELMK_RESTART_ALT, id = ELMK_ALT_ALT, ELMK_ALT_ALTMAX, ELMK_ALT_ALTMAX_LASTYEAR, nlev = 1, F64, extent = ncols: the three rows,
+ * checksummed as the other column sections.  A version-3 image loads only into a context with the feature enabled, a version-1 or
+ * version-2 image only into one without it.
+ *
  * elmk_restart_size: bytes of this context's image.  elmk_restart_save: the image of the context's columns, which are global
  * columns [gcol0, gcol0 + ncols) of the run.  elmk_restart_load: verifies the whole image on the device (every checksum, snl in
  * 0..nlevsno, as elmk_upload) before it writes anything, then writes the fields, the accumulators, the tape counts and the
@@ -642,7 +700,8 @@ int elmk_aerosol_clear(elmk_ctx *ctx);
  * captured, a too small or truncated buffer, a bad magic
  * or version, another schema, another ncols or gcol0, a history entry table other than the context's (same entries, same order,
  * gridded entries with the same ncells), an accumulator table other than the context's (same source, kind, period and destination,
- * same order; the counts are loaded, not compared), any checksum mismatch, snl out of range.
+ * same order; the counts are loaded, not compared), a version-3 image without the active layer thickness enabled or an older one with
+ * it, any checksum mismatch, snl out of range.
  *
  * The image holds column data and history only.  Parameters, SNICAR and snow-age tables, geography, forcing and output maps, run
  * reservations and series, shortwave mode and record times, options and graphs stay with the driver, which sets them up as at
@@ -650,10 +709,11 @@ int elmk_aerosol_clear(elmk_ctx *ctx);
  * then the current forcing records or run series and their record times.
  * Graphs captured before a load stay valid (the arena and the history table do not move). */
 enum { ELMK_CLASS_PROGNOSTIC = 0, ELMK_CLASS_SURFACE = 1, ELMK_CLASS_FORCING = 2, ELMK_CLASS_DIAGNOSTIC = 3 };
-enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2, ELMK_RESTART_ACCUM = 3 };
+enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2, ELMK_RESTART_ACCUM = 3, ELMK_RESTART_ALT = 4 };
 #define ELMK_RESTART_MAGIC "ELMKRST\0"
 #define ELMK_RESTART_VERSION 1u       /* of a context without accumulator entries */
 #define ELMK_RESTART_VERSION_ACCUM 2u /* of a context with accumulator entries */
+#define ELMK_RESTART_VERSION_ALT 3u   /* of a context with the active layer thickness enabled */
 typedef struct {
   char magic[8];              /* ELMK_RESTART_MAGIC */
   uint32_t version;           /* ELMK_RESTART_VERSION */

@@ -280,6 +280,20 @@ class ELMInterface {
   }
   void accum_clear() { ok(elmk_accum_clear(ctx_)); }
 
+  /* Active layer thickness (elmk.h "active layer thickness"; ELM's ActiveLayerMod::alt_calc): active_layer_enable() allocates the rows
+   * alt, altmax and altmax_lastyear; update_active_layer() after every advance() and before update_accum() computes the thaw depth from
+   * t_soisno and keeps altmax_indx / altmax_lastyear_indx (0-based soil layers, -1: none) live, or run(..., update_active_layer = true)
+   * does it in every step with the annual rollover on the steps that start at 00:00 of 1 January / 1 July.  active_layer_init() takes a
+   * restart file's ALTMAX and ALTMAX_LASTYEAR ([ncols] each, nullptr: zeros); active_layer_read() fills [ncols] of row ELMK_ALT_*. */
+  void active_layer_enable() { ok(elmk_active_layer_enable(ctx_)); }
+  void active_layer_init(const double* altmax = nullptr, const double* altmax_lastyear = nullptr)
+  {
+    ok(elmk_active_layer_init(ctx_, altmax, altmax_lastyear));
+  }
+  void update_active_layer(int rollover = 0) { ok(elmk_active_layer_update(ctx_, rollover)); }
+  void active_layer_read(int which, double* host) { ok(elmk_active_layer_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
+  void active_layer_clear() { ok(elmk_active_layer_clear(ctx_)); }
+
   /* Restart images (elmk.h "restart"): saveRestart() returns the image of the columns, global columns [gcol0, gcol0 + ncols);
    * loadRestart() takes one after setup, geography, maps and the same history and accumulator entries, in place of initialize().
    * Both throw on a refusal; the state is then untouched. */
@@ -311,11 +325,11 @@ class ELMInterface {
     ok(elmk_series_upload(ctx_, id(field), slot0, nslots, host, 0, ncols_));
   }
   void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
-                   bool update_accum = false, bool update_aerosol = false)
+                   bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false)
   {
     ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(),
                 (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0) | (update_accum ? ELMK_RUN_ACCUM : 0) |
-                    (update_aerosol ? ELMK_RUN_AEROSOL : 0)));
+                    (update_aerosol ? ELMK_RUN_AEROSOL : 0) | (update_active_layer ? ELMK_RUN_ALT : 0)));
   }
   bool finish_run()
   {
@@ -337,9 +351,9 @@ class ELMInterface {
     return false;
   }
   bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
-           bool update_accum = false, bool update_aerosol = false)
+           bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false)
   {
-    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol);
+    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol, update_active_layer);
     return finish_run();
   }
   const std::vector<double>& run_conservation() const { return run_conservation_; }

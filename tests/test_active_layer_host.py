@@ -1,0 +1,339 @@
+"""Active layer thickness on the host: active_layer.update (the numpy restatement of include/elmk.h "active layer thickness") against a
+scalar per-column loop written straight from the spec, the pinned interpolation, the run's rollover rule over a year of step starts,
+the version-3 restart image in the codec, and the declarations."""
+import math
+import os
+import re
+import struct
+
+import numpy as np
+import pytest
+
+from elmkernels_amd import _lib as L
+from elmkernels_amd import active_layer as al
+from elmkernels_amd import restart as R
+from elmkernels_amd import state as st
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("elmk_active_layer_enable", "elmk_active_layer_init", "elmk_active_layer_update", "elmk_active_layer_read",
+               "elmk_active_layer_clear")
+TFRZ = 273.15
+
+
+def bits(a):
+    return np.ascontiguousarray(a).tobytes()
+
+
+def scalar_update(t, z, alt, altmax, altmax_ly, indx, indx_ly, north, rollover):
+    """One column, straight from the spec: t, z the 15 soil layers; Python floats are IEEE fp64 and every line is one operation."""
+    t, z = [float(x) for x in t], [float(x) for x in z]
+    roll = bool(rollover & 1 and north) or bool(rollover & 2 and not north)
+    if roll:
+        altmax_ly, indx_ly = altmax, indx
+        altmax, indx = 0.0, -1
+    if t[14] > TFRZ:
+        a, k = z[14], 14
+    else:
+        k = -1
+        for j in range(13, -1, -1):
+            if t[j] > TFRZ:
+                k = j
+                break
+        if k >= 0:
+            z1, z2, t1, t2 = z[k], z[k + 1], t[k], t[k + 1]
+            num = t1 - TFRZ
+            dz = z2 - z1
+            num = num * dz
+            den = t1 - t2
+            q = (num / den) if den != 0.0 else (math.nan if (num == 0.0 or math.isnan(num)) else math.copysign(math.inf, num) * math.copysign(1.0, den))
+            a = z1 + q
+        else:
+            a = 0.0
+    if a != a:
+        a = math.nan  # the canonical quiet NaN
+    alt = a
+    if a > altmax:
+        altmax, indx = a, k
+    return alt, altmax, altmax_ly, indx, indx_ly
+
+
+def columns(n, seed, special=True):
+    """t_soisno, zsoi [20, n]: random around tfrz over a monotone soil mesh; with `special`, hand-built columns first: every k from -1
+    to 14, a talik, a layer at exactly tfrz, t1 - t2 of one ulp, NaN and infinities in t_soisno and zsoi."""
+    rng = np.random.default_rng(seed)
+    t = TFRZ + 3.0 * rng.standard_normal((20, n))
+    z = np.cumsum(0.02 + rng.random((20, n)), axis=0) - 0.5
+    if not special:
+        return t, z
+    c = 0
+
+    def put(tt, zz=None):
+        nonlocal c
+        if c < n:
+            t[5:, c] = tt
+            if zz is not None:
+                z[5:, c] = zz
+        c += 1
+
+    cold, warm = np.full(15, 271.15), 275.15
+    for k in range(-1, 15):  # thawed down to layer k, frozen below
+        tt = cold.copy()
+        tt[:k + 1] = warm
+        put(tt)
+    tt = cold.copy()
+    tt[14] = warm  # only the bottom layer thawed
+    put(tt)
+    tt = cold.copy()
+    tt[[0, 1, 6, 7]] = warm  # a talik: thawed below frozen below thawed -> k = 7
+    put(tt)
+    tt = cold.copy()
+    tt[:3] = warm
+    tt[3] = TFRZ  # exactly tfrz is frozen -> k = 2, t2 = tfrz
+    put(tt)
+    tt = cold.copy()
+    tt[:5] = TFRZ  # nothing above tfrz at all
+    put(tt)
+    tt = np.full(15, np.nextafter(TFRZ, 0.0))
+    tt[4] = np.nextafter(TFRZ, 1e9)  # t1 - t2 = two ulps, t1 - tfrz = one ulp
+    put(tt)
+    tt = cold.copy()
+    tt[5] = warm
+    tt[6] = np.nextafter(warm, 0.0)  # t1 - t2 of one ulp, t[6] thawed: k = 6 against a frozen 7
+    tt[4] = np.nextafter(warm, 1e9)
+    put(tt)
+    tt = np.full(15, warm)
+    tt[9:] = np.nextafter(warm, 0.0)
+    tt[14] = 271.15  # k = 13; above it t[k] - t[k+1] is large, but t[8] - t[9] = 1 ulp is never used
+    put(tt)
+    for bad in (np.nan, np.inf, -np.inf):
+        for where in (14, 3, 0):
+            tt = cold.copy()
+            tt[:3] = warm
+            tt[where] = bad
+            put(tt)
+        tt = cold.copy()
+        tt[:4] = warm
+        tt[4] = bad  # t2 is bad (k = 3), or +inf is thawed itself (k = 4)
+        put(tt)
+        for where in (2, 3, 14):
+            tt = cold.copy()
+            tt[:3] = warm
+            zz = np.cumsum(np.full(15, 0.25))
+            zz[where] = bad
+            put(tt, zz)
+        tt = np.full(15, warm)
+        zz = np.cumsum(np.full(15, 0.25))
+        zz[14] = bad  # the bottom layer thawed over a bad depth
+        put(tt, zz)
+    tt = cold.copy()
+    tt[:2] = warm
+    put(tt, np.zeros(15))  # z2 - z1 = 0
+    return t, z
+
+
+@pytest.mark.parametrize("n", [1, 97])
+def test_update_equals_the_scalar_loop(n):
+    """Six chained updates with the rollover sequence 0, 0, NORTH, 0, SOUTH, NORTH | SOUTH over both hemispheres."""
+    rng = np.random.default_rng(n)
+    north = rng.random(n) < 0.5
+    alt, am, aly = np.zeros(n), np.zeros(n), np.zeros(n)
+    ix, ily = np.full(n, 5, np.int32), np.zeros(n, np.int32)
+    ref = [(0.0, 0.0, 0.0, 5, 0)] * n
+    for step, roll in enumerate((0, 0, al.ROLL_NORTH, 0, al.ROLL_SOUTH, al.ROLL_NORTH | al.ROLL_SOUTH)):
+        t, z = columns(n, 10 * n + step, special=step % 2 == 0)
+        alt, am, aly, ix, ily = al.update(t, z, alt, am, aly, ix, ily, north, roll)
+        ref = [scalar_update(t[5:, c], z[5:, c], *ref[c], bool(north[c]), roll) for c in range(n)]
+        for i, got in enumerate((alt, am, aly)):
+            assert bits(got) == bits(np.array([r[i] for r in ref])), (step, i)
+        assert bits(ix) == bits(np.array([r[3] for r in ref], np.int32)) and bits(ily) == bits(np.array([r[4] for r in ref], np.int32)), step
+        assert ix.dtype == np.int32 and ily.dtype == np.int32
+
+
+def test_hand_built_columns_give_their_k():
+    n = 64
+    t, z = columns(n, 5)
+    out = al.update(t, z, np.zeros(n), np.zeros(n), np.zeros(n), np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.ones(n, bool), 0)
+    alt, am, _, ix, _ = out
+    assert ix[1:16].tolist() == list(range(0, 15)) and ix[0] == -1 and alt[0] == 0.0 and am[0] == 0.0
+    assert alt[15] == z[5 + 14, 15] and alt[16] == z[5 + 14, 16] and ix[16] == 14  # the bottom layer thawed: its node depth
+    assert ix[17] == 7  # the talik counts as active layer
+    assert ix[18] == 2 and alt[18] == z[7, 18] + ((275.15 - TFRZ) * (z[8, 18] - z[7, 18])) / (275.15 - TFRZ)
+    assert ix[19] == -1 and alt[19] == 0.0
+    assert ix[20] == 4 and ix[21] == 6 and ix[22] == 13
+    assert np.isnan(alt).any() and not np.isnan(am).any()  # a NaN a is stored in alt and leaves altmax alone
+    assert set(alt[np.isnan(alt)].view(np.uint64).tolist()) == {0x7FF8000000000000}  # as the one canonical NaN
+
+
+def test_the_pinned_case():
+    """Soil layers 0..2 at 275.15 K, 3..14 at 271.15 K, zsoi of layers 2 and 3 at 1.0 and 2.0: k = 2 and alt == 1.5 exactly (the
+    subtractions give 2.0 and 4.0 exactly: the operands are a whole number of ulps apart in one binade)."""
+    t = np.full((20, 1), 271.15)
+    t[5:8] = 275.15
+    z = np.cumsum(np.full((20, 1), 0.1), axis=0)
+    z[5 + 2], z[5 + 3] = 1.0, 2.0
+    assert 275.15 - TFRZ == 2.0 and 275.15 - 271.15 == 4.0
+    alt, am, aly, ix, ily = al.update(t, z, [0.0], [0.25], [0.125], [7], [9], [True], 0)
+    assert alt[0] == 1.5 and am[0] == 1.5 and ix[0] == 2 and aly[0] == 0.125 and ily[0] == 9
+    # a deeper maximum stays, with its index
+    alt, am, aly, ix, ily = al.update(t, z, [0.0], [1.75], [0.125], [7], [9], [True], 0)
+    assert alt[0] == 1.5 and am[0] == 1.75 and ix[0] == 7
+    # the rollover comes before the search
+    alt, am, aly, ix, ily = al.update(t, z, [0.0], [1.75], [0.125], [7], [9], [True], al.ROLL_NORTH)
+    assert (alt[0], am[0], aly[0], ix[0], ily[0]) == (1.5, 1.5, 1.75, 2, 7)
+    alt, am, aly, ix, ily = al.update(t, z, [0.0], [1.75], [0.125], [7], [9], [False], al.ROLL_NORTH)
+    assert (alt[0], am[0], aly[0], ix[0], ily[0]) == (1.5, 1.75, 0.125, 7, 9)
+    # frozen through a rollover: the indices reset to -1
+    alt, am, aly, ix, ily = al.update(np.full((20, 1), 260.0), z, [0.0], [1.75], [0.125], [7], [9], [False], al.ROLL_SOUTH)
+    assert (alt[0], am[0], aly[0], ix[0], ily[0]) == (0.0, 0.0, 1.75, -1, 7) and not np.signbit(am[0])
+
+
+def test_update_in_place_and_bad_bits():
+    t, z = columns(9, 2, special=False)
+    arrs = [np.zeros(9), np.zeros(9), np.zeros(9), np.zeros(9, np.int32), np.zeros(9, np.int32)]
+    want = al.update(t, z, *arrs, np.ones(9, bool), 1)
+    assert all(not np.shares_memory(w, a) for w, a in zip(want, arrs))
+    got = al.update(t, z, *arrs, np.ones(9, bool), 1, inplace=True)
+    assert all(g is a for g, a in zip(got, arrs)) and all(bits(g) == bits(w) for g, w in zip(got, want))
+    with pytest.raises(ValueError):
+        al.update(t, z, *arrs, np.ones(9, bool), 4)
+    # fp32 samples are widened
+    want = al.update(t.astype(np.float32).astype(np.float64), z, *arrs, np.ones(9, bool), 0)
+    got = al.update(t.astype(np.float32), z, *arrs, np.ones(9, bool), 0)
+    assert all(bits(g) == bits(w) for g, w in zip(got, want))
+
+
+def test_north_is_the_sign_of_sin_lat():
+    lat = np.array([0.0, -0.0, 1e-300, -1e-300, np.pi / 2, -np.pi / 2, 0.7, -0.7])
+    assert al.north(lat).tolist() == [False, False, True, False, True, False, True, False]
+
+
+@pytest.mark.parametrize("dt", [1800.0, 3600.0])
+def test_rollover_rule_over_a_year_of_step_starts(dt):
+    """Step starts of a no-leap year as a driver fills elmk_run_step (tests/test_gpu_run.py: schedule): exactly one NORTH and one
+    SOUTH step, those that start at 00:00 of 1 January and 1 July."""
+    per_day = int(86400.0 / dt)
+    hits = {}
+    for s in range(365 * per_day):
+        ddoy = s * dt / 86400.0
+        r = al.rollover(int(ddoy), ddoy + 1.0)
+        if r:
+            hits[s] = r
+    assert hits == {0: al.ROLL_NORTH, 181 * per_day: al.ROLL_SOUTH}
+    # 1 July is day 181 of the no-leap calendar (0-based): 31 + 28 + 31 + 30 + 31 + 30
+    assert sum((31, 28, 31, 30, 31, 30)) == 181
+    # the next step of the same day, and the same time of another day, are not rollovers
+    assert al.rollover(0, 1.0 + dt / 86400.0) == 0 and al.rollover(1, 2.0) == 0 and al.rollover(181, 182.5) == 0 and al.rollover(180, 181.0) == 0
+
+
+# ---- the codec: version 3 ---------------------------------------------------------------------------------------------------------
+def _image(gcol0=0, n=37, seed=3, accum_table=((29, 0, 30, 480, 6),), alt=True):
+    """As test_accum_host._image, with the three ALT sections last when alt."""
+    rng = np.random.default_rng(seed)
+    h = np.zeros((), R.HEADER)
+    h["magic"], h["version"], h["real_bytes"], h["schema_hash"] = R.MAGIC, R.VERSION, 8, 0x1234
+    h["gcol0"], h["ncols"], h["tape_count"] = gcol0, n, [5, 2, 0, 0]
+    ent = np.zeros(1, R.ENTRY)
+    ent[0] = (0, 52, 0, 0, 0)
+    secs = [(R.FIELD, 29, 1, 1), (R.FIELD, 51, 20, 0), (R.FIELD, 167, 1, 2), (R.HISTORY, 0, 1, 0)]
+    acc = np.zeros(len(accum_table), R.ACCUM)
+    for i, (src, kind, dst, period, nsteps) in enumerate(accum_table):
+        acc[i] = (src, kind, dst, 0, period, nsteps)
+        secs.append((R.ACCUM_SECTION, i, 1, 0))
+    if alt:
+        secs += [(R.ALT_SECTION, which, 1, 0) for which in range(3)]
+    sec = np.zeros(len(secs), R.SECTION)
+    data = []
+    for i, (kind, fid, nlev, dt) in enumerate(secs):
+        d = (rng.integers(0, 6, (nlev, n)) if dt != 0 else rng.standard_normal((nlev, n))).astype(R.ELEM[dt])
+        sec[i] = (kind, fid, nlev, dt, n, 0, R.checksum(d, gcol0))
+        data.append(d)
+    return R.build(h, ent, sec, data, acc)
+
+
+@pytest.mark.parametrize("entries", [0, 1])
+def test_version_3_image_round_trips_through_slice_and_merge(entries):
+    img = _image(gcol0=100, n=37, accum_table=((29, 0, 30, 480, 6),)[:entries])
+    p = R.verify(img)
+    assert int(p["header"]["version"]) == R.VERSION_ALT == 3 and p["accum"].size == entries
+    # the accumulator-count word is present also without entries
+    assert struct.unpack("<II", img[R.HEADER.itemsize:R.HEADER.itemsize + 8].tobytes()) == (entries, 0)
+    kinds = [int(s["kind"]) for s in p["sections"]]
+    assert kinds[-3:] == [R.ALT_SECTION] * 3 and [int(s["id"]) for s in p["sections"]][-3:] == [0, 1, 2]
+    assert all(int(s["nlev"]) == 1 and int(s["dtype"]) == 0 and int(s["extent"]) == 37 for s in p["sections"][-3:])
+    # a split at a column inside a section; checksums add; merge(slice, slice) gives the image back
+    parts = [R.slice(img, 100, 10), R.slice(img, 110, 1), R.slice(img, 111, 26)]
+    for q in parts:
+        assert int(R.verify(q)["header"]["version"]) == 3
+    assert R.merge(parts[::-1]).tobytes() == img.tobytes()
+    a, b = parts[0], R.slice(img, 110, 27)
+    pa, pb = R.parse(a), R.parse(b)
+    for i, s in enumerate(p["sections"]):
+        assert int(s["checksum"]) == (int(pa["sections"][i]["checksum"]) + int(pb["sections"][i]["checksum"])) % (1 << 64)
+        assert bits(np.concatenate([pa["data"][i], pb["data"][i]], axis=1)) == bits(p["data"][i])
+    assert R.build(p["header"], p["entries"], p["sections"], p["data"], p["accum"]).tobytes() == img.tobytes()
+
+
+def test_version_3_does_not_mix_and_damage_is_refused():
+    a = _image(0, 10)
+    with pytest.raises(R.RestartError):  # a version-2 image beside a version-3 image
+        R.merge([a, _image(10, 10, alt=False)])
+    R.verify(R.merge([a, _image(10, 10)]))
+    img = _image()
+    p = R.parse(img)
+    for off in (R.HEADER.itemsize, int(p["sections"][-1]["offset"]) + 3, int(p["sections"][-3]["offset"]) + 8):
+        bad = img.copy()
+        bad[off] ^= 1
+        with pytest.raises(R.RestartError):
+            R.verify(bad)
+    # the version word and the sections go together
+    for version in (R.VERSION_ACCUM, 4):
+        bad = img.copy()
+        bad[8:12] = np.frombuffer(struct.pack("<I", version), np.uint8)
+        with pytest.raises(R.RestartError):
+            R.parse(bad)
+    old = _image(alt=False)
+    bad = old.copy()
+    bad[8:12] = np.frombuffer(struct.pack("<I", R.VERSION_ALT), np.uint8)
+    with pytest.raises(R.RestartError):
+        R.parse(bad)
+    # images without the rows are what they were: version 2 with entries, version 1 without
+    assert int(R.verify(old)["header"]["version"]) == 2
+    assert int(R.verify(_image(accum_table=(), alt=False))["header"]["version"]) == 1
+
+
+# ---- declarations -----------------------------------------------------------------------------------------------------------------
+def test_active_layer_abi_is_declared_and_mirrored():
+    hdr = open(os.path.join(ROOT, "include", "elmk.h")).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b" + name + r"\s*\(", hdr), name
+        assert name in L.SIGNATURES
+    for name, value in (("ELMK_ALT_ALT", al.ALT), ("ELMK_ALT_ALTMAX", al.ALTMAX), ("ELMK_ALT_ALTMAX_LASTYEAR", al.ALTMAX_LASTYEAR),
+                        ("ELMK_ALT_ROLL_NORTH", al.ROLL_NORTH), ("ELMK_ALT_ROLL_SOUTH", al.ROLL_SOUTH), ("ELMK_RESTART_ALT", R.ALT_SECTION)):
+        assert re.search(r"\b" + name + r" = " + str(value) + r"\b", hdr), name
+    assert re.search(r"#define ELMK_RUN_ALT " + str(st.RUN_ALT) + r"\b", hdr) and st.RUN_ALT == 16
+    assert re.search(r"#define ELMK_RESTART_VERSION_ALT 3u", hdr) and R.VERSION_ALT == 3
+    assert (st.ALT_ALT, st.ALT_ALTMAX, st.ALT_ALTMAX_LASTYEAR, st.ALT_ROLL_NORTH, st.ALT_ROLL_SOUTH) == (0, 1, 2, 1, 2)
+    assert "0-BASED" in hdr and "ELM's index minus one" in hdr  # the index convention is stated
+    for m in ("active_layer_enable", "active_layer_init", "active_layer_update", "active_layer_read", "active_layer_clear"):
+        assert callable(getattr(st.ELMState, m))
+    assert st.field_class("altmax_indx") == st.CLASS_SURFACE and st.field_class("altmax_lastyear_indx") == st.CLASS_SURFACE
+    ft = st.field_table()
+    assert ft["altmax_indx"][1:] == (1, np.int32) and ft["t_soisno"][1] == 20 and ft["zsoi"][1] == 20
+
+
+def test_cold_start_calls():
+    class Fake:
+        ncols = 4
+
+        def __init__(self):
+            self.calls = []
+
+        def active_layer_init(self, a, b):
+            self.calls.append(("init", a, b))
+
+        def __setitem__(self, k, v):
+            self.calls.append((k, v.tolist(), v.dtype))
+
+    F = Fake()
+    al.cold_start(F)
+    assert F.calls == [("init", None, None), ("altmax_indx", [-1] * 4, np.int32), ("altmax_lastyear_indx", [-1] * 4, np.int32)]
