@@ -122,6 +122,12 @@ SIGNATURES = {
     "elmk_active_layer_update": (C.c_int, [_P, C.c_int]),
     "elmk_active_layer_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
     "elmk_active_layer_clear": (C.c_int, [_P]),
+    "elmk_soil_hydrology_enable": (C.c_int, [_P]),
+    "elmk_soil_hydrology_set_params": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "elmk_soil_hydrology_init": (C.c_int, [_P, _P, _P]),
+    "elmk_soil_hydrology": (C.c_int, [_P, C.c_double]),
+    "elmk_soil_hydrology_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_soil_hydrology_clear": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)
@@ -154,9 +160,9 @@ _libs = {}
 F32_LIB_PATH = os.path.join(HERE, "libelmk_f32.so")
 
 
-def load(path=None):
+def load(path=None, optional=()):
     """Load libelmk.so (or another build of the same ABI) and declare every entry point; fails loudly when the HIP
-    extension is not built."""
+    extension is not built.  optional: name prefixes of entry points the library may lack (an older build measured beside this one)."""
     path = path or LIB_PATH
     if path in _libs:
         return _libs[path]
@@ -168,6 +174,8 @@ def load(path=None):
         )
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if any(name.startswith(p) for p in optional) and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError here means the .so is stale w.r.t. include/elmk.h
         fn.restype = res
         fn.argtypes = args

@@ -165,6 +165,7 @@ struct GraphSlot {
   double dt = 0.0;
   hipStream_t stream = nullptr;
   uint64_t tag = 0;  // what else the captured launches depend on (elmk_run: its flags and the history and accumulator tables' versions)
+  uint64_t tag2 = 0;  // more of the same (elmk_run: whether the soil hydrology stage is in the step: its flag and the land unit)
   void drop()  // (nothing may still run it)
   {
     if (exec) (void)hipGraphExecDestroy(exec);
@@ -239,6 +240,9 @@ struct elmk_ctx {
   // active layer thickness (elmk_active_layer_*): the rows alt, altmax, altmax_lastyear [3][ld] in fp64, held exactly while the feature
   // is enabled
   DevBuf<double> alt_rows;
+  // soil hydrology (elmk_soil_hydrology_*): the ELMK_HYD_NROWS fp64 rows [row][ld], held exactly while the feature is enabled
+  DevBuf<double> hyd_rows;
+  bool hyd_params = false;  // elmk_soil_hydrology_set_params has been called since the enable
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
@@ -666,7 +670,8 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
   if (!ctx) return -1;
   size_t n = ctx->arena.bytes() + ctx->staging.bytes() + ctx->scratch.bytes() + ctx->snicar.bytes() + ctx->snowage.bytes() + ctx->d.bytes() +
              ctx->run.mem.bytes() + ctx->grid.mem.bytes() + ctx->ogrid.mem.bytes() + ctx->sw.czf.bytes() + ctx->run.rec.bytes() +
-             ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes() + ctx->alt_rows.bytes();
+             ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes() + ctx->alt_rows.bytes() +
+             ctx->hyd_rows.bytes();
   // the cell rows of gridded history entries (not the column rows) and the accumulators' values: whole rows of ld or cld doubles,
   // both multiples of 64, so every size is a multiple of 256 already
   for (const elmk_ctx::HistEntry& e : ctx->hist) n += e.cells ? e.acc.bytes() : 0;
@@ -1618,9 +1623,9 @@ int enqueue_stages(elmk_ctx* ctx, Stages L, double dt, hipEvent_t* marks = nullp
 
 // the stages captured once as a HIP graph (kernel nodes in one chain: the side-stream forks are issued in order on the
 // capturing stream) and replayed
-int run_graph(elmk_ctx* ctx, GraphSlot& g, Stages L, double dt, uint64_t tag)
+int run_graph(elmk_ctx* ctx, GraphSlot& g, Stages L, double dt, uint64_t tag, uint64_t tag2)
 {
-  if (!g.exec || g.dt != dt || g.stream != ctx->stream || g.tag != tag) {
+  if (!g.exec || g.dt != dt || g.stream != ctx->stream || g.tag != tag || g.tag2 != tag2) {
     if (g.exec) {
       // dt or the stream changed: the old executable may still be running its last launch.  (Best effort: a caller that
       // destroyed the old stream has synchronised it itself, and the error of waiting on it is not this call's.)
@@ -1652,15 +1657,16 @@ int run_graph(elmk_ctx* ctx, GraphSlot& g, Stages L, double dt, uint64_t tag)
     g.dt = dt;
     g.stream = ctx->stream;
     g.tag = tag;
+    g.tag2 = tag2;
   }
   HIPCHK(hipGraphLaunch(g.exec, ctx->stream));
   return ELMK_OK;
 }
 
 // a sequence elmk_set_graph applies to: replayed from its captured graph, or enqueued stage by stage
-int launch_sequence(elmk_ctx* ctx, GraphId id, Stages L, double dt, uint64_t tag = 0)
+int launch_sequence(elmk_ctx* ctx, GraphId id, Stages L, double dt, uint64_t tag = 0, uint64_t tag2 = 0)
 {
-  if (ctx->use_graph) return run_graph(ctx, ctx->graph[id], L, dt, tag);
+  if (ctx->use_graph) return run_graph(ctx, ctx->graph[id], L, dt, tag, tag2);
   return enqueue_stages(ctx, L, dt);
 }
 
@@ -1720,6 +1726,138 @@ int elmk_canopy_fluxes(elmk_ctx* ctx, double dt) { return launch_stage(ctx, TS7[
 int elmk_soil_temperature(elmk_ctx* ctx, double dt) { return launch_stage(ctx, SOIL_TEMPERATURE, dt); }
 int elmk_snow_hydrology(elmk_ctx* ctx, double dt) { return launch_stage(ctx, SNOW_HYDROLOGY, dt); }
 int elmk_surface_fluxes(elmk_ctx* ctx, double dt) { return launch_stage(ctx, SURFACE_FLUXES, dt); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// soil hydrology (k_soil_hydrology.hip; include/elmk.h "soil hydrology")
+// ---------------------------------------------------------------------------------------------------
+namespace {
+bool hyd_land(const elmk_ctx* ctx) { return ctx->h.land.ltype == istsoil || ctx->h.land.ltype == istcrop; }
+void hyd_launch(elmk_ctx* ctx, double dt)
+{
+  if (hyd_land(ctx)) launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, dt, ctx->stream);
+}
+}  // namespace
+
+extern "C" {
+
+int elmk_soil_hydrology_enable(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (ctx->hyd_rows) return invalid(ctx, "elmk_soil_hydrology_enable: already enabled");
+  if (int rc = refuse_capture(ctx, "elmk_soil_hydrology_enable: the stream is being captured")) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the stages of its flags' moment)
+  const size_t bytes = (size_t)ELMK_HYD_NROWS * (size_t)ctx->ld * sizeof(double);
+  if (hip_fail(ctx, ctx->hyd_rows.alloc(bytes), "hipMalloc(soil hydrology rows)")) return ELMK_E_NOMEM;
+  if (hip_fail(ctx, hipMemsetAsync(ctx->hyd_rows, 0, bytes, ctx->stream), "hipMemset(soil hydrology rows)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)ctx->hyd_rows.reset();
+    return ELMK_E_HIP;
+  }
+  ctx->hyd_params = false;
+  return ELMK_OK;
+}
+
+int elmk_soil_hydrology_set_params(elmk_ctx* ctx, const double* hksat, const double* wtfact, const double* h2osfc_thresh,
+                                   const double* k_wet, const double* rsub_top_max)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->hyd_rows) return invalid(ctx, "elmk_soil_hydrology_set_params: not enabled (elmk_soil_hydrology_enable)");
+  if (!hksat || !wtfact || !h2osfc_thresh || !k_wet || !rsub_top_max) return invalid(ctx, "elmk_soil_hydrology_set_params: null argument");
+  if (int rc = refuse_capture(ctx, "elmk_soil_hydrology_set_params: the stream is being captured")) return rc;
+  const size_t ld = (size_t)ctx->ld, n = (size_t)ctx->ncols;
+  if (n) {
+    HIPCHK(hipMemcpy2DAsync(ctx->hyd_rows + ELMK_HYD_HKSAT * ld, ld * 8, hksat, n * 8, n * 8, ELMK_HYD_NLAYER, hipMemcpyHostToDevice,
+                            ctx->stream));
+    const double* one[4] = {wtfact, h2osfc_thresh, k_wet, rsub_top_max};
+    for (int k = 0; k < 4; k++)
+      HIPCHK(hipMemcpyAsync(ctx->hyd_rows + (size_t)(ELMK_HYD_WTFACT + k) * ld, one[k], n * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->hyd_params = true;
+  return ELMK_OK;
+}
+
+int elmk_soil_hydrology_init(elmk_ctx* ctx, const double* zwt, const double* wa)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->hyd_rows) return invalid(ctx, "elmk_soil_hydrology_init: not enabled (elmk_soil_hydrology_enable)");
+  if (int rc = refuse_capture(ctx, "elmk_soil_hydrology_init: the stream is being captured")) return rc;
+  const size_t ld = (size_t)ctx->ld, n = (size_t)ctx->ncols;
+  std::vector<double> cold;
+  if (n && (!zwt || !wa)) {
+    // ELM's cold start: wa = 4000 mm, zwt = (zi[9] + 25) - wa / 0.2 / 1000 from the bottom of layer 9 (level 15 of zisoi, as stored)
+    cold.assign(n, 4000.0);
+    if (!zwt) {
+      const int es = store_size(ELMK_F64);
+      std::vector<unsigned char> raw(n * (size_t)es);
+      HIPCHK(hipMemcpyAsync(raw.data(), (const char*)ctx->fptr[ELMK_FIELD_zisoi] + (size_t)(ELMK_NLEVSNO + ELMK_HYD_NLAYER) * ld * es,
+                            raw.size(), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      std::vector<double> z(n);
+      for (size_t i = 0; i < n; i++) {
+        double zi9;
+        if (es == 4) {
+          float f;
+          memcpy(&f, &raw[i * 4], 4);
+          zi9 = (double)f;
+        } else {
+          memcpy(&zi9, &raw[i * 8], 8);
+        }
+        z[i] = (zi9 + 25.0) - 4000.0 / 0.2 / 1000.0;
+      }
+      HIPCHK(hipMemcpyAsync(ctx->hyd_rows + ELMK_HYD_ZWT * ld, z.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));  // (z leaves scope)
+    }
+  }
+  if (n && zwt) HIPCHK(hipMemcpyAsync(ctx->hyd_rows + ELMK_HYD_ZWT * ld, zwt, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (n) HIPCHK(hipMemcpyAsync(ctx->hyd_rows + ELMK_HYD_WA * ld, wa ? wa : cold.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+int elmk_soil_hydrology(elmk_ctx* ctx, double dt)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->hyd_rows) return invalid(ctx, "elmk_soil_hydrology: not enabled (elmk_soil_hydrology_enable)");
+  if (!ctx->hyd_params) return invalid(ctx, "elmk_soil_hydrology: the parameters are not set (elmk_soil_hydrology_set_params)");
+  if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_soil_hydrology: dt must be finite and positive");
+  if (int rc = enter_physics(ctx)) return rc;
+  hyd_launch(ctx, dt);
+  HIPCHK(hipGetLastError());
+  return ELMK_OK;
+}
+
+int elmk_soil_hydrology_read(elmk_ctx* ctx, int which, double* host, int64_t col0, int64_t n)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->hyd_rows) return invalid(ctx, "elmk_soil_hydrology_read: not enabled (elmk_soil_hydrology_enable)");
+  if (which < 0 || which >= ELMK_HYD_NROWS) return invalid(ctx, "elmk_soil_hydrology_read: unknown row");
+  if ((!host && n > 0) || col0 < 0 || n < 0 || col0 + n > ctx->ncols) return invalid(ctx, "elmk_soil_hydrology_read: bad column range");
+  if (int rc = refuse_capture(ctx, "elmk_soil_hydrology_read: the stream is being captured")) return rc;
+  if (n > 0)
+    HIPCHK(hipMemcpyAsync(host, ctx->hyd_rows + (size_t)which * (size_t)ctx->ld + (size_t)col0, (size_t)n * 8, hipMemcpyDeviceToHost,
+                          ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return ELMK_OK;
+}
+
+int elmk_soil_hydrology_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_soil_hydrology_clear: the stream is being captured")) return rc;
+  if (!ctx->hyd_rows) return ELMK_OK;
+  if (int rc = quiesce(ctx, false)) return rc;
+  HIPCHK(ctx->hyd_rows.reset());
+  ctx->hyd_params = false;
+  return ELMK_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // L2-level entries: the forcing-derived scalars handed in, as the reference's unit tests call the physics
 // (test/test_CanFlux.cc:285-340, test/test_BGFlux.cc:200-260) instead of the wrapper's derive_forc_* (atm_physics_impl.hh:246-272)
@@ -1914,6 +2052,10 @@ void run_aerosol(elmk_ctx* ctx, double)
     launch_aerosol_deposition_run(ctx->d, ctx->ncols, aer_series(ctx), ctx->run.table, ctx->run.cursor, ctx->stream);
 }
 void run_init_timestep(elmk_ctx* ctx, double) { launch_init_timestep(ctx->d, ctx->ncols, ctx->stream); }
+void run_soil_hydrology(elmk_ctx* ctx, double dt)
+{
+  if (ctx->run.flags & ELMK_RUN_HYDROLOGY) hyd_launch(ctx, dt);
+}
 void run_conservation(elmk_ctx* ctx, double dt)
 {
   const elmk_ctx::Run& R = ctx->run;
@@ -1941,11 +2083,12 @@ void run_next(elmk_ctx* ctx, double) { launch_run_next(ctx->run.cursor, ctx->str
 
 // one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
 // forcing, aerosol deposition (ELMK_RUN_AEROSOL: where the reference's hook sits, init_timestep_kokkos.cc:48-49), init_timestep,
-// advance_physics' stages, conservation -> ring row, flag summary -> ring row, active layer thickness (ELMK_RUN_ALT), accumulated fields,
+// advance_physics' stages, soil hydrology (ELMK_RUN_HYDROLOGY), conservation -> ring row, flag summary -> ring row, active layer thickness (ELMK_RUN_ALT), accumulated fields,
 // history, next row
 constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},   {run_forcing, nullptr}, {run_aerosol, nullptr},
                               {run_init_timestep, nullptr},
                               ADVANCE[0], ADVANCE[1], ADVANCE[2], ADVANCE[3], ADVANCE[4], ADVANCE[5], ADVANCE[6], ADVANCE[7],
+                              {run_soil_hydrology, nullptr},
                               {run_conservation, nullptr},   {run_flag_reduce, nullptr}, {run_active_layer, nullptr},
                               {run_accum, nullptr},          {run_history, nullptr},     {run_next, nullptr}};
 static_assert(sizeof ADVANCE / sizeof ADVANCE[0] == 8, "RUN_STEP holds every stage of ADVANCE");
@@ -2035,12 +2178,16 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   if (!ctx->snowage_set) return invalid(ctx, "elmk_run: the snow-age tables are not set (elmk_set_snow_age_tables)");
   if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
   if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
-  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL | ELMK_RUN_ALT))
+  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL | ELMK_RUN_ALT | ELMK_RUN_HYDROLOGY))
     return invalid(ctx, "elmk_run: unknown flags");
   if ((flags & ELMK_RUN_AEROSOL) && !ctx->aer.mem) return invalid(ctx, "elmk_run: ELMK_RUN_AEROSOL without an aerosol series (elmk_aerosol_reserve)");
   if ((flags & ELMK_RUN_ACCUM) && ctx->accum.empty()) return invalid(ctx, "elmk_run: ELMK_RUN_ACCUM without an accumulator entry (elmk_accum_add)");
   if ((flags & ELMK_RUN_ALT) && !ctx->alt_rows)
     return invalid(ctx, "elmk_run: ELMK_RUN_ALT without the active layer thickness enabled (elmk_active_layer_enable)");
+  if ((flags & ELMK_RUN_HYDROLOGY) && !ctx->hyd_rows)
+    return invalid(ctx, "elmk_run: ELMK_RUN_HYDROLOGY without the soil hydrology enabled (elmk_soil_hydrology_enable)");
+  if ((flags & ELMK_RUN_HYDROLOGY) && !ctx->hyd_params)
+    return invalid(ctx, "elmk_run: ELMK_RUN_HYDROLOGY without parameters (elmk_soil_hydrology_set_params)");
   const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   int lo = R.slots, hi = -1;
   unsigned months = 0;
@@ -2094,15 +2241,18 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.count++;
   R.last_buf = buf;
   R.last_nsteps = nsteps;
-  const uint64_t tag = (uint64_t)flags | ((uint64_t)(ds_topo(ctx) && ctx->ds.gmem) << 5) | ((uint64_t)ds_topo(ctx) << 6) |
+  // (the five flags below ELMK_RUN_HYDROLOGY: bits 5 .. 7 were taken before that flag existed)
+  const uint64_t tag = (uint64_t)(flags & 31) | ((uint64_t)(ds_topo(ctx) && ctx->ds.gmem) << 5) | ((uint64_t)ds_topo(ctx) << 6) |
                        ((uint64_t)cz << 7) | ((ctx->hist_version & 0xFFFFFFFull) << 8) |  // bits 8..35 and 36..63: the tables'
                        ((ctx->accum_version & 0xFFFFFFFull) << 36);                       // versions, 28 bits each
+  // the soil hydrology stage is in the captured step exactly when the run is flagged and the land unit is soil or crop
+  const uint64_t tag2 = (flags & ELMK_RUN_HYDROLOGY) ? 1u + (uint64_t)hyd_land(ctx) : 0u;
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;
   }
   int rc = ELMK_OK;
-  for (int s = 0; s < nsteps && rc == ELMK_OK; s++) rc = launch_sequence(ctx, GRAPH_RUN_STEP, RUN_STEP, dt, tag);
+  for (int s = 0; s < nsteps && rc == ELMK_OK; s++) rc = launch_sequence(ctx, GRAPH_RUN_STEP, RUN_STEP, dt, tag, tag2);
   HIPCHK(hipEventRecord(ctx->run_done[buf], ctx->stream));
   if (rc) return rc;
   if ((flags & ELMK_RUN_HISTORY) && !ctx->hist.empty()) mark_sampled(ctx, hist_tape_mask(ctx));
@@ -2793,6 +2943,7 @@ struct RstLayout {
   std::vector<elmk_restart_accum> acc;  // version 2: one per accumulator entry (nsteps filled in by the save)
   std::vector<elmk_restart_section> sec;
   std::vector<RstSrc> src;
+  bool hyd = false;  // version 4: the soil hydrology is enabled (the count word is present, the ZWT and WA sections last)
   bool alt = false;  // version 3: the active layer thickness is enabled (the accumulator-count word is present, three ALT sections last)
   size_t header_bytes = 0, total = 0;
 };
@@ -2825,8 +2976,13 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
     L.sec.push_back(elmk_restart_section{ELMK_RESTART_ALT, which, 1, ELMK_F64, ctx->ncols, 0, 0});
     L.src.push_back(RstSrc{(char*)(ctx->alt_rows + (size_t)which * (size_t)ctx->ld), ctx->ld, ELMK_F64, gcol0, false});
   }
-  // version 2 (with accumulator entries) and 3: their number in the word after the header, their table after the history entries
-  L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.acc.empty() && !L.alt ? 0 : 8 + L.acc.size() * sizeof(elmk_restart_accum)) +
+  L.hyd = (bool)ctx->hyd_rows;
+  for (int which = ELMK_HYD_ZWT; L.hyd && which <= ELMK_HYD_WA; which++) {
+    L.sec.push_back(elmk_restart_section{ELMK_RESTART_HYDROLOGY, which, 1, ELMK_F64, ctx->ncols, 0, 0});
+    L.src.push_back(RstSrc{(char*)(ctx->hyd_rows + (size_t)which * (size_t)ctx->ld), ctx->ld, ELMK_F64, gcol0, false});
+  }
+  // version 2 (with accumulator entries), 3 and 4: their number in the word after the header, their table after the history entries
+  L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.acc.empty() && !L.alt && !L.hyd ? 0 : 8 + L.acc.size() * sizeof(elmk_restart_accum)) +
                                 L.ent.size() * sizeof(elmk_restart_entry) + L.sec.size() * sizeof(elmk_restart_section),
                             RST_ALIGN);
   size_t off = L.header_bytes;
@@ -3017,7 +3173,7 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
   }
   elmk_restart_header H{};
   memcpy(H.magic, ELMK_RESTART_MAGIC, 8);
-  H.version = L.alt ? ELMK_RESTART_VERSION_ALT : L.acc.empty() ? ELMK_RESTART_VERSION : ELMK_RESTART_VERSION_ACCUM;
+  H.version = L.hyd ? ELMK_RESTART_VERSION_HYDROLOGY : L.alt ? ELMK_RESTART_VERSION_ALT : L.acc.empty() ? ELMK_RESTART_VERSION : ELMK_RESTART_VERSION_ACCUM;
   H.real_bytes = (uint32_t)store_size(ELMK_F64);
   H.schema_hash = schema_hash();
   H.gcol0 = gcol0;
@@ -3029,7 +3185,7 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
   H.total_bytes = L.total;
   memcpy(out, &H, sizeof H);
   unsigned char* p = out + sizeof H;
-  if (!L.acc.empty() || L.alt) {
+  if (!L.acc.empty() || L.alt || L.hyd) {
     const uint32_t word[2] = {(uint32_t)L.acc.size(), 0u};
     memcpy(p, word, 8);
     p += 8;
@@ -3059,7 +3215,8 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   elmk_restart_header H;
   if (bytes < (int64_t)sizeof H) return invalid(ctx, "elmk_restart_load: truncated image");
   memcpy(&H, in, sizeof H);
-  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || (H.version != ELMK_RESTART_VERSION && H.version != ELMK_RESTART_VERSION_ACCUM && H.version != ELMK_RESTART_VERSION_ALT))
+  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || (H.version != ELMK_RESTART_VERSION && H.version != ELMK_RESTART_VERSION_ACCUM && H.version != ELMK_RESTART_VERSION_ALT &&
+                                                 H.version != ELMK_RESTART_VERSION_HYDROLOGY))
     return invalid(ctx, "elmk_restart_load: not a restart image of this format version");
   if (H.header_bytes > (uint64_t)bytes || H.total_bytes > (uint64_t)bytes || H.header_bytes % 8 != 0)
     return invalid(ctx, "elmk_restart_load: truncated image");
@@ -3073,16 +3230,35 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   unsigned long long nacc[ELMK_ACCUM_MAX_ENTRIES] = {};
   const char* const acc_differs = "elmk_restart_load: the image's accumulator entries differ from the context's";
   // (version 3 is what a context with the active layer thickness saves and loads, with or without accumulator entries)
-  if ((H.version == ELMK_RESTART_VERSION_ALT) != L.alt)
+  // (version 4 is what a context with the soil hydrology saves and loads; whether it holds the ALT sections too is the section table's to say)
+  if ((H.version == ELMK_RESTART_VERSION_HYDROLOGY) != L.hyd)
+    return invalid(ctx, L.hyd ? "elmk_restart_load: the soil hydrology is enabled and the image holds none (version 1 to 3)"
+                              : "elmk_restart_load: a version-4 image needs the soil hydrology enabled (elmk_soil_hydrology_enable)");
+  if (!L.hyd && (H.version == ELMK_RESTART_VERSION_ALT) != L.alt)
     return invalid(ctx, L.alt ? "elmk_restart_load: the active layer thickness is enabled and the image holds none (version 1 or 2)"
                               : "elmk_restart_load: a version-3 image needs the active layer thickness enabled (elmk_active_layer_enable)");
-  if (!L.alt && (H.version == ELMK_RESTART_VERSION_ACCUM) != !L.acc.empty()) return invalid(ctx, acc_differs);
-  if (!L.acc.empty() || L.alt) {
+  if (!L.alt && !L.hyd && (H.version == ELMK_RESTART_VERSION_ACCUM) != !L.acc.empty()) return invalid(ctx, acc_differs);
+  if (!L.acc.empty() || L.alt || L.hyd) {
     uint32_t word[2];
     if (H.header_bytes < sizeof H + 8) return invalid(ctx, "elmk_restart_load: truncated image");
     memcpy(word, p, 8);
     if (word[0] != L.acc.size() || word[1] != 0u) return invalid(ctx, acc_differs);
     p += 8;
+  }
+  if (L.hyd) {
+    // a version-4 image says in its section table whether it holds the active layer rows too: the enabled features must match
+    const size_t at = (size_t)(p - in) + (size_t)H.nentries * sizeof(elmk_restart_entry) + L.acc.size() * sizeof(elmk_restart_accum);
+    if (at > H.header_bytes || (H.header_bytes - at) / sizeof(elmk_restart_section) < H.nsections)
+      return invalid(ctx, "elmk_restart_load: truncated image");
+    bool alt = false;
+    for (uint32_t k = 0; k < H.nsections; k++) {
+      elmk_restart_section S;
+      memcpy(&S, in + at + (size_t)k * sizeof S, sizeof S);
+      alt = alt || S.kind == ELMK_RESTART_ALT;
+    }
+    if (alt != L.alt)
+      return invalid(ctx, L.alt ? "elmk_restart_load: the active layer thickness is enabled and the version-4 image holds no such rows"
+                                : "elmk_restart_load: the version-4 image holds active layer rows and the feature is not enabled (elmk_active_layer_enable)");
   }
   if (H.nentries != L.ent.size() || H.nsections != L.sec.size() || H.header_bytes != L.header_bytes || H.total_bytes != L.total)
     return invalid(ctx, "elmk_restart_load: the image's history entries differ from the context's");

@@ -1,0 +1,497 @@
+"""Column soil hydrology on the host (include/elmk.h "soil hydrology"; ELM v1's SoilHydrologyMod in the CLM4.5 formulation): the
+restatement of the stage the device performs (k_soil_hydrology.hip), one column at a time in plain Python floats, so that every
+operation is one IEEE fp64 operation in the order of the header and nothing is fused.  The reference has no soil hydrology; the header's
+text is the specification and `step` is its host truth.
+
+    S.soil_hydrology_enable()
+    S.soil_hydrology_set_params(hksat_from_texture(...), wtfact, h2osfc_thresh(sigma), k_wet(slope), rsub_top_max(slope))
+    S.soil_hydrology_init()                         # ELM's cold start: wa = 4000 mm, zwt = cold_start_zwt(zisoi)
+    advance_physics(S, dt); S.soil_hydrology(dt)    # or S.run(dt, steps, RUN_HYDROLOGY)
+
+pow, exp and erf are math.pow / math.exp / math.erf per element (glibc), which the device's elmk_pow / elmk_exp restate bit for bit;
+np.power and np.exp are not guaranteed to.  min(a, b) and max(a, b) are (b < a ? b : a) and (a < b ? b : a), written out.
+"""
+import math
+
+import numpy as np
+
+NLEVSNO = 5
+N = 10  # hydrologically active soil layers: layer j is level 5 + j of h2osoi_liq, h2osoi_ice, dz, zsoi; its bottom level 6 + j of zisoi
+DENH2O, DENICE, E_ICE, SMPMIN, WATMIN = 1000.0, 917.0, 6.0, -1.0e8, 0.01
+PC, MU, FFF_S, FFF_D, AQUIFER_MAX, ROUS_MIN = 0.4, 0.13889, 0.5, 2.5, 5000.0, 0.02
+WA_COLD = 4000.0
+
+# the rows of the feature (ELMK_HYD_*)
+ZWT, WA, HKSAT, WTFACT, H2OSFC_THRESH, K_WET, RSUB_TOP_MAX = 0, 1, 2, 12, 13, 14, 15
+QFLX_SURF, QFLX_INFL, QFLX_H2OSFC_SURF, QFLX_DRAIN, QFLX_RSUB_SAT, QCHARGE, FSAT = range(16, 23)
+NROWS = 23
+DIAGNOSTICS = ("qflx_surf", "qflx_infl", "qflx_h2osfc_surf", "qflx_drain", "qflx_rsub_sat", "qcharge", "fsat")
+
+# the state fields the stage reads, and those it writes
+READS = ("h2osoi_liq", "h2osoi_ice", "dz", "zsoi", "zisoi", "watsat", "sucsat", "bsw", "h2osfc", "frac_h2osfc", "frac_sno_eff", "snl",
+         "qflx_top_soil", "qflx_rootsoi", "qflx_evap_grnd", "qflx_ev_soil", "qflx_ev_h2osfc", "qflx_dew_grnd", "qflx_dew_snow",
+         "qflx_sub_snow")
+WRITES = ("h2osoi_liq", "h2osoi_ice", "h2osoi_vol", "h2osfc")
+
+_NAN = float(np.float64(np.nan))
+_INF = float("inf")
+
+
+def _min(a, b):
+    return b if b < a else a
+
+
+def _max(a, b):
+    return b if a < b else a
+
+
+def _div(a, b):
+    """IEEE a / b (Python raises where IEEE gives an infinity or a NaN)."""
+    if b != 0.0:
+        return a / b
+    if a != a or a == 0.0:
+        return _NAN
+    return math.copysign(_INF, a) * math.copysign(1.0, b)
+
+
+def _pow(x, y):
+    try:
+        return math.pow(x, y)
+    except ValueError:
+        return _NAN if x < 0.0 else _INF  # a negative base with a fractional exponent; 0 to a negative power
+    except OverflowError:
+        return _INF
+
+
+def _exp(x):
+    try:
+        return math.exp(x)
+    except OverflowError:
+        return _INF
+
+
+def _canon(x):
+    return _NAN if x != x else x
+
+
+def cold_start_zwt(zi9):
+    """ELM's cold start of the water table from the bottom of layer 9 (level 15 of zisoi): zi + 25 - wa / 0.2 / 1000 with wa = 4000 mm,
+    that is zi + 5 m up to rounding."""
+    return (zi9 + 25.0) - WA_COLD / 0.2 / 1000.0
+
+
+def _sy(zwt, watsat, sucsat, bsw):
+    return _max(ROUS_MIN, watsat * (1.0 - _pow(1.0 + _div(1.0e3 * zwt, sucsat), _div(-1.0, bsw))))
+
+
+def _jwt(zwt, zi):
+    for j in range(N):
+        if zwt <= zi[j + 1]:
+            return j
+    return N
+
+
+def column(c, dt, hit=None):
+    """One column: c is a dict of Python floats / lists (see step); returns the dict of outputs.  hit: a set that collects the
+    names of the branches taken (the tests assert coverage from it)."""
+    def mark(name):
+        if hit is not None:
+            hit.add(name)
+
+    liq, ice, dz, z = list(c["liq"]), list(c["ice"]), c["dz"], c["z"]
+    zi = c["zi"]  # zi[0] = the surface, zi[j + 1] = the bottom of layer j
+    watsat, sucsat, bsw, hksat, rootsoi = c["watsat"], c["sucsat"], c["bsw"], c["hksat"], c["rootsoi"]
+    zwt, wa, h2osfc = c["zwt"], c["wa"], c["h2osfc"]
+    frac_h2osfc, fsno, snl, top = c["frac_h2osfc"], c["fsno"], c["snl"], c["qflx_top_soil"]
+
+    # A. ice and porosity
+    effpor, icefrac, vol_liq, vol = [0.0] * N, [0.0] * N, [0.0] * N, [0.0] * N
+    zmm, dzmm, zimm = [0.0] * (N + 1), [0.0] * (N + 1), [v * 1.0e3 for v in zi]
+    for j in range(N):
+        vol_ice = _min(watsat[j], _div(ice[j], dz[j] * DENICE))
+        effpor[j] = _max(0.01, watsat[j] - vol_ice)
+        icefrac[j] = _min(1.0, _div(vol_ice, watsat[j]))
+        vol_liq[j] = _div(_max(liq[j], 1.0e-6), dz[j] * DENH2O)
+        vol[j] = _div(liq[j], dz[j] * DENH2O) + _div(ice[j], dz[j] * DENICE)
+        zmm[j] = z[j] * 1.0e3
+        dzmm[j] = dz[j] * 1.0e3
+
+    # B. surface runoff
+    fsat = c["wtfact"] * _exp(-0.5 * FFF_S * zwt)
+    qflx_surf = fsat * top
+
+    # C. infiltration and h2osfc
+    qevap = c["qflx_evap_grnd"] if snl == 0 else c["qflx_ev_soil"]
+    q_in_soil = (1.0 - frac_h2osfc) * (top - qflx_surf)
+    q_in_soil = q_in_soil - (1.0 - fsno - frac_h2osfc) * qevap
+    q_in_sfc = frac_h2osfc * (top - qflx_surf)
+    q_in_sfc = q_in_sfc - frac_h2osfc * c["qflx_ev_h2osfc"]
+    m = _pow(10.0, -E_ICE * icefrac[0]) * hksat[0]
+    m = _min(m, _pow(10.0, -E_ICE * icefrac[1]) * hksat[1])
+    m = _min(m, _pow(10.0, -E_ICE * icefrac[2]) * hksat[2])
+    qinmax = (1.0 - fsat) * m
+    excess = _max(0.0, q_in_soil - (1.0 - frac_h2osfc) * qinmax)
+    if excess > 0.0:
+        mark("infiltration_excess")
+    infl = q_in_soil - excess
+    q_in_sfc = q_in_sfc + excess
+    frac_infclust = 0.0 if frac_h2osfc <= PC else _pow(frac_h2osfc - PC, MU)
+    thresh = c["h2osfc_thresh"]
+    if h2osfc >= thresh:
+        mark("h2osfc_above_threshold")
+        qs = c["k_wet"] * frac_infclust * (h2osfc - thresh)
+        qs = _min(qs, _div(h2osfc - thresh, dt))
+    else:
+        mark("h2osfc_below_threshold")
+        qs = 0.0
+    if qs < 1.0e-8:
+        qs = 0.0
+    else:
+        mark("h2osfc_runoff")
+    h2osfc = h2osfc + (q_in_sfc - qs) * dt
+    if h2osfc < 0.0:
+        mark("h2osfc_negative")
+        infl = infl + _div(h2osfc, dt)
+        h2osfc = 0.0
+        drain_sfc = 0.0
+    else:
+        drain_sfc = _min(frac_h2osfc * qinmax, _div(h2osfc, dt))
+    h2osfc = h2osfc - drain_sfc * dt
+    infl = infl + drain_sfc
+
+    # D. soil water
+    jwt = _jwt(zwt, zi)
+    mark("jwt_0" if jwt == 0 else ("jwt_N" if jwt == N else "jwt_mid"))
+    zwtmm = zwt * 1.0e3
+    zq = [0.0] * (N + 1)
+    for j in range(N):
+        b1 = 1.0 - _div(1.0, bsw[j])
+        if zwtmm <= zimm[j]:
+            ve = watsat[j]
+        elif zwtmm < zimm[j + 1]:
+            t0 = _pow(_div(sucsat[j] + zwtmm - zimm[j], sucsat[j]), b1)
+            v1 = _div(_div(-sucsat[j] * watsat[j], b1), zwtmm - zimm[j]) * (1.0 - t0)
+            ve = _div(v1 * (zwtmm - zimm[j]) + watsat[j] * (zimm[j + 1] - zwtmm), zimm[j + 1] - zimm[j])
+        else:
+            ti = _pow(_div(sucsat[j] + zwtmm - zimm[j + 1], sucsat[j]), b1)
+            t0 = _pow(_div(sucsat[j] + zwtmm - zimm[j], sucsat[j]), b1)
+            ve = _div(_div(-sucsat[j] * watsat[j], b1), zimm[j + 1] - zimm[j]) * (ti - t0)
+        ve = _min(watsat[j], _max(ve, 0.0))
+        zq[j] = _max(SMPMIN, -sucsat[j] * _pow(_max(_div(ve, watsat[j]), 0.01), -bsw[j]))
+    L = N - 1
+    if jwt == N:
+        b1 = 1.0 - _div(1.0, bsw[L])
+        t0 = _pow(_div(sucsat[L] + zwtmm - zimm[N], sucsat[L]), b1)
+        ve = _div(_div(-sucsat[L] * watsat[L], b1), zwtmm - zimm[N]) * (1.0 - t0)
+        ve = _min(watsat[L], _max(ve, 0.0))
+        zq[N] = _max(SMPMIN, -sucsat[L] * _pow(_max(_div(ve, watsat[L]), 0.01), -bsw[L]))
+        zmm[N] = 0.5 * (zwtmm + zmm[L])
+        dzmm[N] = zwtmm - zimm[N]
+    hk, dhkdw, imped, smp, dsmpdw = [0.0] * N, [0.0] * N, [0.0] * N, [0.0] * N, [0.0] * N
+    for j in range(N):
+        jp = _min(N - 1, j + 1)
+        s1 = _min(1.0, _div(0.5 * (vol[j] + vol[jp]), 0.5 * (watsat[j] + watsat[jp])))
+        s2 = hksat[j] * _pow(s1, 2.0 * bsw[j] + 2.0)
+        imped[j] = _pow(10.0, -E_ICE * (0.5 * (icefrac[j] + icefrac[jp])))
+        if imped[j] < 1.0:
+            mark("imped")
+        hk[j] = imped[j] * s1 * s2
+        dhkdw[j] = imped[j] * (2.0 * bsw[j] + 3.0) * s2 * _div(1.0, watsat[j] + watsat[jp])
+        sn = _min(1.0, _max(_div(vol_liq[j], watsat[j]), 0.01))
+        smp[j] = _max(SMPMIN, -sucsat[j] * _pow(sn, -bsw[j]))
+        dsmpdw[j] = _div(-bsw[j] * smp[j], sn * watsat[j])
+    # the interfaces: q[i] between nodes i and i + 1; interface N - 1 is towards the aquifer node
+    q, dq1, dq2 = [0.0] * N, [0.0] * N, [0.0] * N
+    for i in range(N - 1):
+        den = zmm[i + 1] - zmm[i]
+        num = (smp[i + 1] - smp[i]) - (zq[i + 1] - zq[i])
+        q[i] = _div(-hk[i] * num, den)
+        dq1[i] = _div(-(-hk[i] * dsmpdw[i] + num * dhkdw[i]), den)
+        dq2[i] = _div(-(hk[i] * dsmpdw[i + 1] + num * dhkdw[i]), den)
+    if jwt == N:
+        sn1 = _min(1.0, _max(_div(vol[L], watsat[L]), 0.01))
+        smp1 = _max(SMPMIN, -sucsat[L] * _pow(sn1, -bsw[L]))
+        dsmpdw1 = _div(-bsw[L] * smp1, sn1 * watsat[L])
+        den = zmm[N] - zmm[L]
+        num = (smp1 - smp[L]) - (zq[N] - zq[L])
+        q[L] = _div(-hk[L] * num, den)
+        dq1[L] = _div(-(-hk[L] * dsmpdw[L] + num * dhkdw[L]), den)
+        dq2[L] = _div(-(hk[L] * dsmpdw1 + num * dhkdw[L]), den)
+    # the rows
+    a, b, cc, r = [0.0] * (N + 1), [0.0] * (N + 1), [0.0] * (N + 1), [0.0] * (N + 1)
+    r[0] = infl - q[0] - rootsoi[0]
+    b[0] = _div(dzmm[0], dt) + dq1[0]
+    cc[0] = dq2[0]
+    for j in range(1, N):
+        r[j] = q[j - 1] - q[j] - rootsoi[j]
+        a[j] = -dq1[j - 1]
+        b[j] = _div(dzmm[j], dt) - dq2[j - 1] + dq1[j]
+        cc[j] = dq2[j]
+    if jwt == N:
+        r[N] = q[L]
+        a[N] = -dq1[L]
+        b[N] = _div(dzmm[N], dt) - dq2[L]
+    else:
+        b[N] = 1.0
+    # the Thomas algorithm
+    gam, u = [0.0] * (N + 1), [0.0] * (N + 1)
+    bet = b[0]
+    u[0] = _div(r[0], bet)
+    for j in range(1, N + 1):
+        gam[j] = _div(cc[j - 1], bet)
+        bet = b[j] - a[j] * gam[j]
+        u[j] = _div(r[j] - a[j] * u[j - 1], bet)
+    for j in range(N - 1, -1, -1):
+        u[j] = u[j] - gam[j + 1] * u[j + 1]
+    for j in range(N):
+        liq[j] = liq[j] + u[j] * dzmm[j]
+    # recharge
+    if jwt == N:
+        qcharge = _div(u[N] * dzmm[N], dt)
+    else:
+        k, up = jwt, _max(0, jwt - 1)
+        sn = _max(_div(vol[k], watsat[k]), 0.01)
+        ka = imped[k] * hksat[k] * _pow(_min(1.0, sn), 2.0 * bsw[k] + 3.0)
+        wh = smp[up] - zq[up]
+        if jwt == 0:
+            qcharge = _div(-ka * (0.0 - wh), (zwt + 1.0e-3) * 1000.0)
+        else:
+            qcharge = _div(-ka * (0.0 - wh), (zwt - z[jwt - 1]) * 1000.0 * 2.0)
+        qcharge = _max(_div(-10.0, dt), qcharge)
+        qcharge = _min(_div(10.0, dt), qcharge)
+
+    # E. water table
+    if jwt == N:
+        rous = _sy(zwt, watsat[L], sucsat[L], bsw[L])
+        wa = wa + qcharge * dt
+        zwt = zwt - _div(_div(qcharge * dt, 1000.0), rous)
+    else:
+        rous = _sy(zwt, watsat[L], sucsat[L], bsw[L])
+        qt = qcharge * dt
+        if qt > 0.0:
+            mark("table_rises")
+            for j in range(jwt, -1, -1):
+                sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
+                ql = _max(0.0, _min(qt, sy * (zwt - zi[j]) * 1.0e3))
+                zwt = zwt - _div(_div(ql, sy), 1000.0)
+                qt = qt - ql
+                if qt <= 0.0:
+                    break
+        else:
+            mark("table_falls")
+            for j in range(jwt, N):
+                sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
+                ql = _min(0.0, _max(qt, -(sy * (zi[j + 1] - zwt) * 1.0e3)))
+                qt = qt - ql
+                if qt >= 0.0:
+                    zwt = zwt - _div(_div(ql, sy), 1000.0)
+                    break
+                zwt = zi[j + 1]
+            if qt < 0.0:
+                zwt = zwt - _div(_div(qt, 1000.0), rous)
+    jwt = _jwt(zwt, zi)
+
+    # F. drainage
+    rous = _sy(zwt, watsat[L], sucsat[L], bsw[L])
+    si, sd = 0.0, 0.0
+    for j in range(_max(jwt - 1, 0), N):
+        si = si + icefrac[j] * dzmm[j]
+        sd = sd + dzmm[j]
+    imp = _pow(10.0, -E_ICE * _div(si, sd))
+    rsub_top = imp * c["rsub_top_max"] * _exp(-FFF_D * zwt)
+    rt = -rsub_top * dt
+    if jwt == N:
+        mark("drain_aquifer")
+        wa = wa + rt
+        zwt = zwt + _div(_div(rt, 1000.0), rous)
+        liq[L] = liq[L] + _max(0.0, wa - AQUIFER_MAX)
+        wa = _min(wa, AQUIFER_MAX)
+    else:
+        mark("drain_soil")
+        for j in range(jwt, N):
+            sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
+            ql = _min(0.0, _max(rt, -(sy * (zi[j + 1] - zwt) * 1.0e3)))
+            liq[j] = liq[j] + ql
+            rt = rt - ql
+            if rt >= 0.0:
+                zwt = zwt - _div(_div(ql, sy), 1000.0)
+                break
+            zwt = zi[j + 1]
+        zwt = zwt - _div(_div(rt, 1000.0), rous)
+        wa = wa + rt
+    zwt = 0.0 if zwt < 0.0 else zwt
+    zwt = 80.0 if 80.0 < zwt else zwt
+    for j in range(N - 1, 0, -1):
+        cap = effpor[j] * dzmm[j]
+        xs = _max(liq[j] - cap, 0.0)
+        if xs > 0.0:
+            mark("excess_up")
+        liq[j] = _min(cap, liq[j])
+        liq[j - 1] = liq[j - 1] + xs
+    xs1 = _max(_max(liq[0], 0.0) - _max(0.0, watsat[0] * dzmm[0] - ice[0]), 0.0)
+    if xs1 > 0.0:
+        mark("excess_to_h2osfc")
+    liq[0] = liq[0] - xs1
+    h2osfc = h2osfc + xs1
+    rsub_sat = 0.0
+    for j in range(N - 1):
+        if liq[j] < WATMIN:
+            mark("watmin_push_down")
+            xs = WATMIN - liq[j]
+            liq[j] = liq[j] + xs
+            liq[j + 1] = liq[j + 1] - xs
+    if liq[L] < WATMIN:
+        mark("watmin_search")
+        xs = WATMIN - liq[L]
+        for i in range(N - 2, -1, -1):
+            if xs > 0.0:
+                avail = _max(liq[i] - WATMIN - xs, 0.0)
+                take = _min(avail, xs)
+                liq[L] = liq[L] + take
+                liq[i] = liq[i] - take
+                xs = _max(xs - take, 0.0)
+        if xs > 0.0:
+            mark("watmin_remainder")
+        liq[L] = liq[L] + xs
+        rsub_top = rsub_top - _div(xs, dt)
+    qflx_drain = rsub_sat + rsub_top
+
+    # G. top-layer dew and sublimation
+    if snl == 0:
+        mark("snl_0")
+        liq[0] = liq[0] + (1.0 - frac_h2osfc) * c["qflx_dew_grnd"] * dt
+        ice[0] = ice[0] + (1.0 - frac_h2osfc) * c["qflx_dew_snow"] * dt
+        if c["qflx_sub_snow"] * dt > ice[0]:
+            ice[0] = 0.0
+        else:
+            ice[0] = ice[0] - (1.0 - frac_h2osfc) * c["qflx_sub_snow"] * dt
+    else:
+        mark("snl_pos")
+
+    # H. stores
+    volnew = [_div(liq[j], dz[j] * DENH2O) + _div(ice[j], dz[j] * DENICE) for j in range(N)]
+    return {"liq": liq, "ice0": ice[0], "vol": volnew, "h2osfc": h2osfc, "zwt": _canon(zwt), "wa": _canon(wa),
+            "qflx_surf": _canon(qflx_surf), "qflx_infl": _canon(infl), "qflx_h2osfc_surf": _canon(qs), "qflx_drain": _canon(qflx_drain),
+            "qflx_rsub_sat": _canon(rsub_sat), "qcharge": _canon(qcharge), "fsat": _canon(fsat)}
+
+
+def step(fields, rows, dt, hit=None, stored=None):
+    """One elmk_soil_hydrology on the host.
+
+    fields: a dict of the state fields READS and h2osoi_vol as S[name] downloads them ([n] or [n, nlev], any float dtype: widened to
+    fp64 as stored); rows: float64 [NROWS, n], the rows of the feature (ZWT .. FSAT).  Returns (out, rows_out): out holds the fields
+    WRITES in the dtype and shape of the inputs (fp64 results rounded once to the stored type), rows_out the rows after the step
+    (parameters unchanged, diagnostics overwritten).  Nothing is changed in place.  hit: see column().  stored: the element type the
+    state is stored in where the inputs do not show it - np.float32 for downloads of the fp32-state build, which come widened to fp64:
+    the results are rounded to it before they take the inputs' dtype."""
+    dt = float(dt)
+    f = {k: np.asarray(fields[k]) for k in READS + ("h2osoi_vol",)}
+    n = f["h2osfc"].shape[0]
+    rows = np.asarray(rows, dtype=np.float64)
+    assert rows.shape == (NROWS, n)
+    w = {k: (v.astype(np.float64) if v.dtype.kind == "f" else v) for k, v in f.items()}
+    out = {k: np.array(f[k]) for k in WRITES}
+    res = {k: np.array(w[k], dtype=np.float64) for k in WRITES}
+    rows_out = rows.copy()
+    s0, s1 = NLEVSNO, NLEVSNO + N
+    for i in range(n):
+        c = {"liq": w["h2osoi_liq"][i, s0:s1].tolist(), "ice": w["h2osoi_ice"][i, s0:s1].tolist(), "dz": w["dz"][i, s0:s1].tolist(),
+             "z": w["zsoi"][i, s0:s1].tolist(), "zi": w["zisoi"][i, s0:s1 + 1].tolist(), "watsat": w["watsat"][i, :N].tolist(),
+             "sucsat": w["sucsat"][i, :N].tolist(), "bsw": w["bsw"][i, :N].tolist(), "rootsoi": w["qflx_rootsoi"][i, :N].tolist(),
+             "hksat": rows[HKSAT:HKSAT + N, i].tolist(), "snl": int(w["snl"][i]), "fsno": float(w["frac_sno_eff"][i])}
+        for k in ("h2osfc", "frac_h2osfc", "qflx_top_soil", "qflx_evap_grnd", "qflx_ev_soil", "qflx_ev_h2osfc", "qflx_dew_grnd",
+                  "qflx_dew_snow", "qflx_sub_snow"):
+            c[k] = float(w[k][i])
+        c["zwt"], c["wa"] = float(rows[ZWT, i]), float(rows[WA, i])
+        c["wtfact"], c["h2osfc_thresh"] = float(rows[WTFACT, i]), float(rows[H2OSFC_THRESH, i])
+        c["k_wet"], c["rsub_top_max"] = float(rows[K_WET, i]), float(rows[RSUB_TOP_MAX, i])
+        o = column(c, dt, hit)
+        res["h2osoi_liq"][i, s0:s1] = o["liq"]
+        res["h2osoi_ice"][i, s0] = o["ice0"]
+        res["h2osoi_vol"][i, :N] = o["vol"]
+        res["h2osfc"][i] = o["h2osfc"]
+        rows_out[ZWT, i], rows_out[WA, i] = o["zwt"], o["wa"]
+        for d, name in enumerate(DIAGNOSTICS):
+            rows_out[QFLX_SURF + d, i] = o[name]
+    with np.errstate(all="ignore"):
+        # untouched levels keep their stored bits; the written ones are rounded once to the stored type
+        def rnd(a, like):
+            return (a if stored is None else a.astype(stored)).astype(like.dtype)
+
+        out["h2osoi_liq"][:, s0:s1] = rnd(res["h2osoi_liq"][:, s0:s1], out["h2osoi_liq"])
+        out["h2osoi_ice"][:, s0] = rnd(res["h2osoi_ice"][:, s0], out["h2osoi_ice"])
+        out["h2osoi_vol"][:, :N] = rnd(res["h2osoi_vol"][:, :N], out["h2osoi_vol"])
+        out["h2osfc"][:] = rnd(res["h2osfc"], out["h2osfc"])
+    return out, rows_out
+
+
+# ---- parameters -------------------------------------------------------------------------------------------------------------------
+def hksat_from_texture(pct_sand, pct_clay, organic, zsoi, organic_max=130.0):
+    """ELM's saturated hydraulic conductivity (mm/s): the Cosby pedotransfer for the mineral part mixed with the organic part above
+    the percolation threshold (iniTimeConst).  pct_sand, pct_clay, organic (kg/m3), zsoi (m): [n, 10] or broadcastable; returns
+    float64 [10, n], the layout of soil_hydrology_set_params."""
+    sand, clay, om, z = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64) for a in (pct_sand, pct_clay, organic, zsoi)))
+    shape = sand.shape
+    out = np.empty(sand.size)
+    pcalpha, pcbeta = 0.5, 0.139
+    for i, (s, _c, o, zz) in enumerate(zip(sand.reshape(-1), clay.reshape(-1), om.reshape(-1), z.reshape(-1))):
+        s, o, zz = float(s), float(o), float(zz)
+        om_frac = _min(o / organic_max, 1.0)
+        xksat = 0.0070556 * _pow(10.0, -0.884 + 0.0153 * s)
+        om_hksat = _max(0.28 - 0.2799 * zz / 0.5, 0.0001)
+        if om_frac > pcalpha:
+            perc_norm = _pow(1.0 - pcalpha, -pcbeta)
+            perc_frac = perc_norm * _pow(om_frac - pcalpha, pcbeta)
+        else:
+            perc_frac = 0.0
+        uncon_frac = (1.0 - om_frac) + (1.0 - perc_frac) * om_frac
+        if om_frac < 1.0:
+            uncon_hksat = uncon_frac / ((1.0 - om_frac) / xksat + ((1.0 - perc_frac) * om_frac) / om_hksat)
+        else:
+            uncon_hksat = 0.0
+        out[i] = uncon_frac * uncon_hksat + (perc_frac * om_frac) * om_hksat
+    out = out.reshape(shape)
+    return np.ascontiguousarray(out.T if out.ndim == 2 else out.reshape(N, -1))
+
+
+def h2osfc_thresh(micro_sigma):
+    """ELM's surface-water threshold (mm) from the microtopography's standard deviation (m): four Newton iterations for the depth d
+    at which the inundated fraction reaches pc, then the mean water depth over that fraction."""
+    sig = np.asarray(micro_sigma, dtype=np.float64)
+    out = np.empty(sig.size)
+    for i, s in enumerate(sig.reshape(-1)):
+        s = float(s)
+        if s > 1.0e-6:
+            d = 0.0
+            for _ in range(4):
+                fd = 0.5 * (1.0 + math.erf(d / (s * math.sqrt(2.0)))) - PC
+                dfdd = math.exp(-d * d / (2.0 * s * s)) / (s * math.sqrt(2.0 * math.pi))
+                d = d - fd / dfdd
+            out[i] = 0.5 * d * (1.0 + math.erf(d / (s * math.sqrt(2.0)))) + s / math.sqrt(2.0 * math.pi) * math.exp(-d * d / (2.0 * s * s))
+            out[i] = 1.0e3 * out[i]
+        else:
+            out[i] = 0.0
+    return out.reshape(sig.shape)
+
+
+def k_wet(topo_slope_deg):
+    """sin of the slope (given in degrees, as ELM's surface data holds it)."""
+    a = np.asarray(topo_slope_deg, dtype=np.float64)
+    return np.array([math.sin(float(v) * (math.pi / 180.0)) for v in a.reshape(-1)]).reshape(a.shape)
+
+
+def rsub_top_max(topo_slope_deg):
+    """The maximum baseflow rate (mm/s): 10 sin(slope)."""
+    return 10.0 * k_wet(topo_slope_deg)
+
+
+def water_balance_error(begwb, endwb, wa_beg, wa_end, forc_rain, forc_snow, qflx_evap_tot, qflx_snwcp_ice, qflx_surf, qflx_h2osfc_surf,
+                        qflx_drain, dt):
+    """The reference's column_water_balance_error with the aquifer in both water masses and
+    hydrology_source_sink = qflx_surf + qflx_h2osfc_surf + qflx_drain in place of its hardwired 0:
+    errh2o = (endwb + wa_end) - (begwb + wa_beg) - (forc_rain + forc_snow - source_sink - qflx_evap_tot - qflx_snwcp_ice) * dt."""
+    a = [np.asarray(v, dtype=np.float64) for v in (begwb, endwb, wa_beg, wa_end, forc_rain, forc_snow, qflx_evap_tot, qflx_snwcp_ice,
+                                                   qflx_surf, qflx_h2osfc_surf, qflx_drain)]
+    begwb, endwb, wa_beg, wa_end, rain, snow, evap, snwcp, surf, h2osfc_surf, drain = a
+    source_sink = surf + h2osfc_surf + drain
+    return (endwb + wa_end) - (begwb + wa_beg) - (rain + snow - source_sink - evap - snwcp) * float(dt)

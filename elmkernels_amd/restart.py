@@ -18,6 +18,10 @@ A context with the active layer thickness enabled (elmk_active_layer_enable) sav
 accumulator-count word always present (0 without entries) and, last, three column sections of kind ALT_SECTION (id 0, 1, 2: alt,
 altmax, altmax_lastyear; one level, F64).  build writes version 3 exactly when it is given such sections; merge and slice carry them
 as they carry every column section.
+
+A context with the soil hydrology enabled (elmk_soil_hydrology_enable) saves a version-4 image: as version 3, with the ALT sections
+present only when that feature is enabled too, and last two column sections of kind HYDROLOGY_SECTION (id 0, 1: ZWT, WA; one level,
+F64).  build writes version 4 exactly when it is given such sections.
 """
 import numpy as np
 
@@ -25,7 +29,8 @@ MAGIC = b"ELMKRST\0"
 VERSION = 1  # of an image without accumulator entries
 VERSION_ACCUM = 2  # of an image with accumulator entries
 VERSION_ALT = 3  # of an image with the active layer thickness rows
-FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION = 0, 1, 2, 3, 4  # ELMK_RESTART_*
+VERSION_HYDROLOGY = 4  # of an image with the soil hydrology rows ZWT and WA
+FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION, HYDROLOGY_SECTION = 0, 1, 2, 3, 4, 5  # ELMK_RESTART_*
 ALIGN = 256
 HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), ("schema_hash", "<u8"), ("gcol0", "<i8"),
                    ("ncols", "<i8"), ("tape_count", "<u8", (4,)), ("nentries", "<u4"), ("nsections", "<u4"),
@@ -91,12 +96,12 @@ def parse(image):
     if img.size < HEADER.itemsize:
         raise RestartError("truncated image")
     h = np.frombuffer(img[:HEADER.itemsize].tobytes(), HEADER)[0]
-    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) not in (VERSION, VERSION_ACCUM, VERSION_ALT):
+    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) not in (VERSION, VERSION_ACCUM, VERSION_ALT, VERSION_HYDROLOGY):
         raise RestartError("not a restart image of this format version")
     hb, tb, ne, ns = int(h["header_bytes"]), int(h["total_bytes"]), int(h["nentries"]), int(h["nsections"])
     o = HEADER.itemsize
     na = 0
-    if int(h["version"]) in (VERSION_ACCUM, VERSION_ALT):
+    if int(h["version"]) in (VERSION_ACCUM, VERSION_ALT, VERSION_HYDROLOGY):
         if img.size < o + 8:
             raise RestartError("truncated image")
         na, zero = (int(x) for x in np.frombuffer(img[o:o + 8].tobytes(), "<u4"))
@@ -110,8 +115,10 @@ def parse(image):
     acc = np.frombuffer(img[o:o + na * ACCUM.itemsize].tobytes(), ACCUM).copy()
     o += na * ACCUM.itemsize
     sec = np.frombuffer(img[o:o + ns * SECTION.itemsize].tobytes(), SECTION).copy()
-    if bool(np.any(sec["kind"] == ALT_SECTION)) != (int(h["version"]) == VERSION_ALT):
-        raise RestartError("active layer sections belong to version 3, and a version-3 image holds them")
+    if bool(np.any(sec["kind"] == HYDROLOGY_SECTION)) != (int(h["version"]) == VERSION_HYDROLOGY):
+        raise RestartError("soil hydrology sections belong to version 4, and a version-4 image holds them")
+    if int(h["version"]) != VERSION_HYDROLOGY and bool(np.any(sec["kind"] == ALT_SECTION)) != (int(h["version"]) == VERSION_ALT):
+        raise RestartError("active layer sections belong to version 3 or 4, and a version-3 image holds them")
     data = []
     for s in sec:
         dt = ELEM[int(s["dtype"])]
@@ -145,7 +152,9 @@ def build(header, entries, sections, data, accum=None):
     acc = np.zeros(0, ACCUM) if accum is None else np.asarray(accum, ACCUM).reshape(-1)
     sec = np.array(sections, SECTION)
     alt = bool(np.any(sec["kind"] == ALT_SECTION)) if sec.size else False
-    h["version"] = VERSION_ALT if alt else (VERSION_ACCUM if acc.size else VERSION)
+    hyd = bool(np.any(sec["kind"] == HYDROLOGY_SECTION)) if sec.size else False
+    h["version"] = VERSION_HYDROLOGY if hyd else (VERSION_ALT if alt else (VERSION_ACCUM if acc.size else VERSION))
+    alt = alt or hyd  # (the count word is present from version 3 on)
     pre = HEADER.itemsize + (8 if acc.size or alt else 0)
     hb = _align(pre + ent.size * ENTRY.itemsize + acc.size * ACCUM.itemsize + sec.size * SECTION.itemsize)
     off = hb

@@ -26,7 +26,8 @@ HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, 
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
 CLASS_PROGNOSTIC, CLASS_SURFACE, CLASS_FORCING, CLASS_DIAGNOSTIC = range(4)  # elmk_field_class
 CLASS_NAMES = ("prognostic", "surface", "forcing", "diagnostic")
-RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM, RUN_AEROSOL, RUN_ALT = 1, 2, 4, 8, 16  # elmk_run flags
+RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM, RUN_AEROSOL, RUN_ALT, RUN_HYDROLOGY = 1, 2, 4, 8, 16, 32  # elmk_run flags
+HYD_NROWS, HYD_NLAYER = 23, 10  # elmk_soil_hydrology_read: the row numbers are hydrology.ZWT .. hydrology.FSAT
 ALT_ALT, ALT_ALTMAX, ALT_ALTMAX_LASTYEAR = range(3)  # elmk_active_layer_read
 ALT_ROLL_NORTH, ALT_ROLL_SOUTH = 1, 2  # elmk_active_layer_update
 ACCUM_RUNMEAN, ACCUM_TIMEAVG, ACCUM_RUNACCUM = range(3)  # elmk_accum_add
@@ -476,6 +477,47 @@ class ELMState:
         """Free the three rows (the index fields keep their values)."""
         self._chk(self.lib.elmk_active_layer_clear(self.ctx), "active_layer_clear")
 
+    # -- soil hydrology (include/elmk.h: elmk_soil_hydrology_enable ...; elmkernels_amd/hydrology.py restates the stage) -----------
+    def soil_hydrology_enable(self):
+        """Allocate the rows of the feature (fp64, zero-filled).  Refused when already enabled or while the stream is captured."""
+        self._chk(self.lib.elmk_soil_hydrology_enable(self.ctx), "soil_hydrology_enable")
+
+    def soil_hydrology_set_params(self, hksat, wtfact, h2osfc_thresh, k_wet, rsub_top_max):
+        """The parameter rows: hksat [10, ncols] (hydrology.hksat_from_texture) and four [ncols] rows (scalars are broadcast)."""
+        hk = np.ascontiguousarray(hksat, dtype=np.float64)
+        if hk.shape != (HYD_NLAYER, self.ncols):
+            raise ValueError(f"soil_hydrology_set_params: hksat must be [{HYD_NLAYER}, {self.ncols}]")
+        one = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.ncols,))) for v in
+               (wtfact, h2osfc_thresh, k_wet, rsub_top_max)]
+        self._chk(self.lib.elmk_soil_hydrology_set_params(self.ctx, _p(hk), *(_p(v) for v in one)), "soil_hydrology_set_params")
+
+    def soil_hydrology_init(self, zwt=None, wa=None):
+        """ZWT and WA from [ncols] each; None: ELM's cold start (wa = 4000 mm, zwt = hydrology.cold_start_zwt).  Synchronises."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (zwt, wa)]
+        for v in a:
+            if v is not None and v.size != self.ncols:
+                raise ValueError(f"soil_hydrology_init: {v.size} values for {self.ncols} columns")
+        self._chk(self.lib.elmk_soil_hydrology_init(self.ctx, *(None if v is None else _p(v) for v in a)), "soil_hydrology_init")
+
+    def soil_hydrology(self, dt):
+        """The stage for every column: one launch, stream-ordered, no sync.  Call after advance_physics."""
+        self._chk(self.lib.elmk_soil_hydrology(self.ctx, float(dt)), "soil_hydrology")
+
+    def soil_hydrology_read(self, which, col0=0, n=None):
+        """Row `which` (hydrology.ZWT .. hydrology.FSAT) of columns [col0, col0 + n): float64 [n].  Synchronises."""
+        n = int(self.ncols - col0 if n is None else n)
+        out = np.empty(n, dtype=np.float64)
+        self._chk(self.lib.elmk_soil_hydrology_read(self.ctx, int(which), _p(out), int(col0), n), "soil_hydrology_read")
+        return out
+
+    def soil_hydrology_rows(self):
+        """Every row of the feature: float64 [HYD_NROWS, ncols], the `rows` of hydrology.step."""
+        return np.stack([self.soil_hydrology_read(w) for w in range(HYD_NROWS)])
+
+    def soil_hydrology_clear(self):
+        """Free the rows (the state fields keep their values)."""
+        self._chk(self.lib.elmk_soil_hydrology_clear(self.ctx), "soil_hydrology_clear")
+
     # -- aerosol deposition (include/elmk.h: elmk_aerosol_reserve ...; elmkernels_amd/aerosol.py restates the kernel) ----------
     def aerosol_reserve(self, ncells=None, idx=None, w=None):
         """The device series of the eleven deposition streams x 12 months x ncells (fp64, zero-filled) and the map of the aerosol
@@ -873,7 +915,7 @@ class ELMInterface:
         return False
 
     def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False, update_accum=False, update_aerosol=False,
-            update_active_layer=False):
+            update_active_layer=False, soil_hydrology=False):
         """ELMInterface::advance for every row of steps (RUN_STEP_DTYPE) in one call (elmk_run; needs S.run_reserve and the series
         uploaded); self.conservation = the last step's triples, self.run_conservation = all of them.  update_accum: every step updates
         the accumulated fields registered on self.S (ELM's UpdateAccVars: after the physics, before the history).  update_aerosol: every
@@ -883,6 +925,7 @@ class ELMInterface:
         S = self.S
         flags = (RUN_HISTORY if accumulate_history else 0) | (RUN_QBOT_IS_RH if qbot_is_rh else 0) | (RUN_ACCUM if update_accum else 0)
         flags |= (RUN_AEROSOL if update_aerosol else 0) | (RUN_ALT if update_active_layer else 0)
+        flags |= RUN_HYDROLOGY if soil_hydrology else 0  # the soil hydrology stage after surface_fluxes (S.soil_hydrology_enable)
         S.run(dt_seconds, steps, flags)
         mms, fo, fb = S.run_diagnostics()
         self.run_conservation = mms

@@ -300,7 +300,9 @@ int elmk_history_clear(elmk_ctx *ctx);
  *                          elmk_solar_geometry(dt, decday, doy); elmk_phenology(month_wt1, month_wt2) over months month1 / month2;
  *                          elmk_get_forcing(forc_wt1, forc_wt2, flags & ELMK_RUN_QBOT_IS_RH) over slots forc_slot / forc_slot + 1;
  *                          with ELMK_RUN_AEROSOL: elmk_aerosol_deposition(month1, month2, month_wt1, month_wt2) ("aerosol deposition");
- *                          elmk_init_timestep; elmk_advance_physics(dt); elmk_evaluate_conservation -> ring row s;
+ *                          elmk_init_timestep; elmk_advance_physics(dt);
+ *                          with ELMK_RUN_HYDROLOGY: elmk_soil_hydrology(dt) ("soil hydrology");
+ *                          elmk_evaluate_conservation -> ring row s;
  *                          elmk_error_summary -> ring row s (flags sticky, as that call sees them after the step);
  *                          with ELMK_RUN_ALT: elmk_active_layer_update(the step's rollover) ("active layer thickness");
  *                          with ELMK_RUN_ACCUM: elmk_accum_update ("accumulated fields");
@@ -651,6 +653,128 @@ int elmk_active_layer_update(elmk_ctx *ctx, int rollover /*ELMK_ALT_ROLL_* bits*
 int elmk_active_layer_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
 int elmk_active_layer_clear(elmk_ctx *ctx);
 
+/* ---- soil hydrology -------------------------------------------------------------------------------
+ * ELM v1's column soil hydrology in the CLM4.5 formulation, as one opt-in stage at the end of the step: surface runoff, infiltration
+ * with the h2osfc store, the Zeng-Decker Richards solve with the aquifer as an extra row, the water-table update and drainage.  The
+ * reference has none of it: its conservation row hardwires hydrology_source_sink = 0.0 (driver/kokkos/conserved_quantity_kokkos.cc:22)
+ * and it expects an external subsurface model, so without this stage no kernel applies qflx_top_soil, qflx_rootsoi or the ground
+ * evaporation terms to the soil layers.  Out of scope: lateral flow, VSFM, perched and frost tables, irrigation, lakes, wetlands, urban.
+ * This text is the specification; elmkernels_amd/hydrology.py: column() is the same operation on the host, and where an evaluation
+ * order is not spelled out here that function fixes it (k_soil_hydrology.hip follows it statement by statement, bit for bit).
+ *
+ * Conventions.  pow, exp: glibc's (elmk_pow, elmk_exp on the device); 10^x is pow(10.0, x).  No contraction; `/` is the correctly
+ * rounded fp64 division; comparisons are plain IEEE; min(a, b) = (b < a ? b : a), max(a, b) = (a < b ? b : a); a * b * c and a / b / c
+ * associate from the left.  N = ELMK_HYD_NLAYER = 10 layers are active: layer j is level 5 + j of h2osoi_liq, h2osoi_ice, dz, zsoi and
+ * level j of watsat, sucsat, bsw, h2osoi_vol, qflx_rootsoi; zi[j] is level 6 + j of zisoi and zi[-1] level 5 (the surface); layers
+ * 10 .. 14 are never touched.  denh2o = 1000, denice = 917, e_ice = 6, smpmin = -1e8, watmin = 0.01, pc = 0.4, mu = 0.13889,
+ * fff_s = 0.5, fff_d = 2.5, aquifer_max = 5000, rous_min = 0.02; zmm, zimm, dzmm, zwtmm = zsoi, zi, dz, zwt times 1e3.  State fields
+ * are widened to fp64 as stored, and a result is rounded once to the stored type.
+ *
+ * The feature owns ELMK_HYD_NROWS fp64 rows [level stride] (in both builds): prognostic ZWT (m), WA (mm); parameters HKSAT[10] (mm/s),
+ * WTFACT, H2OSFC_THRESH (mm), K_WET, RSUB_TOP_MAX (mm/s); diagnostics, overwritten every step, QFLX_SURF, QFLX_INFL,
+ * QFLX_H2OSFC_SURF, QFLX_DRAIN, QFLX_RSUB_SAT, QCHARGE, FSAT.
+ *
+ * Per column, with dt and fsno = frac_sno_eff:
+ * A. for j < N: vol_ice = min(watsat, ice / (dz * denice)); effpor = max(0.01, watsat - vol_ice); icefrac = min(1, vol_ice / watsat);
+ *    vol_liq = max(liq, 1e-6) / (dz * denh2o); vol = liq / (dz * denh2o) + ice / (dz * denice).
+ * B. fsat = wtfact * exp(-0.5 * fff_s * zwt); qflx_surf = fsat * qflx_top_soil.
+ * C. qevap = snl == 0 ? qflx_evap_grnd : qflx_ev_soil;
+ *    q_in_soil = (1 - frac_h2osfc) * (qflx_top_soil - qflx_surf); q_in_soil = q_in_soil - (1 - fsno - frac_h2osfc) * qevap;
+ *    q_in_sfc = frac_h2osfc * (qflx_top_soil - qflx_surf); q_in_sfc = q_in_sfc - frac_h2osfc * qflx_ev_h2osfc;
+ *    m = pow(10, -e_ice * icefrac[0]) * hksat[0]; m = min(m, the same of layer 1); m = min(m, of layer 2); qinmax = (1 - fsat) * m;
+ *    excess = max(0, q_in_soil - (1 - frac_h2osfc) * qinmax); infl = q_in_soil - excess; q_in_sfc = q_in_sfc + excess;
+ *    frac_infclust = frac_h2osfc <= pc ? 0 : pow(frac_h2osfc - pc, mu);
+ *    qs = h2osfc >= thresh ? min(k_wet * frac_infclust * (h2osfc - thresh), (h2osfc - thresh) / dt) : 0; if (qs < 1e-8) qs = 0;
+ *    h2osfc = h2osfc + (q_in_sfc - qs) * dt;
+ *    if (h2osfc < 0) { infl = infl + h2osfc / dt; h2osfc = 0; drain_sfc = 0; } else drain_sfc = min(frac_h2osfc * qinmax, h2osfc / dt);
+ *    h2osfc = h2osfc - drain_sfc * dt; infl = infl + drain_sfc.        (qs is the diagnostic QFLX_H2OSFC_SURF)
+ * D. 1. jwt = the first j with zwt <= zi[j], else N.
+ *    2. for j < N, b1 = 1 - 1 / bsw:  zwtmm <= zimm[j-1]: ve = watsat;
+ *       else zwtmm < zimm[j]: t0 = pow((sucsat + zwtmm - zimm[j-1]) / sucsat, b1);
+ *            v1 = -sucsat * watsat / b1 / (zwtmm - zimm[j-1]) * (1 - t0);
+ *            ve = (v1 * (zwtmm - zimm[j-1]) + watsat * (zimm[j] - zwtmm)) / (zimm[j] - zimm[j-1]);
+ *       else ti = pow((sucsat + zwtmm - zimm[j]) / sucsat, b1); t0 as above; ve = -sucsat * watsat / b1 / (zimm[j] - zimm[j-1]) * (ti - t0);
+ *       ve = min(watsat, max(ve, 0)); zq[j] = max(smpmin, -sucsat * pow(max(ve / watsat, 0.01), -bsw)).
+ *    3. only if jwt == N, with layer N-1's parameters: t0 and v1 as in the middle case over [zimm[N-1], zwtmm]; ve = v1 (the layer ends at
+ *       the water table, as in ELM), clamped as above; zq[N] from it; zmm[N] = 0.5 * (zwtmm + zmm[N-1]); dzmm[N] = zwtmm - zimm[N-1].
+ *    4. jp = min(N-1, j+1): s1 = min(1, 0.5 * (vol[j] + vol[jp]) / (0.5 * (watsat[j] + watsat[jp]))); s2 = hksat[j] * pow(s1, 2 * bsw[j] + 2);
+ *       imped[j] = pow(10, -e_ice * (0.5 * (icefrac[j] + icefrac[jp]))); hk[j] = imped * s1 * s2;
+ *       dhkdw[j] = imped * (2 * bsw[j] + 3) * s2 * (1 / (watsat[j] + watsat[jp])).
+ *    5. sn = min(1, max(vol_liq[j] / watsat[j], 0.01)); smp[j] = max(smpmin, -sucsat * pow(sn, -bsw)); dsmpdw[j] = -bsw * smp / (sn * watsat);
+ *       aquifer (jwt == N): sn1 = min(1, max(vol[N-1] / watsat[N-1], 0.01)), smp1 and dsmpdw1 from it with layer N-1's parameters.
+ *    6. interface i between nodes i and i+1, i = 0 .. N-2: den = zmm[i+1] - zmm[i]; num = (smp[i+1] - smp[i]) - (zq[i+1] - zq[i]);
+ *       q[i] = -hk[i] * num / den; dq1[i] = -(-hk[i] * dsmpdw[i] + num * dhkdw[i]) / den; dq2[i] = -(hk[i] * dsmpdw[i+1] + num * dhkdw[i]) / den.
+ *       Interface N-1: with jwt == N the same against the aquifer node (zmm[N], zq[N], smp1, dsmpdw1; hk[N-1], dhkdw[N-1]); else all 0.
+ *    7. rows: r[0] = infl - q[0] - rootsoi[0], a[0] = 0, b[0] = dzmm[0] / dt + dq1[0], c[0] = dq2[0];
+ *       j = 1 .. N-1: r = q[j-1] - q[j] - rootsoi[j], a = -dq1[j-1], b = dzmm[j] / dt - dq2[j-1] + dq1[j], c = dq2[j];
+ *       row N: jwt == N: r = q[N-1], a = -dq1[N-1], b = dzmm[N] / dt - dq2[N-1], c = 0; else r = 0, a = 0, b = 1, c = 0.
+ *    8. Thomas: bet = b[0]; u[0] = r[0] / bet; for j = 1 .. N: gam[j] = c[j-1] / bet; bet = b[j] - a[j] * gam[j];
+ *       u[j] = (r[j] - a[j] * u[j-1]) / bet;   then for j = N-1 .. 0: u[j] = u[j] - gam[j+1] * u[j+1].
+ *    9. liq[j] = liq[j] + u[j] * dzmm[j], j < N.
+ *    10. jwt == N: qcharge = u[N] * dzmm[N] / dt.  Else k = jwt, up = max(0, jwt - 1), from the values before the solve:
+ *        sn = max(vol[k] / watsat[k], 0.01); ka = imped[k] * hksat[k] * pow(min(1, sn), 2 * bsw[k] + 3); wh = smp[up] - zq[up];
+ *        qcharge = jwt == 0 ? -ka * (0 - wh) / ((zwt + 1e-3) * 1000) : -ka * (0 - wh) / ((zwt - zsoi[jwt-1]) * 1000 * 2);
+ *        qcharge = max(-10 / dt, qcharge); qcharge = min(10 / dt, qcharge).
+ * E. sy(j) = max(rous_min, watsat[j] * (1 - pow(1 + 1e3 * zwt / sucsat[j], -1 / bsw[j]))) with the zwt current where it is evaluated;
+ *    rous = sy(N-1) at the start of E.  jwt == N: wa = wa + qcharge * dt; zwt = zwt - qcharge * dt / 1000 / rous.  Else qt = qcharge * dt;
+ *    qt > 0: for j = jwt down to 0: ql = max(0, min(qt, sy(j) * (zwt - zi[j-1]) * 1e3)); zwt = zwt - ql / sy(j) / 1000 (the same sy);
+ *            qt = qt - ql; stop when qt <= 0.
+ *    else:   for j = jwt .. N-1: ql = min(0, max(qt, -(sy(j) * (zi[j] - zwt) * 1e3))); qt = qt - ql;
+ *            if (qt >= 0) { zwt = zwt - ql / sy(j) / 1000; stop; } else zwt = zi[j];     after the walk: if (qt < 0) zwt = zwt - qt / 1000 / rous.
+ *    Then jwt is recomputed.
+ * F. 1. rous = sy(N-1) again (ELM's Drainage recomputes it); imp = pow(10, -e_ice * (si / sd)), si = sum of icefrac * dzmm and sd = sum
+ *       of dzmm over j = max(jwt-1, 0) .. N-1, each from 0.0 in ascending j; rsub_top = imp * rsub_top_max * exp(-fff_d * zwt);
+ *       rt = -rsub_top * dt.
+ *    2. jwt == N: wa = wa + rt; zwt = zwt + rt / 1000 / rous; liq[N-1] = liq[N-1] + max(0, wa - aquifer_max); wa = min(wa, aquifer_max).
+ *       Else the falling walk of E with rt for qt and liq[j] = liq[j] + ql in every visited layer, then (always) zwt = zwt - rt / 1000 / rous
+ *       and wa = wa + rt with the rt that is left.
+ *    3. zwt = zwt < 0 ? 0 : zwt; zwt = 80 < zwt ? 80 : zwt   (a NaN stays).
+ *    4. j = N-1 down to 1: cap = effpor[j] * dzmm[j]; xs = max(liq[j] - cap, 0); liq[j] = min(cap, liq[j]); liq[j-1] = liq[j-1] + xs.
+ *    5. xs1 = max(max(liq[0], 0) - max(0, watsat[0] * dzmm[0] - ice[0]), 0); liq[0] = liq[0] - xs1; h2osfc = h2osfc + xs1; rsub_sat = 0.
+ *    6. j = 0 .. N-2: if (liq[j] < watmin) { xs = watmin - liq[j]; liq[j] = liq[j] + xs; liq[j+1] = liq[j+1] - xs; }
+ *    7. if (liq[N-1] < watmin) { xs = watmin - liq[N-1]; for i = N-2 down to 0 while xs > 0: avail = max(liq[i] - watmin - xs, 0);
+ *       take = min(avail, xs); liq[N-1] = liq[N-1] + take; liq[i] = liq[i] - take; xs = max(xs - take, 0);   then
+ *       liq[N-1] = liq[N-1] + xs; rsub_top = rsub_top - xs / dt; }
+ *    8. qflx_drain = rsub_sat + rsub_top.
+ * G. where snl == 0: liq[0] = liq[0] + (1 - frac_h2osfc) * qflx_dew_grnd * dt; ice[0] = ice[0] + (1 - frac_h2osfc) * qflx_dew_snow * dt;
+ *    if (qflx_sub_snow * dt > ice[0]) ice[0] = 0; else ice[0] = ice[0] - (1 - frac_h2osfc) * qflx_sub_snow * dt.
+ * H. h2osoi_vol[j] = liq / (dz * denh2o) + ice / (dz * denice) from the new fp64 values, j < N.  The stage writes h2osoi_liq (layers
+ *    0 .. N-1), h2osoi_ice (layer 0, where snl == 0), h2osoi_vol, h2osfc, ZWT, WA and the seven diagnostic rows.  A NaN stored into a row of
+ *    the feature is the canonical quiet NaN (bits 0x7FF8000000000000), as in the active layer thickness.  No error bit is raised.
+ *
+ *   elmk_soil_hydrology_enable      allocates the rows, zero-filled (ELMK_HYD_NROWS x 8 bytes x elmk_level_stride, counted in
+ *                                   elmk_device_bytes); drops the captured run step.  ELMK_E_INVALID, nothing changed: already enabled;
+ *                                   a stream being captured.
+ *   elmk_soil_hydrology_set_params  the parameter rows from the host: hksat[10][ncols] (layer-major) and four [ncols] rows.  Synchronises.
+ *   elmk_soil_hydrology_init        ZWT and WA from host[ncols] each; NULL for either means ELM's cold start, wa = 4000 and
+ *                                   zwt = (zi[9] + 25) - 4000 / 0.2 / 1000 from the column's zisoi (hydrology.cold_start_zwt).  Synchronises.
+ *   elmk_soil_hydrology             one launch; stream-ordered and capturable, no host memory, no synchronisation.  ELMK_E_INVALID,
+ *                                   nothing enqueued: not enabled; parameters never set; dt not finite and positive.  A context whose
+ *                                   land unit (elmk_set_land) is not soil or crop enqueues nothing and returns ELMK_OK.
+ *   elmk_soil_hydrology_read        row `which` (ELMK_HYD_*) of columns [col0, col0 + n) as doubles; synchronises.
+ *   elmk_soil_hydrology_clear       frees the rows and drops the captured run step; the state fields keep their values.
+ * elmk_run with ELMK_RUN_HYDROLOGY runs the stage in every step after elmk_surface_fluxes and before the step's conservation row (whose
+ * errh2o keeps the reference's hardwired source_sink = 0; hydrology.water_balance_error is the closed budget); refused before anything is
+ * enqueued when not enabled or without parameters.  Graph on and off give the same bits.
+ * Restart: a context with the feature enabled saves a version-4 image that carries ZWT and WA ("restart" below); the parameter rows
+ * stay with the driver, like the geography.  A context that never enables the feature runs the kernels, launch sequences and graphs
+ * it ran before, allocates nothing more and saves the image it saved before. */
+#define ELMK_HYD_NLAYER 10
+enum {
+  ELMK_HYD_ZWT = 0, ELMK_HYD_WA = 1, ELMK_HYD_HKSAT = 2 /* .. 11 */, ELMK_HYD_WTFACT = 12, ELMK_HYD_H2OSFC_THRESH = 13, ELMK_HYD_K_WET = 14,
+  ELMK_HYD_RSUB_TOP_MAX = 15, ELMK_HYD_QFLX_SURF = 16, ELMK_HYD_QFLX_INFL = 17, ELMK_HYD_QFLX_H2OSFC_SURF = 18, ELMK_HYD_QFLX_DRAIN = 19,
+  ELMK_HYD_QFLX_RSUB_SAT = 20, ELMK_HYD_QCHARGE = 21, ELMK_HYD_FSAT = 22, ELMK_HYD_NROWS = 23
+};
+#define ELMK_RUN_HYDROLOGY 32 /* the sixth flag bit of elmk_run: every step runs the soil hydrology stage */
+int elmk_soil_hydrology_enable(elmk_ctx *ctx);
+int elmk_soil_hydrology_set_params(elmk_ctx *ctx, const double *hksat /*[10][ncols]*/, const double *wtfact /*[ncols]*/,
+                                   const double *h2osfc_thresh /*[ncols]*/, const double *k_wet /*[ncols]*/,
+                                   const double *rsub_top_max /*[ncols]*/);
+int elmk_soil_hydrology_init(elmk_ctx *ctx, const double *zwt /*[ncols] or NULL*/, const double *wa /*[ncols] or NULL*/);
+int elmk_soil_hydrology(elmk_ctx *ctx, double dt);
+int elmk_soil_hydrology_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
+int elmk_soil_hydrology_clear(elmk_ctx *ctx);
+
 /* ---- restart ---------------------------------------------------------------------------------
  * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state
  * and history into a self-describing byte buffer, the image, and another context - in another process, or with another column
@@ -691,6 +815,11 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  * checksummed as the other column sections.  A version-3 image loads only into a context with the feature enabled, a version-1 or
  * version-2 image only into one without it.
  *
+ * Image format, version 4: what a context with the soil hydrology enabled (elmk_soil_hydrology_enable) saves.  As version 3, with the
+ * ELMK_RESTART_ALT sections present exactly when the active layer thickness is enabled too (the section table says which optional kinds
+ * an image holds), and last two sections of kind ELMK_RESTART_HYDROLOGY, id = ELMK_HYD_ZWT, ELMK_HYD_WA, nlev = 1, F64, extent = ncols.
+ * A version-4 image loads only into a context with the same features enabled; the parameter rows are not part of it.
+ *
  * elmk_restart_size: bytes of this context's image.  elmk_restart_save: the image of the context's columns, which are global
  * columns [gcol0, gcol0 + ncols) of the run.  elmk_restart_load: verifies the whole image on the device (every checksum, snl in
  * 0..nlevsno, as elmk_upload) before it writes anything, then writes the fields, the accumulators, the tape counts and the
@@ -709,11 +838,13 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  * then the current forcing records or run series and their record times.
  * Graphs captured before a load stay valid (the arena and the history table do not move). */
 enum { ELMK_CLASS_PROGNOSTIC = 0, ELMK_CLASS_SURFACE = 1, ELMK_CLASS_FORCING = 2, ELMK_CLASS_DIAGNOSTIC = 3 };
-enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2, ELMK_RESTART_ACCUM = 3, ELMK_RESTART_ALT = 4 };
+enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2, ELMK_RESTART_ACCUM = 3, ELMK_RESTART_ALT = 4,
+       ELMK_RESTART_HYDROLOGY = 5 };
 #define ELMK_RESTART_MAGIC "ELMKRST\0"
 #define ELMK_RESTART_VERSION 1u       /* of a context without accumulator entries */
 #define ELMK_RESTART_VERSION_ACCUM 2u /* of a context with accumulator entries */
 #define ELMK_RESTART_VERSION_ALT 3u   /* of a context with the active layer thickness enabled */
+#define ELMK_RESTART_VERSION_HYDROLOGY 4u /* of a context with the soil hydrology enabled */
 typedef struct {
   char magic[8];              /* ELMK_RESTART_MAGIC */
   uint32_t version;           /* ELMK_RESTART_VERSION */

@@ -294,6 +294,22 @@ class ELMInterface {
   void active_layer_read(int which, double* host) { ok(elmk_active_layer_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
   void active_layer_clear() { ok(elmk_active_layer_clear(ctx_)); }
 
+  /* Soil hydrology (elmk.h "soil hydrology"; ELM v1's column hydrology, which the reference leaves to an external model):
+   * soil_hydrology_enable() allocates the rows, soil_hydrology_set_params() takes hksat [10][ncols] and four [ncols] rows,
+   * soil_hydrology_init() the water table and the aquifer (nullptr: ELM's cold start); soil_hydrology(dt) after every advance() applies
+   * runoff, infiltration, the Richards solve, the water table and drainage, or run(..., soil_hydrology = true) does it in every step
+   * before the conservation row.  soil_hydrology_read() fills [ncols] of row ELMK_HYD_*. */
+  void soil_hydrology_enable() { ok(elmk_soil_hydrology_enable(ctx_)); }
+  void soil_hydrology_set_params(const double* hksat, const double* wtfact, const double* h2osfc_thresh, const double* k_wet,
+                                 const double* rsub_top_max)
+  {
+    ok(elmk_soil_hydrology_set_params(ctx_, hksat, wtfact, h2osfc_thresh, k_wet, rsub_top_max));
+  }
+  void soil_hydrology_init(const double* zwt = nullptr, const double* wa = nullptr) { ok(elmk_soil_hydrology_init(ctx_, zwt, wa)); }
+  void soil_hydrology(double dt_seconds) { ok(elmk_soil_hydrology(ctx_, dt_seconds)); }
+  void soil_hydrology_read(int which, double* host) { ok(elmk_soil_hydrology_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
+  void soil_hydrology_clear() { ok(elmk_soil_hydrology_clear(ctx_)); }
+
   /* Restart images (elmk.h "restart"): saveRestart() returns the image of the columns, global columns [gcol0, gcol0 + ncols);
    * loadRestart() takes one after setup, geography, maps and the same history and accumulator entries, in place of initialize().
    * Both throw on a refusal; the state is then untouched. */
@@ -325,11 +341,12 @@ class ELMInterface {
     ok(elmk_series_upload(ctx_, id(field), slot0, nslots, host, 0, ncols_));
   }
   void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
-                   bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false)
+                   bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false, bool soil_hydrology = false)
   {
     ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(),
                 (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0) | (update_accum ? ELMK_RUN_ACCUM : 0) |
-                    (update_aerosol ? ELMK_RUN_AEROSOL : 0) | (update_active_layer ? ELMK_RUN_ALT : 0)));
+                    (update_aerosol ? ELMK_RUN_AEROSOL : 0) | (update_active_layer ? ELMK_RUN_ALT : 0) |
+                    (soil_hydrology ? ELMK_RUN_HYDROLOGY : 0)));
   }
   bool finish_run()
   {
@@ -351,9 +368,9 @@ class ELMInterface {
     return false;
   }
   bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
-           bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false)
+           bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false, bool soil_hydrology = false)
   {
-    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol, update_active_layer);
+    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol, update_active_layer, soil_hydrology);
     return finish_run();
   }
   const std::vector<double>& run_conservation() const { return run_conservation_; }
