@@ -1,0 +1,196 @@
+// api_rows.cpp - the features that keep fp64 rows [row][ld] of their own beside the state, held exactly while the feature is enabled:
+// active layer thickness (k_active_layer.hip) and soil hydrology (k_soil_hydrology.hip); include/elmk.h under those names.
+#include "elmk_ctx.h"
+
+namespace {
+struct Rows {
+  DevBuf<double> elmk_ctx::*buf;
+  int nrows;
+  const char* label;   // in the text of a HIP error
+  const char* enable;  // the enabling call, for refusals
+};
+static_assert(ELMK_ALT_ALT == 0 && ELMK_ALT_ALTMAX_LASTYEAR == ALT_NROWS - 1, "three rows");
+constexpr Rows ALT{&elmk_ctx::alt_rows, ALT_NROWS, "active layer", "elmk_active_layer_enable"};
+constexpr Rows HYD{&elmk_ctx::hyd_rows, ELMK_HYD_NROWS, "soil hydrology", "elmk_soil_hydrology_enable"};
+
+// how every call but enable and clear begins
+int rows_enter(elmk_ctx* ctx, const Rows& R, const char* who)
+{
+  if (int rc = enter(ctx)) return rc;
+  return ctx->*R.buf ? ELMK_OK : invalid(ctx, (std::string(who) + ": not enabled (" + R.enable + ")").c_str());
+}
+
+// allocate and zero the rows; nothing is held after a failure
+int rows_enable(elmk_ctx* ctx, const Rows& R, const char* who)
+{
+  if (int rc = enter(ctx)) return rc;
+  DevBuf<double>& buf = ctx->*R.buf;
+  if (buf) return invalid(ctx, (std::string(who) + ": already enabled").c_str());
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the stages of its flags' moment)
+  const size_t bytes = (size_t)R.nrows * (size_t)ctx->ld * sizeof(double);
+  const std::string what = std::string("(") + R.label + " rows)";
+  if (hip_fail(ctx, buf.alloc(bytes), ("hipMalloc" + what).c_str())) return ELMK_E_NOMEM;
+  if (hip_fail(ctx, hipMemsetAsync(buf, 0, bytes, ctx->stream), ("hipMemset" + what).c_str()) ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)buf.reset();
+    return ELMK_E_HIP;
+  }
+  return ELMK_OK;
+}
+
+// columns [col0, col0 + n) of one row; synchronises
+int rows_read(elmk_ctx* ctx, const Rows& R, const char* who, int which, double* host, int64_t col0, int64_t n)
+{
+  if (int rc = rows_enter(ctx, R, who)) return rc;
+  if (which < 0 || which >= R.nrows) return invalid(ctx, (std::string(who) + ": unknown row").c_str());
+  if (int rc = check_range(ctx, who, host, col0, n, ctx->ncols)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  const double* rows = ctx->*R.buf;
+  if (n > 0) HIPCHK(hipMemcpyAsync(host, rows + (size_t)which * (size_t)ctx->ld + (size_t)col0, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return synced(ctx);
+}
+
+int rows_clear(elmk_ctx* ctx, const Rows& R, const char* who)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (!(ctx->*R.buf)) return ELMK_OK;
+  if (int rc = quiesce(ctx, false)) return rc;
+  HIPCHK((ctx->*R.buf).reset());
+  return ELMK_OK;
+}
+}  // namespace
+
+namespace elmk {
+ActiveLayerArgs alt_args(const elmk_ctx* ctx)
+{
+  return ActiveLayerArgs{ctx->fptr[ELMK_FIELD_t_soisno], ctx->fptr[ELMK_FIELD_zsoi], (int32_t*)ctx->fptr[ELMK_FIELD_altmax_indx],
+                         (int32_t*)ctx->fptr[ELMK_FIELD_altmax_lastyear_indx], ctx->alt_rows,
+                         ctx->geo + (size_t)ELMK_GEO_SIN_LAT * (size_t)ctx->ld, ctx->ld, ctx->ncols};
+}
+bool hyd_land(const elmk_ctx* ctx) { return ctx->h.land.ltype == istsoil || ctx->h.land.ltype == istcrop; }
+void hyd_launch(elmk_ctx* ctx, double dt)
+{
+  if (hyd_land(ctx)) launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, dt, ctx->stream);
+}
+}  // namespace elmk
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------------
+// active layer thickness
+// ---------------------------------------------------------------------------------------------------
+int elmk_active_layer_enable(elmk_ctx* ctx) { return rows_enable(ctx, ALT, "elmk_active_layer_enable"); }
+
+int elmk_active_layer_init(elmk_ctx* ctx, const double* altmax, const double* altmax_lastyear)
+{
+  if (int rc = rows_enter(ctx, ALT, "elmk_active_layer_init")) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_active_layer_init")) return rc;
+  const size_t ld = (size_t)ctx->ld, n = (size_t)ctx->ncols;
+  HIPCHK(hipMemsetAsync(ctx->alt_rows, 0, ctx->alt_rows.bytes(), ctx->stream));
+  if (altmax && n) HIPCHK(hipMemcpyAsync(ctx->alt_rows + ELMK_ALT_ALTMAX * ld, altmax, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (altmax_lastyear && n)
+    HIPCHK(hipMemcpyAsync(ctx->alt_rows + ELMK_ALT_ALTMAX_LASTYEAR * ld, altmax_lastyear, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  return synced(ctx);
+}
+
+int elmk_active_layer_update(elmk_ctx* ctx, int rollover)
+{
+  if (int rc = rows_enter(ctx, ALT, "elmk_active_layer_update")) return rc;
+  if (!ctx->geo_set) return invalid(ctx, "elmk_active_layer_update: no column geography (elmk_set_column_geography)");
+  if (rollover & ~(ELMK_ALT_ROLL_NORTH | ELMK_ALT_ROLL_SOUTH)) return invalid(ctx, "elmk_active_layer_update: unknown rollover bits");
+  launch_active_layer(alt_args(ctx), rollover, ctx->stream);
+  return launched(ctx);
+}
+
+int elmk_active_layer_read(elmk_ctx* ctx, int w, double* host, int64_t col0, int64_t n) { return rows_read(ctx, ALT, "elmk_active_layer_read", w, host, col0, n); }
+
+int elmk_active_layer_clear(elmk_ctx* ctx) { return rows_clear(ctx, ALT, "elmk_active_layer_clear"); }
+
+// ---------------------------------------------------------------------------------------------------
+// soil hydrology
+// ---------------------------------------------------------------------------------------------------
+int elmk_soil_hydrology_enable(elmk_ctx* ctx)
+{
+  const int rc = rows_enable(ctx, HYD, "elmk_soil_hydrology_enable");
+  if (rc == ELMK_OK) ctx->hyd_params = false;
+  return rc;
+}
+
+int elmk_soil_hydrology_set_params(elmk_ctx* ctx, const double* hksat, const double* wtfact, const double* h2osfc_thresh,
+                                   const double* k_wet, const double* rsub_top_max)
+{
+  if (int rc = rows_enter(ctx, HYD, "elmk_soil_hydrology_set_params")) return rc;
+  if (!hksat || !wtfact || !h2osfc_thresh || !k_wet || !rsub_top_max) return invalid(ctx, "elmk_soil_hydrology_set_params: null argument");
+  if (int rc = refuse_capture(ctx, "elmk_soil_hydrology_set_params")) return rc;
+  const size_t ld = (size_t)ctx->ld, n = (size_t)ctx->ncols;
+  if (n) {
+    HIPCHK(hipMemcpy2DAsync(ctx->hyd_rows + ELMK_HYD_HKSAT * ld, ld * 8, hksat, n * 8, n * 8, ELMK_HYD_NLAYER, hipMemcpyHostToDevice,
+                            ctx->stream));
+    const double* one[4] = {wtfact, h2osfc_thresh, k_wet, rsub_top_max};
+    for (int k = 0; k < 4; k++)
+      HIPCHK(hipMemcpyAsync(ctx->hyd_rows + (size_t)(ELMK_HYD_WTFACT + k) * ld, one[k], n * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->hyd_params = true;
+  return ELMK_OK;
+}
+
+int elmk_soil_hydrology_init(elmk_ctx* ctx, const double* zwt, const double* wa)
+{
+  if (int rc = rows_enter(ctx, HYD, "elmk_soil_hydrology_init")) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_soil_hydrology_init")) return rc;
+  const size_t ld = (size_t)ctx->ld, n = (size_t)ctx->ncols;
+  std::vector<double> cold;
+  if (n && (!zwt || !wa)) {
+    // ELM's cold start: wa = 4000 mm, zwt = (zi[9] + 25) - wa / 0.2 / 1000 from the bottom of layer 9 (level 15 of zisoi, as stored)
+    cold.assign(n, 4000.0);
+    if (!zwt) {
+      const int es = store_size(ELMK_F64);
+      std::vector<unsigned char> raw(n * (size_t)es);
+      HIPCHK(hipMemcpyAsync(raw.data(), (const char*)ctx->fptr[ELMK_FIELD_zisoi] + (size_t)(ELMK_NLEVSNO + ELMK_HYD_NLAYER) * ld * es,
+                            raw.size(), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      std::vector<double> z(n);
+      for (size_t i = 0; i < n; i++) {
+        double zi9;
+        if (es == 4) {
+          float f;
+          memcpy(&f, &raw[i * 4], 4);
+          zi9 = (double)f;
+        } else {
+          memcpy(&zi9, &raw[i * 8], 8);
+        }
+        z[i] = (zi9 + 25.0) - 4000.0 / 0.2 / 1000.0;
+      }
+      HIPCHK(hipMemcpyAsync(ctx->hyd_rows + ELMK_HYD_ZWT * ld, z.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));  // (z leaves scope)
+    }
+  }
+  if (n && zwt) HIPCHK(hipMemcpyAsync(ctx->hyd_rows + ELMK_HYD_ZWT * ld, zwt, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (n) HIPCHK(hipMemcpyAsync(ctx->hyd_rows + ELMK_HYD_WA * ld, wa ? wa : cold.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+  return synced(ctx);
+}
+
+int elmk_soil_hydrology(elmk_ctx* ctx, double dt)
+{
+  if (int rc = rows_enter(ctx, HYD, "elmk_soil_hydrology")) return rc;
+  if (!ctx->hyd_params) return invalid(ctx, "elmk_soil_hydrology: the parameters are not set (elmk_soil_hydrology_set_params)");
+  if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_soil_hydrology: dt must be finite and positive");
+  if (int rc = enter_physics(ctx)) return rc;
+  hyd_launch(ctx, dt);
+  return launched(ctx);
+}
+
+int elmk_soil_hydrology_read(elmk_ctx* ctx, int w, double* host, int64_t col0, int64_t n) { return rows_read(ctx, HYD, "elmk_soil_hydrology_read", w, host, col0, n); }
+
+int elmk_soil_hydrology_clear(elmk_ctx* ctx)
+{
+  const int rc = rows_clear(ctx, HYD, "elmk_soil_hydrology_clear");
+  if (rc == ELMK_OK) ctx->hyd_params = false;
+  return rc;
+}
+
+}  // extern "C"

@@ -9,19 +9,15 @@ elmk_restart_save writes, so that a run can restart with another column decompos
 merge and slice refuse images with gridded history entries: per-rank partial cell accumulators do not survive a change of
 decomposition under MAX and MIN.
 
-A context with accumulated fields (elmk_accum_add) saves a version-2 image: the word after the header counts the accumulator
-entries, their table (ACCUM: source, kind, destination, period, step count) follows the history entries, and their value rows are
-sections of kind ACCUM_SECTION.  parse returns the table under "accum" (empty for version 1), build takes it as `accum`, and merge
-requires equal tables and equal step counts.  An image without accumulator entries is version 1, byte for byte as before.
-
-A context with the active layer thickness enabled (elmk_active_layer_enable) saves a version-3 image: as version 2 with the
-accumulator-count word always present (0 without entries) and, last, three column sections of kind ALT_SECTION (id 0, 1, 2: alt,
-altmax, altmax_lastyear; one level, F64).  build writes version 3 exactly when it is given such sections; merge and slice carry them
-as they carry every column section.
-
-A context with the soil hydrology enabled (elmk_soil_hydrology_enable) saves a version-4 image: as version 3, with the ALT sections
-present only when that feature is enabled too, and last two column sections of kind HYDROLOGY_SECTION (id 0, 1: ZWT, WA; one level,
-F64).  build writes version 4 exactly when it is given such sections.
+An image holds exactly the optional kinds of its context, after the field and history sections and in this order, and its version is
+the highest among them (OPTIONAL; version 1 without any, byte for byte as before the kinds existed):
+  version 2, accumulated fields (elmk_accum_add): the word after the header counts the entries - present from version 2 on, 0 without
+    entries -, their table (ACCUM: source, kind, destination, period, step count) follows the history entries, their value rows are
+    sections of kind ACCUM_SECTION; parse returns the table under "accum", build takes it as `accum`, merge requires equal tables;
+  version 3, active layer thickness (elmk_active_layer_enable): three column sections of kind ALT_SECTION (id 0, 1, 2: alt, altmax,
+    altmax_lastyear; one level, F64);
+  version 4, soil hydrology (elmk_soil_hydrology_enable): two column sections of kind HYDROLOGY_SECTION (id 0, 1: ZWT, WA; one level, F64).
+build derives the version from the sections and `accum` it is given; merge and slice carry the sections as they carry every column section.
 """
 import numpy as np
 
@@ -31,6 +27,8 @@ VERSION_ACCUM = 2  # of an image with accumulator entries
 VERSION_ALT = 3  # of an image with the active layer thickness rows
 VERSION_HYDROLOGY = 4  # of an image with the soil hydrology rows ZWT and WA
 FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION, HYDROLOGY_SECTION = 0, 1, 2, 3, 4, 5  # ELMK_RESTART_*
+# the optional kinds and the version that introduced each; from version 2 on the word after the header counts the accumulator entries
+OPTIONAL = ((ACCUM_SECTION, VERSION_ACCUM), (ALT_SECTION, VERSION_ALT), (HYDROLOGY_SECTION, VERSION_HYDROLOGY))
 ALIGN = 256
 HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), ("schema_hash", "<u8"), ("gcol0", "<i8"),
                    ("ncols", "<i8"), ("tape_count", "<u8", (4,)), ("nentries", "<u4"), ("nsections", "<u4"),
@@ -46,6 +44,11 @@ _CK_OFF = HEADER.fields["header_checksum"][1]
 
 class RestartError(ValueError):
     pass
+
+
+def _version(sec, na):
+    """An image's version: the highest among the optional kinds it holds (ACCUM_SECTION: with na > 0 accumulator entries), else 1."""
+    return max((v for k, v in OPTIONAL if (na > 0 if k == ACCUM_SECTION else bool(np.any(sec["kind"] == k)))), default=VERSION)
 
 
 def _align(v):
@@ -96,17 +99,17 @@ def parse(image):
     if img.size < HEADER.itemsize:
         raise RestartError("truncated image")
     h = np.frombuffer(img[:HEADER.itemsize].tobytes(), HEADER)[0]
-    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or int(h["version"]) not in (VERSION, VERSION_ACCUM, VERSION_ALT, VERSION_HYDROLOGY):
+    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or not VERSION <= int(h["version"]) <= OPTIONAL[-1][1]:
         raise RestartError("not a restart image of this format version")
     hb, tb, ne, ns = int(h["header_bytes"]), int(h["total_bytes"]), int(h["nentries"]), int(h["nsections"])
     o = HEADER.itemsize
     na = 0
-    if int(h["version"]) in (VERSION_ACCUM, VERSION_ALT, VERSION_HYDROLOGY):
+    if int(h["version"]) >= VERSION_ACCUM:
         if img.size < o + 8:
             raise RestartError("truncated image")
         na, zero = (int(x) for x in np.frombuffer(img[o:o + 8].tobytes(), "<u4"))
-        if zero != 0 or (na < 1 and int(h["version"]) == VERSION_ACCUM):
-            raise RestartError("a version-2 image holds at least one accumulator entry")
+        if zero != 0:
+            raise RestartError("the word after the accumulator count is not 0")
         o += 8
     if hb > img.size or tb > img.size or hb < o + ne * ENTRY.itemsize + na * ACCUM.itemsize + ns * SECTION.itemsize:
         raise RestartError("truncated image")
@@ -115,10 +118,8 @@ def parse(image):
     acc = np.frombuffer(img[o:o + na * ACCUM.itemsize].tobytes(), ACCUM).copy()
     o += na * ACCUM.itemsize
     sec = np.frombuffer(img[o:o + ns * SECTION.itemsize].tobytes(), SECTION).copy()
-    if bool(np.any(sec["kind"] == HYDROLOGY_SECTION)) != (int(h["version"]) == VERSION_HYDROLOGY):
-        raise RestartError("soil hydrology sections belong to version 4, and a version-4 image holds them")
-    if int(h["version"]) != VERSION_HYDROLOGY and bool(np.any(sec["kind"] == ALT_SECTION)) != (int(h["version"]) == VERSION_ALT):
-        raise RestartError("active layer sections belong to version 3 or 4, and a version-3 image holds them")
+    if _version(sec, na) != int(h["version"]):
+        raise RestartError(f"a version-{int(h['version'])} image with the optional sections of version {_version(sec, na)}")
     data = []
     for s in sec:
         dt = ELEM[int(s["dtype"])]
@@ -145,17 +146,15 @@ def verify(image):
 
 
 def build(header, entries, sections, data, accum=None):
-    """An image from its parts: offsets, header_bytes, total_bytes, the version (3 with sections of kind ALT_SECTION, else 2 with accumulator entries `accum`, else 1) and the
+    """An image from its parts: offsets, header_bytes, total_bytes, the version (OPTIONAL: by its sections and `accum`) and the
     header checksum are computed; section checksums are taken from sections['checksum']."""
     h = np.array(header, HEADER).reshape(())
     ent = np.asarray(entries, ENTRY)
     acc = np.zeros(0, ACCUM) if accum is None else np.asarray(accum, ACCUM).reshape(-1)
     sec = np.array(sections, SECTION)
-    alt = bool(np.any(sec["kind"] == ALT_SECTION)) if sec.size else False
-    hyd = bool(np.any(sec["kind"] == HYDROLOGY_SECTION)) if sec.size else False
-    h["version"] = VERSION_HYDROLOGY if hyd else (VERSION_ALT if alt else (VERSION_ACCUM if acc.size else VERSION))
-    alt = alt or hyd  # (the count word is present from version 3 on)
-    pre = HEADER.itemsize + (8 if acc.size or alt else 0)
+    h["version"] = _version(sec, acc.size)
+    word = int(h["version"]) >= VERSION_ACCUM  # (the count word)
+    pre = HEADER.itemsize + (8 if word else 0)
     hb = _align(pre + ent.size * ENTRY.itemsize + acc.size * ACCUM.itemsize + sec.size * SECTION.itemsize)
     off = hb
     for i, d in enumerate(data):
@@ -164,7 +163,7 @@ def build(header, entries, sections, data, accum=None):
     h["nentries"], h["nsections"], h["header_bytes"], h["total_bytes"], h["header_checksum"] = ent.size, sec.size, hb, off, 0
     img = np.zeros(off, np.uint8)
     img[:HEADER.itemsize] = np.frombuffer(h.tobytes(), np.uint8)
-    if acc.size or alt:
+    if word:
         img[HEADER.itemsize:pre] = np.frombuffer(np.array([acc.size, 0], "<u4").tobytes(), np.uint8)
     o = pre
     img[o:o + ent.nbytes] = np.frombuffer(ent.tobytes(), np.uint8)

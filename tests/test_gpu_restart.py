@@ -1,7 +1,8 @@
 """Exact restarts on the device (include/elmk.h "restart"): E3SM's ERS test - 2N steps against N steps, a save, a fresh context
 whose every field outside the image is poisoned, a load and N more steps - bit for bit in every field, every history result,
 the tape counts and the error summary; a change of column decomposition through restart.merge / restart.slice; the image's
-contents against elmk_download; and every refusal of elmk_restart_load, each leaving the context as it was."""
+contents against elmk_download; every refusal of elmk_restart_load, each leaving the context as it was; and the matrix of the
+optional features: which image loads into which context."""
 import ctypes as C
 
 import numpy as np
@@ -258,6 +259,80 @@ def test_refusals_leave_the_context_as_it_was(base):
     _assert_same(_snapshot(D, ids), _snapshot(Cx, ids_c))
     D.close()
     Cx.close()
+
+
+# ---- the feature matrix ------------------------------------------------------------------------------------------------------------
+MATRIX_N = 70  # one full wave and a partial one: the smallest shape with a tail in the piece kernel
+# the optional kinds in image order: (bit of the context's mask, section kind, sections, the words a refusal names the feature by)
+OPTIONAL = ((1, R.ACCUM_SECTION, 1, "accumulator entries"), (2, R.ALT_SECTION, 3, "active layer"), (4, R.HYDROLOGY_SECTION, 2, "soil hydrology"))
+# What the library did before the host API was split, recorded once from that build: per mask (version, image bytes, the optional
+# section kinds after the field sections), and the (image mask, context mask) pairs that load.
+MATRIX_IMAGES = {0: (1, 298240, ()), 1: (2, 299008, (3,)), 2: (3, 300544, (4, 4, 4)), 3: (3, 301568, (3, 4, 4, 4)),
+                 4: (4, 299776, (5, 5)), 5: (4, 300544, (3, 5, 5)), 6: (4, 302336, (4, 4, 4, 5, 5)), 7: (4, 303104, (3, 4, 4, 4, 5, 5))}
+MATRIX_LOADS = {(m, m) for m in range(8)}
+
+
+def _matrix_context(inputs, mask):
+    D = _device(*inputs[:5])
+    n = D.ncols
+    D["t_grnd"] = np.full(n, 250.0 + mask)
+    if mask & 1:
+        D.accum_init(D.accum_add("t_grnd", "runmean", 10), np.arange(n) + 0.5 * mask, nsteps=3 + mask)
+    if mask & 2:
+        D.active_layer_enable()
+        D.active_layer_init(np.arange(n) * 0.01 + mask, np.arange(n) * 0.02 + mask)
+    if mask & 4:
+        D.soil_hydrology_enable()
+        D.soil_hydrology_init(np.arange(n) * 0.03 + mask, 4000.0 + np.arange(n) + mask)
+    return D
+
+
+def restart_matrix():
+    """-> ({mask: (version, bytes, optional kinds)}, {(image mask, context mask) that load}, {refused pair: message}); asserts what
+    holds for every library: the codec's round trip, and that a refusal is ELMK_E_INVALID and leaves t_grnd alone."""
+    inputs = _inputs(MATRIX_N, 98)
+    ctx = [_matrix_context(inputs, m) for m in range(8)]
+    imgs = [D.restart_save() for D in ctx]
+    nfield = len(R.field_sections(imgs[0]))
+    images, loads, refused = {}, set(), {}
+    for m, img in enumerate(imgs):
+        p = R.verify(img)
+        kinds = [int(k) for k in p["sections"]["kind"]]
+        assert kinds[:nfield] == [R.FIELD] * nfield
+        images[m] = (int(p["header"]["version"]), int(img.size), tuple(kinds[nfield:]))
+        again = R.build(p["header"], p["entries"], p["sections"], p["data"], p["accum"])
+        assert again.tobytes() == img.tobytes(), m
+    for src, img in enumerate(imgs):
+        for dst, D in enumerate(ctx):
+            before = D["t_grnd"]
+            rc = D.lib.elmk_restart_load(D.ctx, 0, img.ctypes.data, img.size)
+            if rc == 0:
+                loads.add((src, dst))
+                D["t_grnd"] = before
+            else:
+                assert rc == -1, (src, dst, rc)  # ELMK_E_INVALID
+                assert same(D["t_grnd"], before), (src, dst)
+                refused[(src, dst)] = D.lib.elmk_last_error(D.ctx).decode()
+    for D in ctx:
+        D.close()
+    return images, loads, refused
+
+
+def test_feature_matrix():
+    """The 8 contexts with an accumulator entry, the active layer thickness and the soil hydrology each off or on: every image has the
+    version include/elmk.h gives it and the optional sections in the order ACCUM, ALT, HYDROLOGY; restart.build reproduces it from
+    restart.parse; of the 64 loads exactly those of an image into the context of its own features succeed, and every other one
+    returns ELMK_E_INVALID, leaves the state as it was and names a feature in which image and context differ."""
+    images, loads, refused = restart_matrix()
+    for m in range(8):
+        want_kinds = tuple(kind for bit, kind, nsec, _ in OPTIONAL if m & bit for _ in range(nsec))
+        want_version = max([1] + [ver for (bit, _, _, _), ver in zip(OPTIONAL, (2, 3, 4)) if m & bit])
+        assert MATRIX_IMAGES[m][0] == want_version and MATRIX_IMAGES[m][2] == want_kinds  # the record follows include/elmk.h
+        assert images[m] == MATRIX_IMAGES[m], m
+    assert loads == MATRIX_LOADS == {(m, m) for m in range(8)}
+    for (src, dst), msg in refused.items():
+        words = [w for bit, _, _, w in OPTIONAL if (src ^ dst) & bit]
+        assert any(w in msg for w in words), (src, dst, msg)
 
 
 def test_restart_demo(tmp_path):

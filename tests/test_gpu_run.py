@@ -341,6 +341,110 @@ def test_refusals_enqueue_nothing(base):
     B.close()
 
 
+def test_the_captured_step_follows_every_part_of_its_key():
+    """One context replays its run step from a captured graph, the other enqueues it stage by stage.  Between two-step runs one part of
+    what the step depends on changes at a time: each run flag, the history and the accumulator tables (an entry more under the same
+    flags), the shortwave mode, the downscaling mode without and with groups, and back.  After every run every field, the diagnostics
+    rows, every history and accumulator read and the rows of the active layer and the soil hydrology are bit-equal: a graph kept past
+    a change of its key would hold the stages, kernels or tables of the moment it was captured.  (The land unit under
+    ELMK_RUN_HYDROLOGY: test_gpu_hydrology.test_the_captured_run_step_follows_the_land_unit.)"""
+    from elmkernels_amd import hydrology as hy
+    from elmkernels_amd import regrid as RG
+    from tests.test_hydrology_host import clear_snow, prepare
+
+    n = 200  # the base fixture is larger; two blocks of most kernels with a ragged tail
+    inputs = _inputs(n, 75)
+    clear_snow(inputs[0])
+    rows = prepare(inputs[0], 76)
+    cols, scal, soil, lat, lon, rec = inputs
+    pair = [_device(cols, scal, soil, lat, lon) for _ in range(2)]
+    for D, graph in zip(pair, (True, False)):
+        D.set_graph(graph)
+        D.run_reserve(NREC, 2)
+        upload_series(D, rec)
+    rng = np.random.default_rng(77)
+    hf = 200.0 + 1500.0 * rng.random(n)
+    hc = hf + rng.uniform(-1500.0, 1500.0, n)
+    cell = np.arange(n) // 60
+    cell[n - 9:] = -1  # columns in no group
+    groups = RG.owner_map(cell, 0.5 + rng.random(n), int(cell.max()) + 1)
+    deposition = 1.0e-12 * (1.0 + rng.random((12, n)))
+    hist, accum = {}, set()  # the entry ids (history: with the tape), the same in both contexts
+
+    def add_history(D, tape, field, op):
+        hist[D.history_add(tape, field, op)] = tape
+
+    def add_accum(D, *entry):
+        accum.add(D.accum_add(*entry))
+
+    def aerosol(D):
+        D.aerosol_reserve()
+        D.aerosol_upload("bcphi", 0, deposition)
+
+    def active_layer(D):
+        D.active_layer_enable()
+        D.active_layer_init()
+
+    def hydrology(D):
+        D.soil_hydrology_enable()
+        D.soil_hydrology_set_params(rows[hy.HKSAT:hy.HKSAT + hy.N], rows[hy.WTFACT], rows[hy.H2OSFC_THRESH], rows[hy.K_WET], rows[hy.RSUB_TOP_MAX])
+        D.soil_hydrology_init(rows[hy.ZWT], rows[hy.WA])
+
+    def coszen(D):
+        D.set_shortwave_mode("coszen", 3600.0)
+        D.series_record_times(0, 14.875 + np.arange(NREC) / 24.0)
+
+    def topo(D):
+        D.set_column_elevation(hc, hf)
+        D.set_downscaling("topo")
+
+    F = st
+    steps = [  # (what changes, the flags from here on, the change)
+        ("nothing: the first capture", 0, None),
+        ("QBOT_IS_RH", F.RUN_QBOT_IS_RH, None),
+        ("flags back to 0", 0, None),
+        ("HISTORY with one entry", F.RUN_HISTORY, lambda D: add_history(D, 0, "t_grnd", "avg")),
+        ("a history entry more", F.RUN_HISTORY, lambda D: add_history(D, 1, "t_soisno", "max")),  # (tape 0 holds samples)
+        ("ACCUM with one entry", F.RUN_HISTORY | F.RUN_ACCUM, lambda D: add_accum(D, "t_grnd", "runmean", 3)),
+        ("an accumulator entry more", F.RUN_HISTORY | F.RUN_ACCUM, lambda D: add_accum(D, "h2osoi_liq", "timeavg", 2)),
+        ("AEROSOL", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_AEROSOL, aerosol),
+        ("ALT", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_AEROSOL | F.RUN_ALT, active_layer),
+        ("ALT flag off, the rows stay", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_AEROSOL, None),
+        ("HYDROLOGY", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT | F.RUN_HYDROLOGY, hydrology),
+        ("HYDROLOGY flag off", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, None),
+        ("shortwave COSZEN", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, coszen),
+        ("downscaling TOPO", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, topo),
+        ("downscaling groups", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, lambda D: D.set_downscaling_groups(*groups)),
+        ("groups cleared", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, lambda D: D.clear_downscaling_groups()),
+        ("downscaling off", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, lambda D: D.set_downscaling("off")),
+        ("shortwave REFERENCE", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, lambda D: D.set_shortwave_mode("reference")),
+        ("every flag", F.RUN_QBOT_IS_RH | F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_AEROSOL | F.RUN_ALT | F.RUN_HYDROLOGY, None),
+        ("flags back to 0 again", 0, None),
+    ]
+    sch = schedule()
+    for k, (what, flags, change) in enumerate(steps):
+        for D in pair:
+            if change:
+                change(D)
+            D.run(DT, sch[2 * (k % 6):2 * (k % 6) + 2], flags)
+        A, B = pair
+        assert_same_rows(A.run_diagnostics(), B.run_diagnostics())
+        for name in A.fields:
+            assert same(A[name], B[name]), (what, name)
+        for e, tape in sorted(hist.items()):
+            assert A.history_count(tape) == B.history_count(tape) > 0
+            assert same(A.history_read(e), B.history_read(e)), (what, "history", e)
+        for e in sorted(accum):
+            (va, na), (vb, nb) = A.accum_read(e), B.accum_read(e)
+            assert na == nb and same(va, vb), (what, "accumulator", e)
+        if flags & F.RUN_ALT or "ALT" in what:
+            assert all(same(A.active_layer_read(w), B.active_layer_read(w)) for w in range(3)), what
+        if flags & F.RUN_HYDROLOGY or "HYDROLOGY" in what:
+            assert same(A.soil_hydrology_rows(), B.soil_hydrology_rows()), what
+    for D in pair:
+        D.close()
+
+
 @pytest.mark.parametrize("half", [False, True])
 def test_large_launch_run_equals_stepwise(half):
     """262 144 columns (the benchmark's launch structure), three steps; ELMK_OPT_CF_HALF_WORKGROUPS off and on."""
