@@ -128,6 +128,9 @@ SIGNATURES = {
     "elmk_soil_hydrology": (C.c_int, [_P, C.c_double]),
     "elmk_soil_hydrology_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
     "elmk_soil_hydrology_clear": (C.c_int, [_P]),
+    "elmk_soil_hydrology_frost_enable": (C.c_int, [_P, _P]),
+    "elmk_soil_hydrology_frost_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_soil_hydrology_frost_clear": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

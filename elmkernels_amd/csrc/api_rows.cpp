@@ -1,5 +1,6 @@
 // api_rows.cpp - the features that keep fp64 rows [row][ld] of their own beside the state, held exactly while the feature is enabled:
-// active layer thickness (k_active_layer.hip) and soil hydrology (k_soil_hydrology.hip); include/elmk.h under those names.
+// active layer thickness (k_active_layer.hip), soil hydrology and its frost-table extension (k_soil_hydrology.hip); include/elmk.h
+// under those names.
 #include "elmk_ctx.h"
 
 namespace {
@@ -12,6 +13,7 @@ struct Rows {
 static_assert(ELMK_ALT_ALT == 0 && ELMK_ALT_ALTMAX_LASTYEAR == ALT_NROWS - 1, "three rows");
 constexpr Rows ALT{&elmk_ctx::alt_rows, ALT_NROWS, "active layer", "elmk_active_layer_enable"};
 constexpr Rows HYD{&elmk_ctx::hyd_rows, ELMK_HYD_NROWS, "soil hydrology", "elmk_soil_hydrology_enable"};
+constexpr Rows HYDF{&elmk_ctx::hydf_rows, ELMK_HYDF_NROWS, "frost table", "elmk_soil_hydrology_frost_enable"};
 
 // how every call but enable and clear begins
 int rows_enter(elmk_ctx* ctx, const Rows& R, const char* who)
@@ -73,7 +75,7 @@ ActiveLayerArgs alt_args(const elmk_ctx* ctx)
 bool hyd_land(const elmk_ctx* ctx) { return ctx->h.land.ltype == istsoil || ctx->h.land.ltype == istcrop; }
 void hyd_launch(elmk_ctx* ctx, double dt)
 {
-  if (hyd_land(ctx)) launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, dt, ctx->stream);
+  if (hyd_land(ctx)) launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, ctx->hydf_rows, dt, ctx->stream);
 }
 }  // namespace elmk
 
@@ -188,9 +190,32 @@ int elmk_soil_hydrology_read(elmk_ctx* ctx, int w, double* host, int64_t col0, i
 
 int elmk_soil_hydrology_clear(elmk_ctx* ctx)
 {
+  if (int rc = rows_clear(ctx, HYDF, "elmk_soil_hydrology_clear")) return rc;
   const int rc = rows_clear(ctx, HYD, "elmk_soil_hydrology_clear");
   if (rc == ELMK_OK) ctx->hyd_params = false;
   return rc;
 }
+
+// the frost-table extension: rows of its own beside the hydrology's, so that ELMK_HYD_NROWS stays what it is
+int elmk_soil_hydrology_frost_enable(elmk_ctx* ctx, const double* q_perch_max)
+{
+  const char* who = "elmk_soil_hydrology_frost_enable";
+  if (int rc = rows_enter(ctx, HYD, who)) return rc;
+  if (!q_perch_max) return invalid(ctx, "elmk_soil_hydrology_frost_enable: null argument");
+  if (int rc = rows_enable(ctx, HYDF, who)) return rc;  // (zero-filled: the diagnostics)
+  const size_t n = (size_t)ctx->ncols;
+  if (n && (hip_fail(ctx, hipMemcpyAsync(ctx->hydf_rows + (size_t)ELMK_HYDF_Q_PERCH_MAX * (size_t)ctx->ld, q_perch_max, n * 8, hipMemcpyHostToDevice, ctx->stream),
+                     "hipMemcpy(frost table rows)") ||
+            hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)ctx->hydf_rows.reset();
+    return ELMK_E_HIP;
+  }
+  return ELMK_OK;
+}
+
+int elmk_soil_hydrology_frost_read(elmk_ctx* ctx, int w, double* host, int64_t col0, int64_t n) { return rows_read(ctx, HYDF, "elmk_soil_hydrology_frost_read", w, host, col0, n); }
+
+int elmk_soil_hydrology_frost_clear(elmk_ctx* ctx) { return rows_clear(ctx, HYDF, "elmk_soil_hydrology_frost_clear"); }
 
 }  // extern "C"

@@ -293,7 +293,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.last_buf = buf;
   R.last_nsteps = nsteps;
   // what the captured step depends on: the stages of the flags, modes and land unit, and the tables of their versions' moment
-  const StepKey key{flags, ds_topo(ctx), ds_topo(ctx) && ctx->ds.gmem, cz, (flags & ELMK_RUN_HYDROLOGY) && hyd_land(ctx), ctx->hist_version,
+  const StepKey key{flags, ds_topo(ctx), ds_topo(ctx) && ctx->ds.gmem, cz, (flags & ELMK_RUN_HYDROLOGY) && hyd_land(ctx),
+                    (flags & ELMK_RUN_HYDROLOGY) && (bool)ctx->hydf_rows, ctx->hist_version,
                     ctx->accum_version};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;

@@ -151,13 +151,13 @@ constexpr size_t COUNTERS_BYTES = ((size_t)(2 * NLISTS + CF_NCLS) * CPAD * 4 + 2
 enum GraphId { GRAPH_TS7, GRAPH_FUSED, GRAPH_ADVANCE, GRAPH_RUN_STEP, GRAPH_N };
 
 // What the captured launches of a sequence depend on besides (dt, stream).  elmk_run's step: the run's flags, the downscaling and
-// shortwave modes, whether the soil hydrology stage is in the step (its flag is set and the land unit is soil or crop) and the
-// history and accumulator tables' versions; the other sequences have none (StepKey{}).
+// shortwave modes, whether the soil hydrology stage is in the step (its flag is set and the land unit is soil or crop), whether that
+// stage takes the frost-table form, and the history and accumulator tables' versions; the other sequences have none (StepKey{}).
 struct StepKey {
   int flags = 0;
-  bool ds_topo = false, ds_groups = false, coszen = false, hyd_stage = false;
+  bool ds_topo = false, ds_groups = false, coszen = false, hyd_stage = false, hyd_frost = false;
   uint64_t hist_version = 0, accum_version = 0;
-  auto tie() const { return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hist_version, accum_version); }
+  auto tie() const { return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version); }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
 
@@ -247,6 +247,8 @@ struct elmk_ctx {
   // soil hydrology (elmk_soil_hydrology_*): the ELMK_HYD_NROWS fp64 rows [row][ld], held exactly while the feature is enabled
   DevBuf<double> hyd_rows;
   bool hyd_params = false;  // elmk_soil_hydrology_set_params has been called since the enable
+  // its frost-table extension (elmk_soil_hydrology_frost_*): the ELMK_HYDF_NROWS fp64 rows [row][ld], held while the extension is enabled
+  DevBuf<double> hydf_rows;
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`

@@ -250,8 +250,9 @@ void launch_active_layer(const ActiveLayerArgs& A, int rollover, hipStream_t st)
 void launch_active_layer_run(const ActiveLayerArgs& A, const RunRow* rows, const int32_t* cursor, hipStream_t st);
 
 // soil hydrology (k_soil_hydrology.hip, elmk_soil_hydrology): one stage over every column; rows = the ELMK_HYD_NROWS fp64 rows of
-// the feature, [row][ld]
-void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double dt, hipStream_t st);
+// the feature, [row][ld]; frost_rows = the ELMK_HYDF_NROWS rows of the frost-table extension, which select the F' form of the kernel, or
+// null for the plain one
+void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* frost_rows, double dt, hipStream_t st);
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

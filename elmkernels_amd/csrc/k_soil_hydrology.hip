@@ -22,6 +22,7 @@ constexpr int HN = ELMK_HYD_NLAYER;  // hydrologically active layers: layer j is
 static_assert(HN == 10 && NLEVSNO + HN + 1 <= NLEVTOT + 1 && HN <= NLEVGRND, "ten layers above the bedrock layers");
 constexpr double HY_DENH2O = 1000.0, HY_DENICE = 917.0, HY_E_ICE = 6.0, HY_SMPMIN = -1.0e8, HY_WATMIN = 0.01;
 constexpr double HY_PC = 0.4, HY_MU = 0.13889, HY_FFF_S = 0.5, HY_FFF_D = 2.5, HY_AQUIFER_MAX = 5000.0, HY_ROUS_MIN = 0.02;
+constexpr double HY_TFRZ = 273.15, HY_SAT_LEV = 0.9;  // F': the frost table and the perched water table
 
 __device__ __forceinline__ double hy_sy(double zwt, double watsat, double sucsat, double bsw)
 {
@@ -30,8 +31,25 @@ __device__ __forceinline__ double hy_sy(double zwt, double watsat, double sucsat
 __device__ __forceinline__ double hy_canon(double x) { return x != x ? __builtin_nan("") : x; }
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restrict__ S, gptr<double> rows, double dt)
+// The rows a launch is handed: the feature's, and in the frost form the extension's.  The plain form keeps the kernel arguments it had
+// before the extension existed, so that its code is that kernel's, instruction for instruction.
+template <bool FROST> struct HydRows {
+  gptr<double> rows;
+};
+template <> struct HydRows<true> {
+  gptr<double> rows, frows;
+};
+
+// FROST: the F' form of the drainage (elmk_soil_hydrology_frost_enable), frows its ELMK_HYDF_NROWS rows.  It keeps nothing of its own
+// live across D and E: the ten temperatures are loaded at F'.0 and reduced at once to kf and frozen, and hksat[j] and the node depths of
+// kf, kp and kp + 1 are loaded again where they are needed.  It also loads dz and the ice again at F' and evaluates effpor and icefrac
+// from them a second time, which frees their registers during the solve: with them carried the kernel spilled to scratch (DESIGN.md
+// section 20).  Branches A and B share one conductivity sum and one removal walk: they differ in the layers and in which table the
+// walk moves.
+template <bool FROST>
+__global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restrict__ S, HydRows<FROST> R, double dt)
 {
+  const gptr<double> rows = R.rows;
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ld = S->ld;
   if (c >= S->ncols) return;
@@ -288,8 +306,124 @@ __global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restri
     if (zwt <= zi[j + 1]) jwt = j;
 
   // F. drainage
-  double rsub_top;
-  {
+  double rsub_top = 0.0;
+  [[maybe_unused]] double ft = 0.0, zwp = 0.0, qp = 0.0;
+  [[maybe_unused]] bool above = false;  // F'.A: the water table lies above the frost table, and F.1's rsub_top and F.2 are skipped
+  if constexpr (FROST) {
+    // An index the compiler cannot match with the loads at the top: what F' reads through it is loaded here, not carried across D and E.
+    int64_t cf = c;
+    asm volatile("" : "+v"(cf));
+#define SLF(f, j) S->f[(int64_t)(NLEVSNO + (j)) * ld + cf]
+    // dz and the ice are last used in A and next here, and effpor and icefrac follow from them: loaded and evaluated again (the same
+    // operands, the same bits), so that their registers are free while the solve is at its widest
+#pragma unroll
+    for (int j = 0; j < HN; j++) {
+      dz[j] = SLF(dz, j);
+      ice[j] = SLF(h2osoi_ice, j);
+      const double vol_ice = dmin(watsat[j], ice[j] / (dz[j] * HY_DENICE));
+      effpor[j] = dmax(0.01, watsat[j] - vol_ice);
+      icefrac[j] = dmin(1.0, vol_ice / watsat[j]);
+    }
+    // F'.0 the frost table: the first frozen layer under a thawed one
+    int kf;
+    bool frozen;
+    {
+      double t[HN];
+#pragma unroll
+      for (int j = 0; j < HN; j++) t[j] = SLF(t_soisno, j);
+      kf = t[0] > HY_TFRZ ? HN - 1 : 0;
+      bool found = false;
+#pragma unroll
+      for (int k = 1; k < HN; k++) {
+        if (!found && t[k - 1] > HY_TFRZ && t[k] <= HY_TFRZ) {
+          kf = k;
+          found = true;
+        }
+      }
+      double tk = t[0];
+#pragma unroll
+      for (int j = 1; j < HN; j++)
+        if (j == kf) tk = t[j];
+      frozen = tk <= HY_TFRZ;
+    }
+    ft = SLF(zsoi, kf);
+    zwp = ft;
+    above = zwt < ft && frozen;
+    int jq = jwt, j0 = jwt;  // the conductivity is summed over jq .. kf, the water is taken from j0 .. kf
+    double zw = zwt;         // the table the walk moves: zwt in A, zwp in B
+    bool drains = above;
+    if (!above) {
+      // F'.B the perched table: the first layer from kf upwards at or below sat_lev, under saturated ones
+      int kp = 0;
+      bool found = false;
+      double s1 = 0.0, s2 = 0.0, sb = 0.0, sbb = 0.0;  // v / watsat of kp and kp + 1; of the layer visited last and the one before
+#pragma unroll
+      for (int k = HN - 1; k >= 0; k--) {
+        if (k <= kf && !found) {
+          const double s = (liq[k] / (dz[k] * HY_DENH2O) + ice[k] / (dz[k] * HY_DENICE)) / watsat[k];
+          if (s <= HY_SAT_LEV) {
+            kp = k;
+            found = true;
+            s1 = s;
+            s2 = sb;
+          }
+          sbb = sb;
+          sb = s;
+        }
+      }
+      if (!found) {  // kp = 0: the walk ended at layer 0
+        s1 = sb;
+        s2 = sbb;
+      }
+      if (!frozen) kp = kf;
+      drains = kf > kp;
+      if (drains) {
+        const double zp = SLF(zsoi, kp), zp1 = SLF(zsoi, kp + 1);
+        const double m = (zp1 - zp) / (s2 - s1);
+        const double b = zp1 - m * s2;
+        zwp = dmax(0.0, m * HY_SAT_LEV + b);
+        zw = zwp;
+      }
+      jq = kp;
+      j0 = kp + 1;
+    }
+    if (drains) {
+      const double qpm = R.frows[(int64_t)ELMK_HYDF_Q_PERCH_MAX * ld + c];
+      double qk = 0.0, ws = 0.0;
+#pragma unroll
+      for (int j = 0; j < HN; j++) {
+        if (j >= jq && j <= kf) {
+          const int jp = j + 1 < HN ? j + 1 : HN - 1;
+          const double imp = elmk_pow(10.0, -HY_E_ICE * (0.5 * (icefrac[j] + icefrac[jp])));  // D.4's imped[j]
+          qk = qk + imp * rows[(int64_t)(ELMK_HYD_HKSAT + j) * ld + cf] * dzmm[j];
+          ws = ws + dzmm[j];
+        }
+      }
+      if (ws > 0.0) qk = qk / ws;
+      qp = qpm * qk * (ft - zw);
+      double rt = -qp * dt;
+      bool done = false;
+#pragma unroll
+      for (int j = 0; j < HN; j++) {
+        if (j >= j0 && j <= kf && !done) {
+          double rl = dmax(rt, -(liq[j] - HY_WATMIN));
+          rl = dmin(rl, 0.0);
+          rt = rt - rl;
+          liq[j] = liq[j] + rl;
+          if (rt >= 0.0) {
+            zw = zw - rl / effpor[j] / 1000.0;
+            done = true;
+          } else {
+            zw = zi[j + 1];
+          }
+        }
+      }
+      qp = qp + rt / dt;
+      if (above) zwt = zw;
+      else zwp = zw;
+    }
+  }
+  if (!(FROST && above)) {
     const double rous = hy_sy(zwt, watsat[L], sucsat[L], bsw[L]);
     double si = 0.0, sd = 0.0;
     const int j0 = jwt - 1 > 0 ? jwt - 1 : 0;
@@ -395,15 +529,28 @@ __global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restri
   ROW(ELMK_HYD_QFLX_RSUB_SAT) = hy_canon(rsub_sat);
   ROW(ELMK_HYD_QCHARGE) = hy_canon(qcharge);
   ROW(ELMK_HYD_FSAT) = hy_canon(fsat);
+  if constexpr (FROST) {
+    R.frows[(int64_t)ELMK_HYDF_FROST_TABLE * ld + c] = hy_canon(ft);
+    R.frows[(int64_t)ELMK_HYDF_ZWT_PERCHED * ld + c] = hy_canon(zwp);
+    R.frows[(int64_t)ELMK_HYDF_QFLX_DRAIN_PERCHED * ld + c] = hy_canon(qp);
+  }
 #undef SL
+#undef SLF
 #undef PL
 #undef ROW
 }
 
-void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double dt, hipStream_t st)
+// The plain form first in the unit's code object, where the kernel stood before the extension: with the frost form in front of it the
+// same instructions ran 1 % slower on the thawed tier.
+template __global__ void k_soil_hydrology<false>(const DevState* __restrict__, HydRows<false>, double);
+template __global__ void k_soil_hydrology<true>(const DevState* __restrict__, HydRows<true>, double);
+
+void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* frost_rows, double dt, hipStream_t st)
 {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_soil_hydrology, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, (gptr<double>)rows, dt);
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (frost_rows) hipLaunchKernelGGL(k_soil_hydrology<true>, grid, block, 0, st, S, HydRows<true>{(gptr<double>)rows, (gptr<double>)frost_rows}, dt);
+  else hipLaunchKernelGGL(k_soil_hydrology<false>, grid, block, 0, st, S, HydRows<false>{(gptr<double>)rows}, dt);
 }
 
 }  // namespace elmk

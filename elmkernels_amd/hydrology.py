@@ -7,6 +7,8 @@ text is the specification and `step` is its host truth.
     S.soil_hydrology_set_params(hksat_from_texture(...), wtfact, h2osfc_thresh(sigma), k_wet(slope), rsub_top_max(slope))
     S.soil_hydrology_init()                         # ELM's cold start: wa = 4000 mm, zwt = cold_start_zwt(zisoi)
     advance_physics(S, dt); S.soil_hydrology(dt)    # or S.run(dt, steps, RUN_HYDROLOGY)
+    S.soil_hydrology_frost_enable(q_perch_max(slope))   # optional: the frost table and the perched water table (the header's F');
+                                                        # step(..., frost=rows) is that form on the host
 
 pow, exp and erf are math.pow / math.exp / math.erf per element (glibc), which the device's elmk_pow / elmk_exp restate bit for bit;
 np.power and np.exp are not guaranteed to.  min(a, b) and max(a, b) are (b < a ? b : a) and (a < b ? b : a), written out.
@@ -20,11 +22,15 @@ N = 10  # hydrologically active soil layers: layer j is level 5 + j of h2osoi_li
 DENH2O, DENICE, E_ICE, SMPMIN, WATMIN = 1000.0, 917.0, 6.0, -1.0e8, 0.01
 PC, MU, FFF_S, FFF_D, AQUIFER_MAX, ROUS_MIN = 0.4, 0.13889, 0.5, 2.5, 5000.0, 0.02
 WA_COLD = 4000.0
+TFRZ, SAT_LEV = 273.15, 0.9  # F': the frost table and the perched water table
 
 # the rows of the feature (ELMK_HYD_*)
 ZWT, WA, HKSAT, WTFACT, H2OSFC_THRESH, K_WET, RSUB_TOP_MAX = 0, 1, 2, 12, 13, 14, 15
 QFLX_SURF, QFLX_INFL, QFLX_H2OSFC_SURF, QFLX_DRAIN, QFLX_RSUB_SAT, QCHARGE, FSAT = range(16, 23)
 NROWS = 23
+# the rows of the frost-table extension (ELMK_HYDF_*)
+Q_PERCH_MAX, FROST_TABLE, ZWT_PERCHED, QFLX_DRAIN_PERCHED = range(4)
+FROST_NROWS = 4
 DIAGNOSTICS = ("qflx_surf", "qflx_infl", "qflx_h2osfc_surf", "qflx_drain", "qflx_rsub_sat", "qcharge", "fsat")
 
 # the state fields the stage reads, and those it writes
@@ -293,32 +299,101 @@ def column(c, dt, hit=None):
 
     # F. drainage
     rous = _sy(zwt, watsat[L], sucsat[L], bsw[L])
-    si, sd = 0.0, 0.0
-    for j in range(_max(jwt - 1, 0), N):
-        si = si + icefrac[j] * dzmm[j]
-        sd = sd + dzmm[j]
-    imp = _pow(10.0, -E_ICE * _div(si, sd))
-    rsub_top = imp * c["rsub_top_max"] * _exp(-FFF_D * zwt)
-    rt = -rsub_top * dt
-    if jwt == N:
-        mark("drain_aquifer")
-        wa = wa + rt
-        zwt = zwt + _div(_div(rt, 1000.0), rous)
-        liq[L] = liq[L] + _max(0.0, wa - AQUIFER_MAX)
-        wa = _min(wa, AQUIFER_MAX)
-    else:
-        mark("drain_soil")
-        for j in range(jwt, N):
-            sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
-            ql = _min(0.0, _max(rt, -(sy * (zi[j + 1] - zwt) * 1.0e3)))
-            liq[j] = liq[j] + ql
-            rt = rt - ql
-            if rt >= 0.0:
-                zwt = zwt - _div(_div(ql, sy), 1000.0)
+    frost = "t" in c and "q_perch_max" in c
+    above = False
+    if frost:
+        # F'. the frost table and the perched water table (replace F.1 and F.2)
+        t, qpm = c["t"], c["q_perch_max"]
+
+        def qsat(j0, j1):  # the thickness-weighted conductivity of layers j0 .. j1
+            qs, ws = 0.0, 0.0
+            for j in range(j0, j1 + 1):
+                qs = qs + imped[j] * hksat[j] * dzmm[j]
+                ws = ws + dzmm[j]
+            if ws > 0.0:
+                qs = _div(qs, ws)
+            return qs
+
+        def remove(rt, j0, j1, zw):  # take -rt out of layers j0 .. j1 from the top; returns (what is left of rt, the table)
+            for j in range(j0, j1 + 1):
+                rl = _max(rt, -(liq[j] - WATMIN))
+                rl = _min(rl, 0.0)
+                rt = rt - rl
+                liq[j] = liq[j] + rl
+                if rt >= 0.0:
+                    zw = zw - _div(_div(rl, effpor[j]), 1000.0)
+                    break
+                zw = zi[j + 1]
+            return rt, zw
+
+        kf = N - 1 if t[0] > TFRZ else 0
+        for k in range(1, N):
+            if t[k - 1] > TFRZ and t[k] <= TFRZ:
+                kf = k
                 break
-            zwt = zi[j + 1]
-        zwt = zwt - _div(_div(rt, 1000.0), rous)
-        wa = wa + rt
+        ft = z[kf]
+        frozen = t[kf] <= TFRZ
+        zwp, qp = ft, 0.0
+        if zwt < ft and frozen:
+            mark("frost_A")
+            above = True
+            qp = qpm * qsat(jwt, kf) * (ft - zwt)
+            rt, zwt = remove(-qp * dt, jwt, kf, zwt)
+            if rt < 0.0:
+                mark("frost_A_exhausted")
+            qp = qp + _div(rt, dt)
+            rsub_top = 0.0
+            jwt = _jwt(zwt, zi)
+        else:
+            def v(k):
+                return _div(liq[k], dz[k] * DENH2O) + _div(ice[k], dz[k] * DENICE)
+
+            kp = 0
+            for k in range(kf, -1, -1):
+                if _div(v(k), watsat[k]) <= SAT_LEV:
+                    kp = k
+                    break
+            if not frozen:
+                kp = kf
+            if kf > kp:
+                mark("frost_B_perched")
+                s1, s2 = _div(v(kp), watsat[kp]), _div(v(kp + 1), watsat[kp + 1])
+                m = _div(z[kp + 1] - z[kp], s2 - s1)
+                b = z[kp + 1] - m * s2
+                zwp = _max(0.0, m * SAT_LEV + b)
+                qp = qpm * qsat(kp, kf) * (ft - zwp)
+                rt, zwp = remove(-qp * dt, kp + 1, kf, zwp)
+                mark("perched_ends_in_layer" if rt >= 0.0 else "perched_exhausted")
+                qp = qp + _div(rt, dt)
+            else:
+                mark("frost_B_none" if frozen else "frost_B_thawed")
+    if not above:
+        si, sd = 0.0, 0.0
+        for j in range(_max(jwt - 1, 0), N):
+            si = si + icefrac[j] * dzmm[j]
+            sd = sd + dzmm[j]
+        imp = _pow(10.0, -E_ICE * _div(si, sd))
+        rsub_top = imp * c["rsub_top_max"] * _exp(-FFF_D * zwt)
+        rt = -rsub_top * dt
+        if jwt == N:
+            mark("drain_aquifer")
+            wa = wa + rt
+            zwt = zwt + _div(_div(rt, 1000.0), rous)
+            liq[L] = liq[L] + _max(0.0, wa - AQUIFER_MAX)
+            wa = _min(wa, AQUIFER_MAX)
+        else:
+            mark("drain_soil")
+            for j in range(jwt, N):
+                sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
+                ql = _min(0.0, _max(rt, -(sy * (zi[j + 1] - zwt) * 1.0e3)))
+                liq[j] = liq[j] + ql
+                rt = rt - ql
+                if rt >= 0.0:
+                    zwt = zwt - _div(_div(ql, sy), 1000.0)
+                    break
+                zwt = zi[j + 1]
+            zwt = zwt - _div(_div(rt, 1000.0), rous)
+            wa = wa + rt
     zwt = 0.0 if zwt < 0.0 else zwt
     zwt = 80.0 if 80.0 < zwt else zwt
     for j in range(N - 1, 0, -1):
@@ -370,12 +445,15 @@ def column(c, dt, hit=None):
 
     # H. stores
     volnew = [_div(liq[j], dz[j] * DENH2O) + _div(ice[j], dz[j] * DENICE) for j in range(N)]
-    return {"liq": liq, "ice0": ice[0], "vol": volnew, "h2osfc": h2osfc, "zwt": _canon(zwt), "wa": _canon(wa),
-            "qflx_surf": _canon(qflx_surf), "qflx_infl": _canon(infl), "qflx_h2osfc_surf": _canon(qs), "qflx_drain": _canon(qflx_drain),
-            "qflx_rsub_sat": _canon(rsub_sat), "qcharge": _canon(qcharge), "fsat": _canon(fsat)}
+    o = {"liq": liq, "ice0": ice[0], "vol": volnew, "h2osfc": h2osfc, "zwt": _canon(zwt), "wa": _canon(wa),
+         "qflx_surf": _canon(qflx_surf), "qflx_infl": _canon(infl), "qflx_h2osfc_surf": _canon(qs), "qflx_drain": _canon(qflx_drain),
+         "qflx_rsub_sat": _canon(rsub_sat), "qcharge": _canon(qcharge), "fsat": _canon(fsat)}
+    if frost:
+        o["frost_table"], o["zwt_perched"], o["qflx_drain_perched"] = _canon(ft), _canon(zwp), _canon(qp)
+    return o
 
 
-def step(fields, rows, dt, hit=None, stored=None):
+def step(fields, rows, dt, hit=None, stored=None, frost=None):
     """One elmk_soil_hydrology on the host.
 
     fields: a dict of the state fields READS and h2osoi_vol as S[name] downloads them ([n] or [n, nlev], any float dtype: widened to
@@ -383,9 +461,11 @@ def step(fields, rows, dt, hit=None, stored=None):
     WRITES in the dtype and shape of the inputs (fp64 results rounded once to the stored type), rows_out the rows after the step
     (parameters unchanged, diagnostics overwritten).  Nothing is changed in place.  hit: see column().  stored: the element type the
     state is stored in where the inputs do not show it - np.float32 for downloads of the fp32-state build, which come widened to fp64:
-    the results are rounded to it before they take the inputs' dtype."""
+    the results are rounded to it before they take the inputs' dtype.  frost: float64 [FROST_NROWS, n], the rows of the frost-table
+    extension (Q_PERCH_MAX .. QFLX_DRAIN_PERCHED); with it the step takes the F' form, reads t_soisno as well and returns
+    (out, rows_out, frost_out), frost_out the extension's rows after the step."""
     dt = float(dt)
-    f = {k: np.asarray(fields[k]) for k in READS + ("h2osoi_vol",)}
+    f = {k: np.asarray(fields[k]) for k in READS + ("h2osoi_vol",) + (("t_soisno",) if frost is not None else ())}
     n = f["h2osfc"].shape[0]
     rows = np.asarray(rows, dtype=np.float64)
     assert rows.shape == (NROWS, n)
@@ -393,6 +473,10 @@ def step(fields, rows, dt, hit=None, stored=None):
     out = {k: np.array(f[k]) for k in WRITES}
     res = {k: np.array(w[k], dtype=np.float64) for k in WRITES}
     rows_out = rows.copy()
+    if frost is not None:
+        frost = np.asarray(frost, dtype=np.float64)
+        assert frost.shape == (FROST_NROWS, n)
+        frost_out = frost.copy()
     s0, s1 = NLEVSNO, NLEVSNO + N
     for i in range(n):
         c = {"liq": w["h2osoi_liq"][i, s0:s1].tolist(), "ice": w["h2osoi_ice"][i, s0:s1].tolist(), "dz": w["dz"][i, s0:s1].tolist(),
@@ -405,7 +489,12 @@ def step(fields, rows, dt, hit=None, stored=None):
         c["zwt"], c["wa"] = float(rows[ZWT, i]), float(rows[WA, i])
         c["wtfact"], c["h2osfc_thresh"] = float(rows[WTFACT, i]), float(rows[H2OSFC_THRESH, i])
         c["k_wet"], c["rsub_top_max"] = float(rows[K_WET, i]), float(rows[RSUB_TOP_MAX, i])
+        if frost is not None:
+            c["t"], c["q_perch_max"] = w["t_soisno"][i, s0:s1].tolist(), float(frost[Q_PERCH_MAX, i])
         o = column(c, dt, hit)
+        if frost is not None:
+            frost_out[FROST_TABLE, i], frost_out[ZWT_PERCHED, i] = o["frost_table"], o["zwt_perched"]
+            frost_out[QFLX_DRAIN_PERCHED, i] = o["qflx_drain_perched"]
         res["h2osoi_liq"][i, s0:s1] = o["liq"]
         res["h2osoi_ice"][i, s0] = o["ice0"]
         res["h2osoi_vol"][i, :N] = o["vol"]
@@ -422,7 +511,7 @@ def step(fields, rows, dt, hit=None, stored=None):
         out["h2osoi_ice"][:, s0] = rnd(res["h2osoi_ice"][:, s0], out["h2osoi_ice"])
         out["h2osoi_vol"][:, :N] = rnd(res["h2osoi_vol"][:, :N], out["h2osoi_vol"])
         out["h2osfc"][:] = rnd(res["h2osfc"], out["h2osfc"])
-    return out, rows_out
+    return (out, rows_out) if frost is None else (out, rows_out, frost_out)
 
 
 # ---- parameters -------------------------------------------------------------------------------------------------------------------
@@ -485,13 +574,21 @@ def rsub_top_max(topo_slope_deg):
     return 10.0 * k_wet(topo_slope_deg)
 
 
+def q_perch_max(topo_slope_deg):
+    """The perched drainage's rate parameter (1/s): 1e-5 sin(slope).  Evaluated on the host, so that the device needs no sin."""
+    return 1.0e-5 * k_wet(topo_slope_deg)
+
+
 def water_balance_error(begwb, endwb, wa_beg, wa_end, forc_rain, forc_snow, qflx_evap_tot, qflx_snwcp_ice, qflx_surf, qflx_h2osfc_surf,
-                        qflx_drain, dt):
+                        qflx_drain, dt, qflx_drain_perched=None):
     """The reference's column_water_balance_error with the aquifer in both water masses and
     hydrology_source_sink = qflx_surf + qflx_h2osfc_surf + qflx_drain in place of its hardwired 0:
-    errh2o = (endwb + wa_end) - (begwb + wa_beg) - (forc_rain + forc_snow - source_sink - qflx_evap_tot - qflx_snwcp_ice) * dt."""
+    errh2o = (endwb + wa_end) - (begwb + wa_beg) - (forc_rain + forc_snow - source_sink - qflx_evap_tot - qflx_snwcp_ice) * dt.
+    qflx_drain_perched: the frost-table extension's lateral drainage, one more term of the source/sink."""
     a = [np.asarray(v, dtype=np.float64) for v in (begwb, endwb, wa_beg, wa_end, forc_rain, forc_snow, qflx_evap_tot, qflx_snwcp_ice,
                                                    qflx_surf, qflx_h2osfc_surf, qflx_drain)]
     begwb, endwb, wa_beg, wa_end, rain, snow, evap, snwcp, surf, h2osfc_surf, drain = a
     source_sink = surf + h2osfc_surf + drain
+    if qflx_drain_perched is not None:
+        source_sink = source_sink + np.asarray(qflx_drain_perched, dtype=np.float64)
     return (endwb + wa_end) - (begwb + wa_beg) - (rain + snow - source_sink - evap - snwcp) * float(dt)

@@ -28,6 +28,7 @@ CLASS_PROGNOSTIC, CLASS_SURFACE, CLASS_FORCING, CLASS_DIAGNOSTIC = range(4)  # e
 CLASS_NAMES = ("prognostic", "surface", "forcing", "diagnostic")
 RUN_QBOT_IS_RH, RUN_HISTORY, RUN_ACCUM, RUN_AEROSOL, RUN_ALT, RUN_HYDROLOGY = 1, 2, 4, 8, 16, 32  # elmk_run flags
 HYD_NROWS, HYD_NLAYER = 23, 10  # elmk_soil_hydrology_read: the row numbers are hydrology.ZWT .. hydrology.FSAT
+HYDF_NROWS = 4  # elmk_soil_hydrology_frost_read: hydrology.Q_PERCH_MAX .. hydrology.QFLX_DRAIN_PERCHED
 ALT_ALT, ALT_ALTMAX, ALT_ALTMAX_LASTYEAR = range(3)  # elmk_active_layer_read
 ALT_ROLL_NORTH, ALT_ROLL_SOUTH = 1, 2  # elmk_active_layer_update
 ACCUM_RUNMEAN, ACCUM_TIMEAVG, ACCUM_RUNACCUM = range(3)  # elmk_accum_add
@@ -515,8 +516,33 @@ class ELMState:
         return np.stack([self.soil_hydrology_read(w) for w in range(HYD_NROWS)])
 
     def soil_hydrology_clear(self):
-        """Free the rows (the state fields keep their values)."""
+        """Free the rows, the frost-table extension's too (the state fields keep their values)."""
         self._chk(self.lib.elmk_soil_hydrology_clear(self.ctx), "soil_hydrology_clear")
+
+    def soil_hydrology_frost_enable(self, q_perch_max):
+        """The frost-table extension (include/elmk.h, F'): allocate its rows and upload q_perch_max [ncols] (hydrology.q_perch_max; a
+        scalar is broadcast).  From here on soil_hydrology and run(..., soil_hydrology=True) drain perched water above frozen layers.
+        Refused without the hydrology, when already enabled or while the stream is captured."""
+        if q_perch_max is None:
+            q = None
+        else:
+            q = np.ascontiguousarray(np.broadcast_to(np.asarray(q_perch_max, dtype=np.float64), (self.ncols,)))
+        self._chk(self.lib.elmk_soil_hydrology_frost_enable(self.ctx, None if q is None else _p(q)), "soil_hydrology_frost_enable")
+
+    def soil_hydrology_frost_read(self, which, col0=0, n=None):
+        """Row `which` (hydrology.Q_PERCH_MAX .. hydrology.QFLX_DRAIN_PERCHED) of columns [col0, col0 + n): float64 [n].  Synchronises."""
+        n = int(self.ncols - col0 if n is None else n)
+        out = np.empty(n, dtype=np.float64)
+        self._chk(self.lib.elmk_soil_hydrology_frost_read(self.ctx, int(which), _p(out), int(col0), n), "soil_hydrology_frost_read")
+        return out
+
+    def soil_hydrology_frost_rows(self):
+        """Every row of the extension: float64 [HYDF_NROWS, ncols], the `frost` of hydrology.step."""
+        return np.stack([self.soil_hydrology_frost_read(w) for w in range(HYDF_NROWS)])
+
+    def soil_hydrology_frost_clear(self):
+        """Free the extension's rows only: the stage is the plain one again."""
+        self._chk(self.lib.elmk_soil_hydrology_frost_clear(self.ctx), "soil_hydrology_frost_clear")
 
     # -- aerosol deposition (include/elmk.h: elmk_aerosol_reserve ...; elmkernels_amd/aerosol.py restates the kernel) ----------
     def aerosol_reserve(self, ncells=None, idx=None, w=None):

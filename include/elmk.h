@@ -658,7 +658,7 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  * with the h2osfc store, the Zeng-Decker Richards solve with the aquifer as an extra row, the water-table update and drainage.  The
  * reference has none of it: its conservation row hardwires hydrology_source_sink = 0.0 (driver/kokkos/conserved_quantity_kokkos.cc:22)
  * and it expects an external subsurface model, so without this stage no kernel applies qflx_top_soil, qflx_rootsoi or the ground
- * evaporation terms to the soil layers.  Out of scope: lateral flow, VSFM, perched and frost tables, irrigation, lakes, wetlands, urban.
+ * evaporation terms to the soil layers.  Out of scope: lateral flow, VSFM, irrigation, lakes, wetlands, urban.
  * This text is the specification; elmkernels_amd/hydrology.py: column() is the same operation on the host, and where an evaluation
  * order is not spelled out here that function fixes it (k_soil_hydrology.hip follows it statement by statement, bit for bit).
  *
@@ -736,6 +736,29 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  *       take = min(avail, xs); liq[N-1] = liq[N-1] + take; liq[i] = liq[i] - take; xs = max(xs - take, 0);   then
  *       liq[N-1] = liq[N-1] + xs; rsub_top = rsub_top - xs / dt; }
  *    8. qflx_drain = rsub_sat + rsub_top.
+ * F'. The frost table and the perched water table, in place of F.1 and F.2 from elmk_soil_hydrology_frost_enable on (F.3 to F.8, G and H
+ *    are unchanged).  In this part layers are 0-based, zi[j] is the bottom of layer j and z[j] is zsoi of layer j.  t[j] is level 5 + j of
+ *    t_soisno, widened to fp64 as stored; tfrz = 273.15, sat_lev = 0.9; q_perch_max is a per-column parameter row (1/s); imped[j] is
+ *    D.4's value, from the ice before the solve; effpor and icefrac are A's values; liq is the current value, after D.9; ice is as read.
+ *    0. rous = sy(N-1), as in F.1.  kf = t[0] > tfrz ? N-1 : 0; for k = 1 .. N-1 ascending: at the first k with t[k-1] > tfrz &&
+ *       t[k] <= tfrz, kf = k and stop.  ft = z[kf]; frozen = t[kf] <= tfrz; zwp = ft; qp = 0.
+ *    A. taken if zwt < ft && frozen (the water table is above the frost table; jwt <= kf follows):
+ *       qs = 0.0; ws = 0.0; for j = jwt .. kf ascending: qs = qs + imped[j] * hksat[j] * dzmm[j]; ws = ws + dzmm[j];
+ *       if (ws > 0) qs = qs / ws; qp = q_perch_max * qs * (ft - zwt); rt = -qp * dt;
+ *       for j = jwt .. kf ascending: rl = max(rt, -(liq[j] - watmin)); rl = min(rl, 0); rt = rt - rl; liq[j] = liq[j] + rl;
+ *           if (rt >= 0) { zwt = zwt - rl / effpor[j] / 1000; stop; } else zwt = zi[j];
+ *       after the walk: qp = qp + rt / dt.  rsub_top = 0; F.1's rsub_top and all of F.2 are skipped; wa is unchanged; jwt is recomputed.
+ *    B. taken otherwise (a NaN zwt lands here).  v(k) = liq[k] / (dz[k] * denh2o) + ice[k] / (dz[k] * denice).
+ *       kp = 0; for k = kf down to 0: at the first k with v(k) / watsat[k] <= sat_lev, kp = k and stop.  if (!frozen) kp = kf.
+ *       If kf > kp: s1 = v(kp) / watsat[kp]; s2 = v(kp+1) / watsat[kp+1]; m = (z[kp+1] - z[kp]) / (s2 - s1); b = z[kp+1] - m * s2;
+ *           zwp = max(0, m * sat_lev + b) (with the max above a NaN gives 0); qs, ws as in A over j = kp .. kf, with the same if (ws > 0);
+ *           qp = q_perch_max * qs * (ft - zwp); rt = -qp * dt; the walk of A over j = kp+1 .. kf with zwp in the place of zwt;
+ *           qp = qp + rt / dt.
+ *       Then F.1 (imp, rsub_top, rt) and F.2, exactly as above, on the liq the removal left.
+ *    Stores, in addition to H's: FROST_TABLE = ft, ZWT_PERCHED = zwp, QFLX_DRAIN_PERCHED = qp; a NaN is stored as the canonical quiet NaN.
+ *    Two consequences: a column whose ten t are all above tfrz, or whose only frozen layer is layer 0 with zwt >= z[0], takes B with
+ *    kp == kf, and its A to H outputs are the bits of the stage without the extension; with q_perch_max == 0 every column of B has the
+ *    bits of the stage without the extension in every A to H output (the removals add -0.0).
  * G. where snl == 0: liq[0] = liq[0] + (1 - frac_h2osfc) * qflx_dew_grnd * dt; ice[0] = ice[0] + (1 - frac_h2osfc) * qflx_dew_snow * dt;
  *    if (qflx_sub_snow * dt > ice[0]) ice[0] = 0; else ice[0] = ice[0] - (1 - frac_h2osfc) * qflx_sub_snow * dt.
  * H. h2osoi_vol[j] = liq / (dz * denh2o) + ice / (dz * denice) from the new fp64 values, j < N.  The stage writes h2osoi_liq (layers
@@ -753,6 +776,19 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  *                                   land unit (elmk_set_land) is not soil or crop enqueues nothing and returns ELMK_OK.
  *   elmk_soil_hydrology_read        row `which` (ELMK_HYD_*) of columns [col0, col0 + n) as doubles; synchronises.
  *   elmk_soil_hydrology_clear       frees the rows and drops the captured run step; the state fields keep their values.
+ * The frost-table extension owns ELMK_HYDF_NROWS fp64 rows of its own [level stride]: the parameter Q_PERCH_MAX (1/s;
+ * hydrology.q_perch_max: 1e-5 sin(slope), evaluated on the host) and the diagnostics FROST_TABLE (m), ZWT_PERCHED (m) and
+ * QFLX_DRAIN_PERCHED (mm/s), overwritten every step.  ELMK_HYD_NROWS and the rows above stay what they are.
+ *   elmk_soil_hydrology_frost_enable  allocates the rows (ELMK_HYDF_NROWS x 8 bytes x elmk_level_stride, counted in elmk_device_bytes),
+ *                                     uploads q_perch_max[ncols], zero-fills the diagnostics and drops the captured run step.  From here
+ *                                     on elmk_soil_hydrology, and elmk_run with ELMK_RUN_HYDROLOGY, take the F' form: there is no flag
+ *                                     of its own.  ELMK_E_INVALID, nothing changed: the hydrology is not enabled; already enabled; a
+ *                                     null argument; a stream being captured.
+ *   elmk_soil_hydrology_frost_read    row `which` (ELMK_HYDF_*) of columns [col0, col0 + n) as doubles; synchronises.
+ *   elmk_soil_hydrology_frost_clear   frees these rows only and drops the captured run step: the stage is F again.
+ *                                     elmk_soil_hydrology_clear frees them too.
+ * The three diagnostics are recomputed from scratch every step and the parameter stays with the driver, so the restart image of a
+ * context with the extension is byte for byte the size of the version-4 image, and N + N steps across a restart equal 2N.
  * elmk_run with ELMK_RUN_HYDROLOGY runs the stage in every step after elmk_surface_fluxes and before the step's conservation row (whose
  * errh2o keeps the reference's hardwired source_sink = 0; hydrology.water_balance_error is the closed budget); refused before anything is
  * enqueued when not enabled or without parameters.  Graph on and off give the same bits.
@@ -774,6 +810,10 @@ int elmk_soil_hydrology_init(elmk_ctx *ctx, const double *zwt /*[ncols] or NULL*
 int elmk_soil_hydrology(elmk_ctx *ctx, double dt);
 int elmk_soil_hydrology_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
 int elmk_soil_hydrology_clear(elmk_ctx *ctx);
+enum { ELMK_HYDF_Q_PERCH_MAX = 0, ELMK_HYDF_FROST_TABLE = 1, ELMK_HYDF_ZWT_PERCHED = 2, ELMK_HYDF_QFLX_DRAIN_PERCHED = 3, ELMK_HYDF_NROWS = 4 };
+int elmk_soil_hydrology_frost_enable(elmk_ctx *ctx, const double *q_perch_max /*[ncols]*/);
+int elmk_soil_hydrology_frost_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
+int elmk_soil_hydrology_frost_clear(elmk_ctx *ctx);
 
 /* ---- restart ---------------------------------------------------------------------------------
  * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state

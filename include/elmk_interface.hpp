@@ -309,6 +309,11 @@ class ELMInterface {
   void soil_hydrology(double dt_seconds) { ok(elmk_soil_hydrology(ctx_, dt_seconds)); }
   void soil_hydrology_read(int which, double* host) { ok(elmk_soil_hydrology_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
   void soil_hydrology_clear() { ok(elmk_soil_hydrology_clear(ctx_)); }
+  /* Its frost-table extension (elmk.h "soil hydrology", F'): from soil_hydrology_frost_enable(q_perch_max[ncols]) on the stage drains
+   * perched water above a frozen layer; soil_hydrology_frost_read() fills [ncols] of row ELMK_HYDF_*. */
+  void soil_hydrology_frost_enable(const double* q_perch_max) { ok(elmk_soil_hydrology_frost_enable(ctx_, q_perch_max)); }
+  void soil_hydrology_frost_read(int which, double* host) { ok(elmk_soil_hydrology_frost_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
+  void soil_hydrology_frost_clear() { ok(elmk_soil_hydrology_frost_clear(ctx_)); }
 
   /* Restart images (elmk.h "restart"): saveRestart() returns the image of the columns, global columns [gcol0, gcol0 + ncols);
    * loadRestart() takes one after setup, geography, maps and the same history and accumulator entries, in place of initialize().
