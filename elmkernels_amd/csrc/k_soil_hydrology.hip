@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restri
     double rt = -rsub_top * dt;
     if (jwt == HN) {
       wa = wa + rt;
-      zwt = zwt + rt / 1000.0 / rous;
+      zwt = zwt - rt / 1000.0 / rous;
       liq[L] = liq[L] + dmax(0.0, wa - HY_AQUIFER_MAX);
       wa = dmin(wa, HY_AQUIFER_MAX);
     } else {

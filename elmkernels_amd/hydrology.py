@@ -97,9 +97,15 @@ def _jwt(zwt, zi):
     return N
 
 
-def column(c, dt, hit=None):
+def column(c, dt, hit=None, probe=None):
     """One column: c is a dict of Python floats / lists (see step); returns the dict of outputs.  hit: a set that collects the
-    names of the branches taken (the tests assert coverage from it)."""
+    names of the branches taken (the tests assert coverage from it).  probe: a dict that receives copies of D's intermediates - the
+    tridiagonal rows a, b, cc, r and the solution u (N + 1 each), the interface fluxes q and their derivatives dq1, dq2, the
+    conductivities hk, the matric potentials smp (N each) and the equilibrium potentials zq (N + 1); and under "walks", per walk over
+    the layers that ran (E_rise, E_fall, F_drain, FA_remove, FB_remove), (the layers it visited, whether it ran off the end of the
+    layers with a remainder left)."""
+    walks = {}
+
     def mark(name):
         if hit is not None:
             hit.add(name)
@@ -249,6 +255,9 @@ def column(c, dt, hit=None):
         u[j] = _div(r[j] - a[j] * u[j - 1], bet)
     for j in range(N - 1, -1, -1):
         u[j] = u[j] - gam[j + 1] * u[j + 1]
+    if probe is not None:
+        probe.update(a=list(a), b=list(b), cc=list(cc), r=list(r), u=list(u), q=list(q), dq1=list(dq1), dq2=list(dq2), hk=list(hk),
+                     smp=list(smp), zq=list(zq), walks=walks)
     for j in range(N):
         liq[j] = liq[j] + u[j] * dzmm[j]
     # recharge
@@ -276,21 +285,25 @@ def column(c, dt, hit=None):
         qt = qcharge * dt
         if qt > 0.0:
             mark("table_rises")
+            walks["E_rise"] = (jwt + 1, True)
             for j in range(jwt, -1, -1):
                 sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
                 ql = _max(0.0, _min(qt, sy * (zwt - zi[j]) * 1.0e3))
                 zwt = zwt - _div(_div(ql, sy), 1000.0)
                 qt = qt - ql
                 if qt <= 0.0:
+                    walks["E_rise"] = (jwt - j + 1, False)
                     break
         else:
             mark("table_falls")
+            walks["E_fall"] = (N - jwt, True)
             for j in range(jwt, N):
                 sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
                 ql = _min(0.0, _max(qt, -(sy * (zi[j + 1] - zwt) * 1.0e3)))
                 qt = qt - ql
                 if qt >= 0.0:
                     zwt = zwt - _div(_div(ql, sy), 1000.0)
+                    walks["E_fall"] = (j - jwt + 1, False)
                     break
                 zwt = zi[j + 1]
             if qt < 0.0:
@@ -314,7 +327,8 @@ def column(c, dt, hit=None):
                 qs = _div(qs, ws)
             return qs
 
-        def remove(rt, j0, j1, zw):  # take -rt out of layers j0 .. j1 from the top; returns (what is left of rt, the table)
+        def remove(rt, j0, j1, zw, walk):  # take -rt out of layers j0 .. j1 from the top; returns (what is left of rt, the table)
+            walks[walk] = (j1 - j0 + 1, True)
             for j in range(j0, j1 + 1):
                 rl = _max(rt, -(liq[j] - WATMIN))
                 rl = _min(rl, 0.0)
@@ -322,6 +336,7 @@ def column(c, dt, hit=None):
                 liq[j] = liq[j] + rl
                 if rt >= 0.0:
                     zw = zw - _div(_div(rl, effpor[j]), 1000.0)
+                    walks[walk] = (j - j0 + 1, False)
                     break
                 zw = zi[j + 1]
             return rt, zw
@@ -338,7 +353,7 @@ def column(c, dt, hit=None):
             mark("frost_A")
             above = True
             qp = qpm * qsat(jwt, kf) * (ft - zwt)
-            rt, zwt = remove(-qp * dt, jwt, kf, zwt)
+            rt, zwt = remove(-qp * dt, jwt, kf, zwt, "FA_remove")
             if rt < 0.0:
                 mark("frost_A_exhausted")
             qp = qp + _div(rt, dt)
@@ -362,7 +377,7 @@ def column(c, dt, hit=None):
                 b = z[kp + 1] - m * s2
                 zwp = _max(0.0, m * SAT_LEV + b)
                 qp = qpm * qsat(kp, kf) * (ft - zwp)
-                rt, zwp = remove(-qp * dt, kp + 1, kf, zwp)
+                rt, zwp = remove(-qp * dt, kp + 1, kf, zwp, "FB_remove")
                 mark("perched_ends_in_layer" if rt >= 0.0 else "perched_exhausted")
                 qp = qp + _div(rt, dt)
             else:
@@ -378,11 +393,12 @@ def column(c, dt, hit=None):
         if jwt == N:
             mark("drain_aquifer")
             wa = wa + rt
-            zwt = zwt + _div(_div(rt, 1000.0), rous)
+            zwt = zwt - _div(_div(rt, 1000.0), rous)
             liq[L] = liq[L] + _max(0.0, wa - AQUIFER_MAX)
             wa = _min(wa, AQUIFER_MAX)
         else:
             mark("drain_soil")
+            walks["F_drain"] = (N - jwt, True)
             for j in range(jwt, N):
                 sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
                 ql = _min(0.0, _max(rt, -(sy * (zi[j + 1] - zwt) * 1.0e3)))
@@ -390,6 +406,7 @@ def column(c, dt, hit=None):
                 rt = rt - ql
                 if rt >= 0.0:
                     zwt = zwt - _div(_div(ql, sy), 1000.0)
+                    walks["F_drain"] = (j - jwt + 1, False)
                     break
                 zwt = zi[j + 1]
             zwt = zwt - _div(_div(rt, 1000.0), rous)
@@ -453,7 +470,7 @@ def column(c, dt, hit=None):
     return o
 
 
-def step(fields, rows, dt, hit=None, stored=None, frost=None):
+def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None):
     """One elmk_soil_hydrology on the host.
 
     fields: a dict of the state fields READS and h2osoi_vol as S[name] downloads them ([n] or [n, nlev], any float dtype: widened to
@@ -463,7 +480,8 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None):
     state is stored in where the inputs do not show it - np.float32 for downloads of the fp32-state build, which come widened to fp64:
     the results are rounded to it before they take the inputs' dtype.  frost: float64 [FROST_NROWS, n], the rows of the frost-table
     extension (Q_PERCH_MAX .. QFLX_DRAIN_PERCHED); with it the step takes the F' form, reads t_soisno as well and returns
-    (out, rows_out, frost_out), frost_out the extension's rows after the step."""
+    (out, rows_out, frost_out), frost_out the extension's rows after the step.  probes: a list that receives column()'s probe of every
+    column in turn."""
     dt = float(dt)
     f = {k: np.asarray(fields[k]) for k in READS + ("h2osoi_vol",) + (("t_soisno",) if frost is not None else ())}
     n = f["h2osfc"].shape[0]
@@ -491,7 +509,11 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None):
         c["k_wet"], c["rsub_top_max"] = float(rows[K_WET, i]), float(rows[RSUB_TOP_MAX, i])
         if frost is not None:
             c["t"], c["q_perch_max"] = w["t_soisno"][i, s0:s1].tolist(), float(frost[Q_PERCH_MAX, i])
-        o = column(c, dt, hit)
+        if probes is None:
+            o = column(c, dt, hit)
+        else:
+            probes.append({})
+            o = column(c, dt, hit, probes[-1])
         if frost is not None:
             frost_out[FROST_TABLE, i], frost_out[ZWT_PERCHED, i] = o["frost_table"], o["zwt_perched"]
             frost_out[QFLX_DRAIN_PERCHED, i] = o["qflx_drain_perched"]

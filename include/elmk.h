@@ -725,7 +725,7 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  * F. 1. rous = sy(N-1) again (ELM's Drainage recomputes it); imp = pow(10, -e_ice * (si / sd)), si = sum of icefrac * dzmm and sd = sum
  *       of dzmm over j = max(jwt-1, 0) .. N-1, each from 0.0 in ascending j; rsub_top = imp * rsub_top_max * exp(-fff_d * zwt);
  *       rt = -rsub_top * dt.
- *    2. jwt == N: wa = wa + rt; zwt = zwt + rt / 1000 / rous; liq[N-1] = liq[N-1] + max(0, wa - aquifer_max); wa = min(wa, aquifer_max).
+ *    2. jwt == N: wa = wa + rt; zwt = zwt - rt / 1000 / rous; liq[N-1] = liq[N-1] + max(0, wa - aquifer_max); wa = min(wa, aquifer_max).
  *       Else the falling walk of E with rt for qt and liq[j] = liq[j] + ql in every visited layer, then (always) zwt = zwt - rt / 1000 / rous
  *       and wa = wa + rt with the rt that is left.
  *    3. zwt = zwt < 0 ? 0 : zwt; zwt = 80 < zwt ? 80 : zwt   (a NaN stays).

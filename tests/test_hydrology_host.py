@@ -1,5 +1,6 @@
 """Soil hydrology on the host (include/elmk.h "soil hydrology"; elmkernels_amd/hydrology.py): hand-checked columns of `step`, the exact
-water budget of one step, the parameter helpers, the header's constants and symbols, and restart images of version 4."""
+water budget of one step, the parameter helpers, the header's constants and symbols, and restart images of version 4; and the
+generators of the stage's inputs: `generated` (every branch) and `edge_columns` (the edge tier; tests/test_hydrology_edges_host.py)."""
 import math
 import os
 import re
@@ -88,6 +89,279 @@ def generated(n, seed, sfc_every=4, full=False, chain=False):
         clear_snow(cols)
     rows = prepare(cols, seed + 1, sfc_every)
     return (cols, scal, soil, rows) if full else (cols, rows)
+
+
+# ---- the edge tier ------------------------------------------------------------------------------------------------------------------
+SOIL_FIELDS = ("h2osoi_liq", "h2osoi_ice", "dz", "zsoi", "zisoi")  # fields that carry the snow levels: layer j is level NLEVSNO + j
+POISONS = (float("nan"), float("inf"), float("-inf"))
+POISONED_ROWS = tuple(range(hy.ZWT, hy.RSUB_TOP_MAX + 1))  # ZWT, WA, the ten HKSAT rows, WTFACT .. RSUB_TOP_MAX
+# snl is the one integer field of hydrology.READS: it has no NaN and no infinity
+POISONED_FIELDS = tuple(k for k in hy.READS if k != "snl") + ("t_soisno",)
+
+
+def edge_classes():
+    """The classes of edge_columns in the order they are dealt: [(name, function of (E, i, k))], E the _Edge under construction, i the
+    column and k a counter that moves the layer a class touches from one round of the classes to the next."""
+    s0 = hy.NLEVSNO
+    out = []
+    turn = (9, 0, 5, 1, 8, 2, 7, 3, 6, 4)  # the layer of round k: the bottom and the top layer first
+
+    def add(name):
+        def deco(f):
+            out.append((name, f))
+            return f
+        return deco
+
+    def dzmm(E, i, j):
+        return float(E.cols["dz"][i, s0 + j]) * 1.0e3
+
+    def wet(E, i, hs=20.0, fh=0.6):
+        E.cols["h2osfc"][i], E.cols["frac_h2osfc"][i] = hs, fh
+
+    # the water table and the aquifer
+    add("zwt=0")(lambda E, i, k: E.row(hy.ZWT, i, 0.0))
+    add("zwt=1e-9")(lambda E, i, k: E.row(hy.ZWT, i, 1.0e-9))
+    for j in range(N):
+        @add(f"zwt=zisoi[{j}]")
+        def _(E, i, k, j=j):
+            # (the interfaces of this column are made fp32 values, so that the equality holds in the fp32-state build too)
+            E.cols["zisoi"][i] = E.cols["zisoi"][i].astype(np.float32)
+            E.row(hy.ZWT, i, float(E.cols["zisoi"][i, s0 + j + 1]))
+    add("zwt=80")(lambda E, i, k: E.row(hy.ZWT, i, 80.0))
+    add("zwt=100")(lambda E, i, k: E.row(hy.ZWT, i, 100.0))
+    add("zwt just below the column")(lambda E, i, k: E.row(hy.ZWT, i, float(np.nextafter(E.cols["zisoi"][i, s0 + N], 100.0))))
+    add("wa=0")(lambda E, i, k: E.row(hy.WA, i, 0.0))
+
+    @add("wa=0, table below")
+    def _(E, i, k):
+        E.row(hy.WA, i, 0.0)
+        E.row(hy.ZWT, i, 8.0)
+
+    @add("wa=5000")
+    def _(E, i, k):
+        E.row(hy.WA, i, 5000.0)
+        E.row(hy.ZWT, i, 8.0)
+
+    @add("wa>5000")
+    def _(E, i, k):
+        E.row(hy.WA, i, 5500.0)
+        E.row(hy.ZWT, i, 8.0)
+        E.row(hy.RSUB_TOP_MAX, i, 0.0)
+
+    # conductivity, ice and water content
+    add("hksat=0 in one layer")(lambda E, i, k: E.row(hy.HKSAT + k % N, i, 0.0))
+
+    @add("hksat=0")
+    def _(E, i, k):
+        E.rows[hy.HKSAT:hy.HKSAT + N, i] = 0.0
+    add("rsub_top_max=0")(lambda E, i, k: E.row(hy.RSUB_TOP_MAX, i, 0.0))
+
+    @add("ice beyond the pores")
+    def _(E, i, k):
+        for j in range(k % 4, N, 3):
+            E.cols["h2osoi_ice"][i, s0 + j] = 1.5 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j) * 0.917
+
+    @add("liq=0 in one layer")
+    def _(E, i, k):
+        E.cols["h2osoi_liq"][i, s0 + k % N] = 0.0
+
+    @add("liq=0")
+    def _(E, i, k):
+        E.cols["h2osoi_liq"][i, s0:s0 + N] = 0.0
+
+    @add("liq<1e-6")
+    def _(E, i, k):
+        E.cols["h2osoi_liq"][i, s0:s0 + N] = 9.0e-8 * (1.0 + np.arange(N))
+
+    @add("bottom layer under 1 %, table below")
+    def _(E, i, k):
+        E.cols["h2osoi_liq"][i, s0 + N - 1] = 0.004 * float(E.cols["watsat"][i, N - 1]) * dzmm(E, i, N - 1)
+        E.cols["h2osoi_ice"][i, s0 + N - 1] = 0.0
+        E.row(hy.ZWT, i, 8.0)
+
+    @add("table layer under 1 %")
+    def _(E, i, k):
+        j = 2 + k % 7
+        E.cols["h2osoi_liq"][i, s0 + j] = 0.004 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j)
+        E.cols["h2osoi_ice"][i, s0 + j] = 0.0
+        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + j]))
+
+    @add("root uptake beyond the water")
+    def _(E, i, k):
+        j = k % 8
+        E.cols["qflx_rootsoi"][i, j] = 2.0 * float(E.cols["h2osoi_liq"][i, s0 + j])
+
+    # the surface fractions
+    add("frac_h2osfc=0")(lambda E, i, k: wet(E, i, 0.0, 0.0))
+    add("frac_h2osfc=0.4")(lambda E, i, k: wet(E, i, 20.0, 0.4))
+    add("frac_h2osfc=1")(lambda E, i, k: wet(E, i, 30.0, 1.0))
+    add("frac_h2osfc just above 0.4")(lambda E, i, k: wet(E, i, 20.0, float(np.nextafter(0.4, 1.0))))
+
+    @add("h2osfc at its threshold")
+    def _(E, i, k):
+        wet(E, i, float(E.rows[hy.H2OSFC_THRESH, i]))
+
+    @add("no rain, evaporation")
+    def _(E, i, k):
+        E.cols["qflx_top_soil"][i] = 0.0
+        E.cols["qflx_evap_grnd"][i] = E.cols["qflx_ev_soil"][i] = 1.0e-4
+
+    @add("frac_sno_eff=0")
+    def _(E, i, k):
+        E.cols["frac_sno_eff"][i] = 0.0
+
+    @add("frac_sno_eff=1")
+    def _(E, i, k):
+        E.cols["frac_sno_eff"][i] = 1.0
+
+    @add("tiny k_wet")
+    def _(E, i, k):
+        wet(E, i)
+        E.row(hy.K_WET, i, 1.0e-6)
+
+    # the soil parameters
+    def params(name, bsw=None, sucsat=None, watsat=None, also=None):
+        @add(name)
+        def _(E, i, k):
+            for key, v in (("bsw", bsw), ("sucsat", sucsat), ("watsat", watsat)):
+                if v is not None:
+                    E.cols[key][i, :N] = v
+            if also:
+                also(E, i, k)
+
+    def dry(E, i, k):
+        E.cols["h2osoi_liq"][i, s0:s0 + N] = 0.02
+        E.cols["h2osoi_ice"][i, s0:s0 + N] = 0.0
+
+    def deep(E, i, k):
+        E.row(hy.ZWT, i, 80.0)
+    params("bsw=1.5", bsw=1.5)
+    params("bsw=20", bsw=20.0)
+    params("sucsat=10", sucsat=10.0)
+    params("sucsat=1000", sucsat=1000.0)
+    params("watsat=0.2", watsat=0.2)
+    params("watsat=0.9", watsat=0.9)
+    params("bsw=20, sucsat=1000, dry", bsw=20.0, sucsat=1000.0, also=dry)       # smp at SMPMIN
+    params("bsw=1.5, sucsat=10, deep table", bsw=1.5, sucsat=10.0, also=deep)  # the equilibrium profile under 1 % of saturation
+    params("layered parameters", bsw=np.array([1.5, 20.0, 3.0, 12.0, 1.5, 20.0, 7.0, 2.0, 16.0, 5.0]),
+           sucsat=np.array([10.0, 1000.0, 40.0, 600.0, 1000.0, 10.0, 200.0, 90.0, 15.0, 800.0]),
+           watsat=np.array([0.9, 0.2, 0.6, 0.3, 0.2, 0.9, 0.45, 0.8, 0.25, 0.5]))
+
+    # the walks: over a wet column a shallow table rises through the layers; a strong drainage runs down through them
+    @add("rise to the surface")
+    def _(E, i, k):
+        E.cols["h2osoi_ice"][i, s0:s0 + N] = 0.0
+        for j in range(N):
+            E.cols["h2osoi_liq"][i, s0 + j] = 0.999 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j)
+        E.rows[hy.HKSAT:hy.HKSAT + N, i] = 0.5
+        # a small specific yield: the recharge, bounded by 10 mm a step, fills layer after layer
+        E.cols["bsw"][i, :N], E.cols["sucsat"][i, :N] = 20.0, 1000.0
+        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + 2 + k % 4]))
+
+    @add("drain through the column")
+    def _(E, i, k):
+        E.row(hy.RSUB_TOP_MAX, i, 50.0 if k % 2 else 0.05)
+        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + 1 + k % 4]))
+
+    @add("fall through the column")
+    def _(E, i, k):
+        # drier than the equilibrium over a shallow table: the recharge is negative and at its bound
+        E.cols["h2osoi_ice"][i, s0:s0 + N] = 0.0
+        for j in range(N):
+            E.cols["h2osoi_liq"][i, s0 + j] = 0.3 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j)
+        E.rows[hy.HKSAT:hy.HKSAT + N, i] = 5.0
+        E.cols["bsw"][i, :N] = 1.5
+        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + (6 if k % 2 else 1)]))
+
+    # the frost form
+    @add("t_soisno=tfrz at the front")
+    def _(E, i, k):
+        kf = 1 + k % (N - 1)
+        E.cols["t_soisno"][i, s0:s0 + kf] = 275.0
+        E.cols["t_soisno"][i, s0 + kf:s0 + N] = hy.TFRZ
+
+    @add("q_perch_max=0")
+    def _(E, i, k):
+        if E.frost is not None:
+            E.frost[hy.Q_PERCH_MAX, i] = 0.0
+
+    @add("dz=0 in one layer")
+    def _(E, i, k):
+        E.cols["dz"][i, s0 + turn[k % N]] = 0.0
+
+    # the non-finite tier: one poisoned input per column
+    for v in POISONS:
+        for key in POISONED_FIELDS:
+            @add(f"{key}={v}")
+            def _(E, i, k, key=key, v=v):
+                a = E.cols[key]
+                if a.ndim == 1:
+                    a[i] = v
+                elif key in SOIL_FIELDS or key == "t_soisno":
+                    a[i, s0 + turn[k % N]] = v
+                else:
+                    a[i, turn[k % N]] = v
+        for w in POISONED_ROWS:
+            add(f"row {w}={v}")(lambda E, i, k, w=w, v=v: E.row(w, i, v))
+
+        @add(f"q_perch_max={v}")
+        def _(E, i, k, v=v):
+            if E.frost is not None:
+                E.frost[hy.Q_PERCH_MAX, i] = v
+
+        # the aquifer node takes the bottom layer's parameters: poisoned under a table below the column
+        for key in ("watsat", "sucsat", "bsw"):
+            @add(f"table below, bottom {key}={v}")
+            def _(E, i, k, key=key, v=v):
+                E.cols[key][i, N - 1] = v
+                E.row(hy.ZWT, i, 8.0)
+    return out
+
+
+class _Edge:
+    def __init__(self, cols, rows, frost):
+        self.cols, self.rows, self.frost = cols, rows, frost
+
+    def row(self, w, i, v):
+        self.rows[w, i] = v
+
+
+EDGE_CLASS_NAMES = tuple(name for name, _ in edge_classes())
+
+
+def edge_class_of(n):
+    """The class of every column of edge_columns(n, ...): an index into EDGE_CLASS_NAMES."""
+    return np.arange(n) % len(EDGE_CLASS_NAMES)
+
+
+def edge_finite(n):
+    """The columns of edge_columns(n, ...) outside the non-finite tier."""
+    first = EDGE_CLASS_NAMES.index("dz=0 in one layer")
+    return edge_class_of(n) < first
+
+
+def edge_columns(n, seed, frost=False, full=False, skip=()):
+    """The edge tier of the stage: generated (frost: generated_frost) with one edge per column, the classes of edge_classes() dealt to
+    the columns in turn and the layer a class touches moved on with every round.  A class changes only what it names, so every edge
+    meets the generator's mix of the other inputs.  skip: names of classes left as the generator made them (the census test shows
+    with it that a class is needed).  Returns (cols, [scal, soil,] rows[, frost rows])."""
+    cols, scal, soil, rows = generated(n, seed, full=True)
+    fr = None
+    if frost:
+        from tests.test_frost_table_host import add_frost
+
+        fr = add_frost(cols, rows, seed + 2)
+    for k in POISONED_FIELDS + ("qflx_rootsoi",):
+        cols[k] = np.array(cols[k], dtype=np.float64)
+    E = _Edge(cols, rows, fr)
+    classes = edge_classes()
+    assert not set(skip) - set(EDGE_CLASS_NAMES)
+    for i in range(n):
+        name, f = classes[i % len(classes)]
+        if name not in skip:
+            f(E, i, i // len(classes))
+    out = (cols, scal, soil, rows) if full else (cols, rows)
+    return out + (fr,) if frost else out
 
 
 # ---- the chain: the physics of one step, then the stage -----------------------------------------------------------------------------
