@@ -137,6 +137,11 @@ SIGNATURES = {
     "elmk_water_balance_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
     "elmk_water_balance_clear": (C.c_int, [_P]),
     "elmk_run_water_balance": (C.c_int, [_P, _P, _P, _P]),
+    "elmk_irrigation_enable": (C.c_int, [_P, _P]),
+    "elmk_irrigation_init": (C.c_int, [_P, _P, _P]),
+    "elmk_irrigation": (C.c_int, [_P, C.c_double, C.c_int]),
+    "elmk_irrigation_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_irrigation_clear": (C.c_int, [_P]),
     "elmk_column_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_gridded_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
 }

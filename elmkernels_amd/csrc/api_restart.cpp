@@ -110,8 +110,10 @@ const RstKind RST_OPTIONAL[] = {
     {ELMK_RESTART_ALT, ELMK_RESTART_VERSION_ALT, "the active layer thickness", "elmk_active_layer_enable",
      [](Ctx c) { return c->alt_rows ? ALT_NROWS : 0; }, [](Ctx c, int i) { return RstRows{i, 1, c->alt_rows + (size_t)i * (size_t)c->ld}; }},
     {ELMK_RESTART_HYDROLOGY, ELMK_RESTART_VERSION_HYDROLOGY, "the soil hydrology", "elmk_soil_hydrology_enable", [](Ctx c) { return c->hyd_rows ? 2 : 0; },
-     [](Ctx c, int i) { return RstRows{ELMK_HYD_ZWT + i, 1, c->hyd_rows + (size_t)(ELMK_HYD_ZWT + i) * (size_t)c->ld}; }}};
-static_assert(ELMK_HYD_WA == ELMK_HYD_ZWT + 1, "the two rows of the image");
+     [](Ctx c, int i) { return RstRows{ELMK_HYD_ZWT + i, 1, c->hyd_rows + (size_t)(ELMK_HYD_ZWT + i) * (size_t)c->ld}; }},
+    {ELMK_RESTART_IRRIGATION, ELMK_RESTART_VERSION_IRRIGATION, "the irrigation", "elmk_irrigation_enable", [](Ctx c) { return c->irr_rows ? 2 : 0; },
+     [](Ctx c, int i) { return RstRows{ELMK_IRR_RATE + i, 1, c->irr_rows + (size_t)(ELMK_IRR_RATE + i) * (size_t)c->ld}; }}};
+static_assert(ELMK_HYD_WA == ELMK_HYD_ZWT + 1 && ELMK_IRR_NLEFT == ELMK_IRR_RATE + 1, "the two rows of the image");
 
 RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
 {

@@ -1,23 +1,18 @@
 // api_rows.cpp - the features that keep fp64 rows [row][ld] of their own beside the state, held exactly while the feature is enabled:
 // active layer thickness (k_active_layer.hip), soil hydrology and its frost-table extension (k_soil_hydrology.hip), the water balance
-// (k_water_balance.hip); include/elmk.h under those names.
+// (k_water_balance.hip); include/elmk.h under those names.  The irrigation's rows are api_irrigation.cpp's.
 #include "elmk_ctx.h"
 
 namespace {
-struct Rows {
-  DevBuf<double> elmk_ctx::*buf;
-  int nrows;
-  const char* label;   // in the text of a HIP error
-  const char* enable;  // the enabling call, for refusals
-  int family;          // ELMK_ROWS_*: history entries over these rows (elmk_column_history_add_row) bar the clear
-};
 static_assert(ELMK_ALT_ALT == 0 && ELMK_ALT_ALTMAX_LASTYEAR == ALT_NROWS - 1, "three rows");
 constexpr Rows ALT{&elmk_ctx::alt_rows, ALT_NROWS, "active layer", "elmk_active_layer_enable", ELMK_ROWS_ALT};
 constexpr Rows HYD{&elmk_ctx::hyd_rows, ELMK_HYD_NROWS, "soil hydrology", "elmk_soil_hydrology_enable", ELMK_ROWS_HYDROLOGY};
 constexpr Rows HYDF{&elmk_ctx::hydf_rows, ELMK_HYDF_NROWS, "frost table", "elmk_soil_hydrology_frost_enable", ELMK_ROWS_FROST};
 constexpr Rows WB{&elmk_ctx::wb_rows, ELMK_WB_NROWS, "water balance", "elmk_water_balance_enable", ELMK_ROWS_WATER_BALANCE};
-constexpr const Rows* FAMILY[ELMK_ROWS_NFAMILY] = {&ALT, &HYD, &HYDF, &WB};
+const Rows* const FAMILY[ELMK_ROWS_NFAMILY] = {&ALT, &HYD, &HYDF, &WB, &ROWS_OF_IRRIGATION};
+}  // namespace
 
+namespace elmk {
 // while a history entry reads the family's rows they stay: "<who>: history entries over the rows exist (elmk_history_clear first)"
 int rows_held(elmk_ctx* ctx, const Rows& R, const char* who)
 {
@@ -30,26 +25,6 @@ int rows_enter(elmk_ctx* ctx, const Rows& R, const char* who)
 {
   if (int rc = enter(ctx)) return rc;
   return ctx->*R.buf ? ELMK_OK : invalid(ctx, (std::string(who) + ": not enabled (" + R.enable + ")").c_str());
-}
-
-// allocate and zero the rows; nothing is held after a failure
-int rows_enable(elmk_ctx* ctx, const Rows& R, const char* who)
-{
-  if (int rc = enter(ctx)) return rc;
-  DevBuf<double>& buf = ctx->*R.buf;
-  if (buf) return invalid(ctx, (std::string(who) + ": already enabled").c_str());
-  if (int rc = refuse_capture(ctx, who)) return rc;
-  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the stages of its flags' moment)
-  const size_t bytes = (size_t)R.nrows * (size_t)ctx->ld * sizeof(double);
-  const std::string what = std::string("(") + R.label + " rows)";
-  if (hip_fail(ctx, buf.alloc(bytes), ("hipMalloc" + what).c_str())) return ELMK_E_NOMEM;
-  if (hip_fail(ctx, hipMemsetAsync(buf, 0, bytes, ctx->stream), ("hipMemset" + what).c_str()) ||
-      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)buf.reset();
-    return ELMK_E_HIP;
-  }
-  return ELMK_OK;
 }
 
 // columns [col0, col0 + n) of one row; synchronises
@@ -72,6 +47,29 @@ int rows_clear(elmk_ctx* ctx, const Rows& R, const char* who)
   if (int rc = rows_held(ctx, R, who)) return rc;
   if (int rc = quiesce(ctx, false)) return rc;
   HIPCHK((ctx->*R.buf).reset());
+  return ELMK_OK;
+}
+
+}  // namespace elmk
+
+namespace {
+// allocate and zero the rows; nothing is held after a failure
+int rows_enable(elmk_ctx* ctx, const Rows& R, const char* who)
+{
+  if (int rc = enter(ctx)) return rc;
+  DevBuf<double>& buf = ctx->*R.buf;
+  if (buf) return invalid(ctx, (std::string(who) + ": already enabled").c_str());
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the stages of its flags' moment)
+  const size_t bytes = (size_t)R.nrows * (size_t)ctx->ld * sizeof(double);
+  const std::string what = std::string("(") + R.label + " rows)";
+  if (hip_fail(ctx, buf.alloc(bytes), ("hipMalloc" + what).c_str())) return ELMK_E_NOMEM;
+  if (hip_fail(ctx, hipMemsetAsync(buf, 0, bytes, ctx->stream), ("hipMemset" + what).c_str()) ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)buf.reset();
+    return ELMK_E_HIP;
+  }
   return ELMK_OK;
 }
 
@@ -122,7 +120,7 @@ void wb_launch(elmk_ctx* ctx, double dt, bool run)
   if (!hyd_land(ctx)) return;
   launch_water_balance(ctx->d, ctx->ncols, ctx->ld, ctx->hyd_rows, ctx->hydf_rows, ctx->wb_rows, dt, ctx->wb_tol, ctx->wb_part, ctx->wb_out,
                        run ? ctx->wb_ring_mms : nullptr, run ? ctx->wb_ring_census : ctx->wb_census, run ? ctx->run.cursor : nullptr,
-                       ctx->stream);
+                       ctx->stream, ctx->irr_rows ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * (size_t)ctx->ld : nullptr);
 }
 int wb_ring_alloc(elmk_ctx* ctx)
 {

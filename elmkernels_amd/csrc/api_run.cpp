@@ -112,7 +112,8 @@ bool all_finite(const double* a, int64_t n)
 
 // one model step of elmk_run, in the order of the stand-alone calls it replaces (include/elmk.h): solar geometry, phenology,
 // forcing, aerosol deposition (ELMK_RUN_AEROSOL: where the reference's hook sits, init_timestep_kokkos.cc:48-49), init_timestep,
-// the water balance's begin (ELMK_RUN_WATER_BALANCE), advance_physics' stages (one stage here: launch_advance), soil hydrology
+// the water balance's begin (ELMK_RUN_WATER_BALANCE), advance_physics' stages (one stage here: launch_advance, with the irrigation stage
+// in front of soil_temperature under ELMK_RUN_IRRIGATION), soil hydrology
 // (ELMK_RUN_HYDROLOGY), conservation -> ring row, flag summary -> ring row, water balance -> its ring rows, active layer thickness
 // (ELMK_RUN_ALT), accumulated fields, history, next row
 constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},     {run_forcing, nullptr},        {run_aerosol, nullptr},
@@ -242,7 +243,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   if (!ctx->snowage_set) return invalid(ctx, "elmk_run: the snow-age tables are not set (elmk_set_snow_age_tables)");
   if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
   if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
-  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL | ELMK_RUN_ALT | ELMK_RUN_HYDROLOGY | ELMK_RUN_WATER_BALANCE))
+  if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL | ELMK_RUN_ALT | ELMK_RUN_HYDROLOGY | ELMK_RUN_WATER_BALANCE |
+                ELMK_RUN_IRRIGATION))
     return invalid(ctx, "elmk_run: unknown flags");
   if ((flags & ELMK_RUN_AEROSOL) && !ctx->aer.mem) return invalid(ctx, "elmk_run: ELMK_RUN_AEROSOL without an aerosol series (elmk_aerosol_reserve)");
   if ((flags & ELMK_RUN_ACCUM) && ctx->accum.empty()) return invalid(ctx, "elmk_run: ELMK_RUN_ACCUM without an accumulator entry (elmk_accum_add)");
@@ -256,6 +258,10 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
     return invalid(ctx, "elmk_run: ELMK_RUN_WATER_BALANCE without the water balance enabled (elmk_water_balance_enable)");
   if ((flags & ELMK_RUN_WATER_BALANCE) && !(flags & ELMK_RUN_HYDROLOGY))
     return invalid(ctx, "elmk_run: ELMK_RUN_WATER_BALANCE without ELMK_RUN_HYDROLOGY");
+  if ((flags & ELMK_RUN_IRRIGATION) && !ctx->irr_rows)
+    return invalid(ctx, "elmk_run: ELMK_RUN_IRRIGATION without the irrigation enabled (elmk_irrigation_enable)");
+  if ((flags & ELMK_RUN_IRRIGATION) && !(dt >= 1.0 && dt <= 86400.0 && dt == std::floor(dt)))
+    return invalid(ctx, "elmk_run: ELMK_RUN_IRRIGATION needs dt to be a whole number of seconds in 1 .. 86400");
   const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   int lo = R.slots, hi = -1;
   unsigned months = 0;
@@ -296,6 +302,11 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
     r.pad = !(flags & ELMK_RUN_ALT) ? 0
                                     : (p.doy == 0 && p.decday == 1.0 ? ELMK_ALT_ROLL_NORTH : 0) |
                                           (p.doy == 181 && p.decday == 182.0 ? ELMK_ALT_ROLL_SOUTH : 0);
+    // the irrigation's time of day: seconds after midnight UTC at the step's start, above the rollover bits
+    if (flags & ELMK_RUN_IRRIGATION) {
+      const long long t = std::llround((p.decday - 1.0 - (double)p.doy) * 86400.0);
+      r.pad |= (int32_t)(((t % 86400) + 86400) % 86400) << RUN_PAD_TOD_SHIFT;
+    }
   }
   const int row0 = buf * R.max_steps;
   HIPCHK(hipMemcpyAsync(R.table + row0, rows, (size_t)nsteps * sizeof(RunRow), hipMemcpyHostToDevice, ctx->stream));
@@ -314,7 +325,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   // what the captured step depends on: the stages of the flags, modes and land unit, and the tables of their versions' moment
   const StepKey key{flags, ds_topo(ctx), ds_topo(ctx) && ctx->ds.gmem, cz, (flags & ELMK_RUN_HYDROLOGY) && hyd_land(ctx),
                     (flags & ELMK_RUN_HYDROLOGY) && (bool)ctx->hydf_rows, ctx->hist_version,
-                    ctx->accum_version};
+                    ctx->accum_version, (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx),
+                    (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;

@@ -4,7 +4,7 @@
 // columns, each field 256-byte aligned), the parameter block (DevState) mirrored into device memory, one
 // HIP stream, and a staging buffer for layout conversion.  No physics lives here and there is no CPU path:
 // every elmk_<physics>() is a single kernel launch on the context's stream.
-// The optional run features live in api_history.cpp, api_accum.cpp, api_rows.cpp, api_run.cpp and api_restart.cpp; elmk_ctx.h is what
+// The optional run features live in api_history.cpp, api_accum.cpp, api_rows.cpp, api_irrigation.cpp, api_run.cpp and api_restart.cpp; elmk_ctx.h is what
 // they share.
 #include "elmk_ctx.h"
 
@@ -273,9 +273,13 @@ void launch(elmk_ctx* ctx, const Stage& st, double dt)
   st.launch(ctx, dt);
 }
 
+// the run step's form of the sequence: with ELMK_RUN_IRRIGATION the irrigation stage goes between the last fused group and
+// soil_temperature ("irrigation": the stepwise placement); elmk_advance_physics itself never irrigates
 void launch_advance(elmk_ctx* ctx, double dt)
 {
-  for (const Stage& st : ADVANCE) launch(ctx, st, dt);
+  for (int k = 0; k < ELMK_FUSED_NSTAGE; k++) launch(ctx, ADVANCE[k], dt);
+  if (ctx->run.flags & ELMK_RUN_IRRIGATION) irr_run_launch(ctx, dt);
+  for (size_t k = ELMK_FUSED_NSTAGE; k < sizeof ADVANCE / sizeof ADVANCE[0]; k++) launch(ctx, ADVANCE[k], dt);
 }
 
 // the stages in order; marks (may be null): events recorded on the context's stream before the first stage and after the last,
@@ -633,7 +637,8 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
   size_t n = ctx->arena.bytes() + ctx->staging.bytes() + ctx->scratch.bytes() + ctx->snicar.bytes() + ctx->snowage.bytes() + ctx->d.bytes() +
              ctx->run.mem.bytes() + ctx->grid.mem.bytes() + ctx->ogrid.mem.bytes() + ctx->sw.czf.bytes() + ctx->run.rec.bytes() +
              ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes() + ctx->alt_rows.bytes() +
-             ctx->hyd_rows.bytes() + ctx->hydf_rows.bytes() + ctx->wb_rows.bytes() + ctx->wb_red.bytes() + ctx->wb_ring.bytes();
+             ctx->hyd_rows.bytes() + ctx->hydf_rows.bytes() + ctx->wb_rows.bytes() + ctx->wb_red.bytes() + ctx->wb_ring.bytes() +
+             ctx->irr_rows.bytes();
   // the cell rows of gridded history entries (not the column rows) and the accumulators' values: whole rows of ld or cld doubles,
   // both multiples of 64, so every size is a multiple of 256 already
   for (const elmk_ctx::HistEntry& e : ctx->hist) n += e.cells ? e.acc.bytes() : 0;

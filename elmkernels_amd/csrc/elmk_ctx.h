@@ -152,12 +152,14 @@ enum GraphId { GRAPH_TS7, GRAPH_FUSED, GRAPH_ADVANCE, GRAPH_RUN_STEP, GRAPH_N };
 
 // What the captured launches of a sequence depend on besides (dt, stream).  elmk_run's step: the run's flags, the downscaling and
 // shortwave modes, whether the soil hydrology stage is in the step (its flag is set and the land unit is soil or crop), whether that
-// stage takes the frost-table form, and the history and accumulator tables' versions; the other sequences have none (StepKey{}).
+// stage takes the frost-table form, the history and accumulator tables' versions, whether the irrigation stage is in the step (its flag
+// is set and the land unit is soil or crop) and whether the water balance takes its term; the other sequences have none (StepKey{}).
 struct StepKey {
   int flags = 0;
   bool ds_topo = false, ds_groups = false, coszen = false, hyd_stage = false, hyd_frost = false;
   uint64_t hist_version = 0, accum_version = 0;
-  auto tie() const { return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version); }
+  bool irr_stage = false, wb_irrig = false;  // the irrigation stage is in the step; the water balance takes the irrigation's term
+  auto tie() const { return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig); }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
 
@@ -265,6 +267,10 @@ struct elmk_ctx {
   long long* wb_ring_census = nullptr;
   double wb_tol = 0.0;
   bool wb_ran = false, wb_ran_empty = false;
+  // irrigation (elmk_irrigation_*): one allocation holds the three fp64 rows [row][ld] and behind them the int32 parameter row sched
+  // [ld], held exactly while the feature is enabled
+  DevBuf<double> irr_rows;
+  int32_t* irr_sched = nullptr;
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
@@ -424,6 +430,21 @@ void mark_sampled(elmk_ctx* ctx, unsigned mask);
 void hist_accumulate_launch(elmk_ctx* ctx);
 unsigned long long* accum_counts(elmk_ctx* ctx);  // api_accum.cpp
 void accum_update_launch(elmk_ctx* ctx);
+// a feature that keeps fp64 rows [row][ld] of its own beside the state (api_rows.cpp, api_irrigation.cpp)
+struct Rows {
+  DevBuf<double> elmk_ctx::*buf;
+  int nrows;
+  const char* label;   // in the text of a HIP error
+  const char* enable;  // the enabling call, for refusals
+  int family;          // ELMK_ROWS_*: history entries over these rows (elmk_column_history_add_row) bar the clear
+};
+extern const Rows ROWS_OF_IRRIGATION;  // api_irrigation.cpp
+int rows_held(elmk_ctx* ctx, const Rows& R, const char* who);   // refuses while a history entry reads the family's rows
+int rows_enter(elmk_ctx* ctx, const Rows& R, const char* who);  // how every call but enable and clear begins
+int rows_read(elmk_ctx* ctx, const Rows& R, const char* who, int which, double* host, int64_t col0, int64_t n);
+int rows_clear(elmk_ctx* ctx, const Rows& R, const char* who);
+constexpr int IRR_NROWS = 3;
+void irr_run_launch(elmk_ctx* ctx, double dt);  // the run step's irrigation stage (api_irrigation.cpp)
 constexpr int ALT_NROWS = 3;  // api_rows.cpp
 ActiveLayerArgs alt_args(const elmk_ctx* ctx);
 bool hyd_land(const elmk_ctx* ctx);

@@ -115,8 +115,12 @@ struct RunRow {
   elmk_solar_step sol;  // elmk_solar_step_consts of the step, computed on the host
   double forc_wt1[8], forc_wt2[8];
   double month_wt1, month_wt2;
-  int32_t forc_slot, month1, month2, pad;  // pad: the step's ELMK_ALT_ROLL_* bits (ELMK_RUN_ALT; 0 otherwise)
+  // pad: the step's ELMK_ALT_ROLL_* bits (ELMK_RUN_ALT; 0 otherwise) in its low RUN_PAD_TOD_SHIFT bits and above them the step's time of
+  // day in seconds, 0 .. 86399 (ELMK_RUN_IRRIGATION; 0 otherwise)
+  int32_t forc_slot, month1, month2, pad;
 };
+constexpr int RUN_PAD_TOD_SHIFT = 8;
+constexpr int RUN_PAD_ROLL_MASK = (1 << RUN_PAD_TOD_SHIFT) - 1;
 // series: the forcing records [RUN_NFORC][slots][ld] and the months [RUN_NPHEN][12][ld], stored element type of the state
 constexpr int RUN_NFORC = 7, RUN_NPHEN = 4, RUN_NMONTH = 12;
 void launch_solar_geometry_run(const DevState* S, int64_t n, const RunRow* rows, const int32_t* cursor, hipStream_t st);
@@ -249,6 +253,13 @@ void launch_active_layer(const ActiveLayerArgs& A, int rollover, hipStream_t st)
 // the same with the rollover bits of table row *cursor (RunRow::pad; elmk_run)
 void launch_active_layer_run(const ActiveLayerArgs& A, const RunRow* rows, const int32_t* cursor, hipStream_t st);
 
+// irrigation (k_irrigation.hip, elmk_irrigation_*): rows = the three fp64 rows of the feature [3][ld], sched = its int32 parameter row;
+// idt = the step in whole seconds, tod = seconds after midnight UTC at the step's start
+void launch_irrigation(const DevState* S, int64_t n, double* rows, const int32_t* sched, int idt, int tod, hipStream_t st);
+// the same with the time of day of table row *cursor (RunRow::pad; elmk_run)
+void launch_irrigation_run(const DevState* S, int64_t n, double* rows, const int32_t* sched, int idt, const RunRow* table,
+                           const int32_t* cursor, hipStream_t st);
+
 // soil hydrology (k_soil_hydrology.hip, elmk_soil_hydrology): one stage over every column; rows = the ELMK_HYD_NROWS fp64 rows of
 // the feature, [row][ld]; frost_rows = the ELMK_HYDF_NROWS rows of the frost-table extension, which select the F' form of the kernel, or
 // null for the plain one
@@ -260,12 +271,13 @@ void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* f
 void launch_min_max_sum(const double* diag, int64_t ld, int64_t n, int ndiag, double* part, double* out, hipStream_t st);
 // W0: BEGWB
 void launch_wb_begin(const DevState* S, int64_t n, const double* hyd_rows, double* wb_rows, hipStream_t st);
+// qirr: the irrigation's QFLX_IRRIG row, which selects W4's form with the term, or null.
 // W1 - W8: the rows, the three triples into out[3][3] (part: 3 x ELMK_CONS_NPART x 3 doubles) and the census {nbad, first bad column or
 // INT64_MAX} into census[0 .. 2).  elmk_run (cursor not null): the triples are copied to ring + *cursor * 9 and the census goes to
 // census + *cursor * 2
 void launch_water_balance(const DevState* S, int64_t n, int64_t ld, const double* hyd_rows, const double* frost_rows, double* wb_rows,
                           double dt, double tol, double* part, double* out, double* ring, long long* census, const int32_t* cursor,
-                          hipStream_t st);
+                          hipStream_t st, const double* qirr = nullptr);
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_active_layer(const dfield t_soisno, con
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncols) return;
-  if constexpr (RUN) rollover = rows[*cursor].pad;
+  if constexpr (RUN) rollover = rows[*cursor].pad & RUN_PAD_ROLL_MASK;  // (above the mask: the irrigation's time of day)
   const dfield t = t_soisno + (int64_t)NLEVSNO * ld + c, z = zsoi + (int64_t)NLEVSNO * ld + c;
 
   // the search, from the bottom upward; t2 = the level below the one in hand

@@ -39,6 +39,7 @@ __device__ __forceinline__ void wb_st(gptr<double> p, double v)
   if (ELMK_WB_NT) __builtin_nontemporal_store(v, p);
   else *p = v;
 }
+__device__ __forceinline__ gptr<const double> wb_first(gptr<const double> p) { return p; }
 }  // namespace
 
 #define LV(f, lev) S->f[(int64_t)(lev) * ld + c]
@@ -53,11 +54,15 @@ __global__ __launch_bounds__(256) void k_wb_begin(const DevState* __restrict__ S
   wb_st(wb + (int64_t)ELMK_WB_BEGWB * ld + c, begwb + hyd[(int64_t)ELMK_HYD_WA * ld + c]);
 }
 
-// W1 - W6.  FROST: QRUNOFF takes QFLX_DRAIN_PERCHED of the frost-table extension's rows hydf as well
-template <bool FROST>
+// W1 - W6.  FROST: QRUNOFF takes QFLX_DRAIN_PERCHED of the frost-table extension's rows hydf as well.  IRRIG: W4 takes the
+// irrigation's QFLX_IRRIG row as a term of the input (ELM's BalanceCheck; include/elmk.h "irrigation").  The row is one more kernel
+// argument, a pack that is empty without IRRIG, so that the two plain instantiations keep the kernel arguments, and with them every
+// instruction, they had before the term existed
+template <bool FROST, bool IRRIG, class... Q>
 __global__ __launch_bounds__(256) void k_water_balance(const DevState* __restrict__ S, gptr<const double> hyd, gptr<const double> hydf,
-                                                       gptr<double> wb, double dt)
+                                                       gptr<double> wb, double dt, Q... qirr)
 {
+  static_assert(sizeof...(Q) == (IRRIG ? 1 : 0), "the QFLX_IRRIG row exactly with IRRIG");
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ld = S->ld;
   if (c >= S->ncols) return;
@@ -88,8 +93,11 @@ __global__ __launch_bounds__(256) void k_water_balance(const DevState* __restric
 
   // W4
   const double begwb = wb[(int64_t)ELMK_WB_BEGWB * ld + c];
-  const double errh2o =
-      endwb - begwb - (S->forc_rain[c] + S->forc_snow[c] - qrunoff - S->qflx_evap_tot[c] - S->qflx_snwcp_ice[c]) * dt;
+  double errh2o;
+  if constexpr (IRRIG)
+    errh2o = endwb - begwb - (((S->forc_rain[c] + S->forc_snow[c]) + wb_first(qirr...)[c]) - qrunoff - S->qflx_evap_tot[c] - S->qflx_snwcp_ice[c]) * dt;
+  else
+    errh2o = endwb - begwb - (S->forc_rain[c] + S->forc_snow[c] - qrunoff - S->qflx_evap_tot[c] - S->qflx_snwcp_ice[c]) * dt;
 
   // W5: the ten active layers
   double totliq = 0.0, totice = 0.0;
@@ -161,16 +169,17 @@ void launch_wb_begin(const DevState* S, int64_t n, const double* hyd_rows, doubl
 
 void launch_water_balance(const DevState* S, int64_t n, int64_t ld, const double* hyd_rows, const double* frost_rows, double* wb_rows,
                           double dt, double tol, double* part, double* out, double* ring, long long* census, const int32_t* cursor,
-                          hipStream_t st)
+                          hipStream_t st, const double* qirr)
 {
   if (n <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (frost_rows)
-    hipLaunchKernelGGL(k_water_balance<true>, grid, block, 0, st, S, (gptr<const double>)hyd_rows, (gptr<const double>)frost_rows,
-                       (gptr<double>)wb_rows, dt);
-  else
-    hipLaunchKernelGGL(k_water_balance<false>, grid, block, 0, st, S, (gptr<const double>)hyd_rows, (gptr<const double>)nullptr,
-                       (gptr<double>)wb_rows, dt);
+  const auto rows = [&](auto kernel, auto... q) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, S, (gptr<const double>)hyd_rows, (gptr<const double>)frost_rows, (gptr<double>)wb_rows,
+                       dt, q...);
+  };
+  const gptr<const double> q = (gptr<const double>)qirr;
+  if (qirr) frost_rows ? rows(k_water_balance<true, true, gptr<const double>>, q) : rows(k_water_balance<false, true, gptr<const double>>, q);
+  else frost_rows ? rows(k_water_balance<true, false>) : rows(k_water_balance<false, false>);
   static_assert(ELMK_WB_QRUNOFF == ELMK_WB_ERRH2O + 1 && ELMK_WB_ENDWB == ELMK_WB_ERRH2O + 2, "the reduced rows are adjacent");
   const double* diag = wb_rows + (size_t)ELMK_WB_ERRH2O * (size_t)ld;
   launch_min_max_sum(diag, ld, n, 3, part, out, st);

@@ -602,17 +602,20 @@ def q_perch_max(topo_slope_deg):
 
 
 def water_balance_error(begwb, endwb, wa_beg, wa_end, forc_rain, forc_snow, qflx_evap_tot, qflx_snwcp_ice, qflx_surf, qflx_h2osfc_surf,
-                        qflx_drain, dt, qflx_drain_perched=None):
+                        qflx_drain, dt, qflx_drain_perched=None, qflx_irrig=None):
     """The reference's column_water_balance_error with the aquifer in both water masses and
     hydrology_source_sink = qflx_surf + qflx_h2osfc_surf + qflx_drain in place of its hardwired 0:
     errh2o = (endwb + wa_end) - (begwb + wa_beg) - (forc_rain + forc_snow - source_sink - qflx_evap_tot - qflx_snwcp_ice) * dt.
-    qflx_drain_perched: the frost-table extension's lateral drainage, one more term of the source/sink."""
+    qflx_drain_perched: the frost-table extension's lateral drainage, one more term of the source/sink.  qflx_irrig: the irrigation's
+    applied rate, one more term of the input: (forc_rain + forc_snow) + qflx_irrig (ELM's BalanceCheck)."""
     a = [np.asarray(v, dtype=np.float64) for v in (begwb, endwb, wa_beg, wa_end, forc_rain, forc_snow, qflx_evap_tot, qflx_snwcp_ice,
                                                    qflx_surf, qflx_h2osfc_surf, qflx_drain)]
     begwb, endwb, wa_beg, wa_end, rain, snow, evap, snwcp, surf, h2osfc_surf, drain = a
     source_sink = surf + h2osfc_surf + drain
     if qflx_drain_perched is not None:
         source_sink = source_sink + np.asarray(qflx_drain_perched, dtype=np.float64)
+    if qflx_irrig is not None:
+        return (endwb + wa_end) - (begwb + wa_beg) - (((rain + snow) + np.asarray(qflx_irrig, dtype=np.float64)) - source_sink - evap - snwcp) * float(dt)
     return (endwb + wa_end) - (begwb + wa_beg) - (rain + snow - source_sink - evap - snwcp) * float(dt)
 
 
@@ -647,11 +650,12 @@ def water_balance_begin(fields, rows, wb=None):
     return out
 
 
-def water_balance_end(fields, rows, wb, dt, frost=None, snwcp_liq_term=True):
+def water_balance_end(fields, rows, wb, dt, frost=None, snwcp_liq_term=True, qflx_irrig=None):
     """W1 - W6 on the host, one numpy operation per IEEE operation in the header's order.  fields: the state fields WB_READS as S[name]
     downloads them; rows: the hydrology's rows after the step's soil_hydrology; wb: the rows of the feature, BEGWB from
     water_balance_begin; frost: the frost-table extension's rows [FROST_NROWS, n] where it is enabled.  Returns the rows after the
-    stage (BEGWB unchanged).  snwcp_liq_term=False leaves W3's last term out (a measurement, not the stage)."""
+    stage (BEGWB unchanged).  snwcp_liq_term=False leaves W3's last term out (a measurement, not the stage).  qflx_irrig: the
+    irrigation's QFLX_IRRIG row [n] where that feature is enabled: W4 takes (forc_rain + forc_snow) + qflx_irrig as the input."""
     dt = float(dt)
     rows, wb = np.asarray(rows, dtype=np.float64), np.array(wb, dtype=np.float64)
     w = _wide(fields, WB_READS)
@@ -665,7 +669,11 @@ def water_balance_end(fields, rows, wb, dt, frost=None, snwcp_liq_term=True):
         if frost is not None:
             q = q + np.asarray(frost, dtype=np.float64)[QFLX_DRAIN_PERCHED]
         qrunoff = q + w["qflx_snwcp_liq"] if snwcp_liq_term else q
-        err = endwb - wb[WB_BEGWB] - (w["forc_rain"] + w["forc_snow"] - qrunoff - w["qflx_evap_tot"] - w["qflx_snwcp_ice"]) * dt  # W4
+        if qflx_irrig is None:
+            err = endwb - wb[WB_BEGWB] - (w["forc_rain"] + w["forc_snow"] - qrunoff - w["qflx_evap_tot"] - w["qflx_snwcp_ice"]) * dt  # W4
+        else:
+            qi = np.asarray(qflx_irrig, dtype=np.float64)
+            err = endwb - wb[WB_BEGWB] - (((w["forc_rain"] + w["forc_snow"]) + qi) - qrunoff - w["qflx_evap_tot"] - w["qflx_snwcp_ice"]) * dt
         n = water.shape[0]
         totliq, totice, s = np.zeros(n), np.zeros(n), np.zeros(n)
         zi = w["zisoi"][:, NLEVSNO:NLEVSNO + N + 1]  # zi[:, 0] = the surface, zi[:, j + 1] = the bottom of layer j

@@ -17,6 +17,7 @@ the highest among them (OPTIONAL; version 1 without any, byte for byte as before
   version 3, active layer thickness (elmk_active_layer_enable): three column sections of kind ALT_SECTION (id 0, 1, 2: alt, altmax,
     altmax_lastyear; one level, F64);
   version 4, soil hydrology (elmk_soil_hydrology_enable): two column sections of kind HYDROLOGY_SECTION (id 0, 1: ZWT, WA; one level, F64).
+  version 5, irrigation (elmk_irrigation_enable): two column sections of kind IRRIGATION_SECTION (id 0, 1: RATE, NLEFT; one level, F64).
 History entries over feature rows (elmk_column_history_add_row; include/elmk_restart.def): the entry's `field` holds row_field(family, which), a
 value beyond every field id; its section is an ordinary HISTORY or GRIDDED section of one level and the version does not change.  merge
 and slice carry such entries as they carry every entry; entry_row decodes one.
@@ -29,12 +30,14 @@ VERSION = 1  # of an image without accumulator entries
 VERSION_ACCUM = 2  # of an image with accumulator entries
 VERSION_ALT = 3  # of an image with the active layer thickness rows
 VERSION_HYDROLOGY = 4  # of an image with the soil hydrology rows ZWT and WA
-FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION, HYDROLOGY_SECTION = 0, 1, 2, 3, 4, 5  # ELMK_RESTART_*
+VERSION_IRRIGATION = 5  # of an image with the irrigation rows RATE and NLEFT
+FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION, HYDROLOGY_SECTION, IRRIGATION_SECTION = 0, 1, 2, 3, 4, 5, 6  # ELMK_RESTART_*
 # the optional kinds and the version that introduced each; from version 2 on the word after the header counts the accumulator entries
-OPTIONAL = ((ACCUM_SECTION, VERSION_ACCUM), (ALT_SECTION, VERSION_ALT), (HYDROLOGY_SECTION, VERSION_HYDROLOGY))
+OPTIONAL = ((ACCUM_SECTION, VERSION_ACCUM), (ALT_SECTION, VERSION_ALT), (HYDROLOGY_SECTION, VERSION_HYDROLOGY),
+            (IRRIGATION_SECTION, VERSION_IRRIGATION))
 ALIGN = 256
 ROW_BASE = 0x40000000  # ELMK_RESTART_ROW_BASE
-ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE = range(4)  # ELMK_ROWS_*
+ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # ELMK_ROWS_*
 HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), ("schema_hash", "<u8"), ("gcol0", "<i8"),
                    ("ncols", "<i8"), ("tape_count", "<u8", (4,)), ("nentries", "<u4"), ("nsections", "<u4"),
                    ("header_bytes", "<u8"), ("total_bytes", "<u8"), ("header_checksum", "<u8")])

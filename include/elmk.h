@@ -300,7 +300,8 @@ int elmk_history_clear(elmk_ctx *ctx);
  *                          elmk_solar_geometry(dt, decday, doy); elmk_phenology(month_wt1, month_wt2) over months month1 / month2;
  *                          elmk_get_forcing(forc_wt1, forc_wt2, flags & ELMK_RUN_QBOT_IS_RH) over slots forc_slot / forc_slot + 1;
  *                          with ELMK_RUN_AEROSOL: elmk_aerosol_deposition(month1, month2, month_wt1, month_wt2) ("aerosol deposition");
- *                          elmk_init_timestep; elmk_advance_physics(dt);
+ *                          elmk_init_timestep; elmk_advance_physics(dt) - with ELMK_RUN_IRRIGATION: its split form with
+ *                          elmk_irrigation(dt, the step's time of day) before elmk_soil_temperature ("irrigation");
  *                          with ELMK_RUN_HYDROLOGY: elmk_soil_hydrology(dt) ("soil hydrology");
  *                          elmk_evaluate_conservation -> ring row s;
  *                          elmk_error_summary -> ring row s (flags sticky, as that call sees them after the step);
@@ -658,7 +659,7 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  * with the h2osfc store, the Zeng-Decker Richards solve with the aquifer as an extra row, the water-table update and drainage.  The
  * reference has none of it: its conservation row hardwires hydrology_source_sink = 0.0 (driver/kokkos/conserved_quantity_kokkos.cc:22)
  * and it expects an external subsurface model, so without this stage no kernel applies qflx_top_soil, qflx_rootsoi or the ground
- * evaporation terms to the soil layers.  Out of scope: lateral flow, VSFM, irrigation, lakes, wetlands, urban.
+ * evaporation terms to the soil layers.  Out of scope: lateral flow, VSFM, lakes, wetlands, urban (irrigation: the section of that name below).
  * This text is the specification; elmkernels_amd/hydrology.py: column() is the same operation on the host, and where an evaluation
  * order is not spelled out here that function fixes it (k_soil_hydrology.hip follows it statement by statement, bit for bit).
  *
@@ -839,7 +840,8 @@ int elmk_soil_hydrology_frost_clear(elmk_ctx *ctx);
  * W3. q = QFLX_SURF + QFLX_H2OSFC_SURF + QFLX_DRAIN; with the frost-table extension enabled q = q + QFLX_DRAIN_PERCHED;
  *     QRUNOFF = q + qflx_snwcp_liq   (the liquid that snow capping removes, which ELM counts as qflx_qrgwl on soil columns; the
  *     reference's budget and hydrology.water_balance_error leave it out).
- * W4. ERRH2O = ENDWB - BEGWB - (forc_rain + forc_snow - QRUNOFF - qflx_evap_tot - qflx_snwcp_ice) * dt.
+ * W4. ERRH2O = ENDWB - BEGWB - (forc_rain + forc_snow - QRUNOFF - qflx_evap_tot - qflx_snwcp_ice) * dt; while the irrigation is enabled
+ *     (forc_rain + forc_snow) + QFLX_IRRIG takes the place of forc_rain + forc_snow ("irrigation" below).
  * W5. TOTSOILLIQ = the sum of liq[j], j = 0 .. N-1 ascending, from 0.0; TOTSOILICE the same over ice[j].  The library's own
  *     definition: the ten active layers; the bedrock levels are never touched by the stage.
  * W6. s = 0.0; for j = 0 .. N-1: if (zi[j] <= 0.1) s = s + (liq[j] + ice[j]);
@@ -881,20 +883,98 @@ int elmk_water_balance_read(elmk_ctx *ctx, int which, double *host, int64_t col0
 int elmk_water_balance_clear(elmk_ctx *ctx);
 int elmk_run_water_balance(elmk_ctx *ctx, double *min_max_sum /*[nsteps][3][3]*/, int64_t *nbad /*[nsteps]*/, int64_t *first_bad_col /*[nsteps]*/);
 
+/* ---- irrigation ------------------------------------------------------------------------------------
+ * ELM's irrigation (CLM4.5 / ELM v1): the daily demand check of CanopyFluxes and the application of canopy_hydrology's Irrigation()
+ * and ground_flux.  The reference carries the three names and hardwires them: irrig_rate = 0.0 and n_irrig_steps_left = 0
+ * (driver/kokkos/elm_kokkos_interface.cc:98-99), qflx_irrig = 0.0 (driver/kokkos/canopy_hydrology_kokkos.cc:24); Irrigation()
+ * (src/physics/canopy_hydrology_impl.hh:70-80) is never called and the routine that sets the rate is a comment block
+ * (src/physics/canopy_fluxes_impl.hh:17-91).  This opt-in stage is both, one launch between the seven wrappers and soil_temperature:
+ * the two fields it changes, qflx_rain_grnd and qflx_snwcp_liq, are stored by canopy_hydrology and read by nothing before
+ * snow_hydrology and surface_fluxes.  elmkernels_amd/irrigation.py: step() is the same operation on the host.
+ *
+ * The feature owns three fp64 rows [level stride] (in both builds): ELMK_IRR_RATE = irrig_rate (mm/s), ELMK_IRR_NLEFT =
+ * n_irrig_steps_left (a small whole number, exact in fp64, so that the row read, history row entries and restart sections serve it
+ * unchanged), ELMK_IRR_QFLX_IRRIG = this step's applied rate (mm/s; a diagnostic, overwritten every step); and one int32 parameter row
+ * sched[c]: -1 = the column is not irrigated, else the column's longitude offset in seconds, 0 .. 86399 (irrigation.schedule:
+ * ELM's round(londeg / degpsec), degpsec = 15 / 3600, half away from zero, reduced mod 86400).  Which columns are irrigated is the
+ * driver's surface data, like hksat.
+ *
+ * One step, per column c.  idt = the step length in whole seconds, dt = idt as a double, tod = seconds after midnight UTC at the start
+ * of the step (0 .. 86399), nspd = (14400 + (idt - 1)) / idt (integer division: the steps of the four-hour window).  Conventions of
+ * "soil hydrology": no contraction, plain IEEE comparisons, `/` the correctly rounded division, pow is glibc's (elmk_pow),
+ * max(a, b) = (a < b ? b : a), state fields widened to fp64 as stored; a NaN stored into a row is the canonical quiet NaN.
+ * Soil layer j = 0 .. 14 is level 5 + j of t_soisno, h2osoi_liq and dz and level j of rootfr, eff_porosity, sucsat and bsw;
+ * denh2o = 1000, tfrz = 273.15; smpso is the PFT parameter of the column's vtype, as calc_root_moist_stress reads it.
+ * A (apply: Irrigation(), then ground_flux's qflx_prec_grnd_rain + qflx_irrig):
+ *   n = NLEFT[c];  if (n > 0) { q = RATE[c];  NLEFT[c] = n - 1; } else q = +0.0;
+ *   QFLX_IRRIG[c] = q;
+ *   if (q > 0.0) { if (do_capsnow[c]) qflx_snwcp_liq[c] += q;  else qflx_rain_grnd[c] += q; }    (added and rounded at state precision)
+ *   In the fp64 build this is bit for bit the reference's sum: the stored field is prec_rain + 0.0, which differs from prec_rain only
+ *   where prec_rain is -0.0, and there both sums equal q.
+ * B (check, after A in the same thread - ELM's order: hydrology before fluxes, the new rate serves the following steps):
+ *   if (sched[c] >= 0 && frac_veg_nosno[c] != 0 && elai[c] > 0.0 && btran[c] < 0.999999) {
+ *     local = (tod + sched[c]) % 86400;  since = (local - 21600 + 86400) % 86400;
+ *     if (since < idt) {                                   (the step in which the local clock passes 06:00)
+ *       NLEFT[c] = nspd;  rate = +0.0;
+ *       for j = 0 .. 14:
+ *         if (t_soisno[j] <= tfrz) break;                  (no layer below a frozen one is measured)
+ *         if (rootfr[j] > 0.0) {
+ *           vol_liq_so = eff_porosity[j] * pow(-smpso / sucsat[j], -1.0 / bsw[j]);
+ *           liq_so = vol_liq_so * denh2o * dz[j];  liq_sat = eff_porosity[j] * denh2o * dz[j];
+ *           deficit = max((liq_so + 0.7 * (liq_sat - liq_so)) - h2osoi_liq[j], 0.0);
+ *           rate = rate + deficit / (dt * nspd); }
+ *       RATE[c] = rate; } }
+ * btran and eff_porosity are this step's: both elmk_timestep7 and elmk_timestep7_fused leave them in the state.
+ *
+ *   elmk_irrigation_enable  allocates the rows and sched (3 x 8 + 4 bytes x elmk_level_stride in one owner, counted in
+ *                           elmk_device_bytes), the rows zero-filled; drops the captured run step.  ELMK_E_INVALID, nothing changed:
+ *                           already enabled; a null sched; a sched value outside -1 .. 86399; a stream being captured.
+ *   elmk_irrigation_init    RATE and NLEFT from host[ncols] each (NULL: zeros), QFLX_IRRIG = zeros.  Synchronises.  ELMK_E_INVALID,
+ *                           nothing changed: not enabled; a rate that is not finite or negative; an nleft that is not a whole number
+ *                           in 0 .. 86400; a stream being captured.
+ *   elmk_irrigation         one launch; stream-ordered and capturable, no host memory, no synchronisation.  ELMK_E_INVALID, nothing
+ *                           enqueued: not enabled; dt not a finite whole number of seconds in 1 .. 86400; tod_seconds outside
+ *                           0 .. 86399.  A context whose land unit (elmk_set_land) is not soil or crop enqueues nothing and returns
+ *                           ELMK_OK (the reference's !lakpoi && !urbpoi).
+ *   elmk_irrigation_read    row `which` (ELMK_IRR_*) of columns [col0, col0 + n) as doubles; synchronises.
+ *   elmk_irrigation_clear   frees the rows and sched and drops the captured run step; refused while a history row entry of the family
+ *                           exists ("elmk_history_clear first").
+ * Stepwise placement: elmk_timestep7_fused (or elmk_timestep7), elmk_irrigation, elmk_soil_temperature, elmk_snow_hydrology,
+ * elmk_surface_fluxes.  elmk_advance_physics stays exactly what it is and never irrigates.
+ * elmk_run with ELMK_RUN_IRRIGATION runs the stage in every step between the last fused group and soil_temperature, with
+ * tod = llround((decday - 1.0 - doy) * 86400.0) reduced to 0 .. 86399, derived on the host from the step's start (elmk_run_step does not
+ * grow); refused before anything is enqueued when the feature is not enabled or dt is not a whole number of seconds in 1 .. 86400.
+ * Graph on and off give the same bits.
+ * Water balance: while the feature is enabled W4 of "water balance" takes ELM's BalanceCheck form,
+ *   ERRH2O = ENDWB - BEGWB - (((forc_rain + forc_snow) + QFLX_IRRIG) - QRUNOFF - qflx_evap_tot - qflx_snwcp_ice) * dt.
+ * Water withdrawal is not modelled: QRUNOFF stays the column's generated runoff, and a driver that takes the water from the river
+ * subtracts its QIRRIG tape itself.
+ * History: ELMK_ROWS_IRRIGATION (which = ELMK_IRR_*) puts ELM's QIRRIG on a tape.  Restart: a context with the feature enabled saves a
+ * version-5 image that carries RATE and NLEFT ("restart" below); sched is a parameter the loading context sets itself.
+ * A context that never enables the feature runs the kernels, launch sequences and graphs it ran before, allocates nothing more and
+ * saves the image it saved before. */
+enum { ELMK_IRR_RATE = 0, ELMK_IRR_NLEFT = 1, ELMK_IRR_QFLX_IRRIG = 2 };
+#define ELMK_RUN_IRRIGATION 128 /* the eighth flag bit of elmk_run: every step applies and checks irrigation */
+int elmk_irrigation_enable(elmk_ctx *ctx, const int32_t *sched /*[ncols]*/);
+int elmk_irrigation_init(elmk_ctx *ctx, const double *rate /*[ncols] or NULL*/, const double *nleft /*[ncols] or NULL*/);
+int elmk_irrigation(elmk_ctx *ctx, double dt, int tod_seconds);
+int elmk_irrigation_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
+int elmk_irrigation_clear(elmk_ctx *ctx);
+
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.
  * These two entries register one such row, over the columns (elmk_column_history_add_row; the six elmk_history_* entries of "history"
  * stay the set they are) or over the output grid's cells: as elmk_history_add / elmk_gridded_history_add (the same entry ids, table, limits, ops,
  * refusals and fold semantics, still one elmk_history_accumulate launch), one level, the sample the row's fp64 value in both builds.
  * family: ELMK_ROWS_ALT (which = ELMK_ALT_*), ELMK_ROWS_HYDROLOGY (ELMK_HYD_*), ELMK_ROWS_FROST (ELMK_HYDF_*), ELMK_ROWS_WATER_BALANCE
- * (ELMK_WB_*).  Refused as well: an unknown family, a family that is not enabled, `which` out of range.
+ * (ELMK_WB_*), ELMK_ROWS_IRRIGATION (ELMK_IRR_*).  Refused as well: an unknown family, a family that is not enabled, `which` out of range.
  * While a row entry exists the *_clear of its family is refused with ELMK_E_INVALID ("elmk_history_clear first") and nothing changes:
  * elmk_soil_hydrology_clear for the hydrology, the frost-table extension and the water balance, elmk_soil_hydrology_frost_clear and
  * a second elmk_soil_hydrology_frost_enable for the extension.  This mirrors elmk_clear_output_grid under gridded entries.
  * Restart: a row entry is saved and loaded like any history entry; its elmk_restart_entry.field holds
  * ELMK_RESTART_ROW_FIELD(family, which), a value no field id reaches, so a loader from before row entries refuses the image as a
  * history table other than its own.  Images of contexts without row entries are what they were. */
-enum { ELMK_ROWS_ALT = 0, ELMK_ROWS_HYDROLOGY = 1, ELMK_ROWS_FROST = 2, ELMK_ROWS_WATER_BALANCE = 3, ELMK_ROWS_NFAMILY = 4 };
+enum { ELMK_ROWS_ALT = 0, ELMK_ROWS_HYDROLOGY = 1, ELMK_ROWS_FROST = 2, ELMK_ROWS_WATER_BALANCE = 3, ELMK_ROWS_IRRIGATION = 4, ELMK_ROWS_NFAMILY = 5 };
 #define ELMK_RESTART_ROW_BASE 0x40000000
 #define ELMK_RESTART_ROW_FIELD(family, which) (ELMK_RESTART_ROW_BASE + ((family) << 16) + (which))
 int elmk_column_history_add_row(elmk_ctx *ctx, int tape, int family, int which, int op);
@@ -945,6 +1025,11 @@ int elmk_gridded_history_add_row(elmk_ctx *ctx, int tape, int family, int which,
  * an image holds), and last two sections of kind ELMK_RESTART_HYDROLOGY, id = ELMK_HYD_ZWT, ELMK_HYD_WA, nlev = 1, F64, extent = ncols.
  * A version-4 image loads only into a context with the same features enabled; the parameter rows are not part of it.
  *
+ * Image format, version 5: what a context with the irrigation enabled (elmk_irrigation_enable) saves.  As version 4, with each optional
+ * kind present exactly when its feature is enabled, and last two sections of kind ELMK_RESTART_IRRIGATION, id = ELMK_IRR_RATE,
+ * ELMK_IRR_NLEFT, nlev = 1, F64, extent = ncols.  A version-5 image loads only into a context with the same features enabled; sched is
+ * not part of it.
+ *
  * elmk_restart_size: bytes of this context's image.  elmk_restart_save: the image of the context's columns, which are global
  * columns [gcol0, gcol0 + ncols) of the run.  elmk_restart_load: verifies the whole image on the device (every checksum, snl in
  * 0..nlevsno, as elmk_upload) before it writes anything, then writes the fields, the accumulators, the tape counts and the
@@ -964,12 +1049,13 @@ int elmk_gridded_history_add_row(elmk_ctx *ctx, int tape, int family, int which,
  * Graphs captured before a load stay valid (the arena and the history table do not move). */
 enum { ELMK_CLASS_PROGNOSTIC = 0, ELMK_CLASS_SURFACE = 1, ELMK_CLASS_FORCING = 2, ELMK_CLASS_DIAGNOSTIC = 3 };
 enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2, ELMK_RESTART_ACCUM = 3, ELMK_RESTART_ALT = 4,
-       ELMK_RESTART_HYDROLOGY = 5 };
+       ELMK_RESTART_HYDROLOGY = 5, ELMK_RESTART_IRRIGATION = 6 };
 #define ELMK_RESTART_MAGIC "ELMKRST\0"
 #define ELMK_RESTART_VERSION 1u       /* of a context without accumulator entries */
 #define ELMK_RESTART_VERSION_ACCUM 2u /* of a context with accumulator entries */
 #define ELMK_RESTART_VERSION_ALT 3u   /* of a context with the active layer thickness enabled */
 #define ELMK_RESTART_VERSION_HYDROLOGY 4u /* of a context with the soil hydrology enabled */
+#define ELMK_RESTART_VERSION_IRRIGATION 5u /* of a context with the irrigation enabled */
 typedef struct {
   char magic[8];              /* ELMK_RESTART_MAGIC */
   uint32_t version;           /* ELMK_RESTART_VERSION */

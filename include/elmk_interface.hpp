@@ -173,7 +173,15 @@ class ELMInterface {
     ok(elmk_phenology(ctx_, w.month_wt1, w.month_wt2));
     ok(elmk_get_forcing(ctx_, w.forc_wt1, w.forc_wt2, w.qbot_is_relative_humidity));
     ok(elmk_init_timestep(ctx_));
-    ok(elmk_advance_physics(ctx_, dt_seconds));
+    if (irrigation_) {  // the split form of elmk_advance_physics with the irrigation stage in it (elmk.h "irrigation")
+      ok(elmk_timestep7_fused(ctx_, dt_seconds));
+      ok(elmk_irrigation(ctx_, dt_seconds, tod_));
+      ok(elmk_soil_temperature(ctx_, dt_seconds));
+      ok(elmk_snow_hydrology(ctx_, dt_seconds));
+      ok(elmk_surface_fluxes(ctx_, dt_seconds));
+    } else {
+      ok(elmk_advance_physics(ctx_, dt_seconds));
+    }
     ok(elmk_evaluate_conservation(ctx_, dt_seconds, &conservation_[0][0], nullptr));
     uint32_t flags = 0;
     int64_t col = -1;
@@ -205,6 +213,7 @@ class ELMInterface {
    * decday = Utils::decimal_doy(date) + 1.0, doy = date.doy of the step's start. */
   bool advance(double dt_seconds, const StepWeights& w, double decday, int doy)
   {
+    set_time_of_day(time_of_day(decday, doy));
     solar_geometry(dt_seconds, decday, doy);
     return advance(dt_seconds, w);
   }
@@ -309,6 +318,31 @@ class ELMInterface {
   void soil_hydrology(double dt_seconds) { ok(elmk_soil_hydrology(ctx_, dt_seconds)); }
   void soil_hydrology_read(int which, double* host) { ok(elmk_soil_hydrology_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
   void soil_hydrology_clear() { ok(elmk_soil_hydrology_clear(ctx_)); }
+  /* Irrigation (elmk.h "irrigation"; ELM's demand check and daily application): irrigation_enable(sched[ncols]) allocates the rows RATE,
+   * NLEFT and QFLX_IRRIG and takes the schedule (-1: not irrigated, else the longitude offset in seconds 0 .. 86399); from then on
+   * advance() takes the split form of the physics with the stage between the seven wrappers and soil_temperature, at the time of day
+   * the advance() overload with decday / doy derives, or set_time_of_day() sets (seconds after midnight UTC at the step's start), and
+   * run(..., irrigation = true) does the same in every step.  irrigation_init() takes a restart file's irrig_rate and
+   * n_irrig_steps_left ([ncols] each, nullptr: zeros); irrigation_read() fills [ncols] of row ELMK_IRR_*. */
+  void irrigation_enable(const int32_t* sched)
+  {
+    ok(elmk_irrigation_enable(ctx_, sched));
+    irrigation_ = true;
+  }
+  void irrigation_init(const double* rate = nullptr, const double* nleft = nullptr) { ok(elmk_irrigation_init(ctx_, rate, nleft)); }
+  void irrigation_read(int which, double* host) { ok(elmk_irrigation_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
+  void irrigation_clear()
+  {
+    ok(elmk_irrigation_clear(ctx_));
+    irrigation_ = false;
+  }
+  void set_time_of_day(int tod_seconds) { tod_ = tod_seconds; }
+  /* llround((decday - 1.0 - doy) * 86400.0) reduced to 0 .. 86399, as elmk_run derives it */
+  static int time_of_day(double decday, int doy)
+  {
+    const long long t = std::llround((decday - 1.0 - (double)doy) * 86400.0);
+    return (int)(((t % 86400) + 86400) % 86400);
+  }
   /* Its frost-table extension (elmk.h "soil hydrology", F'): from soil_hydrology_frost_enable(q_perch_max[ncols]) on the stage drains
    * perched water above a frozen layer; soil_hydrology_frost_read() fills [ncols] of row ELMK_HYDF_*. */
   void soil_hydrology_frost_enable(const double* q_perch_max) { ok(elmk_soil_hydrology_frost_enable(ctx_, q_perch_max)); }
@@ -382,12 +416,13 @@ class ELMInterface {
   }
   void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
                    bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false, bool soil_hydrology = false,
-                   bool water_balance = false)
+                   bool water_balance = false, bool irrigation = false)
   {
     ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(),
                 (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0) | (update_accum ? ELMK_RUN_ACCUM : 0) |
                     (update_aerosol ? ELMK_RUN_AEROSOL : 0) | (update_active_layer ? ELMK_RUN_ALT : 0) |
-                    (soil_hydrology ? ELMK_RUN_HYDROLOGY : 0) | (water_balance ? ELMK_RUN_WATER_BALANCE : 0)));
+                    (soil_hydrology ? ELMK_RUN_HYDROLOGY : 0) | (water_balance ? ELMK_RUN_WATER_BALANCE : 0) |
+                    (irrigation ? ELMK_RUN_IRRIGATION : 0)));
   }
   bool finish_run()
   {
@@ -410,9 +445,10 @@ class ELMInterface {
   }
   bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
            bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false, bool soil_hydrology = false,
-           bool water_balance = false)
+           bool water_balance = false, bool irrigation = false)
   {
-    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol, update_active_layer, soil_hydrology, water_balance);
+    enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol, update_active_layer, soil_hydrology, water_balance,
+                irrigation);
     return finish_run();
   }
   const std::vector<double>& run_conservation() const { return run_conservation_; }
@@ -531,6 +567,8 @@ class ELMInterface {
   double conservation_[8][3]{};
   uint32_t last_flags_{0};
   int max_steps_{0};
+  bool irrigation_{false};  // irrigation_enable(): advance() takes the split form
+  int tod_{0};              // seconds after midnight UTC at the start of the next advance()
   int64_t grid_ncells_{0};
   int64_t output_ncells_{0};
   std::vector<double> run_conservation_;
