@@ -19,87 +19,27 @@ the A/Bs of the unit's two switches:
 --parent LIB: the unflagged run step alone, alternated between this build and LIB, a build of the parent commit's library
 (git worktree add ../parent HEAD~1 && make -C ../parent/elmkernels_amd/csrc): the unflagged step must not have moved.
 python tests/tools/active_layer_cost.py [--cols 1000000,10000000] [--rounds 5] [--run-steps 6] [--ab LIB | --parent LIB [--parent-first]]"""
-import argparse
-import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
-from elmkernels_amd import _lib as L  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 from elmkernels_amd import accum  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
-from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 # soil layers thawed from the top (280 K over 260 K), bytes per column on the tally
 TIERS = {"alt_thawed": (15, 32), "alt_frozen": (0, 136), "alt_front": (7, 104)}
-
-
-def load_parent(path):
-    """A build of the parent commit has every symbol but the new ones: declare what it exports."""
-    lib = C.CDLL(path)
-    for name, (res, args) in L.SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            assert name.startswith("elmk_active_layer_"), name
-            continue
-        fn.restype, fn.argtypes = res, args
-    L._libs[path] = lib
+CALLS = 40  # launches of a back-to-back series
 
 
 def build(cols, lib_path=None, feature=True):
-    D, _ = bench.build_state(cols, 0, "A", 0x5EEDE1A0, lib_path=lib_path)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
-    lat, lon = synth.global_grid(cols, seed=11)
-    D.set_column_geography(lat, lon)
-    # a run over the two forcing records and two months the state already holds
-    D.run_reserve(2, 64)
-    for k in st.SERIES_FORCING + st.SERIES_PHENOLOGY:
-        a = D.download(k, layout=st.LAYOUT_SOA)
-        D.series_upload(k, 0, a)
+    D = CL.run_context(cols, lib_path=lib_path)
     if feature:
         D.active_layer_enable()
     return D
-
-
-def schedule(n):
-    S = np.zeros(n, st.RUN_STEP_DTYPE)
-    for s in range(n):
-        ddoy = 180.25 + s * DT / 86400.0
-        S[s]["decday"], S[s]["doy"], S[s]["forc_slot"] = ddoy + 1.0, int(ddoy), 0
-        w2 = np.full(8, (s + 0.5) / n)
-        S[s]["forc_wt1"], S[s]["forc_wt2"] = 1.0 - w2, w2
-        S[s]["month1"], S[s]["month2"], S[s]["month_wt1"], S[s]["month_wt2"] = 0, 1, 0.6, 0.4
-    return S
-
-
-def back_to_back(D, fn, n=40):
-    fn()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    D.sync()
-    return (time.perf_counter() - t0) / n * 1e3
-
-
-def run_ms(D, steps, flags, n=3):
-    def once():
-        D.restore_fields()
-        D.run(DT, steps, flags)
-    once()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        once()
-    D.sync()
-    return (time.perf_counter() - t0) / (n * len(steps)) * 1e3
 
 
 _TIER_SOIL = {}
@@ -114,32 +54,27 @@ def tier_ms(D, tier, soil):
         a[5:5 + TIERS[tier][0]] = 280.0
         _TIER_SOIL[key] = a
     D.upload("t_soisno", _TIER_SOIL[key], layout=st.LAYOUT_SOA)
-    ms = back_to_back(D, D.active_layer_update)
+    ms = CL.back_to_back(D, D.active_layer_update, CALLS)
     D.upload("t_soisno", soil, layout=st.LAYOUT_SOA)
     return ms
 
 
-def spread(v):
-    return (max(v) - min(v)) / float(np.median(v))
-
-
 def measure(cols, rounds, run_steps):
     D = build(cols)
-    steps = schedule(run_steps)
+    steps = CL.schedule(run_steps)
     soil = D.download("t_soisno", layout=st.LAYOUT_SOA)
     accum.add_t10(D, DT)
     res = {m: [] for m in tuple(TIERS) + ("accum_t10", "run", "run+alt")}
     for r in range(rounds):
-        for tier in (tuple(TIERS) if r % 2 == 0 else tuple(TIERS)[::-1]):
+        for tier in CL.interleave(r, TIERS):
             res[tier].append(tier_ms(D, tier, soil))
-        res["accum_t10"].append(back_to_back(D, D.accum_update))
-        order = (("run", 0), ("run+alt", st.RUN_ALT)) if r % 2 == 0 else (("run+alt", st.RUN_ALT), ("run", 0))
-        for key, flags in order:
-            res[key].append(run_ms(D, steps, flags))
-    med = {k: float(np.median(v)) for k, v in res.items()}
+        res["accum_t10"].append(CL.back_to_back(D, D.accum_update, CALLS))
+        for key, flags in CL.interleave(r, (("run", 0), ("run+alt", st.RUN_ALT))):
+            res[key].append(CL.run_ms(D, steps, flags))
+    med = CL.medians(res)
     D.close()
     out = {"columns": cols, "rounds": rounds, "run_steps": run_steps, "ms_median": med, "ms_all": res,
-           "spread": {k: spread(v) for k, v in res.items()}, "accum_t10_GBps": 32 * cols / (med["accum_t10"] * 1e-3) / 1e9,
+           "spread": CL.spreads(res), "accum_t10_GBps": 32 * cols / (med["accum_t10"] * 1e-3) / 1e9,
            "run_step_with_over_without": med["run+alt"] / med["run"], "run_step_added_ms": med["run+alt"] - med["run"]}
     for tier, (_, nbytes) in TIERS.items():
         out[tier + "_bytes"] = nbytes * cols
@@ -149,65 +84,39 @@ def measure(cols, rounds, run_steps):
 
 
 def ab(cols, rounds, run_steps, lib_b):
-    A, B = build(cols), build(cols, lib_path=lib_b)
-    steps = schedule(run_steps)
-    soil = A.download("t_soisno", layout=st.LAYOUT_SOA)
-    pair = (("product", A), ("variant", B))
-    res = {k: {m: [] for m in tuple(TIERS) + ("run+alt",)} for k, _ in pair}
-    for r in range(rounds):
-        turn = pair if r % 2 == 0 else pair[::-1]
-        for tier in TIERS:
-            for key, D in turn:
-                res[key][tier].append(tier_ms(D, tier, soil))
-        for key, D in turn:
-            res[key]["run+alt"].append(run_ms(D, steps, st.RUN_ALT))
-    out = {"columns": cols, "rounds": rounds, "run_steps": run_steps, "variant": os.path.basename(lib_b), "ms_all": res,
-           "ms_median": {k: {m: float(np.median(v)) for m, v in d.items()} for k, d in res.items()},
-           "spread": {k: {m: spread(v) for m, v in d.items()} for k, d in res.items()}}
-    A.close()
-    B.close()
-    return out
+    steps = CL.schedule(run_steps)
+    soil = []  # the product context's soil temperatures, put back after every tier
+    modes = {tier: (lambda D, tier=tier: tier_ms(D, tier, soil[0])) for tier in TIERS}
+    modes["run+alt"] = lambda D: CL.run_ms(D, steps, st.RUN_ALT)
+    c = CL.compare_libraries(cols, rounds, [("product", None), ("variant", lib_b)], lambda n, p: build(n, lib_path=p), modes,
+                             prepare=lambda ctx: soil.append(ctx["product"].download("t_soisno", layout=st.LAYOUT_SOA)))
+    return {"columns": cols, "rounds": rounds, "run_steps": run_steps, "variant": os.path.basename(lib_b), "ms_all": c["all"],
+            "ms_median": c["median"], "spread": c["spread"]}
 
 
 def parent(cols, rounds, run_steps, lib_parent, parent_first):
     """The parent's library has no elmk_active_layer_*: neither context enables the feature, both run the unflagged step.  The second
     context of a process has run a step faster than the first at 1 M columns whatever the library, so both orders are recorded."""
-    load_parent(lib_parent)
-    if parent_first:
-        B, A = build(cols, lib_path=lib_parent, feature=False), build(cols, feature=False)
-    else:
-        A, B = build(cols, feature=False), build(cols, lib_path=lib_parent, feature=False)
-    steps = schedule(run_steps)
-    pair = (("this", A), ("parent", B))
-    res = {k: [] for k, _ in pair}
-    for r in range(rounds):
-        for key, D in (pair if r % 2 == 0 else pair[::-1]):
-            res[key].append(run_ms(D, steps, 0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    A.close()
-    B.close()
+    steps = CL.schedule(run_steps)
+    c = CL.compare_libraries(cols, rounds, [("this", None), ("parent", lib_parent)], lambda n, p: build(n, lib_path=p, feature=False),
+                             lambda D: CL.run_ms(D, steps, 0), first="parent" if parent_first else "this",
+                             optional=("elmk_active_layer_",), baseline="parent")
     return {"columns": cols, "rounds": rounds, "run_steps": run_steps, "parent": os.path.basename(lib_parent),
-            "first_context": "parent" if parent_first else "this", "run_ms_all": res,
-            "run_ms_median": med, "spread": {k: spread(v) for k, v in res.items()}, "this_over_parent": med["this"] / med["parent"]}
+            "first_context": "parent" if parent_first else "this", "run_ms_all": c["all"],
+            "run_ms_median": c["median"], "spread": c["spread"], "this_over_parent": c["this_over_parent"]}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--run-steps", type=int, default=6)
-    ap.add_argument("--ab", default=None)
-    ap.add_argument("--parent", default=None)
-    ap.add_argument("--parent-first", action="store_true")
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
+    a = CL.cli("1000000,10000000", 5, (CL.RUN_STEPS, CL.AB, CL.PARENT, CL.PARENT_FIRST))
+
+    def one(c):
         if a.ab:
-            r = ab(c, a.rounds, a.run_steps, a.ab)
-        elif a.parent:
-            r = parent(c, a.rounds, a.run_steps, a.parent, a.parent_first)
-        else:
-            r = measure(c, a.rounds, a.run_steps)
-        print(json.dumps(r), flush=True)
+            return ab(c, a.rounds, a.run_steps, a.ab)
+        if a.parent:
+            return parent(c, a.rounds, a.run_steps, a.parent, a.parent_first)
+        return measure(c, a.rounds, a.run_steps)
+
+    CL.emit_each(a, one)
 
 
 if __name__ == "__main__":

@@ -17,17 +17,13 @@ timed batch):
               run-to-run spread (max - min over the rounds) as the margin
 Prints one JSON line per column count (profiles/r14_aerosol_cost.jsonl).
 python tests/tools/aerosol_cost.py [--cols 1000000,10000000] [--rounds 5] [--run-steps 6] [--parent-lib path/to/libelmk_parent.so]"""
-import argparse
-import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 from elmkernels_amd import _lib as L  # noqa: E402
 from elmkernels_amd import accum  # noqa: E402
 from elmkernels_amd import aerosol  # noqa: E402
@@ -35,69 +31,17 @@ from elmkernels_amd import regrid  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
 from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 NLON, NLAT = 144, 96
 NCELLS = NLON * NLAT
-
-
-def load_parent(path):
-    """A build of the parent commit has every symbol but the new ones: declare what it exports."""
-    lib = C.CDLL(path)
-    for name, (res, args) in L.SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            assert name.startswith("elmk_aerosol_"), name
-            continue
-        fn.restype, fn.argtypes = res, args
-    L._libs[path] = lib
+CALLS = 40  # launches of a back-to-back series (upload_11: 3)
 
 
 def build(cols, lib_path=None):
-    D, _ = bench.build_state(cols, 0, "A", 0x5EEDE1A0, lib_path=lib_path)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
     lat, lon = synth.global_grid(cols, seed=11)
-    D.set_column_geography(lat, lon)
-    # a run over the two forcing records and two months the state already holds
-    D.run_reserve(2, 64)
-    for k in st.SERIES_FORCING + st.SERIES_PHENOLOGY:
-        a = D.download(k, layout=st.LAYOUT_SOA)
-        D.series_upload(k, 0, a)
+    D = CL.base_context(cols, lib_path=lib_path, geography=(lat, lon))
+    CL.resident_records(D)
     return D, np.degrees(lat), np.degrees(lon)
-
-
-def schedule(n):
-    S = np.zeros(n, st.RUN_STEP_DTYPE)
-    for s in range(n):
-        ddoy = 180.25 + s * DT / 86400.0
-        S[s]["decday"], S[s]["doy"], S[s]["forc_slot"] = ddoy + 1.0, int(ddoy), 0
-        w2 = np.full(8, (s + 0.5) / n)
-        S[s]["forc_wt1"], S[s]["forc_wt2"] = 1.0 - w2, w2
-        S[s]["month1"], S[s]["month2"], S[s]["month_wt1"], S[s]["month_wt2"] = 0, 1, 0.6, 0.4
-    return S
-
-
-def back_to_back(D, fn, n=40):
-    fn()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    D.sync()
-    return (time.perf_counter() - t0) / n * 1e3
-
-
-def run_ms(D, steps, flags, n=3):
-    def once():
-        D.restore_fields()
-        D.run(DT, steps, flags)
-    once()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        once()
-    D.sync()
-    return (time.perf_counter() - t0) / (n * len(steps)) * 1e3
 
 
 def reserve(D, series, idx, w):
@@ -114,7 +58,7 @@ def measure(cols, rounds, run_steps, parent_lib):
             Pn = build(cols, lib_path=parent_lib)[0]
         except L.ElmkError as e:  # (two contexts of this size do not fit: the line then says so instead of a parent figure)
             print(f"parent context at {cols} columns: {e}", file=sys.stderr)
-    steps = schedule(run_steps)
+    steps = CL.schedule(run_steps)
     series = aerosol.synthetic_climatology(NCELLS, seed=1)
     maps = {"aer_n1": regrid.nearest_map(lat, lon, NLON, NLAT), "aer_n4": regrid.bilinear_map(lat, lon, NLON, NLAT)}
     host = [np.ascontiguousarray(D[f]) for f in aerosol.FIELDS]
@@ -127,18 +71,18 @@ def measure(cols, rounds, run_steps, parent_lib):
     res = {m: [] for m in modes}
     for r in range(rounds):
         accum.add_t10(D, DT)
-        res["accum_1"].append(back_to_back(D, D.accum_update))
+        res["accum_1"].append(CL.back_to_back(D, D.accum_update, CALLS))
         D.accum_clear()
-        for key in (("aer_n4", "aer_n1") if r % 2 == 0 else ("aer_n1", "aer_n4")):
+        for key in CL.interleave(r, ("aer_n4", "aer_n1")):
             reserve(D, series, *maps[key])
-            res[key].append(back_to_back(D, lambda: D.aerosol_deposition(0, 1, 0.6, 0.4)))
-        res["upload_11"].append(back_to_back(D, upload_11, n=3))
+            res[key].append(CL.back_to_back(D, lambda: D.aerosol_deposition(0, 1, 0.6, 0.4), CALLS))
+        res["upload_11"].append(CL.back_to_back(D, upload_11, 3))
         reserve(D, series, *maps["aer_n1"])
         order = [("run", D, 0), ("run+aer", D, st.RUN_AEROSOL)] + ([("run_parent", Pn, 0)] if Pn else [])
-        for key, ctx, flags in (order if r % 2 == 0 else order[::-1]):
-            res[key].append(run_ms(ctx, steps, flags))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    spread = {k: float(max(v) - min(v)) for k, v in res.items()}
+        for key, ctx, flags in CL.interleave(r, order):
+            res[key].append(CL.run_ms(ctx, steps, flags))
+    med = CL.medians(res)
+    spread = {k: float(max(v) - min(v)) for k, v in res.items()}  # in ms, not over the median: the parent's is the margin
     bw0 = D.copy_bandwidth(1 << 30, 20, 0)
     D.close()
     if Pn:
@@ -161,16 +105,10 @@ def measure(cols, rounds, run_steps, parent_lib):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--run-steps", type=int, default=6)
-    ap.add_argument("--parent-lib", default=None)
-    a = ap.parse_args()
+    a = CL.cli("1000000,10000000", 5, (CL.RUN_STEPS, CL.arg("--parent-lib", default=None)))
     if a.parent_lib:
-        load_parent(a.parent_lib)
-    for c in [int(x) for x in a.cols.split(",")]:
-        print(json.dumps(measure(c, a.rounds, a.run_steps, a.parent_lib)), flush=True)
+        CL.load_build(a.parent_lib, optional=("elmk_aerosol_",))
+    CL.emit_each(a, lambda c: measure(c, a.rounds, a.run_steps, a.parent_lib))
 
 
 if __name__ == "__main__":

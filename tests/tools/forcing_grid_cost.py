@@ -14,8 +14,6 @@ make -C elmkernels_amd/csrc variant V=gridnt VFLAGS=-DELMK_GRID_MAP_NT=1), inter
 --only MODE/ORDER: one mode only (e.g. "column/spatial", "grid/16/bilinear/spatial"), for a rocprofv3 --kernel-trace --stats run of its
 own.
 python tests/tools/forcing_grid_cost.py [--cols 1000000,10000000] [--rounds 3] [--out profiles/r08_forcing_grid_cost.jsonl]"""
-import argparse
-import json
 import os
 import sys
 import time
@@ -23,27 +21,20 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
+from costlib import FORC, PHEN  # noqa: E402
 from elmkernels_amd import regrid as RG  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
 from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 NSTEPS, NREC, WINDOW = 48, 25, 24
-FORC, PHEN = st.SERIES_FORCING, st.SERIES_PHENOLOGY
 
 
 def schedule():
-    S = np.zeros(NSTEPS, st.RUN_STEP_DTYPE)
-    for s in range(NSTEPS):
-        ddoy = 13.875 + s * DT / 86400.0
-        S[s]["decday"], S[s]["doy"], S[s]["forc_slot"] = ddoy + 1.0, int(ddoy), s // 2
-        w2 = np.clip((s % 2) * 0.5 + 0.03 * np.arange(8), 0.0, 1.0)
-        S[s]["forc_wt2"], S[s]["forc_wt1"] = w2, 1.0 - w2
-        S[s]["month1"], S[s]["month2"] = (11, 0) if s < NSTEPS // 2 else (0, 1)
-        S[s]["month_wt1"], S[s]["month_wt2"] = 0.4, 0.6
-    return S
+    """The day of run_cost.py: hourly records from mid-January, the month bracket moving at half time."""
+    return CL.evolving_schedule(NSTEPS, 13.875, 2, [(11, 0)] * (NSTEPS // 2) + [(0, 1)] * (NSTEPS // 2))
 
 
 def grid_shape(ncells):
@@ -65,11 +56,8 @@ class Case:
     """One context with its geography; host records alternate between two rows (the bytes moved are those of distinct records)."""
 
     def __init__(self, ncols, order, lib_path=None):
-        self.D, _ = bench.build_state(ncols, 0, "B", 0x5EEDE1A0, lib_path=lib_path)
-        self.D.set_snow_age_tables(synth.snow_age_tables())
-        self.D.set_graph(True)
         self.lat, self.lon = geography(ncols, order)
-        self.D.set_column_geography(self.lat, self.lon)
+        self.D = CL.base_context(ncols, "B", lib_path, geography=(self.lat, self.lon))
         self.rows = {}
         for k in FORC + PHEN:
             a = self.D.download(k, layout=st.LAYOUT_SOA)
@@ -109,19 +97,17 @@ class Case:
 
     def two_runs(self, steps):
         D = self.D
-        D.sync()
-        t0 = time.perf_counter()
-        D.run(DT, steps[:WINDOW])
-        self.upload(self.split, NREC)
-        D.run(DT, steps[WINDOW:])
-        D.run_diagnostics()
-        return (time.perf_counter() - t0) * 1e3 / NSTEPS
+
+        def runs():
+            D.run(DT, steps[:WINDOW])
+            self.upload(self.split, NREC)
+            D.run(DT, steps[WINDOW:])
+            D.run_diagnostics()
+
+        return CL.wall_ms(D, runs) / NSTEPS
 
     def window_upload(self):
-        self.D.sync()
-        t0 = time.perf_counter()
-        self.upload(self.split, self.split + 12)
-        return (time.perf_counter() - t0) * 1e3
+        return CL.wall_ms(self.D, lambda: self.upload(self.split, self.split + 12))
 
 
 def mode_name(m):
@@ -175,7 +161,7 @@ def measure(ncols, rounds, threads, only=None, ab=None):
                     ms = B.two_runs(steps)
                     if r > 0:
                         res[mode_name(m) + "/ab"].append(ms)
-        med = {k: float(np.median(v)) for k, v in res.items() if v}
+        med = CL.medians({k: v for k, v in res.items() if v})
         rec = {"columns": ncols, "order": order, "tier": "B", "steps": NSTEPS, "runs": 2, "records": NREC, "rounds": rounds,
                "unit": "ms per step (wall clock)", "median": med, "all": res, "window12_upload_ms": upl, "device_bytes": dev,
                "ncells": {f"grid/{d}": int(np.prod(grid_shape(ncols // d))) for d in (16, 150)},
@@ -193,21 +179,8 @@ def measure(ncols, rounds, threads, only=None, ab=None):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--only", default=None)
-    ap.add_argument("--ab", default=None)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
-        for r in measure(c, a.rounds, a.threads, a.only, a.ab):
-            line = json.dumps(r)
-            print(line, flush=True)
-            if a.out:
-                with open(a.out, "a") as f:
-                    f.write(line + "\n")
+    a = CL.cli("1000000,10000000", 3, (CL.arg("--threads", type=int, default=16), CL.arg("--only", default=None), CL.AB), out=True)
+    CL.emit_each(a, lambda c: measure(c, a.rounds, a.threads, a.only, a.ab))
 
 
 if __name__ == "__main__":

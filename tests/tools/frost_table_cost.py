@@ -14,23 +14,19 @@ Prints one JSON line per column count (profiles/r17_frost_table_cost.jsonl), wit
 --parent LIB: the stage without the extension alone, alternated between this build and LIB, a build of the parent commit's library, on
 both tiers: `off` must not have moved, and the margin is this job's own spread.
 python tests/tools/frost_table_cost.py [--cols 1000000,10000000] [--rounds 5] [--run-steps 6] [--parent LIB [--parent-first]]"""
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(HERE, "..", ".."))
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 import hydrology_cost as HC  # noqa: E402
-from elmkernels_amd import _lib as L  # noqa: E402
 from elmkernels_amd import hydrology as hy  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
 
-DT = HC.DT
+DT = CL.DT
+CALLS = HC.CALLS
 # DESIGN.md section 20: the stage's tally plus ten t_soisno, the parameter, three stored rows, and the loads F' repeats (dz and the ice:
 # 20; hksat over the layers it sums: up to 10; three node depths)
 BYTES_PER_COLUMN = {"off": HC.BYTES_PER_COLUMN, "on": HC.BYTES_PER_COLUMN + 8 * (10 + 1 + 3 + 20 + 10 + 3)}
@@ -89,10 +85,10 @@ def measure(cols, rounds, run_steps):
     for name, tier in T.items():
         set_tier(D, tier, wa)
         for r in range(rounds):
-            for on in ((False, True) if r % 2 == 0 else (True, False)):
+            for on in CL.interleave(r, (False, True)):
                 extension(D, on, q)
                 reset(D, tier, wa)
-                res[f"{name}_{'on' if on else 'off'}"].append(HC.back_to_back(D, lambda: D.soil_hydrology(DT)))
+                res[f"{name}_{'on' if on else 'off'}"].append(CL.back_to_back(D, lambda: D.soil_hydrology(DT), CALLS))
     # the branches of the permafrost tier, on the first columns (the tier is still set)
     extension(D, True, q)
     reset(D, T["permafrost"], wa)
@@ -110,18 +106,18 @@ def measure(cols, rounds, run_steps):
     branches = {k: v for k, v in sorted(marks.items()) if k.startswith(("frost_", "perched_"))}
     # the run step: the snapshot of the benchmark again, so that its restore costs what it costs there
     D.restore_fields()
-    D.snapshot_fields(bench.RESTORE_FIELDS)
-    steps = HC.schedule(run_steps)
+    D.snapshot_fields(CL.bench.RESTORE_FIELDS)
+    steps = CL.schedule(run_steps)
     for r in range(rounds):
-        for on in ((False, True) if r % 2 == 0 else (True, False)):
+        for on in CL.interleave(r, (False, True)):
             extension(D, on, q)
             D.soil_hydrology_init(T["permafrost"][1], wa)
             D.upload("t_soisno", T["permafrost"][0])
-            res["run_on" if on else "run_off"].append(HC.run_ms(D, steps, st.RUN_HYDROLOGY))
-    med = {k: float(np.median(v)) for k, v in res.items()}
+            res["run_on" if on else "run_off"].append(CL.run_ms(D, steps, st.RUN_HYDROLOGY))
+    med = CL.medians(res)
     D.close()
     out = {"columns": cols, "rounds": rounds, "run_steps": run_steps, "ms_median": med, "ms_all": res,
-           "spread": {k: HC.spread(v) for k, v in res.items()}, "bytes_per_column": BYTES_PER_COLUMN, "branches_first_columns": branches}
+           "spread": CL.spreads(res), "bytes_per_column": BYTES_PER_COLUMN, "branches_first_columns": branches}
     for t in T:
         out[f"{t}_on_over_off"] = med[f"{t}_on"] / med[f"{t}_off"]
         out[f"{t}_TBps"] = {m: BYTES_PER_COLUMN[m] * cols / (med[f"{t}_{m}"] * 1e-3) / 1e12 for m in ("off", "on")}
@@ -131,44 +127,35 @@ def measure(cols, rounds, run_steps):
 
 
 def parent(cols, rounds, lib_parent, parent_first):
-    """The parent's library has the stage and none of elmk_soil_hydrology_frost_*: both contexts run the stage without the extension."""
-    L.load(lib_parent, optional=("elmk_soil_hydrology_frost",))
-    if parent_first:
-        B, A = HC.build(cols, lib_path=lib_parent), HC.build(cols)
-    else:
-        A, B = HC.build(cols), HC.build(cols, lib_path=lib_parent)
-    pair = (("this", A), ("parent", B))
-    wa = np.full(cols, 4000.0)
-    for _, D in pair:
-        D.snapshot_fields(WRITTEN)
-    T = tiers(A, cols)
-    res = {f"{t}_{k}": [] for t in T for k, _ in pair}
-    for name, tier in T.items():
-        for _, D in pair:
-            set_tier(D, tier, wa)
-        for r in range(rounds):
-            for key, D in (pair if r % 2 == 0 else pair[::-1]):
-                reset(D, tier, wa)
-                res[f"{name}_{key}"].append(HC.back_to_back(D, lambda: D.soil_hydrology(DT)))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    A.close()
-    B.close()
+    """The parent's library has the stage and none of elmk_soil_hydrology_frost_*: both contexts run the stage without the extension.
+    One tier after the other, all rounds of a tier together: the contexts are opened once and take their turns inside each tier."""
+    pair = CL.open_builds(cols, [("this", None), ("parent", lib_parent)], lambda n, p: HC.build(n, lib_path=p),
+                          first="parent" if parent_first else "this", optional=("elmk_soil_hydrology_frost",))
+    try:
+        wa = np.full(cols, 4000.0)
+        for D in pair.values():
+            D.snapshot_fields(WRITTEN)
+        T = tiers(pair["this"], cols)
+        res = {f"{t}_{k}": [] for t in T for k in pair}
+        for name, tier in T.items():
+            for D in pair.values():
+                set_tier(D, tier, wa)
+            for r in range(rounds):
+                for key in CL.interleave(r, pair):
+                    D = pair[key]
+                    reset(D, tier, wa)
+                    res[f"{name}_{key}"].append(CL.back_to_back(D, lambda: D.soil_hydrology(DT), CALLS))
+    finally:
+        CL.close_all(pair)
+    med = CL.medians(res)
     return {"columns": cols, "rounds": rounds, "parent": os.path.basename(lib_parent), "first_context": "parent" if parent_first else "this",
-            "stage_off_ms_all": res, "stage_off_ms_median": med, "spread": {k: HC.spread(v) for k, v in res.items()},
+            "stage_off_ms_all": res, "stage_off_ms_median": med, "spread": CL.spreads(res),
             "this_over_parent": {t: med[f"{t}_this"] / med[f"{t}_parent"] for t in T}}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--run-steps", type=int, default=6)
-    ap.add_argument("--parent", default=None)
-    ap.add_argument("--parent-first", action="store_true")
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
-        r = parent(c, a.rounds, a.parent, a.parent_first) if a.parent else measure(c, a.rounds, a.run_steps)
-        print(json.dumps(r), flush=True)
+    a = CL.cli("1000000,10000000", 5, (CL.RUN_STEPS, CL.PARENT, CL.PARENT_FIRST))
+    CL.emit_each(a, lambda c: parent(c, a.rounds, a.parent, a.parent_first) if a.parent else measure(c, a.rounds, a.run_steps))
 
 
 if __name__ == "__main__":

@@ -11,20 +11,16 @@ For each column count, interleaved over `rounds` repeats (the modes take turns i
 and elmk_copy_bandwidth (shape 0, and the best of shapes 0..3) from the same process.
 --ab LIB: accumulate alone, interleaved between the product library and LIB (a build of the same ABI), for an A/B.
 python tests/tools/history_cost.py [--cols 1000000,10000000] [--rounds 5] [--ab path/to/libelmk_variant.so]"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
-from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 FLUXES = ["eflx_sh_tot", "eflx_lh_tot", "qflx_evap_tot", "eflx_soil_grnd", "eflx_lwrad_out", "fsa", "fsr", "sabg", "sabv",
           "qflx_tran_veg", "t_ref2m", "q_ref2m"]
 PRIMARY = st.ELMInterface.PRIMARY_VARS
@@ -48,10 +44,7 @@ def register(D, names):
 
 
 def build(cols, lib_path=None):
-    D, _ = bench.build_state(cols, 0, "A", 0x5EEDE1A0, lib_path=lib_path)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
-    return D
+    return CL.base_context(cols, lib_path=lib_path)
 
 
 def measure(cols, rounds, steps):
@@ -71,27 +64,18 @@ def measure(cols, rounds, steps):
         for k in PRIMARY:
             D.download(k, out=out[k])
 
-    def run(fn, n):
-        fn()
-        D.sync()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        D.sync()
-        return (time.perf_counter() - t0) / n * 1e3
-
     res = {m: [] for m in ("phys", "phys+acc_a", "phys+acc_b", "phys+dl_b", "acc_a", "acc_b")}
     for r in range(rounds):
-        res["phys"].append(run(phys, steps))
+        res["phys"].append(CL.back_to_back(D, phys, steps))
         register(D, FLUXES)
-        res["phys+acc_a"].append(run(phys_acc, steps))
-        res["acc_a"].append(run(D.history_accumulate, 4 * steps))
+        res["phys+acc_a"].append(CL.back_to_back(D, phys_acc, steps))
+        res["acc_a"].append(CL.back_to_back(D, D.history_accumulate, 4 * steps))
         register(D, PRIMARY)
-        res["phys+acc_b"].append(run(phys_acc, steps))
-        res["acc_b"].append(run(D.history_accumulate, 4 * steps))
+        res["phys+acc_b"].append(CL.back_to_back(D, phys_acc, steps))
+        res["acc_b"].append(CL.back_to_back(D, D.history_accumulate, 4 * steps))
         D.history_clear()
-        res["phys+dl_b"].append(run(phys_dl, max(2, steps // 3)))
-    med = {k: float(np.median(v)) for k, v in res.items()}
+        res["phys+dl_b"].append(CL.back_to_back(D, phys_dl, max(2, steps // 3)))
+    med = CL.medians(res)
     bytes_a, bytes_b = tape_bytes(D, FLUXES), tape_bytes(D, PRIMARY)
     bw0 = D.copy_bandwidth(1 << 30, 20, 0)
     bw_best = max([bw0] + [D.copy_bandwidth(1 << 30, 20, s) for s in (1, 2, 3)])
@@ -109,40 +93,19 @@ def measure(cols, rounds, steps):
 
 
 def ab(cols, rounds, lib_b):
-    A, B = build(cols), build(cols, lib_path=lib_b)
-    res = {"product": {"a": [], "b": []}, "variant": {"a": [], "b": []}}
+    def tape(names):
+        def t(D):
+            register(D, names)
+            return CL.back_to_back(D, D.history_accumulate, 20)
+        return t
 
-    def t(D, n=20):
-        D.history_accumulate()
-        D.sync()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            D.history_accumulate()
-        D.sync()
-        return (time.perf_counter() - t0) / n * 1e3
-
-    for r in range(rounds):
-        for tape, names in (("a", FLUXES), ("b", PRIMARY)):
-            for key, D in ((("product", A), ("variant", B)) if r % 2 == 0 else (("variant", B), ("product", A))):
-                register(D, names)
-                res[key][tape].append(t(D))
-    out = {"columns": cols, "rounds": rounds, "variant": os.path.basename(lib_b), "ms_all": res,
-           "ms_median": {k: {tp: float(np.median(v)) for tp, v in d.items()} for k, d in res.items()}}
-    A.close()
-    B.close()
-    return out
+    c = CL.compare_libraries(cols, rounds, [("product", None), ("variant", lib_b)], build, {"a": tape(FLUXES), "b": tape(PRIMARY)})
+    return {"columns": cols, "rounds": rounds, "variant": os.path.basename(lib_b), "ms_all": c["all"], "ms_median": c["median"]}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", type=int, default=6)
-    ap.add_argument("--ab", default=None)
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
-        r = ab(c, a.rounds, a.ab) if a.ab else measure(c, a.rounds, a.steps)
-        print(json.dumps(r), flush=True)
+    a = CL.cli("1000000,10000000", 5, (CL.arg("--steps", type=int, default=6), CL.AB))
+    CL.emit_each(a, lambda c: ab(c, a.rounds, a.ab) if a.ab else measure(c, a.rounds, a.steps))
 
 
 if __name__ == "__main__":

@@ -14,39 +14,23 @@ Prints one JSON line per column count (profiles/r16_hydrology_cost.jsonl), with 
 --parent LIB: the unflagged run step alone, alternated between this build and LIB, a build of the parent commit's library: the
 unflagged step must not have moved.
 python tests/tools/hydrology_cost.py [--cols 1000000,10000000] [--rounds 5] [--run-steps 6] [--parent LIB [--parent-first]]"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
-from elmkernels_amd import _lib as L  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 from elmkernels_amd import hydrology as hy  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
-from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 BYTES_PER_COLUMN = 1196
-
-
-def load_parent(path):
-    """A build of the parent commit has every symbol but the new ones."""
-    L.load(path, optional=("elmk_soil_hydrology",))
+CALLS = 20  # launches of a back-to-back series
 
 
 def build(cols, lib_path=None, feature=True):
-    D, _ = bench.build_state(cols, 0, "A", 0x5EEDE1A0, lib_path=lib_path)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
-    lat, lon = synth.global_grid(cols, seed=11)
-    D.set_column_geography(lat, lon)
-    D.run_reserve(2, 64)
-    for k in st.SERIES_FORCING + st.SERIES_PHENOLOGY:
-        D.series_upload(k, 0, D.download(k, layout=st.LAYOUT_SOA))
+    D = CL.run_context(cols, lib_path=lib_path)
     if feature:
         D.soil_hydrology_enable()
         one = hy.hksat_from_texture(np.full((1, hy.N), 45.0), np.full((1, hy.N), 20.0), np.full((1, hy.N), 10.0), np.geomspace(0.007, 2.9, hy.N)[None, :])
@@ -56,66 +40,27 @@ def build(cols, lib_path=None, feature=True):
     return D
 
 
-def schedule(n):
-    S = np.zeros(n, st.RUN_STEP_DTYPE)
-    for s in range(n):
-        ddoy = 180.25 + s * DT / 86400.0
-        S[s]["decday"], S[s]["doy"], S[s]["forc_slot"] = ddoy + 1.0, int(ddoy), 0
-        w2 = np.full(8, (s + 0.5) / n)
-        S[s]["forc_wt1"], S[s]["forc_wt2"] = 1.0 - w2, w2
-        S[s]["month1"], S[s]["month2"], S[s]["month_wt1"], S[s]["month_wt2"] = 0, 1, 0.6, 0.4
-    return S
-
-
-def back_to_back(D, fn, n=20):
-    fn()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    D.sync()
-    return (time.perf_counter() - t0) / n * 1e3
-
-
-def run_ms(D, steps, flags, n=3):
-    def once():
-        D.restore_fields()
-        D.run(DT, steps, flags)
-    once()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        once()
-    D.sync()
-    return (time.perf_counter() - t0) / (n * len(steps)) * 1e3
-
-
-def spread(v):
-    return (max(v) - min(v)) / float(np.median(v))
-
-
 def measure(cols, rounds, run_steps):
     D = build(cols)
-    steps = schedule(run_steps)
+    steps = CL.schedule(run_steps)
     res = {m: [] for m in ("stage", "mixed", "run", "run+hyd")}
     zw = np.array([0.01, 0.05, 0.3, 1.0, 2.5, 3.7, 3.9, 8.8, 12.0])[np.arange(cols) % 9]
     wa = np.full(cols, 4000.0)
     for r in range(rounds):
-        for key in (("stage", "mixed") if r % 2 == 0 else ("mixed", "stage")):
+        for key in CL.interleave(r, ("stage", "mixed")):
             if key == "mixed":
                 D.soil_hydrology_init(zw, wa)
             else:
                 D.soil_hydrology_init()
-            res[key].append(back_to_back(D, lambda: D.soil_hydrology(DT)))
+            res[key].append(CL.back_to_back(D, lambda: D.soil_hydrology(DT), CALLS))
         D.soil_hydrology_init()
-        order = (("run", 0), ("run+hyd", st.RUN_HYDROLOGY)) if r % 2 == 0 else (("run+hyd", st.RUN_HYDROLOGY), ("run", 0))
-        for key, flags in order:
-            res[key].append(run_ms(D, steps, flags))
+        for key, flags in CL.interleave(r, (("run", 0), ("run+hyd", st.RUN_HYDROLOGY))):
+            res[key].append(CL.run_ms(D, steps, flags))
             D.soil_hydrology_init()
-    med = {k: float(np.median(v)) for k, v in res.items()}
+    med = CL.medians(res)
     D.close()
     return {"columns": cols, "rounds": rounds, "run_steps": run_steps, "ms_median": med, "ms_all": res,
-            "spread": {k: spread(v) for k, v in res.items()}, "stage_bytes": BYTES_PER_COLUMN * cols,
+            "spread": CL.spreads(res), "stage_bytes": BYTES_PER_COLUMN * cols,
             "stage_TBps": BYTES_PER_COLUMN * cols / (med["stage"] * 1e-3) / 1e12,
             "mixed_TBps": BYTES_PER_COLUMN * cols / (med["mixed"] * 1e-3) / 1e12, "mixed_over_stage": med["mixed"] / med["stage"], "run_step_with_over_without": med["run+hyd"] / med["run"],
             "run_step_added_ms": med["run+hyd"] - med["run"]}
@@ -123,36 +68,18 @@ def measure(cols, rounds, run_steps):
 
 def parent(cols, rounds, run_steps, lib_parent, parent_first):
     """The parent's library has no elmk_soil_hydrology*: neither context enables the feature, both run the unflagged step."""
-    load_parent(lib_parent)
-    if parent_first:
-        B, A = build(cols, lib_path=lib_parent, feature=False), build(cols, feature=False)
-    else:
-        A, B = build(cols, feature=False), build(cols, lib_path=lib_parent, feature=False)
-    steps = schedule(run_steps)
-    pair = (("this", A), ("parent", B))
-    res = {k: [] for k, _ in pair}
-    for r in range(rounds):
-        for key, D in (pair if r % 2 == 0 else pair[::-1]):
-            res[key].append(run_ms(D, steps, 0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    A.close()
-    B.close()
+    steps = CL.schedule(run_steps)
+    c = CL.compare_libraries(cols, rounds, [("this", None), ("parent", lib_parent)], lambda n, p: build(n, lib_path=p, feature=False),
+                             lambda D: CL.run_ms(D, steps, 0), first="parent" if parent_first else "this",
+                             optional=("elmk_soil_hydrology",), baseline="parent")
     return {"columns": cols, "rounds": rounds, "run_steps": run_steps, "parent": os.path.basename(lib_parent),
-            "first_context": "parent" if parent_first else "this", "run_ms_all": res, "run_ms_median": med,
-            "spread": {k: spread(v) for k, v in res.items()}, "this_over_parent": med["this"] / med["parent"]}
+            "first_context": "parent" if parent_first else "this", "run_ms_all": c["all"], "run_ms_median": c["median"],
+            "spread": c["spread"], "this_over_parent": c["this_over_parent"]}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--run-steps", type=int, default=6)
-    ap.add_argument("--parent", default=None)
-    ap.add_argument("--parent-first", action="store_true")
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
-        r = parent(c, a.rounds, a.run_steps, a.parent, a.parent_first) if a.parent else measure(c, a.rounds, a.run_steps)
-        print(json.dumps(r), flush=True)
+    a = CL.cli("1000000,10000000", 5, (CL.RUN_STEPS, CL.PARENT, CL.PARENT_FIRST))
+    CL.emit_each(a, lambda c: parent(c, a.rounds, a.run_steps, a.parent, a.parent_first) if a.parent else measure(c, a.rounds, a.run_steps))
 
 
 if __name__ == "__main__":

@@ -16,38 +16,21 @@ Prints one JSON line per column count (profiles/r18_irrigation_cost.jsonl).
 (git worktree add ../parent HEAD~1 && make -C ../parent/elmkernels_amd/csrc): the unflagged step must not have moved.
 --parent2 LIB2 with --parent: LIB2, a second build of the parent, takes this build's place: the difference of the two is the margin.
 python tests/tools/irrigation_cost.py [--cols 1000000,10000000] [--rounds 5] [--run-steps 6] [--parent LIB [--parent-first] [--parent2 LIB2]]"""
-import argparse
-import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
-from elmkernels_amd import _lib as L  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 from elmkernels_amd import accum  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
-from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 IDLE_BYTES = 40
 NOON = 43200
 IDLE_DT = 900.0  # the idle tier's step: from a quarter past to the half hour, between the bands' clocks
-
-
-def load_parent(path):
-    """A build of the parent commit has every symbol but the new ones: declare what it exports."""
-    lib = C.CDLL(path)
-    for name, (res, args) in L.SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            assert name.startswith("elmk_irrigation"), name
-            continue
-        fn.restype, fn.argtypes = res, args
-    L._libs[path] = lib
+CALLS = 40  # launches of a back-to-back series
 
 
 def band_sched(cols):
@@ -56,57 +39,10 @@ def band_sched(cols):
 
 
 def build(cols, lib_path=None, sched=None):
-    D, _ = bench.build_state(cols, 0, "A", 0x5EEDE1A0, lib_path=lib_path)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
-    lat, lon = synth.global_grid(cols, seed=11)
-    D.set_column_geography(lat, lon)
-    # a run over the two forcing records and two months the state already holds
-    D.run_reserve(2, 64)
-    for k in st.SERIES_FORCING + st.SERIES_PHENOLOGY:
-        a = D.download(k, layout=st.LAYOUT_SOA)
-        D.series_upload(k, 0, a)
+    D = CL.run_context(cols, lib_path=lib_path)
     if sched is not None:
         D.irrigation_enable(sched)
     return D
-
-
-def schedule(n):
-    S = np.zeros(n, st.RUN_STEP_DTYPE)
-    for s in range(n):
-        ddoy = 180.25 + s * DT / 86400.0
-        S[s]["decday"], S[s]["doy"], S[s]["forc_slot"] = ddoy + 1.0, int(ddoy), 0
-        w2 = np.full(8, (s + 0.5) / n)
-        S[s]["forc_wt1"], S[s]["forc_wt2"] = 1.0 - w2, w2
-        S[s]["month1"], S[s]["month2"], S[s]["month_wt1"], S[s]["month_wt2"] = 0, 1, 0.6, 0.4
-    return S
-
-
-def back_to_back(D, fn, n=40):
-    fn()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    D.sync()
-    return (time.perf_counter() - t0) / n * 1e3
-
-
-def run_ms(D, steps, flags, n=3):
-    def once():
-        D.restore_fields()
-        D.run(DT, steps, flags)
-    once()
-    D.sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        once()
-    D.sync()
-    return (time.perf_counter() - t0) / (n * len(steps)) * 1e3
-
-
-def spread(v):
-    return (max(v) - min(v)) / float(np.median(v))
 
 
 def checking_bytes(D, col0, n):
@@ -126,7 +62,7 @@ def checking_bytes(D, col0, n):
 def measure(cols, rounds, run_steps):
     sched = band_sched(cols)
     D = build(cols, sched=sched)
-    steps = schedule(run_steps)
+    steps = CL.schedule(run_steps)
     accum.add_t10(D, DT)
     # band 24 passes 06:00 local at tod = 21600 - 24 * 1800 (mod a day); in the 900 s from noon + 900 s no band does (every band is on a
     # half hour)
@@ -138,22 +74,22 @@ def measure(cols, rounds, run_steps):
     res = {m: [] for m in ("irr_idle", "irr_band", "accum_t10", "run", "run+irr")}
     tally = []
     for r in range(rounds):
-        for mode in (("irr_idle", "irr_band") if r % 2 == 0 else ("irr_band", "irr_idle")):
+        for mode in CL.interleave(r, ("irr_idle", "irr_band")):
             D.irrigation_init()
             if mode == "irr_band":
                 tally.append(checking_bytes(D, int(band[0]), band.size))
-            res[mode].append(back_to_back(D, (lambda: D.irrigation(IDLE_DT, idle_tod)) if mode == "irr_idle" else (lambda: D.irrigation(DT, tod_band))))
-        res["accum_t10"].append(back_to_back(D, D.accum_update))
+            launch = (lambda: D.irrigation(IDLE_DT, idle_tod)) if mode == "irr_idle" else (lambda: D.irrigation(DT, tod_band))
+            res[mode].append(CL.back_to_back(D, launch, CALLS))
+        res["accum_t10"].append(CL.back_to_back(D, D.accum_update, CALLS))
         D.irrigation_init()
-        order = (("run", 0), ("run+irr", st.RUN_IRRIGATION)) if r % 2 == 0 else (("run+irr", st.RUN_IRRIGATION), ("run", 0))
-        for key, flags in order:
-            res[key].append(run_ms(D, steps, flags))
-    med = {k: float(np.median(v)) for k, v in res.items()}
+        for key, flags in CL.interleave(r, (("run", 0), ("run+irr", st.RUN_IRRIGATION))):
+            res[key].append(CL.run_ms(D, steps, flags))
+    med = CL.medians(res)
     nchecks, check_bytes = tally[len(tally) // 2]
     band_bytes = IDLE_BYTES * cols + check_bytes
     D.close()
     return {"columns": cols, "rounds": rounds, "run_steps": run_steps, "ms_median": med, "ms_all": res,
-            "spread": {k: spread(v) for k, v in res.items()}, "accum_t10_GBps": 32 * cols / (med["accum_t10"] * 1e-3) / 1e9,
+            "spread": CL.spreads(res), "accum_t10_GBps": 32 * cols / (med["accum_t10"] * 1e-3) / 1e9,
             "irr_idle_bytes": IDLE_BYTES * cols, "irr_idle_GBps": IDLE_BYTES * cols / (med["irr_idle"] * 1e-3) / 1e9,
             "irr_band_bytes": band_bytes, "irr_band_GBps": band_bytes / (med["irr_band"] * 1e-3) / 1e9, "band_columns": int(band.size),
             "checking_columns_per_round": [t[0] for t in tally],
@@ -165,39 +101,18 @@ def parent(cols, rounds, run_steps, lib_parent, parent_first, lib_this=None):
     """The parent's library has no elmk_irrigation_*: neither context enables the feature, both run the unflagged step.  The second
     context of a process has run a step faster than the first at 1 M columns whatever the library, so both orders are recorded.
     lib_this: a second build of the parent in the place of this build - what two builds of the same sources differ by is the margin."""
-    load_parent(lib_parent)
-    if lib_this:
-        load_parent(lib_this)
-    if parent_first:
-        B, A = build(cols, lib_path=lib_parent), build(cols, lib_path=lib_this)
-    else:
-        A, B = build(cols, lib_path=lib_this), build(cols, lib_path=lib_parent)
-    steps = schedule(run_steps)
-    pair = (("this", A), ("parent", B))
-    res = {k: [] for k, _ in pair}
-    for r in range(rounds):
-        for key, D in (pair if r % 2 == 0 else pair[::-1]):
-            res[key].append(run_ms(D, steps, 0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    A.close()
-    B.close()
+    steps = CL.schedule(run_steps)
+    c = CL.compare_libraries(cols, rounds, [("this", lib_this), ("parent", lib_parent)], lambda n, p: build(n, lib_path=p),
+                             lambda D: CL.run_ms(D, steps, 0), first="parent" if parent_first else "this",
+                             optional=("elmk_irrigation",), baseline="parent")
     return {"columns": cols, "rounds": rounds, "run_steps": run_steps, "parent": os.path.basename(lib_parent),
-            "this": os.path.basename(lib_this) if lib_this else "libelmk.so", "first_context": "parent" if parent_first else "this", "run_ms_all": res,
-            "run_ms_median": med, "spread": {k: spread(v) for k, v in res.items()}, "this_over_parent": med["this"] / med["parent"]}
+            "this": os.path.basename(lib_this) if lib_this else "libelmk.so", "first_context": "parent" if parent_first else "this", "run_ms_all": c["all"],
+            "run_ms_median": c["median"], "spread": c["spread"], "this_over_parent": c["this_over_parent"]}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--run-steps", type=int, default=6)
-    ap.add_argument("--parent", default=None)
-    ap.add_argument("--parent-first", action="store_true")
-    ap.add_argument("--parent2", default=None)
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
-        r = parent(c, a.rounds, a.run_steps, a.parent, a.parent_first, a.parent2) if a.parent else measure(c, a.rounds, a.run_steps)
-        print(json.dumps(r), flush=True)
+    a = CL.cli("1000000,10000000", 5, (CL.RUN_STEPS, CL.PARENT, CL.PARENT_FIRST, CL.PARENT2))
+    CL.emit_each(a, lambda c: parent(c, a.rounds, a.run_steps, a.parent, a.parent_first, a.parent2) if a.parent else measure(c, a.rounds, a.run_steps))
 
 
 if __name__ == "__main__":

@@ -11,22 +11,18 @@ the same cells over permuted columns ("shuffled").  Per column count and map it 
 --kernel-loop MAP: only N gridded downloads of one map, for a rocprofv3 --kernel-trace --stats run of its own;
 --stats DB: read that run's results database and append the aggregate kernel's time with the rate it implies at the floor bytes.
 python tests/tools/output_grid_cost.py [--cols 1000000,10000000] [--rounds 3] [--out profiles/r09_output_grid_cost.jsonl]"""
-import argparse
-import json
 import os
 import sqlite3
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 from elmkernels_amd import regrid as RG  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
-from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 NCELLS = 67420
 FILL = 1.0e36
 FLUXES = ["eflx_sh_tot", "eflx_lh_tot", "qflx_evap_tot", "eflx_soil_grnd", "eflx_lwrad_out", "fsa", "fsr", "sabg", "sabv",
@@ -46,20 +42,7 @@ def floor_bytes(ptr, ncols):
 
 
 def build(cols):
-    D, _ = bench.build_state(cols, 0, "A", 0x5EEDE1A0)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
-    return D
-
-
-def timed(fn, n, sync):
-    fn()
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    sync()
-    return (time.perf_counter() - t0) / n * 1e3
+    return CL.base_context(cols)
 
 
 def measure(cols, rounds, steps):
@@ -73,9 +56,9 @@ def measure(cols, rounds, steps):
             D.set_output_grid(ptr, col, w, FILL)
             R = res.setdefault(kind, {m: [] for m in ("dl_gridded", "dl_column", "dl_column+host", "phys", "phys+acc_col", "phys+acc_grid",
                                                        "acc_col", "acc_grid")})
-            R["dl_gridded"].append(timed(lambda: D.download_gridded("t_grnd"), 20, D.sync))
-            R["dl_column"].append(timed(lambda: D.download("t_grnd", out=out), 5, D.sync))
-            R["dl_column+host"].append(timed(lambda: RG.apply_aggregate(ptr, col, w, D.download("t_grnd", out=out), FILL), 3, D.sync))
+            R["dl_gridded"].append(CL.back_to_back(D, lambda: D.download_gridded("t_grnd"), 20))
+            R["dl_column"].append(CL.back_to_back(D, lambda: D.download("t_grnd", out=out), 5))
+            R["dl_column+host"].append(CL.back_to_back(D, lambda: RG.apply_aggregate(ptr, col, w, D.download("t_grnd", out=out), FILL), 3))
 
             def phys():
                 D.restore_fields()
@@ -85,19 +68,19 @@ def measure(cols, rounds, steps):
                 phys()
                 D.history_accumulate()
 
-            R["phys"].append(timed(phys, steps, D.sync))
+            R["phys"].append(CL.back_to_back(D, phys, steps))
             for tag, add in (("col", D.history_add), ("grid", D.gridded_history_add)):
                 D.history_clear()
                 for k in FLUXES:
                     add(0, k, "avg")
-                R[f"phys+acc_{tag}"].append(timed(phys_acc, steps, D.sync))
-                R[f"acc_{tag}"].append(timed(D.history_accumulate, 4 * steps, D.sync))
+                R[f"phys+acc_{tag}"].append(CL.back_to_back(D, phys_acc, steps))
+                R[f"acc_{tag}"].append(CL.back_to_back(D, D.history_accumulate, 4 * steps))
     D.history_clear()
     bw0 = D.copy_bandwidth(1 << 30, 20, 0)
     bw_best = max([bw0] + [D.copy_bandwidth(1 << 30, 20, s) for s in (1, 2, 3)])
     lines = []
     for kind, (ptr, col, w) in maps.items():
-        med = {k: float(np.median(v)) for k, v in res[kind].items()}
+        med = CL.medians(res[kind])
         fb = floor_bytes(ptr, cols)
         lines.append({
             "tool": "output_grid_cost", "columns": cols, "cells": NCELLS, "map": kind, "nnz": int(ptr[-1]), "rounds": rounds,
@@ -133,26 +116,14 @@ def stats_line(path, cols, kind):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=6)
-    ap.add_argument("--kernel-loop", default=None, help="contiguous | shuffled")
-    ap.add_argument("--stats", default=None)
-    ap.add_argument("--map", default="contiguous")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    cols = [int(c) for c in a.cols.split(",")]
+    a = CL.cli("1000000,10000000", 3, (CL.arg("--steps", type=int, default=6), CL.arg("--kernel-loop", default=None, help="contiguous | shuffled"),
+                                         CL.arg("--stats", default=None), CL.arg("--map", default="contiguous")), out=True)
     if a.kernel_loop:
-        kernel_loop(cols[0], a.kernel_loop, 50)
-        return
-    lines = [stats_line(a.stats, cols[0], a.map)] if a.stats else [ln for c in cols for ln in measure(c, a.rounds, a.steps)]
-    for ln in lines:
-        s = json.dumps(ln)
-        print(s)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(s + "\n")
+        kernel_loop(a.cols[0], a.kernel_loop, 50)
+    elif a.stats:
+        CL.emit(stats_line(a.stats, a.cols[0], a.map), a.out)
+    else:
+        CL.emit_each(a, lambda c: measure(c, a.rounds, a.steps))
 
 
 if __name__ == "__main__":

@@ -9,17 +9,15 @@ as the median of `rounds` repeats:
   - the link bound: one pinned hipMemcpy of the image's bytes from device memory, and the spec-sheet line (PCIe Gen5 x16, 63 GB/s).
 Column counts that do not fit into the host's available memory (three images and the download route's arrays) are skipped.
 python tests/tools/restart_cost.py [--cols 1000000,10000000] [--rounds 3] [--out profiles/r10_restart_cost.jsonl]"""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
 from elmkernels_amd import _lib as L  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
 
@@ -56,7 +54,7 @@ def timed(fn, rounds):
 
 
 def measure(cols, rounds, hip):
-    D, _ = bench.build_state(cols, 0, "A", 0x5EEDE1A0)
+    D, _ = CL.bench.build_state(cols, 0, "A", 0x5EEDE1A0)
     nbytes = D.restart_size()
     names = [k for k in D.fields if st.field_class(k) in (st.CLASS_PROGNOSTIC, st.CLASS_SURFACE)]
     field_bytes = sum(cols * D.fields[k][1] * np.dtype(D.fields[k][2]).itemsize for k in names)
@@ -89,28 +87,20 @@ def measure(cols, rounds, hip):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = CL.cli("1000000,10000000", 3, out=True)
     hip = hip_runtime()
-    lines = []
-    for cols in [int(c) for c in a.cols.split(",")]:
+
+    def one(cols):
         probe = st.ELMState(64)
         per_col = probe.restart_size() / 64
         probe.close()
         need = 3.2 * per_col * cols
         if need > 0.8 * mem_available():
-            lines.append(dict(tool="restart_cost", cols=cols, skipped=f"needs ~{need / 2**30:.1f} GiB of host memory, "
-                                                                        f"{mem_available() / 2**30:.1f} GiB available"))
-        else:
-            lines.append(measure(cols, a.rounds, hip))
-        print(json.dumps(lines[-1]), flush=True)
-    if a.out:
-        with open(a.out, "a") as f:
-            for ln in lines:
-                f.write(json.dumps(ln) + "\n")
+            return dict(tool="restart_cost", cols=cols, skipped=f"needs ~{need / 2**30:.1f} GiB of host memory, "
+                                                                f"{mem_available() / 2**30:.1f} GiB available")
+        return measure(cols, a.rounds, hip)
+
+    CL.emit_each(a, one)
 
 
 if __name__ == "__main__":

@@ -11,43 +11,27 @@ that spans latitudes and longitudes; interleaved over `rounds` repeats, the loop
 Wall-clock ms per model step, median over the rounds.  Records alternate between two host rows (the host holds 3 x ncols per
 stream instead of 25 x ncols); the physics does not care, the bytes moved are the same.
 python tests/tools/run_cost.py [--cols 4096,65536,1000000,10000000] [--rounds 3] [--out profiles/r07_run_cost.jsonl]"""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
+from costlib import FORC, PHEN  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
-from elmkernels_amd import synth  # noqa: E402
 
-DT = 1800.0
+DT = CL.DT
 NSTEPS, NREC, WINDOW = 48, 25, 24
-FORC, PHEN = st.SERIES_FORCING, st.SERIES_PHENOLOGY
 
 
 def schedule():
-    S = np.zeros(NSTEPS, st.RUN_STEP_DTYPE)
-    for s in range(NSTEPS):
-        ddoy = 13.875 + s * DT / 86400.0
-        S[s]["decday"], S[s]["doy"], S[s]["forc_slot"] = ddoy + 1.0, int(ddoy), s // 2
-        w2 = np.clip((s % 2) * 0.5 + 0.03 * np.arange(8), 0.0, 1.0)
-        S[s]["forc_wt2"], S[s]["forc_wt1"] = w2, 1.0 - w2
-        S[s]["month1"], S[s]["month2"] = (11, 0) if s < NSTEPS // 2 else (0, 1)
-        S[s]["month_wt1"] = 0.4
-        S[s]["month_wt2"] = 0.6
-    return S
+    """Hourly records from mid-January, the month bracket moving at half time."""
+    return CL.evolving_schedule(NSTEPS, 13.875, 2, [(11, 0)] * (NSTEPS // 2) + [(0, 1)] * (NSTEPS // 2))
 
 
 def setup(cols):
-    D, _ = bench.build_state(cols, 0, "B", 0x5EEDE1A0)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
-    lat, lon = synth.global_grid(cols)
-    D.set_column_geography(lat, lon)
+    D = CL.base_context(cols, "B", geography=CL.synth.global_grid(cols))
     # host rows r0, r1, r0 per stream: the record pair (t, t + 1) is rows [t % 2, t % 2 + 2), one contiguous [2][ncols] block
     rows = {}
     for k in FORC + PHEN:
@@ -89,11 +73,7 @@ def measure(cols, rounds):
     res = {"a_stepwise": [], "b_run": [], "c_two_runs": [], "c_window2_upload_alone": []}
 
     def t(fn):
-        D.sync()
-        t0 = time.perf_counter()
-        fn()
-        D.sync()
-        return (time.perf_counter() - t0) * 1e3
+        return CL.wall_ms(D, fn, sync_after=True)
 
     def b():
         D.run(DT, steps)
@@ -123,25 +103,15 @@ def measure(cols, rounds):
             res["b_run"].append(ms_b / NSTEPS)
             res["c_two_runs"].append(ms_c / NSTEPS)
             res["c_window2_upload_alone"].append(ms_u)
-    med = {k: float(np.median(v)) for k, v in res.items()}
+    med = CL.medians(res)
     D.close()
     return {"columns": cols, "tier": "B", "steps": NSTEPS, "records": NREC, "rounds": rounds, "unit": "ms per step (wall clock)",
             "median": med, "all": res, "b_over_a": med["b_run"] / med["a_stepwise"], "c_over_b": med["c_two_runs"] / med["b_run"]}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="4096,65536,1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
-        r = measure(c, a.rounds)
-        line = json.dumps(r)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+    a = CL.cli("4096,65536,1000000,10000000", 3, out=True)
+    CL.emit_each(a, lambda c: measure(c, a.rounds))
 
 
 if __name__ == "__main__":

@@ -6,37 +6,25 @@ to round (an interleaved A/B).  Wall-clock ms per model step, median over the ro
 rows of profiles/r07_run_cost.jsonl ("b_run", the same step over hourly records).
 python tests/tools/shortwave_cost.py [--cols 1000000,10000000] [--rounds 5] [--out profiles/r11_shortwave_cost.jsonl]
 python tests/tools/shortwave_cost.py --only coszen --cols 1000000 --rounds 1     (one mode, for a kernel trace)"""
-import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
-sys.path.insert(0, ROOT)
-import bench  # noqa: E402
-from elmkernels_amd import state as st  # noqa: E402
-from elmkernels_amd import synth  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import costlib as CL  # noqa: E402
+from costlib import ROOT  # noqa: E402
 
-DT, FORC_DT = 1800.0, 3 * 3600.0
+DT, FORC_DT = CL.DT, 3 * 3600.0
 NSTEPS = 48
 SPR = int(FORC_DT // DT)
 NREC = NSTEPS // SPR + 1
 DAY0 = 171.0
-FORC, PHEN = st.SERIES_FORCING, st.SERIES_PHENOLOGY
 
 
 def schedule():
-    S = np.zeros(NSTEPS, st.RUN_STEP_DTYPE)
-    for s in range(NSTEPS):
-        ddoy = DAY0 + s * DT / 86400.0
-        S[s]["decday"], S[s]["doy"], S[s]["forc_slot"] = ddoy + 1.0, int(ddoy), s // SPR
-        w2 = np.clip(((s % SPR) / SPR) + 0.03 * np.arange(8), 0.0, 1.0)
-        S[s]["forc_wt2"], S[s]["forc_wt1"] = w2, 1.0 - w2
-        S[s]["month1"], S[s]["month2"], S[s]["month_wt1"], S[s]["month_wt2"] = 5, 6, 0.4, 0.6
-    return S
+    return CL.evolving_schedule(NSTEPS, DAY0, SPR, (5, 6))
 
 
 def rec_times():
@@ -44,20 +32,7 @@ def rec_times():
 
 
 def setup(cols):
-    D, _ = bench.build_state(cols, 0, "B", 0x5EEDE1A0)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    D.set_graph(True)
-    lat, lon = synth.global_grid(cols)
-    D.set_column_geography(lat, lon)
-    D.run_reserve(NREC, NSTEPS)
-    for k in FORC:
-        a = D.download(k, layout=st.LAYOUT_SOA)
-        for r in range(NREC):
-            D.series_upload(k, r, a[r % 2])
-    for k in PHEN:
-        a = D.download(k, layout=st.LAYOUT_SOA)
-        D.series_upload(k, 0, np.stack([a[m % 2] for m in range(12)]))
-    return D
+    return CL.run_context(cols, "B", geography_seed=None, slots=NREC, max_steps=NSTEPS, records=NREC)
 
 
 def set_mode(D, mode):
@@ -82,22 +57,18 @@ def measure(cols, rounds, modes):
     steps = schedule()
     res = {m: [] for m in modes}
 
-    def timed():
-        D.sync()
-        t0 = time.perf_counter()
+    def run():
         D.run(DT, steps)
         D.run_diagnostics()
-        return (time.perf_counter() - t0) * 1e3 / NSTEPS
 
     for r in range(rounds):
-        order = modes if r % 2 == 0 else modes[::-1]
-        for m in order:
+        for m in CL.interleave(r, modes):
             set_mode(D, m)
             D.run(DT, steps[:1])  # untimed: the capture of the mode's run step
             D.run_diagnostics()
-            res[m].append(timed())
+            res[m].append(CL.wall_ms(D, run) / NSTEPS)
     D.close()
-    med = {m: float(np.median(v)) for m, v in res.items()}
+    med = CL.medians(res)
     out = {"columns": cols, "tier": "B", "steps": NSTEPS, "records": NREC, "forc_dt": FORC_DT, "rounds": rounds,
            "unit": "ms per step (wall clock)", "median": med, "all": res}
     if "coszen" in med and "reference" in med:
@@ -111,19 +82,9 @@ def measure(cols, rounds, modes):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--only", choices=["reference", "coszen"], default=None)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = CL.cli("1000000,10000000", 5, (CL.arg("--only", choices=["reference", "coszen"], default=None),), out=True)
     modes = [a.only] if a.only else ["reference", "coszen"]
-    for c in [int(x) for x in a.cols.split(",")]:
-        line = json.dumps(measure(c, a.rounds, modes))
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+    CL.emit_each(a, lambda c: measure(c, a.rounds, modes))
 
 
 if __name__ == "__main__":

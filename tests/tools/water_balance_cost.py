@@ -19,24 +19,20 @@ Prints one JSON line per column count (profiles/r18_water_balance_cost.jsonl), w
               library; with --parent2, a second build of the parent takes turns as well, and the spread between the two parents is the
               margin this build's step has to lie in
 python tests/tools/water_balance_cost.py [--cols 1000000,10000000] [--rounds 3] [--run-steps 6] [--ab LIB | --parent LIB [--parent2 LIB2]]"""
-import argparse
-import json
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+import costlib as CL  # noqa: E402
 import hydrology_cost as HC  # noqa: E402
-from elmkernels_amd import _lib as L  # noqa: E402
 from elmkernels_amd import hydrology as hy  # noqa: E402
 from elmkernels_amd import state as st  # noqa: E402
 
-DT = HC.DT
+DT = CL.DT
 BALANCE_BYTES = 616       # 67 x 8 read by k_water_balance, 6 x 8 written, 3 x 8 read by stage 1 of the reduction, 8 by the census
 CONSERVATION_BYTES = 636  # 63 x 8 + 4 read by k_conservation on a snow-free column, 8 x 8 written, 8 x 8 read by stage 1
 NEW = ("elmk_water_balance", "elmk_run_water_balance", "elmk_column_history_add_row", "elmk_gridded_history_add_row")
+CALLS = HC.CALLS
 
 
 def build(cols, lib_path=None, feature=True):
@@ -50,7 +46,7 @@ def measure(cols, rounds, run_steps):
     D = build(cols)
     t10 = D.accum_add("t_ref2m", "runmean", 480, "t10")
     D.accum_init(t10)
-    steps = HC.schedule(run_steps)
+    steps = CL.schedule(run_steps)
     D.water_balance_begin()
     alone = {"balance": lambda: D.water_balance(DT, read=False), "balance+sync": lambda: D.water_balance(DT),
              "conservation": lambda: st.kokkos_evaluate_conservation(D, DT), "begin": D.water_balance_begin, "t10": D.accum_update}
@@ -58,21 +54,19 @@ def measure(cols, rounds, run_steps):
             "run+hyd+wb+4": st.RUN_HYDROLOGY | st.RUN_WATER_BALANCE | st.RUN_HISTORY}
     res = {m: [] for m in list(alone) + list(runs)}
     for r in range(rounds):
-        keys = list(alone)
-        for key in (keys if r % 2 == 0 else keys[::-1]):
-            res[key].append(HC.back_to_back(D, alone[key]))
-        keys = list(runs)
-        for key in (keys if r % 2 == 0 else keys[::-1]):
+        for key in CL.interleave(r, alone):
+            res[key].append(CL.back_to_back(D, alone[key], CALLS))
+        for key in CL.interleave(r, runs):
             if key == "run+hyd+wb+4":
                 for fam, which in (("water_balance", hy.WB_QRUNOFF), ("water_balance", hy.WB_ENDWB), ("hydrology", hy.ZWT), ("hydrology", hy.QFLX_DRAIN)):
                     D.history_add_row(0, fam, which, "avg")
             D.soil_hydrology_init()
-            res[key].append(HC.run_ms(D, steps, runs[key]))
+            res[key].append(CL.run_ms(D, steps, runs[key]))
             D.history_clear()
-    med = {k: float(np.median(v)) for k, v in res.items()}
+    med = CL.medians(res)
     D.close()
     return {"columns": cols, "rounds": rounds, "run_steps": run_steps, "ms_median": med, "ms_all": res,
-            "spread": {k: HC.spread(v) for k, v in res.items()}, "balance_bytes": BALANCE_BYTES * cols, "conservation_bytes": CONSERVATION_BYTES * cols,
+            "spread": CL.spreads(res), "balance_bytes": BALANCE_BYTES * cols, "conservation_bytes": CONSERVATION_BYTES * cols,
             "balance_TBps": BALANCE_BYTES * cols / (med["balance"] * 1e-3) / 1e12,
             "bytes_ratio": BALANCE_BYTES / CONSERVATION_BYTES, "time_ratio_synced": med["balance+sync"] / med["conservation"],
             "time_ratio_launches": med["balance"] / med["conservation"], "begin_over_t10": med["begin"] / med["t10"],
@@ -82,59 +76,40 @@ def measure(cols, rounds, run_steps):
 
 def store_ab(cols, rounds, lib_nt):
     """The stage alone on two contexts in one process, plain stores (this build) and nontemporal stores (lib_nt), taking turns."""
-    L.load(lib_nt)
-    pair = (("plain", build(cols)), ("nontemporal", build(cols, lib_path=lib_nt)))
-    res = {k: [] for k, _ in pair}
-    for _, D in pair:
-        D.water_balance_begin()
-    for r in range(rounds):
-        for key, D in (pair if r % 2 == 0 else pair[::-1]):
-            res[key].append(HC.back_to_back(D, lambda D=D: D.water_balance(DT, read=False)))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    for _, D in pair:
-        D.close()
-    return {"columns": cols, "rounds": rounds, "ab": os.path.basename(lib_nt), "ms_all": res, "ms_median": med,
-            "spread": {k: HC.spread(v) for k, v in res.items()}, "nontemporal_over_plain": med["nontemporal"] / med["plain"]}
+    def begin(ctx):
+        for D in ctx.values():
+            D.water_balance_begin()
+
+    c = CL.compare_libraries(cols, rounds, [("plain", None), ("nontemporal", lib_nt)], lambda n, p: build(n, lib_path=p),
+                             lambda D: CL.back_to_back(D, lambda: D.water_balance(DT, read=False), CALLS), baseline="plain", prepare=begin)
+    return {"columns": cols, "rounds": rounds, "ab": os.path.basename(lib_nt), "ms_all": c["all"], "ms_median": c["median"],
+            "spread": c["spread"], "nontemporal_over_plain": c["nontemporal_over_plain"]}
 
 
 def parent(cols, rounds, run_steps, lib_parent, lib_parent2):
     """A build of the parent commit has none of the new entry points: no context enables a feature, all run the unflagged step."""
     libs = [("this", None), ("parent", lib_parent)] + ([("parent2", lib_parent2)] if lib_parent2 else [])
-    for _, p in libs[1:]:
-        L.load(p, optional=NEW + ("elmk_soil_hydrology", "elmk_active_layer"))
-    ctx = [(k, HC.build(cols, lib_path=p, feature=False)) for k, p in libs]
-    steps = HC.schedule(run_steps)
-    res = {k: [] for k, _ in ctx}
-    for r in range(rounds):
-        for key, D in (ctx if r % 2 == 0 else ctx[::-1]):
-            res[key].append(HC.run_ms(D, steps, 0))
-    med = {k: float(np.median(v)) for k, v in res.items()}
-    for _, D in ctx:
-        D.close()
+    steps = CL.schedule(run_steps)
+    c = CL.compare_libraries(cols, rounds, libs, lambda n, p: HC.build(n, lib_path=p, feature=False), lambda D: CL.run_ms(D, steps, 0),
+                             optional=NEW + ("elmk_soil_hydrology", "elmk_active_layer"), baseline="parent")
     out = {"columns": cols, "rounds": rounds, "run_steps": run_steps, "libraries": {k: os.path.basename(p) if p else "this build" for k, p in libs},
-           "run_ms_all": res, "run_ms_median": med, "spread": {k: HC.spread(v) for k, v in res.items()}, "this_over_parent": med["this"] / med["parent"]}
+           "run_ms_all": c["all"], "run_ms_median": c["median"], "spread": c["spread"], "this_over_parent": c["this_over_parent"]}
     if lib_parent2:
-        out["parent2_over_parent"] = med["parent2"] / med["parent"]
+        out["parent2_over_parent"] = c["parent2_over_parent"]
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cols", default="1000000,10000000")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--run-steps", type=int, default=6)
-    ap.add_argument("--ab", default=None)
-    ap.add_argument("--parent", default=None)
-    ap.add_argument("--parent2", default=None)
-    a = ap.parse_args()
-    for c in [int(x) for x in a.cols.split(",")]:
+    a = CL.cli("1000000,10000000", 3, (CL.RUN_STEPS, CL.AB, CL.PARENT, CL.PARENT2))
+
+    def one(c):
         if a.ab:
-            r = store_ab(c, a.rounds, a.ab)
-        elif a.parent:
-            r = parent(c, a.rounds, a.run_steps, a.parent, a.parent2)
-        else:
-            r = measure(c, a.rounds, a.run_steps)
-        print(json.dumps(r), flush=True)
+            return store_ab(c, a.rounds, a.ab)
+        if a.parent:
+            return parent(c, a.rounds, a.run_steps, a.parent, a.parent2)
+        return measure(c, a.rounds, a.run_steps)
+
+    CL.emit_each(a, one)
 
 
 if __name__ == "__main__":
