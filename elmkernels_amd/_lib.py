@@ -142,6 +142,15 @@ SIGNATURES = {
     "elmk_irrigation": (C.c_int, [_P, C.c_double, C.c_int]),
     "elmk_irrigation_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
     "elmk_irrigation_clear": (C.c_int, [_P]),
+    "elmk_routing_enable": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_double, C.c_int]),
+    "elmk_routing_init": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "elmk_routing": (C.c_int, [_P, C.c_double]),
+    "elmk_routing_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_routing_count": (C.c_int, [_P, _P]),
+    "elmk_routing_reset_mean": (C.c_int, [_P]),
+    "elmk_routing_set_withdrawal": (C.c_int, [_P, C.c_int]),
+    "elmk_routing_budget": (C.c_int, [_P, _P]),
+    "elmk_routing_clear": (C.c_int, [_P]),
     "elmk_column_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_gridded_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
 }

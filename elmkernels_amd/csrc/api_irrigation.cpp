@@ -79,6 +79,8 @@ int elmk_irrigation_read(elmk_ctx* ctx, int w, double* host, int64_t col0, int64
 
 int elmk_irrigation_clear(elmk_ctx* ctx)
 {
+  if (ctx && ctx->irr_rows)
+    if (int rc = route_holds(ctx, "elmk_irrigation_clear", true)) return rc;  // (the withdrawal reads QFLX_IRRIG)
   const int rc = rows_clear(ctx, IRR, "elmk_irrigation_clear");
   if (rc == ELMK_OK && !ctx->irr_rows) ctx->irr_sched = nullptr;
   return rc;

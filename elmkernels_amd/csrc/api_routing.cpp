@@ -1,0 +1,191 @@
+// api_routing.cpp - runoff routing (k_routing.hip; include/elmk.h "runoff routing"): the cell rows VOLR, QIN, QOUT, QOUT_SUM over the
+// output grid's cells, the network's parameter rows and upstream map and the budget's reduction scratch, in one allocation held
+// exactly while the feature is enabled.
+#include "elmk_ctx.h"
+
+namespace {
+// ELMK_ROUTE_* -> the row of the allocation (the budget's three rows lie first: elmk_kernels.h)
+constexpr int ROUTE_ROW_OF[4] = {ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT, ROUTE_QOUT_SUM};
+static_assert(ELMK_ROUTE_VOLR == 0 && ELMK_ROUTE_QIN == 1 && ELMK_ROUTE_QOUT == 2 && ELMK_ROUTE_QOUT_SUM == 3, "four rows");
+
+RouteArgs route_args(const elmk_ctx* ctx)
+{
+  const elmk_ctx::Routing& T = ctx->route;
+  return RouteArgs{T.ncells, T.cld, T.npad, T.nsub, T.rows, T.kout, T.area, T.up};
+}
+
+int route_enter(elmk_ctx* ctx, const char* who)
+{
+  if (int rc = enter(ctx)) return rc;
+  return ctx->route.mem ? ELMK_OK : invalid(ctx, (std::string(who) + ": not enabled (elmk_routing_enable)").c_str());
+}
+}  // namespace
+
+namespace elmk {
+void route_launch(elmk_ctx* ctx, double dt)
+{
+  const elmk_ctx::Routing& T = ctx->route;
+  const CsrMap& M = ctx->ogrid.map;
+  const size_t ld = (size_t)ctx->ld;
+  launch_routing(route_args(ctx), OGridMap{M.ptr, M.col, M.w, M.nrows, 0.0}, ctx->wb_rows + (size_t)ELMK_WB_QRUNOFF * ld,
+                 T.withdraw ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * ld : nullptr, dt, ctx->stream);
+}
+
+int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal)
+{
+  if (!ctx->route.mem || (with_withdrawal && !ctx->route.withdraw)) return ELMK_OK;
+  return invalid(ctx, (std::string(who) + ": runoff routing is enabled" + (with_withdrawal ? " with the withdrawal on" : "") +
+                       " (elmk_routing_clear first)").c_str());
+}
+}  // namespace elmk
+
+extern "C" {
+
+int elmk_routing_enable(elmk_ctx* ctx, int64_t ncells, const int32_t* down, const double* ddist, const double* area, double effvel, int nsub)
+{
+  const char* who = "elmk_routing_enable";
+  if (int rc = enter(ctx)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  if (!ctx->ogrid.mem) return invalid(ctx, "elmk_routing_enable: no output grid (elmk_set_output_grid)");
+  if (ncells != ctx->ogrid.map.nrows) return invalid(ctx, "elmk_routing_enable: ncells differs from the output grid's");
+  if (!ctx->wb_rows) return invalid(ctx, "elmk_routing_enable: the water balance is not enabled (elmk_water_balance_enable)");
+  if (T.mem) return invalid(ctx, "elmk_routing_enable: already enabled");
+  if (!(std::isfinite(effvel) && effvel > 0.0)) return invalid(ctx, "elmk_routing_enable: effvel not finite and > 0");
+  if (nsub < 1 || nsub > 64) return invalid(ctx, "elmk_routing_enable: nsub outside 1 .. 64");
+  const int64_t cld = (ncells + 63) / 64 * 64;
+  int nup = 0;
+  std::vector<int32_t> up;
+  // (every gather of k_routing_step stays inside a cell row because of this check)
+  if (int rc = invalid_map(ctx, who, route_check(ncells, down, ddist, area, cld, &nup, &up))) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the stages of its flags' moment)
+  const int npad = ell_npad(nup);
+  T = elmk_ctx::Routing{};
+  if (hip_fail(ctx, carve(T.mem, [&](Carve& L) {
+                 L.take(T.rows, (size_t)ROUTE_NROWS * cld * sizeof(double));
+                 L.take(T.kout, (size_t)cld * sizeof(double));
+                 L.take(T.area, (size_t)cld * sizeof(double));
+                 L.take(T.up, (size_t)npad * cld * sizeof(int32_t));
+                 L.take(T.down, (size_t)cld * sizeof(int32_t));
+                 L.take(T.part, (size_t)3 * ELMK_CONS_NPART * 3 * sizeof(double));
+                 L.take(T.out, 256);
+               }), "hipMalloc(runoff routing)")) {
+    T = elmk_ctx::Routing{};
+    return ELMK_E_NOMEM;
+  }
+  std::vector<double> kout((size_t)ncells);
+  for (int64_t c = 0; c < ncells; c++) kout[(size_t)c] = effvel / ddist[c];
+  const size_t n = (size_t)ncells;
+  // everything zero, the padding cells of down -1, then the network
+  if (hip_fail(ctx, hipMemsetAsync(T.mem, 0, T.mem.bytes(), ctx->stream), "hipMemset(runoff routing)") ||
+      hip_fail(ctx, hipMemsetAsync(T.down, 0xFF, (size_t)cld * sizeof(int32_t), ctx->stream), "hipMemset(runoff routing down)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.kout, kout.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(runoff routing KOUT)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.area, area, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(runoff routing area)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.up, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(runoff routing up)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.down, down, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(runoff routing down)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    T = elmk_ctx::Routing{};
+    return ELMK_E_HIP;
+  }
+  T.ncells = ncells;
+  T.cld = cld;
+  T.npad = npad;
+  T.nsub = nsub;
+  return ELMK_OK;
+}
+
+int elmk_routing_init(elmk_ctx* ctx, const double* volr, const double* qout_sum, int64_t ncalls)
+{
+  const char* who = "elmk_routing_init";
+  if (int rc = route_enter(ctx, who)) return rc;
+  if (ncalls < 0) return invalid(ctx, "elmk_routing_init: ncalls is negative");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  const size_t cld = (size_t)T.cld, n = (size_t)T.ncells;
+  HIPCHK(hipMemsetAsync(T.rows, 0, (size_t)ROUTE_NROWS * cld * sizeof(double), ctx->stream));
+  if (volr) HIPCHK(hipMemcpyAsync(T.rows + ROUTE_VOLR * cld, volr, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (qout_sum) HIPCHK(hipMemcpyAsync(T.rows + ROUTE_QOUT_SUM * cld, qout_sum, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = synced(ctx)) return rc;
+  T.ncalls = ncalls;
+  return ELMK_OK;
+}
+
+int elmk_routing(elmk_ctx* ctx, double dt)
+{
+  if (int rc = route_enter(ctx, "elmk_routing")) return rc;
+  if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_routing: dt must be finite and positive");
+  route_launch(ctx, dt);
+  ctx->route.ncalls++;
+  return launched(ctx);
+}
+
+int elmk_routing_read(elmk_ctx* ctx, int which, double* host, int64_t cell0, int64_t n)
+{
+  const char* who = "elmk_routing_read";
+  if (int rc = route_enter(ctx, who)) return rc;
+  if (which < 0 || which > ELMK_ROUTE_QOUT_SUM) return invalid(ctx, "elmk_routing_read: unknown row");
+  const elmk_ctx::Routing& T = ctx->route;
+  if (int rc = check_range(ctx, who, host, cell0, n, T.ncells, "cell")) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (n > 0)
+    HIPCHK(hipMemcpyAsync(host, T.rows + (size_t)ROUTE_ROW_OF[which] * (size_t)T.cld + (size_t)cell0, (size_t)n * 8, hipMemcpyDeviceToHost,
+                          ctx->stream));
+  return synced(ctx);
+}
+
+int elmk_routing_count(elmk_ctx* ctx, int64_t* ncalls)
+{
+  if (int rc = route_enter(ctx, "elmk_routing_count")) return rc;
+  if (!ncalls) return invalid(ctx, "elmk_routing_count: null argument");
+  *ncalls = ctx->route.ncalls;
+  return ELMK_OK;
+}
+
+int elmk_routing_reset_mean(elmk_ctx* ctx)
+{
+  if (int rc = route_enter(ctx, "elmk_routing_reset_mean")) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  HIPCHK(hipMemsetAsync(T.rows + ROUTE_QOUT_SUM * (size_t)T.cld, 0, (size_t)T.cld * sizeof(double), ctx->stream));
+  T.ncalls = 0;
+  return ELMK_OK;
+}
+
+int elmk_routing_set_withdrawal(elmk_ctx* ctx, int on)
+{
+  const char* who = "elmk_routing_set_withdrawal";
+  if (int rc = route_enter(ctx, who)) return rc;
+  if (on && !ctx->irr_rows) return invalid(ctx, "elmk_routing_set_withdrawal: the irrigation is not enabled (elmk_irrigation_enable)");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  ctx->route.withdraw = on != 0;  // (the captured run step is keyed by it)
+  return ELMK_OK;
+}
+
+int elmk_routing_budget(elmk_ctx* ctx, double* sums)
+{
+  const char* who = "elmk_routing_budget";
+  if (int rc = route_enter(ctx, who)) return rc;
+  if (!sums) return invalid(ctx, "elmk_routing_budget: null argument");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  const elmk_ctx::Routing& T = ctx->route;
+  launch_routing_outlets(route_args(ctx), T.down, ctx->stream);
+  launch_min_max_sum(T.rows, T.cld, T.ncells, 3, T.part, T.out, ctx->stream);
+  HIPCHK(hipGetLastError());
+  double mms[9];
+  HIPCHK(hipMemcpyAsync(mms, T.out, sizeof mms, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 3; k++) sums[k] = mms[3 * k + 2];
+  return ELMK_OK;
+}
+
+int elmk_routing_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_routing_clear")) return rc;
+  if (!ctx->route.mem) return ELMK_OK;
+  if (int rc = quiesce(ctx, false)) return rc;
+  ctx->route = elmk_ctx::Routing{};
+  return ELMK_OK;
+}
+
+}  // extern "C"

@@ -270,6 +270,7 @@ int elmk_soil_hydrology_clear(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, who)) return rc;
   for (const Rows* R : {&HYD, &HYDF, &WB})  // nothing changes unless all three may go
     if (int rc = rows_held(ctx, *R, who)) return rc;
+  if (int rc = route_holds(ctx, who)) return rc;  // (the routing reads the water balance's QRUNOFF)
   if (int rc = elmk_water_balance_clear(ctx)) return rc;
   if (int rc = rows_clear(ctx, HYDF, who)) return rc;
   const int rc = rows_clear(ctx, HYD, who);
@@ -363,6 +364,8 @@ int elmk_water_balance_read(elmk_ctx* ctx, int w, double* host, int64_t col0, in
 
 int elmk_water_balance_clear(elmk_ctx* ctx)
 {
+  if (ctx && ctx->wb_rows)
+    if (int rc = route_holds(ctx, "elmk_water_balance_clear")) return rc;
   if (int rc = rows_clear(ctx, WB, "elmk_water_balance_clear")) return rc;
   if (!ctx->wb_rows) wb_release(ctx);  // (rows_clear has made the stream idle)
   return ELMK_OK;

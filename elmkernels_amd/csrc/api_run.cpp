@@ -78,6 +78,10 @@ void run_flag_reduce(elmk_ctx* ctx, double)
   const elmk_ctx::Run& R = ctx->run;
   launch_flag_reduce_run((const uint32_t*)ctx->fptr[ELMK_FIELD_err_flags], ctx->ncols, R.flag_or, R.flag_first, R.cursor, ctx->stream);
 }
+void run_routing(elmk_ctx* ctx, double dt)
+{
+  if (ctx->run.flags & ELMK_RUN_ROUTING) route_launch(ctx, dt);
+}
 void run_active_layer(elmk_ctx* ctx, double)
 {
   if (ctx->run.flags & ELMK_RUN_ALT) launch_active_layer_run(alt_args(ctx), ctx->run.table, ctx->run.cursor, ctx->stream);
@@ -114,12 +118,12 @@ bool all_finite(const double* a, int64_t n)
 // forcing, aerosol deposition (ELMK_RUN_AEROSOL: where the reference's hook sits, init_timestep_kokkos.cc:48-49), init_timestep,
 // the water balance's begin (ELMK_RUN_WATER_BALANCE), advance_physics' stages (one stage here: launch_advance, with the irrigation stage
 // in front of soil_temperature under ELMK_RUN_IRRIGATION), soil hydrology
-// (ELMK_RUN_HYDROLOGY), conservation -> ring row, flag summary -> ring row, water balance -> its ring rows, active layer thickness
-// (ELMK_RUN_ALT), accumulated fields, history, next row
+// (ELMK_RUN_HYDROLOGY), conservation -> ring row, flag summary -> ring row, water balance -> its ring rows, runoff routing
+// (ELMK_RUN_ROUTING), active layer thickness (ELMK_RUN_ALT), accumulated fields, history, next row
 constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},     {run_forcing, nullptr},        {run_aerosol, nullptr},
                               {run_init_timestep, nullptr},  {run_wb_begin, nullptr},      {launch_advance, nullptr},     {run_soil_hydrology, nullptr},
-                              {run_conservation, nullptr},   {run_flag_reduce, nullptr},   {run_water_balance, nullptr},  {run_active_layer, nullptr},
-                              {run_accum, nullptr},          {run_history, nullptr},       {run_next, nullptr}};
+                              {run_conservation, nullptr},   {run_flag_reduce, nullptr},   {run_water_balance, nullptr},  {run_routing, nullptr},
+                              {run_active_layer, nullptr},   {run_accum, nullptr},         {run_history, nullptr},        {run_next, nullptr}};
 }  // namespace
 
 namespace elmk {
@@ -244,7 +248,7 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   if (nsteps < 1 || nsteps > R.max_steps || !steps) return invalid(ctx, "elmk_run: nsteps outside 1 .. max_steps of elmk_run_reserve");
   if (!(dt > 0.0 && dt <= 1.0e9)) return invalid(ctx, "elmk_run: dt must be finite and positive");
   if (flags & ~(ELMK_RUN_QBOT_IS_RH | ELMK_RUN_HISTORY | ELMK_RUN_ACCUM | ELMK_RUN_AEROSOL | ELMK_RUN_ALT | ELMK_RUN_HYDROLOGY | ELMK_RUN_WATER_BALANCE |
-                ELMK_RUN_IRRIGATION))
+                ELMK_RUN_IRRIGATION | ELMK_RUN_ROUTING))
     return invalid(ctx, "elmk_run: unknown flags");
   if ((flags & ELMK_RUN_AEROSOL) && !ctx->aer.mem) return invalid(ctx, "elmk_run: ELMK_RUN_AEROSOL without an aerosol series (elmk_aerosol_reserve)");
   if ((flags & ELMK_RUN_ACCUM) && ctx->accum.empty()) return invalid(ctx, "elmk_run: ELMK_RUN_ACCUM without an accumulator entry (elmk_accum_add)");
@@ -262,6 +266,10 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
     return invalid(ctx, "elmk_run: ELMK_RUN_IRRIGATION without the irrigation enabled (elmk_irrigation_enable)");
   if ((flags & ELMK_RUN_IRRIGATION) && !(dt >= 1.0 && dt <= 86400.0 && dt == std::floor(dt)))
     return invalid(ctx, "elmk_run: ELMK_RUN_IRRIGATION needs dt to be a whole number of seconds in 1 .. 86400");
+  if ((flags & ELMK_RUN_ROUTING) && !ctx->route.mem)
+    return invalid(ctx, "elmk_run: ELMK_RUN_ROUTING without the runoff routing enabled (elmk_routing_enable)");
+  if ((flags & ELMK_RUN_ROUTING) && !(flags & ELMK_RUN_WATER_BALANCE))
+    return invalid(ctx, "elmk_run: ELMK_RUN_ROUTING without ELMK_RUN_WATER_BALANCE");
   const bool cz = ctx->sw.mode == ELMK_SW_COSZEN;
   int lo = R.slots, hi = -1;
   unsigned months = 0;
@@ -321,12 +329,13 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   R.last_buf = buf;
   R.last_nsteps = nsteps;
   ctx->wb_ran = (flags & ELMK_RUN_WATER_BALANCE) != 0;
+  if (flags & ELMK_RUN_ROUTING) ctx->route.ncalls += nsteps;  // (the calls are enqueued below)
   ctx->wb_ran_empty = ctx->wb_ran && (!hyd_land(ctx) || ctx->ncols <= 0);
   // what the captured step depends on: the stages of the flags, modes and land unit, and the tables of their versions' moment
   const StepKey key{flags, ds_topo(ctx), ds_topo(ctx) && ctx->ds.gmem, cz, (flags & ELMK_RUN_HYDROLOGY) && hyd_land(ctx),
                     (flags & ELMK_RUN_HYDROLOGY) && (bool)ctx->hydf_rows, ctx->hist_version,
                     ctx->accum_version, (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx),
-                    (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows};
+                    (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows, (flags & ELMK_RUN_ROUTING) && ctx->route.withdraw};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;

@@ -153,13 +153,18 @@ enum GraphId { GRAPH_TS7, GRAPH_FUSED, GRAPH_ADVANCE, GRAPH_RUN_STEP, GRAPH_N };
 // What the captured launches of a sequence depend on besides (dt, stream).  elmk_run's step: the run's flags, the downscaling and
 // shortwave modes, whether the soil hydrology stage is in the step (its flag is set and the land unit is soil or crop), whether that
 // stage takes the frost-table form, the history and accumulator tables' versions, whether the irrigation stage is in the step (its flag
-// is set and the land unit is soil or crop) and whether the water balance takes its term; the other sequences have none (StepKey{}).
+// is set and the land unit is soil or crop), whether the water balance takes its term and whether the routing stage takes the withdrawal;
+// the other sequences have none (StepKey{}).
 struct StepKey {
   int flags = 0;
   bool ds_topo = false, ds_groups = false, coszen = false, hyd_stage = false, hyd_frost = false;
   uint64_t hist_version = 0, accum_version = 0;
   bool irr_stage = false, wb_irrig = false;  // the irrigation stage is in the step; the water balance takes the irrigation's term
-  auto tie() const { return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig); }
+  bool route_withdraw = false;               // the routing stage is in the step (its flag) and subtracts the irrigation's withdrawal
+  auto tie() const
+  {
+    return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw);
+  }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
 
@@ -271,6 +276,23 @@ struct elmk_ctx {
   // [ld], held exactly while the feature is enabled
   DevBuf<double> irr_rows;
   int32_t* irr_sched = nullptr;
+  // runoff routing (elmk_routing_*): one allocation `mem` holds the rows [ROUTE_NROWS][cld], KOUT and area [cld], the upstream map
+  // [npad][cld], down [cld] and the budget reduction's partials [3][ELMK_CONS_NPART][3] and triples [3][3]; held exactly while the
+  // feature is enabled.  ncalls: the calls since the last elmk_routing_init / _reset_mean (QOUT_SUM's count)
+  struct Routing {
+    DevBuf<char> mem;
+    int64_t ncells = 0, cld = 0;
+    int npad = 0, nsub = 0;
+    bool withdraw = false;
+    int64_t ncalls = 0;
+    double* rows = nullptr;
+    double* kout = nullptr;
+    double* area = nullptr;
+    int32_t* up = nullptr;
+    int32_t* down = nullptr;
+    double* part = nullptr;
+    double* out = nullptr;
+  } route;
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
@@ -445,6 +467,10 @@ int rows_read(elmk_ctx* ctx, const Rows& R, const char* who, int which, double* 
 int rows_clear(elmk_ctx* ctx, const Rows& R, const char* who);
 constexpr int IRR_NROWS = 3;
 void irr_run_launch(elmk_ctx* ctx, double dt);  // the run step's irrigation stage (api_irrigation.cpp)
+void route_launch(elmk_ctx* ctx, double dt);    // one call of the runoff routing (api_routing.cpp)
+// "<who>: runoff routing is enabled (elmk_routing_clear first)" while it is - what the routing reads stays; with_withdrawal: only while
+// the withdrawal is on
+int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal = false);
 constexpr int ALT_NROWS = 3;  // api_rows.cpp
 ActiveLayerArgs alt_args(const elmk_ctx* ctx);
 bool hyd_land(const elmk_ctx* ctx);

@@ -279,6 +279,23 @@ void launch_water_balance(const DevState* S, int64_t n, int64_t ld, const double
                           double dt, double tol, double* part, double* out, double* ring, long long* census, const int32_t* cursor,
                           hipStream_t st, const double* qirr = nullptr);
 
+// runoff routing (k_routing.hip, elmk_routing_*): the feature's fp64 rows [ROUTE_NROWS][cld] over the output grid's cells, cld = ncells
+// rounded up to 64.  The first three rows are the ones launch_min_max_sum reduces for the budget; ROUTE_OUTLET (QOUT of the outlets,
+// +0.0 elsewhere) is written by launch_routing_outlets only, ROUTE_VOLR_B is the second storage buffer of the sub-steps.
+enum { ROUTE_VOLR = 0, ROUTE_QIN = 1, ROUTE_OUTLET = 2, ROUTE_QOUT = 3, ROUTE_QOUT_SUM = 4, ROUTE_VOLR_B = 5, ROUTE_NROWS = 6 };
+struct RouteArgs {
+  int64_t ncells, cld;
+  int npad, nsub;      // npad = ell_npad(largest in-degree): the rows of up
+  double* rows;
+  const double* kout;  // [cld]: effvel / ddist
+  const double* area;  // [cld]
+  const int32_t* up;   // [npad][cld]: the upstream cells of each cell in ascending order, -1 = none
+};
+// one call: R1 (QIN from the column row qrunoff through the output grid's map M; qirr not null: the withdrawal's row) as one launch,
+// then nsub sub-step launches; the storages end in row ROUTE_VOLR
+void launch_routing(const RouteArgs& A, const OGridMap& M, const double* qrunoff, const double* qirr, double dt, hipStream_t st);
+void launch_routing_outlets(const RouteArgs& A, const int32_t* down, hipStream_t st);
+
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element
 struct RstPiece {

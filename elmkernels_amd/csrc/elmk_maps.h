@@ -61,4 +61,54 @@ inline const char* csr_check(int64_t nrows, int64_t ncols, const int64_t* ptr, c
   return nonneg ? "weight not finite and >= 0" : "non-finite weight";
 }
 
+// River network (elmk_routing_enable; include/elmk.h "runoff routing"): every cell drains into one downstream cell down[c], or is an
+// outlet (-1).  ddist: metres to the downstream cell (> 0), area: square metres (>= 0).  Checks, in this order: the arguments; per cell
+// in index order the range of down, then a self-loop; the in-degree (at most ROUTE_MAXUP cells drain into one); cycles; ddist; area.
+// The cycle check follows every unvisited cell downstream and marks what it passes as on the path (1), then walks the same path again
+// and marks it done (2): a path that runs into a cell still marked 1 has closed on itself.  Every cell is marked once each way, so the
+// check is linear in ncells, and nothing recurses (a chain as long as the grid is an ordinary network).
+// For an accepted network *nup is the largest in-degree (0 .. 8) and up the upstream map as the device reads it: row p of
+// ell_npad(*nup) rows of ld >= ncells entries each holds, for cell c, the p-th cell u with down[u] == c in ascending u, else -1.
+constexpr int ROUTE_MAXUP = 8;
+inline const char* route_check(int64_t ncells, const int32_t* down, const double* ddist, const double* area, int64_t ld, int* nup,
+                               std::vector<int32_t>* up)
+{
+  if (ncells < 1 || ncells > INT32_MAX) return "ncells outside 1 .. 2^31-1";
+  if (!down || !ddist || !area) return "null argument";
+  for (int64_t c = 0; c < ncells; c++) {
+    if (down[c] < -1 || down[c] >= ncells) return "down outside [-1, ncells)";
+    if (down[c] == c) return "down equals its own index";
+  }
+  std::vector<char> deg((size_t)ncells, 0);
+  int most = 0;
+  for (int64_t c = 0; c < ncells; c++) {
+    if (down[c] < 0) continue;
+    char& d = deg[(size_t)down[c]];
+    if (d == ROUTE_MAXUP) return "more than 8 upstream cells drain into one cell";
+    d++;
+    if (d > most) most = d;
+  }
+  std::vector<char> mark((size_t)ncells, 0);
+  for (int64_t c = 0; c < ncells; c++) {
+    if (mark[(size_t)c]) continue;
+    int64_t j = c;
+    for (; j >= 0 && mark[(size_t)j] == 0; j = down[j]) mark[(size_t)j] = 1;
+    if (j >= 0 && mark[(size_t)j] == 1) return "the network has a cycle";
+    for (j = c; j >= 0 && mark[(size_t)j] == 1; j = down[j]) mark[(size_t)j] = 2;
+  }
+  for (int64_t c = 0; c < ncells; c++)
+    if (!(std::isfinite(ddist[c]) && ddist[c] > 0.0)) return "ddist not finite and > 0";
+  for (int64_t c = 0; c < ncells; c++)
+    if (!(std::isfinite(area[c]) && area[c] >= 0.0)) return "area not finite and >= 0";
+  if (nup) *nup = most;
+  if (up) {
+    if (ld < ncells) ld = ncells;
+    up->assign((size_t)ell_npad(most) * (size_t)ld, -1);
+    deg.assign((size_t)ncells, 0);
+    for (int64_t u = 0; u < ncells; u++)  // ascending u: each cell's slots fill in ascending order
+      if (down[u] >= 0) (*up)[(size_t)deg[(size_t)down[u]]++ * (size_t)ld + (size_t)down[u]] = (int32_t)u;
+  }
+  return nullptr;
+}
+
 }  // namespace elmk

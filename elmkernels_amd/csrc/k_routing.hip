@@ -1,0 +1,167 @@
+// k_routing.hip - runoff routing on the device (elmk_routing_*; include/elmk.h "runoff routing"): the linear-reservoir river transport
+// model of the CLM family (RTM) over the output grid's cells.  Every cell drains into one downstream cell; a call aggregates the water
+// balance's QRUNOFF row onto the cells (R1) and takes nsub explicit sub-steps of the storages (R2 - R5).  elmkernels_amd/routing.py:
+// call() restates the operation in numpy, and this file follows it statement by statement.  No contraction (the Makefile's
+// -ffp-contract=off), plain IEEE comparisons, `/` the correctly rounded fp64 division; a NaN is stored into a row as the canonical
+// quiet NaN.  Every row is fp64 in both builds, so both builds compile the same kernels.
+//
+// One thread per cell, 256-thread workgroups, no LDS, no atomics, no fences.  A sub-step reads the storages of its start from one
+// buffer and writes the new ones into the other, so no cell sees a neighbour's update: the order between sub-steps is the launch
+// boundary, and the two buffers are used in turn.  The chain starts in the buffer from which nsub sub-steps end in the VOLR row: for an
+// odd nsub the R1 launch copies VOLR into the second buffer first.  The upstream map is stored [npad][ld], so a wave's index loads
+// coalesce; the loop over its slots is unrolled over npad = ell_npad(largest in-degree), every slot's gather is issued whether the
+// slot holds a cell or not (an empty slot reads the cell's own storage and adds nothing), so the loads of a cell are all in flight
+// together.  The flow of an upstream cell is evaluated again from its storage rather than read from a row of flows: the same bits,
+// one row less to write and read.  A cell reads 8 (storage) + 8 (KOUT) + 8 (QIN) + 4 npad (map) + 16 per upstream cell and, past the
+// first sub-step, 8 (the flow sum), and writes 16.  The unit carries no nontemporal hint: none has been measured for it.
+#include "elmk_dev.h"
+#include "elmk_kernels.h"
+
+namespace elmk {
+
+namespace {
+__device__ __forceinline__ void route_st(gptr<double> p, double v)
+{
+  if (v != v) v = __builtin_nan("");
+  *p = v;
+}
+
+// R2: what a storage v releases per second at rate constant k; the cap v / dts keeps a cell from releasing more than it holds
+__device__ __forceinline__ double route_flow(double v, double k, double dts)
+{
+  if (!(v > 0.0)) return 0.0;
+  const double a = v * k, b = v / dts;
+  return a < b ? a : b;
+}
+}  // namespace
+
+// R1: QIN of every cell from the column rows through the output grid's CSR map, in the order of k_ogrid_aggregate's sums; a cell
+// without terms takes +0.0.  WITHDRAW: the irrigation's QFLX_IRRIG row is aggregated the same way and subtracted.  volr_b not null: the
+// storages are copied into the second buffer (an odd nsub starts there).
+template <bool WITHDRAW>
+__global__ __launch_bounds__(256) void k_routing_qin(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
+                                                     gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> area,
+                                                     gptr<double> qin, gptr<const double> volr, gptr<double> volr_b, int64_t ncells)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncells) return;
+  const int64_t p0 = ptr[c], p1 = ptr[c + 1];
+  double r = 0.0, i = 0.0;
+  for (int64_t p = p0; p < p1; p++) {
+    const int32_t k = col[p];
+    const double wp = w[p];
+    const double x = wp * qrunoff[k];
+    r = p == p0 ? x : r + x;
+    if constexpr (WITHDRAW) {
+      const double y = wp * qirr[k];
+      i = p == p0 ? y : i + y;
+    }
+  }
+  if constexpr (WITHDRAW) r = r - i;
+  route_st(qin + c, (r * 0.001) * area[c]);
+  if (volr_b) volr_b[c] = volr[c];
+}
+
+// R3 - R5: one sub-step.  FIRST: the flow sum starts at +0.0; otherwise it continues from the QOUT row.  LAST: QOUT takes the mean
+// over the sub-steps and QOUT_SUM adds it.
+template <int NPAD, bool FIRST, bool LAST>
+__global__ __launch_bounds__(256) void k_routing_step(gptr<const double> v_old, gptr<double> v_new, gptr<const double> kout,
+                                                      gptr<const int32_t> up, gptr<const double> qin, gptr<double> qout,
+                                                      gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts, double dnsub)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncells) return;
+  int32_t u[NPAD];
+#pragma unroll
+  for (int p = 0; p < NPAD; p++) u[p] = up[(int64_t)p * cld + c];
+  const double v = v_old[c], k = kout[c], q = qin[c];
+  double qacc = 0.0;
+  if constexpr (!FIRST) qacc = qout[c];
+  double vu[NPAD], ku[NPAD];
+#pragma unroll
+  for (int p = 0; p < NPAD; p++) {
+    const int64_t j = u[p] >= 0 ? (int64_t)u[p] : c;
+    vu[p] = v_old[j];
+    ku[p] = kout[j];
+  }
+  const double f = route_flow(v, k, dts);
+  double fin = 0.0;
+#pragma unroll
+  for (int p = 0; p < NPAD; p++) {
+    const double fu = route_flow(vu[p], ku[p], dts);
+    if (u[p] >= 0) fin = fin + fu;
+  }
+  route_st(v_new + c, v + ((fin - f) + q) * dts);
+  qacc = qacc + f;
+  if constexpr (LAST) {
+    const double mean = qacc / dnsub;
+    route_st(qout + c, mean);
+    route_st(qout_sum + c, qout_sum[c] + mean);
+  } else {
+    route_st(qout + c, qacc);
+  }
+}
+
+// R6's third row: QOUT of the outlets, +0.0 elsewhere
+__global__ __launch_bounds__(256) void k_routing_outlets(gptr<const int32_t> down, gptr<const double> qout, gptr<double> outlet,
+                                                         int64_t ncells)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncells) return;
+  outlet[c] = down[c] < 0 ? qout[c] : 0.0;
+}
+
+namespace {
+template <int NPAD, bool FIRST, bool LAST>
+void launch_step(const RouteArgs& A, const double* v_old, double* v_new, double dts, hipStream_t st)
+{
+  hipLaunchKernelGGL((k_routing_step<NPAD, FIRST, LAST>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
+                     (gptr<const double>)v_old, (gptr<double>)v_new, (gptr<const double>)A.kout, (gptr<const int32_t>)A.up,
+                     (gptr<const double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT * A.cld),
+                     (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts, (double)A.nsub);
+}
+template <int NPAD>
+void launch_step(const RouteArgs& A, const double* v_old, double* v_new, double dts, bool first, bool last, hipStream_t st)
+{
+  if (first && last) launch_step<NPAD, true, true>(A, v_old, v_new, dts, st);
+  else if (first) launch_step<NPAD, true, false>(A, v_old, v_new, dts, st);
+  else if (last) launch_step<NPAD, false, true>(A, v_old, v_new, dts, st);
+  else launch_step<NPAD, false, false>(A, v_old, v_new, dts, st);
+}
+}  // namespace
+
+void launch_routing(const RouteArgs& A, const OGridMap& M, const double* qrunoff, const double* qirr, double dt, hipStream_t st)
+{
+  if (A.ncells <= 0) return;
+  const dim3 grid((unsigned)((A.ncells + 255) / 256)), block(256);
+  double* const volr = A.rows + ROUTE_VOLR * A.cld;
+  double* const volr_b = A.rows + ROUTE_VOLR_B * A.cld;
+  const bool odd = (A.nsub & 1) != 0;
+  const auto qin = qirr ? k_routing_qin<true> : k_routing_qin<false>;
+  hipLaunchKernelGGL(qin, grid, block, 0, st, (gptr<const int64_t>)M.ptr, (gptr<const int32_t>)M.col, (gptr<const double>)M.w,
+                     (gptr<const double>)qrunoff, (gptr<const double>)qirr, (gptr<const double>)A.area,
+                     (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<const double>)volr, (gptr<double>)(odd ? volr_b : nullptr), A.ncells);
+  const double dts = dt / (double)A.nsub;  // R0
+  double *src = odd ? volr_b : volr, *dst = odd ? volr : volr_b;
+  for (int s = 0; s < A.nsub; s++) {
+    const bool first = s == 0, last = s == A.nsub - 1;
+    switch (A.npad) {
+      case 1: launch_step<1>(A, src, dst, dts, first, last, st); break;
+      case 2: launch_step<2>(A, src, dst, dts, first, last, st); break;
+      case 4: launch_step<4>(A, src, dst, dts, first, last, st); break;
+      default: launch_step<8>(A, src, dst, dts, first, last, st); break;
+    }
+    double* const t = src;
+    src = dst;
+    dst = t;
+  }
+}
+
+void launch_routing_outlets(const RouteArgs& A, const int32_t* down, hipStream_t st)
+{
+  if (A.ncells <= 0) return;
+  hipLaunchKernelGGL(k_routing_outlets, dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st, (gptr<const int32_t>)down,
+                     (gptr<const double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_OUTLET * A.cld), A.ncells);
+}
+
+}  // namespace elmk

@@ -31,6 +31,8 @@ RUN_WATER_BALANCE = 64  # every step closes the water budget (water_balance_enab
 RUN_IRRIGATION = 128  # every step applies and checks irrigation between the seven wrappers and soil_temperature (irrigation_enable)
 IRR_RATE, IRR_NLEFT, IRR_QFLX_IRRIG = range(3)  # elmk_irrigation_read (irrigation.RATE .. irrigation.QFLX_IRRIG)
 IRR_NROWS = 3
+RUN_ROUTING = 256  # every step routes the step's runoff after the water balance (routing_enable; needs RUN_WATER_BALANCE)
+ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT, ROUTE_QOUT_SUM = range(4)  # elmk_routing_read (routing.VOLR .. routing.QOUT_SUM)
 WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB .. hydrology.WB_TOTSOILICE
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
@@ -518,6 +520,63 @@ class ELMState:
     def irrigation_clear(self):
         """Free the rows and sched.  Refused while history entries over the rows exist."""
         self._chk(self.lib.elmk_irrigation_clear(self.ctx), "irrigation_clear")
+
+    # -- runoff routing (include/elmk.h: elmk_routing_enable ...; elmkernels_amd/routing.py restates the stage) ---------------------------
+    def routing_enable(self, down, ddist, area, effvel=0.35, nsub=1):
+        """Allocate the cell rows VOLR, QIN, QOUT, QOUT_SUM (fp64, zero-filled) over the output grid's cells and take the network: down
+        int32 [ncells] (-1 = an outlet), ddist [ncells] metres, area [ncells] square metres, effvel m/s, nsub sub-steps per call.  Needs
+        an output grid and the water balance.  Refused for a network that is out of range, has a self-loop, a cycle or more than 8 cells
+        draining into one, and while the stream is captured."""
+        d = np.ascontiguousarray(down, dtype=np.int32).reshape(-1)
+        dd = np.ascontiguousarray(ddist, dtype=np.float64).reshape(-1)
+        a = np.ascontiguousarray(area, dtype=np.float64).reshape(-1)
+        if not (d.size == dd.size == a.size):
+            raise ValueError("routing_enable: down, ddist and area must all be [ncells]")
+        self._chk(self.lib.elmk_routing_enable(self.ctx, int(d.size), _p(d), _p(dd), _p(a), float(effvel), int(nsub)), "routing_enable")
+        self.routing_ncells = int(d.size)
+
+    def routing_init(self, volr=None, qout_sum=None, ncalls=0):
+        """VOLR and QOUT_SUM from [ncells] each (None: zeros), QIN and QOUT zeros, the call count = ncalls: a restart file's values.
+        Synchronises."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (volr, qout_sum)]
+        for v in a:
+            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
+                raise ValueError(f"routing_init: {v.size} values for {self.routing_ncells} cells")
+        self._chk(self.lib.elmk_routing_init(self.ctx, *(None if v is None else _p(v) for v in a), int(ncalls)), "routing_init")
+
+    def routing(self, dt):
+        """One call: QIN from the water balance's QRUNOFF row, then nsub sub-steps.  After water_balance(dt); nsub + 1 launches,
+        stream-ordered, no sync."""
+        self._chk(self.lib.elmk_routing(self.ctx, float(dt)), "routing")
+
+    def routing_read(self, which, cell0=0, n=None):
+        """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
+        n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
+        out = np.empty(max(n, 0), dtype=np.float64)
+        self._chk(self.lib.elmk_routing_read(self.ctx, int(which), _p(out), int(cell0), n), "routing_read")
+        return out
+
+    def routing_count(self):
+        """The calls since the last routing_init / routing_reset_mean: routing_read(ROUTE_QOUT_SUM) / routing_count() is the mean."""
+        n = C.c_int64(0)
+        self._chk(self.lib.elmk_routing_count(self.ctx, C.byref(n)), "routing_count")
+        return int(n.value)
+
+    def routing_reset_mean(self):
+        self._chk(self.lib.elmk_routing_reset_mean(self.ctx), "routing_reset_mean")
+
+    def routing_set_withdrawal(self, on=True):
+        """on: every call takes the irrigation's applied water out of the cells' input (needs irrigation_enable)."""
+        self._chk(self.lib.elmk_routing_set_withdrawal(self.ctx, 1 if on else 0), "routing_set_withdrawal")
+
+    def routing_budget(self):
+        """float64 [3]: the sums of VOLR and QIN and the sum of QOUT over the outlets (routing.budget).  Synchronises."""
+        out = np.empty(3, dtype=np.float64)
+        self._chk(self.lib.elmk_routing_budget(self.ctx, _p(out)), "routing_budget")
+        return out
+
+    def routing_clear(self):
+        self._chk(self.lib.elmk_routing_clear(self.ctx), "routing_clear")
 
     # -- water balance (include/elmk.h: elmk_water_balance_enable ...; hydrology.water_balance_begin / _end restate the stage) -----
     def water_balance_enable(self, tol_mm):
@@ -1051,7 +1110,7 @@ class ELMInterface:
         return False
 
     def run(self, dt_seconds, steps, accumulate_history=False, qbot_is_rh=False, update_accum=False, update_aerosol=False,
-            update_active_layer=False, soil_hydrology=False, water_balance=False, irrigation=False):
+            update_active_layer=False, soil_hydrology=False, water_balance=False, irrigation=False, routing=False):
         """ELMInterface::advance for every row of steps (RUN_STEP_DTYPE) in one call (elmk_run; needs S.run_reserve and the series
         uploaded); self.conservation = the last step's triples, self.run_conservation = all of them.  update_accum: every step updates
         the accumulated fields registered on self.S (ELM's UpdateAccVars: after the physics, before the history).  update_aerosol: every
@@ -1059,13 +1118,15 @@ class ELMInterface:
         between the forcing and init_timestep.  update_active_layer: every step runs ELM's alt_calc after the physics (S.active_layer_enable),
         with the annual rollover on the steps that start at 00:00 of 1 January / 1 July.  water_balance: every step closes the water budget
         (S.water_balance_enable; with soil_hydrology); self.run_water_balance = S.run_water_balance() of the run.  irrigation: every step
-        applies and checks irrigation between the seven wrappers and soil_temperature (S.irrigation_enable; dt a whole number of seconds).  Raises after the run if a step raised a fatal flag, naming the first such step and column."""
+        applies and checks irrigation between the seven wrappers and soil_temperature (S.irrigation_enable; dt a whole number of seconds).  routing: every step
+        routes the step's runoff after the water balance (S.routing_enable; with water_balance).  Raises after the run if a step raised a fatal flag, naming the first such step and column."""
         S = self.S
         flags = (RUN_HISTORY if accumulate_history else 0) | (RUN_QBOT_IS_RH if qbot_is_rh else 0) | (RUN_ACCUM if update_accum else 0)
         flags |= (RUN_AEROSOL if update_aerosol else 0) | (RUN_ALT if update_active_layer else 0)
         flags |= RUN_HYDROLOGY if soil_hydrology else 0  # the soil hydrology stage after surface_fluxes (S.soil_hydrology_enable)
         flags |= RUN_WATER_BALANCE if water_balance else 0
         flags |= RUN_IRRIGATION if irrigation else 0
+        flags |= RUN_ROUTING if routing else 0
         S.run(dt_seconds, steps, flags)
         if water_balance:
             self.run_water_balance = S.run_water_balance()

@@ -305,6 +305,7 @@ int elmk_history_clear(elmk_ctx *ctx);
  *                          with ELMK_RUN_HYDROLOGY: elmk_soil_hydrology(dt) ("soil hydrology");
  *                          elmk_evaluate_conservation -> ring row s;
  *                          elmk_error_summary -> ring row s (flags sticky, as that call sees them after the step);
+ *                          with ELMK_RUN_ROUTING: elmk_routing(dt) after the step's water balance ("runoff routing");
  *                          with ELMK_RUN_ALT: elmk_active_layer_update(the step's rollover) ("active layer thickness");
  *                          with ELMK_RUN_ACCUM: elmk_accum_update ("accumulated fields");
  *                          with ELMK_RUN_HISTORY: elmk_history_accumulate.
@@ -947,8 +948,9 @@ int elmk_run_water_balance(elmk_ctx *ctx, double *min_max_sum /*[nsteps][3][3]*/
  * Graph on and off give the same bits.
  * Water balance: while the feature is enabled W4 of "water balance" takes ELM's BalanceCheck form,
  *   ERRH2O = ENDWB - BEGWB - (((forc_rain + forc_snow) + QFLX_IRRIG) - QRUNOFF - qflx_evap_tot - qflx_snwcp_ice) * dt.
- * Water withdrawal is not modelled: QRUNOFF stays the column's generated runoff, and a driver that takes the water from the river
- * subtracts its QIRRIG tape itself.
+ * Water withdrawal: QRUNOFF stays the column's generated runoff.  With the runoff routing enabled ("runoff routing" below)
+ * elmk_routing_set_withdrawal takes the applied water out of the channel storage of the column's cell; supply is not limited by that
+ * storage.  Without it a driver that takes the water from the river subtracts its QIRRIG tape itself.
  * History: ELMK_ROWS_IRRIGATION (which = ELMK_IRR_*) puts ELM's QIRRIG on a tape.  Restart: a context with the feature enabled saves a
  * version-5 image that carries RATE and NLEFT ("restart" below); sched is a parameter the loading context sets itself.
  * A context that never enables the feature runs the kernels, launch sequences and graphs it ran before, allocates nothing more and
@@ -960,6 +962,85 @@ int elmk_irrigation_init(elmk_ctx *ctx, const double *rate /*[ncols] or NULL*/, 
 int elmk_irrigation(elmk_ctx *ctx, double dt, int tod_seconds);
 int elmk_irrigation_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
 int elmk_irrigation_clear(elmk_ctx *ctx);
+
+/* ---- runoff routing --------------------------------------------------------------------------------
+ * The linear-reservoir river transport model the CLM family shipped as RTM, over the output grid's cells ("output grid"): every cell
+ * passes water to one downstream cell, the input is the water balance's QRUNOFF row aggregated onto the cells, and the result is the
+ * channel storage and the discharge of every cell.  Routing is a recurrence in time, so a driver that wants discharge would otherwise
+ * download the gridded runoff every step; this opt-in stage keeps it on the device.  k_routing.hip; elmkernels_amd/routing.py: call()
+ * is the same operation on the host.  A context routes the basins whose cells it holds completely; nothing here is collective.
+ *
+ * Conventions of "soil hydrology": no contraction, left-associated + - *, `/` the correctly rounded fp64 division, plain IEEE
+ * comparisons; every row is fp64 in both builds; a NaN stored into a row is the canonical quiet NaN.
+ *
+ * Network, given at enable time: ncells (the output grid's), down[ncells] (int32: the downstream cell, -1 = an outlet, ocean or
+ * interior sink), ddist[ncells] (metres to the downstream cell; for an outlet the length of its own reach), area[ncells] (square metres
+ * of land the cell's runoff stands for), effvel (the effective velocity in m/s, RTM's 0.35), nsub (sub-steps per call).  The host
+ * derives KOUT[c] = effvel / ddist[c] (one division) and the upstream map up[8][ncells]: the cells u with down[u] == c in ascending u,
+ * padded with -1; nup is the largest in-degree rounded up to 1, 2, 4 or 8 (as the forcing grid's npts).
+ *
+ * State and rows, each [ncells rounded up to 64] doubles: ELMK_ROUTE_VOLR (m3, the only prognostic row), ELMK_ROUTE_QIN (m3/s),
+ * ELMK_ROUTE_QOUT (m3/s: the mean over the call's sub-steps of the flow leaving the cell), ELMK_ROUTE_QOUT_SUM (the sum of QOUT over
+ * the calls since the last reset), and a host-side call count.
+ *
+ * One call elmk_routing(ctx, dt):
+ * R0. dts = dt / (double)nsub.
+ * R1. (once per call) r = the aggregate of the QRUNOFF row over the cell's terms, exactly the expression and order of "output grid":
+ *     w[p0] * x[col[p0]], then + w[p] * x[col[p]]; a cell without terms takes r = 0.0 (not fill).  With the withdrawal on, i = the same
+ *     aggregate of the irrigation's QFLX_IRRIG row and r = r - i.  QIN[c] = (r * 0.001) * area[c].
+ * R2. flow(v, k): if (v > 0.0) { a = v * k;  b = v / dts;  flow = (a < b) ? a : b; } else flow = 0.0.  A NaN, zero, negative-zero or
+ *     negative storage releases nothing; the cap b keeps a cell from releasing more than it holds when k * dts >= 1.
+ * R3. per sub-step and cell: f = flow(v_old[c], KOUT[c]);  fin = 0.0;  for p = 0 .. 7 ascending with u = up[p][c] >= 0:
+ *     fin = fin + flow(v_old[u], KOUT[u]).
+ * R4. v_new[c] = v_old[c] + ((fin - f) + QIN[c]) * dts.  Every cell reads the storages of the sub-step's start (the device keeps two
+ *     storage buffers and uses them in turn; the order between sub-steps is the launch boundary).
+ * R5. qacc starts at 0.0 and takes qacc + f every sub-step.  After the last: QOUT = qacc / (double)nsub;  VOLR = v;
+ *     QOUT_SUM = QOUT_SUM + QOUT.
+ * R6. (elmk_routing_budget) sums[0] = the sum of VOLR, sums[1] = the sum of QIN, sums[2] = the sum of QOUT over the outlets, a cell that
+ *     is no outlet contributing +0.0; each is the `sum` of elmk_evaluate_conservation's reduction over the cells (diagnostics.
+ *     reduce_min_max_sum), bit for bit, from the same reduction kernels.
+ * A call takes nsub + 1 launches (R1, then one per sub-step), each stream-ordered, host-free and capturable as one chain of nodes.
+ * Supply is not limited by storage: with the withdrawal on VOLR may go negative, and a negative storage releases nothing until the
+ * inflow has refilled it.
+ *
+ *   elmk_routing_enable     allocates the rows, zero-filled, KOUT, area and the maps (one owner, counted in elmk_device_bytes) and
+ *                           drops the captured run step.  ELMK_E_INVALID, nothing changed: no output grid; ncells other than the output
+ *                           grid's; the water balance not enabled; already enabled; effvel not finite and > 0; nsub outside 1 .. 64; a
+ *                           null array; a down outside [-1, ncells) or equal to its own index; more than 8 upstream cells draining into
+ *                           one cell; a cycle; a ddist that is not finite and > 0; an area that is not finite and >= 0; a stream being
+ *                           captured.
+ *   elmk_routing_init       VOLR and QOUT_SUM from host[ncells] each (NULL: zeros), QIN and QOUT zeros, the call count = ncalls >= 0: a
+ *                           restart file's values.  Synchronises.
+ *   elmk_routing            one call; stream-ordered and capturable, no host memory, no synchronisation; the call count advances by one.
+ *                           ELMK_E_INVALID, nothing enqueued: not enabled; dt not finite and positive.
+ *   elmk_routing_read       row `which` (ELMK_ROUTE_*) of cells [cell0, cell0 + n) as doubles; synchronises.
+ *   elmk_routing_count      the calls since the last elmk_routing_init / elmk_routing_reset_mean: QOUT_SUM / count is the mean discharge.
+ *   elmk_routing_reset_mean QOUT_SUM = zeros (stream-ordered), the count = 0.
+ *   elmk_routing_set_withdrawal  on != 0: R1 subtracts the irrigation's applied water; refused without the irrigation enabled.  Off
+ *                           (the default) gives the bits of a context that never called it.
+ *   elmk_routing_budget     R6; synchronises.
+ *   elmk_routing_clear      frees everything and drops the captured run step.
+ * While the feature is enabled what it reads stays: elmk_set_output_grid, elmk_clear_output_grid, elmk_water_balance_clear,
+ * elmk_soil_hydrology_clear and, with the withdrawal on, elmk_irrigation_clear are refused with ELMK_E_INVALID ("elmk_routing_clear
+ * first") and nothing changes.
+ * elmk_run with ELMK_RUN_ROUTING runs the call in every step with the run's dt, after W1 - W8 of the water balance and before the
+ * active layer update, the accumulated fields and the history; refused before anything is enqueued when the feature is not enabled or
+ * the flag comes without ELMK_RUN_WATER_BALANCE.  The call count advances by nsteps at enqueue.  Graph on and off give the same bits.
+ * Restart: the routing state lives on cells and is not part of the column image ("restart").  A driver saves VOLR, QOUT_SUM and the
+ * count with elmk_routing_read / elmk_routing_count and restores them with elmk_routing_init after elmk_routing_enable.
+ * A context that never enables the feature runs the kernels, launch sequences and graphs it ran before, allocates nothing more and
+ * saves the image it saved before. */
+enum { ELMK_ROUTE_VOLR = 0, ELMK_ROUTE_QIN = 1, ELMK_ROUTE_QOUT = 2, ELMK_ROUTE_QOUT_SUM = 3 };
+#define ELMK_RUN_ROUTING 256 /* the ninth flag bit of elmk_run: every step routes the step's runoff */
+int elmk_routing_enable(elmk_ctx *ctx, int64_t ncells, const int32_t *down, const double *ddist, const double *area, double effvel, int nsub);
+int elmk_routing_init(elmk_ctx *ctx, const double *volr /*[ncells] or NULL*/, const double *qout_sum /*[ncells] or NULL*/, int64_t ncalls);
+int elmk_routing(elmk_ctx *ctx, double dt);
+int elmk_routing_read(elmk_ctx *ctx, int which, double *host, int64_t cell0, int64_t n);
+int elmk_routing_count(elmk_ctx *ctx, int64_t *ncalls);
+int elmk_routing_reset_mean(elmk_ctx *ctx);
+int elmk_routing_set_withdrawal(elmk_ctx *ctx, int on);
+int elmk_routing_budget(elmk_ctx *ctx, double *sums /*[3]*/);
+int elmk_routing_clear(elmk_ctx *ctx);
 
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.

@@ -369,6 +369,31 @@ class ELMInterface {
     ok(n < 0 ? n : ELMK_OK);
     return n;
   }
+  /* Runoff routing (elmk.h "runoff routing"): the linear-reservoir river model over the output grid's cells.  routing_enable() takes the
+   * network (down[ncells], -1 = an outlet; ddist metres; area square metres) after set_output_grid and water_balance_enable;
+   * routing(dt) after water_balance(dt), or run(..., routing = true) in every step.  routing_read() fills [ncells] of row ELMK_ROUTE_*;
+   * routing_init() takes a restart's VOLR, QOUT_SUM ([ncells] each, nullptr: zeros) and call count; routing_budget() fills sums[3]. */
+  void routing_enable(int64_t ncells, const int32_t* down, const double* ddist, const double* area, double effvel = 0.35, int nsub = 1)
+  {
+    ok(elmk_routing_enable(ctx_, ncells, down, ddist, area, effvel, nsub));
+    routing_ncells_ = ncells;
+  }
+  void routing_init(const double* volr = nullptr, const double* qout_sum = nullptr, int64_t ncalls = 0)
+  {
+    ok(elmk_routing_init(ctx_, volr, qout_sum, ncalls));
+  }
+  void routing(double dt_seconds) { ok(elmk_routing(ctx_, dt_seconds)); }
+  void routing_read(int which, double* host) { ok(elmk_routing_read(ctx_, which, host, 0, host ? routing_ncells_ : 0)); }
+  int64_t routing_count()
+  {
+    int64_t n = 0;
+    ok(elmk_routing_count(ctx_, &n));
+    return n;
+  }
+  void routing_reset_mean() { ok(elmk_routing_reset_mean(ctx_)); }
+  void routing_set_withdrawal(bool on) { ok(elmk_routing_set_withdrawal(ctx_, on ? 1 : 0)); }
+  void routing_budget(double* sums) { ok(elmk_routing_budget(ctx_, sums)); }
+  void routing_clear() { ok(elmk_routing_clear(ctx_)); }
   /* History entries over one fp64 row of a feature (elmk.h "feature rows on history tapes"): family ELMK_ROWS_*, which the family's
    * row number; as history_add / gridded_history_add otherwise, one level.  While such an entry exists the family's clear is refused. */
   int history_add_row(int tape, int family, int which, int op)
@@ -416,13 +441,13 @@ class ELMInterface {
   }
   void enqueue_run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
                    bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false, bool soil_hydrology = false,
-                   bool water_balance = false, bool irrigation = false)
+                   bool water_balance = false, bool irrigation = false, bool routing = false)
   {
     ok(elmk_run(ctx_, dt_seconds, steps.data(), (int)steps.size(),
                 (accumulate_history ? ELMK_RUN_HISTORY : 0) | (qbot_rh ? ELMK_RUN_QBOT_IS_RH : 0) | (update_accum ? ELMK_RUN_ACCUM : 0) |
                     (update_aerosol ? ELMK_RUN_AEROSOL : 0) | (update_active_layer ? ELMK_RUN_ALT : 0) |
                     (soil_hydrology ? ELMK_RUN_HYDROLOGY : 0) | (water_balance ? ELMK_RUN_WATER_BALANCE : 0) |
-                    (irrigation ? ELMK_RUN_IRRIGATION : 0)));
+                    (irrigation ? ELMK_RUN_IRRIGATION : 0) | (routing ? ELMK_RUN_ROUTING : 0)));
   }
   bool finish_run()
   {
@@ -445,10 +470,10 @@ class ELMInterface {
   }
   bool run(double dt_seconds, const std::vector<elmk_run_step>& steps, bool accumulate_history = false, bool qbot_rh = false,
            bool update_accum = false, bool update_aerosol = false, bool update_active_layer = false, bool soil_hydrology = false,
-           bool water_balance = false, bool irrigation = false)
+           bool water_balance = false, bool irrigation = false, bool routing = false)
   {
     enqueue_run(dt_seconds, steps, accumulate_history, qbot_rh, update_accum, update_aerosol, update_active_layer, soil_hydrology, water_balance,
-                irrigation);
+                irrigation, routing);
     return finish_run();
   }
   const std::vector<double>& run_conservation() const { return run_conservation_; }
@@ -570,6 +595,7 @@ class ELMInterface {
   bool irrigation_{false};  // irrigation_enable(): advance() takes the split form
   int tod_{0};              // seconds after midnight UTC at the start of the next advance()
   int64_t grid_ncells_{0};
+  int64_t routing_ncells_{0};
   int64_t output_ncells_{0};
   std::vector<double> run_conservation_;
 };
