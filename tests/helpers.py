@@ -30,19 +30,99 @@ def oracle_state(cols, scal, soil, land=None, pft=None, optics=None):
     return S
 
 
-def device_state(cols, scal, soil, land=None, device=0):
+def device_state(cols, scal, soil, land=None, device=0, lat=None, lon=None, lib_path=None):
+    """The one context builder of the tests: the test parameters and tables, every field of cols uploaded; with lat and lon, the
+    column geography; lib_path: another build of the library (libelmk_f32.so); scal None: elmk_set_scalars is never called."""
     n = next(iter(cols.values())).shape[0]
-    D = st.ELMState(n, device)
+    D = st.ELMState(n, device, lib_path=lib_path)
     pft, optics = synth.load_params()
     D.set_pft(pft)
     D.set_snicar(optics)
     D.set_soilcolor(soil["albsat"], soil["albdry"])
     D.set_land(**(land or synth.TEST_LAND))
-    D.set_scalars(**scal)
+    if scal is not None:
+        D.set_scalars(**scal)
     D.set_snow_age_tables(synth.snow_age_tables())
     for k, v in cols.items():
         D[k] = v
+    if lat is not None:
+        D.set_column_geography(lat, lon)
     return D
+
+
+# err_flags bits that the oracle-against-reference tests read: the snow hydrology's warnings and errors, and the bit the reference
+# harness sets where the reference threw
+WARN_WATER, WARN_COMBINE, ERR_DIVIDE, ERR_AGE = 1 << 12, 1 << 13, 1 << 14, 1 << 15
+REF_THREW = np.uint32(1 << 31)
+
+
+def oracle_diffs(A, B, names=None):
+    """Two oracle states field by field, any NaN equal to any NaN -> {field: (count of differing values, worst relative error)}."""
+    diffs = {}
+    for k in names or A.fields:
+        a, b = A.fields[k], B.fields[k]
+        eq = (a == b) | (np.isnan(a.astype(float)) & np.isnan(b.astype(float)))
+        if not eq.all():
+            diffs[k] = (int((~eq).sum()), float(np.max(F.rel_err(a, b, floor=0.0))))
+    return diffs
+
+
+# ---- the reference's fixtures in the oracle -------------------------------------------------------------------------------------------
+def fixture_state(module):
+    """The oracle state of a module's fixture (tests/fixtures.py), one fixture step per column -> (d, rows, S, other inputs, expected outputs)."""
+    d = F.load(module)
+    rows = F.select_steps(d, module)
+    S = O.OracleState(len(rows))
+    S.load_params()
+    S.set_scalars(**F.TEST_LAND)
+    fin, oin = F.split(d, "in/", rows, S.nlev)
+    fout, _ = F.split(d, "out/", rows, S.nlev)
+    F.fill_state(S, fin)
+    S["vtype"][:] = F.TEST_LAND["vtype"]
+    S["veg_active"][:] = 1
+    return d, rows, S, oin, fout
+
+
+def compare_with_fixture(S, fout, n, rel=1e-15, skip=()):
+    bad = {}
+    total = 0
+    for name, exp in fout.items():
+        if name in skip:
+            continue
+        got = S[name].reshape(n, -1).astype(np.float64)
+        ok = F.almost_equal(got, exp, rel) | np.isnan(exp)
+        total += ok.size
+        if not ok.all():
+            bad[name] = (int((~ok).sum()), float(np.max(np.where(ok, 0.0, F.rel_err(got, exp)))))
+    return total, bad
+
+
+def run_canflux_fixture(given):
+    d = F.load("CanopyFluxes")
+    rows = F.select_steps(d, "CanopyFluxes")
+    probe = O.OracleState(1)
+    fin, oin = F.split(d, "in/", rows, probe.nlev)
+    fout, _ = F.split(d, "out/", rows, probe.nlev)
+    got = {k: np.zeros_like(v) for k, v in fout.items()}
+    niters = []
+    flags = 0
+    # dayl / max_dayl are state scalars (elm_state.h:222) but vary per fixture step: one 1-column run per step
+    for i in range(len(rows)):
+        S = O.OracleState(1)
+        S.load_params()
+        S.set_scalars(**F.TEST_LAND, dayl=float(oin["dayl"][i, 0]), max_dayl=float(oin["max_dayl"][i, 0]))
+        F.fill_state(S, {k: v[i : i + 1] for k, v in fin.items()})
+        S["vtype"][:] = F.TEST_LAND["vtype"]
+        if given:
+            nit = S.canopy_fluxes_given(F.TEST_DTIME, oin["forc_rho"][i], oin["forc_po2"][i], oin["forc_pco2"][i], True)
+        else:
+            # forc_rho derived as the wrapper does; CO2/O2 partial pressures still from the fixture (see below)
+            nit = S.canopy_fluxes_given(F.TEST_DTIME, None, oin["forc_po2"][i], oin["forc_pco2"][i], True)
+        niters.append(int(nit[0]))
+        flags |= int(S["err_flags"][0])
+        for k in got:
+            got[k][i] = S[k].reshape(1, -1)
+    return d["steps"][rows], got, fout, np.array(niters), flags
 
 
 # Outputs that are formed as a small difference of large operands carry the rounding error of the OPERANDS:

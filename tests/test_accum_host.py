@@ -12,13 +12,9 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import accum
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
+from tests.support import ROOT, bits_f64
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("elmk_accum_add", "elmk_accum_init", "elmk_accum_update", "elmk_accum_read", "elmk_accum_clear")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).tobytes()
 
 
 def scalar_update(val, v, kind, P, nstep):
@@ -58,16 +54,16 @@ def test_update_equals_the_scalar_loop(kind, P):
             v[::5] = -99999.0
         val = accum.update(val, v, kind, P, nstep)
         ref = [scalar_update(ref[i], v[i], kind, P, nstep) for i in range(n)]
-        assert bits(val) == bits(ref), (kind, P, nstep)
+        assert bits_f64(val) == bits_f64(ref), (kind, P, nstep)
     assert np.all(np.isfinite(val))
 
 
 def test_update_accepts_names_and_integer_samples():
     v = np.array([-2, 0, 3], np.int32)
     a = accum.update(np.zeros(3), v, "timeavg", 2, 1)
-    assert bits(a) == bits([-2.0, 0.0, 3.0])
-    assert bits(accum.update(a, v, "timeavg", 2, 2)) == bits([-2.0, 0.0, 3.0])
-    assert bits(accum.update(np.zeros(3), np.array([1, 2, 3], np.uint8), "runmean", 4, 1)) == bits([1.0, 2.0, 3.0])
+    assert bits_f64(a) == bits_f64([-2.0, 0.0, 3.0])
+    assert bits_f64(accum.update(a, v, "timeavg", 2, 2)) == bits_f64([-2.0, 0.0, 3.0])
+    assert bits_f64(accum.update(np.zeros(3), np.array([1, 2, 3], np.uint8), "runmean", 4, 1)) == bits_f64([1.0, 2.0, 3.0])
     with pytest.raises(ValueError):
         accum.update(np.zeros(1), np.zeros(1), 3, 4, 1)
     with pytest.raises(ValueError):
@@ -80,18 +76,18 @@ def test_update_signed_zero_and_nan():
     nz, nan = -0.0, float("nan")
     # RUNMEAN as written for a == 1: (0.0 * val + v) / 1.0; +0.0 + -0.0 = +0.0
     out = accum.update(np.array([0.0, -0.0, 5.0]), np.array([nz, nz, nz]), accum.RUNMEAN, 4, 1)
-    assert bits(out) == bits([0.0, -0.0, 0.0])
+    assert bits_f64(out) == bits_f64([0.0, -0.0, 0.0])
     # ... and a NaN or infinite value before the first update is not masked by the zero factor
     assert np.isnan(accum.update(np.array([np.inf]), np.array([1.0]), accum.RUNMEAN, 4, 1))[0]
     # TIMEAVG: the period starts from +0.0, so a sample of -0.0 gives +0.0
-    assert bits(accum.update(np.array([7.0]), np.array([nz]), accum.TIMEAVG, 4, 1)) == bits([0.0])
-    assert bits(accum.update(np.array([nz]), np.array([nz]), accum.TIMEAVG, 4, 2)) == bits([nz])
+    assert bits_f64(accum.update(np.array([7.0]), np.array([nz]), accum.TIMEAVG, 4, 1)) == bits_f64([0.0])
+    assert bits_f64(accum.update(np.array([nz]), np.array([nz]), accum.TIMEAVG, 4, 2)) == bits_f64([nz])
     # a NaN sample: sticks in the means, resets RUNACCUM (t > 0.0 is false for NaN)
     assert np.isnan(accum.update(np.array([1.0]), np.array([nan]), accum.RUNMEAN, 4, 3))[0]
     assert np.isnan(accum.update(np.array([1.0]), np.array([nan]), accum.TIMEAVG, 4, 3))[0]
-    assert bits(accum.update(np.array([1.0]), np.array([nan]), accum.RUNACCUM, 4, 3)) == bits([0.0])
+    assert bits_f64(accum.update(np.array([1.0]), np.array([nan]), accum.RUNACCUM, 4, 3)) == bits_f64([0.0])
     # ... and a NaN value leaves the period with the next TIMEAVG reset, RUNMEAN never on its own
-    assert bits(accum.update(np.array([nan]), np.array([2.0]), accum.TIMEAVG, 4, 5)) == bits([2.0])
+    assert bits_f64(accum.update(np.array([nan]), np.array([2.0]), accum.TIMEAVG, 4, 5)) == bits_f64([2.0])
     assert np.isnan(accum.update(np.array([nan]), np.array([2.0]), accum.RUNMEAN, 4, 5))[0]
 
 
@@ -100,14 +96,14 @@ def test_runaccum_reset_value_and_clamps():
     # the reset value is matched after rounding to the nearest integer, half to even; from a value above the clamp a reset (0.0)
     # and a sum differ
     big = 150000.0
-    assert bits(up([big, big, big], [-99999.0, -99999.4, -99998.6])) == bits([0.0, 0.0, 0.0])
-    assert bits(up([big, big, big], [-99999.5, -99998.5, -99998.4])) == bits([50000.5, 50001.5, big + -99998.4])  # -100000, -99998
+    assert bits_f64(up([big, big, big], [-99999.0, -99999.4, -99998.6])) == bits_f64([0.0, 0.0, 0.0])
+    assert bits_f64(up([big, big, big], [-99999.5, -99998.5, -99998.4])) == bits_f64([50000.5, 50001.5, big + -99998.4])  # -100000, -99998
     # lower clamp gives +0.0, also from -0.0
-    assert bits(up([1.0, 0.0, -0.0], [-3.0, -0.0, -0.0])) == bits([0.0, 0.0, 0.0])
+    assert bits_f64(up([1.0, 0.0, -0.0], [-3.0, -0.0, -0.0])) == bits_f64([0.0, 0.0, 0.0])
     # upper clamp: t < 99999.0 keeps t, anything else (99999.0 itself, above, +inf) is 99999.0
     below = np.nextafter(99999.0, 0.0)
-    assert bits(up([99998.0, 99998.0, 99998.0, 0.0], [below - 99998.0, 1.0, 2.0, np.inf])) == bits([below, 99999.0, 99999.0, 99999.0])
-    assert bits(up([1.5], [2.25])) == bits([3.75])
+    assert bits_f64(up([99998.0, 99998.0, 99998.0, 0.0], [below - 99998.0, 1.0, 2.0, np.inf])) == bits_f64([below, 99999.0, 99999.0, 99999.0])
+    assert bits_f64(up([1.5], [2.25])) == bits_f64([3.75])
 
 
 def test_writes_destination():

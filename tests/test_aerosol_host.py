@@ -13,13 +13,9 @@ import pytest
 from elmkernels_amd import _lib as L
 from elmkernels_amd import aerosol
 from elmkernels_amd import state as st
+from tests.support import ROOT, bits_f64
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("elmk_aerosol_reserve", "elmk_aerosol_upload", "elmk_aerosol_deposition", "elmk_aerosol_clear")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).tobytes()
 
 
 def bits1(x):
@@ -79,14 +75,14 @@ def test_interpolate_equals_the_scalar_loop(mapped):
         assert tuple(got) == aerosol.STREAMS
         for s in aerosol.STREAMS:
             assert got[s].shape == (n,) and got[s].dtype == np.float64
-            assert bits(got[s]) == bits(want[s]), (s, m1, m2)
+            assert bits_f64(got[s]) == bits_f64(want[s]), (s, m1, m2)
     # the array form [11, 12, ncells] and the aer_ keys are the same series
     arr = np.stack([series[s] for s in aerosol.STREAMS])
     pre = {"aer_" + s: v for s, v in series.items()}
     for alt in (arr, pre):
         got = aerosol.interpolate(alt, 11, 0, 0.3, 0.7, idx, w)
         for s in aerosol.STREAMS:
-            assert bits(got[s]) == bits(aerosol.interpolate(series, 11, 0, 0.3, 0.7, idx, w)[s])
+            assert bits_f64(got[s]) == bits_f64(aerosol.interpolate(series, 11, 0, 0.3, 0.7, idx, w)[s])
 
 
 def test_weights_one_and_zero_are_products_not_copies():
@@ -96,7 +92,7 @@ def test_weights_one_and_zero_are_products_not_copies():
     series = aerosol.synthetic_climatology(5, seed=1)
     x, y = series["bcphi"][0].copy(), series["bcphi"][1].copy()
     got = aerosol.interpolate(series, 0, 1, 1.0, 0.0)["bcphi"]
-    assert np.array_equal(got, x) and bits(got) == bits(x * 1.0 + y * 0.0)
+    assert np.array_equal(got, x) and bits_f64(got) == bits_f64(x * 1.0 + y * 0.0)
     got = aerosol.interpolate(series, 0, 1, 0.0, 1.0)["bcphi"]
     assert np.array_equal(got, y)
     series["bcphi"][1, 3] = np.nan
@@ -112,7 +108,7 @@ def test_bracket_december_january():
     got = aerosol.interpolate(series, 11, 0, 0.3, 0.7)
     for s in aerosol.STREAMS:
         want = np.array([0.3 * float(series[s][11][c]) + 0.7 * float(series[s][0][c]) for c in range(9)])
-        assert bits(got[s]) == bits(want)
+        assert bits_f64(got[s]) == bits_f64(want)
     for bad in ((12, 0), (0, -1)):
         with pytest.raises(ValueError):
             aerosol.interpolate(series, bad[0], bad[1], 0.5, 0.5)
@@ -152,7 +148,7 @@ def test_synthetic_climatology_is_seasonal_with_its_edge_cells():
             assert int(np.argmax(tot)) == 3 and tot[3] > 5.0 * tot[9]  # April over October
     assert bits1(series["dst1_1"][0, 0]) == bits1(-0.0)
     again = aerosol.synthetic_climatology(ncells, seed=6)
-    assert all(bits(series[s]) == bits(again[s]) for s in aerosol.STREAMS)
+    assert all(bits_f64(series[s]) == bits_f64(again[s]) for s in aerosol.STREAMS)
     m1, m2, w1, w2 = aerosol.month_bracket(0.0)
     assert (m1, m2) == (11, 0) and w1 + w2 == 1.0
     m1, m2, w1, w2 = aerosol.month_bracket(16.0)  # just past mid January

@@ -4,13 +4,10 @@ import numpy as np
 import pytest
 
 from elmkernels_amd import diagnostics as dg
+from tests.support import words_f64
 
 NPART, BLOCK = 512, 256
 T = NPART * BLOCK
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def _min(acc, v):
@@ -75,10 +72,10 @@ def wide_values(n, seed):
 def test_restatement_equals_the_literal_thread_loop(n):
     x = wide_values(n, 100 + n % 97)
     got, want = dg.reduce_min_max_sum(x), literal(x)
-    assert np.array_equal(bits(got), bits(want)), (n, got, want)
+    assert np.array_equal(words_f64(got), words_f64(want)), (n, got, want)
     assert got[0] == x.min() and got[1] == x.max()
     if n > 1:  # the order is visible in these values: numpy's pairwise sum and the running sum round differently
-        assert bits(got[2]) != bits(np.sum(x)) and bits(got[2]) != bits(np.cumsum(x)[-1])
+        assert words_f64(got[2]) != words_f64(np.sum(x)) and words_f64(got[2]) != words_f64(np.cumsum(x)[-1])
 
 
 @pytest.mark.parametrize("n,at,what", [(300, a, w) for a in (0, 137, 299) for w in (np.nan, np.inf, -np.inf)]
@@ -104,19 +101,19 @@ def test_padding_with_plus_zero_changes_no_bit():
     accumulator that starts at +0.0 never becomes -0.0: (+0.0) + (-0.0) = +0.0, x + (-x) = +0.0, and a sum of terms none of which is
     -0.0 is not -0.0 either.  So a column of nothing but -0.0 (the only candidate) still sums to +0.0 on both paths."""
     s = np.array([1.5, -1.5, 1e-320, -1e-320, 1e308, -1e308, np.inf, -np.inf, 0.0, 4.9e-324])
-    assert np.array_equal(bits(s + 0.0), bits(s))
-    assert bits(np.float64(-0.0) + np.float64(0.0)) == bits(0.0) and bits(np.float64(0.0) + np.float64(-0.0)) == bits(0.0)
-    assert bits(np.float64(2.5) + np.float64(-2.5)) == bits(0.0)
+    assert np.array_equal(words_f64(s + 0.0), words_f64(s))
+    assert words_f64(np.float64(-0.0) + np.float64(0.0)) == words_f64(0.0) and words_f64(np.float64(0.0) + np.float64(-0.0)) == words_f64(0.0)
+    assert words_f64(np.float64(2.5) + np.float64(-2.5)) == words_f64(0.0)
     for n in (1, 2, 300):
         x = np.full(n, -0.0)
         got = dg.reduce_min_max_sum(x)
-        assert bits(got[2]) == bits(0.0) and np.array_equal(bits(got), bits(literal(x)))
+        assert words_f64(got[2]) == words_f64(0.0) and np.array_equal(words_f64(got), words_f64(literal(x)))
     x = wide_values(300, 5)
     x[:5] = -0.0
-    assert np.array_equal(bits(dg.reduce_min_max_sum(x)), bits(literal(x)))
+    assert np.array_equal(words_f64(dg.reduce_min_max_sum(x)), words_f64(literal(x)))
 
 
 def test_empty_and_identity():
     """No columns: the identities (what an all-identity stage 2 gives)."""
     got = dg.reduce_min_max_sum(np.zeros(0))
-    assert got[0] == np.inf and got[1] == -np.inf and bits(got[2]) == bits(0.0)
+    assert got[0] == np.inf and got[1] == -np.inf and words_f64(got[2]) == words_f64(0.0)

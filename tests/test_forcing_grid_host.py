@@ -9,8 +9,8 @@ import pytest
 from elmkernels_amd import _lib as L
 from elmkernels_amd import decomp
 from elmkernels_amd import regrid as R
+from tests.support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NLON, NLAT = 64, 32
 
 

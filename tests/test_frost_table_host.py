@@ -11,18 +11,14 @@ import pytest
 from elmkernels_amd import _lib as L
 from elmkernels_amd import hydrology as hy
 from elmkernels_amd import state as st
-from tests.test_hydrology_host import BRANCHES, CHAIN_STEPS, CLOSURE_BOUND, CLOSURE_FIELDS, DT, ROOT, column, generated, water_mass
-
-N = hy.N
-FROST_BRANCHES = {"frost_A", "frost_A_exhausted", "frost_B_perched", "frost_B_none", "frost_B_thawed", "perched_ends_in_layer",
-                  "perched_exhausted"}
-S0, S1 = hy.NLEVSNO, hy.NLEVSNO + N
-WARM, COLD = 275.0, 270.0
+from tests.hydrology_cases import (BRANCHES, CHAIN_STEPS, CLOSURE_BOUND, CLOSURE_FIELDS, COLD, DT, FROST_BRANCHES, S0, S1, WARM, Count, N, column,
+                                   generated_frost, water_mass)
+from tests.support import ROOT, bits
 
 
 # ---- hand-built columns -----------------------------------------------------------------------------------------------------------
 def frost_column(kf, q_perch_max=1.0e-6, **kw):
-    """test_hydrology_host.column with layers 0 .. kf-1 thawed and kf .. 9 frozen (kf = N: all thawed)."""
+    """hydrology_cases.column with layers 0 .. kf-1 thawed and kf .. 9 frozen (kf = N: all thawed)."""
     return column(t=[WARM] * kf + [COLD] * (N - kf), q_perch_max=q_perch_max, **kw)
 
 
@@ -154,69 +150,6 @@ def test_a_frozen_top_layer():
 
 
 # ---- the generated columns --------------------------------------------------------------------------------------------------------
-def add_frost(cols, rows, seed):
-    """The permafrost tier on top of the generator's columns: in consecutive columns all thawed, all frozen, thaw fronts at layers
-    1 .. 9, a frozen lens over thawed ground and a frozen top layer over a thawed one; per thirteen columns in turn the water table above
-    the frost table, below it, and where the generator put it; below it, the two layers over the frost table near saturation under drier
-    ones (a perched table).  One column in five has a rate of 10 to 1000 per second, far beyond any slope's, so that the walks run out of water.  Changes
-    cols["t_soisno"] and rows[ZWT] in place; returns the rows of the extension [FROST_NROWS, n]."""
-    n = rows.shape[1]
-    rng = np.random.default_rng(seed)
-    t = np.array(cols["t_soisno"], dtype=np.float64)
-    liq, ice = cols["h2osoi_liq"], cols["h2osoi_ice"]
-    z = cols["zsoi"][:, S0:S1].astype(np.float64)
-    dzmm = cols["dz"][:, S0:S1].astype(np.float64) * 1.0e3
-    watsat = cols["watsat"][:, :N].astype(np.float64)
-    for i in range(n):
-        kind, where = i % 13, (i // 13) % 3
-        prof = np.full(N, WARM) + rng.random(N)
-        if kind == 1:
-            prof[:] = COLD - rng.random(N)
-            kf = 0
-        elif 2 <= kind <= 10:
-            kf = kind - 1
-            prof[kf:] = COLD - rng.random(N - kf)
-        elif kind == 11:
-            kf = 4
-            prof[4:6] = COLD
-        elif kind == 12:
-            kf = 3
-            prof[0] = COLD
-            prof[3:] = COLD
-        else:
-            kf = None
-        t[i, S0:S1] = prof
-        if kf is None:
-            continue
-        if where == 0:
-            rows[hy.ZWT, i] = z[i, kf] * rng.uniform(0.05, 0.95)
-        elif where == 1:
-            rows[hy.ZWT, i] = z[i, kf] + rng.uniform(0.01, 6.0)
-            if kf >= 2 and i % 7 != 3:
-                for j in (kf - 1, kf):
-                    liq[i, S0 + j] = max(0.97 * watsat[i, j] * dzmm[i, j] - ice[i, S0 + j] * (1000.0 / 917.0), 0.02)
-                for j in range(kf - 1):
-                    liq[i, S0 + j] = min(liq[i, S0 + j], 0.5 * watsat[i, j] * dzmm[i, j])
-    cols["t_soisno"] = t.astype(cols["t_soisno"].dtype)
-    frost = np.zeros((hy.FROST_NROWS, n))
-    frost[hy.Q_PERCH_MAX] = np.where(np.arange(n) % 5 == 4, rng.uniform(10.0, 1000.0, n), hy.q_perch_max(rng.uniform(0.5, 12.0, n)))
-    return frost
-
-
-def generated_frost(n, seed, **kw):
-    """test_hydrology_host.generated plus add_frost: (cols, [scal, soil,] rows, frost)."""
-    g = generated(n, seed, **kw)
-    frost = add_frost(g[0], g[-1], seed + 2)
-    return g + (frost,)
-
-
-class Count(dict):
-    """A `hit` that counts: every new mark is set at most once per column."""
-
-    def add(self, name):
-        self[name] = self.get(name, 0) + 1
-
-
 @pytest.fixture(scope="module")
 def gen():
     cols, rows, frost = generated_frost(1001, 77)
@@ -233,10 +166,6 @@ def test_the_generated_columns_take_every_branch(gen):
     assert BRANCHES - {"drain_aquifer", "drain_soil"} <= set(hit), BRANCHES - set(hit)
     frost_out = gen[5]
     assert np.isfinite(frost_out).all() and bits(frost_out[hy.Q_PERCH_MAX]) == bits(gen[2][hy.Q_PERCH_MAX])
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def _same_outputs(a, b, sel):
@@ -322,7 +251,7 @@ def test_fp32_inputs_round_once():
 
 # ---- the chain --------------------------------------------------------------------------------------------------------------------
 def frost_closure(f, wa_beg, h2osno_beg, rows_out, dt, qp):
-    """test_hydrology_host.closure with the perched drainage in the source/sink (qp None: without it)."""
+    """hydrology_cases.closure with the perched drainage in the source/sink (qp None: without it)."""
     e = hy.water_balance_error(f["dtbegin_column_h2o"], water_mass(f), wa_beg, rows_out[hy.WA], f["forc_rain"], f["forc_snow"],
                                f["qflx_evap_tot"], f["qflx_snwcp_ice"], rows_out[hy.QFLX_SURF], rows_out[hy.QFLX_H2OSFC_SURF],
                                rows_out[hy.QFLX_DRAIN], dt, qflx_drain_perched=qp)
@@ -331,7 +260,7 @@ def frost_closure(f, wa_beg, h2osno_beg, rows_out, dt, qp):
 
 
 def frost_host_chain(cols, scal, soil, rows, frost, nsteps=CHAIN_STEPS, dt=DT):
-    """test_hydrology_host.host_chain with the extension (frost None: without): per step (errh2o, keep, frost rows)."""
+    """hydrology_cases.host_chain with the extension (frost None: without): per step (errh2o, keep, frost rows)."""
     from tests import helpers as H
 
     S = H.oracle_state(cols, scal, soil)

@@ -2,10 +2,6 @@
 (elmkernels_amd/accum.py) bit for bit in both builds, t10 fed back through elmk_run against the loop with a host round trip per
 step, seeding, exact restarts (also across a change of decomposition), every refusal, and the demo."""
 import ctypes as C
-import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +10,9 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import accum
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
-from tests.test_gpu_history import _hip_runtime
-from tests.test_gpu_run import DT, NREC, NSTEPS, ROOT, SERIES, _device, _inputs, same, schedule, stepwise, upload_series
+from tests import helpers as H
+from tests.run_cases import DT, NREC, NSTEPS, SERIES, _inputs, demo_records, device, schedule, stepwise, upload_series
+from tests.support import bits, build_demo, captured, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +21,6 @@ P10 = 4  # steps of the t10 window in the run tests: saturates inside the 12 ste
 # (source, kind, period, destination): one entry of each kind with P in {4, 10}; 1 and 20 levels, fp64 and int32 sources
 ENTRIES = [("t_ref2m", accum.RUNMEAN, 4, "t10"), ("t_soisno", accum.RUNMEAN, 10, "csol"), ("t_ref2m", accum.TIMEAVG, 4, "n_melt"),
            ("t_soisno", accum.TIMEAVG, 10, None), ("t_ref2m", accum.RUNACCUM, 4, "micro_sigma"), ("snl", accum.RUNACCUM, 10, None)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def _samples(n, step, rng):
@@ -150,32 +143,17 @@ def test_update_in_a_captured_graph_advances_the_count():
     e = D.accum_add("t_ref2m", accum.TIMEAVG, 4, "t10")
     t = 250.0 + np.arange(n, dtype=np.float64)
     D["t_ref2m"] = t
-    hip = _hip_runtime()
-    P = C.c_void_p
-    for name, args in (("hipGraphInstantiate", [C.POINTER(P), P, P, P, C.c_size_t]), ("hipGraphLaunch", [P, P]), ("hipGraphExecDestroy", [P]),
-                       ("hipStreamSynchronize", [P])):
-        getattr(hip, name).argtypes = args
-        getattr(hip, name).restype = C.c_int
-    strm, graph, ex = P(), P(), P()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    D.accum_update()
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
-    assert D.accum_read(e)[1] == 0  # captured, not run
-    assert hip.hipGraphInstantiate(C.byref(ex), graph, None, None, 0) == 0
-    val = np.zeros(n)
-    for k in range(1, 7):
-        assert hip.hipGraphLaunch(ex, strm) == 0
-        val = accum.update(val, t, accum.TIMEAVG, 4, k)
-    assert hip.hipStreamSynchronize(strm) == 0
-    got, cnt = D.accum_read(e)
-    assert cnt == 6 and bits(got) == bits(val)
-    assert bits(D["t10"]) == bits(t)  # the average of the one whole period
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(strm)
+    with captured(D) as cap:
+        D.accum_update()
+        cap.end()
+        assert D.accum_read(e)[1] == 0  # captured, not run
+        cap.replay(6)
+        val = np.zeros(n)
+        for k in range(1, 7):
+            val = accum.update(val, t, accum.TIMEAVG, 4, k)
+        got, cnt = D.accum_read(e)
+        assert cnt == 6 and bits(got) == bits(val)
+        assert bits(D["t10"]) == bits(t)  # the average of the one whole period
     D.close()
 
 
@@ -201,7 +179,7 @@ def _host_feedback(D, rec, steps, val, n0, history=False):
 
 
 def _run_context(base, graph):
-    D = _device(*base[:5])
+    D = device(base)
     D.set_graph(graph)
     e = accum.add_t10(D, DT, period=P10)
     D.run_reserve(NREC, NSTEPS)
@@ -212,7 +190,7 @@ def _run_context(base, graph):
 def test_t10_feedback_through_the_run(base):
     cols, rec = base[0], base[5]
     steps = schedule()
-    A = _device(*base[:5])
+    A = device(base)
     want, val = _host_feedback(A, rec, steps, np.zeros(200), 0)
     want_state = {k: A[k] for k in A.fields if k not in SERIES}
     A.close()
@@ -238,7 +216,7 @@ def test_t10_feedback_through_the_run(base):
 def test_seeding_from_the_destination(base):
     """accum_init without values: val = the t10 that was uploaded, the window already full; one update gives ((P-1) * t10 + v) / P."""
     cols = base[0]
-    D = _device(*base[:5])
+    D = device(base)
     e = accum.add_t10(D, DT, period=P10)
     D.accum_init(e, None, P10 + 3)
     got, cnt = D.accum_read(e)
@@ -274,7 +252,7 @@ def _sub(base, c0, n):
 
 
 def _restart_context(base, fields=True):
-    D = _device(*base[:5])
+    D = device(base)
     if not fields:
         for name, (fid, nlev, dt) in D.fields.items():
             D.fill(name, np.nan if dt == np.float64 else 3.0)
@@ -346,7 +324,7 @@ def test_restart_across_a_change_of_decomposition(base, continuous):
 
 
 def test_no_entries_is_the_version_1_image(base):
-    D = _device(*base[:5])
+    D = device(base)
     size0 = D.restart_size()
     img0 = D.restart_save()
     assert int(R.verify(img0)["header"]["version"]) == 1 and img0.size == size0
@@ -365,7 +343,7 @@ def _invalid(rc):
 
 
 def test_refusals_change_nothing(base):
-    D = _device(*base[:5])
+    D = device(base)
     lib, ctx, f = D.lib, D.ctx, {k: v[0] for k, v in D.fields.items()}
     nf = lib.elmk_num_fields()
     e0 = D.accum_add("t_ref2m", accum.RUNMEAN, 4, "t10")
@@ -398,18 +376,10 @@ def test_refusals_change_nothing(base):
     for what, a in {"entry 2": (2, 0, 200), "columns past the end": (e0, 1, 200), "negative col0": (e0, -1, 10)}.items():
         assert _invalid(lib.elmk_accum_read(ctx, a[0], buf.ctypes.data_as(C.c_void_p), a[1], a[2], st.LAYOUT_SOA, C.byref(cnt))), what
     # a stream being captured
-    hip = _hip_runtime()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rcs = [lib.elmk_accum_add(ctx, f["t_ref2m"], 0, 4, -1), lib.elmk_accum_init(ctx, e0, None, 5), lib.elmk_accum_clear(ctx)]
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
-    assert all(_invalid(rc) for rc in rcs), rcs
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(strm)
+    with captured(D) as cap:
+        rcs = [lib.elmk_accum_add(ctx, f["t_ref2m"], 0, 4, -1), lib.elmk_accum_init(ctx, e0, None, 5), lib.elmk_accum_clear(ctx)]
+        cap.end()
+        assert all(_invalid(rc) for rc in rcs), rcs
     assert unchanged(before, state())
     # elmk_restart_load: another accumulator table
     img = D.restart_save()
@@ -459,41 +429,9 @@ def test_refusals_change_nothing(base):
 # ---- the demo ------------------------------------------------------------------------------------------------------------------------
 def test_accum_demo(tmp_path):
     """examples/accum_demo.cc builds and runs 48 steps with t10 on the device against the loop with a host round trip per step."""
-    from tests import helpers as H
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     n = 320
     cols, scal, soil, lat, lon, rec = _inputs(n, 75, nrec=25)
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "accum_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "accum_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    for i, k in enumerate(("age_tau", "age_kappa", "age_drdt0")):
-        put(k, 1, S.snowage[i])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in SERIES:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
-    put("steps", 1, schedule(48))
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(tmp_path / "state.bin")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    exe = build_demo("accum_demo", tmp_path)
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, demo_records(lat, lon, rec) + [("steps", schedule(48))]))
+    r = run_demo(exe, tmp_path / "state.bin")
     assert "bit-identical" in r.stdout

@@ -3,10 +3,7 @@
 update inside elmk_run against the stepwise calls, exact restarts (also across a change of decomposition), every refusal, no effect on
 anything else, and the demo."""
 import ctypes as C
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,18 +13,15 @@ from elmkernels_amd import accum
 from elmkernels_amd import active_layer as al
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
-from tests.test_active_layer_host import TFRZ, columns
-from tests.test_gpu_history import _hip_runtime
-from tests.test_gpu_run import DT, NREC, ROOT, SERIES, _device, _inputs, same, schedule, stepwise, upload_series
+from tests import helpers as H
+from tests.active_layer_cases import TFRZ, columns
+from tests.run_cases import DT, NREC, SERIES, _inputs, demo_records, device, schedule, stepwise, upload_series
+from tests.support import bits, build_demo, captured, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
 
 ROWS = (al.ALT, al.ALTMAX, al.ALTMAX_LASTYEAR)
 INDX = ("altmax_indx", "altmax_lastyear_indx")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def _lat(n, seed):
@@ -169,31 +163,16 @@ def test_update_in_a_captured_graph():
     al.cold_start(D)
     t, z = _soil(n, 22)
     D["t_soisno"], D["zsoi"] = t.T, z.T
-    hip = _hip_runtime()
-    P = C.c_void_p
-    for name, args in (("hipGraphInstantiate", [C.POINTER(P), P, P, P, C.c_size_t]), ("hipGraphLaunch", [P, P]), ("hipGraphExecDestroy", [P]),
-                       ("hipStreamSynchronize", [P])):
-        getattr(hip, name).argtypes = args
-        getattr(hip, name).restype = C.c_int
-    strm, graph, ex = P(), P(), P()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    D.active_layer_update(al.ROLL_SOUTH)
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
-    assert not D.active_layer_read(al.ALT).any()  # captured, not run
-    assert hip.hipGraphInstantiate(C.byref(ex), graph, None, None, 0) == 0
-    want = [np.zeros(n), np.zeros(n), np.zeros(n), np.full(n, -1, np.int32), np.full(n, -1, np.int32)]
-    for _ in range(2):
-        assert hip.hipGraphLaunch(ex, strm) == 0
-        want = al.update(t, z, *want, al.north(lat), al.ROLL_SOUTH)
-    assert hip.hipStreamSynchronize(strm) == 0
-    for g, w in zip(_rows(D), want):
-        assert bits(g) == bits(w)
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(strm)
+    with captured(D) as cap:
+        D.active_layer_update(al.ROLL_SOUTH)
+        cap.end()
+        assert not D.active_layer_read(al.ALT).any()  # captured, not run
+        cap.replay(2)
+        want = [np.zeros(n), np.zeros(n), np.zeros(n), np.full(n, -1, np.int32), np.full(n, -1, np.int32)]
+        for _ in range(2):
+            want = al.update(t, z, *want, al.north(lat), al.ROLL_SOUTH)
+        for g, w in zip(_rows(D), want):
+            assert bits(g) == bits(w)
     D.close()
 
 
@@ -234,7 +213,7 @@ def _altmax0(n):
 
 
 def _context(base, graph, entries=False):
-    D = _device(*base[:5])
+    D = device(base)
     D.set_graph(graph)
     D.active_layer_enable()
     D.active_layer_init(*_altmax0(D.ncols))
@@ -319,8 +298,8 @@ def test_run_equals_stepwise(base, stepwise_result, graph, entries):
 def test_no_effect_elsewhere(base):
     """One step after an update of the feature leaves every field but the two indices as a context without the feature has it."""
     steps = new_year_schedule()[:1]
-    A = _device(*base[:5])
-    B = _device(*base[:5])
+    A = device(base)
+    B = device(base)
     before = B.device_bytes
     B.active_layer_enable()
     assert B.device_bytes - before == 3 * 8 * B.level_stride and A.device_bytes == before
@@ -402,7 +381,7 @@ def test_restart_across_a_change_of_decomposition(base, continuous):
 def test_versions_do_not_mix(base):
     """enable then clear saves the bytes a never-enabled context saves; a version-3 image into a plain context and a version-1 image into
     an enabled one are refused with state and rows unchanged."""
-    D = _device(*base[:5])
+    D = device(base)
     size0, bytes0 = D.restart_size(), D.device_bytes
     img1 = D.restart_save()
     assert int(R.verify(img1)["header"]["version"]) == 1 and img1.size == size0
@@ -412,7 +391,7 @@ def test_versions_do_not_mix(base):
     assert D.restart_size() == size0 and D.device_bytes == bytes0
     assert bits(D.restart_save()) == bits(img1)
     # an enabled context without accumulator entries: version 3 with the count word 0
-    E = _device(*base[:5])
+    E = device(base)
     E.active_layer_enable()
     E.active_layer_init(*_altmax0(NCOL))
     E.active_layer_update(al.ROLL_SOUTH)
@@ -464,7 +443,7 @@ def test_refusals_change_nothing(base):
     assert same(P["altmax_indx"], indx) and not P.active_layer_read(al.ALTMAX).any()
     P.close()
 
-    D = _device(*base[:5])
+    D = device(base)
     ctx = D.ctx
     D.run_reserve(NREC, NSTEPS)
     upload_series(D, base[5])
@@ -500,21 +479,10 @@ def test_refusals_change_nothing(base):
     # a stream being captured: enable (on another context), init, read and clear are refused; nothing changes
     O = st.ELMState(NCOL)
     o_bytes = O.device_bytes
-    hip = _hip_runtime()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    D.set_stream(strm.value)
-    O.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rcs = [lib.elmk_active_layer_enable(O.ctx), lib.elmk_active_layer_init(ctx, None, None), lib.elmk_active_layer_read(ctx, 0, ptr, 0, NCOL),
-           lib.elmk_active_layer_clear(ctx)]
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    with captured(D, O):
+        rcs = [lib.elmk_active_layer_enable(O.ctx), lib.elmk_active_layer_init(ctx, None, None), lib.elmk_active_layer_read(ctx, 0, ptr, 0, NCOL),
+               lib.elmk_active_layer_clear(ctx)]
     assert rcs == [-1] * 4, rcs
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    O.set_stream(None)
-    hip.hipStreamDestroy(strm)
     assert unchanged(before, state()) and O.device_bytes == o_bytes
     assert lib.elmk_active_layer_read(O.ctx, 0, ptr, 0, NCOL) == -1  # O was never enabled
     O.close()
@@ -528,42 +496,11 @@ def test_refusals_change_nothing(base):
 # ---- the demo ------------------------------------------------------------------------------------------------------------------------
 def test_active_layer_demo(tmp_path):
     """examples/active_layer_demo.cc builds and runs 6 steps across 00:00 of 1 January: one run against the stepwise updates."""
-    from tests import helpers as H
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     n = 320
     cols, scal, soil, lat, lon, rec = _inputs(n, 75, nrec=25)
     cols["t_soisno"] = TFRZ + 5.0 * np.random.default_rng(1).random((n, 1)) - 0.5 * np.arange(20)[None, :] + 2.0
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "active_layer_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "active_layer_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    for i, k in enumerate(("age_tau", "age_kappa", "age_drdt0")):
-        put(k, 1, S.snowage[i])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in SERIES:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
-    put("steps", 1, new_year_schedule(6))
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(tmp_path / "state.bin")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    exe = build_demo("active_layer_demo", tmp_path)
+    extra = demo_records(lat, lon, rec) + [("steps", new_year_schedule(6))]
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, extra))
+    r = run_demo(exe, tmp_path / "state.bin")
     assert "bit-identical" in r.stdout and "ALTMAX_LASTYEAR" in r.stdout

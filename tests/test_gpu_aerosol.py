@@ -2,10 +2,6 @@
 in both builds, elmk_run with ELMK_RUN_AEROSOL against the stepwise calls, a second device path, the flag beside the others,
 restarts, every refusal, and the demo."""
 import ctypes as C
-import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,8 +11,9 @@ from elmkernels_amd import accum
 from elmkernels_amd import aerosol
 from elmkernels_amd import regrid
 from elmkernels_amd import state as st
-from tests.test_gpu_history import _hip_runtime
-from tests.test_gpu_run import DT, NREC, NSTEPS, ROOT, SERIES, _device, _inputs, same, schedule, stepwise, upload_series
+from tests import helpers as H
+from tests.run_cases import DT, NREC, NSTEPS, SERIES, _inputs, demo_records, schedule, stepwise, upload_series
+from tests.support import build_demo, captured, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
 
@@ -74,7 +71,7 @@ def stored(D, a):
 @pytest.mark.parametrize("n", [1, N])
 def test_kernel_equals_the_restatement(n, kind, lib_path):
     cols, scal, soil, lat, lon, _ = _inputs(n, SEED)
-    D = _device(cols, scal, soil, lat, lon, lib_path)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=lib_path)
     ncells, idx, w = make_map(kind, n)
     series = aerosol.synthetic_climatology(ncells, seed=3)
     for s in aerosol.STREAMS:
@@ -118,7 +115,7 @@ def mapped():
 
 
 def stepwise_device(D, rec, steps, history=False, update_accum=False):
-    """tests/test_gpu_run.py: stepwise with elmk_aerosol_deposition before elmk_init_timestep, where elmk_run has it."""
+    """tests/run_cases.py: stepwise with elmk_aerosol_deposition before elmk_init_timestep, where elmk_run has it."""
     cons, fo, fb = [], [], []
     for p in steps:
         D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
@@ -145,7 +142,7 @@ def stepwise_device(D, rec, steps, history=False, update_accum=False):
 
 def run_context(base, mapped, graph, lib_path=None):
     cols, scal, soil, lat, lon, rec = base
-    D = _device(cols, scal, soil, lat, lon, lib_path)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=lib_path)
     D.set_graph(graph)
     D.run_reserve(NREC, NSTEPS)
     upload_series(D, rec)
@@ -181,7 +178,7 @@ def test_run_equals_stepwise(base, mapped, flagged):
     snow0 = cols["snl"].reshape(-1) > 0
     assert snow0.any()  # (from synth.make_state: no GPU needed to know it)
     # A: the existing calls, the host-interpolated aer_* uploaded before every step
-    A = _device(cols, scal, soil, lat, lon)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     rows = []
     for p in steps:
         want = aerosol.interpolate(series, p["month1"], p["month2"], p["month_wt1"], p["month_wt2"], idx, w)
@@ -192,7 +189,7 @@ def test_run_equals_stepwise(base, mapped, flagged):
     want_state = state_of(A)
     A.close()
     # A2: the same with the device's stepwise call
-    A2 = _device(cols, scal, soil, lat, lon)
+    A2 = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     reserve_and_upload(A2, ncells, idx, w, series)
     rows2 = stepwise_device(A2, rec, steps)
     assert_states(want_state, state_of(A2), "stepwise device call")
@@ -232,7 +229,7 @@ def test_deposition_equals_upload_gridded_of_host_interpolated_cells(base):
     ncells = nlon * nlat
     assert len(np.unique(idx)) > 3
     series = aerosol.synthetic_climatology(ncells, seed=11)
-    D = _device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     reserve_and_upload(D, ncells, idx, w, series, months=(11, 0))
     D.aerosol_deposition(11, 0, 0.3, 0.7)
     first = D["aer_bcphi"]
@@ -360,19 +357,10 @@ def test_refusals_enqueue_nothing(base, mapped, flagged):
     assert lib.elmk_run(ctx, DT, P(sa), int(sa.size), 16) == -1  # the next flag bit does not exist
     valid_run_still_gives_the_bits("bad run")
     # a stream being captured
-    hip = _hip_runtime()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    B.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rcs = [lib.elmk_aerosol_reserve(ctx, ncells, 3, P(idx), P(w)), lib.elmk_aerosol_upload(ctx, fid, 0, 1, P(month)),
-           lib.elmk_aerosol_deposition(ctx, 0, 1, 0.5, 0.5), lib.elmk_aerosol_clear(ctx), run_flagged()]
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    with captured(B):
+        rcs = [lib.elmk_aerosol_reserve(ctx, ncells, 3, P(idx), P(w)), lib.elmk_aerosol_upload(ctx, fid, 0, 1, P(month)),
+               lib.elmk_aerosol_deposition(ctx, 0, 1, 0.5, 0.5), lib.elmk_aerosol_clear(ctx), run_flagged()]
     assert rcs == [-1] * 5, rcs
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    B.set_stream(None)
-    hip.hipStreamDestroy(strm)
     assert B.device_bytes == bytes1
     valid_run_still_gives_the_bits("stream being captured")
 
@@ -423,41 +411,9 @@ def test_refusals_enqueue_nothing(base, mapped, flagged):
 # ---- 7. the demo ----------------------------------------------------------------------------------------------------------------------
 def test_aerosol_demo(tmp_path):
     """examples/aerosol_demo.cc builds against the C ABI and runs 48 steps across a month boundary against the stepwise loop."""
-    from tests import helpers as H
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     n = 320
     cols, scal, soil, lat, lon, rec = _inputs(n, SEED, nrec=25)
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "aerosol_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "aerosol_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    for i, k in enumerate(("age_tau", "age_kappa", "age_drdt0")):
-        put(k, 1, S.snowage[i])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in SERIES:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
-    put("steps", 1, schedule(48))
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(tmp_path / "state.bin")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    exe = build_demo("aerosol_demo", tmp_path)
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, demo_records(lat, lon, rec) + [("steps", schedule(48))]))
+    r = run_demo(exe, tmp_path / "state.bin")
     assert "bit-identical" in r.stdout and "mss_dst1 of column" in r.stdout, r.stdout

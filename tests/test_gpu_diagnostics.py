@@ -17,7 +17,9 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import diagnostics as dg
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
-from tests import test_gpu_run as GR
+from tests import helpers as H
+from tests import run_cases as GR
+from tests.support import words_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +32,11 @@ SIZES = [1, 63, 255, 256, 257, 20000, T - 1, T, T + 1, 2 * T + 5]
 SEEDS = {1: 1, 63: 11, 255: 1, 256: 5, 257: 13, 20000: 1, T - 1: 3, T: 6, T + 1: 3, 2 * T + 5: 4}  # see order_is_visible
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
 def same_triples(got, want):
     """64-bit patterns; any NaN equals any NaN; a min or max that is a zero compares by value (the sign of a zero extreme is the one
     met first in the device's order, which the restatement shares but no caller should lean on)."""
     got, want = np.asarray(got), np.asarray(want)
-    ok = (bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))
+    ok = (words_f64(got) == words_f64(want)) | (np.isnan(got) & np.isnan(want))
     zero = (got == 0.0) & (want == 0.0)
     zero[..., 2] = False  # the sum's bits count, zero or not
     return bool((ok | zero).all())
@@ -90,7 +88,7 @@ def order_is_visible(cols):
     none does: a device sum in one of those orders could not pass in any of the three."""
     want = restated(cols)
     others = (np.sum, lambda x: np.cumsum(x)[-1], lambda x: np.cumsum(x[::-1])[-1])
-    return all(bits(want[k, 2])[0] != bits(f(cols[:, k]))[0] for k in (0, 4, 5) for f in others)
+    return all(words_f64(want[k, 2])[0] != words_f64(f(cols[:, k]))[0] for k in (0, 4, 5) for f in others)
 
 
 def _state(n, v, lib_path=None):
@@ -126,7 +124,7 @@ def test_triples_equal_the_restatement_fp32_state_library():
 
 
 def _stepwise_columns(D, rec, steps):
-    """tests/test_gpu_run.py's stepwise loop, keeping every step's per-column diagnostics and err_flags."""
+    """tests/run_cases.py's stepwise loop, keeping every step's per-column diagnostics and err_flags."""
     cons, cols, flags = [], [], []
     for p in steps:
         D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
@@ -151,8 +149,8 @@ def test_run_rows_equal_the_restatement():
     restatement of that step's per-column values, which the stepwise calls of the same steps give."""
     n = T + 1
     cols, scal, soil, lat, lon, rec = GR._inputs(n, 75, nrec=4)
-    A = GR._device(cols, scal, soil, lat, lon)
-    B = GR._device(cols, scal, soil, lat, lon)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     steps = GR.schedule(3)
     cons, percol, _ = _stepwise_columns(A, rec, steps)
     B.run_reserve(4, 3)
@@ -164,7 +162,7 @@ def test_run_rows_equal_the_restatement():
         want = restated(percol[s])
         assert same_triples(rows[s], want), (s, rows[s].tolist(), want.tolist())
         assert same_triples(cons[s], want), s
-        assert any(bits(want[k, 2]) != bits(np.sum(percol[s][:, k])) for k in range(8)), s  # the order shows in physical values too
+        assert any(words_f64(want[k, 2]) != words_f64(np.sum(percol[s][:, k])) for k in range(8)), s  # the order shows in physical values too
     assert len({rows[s, 6, 2] for s in range(3)}) == 3  # the steps differ
     A.close()
     B.close()
@@ -287,8 +285,8 @@ def test_run_rows_of_the_error_summary():
     cols, scal, soil, lat, lon, rec = GR._inputs(n, 76, nrec=6, tier="A")
     snowy = synth.make_state(st.field_table(), n, tier="B", seed=76)[0]
     j = int(np.nonzero(snowy["snl"] == 1)[0][0])
-    A = GR._device(cols, scal, soil, lat, lon)
-    B = GR._device(cols, scal, soil, lat, lon)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     steps = GR.schedule(8)
     B.run_reserve(6, 4)
     GR.upload_series(B, rec)

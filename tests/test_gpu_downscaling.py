@@ -3,28 +3,22 @@ bits of OFF, elmk_get_forcing in TOPO mode against elmkernels_amd/downscale.py (
 stepwise calls (per-column series and a forcing grid, graph on and off), the physical properties of the adjusted fields, the snow a
 mountain column keeps, the refusals, an exact restart and the demo."""
 import ctypes as C
-import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from elmkernels_amd import _lib as L
 from elmkernels_amd import downscale as DSC
 from elmkernels_amd import regrid as RG
 from elmkernels_amd import state as st
 from tests import helpers as H
-from tests import test_gpu_run as GR
+from tests import run_cases as GR
+from tests.support import build_demo, captured, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
 
 DT = GR.DT
-ROOT = GR.ROOT
 NSTEPS = 24
 NREC = NSTEPS // 2 + 1  # GR.schedule: slot s // 2
-same = GR.same
 DS_FIELDS = ("forc_tbot", "forc_thbot", "forc_pbot", "forc_qbot", "forc_lwrad", "forc_rain", "forc_snow")
 KEPT_FIELDS = ("forc_solad", "forc_solai", "forc_u", "forc_v", "forc_hgt", "forc_hgt_u_patch", "forc_hgt_t_patch", "forc_hgt_q_patch")
 NLON, NLAT = 64, 32
@@ -73,7 +67,7 @@ def _forcing(D):
 
 def _topo_device(base, hc, hf, groups=None, graph=False, mode="topo"):
     cols, scal, soil, lat, lon, rec = base
-    D = GR._device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     D.set_graph(graph)
     D.set_column_elevation(hc, hf)
     if groups is not None:
@@ -125,7 +119,7 @@ def test_stepwise_matches_the_host_restatement(base, grid, rh, sw, groups):
     n = cols["t_grnd"].shape[0]
     rng = np.random.default_rng(17)
     hc, hf = _elevations(n, 18)
-    D = GR._device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     if grid:
         ncells = NLON * NLAT
         idx, w = RG.bilinear_map(np.degrees(lat), np.degrees(lon), NLON, NLAT)
@@ -198,7 +192,7 @@ def test_run_equals_stepwise(base, grid, graph):
             rec_cols[k] = RG.apply_map(idx, w, cells[k])
         A = _topo_device(base, hc, RG.apply_map(idx, w, hcells), G, graph)
         want = GR.stepwise(A, rec_cols, steps)
-        B = GR._device(cols, scal, soil, lat, lon)
+        B = H.device_state(cols, scal, soil, lat=lat, lon=lon)
         B.set_graph(graph)
         B.set_forcing_grid(idx, w, ncells)
         B.set_column_elevation(hc)
@@ -228,7 +222,7 @@ def test_physical_properties(base):
     hc, hf = _elevations(n, 31)
     G = _groups(n, 32)
     lapse, lapse_lw, lw_limit = 0.0065, 0.05, 0.3
-    D = GR._device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     D.set_column_elevation(hc, hf)
     for k in st.SERIES_FORCING:
         D.upload(k, np.stack([rec[k][0], rec[k][1]], axis=1))
@@ -303,10 +297,6 @@ def test_mountain_columns_keep_more_snow():
     assert (h[mountain] > h[valley]).all() and (h[mountain] > out["off"][mountain]).all(), (h[valley][:3], h[mountain][:3])
 
 
-def _hip():
-    return GR._hip_runtime()
-
-
 def test_refusals_enqueue_nothing(base):
     """Every refusal is ELMK_E_INVALID and leaves the context as a twin that made only the valid calls: the same forcing bits after a
     TOPO step and the same device bytes.  A context that never downscales allocates nothing more."""
@@ -314,8 +304,8 @@ def test_refusals_enqueue_nothing(base):
     n = cols["t_grnd"].shape[0]
     hc, hf = _elevations(n, 41)
     G = _groups(n, 42)
-    A = GR._device(cols, scal, soil, lat, lon)  # refusals
-    B = GR._device(cols, scal, soil, lat, lon)  # twin
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)  # refusals
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon)  # twin
     bytes0 = A.device_bytes
 
     def P(a):
@@ -371,22 +361,13 @@ def test_refusals_enqueue_nothing(base):
     # valid calls, then refusals under capture of each setter
     A.set_downscaling_groups(*G)
     A.set_downscaling("topo", 0.0065, 0.04, 0.4)
-    hip = _hip()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    A.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    refused = [rc("elmk_set_column_elevation", P(hf), P(hc)) == -1,
-               rc("elmk_set_downscaling", 0, *good) == -1,
-               rc("elmk_set_downscaling_groups", C.c_int64(1), P(np.array([0, 1], np.int64)), P(np.array([0], np.int32)), P(np.ones(1))) == -1,
-               rc("elmk_clear_downscaling_groups") == -1,
-               rc("elmk_download_column_elevation", P(np.zeros(n)), None) == -1]
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    with captured(A):
+        refused = [rc("elmk_set_column_elevation", P(hf), P(hc)) == -1,
+                   rc("elmk_set_downscaling", 0, *good) == -1,
+                   rc("elmk_set_downscaling_groups", C.c_int64(1), P(np.array([0, 1], np.int64)), P(np.array([0], np.int32)), P(np.ones(1))) == -1,
+                   rc("elmk_clear_downscaling_groups") == -1,
+                   rc("elmk_download_column_elevation", P(np.zeros(n)), None) == -1]
     assert all(refused), refused
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    A.set_stream(None)
-    hip.hipStreamDestroy(strm)
     # the twin
     B.set_column_elevation(hc, hf)
     B.set_downscaling_groups(*G)
@@ -406,7 +387,6 @@ def test_refusals_enqueue_nothing(base):
 def test_exact_restart_in_topo_mode(base):
     """N steps, save, load into a fresh context with the same downscaling setup, N steps: the bits of 2N steps."""
     from elmkernels_amd import restart as RS
-    from tests.test_gpu_restart import _poison
 
     cols, scal, soil, lat, lon, rec = base
     n = cols["t_grnd"].shape[0]
@@ -425,9 +405,9 @@ def test_exact_restart_in_topo_mode(base):
     img = B.restart_save()
     B.close()
     RS.verify(img)
-    Cx = GR._device(cols, scal, soil, lat, lon)
+    Cx = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     Cx.set_graph(True)
-    _poison(Cx)
+    GR.poison(Cx)
     Cx.set_column_elevation(hc, hf)
     Cx.set_downscaling_groups(*G)
     Cx.set_downscaling("topo")
@@ -445,43 +425,11 @@ def test_exact_restart_in_topo_mode(base):
 def test_downscaling_demo(tmp_path):
     """examples/downscaling_demo.cc compiles with g++ against the C ABI and runs a day of valley and mountain columns in one forcing
     cell: with downscaling OFF they end alike, in TOPO mode the mountain is colder and keeps more snow."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "downscaling_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "downscaling_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
+    exe = build_demo("downscaling_demo", tmp_path)
     n = 512
     (cols, scal, soil, lat, lon, rec), hc, hf = _snow_case(n, 311)
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    put("age_tau", 1, S.snowage[0])
-    put("age_kappa", 1, S.snowage[1])
-    put("age_drdt0", 1, S.snowage[2])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in GR.SERIES:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
-    put("topo", 1, hc)
-    put("hf", 1, hf[:1])
-    put("steps", 1, GR.schedule(48))
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    out = subprocess.run([exe, str(tmp_path / "state.bin")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
+    extra = GR.demo_records(lat, lon, rec) + [("topo", hc), ("hf", hf[:1]), ("steps", GR.schedule(48))]
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, extra))
+    out = run_demo(exe, tmp_path / "state.bin")
     print(out.stdout)
     assert "off: valley and mountain alike" in out.stdout and "topo: more snow on the mountain" in out.stdout, out.stdout

@@ -2,10 +2,6 @@
 on the host by regrid.apply_map and sent per column through the existing calls - elmk_upload for the stepwise path, per-column series
 for elmk_run."""
 import ctypes as C
-import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,19 +9,19 @@ import pytest
 from elmkernels_amd import _lib as L
 from elmkernels_amd import regrid as RG
 from elmkernels_amd import state as st
-from tests import test_gpu_run as GR
+from tests import helpers as H
+from tests import run_cases as GR
+from tests.support import build_demo, captured, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
 
 DT, NREC, NSTEPS = GR.DT, GR.NREC, GR.NSTEPS
-ROOT = GR.ROOT
 NLON, NLAT = 64, 32
 NCELLS = NLON * NLAT
-same = GR.same
 
 
 def _cell_records(ncells, seed, nrec=NREC):
-    """Forcing records on the cells, [nrec, ncells] per atm_* stream, with the ranges and branches of test_gpu_run's records."""
+    """Forcing records on the cells, [nrec, ncells] per atm_* stream, with the ranges and branches of run_cases' records."""
     return {k: v for k, v in GR._inputs(ncells, seed, nrec=nrec)[-1].items() if k in st.SERIES_FORCING}
 
 
@@ -97,8 +93,8 @@ def test_upload_gridded_equals_upload_of_the_host_remap(base, lib):
     """Both levels of every atm_*, an aer_* field and one level of a multi-level field."""
     cols, scal, soil, lat, lon, rec, cells = base
     path = L.F32_LIB_PATH if lib == "f32" else None
-    A = GR._device(cols, scal, soil, lat, lon, path)
-    B = GR._device(cols, scal, soil, lat, lon, path)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=path)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=path)
     idx, w = _map("bilinear_land", lat, lon, 3)
     B.set_forcing_grid(idx, w, NCELLS)
     rng = np.random.default_rng(83)
@@ -122,8 +118,8 @@ def test_twelve_stepwise_steps_with_gridded_uploads(base):
     """The stepwise driver's path: 12 steps whose forcing goes up with upload_gridded equal 12 steps whose forcing goes up as the host
     remap, in every field."""
     cols, scal, soil, lat, lon, rec, cells = base
-    A = GR._device(cols, scal, soil, lat, lon)
-    B = GR._device(cols, scal, soil, lat, lon)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     idx, w = _map("bilinear", lat, lon)
     B.set_forcing_grid(idx, w, NCELLS)
     rec_cols = _column_records(idx, w, cells, rec)
@@ -197,8 +193,8 @@ def test_large_launch_grid_run():
     """262 144 columns (the benchmark's launch structure), bilinear map, three steps."""
     cols, scal, soil, lat, lon, rec = GR._inputs(262144, 84)
     cells = _cell_records(NCELLS, 85)
-    A = GR._device(cols, scal, soil, lat, lon)
-    B = GR._device(cols, scal, soil, lat, lon)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     for D in (A, B):
         D.set_graph(True)
     idx, w = _map("bilinear", lat, lon)
@@ -260,21 +256,12 @@ def test_refusals_enqueue_nothing(base):
         assert lib.elmk_upload_gridded(ctx, f, lev, cells["atm_tbot"][0].ctypes.data_as(C.c_void_p)) == -1, what
         still_gives_the_bits(what)
     # a stream being captured: set, clear and upload_gridded refuse
-    hip = GR._hip_runtime()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    B.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rcs = [lib.elmk_set_forcing_grid(ctx, NCELLS, idx.shape[0], np.ascontiguousarray(idx, np.int32).ctypes.data_as(C.c_void_p),
-                                     np.ascontiguousarray(w).ctypes.data_as(C.c_void_p)),
-           lib.elmk_clear_forcing_grid(ctx),
-           lib.elmk_upload_gridded(ctx, B.fields["atm_tbot"][0], 0, cells["atm_tbot"][0].ctypes.data_as(C.c_void_p))]
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    with captured(B):
+        rcs = [lib.elmk_set_forcing_grid(ctx, NCELLS, idx.shape[0], np.ascontiguousarray(idx, np.int32).ctypes.data_as(C.c_void_p),
+                                         np.ascontiguousarray(w).ctypes.data_as(C.c_void_p)),
+               lib.elmk_clear_forcing_grid(ctx),
+               lib.elmk_upload_gridded(ctx, B.fields["atm_tbot"][0], 0, cells["atm_tbot"][0].ctypes.data_as(C.c_void_p))]
     assert rcs == [-1, -1, -1]
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    B.set_stream(None)
-    hip.hipStreamDestroy(strm)
     still_gives_the_bits("stream being captured")
     # a non-finite weight behind padding is accepted (never read), and the run still gives the bits
     ww = w.copy()
@@ -321,7 +308,7 @@ def test_set_and_clear_release_the_reservation(base):
 
 def test_device_bytes_account_for_the_map_and_the_cell_series(base):
     cols, scal, soil, lat, lon, rec, cells = base
-    D = GR._device(*base[:5])
+    D = GR.device(base)
     ld, es = D.level_stride, D.lib.elmk_state_real_bytes()
 
     def al(b):
@@ -348,8 +335,8 @@ def test_fp32_build_nearest_map_is_bitwise():
     equals the per-column run bit for bit."""
     cols, scal, soil, lat, lon, rec = GR._inputs(2053, 86)
     cells = _cell_records(NCELLS, 87)
-    A = GR._device(cols, scal, soil, lat, lon, L.F32_LIB_PATH)
-    B = GR._device(cols, scal, soil, lat, lon, L.F32_LIB_PATH)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=L.F32_LIB_PATH)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=L.F32_LIB_PATH)
     assert B.lib.elmk_state_real_bytes() == 4
     idx, w = _map("nearest", lat, lon)
     steps = GR.schedule()
@@ -363,55 +350,20 @@ def test_fp32_build_nearest_map_is_bitwise():
 def test_forcing_grid_demo(tmp_path):
     """examples/forcing_grid_demo.cc: a global grid of columns forced from 64 x 32 cells for a day of 48 steps as two runs; its
     PrimaryVars and conservation rows equal the Python layer's stepwise run with upload_gridded."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     n, nsteps, nrec = 3008, 48, 25
     cols, scal, soil, lat, lon, rec = GR._inputs(n, 88, nrec=nrec)
     cells = _cell_records(NCELLS, 89, nrec=nrec)
     steps = GR.schedule(nsteps)
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "forcing_grid_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "forcing_grid_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir,
-                           "-o", exe])
-    from tests import helpers as H
-
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    put("age_tau", 1, S.snowage[0])
-    put("age_kappa", 1, S.snowage[1])
-    put("age_drdt0", 1, S.snowage[2])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in st.SERIES_FORCING:
-        put(f"cells/{k}", 1, np.ascontiguousarray(cells[k], np.float64))
-    for k in st.SERIES_PHENOLOGY:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
+    exe = build_demo("forcing_grid_demo", tmp_path)
     idx, w = _map("bilinear", lat, lon)
-    put("map/idx", 1, idx.astype(np.int32))
-    put("map/w", 1, w)
-    put("steps", 1, steps)
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(tmp_path / "state.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    extra = [("lat", lat), ("lon", lon)] + [(f"cells/{k}", np.ascontiguousarray(cells[k], np.float64)) for k in st.SERIES_FORCING]
+    extra += [(f"series/{k}", np.ascontiguousarray(rec[k], np.float64)) for k in st.SERIES_PHENOLOGY]
+    extra += [("map/idx", idx.astype(np.int32)), ("map/w", w), ("steps", steps)]
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, extra))
+    r = run_demo(exe, tmp_path / "state.bin", tmp_path / "out.bin")
     assert "48 steps" in r.stdout and "2048 forcing cells (4 terms per column)" in r.stdout, r.stdout
     # the same steps through the Python layer, stepwise with upload_gridded
-    D = GR._device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     D.set_graph(True)
     D.set_forcing_grid(idx, w, NCELLS)
     cons = []

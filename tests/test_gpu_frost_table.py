@@ -11,26 +11,14 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import hydrology as hy
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
-from tests.test_frost_table_host import FROST_BRANCHES, Count, add_frost, generated_frost
-from tests.test_gpu_hydrology import _new, _physics, _stepwise
-from tests.test_gpu_run import DT, NREC, ROOT, SERIES, _device, _hip_runtime, _inputs, same, schedule, upload_series
-from tests.test_hydrology_host import BRANCHES, CHAIN_STEPS, clear_snow, prepare
+from tests.hydrology_cases import (BRANCHES, CHAIN_STEPS, FROST_BRANCHES, Count, _new, _new_frost, _physics, _stepwise, add_frost, clear_snow,
+                                   generated_frost, prepare)
+from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, upload_series
+from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
 
 STEP_FIELDS = hy.READS + ("h2osoi_vol", "t_soisno")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-def _new_frost(cols, scal, soil, rows, frost, lib_path=None, lat=None, lon=None):
-    D = _new(cols, scal, soil, rows, lib_path, lat, lon)
-    before = D.device_bytes
-    D.soil_hydrology_frost_enable(frost[hy.Q_PERCH_MAX])
-    assert D.device_bytes - before == hy.FROST_NROWS * 8 * D.level_stride
-    return D
 
 
 def _host_step(D, hit=None, lib_path=None, frost=True):
@@ -115,7 +103,7 @@ def base():
 def _context(base, graph, lib_path=None, frost=True, hydrology=True):
     b, rows, fr = base
     if not hydrology:
-        D = _device(*b[:5], lib_path)
+        D = device(b, lib_path=lib_path)
     elif frost:
         D = _new_frost(b[0], b[1], b[2], rows, fr, lib_path, b[3], b[4])
     else:
@@ -256,18 +244,10 @@ def test_refusals_change_nothing(base):
             call()
     unchanged(before, state(True))
     # a stream being captured: enable is refused
-    hip = _hip_runtime()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
     buf = np.zeros(NCOL)
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rcs = [D.lib.elmk_soil_hydrology_frost_enable(D.ctx, q.ctypes.data_as(C.c_void_p))]
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    with captured(D):
+        rcs = [D.lib.elmk_soil_hydrology_frost_enable(D.ctx, q.ctypes.data_as(C.c_void_p))]
     assert rcs == [-1]  # ELMK_E_INVALID
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    D.set_stream(None)
     unchanged(before, state(True))
     D.soil_hydrology_frost_enable(q)
     assert D.device_bytes - before[1] == hy.FROST_NROWS * 8 * D.level_stride and D.restart_size() == before[2]
@@ -280,18 +260,11 @@ def test_refusals_change_nothing(base):
         with pytest.raises(L.ElmkError):
             call()
     # a stream being captured: read, clear, enable and the hydrology's clear are refused
-    graph = C.c_void_p()
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rcs = [D.lib.elmk_soil_hydrology_frost_read(D.ctx, hy.FROST_TABLE, buf.ctypes.data_as(C.c_void_p), 0, NCOL),
-           D.lib.elmk_soil_hydrology_frost_clear(D.ctx), D.lib.elmk_soil_hydrology_frost_enable(D.ctx, q.ctypes.data_as(C.c_void_p)),
-           D.lib.elmk_soil_hydrology_clear(D.ctx)]
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    with captured(D):
+        rcs = [D.lib.elmk_soil_hydrology_frost_read(D.ctx, hy.FROST_TABLE, buf.ctypes.data_as(C.c_void_p), 0, NCOL),
+               D.lib.elmk_soil_hydrology_frost_clear(D.ctx), D.lib.elmk_soil_hydrology_frost_enable(D.ctx, q.ctypes.data_as(C.c_void_p)),
+               D.lib.elmk_soil_hydrology_clear(D.ctx)]
     assert rcs == [-1] * 4, rcs
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(strm)
     unchanged(before, state(True))
     assert bits(D.soil_hydrology_frost_rows()) == bits(f0)
     D.close()
@@ -301,7 +274,7 @@ def test_accounting_and_a_cleared_context(base):
     """Enable adds exactly 4 x 8 x level_stride bytes and clear returns them; elmk_soil_hydrology_clear returns both sets; and a context
     that enabled and cleared the extension gives, in the next step, the bits of hydrology.step without `frost`."""
     b, rows, frost = base
-    plain = _device(*b[:5])
+    plain = device(b)
     bytes0 = plain.device_bytes
     plain.close()
     D = _new(b[0], b[1], b[2], rows, None, b[3], b[4])
@@ -340,19 +313,7 @@ def test_accounting_and_a_cleared_context(base):
 def test_permafrost_hydrology_demo(tmp_path):
     """examples/permafrost_hydrology_demo.cc builds and runs: four steps on five columns, finite values, the thaw depth and the perched
     table at or above the frost table, perched drainage in some column of every step."""
-    import os
-    import shutil
-    import subprocess
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "permafrost_hydrology_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "permafrost_hydrology_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir,
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_demo(build_demo("permafrost_hydrology_demo", tmp_path), timeout=120)
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 2 + 4 * 5 and "permafrost hydrology, 4 steps" in lines[0]
     v = np.array([[float(x) for x in ln.split()] for ln in lines[2:]])

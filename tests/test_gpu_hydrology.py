@@ -11,30 +11,14 @@ from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests.parity_cases import WETLAND
-from tests.test_gpu_run import DT, NREC, SERIES, _device, _inputs, same, schedule, stepwise, upload_series
-from tests.test_hydrology_host import (BRANCHES, CHAIN_STEPS, CLOSURE_BOUND, CLOSURE_FIELDS, CLOSURE_MEASURED, clear_snow, closure, generated,
-                                       host_chain, prepare)
+from tests.hydrology_cases import (BRANCHES, CHAIN_STEPS, CLOSURE_BOUND, CLOSURE_FIELDS, CLOSURE_MEASURED, _new, _physics, _stepwise, clear_snow,
+                                   closure, generated, host_chain, prepare)
+from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, stepwise, upload_series
+from tests.support import bits, build_demo, run_demo
 
 pytestmark = pytest.mark.gpu
 
 STEP_FIELDS = hy.READS + ("h2osoi_vol",)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
-
-
-def _new(cols, scal, soil, rows, lib_path=None, lat=None, lon=None):
-    n = rows.shape[1]
-    if lat is None:
-        lat, lon = synth.global_grid(n, seed=9)
-    D = _device(cols, scal, soil, lat, lon, lib_path)
-    before = D.device_bytes
-    D.soil_hydrology_enable()
-    assert D.device_bytes - before == hy.NROWS * 8 * D.level_stride
-    D.soil_hydrology_set_params(rows[hy.HKSAT:hy.HKSAT + hy.N], rows[hy.WTFACT], rows[hy.H2OSFC_THRESH], rows[hy.K_WET], rows[hy.RSUB_TOP_MAX])
-    D.soil_hydrology_init(rows[hy.ZWT], rows[hy.WA])
-    return D
 
 
 def _host_step(D, hit=None, lib_path=None):
@@ -91,11 +75,6 @@ def chain_inputs():
     return generated(1001, 77, full=True, chain=True)
 
 
-def _physics(D):
-    st.kokkos_init_timestep(D)
-    st.advance_physics(D, DT)
-
-
 @pytest.mark.parametrize("lib_path", [None, L.F32_LIB_PATH], ids=["f64", "f32"])
 def test_six_step_chain_equals_the_restatement(chain_inputs, lib_path):
     """elmk_advance_physics, then the stage, six times: after every stage the device against hydrology.step on what the device held
@@ -121,7 +100,7 @@ def test_closure_of_the_water_budget(chain_inputs):
     cols, scal, soil, rows = chain_inputs
     _, _, host = host_chain(cols, scal, soil, rows)
     D = _new(cols, scal, soil, rows)
-    P = _device(cols, scal, soil, *synth.global_grid(rows.shape[1], seed=9))
+    P = device((cols, scal, soil, *synth.global_grid(rows.shape[1], seed=9)))
     assert CLOSURE_BOUND == 10.0 * CLOSURE_MEASURED
     for s in range(CHAIN_STEPS):
         wa_beg = D.soil_hydrology_read(hy.WA)
@@ -160,33 +139,11 @@ def base():
 
 def _context(base, graph, lib_path=None, enable=True):
     b, rows = base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4]) if enable else _device(*b[:5], lib_path)
+    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4]) if enable else device(b, lib_path=lib_path)
     D.set_graph(graph)
     D.run_reserve(NREC, 2 * NSTEPS)
     upload_series(D, b[5])
     return D
-
-
-def _stepwise(D, rec, steps):
-    """test_gpu_run.stepwise with the stage between the physics and the conservation row."""
-    cons, fo, fb = [], [], []
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        cons.append(st.kokkos_evaluate_conservation(D, DT))
-        flags, first = D.error_summary()
-        fo.append(flags)
-        fb.append(first)
-    return np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)
 
 
 def _snapshot(D, rows=True):
@@ -399,20 +356,7 @@ def test_restart_says_which_feature_differs(base):
 # ---- the demo ---------------------------------------------------------------------------------------------------------------------
 def test_soil_hydrology_demo(tmp_path):
     """examples/soil_hydrology_demo.cc builds and runs: a day of rain on six columns, the budget of the stores closed."""
-    import os
-    import shutil
-    import subprocess
-
-    from tests.test_gpu_run import ROOT
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "soil_hydrology_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "soil_hydrology_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_demo(build_demo("soil_hydrology_demo", tmp_path), timeout=120)
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 8 and "soil hydrology, 48 steps" in lines[0]
     soil0, soil1 = (np.array([float(ln.split()[i]) for ln in lines[2:]]) for i in (3, 4))

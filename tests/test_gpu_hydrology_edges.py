@@ -1,4 +1,4 @@
-"""Soil hydrology on the device on the edge tier (tests/test_hydrology_host.py: edge_columns): k_soil_hydrology<false> and <true> against
+"""Soil hydrology on the device on the edge tier (tests/hydrology_cases.py: edge_columns): k_soil_hydrology<false> and <true> against
 the host restatement (elmkernels_amd/hydrology.py: step) in both builds.  Every written field and every row bit for bit, where both
 sides hold a NaN that counts as equal (the rows are canonical on both sides; a NaN of a state field keeps whatever sign and payload
 the arithmetic gave it); every other field untouched.  The comparison is per column, and a third of the columns hold a NaN or an
@@ -15,10 +15,8 @@ from elmkernels_amd import hydrology as hy
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests import parity_cases as P
-from tests.test_gpu_frost_table import _new_frost
-from tests.test_gpu_hydrology import _new, _stepwise
-from tests.test_gpu_run import DT, NREC, SERIES, _inputs, same, schedule, upload_series
-from tests.test_hydrology_host import EDGE_CLASS_NAMES, edge_columns, prepare
+from tests.hydrology_cases import EDGE_CLASS_NAMES, _new, _new_frost, _stepwise, edge_columns, prepare
+from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
 
 pytestmark = pytest.mark.gpu
 

@@ -3,9 +3,6 @@ both builds, after elmk_timestep7 and after elmk_timestep7_fused, over fifty cha
 the split step with the stage in it against elmk_advance_physics; the stage inside elmk_run against the stepwise calls, graph on and
 off, with the closed water budget taking the term; exact restarts with a QIRRIG tape; every refusal; the demo."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,20 +13,16 @@ from elmkernels_amd import irrigation as ir
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
+from tests import helpers as H
+from tests.hydrology_cases import _new, clear_snow, prepare
+from tests.irrigation_cases import CHAIN_STEPS, chain_tod, generated, smpso_of
 from tests.parity_cases import WETLAND
-from tests.test_gpu_history import _hip_runtime
-from tests.test_gpu_hydrology import _new
-from tests.test_gpu_run import DT, NREC, ROOT, SERIES, _device, _inputs, same, schedule, upload_series
-from tests.test_hydrology_host import clear_snow, prepare
-from tests.test_irrigation_host import CHAIN_STEPS, chain_tod, generated, smpso_of
+from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, upload_series
+from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
 
 WB_FIELDS = hy.WB_READS + ("dtbegin_column_h2o",)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def _enable(D, sched):
@@ -50,7 +43,7 @@ def test_fifty_chained_steps_equal_the_restatement(n, lib_path, fused):
     (tests/test_irrigation_host.py shows the same on the CPU); one column is an irrigated one that checks and applies."""
     cols, scal, soil, sched = generated(n, 900)
     lat, lon = synth.global_grid(n, seed=9)
-    D = _device(cols, scal, soil, lat, lon, lib_path)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=lib_path)
     _enable(D, sched)
     assert n == 1 or D.level_stride != n
     smpso = smpso_of(cols["vtype"])
@@ -85,34 +78,18 @@ def test_the_stage_replays_from_a_captured_graph():
     """elmk_irrigation captured once on a caller's stream and replayed: every replay is one step (the rows live on the device)."""
     n = 193
     cols, scal, soil, _ = generated(n, 900)
-    D = _device(cols, scal, soil, *synth.global_grid(n, seed=9))
+    D = device((cols, scal, soil, *synth.global_grid(n, seed=9)))
     _enable(D, np.full(n, -1, np.int32))  # (no column checks: the replays only apply)
     st.timestep7_fused(D, DT)
     rate = np.full(n, 2.0e-4)
     D.irrigation_init(rate, np.full(n, 5.0))
     D.sync()
-    hip = _hip_runtime()
-    P = C.c_void_p
-    for name, args in (("hipGraphInstantiate", [C.POINTER(P), P, P, P, C.c_size_t]), ("hipGraphLaunch", [P, P]), ("hipGraphExecDestroy", [P]),
-                       ("hipStreamSynchronize", [P])):
-        getattr(hip, name).argtypes = args
-        getattr(hip, name).restype = C.c_int
-    strm, graph, ex = P(), P(), P()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    D.irrigation(DT, 12 * 3600)
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
-    assert (D.irrigation_read(ir.NLEFT) == 5.0).all()  # captured, not run
-    assert hip.hipGraphInstantiate(C.byref(ex), graph, None, None, 0) == 0
-    for _ in range(3):
-        assert hip.hipGraphLaunch(ex, strm) == 0
-    assert hip.hipStreamSynchronize(strm) == 0
-    assert (D.irrigation_read(ir.NLEFT) == 2.0).all() and bits(D.irrigation_read(ir.QFLX_IRRIG)) == bits(rate)
-    hip.hipGraphExecDestroy(ex)
-    hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(strm)
+    with captured(D) as cap:
+        D.irrigation(DT, 12 * 3600)
+        cap.end()
+        assert (D.irrigation_read(ir.NLEFT) == 5.0).all()  # captured, not run
+        cap.replay(3)
+        assert (D.irrigation_read(ir.NLEFT) == 2.0).all() and bits(D.irrigation_read(ir.QFLX_IRRIG)) == bits(rate)
     D.close()
 
 
@@ -122,7 +99,7 @@ def test_the_split_step_without_irrigated_columns_is_advance_physics(lib_path):
     n = 600
     cols, scal, soil, _ = generated(n, 901)
     lat, lon = synth.global_grid(n, seed=9)
-    A, B = _device(cols, scal, soil, lat, lon, lib_path), _device(cols, scal, soil, lat, lon, lib_path)
+    A, B = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=lib_path), H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=lib_path)
     _enable(B, np.full(n, -1, np.int32))
     B.irrigation_init(np.full(n, 1.0e-3), None)  # a rate without a window is never applied
     for s in range(3):
@@ -363,19 +340,11 @@ def test_refusals_change_nothing(base):
     assert D.device_bytes == bytes0 and D.restart_size() == size0
     _assert_same(_snapshot(D, irrig=False), before)
     # a stream being captured
-    hip = _hip_runtime()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    s32 = np.ascontiguousarray(sched, dtype=np.int32)
-    rc = D.lib.elmk_irrigation_enable(D.ctx, s32.ctypes.data_as(C.c_void_p))
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
-    assert rc == -1 and D.device_bytes == bytes0
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(strm)
+    with captured(D) as cap:
+        s32 = np.ascontiguousarray(sched, dtype=np.int32)
+        rc = D.lib.elmk_irrigation_enable(D.ctx, s32.ctypes.data_as(C.c_void_p))
+        cap.end()
+        assert rc == -1 and D.device_bytes == bytes0
 
     _enable(D, sched)
     bytes1, size1 = D.device_bytes, D.restart_size()
@@ -422,14 +391,7 @@ def test_refusals_change_nothing(base):
 def test_irrigation_demo(tmp_path):
     """examples/irrigation_demo.cc builds with g++ against the C ABI and runs: on the first morning the check sets a rate and NLEFT counts
     down from 8 while QIRRIG is applied; on the second morning the column is unstressed."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "irrigation_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "irrigation_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_demo(build_demo("irrigation_demo", tmp_path), timeout=120)
     lines = out.stdout.strip().splitlines()
     assert "irrigation, 96 steps" in lines[0] and lines[-1].startswith("applied to column 0:")
     steps = [ln.split() for ln in lines[2:-1]]

@@ -12,6 +12,7 @@ from elmkernels_amd.diagnostics import reduce_min_max_sum
 from tests import _parity_mode
 from tests import fixtures as F
 from tests import helpers as H
+from tests.support import build_demo, run_demo, state_blob
 
 pytestmark = pytest.mark.gpu
 
@@ -192,57 +193,15 @@ def test_cpp_interface_mirror(tmp_path):
     getPrimaryVars; elm_kokkos_interface.cc:38-358) - compiled with g++ against libelmk and run as the reference's driver
     loop (examples/elm_interface_demo.cc): three advance() steps (phenology, forcing, init_timestep, the ten physics calls
     as one HIP graph, conservation) give the oracle chain's PrimaryVars and conservation diagnostics bit for bit."""
-    import shutil
-    import struct
-    import subprocess
-
-    from elmkernels_amd import _lib as L
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     n, nsteps = 3008, 3
     D, S = _pair(n, "B", 33)
     D.close()
-    exe = tmp_path / "demo"
-    import os
-
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    libdir = os.path.dirname(L.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "elm_interface_demo.cc"), "-L" + libdir, "-lelmk",
-                           "-Wl,-rpath," + libdir, "-o", str(exe)])
+    exe = build_demo("elm_interface_demo", tmp_path)
     rng = np.random.default_rng(3)
     e = rng.random(8)
     wt1, wt2 = 1.0 - e, e
-    blob = [struct.pack("<q", n)]
-
-    def rec(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            rec(k, 0, v)
-    sc = S.scalars
-    rec("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    rec("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    rec("pft_psn", 1, S.pft_psn)
-    rec("pft_alb", 1, S.pft_alb)
-    rec("z0mr", 1, S.z0mr)
-    rec("displar", 1, S.displar)
-    rec("albsat", 1, S.albsat)
-    rec("albdry", 1, S.albdry)
-    for i, name in enumerate(L.SNICAR_NAMES):
-        rec(f"snicar/{i}", 1, S.snicar[name])
-    rec("age_tau", 1, S.snowage[0])
-    rec("age_kappa", 1, S.snowage[1])
-    rec("age_drdt0", 1, S.snowage[2])
-    rec("forc_wt1", 1, wt1)
-    rec("forc_wt2", 1, wt2)
-    rec("month_wt", 1, np.array([0.3, 0.7]))
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    out = subprocess.run([str(exe), str(tmp_path / "state.bin"), str(nsteps), str(tmp_path / "out.bin")], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr
+    (tmp_path / "state.bin").write_bytes(state_blob(S, DT, [("forc_wt1", wt1), ("forc_wt2", wt2), ("month_wt", np.array([0.3, 0.7]))]))
+    run_demo(exe, tmp_path / "state.bin", nsteps, tmp_path / "out.bin")
     for _ in range(nsteps):
         S.phenology(0.3, 0.7)
         S.get_forcing(wt1, wt2, False)

@@ -3,21 +3,19 @@ whose every field outside the image is poisoned, a load and N more steps - bit f
 the tape counts and the error summary; a change of column decomposition through restart.merge / restart.slice; the image's
 contents against elmk_download; every refusal of elmk_restart_load, each leaving the context as it was; and the matrix of the
 optional features: which image loads into which context."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from elmkernels_amd import _lib as L
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
-from tests.test_gpu_history import _hip_runtime
-from tests.test_gpu_run import DT, NREC, NSTEPS, _device, _inputs, same, schedule, stepwise, upload_series
+from tests import helpers as H
+from tests.run_cases import DT, IMAGE_CLASSES, NREC, NSTEPS, _inputs, demo_records, device, poison, schedule, stepwise, upload_series
+from tests.support import build_demo, captured, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
 
 N = NSTEPS // 2
-IMAGE_CLASSES = (st.CLASS_PROGNOSTIC, st.CLASS_SURFACE)
 
 
 @pytest.fixture(scope="module")
@@ -29,13 +27,6 @@ def _sub(base, c0, n):
     cols, scal, soil, lat, lon, rec = base
     return ({k: v[c0:c0 + n] for k, v in cols.items()}, scal, soil, lat[c0:c0 + n], lon[c0:c0 + n],
             {k: v[:, c0:c0 + n] for k, v in rec.items()})
-
-
-def _poison(D):
-    """Every field the image does not hold: NaN, or an out-of-the-way integer."""
-    for name, (fid, nlev, dt) in D.fields.items():
-        if st.field_class(name) not in IMAGE_CLASSES:
-            D.fill(name, np.nan if dt == np.float64 else 3.0)
 
 
 def _output_map(n, per=7):
@@ -78,10 +69,10 @@ def _assert_same(a, b, skip=()):
 
 
 def _fresh(base, gridded=True, graph=False, lib_path=None):
-    D = _device(*base[:5], lib_path=lib_path)
+    D = device(base, lib_path=lib_path)
     D.set_graph(graph)
     ids = _history(D, gridded)
-    _poison(D)
+    poison(D)
     return D, ids
 
 
@@ -90,10 +81,10 @@ def test_ers_stepwise(base, lib_path):
     """ERS through the stepwise calls, history with every op on two tapes and gridded entries."""
     rec = base[5]
     sch = schedule()
-    A = _device(*base[:5], lib_path=lib_path)
+    A = device(base, lib_path=lib_path)
     ids = _history(A)
     stepwise(A, rec, sch, history=True)
-    B = _device(*base[:5], lib_path=lib_path)
+    B = device(base, lib_path=lib_path)
     _history(B)
     stepwise(B, rec, sch[:N], history=True)
     img = B.restart_save()
@@ -113,13 +104,13 @@ def test_ers_run_with_graph(base):
     """ERS through elmk_run with graphs on: N steps in one run, save, a fresh poisoned context, load, the other N in one run."""
     rec = base[5]
     sch = schedule()
-    A = _device(*base[:5])
+    A = device(base)
     A.set_graph(True)
     ids = _history(A)
     A.run_reserve(NREC, NSTEPS)
     upload_series(A, rec)
     A.run(DT, sch, st.RUN_HISTORY)
-    B = _device(*base[:5])
+    B = device(base)
     B.set_graph(True)
     _history(B)
     B.run_reserve(NREC, NSTEPS)
@@ -143,7 +134,7 @@ def test_decomposition_change(base):
     n = base[0]["snl"].shape[0]
     rec = base[5]
     sch = schedule()
-    A = _device(*base[:5])
+    A = device(base)
     ids = _history(A, gridded=False)
     stepwise(A, rec, sch, history=True)
     want = _snapshot(A, ids)
@@ -151,11 +142,11 @@ def test_decomposition_change(base):
     halves = [(0, 1400), (1400, n - 1400)]
     imgs = []
     for c0, m in halves:
-        H = _device(*_sub(base, c0, m)[:5])
-        _history(H, gridded=False)
-        stepwise(H, _sub(base, c0, m)[5], sch[:N], history=True)
-        imgs.append(H.restart_save(c0))
-        H.close()
+        half = device(_sub(base, c0, m))
+        _history(half, gridded=False)
+        stepwise(half, _sub(base, c0, m)[5], sch[:N], history=True)
+        imgs.append(half.restart_save(c0))
+        half.close()
     full = R.merge(imgs[::-1])
     for c0, m in [(0, 517), (517, 1999), (2516, n - 2516)]:
         part = R.slice(full, c0, m)
@@ -175,7 +166,7 @@ def test_decomposition_change(base):
 def test_image_contents(base):
     """Field sections equal elmk_download bit for bit; the device's checksums equal restart.py's; the image holds exactly the
     PROGNOSTIC and SURFACE fields."""
-    D = _device(*base[:5])
+    D = device(base)
     stepwise(D, base[5], schedule()[:2])
     img = D.restart_save(gcol0=12345)
     assert img.size == D.restart_size()
@@ -194,7 +185,7 @@ def test_image_contents(base):
 def test_refusals_leave_the_context_as_it_was(base):
     rec = base[5]
     sch = schedule()
-    B = _device(*base[:5])
+    B = device(base)
     _history(B)
     stepwise(B, rec, sch[:N], history=True)
     img = B.restart_save()
@@ -227,29 +218,21 @@ def test_refusals_leave_the_context_as_it_was(base):
             D.restart_load(b, g0)
         _assert_same(before, _snapshot(D, ids))
     # another ncols
-    E = _device(*_sub(base, 0, 2000)[:5])
+    E = device(_sub(base, 0, 2000))
     _history(E)
     with pytest.raises(L.ElmkError):
         E.restart_load(img)
     E.close()
     # another history table
-    E = _device(*base[:5])
+    E = device(base)
     E.history_add(0, "t_grnd", "avg")
     with pytest.raises(L.ElmkError):
         E.restart_load(img)
     E.close()
     # a load while the stream is being captured
-    hip = _hip_runtime()
-    s, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(s), 1) == 0
-    D.set_stream(s.value)
-    assert hip.hipStreamBeginCapture(s, 1) == 0
-    rc = D.lib.elmk_restart_load(D.ctx, 0, img.ctypes.data, img.size)
-    assert hip.hipStreamEndCapture(s, C.byref(graph)) == 0
+    with captured(D):
+        rc = D.lib.elmk_restart_load(D.ctx, 0, img.ctypes.data, img.size)
     assert rc == -1
-    hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(s)
     _assert_same(before, _snapshot(D, ids))
     # the context still gives the bits of a clean one
     Cx, ids_c = _fresh(base)
@@ -273,7 +256,7 @@ MATRIX_LOADS = {(m, m) for m in range(8)}
 
 
 def _matrix_context(inputs, mask):
-    D = _device(*inputs[:5])
+    D = device(inputs)
     n = D.ncols
     D["t_grnd"] = np.full(n, 250.0 + mask)
     if mask & 1:
@@ -337,48 +320,10 @@ def test_feature_matrix():
 
 def test_restart_demo(tmp_path):
     """examples/restart_demo.cc builds, restarts half way through 48 steps and prints bit-identical."""
-    import os
-    import shutil
-    import struct
-    import subprocess
-
-    from tests import helpers as H
-    from tests.test_gpu_run import ROOT, SERIES
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     n = 3008
     cols, scal, soil, lat, lon, rec = _inputs(n, 74, nrec=25)
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "restart_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "restart_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    for i, k in enumerate(("age_tau", "age_kappa", "age_drdt0")):
-        put(k, 1, S.snowage[i])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in SERIES:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
-    put("steps", 1, schedule(48))
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(tmp_path / "state.bin"), str(tmp_path / "restart.img")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    exe = build_demo("restart_demo", tmp_path)
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, demo_records(lat, lon, rec) + [("steps", schedule(48))]))
+    r = run_demo(exe, tmp_path / "state.bin", tmp_path / "restart.img")
     assert "bit-identical" in r.stdout
     R.verify(R.read(tmp_path / "restart.img"))

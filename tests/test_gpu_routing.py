@@ -12,10 +12,10 @@ from elmkernels_amd import hydrology as hy
 from elmkernels_amd import irrigation as ir
 from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
-from tests.test_gpu_history import _hip_runtime
-from tests.test_gpu_hydrology import _new
-from tests.test_gpu_run import DT, NREC, SERIES, _inputs, same, schedule, upload_series
-from tests.test_hydrology_host import clear_snow, prepare
+from tests.hydrology_cases import _new, clear_snow, prepare
+from tests.irrigation_cases import generated
+from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests.support import bits, captured
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +23,6 @@ NCOLS = 1001
 TOL = 1.0e-9
 ROWS = (rt.VOLR, rt.QIN, rt.QOUT, rt.QOUT_SUM)
 NAN, INF = float("nan"), float("inf")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
@@ -211,8 +207,6 @@ def test_withdrawal_on_and_off(lib_path):
     """The irrigation's generated tier: the seven wrappers and the stage until columns apply; then routing with the withdrawal on
     subtracts the aggregate of QFLX_IRRIG, bit for bit the restatement, drives some cells' storage negative, and those release nothing;
     off again gives the bits of a context that never called set_withdrawal."""
-    from tests.test_irrigation_host import generated
-
     n, ncells = 600, 65
     cols, scal, soil, sched = generated(n, 900)
     rows = prepare(cols, 613)
@@ -469,18 +463,10 @@ def test_refusals_and_interlocks_change_nothing(run_base):
         args[k] = None
         assert D.lib.elmk_routing_enable(D.ctx, NCELL, *args, 0.35, 1) == -1 and b"null argument" in D.lib.elmk_last_error(D.ctx)
     # a stream being captured
-    hip = _hip_runtime()
-    strm, graph = P(), P()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    D.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rc = D.lib.elmk_routing_enable(D.ctx, NCELL, *ptrs, 0.35, 1)
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
-    assert rc == -1 and b"captured" in D.lib.elmk_last_error(D.ctx)
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    D.set_stream(None)
-    hip.hipStreamDestroy(strm)
+    with captured(D) as cap:
+        rc = D.lib.elmk_routing_enable(D.ctx, NCELL, *ptrs, 0.35, 1)
+        cap.end()
+        assert rc == -1 and b"captured" in D.lib.elmk_last_error(D.ctx)
     D.routing_clear()  # nothing to free: OK
     assert D.device_bytes == bytes0 and D.restart_size() == size0
     _assert_same(_snapshot(D, routing=False), before)

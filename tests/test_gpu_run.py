@@ -3,151 +3,24 @@ driven through the existing calls ("stepwise": the atm_* and mlai .. mhbot field
 step, elmk_solar_geometry, elmk_phenology, elmk_get_forcing, elmk_init_timestep, elmk_advance_physics, then
 elmk_evaluate_conservation and elmk_error_summary after every step)."""
 import ctypes as C
-import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from elmkernels_amd import _lib as L
 from elmkernels_amd import state as st
-from elmkernels_amd import synth
+from tests import helpers as H
+from tests.hydrology_cases import clear_snow, prepare
+from tests.run_cases import (DT, NREC, NSTEPS, SERIES, _inputs, _pair, assert_same_rows, assert_same_state, demo_records, schedule,
+                             stepwise, upload_series)
+from tests.support import build_demo, captured, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
-
-DT = 1800.0
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SERIES = st.SERIES_FORCING + st.SERIES_PHENOLOGY
-NREC = 10  # hourly forcing records
-NSTEPS = 12  # half-hour steps: forcing slots 0 .. 6
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _inputs(n, seed, nrec=NREC, tier="B"):
-    """State, geography, nrec hourly records per forcing stream and 12 months per phenology field, all [records, n]."""
-    ft = st.field_table()
-    cols, scal, soil = synth.make_state(ft, n, tier=tier, seed=seed)
-    lat, lon = synth.global_grid(n, seed=seed + 1)
-    rng = np.random.default_rng(seed + 2)
-    rec = {}
-    for k in st.SERIES_FORCING:
-        a, b = cols[k][:, 0], cols[k][:, 1]
-        t = np.linspace(0.0, 1.0, nrec)[:, None]
-        rec[k] = (1.0 - t) * a[None, :] + t * b[None, :] + 0.01 * np.abs(a)[None, :] * rng.standard_normal((nrec, n))
-    # long-wave: both branches of ProcessFLDS (<= 50, >= 600) in some columns of some records
-    m = rng.random((nrec, n))
-    rec["atm_flds"] = np.where(m < 0.05, 30.0, np.where(m > 0.95, 700.0, rec["atm_flds"]))
-    rec["atm_prec"] = np.where(rng.random((nrec, n)) < 0.3, 0.0, np.abs(rec["atm_prec"]))  # some dry records
-    rec["atm_fsds"] = np.abs(rec["atm_fsds"])
-    for k in st.SERIES_PHENOLOGY:
-        base = cols[k][:, 0]
-        rec[k] = np.abs(base[None, :] * (1.0 + 0.1 * rng.standard_normal((12, n))))
-    return cols, scal, soil, lat, lon, rec
-
-
-def schedule(nsteps=NSTEPS, slot0=0):
-    """Half-hour steps from 21:00 of day 13: crosses midnight; the month bracket moves from (11, 0) to (0, 1) half way; distinct
-    weights for every stream."""
-    S = np.zeros(nsteps, st.RUN_STEP_DTYPE)
-    for s in range(nsteps):
-        ddoy = 13.875 + s * DT / 86400.0
-        S[s]["decday"] = ddoy + 1.0
-        S[s]["doy"] = int(ddoy)
-        S[s]["forc_slot"] = slot0 + s // 2
-        e = (s % 2) * 0.5 + 0.25
-        w2 = np.clip(e + 0.03 * np.arange(8) - 0.1, 0.0, 1.0)
-        S[s]["forc_wt2"] = w2
-        S[s]["forc_wt1"] = 1.0 - w2
-        if s < nsteps // 2:
-            S[s]["month1"], S[s]["month2"], S[s]["month_wt1"] = 11, 0, 0.3 - 0.01 * s
-        else:
-            S[s]["month1"], S[s]["month2"], S[s]["month_wt1"] = 0, 1, 0.9 - 0.01 * s
-        S[s]["month_wt2"] = 1.0 - S[s]["month_wt1"]
-    return S
-
-
-def _device(cols, scal, soil, lat, lon, lib_path=None):
-    n = next(iter(cols.values())).shape[0]
-    D = st.ELMState(n, lib_path=lib_path)
-    pft, optics = synth.load_params()
-    D.set_pft(pft)
-    D.set_snicar(optics)
-    D.set_soilcolor(soil["albsat"], soil["albdry"])
-    D.set_land(**synth.TEST_LAND)
-    D.set_scalars(**scal)
-    D.set_snow_age_tables(synth.snow_age_tables())
-    for k, v in cols.items():
-        D.upload(k, v)
-    D.set_column_geography(lat, lon)
-    return D
-
-
-def stepwise(D, rec, steps, qbot_is_rh=False, history=False, rec_late=None, late_from=None):
-    """The existing calls; returns conservation [nsteps, 8, 3], flags [nsteps], first [nsteps].  rec_late: the records from step
-    late_from on."""
-    cons, fo, fb = [], [], []
-    for s, p in enumerate(steps):
-        R = rec_late if (rec_late is not None and s >= late_from) else rec
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([R[k][f], R[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([R[k][p["month1"]], R[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], qbot_is_rh)
-        st.kokkos_init_timestep(D)
-        st.advance_physics(D, DT)
-        cons.append(st.kokkos_evaluate_conservation(D, DT))
-        flags, first = D.error_summary()
-        fo.append(flags)
-        fb.append(first)
-        if history:
-            D.history_accumulate()
-    return np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)
-
-
-def upload_series(D, rec, forc_slots=None):
-    for k in st.SERIES_FORCING:
-        sl = range(rec[k].shape[0]) if forc_slots is None else forc_slots
-        D.series_upload(k, sl[0], rec[k][sl[0]:sl[-1] + 1])
-    for k in st.SERIES_PHENOLOGY:
-        D.series_upload(k, 0, rec[k])
-
-
-def assert_same_state(A, B, cols):
-    """Every field but the series inputs bit for bit; the series inputs of the run context (B) untouched."""
-    for name in A.fields:
-        if name in SERIES:
-            assert same(B[name], np.ascontiguousarray(cols[name], dtype=B[name].dtype)), name
-        else:
-            assert same(A[name], B[name]), name
-
-
-def assert_same_rows(got, want):
-    for g, w in zip(got, want):
-        assert same(g, w)
 
 
 @pytest.fixture(scope="module")
 def base():
     return _inputs(5003, 71)
-
-
-def _pair(base, graph=True, lib_path=None):
-    cols, scal, soil, lat, lon, rec = base
-    A = _device(cols, scal, soil, lat, lon, lib_path)
-    B = _device(cols, scal, soil, lat, lon, lib_path)
-    A.set_graph(graph)
-    B.set_graph(graph)
-    assert A.level_stride != A.ncols
-    return A, B
 
 
 def test_run_equals_stepwise_graph_on(base):
@@ -267,20 +140,6 @@ def test_qbot_is_rh_option_equals_stepwise(base):
     B.close()
 
 
-def _hip_runtime():
-    """The HIP runtime this process already uses (loaded by libelmk)."""
-    L.load()
-    path = next((ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64.so" in ln), None)
-    assert path, "libamdhip64 is not loaded"
-    hip = C.CDLL(path)
-    P = C.c_void_p
-    for name, args in (("hipStreamCreateWithFlags", [C.POINTER(P), C.c_uint]), ("hipStreamBeginCapture", [P, C.c_int]),
-                       ("hipStreamEndCapture", [P, C.POINTER(P)]), ("hipGraphDestroy", [P]), ("hipStreamDestroy", [P])):
-        getattr(hip, name).argtypes = args
-        getattr(hip, name).restype = C.c_int
-    return hip
-
-
 def test_refusals_enqueue_nothing(base):
     """Every refusal of elmk_run returns ELMK_E_INVALID, and after each one a valid run from the same starting state (restored
     from a snapshot of every field) still gives the bits of the stepwise run."""
@@ -324,18 +183,9 @@ def test_refusals_enqueue_nothing(base):
     for what, dt, s, flags in cases:
         assert refused(dt, s, flags), what
         valid_run_still_gives_the_bits(what)
-    hip = _hip_runtime()
-    strm, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreateWithFlags(C.byref(strm), 1) == 0
-    B.set_stream(strm.value)
-    assert hip.hipStreamBeginCapture(strm, 1) == 0
-    rc = refused(DT, steps)
-    assert hip.hipStreamEndCapture(strm, C.byref(graph)) == 0
+    with captured(B):
+        rc = refused(DT, steps)
     assert rc
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    B.set_stream(None)
-    hip.hipStreamDestroy(strm)
     valid_run_still_gives_the_bits("stream being captured")
     A.close()
     B.close()
@@ -350,14 +200,13 @@ def test_the_captured_step_follows_every_part_of_its_key():
     ELMK_RUN_HYDROLOGY: test_gpu_hydrology.test_the_captured_run_step_follows_the_land_unit.)"""
     from elmkernels_amd import hydrology as hy
     from elmkernels_amd import regrid as RG
-    from tests.test_hydrology_host import clear_snow, prepare
 
     n = 200  # the base fixture is larger; two blocks of most kernels with a ragged tail
     inputs = _inputs(n, 75)
     clear_snow(inputs[0])
     rows = prepare(inputs[0], 76)
     cols, scal, soil, lat, lon, rec = inputs
-    pair = [_device(cols, scal, soil, lat, lon) for _ in range(2)]
+    pair = [H.device_state(cols, scal, soil, lat=lat, lon=lon) for _ in range(2)]
     for D, graph in zip(pair, (True, False)):
         D.set_graph(graph)
         D.run_reserve(NREC, 2)
@@ -449,8 +298,8 @@ def test_the_captured_step_follows_every_part_of_its_key():
 def test_large_launch_run_equals_stepwise(half):
     """262 144 columns (the benchmark's launch structure), three steps; ELMK_OPT_CF_HALF_WORKGROUPS off and on."""
     cols, scal, soil, lat, lon, rec = _inputs(262144, 72)
-    A = _device(cols, scal, soil, lat, lon)
-    B = _device(cols, scal, soil, lat, lon)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     for D in (A, B):
         D.set_graph(True)
         D.set_option(st.OPT_CF_HALF_WORKGROUPS, int(half))
@@ -467,8 +316,8 @@ def test_large_launch_run_equals_stepwise(half):
 
 def test_fp32_state_library():
     cols, scal, soil, lat, lon, rec = _inputs(2053, 73)
-    A = _device(cols, scal, soil, lat, lon, L.F32_LIB_PATH)
-    B = _device(cols, scal, soil, lat, lon, L.F32_LIB_PATH)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=L.F32_LIB_PATH)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=L.F32_LIB_PATH)
     assert B.lib.elmk_state_real_bytes() == 4
     steps = schedule()
     want = stepwise(A, rec, steps)
@@ -488,48 +337,15 @@ def test_fp32_state_library():
 def test_run_demo(tmp_path):
     """examples/run_demo.cc (48 half-hour steps over 25 hourly records as two runs of 24, the second window uploaded during the
     first run) writes the PrimaryVars and the 48 conservation rows of the stepwise run, bit for bit."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     n, nsteps = 3008, 48
     cols, scal, soil, lat, lon, rec = _inputs(n, 74, nrec=25)
     steps = schedule(nsteps)
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "run_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "run_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    from tests import helpers as H
-
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    put("age_tau", 1, S.snowage[0])
-    put("age_kappa", 1, S.snowage[1])
-    put("age_drdt0", 1, S.snowage[2])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in SERIES:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
-    put("steps", 1, steps)
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(tmp_path / "state.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    exe = build_demo("run_demo", tmp_path)
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, demo_records(lat, lon, rec) + [("steps", steps)]))
+    r = run_demo(exe, tmp_path / "state.bin", tmp_path / "out.bin")
     assert "48 steps" in r.stdout, r.stdout
     # the same steps through the Python layer, stepwise
-    D = _device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     D.set_graph(True)
     cons, _, _ = stepwise(D, rec, steps)
     raw = (tmp_path / "out.bin").read_bytes()

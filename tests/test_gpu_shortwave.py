@@ -2,9 +2,6 @@
 stepwise physics against the oracle, elmk_run against the stepwise calls (per-column series and a forcing grid, graph on and off),
 conservation of each record's energy over its interval, the default left as it was, the refusals, and an exact restart."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,18 +12,17 @@ from elmkernels_amd import regrid as RG
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests import helpers as H
-from tests import test_gpu_run as GR
+from tests import run_cases as GR
+from tests.support import build_demo, run_demo, same, state_blob
 
 pytestmark = pytest.mark.gpu
 
 DT = GR.DT
-ROOT = GR.ROOT
 FORC_DT = 3 * 3600.0  # 3-hourly records (GSWP3)
 SPR = int(FORC_DT // DT)  # steps per record: 6
 NSTEPS = 24
 NREC = NSTEPS // SPR + 1  # slots 0 .. 4
 DAY0 = 171.0  # records from 00:00 of the June solstice (decimal_doy)
-same = GR.same
 
 
 def rec_times(nrec=NREC, day0=DAY0, forc_dt=FORC_DT):
@@ -35,7 +31,7 @@ def rec_times(nrec=NREC, day0=DAY0, forc_dt=FORC_DT):
 
 
 def schedule(nsteps=NSTEPS, day0=DAY0):
-    """Half-hour steps from 00:00 of day0 over 3-hourly records (slot s // 6), with test_gpu_run's weights and months."""
+    """Half-hour steps from 00:00 of day0 over 3-hourly records (slot s // 6), with run_cases' weights and months."""
     S = GR.schedule(nsteps)
     for s in range(nsteps):
         ddoy = day0 + s * DT / 86400.0
@@ -71,7 +67,7 @@ def stepwise(D, rec, steps, recs, history=False):
 
 def _coszen_device(base, graph=False):
     cols, scal, soil, lat, lon, rec = base
-    D = GR._device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     D.set_graph(graph)
     D.set_shortwave_mode("coszen", FORC_DT)
     return D
@@ -110,7 +106,7 @@ def test_czf_matches_the_reference_over_the_globe():
     ft = st.field_table()
     cols, scal, soil = synth.make_state(ft, n, tier="B", seed=121)
     lat, lon = synth.global_grid(n, seed=122)
-    D = GR._device(cols, scal, soil, lat, lon)
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     D.run_reserve(2, 1)
     for k in st.SERIES_FORCING:
         D.series_upload(k, 0, cols[k].T)
@@ -241,7 +237,7 @@ def test_energy_of_each_record_is_kept(base):
     fsds = rec["atm_fsds"]
     wt = np.zeros(8)
     for mode in ("coszen", "reference"):
-        D = GR._device(cols, scal, soil, lat, lon)
+        D = H.device_state(cols, scal, soil, lat=lat, lon=lon)
         D.set_shortwave_mode(mode, FORC_DT)
         for r in range(NREC - 1):
             D.upload("atm_fsds", np.stack([fsds[r], fsds[r + 1]], axis=1))
@@ -276,8 +272,8 @@ def test_reference_mode_is_the_default(base):
     nothing more."""
     cols, scal, soil, lat, lon, rec = base
     steps = GR.schedule()
-    A = GR._device(cols, scal, soil, lat, lon)
-    B = GR._device(cols, scal, soil, lat, lon)
+    A = H.device_state(cols, scal, soil, lat=lat, lon=lon)
+    B = H.device_state(cols, scal, soil, lat=lat, lon=lon)
     A.set_graph(True)
     B.set_graph(True)
     bytes_fresh = B.device_bytes
@@ -384,7 +380,6 @@ def test_refusals_leave_everything_as_it_was(base):
 def test_exact_restart_in_coszen_mode(base):
     """2N steps give the bits of N steps, save, load into a fresh context (mode and times set again), then N steps."""
     from elmkernels_amd import restart as RS
-    from tests.test_gpu_restart import _poison
 
     cols, scal, soil, lat, lon, rec = base
     recs = rec_times()
@@ -404,7 +399,7 @@ def test_exact_restart_in_coszen_mode(base):
     B.close()
     RS.verify(img)
     Cx = _coszen_device(base, graph=True)
-    _poison(Cx)
+    GR.poison(Cx)
     Cx.run_reserve(NREC, NSTEPS)
     Cx.restart_load(img)
     GR.upload_series(Cx, rec)
@@ -422,14 +417,7 @@ def test_shortwave_demo_runs(tmp_path):
     """examples/shortwave_demo.cc compiles with g++ against the C ABI and runs 48 half-hour steps over 3-hourly records whose FSDS is
     1000 W/m2 x czf (no sunlight where the sun stays down): in COSZEN mode the day's mean incident shortwave is the records' mean
     (within 1 %: the 0.001 threshold and the cap), in REFERENCE mode it falls short."""
-    import struct
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "shortwave_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "shortwave_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
+    exe = build_demo("shortwave_demo", tmp_path)
     n, nrec, nsteps = 3008, 2 * NSTEPS // SPR + 1, 2 * NSTEPS
     cols, scal, soil, lat, lon, rec = GR._inputs(n, 141, nrec=nrec)
     recs = rec_times(nrec)
@@ -440,34 +428,8 @@ def test_shortwave_demo_runs(tmp_path):
         G.set_forcing_record_time(recs[r])
         rec["atm_fsds"][r] = 1000.0 * G.forcing_cosz()
     G.close()
-    S = H.oracle_state(cols, scal, soil)
-    blob = [struct.pack("<q", n)]
-
-    def put(name, kind, arr):
-        a = np.ascontiguousarray(arr)
-        blob.append(name.encode().ljust(32, b"\0") + struct.pack("<iq", kind, a.nbytes) + a.tobytes())
-
-    for k, v in S.fields.items():
-        if k != "err_flags":
-            put(k, 0, v)
-    sc = S.scalars
-    put("land", 1, np.array([sc["ltype"], sc["ctype"], sc["vtype"], sc["urbpoi"], sc["lakpoi"]], np.int32))
-    put("scalars", 1, np.array([sc["dewmx"], sc["oldfflag"], sc["dayl"], sc["max_dayl"], DT], np.float64))
-    for k in ("pft_psn", "pft_alb", "z0mr", "displar", "albsat", "albdry"):
-        put(k, 1, getattr(S, k))
-    for i, name in enumerate(L.SNICAR_NAMES):
-        put(f"snicar/{i}", 1, S.snicar[name])
-    put("age_tau", 1, S.snowage[0])
-    put("age_kappa", 1, S.snowage[1])
-    put("age_drdt0", 1, S.snowage[2])
-    put("lat", 1, lat)
-    put("lon", 1, lon)
-    for k in GR.SERIES:
-        put(f"series/{k}", 1, np.ascontiguousarray(rec[k], np.float64))
-    put("recs", 1, recs)
-    put("steps", 1, schedule(nsteps))
-    (tmp_path / "state.bin").write_bytes(b"".join(blob))
-    out = subprocess.run([exe, str(tmp_path / "state.bin")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
+    extra = GR.demo_records(lat, lon, rec) + [("recs", recs), ("steps", schedule(nsteps))]
+    (tmp_path / "state.bin").write_bytes(state_blob(H.oracle_state(cols, scal, soil), DT, extra))
+    out = run_demo(exe, tmp_path / "state.bin")
     print(out.stdout)
     assert "coszen: kept" in out.stdout and "reference: short" in out.stdout, out.stdout

@@ -13,12 +13,11 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests import helpers as H
+from tests.run_cases import DT, _device_step, _global_pair, _groups, _oracle_step
+from tests.support import ROOT, build_demo, run_demo
 
 pytestmark = pytest.mark.gpu
 
-DT = 1800.0
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FORC_WT = np.random.default_rng(3).random(8)
 
 
 def same_bits(a, b):
@@ -98,46 +97,6 @@ def test_solar_geometry_matches_the_reference_over_the_globe(tmp_path):
         if dt < 86400.0:
             assert (cosz > 0).any() and (cosz == 0).any()
     D.close()
-
-
-def _global_pair(n, seed, lat=None, lon=None, tier="B"):
-    ft = st.field_table()
-    cols, scal, soil = synth.make_state(ft, n, tier=tier, seed=seed)
-    D = H.device_state(cols, scal, soil)
-    if lat is None:
-        lat, lon = synth.global_grid(n, seed=seed)
-    D.set_column_geography(lat, lon)
-    return D, cols, scal, soil
-
-
-def _groups(dayl, max_dayl):
-    key = np.stack([dayl.view(np.uint64), max_dayl.view(np.uint64)], axis=1)
-    uniq, inv = np.unique(key, axis=0, return_inverse=True)
-    return [(uniq[g, 0:1].view(np.float64)[0], uniq[g, 1:2].view(np.float64)[0], inv.reshape(-1) == g) for g in range(len(uniq))]
-
-
-def _oracle_step(S, coszen):
-    S["coszen"][...] = coszen.reshape(S["coszen"].shape)
-    S.phenology(0.3, 0.7)
-    S.get_forcing(1.0 - FORC_WT, FORC_WT, False)
-    S.init_timestep()
-    S.timestep7(DT)
-    S.soil_temperature(DT)
-    S.snow_hydrology(DT)
-    S.surface_fluxes(DT)
-
-
-def _device_step(D, how):
-    st.compute_phenology(D, 0.3, 0.7)
-    st.get_forcing(D, 1.0 - FORC_WT, FORC_WT, False)
-    st.kokkos_init_timestep(D)
-    if how == "advance":
-        st.advance_physics(D, DT)
-    else:
-        (st.timestep7_fused if how == "fused" else st.timestep7)(D, DT)
-        st.kokkos_soil_temperature(D, DT)
-        st.kokkos_snow_hydrology(D, DT)
-        st.kokkos_surface_fluxes(D, DT)
 
 
 @pytest.mark.parametrize("how,graph,half", [("per_wrapper", False, False), ("fused", False, True), ("advance", True, False),
@@ -287,14 +246,6 @@ def test_twelve_step_chain_with_advancing_date():
 
 def test_global_grid_demo_runs(tmp_path):
     """examples/global_grid_demo.cc compiles against include/ and libelmk and steps a simulated day over both hemispheres."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "global_grid_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir,
-                           "-o", exe])
-    r = subprocess.run([exe, "4096"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = run_demo(build_demo("global_grid_demo", tmp_path), "4096", timeout=300)
     fr = [float(ln.split("day fraction")[1].split()[0]) for ln in r.stdout.splitlines() if "day fraction" in ln]
     assert len(fr) == 48 and min(fr) > 0.0 and max(fr) < 1.0, r.stdout

@@ -12,12 +12,10 @@ from elmkernels_amd import regrid as RG
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
+from tests.hydrology_cases import _new, _new_frost, add_frost, clear_snow, generated_frost, prepare
 from tests.parity_cases import WETLAND
-from tests.test_frost_table_host import add_frost, generated_frost
-from tests.test_gpu_frost_table import _new_frost
-from tests.test_gpu_hydrology import _new
-from tests.test_gpu_run import DT, NREC, ROOT, SERIES, _device, _inputs, same, schedule, stepwise, upload_series
-from tests.test_hydrology_host import clear_snow, prepare
+from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, stepwise, upload_series
+from tests.support import bits, build_demo, run_demo
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +24,6 @@ RED_BYTES = 3 * DG.CONS_NPART * 3 * 8 + 256  # the reduction's partials, then th
 # stage 1 of the reduction is a fixed grid of CONS_NPART workgroups of 256 threads (launch_min_max_sum): past CONS_NPART * 256 columns a
 # thread folds a second element
 SIZES = [1, 255, 257, 1001, DG.CONS_NPART * DG.CONS_BLOCK + 1]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).tobytes()
 
 
 def _ring_bytes(max_steps):
@@ -147,14 +141,14 @@ def _context(base, graph, lib_path=None, features=True, wb=True, tol=TOL, wb_fir
         D.active_layer_enable()
         D.active_layer_init()
     else:
-        D = _device(*b[:5], lib_path)
+        D = device(b, lib_path=lib_path)
     D.set_graph(graph)
     if features and wb and wb_first:
         _enable(D, tol)
     before = D.device_bytes
     D.run_reserve(NREC, 2 * NSTEPS)
     if features and wb and wb_first:
-        plain = _device(*b[:5], lib_path)
+        plain = device(b, lib_path=lib_path)
         p0 = plain.device_bytes
         plain.run_reserve(NREC, 2 * NSTEPS)
         assert D.device_bytes - before == plain.device_bytes - p0 + _ring_bytes(2 * NSTEPS)
@@ -166,7 +160,7 @@ def _context(base, graph, lib_path=None, features=True, wb=True, tol=TOL, wb_fir
 
 
 def _stepwise(D, rec, steps, wb=True, history=False, per_step=None):
-    """test_gpu_run.stepwise with W0 after init_timestep, the hydrology after the physics, W1 - W8 after the flag summary, then the
+    """run_cases.stepwise with W0 after init_timestep, the hydrology after the physics, W1 - W8 after the flag summary, then the
     active layer update and the history sample.  per_step: a list that receives a function's value after every step."""
     cons, fo, fb, bal = [], [], [], []
     for p in steps:
@@ -518,18 +512,7 @@ def test_a_context_without_the_feature_is_what_it_was(base):
 def test_water_balance_demo(tmp_path):
     """examples/water_balance_demo.cc builds with g++ against the C ABI and runs: 48 steps, the budget closed in every one, the tape
     means of QRUNOFF and ZWT per column."""
-    import os
-    import shutil
-    import subprocess
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    libdir = os.path.dirname(L.LIB_PATH)
-    exe = str(tmp_path / "water_balance_demo")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "water_balance_demo.cc"), "-L" + libdir, "-lelmk", "-Wl,-rpath," + libdir, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_demo(build_demo("water_balance_demo", tmp_path), timeout=120)
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 2 + 48 + 1 + 6 and "water balance, 48 steps" in lines[0]
     steps = [ln.split() for ln in lines[2:50]]

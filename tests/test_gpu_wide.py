@@ -4,9 +4,9 @@ import numpy as np
 import pytest
 
 from elmkernels_amd import state as st
-from elmkernels_amd import synth
 from tests import helpers as H
 from tests import parity_cases as P
+from tests import run_cases as GR
 
 pytestmark = pytest.mark.gpu
 
@@ -17,23 +17,8 @@ def _pair(case, n=None, set_scalars=True):
     cols, scal, soil = P.state(case if n is None else P.Case(case.name, case.tier, n, case.seed, scalars=case.scalars),
                                st.field_table())
     S = H.oracle_state(cols, scal, soil, case.land)
-    D = H.device_state(cols, scal, soil, case.land) if set_scalars else _device_without_scalars(cols, soil, case.land)
-    return D, S
-
-
-def _device_without_scalars(cols, soil, land):
-    """A context that never calls elmk_set_scalars: it runs on the library's defaults (parity_cases.ABI_DEFAULT)."""
-    n = next(iter(cols.values())).shape[0]
-    D = st.ELMState(n, 0)
-    pft, optics = synth.load_params()
-    D.set_pft(pft)
-    D.set_snicar(optics)
-    D.set_soilcolor(soil["albsat"], soil["albdry"])
-    D.set_land(**(land or synth.TEST_LAND))
-    D.set_snow_age_tables(synth.snow_age_tables())
-    for k, v in cols.items():
-        D[k] = v
-    return D
+    # (scal None: a context that never calls elmk_set_scalars runs on the library's defaults, parity_cases.ABI_DEFAULT)
+    return H.device_state(cols, scal if set_scalars else None, soil, case.land), S
 
 
 def _check(D, S, what):
@@ -185,43 +170,39 @@ def test_hot_path_on_device_against_the_reference_library_on_wide_inputs():
 
 def test_run_equals_stepwise_on_wide_inputs():
     """elmk_run (twelve steps replayed from one captured step) against the same steps called one by one, on tier W: state,
-    err_flags, conservation and flag rows bit for bit (tests/test_gpu_run.py's harness)."""
-    from tests import test_gpu_run as R
-
-    base = R._inputs(5003, 91, tier="W")  # (a ragged size: the harness wants a padded level stride)
+    err_flags, conservation and flag rows bit for bit (tests/run_cases.py's harness)."""
+    base = GR._inputs(5003, 91, tier="W")  # (a ragged size: the harness wants a padded level stride)
     cols, _, _, _, _, rec = base
-    A, B = R._pair(base)
-    steps = R.schedule()
-    want = R.stepwise(A, rec, steps)
-    B.run_reserve(R.NREC, R.NSTEPS)
-    R.upload_series(B, rec)
+    A, B = GR._pair(base)
+    steps = GR.schedule()
+    want = GR.stepwise(A, rec, steps)
+    B.run_reserve(GR.NREC, GR.NSTEPS)
+    GR.upload_series(B, rec)
     B.run(DT, steps)
-    R.assert_same_rows(B.run_diagnostics(), want)
-    R.assert_same_state(A, B, cols)
+    GR.assert_same_rows(B.run_diagnostics(), want)
+    GR.assert_same_state(A, B, cols)
     A.close()
     B.close()
 
 
 def test_per_column_day_length_on_wide_inputs():
     """Per-column solar geometry and day length (set_column_geography) on tier W: two steps of the whole chain checked against
-    the oracle run once per group of columns sharing (dayl, max_dayl), bit for bit (tests/test_gpu_solar_geometry.py's harness)."""
-    from tests import test_gpu_solar_geometry as G
-
+    the oracle run once per group of columns sharing (dayl, max_dayl), bit for bit (tests/run_cases.py's harness)."""
     n = 8192
-    D, cols, scal, soil = G._global_pair(n, 35, tier="W")
+    D, cols, scal, soil = GR._global_pair(n, 35, tier="W")
     oracles = {}
     for step, decday in enumerate((172.25, 172.3125)):
         D.solar_geometry(DT, decday, int(decday) - 1)
         coszen = D["coszen"].copy()
         dayl, max_dayl = D.day_length()
-        groups = G._groups(dayl, max_dayl)
+        groups = GR._groups(dayl, max_dayl)
         assert len(groups) >= 2
-        G._device_step(D, "advance")
+        GR._device_step(D, "advance")
         for dl, mdl, m in groups:
             key = (dl.tobytes(), mdl.tobytes())
             if key not in oracles:
                 oracles[key] = H.oracle_state(cols, dict(scal, dayl=float(dl), max_dayl=float(mdl)), soil)
-            G._oracle_step(oracles[key], coszen)
+            GR._oracle_step(oracles[key], coszen)
             worst, bad = H.compare_states(D, oracles[key], skip_cols=~m, bitwise=True)
             assert not bad, (step, float(dl), float(mdl), bad)
     D.close()

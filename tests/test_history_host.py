@@ -5,8 +5,8 @@ import re
 
 from elmkernels_amd import _lib as L
 from elmkernels_amd import state as st
+from tests.support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "elmk.h")).read()
 
 

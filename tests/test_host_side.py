@@ -15,8 +15,7 @@ from elmkernels_amd import state as st
 from oracle import oracle as O
 from tests import fixtures as F
 from tests import helpers as H
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT, build_demo
 
 
 def _header_symbols():
@@ -151,16 +150,10 @@ def test_cpp_interface_mirror_compiles_and_links():
     """include/elmk_interface.hpp (the C++ mirror of ELM::ELMInterface above the C ABI) and the driver loop that uses it
     (examples/elm_interface_demo.cc) compile with -Wall -Wextra -Werror and link against libelmk; the class has the
     reference's member functions (elm_kokkos_interface.hh:16-20).  Nothing is run here (no GPU)."""
-    import subprocess
     import tempfile
 
-    from elmkernels_amd import _lib as L
-
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                            os.path.join(ROOT, "examples", "elm_interface_demo.cc"), "-L" + os.path.dirname(L.LIB_PATH), "-lelmk",
-                            "-o", os.path.join(d, "demo")], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-        assert r.returncode == 0, r.stderr.decode()
+        build_demo("elm_interface_demo", d)
     hdr = open(os.path.join(ROOT, "include", "elmk_interface.hpp")).read()
     for member in ("void setup(", "bool advance(", "void copyPrimaryVars(", "getPrimaryVars()"):
         assert member in hdr, member

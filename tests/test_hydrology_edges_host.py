@@ -1,4 +1,4 @@
-"""The edge tier of the soil hydrology on the host (tests/test_hydrology_host.py: edge_columns) and the select census of the restatement
+"""The edge tier of the soil hydrology on the host (tests/hydrology_cases.py: edge_columns) and the select census of the restatement
 (tests/hydrology_sites.py): every `_min` / `_max` of hydrology.column() and hydrology._sy - a select in k_soil_hydrology - returns each
 of its operands in some column of the generators plus the edge tier, apart from the sites listed in EXEMPT with the reason why no
 input can flip them; every walk over the layers crosses two layer boundaries in some column and runs off the end of the layers in
@@ -10,9 +10,8 @@ import pytest
 
 from elmkernels_amd import hydrology as hy
 from tests import hydrology_sites as HS
-from tests.test_frost_table_host import generated_frost
-from tests.test_hydrology_host import (DT, EDGE_CLASS_NAMES, POISONED_FIELDS, POISONED_ROWS, POISONS, SOIL_FIELDS, edge_class_of, edge_columns,
-                                       edge_finite, generated)
+from tests.hydrology_cases import (DT, EDGE_CLASS_NAMES, POISONED_FIELDS, POISONED_ROWS, POISONS, SOIL_FIELDS, edge_class_of, edge_columns,
+                                   edge_finite, generated, generated_frost)
 
 N = hy.N
 NCOL, SEED = 1001, 5

@@ -1,6 +1,6 @@
 """Soil hydrology on the host (include/elmk.h "soil hydrology"; elmkernels_amd/hydrology.py): hand-checked columns of `step`, the exact
-water budget of one step, the parameter helpers, the header's constants and symbols, and restart images of version 4; and the
-generators of the stage's inputs: `generated` (every branch) and `edge_columns` (the edge tier; tests/test_hydrology_edges_host.py)."""
+water budget of one step, the parameter helpers, the header's constants and symbols, and restart images of version 4.  The generators of
+the stage's inputs are tests/hydrology_cases.py."""
 import math
 import os
 import re
@@ -12,436 +12,11 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import hydrology as hy
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
-from elmkernels_amd import synth
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DT = 1800.0
-N = hy.N
-BRANCHES = {"jwt_0", "jwt_mid", "jwt_N", "infiltration_excess", "h2osfc_above_threshold", "h2osfc_below_threshold", "h2osfc_runoff",
-            "h2osfc_negative", "imped", "table_rises", "table_falls", "drain_aquifer", "drain_soil", "excess_up", "excess_to_h2osfc",
-            "watmin_push_down", "watmin_search", "watmin_remainder", "snl_0", "snl_pos"}
-
-
-def prepare(cols, seed, sfc_every=4):
-    """The branch-mix generator's columns (synth.make_state) with the rows the stage reads set so that every branch of it occurs:
-    rain up to infiltration excess, root uptake, ice in the top three layers, near-saturated and near-dry layers, h2osfc above and below
-    its threshold (in two of every sfc_every columns), and water tables from the top layer down to 12 m.  Changes cols in place; returns the rows of the feature [NROWS, n]."""
-    n = cols["snl"].shape[0]
-    rng = np.random.default_rng(seed)
-    c = np.arange(n)
-    s0, s1 = hy.NLEVSNO, hy.NLEVSNO + N
-    dzmm = cols["dz"][:, s0:s1] * 1.0e3
-    watsat = cols["watsat"][:, :N]
-    top = rng.uniform(0.0, 3.0e-4, n)
-    top[c % 6 == 0] = 0.0
-    top[c % 6 == 1] = rng.uniform(0.02, 0.08, (c % 6 == 1).sum())  # heavier than any hksat: infiltration excess
-    cols["qflx_top_soil"] = top
-    root = np.zeros((n, 15))
-    root[:, :8] = rng.uniform(0.0, 2.0e-6, (n, 8))
-    cols["qflx_rootsoi"] = root
-    liq, ice = cols["h2osoi_liq"], cols["h2osoi_ice"]
-    m = c % 5 == 1  # ice in the top three layers
-    ice[m, s0:s0 + 3] = (rng.uniform(0.2, 1.1, (m.sum(), 3)) * watsat[m, :3]) * dzmm[m, :3] * 0.917
-    m = c % 7 == 2  # near-saturated
-    liq[m, s0:s1] = np.maximum(0.995 * watsat[m] * dzmm[m] - ice[m, s0:s1], 0.02)
-    m = c % 7 == 3  # near-dry, below watmin in places
-    liq[m, s0:s1] = rng.choice([0.002, 0.008, 0.05, 0.5], (m.sum(), N))
-    m = c % 21 == 10  # the bottom layer below watmin over layers that can spare water
-    liq[m, s1 - 1] = 0.001
-    hs = np.zeros(n)
-    fh = np.zeros(n)
-    k = sfc_every
-    hs[c % k == 0], fh[c % k == 0] = 20.0 + rng.random((c % k == 0).sum()), 0.6
-    hs[c % k == 1], fh[c % k == 1] = 0.5, 0.2
-    cols["h2osfc"], cols["frac_h2osfc"] = hs, fh
-    ev = cols["qflx_ev_h2osfc"]
-    ev[c % (2 * k) == k + 1] = 1.0e-2  # evaporation beyond the store: h2osfc would go negative
-    rows = np.zeros((hy.NROWS, n))
-    zw = np.array([0.01, 0.05, 0.3, 1.0, 2.5, 3.7, 3.9, 8.8, 12.0])
-    rows[hy.ZWT] = zw[c % zw.size] * (1.0 + 0.05 * rng.random(n))
-    rows[hy.WA] = np.where(c % 11 == 0, 4999.9999, 4000.0 + 100.0 * rng.random(n))
-    sand, clay = rng.uniform(5.0, 90.0, (n, N)), rng.uniform(2.0, 50.0, (n, N))
-    om = np.where(rng.random((n, N)) < 0.3, rng.uniform(60.0, 130.0, (n, N)), rng.uniform(0.0, 30.0, (n, N)))
-    rows[hy.HKSAT:hy.HKSAT + N] = hy.hksat_from_texture(sand, clay, om, cols["zsoi"][:, s0:s1])
-    slope = rng.uniform(0.0, 12.0, n)
-    rows[hy.WTFACT] = rng.uniform(0.05, 0.6, n)
-    rows[hy.H2OSFC_THRESH] = hy.h2osfc_thresh(rng.uniform(0.005, 0.05, n))
-    rows[hy.K_WET] = hy.k_wet(slope)
-    rows[hy.RSUB_TOP_MAX] = hy.rsub_top_max(slope)
-    return rows
-
-
-def clear_snow(cols, every=8):
-    """Make all but one column in `every` snow-free and keep them so (no snowfall): the generator's snow share plus the columns
-    that pond would otherwise leave under half of the columns to the closure."""
-    m = np.arange(cols["snl"].shape[0]) % every != every - 1
-    for k in ("h2osno", "snow_depth", "frac_sno", "frac_sno_eff", "int_snow", "forc_snow"):
-        cols[k][m] = 0.0
-    cols["snl"][m] = 0
-    for k in ("h2osoi_liq", "h2osoi_ice", "dz", "zsoi", "zisoi"):
-        cols[k][m, :hy.NLEVSNO] = 0.0
-
-
-def generated(n, seed, sfc_every=4, full=False, chain=False):
-    cols, scal, soil = synth.make_state(st.field_table(), n, tier="B", seed=seed)
-    if chain:
-        sfc_every = CHAIN_SFC_EVERY
-        clear_snow(cols)
-    rows = prepare(cols, seed + 1, sfc_every)
-    return (cols, scal, soil, rows) if full else (cols, rows)
-
-
-# ---- the edge tier ------------------------------------------------------------------------------------------------------------------
-SOIL_FIELDS = ("h2osoi_liq", "h2osoi_ice", "dz", "zsoi", "zisoi")  # fields that carry the snow levels: layer j is level NLEVSNO + j
-POISONS = (float("nan"), float("inf"), float("-inf"))
-POISONED_ROWS = tuple(range(hy.ZWT, hy.RSUB_TOP_MAX + 1))  # ZWT, WA, the ten HKSAT rows, WTFACT .. RSUB_TOP_MAX
-# snl is the one integer field of hydrology.READS: it has no NaN and no infinity
-POISONED_FIELDS = tuple(k for k in hy.READS if k != "snl") + ("t_soisno",)
-
-
-def edge_classes():
-    """The classes of edge_columns in the order they are dealt: [(name, function of (E, i, k))], E the _Edge under construction, i the
-    column and k a counter that moves the layer a class touches from one round of the classes to the next."""
-    s0 = hy.NLEVSNO
-    out = []
-    turn = (9, 0, 5, 1, 8, 2, 7, 3, 6, 4)  # the layer of round k: the bottom and the top layer first
-
-    def add(name):
-        def deco(f):
-            out.append((name, f))
-            return f
-        return deco
-
-    def dzmm(E, i, j):
-        return float(E.cols["dz"][i, s0 + j]) * 1.0e3
-
-    def wet(E, i, hs=20.0, fh=0.6):
-        E.cols["h2osfc"][i], E.cols["frac_h2osfc"][i] = hs, fh
-
-    # the water table and the aquifer
-    add("zwt=0")(lambda E, i, k: E.row(hy.ZWT, i, 0.0))
-    add("zwt=1e-9")(lambda E, i, k: E.row(hy.ZWT, i, 1.0e-9))
-    for j in range(N):
-        @add(f"zwt=zisoi[{j}]")
-        def _(E, i, k, j=j):
-            # (the interfaces of this column are made fp32 values, so that the equality holds in the fp32-state build too)
-            E.cols["zisoi"][i] = E.cols["zisoi"][i].astype(np.float32)
-            E.row(hy.ZWT, i, float(E.cols["zisoi"][i, s0 + j + 1]))
-    add("zwt=80")(lambda E, i, k: E.row(hy.ZWT, i, 80.0))
-    add("zwt=100")(lambda E, i, k: E.row(hy.ZWT, i, 100.0))
-    add("zwt just below the column")(lambda E, i, k: E.row(hy.ZWT, i, float(np.nextafter(E.cols["zisoi"][i, s0 + N], 100.0))))
-    add("wa=0")(lambda E, i, k: E.row(hy.WA, i, 0.0))
-
-    @add("wa=0, table below")
-    def _(E, i, k):
-        E.row(hy.WA, i, 0.0)
-        E.row(hy.ZWT, i, 8.0)
-
-    @add("wa=5000")
-    def _(E, i, k):
-        E.row(hy.WA, i, 5000.0)
-        E.row(hy.ZWT, i, 8.0)
-
-    @add("wa>5000")
-    def _(E, i, k):
-        E.row(hy.WA, i, 5500.0)
-        E.row(hy.ZWT, i, 8.0)
-        E.row(hy.RSUB_TOP_MAX, i, 0.0)
-
-    # conductivity, ice and water content
-    add("hksat=0 in one layer")(lambda E, i, k: E.row(hy.HKSAT + k % N, i, 0.0))
-
-    @add("hksat=0")
-    def _(E, i, k):
-        E.rows[hy.HKSAT:hy.HKSAT + N, i] = 0.0
-    add("rsub_top_max=0")(lambda E, i, k: E.row(hy.RSUB_TOP_MAX, i, 0.0))
-
-    @add("ice beyond the pores")
-    def _(E, i, k):
-        for j in range(k % 4, N, 3):
-            E.cols["h2osoi_ice"][i, s0 + j] = 1.5 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j) * 0.917
-
-    @add("liq=0 in one layer")
-    def _(E, i, k):
-        E.cols["h2osoi_liq"][i, s0 + k % N] = 0.0
-
-    @add("liq=0")
-    def _(E, i, k):
-        E.cols["h2osoi_liq"][i, s0:s0 + N] = 0.0
-
-    @add("liq<1e-6")
-    def _(E, i, k):
-        E.cols["h2osoi_liq"][i, s0:s0 + N] = 9.0e-8 * (1.0 + np.arange(N))
-
-    @add("bottom layer under 1 %, table below")
-    def _(E, i, k):
-        E.cols["h2osoi_liq"][i, s0 + N - 1] = 0.004 * float(E.cols["watsat"][i, N - 1]) * dzmm(E, i, N - 1)
-        E.cols["h2osoi_ice"][i, s0 + N - 1] = 0.0
-        E.row(hy.ZWT, i, 8.0)
-
-    @add("table layer under 1 %")
-    def _(E, i, k):
-        j = 2 + k % 7
-        E.cols["h2osoi_liq"][i, s0 + j] = 0.004 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j)
-        E.cols["h2osoi_ice"][i, s0 + j] = 0.0
-        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + j]))
-
-    @add("root uptake beyond the water")
-    def _(E, i, k):
-        j = k % 8
-        E.cols["qflx_rootsoi"][i, j] = 2.0 * float(E.cols["h2osoi_liq"][i, s0 + j])
-
-    # the surface fractions
-    add("frac_h2osfc=0")(lambda E, i, k: wet(E, i, 0.0, 0.0))
-    add("frac_h2osfc=0.4")(lambda E, i, k: wet(E, i, 20.0, 0.4))
-    add("frac_h2osfc=1")(lambda E, i, k: wet(E, i, 30.0, 1.0))
-    add("frac_h2osfc just above 0.4")(lambda E, i, k: wet(E, i, 20.0, float(np.nextafter(0.4, 1.0))))
-
-    @add("h2osfc at its threshold")
-    def _(E, i, k):
-        wet(E, i, float(E.rows[hy.H2OSFC_THRESH, i]))
-
-    @add("no rain, evaporation")
-    def _(E, i, k):
-        E.cols["qflx_top_soil"][i] = 0.0
-        E.cols["qflx_evap_grnd"][i] = E.cols["qflx_ev_soil"][i] = 1.0e-4
-
-    @add("frac_sno_eff=0")
-    def _(E, i, k):
-        E.cols["frac_sno_eff"][i] = 0.0
-
-    @add("frac_sno_eff=1")
-    def _(E, i, k):
-        E.cols["frac_sno_eff"][i] = 1.0
-
-    @add("tiny k_wet")
-    def _(E, i, k):
-        wet(E, i)
-        E.row(hy.K_WET, i, 1.0e-6)
-
-    # the soil parameters
-    def params(name, bsw=None, sucsat=None, watsat=None, also=None):
-        @add(name)
-        def _(E, i, k):
-            for key, v in (("bsw", bsw), ("sucsat", sucsat), ("watsat", watsat)):
-                if v is not None:
-                    E.cols[key][i, :N] = v
-            if also:
-                also(E, i, k)
-
-    def dry(E, i, k):
-        E.cols["h2osoi_liq"][i, s0:s0 + N] = 0.02
-        E.cols["h2osoi_ice"][i, s0:s0 + N] = 0.0
-
-    def deep(E, i, k):
-        E.row(hy.ZWT, i, 80.0)
-    params("bsw=1.5", bsw=1.5)
-    params("bsw=20", bsw=20.0)
-    params("sucsat=10", sucsat=10.0)
-    params("sucsat=1000", sucsat=1000.0)
-    params("watsat=0.2", watsat=0.2)
-    params("watsat=0.9", watsat=0.9)
-    params("bsw=20, sucsat=1000, dry", bsw=20.0, sucsat=1000.0, also=dry)       # smp at SMPMIN
-    params("bsw=1.5, sucsat=10, deep table", bsw=1.5, sucsat=10.0, also=deep)  # the equilibrium profile under 1 % of saturation
-    params("layered parameters", bsw=np.array([1.5, 20.0, 3.0, 12.0, 1.5, 20.0, 7.0, 2.0, 16.0, 5.0]),
-           sucsat=np.array([10.0, 1000.0, 40.0, 600.0, 1000.0, 10.0, 200.0, 90.0, 15.0, 800.0]),
-           watsat=np.array([0.9, 0.2, 0.6, 0.3, 0.2, 0.9, 0.45, 0.8, 0.25, 0.5]))
-
-    # the walks: over a wet column a shallow table rises through the layers; a strong drainage runs down through them
-    @add("rise to the surface")
-    def _(E, i, k):
-        E.cols["h2osoi_ice"][i, s0:s0 + N] = 0.0
-        for j in range(N):
-            E.cols["h2osoi_liq"][i, s0 + j] = 0.999 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j)
-        E.rows[hy.HKSAT:hy.HKSAT + N, i] = 0.5
-        # a small specific yield: the recharge, bounded by 10 mm a step, fills layer after layer
-        E.cols["bsw"][i, :N], E.cols["sucsat"][i, :N] = 20.0, 1000.0
-        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + 2 + k % 4]))
-
-    @add("drain through the column")
-    def _(E, i, k):
-        E.row(hy.RSUB_TOP_MAX, i, 50.0 if k % 2 else 0.05)
-        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + 1 + k % 4]))
-
-    @add("fall through the column")
-    def _(E, i, k):
-        # drier than the equilibrium over a shallow table: the recharge is negative and at its bound
-        E.cols["h2osoi_ice"][i, s0:s0 + N] = 0.0
-        for j in range(N):
-            E.cols["h2osoi_liq"][i, s0 + j] = 0.3 * float(E.cols["watsat"][i, j]) * dzmm(E, i, j)
-        E.rows[hy.HKSAT:hy.HKSAT + N, i] = 5.0
-        E.cols["bsw"][i, :N] = 1.5
-        E.row(hy.ZWT, i, float(E.cols["zsoi"][i, s0 + (6 if k % 2 else 1)]))
-
-    # the frost form
-    @add("t_soisno=tfrz at the front")
-    def _(E, i, k):
-        kf = 1 + k % (N - 1)
-        E.cols["t_soisno"][i, s0:s0 + kf] = 275.0
-        E.cols["t_soisno"][i, s0 + kf:s0 + N] = hy.TFRZ
-
-    @add("q_perch_max=0")
-    def _(E, i, k):
-        if E.frost is not None:
-            E.frost[hy.Q_PERCH_MAX, i] = 0.0
-
-    @add("dz=0 in one layer")
-    def _(E, i, k):
-        E.cols["dz"][i, s0 + turn[k % N]] = 0.0
-
-    # the non-finite tier: one poisoned input per column
-    for v in POISONS:
-        for key in POISONED_FIELDS:
-            @add(f"{key}={v}")
-            def _(E, i, k, key=key, v=v):
-                a = E.cols[key]
-                if a.ndim == 1:
-                    a[i] = v
-                elif key in SOIL_FIELDS or key == "t_soisno":
-                    a[i, s0 + turn[k % N]] = v
-                else:
-                    a[i, turn[k % N]] = v
-        for w in POISONED_ROWS:
-            add(f"row {w}={v}")(lambda E, i, k, w=w, v=v: E.row(w, i, v))
-
-        @add(f"q_perch_max={v}")
-        def _(E, i, k, v=v):
-            if E.frost is not None:
-                E.frost[hy.Q_PERCH_MAX, i] = v
-
-        # the aquifer node takes the bottom layer's parameters: poisoned under a table below the column
-        for key in ("watsat", "sucsat", "bsw"):
-            @add(f"table below, bottom {key}={v}")
-            def _(E, i, k, key=key, v=v):
-                E.cols[key][i, N - 1] = v
-                E.row(hy.ZWT, i, 8.0)
-    return out
-
-
-class _Edge:
-    def __init__(self, cols, rows, frost):
-        self.cols, self.rows, self.frost = cols, rows, frost
-
-    def row(self, w, i, v):
-        self.rows[w, i] = v
-
-
-EDGE_CLASS_NAMES = tuple(name for name, _ in edge_classes())
-
-
-def edge_class_of(n):
-    """The class of every column of edge_columns(n, ...): an index into EDGE_CLASS_NAMES."""
-    return np.arange(n) % len(EDGE_CLASS_NAMES)
-
-
-def edge_finite(n):
-    """The columns of edge_columns(n, ...) outside the non-finite tier."""
-    first = EDGE_CLASS_NAMES.index("dz=0 in one layer")
-    return edge_class_of(n) < first
-
-
-def edge_columns(n, seed, frost=False, full=False, skip=()):
-    """The edge tier of the stage: generated (frost: generated_frost) with one edge per column, the classes of edge_classes() dealt to
-    the columns in turn and the layer a class touches moved on with every round.  A class changes only what it names, so every edge
-    meets the generator's mix of the other inputs.  skip: names of classes left as the generator made them (the census test shows
-    with it that a class is needed).  Returns (cols, [scal, soil,] rows[, frost rows])."""
-    cols, scal, soil, rows = generated(n, seed, full=True)
-    fr = None
-    if frost:
-        from tests.test_frost_table_host import add_frost
-
-        fr = add_frost(cols, rows, seed + 2)
-    for k in POISONED_FIELDS + ("qflx_rootsoi",):
-        cols[k] = np.array(cols[k], dtype=np.float64)
-    E = _Edge(cols, rows, fr)
-    classes = edge_classes()
-    assert not set(skip) - set(EDGE_CLASS_NAMES)
-    for i in range(n):
-        name, f = classes[i % len(classes)]
-        if name not in skip:
-            f(E, i, i // len(classes))
-    out = (cols, scal, soil, rows) if full else (cols, rows)
-    return out + (fr,) if frost else out
-
-
-# ---- the chain: the physics of one step, then the stage -----------------------------------------------------------------------------
-CHAIN_STEPS = 6
-CHAIN_SFC_EVERY = 16  # surface water in one column of eight: with the snow columns, under half are left out of the closure
-# |errh2o| of the closed budget over the snow-free columns without surface water of the six-step host chain of
-# generated(1001, 77, chain=True): the largest value measured on the host (mm; its median there is 3.3e-13).  The maximum comes from
-# a few columns where the reference's snow hydrology sets the ice of the top soil layer to the literal 0.9 when sublimation would
-# take it below zero (src/physics/snow_hydrology_impl.hh:303 and :311, `h2osoi_ice(top) = 0.9` with top = the first soil layer for
-# snl == 0): 0.9 mm that no flux accounts for.  The bound is ten times the maximum, headroom over one seed; at 9 mm it lies far above
-# the budget without the stage (median 1.9e-2 mm) and can only catch a gross fault - the bit equality with the host chain and the
-# medians carry the closure tests.
-CLOSURE_MEASURED = 0.9000328415202219
-CLOSURE_BOUND = 10.0 * CLOSURE_MEASURED
-
-
-def water_mass(f):
-    """column_water_mass in the conservation kernel's order: h2ocan + h2osno + h2osfc, then ice + liq of the 20 levels in turn."""
-    w = (f["h2ocan"].astype(np.float64) + f["h2osno"].astype(np.float64)) + f["h2osfc"].astype(np.float64)
-    for i in range(20):
-        w = w + (f["h2osoi_ice"][:, i].astype(np.float64) + f["h2osoi_liq"][:, i].astype(np.float64))
-    return w
-
-
-CLOSURE_FIELDS = ("h2ocan", "h2osno", "h2osfc", "h2osoi_ice", "h2osoi_liq", "dtbegin_column_h2o", "forc_rain", "forc_snow", "qflx_evap_tot",
-                  "qflx_snwcp_ice", "snl", "frac_h2osfc")
-
-
-def closure(f, wa_beg, h2osno_beg, rows_out, dt, with_stage=True):
-    """(errh2o per column, the columns it is judged on) from the fields after a step: hydrology.water_balance_error with the stage's
-    runoff and drainage (or, with_stage False, the reference's hardwired zero and no aquifer); snow-free columns (no snow mass before or after the step: the reference's snow hydrology drops a layerless snow cover
-    without a flux) without surface water."""
-    z = np.zeros(wa_beg.shape)
-    e = hy.water_balance_error(f["dtbegin_column_h2o"], water_mass(f), wa_beg, rows_out[hy.WA] if with_stage else wa_beg, f["forc_rain"],
-                               f["forc_snow"], f["qflx_evap_tot"], f["qflx_snwcp_ice"], *((rows_out[hy.QFLX_SURF], rows_out[hy.QFLX_H2OSFC_SURF],
-                                                                                         rows_out[hy.QFLX_DRAIN]) if with_stage else (z, z, z)), dt)
-    keep = (f["snl"] == 0) & (f["h2osno"] == 0.0) & (h2osno_beg == 0.0) & (f["frac_h2osfc"] == 0.0)
-    return e, keep
-
-
-def host_chain(cols, scal, soil, rows, nsteps=CHAIN_STEPS, dt=DT, stage=True):
-    """The oracle's step (init_timestep, the seven wrappers, soil temperature, snow hydrology, surface fluxes) and then hydrology.step,
-    nsteps times.  Returns the oracle state, the rows, and per step (errh2o, keep) of closure()."""
-    from tests import helpers as H
-
-    S = H.oracle_state(cols, scal, soil)
-    rows = rows.copy()
-    per_step = []
-    for _ in range(nsteps):
-        S.init_timestep()
-        h2osno_beg = np.array(S.fields["h2osno"])
-        S.timestep7(dt)
-        S.soil_temperature(dt)
-        S.snow_hydrology(dt)
-        S.surface_fluxes(dt)
-        wa_beg = rows[hy.WA].copy()
-        if stage:
-            out, rows = hy.step(S.fields, rows, dt)
-            for k, v in out.items():
-                S.fields[k][...] = v
-        per_step.append(closure({k: np.array(S.fields[k]) for k in CLOSURE_FIELDS}, wa_beg, h2osno_beg, rows, dt, stage))
-    return S, rows, per_step
+from tests.hydrology_cases import BRANCHES, CLOSURE_BOUND, CLOSURE_MEASURED, DT, N, column, generated, host_chain
+from tests.support import ROOT
 
 
 # ---- hand-built columns -----------------------------------------------------------------------------------------------------------
-def column(zwt=1.0, wa=4000.0, hksat=0.0, sat=0.5, **kw):
-    """A uniform loam column on ELM's grid: watsat 0.45, sucsat 200 mm, bsw 5; liq = sat * watsat * dzmm; no ice, no fluxes, no
-    runoff parameters.  Keywords replace entries."""
-    zi = [0.0, 0.0175, 0.0451, 0.0906, 0.1655, 0.2891, 0.4929, 0.8289, 1.3828, 2.2961, 3.8019]
-    dz = [zi[j + 1] - zi[j] for j in range(N)]
-    z = [0.5 * (zi[j + 1] + zi[j]) for j in range(N)]
-    c = {"liq": [sat * (0.45 * (d * 1.0e3)) for d in dz], "ice": [0.0] * N, "dz": dz, "z": z, "zi": zi, "watsat": [0.45] * N,
-         "sucsat": [200.0] * N, "bsw": [5.0] * N, "rootsoi": [0.0] * N, "hksat": [hksat] * N, "snl": 0, "fsno": 0.0, "h2osfc": 0.0,
-         "frac_h2osfc": 0.0, "qflx_top_soil": 0.0, "qflx_evap_grnd": 0.0, "qflx_ev_soil": 0.0, "qflx_ev_h2osfc": 0.0, "qflx_dew_grnd": 0.0,
-         "qflx_dew_snow": 0.0, "qflx_sub_snow": 0.0, "zwt": zwt, "wa": wa, "wtfact": 0.0, "h2osfc_thresh": 5.0, "k_wet": 0.05,
-         "rsub_top_max": 0.0}
-    c.update(kw)
-    return c
-
-
 def test_a_dry_column_stays_put():
     """Nothing falls, nothing is taken, nothing conducts (hksat = 0) and nothing drains: every store keeps its bits."""
     for zwt in (1.0, 8.0):

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from elmkernels_amd import hydrology as hy
-from tests.test_hydrology_host import DT, column, edge_columns, edge_finite
+from tests.hydrology_cases import DT, column, edge_columns, edge_finite
 
 mp.mp.dps = 40
 N = hy.N
@@ -87,7 +87,7 @@ def darcy(theta, zwt_m, par, hksat, pe=None):
 
 
 def build(theta, zwt_m, par, hksat, **kw):
-    """The column of test_hydrology_host.column with these parameters and liq = theta * dz in mm (rounded to fp64 once each)."""
+    """The column of hydrology_cases.column with these parameters and liq = theta * dz in mm (rounded to fp64 once each)."""
     c = column(zwt=float(zwt_m), hksat=0.0, **kw)
     c.update(bsw=list(par["bsw"]), sucsat=list(par["sucsat"]), watsat=list(par["watsat"]), hksat=list(hksat))
     c["liq"] = [float(theta[j]) * (c["dz"][j] * 1.0e3) for j in range(N)]

@@ -8,7 +8,8 @@ import warnings
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
+
 
 NPTS = "npts outside 1 .. 8"
 NCELLS = "ncells outside 1 .. 2^31-1"

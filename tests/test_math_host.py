@@ -8,7 +8,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
+
 SRC = os.path.join(ROOT, "tests", "tools", "math_host_check.c")
 
 

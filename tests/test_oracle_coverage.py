@@ -24,7 +24,8 @@ import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
+
 ORACLE = os.path.join(ROOT, "oracle")
 SRCS = ["elmo_physics_a.c", "elmo_physics_b.c", "elmo_physics_c.c", "elmo_physics_d.c", "elmo_physics_e.c", "elmo_physics_f.c",
         "elmo_physics_g.c", "elmo_physics_h.c", "elmo_driver.c"]

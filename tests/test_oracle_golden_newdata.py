@@ -11,17 +11,17 @@ new_data/BareGroundFluxes_IN.txt is malformed (duplicate keys; SURVEY.md section
 import numpy as np
 
 from tests import fixtures as F
-from tests import test_oracle_golden as T
+from tests import helpers as H
 
 
 def test_newdata_canopy_hydrology():
     with F.dataset("newdata"):
-        d, rows, S, oin, fout = T._prepare("CanopyHydrology")
+        d, rows, S, oin, fout = H.fixture_state("CanopyHydrology")
         assert len(rows) == 97
         S.set_scalars(oldfflag=int(oin["oldfflag"][0, 0]), dewmx=float(oin["dewmx"][0, 0]))
         S.canopy_hydrology(F.TEST_DTIME)
         S.frac_wet()
-        total, bad = T._compare(S, fout, len(rows))
+        total, bad = H.compare_with_fixture(S, fout, len(rows))
     assert total >= 3600 and not bad, bad
     assert not S["err_flags"].any()
 
@@ -29,34 +29,34 @@ def test_newdata_canopy_hydrology():
 def test_newdata_sunshade_and_surface_radiation():
     for module, minimum in (("CanopySunShadeFractions", 500), ("SurfaceRadiation", 2000)):
         with F.dataset("newdata"):
-            d, rows, S, oin, fout = T._prepare(module)
+            d, rows, S, oin, fout = H.fixture_state(module)
             assert len(rows) == 97
             S.surface_radiation()
-            total, bad = T._compare(S, fout, len(rows))
+            total, bad = H.compare_with_fixture(S, fout, len(rows))
         assert total >= minimum and not bad, (module, bad)
 
 
 def test_newdata_canopy_temperature():
     with F.dataset("newdata"):
-        d, rows, S, oin, fout = T._prepare("CanopyTemperature")
+        d, rows, S, oin, fout = H.fixture_state("CanopyTemperature")
         S.z0mr[:17] = oin["z0mr"][0]
         S.displar[:17] = oin["displar"][0]
         for k in "utq":
             S[f"forc_hgt_{k}_patch"][:] = oin[f"forc_hgt_{k}"][:, 0]
         S.canopy_temperature()
-        total, bad = T._compare(S, fout, len(rows))
+        total, bad = H.compare_with_fixture(S, fout, len(rows))
     assert total >= 22000 and not bad, bad
     assert (S["t_grnd"] > 273.15).all()  # the warm season: no frozen ground anywhere in this dump
 
 
 def test_newdata_surface_albedo_snow_free():
     with F.dataset("newdata"):
-        d, rows, S, oin, fout = T._prepare("SurfaceAlbedo")
+        d, rows, S, oin, fout = H.fixture_state("SurfaceAlbedo")
         S.albsat[:] = oin["albsat"][0]
         S.albdry[:] = oin["albdry"][0]
         S["isoicol"][:] = 3
         sun, sha = S.albedo_snicar_ex()
-        total, bad = T._compare(S, fout, len(rows), skip=("fabd_sun", "fabd_sha"))
+        total, bad = H.compare_with_fixture(S, fout, len(rows), skip=("fabd_sun", "fabd_sha"))
         for name, got in (("fabd_sun", sun), ("fabd_sha", sha)):
             assert (F.almost_equal(got, fout[name]) | np.isnan(fout[name])).all(), name
     assert total >= 15000 and not bad, bad
@@ -67,7 +67,7 @@ def test_newdata_surface_albedo_snow_free():
 
 def test_newdata_canopy_fluxes():
     with F.dataset("newdata"):
-        steps, got, fout, niters, flags = T._run_canflux(given=True)
+        steps, got, fout, niters, flags = H.run_canflux_fixture(given=True)
     total, nloose, worst = 0, 0, 0.0
     for name, exp in fout.items():
         ok = F.almost_equal(got[name], exp) | np.isnan(exp)

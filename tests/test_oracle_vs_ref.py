@@ -11,7 +11,6 @@ import pytest
 
 from elmkernels_amd import synth
 from oracle import oracle as O
-from tests import fixtures as F
 from tests import helpers as H
 
 pytestmark = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref/libelmref.so not built here")
@@ -26,16 +25,6 @@ def states():
     A = H.oracle_state(cols, scal, soil)
     B = A.clone()
     return A, B
-
-
-def _same(A, B, names=None):
-    diffs = {}
-    for k in names or A.fields:
-        a, b = A.fields[k], B.fields[k]
-        eq = (a == b) | (np.isnan(a.astype(float)) & np.isnan(b.astype(float)))
-        if not eq.all():
-            diffs[k] = (int((~eq).sum()), float(np.max(F.rel_err(a, b, floor=0.0))))
-    return diffs
 
 
 def test_branch_coverage_of_the_synthetic_state(states):
@@ -53,22 +42,22 @@ def test_five_wrappers_bit_exact_vs_reference(states):
     A, B = states
     R = O.Reference()
     A.frac_wet(); R.frac_wet(B)
-    assert not _same(A, B)
+    assert not H.oracle_diffs(A, B)
     A.canopy_hydrology(1800.0); R.canopy_hydrology(B, 1800.0)
-    assert not _same(A, B)
+    assert not H.oracle_diffs(A, B)
     # albedo products come from the oracle on both sides here (the albedo wrapper by the reference's own functions, and all
     # seven wrappers chained by the reference alone: tests/test_oracle_vs_ref_canopy.py)
     A.albedo_snicar()
     for k in A.fields:
         B.fields[k][...] = A.fields[k]
     A.surface_radiation(); R.surface_radiation(B)
-    d = _same(A, B, [k for k in A.fields if k != "err_flags"])
+    d = H.oracle_diffs(A, B, [k for k in A.fields if k != "err_flags"])
     assert not d, d
     A.canopy_temperature(); R.canopy_temperature(B)
-    d = _same(A, B, [k for k in A.fields if k != "err_flags"])
+    d = H.oracle_diffs(A, B, [k for k in A.fields if k != "err_flags"])
     assert not d, d
     A.bareground_fluxes(); R.bareground_fluxes(B)
-    d = _same(A, B, [k for k in A.fields if k != "err_flags"])
+    d = H.oracle_diffs(A, B, [k for k in A.fields if k != "err_flags"])
     assert not d, d
     # the new-snow-layer branch of snow_init must have fired somewhere
     assert (A["snl"] == 1).sum() > 0
@@ -237,7 +226,7 @@ def test_phase_change_bitwise(soil_states):
     A, B = prepared(), prepared()
     A.phase_change(1800.0, ex["hs"][:, 3], c_h2osfc)
     B.phase_change(1800.0, ex["hs"][:, 3], c_h2osfc, lib=O.Reference().R)
-    assert not _same(A, B)
+    assert not H.oracle_diffs(A, B)
     im = np.bincount(A["imelt"].ravel(), minlength=3)
     assert im[1] > 1000 and im[2] > 1000 and (A["qflx_h2osfc_ice"] != 0).sum() > 100  # melting, freezing, pond freezing
     assert (A["qflx_snomelt"] > 0).any() and (A["qflx_snofrz"] > 0).any()
@@ -250,7 +239,7 @@ def test_surface_fluxes_and_conservation_bitwise(soil_states):
     B = A.clone()
     A.surface_fluxes(1800.0)
     B.surface_fluxes(1800.0, lib=O.Reference().R)
-    assert not _same(A, B)
+    assert not H.oracle_diffs(A, B)
     da = A.evaluate_conservation(1800.0)
     db = B.evaluate_conservation(1800.0, lib=O.Reference().R)
     assert np.array_equal(da, db, equal_nan=True)
@@ -265,7 +254,7 @@ def test_init_timestep_column_kernel_bitwise(states):
     A, B = states[0].clone(), states[0].clone()
     A.init_timestep()
     B.init_timestep(lib=O.Reference().R)
-    assert not _same(A, B)
+    assert not H.oracle_diffs(A, B)
     assert np.array_equal(A["h2osno_old"], A["h2osno"]) and (A["do_capsnow"] == (A["h2osno"] > 1000.0)).all()
 
 
@@ -285,7 +274,7 @@ def test_get_forcing_and_phenology_bitwise(states):
         e = rng.random(8)
         A.get_forcing(1.0 - e, e, rh)
         B.get_forcing(1.0 - e, e, rh, lib=R)
-        assert not _same(A, B)
+        assert not H.oracle_diffs(A, B)
         assert (A["forc_tbot"] == 323.0).any() and (A["forc_pbot"] == 4.0e4).any() and (A["forc_hgt_u_patch"] == 30.0).all()
         assert (A["forc_lwrad"] == 700.0).sum() == 0 and np.isfinite(A["forc_lwrad"]).all() and (A["forc_solad"] >= 0).all()
         assert (A["forc_rain"] >= 0).all() and (A["forc_snow"] >= 0).all() and ((A["forc_rain"] > 0) & (A["forc_snow"] > 0)).any()
@@ -295,7 +284,7 @@ def test_get_forcing_and_phenology_bitwise(states):
         X["vtype"][1::7] = 14  # taller than the shrub limit: the 0.2 m burial rule
     A.phenology(0.3, 0.7)
     B.phenology(0.3, 0.7, lib=R)
-    assert not _same(A, B)
+    assert not H.oracle_diffs(A, B)
     assert (A["frac_veg_nosno_alb"] == 0).any() and (A["frac_veg_nosno_alb"] == 1).any() and (A["elai"] == 0).any()
 
 
@@ -326,7 +315,7 @@ def test_initialize_state_bitwise():
         B = A.clone()
         A.initialize_state()
         B.initialize_state(lib=R)
-        assert _same(A, B) == {}, land
+        assert H.oracle_diffs(A, B) == {}, land
         seen_snl |= set(np.unique(A["snl"]).tolist())
         assert np.isfinite(A["watsat"]).all() and (A["watsat"] > 0).all() and (A["watsat"] < 1).all()
     assert seen_snl == {0, 1, 2, 3, 4, 5}
@@ -353,11 +342,11 @@ def test_soil_temperature_whole_wrapper_bitwise(soil_states):
         eb = B.soil_temperature_ref(1800.0)
         for k in ("hs", "rhs", "lhs"):
             assert np.array_equal(ea[k], eb[k], equal_nan=True), (trial, k)
-        assert not _same(A, B), trial
+        assert not H.oracle_diffs(A, B), trial
         # a second solve from the state the first one left (chained, as ELMInterface::advance does)
         A.soil_temperature(1800.0)
         B.soil_temperature_ref(1800.0)
-        assert not _same(A, B), trial
+        assert not H.oracle_diffs(A, B), trial
         assert set(np.unique(A["snl"])) == {0, 1, 2, 3, 4, 5}
         im = np.bincount(A["imelt"].ravel(), minlength=3)
         assert im[1] > 100 and im[2] > 100
@@ -369,9 +358,6 @@ def test_soil_temperature_whole_wrapper_bitwise(soil_states):
 # with the reference's own SnwRdsTable).  Columns in which the reference reads outside an array (the restatement raises a
 # warning bit exactly there) are left out: its result there is whatever lies next to the array.  Not run by the reference: the
 # two whole-array aerosol functions (their only body is a lambda for the Kokkos dispatch): those two stay "parity unpinned".
-WARN_WATER, WARN_COMBINE, ERR_DIVIDE, ERR_AGE = 1 << 12, 1 << 13, 1 << 14, 1 << 15
-
-
 AERO = ("bcphi", "bcpho", "dst1", "dst2", "dst3", "dst4")
 
 
@@ -431,12 +417,12 @@ def test_snow_hydrology_stages_bitwise_vs_reference():
                 if not ref_runs:
                     continue
                 raised = S["err_flags"] & ~before
-                skip = (raised & (WARN_WATER | WARN_COMBINE)) != 0
+                skip = (raised & (H.WARN_WATER | H.WARN_COMBINE)) != 0
                 R["err_flags"][...] = 0
                 threw = R.snow_hydrology_stage(DT, stage, ref=True, skip=skip)
                 ref_threw = (R["err_flags"] >> 31) != 0
                 # the reference throws exactly where the restatement raises the divide_layers radius flag / snow_aging's dr_fresh flag
-                assert threw == int(ref_threw.sum()) and np.array_equal(ref_threw, (raised & (ERR_DIVIDE | ERR_AGE)) != 0), (seed, step, stage)
+                assert threw == int(ref_threw.sum()) and np.array_equal(ref_threw, (raised & (H.ERR_DIVIDE | H.ERR_AGE)) != 0), (seed, step, stage)
                 ok = ~skip & ~ref_threw
                 for k in S.fields:
                     if k == "err_flags":

@@ -21,7 +21,6 @@ from tests import helpers as H
 pytestmark = pytest.mark.skipif(not O.have_ref_canopy(), reason="oracle/_ref/libelmref_canopy.so not built here")
 
 DT = 1800.0
-REF_THREW = np.uint32(1 << 31)
 
 
 def _diff(A, B, skip=("err_flags",)):
@@ -74,7 +73,7 @@ def test_albedo_snicar_whole_wrapper_bitwise(land):
     B = A.clone()
     sun_a, sha_a = A.albedo_snicar_ex()
     sun_b, sha_b = B.albedo_snicar_ref()
-    assert not (B["err_flags"] & REF_THREW).any()
+    assert not (B["err_flags"] & H.REF_THREW).any()
     d = _diff(A, B)
     assert not d, d
     assert np.array_equal(sun_a.view(np.uint64), sun_b.view(np.uint64)) and np.array_equal(sha_a.view(np.uint64), sha_b.view(np.uint64))
@@ -101,7 +100,7 @@ def test_canopy_fluxes_whole_wrapper_bitwise(land):
         for k, v in O.psn_counters().items():
             counts[k] += v
         B.canopy_fluxes_ref(DT)
-        threw = (B["err_flags"] & REF_THREW) != 0
+        threw = (B["err_flags"] & H.REF_THREW) != 0
         # the reference throws where the restatement raises a fatal photosynthesis flag, and nowhere else
         fatal = (A["err_flags"] & np.uint32(0b11100)) != 0
         assert np.array_equal(threw, fatal), (int(threw.sum()), int(fatal.sum()))
@@ -263,7 +262,7 @@ def test_seven_wrappers_chained_by_the_reference():
         ):
             run_a()
             run_b()
-            assert not (B["err_flags"] & REF_THREW).any(), (step, name)
+            assert not (B["err_flags"] & H.REF_THREW).any(), (step, name)
             d = _diff(A, B)
             assert not d, (step, name, d)
     assert (A["t_veg"] != A["forc_tbot"]).any() and (A["snl"] > 0).any()
@@ -290,7 +289,7 @@ def test_reference_functions_on_the_references_own_fixtures():
         B = S.clone()
         S.canopy_fluxes_given(F.TEST_DTIME, oin["forc_rho"][i], oin["forc_po2"][i], oin["forc_pco2"][i])
         B.canopy_fluxes_ref(F.TEST_DTIME, oin["forc_rho"][i], oin["forc_po2"][i], oin["forc_pco2"][i])
-        assert not (B["err_flags"] & REF_THREW).any()
+        assert not (B["err_flags"] & H.REF_THREW).any()
         dd = _diff(S, B)
         assert not dd, (i, dd)
         for name, exp in fout.items():
@@ -324,7 +323,7 @@ def test_reference_throws_where_the_restatement_flags():
     B = A.clone()
     A.albedo_snicar()
     B.albedo_snicar_ref()
-    threw = (B["err_flags"] & REF_THREW) != 0
+    threw = (B["err_flags"] & H.REF_THREW) != 0
     flagged = (A["err_flags"] & np.uint32(1 << 6)) != 0
     assert np.array_equal(threw, flagged) and 20 <= int(threw.sum()) < 400  # (only sunlit columns with a snow pack get there)
     keep = ~threw

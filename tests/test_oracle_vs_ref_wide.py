@@ -7,8 +7,6 @@ import pytest
 from oracle import oracle as O
 from tests import helpers as H
 from tests import parity_cases as P
-from tests.test_oracle_vs_ref import _same
-from tests.test_oracle_vs_ref_canopy import REF_THREW as REF_THREW_BIT
 
 pytestmark = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref/libelmref.so not built here")
 
@@ -28,16 +26,16 @@ def test_five_wrappers_bit_exact_on_wide_inputs(name):
     B = A.clone()
     R = O.Reference()
     A.frac_wet(); R.frac_wet(B)
-    assert not _same(A, B, NOFLAGS(A))
+    assert not H.oracle_diffs(A, B, NOFLAGS(A))
     A.canopy_hydrology(DT); R.canopy_hydrology(B, DT)
-    assert not _same(A, B, NOFLAGS(A))
+    assert not H.oracle_diffs(A, B, NOFLAGS(A))
     A.albedo_snicar()
     for k in A.fields:
         B.fields[k][...] = A.fields[k]
     for a, r in ((A.surface_radiation, R.surface_radiation), (A.canopy_temperature, R.canopy_temperature),
                  (A.bareground_fluxes, R.bareground_fluxes)):
         a(); r(B)
-        d = _same(A, B, NOFLAGS(A))
+        d = H.oracle_diffs(A, B, NOFLAGS(A))
         assert not d, d
     assert not (A["err_flags"] & 0x7FF).any()
 
@@ -49,7 +47,7 @@ def test_snicar_bit_exact_on_wide_inputs():
     B["albsnd"][:] = -1.0
     B["albsni"][:] = -1.0
     O.Reference().snicar(B)
-    assert not (B["err_flags"] & REF_THREW_BIT).any() and not (A["err_flags"] & 0x7FF).any()
+    assert not (B["err_flags"] & H.REF_THREW).any() and not (A["err_flags"] & 0x7FF).any()
     assert np.array_equal(A["albsnd"], B["albsnd"]) and np.array_equal(A["albsni"], B["albsni"])
     snow = (A["coszen"] > 0) & (A["h2osno"] > 0)
     assert set(np.unique(A["snl"][snow])) == {0, 1, 2, 3, 4, 5}
@@ -67,8 +65,8 @@ def test_canopy_fluxes_bit_exact_on_wide_inputs(name):
         A.canopy_fluxes(DT)
         counts = O.psn_counters()
         B.canopy_fluxes_ref(DT)
-        assert not (B["err_flags"] & REF_THREW_BIT).any() and not (A["err_flags"] & 0x7FF).any()
-        d = _same(A, B, NOFLAGS(A))
+        assert not (B["err_flags"] & H.REF_THREW).any() and not (A["err_flags"] & 0x7FF).any()
+        d = H.oracle_diffs(A, B, NOFLAGS(A))
         assert not d, (step, d)
     assert counts["brent"] > 0 and counts["c4"] > 0, counts
 
@@ -82,7 +80,7 @@ def test_soil_temperature_and_surface_fluxes_bit_exact_on_wide_inputs(name):
     B = A.clone()
     A.soil_temperature(DT)
     B.soil_temperature_ref(DT)
-    d = _same(A, B, NOFLAGS(A))
+    d = H.oracle_diffs(A, B, NOFLAGS(A))
     assert not d, d
     im = np.bincount(A["imelt"].ravel(), minlength=3)
     assert im[1] > 0 and im[2] > 0 and (A["qflx_h2osfc_ice"] != 0).any()
@@ -92,15 +90,13 @@ def test_soil_temperature_and_surface_fluxes_bit_exact_on_wide_inputs(name):
     B = A.clone()
     A.surface_fluxes(DT)
     B.surface_fluxes(DT, lib=O.Reference().R)
-    assert not _same(A, B)
+    assert not H.oracle_diffs(A, B)
     assert np.array_equal(A.evaluate_conservation(DT), B.evaluate_conservation(DT, lib=O.Reference().R), equal_nan=True)
     assert limited.any()
 
 
 @pytest.mark.skipif(O.lib().ref_snow is None, reason="oracle/_ref/libelmref_snow.so not built here")
 def test_snow_hydrology_stages_bit_exact_on_wide_inputs():
-    from tests.test_oracle_vs_ref import ERR_AGE, ERR_DIVIDE, WARN_COMBINE, WARN_WATER
-
     S = _wide("W_advance")
     merged = 0
     for step in range(3):
@@ -115,11 +111,11 @@ def test_snow_hydrology_stages_bit_exact_on_wide_inputs():
             if R is None:
                 continue
             raised = S["err_flags"] & ~before
-            skip = (raised & (WARN_WATER | WARN_COMBINE)) != 0
+            skip = (raised & (H.WARN_WATER | H.WARN_COMBINE)) != 0
             R["err_flags"][...] = 0
             R.snow_hydrology_stage(DT, stage, ref=True, skip=skip)
             ref_threw = (R["err_flags"] >> 31) != 0
-            assert np.array_equal(ref_threw, (raised & (ERR_DIVIDE | ERR_AGE)) != 0), (step, stage)
+            assert np.array_equal(ref_threw, (raised & (H.ERR_DIVIDE | H.ERR_AGE)) != 0), (step, stage)
             ok = ~skip & ~ref_threw
             for k in NOFLAGS(S):
                 a, b = S.fields[k][ok], R.fields[k][ok]

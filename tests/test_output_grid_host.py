@@ -9,16 +9,10 @@ import numpy as np
 from elmkernels_amd import _lib as L
 from elmkernels_amd import decomp
 from elmkernels_amd import regrid as R
+from tests.support import ROOT, same_nan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "elmk.h")).read()
 ENTRY_POINTS = {"elmk_set_output_grid", "elmk_clear_output_grid", "elmk_download_gridded", "elmk_gridded_history_add"}
-
-
-def same(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))))
 
 
 def loop_aggregate(ptr, col, w, x, fill):
@@ -66,8 +60,8 @@ def test_apply_aggregate_equals_a_plain_loop_bit_for_bit():
     got = R.apply_aggregate(ptr, col, w, x, -999.0)
     assert got.shape == (3, ncells)
     for r in range(3):
-        assert same(got[r], loop_aggregate(ptr, col, w, x[r], -999.0))
-        assert same(R.apply_aggregate(ptr, col, w, x[r], -999.0), got[r])
+        assert same_nan(got[r], loop_aggregate(ptr, col, w, x[r], -999.0))
+        assert same_nan(R.apply_aggregate(ptr, col, w, x[r], -999.0), got[r])
     assert got[0, 7] == -999.0
 
 
@@ -83,9 +77,9 @@ def test_apply_aggregate_keeps_negative_zero_and_propagates_nan_and_inf():
     assert np.isnan(v[3])  # NaN term
     assert v[4] == np.inf
     assert v[5] == 3.0
-    assert same(v, loop_aggregate(ptr, col, w, x, np.nan))
+    assert same_nan(v, loop_aggregate(ptr, col, w, x, np.nan))
     # a map with no terms at all
-    assert same(R.apply_aggregate([0, 0, 0], [], [], x, 5.0), [5.0, 5.0])
+    assert same_nan(R.apply_aggregate([0, 0, 0], [], [], x, 5.0), [5.0, 5.0])
 
 
 def test_owner_map_weights_are_area_fractions():
@@ -127,7 +121,7 @@ def test_from_sparse_cells_orders_terms_by_column_per_cell():
         assert np.array_equal(c[ptr[i]:ptr[i + 1]], col[want])
         assert np.array_equal(w[ptr[i]:ptr[i + 1]], S[want])
     x = rng.standard_normal(ncols)
-    assert same(R.apply_aggregate(ptr, c, w, x, -1.0), loop_aggregate(ptr, c, w, x, -1.0))
+    assert same_nan(R.apply_aggregate(ptr, c, w, x, -1.0), loop_aggregate(ptr, c, w, x, -1.0))
 
 
 def test_slice_output_map_over_all_ranks_reproduces_the_global_result():
@@ -145,7 +139,7 @@ def test_slice_output_map_over_all_ranks_reproduces_the_global_result():
         c0, n = decomp.block_range(ncols, 7, rank)
         pl, cl, wl, cells, straddling = R.slice_output_map(ptr, col, w, c0, n)
         assert pl.size == cells.size + 1 and np.all((cl >= 0) & (cl < n))
-        assert same(R.apply_aggregate(pl, cl, wl, x[c0:c0 + n], np.nan), want[cells])
+        assert same_nan(R.apply_aggregate(pl, cl, wl, x[c0:c0 + n], np.nan), want[cells])
         seen.append(cells)
         strad |= set(straddling.tolist())
     seen = np.concatenate(seen)

@@ -12,8 +12,8 @@ from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests import helpers as H
+from tests.support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT = 1800.0
 SERIES = st.SERIES_FORCING + st.SERIES_PHENOLOGY
 PRIMARY_VARS = ("snl", "snow_depth", "frac_sno", "int_snow", "snw_rds", "h2osoi_liq", "h2osoi_ice", "h2osoi_vol", "h2ocan", "h2osno",

@@ -14,8 +14,8 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import restart as R
 from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
+from tests.support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53  # the unit roundoff of fp64
 
 

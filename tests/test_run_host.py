@@ -9,8 +9,8 @@ import pytest
 
 from elmkernels_amd import _lib as L
 from elmkernels_amd import state as st
+from tests.support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "elmk.h")).read()
 MEMBERS = ("decday", "doy", "forc_slot", "forc_wt1", "forc_wt2", "month1", "month2", "month_wt1", "month_wt2")
 

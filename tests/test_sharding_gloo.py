@@ -16,7 +16,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
+
 N_GLOBAL = 3001  # odd on purpose: ranks get different sizes
 SEED = 31
 

@@ -17,7 +17,6 @@ from tests import helpers as H
 DT = 1800.0
 TFRZ, CPICE, CPWAT, HFUS = 273.15, 2.11727e3, 4.188e3, 3.337e5
 AER = ("mss_bcphi", "mss_bcpho", "mss_dst1", "mss_dst2", "mss_dst3", "mss_dst4")
-WARN_WATER, WARN_COMBINE, ERR_DIVIDE, ERR_AGE = 1 << 12, 1 << 13, 1 << 14, 1 << 15
 
 
 def _state(n=6016, seed=5, tier="B"):
@@ -91,8 +90,8 @@ def test_combine_and_divide_conserve_mass_and_energy():
         before = dict(ice=a["ice"][:6].sum(), liq=a["liq"][:6].sum(), H=_enthalpy(a), dz=a["dz"][:5].sum(),
                       **{k: a[k].sum() for k in AER})
         snl2, sc, err = _call_combine(lib, a, snl)
-        assert 0 <= snl2 <= snl and not (err & ~WARN_COMBINE)
-        noob += bool(err & WARN_COMBINE)
+        assert 0 <= snl2 <= snl and not (err & ~H.WARN_COMBINE)
+        noob += bool(err & H.WARN_COMBINE)
         gone = snl2 == 0 and snl > 0 and sc[0] > 0 and a["ice"][:5].sum() > 0  # "all snow gone": ice stays in h2osno
         # water and ice of the pack + the top soil level (what leaves the pack goes there): nothing is lost.  (Levels above
         # the new top keep stale copies of shifted elements until prune_snow_layers zeroes them: they are not counted.)
@@ -116,7 +115,7 @@ def test_combine_and_divide_conserve_mass_and_energy():
                 a[k][:5 - snl2] = 0.0
             i0, l0, h0, d0 = a["ice"][:5].sum(), a["liq"][:5].sum(), _enthalpy(a), a["dz"][:5].sum()
             snl3, err3 = _call_divide(lib, a, snl2)
-            assert snl2 <= snl3 <= 5 and not (err3 & ~ERR_DIVIDE)
+            assert snl2 <= snl3 <= 5 and not (err3 & ~H.ERR_DIVIDE)
             ndiv += snl3 > snl2
             assert abs(a["ice"][:5].sum() - i0) <= 1e-12 * i0 and abs(a["liq"][:5].sum() - l0) <= 1e-12 * l0 + 1e-18
             assert abs(a["dz"][5 - snl3:5].sum() - d0) <= 1e-12 * d0
@@ -147,7 +146,7 @@ def test_combine_out_of_bounds_choice_is_flagged_only_for_five_layers():
         a = _pack(rng, snl, thin=True)
         a["ice"][5 - snl:5] = np.maximum(a["ice"][5 - snl:5], 0.05)  # keep the first (ice <= 0.01) loop out of it
         _, _, err = _call_combine(lib, a, snl)
-        flagged = bool(err & WARN_COMBINE)
+        flagged = bool(err & H.WARN_COMBINE)
         seen[flagged] += 1
         if flagged:
             assert snl == 5
@@ -158,9 +157,9 @@ def test_snow_water_out_of_bounds_choice_is_flagged_only_when_taken():
     S = _state()
     snl0 = S["snl"].copy()
     S.snow_hydrology(DT)
-    flagged = (S["err_flags"] & WARN_WATER) != 0
+    flagged = (S["err_flags"] & H.WARN_WATER) != 0
     assert flagged.any() and not flagged[snl0 < 2].any()  # needs the layer pair (3, 4): at least two layers
-    assert not (S["err_flags"] & np.uint32(0xFFFFFFFF ^ (WARN_WATER | WARN_COMBINE | ERR_DIVIDE | ERR_AGE))).any()
+    assert not (S["err_flags"] & np.uint32(0xFFFFFFFF ^ (H.WARN_WATER | H.WARN_COMBINE | H.ERR_DIVIDE | H.ERR_AGE))).any()
 
 
 def test_whole_wrapper_keeps_the_water_and_the_mesh():
@@ -200,7 +199,7 @@ def test_whole_wrapper_keeps_the_water_and_the_mesh():
     ok = lay0 & (snl > 0) & (S["mflx_neg_snow"] == 0)
     resid = np.abs(w1 - w0 - src)[ok]
     assert np.percentile(resid, 95) < 1e-9
-    assert not (S["err_flags"] & ERR_AGE).any()
+    assert not (S["err_flags"] & H.ERR_AGE).any()
 
 
 def test_idempotent_without_fluxes():

@@ -10,7 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
+
 CSRC = os.path.join(ROOT, "elmkernels_amd", "csrc")
 
 

@@ -12,15 +12,14 @@ from elmkernels_amd import diagnostics as D
 from elmkernels_amd import hydrology as hy
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
-from tests.test_frost_table_host import generated_frost
-from tests.test_hydrology_host import CHAIN_STEPS, DT, water_mass
+from tests.hydrology_cases import CHAIN_STEPS, DT, generated_frost, water_mass
+from tests.support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = hy.N
 
 
 def wb_host_chain(cols, scal, soil, rows, frost, nsteps=CHAIN_STEPS, dt=DT):
-    """test_hydrology_host.host_chain (frost: test_frost_table_host.frost_host_chain) with W0 after init_timestep and W1 - W6 after the
+    """hydrology_cases.host_chain (frost: test_frost_table_host.frost_host_chain) with W0 after init_timestep and W1 - W6 after the
     stage.  Per step: the rows of the feature, the same without W3's last term, hydrology.water_balance_error of the step and
     qflx_snwcp_liq."""
     from tests import helpers as H
