@@ -151,6 +151,10 @@ SIGNATURES = {
     "elmk_routing_set_withdrawal": (C.c_int, [_P, C.c_int]),
     "elmk_routing_budget": (C.c_int, [_P, _P]),
     "elmk_routing_clear": (C.c_int, [_P]),
+    "elmk_routing_kinematic_enable": (C.c_int, [_P, _P]),
+    "elmk_routing_kinematic_init": (C.c_int, [_P, _P, _P]),
+    "elmk_routing_kinematic_budget": (C.c_int, [_P, _P]),
+    "elmk_routing_kinematic_clear": (C.c_int, [_P]),
     "elmk_column_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_gridded_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
 }

@@ -1,12 +1,16 @@
 // api_routing.cpp - runoff routing (k_routing.hip; include/elmk.h "runoff routing"): the cell rows VOLR, QIN, QOUT, QOUT_SUM over the
 // output grid's cells, the network's parameter rows and upstream map and the budget's reduction scratch, in one allocation held
-// exactly while the feature is enabled.
+// exactly while the feature is enabled; and the stage's second scheme, kinematic-wave routing (include/elmk.h "kinematic-wave
+// routing"), whose rows WH, WT, QSUR and derived parameters live in a second allocation held exactly while that scheme is on.
 #include "elmk_ctx.h"
 
 namespace {
 // ELMK_ROUTE_* -> the row of the allocation (the budget's three rows lie first: elmk_kernels.h)
 constexpr int ROUTE_ROW_OF[4] = {ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT, ROUTE_QOUT_SUM};
 static_assert(ELMK_ROUTE_VOLR == 0 && ELMK_ROUTE_QIN == 1 && ELMK_ROUTE_QOUT == 2 && ELMK_ROUTE_QOUT_SUM == 3, "four rows");
+// the kinematic-wave scheme's public rows are the first three of its own allocation
+static_assert(ELMK_ROUTE_WH - 4 == KW_WH && ELMK_ROUTE_WT - 4 == KW_WT && ELMK_ROUTE_QSUR - 4 == KW_QSUR, "three rows");
+static_assert(ELMK_KW_NPARAM == KINEMATIC_NPARAM, "the parameter rows of elmk_maps.h");
 
 RouteArgs route_args(const elmk_ctx* ctx)
 {
@@ -19,6 +23,12 @@ int route_enter(elmk_ctx* ctx, const char* who)
   if (int rc = enter(ctx)) return rc;
   return ctx->route.mem ? ELMK_OK : invalid(ctx, (std::string(who) + ": not enabled (elmk_routing_enable)").c_str());
 }
+
+int kinematic_enter(elmk_ctx* ctx, const char* who)
+{
+  if (int rc = route_enter(ctx, who)) return rc;
+  return ctx->route.kw_mem ? ELMK_OK : invalid(ctx, (std::string(who) + ": the scheme is not on (elmk_routing_kinematic_enable)").c_str());
+}
 }  // namespace
 
 namespace elmk {
@@ -27,8 +37,15 @@ void route_launch(elmk_ctx* ctx, double dt)
   const elmk_ctx::Routing& T = ctx->route;
   const CsrMap& M = ctx->ogrid.map;
   const size_t ld = (size_t)ctx->ld;
-  launch_routing(route_args(ctx), OGridMap{M.ptr, M.col, M.w, M.nrows, 0.0}, ctx->wb_rows + (size_t)ELMK_WB_QRUNOFF * ld,
-                 T.withdraw ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * ld : nullptr, dt, ctx->stream);
+  const OGridMap G{M.ptr, M.col, M.w, M.nrows, 0.0};
+  const double* const qrunoff = ctx->wb_rows + (size_t)ELMK_WB_QRUNOFF * ld;
+  const double* const qirr = T.withdraw ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * ld : nullptr;
+  if (T.kw_mem)  // the scheme switch: the kinematic-wave scheme exactly while its memory is held
+    launch_routing_kinematic(route_args(ctx), KinematicArgs{T.kw_rows, T.kw_par}, G, qrunoff, qirr,
+                             ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
+                             ctx->stream);
+  else
+    launch_routing(route_args(ctx), G, qrunoff, qirr, dt, ctx->stream);
 }
 
 int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal)
@@ -124,13 +141,13 @@ int elmk_routing_read(elmk_ctx* ctx, int which, double* host, int64_t cell0, int
 {
   const char* who = "elmk_routing_read";
   if (int rc = route_enter(ctx, who)) return rc;
-  if (which < 0 || which > ELMK_ROUTE_QOUT_SUM) return invalid(ctx, "elmk_routing_read: unknown row");
   const elmk_ctx::Routing& T = ctx->route;
+  if (which < 0 || which > (T.kw_mem ? ELMK_ROUTE_QSUR : ELMK_ROUTE_QOUT_SUM)) return invalid(ctx, "elmk_routing_read: unknown row");
   if (int rc = check_range(ctx, who, host, cell0, n, T.ncells, "cell")) return rc;
   if (int rc = refuse_capture(ctx, who)) return rc;
-  if (n > 0)
-    HIPCHK(hipMemcpyAsync(host, T.rows + (size_t)ROUTE_ROW_OF[which] * (size_t)T.cld + (size_t)cell0, (size_t)n * 8, hipMemcpyDeviceToHost,
-                          ctx->stream));
+  const double* const row = which > ELMK_ROUTE_QOUT_SUM ? T.kw_rows + (size_t)(which - ELMK_ROUTE_WH) * (size_t)T.cld
+                                                         : T.rows + (size_t)ROUTE_ROW_OF[which] * (size_t)T.cld;
+  if (n > 0) HIPCHK(hipMemcpyAsync(host, row + (size_t)cell0, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   return synced(ctx);
 }
 
@@ -175,6 +192,81 @@ int elmk_routing_budget(elmk_ctx* ctx, double* sums)
   HIPCHK(hipMemcpyAsync(mms, T.out, sizeof mms, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (int k = 0; k < 3; k++) sums[k] = mms[3 * k + 2];
+  return ELMK_OK;
+}
+
+int elmk_routing_kinematic_enable(elmk_ctx* ctx, const double* params)
+{
+  const char* who = "elmk_routing_kinematic_enable";
+  if (int rc = route_enter(ctx, who)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  if (!ctx->hyd_rows) return invalid(ctx, "elmk_routing_kinematic_enable: the soil hydrology is not enabled (elmk_soil_hydrology_enable)");
+  if (T.kw_mem) return invalid(ctx, "elmk_routing_kinematic_enable: already on");
+  std::vector<double> par;
+  if (int rc = invalid_map(ctx, who, kinematic_check(T.ncells, params, T.cld, &par))) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the scheme of its moment)
+  const size_t cld = (size_t)T.cld;
+  const auto off = [&] {
+    T.kw_mem = DevBuf<char>{};
+    T.kw_rows = T.kw_par = nullptr;
+  };
+  if (hip_fail(ctx, carve(T.kw_mem, [&](Carve& L) {
+                 L.take(T.kw_rows, (size_t)KW_NROWS * cld * sizeof(double));
+                 L.take(T.kw_par, (size_t)KW_NPAR * cld * sizeof(double));
+               }), "hipMalloc(kinematic-wave routing)")) {
+    off();
+    return ELMK_E_NOMEM;
+  }
+  if (hip_fail(ctx, hipMemsetAsync(T.kw_mem, 0, T.kw_mem.bytes(), ctx->stream), "hipMemset(kinematic-wave routing)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.kw_par, par.data(), par.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream),
+               "hipMemcpy(kinematic-wave routing parameters)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    off();
+    return ELMK_E_HIP;
+  }
+  return ELMK_OK;
+}
+
+int elmk_routing_kinematic_init(elmk_ctx* ctx, const double* wh, const double* wt)
+{
+  const char* who = "elmk_routing_kinematic_init";
+  if (int rc = kinematic_enter(ctx, who)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  const size_t cld = (size_t)T.cld, n = (size_t)T.ncells;
+  HIPCHK(hipMemsetAsync(T.kw_rows, 0, (size_t)KW_NROWS * cld * sizeof(double), ctx->stream));
+  if (wh) HIPCHK(hipMemcpyAsync(T.kw_rows + KW_WH * cld, wh, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (wt) HIPCHK(hipMemcpyAsync(T.kw_rows + KW_WT * cld, wt, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  return synced(ctx);
+}
+
+int elmk_routing_kinematic_budget(elmk_ctx* ctx, double* sums)
+{
+  const char* who = "elmk_routing_kinematic_budget";
+  if (int rc = kinematic_enter(ctx, who)) return rc;
+  if (!sums) return invalid(ctx, "elmk_routing_kinematic_budget: null argument");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  const elmk_ctx::Routing& T = ctx->route;
+  launch_min_max_sum(T.kw_rows, T.cld, T.ncells, 2, T.part, T.out, ctx->stream);  // K8 (the routing's partials: both budgets synchronise)
+  HIPCHK(hipGetLastError());
+  double mms[6];
+  HIPCHK(hipMemcpyAsync(mms, T.out, sizeof mms, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 2; k++) sums[k] = mms[3 * k + 2];
+  return ELMK_OK;
+}
+
+int elmk_routing_kinematic_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_routing_kinematic_clear")) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  if (!T.kw_mem) return ELMK_OK;
+  if (int rc = quiesce(ctx, false)) return rc;
+  T.kw_mem = DevBuf<char>{};
+  T.kw_rows = T.kw_par = nullptr;
   return ELMK_OK;
 }
 

@@ -292,6 +292,11 @@ struct elmk_ctx {
     int32_t* down = nullptr;
     double* part = nullptr;
     double* out = nullptr;
+    // the kinematic-wave scheme (elmk_routing_kinematic_*): a second allocation with the rows [KW_NROWS][cld] and the derived
+    // parameters [KW_NPAR][cld], held exactly while the scheme is on; route_launch takes the scheme whose memory is there
+    DevBuf<char> kw_mem;
+    double* kw_rows = nullptr;
+    double* kw_par = nullptr;
   } route;
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the

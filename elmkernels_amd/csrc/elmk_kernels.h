@@ -295,6 +295,20 @@ struct RouteArgs {
 // then nsub sub-step launches; the storages end in row ROUTE_VOLR
 void launch_routing(const RouteArgs& A, const OGridMap& M, const double* qrunoff, const double* qirr, double dt, hipStream_t st);
 void launch_routing_outlets(const RouteArgs& A, const int32_t* down, hipStream_t st);
+// kinematic-wave routing (k_routing.hip, elmk_routing_kinematic_*): the scheme's own fp64 rows [KW_NROWS][cld] beside the routing's.  The
+// first two are the ones launch_min_max_sum reduces for K8; KW_QSUB (QIN - QSUR) and the two flow buffers KW_ER_A / KW_ER_B (the main
+// channel's er of every cell, written by one launch and gathered by the next) are internal.  par: the derived parameter rows
+// [KW_NPAR][cld] (elmk_maps.h: kinematic_check).
+enum { KW_WH = 0, KW_WT = 1, KW_QSUR = 2, KW_QSUB = 3, KW_ER_A = 4, KW_ER_B = 5, KW_NROWS = 6 };
+enum { KW_CH = 0, KW_CT = 1, KW_CR = 2, KW_TLEN = 3, KW_TWIDTH = 4, KW_RLEN = 5, KW_RWIDTH = 6, KW_NPAR = 7 };
+struct KinematicArgs {
+  double* rows;
+  const double* par;
+};
+// one call: K1 (QIN as R1, QSUR from the hydrology's rows qsurf + qh2osfc, QSUB, the first er) as one launch, then nsub sub-step
+// launches that update WH, WT and VOLR in place; A.kout and ROUTE_VOLR_B are not read
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const OGridMap& M, const double* qrunoff, const double* qirr,
+                              const double* qsurf, const double* qh2osfc, double dt, hipStream_t st);
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

@@ -111,4 +111,47 @@ inline const char* route_check(int64_t ncells, const int32_t* down, const double
   return nullptr;
 }
 
+// Kinematic-wave routing parameters (elmk_routing_kinematic_enable; include/elmk.h "kinematic-wave routing"): params as
+// [KINEMATIC_NPARAM][ncells] in the order of ELMK_KW_*, every value finite and > 0.  Checks row by row, in row order; the text names
+// the first failing row.  For accepted parameters dev holds the seven rows the device keeps, [7][ld] with ld >= ncells in the order CH,
+// CT, CR, TLEN, TWIDTH, RLEN, RWIDTH (elmk_kernels.h: KW_*), padding cells 1.0: CH = (sqrt(HSLP) / NH) * GXR, CT = sqrt(TSLP) / NT,
+// CR = sqrt(RSLP) / NR, each operation rounded once.
+constexpr int KINEMATIC_NPARAM = 11;
+inline const char* kinematic_check(int64_t ncells, const double* params, int64_t ld, std::vector<double>* dev)
+{
+  static const char* const bad[KINEMATIC_NPARAM] = {
+      "HSLP not finite and > 0",   "NH not finite and > 0",   "GXR not finite and > 0",  "TLEN not finite and > 0",
+      "TWIDTH not finite and > 0", "TSLP not finite and > 0", "NT not finite and > 0",   "RLEN not finite and > 0",
+      "RWIDTH not finite and > 0", "RSLP not finite and > 0", "NR not finite and > 0"};
+  if (ncells < 1 || ncells > INT32_MAX) return "ncells outside 1 .. 2^31-1";
+  if (!params) return "null argument";
+  const size_t n = (size_t)ncells;
+  for (int k = 0; k < KINEMATIC_NPARAM; k++) {
+    const double* row = params + (size_t)k * n;
+    size_t c = 0;
+    for (; c < n; c++)
+      if (!(std::isfinite(row[c]) && row[c] > 0.0)) break;
+    if (c < n) return bad[k];
+  }
+  if (dev) {
+    if (ld < ncells) ld = ncells;
+    const size_t l = (size_t)ld;
+    dev->assign((size_t)7 * l, 1.0);
+    const double *hslp = params, *nh = params + n, *gxr = params + 2 * n, *tlen = params + 3 * n, *twidth = params + 4 * n,
+                 *tslp = params + 5 * n, *nt = params + 6 * n, *rlen = params + 7 * n, *rwidth = params + 8 * n, *rslp = params + 9 * n,
+                 *nr = params + 10 * n;
+    double* d = dev->data();
+    for (size_t c = 0; c < n; c++) {
+      d[c] = (std::sqrt(hslp[c]) / nh[c]) * gxr[c];  // (no addition in any of the three: nothing a host compiler could contract)
+      d[l + c] = std::sqrt(tslp[c]) / nt[c];
+      d[2 * l + c] = std::sqrt(rslp[c]) / nr[c];
+      d[3 * l + c] = tlen[c];
+      d[4 * l + c] = twidth[c];
+      d[5 * l + c] = rlen[c];
+      d[6 * l + c] = rwidth[c];
+    }
+  }
+  return nullptr;
+}
+
 }  // namespace elmk

@@ -14,6 +14,7 @@
 // together.  The flow of an upstream cell is evaluated again from its storage rather than read from a row of flows: the same bits,
 // one row less to write and read.  A cell reads 8 (storage) + 8 (KOUT) + 8 (QIN) + 4 npad (map) + 16 per upstream cell and, past the
 // first sub-step, 8 (the flow sum), and writes 16.  The unit carries no nontemporal hint: none has been measured for it.
+// The second scheme of the stage, kinematic-wave routing (k_kinematic_prep, k_kinematic_step), follows the linear one below.
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
 
@@ -162,6 +163,167 @@ void launch_routing_outlets(const RouteArgs& A, const int32_t* down, hipStream_t
   if (A.ncells <= 0) return;
   hipLaunchKernelGGL(k_routing_outlets, dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st, (gptr<const int32_t>)down,
                      (gptr<const double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_OUTLET * A.cld), A.ncells);
+}
+
+// ---- kinematic-wave routing (include/elmk.h "kinematic-wave routing", K0 - K9; elmkernels_amd/routing.py: kinematic_call) ----------
+// The second scheme of the stage: three stores per cell (hillslope WH, tributaries WT, main channel VOLR), each released by Manning's
+// equation.  One thread per cell and 256-thread workgroups as above.  A cell's own three storages are read and written by its own
+// thread only, so they update in place; what crosses cells is the main channel's flow er, and it goes through a row of flows in two
+// buffers: the K1 launch writes the er of the call's first sub-step, every sub-step but the last writes the er of its new VOLR into
+// the other buffer, and the next sub-step gathers from there.  That is the same operands through the same operations as evaluating
+// er again from the upstream storages (the linear kernel's way), at 8 bytes per upstream slot instead of a pow, four divisions and four
+// gathers.  pow is elmk_pow with its tables in global memory: a thread evaluates it three times per launch, outside any loop, and a
+// workgroup's copy of the tables into LDS (elmk_math_lds_init: 7 KB, 3.5 loads per thread) would cost as many vector-memory loads as
+// the lookups it saves; the 5 KB the three evaluations touch stay in L1 / L2.  No LDS, no fences, no nontemporal hint (no A/B run).
+namespace {
+constexpr double KW_T23 = 2.0 / 3.0, KW_T53 = 5.0 / 3.0;
+
+// K2 with the rate formed only where it is taken (K9: any other storage releases nothing)
+// K3
+__device__ __forceinline__ double kw_hill(double wh, double area, double ch, double dts)
+{
+  if (!(area > 0.0) || !(wh > 0.0)) return 0.0;
+  const double h = wh / area;
+  const double a = (ch * elmk_pow(h, KW_T53)) * area, b = wh / dts;
+  return a < b ? a : b;
+}
+// K4
+__device__ __forceinline__ double kw_chan(double w, double len, double wid, double c, double dts)
+{
+  if (!(w > 0.0)) return 0.0;
+  const double a = w / len;
+  const double y = a / wid;
+  const double p = wid + 2.0 * y;
+  const double r = a / p;
+  const double q = (c * elmk_pow(r, KW_T23)) * a, b = w / dts;
+  return q < b ? q : b;
+}
+}  // namespace
+
+// K1: QIN as k_routing_qin, QSUR from the hydrology's two surface rows in the same order, QSUB, and the er of the first sub-step
+template <bool WITHDRAW>
+__global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
+                                                        gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
+                                                        gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
+                                                        gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
+                                                        gptr<double> er, int64_t ncells, int64_t cld, double dts)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncells) return;
+  const int64_t p0 = ptr[c], p1 = ptr[c + 1];
+  double r = 0.0, i = 0.0, s = 0.0;
+  for (int64_t p = p0; p < p1; p++) {
+    const int32_t k = col[p];
+    const double wp = w[p];
+    const double x = wp * qrunoff[k];
+    r = p == p0 ? x : r + x;
+    if constexpr (WITHDRAW) {
+      const double y = wp * qirr[k];
+      i = p == p0 ? y : i + y;
+    }
+    const double z = wp * (qsurf[k] + qh2osfc[k]);
+    s = p == p0 ? z : s + z;
+  }
+  if constexpr (WITHDRAW) r = r - i;
+  const double ar = area[c];
+  const double q = (r * 0.001) * ar, qs = (s * 0.001) * ar;
+  route_st(qin + c, q);
+  route_st(qsur + c, qs);
+  route_st(qsub + c, q - qs);
+  er[c] = kw_chan(volr[c], par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+}
+
+// K3 - K7: one sub-step.  er_old: the flows of the sub-step's start; er_new: those of its end (not written by the LAST one).  FIRST and
+// LAST as k_routing_step's.
+template <int NPAD, bool FIRST, bool LAST>
+__global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
+                                                        gptr<double> er_new, gptr<const double> par, gptr<const double> area,
+                                                        gptr<const int32_t> up, gptr<const double> qsur, gptr<const double> qsub,
+                                                        gptr<double> qout, gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts,
+                                                        double dnsub)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncells) return;
+  int32_t u[NPAD];
+#pragma unroll
+  for (int p = 0; p < NPAD; p++) u[p] = up[(int64_t)p * cld + c];
+  const double er = er_old[c];
+  double eu[NPAD];
+#pragma unroll
+  for (int p = 0; p < NPAD; p++) eu[p] = er_old[u[p] >= 0 ? (int64_t)u[p] : c];
+  const double wh = wh_row[c], wt = wt_row[c], v = volr[c], ar = area[c], qs = qsur[c], qb = qsub[c];
+  double qacc = 0.0;
+  if constexpr (!FIRST) qacc = qout[c];
+  const double eh = kw_hill(wh, ar, par[KW_CH * cld + c], dts);
+  const double et = kw_chan(wt, par[KW_TLEN * cld + c], par[KW_TWIDTH * cld + c], par[KW_CT * cld + c], dts);
+  double fin = 0.0;
+#pragma unroll
+  for (int p = 0; p < NPAD; p++)
+    if (u[p] >= 0) fin = fin + eu[p];
+  route_st(wh_row + c, wh + (qs - eh) * dts);
+  route_st(wt_row + c, wt + ((eh - et) + qb) * dts);
+  double vn = v + ((fin - er) + et) * dts;
+  if (vn != vn) vn = __builtin_nan("");
+  volr[c] = vn;
+  qacc = qacc + er;
+  if constexpr (LAST) {
+    const double mean = qacc / dnsub;
+    route_st(qout + c, mean);
+    route_st(qout_sum + c, qout_sum[c] + mean);
+  } else {
+    route_st(qout + c, qacc);
+    er_new[c] = kw_chan(vn, par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+  }
+}
+
+namespace {
+template <int NPAD, bool FIRST, bool LAST>
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const double* er_old, double* er_new, double dts, hipStream_t st)
+{
+  hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
+                     (gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld),
+                     (gptr<double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)er_old, (gptr<double>)er_new,
+                     (gptr<const double>)K.par, (gptr<const double>)A.area, (gptr<const int32_t>)A.up,
+                     (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<const double>)(K.rows + KW_QSUB * A.cld),
+                     (gptr<double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts,
+                     (double)A.nsub);
+}
+template <int NPAD>
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const double* er_old, double* er_new, double dts, bool first, bool last,
+                    hipStream_t st)
+{
+  if (first && last) launch_kw_step<NPAD, true, true>(A, K, er_old, er_new, dts, st);
+  else if (first) launch_kw_step<NPAD, true, false>(A, K, er_old, er_new, dts, st);
+  else if (last) launch_kw_step<NPAD, false, true>(A, K, er_old, er_new, dts, st);
+  else launch_kw_step<NPAD, false, false>(A, K, er_old, er_new, dts, st);
+}
+}  // namespace
+
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const OGridMap& M, const double* qrunoff, const double* qirr,
+                              const double* qsurf, const double* qh2osfc, double dt, hipStream_t st)
+{
+  if (A.ncells <= 0) return;
+  const dim3 grid((unsigned)((A.ncells + 255) / 256)), block(256);
+  const double dts = dt / (double)A.nsub;  // K0
+  double *src = K.rows + KW_ER_A * A.cld, *dst = K.rows + KW_ER_B * A.cld;
+  const auto prep = qirr ? k_kinematic_prep<true> : k_kinematic_prep<false>;
+  hipLaunchKernelGGL(prep, grid, block, 0, st, (gptr<const int64_t>)M.ptr, (gptr<const int32_t>)M.col, (gptr<const double>)M.w,
+                     (gptr<const double>)qrunoff, (gptr<const double>)qirr, (gptr<const double>)qsurf, (gptr<const double>)qh2osfc,
+                     (gptr<const double>)A.area, (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
+                     (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
+                     (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts);
+  for (int s = 0; s < A.nsub; s++) {
+    const bool first = s == 0, last = s == A.nsub - 1;
+    switch (A.npad) {
+      case 1: launch_kw_step<1>(A, K, src, dst, dts, first, last, st); break;
+      case 2: launch_kw_step<2>(A, K, src, dst, dts, first, last, st); break;
+      case 4: launch_kw_step<4>(A, K, src, dst, dts, first, last, st); break;
+      default: launch_kw_step<8>(A, K, src, dst, dts, first, last, st); break;
+    }
+    double* const t = src;
+    src = dst;
+    dst = t;
+  }
 }
 
 }  // namespace elmk

@@ -12,10 +12,21 @@ helpers a driver needs.
 
     qin = qin_from_rows(ptr, col, w, qrunoff, area)
     volr, qout = call(volr, qin, effvel / ddist, upstream_map(down), dt, nsub)
+
+The kinematic-wave scheme (include/elmk.h "kinematic-wave routing"; k_kinematic_prep, k_kinematic_step), after S.soil_hydrology_enable:
+
+    S.routing_kinematic_enable(params)                                  # [11, ncells]: HSLP .. NR
+    S.routing_kinematic_init(wh_from_restart, wt_from_restart)
+    ... S.routing(dt) and S.run(..., RUN_ROUTING) now route through hillslope, tributaries and main channel ...
+    wh, wt = S.routing_read(WH), S.routing_read(WT)
+
+    qsur = qsur_from_rows(ptr, col, w, qflx_surf, qflx_h2osfc_surf, area)
+    wh, wt, volr, qout = kinematic_call(wh, wt, volr, qin, qsur, area, params, upstream_map(down), dt, nsub)
 """
 import numpy as np
 
 from . import diagnostics, regrid
+from .hydrology import _pow
 
 VOLR, QIN, QOUT, QOUT_SUM = range(4)  # ELMK_ROUTE_*
 MAXUP = 8
@@ -165,6 +176,125 @@ def budget(volr, qin, qout, down):
     """R6: the sums of VOLR and QIN and the sum of QOUT over the outlets, in the device reduction's order."""
     outlet = np.where(np.asarray(down).reshape(-1) < 0, np.asarray(qout, dtype=np.float64).reshape(-1), 0.0)
     return np.array([diagnostics.reduce_min_max_sum(x)[2] for x in (volr, qin, outlet)])
+
+
+# ---- kinematic-wave routing (include/elmk.h "kinematic-wave routing", K0 - K9) ---------------------------------------------------------
+WH, WT, QSUR = 4, 5, 6  # ELMK_ROUTE_*, readable while the scheme is on
+HSLP, NH, GXR, TLEN, TWIDTH, TSLP, NT, RLEN, RWIDTH, RSLP, NR = range(11)  # ELMK_KW_*: the rows of the parameters
+NPARAM = 11
+PARAM_NAMES = ("HSLP", "NH", "GXR", "TLEN", "TWIDTH", "TSLP", "NT", "RLEN", "RWIDTH", "RSLP", "NR")
+T23, T53 = 2.0 / 3.0, 5.0 / 3.0
+
+
+def e_param(row):
+    """The refusal of elmk_routing_kinematic_enable's parameter check (elmk_maps.h: kinematic_check) for row `row`."""
+    return PARAM_NAMES[row] + " not finite and > 0"
+
+
+def kinematic_params(params):
+    """The check of elmk_routing_kinematic_enable on params [11, ncells] (every value finite and > 0; raises ValueError with the entry
+    point's text, which names the first failing row) and the host's derivation: returns (CH, CT, CR) with
+    CH = (sqrt(HSLP) / NH) * GXR, CT = sqrt(TSLP) / NT, CR = sqrt(RSLP) / NR."""
+    p = np.asarray(params, dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] != NPARAM:
+        raise ValueError("params must be [11, ncells]")
+    for k in range(NPARAM):
+        if not np.all(np.isfinite(p[k]) & (p[k] > 0.0)):
+            raise ValueError(e_param(k))
+    return (np.sqrt(p[HSLP]) / p[NH]) * p[GXR], np.sqrt(p[TSLP]) / p[NT], np.sqrt(p[RSLP]) / p[NR]
+
+
+def _vpow(x, y):
+    """pow per element through math.pow (glibc's bits; np.power is not guaranteed to give them), with hydrology._pow's handling of
+    its exceptions."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.fromiter((_pow(v, y) for v in x.reshape(-1).tolist()), np.float64, x.size).reshape(x.shape)
+
+
+def _cap(v, a, dts, cap=True):
+    """K2: v > 0: min-by-select of the rate a and v / dts; anything else releases +0.0.  cap=False: the rate alone (a wrong variant)."""
+    with np.errstate(all="ignore"):
+        if cap:
+            b = v / dts
+            a = np.where(a < b, a, b)
+        return np.where(v > 0.0, a, 0.0)
+
+
+def hillslope_flow(wh, area, ch, dts, cap=True):
+    """K3: eh [ncells].  The rate is formed only where it is taken (wh > 0 and area > 0); elsewhere the flow is +0.0 (K9)."""
+    wh = np.asarray(wh, dtype=np.float64)
+    area = np.asarray(area, dtype=np.float64)
+    on = (wh > 0.0) & (area > 0.0)
+    with np.errstate(all="ignore"):
+        h = np.where(on, wh, 1.0) / np.where(on, area, 1.0)
+        a = (ch * _vpow(h, T53)) * area
+        return np.where(on, _cap(wh, a, dts, cap), 0.0)
+
+
+def channel_flow(w, length, width, c, dts, cap=True):
+    """K4: chan(w, len, wid, c) [ncells], the tributaries' et and the main channel's er."""
+    w = np.asarray(w, dtype=np.float64)
+    on = w > 0.0
+    with np.errstate(all="ignore"):
+        a = np.where(on, w, 1.0) / length
+        y = a / width
+        p = width + 2.0 * y
+        r = a / p
+        q = (c * _vpow(r, T23)) * a
+        return np.where(on, _cap(w, q, dts, cap), 0.0)
+
+
+def qsur_from_rows(ptr, col, w, qflx_surf, qflx_h2osfc_surf, area):
+    """K1: QSUR [ncells] from the soil hydrology's column rows QFLX_SURF and QFLX_H2OSFC_SURF (mm/s), aggregated as qin_from_rows does."""
+    with np.errstate(all="ignore"):
+        x = np.asarray(qflx_surf, dtype=np.float64) + np.asarray(qflx_h2osfc_surf, dtype=np.float64)
+        s = regrid.apply_aggregate(ptr, col, w, x, 0.0)
+        return _canon((s * 0.001) * np.asarray(area, dtype=np.float64).reshape(-1))
+
+
+def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True):
+    """One elmk_routing with the scheme on, on the host: K0, K2 - K7.  wh, wt, volr, qin, qsur, area: float64 [ncells]; params
+    [11, ncells]; up: upstream_map(down).  Returns (wh_new, wt_new, volr_new, qout).  in_place and cap are the wrong variants the host
+    tests hold their checks against, as call's: in_place updates the cells one after another in index order, the upstream flows taken
+    from main-channel storages already updated in the sub-step; cap=False takes every flow without the cap v / dts."""
+    wh, wt, v = (np.array(x, dtype=np.float64).reshape(-1) for x in (wh, wt, volr))
+    qin, qsur, area = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (qin, qsur, area))
+    p = np.asarray(params, dtype=np.float64)
+    ch, ct, cr = kinematic_params(p)
+    up = np.asarray(up)
+    nsub = int(nsub)
+    dts = float(dt) / float(nsub)
+    qacc = np.zeros_like(v)
+    safe = np.where(up >= 0, up, 0)
+    with np.errstate(all="ignore"):
+        qsub = qin - qsur
+        for _ in range(nsub):
+            eh = hillslope_flow(wh, area, ch, dts, cap)
+            et = channel_flow(wt, p[TLEN], p[TWIDTH], ct, dts, cap)
+            er = channel_flow(v, p[RLEN], p[RWIDTH], cr, dts, cap)
+            if in_place:
+                for c in range(v.size):
+                    fin = 0.0
+                    for k in range(up.shape[0]):
+                        u = up[k, c]
+                        if u >= 0:
+                            fin = fin + float(channel_flow(v[u:u + 1], p[RLEN, u], p[RWIDTH, u], cr[u], dts, cap)[0])
+                    v[c] = v[c] + ((fin - er[c]) + et[c]) * dts
+            else:
+                fin = np.zeros_like(v)
+                for k in range(up.shape[0]):
+                    fin = np.where(up[k] >= 0, fin + er[safe[k]], fin)
+                v = _canon(v + ((fin - er) + et) * dts)
+            wh = _canon(wh + (qsur - eh) * dts)
+            wt = _canon(wt + ((eh - et) + qsub) * dts)
+            qacc = qacc + er
+        qout = _canon(qacc / float(nsub))
+    return wh, wt, _canon(v), qout
+
+
+def kinematic_budget(wh, wt):
+    """K8: the sums of WH and WT in the device reduction's order."""
+    return np.array([diagnostics.reduce_min_max_sum(x)[2] for x in (wh, wt)])
 
 
 # D8 direction codes (the ESRI convention): the neighbour a cell drains into, as (row step, column step) with row 0 the northernmost

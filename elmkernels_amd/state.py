@@ -33,6 +33,8 @@ IRR_RATE, IRR_NLEFT, IRR_QFLX_IRRIG = range(3)  # elmk_irrigation_read (irrigati
 IRR_NROWS = 3
 RUN_ROUTING = 256  # every step routes the step's runoff after the water balance (routing_enable; needs RUN_WATER_BALANCE)
 ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT, ROUTE_QOUT_SUM = range(4)  # elmk_routing_read (routing.VOLR .. routing.QOUT_SUM)
+ROUTE_WH, ROUTE_WT, ROUTE_QSUR = 4, 5, 6  # ... while the kinematic-wave scheme is on (routing.WH, routing.WT, routing.QSUR)
+ROUTE_KW_NPARAM = 11  # the rows of routing_kinematic_enable's params (routing.HSLP .. routing.NR)
 WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB .. hydrology.WB_TOTSOILICE
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
@@ -550,7 +552,8 @@ class ELMState:
         self._chk(self.lib.elmk_routing(self.ctx, float(dt)), "routing")
 
     def routing_read(self, which, cell0=0, n=None):
-        """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
+        """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM (with the kinematic-wave scheme on also ROUTE_WH, ROUTE_WT, ROUTE_QSUR)
+        of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
         n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
         out = np.empty(max(n, 0), dtype=np.float64)
         self._chk(self.lib.elmk_routing_read(self.ctx, int(which), _p(out), int(cell0), n), "routing_read")
@@ -577,6 +580,35 @@ class ELMState:
 
     def routing_clear(self):
         self._chk(self.lib.elmk_routing_clear(self.ctx), "routing_clear")
+
+    # -- kinematic-wave routing (include/elmk.h: elmk_routing_kinematic_enable ...; routing.kinematic_call restates the scheme) -----------
+    def routing_kinematic_enable(self, params):
+        """Switch the routing stage to the kinematic-wave scheme: params float64 [ROUTE_KW_NPARAM, ncells] in the order of routing.HSLP ..
+        routing.NR, every value finite and > 0.  Allocates the rows WH, WT, QSUR (zero-filled); routing_read takes ROUTE_WH, ROUTE_WT and
+        ROUTE_QSUR from here on.  Needs routing_enable and soil_hydrology_enable."""
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        n = getattr(self, "routing_ncells", None)
+        if n is not None and p.shape != (ROUTE_KW_NPARAM, n):
+            raise ValueError(f"routing_kinematic_enable: params must be [{ROUTE_KW_NPARAM}, {n}]")
+        self._chk(self.lib.elmk_routing_kinematic_enable(self.ctx, _p(p)), "routing_kinematic_enable")
+
+    def routing_kinematic_init(self, wh=None, wt=None):
+        """WH and WT from [ncells] each (None: zeros), QSUR zeros; VOLR, QOUT_SUM and the count stay routing_init's.  Synchronises."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (wh, wt)]
+        for v in a:
+            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
+                raise ValueError(f"routing_kinematic_init: {v.size} values for {self.routing_ncells} cells")
+        self._chk(self.lib.elmk_routing_kinematic_init(self.ctx, *(None if v is None else _p(v) for v in a)), "routing_kinematic_init")
+
+    def routing_kinematic_budget(self):
+        """float64 [2]: the sums of WH and WT (routing.kinematic_budget).  Synchronises."""
+        out = np.empty(2, dtype=np.float64)
+        self._chk(self.lib.elmk_routing_kinematic_budget(self.ctx, _p(out)), "routing_kinematic_budget")
+        return out
+
+    def routing_kinematic_clear(self):
+        """Back to the linear scheme; VOLR, QOUT_SUM and the count stay."""
+        self._chk(self.lib.elmk_routing_kinematic_clear(self.ctx), "routing_kinematic_clear")
 
     # -- water balance (include/elmk.h: elmk_water_balance_enable ...; hydrology.water_balance_begin / _end restate the stage) -----
     def water_balance_enable(self, tol_mm):

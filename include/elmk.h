@@ -1042,6 +1042,73 @@ int elmk_routing_set_withdrawal(elmk_ctx *ctx, int on);
 int elmk_routing_budget(elmk_ctx *ctx, double *sums /*[3]*/);
 int elmk_routing_clear(elmk_ctx *ctx);
 
+/* ---- kinematic-wave routing ------------------------------------------------------------------------
+ * An opt-in second scheme of the routing stage above, after the river model the E3SM land model routes with today (MOSART): runoff
+ * passes through three stores per cell - the hillslope (overland flow), the sub-network of tributaries and the main channel - and each
+ * releases by Manning's equation, so the velocity rises with the hydraulic radius.  Surface runoff enters the hillslope, subsurface
+ * runoff the tributaries.  The statement below is the specification; k_routing.hip (k_kinematic_prep, k_kinematic_step) performs it
+ * and elmkernels_amd/routing.py: kinematic_call() restates it on the host.
+ *
+ * Conventions of "runoff routing": no contraction, left-associated + - *, `/` the correctly rounded fp64 division, sqrt correctly
+ * rounded, plain IEEE comparisons; every row is fp64 in both builds; a NaN is stored as the canonical quiet NaN.  pow is elmk_pow on the
+ * device (elmk_math.h: glibc's bits) and glibc's pow on the host.  T23 = 2.0 / 3.0 and T53 = 5.0 / 3.0 are the doubles those quotients
+ * give.
+ *
+ * Parameters, given once after elmk_routing_enable as params[ELMK_KW_NPARAM][ncells]: HSLP (hillslope slope), NH (hillslope Manning
+ * n), GXR (drainage density, 1/m), TLEN, TWIDTH (tributary length and width, m), TSLP, NT (tributary slope and Manning n), RLEN, RWIDTH
+ * (main channel length and width, m), RSLP, NR (main channel slope and Manning n).  Every value must be finite and > 0.  The host
+ * derives CH = (sqrt(HSLP) / NH) * GXR, CT = sqrt(TSLP) / NT, CR = sqrt(RSLP) / NR and keeps CH, CT, CR, TLEN, TWIDTH, RLEN, RWIDTH on
+ * the device.  effvel, ddist and KOUT are not read while the scheme is on; area, down, the upstream map, nsub and the withdrawal
+ * switch stay the routing's.
+ *
+ * State and rows: ELMK_ROUTE_VOLR is the main channel's storage (m3) while the scheme is on; new prognostic rows ELMK_ROUTE_WH
+ * (hillslope water, m3) and ELMK_ROUTE_WT (tributary storage, m3); new diagnostic row ELMK_ROUTE_QSUR (m3/s: the surface part of
+ * QIN).  QIN, QOUT and QOUT_SUM keep their meaning.  elmk_routing_read accepts the three new rows only while the scheme is on.
+ *
+ * One call elmk_routing(ctx, dt) while the scheme is on:
+ * K0. dts = dt / (double)nsub.
+ * K1. (once per call) QIN exactly as R1, withdrawal included.  s = the aggregate over the cell's terms, in R1's order, of
+ *     w[p] * (QFLX_SURF[col[p]] + QFLX_H2OSFC_SURF[col[p]]), the soil hydrology's rows; a cell without terms takes 0.0.
+ *     QSUR = (s * 0.001) * area;  QSUB = QIN - QSUR.
+ * K2. cap(v, a): if (v > 0.0) { b = v / dts;  cap = (a < b) ? a : b; } else cap = 0.0.  R2 with the rate already formed.
+ * K3. hillslope: if (area > 0.0) { h = WH / area;  eh = cap(WH, (CH * pow(h, T53)) * area); } else eh = 0.0.
+ * K4. chan(w, len, wid, c): a = w / len;  y = a / wid;  p = wid + 2.0 * y;  r = a / p;  chan = cap(w, (c * pow(r, T23)) * a).
+ *     et = chan(WT, TLEN, TWIDTH, CT);  er = chan(VOLR, RLEN, RWIDTH, CR).
+ * K5. fin = 0.0; for p = 0 .. 7 ascending with u = up[p][c] >= 0: fin = fin + er[u], the upstream cell's er of this sub-step's start.
+ * K6. all three flows are evaluated from the storages of the sub-step's start; then WH = WH + (QSUR - eh) * dts;
+ *     WT = WT + ((eh - et) + QSUB) * dts;  VOLR = VOLR + ((fin - er) + et) * dts.
+ * K7. qacc starts at 0.0 and takes qacc + er every sub-step.  After the last: QOUT = qacc / (double)nsub;
+ *     QOUT_SUM = QOUT_SUM + QOUT.
+ * K8. (elmk_routing_kinematic_budget) sums[0] = the sum of WH, sums[1] = the sum of WT, through the reduction kernels of R6.  With
+ *     elmk_routing_budget's three sums: the change of (sum WH + sum WT + sum VOLR) over a call = dt (sum QIN - sum outlet QOUT).
+ * K9. A NaN, zero, negative or -inf storage releases nothing, as in R2 (where the cap returns 0.0 the rate is not formed).
+ * A call takes nsub + 1 launches, as the linear scheme's.  The device keeps a row of er per cell in two buffers: the K1 launch writes
+ * the er of the call's first sub-step, every sub-step but the last writes the er of its new VOLR for the next to gather (the same
+ * operands through the same operations as evaluating it there), and WH, WT and VOLR update in place.
+ *
+ *   elmk_routing_kinematic_enable  takes the parameters, allocates the scheme's rows zero-filled (one owner, counted in
+ *                           elmk_device_bytes) and drops the captured run step.  ELMK_E_INVALID, nothing changed: the routing not
+ *                           enabled; the soil hydrology not enabled; already on; a null argument; a value that is not finite and > 0
+ *                           (the text names the row, "elmk_routing_kinematic_enable: TLEN not finite and > 0"); a stream being captured.
+ *   elmk_routing_kinematic_init    WH and WT from host[ncells] each (NULL: zeros), QSUR zeros.  VOLR, QOUT_SUM and the count stay
+ *                           elmk_routing_init's.  Synchronises.
+ *   elmk_routing_kinematic_budget  K8; synchronises.
+ *   elmk_routing_kinematic_clear   back to the linear scheme with VOLR, QOUT_SUM and the count kept; frees what enable allocated and
+ *                           drops the captured run step.  elmk_routing_clear frees both.
+ * elmk_routing and elmk_run with ELMK_RUN_ROUTING run whichever scheme is on; the call count and elmk_routing_reset_mean are unchanged.
+ * Restart: a driver saves WH and WT with elmk_routing_read beside VOLR, QOUT_SUM and the count and restores them with
+ * elmk_routing_kinematic_init after elmk_routing_kinematic_enable.  A context that never calls these entries runs the kernels, launch
+ * sequences and graphs it ran before and allocates nothing more. */
+enum { ELMK_ROUTE_WH = 4, ELMK_ROUTE_WT = 5, ELMK_ROUTE_QSUR = 6 };
+enum {
+  ELMK_KW_HSLP = 0, ELMK_KW_NH = 1, ELMK_KW_GXR = 2, ELMK_KW_TLEN = 3, ELMK_KW_TWIDTH = 4, ELMK_KW_TSLP = 5, ELMK_KW_NT = 6,
+  ELMK_KW_RLEN = 7, ELMK_KW_RWIDTH = 8, ELMK_KW_RSLP = 9, ELMK_KW_NR = 10, ELMK_KW_NPARAM = 11
+};
+int elmk_routing_kinematic_enable(elmk_ctx *ctx, const double *params /*[ELMK_KW_NPARAM][ncells]*/);
+int elmk_routing_kinematic_init(elmk_ctx *ctx, const double *wh /*[ncells] or NULL*/, const double *wt /*[ncells] or NULL*/);
+int elmk_routing_kinematic_budget(elmk_ctx *ctx, double *sums /*[2]*/);
+int elmk_routing_kinematic_clear(elmk_ctx *ctx);
+
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.
  * These two entries register one such row, over the columns (elmk_column_history_add_row; the six elmk_history_* entries of "history"

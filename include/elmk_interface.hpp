@@ -394,6 +394,15 @@ class ELMInterface {
   void routing_set_withdrawal(bool on) { ok(elmk_routing_set_withdrawal(ctx_, on ? 1 : 0)); }
   void routing_budget(double* sums) { ok(elmk_routing_budget(ctx_, sums)); }
   void routing_clear() { ok(elmk_routing_clear(ctx_)); }
+  /* Kinematic-wave routing (elmk.h "kinematic-wave routing"): the routing stage's second scheme, through hillslope, tributaries and
+   * main channel.  routing_kinematic_enable() takes params[ELMK_KW_NPARAM][ncells] after routing_enable and soil_hydrology_enable;
+   * routing(dt) and run(..., routing = true) then run it, and routing_read() takes ELMK_ROUTE_WH, ELMK_ROUTE_WT and ELMK_ROUTE_QSUR as
+   * well.  routing_kinematic_init() takes a restart's WH and WT ([ncells] each, nullptr: zeros); routing_kinematic_budget() fills
+   * sums[2]; routing_kinematic_clear() returns to the linear scheme and keeps VOLR, QOUT_SUM and the count. */
+  void routing_kinematic_enable(const double* params) { ok(elmk_routing_kinematic_enable(ctx_, params)); }
+  void routing_kinematic_init(const double* wh = nullptr, const double* wt = nullptr) { ok(elmk_routing_kinematic_init(ctx_, wh, wt)); }
+  void routing_kinematic_budget(double* sums) { ok(elmk_routing_kinematic_budget(ctx_, sums)); }
+  void routing_kinematic_clear() { ok(elmk_routing_kinematic_clear(ctx_)); }
   /* History entries over one fp64 row of a feature (elmk.h "feature rows on history tapes"): family ELMK_ROWS_*, which the family's
    * row number; as history_add / gridded_history_add otherwise, one level.  While such an entry exists the family's clear is refused. */
   int history_add_row(int tape, int family, int which, int op)
