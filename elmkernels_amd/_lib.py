@@ -142,6 +142,11 @@ SIGNATURES = {
     "elmk_irrigation": (C.c_int, [_P, C.c_double, C.c_int]),
     "elmk_irrigation_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
     "elmk_irrigation_clear": (C.c_int, [_P]),
+    "elmk_irrigation_supply_enable": (C.c_int, [_P, C.c_double]),
+    "elmk_irrigation_supply_init": (C.c_int, [_P, _P]),
+    "elmk_irrigation_supply_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_irrigation_supply_reset": (C.c_int, [_P]),
+    "elmk_irrigation_supply_clear": (C.c_int, [_P]),
     "elmk_routing_enable": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_double, C.c_int]),
     "elmk_routing_init": (C.c_int, [_P, _P, _P, C.c_int64]),
     "elmk_routing": (C.c_int, [_P, C.c_double]),

@@ -230,6 +230,7 @@ int elmk_set_output_grid(elmk_ctx* ctx, int64_t ncells, const int64_t* ptr, cons
   if (int rc = invalid_map(ctx, "elmk_set_output_grid", csr_check(ncells, ctx->ncols, ptr, col, w, "ncells outside 1 .. 2^31-1", false, false))) return rc;
   if (int rc = refuse_capture(ctx, "elmk_set_output_grid")) return rc;
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_set_output_grid: gridded history entries exist (elmk_history_clear first)");
+  if (int rc = irrsup_holds(ctx, "elmk_set_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_set_output_grid")) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));  // (a gridded download may still read the old map)
   elmk_ctx::OGrid& O = ctx->ogrid;
@@ -247,6 +248,7 @@ int elmk_clear_output_grid(elmk_ctx* ctx)
   if (int rc = enter(ctx)) return rc;
   if (int rc = refuse_capture(ctx, "elmk_clear_output_grid")) return rc;
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_clear_output_grid: gridded history entries exist (elmk_history_clear first)");
+  if (int rc = irrsup_holds(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_clear_output_grid")) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->ogrid = elmk_ctx::OGrid{};

@@ -173,6 +173,8 @@ int elmk_routing_set_withdrawal(elmk_ctx* ctx, int on)
   const char* who = "elmk_routing_set_withdrawal";
   if (int rc = route_enter(ctx, who)) return rc;
   if (on && !ctx->irr_rows) return invalid(ctx, "elmk_routing_set_withdrawal: the irrigation is not enabled (elmk_irrigation_enable)");
+  if (!on)
+    if (int rc = irrsup_holds(ctx, who)) return rc;  // (the limit grants water that only the withdrawal takes out of VOLR)
   if (int rc = refuse_capture(ctx, who)) return rc;
   ctx->route.withdraw = on != 0;  // (the captured run step is keyed by it)
   return ELMK_OK;
@@ -275,6 +277,7 @@ int elmk_routing_clear(elmk_ctx* ctx)
   if (int rc = enter(ctx)) return rc;
   if (int rc = refuse_capture(ctx, "elmk_routing_clear")) return rc;
   if (!ctx->route.mem) return ELMK_OK;
+  if (int rc = irrsup_holds(ctx, "elmk_routing_clear")) return rc;  // (the limit reads VOLR and area)
   if (int rc = quiesce(ctx, false)) return rc;
   ctx->route = elmk_ctx::Routing{};
   return ELMK_OK;

@@ -335,7 +335,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   const StepKey key{flags, ds_topo(ctx), ds_topo(ctx) && ctx->ds.gmem, cz, (flags & ELMK_RUN_HYDROLOGY) && hyd_land(ctx),
                     (flags & ELMK_RUN_HYDROLOGY) && (bool)ctx->hydf_rows, ctx->hist_version,
                     ctx->accum_version, (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx),
-                    (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows, (flags & ELMK_RUN_ROUTING) && ctx->route.withdraw};
+                    (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows, (flags & ELMK_RUN_ROUTING) && ctx->route.withdraw,
+                    (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx) && (bool)ctx->irrsup_rows};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;

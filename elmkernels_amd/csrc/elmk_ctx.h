@@ -153,7 +153,8 @@ enum GraphId { GRAPH_TS7, GRAPH_FUSED, GRAPH_ADVANCE, GRAPH_RUN_STEP, GRAPH_N };
 // What the captured launches of a sequence depend on besides (dt, stream).  elmk_run's step: the run's flags, the downscaling and
 // shortwave modes, whether the soil hydrology stage is in the step (its flag is set and the land unit is soil or crop), whether that
 // stage takes the frost-table form, the history and accumulator tables' versions, whether the irrigation stage is in the step (its flag
-// is set and the land unit is soil or crop), whether the water balance takes its term and whether the routing stage takes the withdrawal;
+// is set and the land unit is soil or crop), whether the water balance takes its term, whether the routing stage takes the withdrawal and
+// whether the irrigation stage has the river supply limit's launch behind it;
 // the other sequences have none (StepKey{}).
 struct StepKey {
   int flags = 0;
@@ -161,9 +162,11 @@ struct StepKey {
   uint64_t hist_version = 0, accum_version = 0;
   bool irr_stage = false, wb_irrig = false;  // the irrigation stage is in the step; the water balance takes the irrigation's term
   bool route_withdraw = false;               // the routing stage is in the step (its flag) and subtracts the irrigation's withdrawal
+  bool irr_supply = false;                   // the irrigation stage is in the step and the river supply limit's launch follows it
   auto tie() const
   {
-    return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw);
+    return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw,
+                    irr_supply);
   }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
@@ -276,6 +279,10 @@ struct elmk_ctx {
   // [ld], held exactly while the feature is enabled
   DevBuf<double> irr_rows;
   int32_t* irr_sched = nullptr;
+  // its river supply limit (elmk_irrigation_supply_*): the four fp64 cell rows [ELMK_IRRSUP_*][route.cld] and the threshold, held exactly
+  // while the limit is on
+  DevBuf<double> irrsup_rows;
+  double irrsup_thr = 0.0;
   // runoff routing (elmk_routing_*): one allocation `mem` holds the rows [ROUTE_NROWS][cld], KOUT and area [cld], the upstream map
   // [npad][cld], down [cld] and the budget reduction's partials [3][ELMK_CONS_NPART][3] and triples [3][3]; held exactly while the
   // feature is enabled.  ncalls: the calls since the last elmk_routing_init / _reset_mean (QOUT_SUM's count)
@@ -472,6 +479,8 @@ int rows_read(elmk_ctx* ctx, const Rows& R, const char* who, int which, double* 
 int rows_clear(elmk_ctx* ctx, const Rows& R, const char* who);
 constexpr int IRR_NROWS = 3;
 void irr_run_launch(elmk_ctx* ctx, double dt);  // the run step's irrigation stage (api_irrigation.cpp)
+// "<who>: the irrigation's river supply limit is on (elmk_irrigation_supply_clear first)" while it is - what the limit reads stays
+int irrsup_holds(elmk_ctx* ctx, const char* who);
 void route_launch(elmk_ctx* ctx, double dt);    // one call of the runoff routing (api_routing.cpp)
 // "<who>: runoff routing is enabled (elmk_routing_clear first)" while it is - what the routing reads stays; with_withdrawal: only while
 // the withdrawal is on

@@ -259,6 +259,11 @@ void launch_irrigation(const DevState* S, int64_t n, double* rows, const int32_t
 // the same with the time of day of table row *cursor (RunRow::pad; elmk_run)
 void launch_irrigation_run(const DevState* S, int64_t n, double* rows, const int32_t* sched, int idt, const RunRow* table,
                            const int32_t* cursor, hipStream_t st);
+// the irrigation's river supply limit (k_history.hip: k_irrigation_supply, elmk_irrigation_supply_*): S0 - S6 of include/elmk.h "irrigation: river
+// supply limit", one launch behind launch_irrigation / launch_irrigation_run with the same idt.  irr_rows: the irrigation's rows [3][ld];
+// M: the output grid's map (every column in at most one cell); area, volr: the routing's [cld]; sup_rows: the limit's rows [4][cld]
+void launch_irrigation_supply(int64_t ncols, double* irr_rows, int64_t ld, int idt, const OGridMap& M, const double* area,
+                              const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st);
 
 // soil hydrology (k_soil_hydrology.hip, elmk_soil_hydrology): one stage over every column; rows = the ELMK_HYD_NROWS fp64 rows of
 // the feature, [row][ld]; frost_rows = the ELMK_HYDF_NROWS rows of the frost-table extension, which select the F' form of the kernel, or

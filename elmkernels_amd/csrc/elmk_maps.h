@@ -32,6 +32,24 @@ inline const char* ell_check(int64_t ncols, int64_t ncells, int npts, const int3
   return nullptr;
 }
 
+// The per-term scan of a CSR map's col (and, with WEIGHTS, w): the first term that fails the column's range, then uniqueness (`unique`:
+// no earlier term holds the column), then the weight (finite, with nonneg also >= 0); nnz if none does.  *repeat: it failed uniqueness.
+// The loop stops at the first bad term and the caller says why.  Returning texts from inside the loop is slower: the library's build
+// switches machine LICM off, so the address of the merged return value is formed again in every iteration.
+template <bool WEIGHTS>
+inline int64_t csr_scan(int64_t ncols, int64_t nnz, const int32_t* col, const double* w, bool unique, bool nonneg, bool* repeat)
+{
+  std::vector<char> seen(unique ? (size_t)ncols : 0, 0);
+  int64_t p = 0;
+  for (; p < nnz; p++) {
+    if (col[p] < 0 || col[p] >= ncols) break;
+    if (unique && seen[(size_t)col[p]]++) break;
+    if (WEIGHTS && (!std::isfinite(w[p]) || (nonneg && !(w[p] >= 0.0)))) break;
+  }
+  *repeat = p < nnz && col[p] >= 0 && col[p] < ncols && unique && seen[(size_t)col[p]] > 1;
+  return p;
+}
+
 // CSR map, by row (an output cell, a group): ptr (int64, nrows + 1), col (int32, nnz = ptr[nrows]: columns), w (fp64, nnz).
 // bad_nrows: the message for nrows outside 1 .. 2^31-1 (it names the caller's rows); unique: a column appears at most once in the
 // whole map; nonneg: weights are >= 0 as well as finite.  Per term the column's range, then uniqueness, then the weight.
@@ -46,19 +64,23 @@ inline const char* csr_check(int64_t nrows, int64_t ncols, const int64_t* ptr, c
   const int64_t nnz = ptr[nrows];
   if (nnz > INT32_MAX) return "nnz outside 0 .. 2^31-1";
   if (nnz > 0 && (!col || !w)) return "null map";
-  // The loop stops at the first bad term and the lines after it say why.  Returning the texts from inside the loop is slower: the
-  // library's build switches machine LICM off, so the address of the merged return value is formed again in every iteration.
-  std::vector<char> seen(unique ? (size_t)ncols : 0, 0);
-  int64_t p = 0;
-  for (; p < nnz; p++) {
-    if (col[p] < 0 || col[p] >= ncols) break;
-    if (unique && seen[(size_t)col[p]]++) break;
-    if (!std::isfinite(w[p]) || (nonneg && !(w[p] >= 0.0))) break;
-  }
+  bool repeat = false;
+  const int64_t p = csr_scan<true>(ncols, nnz, col, w, unique, nonneg, &repeat);
   if (p == nnz) return nullptr;
   if (col[p] < 0 || col[p] >= ncols) return "col outside [0, ncols)";
-  if (unique && seen[(size_t)col[p]] > 1) return "a column in more than one group (or twice in one)";
+  if (repeat) return "a column in more than one group (or twice in one)";
   return nonneg ? "weight not finite and >= 0" : "non-finite weight";
+}
+
+// Every column in at most one row of a map (elmk_irrigation_supply_enable: the output grid's, which is set without `unique`): the column
+// of the first term in CSR order that an earlier term holds already, -1 if there is none, -2 if a column before it is out of range (no
+// accepted map).  csr_check's scan with the weights left out.
+inline int64_t csr_shared_column(int64_t ncols, int64_t nnz, const int32_t* col)
+{
+  if (nnz <= 0 || !col) return -1;
+  bool repeat = false;
+  const int64_t p = csr_scan<false>(ncols, nnz, col, nullptr, true, false, &repeat);
+  return p == nnz ? -1 : repeat ? (int64_t)col[p] : -2;
 }
 
 // River network (elmk_routing_enable; include/elmk.h "runoff routing"): every cell drains into one downstream cell down[c], or is an

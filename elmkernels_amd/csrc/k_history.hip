@@ -301,4 +301,135 @@ void launch_ogrid_finalize(const double* acc, int64_t ld, int nlev, int op, int6
                      cell0, m, out);
 }
 
+
+// ---------------------------------------------------------------------------------------------------
+// the irrigation's river supply limit (elmk_irrigation_supply_*; include/elmk.h "irrigation: river supply limit"): CLM5's
+// limit_irrigation_if_rof_enabled / CalcDeficitVolrLimited at the daily demand check.  One launch right after k_irrigation on the same
+// stream.  elmkernels_amd/irrigation.py: supply_limit() restates S0 - S6 in numpy, and the kernel follows them statement by statement:
+// no contraction, plain IEEE comparisons, `/` the correctly rounded fp64 division; a NaN is stored into a row as the canonical quiet NaN.
+//
+// The shape is k_ds_lw_norm's: one workgroup takes SUP_CELLS consecutive cells of the output grid's map, whose terms are one contiguous
+// span of the map.  The workgroup walks the span in tiles of SUP_TILE terms; every thread forms the two products of S2 of its share of a
+// tile - coalesced loads of col and w, gathers of RATE, NLEFT and QFLX_IRRIG that are coalesced where a cell's columns are neighbours - into two LDS
+// tiles, then thread t adds the products of cell t out of LDS in CSR order.  A product is one rounding whichever lane forms it and every
+// sum is taken by one lane in term order, so D and C are regrid.apply_aggregate's bit for bit.  Both sums come from ONE walk of its own:
+// agg_cells forms one sum per walk from a source row, and two walks would load the map and the rows twice; agg_cells and the kernels
+// above are left exactly as they were.  Then S3, S4 and S6 per cell, and S5 only in a workgroup that has a cell with ratio != 1.0: every
+// thread scales the checking columns of its share of the span, finding a term's cell by a binary search over the span's ptr in LDS.  A
+// column is in at most one cell (checked when the limit is enabled), so it is read and written by one workgroup only, after that
+// workgroup's sums: no atomics and no fence.
+//
+// SUP_CELLS = 64, as AGG_CELLS and not DS_CELLS: the map is the output grid's, whose cells hold few columns (four per cell fill the 256
+// threads of a tile pass with one term each, and the 64 serial sums are four terms long), where a downscaling group holds a gridcell's
+// 150.  SUP_TILE = 1024: two tiles of 8 KiB are k_ds_lw_norm's 16 KiB of LDS.  A quiet step - no column checking - reads col, w, RATE,
+// NLEFT and QFLX_IRRIG once and writes three cell rows.  No nontemporal hint: none has been measured for it.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+constexpr int SUP_THREADS = AGG_THREADS, SUP_CELLS = 64, SUP_TILE = 1024;
+static_assert(SUP_CELLS < SUP_THREADS && SUP_TILE % SUP_THREADS == 0, "thread t <= SUP_CELLS loads ptr; whole passes over a tile");
+
+__device__ __forceinline__ void sup_st(gptr<double> p, double v)
+{
+  if (v != v) v = __builtin_nan("");
+  *p = v;
+}
+}  // namespace
+
+// grid (ceil(ncells / SUP_CELLS)); irr = the irrigation's rows [3][ld], sup = the limit's rows [4][cld]
+__global__ __launch_bounds__(SUP_THREADS) void k_irrigation_supply(gptr<double> irr, int64_t ld, int idt, int nspd, OGridMap M,
+                                                                   gptr<const double> area, gptr<const double> volr, double thr,
+                                                                   gptr<double> sup, int64_t cld)
+{
+  __shared__ double tile_d[SUP_TILE];
+  __shared__ double tile_c[SUP_TILE];
+  __shared__ double ratio_s[SUP_CELLS];
+  __shared__ int64_t sp[SUP_CELLS + 1];
+  __shared__ int limited;
+  const int t = threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * SUP_CELLS;
+  const int64_t c1 = c0 + SUP_CELLS < M.ncells ? c0 + SUP_CELLS : M.ncells;
+  const int ncl = (int)(c1 - c0);
+  const gptr<double> rate = irr + (int64_t)ELMK_IRR_RATE * ld;
+  const gptr<const double> nleft = irr + (int64_t)ELMK_IRR_NLEFT * ld, qirr = irr + (int64_t)ELMK_IRR_QFLX_IRRIG * ld;
+  const double dnspd = (double)nspd, didt = (double)idt;
+
+  if (t == 0) limited = 0;
+  if (t <= ncl) sp[t] = M.ptr[c0 + t];
+  __syncthreads();
+  const int64_t P0 = sp[0], P1 = sp[ncl];
+  int64_t p0 = 0, p1 = 0;
+  if (t < ncl) {
+    p0 = sp[t];
+    p1 = sp[t + 1];
+  }
+  // S1, S2: a cell without terms keeps 0.0 for both
+  double D = 0.0, C = 0.0;
+  for (int64_t base = P0; base < P1; base += SUP_TILE) {
+    const int m = (int)(P1 - base < SUP_TILE ? P1 - base : SUP_TILE);
+#pragma unroll
+    for (int k = 0; k < SUP_TILE / SUP_THREADS; k++) {
+      const int q = k * SUP_THREADS + t;
+      if (q < m) {
+        const int64_t i = M.col[base + q];
+        const double w = M.w[base + q], n = nleft[i];
+        const double x = rate[i] * (didt * n);
+        const double y = qirr[i] * didt;
+        const bool checks = n == dnspd;  // S0
+        tile_d[q] = w * (checks ? x : 0.0);
+        tile_c[q] = w * ((!checks && n > 0.0 ? x : 0.0) + y);
+      }
+    }
+    __syncthreads();
+    const int64_t lo = p0 > base ? p0 : base, hi = p1 < base + m ? p1 : base + m;
+    for (int64_t p = lo; p < hi; p++) {
+      const double xd = tile_d[p - base], xc = tile_c[p - base];
+      D = p == p0 ? xd : D + xd;
+      C = p == p0 ? xc : C + xc;
+    }
+    __syncthreads();
+  }
+  if (t < ncl) {
+    const int64_t c = c0 + t;
+    const double ar = area[c];
+    const double Vd = (D * 0.001) * ar, Vc = (C * 0.001) * ar;  // S3
+    const double a = volr[c] * (1.0 - thr) - Vc;
+    const double avail = a > 0.0 ? a : 0.0;
+    const double ratio = Vd > avail ? avail / Vd : 1.0;  // S4
+    ratio_s[t] = ratio;
+    if (ratio != 1.0) limited = 1;  // (every writer stores the same word)
+    // S6
+    sup_st(sup + (int64_t)ELMK_IRRSUP_DEMAND * cld + c, Vd);
+    sup_st(sup + (int64_t)ELMK_IRRSUP_COMMITTED * cld + c, Vc);
+    sup_st(sup + (int64_t)ELMK_IRRSUP_RATIO * cld + c, ratio);
+    const gptr<double> u = sup + (int64_t)ELMK_IRRSUP_UNMET_SUM * cld + c;
+    sup_st(u, *u + (Vd - Vd * ratio));
+  }
+  __syncthreads();
+  if (!limited) return;  // (uniform: read after the barrier)
+  // S5
+  for (int64_t q = P0 + t; q < P1; q += SUP_THREADS) {
+    int lo = 0, hi = ncl;  // sp[lo] <= q < sp[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (sp[mid] <= q) lo = mid;
+      else hi = mid;
+    }
+    const double r = ratio_s[lo];
+    if (r != 1.0) {
+      const int64_t i = M.col[q];
+      if (nleft[i] == dnspd) sup_st(rate + i, rate[i] * r);
+    }
+  }
+}
+
+void launch_irrigation_supply(int64_t ncols, double* irr_rows, int64_t ld, int idt, const OGridMap& M, const double* area,
+                              const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st)
+{
+  if (ncols <= 0 || M.ncells <= 0) return;
+  const int nspd = (14400 + (idt - 1)) / idt;
+  hipLaunchKernelGGL(k_irrigation_supply, dim3((unsigned)((M.ncells + SUP_CELLS - 1) / SUP_CELLS)), dim3(SUP_THREADS), 0, st,
+                     (gptr<double>)irr_rows, ld, idt, nspd, M, (gptr<const double>)area, (gptr<const double>)volr, thr,
+                     (gptr<double>)sup_rows, cld);
+}
+
 }  // namespace elmk

@@ -9,6 +9,11 @@ with the same operation order, and the host-side helpers a driver needs.
     rate, nleft, qirr = (S.irrigation_read(w) for w in (RATE, NLEFT, QFLX_IRRIG))
 
     out, rows = step(fields, rows, sched, dt, tod, smpso)
+
+The river supply limit (include/elmk.h "irrigation: river supply limit"; S.irrigation_supply_enable(threshold)) follows the stage:
+
+    rate, (demand, committed, ratio, unmet_sum) = supply_limit(ptr, col, w, area, volr, rows[RATE], rows[NLEFT], dt, thr, unmet_sum,
+                                                               qflx_irrig=rows[QFLX_IRRIG])
 """
 import math
 
@@ -163,3 +168,56 @@ def step(fields, rows, sched, dt, tod, smpso, stored=None, hit=None):
                                            w["bsw"][i, :NLEVGRND].tolist(), w["dz"][i, s0:s1].tolist(), w["h2osoi_liq"][i, s0:s1].tolist(),
                                            float(smpso[c]), dtn, hit)
     return out, rows_out
+
+
+# ---- the river supply limit (include/elmk.h "irrigation: river supply limit"; k_history.hip: k_irrigation_supply) -------------------------------
+DEMAND, COMMITTED, RATIO, UNMET_SUM = range(4)  # ELMK_IRRSUP_*
+SUPPLY_NROWS = 4
+
+
+def _canon(v):
+    """A NaN is stored into a row as the canonical quiet NaN."""
+    v = np.asarray(v, dtype=np.float64)
+    return np.where(v != v, _NAN, v)
+
+
+def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx_irrig=None):
+    """S0 - S6 on the host: the launch that follows elmk_irrigation while the limit is on.
+
+    ptr, col, w: the output grid's CSR map (every column in at most one cell); area, volr: the routing's [ncells]; rate, nleft: the
+    irrigation's rows after this step's irrigation.step ([ncols]); idt: the step in whole seconds; thr: the threshold; unmet_sum:
+    [ncells], the prognostic row; qflx_irrig: the irrigation's QFLX_IRRIG row of this step ([ncols]; None: zeros) - the water applied
+    in this step, which the routing has not yet taken out of volr (S2's y).  Returns (rate_out, rows): rate_out float64 [ncols], rows float64 [SUPPLY_NROWS, ncells] in the order
+    DEMAND, COMMITTED, RATIO, UNMET_SUM.  Nothing is changed in place."""
+    from . import regrid
+
+    idt = _whole_dt(idt)
+    nspd = (IRRIG_LENGTH + (idt - 1)) // idt
+    ptr = np.asarray(ptr, dtype=np.int64).reshape(-1)
+    col = np.asarray(col, dtype=np.int64).reshape(-1)
+    rate = np.array(rate, dtype=np.float64).reshape(-1)
+    nleft = np.asarray(nleft, dtype=np.float64).reshape(-1)
+    area = np.asarray(area, dtype=np.float64).reshape(-1)
+    volr = np.asarray(volr, dtype=np.float64).reshape(-1)
+    unmet_sum = np.asarray(unmet_sum, dtype=np.float64).reshape(-1)
+    thr = float(thr)
+    ncells = ptr.size - 1
+    assert area.shape == volr.shape == unmet_sum.shape == (ncells,) and rate.shape == nleft.shape
+    with np.errstate(all="ignore"):
+        checks = nleft == float(nspd)                                # S0
+        x = rate * (float(idt) * nleft)                              # S1
+        D = regrid.apply_aggregate(ptr, col, w, np.where(checks, x, 0.0), 0.0)  # S2
+        y = (np.zeros_like(rate) if qflx_irrig is None else np.asarray(qflx_irrig, dtype=np.float64).reshape(-1)) * float(idt)
+        C = regrid.apply_aggregate(ptr, col, w, np.where(~checks & (nleft > 0.0), x, 0.0) + y, 0.0)
+        Vd = (D * 0.001) * area                                      # S3
+        Vc = (C * 0.001) * area
+        a = volr * (1.0 - thr) - Vc
+        avail = np.where(a > 0.0, a, 0.0)
+        ratio = np.where(Vd > avail, avail / np.where(Vd > avail, Vd, 1.0), 1.0)  # S4 (the division only where it is taken)
+        cell_of = np.full(rate.size, -1, np.int64)                   # S5: a column in no cell is not limited
+        cell_of[col] = np.repeat(np.arange(ncells), np.diff(ptr))
+        r = np.where(cell_of >= 0, ratio[np.maximum(cell_of, 0)], 1.0)
+        scale = checks & (r != 1.0)
+        rate_out = np.where(scale, _canon(rate * r), rate)
+        rows = np.stack([_canon(Vd), _canon(Vc), _canon(ratio), _canon(unmet_sum + (Vd - Vd * ratio))])  # S6
+    return rate_out, rows

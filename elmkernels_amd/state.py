@@ -31,6 +31,8 @@ RUN_WATER_BALANCE = 64  # every step closes the water budget (water_balance_enab
 RUN_IRRIGATION = 128  # every step applies and checks irrigation between the seven wrappers and soil_temperature (irrigation_enable)
 IRR_RATE, IRR_NLEFT, IRR_QFLX_IRRIG = range(3)  # elmk_irrigation_read (irrigation.RATE .. irrigation.QFLX_IRRIG)
 IRR_NROWS = 3
+IRRSUP_DEMAND, IRRSUP_COMMITTED, IRRSUP_RATIO, IRRSUP_UNMET_SUM = range(4)  # elmk_irrigation_supply_read (irrigation.DEMAND .. UNMET_SUM)
+IRRSUP_NROWS = 4
 RUN_ROUTING = 256  # every step routes the step's runoff after the water balance (routing_enable; needs RUN_WATER_BALANCE)
 ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT, ROUTE_QOUT_SUM = range(4)  # elmk_routing_read (routing.VOLR .. routing.QOUT_SUM)
 ROUTE_WH, ROUTE_WT, ROUTE_QSUR = 4, 5, 6  # ... while the kinematic-wave scheme is on (routing.WH, routing.WT, routing.QSUR)
@@ -522,6 +524,41 @@ class ELMState:
     def irrigation_clear(self):
         """Free the rows and sched.  Refused while history entries over the rows exist."""
         self._chk(self.lib.elmk_irrigation_clear(self.ctx), "irrigation_clear")
+
+    # -- the irrigation's river supply limit (include/elmk.h: elmk_irrigation_supply_enable ...; irrigation.supply_limit restates it) ----
+    def irrigation_supply_enable(self, threshold=0.1):
+        """Limit every demand check by the channel storage of the column's cell: from here on irrigation() and the irrigation stage of
+        run() enqueue the limiter behind the irrigation.  Allocates the cell rows DEMAND, COMMITTED, RATIO, UNMET_SUM (fp64, zero-filled).
+        Needs irrigation_enable, routing_enable with routing_set_withdrawal(True), 0 <= threshold < 1 and an output grid in which every
+        column lies in at most one cell."""
+        self._chk(self.lib.elmk_irrigation_supply_enable(self.ctx, float(threshold)), "irrigation_supply_enable")
+
+    def irrigation_supply_init(self, unmet_sum=None):
+        """UNMET_SUM from [ncells] (None: zeros), the other rows zeros: a restart file's values.  Synchronises."""
+        v = None if unmet_sum is None else np.ascontiguousarray(unmet_sum, dtype=np.float64).reshape(-1)
+        n = getattr(self, "routing_ncells", None)
+        if v is not None and n is not None and v.size != n:
+            raise ValueError(f"irrigation_supply_init: {v.size} values for {n} cells")
+        self._chk(self.lib.elmk_irrigation_supply_init(self.ctx, None if v is None else _p(v)), "irrigation_supply_init")
+
+    def irrigation_supply_read(self, which, cell0=0, n=None):
+        """Row IRRSUP_DEMAND, IRRSUP_COMMITTED, IRRSUP_RATIO or IRRSUP_UNMET_SUM of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
+        n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
+        out = np.empty(max(n, 0), dtype=np.float64)
+        self._chk(self.lib.elmk_irrigation_supply_read(self.ctx, int(which), _p(out), int(cell0), n), "irrigation_supply_read")
+        return out
+
+    def irrigation_supply_rows(self):
+        """Every row of the limit: float64 [IRRSUP_NROWS, ncells]."""
+        return np.stack([self.irrigation_supply_read(w) for w in range(IRRSUP_NROWS)])
+
+    def irrigation_supply_reset(self):
+        """UNMET_SUM = zeros (stream-ordered)."""
+        self._chk(self.lib.elmk_irrigation_supply_reset(self.ctx), "irrigation_supply_reset")
+
+    def irrigation_supply_clear(self):
+        """Switch the limit off and free its rows."""
+        self._chk(self.lib.elmk_irrigation_supply_clear(self.ctx), "irrigation_supply_clear")
 
     # -- runoff routing (include/elmk.h: elmk_routing_enable ...; elmkernels_amd/routing.py restates the stage) ---------------------------
     def routing_enable(self, down, ddist, area, effvel=0.35, nsub=1):

@@ -950,7 +950,7 @@ int elmk_run_water_balance(elmk_ctx *ctx, double *min_max_sum /*[nsteps][3][3]*/
  *   ERRH2O = ENDWB - BEGWB - (((forc_rain + forc_snow) + QFLX_IRRIG) - QRUNOFF - qflx_evap_tot - qflx_snwcp_ice) * dt.
  * Water withdrawal: QRUNOFF stays the column's generated runoff.  With the runoff routing enabled ("runoff routing" below)
  * elmk_routing_set_withdrawal takes the applied water out of the channel storage of the column's cell; supply is not limited by that
- * storage.  Without it a driver that takes the water from the river subtracts its QIRRIG tape itself.
+ * storage unless the river supply limit is on ("irrigation: river supply limit" below).  Without it a driver that takes the water from the river subtracts its QIRRIG tape itself.
  * History: ELMK_ROWS_IRRIGATION (which = ELMK_IRR_*) puts ELM's QIRRIG on a tape.  Restart: a context with the feature enabled saves a
  * version-5 image that carries RATE and NLEFT ("restart" below); sched is a parameter the loading context sets itself.
  * A context that never enables the feature runs the kernels, launch sequences and graphs it ran before, allocates nothing more and
@@ -962,6 +962,69 @@ int elmk_irrigation_init(elmk_ctx *ctx, const double *rate /*[ncols] or NULL*/, 
 int elmk_irrigation(elmk_ctx *ctx, double dt, int tod_seconds);
 int elmk_irrigation_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
 int elmk_irrigation_clear(elmk_ctx *ctx);
+
+/* ---- irrigation: river supply limit ----------------------------------------------------------------
+ * CLM5's and ELM's limit of the demand check by the river (limit_irrigation_if_rof_enabled, irrig_river_volume_threshold,
+ * CalcDeficitVolrLimited): at the daily check the demand of a cell's columns is compared with the water the cell's channel held at the
+ * end of the previous step, and if the demand is larger every demanding column of the cell is scaled back by one ratio.  Opt-in, with
+ * entries of its own and no run flag: while the limit is on, elmk_irrigation and the ELMK_RUN_IRRIGATION stage of elmk_run enqueue one
+ * more launch (k_irrigation_supply in k_history.hip) right behind the irrigation's on the same stream.  elmkernels_amd/irrigation.py: supply_limit()
+ * is the same operation on the host.  Needs the irrigation, the runoff routing ("runoff routing" below) with the withdrawal on, and an
+ * output grid in which every column lies in at most one cell.
+ *
+ * Conventions of "irrigation"; idt, nspd as there and dtn = (double)idt * (double)nspd.  M = the output grid's map (ptr, col, w), area
+ * and VOLR the routing's, thr the threshold of elmk_irrigation_supply_enable.  The cell rows are [4][ncells rounded up to 64] fp64 in
+ * both builds: ELMK_IRRSUP_DEMAND, ELMK_IRRSUP_COMMITTED (m3), ELMK_IRRSUP_RATIO (diagnostics, overwritten every step) and
+ * ELMK_IRRSUP_UNMET_SUM (m3, the feature's only prognostic row).
+ * S0. Column i CHECKED IN THIS STEP iff NLEFT[i] == (double)nspd after the irrigation's launch.  The marker is exact: A of "irrigation"
+ *     applies (n - 1) before B checks (= nspd), in the same thread.  A column that did not take B in this launch holds either what it
+ *     held before (n <= 0 unchanged, at most 0) or n - 1 of an n that an earlier B set to the nspd of its step, so at most nspd - 1
+ *     while dt is unchanged; only B stores nspd.  (A driver that changes dt between steps inside an open window, or that hands
+ *     elmk_irrigation_init an nleft equal to nspd, marks columns itself: the first step after either is the driver's to place.)
+ *     k_irrigation is not changed.
+ * S1. x[i] = RATE[i] * ((double)idt * NLEFT[i]): the depth in mm the column will still draw in its open window; for a checking column
+ *     the whole new window.
+ * S2. Per cell c two aggregates through M with the arithmetic of "output grid" (w[p0] * v, then + w[p] * v in CSR order, no
+ *     contraction): D[c] over d[i] = x[i] for a checking column and 0.0 for every other; C[c] over c[i] = e[i] + y[i], where e[i] = x[i]
+ *     for a non-checking column with NLEFT > 0 and 0.0 for every other, and y[i] = QFLX_IRRIG[i] * (double)idt is the depth the column
+ *     was given in THIS step: the routing takes it out of VOLR only later in the step, so the VOLR the check sees still holds it.  A
+ *     cell without terms gives 0.0 for both.
+ * S3. Vd = (D * 0.001) * area[c];  Vc = (C * 0.001) * area[c]   (R1's shape);  a = VOLR[c] * (1.0 - thr) - Vc;
+ *     avail = a > 0.0 ? a : 0.0   (a NaN storage supplies nothing).
+ * S4. ratio = Vd > avail ? avail / Vd : 1.0.
+ * S5. Every checking column of the cell: RATE[i] = RATE[i] * ratio, stored only where ratio != 1.0 (the bits are the same either way);
+ *     a column in no cell is not limited; a NaN is stored as the canonical quiet NaN.
+ * S6. DEMAND[c] = Vd;  COMMITTED[c] = Vc;  RATIO[c] = ratio;  UNMET_SUM[c] = UNMET_SUM[c] + (Vd - Vd * ratio).
+ * Vc is not in CLM: there all columns of a gridcell share one clock.  Here sched is each column's longitude, so the columns of a cell
+ * may check in adjacent steps, and without Vc the second batch would be promised water the first already holds.
+ * Guaranteed: at a check, committed plus newly granted water does not exceed (1 - thr) * VOLR of the previous step's end, committed
+ * being everything granted and not yet withdrawn from that VOLR (the open windows' remainders and this step's application).  Without
+ * y the remainder would miss one step of every open window - NLEFT is already counted down when the limit runs - and two batches of
+ * one cell in adjacent steps could be granted (1 - thr) * (1 + 1 / nspd) of the storage: more than all of it for thr = 0.1, nspd = 8.
+ * Not guaranteed: the channel also releases water downstream during the four-hour window; thr is the margin for that.
+ *
+ *   elmk_irrigation_supply_enable  allocates the four rows, zero-filled (one owner, counted in elmk_device_bytes) and drops the captured
+ *                           run step.  ELMK_E_INVALID, nothing changed: the irrigation not enabled; the routing not enabled or its
+ *                           withdrawal off; threshold not finite or outside [0, 1); a column in more than one cell of the output grid
+ *                           (or twice in one) - the text names the first such column; already enabled; a stream being captured.
+ *   elmk_irrigation_supply_init    UNMET_SUM from host[ncells] (NULL: zeros), the other rows zeros: a restart file's values.  Synchronises.
+ *   elmk_irrigation_supply_read    row `which` (ELMK_IRRSUP_*) of cells [cell0, cell0 + n) as doubles; synchronises.
+ *   elmk_irrigation_supply_reset   UNMET_SUM = zeros (stream-ordered).
+ *   elmk_irrigation_supply_clear   frees the rows and drops the captured run step.
+ * While the limit is on what it reads stays: elmk_routing_set_withdrawal(ctx, 0), elmk_routing_clear, elmk_irrigation_clear,
+ * elmk_set_output_grid and elmk_clear_output_grid are refused with ELMK_E_INVALID ("elmk_irrigation_supply_clear first") and nothing
+ * changes.  elmk_routing_kinematic_enable and elmk_routing_kinematic_clear leave VOLR's buffer where it is and stay allowed.
+ * A captured run step is keyed by whether the limit is on.  Restart: the rows live on cells and are not part of the column image; a
+ * driver carries UNMET_SUM through elmk_irrigation_supply_read / _init, as it carries VOLR.  Multi-rank: as the routing, a context
+ * limits the cells it holds completely.
+ * A context that never enables the limit runs the kernels, launch sequences and graphs it ran before, allocates nothing more and saves
+ * the image it saved before. */
+enum { ELMK_IRRSUP_DEMAND = 0, ELMK_IRRSUP_COMMITTED = 1, ELMK_IRRSUP_RATIO = 2, ELMK_IRRSUP_UNMET_SUM = 3 };
+int elmk_irrigation_supply_enable(elmk_ctx *ctx, double threshold);
+int elmk_irrigation_supply_init(elmk_ctx *ctx, const double *unmet_sum /*[ncells] or NULL*/);
+int elmk_irrigation_supply_read(elmk_ctx *ctx, int which, double *host, int64_t cell0, int64_t n);
+int elmk_irrigation_supply_reset(elmk_ctx *ctx);
+int elmk_irrigation_supply_clear(elmk_ctx *ctx);
 
 /* ---- runoff routing --------------------------------------------------------------------------------
  * The linear-reservoir river transport model the CLM family shipped as RTM, over the output grid's cells ("output grid"): every cell
@@ -1000,8 +1063,8 @@ int elmk_irrigation_clear(elmk_ctx *ctx);
  *     is no outlet contributing +0.0; each is the `sum` of elmk_evaluate_conservation's reduction over the cells (diagnostics.
  *     reduce_min_max_sum), bit for bit, from the same reduction kernels.
  * A call takes nsub + 1 launches (R1, then one per sub-step), each stream-ordered, host-free and capturable as one chain of nodes.
- * Supply is not limited by storage: with the withdrawal on VOLR may go negative, and a negative storage releases nothing until the
- * inflow has refilled it.
+ * Supply is not limited by storage unless the irrigation's river supply limit is on ("irrigation: river supply limit" above): with the
+ * withdrawal on VOLR may go negative, and a negative storage releases nothing until the inflow has refilled it.
  *
  *   elmk_routing_enable     allocates the rows, zero-filled, KOUT, area and the maps (one owner, counted in elmk_device_bytes) and
  *                           drops the captured run step.  ELMK_E_INVALID, nothing changed: no output grid; ncells other than the output

@@ -336,6 +336,16 @@ class ELMInterface {
     ok(elmk_irrigation_clear(ctx_));
     irrigation_ = false;
   }
+  /* The river supply limit (elmk.h "irrigation: river supply limit"): irrigation_supply_enable(threshold) after irrigation_enable,
+   * routing_enable and routing_set_withdrawal(true), with an output grid in which every column lies in at most one cell; from then
+   * on every demand check - in advance() and in run(..., irrigation = true) - is cut back to what the cell's channel held at the end
+   * of the previous step.  irrigation_supply_read() fills [ncells] of row ELMK_IRRSUP_*; irrigation_supply_init() takes a restart's
+   * UNMET_SUM ([ncells], nullptr: zeros); irrigation_supply_reset() zeroes it; irrigation_supply_clear() switches the limit off. */
+  void irrigation_supply_enable(double threshold = 0.1) { ok(elmk_irrigation_supply_enable(ctx_, threshold)); }
+  void irrigation_supply_init(const double* unmet_sum = nullptr) { ok(elmk_irrigation_supply_init(ctx_, unmet_sum)); }
+  void irrigation_supply_read(int which, double* host) { ok(elmk_irrigation_supply_read(ctx_, which, host, 0, host ? routing_ncells_ : 0)); }
+  void irrigation_supply_reset() { ok(elmk_irrigation_supply_reset(ctx_)); }
+  void irrigation_supply_clear() { ok(elmk_irrigation_supply_clear(ctx_)); }
   void set_time_of_day(int tod_seconds) { tod_ = tod_seconds; }
   /* llround((decday - 1.0 - doy) * 86400.0) reduced to 0 .. 86399, as elmk_run derives it */
   static int time_of_day(double decday, int doy)
