@@ -160,6 +160,10 @@ SIGNATURES = {
     "elmk_routing_kinematic_init": (C.c_int, [_P, _P, _P]),
     "elmk_routing_kinematic_budget": (C.c_int, [_P, _P]),
     "elmk_routing_kinematic_clear": (C.c_int, [_P]),
+    "elmk_routing_inundation_enable": (C.c_int, [_P, _P, _P]),
+    "elmk_routing_inundation_init": (C.c_int, [_P, _P]),
+    "elmk_routing_inundation_budget": (C.c_int, [_P, _P]),
+    "elmk_routing_inundation_clear": (C.c_int, [_P]),
     "elmk_column_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_gridded_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
 }

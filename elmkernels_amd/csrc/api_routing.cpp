@@ -1,7 +1,9 @@
 // api_routing.cpp - runoff routing (k_routing.hip; include/elmk.h "runoff routing"): the cell rows VOLR, QIN, QOUT, QOUT_SUM over the
 // output grid's cells, the network's parameter rows and upstream map and the budget's reduction scratch, in one allocation held
 // exactly while the feature is enabled; and the stage's second scheme, kinematic-wave routing (include/elmk.h "kinematic-wave
-// routing"), whose rows WH, WT, QSUR and derived parameters live in a second allocation held exactly while that scheme is on.
+// routing"), whose rows WH, WT, QSUR and derived parameters live in a second allocation held exactly while that scheme is on; and that
+// scheme's floodplain inundation (include/elmk.h "floodplain inundation"), whose rows WF, FLOOD_DEPTH, FLOOD_FRAC and tables live in a
+// third, held exactly while the extension is on.
 #include "elmk_ctx.h"
 
 namespace {
@@ -11,6 +13,9 @@ static_assert(ELMK_ROUTE_VOLR == 0 && ELMK_ROUTE_QIN == 1 && ELMK_ROUTE_QOUT == 
 // the kinematic-wave scheme's public rows are the first three of its own allocation
 static_assert(ELMK_ROUTE_WH - 4 == KW_WH && ELMK_ROUTE_WT - 4 == KW_WT && ELMK_ROUTE_QSUR - 4 == KW_QSUR, "three rows");
 static_assert(ELMK_KW_NPARAM == KINEMATIC_NPARAM, "the parameter rows of elmk_maps.h");
+// the floodplain inundation's public rows are the rows of its own allocation
+static_assert(ELMK_ROUTE_WF - 7 == FP_WF && ELMK_ROUTE_FLOOD_DEPTH - 7 == FP_DEPTH && ELMK_ROUTE_FLOOD_FRAC - 7 == FP_FRAC, "three rows");
+static_assert(ELMK_FP_NPROF == INUNDATION_NPROF && FP_VB - FP_E == ELMK_FP_NPROF && FP_NTAB - FP_VB == ELMK_FP_NPROF, "the profile of elmk_maps.h");
 
 RouteArgs route_args(const elmk_ctx* ctx)
 {
@@ -29,6 +34,18 @@ int kinematic_enter(elmk_ctx* ctx, const char* who)
   if (int rc = route_enter(ctx, who)) return rc;
   return ctx->route.kw_mem ? ELMK_OK : invalid(ctx, (std::string(who) + ": the scheme is not on (elmk_routing_kinematic_enable)").c_str());
 }
+
+int inundation_enter(elmk_ctx* ctx, const char* who)
+{
+  if (int rc = kinematic_enter(ctx, who)) return rc;
+  return ctx->route.fp_mem ? ELMK_OK : invalid(ctx, (std::string(who) + ": the extension is not on (elmk_routing_inundation_enable)").c_str());
+}
+
+void inundation_off(elmk_ctx::Routing& T)
+{
+  T.fp_mem = DevBuf<char>{};
+  T.fp_rows = T.fp_tab = nullptr;
+}
 }  // namespace
 
 namespace elmk {
@@ -41,7 +58,7 @@ void route_launch(elmk_ctx* ctx, double dt)
   const double* const qrunoff = ctx->wb_rows + (size_t)ELMK_WB_QRUNOFF * ld;
   const double* const qirr = T.withdraw ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * ld : nullptr;
   if (T.kw_mem)  // the scheme switch: the kinematic-wave scheme exactly while its memory is held
-    launch_routing_kinematic(route_args(ctx), KinematicArgs{T.kw_rows, T.kw_par}, G, qrunoff, qirr,
+    launch_routing_kinematic(route_args(ctx), KinematicArgs{T.kw_rows, T.kw_par}, FloodArgs{T.fp_rows, T.fp_tab}, G, qrunoff, qirr,
                              ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
                              ctx->stream);
   else
@@ -142,11 +159,13 @@ int elmk_routing_read(elmk_ctx* ctx, int which, double* host, int64_t cell0, int
   const char* who = "elmk_routing_read";
   if (int rc = route_enter(ctx, who)) return rc;
   const elmk_ctx::Routing& T = ctx->route;
-  if (which < 0 || which > (T.kw_mem ? ELMK_ROUTE_QSUR : ELMK_ROUTE_QOUT_SUM)) return invalid(ctx, "elmk_routing_read: unknown row");
+  if (which < 0 || which > (T.fp_mem ? ELMK_ROUTE_FLOOD_FRAC : T.kw_mem ? ELMK_ROUTE_QSUR : ELMK_ROUTE_QOUT_SUM))
+    return invalid(ctx, "elmk_routing_read: unknown row");
   if (int rc = check_range(ctx, who, host, cell0, n, T.ncells, "cell")) return rc;
   if (int rc = refuse_capture(ctx, who)) return rc;
-  const double* const row = which > ELMK_ROUTE_QOUT_SUM ? T.kw_rows + (size_t)(which - ELMK_ROUTE_WH) * (size_t)T.cld
-                                                         : T.rows + (size_t)ROUTE_ROW_OF[which] * (size_t)T.cld;
+  const double* const row = which > ELMK_ROUTE_QSUR       ? T.fp_rows + (size_t)(which - ELMK_ROUTE_WF) * (size_t)T.cld
+                            : which > ELMK_ROUTE_QOUT_SUM ? T.kw_rows + (size_t)(which - ELMK_ROUTE_WH) * (size_t)T.cld
+                                                          : T.rows + (size_t)ROUTE_ROW_OF[which] * (size_t)T.cld;
   if (n > 0) HIPCHK(hipMemcpyAsync(host, row + (size_t)cell0, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   return synced(ctx);
 }
@@ -266,9 +285,94 @@ int elmk_routing_kinematic_clear(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, "elmk_routing_kinematic_clear")) return rc;
   elmk_ctx::Routing& T = ctx->route;
   if (!T.kw_mem) return ELMK_OK;
+  if (T.fp_mem)  // (the extension's tables are formed from the scheme's RLEN and RWIDTH, and its kernel is the scheme's)
+    return invalid(ctx, "elmk_routing_kinematic_clear: the floodplain inundation is on (elmk_routing_inundation_clear first)");
   if (int rc = quiesce(ctx, false)) return rc;
   T.kw_mem = DevBuf<char>{};
   T.kw_rows = T.kw_par = nullptr;
+  return ELMK_OK;
+}
+
+int elmk_routing_inundation_enable(elmk_ctx* ctx, const double* rdepth, const double* eprof)
+{
+  const char* who = "elmk_routing_inundation_enable";
+  if (int rc = kinematic_enter(ctx, who)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  if (T.fp_mem) return invalid(ctx, "elmk_routing_inundation_enable: already on");
+  if (!rdepth || !eprof) return invalid(ctx, "elmk_routing_inundation_enable: null argument");
+  {
+    int64_t cell = -1;
+    const char* const text = inundation_check(T.ncells, rdepth, eprof, nullptr, nullptr, nullptr, T.cld, nullptr, &cell);
+    if (text && cell >= 0) return invalid_map(ctx, who, (std::string(text) + " at cell " + std::to_string(cell)).c_str());
+    if (int rc = invalid_map(ctx, who, text)) return rc;
+  }
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the form of its moment)
+  const size_t cld = (size_t)T.cld, n = (size_t)T.ncells;
+  // I0 reads the cells' area and the scheme's RLEN and RWIDTH: the device holds the only copies
+  std::vector<double> area(n), rlen(n), rwidth(n), tab;
+  if (hip_fail(ctx, hipMemcpyAsync(area.data(), T.area, n * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(area)") ||
+      hip_fail(ctx, hipMemcpyAsync(rlen.data(), T.kw_par + KW_RLEN * cld, n * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(RLEN)") ||
+      hip_fail(ctx, hipMemcpyAsync(rwidth.data(), T.kw_par + KW_RWIDTH * cld, n * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(RWIDTH)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return ELMK_E_HIP;
+  }
+  (void)inundation_check(T.ncells, rdepth, eprof, area.data(), rlen.data(), rwidth.data(), T.cld, &tab, nullptr);
+  if (hip_fail(ctx, carve(T.fp_mem, [&](Carve& L) {
+                 L.take(T.fp_rows, (size_t)FP_NROWS * cld * sizeof(double));
+                 L.take(T.fp_tab, (size_t)FP_NTAB * cld * sizeof(double));
+               }), "hipMalloc(floodplain inundation)")) {
+    inundation_off(T);
+    return ELMK_E_NOMEM;
+  }
+  if (hip_fail(ctx, hipMemsetAsync(T.fp_mem, 0, T.fp_mem.bytes(), ctx->stream), "hipMemset(floodplain inundation)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.fp_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream),
+               "hipMemcpy(floodplain inundation tables)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    inundation_off(T);
+    return ELMK_E_HIP;
+  }
+  return ELMK_OK;
+}
+
+int elmk_routing_inundation_init(elmk_ctx* ctx, const double* wf)
+{
+  const char* who = "elmk_routing_inundation_init";
+  if (int rc = inundation_enter(ctx, who)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  const size_t cld = (size_t)T.cld, n = (size_t)T.ncells;
+  HIPCHK(hipMemsetAsync(T.fp_rows, 0, (size_t)FP_NROWS * cld * sizeof(double), ctx->stream));
+  if (wf) HIPCHK(hipMemcpyAsync(T.fp_rows + FP_WF * cld, wf, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  return synced(ctx);
+}
+
+int elmk_routing_inundation_budget(elmk_ctx* ctx, double* sums)
+{
+  const char* who = "elmk_routing_inundation_budget";
+  if (int rc = inundation_enter(ctx, who)) return rc;
+  if (!sums) return invalid(ctx, "elmk_routing_inundation_budget: null argument");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  const elmk_ctx::Routing& T = ctx->route;
+  launch_min_max_sum(T.fp_rows, T.cld, T.ncells, 1, T.part, T.out, ctx->stream);  // I7 (the routing's partials: every budget synchronises)
+  HIPCHK(hipGetLastError());
+  double mms[3];
+  HIPCHK(hipMemcpyAsync(mms, T.out, sizeof mms, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  sums[0] = mms[2];
+  return ELMK_OK;
+}
+
+int elmk_routing_inundation_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_routing_inundation_clear")) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  if (!T.fp_mem) return ELMK_OK;
+  if (int rc = quiesce(ctx, false)) return rc;
+  inundation_off(T);
   return ELMK_OK;
 }
 

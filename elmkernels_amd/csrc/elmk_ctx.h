@@ -304,6 +304,11 @@ struct elmk_ctx {
     DevBuf<char> kw_mem;
     double* kw_rows = nullptr;
     double* kw_par = nullptr;
+    // its floodplain inundation (elmk_routing_inundation_*): a third allocation with the rows [FP_NROWS][cld] and the host's tables
+    // [FP_NTAB][cld], held exactly while the extension is on; route_launch takes the flood form while it is there
+    DevBuf<char> fp_mem;
+    double* fp_rows = nullptr;
+    double* fp_tab = nullptr;
   } route;
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the

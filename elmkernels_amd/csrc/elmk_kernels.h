@@ -310,10 +310,20 @@ struct KinematicArgs {
   double* rows;
   const double* par;
 };
+// floodplain inundation (elmk_routing_inundation_*; include/elmk.h "floodplain inundation", I0 - I8): the extension's fp64 rows
+// [FP_NROWS][cld] and the host's tables [FP_NTAB][cld] (elmk_maps.h: inundation_check): VC, ACHN, AF, then the eleven E_k and the
+// eleven VB_k.  The first row is the one launch_min_max_sum reduces for I7.
+enum { FP_WF = 0, FP_DEPTH = 1, FP_FRAC = 2, FP_NROWS = 3 };
+enum { FP_VC = 0, FP_ACHN = 1, FP_AF = 2, FP_E = 3, FP_VB = 14, FP_NTAB = 25 };
+struct FloodArgs {
+  double* rows;
+  const double* tab;
+};
 // one call: K1 (QIN as R1, QSUR from the hydrology's rows qsurf + qh2osfc, QSUB, the first er) as one launch, then nsub sub-step
-// launches that update WH, WT and VOLR in place; A.kout and ROUTE_VOLR_B are not read
-void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const OGridMap& M, const double* qrunoff, const double* qirr,
-                              const double* qsurf, const double* qh2osfc, double dt, hipStream_t st);
+// launches that update WH, WT and VOLR in place; A.kout and ROUTE_VOLR_B are not read.  F.rows not null: the sub-steps take the flood
+// form (I1 - I5)
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const OGridMap& M, const double* qrunoff,
+                              const double* qirr, const double* qsurf, const double* qh2osfc, double dt, hipStream_t st);
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

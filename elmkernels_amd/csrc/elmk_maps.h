@@ -176,4 +176,67 @@ inline const char* kinematic_check(int64_t ncells, const double* params, int64_t
   return nullptr;
 }
 
+// Floodplain inundation (elmk_routing_inundation_enable; include/elmk.h "floodplain inundation"): rdepth [ncells], the bank height,
+// finite and > 0; eprof [INUNDATION_NPROF][ncells], the elevation profile, finite, eprof[0] == 0.0 and strictly increasing in k.
+// Checks, in this order: the arguments; rdepth cell by cell; then per cell in index order the profile: finite (k ascending), its
+// first entry, increasing.  Returns the text, which names the row, and in *cell the first offending cell (-1 where the text is about
+// no cell); the entry point puts " at cell <cell>" behind the text.  nullptr: accepted.
+// For accepted inputs and dev not null, with the cells' area, RLEN and RWIDTH, dev holds I0's tables as the device reads them,
+// [25][ld] with ld >= ncells in the order VC, ACHN, AF, E_0 .. E_10, VB_0 .. VB_10 (elmk_kernels.h: FP_*), padding cells 0.0.  VB's
+// recurrence has products under sums: compile with -ffp-contract=off, as the library's Makefile does, or the tables may differ from
+// the statement's by a rounding.
+constexpr int INUNDATION_NPROF = 11;
+inline const char* inundation_check(int64_t ncells, const double* rdepth, const double* eprof, const double* area, const double* rlen,
+                                    const double* rwidth, int64_t ld, std::vector<double>* dev, int64_t* cell)
+{
+  if (cell) *cell = -1;
+  if (ncells < 1 || ncells > INT32_MAX) return "ncells outside 1 .. 2^31-1";
+  if (!rdepth || !eprof || (dev && (!area || !rlen || !rwidth))) return "null argument";
+  const size_t n = (size_t)ncells;
+  const auto at = [cell](const char* what, size_t c) {
+    if (cell) *cell = (int64_t)c;
+    return what;
+  };
+  for (size_t c = 0; c < n; c++)
+    if (!(std::isfinite(rdepth[c]) && rdepth[c] > 0.0)) return at("RDEPTH not finite and > 0", c);
+  for (size_t c = 0; c < n; c++) {
+    for (int k = 0; k < INUNDATION_NPROF; k++)
+      if (!std::isfinite(eprof[(size_t)k * n + c])) return at("EPROF not finite", c);
+    if (!(eprof[c] == 0.0)) return at("EPROF[0] not 0", c);
+    for (int k = 0; k + 1 < INUNDATION_NPROF; k++)
+      if (!(eprof[(size_t)(k + 1) * n + c] > eprof[(size_t)k * n + c])) return at("EPROF not increasing", c);
+  }
+  if (dev) {
+    if (ld < ncells) ld = ncells;
+    const size_t l = (size_t)ld;
+    dev->assign((size_t)25 * l, 0.0);
+    double* d = dev->data();
+    for (size_t c = 0; c < n; c++) {  // I0, operation by operation
+      const double achn = rlen[c] * rwidth[c];
+      const double vc = achn * rdepth[c];
+      double af = area[c] - achn;
+      if (!(af > 0.0)) af = 0.0;
+      d[c] = vc;
+      d[l + c] = achn;
+      d[2 * l + c] = af;
+      double vb = 0.0;
+      for (int k = 0; k < INUNDATION_NPROF; k++) {
+        const double e = eprof[(size_t)k * n + c];
+        d[(size_t)(3 + k) * l + c] = e;
+        d[(size_t)(14 + k) * l + c] = vb;
+        if (k + 1 < INUNDATION_NPROF) {
+          const double fk = (double)k / 10.0, fk1 = (double)(k + 1) / 10.0;
+          const double p0 = af * fk, p1 = af * fk1;
+          const double s0 = achn + p0, s1 = achn + p1;
+          const double de = eprof[(size_t)(k + 1) * n + c] - e;
+          const double m = 0.5 * (s0 + s1);
+          const double t = m * de;
+          vb = vb + t;
+        }
+      }
+    }
+  }
+  return nullptr;
+}
+
 }  // namespace elmk

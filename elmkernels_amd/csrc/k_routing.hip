@@ -14,7 +14,8 @@
 // together.  The flow of an upstream cell is evaluated again from its storage rather than read from a row of flows: the same bits,
 // one row less to write and read.  A cell reads 8 (storage) + 8 (KOUT) + 8 (QIN) + 4 npad (map) + 16 per upstream cell and, past the
 // first sub-step, 8 (the flow sum), and writes 16.  The unit carries no nontemporal hint: none has been measured for it.
-// The second scheme of the stage, kinematic-wave routing (k_kinematic_prep, k_kinematic_step), follows the linear one below.
+// The second scheme of the stage, kinematic-wave routing (k_kinematic_prep, k_kinematic_step), follows the linear one below, with its
+// floodplain inundation (k_kinematic_step's FLOOD form).
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
 
@@ -233,14 +234,80 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
   er[c] = kw_chan(volr[c], par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
 }
 
+// ---- floodplain inundation (include/elmk.h "floodplain inundation", I0 - I8; elmkernels_amd/routing.py: inundation_exchange) --------
+// The flood form of the sub-step: between K6's new VOLR and its store, the cell's channel and floodplain are brought to one water
+// level.  A cell whose river is inside its banks and whose floodplain is dry (I1) reads VC and WF, 16 bytes, and nothing else of the
+// tables; the 22 rows of the profile (E_0 .. E_10, VB_1 .. VB_10, ACHN, AF: 184 bytes) are loaded behind the cell's own condition, all
+// at once so that they are in flight together, and the segment is found by a compare-and-select chain over them: the arrays are
+// indexed by unrolled constants only, so they live in registers and the kernel has no scratch.  S_k, DE_k and M_k are formed again from
+// ACHN, AF and the E_k with I0's operations, which gives the host's bits at 0 bytes instead of 31 more rows.  The two diagnostics are
+// stored by the LAST sub-step only: every sub-step would overwrite them, and nothing reads them in between.
+template <bool FLOOD>
+struct FloodRows {};  // the plain form takes nothing: its kernel arguments, instructions and registers stay what they were
+template <>
+struct FloodRows<true> {
+  gptr<double> rows;       // [FP_NROWS][cld]
+  gptr<const double> tab;  // [FP_NTAB][cld]
+};
+
+namespace {
+// I2 - I4 for a cell that I1 lets in; v: K6's VOLR on entry, the channel's share on return; wf likewise.  h, f: the diagnostics.
+__device__ __forceinline__ void fp_exchange(double& v, double& wf, double& h, double& f, double vc, double ar, gptr<const double> tab,
+                                            int64_t cld, int64_t c)
+{
+  const double W = v + wf;
+  if (!(W > vc)) {  // I2 (a NaN comes here)
+    v = W;
+    wf = 0.0;
+    return;
+  }
+  const double achn = tab[FP_ACHN * cld + c], af = tab[FP_AF * cld + c];
+  double E[11], VB[11];
+#pragma unroll
+  for (int k = 0; k < 11; k++) E[k] = tab[(FP_E + k) * cld + c];
+  VB[0] = 0.0;
+#pragma unroll
+  for (int k = 1; k < 11; k++) VB[k] = tab[(FP_VB + k) * cld + c];
+  const double X = W - vc;  // I3
+  double frac;
+  if (X >= VB[10]) {
+    const double s10 = achn + af * (10.0 / 10.0);
+    h = E[10] + (X - VB[10]) / s10;
+    frac = 1.0;
+  } else {
+    double vbk = VB[0], ek = E[0], ek1 = E[1], fk = 0.0 / 10.0;
+#pragma unroll
+    for (int k = 1; k < 10; k++) {
+      const bool in = X >= VB[k];
+      vbk = in ? VB[k] : vbk;
+      ek = in ? E[k] : ek;
+      ek1 = in ? E[k + 1] : ek1;
+      fk = in ? (double)k / 10.0 : fk;
+    }
+    const double sk = achn + af * fk, de = ek1 - ek;
+    const double mk = (af * 0.1) / de;
+    const double r = X - vbk;
+    double d = (2.0 * r) / (sk + sqrt(sk * sk + (2.0 * mk) * r));
+    if (d > de) d = de;
+    h = ek + d;
+    frac = fk + (0.1 * d) / de;
+  }
+  double vc2 = vc + achn * h;  // I4
+  if (vc2 > W) vc2 = W;
+  v = vc2;
+  wf = W - vc2;
+  f = ar > 0.0 ? (af * frac) / ar : 0.0;
+}
+}  // namespace
+
 // K3 - K7: one sub-step.  er_old: the flows of the sub-step's start; er_new: those of its end (not written by the LAST one).  FIRST and
-// LAST as k_routing_step's.
-template <int NPAD, bool FIRST, bool LAST>
+// LAST as k_routing_step's.  FLOOD: the flood form, I1 - I5.
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD>
 __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
                                                         gptr<double> er_new, gptr<const double> par, gptr<const double> area,
                                                         gptr<const int32_t> up, gptr<const double> qsur, gptr<const double> qsub,
                                                         gptr<double> qout, gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts,
-                                                        double dnsub)
+                                                        double dnsub, FloodRows<FLOOD> fl)
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncells) return;
@@ -263,6 +330,18 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
   route_st(wh_row + c, wh + (qs - eh) * dts);
   route_st(wt_row + c, wt + ((eh - et) + qb) * dts);
   double vn = v + ((fin - er) + et) * dts;
+  if constexpr (FLOOD) {
+    const double vc = fl.tab[FP_VC * cld + c];
+    double wf = fl.rows[FP_WF * cld + c], h = 0.0, f = 0.0;
+    if (wf > 0.0 || vn > vc) {  // I1
+      fp_exchange(vn, wf, h, f, vc, ar, fl.tab, cld, c);
+      route_st(fl.rows + (FP_WF * cld + c), wf);
+    }
+    if constexpr (LAST) {
+      route_st(fl.rows + (FP_DEPTH * cld + c), h);
+      route_st(fl.rows + (FP_FRAC * cld + c), f);
+    }
+  }
   if (vn != vn) vn = __builtin_nan("");
   volr[c] = vn;
   qacc = qacc + er;
@@ -277,36 +356,50 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
 }
 
 namespace {
-template <int NPAD, bool FIRST, bool LAST>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const double* er_old, double* er_new, double dts, hipStream_t st)
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD>
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const double* er_old, double* er_new, double dts,
+                    hipStream_t st)
 {
-  hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
+  FloodRows<FLOOD> fl;
+  if constexpr (FLOOD) fl = FloodRows<true>{(gptr<double>)F.rows, (gptr<const double>)F.tab};
+  hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST, FLOOD>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
                      (gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld),
                      (gptr<double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)er_old, (gptr<double>)er_new,
                      (gptr<const double>)K.par, (gptr<const double>)A.area, (gptr<const int32_t>)A.up,
                      (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<const double>)(K.rows + KW_QSUB * A.cld),
                      (gptr<double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts,
-                     (double)A.nsub);
+                     (double)A.nsub, fl);
 }
-template <int NPAD>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const double* er_old, double* er_new, double dts, bool first, bool last,
-                    hipStream_t st)
+template <int NPAD, bool FLOOD>
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const double* er_old, double* er_new, double dts,
+                    bool first, bool last, hipStream_t st)
 {
-  if (first && last) launch_kw_step<NPAD, true, true>(A, K, er_old, er_new, dts, st);
-  else if (first) launch_kw_step<NPAD, true, false>(A, K, er_old, er_new, dts, st);
-  else if (last) launch_kw_step<NPAD, false, true>(A, K, er_old, er_new, dts, st);
-  else launch_kw_step<NPAD, false, false>(A, K, er_old, er_new, dts, st);
+  if (first && last) launch_kw_step<NPAD, true, true, FLOOD>(A, K, F, er_old, er_new, dts, st);
+  else if (first) launch_kw_step<NPAD, true, false, FLOOD>(A, K, F, er_old, er_new, dts, st);
+  else if (last) launch_kw_step<NPAD, false, true, FLOOD>(A, K, F, er_old, er_new, dts, st);
+  else launch_kw_step<NPAD, false, false, FLOOD>(A, K, F, er_old, er_new, dts, st);
+}
+template <bool FLOOD>
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const double* er_old, double* er_new, double dts,
+                    bool first, bool last, hipStream_t st)
+{
+  switch (A.npad) {
+    case 1: launch_kw_step<1, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
+    case 2: launch_kw_step<2, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
+    case 4: launch_kw_step<4, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
+    default: launch_kw_step<8, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
+  }
 }
 }  // namespace
 
-void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const OGridMap& M, const double* qrunoff, const double* qirr,
-                              const double* qsurf, const double* qh2osfc, double dt, hipStream_t st)
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const OGridMap& M, const double* qrunoff,
+                              const double* qirr, const double* qsurf, const double* qh2osfc, double dt, hipStream_t st)
 {
   if (A.ncells <= 0) return;
   const dim3 grid((unsigned)((A.ncells + 255) / 256)), block(256);
   const double dts = dt / (double)A.nsub;  // K0
   double *src = K.rows + KW_ER_A * A.cld, *dst = K.rows + KW_ER_B * A.cld;
-  const auto prep = qirr ? k_kinematic_prep<true> : k_kinematic_prep<false>;
+  const auto prep = qirr ? k_kinematic_prep<true> : k_kinematic_prep<false>;  // (I6: the same launch in the flood form)
   hipLaunchKernelGGL(prep, grid, block, 0, st, (gptr<const int64_t>)M.ptr, (gptr<const int32_t>)M.col, (gptr<const double>)M.w,
                      (gptr<const double>)qrunoff, (gptr<const double>)qirr, (gptr<const double>)qsurf, (gptr<const double>)qh2osfc,
                      (gptr<const double>)A.area, (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
@@ -314,12 +407,8 @@ void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const 
                      (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts);
   for (int s = 0; s < A.nsub; s++) {
     const bool first = s == 0, last = s == A.nsub - 1;
-    switch (A.npad) {
-      case 1: launch_kw_step<1>(A, K, src, dst, dts, first, last, st); break;
-      case 2: launch_kw_step<2>(A, K, src, dst, dts, first, last, st); break;
-      case 4: launch_kw_step<4>(A, K, src, dst, dts, first, last, st); break;
-      default: launch_kw_step<8>(A, K, src, dst, dts, first, last, st); break;
-    }
+    if (F.rows) launch_kw_step<true>(A, K, F, src, dst, dts, first, last, st);
+    else launch_kw_step<false>(A, K, F, src, dst, dts, first, last, st);
     double* const t = src;
     src = dst;
     dst = t;

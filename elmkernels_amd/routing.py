@@ -22,6 +22,16 @@ The kinematic-wave scheme (include/elmk.h "kinematic-wave routing"; k_kinematic_
 
     qsur = qsur_from_rows(ptr, col, w, qflx_surf, qflx_h2osfc_surf, area)
     wh, wt, volr, qout = kinematic_call(wh, wt, volr, qin, qsur, area, params, upstream_map(down), dt, nsub)
+
+Its floodplain inundation (include/elmk.h "floodplain inundation"; k_kinematic_step's flood form), after S.routing_kinematic_enable:
+
+    S.routing_inundation_enable(rdepth, eprof)                          # bank height [ncells], elevation profile [11, ncells]
+    S.routing_inundation_init(wf_from_restart)
+    ... S.routing(dt) and S.run(..., RUN_ROUTING) now spill over the banks and back ...
+    wf, frac = S.routing_read(WF), S.routing_read(FLOOD_FRAC)
+
+    tab = inundation_tables(area, params, rdepth, eprof)
+    wh, wt, volr, qout, wf, depth, frac = kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, flood=(tab, wf))
 """
 import numpy as np
 
@@ -252,11 +262,17 @@ def qsur_from_rows(ptr, col, w, qflx_surf, qflx_h2osfc_surf, area):
         return _canon((s * 0.001) * np.asarray(area, dtype=np.float64).reshape(-1))
 
 
-def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True):
+def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True, flood=None):
     """One elmk_routing with the scheme on, on the host: K0, K2 - K7.  wh, wt, volr, qin, qsur, area: float64 [ncells]; params
     [11, ncells]; up: upstream_map(down).  Returns (wh_new, wt_new, volr_new, qout).  in_place and cap are the wrong variants the host
     tests hold their checks against, as call's: in_place updates the cells one after another in index order, the upstream flows taken
-    from main-channel storages already updated in the sub-step; cap=False takes every flow without the cap v / dts."""
+    from main-channel storages already updated in the sub-step; cap=False takes every flow without the cap v / dts.
+    flood=(tables, wf): the flood form ("floodplain inundation", I1 - I6) with inundation_tables' tables and the floodplain storage wf
+    [ncells]; returns (wh_new, wt_new, volr_new, qout, wf_new, flood_depth, flood_frac)."""
+    if flood is not None:
+        tab, wf = flood
+        wf = np.array(wf, dtype=np.float64).reshape(-1)
+        depth = frac = np.zeros_like(wf)
     wh, wt, v = (np.array(x, dtype=np.float64).reshape(-1) for x in (wh, wt, volr))
     qin, qsur, area = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (qin, qsur, area))
     p = np.asarray(params, dtype=np.float64)
@@ -285,16 +301,114 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
                 for k in range(up.shape[0]):
                     fin = np.where(up[k] >= 0, fin + er[safe[k]], fin)
                 v = _canon(v + ((fin - er) + et) * dts)
+            if flood is not None:  # I1: after K6, before the next sub-step's er
+                v, wf, depth, frac = inundation_exchange(v, wf, tab, area)
             wh = _canon(wh + (qsur - eh) * dts)
             wt = _canon(wt + ((eh - et) + qsub) * dts)
             qacc = qacc + er
         qout = _canon(qacc / float(nsub))
+    if flood is not None:
+        return wh, wt, _canon(v), qout, wf, depth, frac
     return wh, wt, _canon(v), qout
 
 
 def kinematic_budget(wh, wt):
     """K8: the sums of WH and WT in the device reduction's order."""
     return np.array([diagnostics.reduce_min_max_sum(x)[2] for x in (wh, wt)])
+
+
+# ---- floodplain inundation (include/elmk.h "floodplain inundation", I0 - I8) -----------------------------------------------------------
+WF, FLOOD_DEPTH, FLOOD_FRAC = 7, 8, 9  # ELMK_ROUTE_*, readable while the extension is on
+NPROF = 11  # ELMK_FP_NPROF: the elevations of the profile, at the area fractions 0, 0.1 .. 1
+
+# the refusals of elmk_routing_inundation_enable's check (elmk_maps.h: inundation_check), in its order; each is followed by the cell
+E_RDEPTH = "RDEPTH not finite and > 0"
+E_EPROF_FINITE = "EPROF not finite"
+E_EPROF_ZERO = "EPROF[0] not 0"
+E_EPROF_ORDER = "EPROF not increasing"
+
+
+def e_cell(text, cell):
+    """The refusal `text` as the entry point gives it: with the first offending cell."""
+    return f"{text} at cell {cell}"
+
+
+def check_inundation(rdepth, eprof):
+    """The checks of elmk_routing_inundation_enable on rdepth [ncells] and eprof [11, ncells], in its order: rdepth cell by cell, then
+    per cell the profile (finite, eprof[0] == 0.0, strictly increasing); raises ValueError with the entry point's text."""
+    r = np.asarray(rdepth, dtype=np.float64).reshape(-1)
+    e = np.asarray(eprof, dtype=np.float64)
+    if e.ndim != 2 or e.shape != (NPROF, r.size):
+        raise ValueError("eprof must be [11, ncells]")
+    bad = ~(np.isfinite(r) & (r > 0.0))
+    if bad.any():
+        raise ValueError(e_cell(E_RDEPTH, int(np.nonzero(bad)[0][0])))
+    with np.errstate(all="ignore"):
+        code = np.where(~np.isfinite(e).all(axis=0), 1, np.where(~(e[0] == 0.0), 2, np.where(~(e[1:] > e[:-1]).all(axis=0), 3, 0)))
+    if code.any():
+        c = int(np.nonzero(code)[0][0])
+        raise ValueError(e_cell((E_EPROF_FINITE, E_EPROF_ZERO, E_EPROF_ORDER)[int(code[c]) - 1], c))
+
+
+def inundation_tables(area, params, rdepth, eprof):
+    """I0: the checked inputs' tables, a dict of float64 arrays: ACHN, VC, AF [ncells]; E, S, VB [11, ncells]; DE, M [10, ncells]; F [11]
+    (f_k).  area [ncells], params [11, ncells] as kinematic_call's (RLEN and RWIDTH are read)."""
+    check_inundation(rdepth, eprof)
+    area = np.asarray(area, dtype=np.float64).reshape(-1)
+    p = np.asarray(params, dtype=np.float64)
+    e = np.array(eprof, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        achn = p[RLEN] * p[RWIDTH]
+        vc = achn * np.asarray(rdepth, dtype=np.float64).reshape(-1)
+        af = area - achn
+        af = np.where(af > 0.0, af, 0.0)
+        f = np.arange(NPROF, dtype=np.float64) / 10.0
+        s = achn[None] + af[None] * f[:, None]
+        de = e[1:] - e[:-1]
+        m = (af * 0.1)[None] / de
+        vb = np.zeros_like(e)
+        for k in range(NPROF - 1):
+            vb[k + 1] = vb[k] + (0.5 * (s[k] + s[k + 1])) * de[k]
+    return {"ACHN": achn, "VC": vc, "AF": af, "E": e, "F": f, "S": s, "DE": de, "M": m, "VB": vb}
+
+
+def inundation_exchange(volr, wf, tab, area):
+    """I1 - I4 for every cell: volr, the main channel's storage K6 has just formed, and wf, the floodplain's, brought to one water
+    level.  Returns (volr_new, wf_new, flood_depth, flood_frac); a cell that I1 leaves untouched keeps its bits."""
+    v = np.asarray(volr, dtype=np.float64).reshape(-1)
+    wf = np.asarray(wf, dtype=np.float64).reshape(-1)
+    area = np.asarray(area, dtype=np.float64).reshape(-1)
+    vc, achn, af, e, f, s, de, m, vb = (tab[k] for k in ("VC", "ACHN", "AF", "E", "F", "S", "DE", "M", "VB"))
+    with np.errstate(all="ignore"):
+        touched = (wf > 0.0) | (v > vc)  # I1
+        w = v + wf
+        over = touched & (w > vc)  # I3, I4; touched & ~over: I2
+        x = w - vc
+        top = x >= vb[10]
+        k = np.zeros(v.size, np.int64)
+        for j in range(1, NPROF - 1):
+            k = np.where(x >= vb[j], j, k)
+
+        def at(t):
+            return np.take_along_axis(t, k[None], axis=0)[0]
+
+        r = x - at(vb)
+        sk, mk, dek = at(s), at(m), at(de)
+        d = (2.0 * r) / (sk + np.sqrt(sk * sk + (2.0 * mk) * r))
+        d = np.where(d > dek, dek, d)
+        h = np.where(top, e[10] + (x - vb[10]) / s[10], at(e) + d)
+        fr = np.where(top, 1.0, f[k] + (0.1 * d) / dek)
+        vc2 = vc + achn * h
+        vc2 = np.where(vc2 > w, w, vc2)
+        frac = np.where(area > 0.0, (af * fr) / np.where(area > 0.0, area, 1.0), 0.0)
+        v_new = np.where(over, vc2, np.where(touched, w, v))
+        wf_new = np.where(touched, _canon(np.where(over, w - vc2, 0.0)), wf)  # (an untouched WF is not stored)
+        return _canon(v_new), wf_new,_canon(np.where(over, h, 0.0)), _canon(np.where(over, frac, 0.0))
+
+
+def inundation_budget(wf):
+    """I7: the sum of WF in the device reduction's order, float64 [1]."""
+    return np.array([diagnostics.reduce_min_max_sum(wf)[2]])
 
 
 # D8 direction codes (the ESRI convention): the neighbour a cell drains into, as (row step, column step) with row 0 the northernmost

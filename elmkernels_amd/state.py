@@ -37,6 +37,8 @@ RUN_ROUTING = 256  # every step routes the step's runoff after the water balance
 ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT, ROUTE_QOUT_SUM = range(4)  # elmk_routing_read (routing.VOLR .. routing.QOUT_SUM)
 ROUTE_WH, ROUTE_WT, ROUTE_QSUR = 4, 5, 6  # ... while the kinematic-wave scheme is on (routing.WH, routing.WT, routing.QSUR)
 ROUTE_KW_NPARAM = 11  # the rows of routing_kinematic_enable's params (routing.HSLP .. routing.NR)
+ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC = 7, 8, 9  # ... while the floodplain inundation is on (routing.WF .. routing.FLOOD_FRAC)
+ROUTE_FP_NPROF = 11  # the rows of routing_inundation_enable's eprof
 WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB .. hydrology.WB_TOTSOILICE
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
@@ -589,7 +591,8 @@ class ELMState:
         self._chk(self.lib.elmk_routing(self.ctx, float(dt)), "routing")
 
     def routing_read(self, which, cell0=0, n=None):
-        """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM (with the kinematic-wave scheme on also ROUTE_WH, ROUTE_WT, ROUTE_QSUR)
+        """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM (with the kinematic-wave scheme on also ROUTE_WH, ROUTE_WT, ROUTE_QSUR,
+        with its floodplain inundation on also ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC)
         of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
         n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
         out = np.empty(max(n, 0), dtype=np.float64)
@@ -646,6 +649,36 @@ class ELMState:
     def routing_kinematic_clear(self):
         """Back to the linear scheme; VOLR, QOUT_SUM and the count stay."""
         self._chk(self.lib.elmk_routing_kinematic_clear(self.ctx), "routing_kinematic_clear")
+
+    # -- floodplain inundation (include/elmk.h: elmk_routing_inundation_enable ...; routing.inundation_exchange restates it) ---------------
+    def routing_inundation_enable(self, rdepth, eprof):
+        """Give the kinematic scheme's main channel banks and a floodplain: rdepth float64 [ncells], the bank height in metres (finite
+        and > 0), eprof float64 [ROUTE_FP_NPROF, ncells], the elevation above the bank top at which the fraction k / 10 of the
+        floodplain is wet (finite, eprof[0] == 0, strictly increasing).  Allocates the rows WF, FLOOD_DEPTH, FLOOD_FRAC (zero-filled);
+        routing_read takes ROUTE_WF, ROUTE_FLOOD_DEPTH and ROUTE_FLOOD_FRAC from here on.  Needs routing_kinematic_enable."""
+        r = np.ascontiguousarray(rdepth, dtype=np.float64).reshape(-1)
+        e = np.ascontiguousarray(eprof, dtype=np.float64)
+        n = getattr(self, "routing_ncells", r.size)
+        if r.size != n or e.shape != (ROUTE_FP_NPROF, n):
+            raise ValueError(f"routing_inundation_enable: rdepth must be [{n}] and eprof [{ROUTE_FP_NPROF}, {n}]")
+        self._chk(self.lib.elmk_routing_inundation_enable(self.ctx, _p(r), _p(e)), "routing_inundation_enable")
+
+    def routing_inundation_init(self, wf=None):
+        """WF from [ncells] (None: zeros), the two diagnostics zeros; VOLR, WH and WT stay their own entries'.  Synchronises."""
+        v = None if wf is None else np.ascontiguousarray(wf, dtype=np.float64).reshape(-1)
+        if v is not None and v.size != getattr(self, "routing_ncells", v.size):
+            raise ValueError(f"routing_inundation_init: {v.size} values for {self.routing_ncells} cells")
+        self._chk(self.lib.elmk_routing_inundation_init(self.ctx, None if v is None else _p(v)), "routing_inundation_init")
+
+    def routing_inundation_budget(self):
+        """float64 [1]: the sum of WF (routing.inundation_budget).  Synchronises."""
+        out = np.empty(1, dtype=np.float64)
+        self._chk(self.lib.elmk_routing_inundation_budget(self.ctx, _p(out)), "routing_inundation_budget")
+        return out
+
+    def routing_inundation_clear(self):
+        """Back to the channel without banks; WF is dropped, VOLR stays."""
+        self._chk(self.lib.elmk_routing_inundation_clear(self.ctx), "routing_inundation_clear")
 
     # -- water balance (include/elmk.h: elmk_water_balance_enable ...; hydrology.water_balance_begin / _end restate the stage) -----
     def water_balance_enable(self, tol_mm):

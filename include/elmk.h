@@ -1172,6 +1172,74 @@ int elmk_routing_kinematic_init(elmk_ctx *ctx, const double *wh /*[ncells] or NU
 int elmk_routing_kinematic_budget(elmk_ctx *ctx, double *sums /*[2]*/);
 int elmk_routing_kinematic_clear(elmk_ctx *ctx);
 
+/* ---- floodplain inundation ----------------------------------------------------------------------
+ * An opt-in extension of the kinematic-wave scheme above, after MOSART-Inundation (Luo et al., Geosci. Model Dev. 10, 2017): the main
+ * channel gets banks.  The channel holds RLEN * RWIDTH * RDEPTH; what exceeds that spreads over a floodplain described by an elevation
+ * profile, channel and floodplain share one water level, and only the water over the channel bed flows downstream (K4 reads the
+ * channel's share), so a flood wave is held back instead of running ever faster.  The pattern is the frost table's: a template
+ * parameter on the existing kernel (k_routing.hip: k_kinematic_step<.., FLOOD>), no run flag and no new call in the step.
+ * elmkernels_amd/routing.py: inundation_tables(), inundation_exchange() and kinematic_call(..., flood=) restate it on the host.
+ *
+ * Conventions of "kinematic-wave routing": no contraction, left-associated + - *, `/` and sqrt correctly rounded, plain IEEE
+ * comparisons, every row fp64 in both builds, a NaN stored as the canonical quiet NaN.
+ *
+ * Inputs, given once after elmk_routing_kinematic_enable: rdepth[ncells], the bank height in metres, finite and > 0; and
+ * eprof[ELMK_FP_NPROF][ncells], E_k = eprof[k][c] the elevation above the bank top at which the fraction k / 10 of the floodplain is
+ * wet: finite, E_0 == 0.0, strictly increasing in k.
+ *
+ * Rows: ELMK_ROUTE_WF (m3, the floodplain storage; the extension's only prognostic row), ELMK_ROUTE_FLOOD_DEPTH (m above the bank
+ * top) and ELMK_ROUTE_FLOOD_FRAC (the share of the cell's area under floodplain water), two diagnostics that hold the value of the
+ * call's last sub-step.  elmk_routing_read accepts the three only while the extension is on.
+ *
+ * I0. host tables, once, in this order: ACHN = RLEN * RWIDTH;  VC = ACHN * RDEPTH;  AF = area - ACHN, taken as 0.0 unless > 0.0;
+ *     f_k = (double)k / 10.0;  S_k = ACHN + AF * f_k;  DE_k = E_{k+1} - E_k;  M_k = (AF * 0.1) / DE_k;  VB_0 = 0.0;
+ *     VB_{k+1} = VB_k + (0.5 * (S_k + S_{k+1})) * DE_k.  S_k is the wet surface at level E_k (channel included), M_k its growth per
+ *     metre inside segment k, VB_k the volume over the bank top at level E_k.
+ * I1. The exchange runs per sub-step and cell after K6 has formed the new VOLR v, before that VOLR is stored and before the next
+ *     sub-step's er is formed from it.  If !(WF > 0.0 || v > VC) nothing is touched: VOLR, WH, WT, er and QOUT keep the bits of the
+ *     plain scheme, and FLOOD_DEPTH = FLOOD_FRAC = 0.0.
+ * I2. W = v + WF.  If !(W > VC): VOLR = W;  WF = 0.0;  both diagnostics 0.0.  The floodplain drains back at once; a NaN W takes
+ *     this path.
+ * I3. Otherwise X = W - VC.  If X >= VB_10: h = E_10 + (X - VB_10) / S_10 and f = 1.0.  Else with k the largest of 0 .. 9 with
+ *     X >= VB_k:  r = X - VB_k;  d = (2.0 * r) / (S_k + sqrt(S_k * S_k + (2.0 * M_k) * r));  if (d > DE_k) d = DE_k;  h = E_k + d;
+ *     f = f_k + (0.1 * d) / DE_k.  (d solves S_k d + M_k d^2 / 2 = r in the form that does not cancel.  h and f rise with W up to
+ *     their own rounding: between neighbouring doubles h may step back by an ulp, and where d reaches DE_k the sum f_k + 0.1 may lie
+ *     an ulp or two above f_{k+1}, as 0.2 + 0.1 does.)
+ * I4. vc2 = VC + ACHN * h;  if (vc2 > W) vc2 = W.  VOLR = vc2;  WF = W - vc2;  FLOOD_DEPTH = h;
+ *     FLOOD_FRAC = (area > 0.0) ? (AF * f) / area : 0.0.
+ * I5. K4 is unchanged: er is evaluated from the post-exchange VOLR, so the water column over the channel moves and the floodplain
+ *     stands still.
+ * I6. The K1 launch does no exchange: the first sub-step's er comes from VOLR as the last call or elmk_routing_init left it.
+ * I7. (elmk_routing_inundation_budget) sums[0] = the sum of WF through R6's reduction kernels.  The change of
+ *     sum WH + sum WT + sum VOLR + sum WF over a call = dt (sum QIN - sum outlet QOUT).
+ * I8. Edge values do what I1 - I4 say literally.  A NaN, zero or negative WF with v <= VC, or a NaN v with such a WF, is untouched
+ *     (I1); a NaN v with WF > 0.0, or a NaN WF with v > VC, gives W = NaN: VOLR = NaN, WF = 0.0 (I2); a negative WF with v > VC is
+ *     added like any other; W = +inf gives h = +inf, VOLR = +inf and WF = inf - inf = NaN; -inf never passes I1 or takes I2.
+ * The device keeps VC, ACHN, AF, E and VB as rows and forms S_k, DE_k and M_k again with I0's operations (the same bits); a cell that
+ * passes I1 untouched reads VC and WF and nothing else of them.
+ *
+ *   elmk_routing_inundation_enable  takes the inputs, builds I0's tables, allocates them and the three rows zero-filled (one owner,
+ *                           counted in elmk_device_bytes) and drops the captured run step.  ELMK_E_INVALID, nothing changed: the
+ *                           kinematic scheme not on; already on; a null argument; a bad value (the text names the row and the first
+ *                           offending cell, "elmk_routing_inundation_enable: EPROF not increasing at cell 17"); a stream being captured.
+ *   elmk_routing_inundation_init    WF from host[ncells] (NULL: zeros), the diagnostics zeros.  Synchronises.
+ *   elmk_routing_inundation_budget  I7; synchronises.
+ *   elmk_routing_inundation_clear   back to the channel without banks, WF dropped, VOLR kept; frees what enable allocated and drops
+ *                           the captured run step.  From then on the kinematic rows take the bits of a context that never had the
+ *                           extension, given the same VOLR.
+ * While the extension is on elmk_routing_kinematic_clear is refused with ELMK_E_INVALID ("elmk_routing_inundation_clear first");
+ * elmk_routing_clear frees everything.  elmk_routing and elmk_run with ELMK_RUN_ROUTING run the flood form while it is on.  The
+ * irrigation's river supply limit keeps reading VOLR: floodplain water is not available to irrigation.
+ * Restart: a driver saves WF with elmk_routing_read beside VOLR, WH and WT and hands it to elmk_routing_inundation_init after
+ * elmk_routing_inundation_enable; the diagnostics are rewritten by the next call.  A context that never calls these entries runs the
+ * kernels, launch sequences and graphs it ran before and allocates nothing more. */
+enum { ELMK_ROUTE_WF = 7, ELMK_ROUTE_FLOOD_DEPTH = 8, ELMK_ROUTE_FLOOD_FRAC = 9 };
+#define ELMK_FP_NPROF 11
+int elmk_routing_inundation_enable(elmk_ctx *ctx, const double *rdepth /*[ncells]*/, const double *eprof /*[ELMK_FP_NPROF][ncells]*/);
+int elmk_routing_inundation_init(elmk_ctx *ctx, const double *wf /*[ncells] or NULL: zeros*/);
+int elmk_routing_inundation_budget(elmk_ctx *ctx, double *sums /*[1]: the sum of WF, through R6's reduction kernels*/);
+int elmk_routing_inundation_clear(elmk_ctx *ctx);
+
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.
  * These two entries register one such row, over the columns (elmk_column_history_add_row; the six elmk_history_* entries of "history"

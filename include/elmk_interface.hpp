@@ -413,6 +413,15 @@ class ELMInterface {
   void routing_kinematic_init(const double* wh = nullptr, const double* wt = nullptr) { ok(elmk_routing_kinematic_init(ctx_, wh, wt)); }
   void routing_kinematic_budget(double* sums) { ok(elmk_routing_kinematic_budget(ctx_, sums)); }
   void routing_kinematic_clear() { ok(elmk_routing_kinematic_clear(ctx_)); }
+  /* Floodplain inundation (elmk.h "floodplain inundation"): banks and a floodplain for the kinematic scheme's main channel.
+   * routing_inundation_enable() takes rdepth[ncells] and eprof[ELMK_FP_NPROF][ncells] after routing_kinematic_enable; routing(dt) and
+   * run(..., routing = true) then run the flood form, and routing_read() takes ELMK_ROUTE_WF, ELMK_ROUTE_FLOOD_DEPTH and
+   * ELMK_ROUTE_FLOOD_FRAC as well.  routing_inundation_init() takes a restart's WF ([ncells], nullptr: zeros);
+   * routing_inundation_budget() fills sums[1]; routing_inundation_clear() returns to the channel without banks and keeps VOLR. */
+  void routing_inundation_enable(const double* rdepth, const double* eprof) { ok(elmk_routing_inundation_enable(ctx_, rdepth, eprof)); }
+  void routing_inundation_init(const double* wf = nullptr) { ok(elmk_routing_inundation_init(ctx_, wf)); }
+  void routing_inundation_budget(double* sums) { ok(elmk_routing_inundation_budget(ctx_, sums)); }
+  void routing_inundation_clear() { ok(elmk_routing_inundation_clear(ctx_)); }
   /* History entries over one fp64 row of a feature (elmk.h "feature rows on history tapes"): family ELMK_ROWS_*, which the family's
    * row number; as history_add / gridded_history_add otherwise, one level.  While such an entry exists the family's clear is refused. */
   int history_add_row(int tape, int family, int which, int op)
