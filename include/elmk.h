@@ -926,6 +926,9 @@ int elmk_run_water_balance(elmk_ctx *ctx, double *min_max_sum /*[nsteps][3][3]*/
  *           rate = rate + deficit / (dt * nspd); }
  *       RATE[c] = rate; } }
  * btran and eff_porosity are this step's: both elmk_timestep7 and elmk_timestep7_fused leave them in the state.
+ * The integer fields are read by C's rules: any non-zero frac_veg_nosno (-1 and 2 as well as 1) counts as vegetated and any non-zero
+ * do_capsnow as capped.  The clock is read at the step's start: a column checks in the step that starts less than idt seconds after
+ * its local 06:00:00 (since = 0 .. idt - 1), so a step of 86400 s checks every eligible column.
  *
  *   elmk_irrigation_enable  allocates the rows and sched (3 x 8 + 4 bytes x elmk_level_stride in one owner, counted in
  *                           elmk_device_bytes), the rows zero-filled; drops the captured run step.  ELMK_E_INVALID, nothing changed:

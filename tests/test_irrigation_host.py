@@ -4,7 +4,6 @@ step count by hand; the check on hand-built columns against the formula written 
 crop column stepped with hydrology.step: the water applied is the deficit measured, the root zone gets wetter, the closed budget takes
 the term.  No GPU."""
 import ctypes as C
-import math
 import os
 import re
 
@@ -18,7 +17,7 @@ from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests.hydrology_cases import CLOSURE_BOUND, column, water_mass
-from tests.irrigation_cases import CHAIN_STEPS, chain_tod, generated, smpso_of
+from tests.irrigation_cases import CHAIN_STEPS, chain_tod, generated, rate_by_hand, smpso_of
 from tests.support import ROOT, bits
 
 DT = 1800.0
@@ -142,20 +141,7 @@ def _fields(ncol, sat=0.3, **over):
     return f
 
 
-def _rate_by_hand(f, c, nlayers, dt, smpso=SMPSO):
-    """The check's formula written out, over soil layers 0 .. nlayers - 1 of column c that have roots."""
-    nspd = (14400 + (int(dt) - 1)) // int(dt)
-    rate = 0.0
-    for j in range(nlayers):
-        if not f["rootfr"][c, j] > 0.0:
-            continue
-        ep, dz = float(f["eff_porosity"][c, j]), float(f["dz"][c, 5 + j])
-        vol_liq_so = ep * math.pow(-smpso / float(f["sucsat"][c, j]), -1.0 / float(f["bsw"][c, j]))
-        liq_so = vol_liq_so * 1000.0 * dz
-        liq_sat = ep * 1000.0 * dz
-        deficit = max((liq_so + 0.7 * (liq_sat - liq_so)) - float(f["h2osoi_liq"][c, 5 + j]), 0.0)
-        rate = rate + deficit / (dt * nspd)
-    return rate
+_rate_by_hand = rate_by_hand  # (the formula written out: tests/irrigation_cases.py, shared with the edge tier's host tests)
 
 
 CASES = ("plain", "frozen_top", "frozen_layer_3", "rootless_layers", "wetter_than_target", "btran_at_threshold", "btran_just_below",
