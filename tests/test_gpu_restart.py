@@ -10,6 +10,7 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from tests import helpers as H
+from tests import restart_cases as RC
 from tests.run_cases import DT, IMAGE_CLASSES, NREC, NSTEPS, _inputs, demo_records, device, poison, schedule, stepwise, upload_series
 from tests.support import build_demo, captured, run_demo, same, state_blob
 
@@ -247,9 +248,11 @@ def test_refusals_leave_the_context_as_it_was(base):
 # ---- the feature matrix ------------------------------------------------------------------------------------------------------------
 MATRIX_N = 70  # one full wave and a partial one: the smallest shape with a tail in the piece kernel
 # the optional kinds in image order: (bit of the context's mask, section kind, sections, the words a refusal names the feature by)
-OPTIONAL = ((1, R.ACCUM_SECTION, 1, "accumulator entries"), (2, R.ALT_SECTION, 3, "active layer"), (4, R.HYDROLOGY_SECTION, 2, "soil hydrology"))
-# What the library did before the host API was split, recorded once from that build: per mask (version, image bytes, the optional
-# section kinds after the field sections), and the (image mask, context mask) pairs that load.
+OPTIONAL = ((1, R.ACCUM_SECTION, 1, "accumulator entries"), (2, R.ALT_SECTION, 3, "active layer"), (4, R.HYDROLOGY_SECTION, 2, "soil hydrology"),
+            (8, R.IRRIGATION_SECTION, 2, "irrigation"))
+NMASK = 1 << len(OPTIONAL)
+# What the library did before the host API was split, recorded once from that build, for the masks without the irrigation: per mask
+# (version, image bytes, the optional section kinds after the field sections), and the (image mask, context mask) pairs that load.
 MATRIX_IMAGES = {0: (1, 298240, ()), 1: (2, 299008, (3,)), 2: (3, 300544, (4, 4, 4)), 3: (3, 301568, (3, 4, 4, 4)),
                  4: (4, 299776, (5, 5)), 5: (4, 300544, (3, 5, 5)), 6: (4, 302336, (4, 4, 4, 5, 5)), 7: (4, 303104, (3, 4, 4, 4, 5, 5))}
 MATRIX_LOADS = {(m, m) for m in range(8)}
@@ -267,6 +270,9 @@ def _matrix_context(inputs, mask):
     if mask & 4:
         D.soil_hydrology_enable()
         D.soil_hydrology_init(np.arange(n) * 0.03 + mask, 4000.0 + np.arange(n) + mask)
+    if mask & 8:
+        D.irrigation_enable(np.arange(n, dtype=np.int32) * 1200 - 1)
+        D.irrigation_init(np.arange(n) * 0.04 + mask, np.arange(n) * 600.0 + mask)
     return D
 
 
@@ -274,7 +280,7 @@ def restart_matrix():
     """-> ({mask: (version, bytes, optional kinds)}, {(image mask, context mask) that load}, {refused pair: message}); asserts what
     holds for every library: the codec's round trip, and that a refusal is ELMK_E_INVALID and leaves t_grnd alone."""
     inputs = _inputs(MATRIX_N, 98)
-    ctx = [_matrix_context(inputs, m) for m in range(8)]
+    ctx = [_matrix_context(inputs, m) for m in range(NMASK)]
     imgs = [D.restart_save() for D in ctx]
     nfield = len(R.field_sections(imgs[0]))
     images, loads, refused = {}, set(), {}
@@ -302,17 +308,24 @@ def restart_matrix():
 
 
 def test_feature_matrix():
-    """The 8 contexts with an accumulator entry, the active layer thickness and the soil hydrology each off or on: every image has the
-    version include/elmk.h gives it and the optional sections in the order ACCUM, ALT, HYDROLOGY; restart.build reproduces it from
-    restart.parse; of the 64 loads exactly those of an image into the context of its own features succeed, and every other one
-    returns ELMK_E_INVALID, leaves the state as it was and names a feature in which image and context differ."""
+    """The 16 contexts with an accumulator entry, the active layer thickness, the soil hydrology and the irrigation each off or on: every
+    image has the version include/elmk.h gives it, the optional sections in the order ACCUM, ALT, HYDROLOGY, IRRIGATION and the bytes its
+    section table takes at 256-byte alignment; restart.build reproduces it from restart.parse; of the 256 loads exactly those of an image
+    into the context of its own features succeed, and every other one returns ELMK_E_INVALID, leaves the state as it was and names a
+    feature in which image and context differ."""
     images, loads, refused = restart_matrix()
-    for m in range(8):
+    assert sorted(images) == list(range(NMASK))
+    for m in range(NMASK):
         want_kinds = tuple(kind for bit, kind, nsec, _ in OPTIONAL if m & bit for _ in range(nsec))
-        want_version = max([1] + [ver for (bit, _, _, _), ver in zip(OPTIONAL, (2, 3, 4)) if m & bit])
-        assert MATRIX_IMAGES[m][0] == want_version and MATRIX_IMAGES[m][2] == want_kinds  # the record follows include/elmk.h
-        assert images[m] == MATRIX_IMAGES[m], m
-    assert loads == MATRIX_LOADS == {(m, m) for m in range(8)}
+        want_version = max([1] + [ver for (bit, _, _, _), ver in zip(OPTIONAL, (2, 3, 4, 5)) if m & bit])
+        want_bytes = RC.layout(MATRIX_N, accum=[1] * (m & 1), optional=[kind for bit, kind, _, _ in OPTIONAL[1:] if m & bit])[1]
+        if m in MATRIX_IMAGES:
+            assert MATRIX_IMAGES[m] == (want_version, want_bytes, want_kinds)  # the record follows include/elmk.h
+            assert images[m] == MATRIX_IMAGES[m], m
+        assert images[m] == (want_version, want_bytes, want_kinds), m
+    assert loads == {(m, m) for m in range(NMASK)}
+    assert MATRIX_LOADS == {(s, d) for s, d in loads if s < 8 and d < 8} == {(m, m) for m in range(8)}
+    assert len(loads) + len(refused) == NMASK * NMASK == 256
     for (src, dst), msg in refused.items():
         words = [w for bit, _, _, w in OPTIONAL if (src ^ dst) & bit]
         assert any(w in msg for w in words), (src, dst, msg)
