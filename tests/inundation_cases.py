@@ -1,22 +1,19 @@
-"""The inputs of the floodplain inundation's tests, host and device (include/elmk.h "floodplain inundation"): the cell map, runoff rows,
-network shapes and cell values of the kinematic-wave test (the same builders at the same sizes and seeds, kept here because no test
-module imports another), the bank heights, profiles and initial storages that put every path of I1 - I4 into every call, the census
-that shows which paths a call held, random cells of the ranges the statement was measured on, and the eight-cell chain under a storm."""
+"""The inputs of the floodplain inundation's tests, host and device (include/elmk.h "floodplain inundation"): the runoff rows, network
+shapes and cell values of the kinematic-wave test (tests/routing_kinematic_cases.py: the same builders at the same sizes and seeds) and
+its cell map with the placed cells emptied, the bank heights, profiles and initial storages that put every path of I1 - I4 into every
+call, the census that shows which paths a call held, random cells of the ranges the statement was measured on, and the eight-cell chain
+under a storm."""
 import numpy as np
 
 from elmkernels_amd import routing as rt
+from tests.routing_kinematic_cases import BASE, CASES, INF, NAN, NCOLS, SPECIAL, cell_values, networks, snwcp  # noqa: F401
 
-NCOLS = 1001
-NAN, INF = float("nan"), float("inf")
-BASE = (0.05, 0.1, 1.0e-3, 1.0e5, 10.0, 0.01, 0.05, 2.0e4, 100.0, 1.0e-3, 0.04)  # HSLP .. NR of a mid-sized cell
-SPECIAL = (0.0, -0.0, -3.5e4, 5e-324, 1e300, NAN, INF, -INF)
-CASES = ((1, 1800.0), (3, 1800.0), (8, 86400.0), (2, 1.0))  # (nsub, dt)
 NCALLS = 5
 PATHS = ("untouched", "returns") + tuple(f"segment {k}" for k in range(10)) + ("above the profile",)
 WINDOW = (192, 320)  # the cells the per-call census is taken over: the last wave of workgroup 0 and the first of workgroup 1
 
 
-# ---- the kinematic-wave test's builders ----------------------------------------------------------------------------------------------
+# ---- the kinematic-wave test's cell map, the placed cells emptied ---------------------------------------------------------------------
 def cell_map(ncells, seed):
     """A CSR map with 0 .. 5 columns per cell over NCOLS columns, weights that are no partition of one; column 5 (negative runoff) and
     column 9 (NaN runoff) are the single column of cells 3 and 6 where there are cells enough, and cell 0 of a grid of more than one
@@ -34,60 +31,6 @@ def cell_map(ncells, seed):
     if ncells >= 8:
         col[ptr[3]], col[ptr[6]] = 5, 9
     return ptr, col, rng.uniform(0.05, 1.5, col.size)
-
-
-def snwcp(call):
-    """The column values the water balance adds to the hydrology's runoff terms: column 5 far below zero, column 9 NaN."""
-    q = np.random.default_rng(700 + call).uniform(0.0, 4.0e-5, NCOLS)
-    q[5], q[9] = -1.0e-2, NAN
-    return q
-
-
-def networks(n, seed):
-    """The network shapes at n cells: name -> down (all outlets, a chain, a chain running backwards, eight cells into one, a forest
-    along a random order of the cells)."""
-    idx = np.arange(n)
-    nets = {"outlets": np.full(n, -1, np.int32), "chain": np.append(idx[1:], -1).astype(np.int32), "reverse": (idx - 1).astype(np.int32)}
-    if n >= 3:
-        t = n // 2
-        srcs = sorted({i for i in (0, 255, 256, 511, n - 4, n - 3, n - 2, n - 1) if 0 <= i < n and i != t})[:8]
-        d = np.full(n, -1, np.int32)
-        d[srcs] = t
-        nets["eight"] = d
-        rng = np.random.default_rng(seed)
-        d = np.full(n, -1, np.int32)
-        deg = np.zeros(n, np.int64)
-        perm = rng.permutation(n)
-        for i in range(n - 1):
-            if rng.random() < 0.05:
-                continue
-            j = int(perm[rng.integers(i + 1, min(i + 1 + 30, n))])
-            if deg[j] < 8:
-                d[perm[i]] = j
-                deg[j] += 1
-        nets["forest"] = d
-    return nets
-
-
-def cell_values(n, seed):
-    """ddist, area, params [11, n] and the initial VOLR, WH, WT with each edge value in a cell of its own where there are cells enough:
-    VOLR's in cells 1, 3 .. 15, WH's in 24, 26 .. 38, WT's in 41, 43 .. 55; cell 18 has no area, cells 19 and 20 a main channel of 40 m,
-    cells 21 and 22 tributaries of 5 m, and every eleventh cell a drainage density that meets the hillslope's cap."""
-    rng = np.random.default_rng(seed)
-    ddist = np.exp(rng.uniform(np.log(500.0), np.log(60000.0), n))
-    area = rng.uniform(0.5e8, 2.5e8, n)
-    p = np.array(BASE)[:, None] * np.exp(rng.uniform(np.log(0.5), np.log(2.0), (rt.NPARAM, n)))
-    p[rt.GXR, 10::11] *= 300.0
-    volr, wh, wt = rng.uniform(0.0, 1.0e6, n), rng.uniform(0.0, 5.0e6, n), rng.uniform(0.0, 1.0e6, n)
-    for i, v in enumerate(SPECIAL):
-        for row, first in ((volr, 1), (wh, 24), (wt, 41)):
-            if first + 2 * i < n:
-                row[first + 2 * i] = v
-    if n > 22:
-        area[18] = 0.0
-        p[rt.RLEN, 19:21] = 40.0
-        p[rt.TLEN, 21:23] = 5.0
-    return ddist, area, p, volr, wh, wt
 
 
 # ---- banks, profiles and storages that hold every path ----------------------------------------------------------------------------------

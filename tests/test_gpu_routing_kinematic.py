@@ -15,19 +15,16 @@ from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
 from tests.hydrology_cases import _new, clear_snow, prepare
 from tests.irrigation_cases import generated
+from tests.routing_kinematic_cases import CASES, NCOLS, cell_map, cell_values, flow_census, networks, snwcp
 from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
 
-NCOLS = 1001
 TOL = 1.0e-9
 ROWS = (rt.VOLR, rt.QIN, rt.QOUT, rt.QOUT_SUM, rt.WH, rt.WT, rt.QSUR)
 NAMES = ("VOLR", "QIN", "QOUT", "QOUT_SUM", "WH", "WT", "QSUR")
 NAN, INF = float("nan"), float("inf")
-BASE = (0.05, 0.1, 1.0e-3, 1.0e5, 10.0, 0.01, 0.05, 2.0e4, 100.0, 1.0e-3, 0.04)  # HSLP .. NR of a mid-sized cell
-SPECIAL = (0.0, -0.0, -3.5e4, 5e-324, 1e300, NAN, INF, -INF)
-CASES = ((1, 1800.0), (3, 1800.0), (8, 86400.0), (2, 1.0))  # (nsub, dt)
 
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
@@ -36,78 +33,6 @@ def base():
     b = _inputs(NCOLS, 611)
     clear_snow(b[0])
     return b, prepare(b[0], 612)
-
-
-def cell_map(ncells, seed):
-    """A CSR map with 0 .. 5 columns per cell over NCOLS columns, weights that are no partition of one; column 5 (negative runoff) and
-    column 9 (NaN runoff) are the single column of cells 3 and 6 where there are cells enough, and cell 0 of a grid of more than one
-    cell has no columns."""
-    rng = np.random.default_rng(seed)
-    cnt = rng.integers(0, 6, ncells)
-    if ncells > 1:
-        cnt[0] = 0
-    if ncells >= 8:
-        cnt[3] = cnt[6] = 1
-    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    col = rng.integers(0, NCOLS, int(ptr[-1])).astype(np.int32)
-    col[(col == 5) | (col == 9)] = 11
-    if ncells >= 8:
-        col[ptr[3]], col[ptr[6]] = 5, 9
-    return ptr, col, rng.uniform(0.05, 1.5, col.size)
-
-
-def snwcp(call):
-    """The column values the water balance adds to the hydrology's runoff terms: column 5 far below zero, column 9 NaN."""
-    q = np.random.default_rng(700 + call).uniform(0.0, 4.0e-5, NCOLS)
-    q[5], q[9] = -1.0e-2, NAN
-    return q
-
-
-def networks(n, seed):
-    """The network shapes at n cells: name -> down (all outlets, a chain, a chain running backwards, eight cells into one, a forest
-    along a random order of the cells)."""
-    idx = np.arange(n)
-    nets = {"outlets": np.full(n, -1, np.int32), "chain": np.append(idx[1:], -1).astype(np.int32), "reverse": (idx - 1).astype(np.int32)}
-    if n >= 3:
-        t = n // 2
-        srcs = sorted({i for i in (0, 255, 256, 511, n - 4, n - 3, n - 2, n - 1) if 0 <= i < n and i != t})[:8]
-        d = np.full(n, -1, np.int32)
-        d[srcs] = t
-        nets["eight"] = d
-        rng = np.random.default_rng(seed)
-        d = np.full(n, -1, np.int32)
-        deg = np.zeros(n, np.int64)
-        perm = rng.permutation(n)
-        for i in range(n - 1):
-            if rng.random() < 0.05:
-                continue
-            j = int(perm[rng.integers(i + 1, min(i + 1 + 30, n))])
-            if deg[j] < 8:
-                d[perm[i]] = j
-                deg[j] += 1
-        nets["forest"] = d
-    return nets
-
-
-def cell_values(n, seed):
-    """ddist, area, params [11, n] and the initial VOLR, WH, WT with each edge value in a cell of its own where there are cells enough:
-    VOLR's in cells 1, 3 .. 15, WH's in 24, 26 .. 38, WT's in 41, 43 .. 55; cell 18 has no area, cells 19 and 20 a main channel of 40 m,
-    cells 21 and 22 tributaries of 5 m, and every eleventh cell a drainage density that meets the hillslope's cap."""
-    rng = np.random.default_rng(seed)
-    ddist = np.exp(rng.uniform(np.log(500.0), np.log(60000.0), n))
-    area = rng.uniform(0.5e8, 2.5e8, n)
-    p = np.array(BASE)[:, None] * np.exp(rng.uniform(np.log(0.5), np.log(2.0), (rt.NPARAM, n)))
-    p[rt.GXR, 10::11] *= 300.0
-    volr, wh, wt = rng.uniform(0.0, 1.0e6, n), rng.uniform(0.0, 5.0e6, n), rng.uniform(0.0, 1.0e6, n)
-    for i, v in enumerate(SPECIAL):
-        for row, first in ((volr, 1), (wh, 24), (wt, 41)):
-            if first + 2 * i < n:
-                row[first + 2 * i] = v
-    if n > 22:
-        area[18] = 0.0
-        p[rt.RLEN, 19:21] = 40.0
-        p[rt.TLEN, 21:23] = 5.0
-    return ddist, area, p, volr, wh, wt
 
 
 def _ctx(base, lib_path, ncells, seed=3):
@@ -137,19 +62,6 @@ def read_rows(D, rows=ROWS):
 def host_inputs(D, qrunoff, area):
     ptr, col, w = D._map
     return rt.qin_from_rows(ptr, col, w, qrunoff, area), rt.qsur_from_rows(ptr, col, w, D._surf[0], D._surf[1], area)
-
-
-def flow_census(seen, wh, wt, v, area, p, dts):
-    """Which of {capped, uncapped} x {hillslope, tributaries, main channel} the storages of a sub-step's start meet."""
-    ch, ct, cr = rt.kinematic_params(p)
-    with np.errstate(all="ignore"):
-        for name, f, s in (("eh", rt.hillslope_flow(wh, area, ch, dts), wh), ("et", rt.channel_flow(wt, p[rt.TLEN], p[rt.TWIDTH], ct, dts), wt),
-                           ("er", rt.channel_flow(v, p[rt.RLEN], p[rt.RWIDTH], cr, dts), v)):
-            pos = np.isfinite(s) & (s > 0.0) & (f > 0.0)
-            if (pos & (f == s / dts)).any():
-                seen.add((name, "capped"))
-            if (pos & (f < s / dts)).any():
-                seen.add((name, "uncapped"))
 
 
 # ---- 1. the stage against the restatement -------------------------------------------------------------------------------------------

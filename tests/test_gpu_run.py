@@ -197,7 +197,8 @@ def test_the_captured_step_follows_every_part_of_its_key():
     flags), the shortwave mode, the downscaling mode without and with groups, and back.  After every run every field, the diagnostics
     rows, every history and accumulator read and the rows of the active layer and the soil hydrology are bit-equal: a graph kept past
     a change of its key would hold the stages, kernels or tables of the moment it was captured.  (The land unit under
-    ELMK_RUN_HYDROLOGY: test_gpu_hydrology.test_the_captured_run_step_follows_the_land_unit.)"""
+    ELMK_RUN_HYDROLOGY: test_gpu_hydrology.test_the_captured_run_step_follows_the_land_unit.  The three newer flags and the rest of
+    the key, with every stage on: test_gpu_full_step.py.)"""
     from elmkernels_amd import hydrology as hy
     from elmkernels_amd import regrid as RG
 
@@ -267,7 +268,7 @@ def test_the_captured_step_follows_every_part_of_its_key():
         ("groups cleared", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, lambda D: D.clear_downscaling_groups()),
         ("downscaling off", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, lambda D: D.set_downscaling("off")),
         ("shortwave REFERENCE", F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_ALT, lambda D: D.set_shortwave_mode("reference")),
-        ("every flag", F.RUN_QBOT_IS_RH | F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_AEROSOL | F.RUN_ALT | F.RUN_HYDROLOGY, None),
+        ("the six older flags", F.RUN_QBOT_IS_RH | F.RUN_HISTORY | F.RUN_ACCUM | F.RUN_AEROSOL | F.RUN_ALT | F.RUN_HYDROLOGY, None),
         ("flags back to 0 again", 0, None),
     ]
     sch = schedule()
