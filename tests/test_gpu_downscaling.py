@@ -1,18 +1,21 @@
 """Downscaling of coarse-grid forcing to column elevation on the device (include/elmk.h "downscaling"): equal elevations give the
 bits of OFF, elmk_get_forcing in TOPO mode against elmkernels_amd/downscale.py (with the reference's own qsat), elmk_run against the
 stepwise calls (per-column series and a forcing grid, graph on and off), the physical properties of the adjusted fields, the snow a
-mountain column keeps, the refusals, an exact restart and the demo."""
+mountain column keeps, the refusals, an exact restart and the demo; and the longwave renormalisation on its own (k_ds_lw_norm) on
+every group shape of tests/output_map_cases.py, in both builds."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from elmkernels_amd import _lib as L
 from elmkernels_amd import downscale as DSC
 from elmkernels_amd import regrid as RG
 from elmkernels_amd import state as st
 from tests import helpers as H
+from tests import output_map_cases as OM
 from tests import run_cases as GR
-from tests.support import build_demo, captured, run_demo, same, state_blob
+from tests.support import build_demo, captured, run_demo, same, same_nan, state_blob
 
 pytestmark = pytest.mark.gpu
 
@@ -257,6 +260,115 @@ def test_physical_properties(base):
     assert (np.abs(mean_c - mean_g) <= 1e-13 * mean_g).all()
     free = np.setdiff1d(np.arange(n), col)
     assert free.size == 19 and same(lcn[free], lc[free])  # columns of no group are not renormalised
+    D.close()
+
+
+F32_GROUP_SHAPES = (("tiles", 33), ("big_last", 17), ("tile_start", 33), ("all_empty", 33))
+GROUP_SHAPES = ([(n, layout, None) for layout in OM.LAYOUTS for n in OM.GROUP_NCELLS]
+                + [(n, layout, L.F32_LIB_PATH) for layout, n in F32_GROUP_SHAPES])
+
+
+@pytest.mark.parametrize("ncells,layout,lib_path", GROUP_SHAPES, ids=lambda v: "f32" if v == L.F32_LIB_PATH else "f64" if v is None else None)
+def test_group_renormalisation_on_every_group_shape(ncells, layout, lib_path):
+    """k_ds_lw_norm on its own, at the shapes its two walks and its search can go wrong at (output_map_cases.shape_map with 16
+    groups per workgroup, every column in at most one group): 1, 15, 16, 17 and 33 groups; a workgroup span of exactly one tile and
+    of one tile and a column, a group of more than two tiles, a workgroup without a column, groups that start exactly at a tile's
+    start, no column at all; an empty group, a
+    one-column group, a group whose weights are all 0.0 (W == 0), a group led by a NaN Lg, a NaN in a column of no group.  OFF gives
+    Lg, TOPO without groups gives the Lc the kernel reads, TOPO with groups must give downscale.renormalise_longwave(Lg, Lc) bit
+    for bit.  In libelmk_f32.so Lg is the widened record itself (weights 1 and 0, no computed column) and the result is the fp64
+    product rounded once to fp32.  No qsat is needed: every other field is compared with the TOPO call before the groups."""
+    f32 = lib_path is not None
+    cnt = OM.cell_counts(ncells, 61, layout, OM.DS_CELLS)[0]
+    n1 = int((cnt == 1).sum())
+    # column 0 leads the first group of two or more columns that shape_map gives away (columns 1 .. n1 lead the one-column groups)
+    lead = tuple(range(1, n1 + 1)) + (0,) if OM.edge_columns(ncells, layout)[0] else ()
+    ptr, col, w, ncols = OM.shape_map(ncells, 61, layout, cells_per_wg=OM.DS_CELLS, disjoint=True, lead=lead)
+    assert (np.diff(ptr) == cnt).all()
+    nan_lead = lead[-1:]
+    cols, scal, soil, lat, lon, rec = GR._inputs(ncols, 62, nrec=2)
+    hc, hf = _elevations(ncols, 63)
+    rng = np.random.default_rng(64)
+    flds = rng.uniform(60.0, 590.0, (2, ncols))
+    computed = np.zeros(ncols, bool)
+    if f32:
+        flds = flds.astype(np.float32).astype(np.float64)
+    else:  # every 13th column: both records outside [50, 600], so the interpolated one is too and lwrad is computed
+        computed[::13] = True
+        flds[:, computed] = np.where(np.arange(computed.sum()) % 2 == 0, 30.0, 700.0)
+    free = np.setdiff1d(np.arange(ncols), col)
+    nan_cols = [int(free[0])] + list(nan_lead)
+    flds[0, nan_cols] = np.nan
+    D = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=lib_path)
+    D.set_column_elevation(hc, hf)
+    for k in st.SERIES_FORCING:
+        D.upload(k, np.stack([rec[k][0], rec[k][1]], axis=1))
+    D.upload("atm_flds", np.stack([flds[0], flds[1]], axis=1))
+    D.solar_geometry(DT, 172.3, 171)
+    wt2 = rng.random(8)
+    if f32:
+        wt2[3] = 0.0
+    wt1 = 1.0 - wt2
+    # 1. OFF: Lg
+    st.get_forcing(D, wt1, wt2, False)
+    lg = _col(D, "forc_lwrad")
+    if f32:
+        assert wt1[3] == 1.0 and same_nan(lg, flds[0].astype(np.float32).astype(np.float64))
+        lg = flds[0].copy()  # exact: 1.0 * record 0 + 0.0 * record 1; the device keeps it in fp64, the download rounds it
+    else:
+        interp = flds[0] * wt1[3] + flds[1] * wt2[3]
+        assert ((interp[computed] <= 50.0) | (interp[computed] >= 600.0) | np.isnan(interp[computed])).all()
+        plain = ~computed & ~np.isnan(interp)
+        assert same(lg[plain], interp[plain]) and (lg[computed & ~np.isnan(interp)] != interp[computed & ~np.isnan(interp)]).all()
+    assert np.isnan(lg[nan_cols]).all() and np.isnan(lg).sum() == len(nan_cols)
+    # 2. TOPO without groups: the Lc the kernel reads
+    D.set_downscaling("topo")
+    st.get_forcing(D, wt1, wt2, False)
+    before = _forcing(D)
+    lc = before["forc_lwrad"].reshape(-1).copy()
+    assert (np.isnan(lc) == np.isnan(lg)).all() and (lc[hc != hf] != lg[hc != hf])[~np.isnan(lg[hc != hf])].any()
+    # 3. with the groups
+    D.set_downscaling_groups(ptr, col, w)
+    st.get_forcing(D, wt1, wt2, False)
+    got = _forcing(D)
+    out = got["forc_lwrad"].reshape(-1)
+    with np.errstate(all="ignore"):
+        norm = DSC.group_norm(lg, lc, ptr, col, w)
+        if f32:
+            want = lc.copy()
+            want[col] = (lc[col] * np.repeat(norm, cnt)).astype(np.float32).astype(np.float64)
+        else:
+            want = DSC.renormalise_longwave(lg, lc, ptr, col, w)
+    bad = np.nonzero(~((out.view(np.uint64) == want.view(np.uint64)) | (np.isnan(out) & np.isnan(want))))[0]
+    group_of = np.full(ncols, -1, np.int64)
+    group_of[col] = np.repeat(np.arange(ncells), cnt)
+    assert not bad.size, (bad[:5].tolist(), group_of[bad[:5]].tolist(), out[bad[:5]].tolist(), want[bad[:5]].tolist(), norm[group_of[bad[:5]]].tolist())
+    # by value
+    assert same(out[free], lc[free]) and free.size >= 3  # a column of no group keeps its bits, the NaN among them
+    W = RG.apply_aggregate(ptr, col, w, np.ones(ncols), 0.0)
+    zero, _, own = OM.special_cells(cnt)
+    unit = np.isin(group_of, np.nonzero(W == 0.0)[0])  # W == 0: the norm is exactly 1
+    assert same(out[unit], lc[unit])
+    if layout == "all_empty":
+        assert same(out, lc) and not col.size
+    else:
+        live = (W > 0.0) & ~np.isnan(norm)
+        assert live.any() and (norm[live] != 1.0).any() and (out[col] != lc[col]).any()
+    if zero is not None:
+        assert W[zero] == 0.0 and cnt[zero] >= 2 and unit[col[ptr[zero]]]
+    new_nan = np.isnan(out) & ~np.isnan(lc)
+    if nan_lead:
+        g = own[n1]
+        assert group_of[0] == g and cnt[g] >= 2 and np.isnan(norm[g]) and np.isnan(out[col[ptr[g]:ptr[g + 1]]]).all()
+        assert (group_of[new_nan] == g).all() and new_nan.sum() == cnt[g] - 1  # no other group took a NaN
+    else:
+        assert not new_nan.any()
+    for k in DS_FIELDS + KEPT_FIELDS:
+        if k != "forc_lwrad":
+            assert same(got[k], before[k]), k
+    # once more: the same bits (forc_lwrad is rewritten by the forcing kernel first, so the norm does not compound)
+    st.get_forcing(D, wt1, wt2, False)
+    assert same(D["forc_lwrad"], got["forc_lwrad"])
     D.close()
 
 

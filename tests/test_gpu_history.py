@@ -1,6 +1,7 @@
 """History accumulation on the device (elmk_history_*, k_history.hip): every entry against numpy applying the rules of include/elmk.h
 ("history") to elmk_download results taken after every step, bit for bit; the physics unchanged by accumulating; a caller's graph;
-the refusals; libelmk_f32.so; the example."""
+the refusals; libelmk_f32.so; the example; the ends of a column pair and of a workgroup (1 .. 1025 columns, every stored type, U32
+among them, both builds) and every edge value under every op."""
 import numpy as np
 import pytest
 
@@ -118,6 +119,105 @@ def test_nan_sticks_and_signed_zero_survives():
     s = D.history_read(z)
     assert (s == 0.0).all() and np.signbit(s).all()  # -0.0 + -0.0 ... = -0.0
     assert (D.history_read(zmax) == 0.0).all()
+    D.close()
+
+
+OPS = ("avg", "sum", "max", "min", "inst")
+# every op on every stored type: F64 with one level and with 20, I32, U8 and U32 (err_flags), over three tapes
+END_ENTRIES = [(k % 3, f, op) for k, (f, op) in
+               enumerate((f, op) for f in ("t_grnd", "t_soisno", "snl", "veg_active", "err_flags") for op in OPS)]
+
+
+@pytest.mark.parametrize("ncols,lib_path", [(n, None) for n in (1, 2, 3, 511, 512, 513, 1025)] + [(n, L.F32_LIB_PATH) for n in (1, 513, 1025)],
+                         ids=lambda v: "f32" if v == L.F32_LIB_PATH else "f64" if v is None else None)
+def test_pair_and_workgroup_ends(ncols, lib_path):
+    """k_hist_accumulate takes two columns per thread and 512 per workgroup: one column (half a pair), a pair, a pair and a half, a
+    workgroup less one column, a workgroup, a workgroup and one column, two and one.  Three accumulates of directly uploaded values
+    against numpy's fold of the downloads, whole and for the last column alone; in both builds at 1, 513 and 1025."""
+    D = st.ELMState(ncols, lib_path=lib_path)
+    ids = [D.history_add(*e) for e in END_ENTRIES]
+    ref = NumpyTapes(END_ENTRIES)
+    names = sorted({f for _, f, _ in END_ENTRIES})
+    rng = np.random.default_rng(40 + ncols)
+    for _ in range(3):
+        D["t_grnd"] = rng.standard_normal(ncols) * 300.0
+        D["t_soisno"] = rng.standard_normal((ncols, D.fields["t_soisno"][1])) * 300.0
+        D["snl"] = rng.integers(0, 6, ncols).astype(np.int32)
+        D["veg_active"] = rng.integers(0, 256, ncols).astype(np.uint8)
+        flags = rng.integers(0, 1 << 32, ncols, dtype=np.uint64).astype(np.uint32)
+        flags[-1] |= np.uint32(1 << 31)  # (the last column, the one read alone: above 2^31)
+        D["err_flags"] = flags
+        assert same(D["err_flags"], flags)
+        D.history_accumulate()
+        ref.fold({k: D[k] for k in names})
+    for k, e in enumerate(ids):
+        want = ref.result(k)
+        assert same_nan(D.history_read(e), want), (ncols, END_ENTRIES[k])
+        assert same_nan(D.history_read(e, col0=ncols - 1, n=1), want[ncols - 1:]), (ncols, END_ENTRIES[k], "the last column")
+        if want.ndim == 2:
+            assert same_nan(D.history_read(e, col0=ncols - 1, n=1, layout=st.LAYOUT_SOA), want[ncols - 1:].T), (ncols, END_ENTRIES[k])
+    assert [D.history_count(t) for t in range(3)] == [3, 3, 3]
+    u = D.history_read(ids[[(f, op) for _, f, op in END_ENTRIES].index(("err_flags", "max"))])
+    assert u[-1] >= 2.0 ** 31  # widened as unsigned
+    D.close()
+
+
+NAN, INF, BIG = float("nan"), float("inf"), 1.7976931348623157e308
+# three samples per class of column (column c is of class c % 10); class 9 holds ordinary numbers
+EDGE_SAMPLES = ((INF, -INF, 1.0),  # 0: SUM and AVG meet +inf then -inf: NaN from then on
+                (1e300, 1e300, 1e300),  # 1: 1e300 + 1e300 is 2e300 in fp64 (the largest fp64 is 1.8e308) ...
+                (BIG, BIG, -1.0),  # 2: ... the sum that overflows: +inf, and stays
+                (-INF, -INF, -INF),  # 3: MAX's initial value as a sample leaves it; MIN takes it
+                (INF, INF, INF),  # 4: the mirror
+                (-0.0, 0.0, -0.0),  # 5: MAX and MIN keep the first zero ...
+                (0.0, -0.0, 0.0),  # 6: ... in either order
+                (NAN, 2.5, -3.0),  # 7: a NaN sticks to SUM, AVG, MAX and MIN; INST takes the number after it
+                (5e-324, 5e-324, 5e-324))  # 8: subnormal sums are exact
+
+
+def test_edge_values_by_op():
+    """1000 columns, every edge value in columns of its own, three samples ordered as EDGE_SAMPLES says; against numpy's fold and,
+    for the cases named there, by value."""
+    n = 1000
+    D = st.ELMState(n)
+    entries = [(0, "t_grnd", op) for op in OPS]
+    ids = [D.history_add(*e) for e in entries]
+    ref = NumpyTapes(entries)
+    cls = np.arange(n) % 10
+    rng = np.random.default_rng(45)
+    for k in range(3):
+        v = rng.standard_normal(n) * 300.0
+        for c, samples in enumerate(EDGE_SAMPLES):
+            v[cls == c] = samples[k]
+        D["t_grnd"] = v
+        assert same_nan(D["t_grnd"], v)
+        D.history_accumulate()
+        with np.errstate(all="ignore"):
+            ref.fold({"t_grnd": D["t_grnd"]})
+    got = {}
+    for k, e in enumerate(ids):
+        got[OPS[k]] = D.history_read(e)
+        assert same_nan(got[OPS[k]], ref.result(k)), OPS[k]
+
+    def of(op, c):
+        return got[op][cls == c]
+
+    def all_bits(a, v):
+        return same(a, np.full(a.shape, v))
+
+    assert np.isnan(of("sum", 0)).all() and np.isnan(of("avg", 0)).all() and all_bits(of("max", 0), INF) and all_bits(of("min", 0), -INF)
+    assert all_bits(of("sum", 1), 1e300 + 1e300 + 1e300) and np.isfinite(of("avg", 1)).all()
+    assert all_bits(of("sum", 2), INF) and all_bits(of("avg", 2), INF) and all_bits(of("max", 2), BIG) and all_bits(of("min", 2), -1.0)
+    assert all_bits(of("max", 3), -INF) and all_bits(of("min", 3), -INF) and all_bits(of("sum", 3), -INF)
+    assert all_bits(of("max", 4), INF) and all_bits(of("min", 4), INF) and all_bits(of("inst", 4), INF)
+    assert all_bits(of("max", 5), -0.0) and all_bits(of("min", 5), -0.0)  # the first zero stays
+    assert all_bits(of("max", 6), 0.0) and all_bits(of("min", 6), 0.0)
+    assert all_bits(of("sum", 5), 0.0) and all_bits(of("sum", 6), 0.0)  # -0.0 + -0.0 + +0.0 ... = +0.0
+    for op in ("sum", "avg", "max", "min"):
+        assert np.isnan(of(op, 7)).all(), op
+    assert all_bits(of("inst", 7), -3.0)  # not sticky
+    assert all_bits(of("sum", 8), 1.5e-323) and all_bits(of("avg", 8), 5e-324) and all_bits(of("max", 8), 5e-324)
+    assert np.isfinite(np.stack([got[op][cls == 9] for op in OPS])).all()
     D.close()
 
 

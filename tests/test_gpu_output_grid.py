@@ -11,6 +11,7 @@ from elmkernels_amd import regrid as RG
 from elmkernels_amd import state as st
 from tests import helpers as H
 from tests import run_cases as GR
+from tests.output_map_cases import CellTapes, host_aggregate
 from tests.support import build_demo, captured, run_demo, same_nan, state_blob
 
 pytestmark = pytest.mark.gpu
@@ -23,13 +24,6 @@ FIELDS = ["t_grnd", "eflx_sh_tot", "t_soisno", "snl", "veg_active", "err_flags"]
 
 def _levels(D, name):
     return D.fields[name][1]
-
-
-def host_aggregate(D, name, ptr, col, w, fill=FILL):
-    """The reference: the field downloaded, widened to fp64, every level aggregated on the host.  [ncells] or [ncells, nlev]."""
-    x = D.download(name, layout=st.LAYOUT_SOA).astype(np.float64)
-    g = RG.apply_aggregate(ptr, col, w, x, fill)
-    return g if g.ndim == 1 else np.ascontiguousarray(g.T)
 
 
 def owner(ncols, ncells, seed, shuffled=False, big=0):
@@ -130,18 +124,6 @@ GRIDDED = [(0, "t_grnd", "avg"), (0, "t_soisno", "avg"), (0, "snl", "avg"), (1, 
            (1, "veg_active", "sum"), (2, "eflx_sh_tot", "sum"), (2, "snl", "inst"), (3, "t_grnd", "min"), (3, "eflx_sh_tot", "avg"),
            (3, "h2osoi_liq", "max"), (3, "qflx_evap_tot", "inst")]
 COLUMN = [(0, "t_grnd", "avg"), (1, "h2osoi_liq", "max"), (2, "snl", "inst"), (2, "eflx_sh_tot", "sum")]
-
-
-class CellTapes(GR.NumpyTapes):
-    """The host fold of the per-step aggregates; a cell without terms reads fill under every op."""
-
-    def __init__(self, entries, empty):
-        super().__init__(entries)
-        self.empty = empty
-
-    def result(self, k):
-        r = super().result(k)
-        return np.where(self.empty if r.ndim == 1 else self.empty[:, None], FILL, r)
 
 
 def _add(D, gridded, column):
