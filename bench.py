@@ -2,7 +2,7 @@
 """bench.py - gridcell-timesteps/sec of the full water+energy timestep (all 7 kernels) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cols C] [--tier A|B] [--workload timestep7|soil_temperature] [--fused]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  `python bench.py --gpus N` without a launcher starts the N rank processes itself (the parent never
@@ -20,10 +20,15 @@ frac_wet -> albedo_snicar -> canopy_hydrology -> surface_radiation -> canopy_tem
 -> canopy_fluxes, each a hand-written HIP kernel over SoA state in HBM (--fused: the same step through
 elmk_timestep7_fused, one streaming stage for the wrappers between albedo and the leaf-temperature iteration).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP-event
-timed on the launch stream), `cpu_baseline` (the C oracle and, where oracle/_ref was built, the reference's own headers,
-both with OpenMP on the host cores, bounded sample) and, at N = 1 on the default workload, `north_star_10M` (the same
-step at the north-star size, 10 M columns, both synthetic tiers).
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and no more: it builds the state, runs the W
+warm-up and the K timed steps, writes --dump-outputs, and prints `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` and the configuration.  --full runs the same steps first and then everything else the benchmark measures,
+each in runs of its own after the timed region: the kernels' error flags, `kernels` and `roofline` (per launch group and
+dominant kernel, HIP-event timed on the launch stream), `step_time`, the empirical copy rates, `cpu_baseline` (the C
+oracle and, where oracle/_ref was built, the reference's own headers, both with OpenMP on the host cores, bounded
+sample) and, at N = 1 on the default workload, the other tier, the fused and the advance step, `north_star_10M` (the
+same step at the north-star size, 10 M columns, both synthetic tiers), the soil solve at that size, the two-block
+pipeline and the fp32-state variant.
 """
 import argparse
 import hashlib
@@ -499,7 +504,7 @@ def fp32_state_variant(device_index, seed, st, compact=False):
     if not os.path.exists(L.F32_LIB_PATH):
         return {"error": "libelmk_f32.so not built"}
     out = {"what": "fused step, fp32-stored state (fp64 arithmetic), libelmk_f32.so; report only", "bytes_per_column_step": ALGO_BYTES_FUSED_F32}
-    # compact (the default run, so that the driver's command times BASELINE config 5 at its own size): 10 M columns only and a
+    # compact (the --full run without --state-f32, so that the driver's command times BASELINE config 5 at its own size): 10 M columns only and a
     # 50 000-column pair for the error percentiles; --state-f32 adds 1 M columns, a 200 000-column pair and the register table
     for cols_n, key in (((NORTH_STAR_COLS, "10M"),) if compact else ((1_000_000, "1M"), (NORTH_STAR_COLS, "10M"))):
         for tier in ("A", "B"):
@@ -629,8 +634,7 @@ def spawn_ranks(ngpus, argv, timeout_s=None, poll_s=0.2):
     return 1
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -644,28 +648,40 @@ def main(argv=None):
     ap.add_argument("--fused", action="store_true",
                     help="the step through elmk_timestep7_fused (BASELINE config 5's launch structure, fp64 state): "
                          "roofline against the 3 405 B/column-step fused bound")
-    ap.add_argument("--no-other-tier", action="store_true", help="skip the secondary measurement on the other tier")
-    ap.add_argument("--no-north-star", action="store_true", help="skip the 10 M-column measurement (north_star_10M)")
+    ap.add_argument("--no-other-tier", action="store_true", help="--full: skip the secondary measurement on the other tier")
+    ap.add_argument("--no-north-star", action="store_true", help="--full: skip the 10 M-column measurement (north_star_10M)")
     ap.add_argument("--seed", type=int, default=0x5EEDE1A0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (cpu_baseline); in any run, leave the OpenMP thread placement it sets alone")
     ap.add_argument("--graph", action="store_true",
                     help="replay the seven wrappers as one captured HIP graph (elmk_set_graph): removes host launch latency, "
                          "which dominates below ~100k columns")
-    ap.add_argument("--profile-steps", type=int, default=5, help="steps of the per-kernel HIP-event profile")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: steps of the per-kernel HIP-event profile")
     ap.add_argument("--one-gpu-value", type=float, default=None,
                     help="the 1-GPU `value` of the same configuration: with it the line carries scaling_efficiency = value / (N * that)")
-    ap.add_argument("--no-soil-10m", action="store_true", help="skip the soil-column solve at 10 M columns (soil_temperature_10M)")
-    ap.add_argument("--no-two-blocks", action="store_true", help="skip the two-block pipeline measurement (two_block_pipeline)")
-    ap.add_argument("--no-state-f32", action="store_true", help="skip the compact fp32-state measurement of the default run (fp32_state_10M)")
+    ap.add_argument("--no-soil-10m", action="store_true", help="--full: skip the soil-column solve at 10 M columns (soil_temperature_10M)")
+    ap.add_argument("--no-two-blocks", action="store_true", help="--full: skip the two-block pipeline measurement (two_block_pipeline)")
+    ap.add_argument("--no-state-f32", action="store_true", help="skip the compact fp32-state measurement of the --full run (fp32_state_10M)")
     ap.add_argument("--state-f32", action="store_true",
-                    help="also measure BASELINE config 5's fp32-state variant (libelmk_f32.so: fp64 fields stored as fp32, fp64 arithmetic, "
+                    help="--full: also measure BASELINE config 5's fp32-state variant (libelmk_f32.so: fp64 fields stored as fp32, fp64 arithmetic, "
                          "fused step) as a separate object fp32_state_10M - reported beside the fp64 numbers, never as `value`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the state they left (every field at a fixed sample of rank 0's columns, "
                          "float64) as DIR/<field>.npy, for comparing the outputs of two builds")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else: error flags, per-kernel times and roofline, "
+                         "step_time, copy rates, the other tier, the fused and advance steps, 10 M columns, the two-block pipeline, the "
+                         "fp32 state, the CPU baseline (the --no-* options drop single parts of it)")
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.state_f32 and not args.full:
+        ap.error("--state-f32 is a part of the --full run")
+    return args
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = parse_args(argv)
 
     if "RANK" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, argv)
@@ -678,7 +694,9 @@ def main(argv=None):
     if world == 1 and not args.no_cpu_baseline:
         # the CPU-baseline leg: OpenMP threads bound to neighbouring cores and sleeping between parallel regions instead of
         # spinning on a shared host.  libgomp reads these once, when it is loaded (import torch loads it), hence here.  Not at
-        # N > 1: binding would pin every rank's launching thread to the first core of the same mask.
+        # N > 1: binding would pin every rank's launching thread to the first core of the same mask.  A plain run has no such
+        # leg and sets them all the same: the thread that launches the timed steps is then placed as it is under --full, and
+        # the two runs time the same thing.
         os.environ.setdefault("OMP_PROC_BIND", "close")
         os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 
@@ -741,9 +759,10 @@ def main(argv=None):
         return D, host_state
 
     dumped = None
+    full = args.full
 
     def measure(D, steps, warmup, with_dist, fused=None, dump=False):
-        """-> (seconds of the timed region, per-launch-group ms, ms of the whole step by HIP events)."""
+        """-> (seconds of the timed region, and with --full: per-launch-group ms, ms of the whole step by HIP events)."""
         nonlocal dumped
         fused = args.fused if fused is None else fused
         def sync_all():
@@ -756,7 +775,7 @@ def main(argv=None):
         el = timed_steps(D, args.workload, steps, warmup, sync_all, dist if with_dist else None, torch, red_device, fused)
         if dump:  # before the profiling steps below advance the state further
             dumped = dump_outputs(D, args.dump_outputs)
-        if rehearsal is not None:
+        if rehearsal is not None or not full:
             return el, [], 0.0
         if soil:
             return el, [], event_time_soil(D, max(1, args.profile_steps))
@@ -783,18 +802,20 @@ def main(argv=None):
         return {"ms_per_step_events": round(ms, 4), "value": n / (ms * 1e-3)}
 
     D, host_state = prepared(args.tier)
-    # population of the predicate-gated wrappers ("active-bytes" variant of the roofline numerator)
-    veg_frac = float((D["frac_veg_nosno"] != 0).mean())
-    sun_frac = float((D["coszen"] > 0).mean())
+    veg_frac = sun_frac = None
+    if full:
+        # population of the predicate-gated wrappers ("active-bytes" variant of the roofline numerator)
+        veg_frac = float((D["frac_veg_nosno"] != 0).mean())
+        sun_frac = float((D["coszen"] > 0).mean())
     if args.graph and not soil and rehearsal is None:
         D.set_graph(True)
     elapsed, ms, ms_total = measure(D, args.steps, args.warmup, True,
                                     dump=args.dump_outputs is not None and rank == 0 and rehearsal is None)
-    flags, first_bad = D.error_summary()
+    flags = D.error_summary()[0] if full else None
     state_gb = round(D.device_bytes / 1e9, 3)
     step_time = None
     empirical = None
-    if rehearsal is None and rank == 0:
+    if full and rehearsal is None and rank == 0:
         if not soil:
             # device time of every step (HIP events around each, same restores): SURVEY 8(d) asks for the median
             each = sorted(D.profile_steps(1800.0, max(3, args.steps), fused=args.fused))
@@ -808,7 +829,7 @@ def main(argv=None):
                                                 "8B_per_lane_x4_loads": round(shapes[2], 1), "16B_per_lane_x4_loads": round(shapes[3], 1)},
                          "peak_GBps": round(max(shapes[k] for k in range(4)), 1), "many_stream_GBps": round(shapes[4], 1)}
     names = [] if rehearsal is not None else (st.KERNEL_NAMES_FUSED if args.fused else st.KERNEL_NAMES)
-    also_fused = rank == 0 and world == 1 and rehearsal is None and not args.fused and not (args.workload == "soil_temperature")
+    also_fused = full and rank == 0 and world == 1 and rehearsal is None and not args.fused and not (args.workload == "soil_temperature")
     fused_step = None
     advance_step = None
     if also_fused:
@@ -819,7 +840,7 @@ def main(argv=None):
 
     other = None
     north = None
-    solo = rank == 0 and world == 1 and rehearsal is None
+    solo = full and rank == 0 and world == 1 and rehearsal is None
     if solo and not args.no_other_tier:
         D.close()
         D = None
@@ -931,7 +952,7 @@ def main(argv=None):
             D = None
         f32 = fp32_state_variant(device_index, args.seed, st, compact=not args.state_f32)
         if "error" in f32 and not args.state_f32:
-            f32 = None  # (libelmk_f32.so not built: the default run simply has no config-5 object)
+            f32 = None  # (libelmk_f32.so not built: the --full run simply has no config-5 object)
 
     if rank == 0:
         value = ncols_global * args.steps / elapsed
@@ -962,11 +983,19 @@ def main(argv=None):
             out["config"] = {"workload": "CPU rehearsal of the multi-rank control flow (tests only)", "columns_per_gpu": args.cols,
                              "columns_total": ncols_global, "parallelism": par}
         elif soil:
-            gbs = SOIL_ALGO_BYTES * ncols / (ms_total * 1e-3) / 1e9
             out["config"] = {
                 "workload": f"soil-column vertical solve (kokkos_soil_temperature: 21-row pentadiagonal system, phase change), {args.cols} columns per GPU, fp64",
                 "columns_per_gpu": args.cols, "columns_total": ncols_global, "levels": 20, "tier": tier_name, "parallelism": par,
             }
+        else:
+            out["config"] = {
+                "workload": f"full water+energy timestep (7 kernels{', fused streaming stage' if args.fused else ''}), {args.cols} columns x 20 soil+snow levels per GPU, fp64",
+                "columns_per_gpu": args.cols, "columns_total": ncols_global, "levels": 20, "tier": tier_name, "parallelism": par,
+            }
+        # the rest of the line is what --full measured after the timed steps
+        detail = full and rehearsal is None
+        if detail and soil:
+            gbs = SOIL_ALGO_BYTES * ncols / (ms_total * 1e-3) / 1e9
             out["roofline"] = {"bound": "hbm", "kernel": "k_soil_temperature", "achieved": gbs, "peak": HBM_PEAK_GBS,
                                "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
                                "traffic": pmc_traffic("soil_temperature", args.tier, args.cols, f"{PROFILE_TAG}_hbm_traffic_pmc_soil_tier{args.tier}.json"),
@@ -975,7 +1004,7 @@ def main(argv=None):
                 out["roofline"]["empirical_peak"] = empirical["peak_GBps"]
                 out["roofline"]["frac_of_empirical_peak"] = gbs / empirical["peak_GBps"]
                 out["roofline"]["empirical"] = empirical
-        else:
+        elif detail:
             act = active_bytes(veg_frac, sun_frac)
             kern = {}
             for name, m in zip(names, ms):
@@ -998,10 +1027,6 @@ def main(argv=None):
                 dom_bytes = ALGO_BYTES[dom[0]]
             dom_gbs = dom_bytes * ncols / (dom[1] * 1e-3) / 1e9
             step_gbs = step_bytes * ncols / (ms_total * 1e-3) / 1e9
-            out["config"] = {
-                "workload": f"full water+energy timestep (7 kernels{', fused streaming stage' if args.fused else ''}), {args.cols} columns x 20 soil+snow levels per GPU, fp64",
-                "columns_per_gpu": args.cols, "columns_total": ncols_global, "levels": 20, "tier": tier_name, "parallelism": par,
-            }
             # which roof applies, from evidence: the committed SQ counter table of this build says how busy the vector ALUs
             # are in the kernels that are not streaming kernels (canopy_fluxes' leaf-temperature iteration, SNICAR)
             comp = compute_roofline(["k_cf_iterate", "k_alb_snicar<1>", "k_bg_flux", "k_cf_init", "k_alb_final"], args.tier, args.cols)
@@ -1042,7 +1067,8 @@ def main(argv=None):
                 "sunlit_fraction": round(sun_frac, 4), "vegetated_fraction": round(veg_frac, 4),
             }
             out["kernels"] = kern
-        out["error_flags"] = flags
+        if full:
+            out["error_flags"] = flags
         out["device_state_GB"] = state_gb
         if other is not None:
             out["other_tier"] = other
@@ -1060,7 +1086,7 @@ def main(argv=None):
             out["fp32_state_10M"] = f32
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if not args.no_cpu_baseline and world == 1 and rehearsal is None:  # reported at N = 1 only
+        if full and not args.no_cpu_baseline and world == 1 and rehearsal is None:  # reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(host_state, workload=args.workload)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -272,3 +272,16 @@ def test_bench_dump_outputs_is_a_fixed_float64_sample(tmp_path):
         if f != "sample_columns.npy":
             src = D.arr[f[:-4]][cols]
             assert np.array_equal(a, (src[:, 0] if src.shape[1] == 1 else src).astype(np.float64))
+
+
+def test_bench_full_is_an_option_that_is_off_by_default():
+    """bench.py's command line: a plain run is the default, --full is the switch for everything beside the headline, and an option
+    that asks for a part of the full run without it is refused instead of silently measuring nothing."""
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and (a.steps, a.warmup, a.gpus, a.dump_outputs) == (7, 3, 1, None)
+    assert bench.parse_args(["--full"]).full is True and bench.parse_args(["--full", "--state-f32"]).state_f32 is True
+    with pytest.raises(SystemExit) as e:
+        bench.parse_args(["--state-f32"])
+    assert e.value.code == 2

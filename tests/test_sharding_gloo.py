@@ -113,6 +113,18 @@ def test_bench_main_spawns_its_own_ranks(tmp_path):
     assert len(line["per_rank_ms"]) == 2 and abs(max(line["per_rank_ms"]) - line["ms_per_step"]) < 1e-3 * line["ms_per_step"] + 1e-3
 
 
+def test_bench_main_full_run_adds_to_the_line(tmp_path):
+    """--full on the same launch: the same shards and headline, and beside them what is checked after the timed steps (here the
+    kernels' error flags: the rehearsal has nothing else to measure), which a plain run leaves out."""
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--cols", "300", "--steps", "2", "--warmup", "1", "--tier", "B"]
+    plain = _run_bench(cmd, tmp_path, 600)
+    _check_shards(tmp_path, plain, 300, 2, 2, 1)
+    full = _run_bench(cmd + ["--full"], tmp_path, 600)
+    _check_shards(tmp_path, full, 300, 2, 2, 1)
+    assert set(full) - set(plain) == {"error_flags"} and set(plain) <= set(full)
+    assert isinstance(full["error_flags"], int) and len(full["per_rank_ms"]) == 2
+
+
 def test_a_rank_that_dies_early_ends_the_run_within_seconds(tmp_path):
     """One rank exits before the barrier: the parent must stop the other rank (which is waiting in the rendezvous or in the
     barrier) and return non-zero quickly, not after the backend's timeout."""

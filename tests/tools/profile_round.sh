@@ -63,7 +63,7 @@ done
 unset ELMK_LIBRARY
 for mode in "" "--fused"; do
   n=bench_10M${mode:+_fused}
-  rocprofv3 --kernel-trace --stats -d $O/kt -o p --output-format csv -- python3 $R/bench.py $mode --cols 10000000 --steps 5 --warmup 2 --no-cpu-baseline --no-other-tier --no-north-star --no-state-f32 --no-two-blocks > $O/${n}_under_rocprof.json 2> $O/kt10.log
+  rocprofv3 --kernel-trace --stats -d $O/kt -o p --output-format csv -- python3 $R/bench.py --full $mode --cols 10000000 --steps 5 --warmup 2 --no-cpu-baseline --no-other-tier --no-north-star --no-state-f32 --no-two-blocks > $O/${n}_under_rocprof.json 2> $O/kt10.log
   cp $O/kt/p_kernel_stats.csv $O/${n}_rocprof_kernel_stats.csv
   cp $O/${n}_rocprof_kernel_stats.csv $R/profiles/${P}_${n}_rocprof_kernel_stats.csv
   rm -rf $O/kt
@@ -85,12 +85,12 @@ fi
 if [ $STAGE = bench ] || [ $STAGE = all ]; then
 # 2. the benchmark line (reads the tables written above) and its rocprofv3 kernel statistics
 cd $R
-python3 bench.py --state-f32 > $O/bench_1M.json 2> $O/bench_1M.err
+python3 bench.py --full --state-f32 > $O/bench_1M.json 2> $O/bench_1M.err
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $O/kt -o p --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-other-tier --no-north-star --no-two-blocks > $O/bench_1M_under_rocprof.json 2> $O/kt.log
+rocprofv3 --kernel-trace --stats -d $O/kt -o p --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-other-tier --no-north-star --no-two-blocks > $O/bench_1M_under_rocprof.json 2> $O/kt.log
 cp $O/kt/p_kernel_stats.csv $O/bench_1M_rocprof_kernel_stats.csv
 rm -rf $O/kt
-rocprofv3 --kernel-trace --stats -d $O/kt -o p --output-format csv -- python3 $R/bench.py --fused --no-cpu-baseline --no-other-tier --no-north-star --no-two-blocks > $O/bench_1M_fused_under_rocprof.json 2> $O/ktf.log
+rocprofv3 --kernel-trace --stats -d $O/kt -o p --output-format csv -- python3 $R/bench.py --full --fused --no-cpu-baseline --no-other-tier --no-north-star --no-two-blocks > $O/bench_1M_fused_under_rocprof.json 2> $O/ktf.log
 cp $O/kt/p_kernel_stats.csv $O/bench_1M_fused_rocprof_kernel_stats.csv
 rm -rf $O/kt
 for f in bench_1M.json bench_1M_rocprof_kernel_stats.csv bench_1M_fused_rocprof_kernel_stats.csv; do cp $O/$f $R/profiles/${P}_$f; done
@@ -98,11 +98,11 @@ fi
 if [ $STAGE = rest ] || [ $STAGE = all ]; then
 cd $R
 # 3. BASELINE config 3: the soil-column vertical solve
-python3 bench.py --workload soil_temperature --cols 10000000 --steps 5 --warmup 2 --tier B > $O/bench_soil_10M.json 2> $O/bench_soil_10M.err
-python3 bench.py --workload soil_temperature --no-cpu-baseline --tier B > $O/bench_soil_1M.json 2> $O/bench_soil_1M.err
+python3 bench.py --full --workload soil_temperature --cols 10000000 --steps 5 --warmup 2 --tier B > $O/bench_soil_10M.json 2> $O/bench_soil_10M.err
+python3 bench.py --full --workload soil_temperature --no-cpu-baseline --tier B > $O/bench_soil_1M.json 2> $O/bench_soil_1M.err
 # 4. the rest of advance() and the multi-rank rehearsal (two ranks sharing this one GPU, gloo for the barrier)
 python3 tests/tools/advance_times.py 1000000 B 5 > $O/advance_times_1M.txt 2>&1
-python3 bench.py --gpus 2 --cols 500000 --no-cpu-baseline > $O/bench_2ranks_on_1gpu.json 2> $O/bench_2ranks.err
+python3 bench.py --full --gpus 2 --cols 500000 --no-cpu-baseline > $O/bench_2ranks_on_1gpu.json 2> $O/bench_2ranks.err
 # 5. the box itself (record what the roofline denominators refer to)
 { rocminfo | grep -E "Marketing Name|Name: +gfx|Compute Unit|Max Clock Freq|Wavefront Size|Workgroup Max Size:|Size: +[0-9]+\(0x[0-9a-f]+\) KB" | sort | uniq -c | sort -rn | head -40; echo; rocm-smi --showmeminfo vram --showclocks --showproductname 2>/dev/null | grep -v "^$" | head -60; } > $O/device_info.txt 2>&1 || true
 for f in bench_soil_10M.json bench_soil_1M.json advance_times_1M.txt bench_2ranks_on_1gpu.json device_info.txt; do cp $O/$f $R/profiles/${P}_$f; done
