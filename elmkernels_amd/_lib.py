@@ -166,6 +166,7 @@ SIGNATURES = {
     "elmk_routing_inundation_clear": (C.c_int, [_P]),
     "elmk_column_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_gridded_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "elmk_cell_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

@@ -19,6 +19,17 @@ OGridMap ogrid_map(const elmk_ctx* ctx)
 bool has_gridded_entries(const elmk_ctx* ctx) { return !ctx->hist_crows.empty(); }
 
 bool tape_ok(int tape) { return tape >= 0 && tape < ELMK_HIST_MAX_TAPES; }
+
+// the rows of a cell-row family (ELMK_CELL_ROWS_*) for a history entry: the device row `which` over the routing's cells, or null with
+// *why set - exactly the rows elmk_routing_read / elmk_irrigation_supply_read accept at this moment
+const double* cell_row(const elmk_ctx* ctx, int family, int which, const char** why)
+{
+  if (family == ELMK_CELL_ROWS_ROUTING) return route_row(ctx, which, why);
+  if (family != ELMK_CELL_ROWS_SUPPLY) return *why = "unknown cell-row family", nullptr;
+  if (!ctx->irrsup_rows) return *why = "the irrigation's river supply limit is not on (elmk_irrigation_supply_enable)", nullptr;
+  if (which < ELMK_IRRSUP_DEMAND || which > ELMK_IRRSUP_UNMET_SUM) return *why = "row out of range", nullptr;
+  return ctx->irrsup_rows + (size_t)which * (size_t)ctx->route.cld;
+}
 }  // namespace
 
 namespace elmk {
@@ -39,6 +50,17 @@ int hist_has_family(const elmk_ctx* ctx, int family)
   return 0;
 }
 
+int cellrows_hold(elmk_ctx* ctx, const char* who, int family, int which0, int which1)
+{
+  for (const elmk_ctx::HistEntry& e : ctx->hist) {
+    if (!e.cellrow) continue;
+    const int which = e.field & 0xFFFF;  // (ELMK_RESTART_ROW_FIELD)
+    if (family < 0 || (e.family == ELMK_ROWS_NFAMILY + family && which >= which0 && which <= which1))
+      return invalid(ctx, (std::string(who) + ": cell-row history entries exist on its rows (elmk_history_clear first)").c_str());
+  }
+  return ELMK_OK;
+}
+
 void mark_sampled(elmk_ctx* ctx, unsigned mask)
 {
   for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
@@ -49,7 +71,10 @@ void mark_sampled(elmk_ctx* ctx, unsigned mask)
 void hist_accumulate_launch(elmk_ctx* ctx)
 {
   const unsigned mask = hist_tape_mask(ctx);
-  if (!has_gridded_entries(ctx))
+  if (!ctx->hist_rrows.empty())  // cell-row entries: the third kernel, which folds every kind of row
+    launch_hist_accumulate_rows(ctx->hist_table, (int)ctx->hist_rows.size(), hist_cell_rows(ctx), (int)ctx->hist_crows.size(), ctx->hist_rtable,
+                                (int)ctx->hist_rrows.size(), ogrid_map(ctx), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
+  else if (!has_gridded_entries(ctx))
     launch_hist_accumulate(ctx->hist_table, (int)ctx->hist_rows.size(), hist_counts(ctx), ctx->ncols, mask, ctx->stream);
   else
     launch_hist_accumulate_cells(ctx->hist_table, (int)ctx->hist_rows.size(), hist_cell_rows(ctx), (int)ctx->hist_crows.size(),
@@ -61,16 +86,18 @@ namespace {
 // elmk_history_add (cells = false: accumulators over the columns) and elmk_gridded_history_add (cells = true: over the output grid's
 // cells); `who` names the entry point in the messages.  family >= 0 (elmk_column_history_add_row, elmk_gridded_history_add_row): the entry
 // samples row `field` of that feature family instead of a state field: one level, true fp64 in both builds
-int hist_add(elmk_ctx* ctx, int tape, int field, int op, bool cells, const char* who, int family = -1)
+// cfamily >= 0 (elmk_cell_history_add_row): the entry samples cell row `field` of that cell-row family, a row over the output grid's cells
+// that is its own sample: one level, accumulators over the cells, no map and no fill
+int hist_add(elmk_ctx* ctx, int tape, int field, int op, bool cells, const char* who, int family = -1, int cfamily = -1)
 {
   if (int rc = enter(ctx)) return rc;
   const std::string w = who;
   if (!tape_ok(tape)) return invalid(ctx, (w + ": unknown tape").c_str());
-  const bool row = family >= 0;
+  const bool cellrow = cfamily >= 0, row = family >= 0 || cellrow;
   const double* frow = nullptr;
   if (row) {
     const char* why = nullptr;
-    frow = feature_row(ctx, family, field, &why);
+    frow = cellrow ? cell_row(ctx, cfamily, field, &why) : feature_row(ctx, family, field, &why);
     if (!frow) return invalid(ctx, (w + ": " + why).c_str());
   } else if (!field_ok(field)) {
     return invalid(ctx, (w + ": unknown field").c_str());
@@ -84,18 +111,22 @@ int hist_add(elmk_ctx* ctx, int tape, int field, int op, bool cells, const char*
     HIPCHK(ctx->hist_table.alloc(HIST_TABLE_BYTES));
     HIPCHK(hipMemsetAsync(ctx->hist_table, 0, HIST_TABLE_BYTES, ctx->stream));
   }
+  if (cellrow && !ctx->hist_rtable) {  // (one level per entry: ELMK_HIST_MAX_ENTRIES rows at the most)
+    HIPCHK(ctx->hist_rtable.alloc((size_t)ELMK_HIST_MAX_ENTRIES * sizeof(HistRow)));
+    HIPCHK(hipMemsetAsync(ctx->hist_rtable, 0, (size_t)ELMK_HIST_MAX_ENTRIES * sizeof(HistRow), ctx->stream));
+  }
   const int nlev = row ? 1 : g_fields[field].nlev;
   // a column row spans the level stride; a cell row the cell count rounded up to 64 (16-byte aligned rows for k_hist_reset's pairs)
-  const int64_t ld = cells ? (ctx->ogrid.map.nrows + 63) / 64 * 64 : ctx->ld;
+  const int64_t ld = cellrow ? ctx->route.cld : cells ? (ctx->ogrid.map.nrows + 63) / 64 * 64 : ctx->ld;
   const size_t bytes = (size_t)nlev * (size_t)ld * sizeof(double);
   DevBuf<double> acc;
   if (hip_fail(ctx, acc.alloc(bytes), "hipMalloc(history)")) return ELMK_E_NOMEM;
   launch_fill(acc, ELMK_F64, nlev, ld, ld, hist_init_value(op), ctx->stream);
-  std::vector<HistRow>& rows = cells ? ctx->hist_crows : ctx->hist_rows;
-  HistRow* table = cells ? hist_cell_rows(ctx) : (HistRow*)ctx->hist_table;
+  std::vector<HistRow>& rows = cellrow ? ctx->hist_rrows : cells ? ctx->hist_crows : ctx->hist_rows;
+  HistRow* table = cellrow ? (HistRow*)ctx->hist_rtable : cells ? hist_cell_rows(ctx) : (HistRow*)ctx->hist_table;
   const int row0 = (int)rows.size();
   if (row) {
-    rows.push_back(HistRow{frow, acc, ELMK_F64, op, tape, 0});
+    rows.push_back(HistRow{frow, acc, ELMK_F64, op, tape, cellrow ? 1 : 0});  // (pad: 1 marks a cell-row entry's row)
   } else {
     const int es = store_size(g_fields[field].dtype);
     for (int l = 0; l < nlev; l++)
@@ -113,7 +144,9 @@ int hist_add(elmk_ctx* ctx, int tape, int field, int op, bool cells, const char*
     (void)hipStreamSynchronize(ctx->stream);
     return ELMK_E_HIP;  // (frees acc)
   }
-  ctx->hist.push_back(elmk_ctx::HistEntry{tape, row ? ELMK_RESTART_ROW_FIELD(family, field) : field, op, nlev, row0, std::move(acc), cells, ld, family});
+  if (cellrow) family = ELMK_ROWS_NFAMILY + cfamily;
+  ctx->hist.push_back(elmk_ctx::HistEntry{tape, row ? ELMK_RESTART_ROW_FIELD(family, field) : field, op, nlev, row0, std::move(acc), cells, ld, family,
+                                          cellrow});
   ctx->hist_version++;
   return (int)ctx->hist.size() - 1;
 }
@@ -152,6 +185,10 @@ int elmk_history_reset(elmk_ctx* ctx, int tape)
                       ctx->stream);
     HIPCHK(hipGetLastError());
   }
+  if (!ctx->hist_rrows.empty()) {  // (and once more)
+    launch_hist_reset(ctx->hist_rtable, (int)ctx->hist_rrows.size(), hist_counts(ctx), ctx->route.cld, tape, ctx->stream);
+    HIPCHK(hipGetLastError());
+  }
   ctx->hist_dirty[tape] = false;
   return ELMK_OK;
 }
@@ -173,9 +210,10 @@ int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int6
   if (int rc = enter(ctx)) return rc;
   if (entry < 0 || entry >= (int)ctx->hist.size()) return invalid(ctx, "elmk_history_read: unknown entry");
   const elmk_ctx::HistEntry& e = ctx->hist[entry];
-  const int64_t lim = e.cells ? ctx->ogrid.map.nrows : ctx->ncols;  // a gridded entry's col0, n index cells
-  if (int rc = check_range(ctx, "elmk_history_read", host, col0, n, lim, e.cells ? "cell" : "column")) return rc;
-  if (layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_history_read: unknown layout");
+  // a gridded entry's col0, n index cells, and so do a cell-row entry's (one level: the layout says nothing and is not looked at)
+  const int64_t lim = e.cellrow ? ctx->route.ncells : e.cells ? ctx->ogrid.map.nrows : ctx->ncols;
+  if (int rc = check_range(ctx, "elmk_history_read", host, col0, n, lim, e.cells || e.cellrow ? "cell" : "column")) return rc;
+  if (!e.cellrow && layout != ELMK_LAYOUT_SOA && layout != ELMK_LAYOUT_COL_MAJOR) return invalid(ctx, "elmk_history_read: unknown layout");
   int64_t count = 0;
   if (int rc = elmk_history_count(ctx, e.tape, &count)) return rc;
   if (count <= 0) return invalid(ctx, "elmk_history_read: the tape holds no samples");
@@ -191,7 +229,7 @@ int elmk_history_read(elmk_ctx* ctx, int entry, double* host, int64_t col0, int6
     if (e.cells)
       launch_ogrid_finalize(e.acc, e.cld, e.nlev, e.op, count, ctx->ogrid.map.ptr, ctx->ogrid.fill, col0 + done, m, soa, ctx->stream);
     else
-      launch_hist_finalize(e.acc, ctx->ld, e.nlev, e.op, count, col0 + done, m, soa, ctx->stream);
+      launch_hist_finalize(e.acc, e.cellrow ? e.cld : ctx->ld, e.nlev, e.op, count, col0 + done, m, soa, ctx->stream);
     if (layout == ELMK_LAYOUT_SOA || e.nlev == 1) {
       HIPCHK(hipMemcpy2DAsync(host + done, (size_t)n * sizeof(double), soa, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
                               e.nlev, hipMemcpyDeviceToHost, ctx->stream));
@@ -213,6 +251,7 @@ int elmk_history_clear(elmk_ctx* ctx)
   ctx->hist.clear();
   ctx->hist_rows.clear();
   ctx->hist_crows.clear();
+  ctx->hist_rrows.clear();
   if (ctx->hist_table)
     HIPCHK(hipMemsetAsync(hist_counts(ctx), 0, ELMK_HIST_MAX_TAPES * sizeof(unsigned long long), ctx->stream));
   for (bool& d : ctx->hist_dirty) d = false;
@@ -230,6 +269,7 @@ int elmk_set_output_grid(elmk_ctx* ctx, int64_t ncells, const int64_t* ptr, cons
   if (int rc = invalid_map(ctx, "elmk_set_output_grid", csr_check(ncells, ctx->ncols, ptr, col, w, "ncells outside 1 .. 2^31-1", false, false))) return rc;
   if (int rc = refuse_capture(ctx, "elmk_set_output_grid")) return rc;
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_set_output_grid: gridded history entries exist (elmk_history_clear first)");
+  if (int rc = cellrows_hold(ctx, "elmk_set_output_grid")) return rc;  // (ncells is the grid's)
   if (int rc = irrsup_holds(ctx, "elmk_set_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_set_output_grid")) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));  // (a gridded download may still read the old map)
@@ -248,6 +288,7 @@ int elmk_clear_output_grid(elmk_ctx* ctx)
   if (int rc = enter(ctx)) return rc;
   if (int rc = refuse_capture(ctx, "elmk_clear_output_grid")) return rc;
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_clear_output_grid: gridded history entries exist (elmk_history_clear first)");
+  if (int rc = cellrows_hold(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = irrsup_holds(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_clear_output_grid")) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -287,6 +328,12 @@ int elmk_gridded_history_add_row(elmk_ctx* ctx, int tape, int family, int which,
 {
   if (family < 0) return ctx ? invalid(ctx, "elmk_gridded_history_add_row: unknown row family") : ELMK_E_INVALID;
   return hist_add(ctx, tape, which, op, true, "elmk_gridded_history_add_row", family);
+}
+
+int elmk_cell_history_add_row(elmk_ctx* ctx, int tape, int family, int which, int op)
+{
+  if (family < 0 || family >= ELMK_CELL_ROWS_NFAMILY) return ctx ? invalid(ctx, "elmk_cell_history_add_row: unknown cell-row family") : ELMK_E_INVALID;
+  return hist_add(ctx, tape, which, op, false, "elmk_cell_history_add_row", -1, family);
 }
 
 }  // extern "C"

@@ -187,6 +187,7 @@ int elmk_irrigation_supply_clear(elmk_ctx* ctx)
   if (int rc = enter(ctx)) return rc;
   if (int rc = refuse_capture(ctx, "elmk_irrigation_supply_clear")) return rc;
   if (!ctx->irrsup_rows) return ELMK_OK;
+  if (int rc = cellrows_hold(ctx, "elmk_irrigation_supply_clear", ELMK_CELL_ROWS_SUPPLY, 0, IRRSUP_NROWS - 1)) return rc;
   if (int rc = quiesce(ctx, false)) return rc;
   (void)ctx->irrsup_rows.reset();
   ctx->irrsup_thr = 0.0;

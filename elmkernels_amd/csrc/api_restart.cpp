@@ -32,6 +32,7 @@ static_assert(every_field_classified(), "include/elmk_restart.def lists every fi
 constexpr size_t RST_ALIGN = 256;
 constexpr size_t RST_CHUNK = (size_t)64 << 20;  // bytes of image per staging chunk
 constexpr int RST_MAX_PIECES = 8192;            // per chunk (grid.y)
+constexpr uint32_t RST_V_ROUTING = ELMK_RESTART_VERSION_ROUTING;
 
 uint64_t fmix64(uint64_t k)
 {
@@ -97,13 +98,27 @@ struct RstRows {
   double* dev;
 };
 using Ctx = const elmk_ctx*;
+// cells: the kind's sections are rows over the routing's cells (extent ncells, stride cld, g = the cell) and not over the columns;
+// implied: an image of the kind's version holds the kind whatever its section table says (every kind that introduced a version)
 struct RstKind {
   int kind;
   uint32_t version;
   const char *feature, *enable;
   int (*count)(Ctx);
   RstRows (*rows)(Ctx, int i);
+  bool cells = false, implied = true;
 };
+// the routing state of version 6 (ELMK_OPT_RESTART_CELLS): the prognostic rows the river stages hold at this moment, in image order
+int route_state_rows(Ctx c, int* ids)
+{
+  if (!c->restart_cells || !c->route.mem) return 0;
+  int n = 0;
+  ids[n++] = ELMK_ROUTE_VOLR;
+  ids[n++] = ELMK_ROUTE_QOUT_SUM;
+  if (c->route.kw_mem) ids[n++] = ELMK_ROUTE_WH, ids[n++] = ELMK_ROUTE_WT;
+  if (c->route.fp_mem) ids[n++] = ELMK_ROUTE_WF;
+  return n;
+}
 const RstKind RST_OPTIONAL[] = {
     {ELMK_RESTART_ACCUM, ELMK_RESTART_VERSION_ACCUM, "accumulator entries", "elmk_accum_add", [](Ctx c) { return (int)c->accum.size(); },
      [](Ctx c, int i) { return RstRows{i, c->accum[i].nlev, c->accum[i].val}; }},
@@ -112,7 +127,23 @@ const RstKind RST_OPTIONAL[] = {
     {ELMK_RESTART_HYDROLOGY, ELMK_RESTART_VERSION_HYDROLOGY, "the soil hydrology", "elmk_soil_hydrology_enable", [](Ctx c) { return c->hyd_rows ? 2 : 0; },
      [](Ctx c, int i) { return RstRows{ELMK_HYD_ZWT + i, 1, c->hyd_rows + (size_t)(ELMK_HYD_ZWT + i) * (size_t)c->ld}; }},
     {ELMK_RESTART_IRRIGATION, ELMK_RESTART_VERSION_IRRIGATION, "the irrigation", "elmk_irrigation_enable", [](Ctx c) { return c->irr_rows ? 2 : 0; },
-     [](Ctx c, int i) { return RstRows{ELMK_IRR_RATE + i, 1, c->irr_rows + (size_t)(ELMK_IRR_RATE + i) * (size_t)c->ld}; }}};
+     [](Ctx c, int i) { return RstRows{ELMK_IRR_RATE + i, 1, c->irr_rows + (size_t)(ELMK_IRR_RATE + i) * (size_t)c->ld}; }},
+    {ELMK_RESTART_ROUTING, ELMK_RESTART_VERSION_ROUTING, "the routing state", "elmk_routing_enable with ELMK_OPT_RESTART_CELLS on",
+     [](Ctx c) {
+       int ids[5];
+       return route_state_rows(c, ids);
+     },
+     [](Ctx c, int i) {
+       int ids[5];
+       const char* why = nullptr;
+       (void)route_state_rows(c, ids);
+       return RstRows{ids[i], 1, const_cast<double*>(route_row(c, ids[i], &why))};
+     },
+     true},
+    {ELMK_RESTART_IRRSUP, ELMK_RESTART_VERSION_ROUTING, "the river supply limit's UNMET_SUM", "elmk_irrigation_supply_enable with ELMK_OPT_RESTART_CELLS on",
+     [](Ctx c) { return c->restart_cells && c->route.mem && c->irrsup_rows ? 1 : 0; },
+     [](Ctx c, int) { return RstRows{ELMK_IRRSUP_UNMET_SUM, 1, c->irrsup_rows + (size_t)ELMK_IRRSUP_UNMET_SUM * (size_t)c->route.cld}; }, true, false}};
+constexpr uint32_t RST_MAX_VERSION = RST_V_ROUTING;
 static_assert(ELMK_HYD_WA == ELMK_HYD_ZWT + 1 && ELMK_IRR_NLEFT == ELMK_IRR_RATE + 1, "the two rows of the image");
 
 RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
@@ -125,10 +156,12 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
   }
   for (size_t i = 0; i < ctx->hist.size(); i++) {
     const elmk_ctx::HistEntry& e = ctx->hist[i];
-    const int64_t ext = e.cells ? ctx->ogrid.map.nrows : ctx->ncols;
-    L.ent.push_back(elmk_restart_entry{e.tape, e.field, e.op, e.cells ? 1 : 0, e.cells ? ctx->ogrid.map.nrows : 0});
-    L.sec.push_back(elmk_restart_section{e.cells ? ELMK_RESTART_GRIDDED : ELMK_RESTART_HISTORY, (int32_t)i, e.nlev, ELMK_F64, ext, 0, 0});
-    L.src.push_back(RstSrc{(char*)(double*)e.acc, e.cld, ELMK_F64, e.cells ? 0 : gcol0, false});
+    // a cell-row entry (elmk_cell_history_add_row): gridded = 2, the routing's cells, its accumulators a GRIDDED section (g = the cell)
+    const bool bycell = e.cells || e.cellrow;
+    const int64_t ext = e.cellrow ? ctx->route.ncells : e.cells ? ctx->ogrid.map.nrows : ctx->ncols;
+    L.ent.push_back(elmk_restart_entry{e.tape, e.field, e.op, e.cellrow ? 2 : e.cells ? 1 : 0, bycell ? ext : 0});
+    L.sec.push_back(elmk_restart_section{bycell ? ELMK_RESTART_GRIDDED : ELMK_RESTART_HISTORY, (int32_t)i, e.nlev, ELMK_F64, ext, 0, 0});
+    L.src.push_back(RstSrc{(char*)(double*)e.acc, e.cld, ELMK_F64, bycell ? 0 : gcol0, false});
   }
   for (const elmk_ctx::AccumEntry& e : ctx->accum) L.acc.push_back(elmk_restart_accum{e.src, e.kind, e.dst, 0, e.period, 0});
   for (const RstKind& K : RST_OPTIONAL) {
@@ -139,12 +172,12 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
     }
     for (int i = 0; i < n; i++) {
       const RstRows r = K.rows(ctx, i);
-      L.sec.push_back(elmk_restart_section{K.kind, r.id, r.nlev, ELMK_F64, ctx->ncols, 0, 0});
-      L.src.push_back(RstSrc{(char*)r.dev, ctx->ld, ELMK_F64, gcol0, false});
+      L.sec.push_back(elmk_restart_section{K.kind, r.id, r.nlev, ELMK_F64, K.cells ? ctx->route.ncells : ctx->ncols, 0, 0});
+      L.src.push_back(RstSrc{(char*)r.dev, K.cells ? ctx->route.cld : ctx->ld, ELMK_F64, K.cells ? 0 : gcol0, false});
     }
   }
   // the accumulator table follows the history entries
-  L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.version >= 2 ? 8 : 0) + L.acc.size() * sizeof(elmk_restart_accum) +
+  L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.version >= 2 ? 8 : 0) + (L.version >= RST_V_ROUTING ? 8 : 0) + L.acc.size() * sizeof(elmk_restart_accum) +
                                 L.ent.size() * sizeof(elmk_restart_entry) + L.sec.size() * sizeof(elmk_restart_section),
                             RST_ALIGN);
   size_t off = L.header_bytes;
@@ -355,6 +388,11 @@ int elmk_restart_save(elmk_ctx* ctx, int64_t gcol0, void* image, int64_t bytes)
     memcpy(p, word, 8);
     p += 8;
   }
+  if (L.version >= RST_V_ROUTING) {  // the routing's call count
+    const int64_t ncalls = ctx->route.ncalls;
+    memcpy(p, &ncalls, 8);
+    p += 8;
+  }
   if (!L.ent.empty()) memcpy(p, L.ent.data(), L.ent.size() * sizeof(elmk_restart_entry));
   p += L.ent.size() * sizeof(elmk_restart_entry);
   for (size_t i = 0; i < L.acc.size(); i++) {
@@ -380,7 +418,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   elmk_restart_header H;
   if (bytes < (int64_t)sizeof H) return invalid(ctx, "elmk_restart_load: truncated image");
   memcpy(&H, in, sizeof H);
-  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || H.version < 1 || H.version > std::end(RST_OPTIONAL)[-1].version)
+  if (memcmp(H.magic, ELMK_RESTART_MAGIC, 8) != 0 || H.version < 1 || H.version > RST_MAX_VERSION)
     return invalid(ctx, "elmk_restart_load: not a restart image of this format version");
   if (H.header_bytes > (uint64_t)bytes || H.total_bytes > (uint64_t)bytes || H.header_bytes % 8 != 0)
     return invalid(ctx, "elmk_restart_load: truncated image");
@@ -401,8 +439,16 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
     memcpy(word, p, 8);
     p += 8;
   }
+  int64_t route_ncalls = 0;
+  if (H.version >= RST_V_ROUTING) {
+    if (H.header_bytes < sizeof H + 16) return invalid(ctx, truncated);
+    memcpy(&route_ncalls, p, 8);
+    p += 8;
+    if (route_ncalls < 0) return invalid(ctx, "elmk_restart_load: the routing's call count is negative");
+  }
   unsigned kinds = word[0] ? 1u << ELMK_RESTART_ACCUM : 0u;
-  for (const RstKind& K : RST_OPTIONAL) kinds |= K.version == H.version ? 1u << K.kind : 0u;
+  for (const RstKind& K : RST_OPTIONAL) kinds |= K.implied && K.version == H.version ? 1u << K.kind : 0u;
+  std::vector<std::pair<int32_t, int64_t>> img_cells, ctx_cells;  // (id, extent) of the cell sections of the routing state
   if (H.version >= ELMK_RESTART_VERSION_HYDROLOGY) {
     const uint64_t at = (uint64_t)(p - in) + (uint64_t)H.nentries * sizeof(elmk_restart_entry) + (uint64_t)word[0] * sizeof(elmk_restart_accum);
     if (at > H.header_bytes || (H.header_bytes - at) / sizeof(elmk_restart_section) < H.nsections) return invalid(ctx, truncated);
@@ -410,6 +456,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
       elmk_restart_section S;
       memcpy(&S, in + at + (size_t)k * sizeof S, sizeof S);
       for (const RstKind& K : RST_OPTIONAL) kinds |= K.kind == S.kind ? 1u << K.kind : 0u;
+      if (S.kind == ELMK_RESTART_ROUTING) img_cells.emplace_back(S.id, S.extent);
     }
   }
   for (const RstKind& K : RST_OPTIONAL) {
@@ -422,6 +469,12 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
     return invalid(ctx, msg);
   }
   if (word[0] != L.acc.size() || word[1] != 0u) return invalid(ctx, acc_differs);
+  for (const elmk_restart_section& S : L.sec)
+    if (S.kind == ELMK_RESTART_ROUTING) ctx_cells.emplace_back(S.id, S.extent);
+  if (img_cells != ctx_cells)
+    return invalid(ctx, "elmk_restart_load: the image's routing state differs from the context's: another ncells (elmk_routing_enable), or the "
+                        "kinematic-wave scheme (elmk_routing_kinematic_enable) or the floodplain inundation (elmk_routing_inundation_enable) "
+                        "on in one and off in the other");
   // a differing entry table; the feature is named where the image holds an entry over a feature row (ELMK_RESTART_ROW_FIELD, include/
   // elmk_restart.def) that the context has not got in that place
   const auto entries_differ = [&]() {
@@ -484,6 +537,15 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   for (size_t s = 0; s < L.sec.size(); s++)
     if (ck[s] != want[s]) return invalid(ctx, "elmk_restart_load: section checksum mismatch");
   if (bad) return invalid(ctx, "elmk_restart_load: snl outside 0..nlevsno");
+  if (L.kinds & (1u << ELMK_RESTART_ROUTING)) {  // every row of the river stages zero, as their _init calls leave the diagnostic ones
+    const elmk_ctx::Routing& T = ctx->route;
+    const size_t row = (size_t)T.cld * sizeof(double);
+    HIPCHK(hipMemsetAsync(T.rows, 0, (size_t)ROUTE_NROWS * row, ctx->stream));
+    if (T.kw_mem) HIPCHK(hipMemsetAsync(T.kw_rows, 0, (size_t)KW_NROWS * row, ctx->stream));
+    if (T.fp_mem) HIPCHK(hipMemsetAsync(T.fp_rows, 0, (size_t)FP_NROWS * row, ctx->stream));
+    if (ctx->irrsup_rows) HIPCHK(hipMemsetAsync(ctx->irrsup_rows, 0, ctx->irrsup_rows.bytes(), ctx->stream));
+    ctx->route.ncalls = route_ncalls;
+  }
   if (int rc = pass(2)) return rc;  // then the tape counts
   if (ctx->hist_table) {
     unsigned long long counts[ELMK_HIST_MAX_TAPES];

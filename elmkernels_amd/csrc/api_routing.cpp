@@ -65,6 +65,18 @@ void route_launch(elmk_ctx* ctx, double dt)
     launch_routing(route_args(ctx), G, qrunoff, qirr, dt, ctx->stream);
 }
 
+const double* route_row(const elmk_ctx* ctx, int which, const char** why)
+{
+  const elmk_ctx::Routing& T = ctx->route;
+  if (!T.mem) return *why = "runoff routing is not enabled (elmk_routing_enable)", nullptr;
+  if (which < 0 || which > ELMK_ROUTE_FLOOD_FRAC) return *why = "row out of range", nullptr;
+  if (which > ELMK_ROUTE_QSUR && !T.fp_mem) return *why = "the floodplain inundation is not on (elmk_routing_inundation_enable)", nullptr;
+  if (which > ELMK_ROUTE_QOUT_SUM && !T.kw_mem) return *why = "the kinematic-wave scheme is not on (elmk_routing_kinematic_enable)", nullptr;
+  return which > ELMK_ROUTE_QSUR       ? T.fp_rows + (size_t)(which - ELMK_ROUTE_WF) * (size_t)T.cld
+         : which > ELMK_ROUTE_QOUT_SUM ? T.kw_rows + (size_t)(which - ELMK_ROUTE_WH) * (size_t)T.cld
+                                       : T.rows + (size_t)ROUTE_ROW_OF[which] * (size_t)T.cld;
+}
+
 int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal)
 {
   if (!ctx->route.mem || (with_withdrawal && !ctx->route.withdraw)) return ELMK_OK;
@@ -287,6 +299,7 @@ int elmk_routing_kinematic_clear(elmk_ctx* ctx)
   if (!T.kw_mem) return ELMK_OK;
   if (T.fp_mem)  // (the extension's tables are formed from the scheme's RLEN and RWIDTH, and its kernel is the scheme's)
     return invalid(ctx, "elmk_routing_kinematic_clear: the floodplain inundation is on (elmk_routing_inundation_clear first)");
+  if (int rc = cellrows_hold(ctx, "elmk_routing_kinematic_clear", ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_WH, ELMK_ROUTE_QSUR)) return rc;
   if (int rc = quiesce(ctx, false)) return rc;
   T.kw_mem = DevBuf<char>{};
   T.kw_rows = T.kw_par = nullptr;
@@ -371,6 +384,7 @@ int elmk_routing_inundation_clear(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, "elmk_routing_inundation_clear")) return rc;
   elmk_ctx::Routing& T = ctx->route;
   if (!T.fp_mem) return ELMK_OK;
+  if (int rc = cellrows_hold(ctx, "elmk_routing_inundation_clear", ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_WF, ELMK_ROUTE_FLOOD_FRAC)) return rc;
   if (int rc = quiesce(ctx, false)) return rc;
   inundation_off(T);
   return ELMK_OK;
@@ -382,6 +396,7 @@ int elmk_routing_clear(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, "elmk_routing_clear")) return rc;
   if (!ctx->route.mem) return ELMK_OK;
   if (int rc = irrsup_holds(ctx, "elmk_routing_clear")) return rc;  // (the limit reads VOLR and area)
+  if (int rc = cellrows_hold(ctx, "elmk_routing_clear")) return rc;  // (every cell row lies in an allocation this call frees)
   if (int rc = quiesce(ctx, false)) return rc;
   ctx->route = elmk_ctx::Routing{};
   return ELMK_OK;

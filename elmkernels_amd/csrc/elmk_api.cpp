@@ -612,6 +612,11 @@ int elmk_set_option(elmk_ctx* ctx, int option, int value)
     }
     return ELMK_OK;
   }
+  if (option == ELMK_OPT_RESTART_CELLS) {  // (no launch depends on it: the captured graphs stay)
+    if (int rc = refuse_capture(ctx, "elmk_set_option")) return rc;
+    ctx->restart_cells = value != 0;
+    return ELMK_OK;
+  }
   if (option != ELMK_OPT_CF_HALF_WORKGROUPS) return invalid(ctx, "elmk_set_option: unknown option");
   int cus = 0;
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->dev));
@@ -641,7 +646,7 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
              ctx->irr_rows.bytes() + ctx->route.mem.bytes() + ctx->route.kw_mem.bytes() + ctx->route.fp_mem.bytes() + ctx->irrsup_rows.bytes();
   // the cell rows of gridded history entries (not the column rows) and the accumulators' values: whole rows of ld or cld doubles,
   // both multiples of 64, so every size is a multiple of 256 already
-  for (const elmk_ctx::HistEntry& e : ctx->hist) n += e.cells ? e.acc.bytes() : 0;
+  for (const elmk_ctx::HistEntry& e : ctx->hist) n += e.cells || e.cellrow ? e.acc.bytes() : 0;  // (a cell-row entry's are cell rows too)
   for (const elmk_ctx::AccumEntry& e : ctx->accum) n += e.val.bytes();
   return (int64_t)n;
 }

@@ -235,11 +235,16 @@ struct elmk_ctx {
     int64_t cld = 0;
     // an entry over a feature row (elmk_column_history_add_row): its family, or -1; `field` then holds ELMK_RESTART_ROW_FIELD(family, which)
     int family = -1;
+    // an entry over a cell row of the river stages (elmk_cell_history_add_row): `cells` is false, cld the routing's, the accumulators cld
+    // doubles counted in elmk_device_bytes; family holds ELMK_ROWS_NFAMILY + the cell-row family and `field` its ELMK_RESTART_ROW_FIELD
+    bool cellrow = false;
   };
   std::vector<HistEntry> hist;
   std::vector<HistRow> hist_rows;
   std::vector<HistRow> hist_crows;
+  std::vector<HistRow> hist_rrows;  // the rows of cell-row entries, as the device table hist_rtable (allocated by the first such entry)
   DevBuf<HistRow> hist_table;
+  DevBuf<HistRow> hist_rtable;
   bool hist_dirty[ELMK_HIST_MAX_TAPES] = {};
   uint64_t hist_version = 0;  // counts elmk_history_add / _clear: a captured step of elmk_run holds the table of its moment
   // accumulated fields (elmk_accum_*): the entries, their rows as the device table k_accum_update reads (accum_table: the rows, then
@@ -310,6 +315,7 @@ struct elmk_ctx {
     double* fp_rows = nullptr;
     double* fp_tab = nullptr;
   } route;
+  bool restart_cells = false;  // ELMK_OPT_RESTART_CELLS: the image carries the routing state (version 6)
   bool snowage_set = false;
   // multi-step runs (elmk_run_reserve, elmk_series_upload, elmk_run): one device allocation `mem` holds the forcing series, the
   // phenology series, the two step tables, the step cursor and the two diagnostics rings (buffer b: rows b * max_steps ..); `rows`
@@ -490,6 +496,9 @@ void route_launch(elmk_ctx* ctx, double dt);    // one call of the runoff routin
 // "<who>: runoff routing is enabled (elmk_routing_clear first)" while it is - what the routing reads stays; with_withdrawal: only while
 // the withdrawal is on
 int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal = false);
+// row `which` (ELMK_ROUTE_*) of the river stages as elmk_routing_read finds it now, or null with *why set (not enabled, out of range, its
+// scheme or extension off)
+const double* route_row(const elmk_ctx* ctx, int which, const char** why);
 constexpr int ALT_NROWS = 3;  // api_rows.cpp
 ActiveLayerArgs alt_args(const elmk_ctx* ctx);
 bool hyd_land(const elmk_ctx* ctx);
@@ -501,6 +510,9 @@ void wb_launch(elmk_ctx* ctx, double dt, bool run);
 // enabled, which out of range)
 const double* feature_row(const elmk_ctx* ctx, int family, int which, const char** why);
 int hist_has_family(const elmk_ctx* ctx, int family);  // a row entry of the family exists (api_history.cpp)
+// "<who>: cell-row history entries exist on its rows (elmk_history_clear first)" while an entry of elmk_cell_history_add_row samples row
+// which0 .. which1 of the cell-row family (family < 0: any family, any row)
+int cellrows_hold(elmk_ctx* ctx, const char* who, int family = -1, int which0 = 0, int which1 = 0);
 // downscaling TOPO mode: the forcing kernels' parameters (ds_topo false: OFF, the kernels as they were); api_run.cpp
 inline bool ds_topo(const elmk_ctx* ctx) { return ctx->ds.mode == ELMK_DS_TOPO; }
 DsParams ds_params(const elmk_ctx* ctx);

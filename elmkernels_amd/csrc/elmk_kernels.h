@@ -190,6 +190,10 @@ void launch_ogrid_aggregate(const void* src, int dtype, const OGridMap& M, int64
 // launch_hist_accumulate over the column rows and, in the same launch, the cell rows crows[ncrows] (acc: cells of one level, fp64)
 void launch_hist_accumulate_cells(const HistRow* rows, int nrows, const HistRow* crows, int ncrows, const OGridMap& M,
                                   unsigned long long* counts, int64_t ncols, unsigned tape_mask, hipStream_t st);
+// launch_hist_accumulate_cells and, in the same launch, the rows rrows[nrrows] of cell-row entries (elmk_cell_history_add_row): src a fp64
+// row over M.ncells cells that is its own sample, acc as a gridded entry's; nothing without such a row
+void launch_hist_accumulate_rows(const HistRow* rows, int nrows, const HistRow* crows, int ncrows, const HistRow* rrows, int nrrows,
+                                 const OGridMap& M, unsigned long long* counts, int64_t ncols, unsigned tape_mask, hipStream_t st);
 // downscaling's longwave renormalisation (k_history.hip, elmk_set_downscaling_groups): M is the CSR map of the groups (fill 0), wsum[g]
 // the sum of group g's weights in term order.  Per group A = aggregate of lg, S = aggregate of lw (stored element type lw_dtype), then
 // norm = (W == 0 || A == 0) ? 1 : (A / W) / (S / W) and lw[col] = lw[col] * norm for every column of the group

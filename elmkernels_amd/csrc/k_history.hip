@@ -211,6 +211,39 @@ __global__ __launch_bounds__(256) void k_hist_accumulate_cells(const HistRow* __
   if (threadIdx.x < AGG_CELLS && c < M.ncells && !empty) r.acc[c] = fold(r.op, r.acc[c], g);
 }
 
+// k_hist_accumulate_cells with the rows of cell-row entries (elmk_cell_history_add_row) after the gridded rows: grid (max(column pair
+// blocks, gridded cell blocks, cell pair blocks), nrows + ncrows + the cell-row count).  Row nrows + ncrows + k is rrows[k]: a fp64 row
+// over the output grid's cells that is its own sample - no map, no fill, every cell a sample - folded by pairs as a column row is: the
+// rows and their accumulators start 256-byte aligned and span cld cells, a multiple of 64, so the second cell of a pair stays inside.
+// Launched only while such an entry exists; the two kernels above are what every other context runs.
+__global__ __launch_bounds__(256) void k_hist_accumulate_rows(const HistRow* __restrict__ rows, int nrows, const HistRow* __restrict__ crows,
+                                                              int ncrows, const HistRow* __restrict__ rrows, OGridMap M,
+                                                              unsigned long long* __restrict__ counts, int64_t npairs, int64_t rpairs,
+                                                              unsigned tape_mask)
+{
+  __shared__ double tile[AGG_TILE];
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    for (int t = 0; t < ELMK_HIST_MAX_TAPES; t++)
+      if (tape_mask & (1u << t)) atomicAdd(&counts[t], 1ull);
+  }
+  const int y = (int)blockIdx.y;
+  if (y < nrows || y >= nrows + ncrows) {
+    const bool cellrow = y >= nrows;
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (cellrow ? rpairs : npairs)) return;
+    const HistRow r = cellrow ? rrows[y - nrows - ncrows] : rows[y];
+    fold_pair(r, p);
+    return;
+  }
+  const int64_t c0 = (int64_t)blockIdx.x * AGG_CELLS;
+  if (c0 >= M.ncells) return;
+  const HistRow r = crows[y - nrows];
+  bool empty;
+  const double g = agg_cells(r.src, r.dtype, M, c0, M.ncells, tile, &empty);
+  const int64_t c = c0 + threadIdx.x;
+  if (threadIdx.x < AGG_CELLS && c < M.ncells && !empty) r.acc[c] = fold(r.op, r.acc[c], g);
+}
+
 // cells [cell0, cell0 + m) of one gridded entry's result into out[lev * m + i]: fill for an empty cell, else as k_hist_finalize
 __global__ __launch_bounds__(256) void k_ogrid_finalize(const double* __restrict__ acc, int64_t ld, int op, int64_t count,
                                                         const int64_t* __restrict__ ptr, double fill, int64_t cell0, int64_t m,
@@ -291,6 +324,17 @@ void launch_hist_accumulate_cells(const HistRow* rows, int nrows, const HistRow*
   const unsigned bx = pb > cb ? pb : cb;
   hipLaunchKernelGGL(k_hist_accumulate_cells, dim3(bx, (unsigned)(nrows + ncrows)), dim3(256), 0, st, rows, nrows, crows, M, counts, npairs,
                      tape_mask);
+}
+
+void launch_hist_accumulate_rows(const HistRow* rows, int nrows, const HistRow* crows, int ncrows, const HistRow* rrows, int nrrows,
+                                 const OGridMap& M, unsigned long long* counts, int64_t ncols, unsigned tape_mask, hipStream_t st)
+{
+  if (nrrows <= 0) return;
+  const int64_t npairs = (ncols + 1) / 2, rpairs = (M.ncells + 1) / 2;
+  const unsigned pb = nrows > 0 ? pair_blocks(npairs) : 1u, cb = ncrows > 0 ? cell_blocks(M.ncells) : 1u, rb = pair_blocks(rpairs);
+  const unsigned pc = pb > cb ? pb : cb, bx = pc > rb ? pc : rb;
+  hipLaunchKernelGGL(k_hist_accumulate_rows, dim3(bx, (unsigned)(nrows + ncrows + nrrows)), dim3(256), 0, st, rows, nrows, crows, ncrows, rrows,
+                     M, counts, npairs, rpairs, tape_mask);
 }
 
 void launch_ogrid_finalize(const double* acc, int64_t ld, int nlev, int op, int64_t count, const int64_t* ptr, double fill, int64_t cell0,

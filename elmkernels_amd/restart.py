@@ -18,9 +18,19 @@ the highest among them (OPTIONAL; version 1 without any, byte for byte as before
     altmax_lastyear; one level, F64);
   version 4, soil hydrology (elmk_soil_hydrology_enable): two column sections of kind HYDROLOGY_SECTION (id 0, 1: ZWT, WA; one level, F64).
   version 5, irrigation (elmk_irrigation_enable): two column sections of kind IRRIGATION_SECTION (id 0, 1: RATE, NLEFT; one level, F64).
+  version 6, the routing state (ELMK_OPT_RESTART_CELLS on a context with the routing enabled): CELL sections of kind ROUTING_SECTION (id =
+    ELMK_ROUTE_*: VOLR and QOUT_SUM always, WH and WT with the kinematic-wave scheme, WF with the inundation; one level, F64, extent = the
+    routing's ncells, checksummed with g = the cell as GRIDDED sections are) and, with the river supply limit on, one of kind
+    IRRSUP_SECTION (id = ELMK_IRRSUP_UNMET_SUM); a second 8-byte word after the accumulator-count word holds the routing's call count
+    (int64): parse returns it under "routing_ncalls" (None below version 6), build takes it as `routing_ncalls`.  merge and slice refuse a
+    version-6 image: cell data does not follow a column decomposition.
 History entries over feature rows (elmk_column_history_add_row; include/elmk_restart.def): the entry's `field` holds row_field(family, which), a
 value beyond every field id; its section is an ordinary HISTORY or GRIDDED section of one level and the version does not change.  merge
 and slice carry such entries as they carry every entry; entry_row decodes one.
+History entries over cell rows of the river stages (elmk_cell_history_add_row): `field` holds row_field(ROWS_NFAMILY + cell-row family,
+which), `gridded` is CELL_ROW_ENTRY (2), `ncells` the routing's cells, and the accumulators are a GRIDDED section of one level and that
+extent, checksummed with g = the cell; the version does not change.  merge and slice refuse an image that holds one, as they refuse
+gridded entries: cell data does not follow a column decomposition.
 build derives the version from the sections and `accum` it is given; merge and slice carry the sections as they carry every column section.
 """
 import numpy as np
@@ -31,13 +41,22 @@ VERSION_ACCUM = 2  # of an image with accumulator entries
 VERSION_ALT = 3  # of an image with the active layer thickness rows
 VERSION_HYDROLOGY = 4  # of an image with the soil hydrology rows ZWT and WA
 VERSION_IRRIGATION = 5  # of an image with the irrigation rows RATE and NLEFT
+VERSION_ROUTING = 6  # of an image with the routing state (ELMK_OPT_RESTART_CELLS): cell sections, and the call count after the count word
 FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION, HYDROLOGY_SECTION, IRRIGATION_SECTION = 0, 1, 2, 3, 4, 5, 6  # ELMK_RESTART_*
+ROUTING_SECTION, IRRSUP_SECTION = 7, 8  # (cell sections: extent = the routing's ncells, checksummed with g = the cell)
+CELL_SECTIONS = (GRIDDED, ROUTING_SECTION, IRRSUP_SECTION)
 # the optional kinds and the version that introduced each; from version 2 on the word after the header counts the accumulator entries
 OPTIONAL = ((ACCUM_SECTION, VERSION_ACCUM), (ALT_SECTION, VERSION_ALT), (HYDROLOGY_SECTION, VERSION_HYDROLOGY),
             (IRRIGATION_SECTION, VERSION_IRRIGATION))
+# the optional CELL kinds (the routing state), after the column kinds in an image, and the highest version parse accepts
+OPTIONAL_CELLS = ((ROUTING_SECTION, VERSION_ROUTING), (IRRSUP_SECTION, VERSION_ROUTING))
+MAX_VERSION = VERSION_ROUTING
 ALIGN = 256
 ROW_BASE = 0x40000000  # ELMK_RESTART_ROW_BASE
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # ELMK_ROWS_*
+ROWS_NFAMILY = 5  # ELMK_ROWS_NFAMILY: a cell-row entry's family is ROWS_NFAMILY + CELL_ROWS_*
+CELL_ROWS_ROUTING, CELL_ROWS_SUPPLY = range(2)  # ELMK_CELL_ROWS_*
+GRIDDED_ENTRY, CELL_ROW_ENTRY = 1, 2  # elmk_restart_entry.gridded
 HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("real_bytes", "<u4"), ("schema_hash", "<u8"), ("gcol0", "<i8"),
                    ("ncols", "<i8"), ("tape_count", "<u8", (4,)), ("nentries", "<u4"), ("nsections", "<u4"),
                    ("header_bytes", "<u8"), ("total_bytes", "<u8"), ("header_checksum", "<u8")])
@@ -67,7 +86,7 @@ def entry_row(field):
 
 def _version(sec, na):
     """An image's version: the highest among the optional kinds it holds (ACCUM_SECTION: with na > 0 accumulator entries), else 1."""
-    return max((v for k, v in OPTIONAL if (na > 0 if k == ACCUM_SECTION else bool(np.any(sec["kind"] == k)))), default=VERSION)
+    return max((v for k, v in OPTIONAL + OPTIONAL_CELLS if (na > 0 if k == ACCUM_SECTION else bool(np.any(sec["kind"] == k)))), default=VERSION)
 
 
 def _align(v):
@@ -118,7 +137,7 @@ def parse(image):
     if img.size < HEADER.itemsize:
         raise RestartError("truncated image")
     h = np.frombuffer(img[:HEADER.itemsize].tobytes(), HEADER)[0]
-    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or not VERSION <= int(h["version"]) <= OPTIONAL[-1][1]:
+    if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or not VERSION <= int(h["version"]) <= MAX_VERSION:
         raise RestartError("not a restart image of this format version")
     hb, tb, ne, ns = int(h["header_bytes"]), int(h["total_bytes"]), int(h["nentries"]), int(h["nsections"])
     o = HEADER.itemsize
@@ -129,6 +148,14 @@ def parse(image):
         na, zero = (int(x) for x in np.frombuffer(img[o:o + 8].tobytes(), "<u4"))
         if zero != 0:
             raise RestartError("the word after the accumulator count is not 0")
+        o += 8
+    ncalls = None
+    if int(h["version"]) >= VERSION_ROUTING:
+        if img.size < o + 8:
+            raise RestartError("truncated image")
+        ncalls = int(np.frombuffer(img[o:o + 8].tobytes(), "<i8")[0])
+        if ncalls < 0:
+            raise RestartError("the routing's call count is negative")
         o += 8
     if hb > img.size or tb > img.size or hb < o + ne * ENTRY.itemsize + na * ACCUM.itemsize + ns * SECTION.itemsize:
         raise RestartError("truncated image")
@@ -147,7 +174,7 @@ def parse(image):
         if off + n * dt.itemsize > tb:
             raise RestartError("truncated image")
         data.append(np.frombuffer(img[off:off + n * dt.itemsize].tobytes(), dt).reshape(int(s["nlev"]), int(s["extent"])))
-    return dict(header=h, entries=ent, accum=acc, sections=sec, data=data)
+    return dict(header=h, entries=ent, accum=acc, sections=sec, data=data, routing_ncalls=ncalls)
 
 
 def verify(image):
@@ -158,13 +185,13 @@ def verify(image):
     if header_checksum(img, int(h["header_bytes"])) != int(h["header_checksum"]):
         raise RestartError("header checksum mismatch")
     for s, d in zip(p["sections"], p["data"]):
-        g0 = 0 if int(s["kind"]) == GRIDDED else int(h["gcol0"])
+        g0 = 0 if int(s["kind"]) in CELL_SECTIONS else int(h["gcol0"])
         if checksum(d, g0) != int(s["checksum"]):
             raise RestartError(f"section checksum mismatch (kind {int(s['kind'])}, id {int(s['id'])})")
     return p
 
 
-def build(header, entries, sections, data, accum=None):
+def build(header, entries, sections, data, accum=None, routing_ncalls=0):
     """An image from its parts: offsets, header_bytes, total_bytes, the version (OPTIONAL: by its sections and `accum`) and the
     header checksum are computed; section checksums are taken from sections['checksum']."""
     h = np.array(header, HEADER).reshape(())
@@ -173,7 +200,8 @@ def build(header, entries, sections, data, accum=None):
     sec = np.array(sections, SECTION)
     h["version"] = _version(sec, acc.size)
     word = int(h["version"]) >= VERSION_ACCUM  # (the count word)
-    pre = HEADER.itemsize + (8 if word else 0)
+    calls = int(h["version"]) >= VERSION_ROUTING  # (the routing's call count)
+    pre = HEADER.itemsize + (8 if word else 0) + (8 if calls else 0)
     hb = _align(pre + ent.size * ENTRY.itemsize + acc.size * ACCUM.itemsize + sec.size * SECTION.itemsize)
     off = hb
     for i, d in enumerate(data):
@@ -183,7 +211,9 @@ def build(header, entries, sections, data, accum=None):
     img = np.zeros(off, np.uint8)
     img[:HEADER.itemsize] = np.frombuffer(h.tobytes(), np.uint8)
     if word:
-        img[HEADER.itemsize:pre] = np.frombuffer(np.array([acc.size, 0], "<u4").tobytes(), np.uint8)
+        img[HEADER.itemsize:HEADER.itemsize + 8] = np.frombuffer(np.array([acc.size, 0], "<u4").tobytes(), np.uint8)
+    if calls:
+        img[pre - 8:pre] = np.frombuffer(np.array([routing_ncalls], "<i8").tobytes(), np.uint8)
     o = pre
     img[o:o + ent.nbytes] = np.frombuffer(ent.tobytes(), np.uint8)
     o += ent.nbytes
@@ -198,6 +228,10 @@ def build(header, entries, sections, data, accum=None):
 
 
 def _no_gridded(p, what):
+    if np.any(np.isin(p["sections"]["kind"], (ROUTING_SECTION, IRRSUP_SECTION))):
+        raise RestartError(f"{what}: a version-{VERSION_ROUTING} image holds the routing state; cell data does not follow a column decomposition")
+    if np.any(p["entries"]["gridded"] == CELL_ROW_ENTRY):
+        raise RestartError(f"{what}: the image holds cell-row history entries; cell data does not follow a column decomposition")
     if np.any(p["entries"]["gridded"] != 0):
         raise RestartError(f"{what}: the image holds gridded history entries, which do not survive a change of decomposition")
 

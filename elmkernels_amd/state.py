@@ -21,6 +21,7 @@ DTYPES = {0: np.float64, 1: np.int32, 2: np.uint8, 3: np.uint32}
 LAYOUT_COL_MAJOR, LAYOUT_SOA = 0, 1
 OPT_CF_HALF_WORKGROUPS = 1  # elmk_set_option
 OPT_ALB_STAGED = 2  # elmk_set_option: albedo_snicar as three stages instead of k_alb_tile
+OPT_RESTART_CELLS = 3  # elmk_set_option: the restart image carries the routing state (version 6; restart.VERSION_ROUTING)
 HIST_AVG, HIST_SUM, HIST_MAX, HIST_MIN, HIST_INST = range(5)  # elmk_history_add
 HIST_OPS = {"avg": HIST_AVG, "sum": HIST_SUM, "max": HIST_MAX, "min": HIST_MIN, "inst": HIST_INST}
 HIST_MAX_TAPES, HIST_MAX_ENTRIES = 4, 64
@@ -43,7 +44,9 @@ WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB 
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
                 "irrigation": ROWS_IRRIGATION}
-HYD_NROWS, HYD_NLAYER = 23, 10  # elmk_soil_hydrology_read: the row numbers are hydrology.ZWT .. hydrology.FSAT
+CELL_ROWS_ROUTING, CELL_ROWS_SUPPLY = range(2)  # cell_history_add_row: the cell-row families (ELMK_CELL_ROWS_*)
+CELL_ROW_FAMILIES = {"routing": CELL_ROWS_ROUTING, "supply": CELL_ROWS_SUPPLY}
+HYD_NROWS, HYD_NLAYER = 23, 10 # elmk_soil_hydrology_read: the row numbers are hydrology.ZWT .. hydrology.FSAT
 HYDF_NROWS = 4  # elmk_soil_hydrology_frost_read: hydrology.Q_PERCH_MAX .. hydrology.QFLX_DRAIN_PERCHED
 ALT_ALT, ALT_ALTMAX, ALT_ALTMAX_LASTYEAR = range(3)  # elmk_active_layer_read
 ALT_ROLL_NORTH, ALT_ROLL_SOUTH = 1, 2  # elmk_active_layer_update
@@ -336,7 +339,9 @@ class ELMState:
 
     def set_option(self, option, value):
         """Launch options (elmk_set_option); OPT_CF_HALF_WORKGROUPS: the leaf-temperature iteration in 256-thread workgroups, one per CU;
-        OPT_ALB_STAGED: albedo_snicar's one-layer SNICAR and final stage as launches of their own instead of k_alb_tile."""
+        OPT_ALB_STAGED: albedo_snicar's one-layer SNICAR and final stage as launches of their own instead of k_alb_tile;
+        OPT_RESTART_CELLS: restart_save / restart_load of a context with the routing enabled carry the river stages' state (VOLR,
+        QOUT_SUM and the call count, WH, WT, WF, UNMET_SUM): no routing_init / ..._init call after a load."""
         self._chk(self.lib.elmk_set_option(self.ctx, int(option), int(value)), "set_option")
 
     def set_graph(self, on=True):
@@ -996,6 +1001,20 @@ class ELMState:
                           f"gridded_history_add_row({family}, {which})")
         self._hist_nlev[entry] = 1
         self._hist_cells.add(entry)
+        return entry
+
+    def cell_history_add_row(self, tape, family, which, op):
+        """As history_add over one fp64 cell row of the river stages: family "routing" (which = ROUTE_*: the rows routing_read takes
+        at this moment) or "supply" (IRRSUP_*, while the river supply limit is on), or CELL_ROWS_*.  One level, accumulators over the
+        routing's cells; no map and no fill - every cell is a sample, one without columns in the output grid's map included.
+        history_read of it returns [ncells].  While the entry exists the clears that would free its row, and set_output_grid /
+        clear_output_grid, are refused (history_clear first).  history.fold_cell_rows restates the fold."""
+        fam = CELL_ROW_FAMILIES[family] if isinstance(family, str) else int(family)
+        code = HIST_OPS[op] if isinstance(op, str) else int(op)
+        entry = self._chk(self.lib.elmk_cell_history_add_row(self.ctx, int(tape), fam, int(which), code),
+                          f"cell_history_add_row({family}, {which})")
+        self._hist_nlev[entry] = 1
+        self._hist_cells.add(entry)  # (the routing's cells are the output grid's)
         return entry
 
     # -- restart images (include/elmk.h "restart"; elmkernels_amd/restart.py reads and rewrites them on the host) -------------

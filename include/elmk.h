@@ -182,6 +182,10 @@ int elmk_set_graph(elmk_ctx *ctx, int on);
  *     stage as launches of their own (k_alb_snicar<1>, k_alb_final) that meet through device memory, instead of k_alb_tile, which does
  *     both for a tile of 256 columns in one workgroup and is the default.  The structure an A/B or a test compares k_alb_tile with. */
 enum { ELMK_OPT_CF_HALF_WORKGROUPS = 1, ELMK_OPT_ALB_STAGED = 2 };
+/* Not a launch option: ELMK_OPT_RESTART_CELLS, value != 0: the restart image of a context with the runoff routing enabled carries the
+ * river stages' state (image format, version 6, under "restart"); off, the default, every image is byte for byte what it was.  Refused
+ * while the stream is being captured. */
+enum { ELMK_OPT_RESTART_CELLS = 3 };
 int elmk_set_option(elmk_ctx *ctx, int option, int value);
 int64_t elmk_ncols(const elmk_ctx *ctx);
 int64_t elmk_level_stride(const elmk_ctx *ctx); /* elements between consecutive levels of a device field */
@@ -1262,6 +1266,32 @@ enum { ELMK_ROWS_ALT = 0, ELMK_ROWS_HYDROLOGY = 1, ELMK_ROWS_FROST = 2, ELMK_ROW
 int elmk_column_history_add_row(elmk_ctx *ctx, int tape, int family, int which, int op);
 int elmk_gridded_history_add_row(elmk_ctx *ctx, int tape, int family, int which, int op);
 
+/* ---- cell rows on history tapes -----------------------------------------------------------------
+ * What the river stages produce lives in fp64 rows over the output grid's CELLS, which neither entry above reaches.  This one registers
+ * such a row: as elmk_history_add (the same entry table, ids, ops, tapes, limits and refusals, the fold semantics of "history" word for
+ * word - SUM / AVG from -0.0, MAX / MIN from -/+inf with a sticking NaN, INST the last sample, AVG divided once when read - and still
+ * ONE elmk_history_accumulate launch, in elmk_run's ELMK_RUN_HISTORY stage too, where it follows the routing stage: the sample of step
+ * k is the routing's result of step k), one level, the sample the row's fp64 value in both builds.
+ * family: ELMK_CELL_ROWS_ROUTING (which = ELMK_ROUTE_*: exactly the rows elmk_routing_read accepts at the moment of the call - WH, WT,
+ * QSUR only while the kinematic-wave scheme is on, WF, FLOOD_DEPTH, FLOOD_FRAC only while the floodplain inundation is on) or
+ * ELMK_CELL_ROWS_SUPPLY (which = ELMK_IRRSUP_*, while the river supply limit is on).  Refused as well: an unknown family, a family that
+ * is not enabled, `which` out of range.
+ * Unlike a gridded entry it has no map and no fill: EVERY cell is a sample, a cell without columns in the output grid's map included (a
+ * pass-through reach still has storage and flow).  The accumulators are ncells rounded up to 64 doubles, counted in elmk_device_bytes.
+ * elmk_history_read on such an entry indexes cells (col0, n within ncells) and ignores `layout`; elmk_history_reset, _count and _clear
+ * treat it as every other entry.
+ * While such an entry exists, the call that would free its source row or change ncells is refused with ELMK_E_INVALID
+ * ("elmk_history_clear first") and nothing changes: elmk_routing_clear; elmk_routing_kinematic_clear under entries on WH, WT, QSUR
+ * (and, through the inundation's own interlock, on the flood rows); elmk_routing_inundation_clear; elmk_irrigation_supply_clear;
+ * elmk_set_output_grid and elmk_clear_output_grid.  The _init and _reset_mean calls stay allowed: they write values, not pointers.
+ * Restart: saved and loaded like any history entry; elmk_restart_entry.field = ELMK_RESTART_ROW_FIELD(ELMK_ROWS_NFAMILY + family,
+ * which), gridded = 2, ncells the routing's, the accumulators an ELMK_RESTART_GRIDDED section of extent ncells.  Images of contexts
+ * without such entries are what they were.  The source rows themselves (VOLR, WH, ...) are in the image only under
+ * ELMK_OPT_RESTART_CELLS (version 6, "restart"); else the driver carries them through the _read / _init pairs of the river stages.
+ * Later changes: a per-step series of chosen cells (a gauge hydrograph), cell data across a change of decomposition. */
+enum { ELMK_CELL_ROWS_ROUTING = 0, ELMK_CELL_ROWS_SUPPLY = 1, ELMK_CELL_ROWS_NFAMILY = 2 };
+int elmk_cell_history_add_row(elmk_ctx *ctx, int tape, int family, int which, int op);
+
 /* ---- restart ---------------------------------------------------------------------------------
  * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state
  * and history into a self-describing byte buffer, the image, and another context - in another process, or with another column
@@ -1312,6 +1342,21 @@ int elmk_gridded_history_add_row(elmk_ctx *ctx, int tape, int family, int which,
  * ELMK_IRR_NLEFT, nlev = 1, F64, extent = ncols.  A version-5 image loads only into a context with the same features enabled; sched is
  * not part of it.
  *
+ * Image format, version 6: what a context with the runoff routing enabled (elmk_routing_enable) saves WHILE ELMK_OPT_RESTART_CELLS is on
+ * (elmk_set_option); with the option off such a context saves what it saved before, and the driver carries the river stages' rows by
+ * hand through their _read / _init pairs.  As version 5, with each optional kind present exactly when its feature is enabled; a second
+ * 8-byte word follows the accumulator-count word and holds the routing's call count (int64: elmk_routing_count); and last come the CELL
+ * sections of the routing state, nlev = 1, F64, extent = the routing's ncells, checksummed as ELMK_RESTART_GRIDDED sections are (g = the
+ * cell, not gcol0 + it): kind ELMK_RESTART_ROUTING with id = ELMK_ROUTE_VOLR and ELMK_ROUTE_QOUT_SUM always, ELMK_ROUTE_WH and
+ * ELMK_ROUTE_WT exactly while the kinematic-wave scheme is on and ELMK_ROUTE_WF exactly while the floodplain inundation is on, in that
+ * order; then one section of a second kind, ELMK_RESTART_IRRSUP, id = ELMK_IRRSUP_UNMET_SUM, exactly while the river supply limit is on.
+ * A version-6 image loads only into a context with the option on, the routing enabled with the same ncells and the same scheme,
+ * extension and limit on; a context with the option on and the routing enabled refuses every older image.  After the load the
+ * diagnostic rows (QIN, QOUT, QSUR, FLOOD_DEPTH, FLOOD_FRAC, DEMAND, COMMITTED, RATIO) are zero, as after the _init calls, and the call
+ * count is the image's: the restart order is "enable the river stages, add the history entries, elmk_restart_load", with no _init call.
+ * The network, the parameters and the tables are not part of the image.  elmkernels_amd/restart.py refuses to merge or slice a
+ * version-6 image: cell data does not follow a column decomposition (a later change).
+ *
  * elmk_restart_size: bytes of this context's image.  elmk_restart_save: the image of the context's columns, which are global
  * columns [gcol0, gcol0 + ncols) of the run.  elmk_restart_load: verifies the whole image on the device (every checksum, snl in
  * 0..nlevsno, as elmk_upload) before it writes anything, then writes the fields, the accumulators, the tape counts and the
@@ -1332,12 +1377,14 @@ int elmk_gridded_history_add_row(elmk_ctx *ctx, int tape, int family, int which,
 enum { ELMK_CLASS_PROGNOSTIC = 0, ELMK_CLASS_SURFACE = 1, ELMK_CLASS_FORCING = 2, ELMK_CLASS_DIAGNOSTIC = 3 };
 enum { ELMK_RESTART_FIELD = 0, ELMK_RESTART_HISTORY = 1, ELMK_RESTART_GRIDDED = 2, ELMK_RESTART_ACCUM = 3, ELMK_RESTART_ALT = 4,
        ELMK_RESTART_HYDROLOGY = 5, ELMK_RESTART_IRRIGATION = 6 };
+enum { ELMK_RESTART_ROUTING = 7, ELMK_RESTART_IRRSUP = 8 }; /* the cell sections of version 6 */
 #define ELMK_RESTART_MAGIC "ELMKRST\0"
 #define ELMK_RESTART_VERSION 1u       /* of a context without accumulator entries */
 #define ELMK_RESTART_VERSION_ACCUM 2u /* of a context with accumulator entries */
 #define ELMK_RESTART_VERSION_ALT 3u   /* of a context with the active layer thickness enabled */
 #define ELMK_RESTART_VERSION_HYDROLOGY 4u /* of a context with the soil hydrology enabled */
 #define ELMK_RESTART_VERSION_IRRIGATION 5u /* of a context with the irrigation enabled */
+enum { ELMK_RESTART_VERSION_ROUTING = 6 };  /* of a context with the routing enabled and ELMK_OPT_RESTART_CELLS on */
 typedef struct {
   char magic[8];              /* ELMK_RESTART_MAGIC */
   uint32_t version;           /* ELMK_RESTART_VERSION */

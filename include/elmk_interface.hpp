@@ -436,6 +436,19 @@ class ELMInterface {
     ok(e < 0 ? e : ELMK_OK);
     return e;
   }
+  /* A history entry over one fp64 CELL row of the river stages (elmk.h "cell rows on history tapes"): family ELMK_CELL_ROWS_ROUTING
+   * (which = ELMK_ROUTE_*) or ELMK_CELL_ROWS_SUPPLY (ELMK_IRRSUP_*); every cell is a sample, history_read of it is [ncells].
+   * run(..., routing = true, history = true) samples it after the step's routing.  While it exists the clear of its rows' owner
+   * and the output grid's calls are refused. */
+  int cell_history_add_row(int tape, int family, int which, int op)
+  {
+    const int e = elmk_cell_history_add_row(ctx_, tape, family, which, op);
+    ok(e < 0 ? e : ELMK_OK);
+    return e;
+  }
+  /* ELMK_OPT_RESTART_CELLS (elmk.h "restart", version 6): saveRestart() / loadRestart() carry the river stages' state - VOLR, QOUT_SUM
+   * and the call count, WH, WT, WF, UNMET_SUM - so that a restart needs no routing_init / ..._init call. */
+  void restart_cells(bool on = true) { ok(elmk_set_option(ctx_, ELMK_OPT_RESTART_CELLS, on ? 1 : 0)); }
 
   /* Restart images (elmk.h "restart"): saveRestart() returns the image of the columns, global columns [gcol0, gcol0 + ncols);
    * loadRestart() takes one after setup, geography, maps and the same history and accumulator entries, in place of initialize().
