@@ -33,6 +33,7 @@ constexpr size_t RST_ALIGN = 256;
 constexpr size_t RST_CHUNK = (size_t)64 << 20;  // bytes of image per staging chunk
 constexpr int RST_MAX_PIECES = 8192;            // per chunk (grid.y)
 constexpr uint32_t RST_V_ROUTING = ELMK_RESTART_VERSION_ROUTING;
+constexpr uint32_t RST_V_RESERVOIR = ELMK_RESTART_VERSION_RESERVOIR;
 
 uint64_t fmix64(uint64_t k)
 {
@@ -108,7 +109,9 @@ struct RstKind {
   RstRows (*rows)(Ctx, int i);
   bool cells = false, implied = true;
 };
-// the routing state of version 6 (ELMK_OPT_RESTART_CELLS): the prognostic rows the river stages hold at this moment, in image order
+// the routing state of version 6 (ELMK_OPT_RESTART_CELLS): the prognostic rows the river stages hold at this moment, in image order;
+// with the reservoirs on RES and KRLS follow, and the image is of version 7
+constexpr int ROUTE_STATE_MAX = 7;
 int route_state_rows(Ctx c, int* ids)
 {
   if (!c->restart_cells || !c->route.mem) return 0;
@@ -117,6 +120,7 @@ int route_state_rows(Ctx c, int* ids)
   ids[n++] = ELMK_ROUTE_QOUT_SUM;
   if (c->route.kw_mem) ids[n++] = ELMK_ROUTE_WH, ids[n++] = ELMK_ROUTE_WT;
   if (c->route.fp_mem) ids[n++] = ELMK_ROUTE_WF;
+  if (c->route.dam_mem) ids[n++] = ELMK_ROUTE_RES, ids[n++] = ELMK_ROUTE_KRLS;
   return n;
 }
 const RstKind RST_OPTIONAL[] = {
@@ -130,11 +134,11 @@ const RstKind RST_OPTIONAL[] = {
      [](Ctx c, int i) { return RstRows{ELMK_IRR_RATE + i, 1, c->irr_rows + (size_t)(ELMK_IRR_RATE + i) * (size_t)c->ld}; }},
     {ELMK_RESTART_ROUTING, ELMK_RESTART_VERSION_ROUTING, "the routing state", "elmk_routing_enable with ELMK_OPT_RESTART_CELLS on",
      [](Ctx c) {
-       int ids[5];
+       int ids[ROUTE_STATE_MAX];
        return route_state_rows(c, ids);
      },
      [](Ctx c, int i) {
-       int ids[5];
+       int ids[ROUTE_STATE_MAX];
        const char* why = nullptr;
        (void)route_state_rows(c, ids);
        return RstRows{ids[i], 1, const_cast<double*>(route_row(c, ids[i], &why))};
@@ -143,7 +147,7 @@ const RstKind RST_OPTIONAL[] = {
     {ELMK_RESTART_IRRSUP, ELMK_RESTART_VERSION_ROUTING, "the river supply limit's UNMET_SUM", "elmk_irrigation_supply_enable with ELMK_OPT_RESTART_CELLS on",
      [](Ctx c) { return c->restart_cells && c->route.mem && c->irrsup_rows ? 1 : 0; },
      [](Ctx c, int) { return RstRows{ELMK_IRRSUP_UNMET_SUM, 1, c->irrsup_rows + (size_t)ELMK_IRRSUP_UNMET_SUM * (size_t)c->route.cld}; }, true, false}};
-constexpr uint32_t RST_MAX_VERSION = RST_V_ROUTING;
+constexpr uint32_t RST_MAX_VERSION = RST_V_RESERVOIR;
 static_assert(ELMK_HYD_WA == ELMK_HYD_ZWT + 1 && ELMK_IRR_NLEFT == ELMK_IRR_RATE + 1, "the two rows of the image");
 
 RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
@@ -176,6 +180,7 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
       L.src.push_back(RstSrc{(char*)r.dev, K.cells ? ctx->route.cld : ctx->ld, ELMK_F64, K.cells ? 0 : gcol0, false});
     }
   }
+  if ((L.kinds & (1u << ELMK_RESTART_ROUTING)) && ctx->route.dam_mem) L.version = std::max(L.version, RST_V_RESERVOIR);  // (RES and KRLS)
   // the accumulator table follows the history entries
   L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.version >= 2 ? 8 : 0) + (L.version >= RST_V_ROUTING ? 8 : 0) + L.acc.size() * sizeof(elmk_restart_accum) +
                                 L.ent.size() * sizeof(elmk_restart_entry) + L.sec.size() * sizeof(elmk_restart_section),
@@ -448,6 +453,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   }
   unsigned kinds = word[0] ? 1u << ELMK_RESTART_ACCUM : 0u;
   for (const RstKind& K : RST_OPTIONAL) kinds |= K.implied && K.version == H.version ? 1u << K.kind : 0u;
+  if (H.version == RST_V_RESERVOIR) kinds |= 1u << ELMK_RESTART_ROUTING;  // (version 7 is version 6 with the reservoirs' two sections)
   std::vector<std::pair<int32_t, int64_t>> img_cells, ctx_cells;  // (id, extent) of the cell sections of the routing state
   if (H.version >= ELMK_RESTART_VERSION_HYDROLOGY) {
     const uint64_t at = (uint64_t)(p - in) + (uint64_t)H.nentries * sizeof(elmk_restart_entry) + (uint64_t)word[0] * sizeof(elmk_restart_accum);
@@ -473,8 +479,8 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
     if (S.kind == ELMK_RESTART_ROUTING) ctx_cells.emplace_back(S.id, S.extent);
   if (img_cells != ctx_cells)
     return invalid(ctx, "elmk_restart_load: the image's routing state differs from the context's: another ncells (elmk_routing_enable), or the "
-                        "kinematic-wave scheme (elmk_routing_kinematic_enable) or the floodplain inundation (elmk_routing_inundation_enable) "
-                        "on in one and off in the other");
+                        "kinematic-wave scheme (elmk_routing_kinematic_enable), the floodplain inundation (elmk_routing_inundation_enable) or "
+                        "the reservoirs (elmk_routing_reservoir_enable) on in one and off in the other");
   // a differing entry table; the feature is named where the image holds an entry over a feature row (ELMK_RESTART_ROW_FIELD, include/
   // elmk_restart.def) that the context has not got in that place
   const auto entries_differ = [&]() {
@@ -543,6 +549,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
     HIPCHK(hipMemsetAsync(T.rows, 0, (size_t)ROUTE_NROWS * row, ctx->stream));
     if (T.kw_mem) HIPCHK(hipMemsetAsync(T.kw_rows, 0, (size_t)KW_NROWS * row, ctx->stream));
     if (T.fp_mem) HIPCHK(hipMemsetAsync(T.fp_rows, 0, (size_t)FP_NROWS * row, ctx->stream));
+    if (T.dam_mem) HIPCHK(hipMemsetAsync(T.dam_rows, 0, (size_t)DAM_NROWS * row, ctx->stream));
     if (ctx->irrsup_rows) HIPCHK(hipMemsetAsync(ctx->irrsup_rows, 0, ctx->irrsup_rows.bytes(), ctx->stream));
     ctx->route.ncalls = route_ncalls;
   }

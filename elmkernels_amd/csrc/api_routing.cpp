@@ -3,7 +3,8 @@
 // exactly while the feature is enabled; and the stage's second scheme, kinematic-wave routing (include/elmk.h "kinematic-wave
 // routing"), whose rows WH, WT, QSUR and derived parameters live in a second allocation held exactly while that scheme is on; and that
 // scheme's floodplain inundation (include/elmk.h "floodplain inundation"), whose rows WF, FLOOD_DEPTH, FLOOD_FRAC and tables live in a
-// third, held exactly while the extension is on.
+// third, held exactly while the extension is on; and its reservoirs (include/elmk.h "reservoirs"), whose rows RES, KRLS, RES_TAKE and
+// tables live in a fourth, held exactly while that extension is on.
 #include "elmk_ctx.h"
 
 namespace {
@@ -16,6 +17,11 @@ static_assert(ELMK_KW_NPARAM == KINEMATIC_NPARAM, "the parameter rows of elmk_ma
 // the floodplain inundation's public rows are the rows of its own allocation
 static_assert(ELMK_ROUTE_WF - 7 == FP_WF && ELMK_ROUTE_FLOOD_DEPTH - 7 == FP_DEPTH && ELMK_ROUTE_FLOOD_FRAC - 7 == FP_FRAC, "three rows");
 static_assert(ELMK_FP_NPROF == INUNDATION_NPROF && FP_VB - FP_E == ELMK_FP_NPROF && FP_NTAB - FP_VB == ELMK_FP_NPROF, "the profile of elmk_maps.h");
+
+// the reservoirs' public rows -> the rows of their own allocation (the budget's two rows lie first: elmk_kernels.h)
+constexpr int DAM_ROW_OF[3] = {DAM_RES, DAM_KRLS, DAM_TAKE};
+static_assert(ELMK_ROUTE_RES == 10 && ELMK_ROUTE_KRLS == 11 && ELMK_ROUTE_RES_TAKE == 12, "three rows");
+static_assert(DAM_NTAB == RESERVOIR_NTAB && DAM_TARGET + RESERVOIR_NMONTH == DAM_NTAB, "the tables of elmk_maps.h");
 
 RouteArgs route_args(const elmk_ctx* ctx)
 {
@@ -41,6 +47,20 @@ int inundation_enter(elmk_ctx* ctx, const char* who)
   return ctx->route.fp_mem ? ELMK_OK : invalid(ctx, (std::string(who) + ": the extension is not on (elmk_routing_inundation_enable)").c_str());
 }
 
+int reservoir_enter(elmk_ctx* ctx, const char* who)
+{
+  if (int rc = kinematic_enter(ctx, who)) return rc;
+  return ctx->route.dam_mem ? ELMK_OK : invalid(ctx, (std::string(who) + ": the extension is not on (elmk_routing_reservoir_enable)").c_str());
+}
+
+void reservoir_off(elmk_ctx::Routing& T)
+{
+  T.dam_mem = DevBuf<char>{};
+  T.dam_rows = T.dam_tab = nullptr;
+  T.dam_mstart = nullptr;
+  T.dam_time = 0;
+}
+
 void inundation_off(elmk_ctx::Routing& T)
 {
   T.fp_mem = DevBuf<char>{};
@@ -49,7 +69,7 @@ void inundation_off(elmk_ctx::Routing& T)
 }  // namespace
 
 namespace elmk {
-void route_launch(elmk_ctx* ctx, double dt)
+void route_launch(elmk_ctx* ctx, double dt, bool run)
 {
   const elmk_ctx::Routing& T = ctx->route;
   const CsrMap& M = ctx->ogrid.map;
@@ -58,8 +78,10 @@ void route_launch(elmk_ctx* ctx, double dt)
   const double* const qrunoff = ctx->wb_rows + (size_t)ELMK_WB_QRUNOFF * ld;
   const double* const qirr = T.withdraw ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * ld : nullptr;
   if (T.kw_mem)  // the scheme switch: the kinematic-wave scheme exactly while its memory is held
-    launch_routing_kinematic(route_args(ctx), KinematicArgs{T.kw_rows, T.kw_par}, FloodArgs{T.fp_rows, T.fp_tab}, G, qrunoff, qirr,
-                             ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
+    launch_routing_kinematic(route_args(ctx), KinematicArgs{T.kw_rows, T.kw_par}, FloodArgs{T.fp_rows, T.fp_tab},
+                             DamArgs{T.dam_rows, T.dam_tab, T.dam_mstart, run ? ctx->run.table : nullptr, run ? ctx->run.cursor : nullptr,
+                                     T.dam_time},
+                             G, qrunoff, qirr, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
                              ctx->stream);
   else
     launch_routing(route_args(ctx), G, qrunoff, qirr, dt, ctx->stream);
@@ -69,7 +91,9 @@ const double* route_row(const elmk_ctx* ctx, int which, const char** why)
 {
   const elmk_ctx::Routing& T = ctx->route;
   if (!T.mem) return *why = "runoff routing is not enabled (elmk_routing_enable)", nullptr;
-  if (which < 0 || which > ELMK_ROUTE_FLOOD_FRAC) return *why = "row out of range", nullptr;
+  if (which < 0 || which > ELMK_ROUTE_RES_TAKE) return *why = "row out of range", nullptr;
+  if (which >= ELMK_ROUTE_RES)  // (the reservoirs' rows are in range exactly while they are on)
+    return T.dam_mem ? T.dam_rows + (size_t)DAM_ROW_OF[which - ELMK_ROUTE_RES] * (size_t)T.cld : (*why = "row out of range", nullptr);
   if (which > ELMK_ROUTE_QSUR && !T.fp_mem) return *why = "the floodplain inundation is not on (elmk_routing_inundation_enable)", nullptr;
   if (which > ELMK_ROUTE_QOUT_SUM && !T.kw_mem) return *why = "the kinematic-wave scheme is not on (elmk_routing_kinematic_enable)", nullptr;
   return which > ELMK_ROUTE_QSUR       ? T.fp_rows + (size_t)(which - ELMK_ROUTE_WF) * (size_t)T.cld
@@ -171,11 +195,13 @@ int elmk_routing_read(elmk_ctx* ctx, int which, double* host, int64_t cell0, int
   const char* who = "elmk_routing_read";
   if (int rc = route_enter(ctx, who)) return rc;
   const elmk_ctx::Routing& T = ctx->route;
-  if (which < 0 || which > (T.fp_mem ? ELMK_ROUTE_FLOOD_FRAC : T.kw_mem ? ELMK_ROUTE_QSUR : ELMK_ROUTE_QOUT_SUM))
+  const bool dam_row = which >= ELMK_ROUTE_RES && which <= ELMK_ROUTE_RES_TAKE;
+  if (dam_row ? !T.dam_mem : which < 0 || which > (T.fp_mem ? ELMK_ROUTE_FLOOD_FRAC : T.kw_mem ? ELMK_ROUTE_QSUR : ELMK_ROUTE_QOUT_SUM))
     return invalid(ctx, "elmk_routing_read: unknown row");
   if (int rc = check_range(ctx, who, host, cell0, n, T.ncells, "cell")) return rc;
   if (int rc = refuse_capture(ctx, who)) return rc;
-  const double* const row = which > ELMK_ROUTE_QSUR       ? T.fp_rows + (size_t)(which - ELMK_ROUTE_WF) * (size_t)T.cld
+  const double* const row = dam_row                       ? T.dam_rows + (size_t)DAM_ROW_OF[which - ELMK_ROUTE_RES] * (size_t)T.cld
+                            : which > ELMK_ROUTE_QSUR     ? T.fp_rows + (size_t)(which - ELMK_ROUTE_WF) * (size_t)T.cld
                             : which > ELMK_ROUTE_QOUT_SUM ? T.kw_rows + (size_t)(which - ELMK_ROUTE_WH) * (size_t)T.cld
                                                           : T.rows + (size_t)ROUTE_ROW_OF[which] * (size_t)T.cld;
   if (n > 0) HIPCHK(hipMemcpyAsync(host, row + (size_t)cell0, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -299,6 +325,8 @@ int elmk_routing_kinematic_clear(elmk_ctx* ctx)
   if (!T.kw_mem) return ELMK_OK;
   if (T.fp_mem)  // (the extension's tables are formed from the scheme's RLEN and RWIDTH, and its kernel is the scheme's)
     return invalid(ctx, "elmk_routing_kinematic_clear: the floodplain inundation is on (elmk_routing_inundation_clear first)");
+  if (T.dam_mem)  // (the reservoirs' kernel is the scheme's)
+    return invalid(ctx, "elmk_routing_kinematic_clear: the reservoirs are on (elmk_routing_reservoir_clear first)");
   if (int rc = cellrows_hold(ctx, "elmk_routing_kinematic_clear", ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_WH, ELMK_ROUTE_QSUR)) return rc;
   if (int rc = quiesce(ctx, false)) return rc;
   T.kw_mem = DevBuf<char>{};
@@ -387,6 +415,101 @@ int elmk_routing_inundation_clear(elmk_ctx* ctx)
   if (int rc = cellrows_hold(ctx, "elmk_routing_inundation_clear", ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_WF, ELMK_ROUTE_FLOOD_FRAC)) return rc;
   if (int rc = quiesce(ctx, false)) return rc;
   inundation_off(T);
+  return ELMK_OK;
+}
+
+int elmk_routing_reservoir_enable(elmk_ctx* ctx, const double* cap, const double* target, const double* beta, const int32_t* mstart)
+{
+  const char* who = "elmk_routing_reservoir_enable";
+  if (int rc = kinematic_enter(ctx, who)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  if (T.dam_mem) return invalid(ctx, "elmk_routing_reservoir_enable: already on");
+  if (!cap || !target || !beta || !mstart) return invalid(ctx, "elmk_routing_reservoir_enable: null argument");
+  std::vector<double> tab;
+  std::vector<int32_t> ms;
+  {
+    int64_t cell = -1;
+    const char* const text = reservoir_check(T.ncells, cap, target, beta, mstart, T.cld, &tab, &ms, &cell);
+    if (text && cell >= 0) return invalid_map(ctx, who, (std::string(text) + " at cell " + std::to_string(cell)).c_str());
+    if (int rc = invalid_map(ctx, who, text)) return rc;
+  }
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the form of its moment)
+  const size_t cld = (size_t)T.cld;
+  if (hip_fail(ctx, carve(T.dam_mem, [&](Carve& L) {
+                 L.take(T.dam_rows, (size_t)DAM_NROWS * cld * sizeof(double));
+                 L.take(T.dam_tab, (size_t)DAM_NTAB * cld * sizeof(double));
+                 L.take(T.dam_mstart, cld * sizeof(int32_t));
+               }), "hipMalloc(reservoirs)")) {
+    reservoir_off(T);
+    return ELMK_E_NOMEM;
+  }
+  std::vector<double> one(cld, 1.0);  // KRLS starts at 1.0, as _init leaves it
+  if (hip_fail(ctx, hipMemsetAsync(T.dam_mem, 0, T.dam_mem.bytes(), ctx->stream), "hipMemset(reservoirs)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.dam_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream),
+               "hipMemcpy(reservoir tables)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.dam_mstart, ms.data(), ms.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream),
+               "hipMemcpy(reservoir MSTART)") ||
+      hip_fail(ctx, hipMemcpyAsync(T.dam_rows + DAM_KRLS * cld, one.data(), cld * sizeof(double), hipMemcpyHostToDevice, ctx->stream),
+               "hipMemcpy(reservoir KRLS)") ||
+      hip_fail(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")) {
+    (void)hipStreamSynchronize(ctx->stream);
+    reservoir_off(T);
+    return ELMK_E_HIP;
+  }
+  T.dam_time = 0;
+  return ELMK_OK;
+}
+
+int elmk_routing_reservoir_init(elmk_ctx* ctx, const double* res, const double* krls)
+{
+  const char* who = "elmk_routing_reservoir_init";
+  if (int rc = reservoir_enter(ctx, who)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  const size_t cld = (size_t)T.cld, n = (size_t)T.ncells;
+  std::vector<double> one(cld, 1.0);
+  HIPCHK(hipMemsetAsync(T.dam_rows, 0, (size_t)DAM_NROWS * cld * sizeof(double), ctx->stream));
+  HIPCHK(hipMemcpyAsync(T.dam_rows + DAM_KRLS * cld, krls ? krls : one.data(), (krls ? n : cld) * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (res) HIPCHK(hipMemcpyAsync(T.dam_rows + DAM_RES * cld, res, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  return synced(ctx);  // (`one` lives until here)
+}
+
+int elmk_routing_reservoir_time(elmk_ctx* ctx, int month, int begins)
+{
+  const char* who = "elmk_routing_reservoir_time";
+  if (int rc = reservoir_enter(ctx, who)) return rc;
+  if (month < 0 || month > 11) return invalid(ctx, "elmk_routing_reservoir_time: month outside 0 .. 11");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  ctx->route.dam_time = (int32_t)(month | (begins ? 16 : 0));  // (a kernel argument of the stepwise call; the run's step reads its pad word)
+  return ELMK_OK;
+}
+
+int elmk_routing_reservoir_budget(elmk_ctx* ctx, double* sums)
+{
+  const char* who = "elmk_routing_reservoir_budget";
+  if (int rc = reservoir_enter(ctx, who)) return rc;
+  if (!sums) return invalid(ctx, "elmk_routing_reservoir_budget: null argument");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  const elmk_ctx::Routing& T = ctx->route;
+  launch_min_max_sum(T.dam_rows, T.cld, T.ncells, 2, T.part, T.out, ctx->stream);  // D6 (the routing's partials: every budget synchronises)
+  HIPCHK(hipGetLastError());
+  double mms[6];
+  HIPCHK(hipMemcpyAsync(mms, T.out, sizeof mms, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 2; k++) sums[k] = mms[3 * k + 2];
+  return ELMK_OK;
+}
+
+int elmk_routing_reservoir_clear(elmk_ctx* ctx)
+{
+  if (int rc = enter(ctx)) return rc;
+  if (int rc = refuse_capture(ctx, "elmk_routing_reservoir_clear")) return rc;
+  elmk_ctx::Routing& T = ctx->route;
+  if (!T.dam_mem) return ELMK_OK;
+  if (int rc = cellrows_hold(ctx, "elmk_routing_reservoir_clear", ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_RES, ELMK_ROUTE_RES_TAKE)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;
+  reservoir_off(T);
   return ELMK_OK;
 }
 

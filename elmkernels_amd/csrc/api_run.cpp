@@ -80,7 +80,7 @@ void run_flag_reduce(elmk_ctx* ctx, double)
 }
 void run_routing(elmk_ctx* ctx, double dt)
 {
-  if (ctx->run.flags & ELMK_RUN_ROUTING) route_launch(ctx, dt);
+  if (ctx->run.flags & ELMK_RUN_ROUTING) route_launch(ctx, dt, true);
 }
 void run_active_layer(elmk_ctx* ctx, double)
 {
@@ -315,6 +315,11 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
       const long long t = std::llround((p.decday - 1.0 - (double)p.doy) * 86400.0);
       r.pad |= (int32_t)(((t % 86400) + 86400) % 86400) << RUN_PAD_TOD_SHIFT;
     }
+    // the reservoirs' month and whether the step starts at 00:00 of its first day (the rollover's test), above the time of day
+    if ((flags & ELMK_RUN_ROUTING) && ctx->route.dam_mem) {
+      const int m = reservoir_month(p.doy);
+      r.pad |= (int32_t)(m | (reservoir_month_begins(p.doy, p.decday) ? 16 : 0)) << RUN_PAD_DAM_SHIFT;
+    }
   }
   const int row0 = buf * R.max_steps;
   HIPCHK(hipMemcpyAsync(R.table + row0, rows, (size_t)nsteps * sizeof(RunRow), hipMemcpyHostToDevice, ctx->stream));
@@ -336,7 +341,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
                     (flags & ELMK_RUN_HYDROLOGY) && (bool)ctx->hydf_rows, ctx->hist_version,
                     ctx->accum_version, (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx),
                     (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows, (flags & ELMK_RUN_ROUTING) && ctx->route.withdraw,
-                    (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx) && (bool)ctx->irrsup_rows};
+                    (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx) && (bool)ctx->irrsup_rows,
+                    (flags & ELMK_RUN_ROUTING) && (bool)ctx->route.dam_mem};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;

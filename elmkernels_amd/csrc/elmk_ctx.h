@@ -163,10 +163,11 @@ struct StepKey {
   bool irr_stage = false, wb_irrig = false;  // the irrigation stage is in the step; the water balance takes the irrigation's term
   bool route_withdraw = false;               // the routing stage is in the step (its flag) and subtracts the irrigation's withdrawal
   bool irr_supply = false;                   // the irrigation stage is in the step and the river supply limit's launch follows it
+  bool route_dam = false;                    // the routing stage is in the step and takes the reservoirs' form (its time from the pad word)
   auto tie() const
   {
     return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw,
-                    irr_supply);
+                    irr_supply, route_dam);
   }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
@@ -314,6 +315,14 @@ struct elmk_ctx {
     DevBuf<char> fp_mem;
     double* fp_rows = nullptr;
     double* fp_tab = nullptr;
+    // its reservoirs (elmk_routing_reservoir_*): a fourth allocation with the rows [DAM_NROWS][cld], the host's tables [DAM_NTAB][cld]
+    // and MSTART [cld], held exactly while the extension is on; route_launch takes the DAM form while it is there.  dam_time: the
+    // month | begins << 4 of elmk_routing_reservoir_time, what the stepwise calls read
+    DevBuf<char> dam_mem;
+    double* dam_rows = nullptr;
+    double* dam_tab = nullptr;
+    int32_t* dam_mstart = nullptr;
+    int32_t dam_time = 0;
   } route;
   bool restart_cells = false;  // ELMK_OPT_RESTART_CELLS: the image carries the routing state (version 6)
   bool snowage_set = false;
@@ -492,7 +501,7 @@ constexpr int IRR_NROWS = 3;
 void irr_run_launch(elmk_ctx* ctx, double dt);  // the run step's irrigation stage (api_irrigation.cpp)
 // "<who>: the irrigation's river supply limit is on (elmk_irrigation_supply_clear first)" while it is - what the limit reads stays
 int irrsup_holds(elmk_ctx* ctx, const char* who);
-void route_launch(elmk_ctx* ctx, double dt);    // one call of the runoff routing (api_routing.cpp)
+void route_launch(elmk_ctx* ctx, double dt, bool run = false);  // one call of the runoff routing (api_routing.cpp); run: inside elmk_run's step
 // "<who>: runoff routing is enabled (elmk_routing_clear first)" while it is - what the routing reads stays; with_withdrawal: only while
 // the withdrawal is on
 int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal = false);

@@ -265,9 +265,11 @@ void launch_irrigation_run(const DevState* S, int64_t n, double* rows, const int
                            const int32_t* cursor, hipStream_t st);
 // the irrigation's river supply limit (k_history.hip: k_irrigation_supply, elmk_irrigation_supply_*): S0 - S6 of include/elmk.h "irrigation: river
 // supply limit", one launch behind launch_irrigation / launch_irrigation_run with the same idt.  irr_rows: the irrigation's rows [3][ld];
-// M: the output grid's map (every column in at most one cell); area, volr: the routing's [cld]; sup_rows: the limit's rows [4][cld]
+// M: the output grid's map (every column in at most one cell); area, volr: the routing's [cld]; sup_rows: the limit's rows [4][cld];
+// dam_rows, dam_tab: the reservoirs' rows and tables (below: DAM_*) while they are on - S3 takes D7's form - else null
 void launch_irrigation_supply(int64_t ncols, double* irr_rows, int64_t ld, int idt, const OGridMap& M, const double* area,
-                              const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st);
+                              const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st,
+                              const double* dam_rows = nullptr, const double* dam_tab = nullptr);
 
 // soil hydrology (k_soil_hydrology.hip, elmk_soil_hydrology): one stage over every column; rows = the ELMK_HYD_NROWS fp64 rows of
 // the feature, [row][ld]; frost_rows = the ELMK_HYDF_NROWS rows of the frost-table extension, which select the F' form of the kernel, or
@@ -323,11 +325,29 @@ struct FloodArgs {
   double* rows;
   const double* tab;
 };
+// reservoirs (elmk_routing_reservoir_*; include/elmk.h "reservoirs", D0 - D8): the extension's fp64 rows [DAM_NROWS][cld], the host's
+// tables [DAM_NTAB][cld] (elmk_maps.h: reservoir_check) and MSTART [cld].  The first two rows are the ones launch_min_max_sum reduces
+// for D6; DAM_ENAT is internal: the natural er of a dam cell's coming sub-step (D4), written and read by the cell's own thread.  The
+// call's month and `begins` come as time = month | begins << 4 (elmk_routing) or, run not null, from the bits RUN_PAD_DAM_* of
+// run[*cursor].pad (elmk_run).
+enum { DAM_RES = 0, DAM_TAKE = 1, DAM_KRLS = 2, DAM_ENAT = 3, DAM_NROWS = 4 };
+enum { DAM_CAP = 0, DAM_SMIN = 1, DAM_C85 = 2, DAM_BETA = 3, DAM_TARGET = 4, DAM_NTAB = 16 };
+struct DamArgs {
+  double* rows;
+  const double* tab;
+  const int32_t* mstart;
+  const RunRow* run;
+  const int32_t* cursor;
+  int32_t time;
+};
+constexpr int RUN_PAD_DAM_SHIFT = 25;  // above the time of day's 17 bits: the month in four bits, then `begins`
+constexpr int RUN_PAD_TOD_MASK = (1 << (RUN_PAD_DAM_SHIFT - RUN_PAD_TOD_SHIFT)) - 1;
 // one call: K1 (QIN as R1, QSUR from the hydrology's rows qsurf + qh2osfc, QSUB, the first er) as one launch, then nsub sub-step
 // launches that update WH, WT and VOLR in place; A.kout and ROUTE_VOLR_B are not read.  F.rows not null: the sub-steps take the flood
-// form (I1 - I5)
-void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const OGridMap& M, const double* qrunoff,
-                              const double* qirr, const double* qsurf, const double* qh2osfc, double dt, hipStream_t st);
+// form (I1 - I5).  Dm.rows not null: every launch takes the DAM form (D1 - D4)
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const OGridMap& M,
+                              const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc, double dt,
+                              hipStream_t st);
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

@@ -239,4 +239,70 @@ inline const char* inundation_check(int64_t ncells, const double* rdepth, const 
   return nullptr;
 }
 
+// Reservoirs (elmk_routing_reservoir_enable; include/elmk.h "reservoirs"): cap [ncells], m3, finite and >= 0, 0.0 = no dam;
+// target [12][ncells], m3/s, finite and >= 0; beta [ncells] in [0, 1]; mstart [ncells] in 0 .. 11.  Checks, in this order: the
+// arguments; cap cell by cell; then per dam cell (cap > 0.0) in index order target (month ascending), beta, mstart.  Returns the
+// text, which names the row, and in *cell the first offending cell (-1 where the text is about no cell); the entry point puts
+// " at cell <cell>" behind the text.  nullptr: accepted.
+// For accepted inputs and dev not null, dev holds the tables as the device reads them, [16][ld] with ld >= ncells in the order CAP,
+// SMIN = 0.1 * CAP, C85 = 0.85 * CAP, BETA, TARGET[0 .. 11] (elmk_kernels.h: DAM_*), and mdev MSTART [ld]; padding cells and the
+// unchecked rows of cells without a dam 0.
+constexpr int RESERVOIR_NMONTH = 12, RESERVOIR_NTAB = 16;
+inline const char* reservoir_check(int64_t ncells, const double* cap, const double* target, const double* beta, const int32_t* mstart,
+                                   int64_t ld, std::vector<double>* dev, std::vector<int32_t>* mdev, int64_t* cell)
+{
+  if (cell) *cell = -1;
+  if (ncells < 1 || ncells > INT32_MAX) return "ncells outside 1 .. 2^31-1";
+  if (!cap || !target || !beta || !mstart) return "null argument";
+  const size_t n = (size_t)ncells;
+  const auto at = [cell](const char* what, size_t c) {
+    if (cell) *cell = (int64_t)c;
+    return what;
+  };
+  for (size_t c = 0; c < n; c++)
+    if (!(std::isfinite(cap[c]) && cap[c] >= 0.0)) return at("CAP not finite and >= 0", c);
+  for (size_t c = 0; c < n; c++) {
+    if (!(cap[c] > 0.0)) continue;
+    for (int m = 0; m < RESERVOIR_NMONTH; m++)
+      if (!(std::isfinite(target[(size_t)m * n + c]) && target[(size_t)m * n + c] >= 0.0)) return at("TARGET not finite and >= 0", c);
+    if (!(beta[c] >= 0.0 && beta[c] <= 1.0)) return at("BETA outside [0, 1]", c);
+    if (mstart[c] < 0 || mstart[c] > 11) return at("MSTART outside 0 .. 11", c);
+  }
+  if (dev && mdev) {
+    if (ld < ncells) ld = ncells;
+    const size_t l = (size_t)ld;
+    dev->assign((size_t)RESERVOIR_NTAB * l, 0.0);
+    mdev->assign(l, 0);
+    double* d = dev->data();
+    for (size_t c = 0; c < n; c++) {
+      if (!(cap[c] > 0.0)) continue;
+      d[c] = cap[c];
+      d[l + c] = 0.1 * cap[c];
+      d[2 * l + c] = 0.85 * cap[c];
+      d[3 * l + c] = beta[c];
+      for (int m = 0; m < RESERVOIR_NMONTH; m++) d[(size_t)(4 + m) * l + c] = target[(size_t)m * n + c];
+      (*mdev)[c] = mstart[c];
+    }
+  }
+  return nullptr;
+}
+
+// The reservoirs' calendar, the reference's no-leap year: the month 0 .. 11 of day-of-year doy (0 = 1 January; any other doy is taken
+// modulo 365), and whether a step with (doy, decday) starts at 00:00 of the first day of its month: the active layer's rollover test,
+// decday == doy + 1.0, on the first doy of each month.
+inline int reservoir_month(int64_t doy)
+{
+  static const int first[13] = {0, 31, 59, 90, 120, 151, 181, 212, 243, 273, 304, 334, 365};
+  const int d = (int)(((doy % 365) + 365) % 365);
+  int m = 0;
+  while (d >= first[m + 1]) m++;
+  return m;
+}
+inline bool reservoir_month_begins(int64_t doy, double decday)
+{
+  static const int first[12] = {0, 31, 59, 90, 120, 151, 181, 212, 243, 273, 304, 334};
+  if (doy < 0 || doy > 364 || !(decday == (double)doy + 1.0)) return false;
+  return first[reservoir_month(doy)] == (int)doy;
+}
+
 }  // namespace elmk

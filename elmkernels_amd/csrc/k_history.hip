@@ -379,10 +379,19 @@ __device__ __forceinline__ void sup_st(gptr<double> p, double v)
 }
 }  // namespace
 
+// D7 (include/elmk.h "reservoirs"): while the reservoirs are on, a dam cell's storage above SMIN counts as available beside the channel's
+template <bool DAM>
+struct SupDam {};  // the plain form takes nothing: its kernel arguments, instructions and registers stay what they were
+template <>
+struct SupDam<true> {
+  gptr<const double> res, smin, cap;  // [cld] each
+};
+
 // grid (ceil(ncells / SUP_CELLS)); irr = the irrigation's rows [3][ld], sup = the limit's rows [4][cld]
+template <bool DAM = false>
 __global__ __launch_bounds__(SUP_THREADS) void k_irrigation_supply(gptr<double> irr, int64_t ld, int idt, int nspd, OGridMap M,
                                                                    gptr<const double> area, gptr<const double> volr, double thr,
-                                                                   gptr<double> sup, int64_t cld)
+                                                                   gptr<double> sup, int64_t cld, SupDam<DAM> dm)
 {
   __shared__ double tile_d[SUP_TILE];
   __shared__ double tile_c[SUP_TILE];
@@ -436,7 +445,14 @@ __global__ __launch_bounds__(SUP_THREADS) void k_irrigation_supply(gptr<double> 
     const int64_t c = c0 + t;
     const double ar = area[c];
     const double Vd = (D * 0.001) * ar, Vc = (C * 0.001) * ar;  // S3
-    const double a = volr[c] * (1.0 - thr) - Vc;
+    double a = volr[c] * (1.0 - thr);
+    if constexpr (DAM) {
+      if (dm.cap[c] > 0.0) {  // D7
+        const double r = dm.res[c] - dm.smin[c];
+        a = a + (r > 0.0 ? r : 0.0);
+      }
+    }
+    a = a - Vc;
     const double avail = a > 0.0 ? a : 0.0;
     const double ratio = Vd > avail ? avail / Vd : 1.0;  // S4
     ratio_s[t] = ratio;
@@ -467,13 +483,20 @@ __global__ __launch_bounds__(SUP_THREADS) void k_irrigation_supply(gptr<double> 
 }
 
 void launch_irrigation_supply(int64_t ncols, double* irr_rows, int64_t ld, int idt, const OGridMap& M, const double* area,
-                              const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st)
+                              const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st, const double* dam_rows,
+                              const double* dam_tab)
 {
   if (ncols <= 0 || M.ncells <= 0) return;
   const int nspd = (14400 + (idt - 1)) / idt;
-  hipLaunchKernelGGL(k_irrigation_supply, dim3((unsigned)((M.ncells + SUP_CELLS - 1) / SUP_CELLS)), dim3(SUP_THREADS), 0, st,
-                     (gptr<double>)irr_rows, ld, idt, nspd, M, (gptr<const double>)area, (gptr<const double>)volr, thr,
-                     (gptr<double>)sup_rows, cld);
+  const dim3 grid((unsigned)((M.ncells + SUP_CELLS - 1) / SUP_CELLS));
+  if (dam_rows)
+    hipLaunchKernelGGL(k_irrigation_supply<true>, grid, dim3(SUP_THREADS), 0, st, (gptr<double>)irr_rows, ld, idt, nspd, M,
+                       (gptr<const double>)area, (gptr<const double>)volr, thr, (gptr<double>)sup_rows, cld,
+                       SupDam<true>{(gptr<const double>)(dam_rows + DAM_RES * cld), (gptr<const double>)(dam_tab + DAM_SMIN * cld),
+                                    (gptr<const double>)(dam_tab + DAM_CAP * cld)});
+  else
+    hipLaunchKernelGGL(k_irrigation_supply<false>, grid, dim3(SUP_THREADS), 0, st, (gptr<double>)irr_rows, ld, idt, nspd, M,
+                       (gptr<const double>)area, (gptr<const double>)volr, thr, (gptr<double>)sup_rows, cld, SupDam<false>{});
 }
 
 }  // namespace elmk

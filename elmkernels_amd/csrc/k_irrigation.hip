@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void k_irrigation(const DevState* __restrict__
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ld = S->ld;
   if (c >= S->ncols) return;
-  if constexpr (RUN) tod = rows[*cursor].pad >> RUN_PAD_TOD_SHIFT;
+  if constexpr (RUN) tod = (rows[*cursor].pad >> RUN_PAD_TOD_SHIFT) & RUN_PAD_TOD_MASK;  // (above it: the reservoirs' month)
   const gptr<double> rate_p = irr + (int64_t)ELMK_IRR_RATE * ld + c, nleft_p = irr + (int64_t)ELMK_IRR_NLEFT * ld + c,
                      qirr_p = irr + (int64_t)ELMK_IRR_QFLX_IRRIG * ld + c;
 

@@ -15,7 +15,7 @@
 // one row less to write and read.  A cell reads 8 (storage) + 8 (KOUT) + 8 (QIN) + 4 npad (map) + 16 per upstream cell and, past the
 // first sub-step, 8 (the flow sum), and writes 16.  The unit carries no nontemporal hint: none has been measured for it.
 // The second scheme of the stage, kinematic-wave routing (k_kinematic_prep, k_kinematic_step), follows the linear one below, with its
-// floodplain inundation (k_kinematic_step's FLOOD form).
+// floodplain inundation (k_kinematic_step's FLOOD form) and its reservoirs (both kernels' DAM form).
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
 
@@ -201,13 +201,73 @@ __device__ __forceinline__ double kw_chan(double w, double len, double wid, doub
 }
 }  // namespace
 
-// K1: QIN as k_routing_qin, QSUR from the hydrology's two surface rows in the same order, QSUB, and the er of the first sub-step
-template <bool WITHDRAW>
+// ---- reservoirs (include/elmk.h "reservoirs", D0 - D8; elmkernels_amd/routing.py: reservoir_prep, reservoir_regulate) ---------------
+// The DAM form of both kernels: a dam stands at the outlet of a cell with CAP > 0.0 and regulates the main channel's er where K4 forms
+// it.  Every cell of the form reads CAP, 8 bytes; a dam cell reads SMIN, BETA, TARGET[m], KRLS and RES and writes RES and its natural
+// er (the row DAM_ENAT, which its own thread reads back in the coming sub-step: D4), 56 bytes, all behind the cell's own condition.
+// The month and `begins` are uniform over the launch: an argument, or the bits of the run row's pad word.
+// D4's other choice, evaluating K4 again from the VOLR of the sub-step's start instead of keeping the row, is -DELMK_DAM_REEVAL (make
+// variant V=damreeval VFLAGS=-DELMK_DAM_REEVAL): the same bits, measured by tests/tools/cost_routing_reservoir.py.
+template <bool DAM>
+struct DamRows {};  // the plain form takes nothing: its kernel arguments, instructions and registers stay what they were
+template <>
+struct DamRows<true> {
+  gptr<double> rows;           // [DAM_NROWS][cld]
+  gptr<const double> tab;      // [DAM_NTAB][cld]
+  gptr<const int32_t> mstart;  // [cld]
+  const RunRow* run;
+  const int32_t* cursor;
+  int32_t time;
+  double dt;
+};
+
+namespace {
+__device__ __forceinline__ int32_t dam_time(const DamRows<true>& dm)
+{
+  const int32_t t = dm.run ? dm.run[*dm.cursor].pad >> RUN_PAD_DAM_SHIFT : dm.time;
+  const int32_t m = t & 15;
+  return (m > 11 ? 11 : m) | (t & 16);  // (the host hands 0 .. 11: TARGET's row stays inside the table whatever the word holds)
+}
+// D3 for a dam cell; e: the natural er.  Stores RES and DAM_ENAT, returns the regulated flow (a NaN as the canonical one)
+__device__ __forceinline__ double dam_regulate(double e, double res, double krls, double cap, int32_t m, const DamRows<true>& dm,
+                                               int64_t cld, int64_t c, double dts)
+{
+  const double smin = dm.tab[DAM_SMIN * cld + c], beta = dm.tab[DAM_BETA * cld + c], tgt = dm.tab[(DAM_TARGET + m) * cld + c];
+  double q = beta * (krls * tgt) + (1.0 - beta) * e;
+  const double qmin = 0.1 * e;
+  if (q < qmin) q = qmin;
+  double eo;
+  if (q > e) {
+    const double a = res - smin;
+    double x = q - e;
+    const double lim = a > 0.0 ? a / dts : 0.0;
+    if (x > lim) x = lim;
+    eo = e + x;
+  } else {
+    eo = q;
+  }
+  double s = res + (e - eo) * dts;
+  if (s > cap) {
+    eo = eo + (s - cap) / dts;
+    s = cap;
+  }
+  route_st(dm.rows + (DAM_RES * cld + c), s);
+#ifndef ELMK_DAM_REEVAL
+  dm.rows[DAM_ENAT * cld + c] = e;
+#endif
+  if (eo != eo) eo = __builtin_nan("");
+  return eo;
+}
+}  // namespace
+
+// K1: QIN as k_routing_qin, QSUR from the hydrology's two surface rows in the same order, QSUB, and the er of the first sub-step.
+// DAM: D1, D2 and the first sub-step's D3 for the dam cells
+template <bool WITHDRAW, bool DAM = false>
 __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
                                                         gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
                                                         gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
                                                         gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
-                                                        gptr<double> er, int64_t ncells, int64_t cld, double dts)
+                                                        gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<DAM> dm)
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncells) return;
@@ -225,9 +285,38 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
     const double z = wp * (qsurf[k] + qh2osfc[k]);
     s = p == p0 ? z : s + z;
   }
+  [[maybe_unused]] const double rn = r;
   if constexpr (WITHDRAW) r = r - i;
   const double ar = area[c];
   const double q = (r * 0.001) * ar, qs = (s * 0.001) * ar;
+  if constexpr (DAM) {
+    const double cap = dm.tab[DAM_CAP * cld + c];
+    if (cap > 0.0) {  // D0
+      const int32_t t = dam_time(dm), m = t & 15;
+      double res = dm.rows[DAM_RES * cld + c], krls = dm.rows[DAM_KRLS * cld + c];
+      if ((t & 16) && m == dm.mstart[c]) {  // D1
+        krls = res / dm.tab[DAM_C85 * cld + c];
+        route_st(dm.rows + (DAM_KRLS * cld + c), krls);
+      }
+      double take = 0.0, qd = q;
+      if constexpr (WITHDRAW) {  // D2
+        const double iv = (i * 0.001) * ar;
+        const double want = iv * dm.dt;
+        const double a = res - dm.tab[DAM_SMIN * cld + c];
+        const double avail = a > 0.0 ? a : 0.0;
+        take = want > avail ? avail : want;
+        res = res - take;
+        qd = (rn * 0.001) * ar - (iv - take / dm.dt);
+      }
+      route_st(dm.rows + (DAM_TAKE * cld + c), take);
+      route_st(qin + c, qd);
+      route_st(qsur + c, qs);
+      route_st(qsub + c, qd - qs);
+      const double e = kw_chan(volr[c], par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+      er[c] = dam_regulate(e, res, krls, cap, m, dm, cld, c, dts);  // D3
+      return;
+    }
+  }
   route_st(qin + c, q);
   route_st(qsur + c, qs);
   route_st(qsub + c, q - qs);
@@ -301,13 +390,14 @@ __device__ __forceinline__ void fp_exchange(double& v, double& wf, double& h, do
 }  // namespace
 
 // K3 - K7: one sub-step.  er_old: the flows of the sub-step's start; er_new: those of its end (not written by the LAST one).  FIRST and
-// LAST as k_routing_step's.  FLOOD: the flood form, I1 - I5.
-template <int NPAD, bool FIRST, bool LAST, bool FLOOD>
+// LAST as k_routing_step's.  FLOOD: the flood form, I1 - I5.  DAM: a dam cell's K6 subtracts its natural er (D4), and the er it forms
+// is regulated (D3).
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM = false>
 __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
                                                         gptr<double> er_new, gptr<const double> par, gptr<const double> area,
                                                         gptr<const int32_t> up, gptr<const double> qsur, gptr<const double> qsub,
                                                         gptr<double> qout, gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts,
-                                                        double dnsub, FloodRows<FLOOD> fl)
+                                                        double dnsub, FloodRows<FLOOD> fl, DamRows<DAM> dm)
 {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncells) return;
@@ -329,7 +419,17 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
     if (u[p] >= 0) fin = fin + eu[p];
   route_st(wh_row + c, wh + (qs - eh) * dts);
   route_st(wt_row + c, wt + ((eh - et) + qb) * dts);
-  double vn = v + ((fin - er) + et) * dts;
+  double en = er;
+  [[maybe_unused]] double cap = 0.0;
+  if constexpr (DAM) {
+    cap = dm.tab[DAM_CAP * cld + c];
+#ifdef ELMK_DAM_REEVAL
+    if (cap > 0.0) en = kw_chan(v, par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+#else
+    if (cap > 0.0) en = dm.rows[DAM_ENAT * cld + c];  // D4: er is what left the dam, en what left the channel
+#endif
+  }
+  double vn = v + ((fin - en) + et) * dts;
   if constexpr (FLOOD) {
     const double vc = fl.tab[FP_VC * cld + c];
     double wf = fl.rows[FP_WF * cld + c], h = 0.0, f = 0.0;
@@ -351,64 +451,96 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
     route_st(qout_sum + c, qout_sum[c] + mean);
   } else {
     route_st(qout + c, qacc);
-    er_new[c] = kw_chan(vn, par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+    double e = kw_chan(vn, par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+    if constexpr (DAM)
+      if (cap > 0.0) e = dam_regulate(e, dm.rows[DAM_RES * cld + c], dm.rows[DAM_KRLS * cld + c], cap, dam_time(dm) & 15, dm, cld, c, dts);
+    er_new[c] = e;
   }
 }
 
 namespace {
-template <int NPAD, bool FIRST, bool LAST, bool FLOOD>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const double* er_old, double* er_new, double dts,
-                    hipStream_t st)
+DamRows<true> dam_rows(const DamArgs& Dm, double dt)
+{
+  return DamRows<true>{(gptr<double>)Dm.rows, (gptr<const double>)Dm.tab, (gptr<const int32_t>)Dm.mstart, Dm.run, Dm.cursor, Dm.time, dt};
+}
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM>
+void launch_kw_form(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
+                    double dts, hipStream_t st)
 {
   FloodRows<FLOOD> fl;
   if constexpr (FLOOD) fl = FloodRows<true>{(gptr<double>)F.rows, (gptr<const double>)F.tab};
-  hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST, FLOOD>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
+  DamRows<DAM> dm;
+  if constexpr (DAM) dm = dam_rows(Dm, dts * (double)A.nsub);
+  hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST, FLOOD, DAM>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
                      (gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld),
                      (gptr<double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)er_old, (gptr<double>)er_new,
                      (gptr<const double>)K.par, (gptr<const double>)A.area, (gptr<const int32_t>)A.up,
                      (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<const double>)(K.rows + KW_QSUB * A.cld),
                      (gptr<double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts,
-                     (double)A.nsub, fl);
+                     (double)A.nsub, fl, dm);
+}
+// the form of the sub-step: the DAM form exactly while the reservoirs' rows are there
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD>
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
+                    double dts, hipStream_t st)
+{
+  if (Dm.rows) launch_kw_form<NPAD, FIRST, LAST, FLOOD, true>(A, K, F, Dm, er_old, er_new, dts, st);
+  else launch_kw_form<NPAD, FIRST, LAST, FLOOD, false>(A, K, F, Dm, er_old, er_new, dts, st);
 }
 template <int NPAD, bool FLOOD>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const double* er_old, double* er_new, double dts,
-                    bool first, bool last, hipStream_t st)
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
+                    double dts, bool first, bool last, hipStream_t st)
 {
-  if (first && last) launch_kw_step<NPAD, true, true, FLOOD>(A, K, F, er_old, er_new, dts, st);
-  else if (first) launch_kw_step<NPAD, true, false, FLOOD>(A, K, F, er_old, er_new, dts, st);
-  else if (last) launch_kw_step<NPAD, false, true, FLOOD>(A, K, F, er_old, er_new, dts, st);
-  else launch_kw_step<NPAD, false, false, FLOOD>(A, K, F, er_old, er_new, dts, st);
+  if (first && last) launch_kw_step<NPAD, true, true, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
+  else if (first) launch_kw_step<NPAD, true, false, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
+  else if (last) launch_kw_step<NPAD, false, true, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
+  else launch_kw_step<NPAD, false, false, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
 }
 template <bool FLOOD>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const double* er_old, double* er_new, double dts,
-                    bool first, bool last, hipStream_t st)
+void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
+                    double dts, bool first, bool last, hipStream_t st)
 {
   switch (A.npad) {
-    case 1: launch_kw_step<1, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
-    case 2: launch_kw_step<2, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
-    case 4: launch_kw_step<4, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
-    default: launch_kw_step<8, FLOOD>(A, K, F, er_old, er_new, dts, first, last, st); break;
+    case 1: launch_kw_step<1, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
+    case 2: launch_kw_step<2, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
+    case 4: launch_kw_step<4, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
+    default: launch_kw_step<8, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
   }
+}
+template <bool WITHDRAW, bool DAM>
+void launch_kw_prep(const RouteArgs& A, const KinematicArgs& K, const DamArgs& Dm, const OGridMap& M, const double* qrunoff,
+                    const double* qirr, const double* qsurf, const double* qh2osfc, double* er, double dt, double dts, hipStream_t st)
+{
+  DamRows<DAM> dm;
+  if constexpr (DAM) dm = dam_rows(Dm, dt);
+  hipLaunchKernelGGL((k_kinematic_prep<WITHDRAW, DAM>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
+                     (gptr<const int64_t>)M.ptr, (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff,
+                     (gptr<const double>)qirr, (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
+                     (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
+                     (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
+                     (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)er, A.ncells, A.cld, dts, dm);
 }
 }  // namespace
 
-void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const OGridMap& M, const double* qrunoff,
-                              const double* qirr, const double* qsurf, const double* qh2osfc, double dt, hipStream_t st)
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const OGridMap& M,
+                              const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc, double dt,
+                              hipStream_t st)
 {
   if (A.ncells <= 0) return;
-  const dim3 grid((unsigned)((A.ncells + 255) / 256)), block(256);
   const double dts = dt / (double)A.nsub;  // K0
   double *src = K.rows + KW_ER_A * A.cld, *dst = K.rows + KW_ER_B * A.cld;
-  const auto prep = qirr ? k_kinematic_prep<true> : k_kinematic_prep<false>;  // (I6: the same launch in the flood form)
-  hipLaunchKernelGGL(prep, grid, block, 0, st, (gptr<const int64_t>)M.ptr, (gptr<const int32_t>)M.col, (gptr<const double>)M.w,
-                     (gptr<const double>)qrunoff, (gptr<const double>)qirr, (gptr<const double>)qsurf, (gptr<const double>)qh2osfc,
-                     (gptr<const double>)A.area, (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
-                     (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
-                     (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts);
+  // (I6: the same launch in the flood form)
+  if (Dm.rows) {
+    if (qirr) launch_kw_prep<true, true>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
+    else launch_kw_prep<false, true>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
+  } else {
+    if (qirr) launch_kw_prep<true, false>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
+    else launch_kw_prep<false, false>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
+  }
   for (int s = 0; s < A.nsub; s++) {
     const bool first = s == 0, last = s == A.nsub - 1;
-    if (F.rows) launch_kw_step<true>(A, K, F, src, dst, dts, first, last, st);
-    else launch_kw_step<false>(A, K, F, src, dst, dts, first, last, st);
+    if (F.rows) launch_kw_step<true>(A, K, F, Dm, src, dst, dts, first, last, st);
+    else launch_kw_step<false>(A, K, F, Dm, src, dst, dts, first, last, st);
     double* const t = src;
     src = dst;
     dst = t;

@@ -181,13 +181,15 @@ def _canon(v):
     return np.where(v != v, _NAN, v)
 
 
-def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx_irrig=None):
+def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx_irrig=None, dam=None):
     """S0 - S6 on the host: the launch that follows elmk_irrigation while the limit is on.
 
     ptr, col, w: the output grid's CSR map (every column in at most one cell); area, volr: the routing's [ncells]; rate, nleft: the
     irrigation's rows after this step's irrigation.step ([ncols]); idt: the step in whole seconds; thr: the threshold; unmet_sum:
     [ncells], the prognostic row; qflx_irrig: the irrigation's QFLX_IRRIG row of this step ([ncols]; None: zeros) - the water applied
-    in this step, which the routing has not yet taken out of volr (S2's y).  Returns (rate_out, rows): rate_out float64 [ncols], rows float64 [SUPPLY_NROWS, ncells] in the order
+    in this step, which the routing has not yet taken out of volr (S2's y).  dam = (tab, res): the reservoirs are on (include/elmk.h
+    "reservoirs", D7; tab: routing.reservoir_tables, res: the RES row [ncells]) - a dam cell's storage above SMIN counts as available
+    beside the channel's; None: S3 as it is.  Returns (rate_out, rows): rate_out float64 [ncols], rows float64 [SUPPLY_NROWS, ncells] in the order
     DEMAND, COMMITTED, RATIO, UNMET_SUM.  Nothing is changed in place."""
     from . import regrid
 
@@ -211,7 +213,11 @@ def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx
         C = regrid.apply_aggregate(ptr, col, w, np.where(~checks & (nleft > 0.0), x, 0.0) + y, 0.0)
         Vd = (D * 0.001) * area                                      # S3
         Vc = (C * 0.001) * area
-        a = volr * (1.0 - thr) - Vc
+        a = volr * (1.0 - thr)
+        if dam is not None:  # D7
+            r = np.asarray(dam[1], dtype=np.float64).reshape(-1) - dam[0]["SMIN"]
+            a = np.where(dam[0]["DAM"], a + np.where(r > 0.0, r, 0.0), a)
+        a = a - Vc
         avail = np.where(a > 0.0, a, 0.0)
         ratio = np.where(Vd > avail, avail / np.where(Vd > avail, Vd, 1.0), 1.0)  # S4 (the division only where it is taken)
         cell_of = np.full(rate.size, -1, np.int64)                   # S5: a column in no cell is not limited

@@ -24,6 +24,9 @@ the highest among them (OPTIONAL; version 1 without any, byte for byte as before
     IRRSUP_SECTION (id = ELMK_IRRSUP_UNMET_SUM); a second 8-byte word after the accumulator-count word holds the routing's call count
     (int64): parse returns it under "routing_ncalls" (None below version 6), build takes it as `routing_ncalls`.  merge and slice refuse a
     version-6 image: cell data does not follow a column decomposition.
+  version 7, the routing state of a context with the reservoirs on (elmk_routing_reservoir_enable): version 6 with two more
+    ROUTING_SECTIONs, ELMK_ROUTE_RES and ELMK_ROUTE_KRLS, after WF.  The device saves and loads it; this module does not read it:
+    parse, and with it verify, merge and slice, refuse a version-7 image by its version word, so it is never merged or sliced.
 History entries over feature rows (elmk_column_history_add_row; include/elmk_restart.def): the entry's `field` holds row_field(family, which), a
 value beyond every field id; its section is an ordinary HISTORY or GRIDDED section of one level and the version does not change.  merge
 and slice carry such entries as they carry every entry; entry_row decodes one.
@@ -42,6 +45,7 @@ VERSION_ALT = 3  # of an image with the active layer thickness rows
 VERSION_HYDROLOGY = 4  # of an image with the soil hydrology rows ZWT and WA
 VERSION_IRRIGATION = 5  # of an image with the irrigation rows RATE and NLEFT
 VERSION_ROUTING = 6  # of an image with the routing state (ELMK_OPT_RESTART_CELLS): cell sections, and the call count after the count word
+VERSION_RESERVOIR = 7  # ... of a context with the reservoirs on: version 6 plus the ROUTING_SECTIONs RES and KRLS; refused by parse
 FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION, HYDROLOGY_SECTION, IRRIGATION_SECTION = 0, 1, 2, 3, 4, 5, 6  # ELMK_RESTART_*
 ROUTING_SECTION, IRRSUP_SECTION = 7, 8  # (cell sections: extent = the routing's ncells, checksummed with g = the cell)
 CELL_SECTIONS = (GRIDDED, ROUTING_SECTION, IRRSUP_SECTION)
@@ -137,6 +141,9 @@ def parse(image):
     if img.size < HEADER.itemsize:
         raise RestartError("truncated image")
     h = np.frombuffer(img[:HEADER.itemsize].tobytes(), HEADER)[0]
+    if bytes(h["magic"]).ljust(8, b"\0") == MAGIC and int(h["version"]) == VERSION_RESERVOIR:
+        raise RestartError("not a restart image of a format version this module reads: version 7 holds the routing state of a context "
+                           "with reservoirs, cell data that is neither merged nor sliced")
     if bytes(h["magic"]).ljust(8, b"\0") != MAGIC or not VERSION <= int(h["version"]) <= MAX_VERSION:
         raise RestartError("not a restart image of this format version")
     hb, tb, ne, ns = int(h["header_bytes"]), int(h["total_bytes"]), int(h["nentries"]), int(h["nsections"])

@@ -32,6 +32,17 @@ Its floodplain inundation (include/elmk.h "floodplain inundation"; k_kinematic_s
 
     tab = inundation_tables(area, params, rdepth, eprof)
     wh, wt, volr, qout, wf, depth, frac = kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, flood=(tab, wf))
+
+Its reservoirs (include/elmk.h "reservoirs"; the DAM form of both kernels), after S.routing_kinematic_enable:
+
+    target, beta, mstart = reservoir_targets(mean_inflow, mean_demand, cap)   # or the driver's own
+    S.routing_reservoir_enable(cap, target, beta, mstart)
+    S.routing_reservoir_init(res_from_restart, krls_from_restart)
+    S.routing_reservoir_time(month_of_doy(doy), month_begins(doy, decday)); S.routing(dt)   # S.run(..., RUN_ROUTING) derives the time
+    res, take = S.routing_read(RES), S.routing_read(RES_TAKE)
+
+    dam = {"tab": reservoir_tables(cap, target, beta, mstart), "res": res, "krls": krls, "month": m, "begins": b}
+    wh, wt, volr, qout, res, krls, take, qin = kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, dam=dam)
 """
 import numpy as np
 
@@ -262,13 +273,27 @@ def qsur_from_rows(ptr, col, w, qflx_surf, qflx_h2osfc_surf, area):
         return _canon((s * 0.001) * np.asarray(area, dtype=np.float64).reshape(-1))
 
 
-def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True, flood=None):
+def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True, flood=None, dam=None):
     """One elmk_routing with the scheme on, on the host: K0, K2 - K7.  wh, wt, volr, qin, qsur, area: float64 [ncells]; params
     [11, ncells]; up: upstream_map(down).  Returns (wh_new, wt_new, volr_new, qout).  in_place and cap are the wrong variants the host
     tests hold their checks against, as call's: in_place updates the cells one after another in index order, the upstream flows taken
     from main-channel storages already updated in the sub-step; cap=False takes every flow without the cap v / dts.
     flood=(tables, wf): the flood form ("floodplain inundation", I1 - I6) with inundation_tables' tables and the floodplain storage wf
-    [ncells]; returns (wh_new, wt_new, volr_new, qout, wf_new, flood_depth, flood_frac)."""
+    [ncells]; returns (wh_new, wt_new, volr_new, qout, wf_new, flood_depth, flood_frac).
+    dam: the DAM form ("reservoirs", D0 - D5), a dict with "tab" (reservoir_tables), "res" and "krls" [ncells], "month" (0 .. 11) and
+    "begins"; optional "withdrawal" = (rn, i), R1's aggregates of QRUNOFF and QFLX_IRRIG [ncells] (the routing's withdrawal is on: D2;
+    qin is then K1's QIN with the withdrawal), and "variant", one of the wrong variants of DAM_VARIANTS.  The result grows by
+    (res_new, krls_new, res_take, qin_new) behind the flood rows, if any."""
+    if dam is not None:
+        if in_place:
+            raise ValueError("kinematic_call: dam with in_place")
+        dtab, dvar = dam["tab"], dam.get("variant")
+        if dvar is not None and dvar not in DAM_VARIANTS:
+            raise ValueError(f"kinematic_call: unknown variant {dvar!r}")
+        res, krls, take, qin = reservoir_prep(dam["res"], dam["krls"], qin, area, dtab, dam["month"], dam["begins"], dt,
+                                              dam.get("withdrawal"), d1_last=dvar == "d1_after_d2")
+        dmonth = int(dam["month"])
+        dkw = {"spill": dvar != "no_spill", "smin": dvar != "no_smin"}
     if flood is not None:
         tab, wf = flood
         wf = np.array(wf, dtype=np.float64).reshape(-1)
@@ -288,6 +313,11 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
             eh = hillslope_flow(wh, area, ch, dts, cap)
             et = channel_flow(wt, p[TLEN], p[TWIDTH], ct, dts, cap)
             er = channel_flow(v, p[RLEN], p[RWIDTH], cr, dts, cap)
+            en = er  # K6's own term: the natural flow
+            if dam is not None:  # D3 where K4 forms the flow of the coming sub-step: the same operands as forming it here; D4
+                er, res = reservoir_regulate(en, res, krls, dtab, dmonth, dts, **dkw)
+                if dvar == "own_eo":
+                    en = er
             if in_place:
                 for c in range(v.size):
                     fin = 0.0
@@ -300,16 +330,21 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
                 fin = np.zeros_like(v)
                 for k in range(up.shape[0]):
                     fin = np.where(up[k] >= 0, fin + er[safe[k]], fin)
-                v = _canon(v + ((fin - er) + et) * dts)
+                v = _canon(v + ((fin - en) + et) * dts)
             if flood is not None:  # I1: after K6, before the next sub-step's er
                 v, wf, depth, frac = inundation_exchange(v, wf, tab, area)
             wh = _canon(wh + (qsur - eh) * dts)
             wt = _canon(wt + ((eh - et) + qsub) * dts)
             qacc = qacc + er
         qout = _canon(qacc / float(nsub))
+        if dam is not None and dvar == "regulate_last":
+            res = reservoir_regulate(channel_flow(v, p[RLEN], p[RWIDTH], cr, dts, cap), res, krls, dtab, dmonth, dts, **dkw)[1]
+    out = (wh, wt, _canon(v), qout)
     if flood is not None:
-        return wh, wt, _canon(v), qout, wf, depth, frac
-    return wh, wt, _canon(v), qout
+        out += (wf, depth, frac)
+    if dam is not None:
+        out += (res, krls, take, qin)
+    return out
 
 
 def kinematic_budget(wh, wt):
@@ -409,6 +444,164 @@ def inundation_exchange(volr, wf, tab, area):
 def inundation_budget(wf):
     """I7: the sum of WF in the device reduction's order, float64 [1]."""
     return np.array([diagnostics.reduce_min_max_sum(wf)[2]])
+
+
+# ---- reservoirs (include/elmk.h "reservoirs", D0 - D8) -----------------------------------------------------------------------------------
+RES, KRLS, RES_TAKE = 10, 11, 12  # ELMK_ROUTE_*, readable while the extension is on
+NMONTH = 12
+MONTH_FIRST_DOY = (0, 31, 59, 90, 120, 151, 181, 212, 243, 273, 304, 334)  # the no-leap calendar
+DAM_VARIANTS = ("own_eo", "regulate_last", "no_spill", "no_smin", "d1_after_d2")  # the wrong variants the host tests hold the statement against
+DAM_BRANCHES = ("floored", "fill", "draw unlimited", "draw limited", "pass-through", "spill", "beta < 1", "take limited", "take unlimited")
+
+# the refusals of elmk_routing_reservoir_enable's check (elmk_maps.h: reservoir_check), in its order; each is followed by the cell
+E_CAP = "CAP not finite and >= 0"
+E_TARGET = "TARGET not finite and >= 0"
+E_BETA = "BETA outside [0, 1]"
+E_MSTART = "MSTART outside 0 .. 11"
+
+
+def check_reservoirs(cap, target, beta, mstart):
+    """The checks of elmk_routing_reservoir_enable on cap [ncells], target [12, ncells], beta [ncells] and mstart [ncells], in its
+    order: cap cell by cell, then per dam cell (cap > 0) target, beta, mstart; raises ValueError with the entry point's text."""
+    c = np.asarray(cap, dtype=np.float64).reshape(-1)
+    t = np.asarray(target, dtype=np.float64)
+    b = np.asarray(beta, dtype=np.float64).reshape(-1)
+    m = np.asarray(mstart).reshape(-1)
+    if t.ndim != 2 or t.shape != (NMONTH, c.size) or b.size != c.size or m.size != c.size:
+        raise ValueError("target must be [12, ncells], beta and mstart [ncells]")
+    bad = ~(np.isfinite(c) & (c >= 0.0))
+    if bad.any():
+        raise ValueError(e_cell(E_CAP, int(np.nonzero(bad)[0][0])))
+    with np.errstate(all="ignore"):
+        code = np.where(~(np.isfinite(t) & (t >= 0.0)).all(axis=0), 1, np.where(~((b >= 0.0) & (b <= 1.0)), 2, np.where((m < 0) | (m > 11), 3, 0)))
+    code = np.where(c > 0.0, code, 0)
+    if code.any():
+        k = int(np.nonzero(code)[0][0])
+        raise ValueError(e_cell((E_TARGET, E_BETA, E_MSTART)[int(code[k]) - 1], k))
+
+
+def reservoir_tables(cap, target, beta, mstart):
+    """The checked inputs' tables as the host derives them, a dict: CAP, SMIN = 0.1 * CAP, C85 = 0.85 * CAP, BETA [ncells], TARGET
+    [12, ncells], MSTART int32 [ncells], DAM bool [ncells] (D0); the rows of cells without a dam are 0."""
+    check_reservoirs(cap, target, beta, mstart)
+    c = np.asarray(cap, dtype=np.float64).reshape(-1)
+    dam = c > 0.0
+    c = np.where(dam, c, 0.0)
+    return {"CAP": c, "SMIN": 0.1 * c, "C85": 0.85 * c, "BETA": np.where(dam, np.asarray(beta, dtype=np.float64).reshape(-1), 0.0),
+            "TARGET": np.where(dam[None], np.asarray(target, dtype=np.float64), 0.0),
+            "MSTART": np.where(dam, np.asarray(mstart).reshape(-1), 0).astype(np.int32), "DAM": dam}
+
+
+def month_of_doy(doy):
+    """The month 0 .. 11 of day-of-year doy (0 = 1 January) in the no-leap calendar; any other doy is taken modulo 365."""
+    return int(np.searchsorted(MONTH_FIRST_DOY, int(doy) % 365, side="right")) - 1
+
+
+def month_begins(doy, decday):
+    """Whether a step with (doy, decday) starts at 00:00 of the first day of its month: the active layer's rollover test,
+    decday == doy + 1.0, on the first doy of each month."""
+    return 0 <= int(doy) <= 364 and int(doy) in MONTH_FIRST_DOY and float(decday) == float(int(doy)) + 1.0
+
+
+def reservoir_prep(res, krls, qin, area, tab, month, begins, dt, withdrawal=None, d1_last=False, census=None):
+    """D1 and D2, the K1 launch's part for the dam cells: res, krls, qin (K1's QIN), area [ncells]; withdrawal = (rn, i), R1's
+    aggregates of QRUNOFF and QFLX_IRRIG, or None while the routing's withdrawal is off.  Returns (res, krls, res_take, qin).
+    d1_last: D1 after D2 (a wrong variant).  census: a dict that takes the bool rows "take limited" and "take unlimited"."""
+    res, krls = (np.array(x, dtype=np.float64).reshape(-1) for x in (res, krls))
+    qin, area = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (qin, area))
+    dam = tab["DAM"]
+    take = np.zeros_like(res)
+    with np.errstate(all="ignore"):
+        def d1(res, krls):
+            on = dam & bool(begins) & (int(month) == tab["MSTART"])
+            return np.where(on, _canon(res / np.where(on, tab["C85"], 1.0)), krls)
+
+        if not d1_last:
+            krls = d1(res, krls)
+        if withdrawal is not None:
+            rn, i = (np.asarray(x, dtype=np.float64).reshape(-1) for x in withdrawal)
+            iv = (i * 0.001) * area
+            want = iv * dt
+            a = res - tab["SMIN"]
+            avail = np.where(a > 0.0, a, 0.0)
+            limited = want > avail
+            t = np.where(limited, avail, want)
+            res = np.where(dam, _canon(res - t), res)
+            take = np.where(dam, _canon(t), 0.0)
+            qin = np.where(dam, _canon((rn * 0.001) * area - (iv - t / dt)), qin)
+            if census is not None:
+                census["take limited"] = dam & limited
+                census["take unlimited"] = dam & ~limited & (want > 0.0)
+        if d1_last:
+            krls = d1(res, krls)
+    return res, krls, take, qin
+
+
+def reservoir_regulate(e, res, krls, tab, month, dts, spill=True, smin=True, census=None):
+    """D3 for every cell: e, the main channel's er that K4 has just formed, res and krls [ncells].  Returns (eo, res_new); a cell without
+    a dam keeps e and its res.  spill=False and smin=False are wrong variants (no spill over CAP; no dead storage).  census: a dict
+    that takes a bool row per branch of DAM_BRANCHES[:7]."""
+    e, res, krls = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (e, res, krls))
+    dam, cap, beta = tab["DAM"], tab["CAP"], tab["BETA"]
+    sm = tab["SMIN"] if smin else np.zeros_like(cap)
+    tgt = tab["TARGET"][int(month)]
+    with np.errstate(all="ignore"):
+        q = beta * (krls * tgt) + (1.0 - beta) * e
+        qmin = 0.1 * e
+        floored = q < qmin
+        q = np.where(floored, qmin, q)
+        draw = q > e
+        a = res - sm
+        x = q - e
+        lim = np.where(a > 0.0, a / dts, 0.0)
+        limited = x > lim
+        x = np.where(limited, lim, x)
+        eo = np.where(draw, e + x, q)
+        s = res + (e - eo) * dts
+        over = (s > cap) if spill else np.zeros(s.shape, bool)
+        eo = np.where(over, eo + (s - cap) / dts, eo)
+        s = np.where(over, cap, s)
+    if census is not None:
+        census.update({"floored": dam & floored, "fill": dam & ~draw & (q < e), "draw unlimited": dam & draw & ~limited,
+                       "draw limited": dam & draw & limited & (a > 0.0), "pass-through": dam & draw & ~(a > 0.0), "spill": dam & over,
+                       "beta < 1": dam & (beta < 1.0)})
+    return np.where(dam, _canon(eo), e), np.where(dam, _canon(s), res)
+
+
+def reservoir_budget(res, res_take):
+    """D6: the sums of RES and RES_TAKE in the device reduction's order."""
+    return np.array([diagnostics.reduce_min_max_sum(x)[2] for x in (res, res_take)])
+
+
+def reservoir_targets(mean_inflow, mean_demand, cap):
+    """TARGET, BETA and MSTART from a climatology, by the rules of Hanasaki et al. (2006): mean_inflow and mean_demand [12] or
+    [12, ncells], the mean monthly inflow and irrigation demand in m3/s; cap [ncells] or a scalar, m3.  With im and dm the annual means
+    of the two (the mean over the twelve months):
+      TARGET[m] = im                                  where dm == 0 (a dam that serves no irrigation),
+                = (im / 2) * (1 + demand[m] / dm)     where dm >= 0.5 * im,
+                = im + demand[m] - dm                 otherwise (never below 0);
+      c = cap / (im * 365 * 86400), the storage as a share of the annual inflow volume;  BETA = min(1, (c / 0.5) ** 2);
+      MSTART = the first month with inflow < im that follows a month with inflow >= im (the operational year begins when the inflow
+               falls below its mean; 0 where no month does).
+    Returns (target float64 [12, ncells], beta float64 [ncells], mstart int32 [ncells])."""
+    cap = np.atleast_1d(np.asarray(cap, dtype=np.float64)).reshape(-1)
+    fi = np.asarray(mean_inflow, dtype=np.float64)
+    fd = np.asarray(mean_demand, dtype=np.float64)
+    fi = np.repeat(fi[:, None], cap.size, axis=1) if fi.ndim == 1 else fi
+    fd = np.repeat(fd[:, None], cap.size, axis=1) if fd.ndim == 1 else fd
+    if fi.shape != (NMONTH, cap.size) or fd.shape != (NMONTH, cap.size):
+        raise ValueError("mean_inflow and mean_demand must be [12] or [12, ncells]")
+    im, dm = fi.mean(axis=0), fd.mean(axis=0)
+    with np.errstate(all="ignore"):
+        share = (im[None] / 2.0) * (1.0 + fd / np.where(dm > 0.0, dm, 1.0)[None])
+        shift = np.maximum(im[None] + fd - dm[None], 0.0)
+        target = np.where((dm == 0.0)[None], np.repeat(im[None], NMONTH, axis=0), np.where((dm >= 0.5 * im)[None], share, shift))
+        c = cap / np.where(im > 0.0, im * (365.0 * 86400.0), 1.0)
+        beta = np.where(im > 0.0, np.minimum(1.0, (c / 0.5) ** 2), 1.0)
+    below = fi < im[None]
+    falls = below & ~np.roll(below, 1, axis=0)
+    mstart = np.where(falls.any(axis=0), falls.argmax(axis=0), 0).astype(np.int32)
+    return target, beta, mstart
 
 
 # D8 direction codes (the ESRI convention): the neighbour a cell drains into, as (row step, column step) with row 0 the northernmost

@@ -40,6 +40,7 @@ ROUTE_WH, ROUTE_WT, ROUTE_QSUR = 4, 5, 6  # ... while the kinematic-wave scheme 
 ROUTE_KW_NPARAM = 11  # the rows of routing_kinematic_enable's params (routing.HSLP .. routing.NR)
 ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC = 7, 8, 9  # ... while the floodplain inundation is on (routing.WF .. routing.FLOOD_FRAC)
 ROUTE_FP_NPROF = 11  # the rows of routing_inundation_enable's eprof
+ROUTE_RES, ROUTE_KRLS, ROUTE_RES_TAKE = 10, 11, 12  # ... while the reservoirs are on (routing.RES .. routing.RES_TAKE)
 WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB .. hydrology.WB_TOTSOILICE
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
@@ -597,7 +598,8 @@ class ELMState:
 
     def routing_read(self, which, cell0=0, n=None):
         """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM (with the kinematic-wave scheme on also ROUTE_WH, ROUTE_WT, ROUTE_QSUR,
-        with its floodplain inundation on also ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC)
+        with its floodplain inundation on also ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC, with its reservoirs on also ROUTE_RES,
+        ROUTE_KRLS, ROUTE_RES_TAKE)
         of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
         n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
         out = np.empty(max(n, 0), dtype=np.float64)
@@ -684,6 +686,44 @@ class ELMState:
     def routing_inundation_clear(self):
         """Back to the channel without banks; WF is dropped, VOLR stays."""
         self._chk(self.lib.elmk_routing_inundation_clear(self.ctx), "routing_inundation_clear")
+
+    # -- reservoirs (include/elmk.h: elmk_routing_reservoir_enable ...; routing.kinematic_call(dam=) restates them) -------------------------
+    def routing_reservoir_enable(self, cap, target, beta, mstart):
+        """Put dams at the outlets of the kinematic scheme's cells: cap float64 [ncells], m3 (finite and >= 0; 0 = no dam), target float64
+        [12, ncells], the monthly target release in m3/s (finite and >= 0), beta float64 [ncells] in [0, 1], mstart int32 [ncells] in
+        0 .. 11; the last three are checked only where cap > 0.  Allocates the rows RES, RES_TAKE (zero-filled) and KRLS (1.0);
+        routing_read takes ROUTE_RES, ROUTE_KRLS and ROUTE_RES_TAKE from here on.  Needs routing_kinematic_enable."""
+        c = np.ascontiguousarray(cap, dtype=np.float64).reshape(-1)
+        t = np.ascontiguousarray(target, dtype=np.float64)
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        m = np.ascontiguousarray(mstart, dtype=np.int32).reshape(-1)
+        n = getattr(self, "routing_ncells", c.size)
+        if c.size != n or t.shape != (12, n) or b.size != n or m.size != n:
+            raise ValueError(f"routing_reservoir_enable: cap, beta and mstart must be [{n}] and target [12, {n}]")
+        self._chk(self.lib.elmk_routing_reservoir_enable(self.ctx, _p(c), _p(t), _p(b), _p(m)), "routing_reservoir_enable")
+
+    def routing_reservoir_init(self, res=None, krls=None):
+        """RES from [ncells] (None: zeros), KRLS from [ncells] (None: 1.0), RES_TAKE zeros.  Synchronises."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (res, krls)]
+        for v in a:
+            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
+                raise ValueError(f"routing_reservoir_init: {v.size} values for {self.routing_ncells} cells")
+        self._chk(self.lib.elmk_routing_reservoir_init(self.ctx, *(None if v is None else _p(v) for v in a)), "routing_reservoir_init")
+
+    def routing_reservoir_time(self, month, begins=False):
+        """The month (0 .. 11) of the following routing() calls, and whether the next one is the call whose step starts at 00:00 of the
+        month's first day (routing.month_of_doy); run() derives both from its steps."""
+        self._chk(self.lib.elmk_routing_reservoir_time(self.ctx, int(month), 1 if begins else 0), "routing_reservoir_time")
+
+    def routing_reservoir_budget(self):
+        """float64 [2]: the sums of RES and RES_TAKE (routing.reservoir_budget).  Synchronises."""
+        out = np.empty(2, dtype=np.float64)
+        self._chk(self.lib.elmk_routing_reservoir_budget(self.ctx, _p(out)), "routing_reservoir_budget")
+        return out
+
+    def routing_reservoir_clear(self):
+        """Back to the free-flowing channel; RES is dropped, VOLR stays."""
+        self._chk(self.lib.elmk_routing_reservoir_clear(self.ctx), "routing_reservoir_clear")
 
     # -- water balance (include/elmk.h: elmk_water_balance_enable ...; hydrology.water_balance_begin / _end restate the stage) -----
     def water_balance_enable(self, tol_mm):

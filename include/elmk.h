@@ -1247,6 +1247,101 @@ int elmk_routing_inundation_init(elmk_ctx *ctx, const double *wf /*[ncells] or N
 int elmk_routing_inundation_budget(elmk_ctx *ctx, double *sums /*[1]: the sum of WF, through R6's reduction kernels*/);
 int elmk_routing_inundation_clear(elmk_ctx *ctx);
 
+/* ---- reservoirs ---------------------------------------------------------------------------------
+ * An opt-in extension of the kinematic-wave scheme above, after the water management of MOSART-WM (Voisin et al., Hydrol. Earth Syst.
+ * Sci. 17, 2013; the release rules of Hanasaki et al., J. Hydrol. 327, 2006): a dam at the outlet of a cell stores water behind it
+ * and releases it towards a monthly target, so the discharge below it is the regulated one, and the cell's irrigation draws on the
+ * stored water.  The pattern is the inundation's: a template parameter on the existing kernels (k_routing.hip:
+ * k_kinematic_prep<.., DAM>, k_kinematic_step<.., DAM>), no run flag and no new call or launch in the step.
+ * elmkernels_amd/routing.py: reservoir_tables(), reservoir_prep(), reservoir_regulate() and kinematic_call(..., dam=) restate it on
+ * the host.
+ *
+ * Conventions of "kinematic-wave routing": no contraction, left-associated + - *, `/` correctly rounded, plain IEEE comparisons, every
+ * row fp64 in both builds, a NaN stored as the canonical quiet NaN.
+ *
+ * Inputs, given once after elmk_routing_kinematic_enable: cap[ncells], the storage capacity in m3, finite and >= 0, 0.0 = no dam;
+ * target[12][ncells], the monthly target release in m3/s, finite and >= 0; beta[ncells] in [0, 1], the weight of the target against
+ * the inflow; mstart[ncells], int32 in 0 .. 11, the first month of the dam's operational year.  target, beta and mstart are checked
+ * only where cap > 0.0.  The host derives SMIN = 0.1 * CAP and C85 = 0.85 * CAP and keeps CAP, SMIN, C85, TARGET, BETA and MSTART on
+ * the device.  elmkernels_amd/routing.py: reservoir_targets() forms target, beta and mstart from a climatology by Hanasaki's rules.
+ *
+ * Time: the month m (0 .. 11) and a bool `begins` (this call is the one whose step starts at 00:00 of the first day of month m) are
+ * the driver's, like the active layer's rollover.  Stepwise, elmk_routing_reservoir_time(ctx, month, begins) sets what the following
+ * elmk_routing calls use (0, false after the enable).  In elmk_run the host derives both from the step's doy and decday in the
+ * reference's no-leap calendar - m from doy, begins = (decday == doy + 1.0) on the first doy of a month, the rollover's test - and
+ * packs them into the run row's pad word above the irrigation's time of day; elmk_run_step does not grow.
+ *
+ * Rows: ELMK_ROUTE_RES (m3, the reservoir storage; prognostic), ELMK_ROUTE_KRLS (the release coefficient; prognostic, 1.0 after the
+ * enable and after an _init without a row) and ELMK_ROUTE_RES_TAKE (m3 taken for irrigation in this call; diagnostic).
+ * elmk_routing_read accepts the three only while the extension is on.
+ *
+ * D0. A cell is a dam cell iff CAP > 0.0.  In any other cell every row of the scheme keeps the bits of the form without the
+ *     extension, and RES, KRLS and RES_TAKE are not written.  The rest of the statement is about dam cells.
+ * D1. (K1 launch, once per call) if (begins && m == MSTART) KRLS = RES / C85.
+ * D2. (K1 launch, only with the routing's withdrawal on) with rn and i R1's aggregates of QRUNOFF and QFLX_IRRIG:
+ *     iv = (i * 0.001) * area;  want = iv * dt;  a = RES - SMIN;  avail = a > 0.0 ? a : 0.0;  t = want > avail ? avail : want;
+ *     RES = RES - t;  RES_TAKE = t;  QIN = (rn * 0.001) * area - (iv - t / dt).  The dam covers what it can of the cell's
+ *     withdrawal; the rest leaves the channel as in R1.  Without the withdrawal RES_TAKE = 0.0 and QIN is K1's.
+ *     QSUB = QIN - QSUR, as in K1.
+ * D3. (regulation) wherever K4 forms the main channel's er for a coming sub-step - the K1 launch and every sub-step but the last,
+ *     in the flood form after I1 - I5 - with e that er:
+ *     q = BETA * (KRLS * TARGET[m]) + (1.0 - BETA) * e;  qmin = 0.1 * e;  if (q < qmin) q = qmin;
+ *     if (q > e) { a = RES - SMIN;  x = q - e;  lim = a > 0.0 ? a / dts : 0.0;  if (x > lim) x = lim;  eo = e + x; } else eo = q;
+ *     s = RES + (e - eo) * dts;  if (s > CAP) { eo = eo + (s - CAP) / dts;  s = CAP; }  RES = s.
+ *     The dam releases the blend of its target and its inflow, never less than a tenth of the inflow; what it releases beyond the
+ *     inflow it draws from the storage above SMIN, what it holds back it stores, and what does not fit spills.
+ * D4. The flow row's buffer takes eo: downstream cells' K5 and the cell's own K7 read that, so QOUT is the regulated discharge.
+ *     The cell's own K6 of the coming sub-step subtracts the natural e: VOLR = VOLR + ((fin - e) + et) * dts.
+ * D5. RES therefore stands one sub-step ahead of VOLR inside a call, and level with it at the call's end, because the last sub-step
+ *     forms no flow.
+ * D6. (elmk_routing_reservoir_budget) sums[0] = the sum of RES, sums[1] = the sum of RES_TAKE, through R6's reduction kernels.  The
+ *     change of sum WH + sum WT + sum VOLR (+ sum WF) + sum RES over a call = dt (sum QIN - sum outlet QOUT) - sum RES_TAKE.
+ * D7. (river supply limit) While the reservoirs and elmk_irrigation_supply_* are both on, S3 reads for a dam cell r = RES - SMIN, taken
+ *     as 0.0 unless > 0.0, and a = (VOLR * (1.0 - thr) + r) - Vc.  Every other cell, and every cell with the extension off, keeps S3
+ *     (k_irrigation_supply's DAM form; elmkernels_amd/irrigation.py: supply_limit(dam=)).  A NaN RES counts as nothing.
+ * D8. Edge values do what D1 - D3 say literally.  A NaN RES gives a = NaN, so avail = 0.0 and lim = 0.0: nothing is taken for a positive
+ *     want and nothing is drawn; s = NaN fails s > CAP and RES stays NaN, while eo is e (where q > e) or q.  A NaN KRLS or e makes q
+ *     NaN, which fails both q < qmin and q > e: eo = NaN and RES = NaN.  RES = +inf has lim = +inf: a finite q draws x = q - e, and
+ *     s = +inf spills: eo = +inf, RES = CAP; in a call that D1 opens, KRLS = +inf makes q and eo +inf and s = inf - inf = NaN.  A
+ *     negative RES, or any RES <= SMIN, draws nothing: the dam passes e, or stores where q < e.  RES = -inf stays -inf (and D1's
+ *     KRLS = -inf gives q = -inf, floored to 0.1 e).  e = +inf gives q = +inf where BETA < 1.0 (eo = q, s = RES + NaN = NaN); at
+ *     BETA == 1.0 the term 0.0 * inf is NaN.  CAP = 5e-324 is a dam: SMIN = 0.0 (0.1 of the smallest double rounds to zero) and
+ *     C85 = 5e-324 (0.85 of it rounds to itself), so D1 gives KRLS = +inf for any RES that is not tiny, and the reservoir draws all it
+ *     holds and spills whatever it would store.
+ * The device keeps the natural e of a dam cell's coming sub-step in a row of its own, which only the cell's own thread writes and
+ * reads; evaluating K4 again from the VOLR of the sub-step's start would give the same operands through the same operations.
+ *
+ *   elmk_routing_reservoir_enable  takes the inputs, builds the tables, allocates them and the rows (RES, RES_TAKE zero-filled, KRLS
+ *                           1.0; one owner, counted in elmk_device_bytes) and drops the captured run step.  ELMK_E_INVALID, nothing
+ *                           changed: the kinematic scheme not on; already on; a null argument; a bad value
+ *                           (the text names the row and the first offending cell, "elmk_routing_reservoir_enable: BETA outside
+ *                           [0, 1] at cell 17"); a stream being captured.
+ *   elmk_routing_reservoir_init    RES from host[ncells] (NULL: zeros), KRLS from host[ncells] (NULL: 1.0), RES_TAKE zeros.
+ *                           Synchronises.
+ *   elmk_routing_reservoir_time    the month and `begins` of the following elmk_routing calls.  ELMK_E_INVALID: month outside 0 .. 11.
+ *   elmk_routing_reservoir_budget  D6; synchronises.
+ *   elmk_routing_reservoir_clear   back to the free-flowing channel, RES dropped, VOLR kept; frees what enable allocated and drops the
+ *                           captured run step.  From then on the scheme's rows take the bits of a context that never had the
+ *                           extension, given the same VOLR.
+ * While the extension is on elmk_routing_kinematic_clear is refused with ELMK_E_INVALID ("elmk_routing_reservoir_clear first");
+ * elmk_routing_clear frees everything.  The reservoirs and the inundation may be enabled in either order and cleared independently.
+ * elmk_routing and elmk_run with ELMK_RUN_ROUTING run the DAM form while it is on.
+ * Tapes: elmk_cell_history_add_row(ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_RES | KRLS | RES_TAKE) works while the extension is on, and while
+ * such an entry exists elmk_routing_reservoir_clear is refused ("elmk_history_clear first").
+ * Restart: under ELMK_OPT_RESTART_CELLS a context with the reservoirs on saves an image of version 7
+ * (ELMK_RESTART_VERSION_RESERVOIR): version 6 plus the cell sections ELMK_ROUTE_RES and ELMK_ROUTE_KRLS after WF; it loads only into a
+ * context with the same stages on, and the load leaves RES_TAKE zero; every other context saves byte for byte what it saved before.
+ * With the option off a driver saves RES and KRLS with elmk_routing_read beside the scheme's rows and hands them to
+ * elmk_routing_reservoir_init after elmk_routing_reservoir_enable.  A context that never calls these entries runs the kernels,
+ * launch sequences and graphs it ran before and allocates nothing more. */
+enum { ELMK_ROUTE_RES = 10, ELMK_ROUTE_KRLS = 11, ELMK_ROUTE_RES_TAKE = 12 };
+int elmk_routing_reservoir_enable(elmk_ctx *ctx, const double *cap /*[ncells]*/, const double *target /*[12][ncells]*/,
+                                  const double *beta /*[ncells]*/, const int32_t *mstart /*[ncells]*/);
+int elmk_routing_reservoir_init(elmk_ctx *ctx, const double *res /*[ncells] or NULL: zeros*/, const double *krls /*[ncells] or NULL: 1.0*/);
+int elmk_routing_reservoir_time(elmk_ctx *ctx, int month /*0 .. 11*/, int begins);
+int elmk_routing_reservoir_budget(elmk_ctx *ctx, double *sums /*[2]: the sums of RES and RES_TAKE, through R6's reduction kernels*/);
+int elmk_routing_reservoir_clear(elmk_ctx *ctx);
+
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.
  * These two entries register one such row, over the columns (elmk_column_history_add_row; the six elmk_history_* entries of "history"
@@ -1385,6 +1480,7 @@ enum { ELMK_RESTART_ROUTING = 7, ELMK_RESTART_IRRSUP = 8 }; /* the cell sections
 #define ELMK_RESTART_VERSION_HYDROLOGY 4u /* of a context with the soil hydrology enabled */
 #define ELMK_RESTART_VERSION_IRRIGATION 5u /* of a context with the irrigation enabled */
 enum { ELMK_RESTART_VERSION_ROUTING = 6 };  /* of a context with the routing enabled and ELMK_OPT_RESTART_CELLS on */
+enum { ELMK_RESTART_VERSION_RESERVOIR = 7 };  /* ... and the reservoirs on: version 6 plus the cell sections ELMK_ROUTE_RES and ELMK_ROUTE_KRLS after WF */
 typedef struct {
   char magic[8];              /* ELMK_RESTART_MAGIC */
   uint32_t version;           /* ELMK_RESTART_VERSION */

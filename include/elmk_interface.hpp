@@ -422,6 +422,20 @@ class ELMInterface {
   void routing_inundation_init(const double* wf = nullptr) { ok(elmk_routing_inundation_init(ctx_, wf)); }
   void routing_inundation_budget(double* sums) { ok(elmk_routing_inundation_budget(ctx_, sums)); }
   void routing_inundation_clear() { ok(elmk_routing_inundation_clear(ctx_)); }
+  /* Reservoirs (elmk.h "reservoirs"): dams at the outlets of the kinematic scheme's cells.  routing_reservoir_enable() takes cap[ncells]
+   * (0 = no dam), target[12][ncells], beta[ncells] and mstart[ncells] after routing_kinematic_enable; routing(dt) and
+   * run(..., routing = true) then run the DAM form, and routing_read() takes ELMK_ROUTE_RES, ELMK_ROUTE_KRLS and ELMK_ROUTE_RES_TAKE as
+   * well.  routing_reservoir_time() sets the month and `begins` of the following routing(dt) calls (run() takes them from its steps);
+   * routing_reservoir_init() takes a restart's RES and KRLS ([ncells], nullptr: zeros and 1.0); routing_reservoir_budget() fills
+   * sums[2]; routing_reservoir_clear() returns to the free-flowing channel and keeps VOLR. */
+  void routing_reservoir_enable(const double* cap, const double* target, const double* beta, const int32_t* mstart)
+  {
+    ok(elmk_routing_reservoir_enable(ctx_, cap, target, beta, mstart));
+  }
+  void routing_reservoir_init(const double* res = nullptr, const double* krls = nullptr) { ok(elmk_routing_reservoir_init(ctx_, res, krls)); }
+  void routing_reservoir_time(int month, bool begins) { ok(elmk_routing_reservoir_time(ctx_, month, begins ? 1 : 0)); }
+  void routing_reservoir_budget(double* sums) { ok(elmk_routing_reservoir_budget(ctx_, sums)); }
+  void routing_reservoir_clear() { ok(elmk_routing_reservoir_clear(ctx_)); }
   /* History entries over one fp64 row of a feature (elmk.h "feature rows on history tapes"): family ELMK_ROWS_*, which the family's
    * row number; as history_add / gridded_history_add otherwise, one level.  While such an entry exists the family's clear is refused. */
   int history_add_row(int tape, int family, int which, int op)
