@@ -109,20 +109,8 @@ struct RstKind {
   RstRows (*rows)(Ctx, int i);
   bool cells = false, implied = true;
 };
-// the routing state of version 6 (ELMK_OPT_RESTART_CELLS): the prognostic rows the river stages hold at this moment, in image order;
-// with the reservoirs on RES and KRLS follow, and the image is of version 7
-constexpr int ROUTE_STATE_MAX = 7;
-int route_state_rows(Ctx c, int* ids)
-{
-  if (!c->restart_cells || !c->route.mem) return 0;
-  int n = 0;
-  ids[n++] = ELMK_ROUTE_VOLR;
-  ids[n++] = ELMK_ROUTE_QOUT_SUM;
-  if (c->route.kw_mem) ids[n++] = ELMK_ROUTE_WH, ids[n++] = ELMK_ROUTE_WT;
-  if (c->route.fp_mem) ids[n++] = ELMK_ROUTE_WF;
-  if (c->route.dam_mem) ids[n++] = ELMK_ROUTE_RES, ids[n++] = ELMK_ROUTE_KRLS;
-  return n;
-}
+// (the routing state of version 6, ELMK_OPT_RESTART_CELLS: route_state_rows of api_routing.cpp; with the reservoirs on RES and KRLS
+// follow, and the image is of version 7)
 const RstKind RST_OPTIONAL[] = {
     {ELMK_RESTART_ACCUM, ELMK_RESTART_VERSION_ACCUM, "accumulator entries", "elmk_accum_add", [](Ctx c) { return (int)c->accum.size(); },
      [](Ctx c, int i) { return RstRows{i, c->accum[i].nlev, c->accum[i].val}; }},
@@ -180,7 +168,7 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
       L.src.push_back(RstSrc{(char*)r.dev, K.cells ? ctx->route.cld : ctx->ld, ELMK_F64, K.cells ? 0 : gcol0, false});
     }
   }
-  if ((L.kinds & (1u << ELMK_RESTART_ROUTING)) && ctx->route.dam_mem) L.version = std::max(L.version, RST_V_RESERVOIR);  // (RES and KRLS)
+  if ((L.kinds & (1u << ELMK_RESTART_ROUTING)) && ctx->route.dam.mem) L.version = std::max(L.version, RST_V_RESERVOIR);  // (RES and KRLS)
   // the accumulator table follows the history entries
   L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.version >= 2 ? 8 : 0) + (L.version >= RST_V_ROUTING ? 8 : 0) + L.acc.size() * sizeof(elmk_restart_accum) +
                                 L.ent.size() * sizeof(elmk_restart_entry) + L.sec.size() * sizeof(elmk_restart_section),
@@ -544,12 +532,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
     if (ck[s] != want[s]) return invalid(ctx, "elmk_restart_load: section checksum mismatch");
   if (bad) return invalid(ctx, "elmk_restart_load: snl outside 0..nlevsno");
   if (L.kinds & (1u << ELMK_RESTART_ROUTING)) {  // every row of the river stages zero, as their _init calls leave the diagnostic ones
-    const elmk_ctx::Routing& T = ctx->route;
-    const size_t row = (size_t)T.cld * sizeof(double);
-    HIPCHK(hipMemsetAsync(T.rows, 0, (size_t)ROUTE_NROWS * row, ctx->stream));
-    if (T.kw_mem) HIPCHK(hipMemsetAsync(T.kw_rows, 0, (size_t)KW_NROWS * row, ctx->stream));
-    if (T.fp_mem) HIPCHK(hipMemsetAsync(T.fp_rows, 0, (size_t)FP_NROWS * row, ctx->stream));
-    if (T.dam_mem) HIPCHK(hipMemsetAsync(T.dam_rows, 0, (size_t)DAM_NROWS * row, ctx->stream));
+    if (int rc = route_zero_rows(ctx)) return rc;
     if (ctx->irrsup_rows) HIPCHK(hipMemsetAsync(ctx->irrsup_rows, 0, ctx->irrsup_rows.bytes(), ctx->stream));
     ctx->route.ncalls = route_ncalls;
   }

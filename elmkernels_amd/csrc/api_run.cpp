@@ -316,7 +316,7 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
       r.pad |= (int32_t)(((t % 86400) + 86400) % 86400) << RUN_PAD_TOD_SHIFT;
     }
     // the reservoirs' month and whether the step starts at 00:00 of its first day (the rollover's test), above the time of day
-    if ((flags & ELMK_RUN_ROUTING) && ctx->route.dam_mem) {
+    if ((flags & ELMK_RUN_ROUTING) && ctx->route.dam.mem) {
       const int m = reservoir_month(p.doy);
       r.pad |= (int32_t)(m | (reservoir_month_begins(p.doy, p.decday) ? 16 : 0)) << RUN_PAD_DAM_SHIFT;
     }
@@ -342,7 +342,7 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
                     ctx->accum_version, (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx),
                     (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows, (flags & ELMK_RUN_ROUTING) && ctx->route.withdraw,
                     (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx) && (bool)ctx->irrsup_rows,
-                    (flags & ELMK_RUN_ROUTING) && (bool)ctx->route.dam_mem};
+                    (flags & ELMK_RUN_ROUTING) && (bool)ctx->route.dam.mem};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;

@@ -289,10 +289,22 @@ struct elmk_ctx {
   // while the limit is on
   DevBuf<double> irrsup_rows;
   double irrsup_thr = 0.0;
-  // runoff routing (elmk_routing_*): one allocation `mem` holds the rows [ROUTE_NROWS][cld], KOUT and area [cld], the upstream map
-  // [npad][cld], down [cld] and the budget reduction's partials [3][ELMK_CONS_NPART][3] and triples [3][3]; held exactly while the
-  // feature is enabled.  ncalls: the calls since the last elmk_routing_init / _reset_mean (QOUT_SUM's count)
+  // The river stage (elmk_routing_*) has four parts, each with one allocation held exactly while the part is on; api_routing.cpp's
+  // table PARTS says the rest about each (rows, public ids, budget, restart rows, refusals).
+  //   base (elmk_routing_enable): `mem` holds the rows [ROUTE_NROWS][cld], KOUT and area [cld], the upstream map [npad][cld], down
+  //     [cld] and the budgets' reduction partials [3][ELMK_CONS_NPART][3] and triples [3][3].  ncalls: the calls since the last
+  //     elmk_routing_init / _reset_mean (QOUT_SUM's count)
+  //   kw (elmk_routing_kinematic_*): the scheme's rows [KW_NROWS][cld]; tab: the derived parameters [KW_NPAR][cld]
+  //   fp (elmk_routing_inundation_*): the floodplain's rows [FP_NROWS][cld]; tab: the host's tables [FP_NTAB][cld]
+  //   dam (elmk_routing_reservoir_*): the reservoirs' rows [DAM_NROWS][cld]; tab: the host's tables [DAM_NTAB][cld]; beside it, in
+  //     the same allocation, MSTART [cld].  dam_time: the month | begins << 4 of elmk_routing_reservoir_time, what the stepwise calls read
+  // route_launch takes the scheme and the forms whose memory is there.
   struct Routing {
+    struct Part {
+      DevBuf<char> mem;
+      double* rows = nullptr;
+      double* tab = nullptr;
+    };
     DevBuf<char> mem;
     int64_t ncells = 0, cld = 0;
     int npad = 0, nsub = 0;
@@ -305,22 +317,7 @@ struct elmk_ctx {
     int32_t* down = nullptr;
     double* part = nullptr;
     double* out = nullptr;
-    // the kinematic-wave scheme (elmk_routing_kinematic_*): a second allocation with the rows [KW_NROWS][cld] and the derived
-    // parameters [KW_NPAR][cld], held exactly while the scheme is on; route_launch takes the scheme whose memory is there
-    DevBuf<char> kw_mem;
-    double* kw_rows = nullptr;
-    double* kw_par = nullptr;
-    // its floodplain inundation (elmk_routing_inundation_*): a third allocation with the rows [FP_NROWS][cld] and the host's tables
-    // [FP_NTAB][cld], held exactly while the extension is on; route_launch takes the flood form while it is there
-    DevBuf<char> fp_mem;
-    double* fp_rows = nullptr;
-    double* fp_tab = nullptr;
-    // its reservoirs (elmk_routing_reservoir_*): a fourth allocation with the rows [DAM_NROWS][cld], the host's tables [DAM_NTAB][cld]
-    // and MSTART [cld], held exactly while the extension is on; route_launch takes the DAM form while it is there.  dam_time: the
-    // month | begins << 4 of elmk_routing_reservoir_time, what the stepwise calls read
-    DevBuf<char> dam_mem;
-    double* dam_rows = nullptr;
-    double* dam_tab = nullptr;
+    Part kw, fp, dam;
     int32_t* dam_mstart = nullptr;
     int32_t dam_time = 0;
   } route;
@@ -508,6 +505,12 @@ int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal = false);
 // row `which` (ELMK_ROUTE_*) of the river stages as elmk_routing_read finds it now, or null with *why set (not enabled, out of range, its
 // scheme or extension off)
 const double* route_row(const elmk_ctx* ctx, int which, const char** why);
+size_t route_bytes(const elmk_ctx* ctx);  // the device bytes of the parts that are on
+int route_zero_rows(elmk_ctx* ctx);       // every row of every part that is on zero (enqueued)
+// the routing state of the restart image (ELMK_OPT_RESTART_CELLS): the ELMK_ROUTE_* of the prognostic rows the parts hold at this
+// moment, in image order (VOLR, QOUT_SUM, WH, WT, WF, RES, KRLS); returns their number
+constexpr int ROUTE_STATE_MAX = 7;
+int route_state_rows(const elmk_ctx* ctx, int* ids);
 constexpr int ALT_NROWS = 3;  // api_rows.cpp
 ActiveLayerArgs alt_args(const elmk_ctx* ctx);
 bool hyd_land(const elmk_ctx* ctx);

@@ -16,6 +16,8 @@
 // first sub-step, 8 (the flow sum), and writes 16.  The unit carries no nontemporal hint: none has been measured for it.
 // The second scheme of the stage, kinematic-wave routing (k_kinematic_prep, k_kinematic_step), follows the linear one below, with its
 // floodplain inundation (k_kinematic_step's FLOOD form) and its reservoirs (both kernels' DAM form).
+#include <type_traits>
+
 #include "elmk_dev.h"
 #include "elmk_kernels.h"
 
@@ -114,21 +116,24 @@ __global__ __launch_bounds__(256) void k_routing_outlets(gptr<const int32_t> dow
 }
 
 namespace {
-template <int NPAD, bool FIRST, bool LAST>
-void launch_step(const RouteArgs& A, const double* v_old, double* v_new, double dts, hipStream_t st)
+// A run-time value as a compile-time one: f is called with the std::integral_constant of the value, and the kernel's template
+// arguments are read off the constants' types where the launch is spelled out.
+template <class F>
+void with_bool(bool b, F f)
 {
-  hipLaunchKernelGGL((k_routing_step<NPAD, FIRST, LAST>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
-                     (gptr<const double>)v_old, (gptr<double>)v_new, (gptr<const double>)A.kout, (gptr<const int32_t>)A.up,
-                     (gptr<const double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT * A.cld),
-                     (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts, (double)A.nsub);
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
-template <int NPAD>
-void launch_step(const RouteArgs& A, const double* v_old, double* v_new, double dts, bool first, bool last, hipStream_t st)
+// npad = ell_npad(largest in-degree): 1, 2, 4 or 8
+template <class F>
+void with_npad(int npad, F f)
 {
-  if (first && last) launch_step<NPAD, true, true>(A, v_old, v_new, dts, st);
-  else if (first) launch_step<NPAD, true, false>(A, v_old, v_new, dts, st);
-  else if (last) launch_step<NPAD, false, true>(A, v_old, v_new, dts, st);
-  else launch_step<NPAD, false, false>(A, v_old, v_new, dts, st);
+  switch (npad) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
 }
 }  // namespace
 
@@ -146,13 +151,16 @@ void launch_routing(const RouteArgs& A, const OGridMap& M, const double* qrunoff
   const double dts = dt / (double)A.nsub;  // R0
   double *src = odd ? volr_b : volr, *dst = odd ? volr : volr_b;
   for (int s = 0; s < A.nsub; s++) {
-    const bool first = s == 0, last = s == A.nsub - 1;
-    switch (A.npad) {
-      case 1: launch_step<1>(A, src, dst, dts, first, last, st); break;
-      case 2: launch_step<2>(A, src, dst, dts, first, last, st); break;
-      case 4: launch_step<4>(A, src, dst, dts, first, last, st); break;
-      default: launch_step<8>(A, src, dst, dts, first, last, st); break;
-    }
+    with_npad(A.npad, [&](auto npad) {
+      with_bool(s == 0, [&](auto first) {
+        with_bool(s == A.nsub - 1, [&](auto last) {
+          hipLaunchKernelGGL((k_routing_step<decltype(npad)::value, decltype(first)::value, decltype(last)::value>), grid, block, 0, st,
+                             (gptr<const double>)src, (gptr<double>)dst, (gptr<const double>)A.kout, (gptr<const int32_t>)A.up,
+                             (gptr<const double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT * A.cld),
+                             (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts, (double)A.nsub);
+        });
+      });
+    });
     double* const t = src;
     src = dst;
     dst = t;
@@ -463,63 +471,6 @@ DamRows<true> dam_rows(const DamArgs& Dm, double dt)
 {
   return DamRows<true>{(gptr<double>)Dm.rows, (gptr<const double>)Dm.tab, (gptr<const int32_t>)Dm.mstart, Dm.run, Dm.cursor, Dm.time, dt};
 }
-template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM>
-void launch_kw_form(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
-                    double dts, hipStream_t st)
-{
-  FloodRows<FLOOD> fl;
-  if constexpr (FLOOD) fl = FloodRows<true>{(gptr<double>)F.rows, (gptr<const double>)F.tab};
-  DamRows<DAM> dm;
-  if constexpr (DAM) dm = dam_rows(Dm, dts * (double)A.nsub);
-  hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST, FLOOD, DAM>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
-                     (gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld),
-                     (gptr<double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)er_old, (gptr<double>)er_new,
-                     (gptr<const double>)K.par, (gptr<const double>)A.area, (gptr<const int32_t>)A.up,
-                     (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<const double>)(K.rows + KW_QSUB * A.cld),
-                     (gptr<double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts,
-                     (double)A.nsub, fl, dm);
-}
-// the form of the sub-step: the DAM form exactly while the reservoirs' rows are there
-template <int NPAD, bool FIRST, bool LAST, bool FLOOD>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
-                    double dts, hipStream_t st)
-{
-  if (Dm.rows) launch_kw_form<NPAD, FIRST, LAST, FLOOD, true>(A, K, F, Dm, er_old, er_new, dts, st);
-  else launch_kw_form<NPAD, FIRST, LAST, FLOOD, false>(A, K, F, Dm, er_old, er_new, dts, st);
-}
-template <int NPAD, bool FLOOD>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
-                    double dts, bool first, bool last, hipStream_t st)
-{
-  if (first && last) launch_kw_step<NPAD, true, true, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
-  else if (first) launch_kw_step<NPAD, true, false, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
-  else if (last) launch_kw_step<NPAD, false, true, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
-  else launch_kw_step<NPAD, false, false, FLOOD>(A, K, F, Dm, er_old, er_new, dts, st);
-}
-template <bool FLOOD>
-void launch_kw_step(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const double* er_old, double* er_new,
-                    double dts, bool first, bool last, hipStream_t st)
-{
-  switch (A.npad) {
-    case 1: launch_kw_step<1, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
-    case 2: launch_kw_step<2, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
-    case 4: launch_kw_step<4, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
-    default: launch_kw_step<8, FLOOD>(A, K, F, Dm, er_old, er_new, dts, first, last, st); break;
-  }
-}
-template <bool WITHDRAW, bool DAM>
-void launch_kw_prep(const RouteArgs& A, const KinematicArgs& K, const DamArgs& Dm, const OGridMap& M, const double* qrunoff,
-                    const double* qirr, const double* qsurf, const double* qh2osfc, double* er, double dt, double dts, hipStream_t st)
-{
-  DamRows<DAM> dm;
-  if constexpr (DAM) dm = dam_rows(Dm, dt);
-  hipLaunchKernelGGL((k_kinematic_prep<WITHDRAW, DAM>), dim3((unsigned)((A.ncells + 255) / 256)), dim3(256), 0, st,
-                     (gptr<const int64_t>)M.ptr, (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff,
-                     (gptr<const double>)qirr, (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
-                     (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
-                     (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
-                     (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)er, A.ncells, A.cld, dts, dm);
-}
 }  // namespace
 
 void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const OGridMap& M,
@@ -529,18 +480,45 @@ void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const 
   if (A.ncells <= 0) return;
   const double dts = dt / (double)A.nsub;  // K0
   double *src = K.rows + KW_ER_A * A.cld, *dst = K.rows + KW_ER_B * A.cld;
-  // (I6: the same launch in the flood form)
-  if (Dm.rows) {
-    if (qirr) launch_kw_prep<true, true>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
-    else launch_kw_prep<false, true>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
-  } else {
-    if (qirr) launch_kw_prep<true, false>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
-    else launch_kw_prep<false, false>(A, K, Dm, M, qrunoff, qirr, qsurf, qh2osfc, src, dt, dts, st);
-  }
+  const dim3 grid((unsigned)((A.ncells + 255) / 256)), block(256);
+  // the DAM form of both kernels exactly while the reservoirs' rows are there
+  with_bool(Dm.rows != nullptr, [&](auto dam) {
+    with_bool(qirr != nullptr, [&](auto withdraw) {
+      constexpr bool DAM = decltype(dam)::value;
+      DamRows<DAM> dm;
+      if constexpr (DAM) dm = dam_rows(Dm, dt);
+      hipLaunchKernelGGL((k_kinematic_prep<decltype(withdraw)::value, DAM>), grid, block, 0, st, (gptr<const int64_t>)M.ptr,
+                         (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff, (gptr<const double>)qirr,
+                         (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
+                         (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
+                         (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
+                         (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts, dm);
+    });
+  });
   for (int s = 0; s < A.nsub; s++) {
-    const bool first = s == 0, last = s == A.nsub - 1;
-    if (F.rows) launch_kw_step<true>(A, K, F, Dm, src, dst, dts, first, last, st);
-    else launch_kw_step<false>(A, K, F, Dm, src, dst, dts, first, last, st);
+    // (I6: the same launch in the flood form)
+    with_bool(F.rows != nullptr, [&](auto flood) {
+      with_npad(A.npad, [&](auto npad) {
+        with_bool(s == 0, [&](auto first) {
+          with_bool(s == A.nsub - 1, [&](auto last) {
+            with_bool(Dm.rows != nullptr, [&](auto dam) {
+              constexpr bool FLOOD = decltype(flood)::value, DAM = decltype(dam)::value;
+              FloodRows<FLOOD> fl;
+              if constexpr (FLOOD) fl = FloodRows<true>{(gptr<double>)F.rows, (gptr<const double>)F.tab};
+              DamRows<DAM> dm;
+              if constexpr (DAM) dm = dam_rows(Dm, dts * (double)A.nsub);
+              hipLaunchKernelGGL((k_kinematic_step<decltype(npad)::value, decltype(first)::value, decltype(last)::value, FLOOD, DAM>), grid,
+                                 block, 0, st, (gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld),
+                                 (gptr<double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)src, (gptr<double>)dst,
+                                 (gptr<const double>)K.par, (gptr<const double>)A.area, (gptr<const int32_t>)A.up,
+                                 (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<const double>)(K.rows + KW_QSUB * A.cld),
+                                 (gptr<double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells,
+                                 A.cld, dts, (double)A.nsub, fl, dm);
+            });
+          });
+        });
+      });
+    });
     double* const t = src;
     src = dst;
     dst = t;

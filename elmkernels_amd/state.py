@@ -585,11 +585,21 @@ class ELMState:
     def routing_init(self, volr=None, qout_sum=None, ncalls=0):
         """VOLR and QOUT_SUM from [ncells] each (None: zeros), QIN and QOUT zeros, the call count = ncalls: a restart file's values.
         Synchronises."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (volr, qout_sum)]
+        self._routing_init("routing_init", (volr, qout_sum), int(ncalls))
+
+    def _routing_init(self, name, rows, *more):
+        """elmk_<name>(ctx, rows ..., more ...): each row an optional [ncells] array (None: the call's default)."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in rows]
         for v in a:
             if v is not None and v.size != getattr(self, "routing_ncells", v.size):
-                raise ValueError(f"routing_init: {v.size} values for {self.routing_ncells} cells")
-        self._chk(self.lib.elmk_routing_init(self.ctx, *(None if v is None else _p(v) for v in a), int(ncalls)), "routing_init")
+                raise ValueError(f"{name}: {v.size} values for {self.routing_ncells} cells")
+        self._chk(getattr(self.lib, "elmk_" + name)(self.ctx, *(None if v is None else _p(v) for v in a), *more), name)
+
+    def _routing_budget(self, name, n):
+        """elmk_<name>(ctx, sums): float64 [n]."""
+        out = np.empty(n, dtype=np.float64)
+        self._chk(getattr(self.lib, "elmk_" + name)(self.ctx, _p(out)), name)
+        return out
 
     def routing(self, dt):
         """One call: QIN from the water balance's QRUNOFF row, then nsub sub-steps.  After water_balance(dt); nsub + 1 launches,
@@ -621,9 +631,7 @@ class ELMState:
 
     def routing_budget(self):
         """float64 [3]: the sums of VOLR and QIN and the sum of QOUT over the outlets (routing.budget).  Synchronises."""
-        out = np.empty(3, dtype=np.float64)
-        self._chk(self.lib.elmk_routing_budget(self.ctx, _p(out)), "routing_budget")
-        return out
+        return self._routing_budget("routing_budget", 3)
 
     def routing_clear(self):
         self._chk(self.lib.elmk_routing_clear(self.ctx), "routing_clear")
@@ -641,17 +649,11 @@ class ELMState:
 
     def routing_kinematic_init(self, wh=None, wt=None):
         """WH and WT from [ncells] each (None: zeros), QSUR zeros; VOLR, QOUT_SUM and the count stay routing_init's.  Synchronises."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (wh, wt)]
-        for v in a:
-            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
-                raise ValueError(f"routing_kinematic_init: {v.size} values for {self.routing_ncells} cells")
-        self._chk(self.lib.elmk_routing_kinematic_init(self.ctx, *(None if v is None else _p(v) for v in a)), "routing_kinematic_init")
+        self._routing_init("routing_kinematic_init", (wh, wt))
 
     def routing_kinematic_budget(self):
         """float64 [2]: the sums of WH and WT (routing.kinematic_budget).  Synchronises."""
-        out = np.empty(2, dtype=np.float64)
-        self._chk(self.lib.elmk_routing_kinematic_budget(self.ctx, _p(out)), "routing_kinematic_budget")
-        return out
+        return self._routing_budget("routing_kinematic_budget", 2)
 
     def routing_kinematic_clear(self):
         """Back to the linear scheme; VOLR, QOUT_SUM and the count stay."""
@@ -672,16 +674,11 @@ class ELMState:
 
     def routing_inundation_init(self, wf=None):
         """WF from [ncells] (None: zeros), the two diagnostics zeros; VOLR, WH and WT stay their own entries'.  Synchronises."""
-        v = None if wf is None else np.ascontiguousarray(wf, dtype=np.float64).reshape(-1)
-        if v is not None and v.size != getattr(self, "routing_ncells", v.size):
-            raise ValueError(f"routing_inundation_init: {v.size} values for {self.routing_ncells} cells")
-        self._chk(self.lib.elmk_routing_inundation_init(self.ctx, None if v is None else _p(v)), "routing_inundation_init")
+        self._routing_init("routing_inundation_init", (wf,))
 
     def routing_inundation_budget(self):
         """float64 [1]: the sum of WF (routing.inundation_budget).  Synchronises."""
-        out = np.empty(1, dtype=np.float64)
-        self._chk(self.lib.elmk_routing_inundation_budget(self.ctx, _p(out)), "routing_inundation_budget")
-        return out
+        return self._routing_budget("routing_inundation_budget", 1)
 
     def routing_inundation_clear(self):
         """Back to the channel without banks; WF is dropped, VOLR stays."""
@@ -704,11 +701,7 @@ class ELMState:
 
     def routing_reservoir_init(self, res=None, krls=None):
         """RES from [ncells] (None: zeros), KRLS from [ncells] (None: 1.0), RES_TAKE zeros.  Synchronises."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (res, krls)]
-        for v in a:
-            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
-                raise ValueError(f"routing_reservoir_init: {v.size} values for {self.routing_ncells} cells")
-        self._chk(self.lib.elmk_routing_reservoir_init(self.ctx, *(None if v is None else _p(v) for v in a)), "routing_reservoir_init")
+        self._routing_init("routing_reservoir_init", (res, krls))
 
     def routing_reservoir_time(self, month, begins=False):
         """The month (0 .. 11) of the following routing() calls, and whether the next one is the call whose step starts at 00:00 of the
@@ -717,9 +710,7 @@ class ELMState:
 
     def routing_reservoir_budget(self):
         """float64 [2]: the sums of RES and RES_TAKE (routing.reservoir_budget).  Synchronises."""
-        out = np.empty(2, dtype=np.float64)
-        self._chk(self.lib.elmk_routing_reservoir_budget(self.ctx, _p(out)), "routing_reservoir_budget")
-        return out
+        return self._routing_budget("routing_reservoir_budget", 2)
 
     def routing_reservoir_clear(self):
         """Back to the free-flowing channel; RES is dropped, VOLR stays."""
