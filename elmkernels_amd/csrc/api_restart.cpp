@@ -34,6 +34,7 @@ constexpr size_t RST_CHUNK = (size_t)64 << 20;  // bytes of image per staging ch
 constexpr int RST_MAX_PIECES = 8192;            // per chunk (grid.y)
 constexpr uint32_t RST_V_ROUTING = ELMK_RESTART_VERSION_ROUTING;
 constexpr uint32_t RST_V_RESERVOIR = ELMK_RESTART_VERSION_RESERVOIR;
+constexpr uint32_t RST_V_HEAT = ELMK_RESTART_VERSION_HEAT;
 
 uint64_t fmix64(uint64_t k)
 {
@@ -135,7 +136,7 @@ const RstKind RST_OPTIONAL[] = {
     {ELMK_RESTART_IRRSUP, ELMK_RESTART_VERSION_ROUTING, "the river supply limit's UNMET_SUM", "elmk_irrigation_supply_enable with ELMK_OPT_RESTART_CELLS on",
      [](Ctx c) { return c->restart_cells && c->route.mem && c->irrsup_rows ? 1 : 0; },
      [](Ctx c, int) { return RstRows{ELMK_IRRSUP_UNMET_SUM, 1, c->irrsup_rows + (size_t)ELMK_IRRSUP_UNMET_SUM * (size_t)c->route.cld}; }, true, false}};
-constexpr uint32_t RST_MAX_VERSION = RST_V_RESERVOIR;
+constexpr uint32_t RST_MAX_VERSION = RST_V_HEAT;
 static_assert(ELMK_HYD_WA == ELMK_HYD_ZWT + 1 && ELMK_IRR_NLEFT == ELMK_IRR_RATE + 1, "the two rows of the image");
 
 RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
@@ -169,6 +170,7 @@ RstLayout rst_layout(elmk_ctx* ctx, int64_t gcol0)
     }
   }
   if ((L.kinds & (1u << ELMK_RESTART_ROUTING)) && ctx->route.dam.mem) L.version = std::max(L.version, RST_V_RESERVOIR);  // (RES and KRLS)
+  if ((L.kinds & (1u << ELMK_RESTART_ROUTING)) && ctx->route.heat.mem) L.version = std::max(L.version, RST_V_HEAT);  // (TT and TR)
   // the accumulator table follows the history entries
   L.header_bytes = align_up(sizeof(elmk_restart_header) + (L.version >= 2 ? 8 : 0) + (L.version >= RST_V_ROUTING ? 8 : 0) + L.acc.size() * sizeof(elmk_restart_accum) +
                                 L.ent.size() * sizeof(elmk_restart_entry) + L.sec.size() * sizeof(elmk_restart_section),
@@ -441,7 +443,8 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   }
   unsigned kinds = word[0] ? 1u << ELMK_RESTART_ACCUM : 0u;
   for (const RstKind& K : RST_OPTIONAL) kinds |= K.implied && K.version == H.version ? 1u << K.kind : 0u;
-  if (H.version == RST_V_RESERVOIR) kinds |= 1u << ELMK_RESTART_ROUTING;  // (version 7 is version 6 with the reservoirs' two sections)
+  // (version 7 is version 6 with the reservoirs' two sections, version 8 version 6 with the stream temperature's two)
+  if (H.version == RST_V_RESERVOIR || H.version == RST_V_HEAT) kinds |= 1u << ELMK_RESTART_ROUTING;
   std::vector<std::pair<int32_t, int64_t>> img_cells, ctx_cells;  // (id, extent) of the cell sections of the routing state
   if (H.version >= ELMK_RESTART_VERSION_HYDROLOGY) {
     const uint64_t at = (uint64_t)(p - in) + (uint64_t)H.nentries * sizeof(elmk_restart_entry) + (uint64_t)word[0] * sizeof(elmk_restart_accum);
@@ -468,7 +471,7 @@ int elmk_restart_load(elmk_ctx* ctx, int64_t gcol0, const void* image, int64_t b
   if (img_cells != ctx_cells)
     return invalid(ctx, "elmk_restart_load: the image's routing state differs from the context's: another ncells (elmk_routing_enable), or the "
                         "kinematic-wave scheme (elmk_routing_kinematic_enable), the floodplain inundation (elmk_routing_inundation_enable) or "
-                        "the reservoirs (elmk_routing_reservoir_enable) on in one and off in the other");
+                        "the reservoirs (elmk_routing_reservoir_enable) or the stream temperature (elmk_routing_heat_enable) on in one and off in the other");
   // a differing entry table; the feature is named where the image holds an entry over a feature row (ELMK_RESTART_ROW_FIELD, include/
   // elmk_restart.def) that the context has not got in that place
   const auto entries_differ = [&]() {

@@ -1,20 +1,20 @@
 // api_routing.cpp - the river stage (k_routing.hip; include/elmk.h "runoff routing", "kinematic-wave routing", "floodplain inundation",
-// "reservoirs").  The stage has four parts, each with one allocation held exactly while the part is on (elmk_ctx.h: Routing): the
-// base part, the kinematic-wave scheme on top of it, and that scheme's two extensions.  The table PARTS describes each part once - its
+// "reservoirs", "stream temperature").  The stage has five parts, each with one allocation held exactly while the part is on (elmk_ctx.h: Routing): the
+// base part, the kinematic-wave scheme on top of it, and that scheme's three extensions.  The table PARTS describes each part once - its
 // rows, its public row ids, what its budget reduces, what the restart image keeps of it, what it needs and how its refusals read - and
-// the part_* helpers below are what the four families of entry points share: how a call enters, how an enable, an init, a budget and a
+// the part_* helpers below are what the five families of entry points share: how a call enters, how an enable, an init, a budget and a
 // clear go.  An entry point keeps what is its own: its argument checks and the arrays it uploads.
 #include "elmk_ctx.h"
 
 namespace {
 using Routing = elmk_ctx::Routing;
 
-enum { BASE, KW, FP, DAM, NPARTS };
+enum { BASE, KW, FP, DAM, HEAT, NPARTS };
 struct PartDesc {
   Routing::Part Routing::*at;  // where the part is held (null: the base part, in Routing itself)
   int needs;                   // the part that has to be on before this one (-1: none)
   int nrows;                   // the rows of its allocation
-  int id0, nids, row_of[4];    // its public rows ELMK_ROUTE_* id0 .. id0 + nids - 1, and the row of the allocation behind each
+  int id0, nids, row_of[7];    // its public rows ELMK_ROUTE_* id0 .. id0 + nids - 1, and the row of the allocation behind each
   int nbudget;                 // its budget reduces this many leading rows (elmk_kernels.h lays them first)
   int nstate, state[2];        // its prognostic rows (ELMK_ROUTE_*) in the order of the restart image
   const char* label;           // in the text of a HIP error
@@ -37,7 +37,11 @@ constexpr PartDesc PARTS[NPARTS] = {
     // (the reservoirs' kernel is the scheme's; their rows are in range exactly while they are on)
     {&Routing::dam, KW, DAM_NROWS, ELMK_ROUTE_RES, 3, {DAM_RES, DAM_KRLS, DAM_TAKE}, 2, 2, {ELMK_ROUTE_RES, ELMK_ROUTE_KRLS},
      "reservoirs", "elmk_routing_reservoir_enable", "elmk_routing_reservoir_clear", "the extension is not on", "row out of range",
-     "the reservoirs are on"}};
+     "the reservoirs are on"},
+    // (the stream temperature's kernel is the scheme's; it excludes the two extensions before it: heat_excludes)
+    {&Routing::heat, KW, HT_NROWS, ELMK_ROUTE_TT, 7, {HT_TT, HT_TR, HT_HEAT, HT_HIN, HT_HSRF, HT_HADJ, HT_HOUT}, 5, 2, {ELMK_ROUTE_TT, ELMK_ROUTE_TR},
+     "stream temperature", "elmk_routing_heat_enable", "elmk_routing_heat_clear", "the extension is not on", "row out of range",
+     "the stream temperature is on"}};
 static_assert(ELMK_ROUTE_VOLR == 0 && ELMK_ROUTE_QIN == 1 && ELMK_ROUTE_QOUT == 2 && ELMK_ROUTE_QOUT_SUM == 3, "four rows");
 static_assert(ELMK_ROUTE_WH - 4 == KW_WH && ELMK_ROUTE_WT - 4 == KW_WT && ELMK_ROUTE_QSUR - 4 == KW_QSUR, "three rows");
 static_assert(ELMK_KW_NPARAM == KINEMATIC_NPARAM, "the parameter rows of elmk_maps.h");
@@ -45,7 +49,11 @@ static_assert(ELMK_ROUTE_WF - 7 == FP_WF && ELMK_ROUTE_FLOOD_DEPTH - 7 == FP_DEP
 static_assert(ELMK_FP_NPROF == INUNDATION_NPROF && FP_VB - FP_E == ELMK_FP_NPROF && FP_NTAB - FP_VB == ELMK_FP_NPROF, "the profile of elmk_maps.h");
 static_assert(ELMK_ROUTE_RES == 10 && ELMK_ROUTE_KRLS == 11 && ELMK_ROUTE_RES_TAKE == 12, "three rows");
 static_assert(DAM_NTAB == RESERVOIR_NTAB && DAM_TARGET + RESERVOIR_NMONTH == DAM_NTAB, "the tables of elmk_maps.h");
-static_assert(PARTS[0].nstate + PARTS[1].nstate + PARTS[2].nstate + PARTS[3].nstate == elmk::ROUTE_STATE_MAX, "the rows of the image");
+static_assert(ELMK_ROUTE_TT == 13 && ELMK_ROUTE_HOUT == 19 && HT_HEAT == 0 && HT_HIN == 1 && HT_HSRF == 2 && HT_HADJ == 3 && HT_OUTLET == 4, "seven rows; H7's five lead");
+static_assert(HEAT_NSUBLEV == 15, "the soil layers of elmk_maps.h");
+// (the heat excludes the inundation and the reservoirs, so the image never holds more than the first four parts' rows)
+static_assert(PARTS[0].nstate + PARTS[1].nstate + PARTS[2].nstate + PARTS[3].nstate == elmk::ROUTE_STATE_MAX &&
+                  PARTS[0].nstate + PARTS[1].nstate + PARTS[4].nstate <= elmk::ROUTE_STATE_MAX, "the rows of the image");
 
 const DevBuf<char>& part_mem(const Routing& T, const PartDesc& P) { return P.at ? (T.*P.at).mem : T.mem; }
 double* part_rows(const Routing& T, const PartDesc& P) { return P.at ? (T.*P.at).rows : T.rows; }
@@ -69,6 +77,14 @@ void part_reset(Routing& T, int p)
   if (p == BASE) T = Routing{};  // (and every other part with it)
   else T.*PARTS[p].at = Routing::Part{};
   if (p == DAM) T.dam_mstart = nullptr, T.dam_time = 0;
+  if (p == HEAT) T.heat_sublev = 0;
+}
+
+// the heat and the scheme's two other extensions exclude each other: "<who>: <on> (<clear> first)" while part q is on
+int part_excludes(elmk_ctx* ctx, int q, const char* who)
+{
+  const PartDesc& Q = PARTS[q];
+  return part_mem(ctx->route, Q) ? invalid(ctx, (std::string(who) + ": " + Q.on + " (" + Q.clear + " first)").c_str()) : ELMK_OK;
 }
 
 // one host array onto the device, enqueued; true: it failed (what: in the error's text)
@@ -136,10 +152,16 @@ int part_budget(elmk_ctx* ctx, int p, const char* who, double* sums)
   const Routing& T = ctx->route;
   const int n = PARTS[p].nbudget;
   if (p == BASE) launch_routing_outlets(route_args(ctx), T.down, ctx->stream);  // (R6's third row)
-  launch_min_max_sum(part_rows(T, PARTS[p]), T.cld, T.ncells, n, T.part, T.out, ctx->stream);
-  HIPCHK(hipGetLastError());
-  double mms[9];
-  HIPCHK(hipMemcpyAsync(mms, T.out, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (p == HEAT)  // (H7's fifth row)
+    launch_routing_outlet_row(T.down, T.heat.rows + (size_t)HT_HOUT * (size_t)T.cld, T.heat.rows + (size_t)HT_OUTLET * (size_t)T.cld, T.ncells, ctx->stream);
+  double mms[18];
+  // (the base part's partials hold three rows: a longer budget goes through them three rows at a time, in stream order)
+  for (int k0 = 0; k0 < n; k0 += 3) {
+    const int m = n - k0 < 3 ? n - k0 : 3;
+    launch_min_max_sum(part_rows(T, PARTS[p]) + (size_t)k0 * (size_t)T.cld, T.cld, T.ncells, m, T.part, T.out, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(mms + 3 * k0, T.out, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (int k = 0; k < n; k++) sums[k] = mms[3 * k + 2];
   return ELMK_OK;
@@ -176,14 +198,26 @@ void route_launch(elmk_ctx* ctx, double dt, bool run)
   const OGridMap G{M.ptr, M.col, M.w, M.nrows, 0.0};
   const double* const qrunoff = ctx->wb_rows + (size_t)ELMK_WB_QRUNOFF * ld;
   const double* const qirr = T.withdraw ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * ld : nullptr;
-  if (T.kw.mem)  // the scheme switch: the kinematic-wave scheme exactly while its memory is held
+  if (T.kw.mem) {  // the scheme switch: the kinematic-wave scheme exactly while its memory is held
+    HeatArgs H{};
+    if (T.heat.mem) {
+      H.rows = T.heat.rows;
+      H.ksw = T.heat.tab;
+      static const int fields[HTF_N] = {ELMK_FIELD_forc_tbot, ELMK_FIELD_forc_pbot, ELMK_FIELD_forc_qbot,  ELMK_FIELD_forc_lwrad, ELMK_FIELD_forc_u,
+                                        ELMK_FIELD_forc_v,    ELMK_FIELD_forc_solad, ELMK_FIELD_forc_solai, ELMK_FIELD_t_grnd,     ELMK_FIELD_t_soisno};
+      for (int k = 0; k < HTF_N; k++) H.fields[k] = ctx->fptr[fields[k]];
+      H.dtype = store_dtype(ELMK_F64);
+      H.sublev = T.heat_sublev;
+      H.ld = ctx->ld;
+    }
     launch_routing_kinematic(route_args(ctx), KinematicArgs{T.kw.rows, T.kw.tab}, FloodArgs{T.fp.rows, T.fp.tab},
                              DamArgs{T.dam.rows, T.dam.tab, T.dam_mstart, run ? ctx->run.table : nullptr, run ? ctx->run.cursor : nullptr,
                                      T.dam_time},
-                             G, qrunoff, qirr, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
+                             H, G, qrunoff, qirr, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
                              ctx->stream);
-  else
+  } else {
     launch_routing(route_args(ctx), G, qrunoff, qirr, dt, ctx->stream);
+  }
 }
 
 const double* route_row(const elmk_ctx* ctx, int which, const char** why)
@@ -383,6 +417,7 @@ int elmk_routing_inundation_enable(elmk_ctx* ctx, const double* rdepth, const do
   if (int rc = part_enter(ctx, KW, who)) return rc;
   Routing& T = ctx->route;
   if (T.fp.mem) return invalid(ctx, "elmk_routing_inundation_enable: already on");
+  if (int rc = part_excludes(ctx, HEAT, who)) return rc;  // (heat on a floodplain is a later change)
   if (!rdepth || !eprof) return invalid(ctx, "elmk_routing_inundation_enable: null argument");
   int64_t cell = -1;
   const char* const text = inundation_check(T.ncells, rdepth, eprof, nullptr, nullptr, nullptr, T.cld, nullptr, &cell);
@@ -428,6 +463,7 @@ int elmk_routing_reservoir_enable(elmk_ctx* ctx, const double* cap, const double
   if (int rc = part_enter(ctx, KW, who)) return rc;
   Routing& T = ctx->route;
   if (T.dam.mem) return invalid(ctx, "elmk_routing_reservoir_enable: already on");
+  if (int rc = part_excludes(ctx, HEAT, who)) return rc;  // (heat in a stratified reservoir is a later change)
   if (!cap || !target || !beta || !mstart) return invalid(ctx, "elmk_routing_reservoir_enable: null argument");
   std::vector<double> tab;
   std::vector<int32_t> ms;
@@ -477,5 +513,52 @@ int elmk_routing_reservoir_time(elmk_ctx* ctx, int month, int begins)
 int elmk_routing_reservoir_budget(elmk_ctx* ctx, double* sums) { return part_budget(ctx, DAM, "elmk_routing_reservoir_budget", sums); }
 
 int elmk_routing_reservoir_clear(elmk_ctx* ctx) { return part_clear(ctx, DAM, "elmk_routing_reservoir_clear"); }
+
+int elmk_routing_heat_enable(elmk_ctx* ctx, int sublev, const double* shade)
+{
+  const char* who = "elmk_routing_heat_enable";
+  if (int rc = part_enter(ctx, KW, who)) return rc;
+  Routing& T = ctx->route;
+  if (T.heat.mem) return invalid(ctx, "elmk_routing_heat_enable: already on");
+  if (int rc = part_excludes(ctx, FP, who)) return rc;
+  if (int rc = part_excludes(ctx, DAM, who)) return rc;
+  std::vector<double> ksw;
+  int64_t cell = -1;
+  const char* const text = heat_check(T.ncells, sublev, shade, T.cld, &ksw, &cell);
+  if (int rc = invalid_at(ctx, who, text, cell)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the form of its moment)
+  const size_t cld = (size_t)T.cld;
+  const std::vector<double> tfrz(cld, 273.15);  // TT and TR start at TFRZ, as _init leaves them
+  T.heat_sublev = sublev;
+  return part_on(
+      ctx, HEAT,
+      [&](Carve& L) {
+        L.take(T.heat.rows, (size_t)HT_NROWS * cld * sizeof(double));
+        L.take(T.heat.tab, cld * sizeof(double));
+      },
+      [&] {
+        return upload(ctx, T.heat.tab, ksw.data(), ksw.size(), "hipMemcpy(stream temperature KSW)") ||
+               upload(ctx, T.heat.rows + HT_TT * cld, tfrz.data(), cld, "hipMemcpy(stream temperature TT)") ||
+               upload(ctx, T.heat.rows + HT_TR * cld, tfrz.data(), cld, "hipMemcpy(stream temperature TR)");
+      });
+}
+
+int elmk_routing_heat_init(elmk_ctx* ctx, const double* tt, const double* tr)
+{
+  const char* who = "elmk_routing_heat_init";
+  if (int rc = part_enter(ctx, HEAT, who)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  const Routing& T = ctx->route;
+  const std::vector<double> tfrz((size_t)T.cld, 273.15);
+  if (int rc = part_init(ctx, HEAT, {{HT_TT, tt}, {HT_TR, tr}})) return rc;
+  if (!tt) HIPCHK(hipMemcpyAsync(T.heat.rows + HT_TT * (size_t)T.cld, tfrz.data(), tfrz.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (!tr) HIPCHK(hipMemcpyAsync(T.heat.rows + HT_TR * (size_t)T.cld, tfrz.data(), tfrz.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  return synced(ctx);  // (`tfrz` lives until here)
+}
+
+int elmk_routing_heat_budget(elmk_ctx* ctx, double* sums) { return part_budget(ctx, HEAT, "elmk_routing_heat_budget", sums); }
+
+int elmk_routing_heat_clear(elmk_ctx* ctx) { return part_clear(ctx, HEAT, "elmk_routing_heat_clear"); }
 
 }  // extern "C"

@@ -164,10 +164,11 @@ struct StepKey {
   bool route_withdraw = false;               // the routing stage is in the step (its flag) and subtracts the irrigation's withdrawal
   bool irr_supply = false;                   // the irrigation stage is in the step and the river supply limit's launch follows it
   bool route_dam = false;                    // the routing stage is in the step and takes the reservoirs' form (its time from the pad word)
+  bool route_heat = false;                   // the routing stage is in the step and takes the stream temperature's form
   auto tie() const
   {
     return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw,
-                    irr_supply, route_dam);
+                    irr_supply, route_dam, route_heat);
   }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
@@ -289,7 +290,7 @@ struct elmk_ctx {
   // while the limit is on
   DevBuf<double> irrsup_rows;
   double irrsup_thr = 0.0;
-  // The river stage (elmk_routing_*) has four parts, each with one allocation held exactly while the part is on; api_routing.cpp's
+  // The river stage (elmk_routing_*) has five parts, each with one allocation held exactly while the part is on; api_routing.cpp's
   // table PARTS says the rest about each (rows, public ids, budget, restart rows, refusals).
   //   base (elmk_routing_enable): `mem` holds the rows [ROUTE_NROWS][cld], KOUT and area [cld], the upstream map [npad][cld], down
   //     [cld] and the budgets' reduction partials [3][ELMK_CONS_NPART][3] and triples [3][3].  ncalls: the calls since the last
@@ -298,6 +299,7 @@ struct elmk_ctx {
   //   fp (elmk_routing_inundation_*): the floodplain's rows [FP_NROWS][cld]; tab: the host's tables [FP_NTAB][cld]
   //   dam (elmk_routing_reservoir_*): the reservoirs' rows [DAM_NROWS][cld]; tab: the host's tables [DAM_NTAB][cld]; beside it, in
   //     the same allocation, MSTART [cld].  dam_time: the month | begins << 4 of elmk_routing_reservoir_time, what the stepwise calls read
+  //   heat (elmk_routing_heat_*): the stream temperature's rows [HT_NROWS][cld]; tab: KSW [cld].  heat_sublev: the soil layer of H1
   // route_launch takes the scheme and the forms whose memory is there.
   struct Routing {
     struct Part {
@@ -317,9 +319,10 @@ struct elmk_ctx {
     int32_t* down = nullptr;
     double* part = nullptr;
     double* out = nullptr;
-    Part kw, fp, dam;
+    Part kw, fp, dam, heat;
     int32_t* dam_mstart = nullptr;
     int32_t dam_time = 0;
+    int heat_sublev = 0;
   } route;
   bool restart_cells = false;  // ELMK_OPT_RESTART_CELLS: the image carries the routing state (version 6)
   bool snowage_set = false;
@@ -508,7 +511,7 @@ const double* route_row(const elmk_ctx* ctx, int which, const char** why);
 size_t route_bytes(const elmk_ctx* ctx);  // the device bytes of the parts that are on
 int route_zero_rows(elmk_ctx* ctx);       // every row of every part that is on zero (enqueued)
 // the routing state of the restart image (ELMK_OPT_RESTART_CELLS): the ELMK_ROUTE_* of the prognostic rows the parts hold at this
-// moment, in image order (VOLR, QOUT_SUM, WH, WT, WF, RES, KRLS); returns their number
+// moment, in image order (VOLR, QOUT_SUM, WH, WT, WF, RES, KRLS, or TT, TR behind WT: the heat excludes the two before it); returns their number
 constexpr int ROUTE_STATE_MAX = 7;
 int route_state_rows(const elmk_ctx* ctx, int* ids);
 constexpr int ALT_NROWS = 3;  // api_rows.cpp

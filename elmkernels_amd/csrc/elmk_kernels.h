@@ -342,10 +342,31 @@ struct DamArgs {
 };
 constexpr int RUN_PAD_DAM_SHIFT = 25;  // above the time of day's 17 bits: the month in four bits, then `begins`
 constexpr int RUN_PAD_TOD_MASK = (1 << (RUN_PAD_DAM_SHIFT - RUN_PAD_TOD_SHIFT)) - 1;
+// stream temperature (elmk_routing_heat_*; include/elmk.h "stream temperature", H0 - H9): the extension's fp64 rows [HT_NROWS][cld] and
+// the host's table KSW [cld] behind them.  The first five rows are the ones launch_min_max_sum reduces for H7; HT_OUTLET (HOUT of the
+// outlets, +0.0 elsewhere) is written by launch_routing_outlet_row only.  HT_RAD .. HT_TSUB are H1's rows, written by the K1 launch and
+// read by every sub-step; HT_HR_A / HT_HR_B the two buffers of the heat flow hr = er * TR, used in turn beside KW_ER_A / KW_ER_B.
+// fields: the state fields H1 aggregates, as stored (dtype: ELMK_F64 or ELMK_F32_STORED; ld the level stride), in the order HTF_*
+enum {
+  HT_HEAT = 0, HT_HIN = 1, HT_HSRF = 2, HT_HADJ = 3, HT_OUTLET = 4, HT_HOUT = 5, HT_TT = 6, HT_TR = 7, HT_HR_A = 8, HT_HR_B = 9,
+  HT_RAD = 10, HT_KE = 11, HT_EMS = 12, HT_TA = 13, HT_QA = 14, HT_PA = 15, HT_TSUR = 16, HT_TSUB = 17, HT_NROWS = 18
+};
+enum { HTF_TBOT = 0, HTF_PBOT, HTF_QBOT, HTF_LWRAD, HTF_U, HTF_V, HTF_SOLAD, HTF_SOLAI, HTF_TGRND, HTF_TSOISNO, HTF_N };
+struct HeatArgs {
+  double* rows;
+  const double* ksw;
+  const void* fields[HTF_N];
+  int dtype;
+  int sublev;
+  int64_t ld;
+};
+// dst = src at the outlets (down < 0), +0.0 elsewhere: R6's outlet rule for any cell row
+void launch_routing_outlet_row(const int32_t* down, const double* src, double* dst, int64_t ncells, hipStream_t st);
 // one call: K1 (QIN as R1, QSUR from the hydrology's rows qsurf + qh2osfc, QSUB, the first er) as one launch, then nsub sub-step
 // launches that update WH, WT and VOLR in place; A.kout and ROUTE_VOLR_B are not read.  F.rows not null: the sub-steps take the flood
-// form (I1 - I5).  Dm.rows not null: every launch takes the DAM form (D1 - D4)
-void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const OGridMap& M,
+// form (I1 - I5).  Dm.rows not null: every launch takes the DAM form (D1 - D4).  H.rows not null (F.rows and Dm.rows null): every
+// launch takes the HEAT form (H1 - H6)
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const HeatArgs& H, const OGridMap& M,
                               const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc, double dt,
                               hipStream_t st);
 

@@ -287,6 +287,33 @@ inline const char* reservoir_check(int64_t ncells, const double* cap, const doub
   return nullptr;
 }
 
+// Stream temperature (elmk_routing_heat_enable; include/elmk.h "stream temperature"): sublev in 0 .. 14; shade [ncells] in [0, 1], or
+// null for 0.0 everywhere.  Checks, in this order: ncells, sublev, shade cell by cell.  Returns the text, which names the row, and in
+// *cell the first offending cell (-1 where the text is about no cell); the entry point puts " at cell <cell>" behind the text.
+// nullptr: accepted.  For accepted inputs and dev not null, dev holds H0's KSW = (1.0 - ALBW) * (1.0 - SHADE) as the device reads it,
+// [ld] with ld >= ncells; padding cells 0.
+constexpr int HEAT_NSUBLEV = 15;
+constexpr double HEAT_ALBW = 0.1;
+inline const char* heat_check(int64_t ncells, int sublev, const double* shade, int64_t ld, std::vector<double>* dev, int64_t* cell)
+{
+  if (cell) *cell = -1;
+  if (ncells < 1 || ncells > INT32_MAX) return "ncells outside 1 .. 2^31-1";
+  if (sublev < 0 || sublev >= HEAT_NSUBLEV) return "sublev outside 0 .. 14";
+  const size_t n = (size_t)ncells;
+  if (shade)
+    for (size_t c = 0; c < n; c++)
+      if (!(shade[c] >= 0.0 && shade[c] <= 1.0)) {
+        if (cell) *cell = (int64_t)c;
+        return "SHADE outside [0, 1]";
+      }
+  if (dev) {
+    if (ld < ncells) ld = ncells;
+    dev->assign((size_t)ld, 0.0);
+    for (size_t c = 0; c < n; c++) (*dev)[c] = (1.0 - HEAT_ALBW) * (1.0 - (shade ? shade[c] : 0.0));
+  }
+  return nullptr;
+}
+
 // The reservoirs' calendar, the reference's no-leap year: the month 0 .. 11 of day-of-year doy (0 = 1 January; any other doy is taken
 // modulo 365), and whether a step with (doy, decday) starts at 00:00 of the first day of its month: the active layer's rollover test,
 // decday == doy + 1.0, on the first doy of each month.

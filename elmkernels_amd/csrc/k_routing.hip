@@ -15,7 +15,8 @@
 // one row less to write and read.  A cell reads 8 (storage) + 8 (KOUT) + 8 (QIN) + 4 npad (map) + 16 per upstream cell and, past the
 // first sub-step, 8 (the flow sum), and writes 16.  The unit carries no nontemporal hint: none has been measured for it.
 // The second scheme of the stage, kinematic-wave routing (k_kinematic_prep, k_kinematic_step), follows the linear one below, with its
-// floodplain inundation (k_kinematic_step's FLOOD form) and its reservoirs (both kernels' DAM form).
+// floodplain inundation (k_kinematic_step's FLOOD form), its reservoirs (both kernels' DAM form) and its stream temperature (the HEAT
+// form: k_kinematic_prep<.., HEAT> and k_kinematic_step_heat).
 #include <type_traits>
 
 #include "elmk_dev.h"
@@ -268,19 +269,83 @@ __device__ __forceinline__ double dam_regulate(double e, double res, double krls
 }
 }  // namespace
 
+// ---- stream temperature (include/elmk.h "stream temperature", H0 - H9; elmkernels_amd/routing.py: heat_prep, heat_phi, heat_settle) ----
+// The HEAT form of both kernels: the tributary store and the main channel carry a temperature.  The K1 launch walks the map once for
+// the water's three sums and H1's eight aggregates - sixteen more registers, still one wave's worth of loads per term in flight - and
+// leaves what the sub-steps need of them as eight rows, so a sub-step reads rows and never the map.  What crosses cells is the heat
+// flow hr = er * TR, in two buffers used in turn with er's.  AT, ACHN, WMINT and WMINR are formed from the scheme's parameter rows with
+// H0's operations: the host's bits at 0 bytes instead of four rows.  A sub-step of the form reads TT, TR, hr, H1's eight rows and the
+// four running diagnostics, 120 bytes and 8 per upstream slot, and writes TT, TR, the four diagnostics and hr (or HEAT), 56 bytes.
+// Two exp and four divisions per cell at most, each behind the cell's own condition; no atomics, no LDS, no scratch.
+template <bool HEAT>
+struct HeatRows {};  // the plain form takes nothing: its kernel arguments, instructions and registers stay what they were
+template <>
+struct HeatRows<true> {
+  gptr<double> rows;         // [HT_NROWS][cld]
+  gptr<const double> ksw;    // [cld] (the K1 launch)
+  const void* f[HTF_N];      // the state fields of H1, as stored (the K1 launch)
+  int dtype;                 // ELMK_F64 or ELMK_F32_STORED
+  int64_t ld, tsub_off;      // the fields' level stride; the element offset of level 5 + sublev
+  double ems0;               // H0
+  gptr<const double> hr_old;  // the heat flows of the sub-step's start (the K1 launch: not read)
+  gptr<double> hr_new;        // those of its end (the K1 launch: the first sub-step's)
+};
+
+namespace {
+constexpr double HT_TFRZ = 273.15, HT_TMAX = 313.15, HT_RHOCP = 4188000.0, HT_EMIS = 0.97, HT_CPAIR = 1004.64, HT_LV = 2.501e6,
+                 HT_RAIR = 287.04, HT_CEX = 1.3e-3, HT_DMIN = 1e-3;
+
+// a state field's element as stored, widened
+__device__ __forceinline__ double heat_ld(const void* p, int dtype, int64_t i)
+{
+  return dtype == ELMK_F32_STORED ? (double)((const ELMK_GLOBAL float*)p)[i] : ((const ELMK_GLOBAL double*)p)[i];
+}
+__device__ __forceinline__ double heat_fl(double t) { return t > HT_TFRZ ? t : HT_TFRZ; }
+
+struct HeatCell {
+  double rad, ke, ems, ta, qa, pa;
+};
+// H2
+__device__ __forceinline__ double heat_phi(double T, const HeatCell& x)
+{
+  const double d = T - HT_TFRZ;
+  const double es = 611.2 * elmk_exp((17.67 * d) / (T - 29.65));
+  const double qs = (0.622 * es) / (x.pa - 0.378 * es);
+  const double t2 = T * T;
+  return (x.rad - x.ems * (t2 * t2)) + (x.ke * (HT_CPAIR * (x.ta - T) - HT_LV * (qs - x.qa))) / HT_RHOCP;
+}
+// H5
+__device__ __forceinline__ double heat_settle(double h, double wn, double wmin, double teq, double& adj)
+{
+  double t = teq;
+  bool acted = true;
+  if (wn > wmin) {
+    t = h / wn;
+    acted = false;
+    if (!(t >= HT_TFRZ)) t = HT_TFRZ, acted = true;
+    if (t > HT_TMAX) t = HT_TMAX, acted = true;
+  }
+  adj = acted ? t * wn - h : 0.0;
+  return t;
+}
+}  // namespace
+
 // K1: QIN as k_routing_qin, QSUR from the hydrology's two surface rows in the same order, QSUB, and the er of the first sub-step.
-// DAM: D1, D2 and the first sub-step's D3 for the dam cells
-template <bool WITHDRAW, bool DAM = false>
+// DAM: D1, D2 and the first sub-step's D3 for the dam cells.  HEAT: H1
+template <bool WITHDRAW, bool DAM = false, bool HEAT = false>
 __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
                                                         gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
                                                         gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
                                                         gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
-                                                        gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<DAM> dm)
+                                                        gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<DAM> dm,
+                                                        HeatRows<HEAT> ht)
 {
+  static_assert(!(HEAT && DAM), "the heat and the reservoirs exclude each other");
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncells) return;
   const int64_t p0 = ptr[c], p1 = ptr[c + 1];
   double r = 0.0, i = 0.0, s = 0.0;
+  [[maybe_unused]] double ta = 0.0, pa = 0.0, qa = 0.0, lw = 0.0, ua = 0.0, sw = 0.0, tsur = 0.0, tsub = 0.0;
   for (int64_t p = p0; p < p1; p++) {
     const int32_t k = col[p];
     const double wp = w[p];
@@ -292,6 +357,26 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
     }
     const double z = wp * (qsurf[k] + qh2osfc[k]);
     s = p == p0 ? z : s + z;
+    if constexpr (HEAT) {  // H1's terms
+      const bool first = p == p0;
+      const int dt_ = ht.dtype;
+      const double fu = heat_ld(ht.f[HTF_U], dt_, k), fv = heat_ld(ht.f[HTF_V], dt_, k);
+      const double xt = wp * heat_ld(ht.f[HTF_TBOT], dt_, k), xp = wp * heat_ld(ht.f[HTF_PBOT], dt_, k);
+      const double xq = wp * heat_ld(ht.f[HTF_QBOT], dt_, k), xl = wp * heat_ld(ht.f[HTF_LWRAD], dt_, k);
+      const double xu = wp * sqrt(fu * fu + fv * fv);
+      const double xs = wp * (((heat_ld(ht.f[HTF_SOLAD], dt_, k) + heat_ld(ht.f[HTF_SOLAD], dt_, ht.ld + k)) +
+                               heat_ld(ht.f[HTF_SOLAI], dt_, k)) + heat_ld(ht.f[HTF_SOLAI], dt_, ht.ld + k));
+      const double xg = wp * heat_fl(heat_ld(ht.f[HTF_TGRND], dt_, k));
+      const double xb = wp * heat_fl(heat_ld(ht.f[HTF_TSOISNO], dt_, ht.tsub_off + k));
+      ta = first ? xt : ta + xt;
+      pa = first ? xp : pa + xp;
+      qa = first ? xq : qa + xq;
+      lw = first ? xl : lw + xl;
+      ua = first ? xu : ua + xu;
+      sw = first ? xs : sw + xs;
+      tsur = first ? xg : tsur + xg;
+      tsub = first ? xb : tsub + xb;
+    }
   }
   [[maybe_unused]] const double rn = r;
   if constexpr (WITHDRAW) r = r - i;
@@ -328,7 +413,33 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
   route_st(qin + c, q);
   route_st(qsur + c, qs);
   route_st(qsub + c, q - qs);
-  er[c] = kw_chan(volr[c], par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+  const double e0 = kw_chan(volr[c], par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
+  er[c] = e0;
+  if constexpr (HEAT) {  // H1
+    double rad = 0.0, ke = 0.0, ems = 0.0;
+    if (p1 > p0) {
+      rad = (ht.ksw[c] * sw + HT_EMIS * lw) / HT_RHOCP;
+      ke = ((pa / (HT_RAIR * ta)) * HT_CEX) * ua;
+      ems = ht.ems0;
+    } else {
+      tsur = tsub = HT_TFRZ;
+      ta = qa = pa = 0.0;
+    }
+    route_st(ht.rows + (HT_RAD * cld + c), rad);
+    route_st(ht.rows + (HT_KE * cld + c), ke);
+    route_st(ht.rows + (HT_EMS * cld + c), ems);
+    route_st(ht.rows + (HT_TA * cld + c), ta);
+    route_st(ht.rows + (HT_QA * cld + c), qa);
+    route_st(ht.rows + (HT_PA * cld + c), pa);
+    route_st(ht.rows + (HT_TSUR * cld + c), tsur);
+    route_st(ht.rows + (HT_TSUB * cld + c), tsub);
+    ht.rows[HT_HEAT * cld + c] = 0.0;
+    ht.rows[HT_HIN * cld + c] = 0.0;
+    ht.rows[HT_HSRF * cld + c] = 0.0;
+    ht.rows[HT_HADJ * cld + c] = 0.0;
+    ht.rows[HT_HOUT * cld + c] = 0.0;
+    route_st(ht.hr_new + c, e0 * ht.rows[HT_TR * cld + c]);
+  }
 }
 
 // ---- floodplain inundation (include/elmk.h "floodplain inundation", I0 - I8; elmkernels_amd/routing.py: inundation_exchange) --------
@@ -399,14 +510,17 @@ __device__ __forceinline__ void fp_exchange(double& v, double& wf, double& h, do
 
 // K3 - K7: one sub-step.  er_old: the flows of the sub-step's start; er_new: those of its end (not written by the LAST one).  FIRST and
 // LAST as k_routing_step's.  FLOOD: the flood form, I1 - I5.  DAM: a dam cell's K6 subtracts its natural er (D4), and the er it forms
-// is regulated (D3).
-template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM = false>
-__global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
-                                                        gptr<double> er_new, gptr<const double> par, gptr<const double> area,
-                                                        gptr<const int32_t> up, gptr<const double> qsur, gptr<const double> qsub,
-                                                        gptr<double> qout, gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts,
-                                                        double dnsub, FloodRows<FLOOD> fl, DamRows<DAM> dm)
+// is regulated (D3).  HEAT: H3 - H6 beside the water (k_kinematic_step_heat).
+// the body of both sub-step kernels below, inlined into each
+namespace {
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM, bool HEAT>
+__device__ __forceinline__ void kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
+                                               gptr<double> er_new, gptr<const double> par, gptr<const double> area, gptr<const int32_t> up,
+                                               gptr<const double> qsur, gptr<const double> qsub, gptr<double> qout, gptr<double> qout_sum,
+                                               int64_t ncells, int64_t cld, double dts, double dnsub, FloodRows<FLOOD> fl, DamRows<DAM> dm,
+                                               HeatRows<HEAT> ht)
 {
+  static_assert(!(HEAT && (FLOOD || DAM)), "the heat excludes the inundation and the reservoirs");
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncells) return;
   int32_t u[NPAD];
@@ -416,6 +530,15 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
   double eu[NPAD];
 #pragma unroll
   for (int p = 0; p < NPAD; p++) eu[p] = er_old[u[p] >= 0 ? (int64_t)u[p] : c];
+  [[maybe_unused]] double fh = 0.0;
+  if constexpr (HEAT) {  // H4's gathers, in flight with K5's
+    double hu[NPAD];
+#pragma unroll
+    for (int p = 0; p < NPAD; p++) hu[p] = ht.hr_old[u[p] >= 0 ? (int64_t)u[p] : c];
+#pragma unroll
+    for (int p = 0; p < NPAD; p++)
+      if (u[p] >= 0) fh = fh + hu[p];
+  }
   const double wh = wh_row[c], wt = wt_row[c], v = volr[c], ar = area[c], qs = qsur[c], qb = qsub[c];
   double qacc = 0.0;
   if constexpr (!FIRST) qacc = qout[c];
@@ -452,6 +575,35 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
   }
   if (vn != vn) vn = __builtin_nan("");
   volr[c] = vn;
+  [[maybe_unused]] double trn = 0.0;
+  if constexpr (HEAT) {  // H3 - H6
+    const double tt = ht.rows[HT_TT * cld + c], tr = ht.rows[HT_TR * cld + c], ho = ht.hr_old[c];
+    const HeatCell x{ht.rows[HT_RAD * cld + c], ht.rows[HT_KE * cld + c], ht.rows[HT_EMS * cld + c],
+                     ht.rows[HT_TA * cld + c],  ht.rows[HT_QA * cld + c], ht.rows[HT_PA * cld + c]};
+    const double tsur = ht.rows[HT_TSUR * cld + c], tsub = ht.rows[HT_TSUB * cld + c];
+    const double hin = ht.rows[HT_HIN * cld + c], hsrf = ht.rows[HT_HSRF * cld + c], hadj = ht.rows[HT_HADJ * cld + c],
+                 hout = ht.rows[HT_HOUT * cld + c];
+    const double at = par[KW_TLEN * cld + c] * par[KW_TWIDTH * cld + c], achn = par[KW_RLEN * cld + c] * par[KW_RWIDTH * cld + c];  // H0
+    const double wmint = at * HT_DMIN, wminr = achn * HT_DMIN;
+    const double teq = heat_fl(x.ta);
+    const double gb = qb > 0.0 ? qb * tsub : qb * tt;  // H3
+    const double sxt = wt > wmint ? at * heat_phi(tt, x) : 0.0;
+    const double hi = eh * tsur + gb;
+    const double h_t = tt * wt + ((hi - et * tt) + sxt) * dts;
+    const double wtn = wt + ((eh - et) + qb) * dts;
+    double adjt, adjr;
+    const double ttn = heat_settle(h_t, wtn, wmint, teq, adjt);
+    const double sxr = v > wminr ? achn * heat_phi(tr, x) : 0.0;  // H4
+    const double h_r = tr * v + (((fh - ho) + et * tt) + sxr) * dts;
+    trn = heat_settle(h_r, vn, wminr, teq, adjr);
+    route_st(ht.rows + (HT_TT * cld + c), ttn);
+    route_st(ht.rows + (HT_TR * cld + c), trn);
+    route_st(ht.rows + (HT_HIN * cld + c), hin + hi * dts);  // H6
+    route_st(ht.rows + (HT_HSRF * cld + c), hsrf + (sxt + sxr) * dts);
+    route_st(ht.rows + (HT_HADJ * cld + c), hadj + (adjt + adjr));
+    route_st(ht.rows + (HT_HOUT * cld + c), hout + ho * dts);
+    if constexpr (LAST) route_st(ht.rows + (HT_HEAT * cld + c), ttn * wtn + trn * vn);
+  }
   qacc = qacc + er;
   if constexpr (LAST) {
     const double mean = qacc / dnsub;
@@ -463,7 +615,33 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
     if constexpr (DAM)
       if (cap > 0.0) e = dam_regulate(e, dm.rows[DAM_RES * cld + c], dm.rows[DAM_KRLS * cld + c], cap, dam_time(dm) & 15, dm, cld, c, dts);
     er_new[c] = e;
+    if constexpr (HEAT) route_st(ht.hr_new + c, e * trn);
   }
+}
+}  // namespace
+
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM = false>
+__global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
+                                                        gptr<double> er_new, gptr<const double> par, gptr<const double> area,
+                                                        gptr<const int32_t> up, gptr<const double> qsur, gptr<const double> qsub,
+                                                        gptr<double> qout, gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts,
+                                                        double dnsub, FloodRows<FLOOD> fl, DamRows<DAM> dm)
+{
+  kinematic_step<NPAD, FIRST, LAST, FLOOD, DAM, false>(wh_row, wt_row, volr, er_old, er_new, par, area, up, qsur, qsub, qout, qout_sum, ncells, cld,
+                                                       dts, dnsub, fl, dm, HeatRows<false>{});
+}
+
+// the HEAT form of the sub-step (H3 - H6): the plain water with the heat beside it, a kernel of its own name so that the kernels above
+// keep theirs
+template <int NPAD, bool FIRST, bool LAST>
+__global__ __launch_bounds__(256) void k_kinematic_step_heat(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr,
+                                                             gptr<const double> er_old, gptr<double> er_new, gptr<const double> par,
+                                                             gptr<const double> area, gptr<const int32_t> up, gptr<const double> qsur,
+                                                             gptr<const double> qsub, gptr<double> qout, gptr<double> qout_sum, int64_t ncells,
+                                                             int64_t cld, double dts, double dnsub, HeatRows<true> ht)
+{
+  kinematic_step<NPAD, FIRST, LAST, false, false, true>(wh_row, wt_row, volr, er_old, er_new, par, area, up, qsur, qsub, qout, qout_sum, ncells, cld,
+                                                        dts, dnsub, FloodRows<false>{}, DamRows<false>{}, ht);
 }
 
 namespace {
@@ -473,47 +651,91 @@ DamRows<true> dam_rows(const DamArgs& Dm, double dt)
 }
 }  // namespace
 
-void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const OGridMap& M,
-                              const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc, double dt,
-                              hipStream_t st)
+void launch_routing_outlet_row(const int32_t* down, const double* src, double* dst, int64_t ncells, hipStream_t st)
+{
+  if (ncells <= 0) return;
+  hipLaunchKernelGGL(k_routing_outlets, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, (gptr<const int32_t>)down,
+                     (gptr<const double>)src, (gptr<double>)dst, ncells);
+}
+
+namespace {
+// hr_old / hr_new: the buffers of this launch (the K1 launch writes hr_new only)
+HeatRows<true> heat_rows(const HeatArgs& H, const double* hr_old, double* hr_new)
+{
+  HeatRows<true> h{};
+  h.rows = (gptr<double>)H.rows;
+  h.ksw = (gptr<const double>)H.ksw;
+  for (int k = 0; k < HTF_N; k++) h.f[k] = H.fields[k];
+  h.dtype = H.dtype;
+  h.ld = H.ld;
+  h.tsub_off = (int64_t)(5 + H.sublev) * H.ld;
+  h.ems0 = (0.97 * 5.67e-8) / 4188000.0;  // H0: (EMIS * SB) / RHOCP
+  h.hr_old = (gptr<const double>)hr_old;
+  h.hr_new = (gptr<double>)hr_new;
+  return h;
+}
+}  // namespace
+
+void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const HeatArgs& H,
+                              const OGridMap& M, const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc,
+                              double dt, hipStream_t st)
 {
   if (A.ncells <= 0) return;
   const double dts = dt / (double)A.nsub;  // K0
   double *src = K.rows + KW_ER_A * A.cld, *dst = K.rows + KW_ER_B * A.cld;
+  // (the heat flows go through their own two buffers in step with er's; null while the heat is off)
+  double *hsrc = H.rows ? H.rows + HT_HR_A * A.cld : nullptr, *hdst = H.rows ? H.rows + HT_HR_B * A.cld : nullptr;
   const dim3 grid((unsigned)((A.ncells + 255) / 256)), block(256);
-  // the DAM form of both kernels exactly while the reservoirs' rows are there
+  // the DAM form of both kernels exactly while the reservoirs' rows are there, the HEAT form exactly while the heat's are (the entry
+  // points keep the heat apart from the reservoirs and the inundation, and only that form is instantiated)
   with_bool(Dm.rows != nullptr, [&](auto dam) {
     with_bool(qirr != nullptr, [&](auto withdraw) {
-      constexpr bool DAM = decltype(dam)::value;
-      DamRows<DAM> dm;
-      if constexpr (DAM) dm = dam_rows(Dm, dt);
-      hipLaunchKernelGGL((k_kinematic_prep<decltype(withdraw)::value, DAM>), grid, block, 0, st, (gptr<const int64_t>)M.ptr,
-                         (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff, (gptr<const double>)qirr,
-                         (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
-                         (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
-                         (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
-                         (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts, dm);
+      with_bool(H.rows != nullptr, [&](auto heat) {
+        constexpr bool DAM = decltype(dam)::value, HEAT = decltype(heat)::value && !DAM;
+        DamRows<DAM> dm;
+        if constexpr (DAM) dm = dam_rows(Dm, dt);
+        HeatRows<HEAT> ht;
+        if constexpr (HEAT) ht = heat_rows(H, nullptr, hsrc);
+        hipLaunchKernelGGL((k_kinematic_prep<decltype(withdraw)::value, DAM, HEAT>), grid, block, 0, st, (gptr<const int64_t>)M.ptr,
+                           (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff, (gptr<const double>)qirr,
+                           (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
+                           (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
+                           (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
+                           (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts, dm, ht);
+      });
     });
   });
   for (int s = 0; s < A.nsub; s++) {
+    const auto args = [&](auto&& launch) {
+      launch((gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld), (gptr<double>)(A.rows + ROUTE_VOLR * A.cld),
+             (gptr<const double>)src, (gptr<double>)dst, (gptr<const double>)K.par, (gptr<const double>)A.area, (gptr<const int32_t>)A.up,
+             (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<const double>)(K.rows + KW_QSUB * A.cld),
+             (gptr<double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells, A.cld, dts, (double)A.nsub);
+    };
     // (I6: the same launch in the flood form)
     with_bool(F.rows != nullptr, [&](auto flood) {
       with_npad(A.npad, [&](auto npad) {
         with_bool(s == 0, [&](auto first) {
           with_bool(s == A.nsub - 1, [&](auto last) {
             with_bool(Dm.rows != nullptr, [&](auto dam) {
+              constexpr int NPAD = decltype(npad)::value;
+              constexpr bool FIRST = decltype(first)::value, LAST = decltype(last)::value;
               constexpr bool FLOOD = decltype(flood)::value, DAM = decltype(dam)::value;
+              if constexpr (!FLOOD && !DAM) {  // (H: the entry points keep the heat apart from the inundation and the reservoirs)
+                if (H.rows) {
+                  args([&](auto... a) {
+                    hipLaunchKernelGGL((k_kinematic_step_heat<NPAD, FIRST, LAST>), grid, block, 0, st, a..., heat_rows(H, hsrc, hdst));
+                  });
+                  return;
+                }
+              }
               FloodRows<FLOOD> fl;
               if constexpr (FLOOD) fl = FloodRows<true>{(gptr<double>)F.rows, (gptr<const double>)F.tab};
               DamRows<DAM> dm;
               if constexpr (DAM) dm = dam_rows(Dm, dts * (double)A.nsub);
-              hipLaunchKernelGGL((k_kinematic_step<decltype(npad)::value, decltype(first)::value, decltype(last)::value, FLOOD, DAM>), grid,
-                                 block, 0, st, (gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld),
-                                 (gptr<double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)src, (gptr<double>)dst,
-                                 (gptr<const double>)K.par, (gptr<const double>)A.area, (gptr<const int32_t>)A.up,
-                                 (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<const double>)(K.rows + KW_QSUB * A.cld),
-                                 (gptr<double>)(A.rows + ROUTE_QOUT * A.cld), (gptr<double>)(A.rows + ROUTE_QOUT_SUM * A.cld), A.ncells,
-                                 A.cld, dts, (double)A.nsub, fl, dm);
+              args([&](auto... a) {
+                hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST, FLOOD, DAM>), grid, block, 0, st, a..., fl, dm);
+              });
             });
           });
         });
@@ -522,6 +744,9 @@ void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const 
     double* const t = src;
     src = dst;
     dst = t;
+    double* const th = hsrc;
+    hsrc = hdst;
+    hdst = th;
   }
 }
 

@@ -27,6 +27,9 @@ the highest among them (OPTIONAL; version 1 without any, byte for byte as before
   version 7, the routing state of a context with the reservoirs on (elmk_routing_reservoir_enable): version 6 with two more
     ROUTING_SECTIONs, ELMK_ROUTE_RES and ELMK_ROUTE_KRLS, after WF.  The device saves and loads it; this module does not read it:
     parse, and with it verify, merge and slice, refuse a version-7 image by its version word, so it is never merged or sliced.
+  version 8, the routing state of a context with the stream temperature on (elmk_routing_heat_enable): version 6 with two more
+    ROUTING_SECTIONs, ELMK_ROUTE_TT and ELMK_ROUTE_TR, after WT.  The device saves and loads it; this module does not read it: its
+    version word lies above MAX_VERSION, so parse, and with it verify, merge and slice, refuse it.
 History entries over feature rows (elmk_column_history_add_row; include/elmk_restart.def): the entry's `field` holds row_field(family, which), a
 value beyond every field id; its section is an ordinary HISTORY or GRIDDED section of one level and the version does not change.  merge
 and slice carry such entries as they carry every entry; entry_row decodes one.
@@ -46,6 +49,7 @@ VERSION_HYDROLOGY = 4  # of an image with the soil hydrology rows ZWT and WA
 VERSION_IRRIGATION = 5  # of an image with the irrigation rows RATE and NLEFT
 VERSION_ROUTING = 6  # of an image with the routing state (ELMK_OPT_RESTART_CELLS): cell sections, and the call count after the count word
 VERSION_RESERVOIR = 7  # ... of a context with the reservoirs on: version 6 plus the ROUTING_SECTIONs RES and KRLS; refused by parse
+VERSION_HEAT = 8  # ... of a context with the stream temperature on: version 6 plus the ROUTING_SECTIONs TT and TR; above MAX_VERSION, refused by parse
 FIELD, HISTORY, GRIDDED, ACCUM_SECTION, ALT_SECTION, HYDROLOGY_SECTION, IRRIGATION_SECTION = 0, 1, 2, 3, 4, 5, 6  # ELMK_RESTART_*
 ROUTING_SECTION, IRRSUP_SECTION = 7, 8  # (cell sections: extent = the routing's ncells, checksummed with g = the cell)
 CELL_SECTIONS = (GRIDDED, ROUTING_SECTION, IRRSUP_SECTION)

@@ -43,7 +43,21 @@ Its reservoirs (include/elmk.h "reservoirs"; the DAM form of both kernels), afte
 
     dam = {"tab": reservoir_tables(cap, target, beta, mstart), "res": res, "krls": krls, "month": m, "begins": b}
     wh, wt, volr, qout, res, krls, take, qin = kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, dam=dam)
+
+Its stream temperature (include/elmk.h "stream temperature"; the HEAT form of both kernels), after S.routing_kinematic_enable and
+without the two extensions above:
+
+    S.routing_heat_enable(sublev=2, shade=shade)
+    S.routing_heat_init(tt_from_restart, tr_from_restart)
+    ... S.routing(dt) and S.run(..., RUN_ROUTING) now carry TT and TR ...
+    tt, tr = S.routing_read(TT), S.routing_read(TR)
+
+    tab = heat_tables(params, sublev, shade)
+    heat = {"tab": tab, "prep": heat_prep(ptr, col, w, columns, tab), "tt": tt, "tr": tr}
+    wh, wt, volr, qout, tt, tr, heat_end, hin, hsrf, hadj, hout = kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, heat=heat)
 """
+import math
+
 import numpy as np
 
 from . import diagnostics, regrid
@@ -273,7 +287,7 @@ def qsur_from_rows(ptr, col, w, qflx_surf, qflx_h2osfc_surf, area):
         return _canon((s * 0.001) * np.asarray(area, dtype=np.float64).reshape(-1))
 
 
-def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True, flood=None, dam=None):
+def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True, flood=None, dam=None, heat=None):
     """One elmk_routing with the scheme on, on the host: K0, K2 - K7.  wh, wt, volr, qin, qsur, area: float64 [ncells]; params
     [11, ncells]; up: upstream_map(down).  Returns (wh_new, wt_new, volr_new, qout).  in_place and cap are the wrong variants the host
     tests hold their checks against, as call's: in_place updates the cells one after another in index order, the upstream flows taken
@@ -283,7 +297,13 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
     dam: the DAM form ("reservoirs", D0 - D5), a dict with "tab" (reservoir_tables), "res" and "krls" [ncells], "month" (0 .. 11) and
     "begins"; optional "withdrawal" = (rn, i), R1's aggregates of QRUNOFF and QFLX_IRRIG [ncells] (the routing's withdrawal is on: D2;
     qin is then K1's QIN with the withdrawal), and "variant", one of the wrong variants of DAM_VARIANTS.  The result grows by
-    (res_new, krls_new, res_take, qin_new) behind the flood rows, if any."""
+    (res_new, krls_new, res_take, qin_new) behind the flood rows, if any.
+    heat: the HEAT form ("stream temperature", H1 - H6), a dict with "tab" (heat_tables), "prep" (heat_prep), "tt" and "tr" [ncells] and
+    optionally "census", a dict that takes a bool row per branch of HEAT_BRANCHES; not together with flood or dam.  The result grows by
+    (tt_new, tr_new, heat, hin, hsrf, hadj, hout); the water rows keep their bits (H8)."""
+    if heat is not None:
+        if flood is not None or dam is not None or in_place:
+            raise ValueError("kinematic_call: heat with flood, dam or in_place")
     if dam is not None:
         if in_place:
             raise ValueError("kinematic_call: dam with in_place")
@@ -307,6 +327,7 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
     dts = float(dt) / float(nsub)
     qacc = np.zeros_like(v)
     safe = np.where(up >= 0, up, 0)
+    ht = _HeatCall(heat, v.size) if heat is not None else None
     with np.errstate(all="ignore"):
         qsub = qin - qsur
         for _ in range(nsub):
@@ -318,6 +339,8 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
                 er, res = reservoir_regulate(en, res, krls, dtab, dmonth, dts, **dkw)
                 if dvar == "own_eo":
                     en = er
+            if ht is not None:
+                ht.before(wt, v, qsub, eh, et, er, up, safe, dts)
             if in_place:
                 for c in range(v.size):
                     fin = 0.0
@@ -335,6 +358,8 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
                 v, wf, depth, frac = inundation_exchange(v, wf, tab, area)
             wh = _canon(wh + (qsur - eh) * dts)
             wt = _canon(wt + ((eh - et) + qsub) * dts)
+            if ht is not None:
+                ht.after(wt, v, dts)
             qacc = qacc + er
         qout = _canon(qacc / float(nsub))
         if dam is not None and dvar == "regulate_last":
@@ -344,6 +369,8 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
         out += (wf, depth, frac)
     if dam is not None:
         out += (res, krls, take, qin)
+    if ht is not None:
+        out += ht.rows()
     return out
 
 
@@ -602,6 +629,180 @@ def reservoir_targets(mean_inflow, mean_demand, cap):
     falls = below & ~np.roll(below, 1, axis=0)
     mstart = np.where(falls.any(axis=0), falls.argmax(axis=0), 0).astype(np.int32)
     return target, beta, mstart
+
+
+# ---- stream temperature (include/elmk.h "stream temperature", H0 - H9) -------------------------------------------------------------------
+TT, TR, HEAT, HIN, HSRF, HADJ, HOUT = range(13, 20)  # ELMK_ROUTE_*, readable while the extension is on
+TFRZ, TMAX, RHOCP, EMIS, SB, ALBW, CPAIR, LV, RAIR, CEX, DMIN = 273.15, 313.15, 4188000.0, 0.97, 5.67e-8, 0.1, 1004.64, 2.501e6, 287.04, 1.3e-3, 1e-3
+NSUBLEV = 15
+HEAT_PREP_ROWS = ("RAD", "KE", "EMS", "TA", "QA", "PA", "TSUR", "TSUB")
+HEAT_BRANCHES = ("terms", "no terms", "QSUB > 0", "QSUB <= 0", "WT > WMINT", "WT <= WMINT", "VOLR > WMINR", "VOLR <= WMINR",
+                 "settle inside", "settle TFRZ", "settle TMAX", "settle TEQ")
+
+# the refusals of elmk_routing_heat_enable's check (elmk_maps.h: heat_check), in its order; E_SHADE is followed by the cell
+E_SUBLEV = "sublev outside 0 .. 14"
+E_SHADE = "SHADE outside [0, 1]"
+
+
+def _exp1(v):
+    try:
+        return math.exp(v)
+    except OverflowError:  # (glibc returns +inf and raises the overflow flag)
+        return float("inf")
+
+
+def _vexp(x):
+    """exp per element through math.exp (glibc's bits, which the device's elmk_exp restates; np.exp is not guaranteed to give them),
+    +inf where glibc overflows."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.fromiter((_exp1(v) for v in x.reshape(-1).tolist()), np.float64, x.size).reshape(x.shape)
+
+
+def _fl(t):
+    """fl(t) = t > TFRZ ? t : TFRZ: a NaN gives TFRZ."""
+    return np.where(np.asarray(t, dtype=np.float64) > TFRZ, t, TFRZ)
+
+
+def check_heat(sublev, shade=None, ncells=None):
+    """The checks of elmk_routing_heat_enable on sublev and shade [ncells] (None: 0.0 everywhere), in its order; raises ValueError with
+    the entry point's text."""
+    if not 0 <= int(sublev) < NSUBLEV:
+        raise ValueError(E_SUBLEV)
+    if shade is None:
+        return
+    s = np.asarray(shade, dtype=np.float64).reshape(-1)
+    if ncells is not None and s.size != ncells:
+        raise ValueError("shade must be [ncells]")
+    with np.errstate(all="ignore"):
+        bad = ~((s >= 0.0) & (s <= 1.0))
+    if bad.any():
+        raise ValueError(e_cell(E_SHADE, int(np.nonzero(bad)[0][0])))
+
+
+def heat_tables(params, sublev=0, shade=None):
+    """H0: the checked inputs' tables, a dict: AT, ACHN, WMINT, WMINR, KSW float64 [ncells], EMS0 and "sublev".  params [11, ncells] as
+    kinematic_call's (TLEN, TWIDTH, RLEN and RWIDTH are read)."""
+    p = np.asarray(params, dtype=np.float64)
+    check_heat(sublev, shade, p.shape[1])
+    s = np.zeros(p.shape[1]) if shade is None else np.asarray(shade, dtype=np.float64).reshape(-1)
+    at, achn = p[TLEN] * p[TWIDTH], p[RLEN] * p[RWIDTH]
+    return {"AT": at, "ACHN": achn, "WMINT": at * DMIN, "WMINR": achn * DMIN, "KSW": (1.0 - ALBW) * (1.0 - s), "EMS0": (EMIS * SB) / RHOCP,
+            "sublev": int(sublev)}
+
+
+def heat_prep(ptr, col, w, cols, tab):
+    """H1's aggregates and derived rows: a dict of float64 [ncells] over HEAT_PREP_ROWS plus "TEQ" and "terms" (bool).  cols: the column
+    fields as the device stores them, widened - forc_tbot, forc_pbot, forc_qbot, forc_lwrad, forc_u, forc_v, t_grnd [ncols]; forc_solad,
+    forc_solai [ncols, 2]; t_soisno [ncols, 20] - through the output grid's CSR map, regrid.apply_aggregate's arithmetic."""
+    def f(k):
+        return np.asarray(cols[k], dtype=np.float64)
+
+    def agg(x):
+        return regrid.apply_aggregate(ptr, col, w, x, 0.0)
+
+    ptr = np.asarray(ptr)
+    terms = ptr[1:] > ptr[:-1]
+    with np.errstate(all="ignore"):
+        ta, pa, qa, lw = agg(f("forc_tbot")), agg(f("forc_pbot")), agg(f("forc_qbot")), agg(f("forc_lwrad"))
+        ua = agg(np.sqrt(f("forc_u") * f("forc_u") + f("forc_v") * f("forc_v")))
+        sd, si = f("forc_solad"), f("forc_solai")
+        sw = agg(((sd[:, 0] + sd[:, 1]) + si[:, 0]) + si[:, 1])
+        tsur, tsub = agg(_fl(f("t_grnd"))), agg(_fl(f("t_soisno")[:, 5 + tab["sublev"]]))
+        rad = (tab["KSW"] * sw + EMIS * lw) / RHOCP
+        ke = ((pa / (RAIR * ta)) * CEX) * ua
+        out = {"RAD": np.where(terms, rad, 0.0), "KE": np.where(terms, ke, 0.0), "EMS": np.where(terms, tab["EMS0"], 0.0),
+               "TA": np.where(terms, ta, 0.0), "QA": np.where(terms, qa, 0.0), "PA": np.where(terms, pa, 0.0),
+               "TSUR": np.where(terms, tsur, TFRZ), "TSUB": np.where(terms, tsub, TFRZ)}
+    out = {k: _canon(v) for k, v in out.items()}
+    out["TEQ"] = _fl(out["TA"])
+    out["terms"] = terms
+    return out
+
+
+def heat_phi(t, x):
+    """H2: phi(T) [ncells], K m/s, with x heat_prep's rows."""
+    t = np.asarray(t, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        d = t - TFRZ
+        es = 611.2 * _vexp((17.67 * d) / (t - 29.65))
+        qs = (0.622 * es) / (x["PA"] - 0.378 * es)
+        t2 = t * t
+        return (x["RAD"] - x["EMS"] * (t2 * t2)) + (x["KE"] * (CPAIR * (x["TA"] - t) - LV * (qs - x["QA"]))) / RHOCP
+
+
+def heat_settle(h, wn, wmin, teq, census=None):
+    """H5: (t, adj) [ncells].  census: a dict whose bool rows "settle inside", "settle TFRZ", "settle TMAX" and "settle TEQ" take the
+    cells of each outcome (or-ed in)."""
+    with np.errstate(all="ignore"):
+        held = wn > wmin
+        t0 = h / np.where(held, wn, 1.0)
+        low = ~(t0 >= TFRZ)
+        t1 = np.where(low, TFRZ, t0)
+        high = t1 > TMAX
+        t = np.where(held, np.where(high, TMAX, t1), teq)
+        adj = np.where(held & ~low & ~high, 0.0, t * wn - h)
+    if census is not None:
+        for k, v in (("settle inside", held & ~low & ~high), ("settle TFRZ", held & low), ("settle TMAX", held & high), ("settle TEQ", ~held)):
+            census[k] = census.get(k, False) | v
+    return t, adj
+
+
+def heat_budget(heat, hin, hsrf, hadj, hout, down):
+    """H7: the sums of HEAT, HIN, HSRF and HADJ and the sum of HOUT over the outlets, in the device reduction's order."""
+    outlet = np.where(np.asarray(down).reshape(-1) < 0, np.asarray(hout, dtype=np.float64).reshape(-1), 0.0)
+    return np.array([diagnostics.reduce_min_max_sum(x)[2] for x in (heat, hin, hsrf, hadj, outlet)])
+
+
+class _HeatCall:
+    """H3 - H6 inside kinematic_call: the state of the call's heat and its two hooks, before and after a sub-step's water."""
+
+    def __init__(self, heat, n):
+        self.tab, self.x, self.census = heat["tab"], heat["prep"], heat.get("census")
+        self.tt, self.tr = (np.array(heat[k], dtype=np.float64).reshape(-1) for k in ("tt", "tr"))
+        self.hin, self.hsrf, self.hadj, self.hout, self.heat = (np.zeros(n) for _ in range(5))
+        self.mag = heat.get("mag")  # a list that takes, per sub-step, the sum of the magnitudes of every term the cell's heat handled
+
+    def before(self, wt, v, qsub, eh, et, er, up, safe, dts):
+        tab, x, tt, tr = self.tab, self.x, self.tt, self.tr
+        hr = _canon(er * tr)
+        fh = np.zeros_like(v)
+        for k in range(up.shape[0]):
+            fh = np.where(up[k] >= 0, fh + hr[safe[k]], fh)
+        gb = np.where(qsub > 0.0, qsub * x["TSUB"], qsub * tt)  # H3
+        wet_t, wet_r = wt > tab["WMINT"], v > tab["WMINR"]
+        self.sxt = np.where(wet_t, tab["AT"] * heat_phi(tt, x), 0.0)
+        self.hi = eh * x["TSUR"] + gb
+        self.h_t = tt * wt + ((self.hi - et * tt) + self.sxt) * dts
+        self.sxr = np.where(wet_r, tab["ACHN"] * heat_phi(tr, x), 0.0)  # H4
+        self.ho = hr
+        self.h_r = tr * v + (((fh - hr) + et * tt) + self.sxr) * dts
+        if self.mag is not None:
+            fa = np.zeros_like(v)
+            for k in range(up.shape[0]):
+                fa = np.where(up[k] >= 0, fa + np.abs(hr[safe[k]]), fa)
+            self._m = (np.abs(tt * wt) + np.abs(tr * v) +
+                       (np.abs(eh * x["TSUR"]) + np.abs(gb) + 2.0 * np.abs(et * tt) + np.abs(self.sxt) + np.abs(self.sxr) + fa + np.abs(hr)) * dts)
+        if self.census is not None:
+            for k, m in (("terms", x["terms"]), ("no terms", ~x["terms"]), ("QSUB > 0", qsub > 0.0), ("QSUB <= 0", ~(qsub > 0.0)),
+                         ("WT > WMINT", wet_t), ("WT <= WMINT", ~wet_t), ("VOLR > WMINR", wet_r), ("VOLR <= WMINR", ~wet_r)):
+                self.census[k] = self.census.get(k, False) | m
+
+    def after(self, wtn, vn, dts):
+        tab, teq = self.tab, self.x["TEQ"]
+        ttn, adjt = heat_settle(self.h_t, wtn, tab["WMINT"], teq, self.census)
+        trn, adjr = heat_settle(self.h_r, vn, tab["WMINR"], teq, self.census)
+        self.tt, self.tr = _canon(ttn), _canon(trn)
+        self.hin = _canon(self.hin + self.hi * dts)  # H6
+        self.hsrf = _canon(self.hsrf + (self.sxt + self.sxr) * dts)
+        self.hadj = _canon(self.hadj + (adjt + adjr))
+        self.hout = _canon(self.hout + self.ho * dts)
+        self.heat = _canon(ttn * wtn + trn * vn)
+        if self.mag is not None:
+            self.mag.append(self._m + np.abs(ttn * wtn) + np.abs(trn * vn) + np.abs(adjt) + np.abs(adjr) + np.abs(self.hin) + np.abs(self.hsrf) +
+                            np.abs(self.hadj) + np.abs(self.hout))
+
+    def rows(self):
+        return self.tt, self.tr, self.heat, self.hin, self.hsrf, self.hadj, self.hout
 
 
 # D8 direction codes (the ESRI convention): the neighbour a cell drains into, as (row step, column step) with row 0 the northernmost

@@ -41,6 +41,7 @@ ROUTE_KW_NPARAM = 11  # the rows of routing_kinematic_enable's params (routing.H
 ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC = 7, 8, 9  # ... while the floodplain inundation is on (routing.WF .. routing.FLOOD_FRAC)
 ROUTE_FP_NPROF = 11  # the rows of routing_inundation_enable's eprof
 ROUTE_RES, ROUTE_KRLS, ROUTE_RES_TAKE = 10, 11, 12  # ... while the reservoirs are on (routing.RES .. routing.RES_TAKE)
+ROUTE_TT, ROUTE_TR, ROUTE_HEAT, ROUTE_HIN, ROUTE_HSRF, ROUTE_HADJ, ROUTE_HOUT = range(13, 20)  # ... while the stream temperature is on (routing.TT .. routing.HOUT)
 WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB .. hydrology.WB_TOTSOILICE
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
@@ -609,7 +610,7 @@ class ELMState:
     def routing_read(self, which, cell0=0, n=None):
         """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM (with the kinematic-wave scheme on also ROUTE_WH, ROUTE_WT, ROUTE_QSUR,
         with its floodplain inundation on also ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC, with its reservoirs on also ROUTE_RES,
-        ROUTE_KRLS, ROUTE_RES_TAKE)
+        ROUTE_KRLS, ROUTE_RES_TAKE, with its stream temperature on also ROUTE_TT .. ROUTE_HOUT)
         of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
         n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
         out = np.empty(max(n, 0), dtype=np.float64)
@@ -715,6 +716,35 @@ class ELMState:
     def routing_reservoir_clear(self):
         """Back to the free-flowing channel; RES is dropped, VOLR stays."""
         self._chk(self.lib.elmk_routing_reservoir_clear(self.ctx), "routing_reservoir_clear")
+
+    # -- stream temperature (include/elmk.h: elmk_routing_heat_enable ...; routing.kinematic_call(heat=) restates it) ------------------------
+    def routing_heat_enable(self, sublev=0, shade=None):
+        """Give the tributary store and the main channel of the kinematic scheme's cells a temperature: sublev 0 .. 14, the soil layer
+        whose temperature the subsurface runoff carries; shade float64 [ncells] in [0, 1], the share of shortwave kept off the water
+        (None: 0).  Allocates the rows TT and TR (273.15 K) and the five diagnostics; routing_read takes ROUTE_TT .. ROUTE_HOUT from
+        here on.  Needs routing_kinematic_enable, and neither the inundation nor the reservoirs."""
+        s = None if shade is None else np.ascontiguousarray(shade, dtype=np.float64).reshape(-1)
+        if s is not None and s.size != getattr(self, "routing_ncells", s.size):
+            raise ValueError(f"routing_heat_enable: {s.size} shade values for {self.routing_ncells} cells")
+        self._chk(self.lib.elmk_routing_heat_enable(self.ctx, int(sublev), None if s is None else _p(s)), "routing_heat_enable")
+
+    def routing_heat_init(self, tt=None, tr=None):
+        """TT and TR from [ncells] (None: 273.15 K), the diagnostics zeros.  Synchronises."""
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (tt, tr)]
+        for v in a:
+            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
+                raise ValueError(f"routing_heat_init: {v.size} values for {self.routing_ncells} cells")
+        self._chk(self.lib.elmk_routing_heat_init(self.ctx, *(None if v is None else _p(v) for v in a)), "routing_heat_init")
+
+    def routing_heat_budget(self):
+        """float64 [5]: the sums of HEAT, HIN, HSRF, HADJ and of HOUT over the outlets (routing.heat_budget).  Synchronises."""
+        out = np.empty(5, dtype=np.float64)
+        self._chk(self.lib.elmk_routing_heat_budget(self.ctx, _p(out)), "routing_heat_budget")
+        return out
+
+    def routing_heat_clear(self):
+        """Back to the scheme without temperatures; TT and TR are dropped, the water stays."""
+        self._chk(self.lib.elmk_routing_heat_clear(self.ctx), "routing_heat_clear")
 
     # -- water balance (include/elmk.h: elmk_water_balance_enable ...; hydrology.water_balance_begin / _end restate the stage) -----
     def water_balance_enable(self, tol_mm):

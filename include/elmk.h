@@ -1342,6 +1342,98 @@ int elmk_routing_reservoir_time(elmk_ctx *ctx, int month /*0 .. 11*/, int begins
 int elmk_routing_reservoir_budget(elmk_ctx *ctx, double *sums /*[2]: the sums of RES and RES_TAKE, through R6's reduction kernels*/);
 int elmk_routing_reservoir_clear(elmk_ctx *ctx);
 
+/* ---- stream temperature -------------------------------------------------------------------------
+ * An opt-in extension of the kinematic-wave scheme above, after the heat module of ELM's river model, MOSART-heat (Li et al., J. Adv.
+ * Model. Earth Syst. 7, 2015): the tributary store and the main channel of every cell carry a water temperature, TT and TR.  Heat
+ * enters with the runoff (surface runoff at the ground's temperature, subsurface runoff at a soil layer's), moves with the water,
+ * and is exchanged through the water surface: absorbed shortwave and longwave, emitted longwave, sensible and latent heat.  The
+ * pattern is the inundation's and the reservoirs': a template parameter on the existing kernels' code (k_routing.hip:
+ * k_kinematic_prep<.., HEAT>, and the sub-step's body as k_kinematic_step_heat), no run flag and no new call or launch in the step.
+ * The heat reads the water and never writes it.  elmkernels_amd/routing.py: heat_tables(), heat_prep(), heat_phi(), heat_settle() and
+ * kinematic_call(..., heat=) restate it on the host.
+ *
+ * Conventions of "kinematic-wave routing": no contraction, left-associated + - *, `/` and sqrt correctly rounded, plain IEEE
+ * comparisons, every row fp64 in both builds, a NaN stored as the canonical quiet NaN.  exp is glibc's (elmk_exp on the device).
+ * X += y below stands for X = X + (y).
+ *
+ * Inputs, given once after elmk_routing_kinematic_enable: sublev, 0 .. 14, the soil layer whose temperature the subsurface runoff
+ * carries (level 5 + sublev of t_soisno), and shade[ncells] in [0, 1], the share of direct and diffuse shortwave kept off the water
+ * (NULL: 0.0 everywhere).
+ *
+ * Rows: ELMK_ROUTE_TT and ELMK_ROUTE_TR (K, the temperatures of the tributary store and the main channel; the only prognostic rows,
+ * TFRZ after the enable) and five diagnostics of the last call in K m3, that is heat divided by RHOCP: ELMK_ROUTE_HEAT (the heat
+ * content at the call's end), ELMK_ROUTE_HIN (entered with runoff), ELMK_ROUTE_HSRF (through the water surface), ELMK_ROUTE_HADJ (by
+ * the settle rule H5) and ELMK_ROUTE_HOUT (left the cell with the main channel's flow).  elmk_routing_read accepts the seven only while
+ * the extension is on.
+ *
+ * Literals: TFRZ = 273.15, TMAX = 313.15, RHOCP = 4188000.0, EMIS = 0.97, SB = 5.67e-8, ALBW = 0.1, CPAIR = 1004.64, LV = 2.501e6,
+ * RAIR = 287.04, CEX = 1.3e-3, DMIN = 1e-3.  fl(t) = t > TFRZ ? t : TFRZ, so a NaN gives TFRZ.
+ *
+ * H0. (tables) AT = TLEN * TWIDTH;  ACHN = RLEN * RWIDTH;  WMINT = AT * DMIN;  WMINR = ACHN * DMIN;
+ *     KSW = (1.0 - ALBW) * (1.0 - SHADE);  EMS0 = (EMIS * SB) / RHOCP.  The host forms KSW and EMS0 once at the enable; the four
+ *     products of the scheme's parameters are formed where they are used, from the same operands.
+ * H1. (K1 launch, once per call) over the cell's terms in R1's order, the first term assigned and the others added, each term w * x:
+ *     TA, PA, QA, LW from x = forc_tbot, forc_pbot, forc_qbot, forc_lwrad;  UA from x = sqrt(forc_u * forc_u + forc_v * forc_v);
+ *     SW from x = ((forc_solad[0] + forc_solad[1]) + forc_solai[0]) + forc_solai[1];  TSUR from x = fl(t_grnd);
+ *     TSUB from x = fl(t_soisno[5 + sublev]).  Every field is read as stored and widened (the fp32-state build sees its stored values).
+ *     A cell with terms: RAD = (KSW * SW + EMIS * LW) / RHOCP;  KE = ((PA / (RAIR * TA)) * CEX) * UA;  EMS = EMS0.
+ *     A cell without terms (a pass-through reach): RAD = KE = EMS = 0.0;  TSUR = TSUB = TFRZ;  TA = QA = PA = 0.0.
+ *     TEQ = fl(TA).  The five diagnostic rows are zeroed.  The heat-flow row takes hr = er * TR, with er the flow this launch writes.
+ * H2. phi(T): d = T - TFRZ;  es = 611.2 * exp((17.67 * d) / (T - 29.65));  qs = (0.622 * es) / (PA - 0.378 * es);  t2 = T * T;
+ *     phi = (RAD - EMS * (t2 * t2)) + (KE * (CPAIR * (TA - T) - LV * (qs - QA))) / RHOCP.
+ * H3. (tributaries, per sub-step) from the sub-step's start values and K3 / K4's eh, et:
+ *     gb = QSUB > 0.0 ? QSUB * TSUB : QSUB * TT;  sx_T = WT > WMINT ? AT * phi(TT) : 0.0;  hi = eh * TSUR + gb;
+ *     h = TT * WT + ((hi - et * TT) + sx_T) * dts;  wn = K6's new WT;  (TT, adj_T) = settle(h, wn, WMINT).
+ * H4. (main channel) fh = the sum of hr[u] over the upstream slots ascending, from +0.0, as K5 sums er;  ho = hr[c];
+ *     sx_R = VOLR > WMINR ? ACHN * phi(TR) : 0.0;  h = TR * VOLR + (((fh - ho) + et * TT) + sx_R) * dts with the TT of the sub-step's
+ *     start;  wn = K6's new VOLR;  (TR, adj_R) = settle(h, wn, WMINR).  Every sub-step but the last writes hr = e * TR from the new TR
+ *     and the er it forms, into the second of a pair of buffers beside er's.
+ * H5. settle(h, wn, wmin): if (wn > wmin) { t = h / wn;  if (!(t >= TFRZ)) t = TFRZ;  if (t > TMAX) t = TMAX; } else t = TEQ;
+ *     adj = t * wn - h where the rule has acted - t is TEQ, or one of the two ifs has fired - and +0.0 where t is the quotient itself:
+ *     there t * wn is h up to the division's rounding, which is no heat.  A store too thin to hold a temperature takes the air's; a
+ *     store driven past the bounds is held at them, and adj is the heat that this adds.
+ * H6. (diagnostics) per sub-step, in this order: HIN += hi * dts;  HSRF += (sx_T + sx_R) * dts;  HADJ += adj_T + adj_R;
+ *     HOUT += ho * dts.  The last sub-step stores HEAT = TT * WT + TR * VOLR from the new values.
+ * H7. (elmk_routing_heat_budget) sums[0 .. 3] = the sums of HEAT, HIN, HSRF and HADJ, sums[4] = the sum of HOUT over the outlets (R6's
+ *     outlet rule: down < 0), all through R6's reduction kernels.  Over a call,
+ *     sum HEAT at its end - sum HEAT at its start = sums[1] + sums[2] + sums[3] - sums[4], up to rounding
+ *     (tests/test_routing_heat_host.py counts the roundings).
+ * H8. Every water row keeps the bits of the scheme without the extension.
+ * H9. Edge values do what H1 - H6 say literally.  A NaN TT or TR makes h NaN; where wn > wmin, t = NaN fails t >= TFRZ and the store
+ *     takes TFRZ, and adj and HADJ are NaN for that call: the temperature recovers, the budget of that call does not.  +inf likewise
+ *     (t2 * t2 = +inf, phi = -inf or NaN).  A NaN, zero, negative or subnormal WT or VOLR is not > wmin: no surface exchange, and where
+ *     the new storage is not > wmin either the store takes TEQ.  PA == 0.0 gives qs = (0.622 * es) / (-(0.378 * es)), finite and
+ *     negative.  A NaN TA makes KE and phi NaN while TEQ = TFRZ.  A cell without terms exchanges nothing through its surface:
+ *     phi = +0.0 for every finite T.
+ *
+ *   elmk_routing_heat_enable  takes the inputs, allocates the rows, H1's rows, KSW and the two hr buffers in one allocation (TT and
+ *                           TR TFRZ, the rest zero; counted in elmk_device_bytes) and drops the captured run step.  ELMK_E_INVALID,
+ *                           nothing changed: the kinematic scheme not on; already on; the floodplain inundation or the reservoirs on
+ *                           ("elmk_routing_inundation_clear first", "elmk_routing_reservoir_clear first"); sublev outside 0 .. 14; a
+ *                           shade value not finite or outside [0, 1] (the text names the row and the first offending cell,
+ *                           "elmk_routing_heat_enable: SHADE outside [0, 1] at cell 17"); a stream being captured.
+ *   elmk_routing_heat_init    TT and TR from host[ncells] (NULL: TFRZ), the diagnostics zero.  Synchronises.
+ *   elmk_routing_heat_budget  H7; synchronises.
+ *   elmk_routing_heat_clear   back to the scheme without temperatures; frees what enable allocated and drops the captured run step.
+ * While the extension is on elmk_routing_kinematic_clear, elmk_routing_inundation_enable and elmk_routing_reservoir_enable are refused
+ * with ELMK_E_INVALID ("elmk_routing_heat_clear first"); elmk_routing_clear frees everything.  elmk_routing and elmk_run with
+ * ELMK_RUN_ROUTING run the HEAT form while it is on.
+ * Tapes: elmk_cell_history_add_row(ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_TT .. ELMK_ROUTE_HOUT) works while the extension is on, and while
+ * such an entry exists elmk_routing_heat_clear is refused ("elmk_history_clear first").
+ * Restart: under ELMK_OPT_RESTART_CELLS a context with the heat on saves an image of version 8 (ELMK_RESTART_VERSION_HEAT): version 6
+ * plus the cell sections ELMK_ROUTE_TT and ELMK_ROUTE_TR after WT; it loads only into a context with the same stages on, and the load
+ * leaves the diagnostics zero; every other context saves byte for byte what it saved before.  With the option off a driver saves TT
+ * and TR with elmk_routing_read and hands them to elmk_routing_heat_init after elmk_routing_heat_enable.  A context that never calls
+ * these entries runs the kernels, launch sequences and graphs it ran before and allocates nothing more.
+ * Out of scope, each a later change: heat on the floodplain and in a stratified reservoir (hence the interlock), river ice, a heat
+ * store on the hillslope, and the linear scheme. */
+enum { ELMK_ROUTE_TT = 13, ELMK_ROUTE_TR = 14, ELMK_ROUTE_HEAT = 15, ELMK_ROUTE_HIN = 16,
+       ELMK_ROUTE_HSRF = 17, ELMK_ROUTE_HADJ = 18, ELMK_ROUTE_HOUT = 19 };
+int elmk_routing_heat_enable(elmk_ctx *ctx, int sublev /*0 .. 14*/, const double *shade /*[ncells] or NULL: 0.0*/);
+int elmk_routing_heat_init(elmk_ctx *ctx, const double *tt /*[ncells] or NULL: TFRZ*/, const double *tr /*[ncells] or NULL: TFRZ*/);
+int elmk_routing_heat_budget(elmk_ctx *ctx, double *sums /*[5]: H7, through R6's reduction kernels*/);
+int elmk_routing_heat_clear(elmk_ctx *ctx);
+
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.
  * These two entries register one such row, over the columns (elmk_column_history_add_row; the six elmk_history_* entries of "history"
@@ -1481,6 +1573,7 @@ enum { ELMK_RESTART_ROUTING = 7, ELMK_RESTART_IRRSUP = 8 }; /* the cell sections
 #define ELMK_RESTART_VERSION_IRRIGATION 5u /* of a context with the irrigation enabled */
 enum { ELMK_RESTART_VERSION_ROUTING = 6 };  /* of a context with the routing enabled and ELMK_OPT_RESTART_CELLS on */
 enum { ELMK_RESTART_VERSION_RESERVOIR = 7 };  /* ... and the reservoirs on: version 6 plus the cell sections ELMK_ROUTE_RES and ELMK_ROUTE_KRLS after WF */
+enum { ELMK_RESTART_VERSION_HEAT = 8 };  /* ... and the stream temperature on: version 6 plus the cell sections ELMK_ROUTE_TT and ELMK_ROUTE_TR after WT */
 typedef struct {
   char magic[8];              /* ELMK_RESTART_MAGIC */
   uint32_t version;           /* ELMK_RESTART_VERSION */

@@ -436,6 +436,15 @@ class ELMInterface {
   void routing_reservoir_time(int month, bool begins) { ok(elmk_routing_reservoir_time(ctx_, month, begins ? 1 : 0)); }
   void routing_reservoir_budget(double* sums) { ok(elmk_routing_reservoir_budget(ctx_, sums)); }
   void routing_reservoir_clear() { ok(elmk_routing_reservoir_clear(ctx_)); }
+  /* Stream temperature (elmk.h "stream temperature"): the tributary store and the main channel of the kinematic scheme's cells carry a
+   * temperature.  routing_heat_enable() takes the soil layer of the subsurface runoff's temperature and shade[ncells] (nullptr: 0) after
+   * routing_kinematic_enable, without the inundation and the reservoirs; routing(dt) and run(..., routing = true) then run the HEAT
+   * form, and routing_read() takes ELMK_ROUTE_TT .. ELMK_ROUTE_HOUT as well.  routing_heat_init() takes a restart's TT and TR
+   * ([ncells], nullptr: 273.15 K); routing_heat_budget() fills sums[5]; routing_heat_clear() drops the temperatures and keeps the water. */
+  void routing_heat_enable(int sublev = 0, const double* shade = nullptr) { ok(elmk_routing_heat_enable(ctx_, sublev, shade)); }
+  void routing_heat_init(const double* tt = nullptr, const double* tr = nullptr) { ok(elmk_routing_heat_init(ctx_, tt, tr)); }
+  void routing_heat_budget(double* sums) { ok(elmk_routing_heat_budget(ctx_, sums)); }
+  void routing_heat_clear() { ok(elmk_routing_heat_clear(ctx_)); }
   /* History entries over one fp64 row of a feature (elmk.h "feature rows on history tapes"): family ELMK_ROWS_*, which the family's
    * row number; as history_add / gridded_history_add otherwise, one level.  While such an entry exists the family's clear is refused. */
   int history_add_row(int tape, int family, int which, int op)
