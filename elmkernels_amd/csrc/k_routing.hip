@@ -16,7 +16,7 @@
 // first sub-step, 8 (the flow sum), and writes 16.  The unit carries no nontemporal hint: none has been measured for it.
 // The second scheme of the stage, kinematic-wave routing (k_kinematic_prep, k_kinematic_step), follows the linear one below, with its
 // floodplain inundation (k_kinematic_step's FLOOD form), its reservoirs (both kernels' DAM form) and its stream temperature (the HEAT
-// form: k_kinematic_prep<.., HEAT> and k_kinematic_step_heat).
+// form: k_kinematic_prep<.., HEAT> and k_kinematic_step<.., HEAT>).
 #include <type_traits>
 
 #include "elmk_dev.h"
@@ -510,15 +510,13 @@ __device__ __forceinline__ void fp_exchange(double& v, double& wf, double& h, do
 
 // K3 - K7: one sub-step.  er_old: the flows of the sub-step's start; er_new: those of its end (not written by the LAST one).  FIRST and
 // LAST as k_routing_step's.  FLOOD: the flood form, I1 - I5.  DAM: a dam cell's K6 subtracts its natural er (D4), and the er it forms
-// is regulated (D3).  HEAT: H3 - H6 beside the water (k_kinematic_step_heat).
-// the body of both sub-step kernels below, inlined into each
-namespace {
-template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM, bool HEAT>
-__device__ __forceinline__ void kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
-                                               gptr<double> er_new, gptr<const double> par, gptr<const double> area, gptr<const int32_t> up,
-                                               gptr<const double> qsur, gptr<const double> qsub, gptr<double> qout, gptr<double> qout_sum,
-                                               int64_t ncells, int64_t cld, double dts, double dnsub, FloodRows<FLOOD> fl, DamRows<DAM> dm,
-                                               HeatRows<HEAT> ht)
+// is regulated (D3).  HEAT: H3 - H6 beside the water.
+template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM = false, bool HEAT = false>
+__global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
+                                                        gptr<double> er_new, gptr<const double> par, gptr<const double> area,
+                                                        gptr<const int32_t> up, gptr<const double> qsur, gptr<const double> qsub,
+                                                        gptr<double> qout, gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts,
+                                                        double dnsub, FloodRows<FLOOD> fl, DamRows<DAM> dm, HeatRows<HEAT> ht)
 {
   static_assert(!(HEAT && (FLOOD || DAM)), "the heat excludes the inundation and the reservoirs");
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -618,31 +616,6 @@ __device__ __forceinline__ void kinematic_step(gptr<double> wh_row, gptr<double>
     if constexpr (HEAT) route_st(ht.hr_new + c, e * trn);
   }
 }
-}  // namespace
-
-template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM = false>
-__global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr, gptr<const double> er_old,
-                                                        gptr<double> er_new, gptr<const double> par, gptr<const double> area,
-                                                        gptr<const int32_t> up, gptr<const double> qsur, gptr<const double> qsub,
-                                                        gptr<double> qout, gptr<double> qout_sum, int64_t ncells, int64_t cld, double dts,
-                                                        double dnsub, FloodRows<FLOOD> fl, DamRows<DAM> dm)
-{
-  kinematic_step<NPAD, FIRST, LAST, FLOOD, DAM, false>(wh_row, wt_row, volr, er_old, er_new, par, area, up, qsur, qsub, qout, qout_sum, ncells, cld,
-                                                       dts, dnsub, fl, dm, HeatRows<false>{});
-}
-
-// the HEAT form of the sub-step (H3 - H6): the plain water with the heat beside it, a kernel of its own name so that the kernels above
-// keep theirs
-template <int NPAD, bool FIRST, bool LAST>
-__global__ __launch_bounds__(256) void k_kinematic_step_heat(gptr<double> wh_row, gptr<double> wt_row, gptr<double> volr,
-                                                             gptr<const double> er_old, gptr<double> er_new, gptr<const double> par,
-                                                             gptr<const double> area, gptr<const int32_t> up, gptr<const double> qsur,
-                                                             gptr<const double> qsub, gptr<double> qout, gptr<double> qout_sum, int64_t ncells,
-                                                             int64_t cld, double dts, double dnsub, HeatRows<true> ht)
-{
-  kinematic_step<NPAD, FIRST, LAST, false, false, true>(wh_row, wt_row, volr, er_old, er_new, par, area, up, qsur, qsub, qout, qout_sum, ncells, cld,
-                                                        dts, dnsub, FloodRows<false>{}, DamRows<false>{}, ht);
-}
 
 namespace {
 DamRows<true> dam_rows(const DamArgs& Dm, double dt)
@@ -718,23 +691,21 @@ void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const 
         with_bool(s == 0, [&](auto first) {
           with_bool(s == A.nsub - 1, [&](auto last) {
             with_bool(Dm.rows != nullptr, [&](auto dam) {
-              constexpr int NPAD = decltype(npad)::value;
-              constexpr bool FIRST = decltype(first)::value, LAST = decltype(last)::value;
-              constexpr bool FLOOD = decltype(flood)::value, DAM = decltype(dam)::value;
-              if constexpr (!FLOOD && !DAM) {  // (H: the entry points keep the heat apart from the inundation and the reservoirs)
-                if (H.rows) {
-                  args([&](auto... a) {
-                    hipLaunchKernelGGL((k_kinematic_step_heat<NPAD, FIRST, LAST>), grid, block, 0, st, a..., heat_rows(H, hsrc, hdst));
-                  });
-                  return;
-                }
-              }
-              FloodRows<FLOOD> fl;
-              if constexpr (FLOOD) fl = FloodRows<true>{(gptr<double>)F.rows, (gptr<const double>)F.tab};
-              DamRows<DAM> dm;
-              if constexpr (DAM) dm = dam_rows(Dm, dts * (double)A.nsub);
-              args([&](auto... a) {
-                hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST, FLOOD, DAM>), grid, block, 0, st, a..., fl, dm);
+              with_bool(H.rows != nullptr, [&](auto heat) {
+                constexpr int NPAD = decltype(npad)::value;
+                constexpr bool FIRST = decltype(first)::value, LAST = decltype(last)::value;
+                constexpr bool FLOOD = decltype(flood)::value, DAM = decltype(dam)::value;
+                // (H: the entry points keep the heat apart from the inundation and the reservoirs)
+                constexpr bool HEAT = decltype(heat)::value && !FLOOD && !DAM;
+                FloodRows<FLOOD> fl;
+                if constexpr (FLOOD) fl = FloodRows<true>{(gptr<double>)F.rows, (gptr<const double>)F.tab};
+                DamRows<DAM> dm;
+                if constexpr (DAM) dm = dam_rows(Dm, dts * (double)A.nsub);
+                HeatRows<HEAT> ht;
+                if constexpr (HEAT) ht = heat_rows(H, hsrc, hdst);
+                args([&](auto... a) {
+                  hipLaunchKernelGGL((k_kinematic_step<NPAD, FIRST, LAST, FLOOD, DAM, HEAT>), grid, block, 0, st, a..., fl, dm, ht);
+                });
               });
             });
           });

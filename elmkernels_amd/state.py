@@ -490,11 +490,25 @@ class ELMState:
 
     def active_layer_init(self, altmax=None, altmax_lastyear=None):
         """altmax and altmax_lastyear from [ncols] each (None: zeros), alt = zeros: a restart file's ALTMAX.  Synchronises."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (altmax, altmax_lastyear)]
+        self._init_rows("active_layer_init", (altmax, altmax_lastyear), "columns")
+
+    def _init_rows(self, name, rows, unit, *more):
+        """elmk_<name>(ctx, rows ..., more ...): each row an optional array (None: the call's default) of one value per column
+        (unit "columns") or per routing cell ("cells")."""
+        n = self.ncols if unit == "columns" else getattr(self, "routing_ncells", None)
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in rows]
         for v in a:
-            if v is not None and v.size != self.ncols:
-                raise ValueError(f"active_layer_init: {v.size} values for {self.ncols} columns")
-        self._chk(self.lib.elmk_active_layer_init(self.ctx, *(None if v is None else _p(v) for v in a)), "active_layer_init")
+            if v is not None and n is not None and v.size != n:
+                raise ValueError(f"{name}: {v.size} values for {n} {unit}")
+        self._chk(getattr(self.lib, "elmk_" + name)(self.ctx, *(None if v is None else _p(v) for v in a), *more), name)
+
+    def _read_row(self, name, which, i0, n, total, clamp=False):
+        """elmk_<name>(ctx, which, out, i0, n): float64 [n] of row `which` from index i0 on; n None: the rest of `total`.  clamp: a
+        negative n is left to the entry point to refuse (otherwise numpy refuses it)."""
+        n = int(total - i0 if n is None else n)
+        out = np.empty(max(n, 0) if clamp else n, dtype=np.float64)
+        self._chk(getattr(self.lib, "elmk_" + name)(self.ctx, int(which), _p(out), int(i0), n), name)
+        return out
 
     # -- irrigation (include/elmk.h: elmk_irrigation_enable ...; elmkernels_amd/irrigation.py restates the stage) ---------------------
     def irrigation_enable(self, sched):
@@ -508,11 +522,7 @@ class ELMState:
 
     def irrigation_init(self, rate=None, nleft=None):
         """RATE and NLEFT from [ncols] each (None: zeros), QFLX_IRRIG = zeros: a restart file's values.  Synchronises."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (rate, nleft)]
-        for v in a:
-            if v is not None and v.size != self.ncols:
-                raise ValueError(f"irrigation_init: {v.size} values for {self.ncols} columns")
-        self._chk(self.lib.elmk_irrigation_init(self.ctx, *(None if v is None else _p(v) for v in a)), "irrigation_init")
+        self._init_rows("irrigation_init", (rate, nleft), "columns")
 
     def irrigation(self, dt, tod):
         """The stage: apply, then check.  After timestep7 / timestep7_fused, before soil_temperature; one launch, stream-ordered, no
@@ -521,10 +531,7 @@ class ELMState:
 
     def irrigation_read(self, which, col0=0, n=None):
         """Row IRR_RATE, IRR_NLEFT or IRR_QFLX_IRRIG of columns [col0, col0 + n): float64 [n].  Synchronises."""
-        n = int(self.ncols - col0 if n is None else n)
-        out = np.empty(max(n, 0), dtype=np.float64)
-        self._chk(self.lib.elmk_irrigation_read(self.ctx, int(which), _p(out), int(col0), n), "irrigation_read")
-        return out
+        return self._read_row("irrigation_read", which, col0, n, self.ncols, clamp=True)
 
     def irrigation_rows(self):
         """Every row of the feature: float64 [IRR_NROWS, ncols], the `rows` of irrigation.step."""
@@ -544,18 +551,11 @@ class ELMState:
 
     def irrigation_supply_init(self, unmet_sum=None):
         """UNMET_SUM from [ncells] (None: zeros), the other rows zeros: a restart file's values.  Synchronises."""
-        v = None if unmet_sum is None else np.ascontiguousarray(unmet_sum, dtype=np.float64).reshape(-1)
-        n = getattr(self, "routing_ncells", None)
-        if v is not None and n is not None and v.size != n:
-            raise ValueError(f"irrigation_supply_init: {v.size} values for {n} cells")
-        self._chk(self.lib.elmk_irrigation_supply_init(self.ctx, None if v is None else _p(v)), "irrigation_supply_init")
+        self._init_rows("irrigation_supply_init", (unmet_sum,), "cells")
 
     def irrigation_supply_read(self, which, cell0=0, n=None):
         """Row IRRSUP_DEMAND, IRRSUP_COMMITTED, IRRSUP_RATIO or IRRSUP_UNMET_SUM of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
-        n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
-        out = np.empty(max(n, 0), dtype=np.float64)
-        self._chk(self.lib.elmk_irrigation_supply_read(self.ctx, int(which), _p(out), int(cell0), n), "irrigation_supply_read")
-        return out
+        return self._read_row("irrigation_supply_read", which, cell0, n, getattr(self, "routing_ncells", 0), clamp=True)
 
     def irrigation_supply_rows(self):
         """Every row of the limit: float64 [IRRSUP_NROWS, ncells]."""
@@ -586,15 +586,7 @@ class ELMState:
     def routing_init(self, volr=None, qout_sum=None, ncalls=0):
         """VOLR and QOUT_SUM from [ncells] each (None: zeros), QIN and QOUT zeros, the call count = ncalls: a restart file's values.
         Synchronises."""
-        self._routing_init("routing_init", (volr, qout_sum), int(ncalls))
-
-    def _routing_init(self, name, rows, *more):
-        """elmk_<name>(ctx, rows ..., more ...): each row an optional [ncells] array (None: the call's default)."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in rows]
-        for v in a:
-            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
-                raise ValueError(f"{name}: {v.size} values for {self.routing_ncells} cells")
-        self._chk(getattr(self.lib, "elmk_" + name)(self.ctx, *(None if v is None else _p(v) for v in a), *more), name)
+        self._init_rows("routing_init", (volr, qout_sum), "cells", int(ncalls))
 
     def _routing_budget(self, name, n):
         """elmk_<name>(ctx, sums): float64 [n]."""
@@ -612,10 +604,7 @@ class ELMState:
         with its floodplain inundation on also ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC, with its reservoirs on also ROUTE_RES,
         ROUTE_KRLS, ROUTE_RES_TAKE, with its stream temperature on also ROUTE_TT .. ROUTE_HOUT)
         of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
-        n = int(getattr(self, "routing_ncells", 0) - cell0 if n is None else n)
-        out = np.empty(max(n, 0), dtype=np.float64)
-        self._chk(self.lib.elmk_routing_read(self.ctx, int(which), _p(out), int(cell0), n), "routing_read")
-        return out
+        return self._read_row("routing_read", which, cell0, n, getattr(self, "routing_ncells", 0), clamp=True)
 
     def routing_count(self):
         """The calls since the last routing_init / routing_reset_mean: routing_read(ROUTE_QOUT_SUM) / routing_count() is the mean."""
@@ -650,7 +639,7 @@ class ELMState:
 
     def routing_kinematic_init(self, wh=None, wt=None):
         """WH and WT from [ncells] each (None: zeros), QSUR zeros; VOLR, QOUT_SUM and the count stay routing_init's.  Synchronises."""
-        self._routing_init("routing_kinematic_init", (wh, wt))
+        self._init_rows("routing_kinematic_init", (wh, wt), "cells")
 
     def routing_kinematic_budget(self):
         """float64 [2]: the sums of WH and WT (routing.kinematic_budget).  Synchronises."""
@@ -675,7 +664,7 @@ class ELMState:
 
     def routing_inundation_init(self, wf=None):
         """WF from [ncells] (None: zeros), the two diagnostics zeros; VOLR, WH and WT stay their own entries'.  Synchronises."""
-        self._routing_init("routing_inundation_init", (wf,))
+        self._init_rows("routing_inundation_init", (wf,), "cells")
 
     def routing_inundation_budget(self):
         """float64 [1]: the sum of WF (routing.inundation_budget).  Synchronises."""
@@ -702,7 +691,7 @@ class ELMState:
 
     def routing_reservoir_init(self, res=None, krls=None):
         """RES from [ncells] (None: zeros), KRLS from [ncells] (None: 1.0), RES_TAKE zeros.  Synchronises."""
-        self._routing_init("routing_reservoir_init", (res, krls))
+        self._init_rows("routing_reservoir_init", (res, krls), "cells")
 
     def routing_reservoir_time(self, month, begins=False):
         """The month (0 .. 11) of the following routing() calls, and whether the next one is the call whose step starts at 00:00 of the
@@ -730,17 +719,11 @@ class ELMState:
 
     def routing_heat_init(self, tt=None, tr=None):
         """TT and TR from [ncells] (None: 273.15 K), the diagnostics zeros.  Synchronises."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (tt, tr)]
-        for v in a:
-            if v is not None and v.size != getattr(self, "routing_ncells", v.size):
-                raise ValueError(f"routing_heat_init: {v.size} values for {self.routing_ncells} cells")
-        self._chk(self.lib.elmk_routing_heat_init(self.ctx, *(None if v is None else _p(v) for v in a)), "routing_heat_init")
+        self._init_rows("routing_heat_init", (tt, tr), "cells")
 
     def routing_heat_budget(self):
         """float64 [5]: the sums of HEAT, HIN, HSRF, HADJ and of HOUT over the outlets (routing.heat_budget).  Synchronises."""
-        out = np.empty(5, dtype=np.float64)
-        self._chk(self.lib.elmk_routing_heat_budget(self.ctx, _p(out)), "routing_heat_budget")
-        return out
+        return self._routing_budget("routing_heat_budget", 5)
 
     def routing_heat_clear(self):
         """Back to the scheme without temperatures; TT and TR are dropped, the water stays."""
@@ -768,10 +751,7 @@ class ELMState:
 
     def water_balance_read(self, which, col0=0, n=None):
         """Row `which` (hydrology.WB_BEGWB .. hydrology.WB_TOTSOILICE) of columns [col0, col0 + n): float64 [n].  Synchronises."""
-        n = self.ncols - col0 if n is None else int(n)
-        out = np.empty(max(n, 0), dtype=np.float64)
-        self._chk(self.lib.elmk_water_balance_read(self.ctx, int(which), _p(out), int(col0), n), "water_balance_read")
-        return out
+        return self._read_row("water_balance_read", which, col0, n, self.ncols, clamp=True)
 
     def water_balance_rows(self):
         """Every row of the feature: float64 [WB_NROWS, ncols], the `wb` of hydrology.water_balance_end."""
@@ -796,10 +776,7 @@ class ELMState:
 
     def active_layer_read(self, which, col0=0, n=None):
         """Row ALT_ALT, ALT_ALTMAX or ALT_ALTMAX_LASTYEAR of columns [col0, col0 + n): float64 [n].  Synchronises."""
-        n = int(self.ncols - col0 if n is None else n)
-        out = np.empty(n, dtype=np.float64)
-        self._chk(self.lib.elmk_active_layer_read(self.ctx, int(which), _p(out), int(col0), n), "active_layer_read")
-        return out
+        return self._read_row("active_layer_read", which, col0, n, self.ncols)
 
     def active_layer_clear(self):
         """Free the three rows (the index fields keep their values)."""
@@ -821,11 +798,7 @@ class ELMState:
 
     def soil_hydrology_init(self, zwt=None, wa=None):
         """ZWT and WA from [ncols] each; None: ELM's cold start (wa = 4000 mm, zwt = hydrology.cold_start_zwt).  Synchronises."""
-        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (zwt, wa)]
-        for v in a:
-            if v is not None and v.size != self.ncols:
-                raise ValueError(f"soil_hydrology_init: {v.size} values for {self.ncols} columns")
-        self._chk(self.lib.elmk_soil_hydrology_init(self.ctx, *(None if v is None else _p(v) for v in a)), "soil_hydrology_init")
+        self._init_rows("soil_hydrology_init", (zwt, wa), "columns")
 
     def soil_hydrology(self, dt):
         """The stage for every column: one launch, stream-ordered, no sync.  Call after advance_physics."""
@@ -833,10 +806,7 @@ class ELMState:
 
     def soil_hydrology_read(self, which, col0=0, n=None):
         """Row `which` (hydrology.ZWT .. hydrology.FSAT) of columns [col0, col0 + n): float64 [n].  Synchronises."""
-        n = int(self.ncols - col0 if n is None else n)
-        out = np.empty(n, dtype=np.float64)
-        self._chk(self.lib.elmk_soil_hydrology_read(self.ctx, int(which), _p(out), int(col0), n), "soil_hydrology_read")
-        return out
+        return self._read_row("soil_hydrology_read", which, col0, n, self.ncols)
 
     def soil_hydrology_rows(self):
         """Every row of the feature: float64 [HYD_NROWS, ncols], the `rows` of hydrology.step."""
@@ -858,10 +828,7 @@ class ELMState:
 
     def soil_hydrology_frost_read(self, which, col0=0, n=None):
         """Row `which` (hydrology.Q_PERCH_MAX .. hydrology.QFLX_DRAIN_PERCHED) of columns [col0, col0 + n): float64 [n].  Synchronises."""
-        n = int(self.ncols - col0 if n is None else n)
-        out = np.empty(n, dtype=np.float64)
-        self._chk(self.lib.elmk_soil_hydrology_frost_read(self.ctx, int(which), _p(out), int(col0), n), "soil_hydrology_frost_read")
-        return out
+        return self._read_row("soil_hydrology_frost_read", which, col0, n, self.ncols)
 
     def soil_hydrology_frost_rows(self):
         """Every row of the extension: float64 [HYDF_NROWS, ncols], the `frost` of hydrology.step."""

@@ -1347,8 +1347,8 @@ int elmk_routing_reservoir_clear(elmk_ctx *ctx);
  * Model. Earth Syst. 7, 2015): the tributary store and the main channel of every cell carry a water temperature, TT and TR.  Heat
  * enters with the runoff (surface runoff at the ground's temperature, subsurface runoff at a soil layer's), moves with the water,
  * and is exchanged through the water surface: absorbed shortwave and longwave, emitted longwave, sensible and latent heat.  The
- * pattern is the inundation's and the reservoirs': a template parameter on the existing kernels' code (k_routing.hip:
- * k_kinematic_prep<.., HEAT>, and the sub-step's body as k_kinematic_step_heat), no run flag and no new call or launch in the step.
+ * pattern is the inundation's and the reservoirs': a template parameter on the existing kernels (k_routing.hip:
+ * k_kinematic_prep<.., HEAT>, k_kinematic_step<.., HEAT>), no run flag and no new call or launch in the step.
  * The heat reads the water and never writes it.  elmkernels_amd/routing.py: heat_tables(), heat_prep(), heat_phi(), heat_settle() and
  * kinematic_call(..., heat=) restate it on the host.
  *

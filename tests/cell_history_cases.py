@@ -11,6 +11,7 @@ from elmkernels_amd import irrigation as ir
 from elmkernels_amd import routing as rt
 from tests import inundation_cases as ic
 from tests import irrigation_supply_cases as sc
+from tests.river_cases import finite  # noqa: F401 (the tests take it from here)
 
 DT = 1800.0
 TOL, THR = 1.0e-9, 0.1
@@ -51,10 +52,6 @@ def river_case(ncols, ncells, seed, cells_with_columns=None):
     return dict(ncols=ncols, ncells=ncells, cols=cols, scal=scal, soil=soil, sched=sched, rows=rows, map=m, ddist=ddist, area=area,
                 params=p, rdepth=rdepth, eprof=eprof, volr=volr, wh=wh, wt=wt, wf=wf, down=nets.get("forest", nets["outlets"]),
                 rate0=rate0, nleft0=nleft0, runoff=runoff)
-
-
-def finite(x, value=7.0):
-    return np.where(np.isfinite(x) & (np.abs(x) < 1e200), x, value)
 
 
 def context(G, lib_path=None, kinematic=True, flood=True, supply=True, routing=True, init=True, nsub=2):

@@ -20,7 +20,6 @@ import functools
 import numpy as np
 
 from elmkernels_amd import _lib as L
-from elmkernels_amd import active_layer as al
 from elmkernels_amd import hydrology as hy
 from elmkernels_amd import irrigation as ir
 from elmkernels_amd import regrid as RG
@@ -244,47 +243,13 @@ def full_context(graph, lib_path=None, G=None, thr=THR, withdraw=True, init=True
 
 # ---- the same steps through the stand-alone calls ------------------------------------------------------------------------------------
 def full_stepwise(D, rec, steps, dt=DT):
-    """The stand-alone calls in RUN_STEP's order (api_run.cpp; launch_advance of elmk_api.cpp for the irrigation's place): solar
-    geometry, the step's records, the record time, phenology, forcing, aerosol deposition, init_timestep, the water balance's begin,
-    the fused seven, the irrigation at the step's time of day (the supply limit's launch follows it), soil temperature, snow hydrology,
-    surface fluxes, soil hydrology, conservation, the flag summary, the water balance, the routing, the active layer with the step's
-    rollover bits, the accumulators, the history sample.  What elmk_run keeps in its ring rows is kept on the context (D._diag) for
-    full_snapshot."""
-    cons, fo, fb, mms, nbad, first = [], [], [], [], [], []
-    for p in steps:
-        decday, doy = float(p["decday"]), int(p["doy"])
-        D.solar_geometry(dt, decday, doy)
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        D.set_forcing_record_time(REC_TIMES[f])
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], True)
-        D.aerosol_deposition(int(p["month1"]), int(p["month2"]), float(p["month_wt1"]), float(p["month_wt2"]))
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        st.timestep7_fused(D, dt)
-        D.irrigation(dt, ir.time_of_day(decday, doy))
-        st.kokkos_soil_temperature(D, dt)
-        st.kokkos_snow_hydrology(D, dt)
-        st.kokkos_surface_fluxes(D, dt)
-        D.soil_hydrology(dt)
-        cons.append(st.kokkos_evaluate_conservation(D, dt))
-        flags, bad = D.error_summary()
-        fo.append(flags)
-        fb.append(bad)
-        m, n, c = D.water_balance(dt)
-        mms.append(m)
-        nbad.append(n)
-        first.append(c)
-        D.routing(dt)
-        D.active_layer_update(al.rollover(doy, decday))
-        D.accum_update()
-        D.history_accumulate()
-    D._diag = (np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64), np.array(mms), np.array(nbad, np.int64),
-               np.array(first, np.int64))
+    """run_cases.stepwise with every stage on and the record times.  What elmk_run keeps in its ring rows is kept on the context
+    (D._diag) for full_snapshot."""
+    from tests.run_cases import stepwise
+
+    r = stepwise(D, rec, steps, ALL_FLAGS, dt, rec_times=REC_TIMES)
+    mms, nbad, first = zip(*r.bal)
+    D._diag = tuple(r) + (np.array(mms), np.array(nbad, np.int64), np.array(first, np.int64))
 
 
 def run(D, steps, flags=ALL_FLAGS, dt=DT):

@@ -1,7 +1,6 @@
 """The inputs of the soil hydrology tests, host and device: `generated` (columns that take every branch of the stage), `edge_columns`
 (the edge tier), the six-step chain of the oracle's physics with the stage and its closure, a hand-built column; the permafrost tier on
-top of them (`add_frost`, `generated_frost`); and, for the device tests, contexts with the stage enabled and the stepwise calls with
-the stage in them."""
+top of them (`add_frost`, `generated_frost`); and, for the device tests, contexts with the stage enabled."""
 import numpy as np
 
 from elmkernels_amd import hydrology as hy
@@ -502,7 +501,7 @@ class Count(dict):
         self[name] = self.get(name, 0) + 1
 
 
-# ---- contexts with the stage, and the stepwise calls with it ---------------------------------------------------------------------------
+# ---- contexts with the stage -----------------------------------------------------------------------------------------------------------
 def _new(cols, scal, soil, rows, lib_path=None, lat=None, lon=None):
     n = rows.shape[1]
     if lat is None:
@@ -527,25 +526,3 @@ def _new_frost(cols, scal, soil, rows, frost, lib_path=None, lat=None, lon=None)
 def _physics(D):
     st.kokkos_init_timestep(D)
     st.advance_physics(D, DT)
-
-
-def _stepwise(D, rec, steps):
-    """run_cases.stepwise with the stage between the physics and the conservation row."""
-    cons, fo, fb = [], [], []
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        cons.append(st.kokkos_evaluate_conservation(D, DT))
-        flags, first = D.error_summary()
-        fo.append(flags)
-        fb.append(first)
-    return np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)

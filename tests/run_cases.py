@@ -4,6 +4,9 @@ records before every step, elmk_solar_geometry, elmk_phenology, elmk_get_forcing
 elmk_evaluate_conservation and elmk_error_summary after every step), the upload of the series, and the bit-for-bit assertions."""
 import numpy as np
 
+from elmkernels_amd import active_layer as al
+from elmkernels_amd import irrigation as ir
+from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests import helpers as H
@@ -74,29 +77,77 @@ def _pair(base, graph=True, lib_path=None):
     return A, B
 
 
-def stepwise(D, rec, steps, qbot_is_rh=False, history=False, rec_late=None, late_from=None):
-    """The existing calls; returns conservation [nsteps, 8, 3], flags [nsteps], first [nsteps].  rec_late: the records from step
-    late_from on."""
-    cons, fo, fb = [], [], []
+class StepRows(tuple):
+    """What stepwise returns: (conservation [nsteps, 8, 3], flags [nsteps], first [nsteps]) as run_diagnostics gives them, with .bal,
+    water_balance's (triples, nbad, first) of every step where RUN_WATER_BALANCE ran, and .qirr, the QFLX_IRRIG row after every step
+    where RUN_IRRIGATION ran."""
+    bal = qirr = ()
+
+
+def stepwise(D, rec, steps, flags=0, dt=DT, rec_late=None, late_from=None, rec_times=None, reservoir_time=False, per_step=None):
+    """What D.run(dt, steps, flags) does, through the stand-alone calls in RUN_STEP's order (api_run.cpp; launch_advance of elmk_api.cpp
+    for the irrigation's place).  This is the one restatement of that order:
+      solar geometry; the step's records, uploaded from the host; the record time (rec_times: one per forcing slot); phenology; forcing
+      (RUN_QBOT_IS_RH); aerosol deposition (RUN_AEROSOL); init_timestep; water_balance_begin (RUN_WATER_BALANCE); the physics -
+      advance_physics or, with RUN_IRRIGATION, its split form: the fused seven, irrigation at the step's time of day (the supply
+      limit's launch follows it), soil temperature, snow hydrology, surface fluxes; soil_hydrology (RUN_HYDROLOGY); conservation and
+      the flag summary; water_balance (RUN_WATER_BALANCE); the reservoirs' time (reservoir_time: the run derives it from the step, a
+      stand-alone call is told) then routing (RUN_ROUTING); active_layer_update with the step's rollover bits (RUN_ALT); accum_update
+      (RUN_ACCUM); history_accumulate (RUN_HISTORY).
+    rec_late: the records from step late_from on.  per_step: (list, function) - the list receives function(D) after every step."""
+    on = lambda f: bool(flags & f)  # noqa: E731
+    cons, fo, fb, bal, qirr = [], [], [], [], []
     for s, p in enumerate(steps):
         R = rec_late if (rec_late is not None and s >= late_from) else rec
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
+        decday, doy = float(p["decday"]), int(p["doy"])
+        D.solar_geometry(dt, decday, doy)
         f = int(p["forc_slot"])
         for k in st.SERIES_FORCING:
             D.upload(k, np.stack([R[k][f], R[k][f + 1]], axis=1))
         for k in st.SERIES_PHENOLOGY:
             D.upload(k, np.stack([R[k][p["month1"]], R[k][p["month2"]]], axis=1))
+        if rec_times is not None:
+            D.set_forcing_record_time(rec_times[f])
         st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], qbot_is_rh)
+        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], on(st.RUN_QBOT_IS_RH))
+        if on(st.RUN_AEROSOL):
+            D.aerosol_deposition(int(p["month1"]), int(p["month2"]), float(p["month_wt1"]), float(p["month_wt2"]))
         st.kokkos_init_timestep(D)
-        st.advance_physics(D, DT)
-        cons.append(st.kokkos_evaluate_conservation(D, DT))
-        flags, first = D.error_summary()
-        fo.append(flags)
+        if on(st.RUN_WATER_BALANCE):
+            D.water_balance_begin()
+        if on(st.RUN_IRRIGATION):
+            st.timestep7_fused(D, dt)
+            D.irrigation(dt, ir.time_of_day(decday, doy))
+            st.kokkos_soil_temperature(D, dt)
+            st.kokkos_snow_hydrology(D, dt)
+            st.kokkos_surface_fluxes(D, dt)
+        else:
+            st.advance_physics(D, dt)
+        if on(st.RUN_HYDROLOGY):
+            D.soil_hydrology(dt)
+        cons.append(st.kokkos_evaluate_conservation(D, dt))
+        flagged, first = D.error_summary()
+        fo.append(flagged)
         fb.append(first)
-        if history:
+        if on(st.RUN_WATER_BALANCE):
+            bal.append(D.water_balance(dt))
+        if on(st.RUN_IRRIGATION):
+            qirr.append(D.irrigation_read(ir.QFLX_IRRIG))
+        if on(st.RUN_ROUTING):
+            if reservoir_time:
+                D.routing_reservoir_time(rt.month_of_doy(doy), rt.month_begins(doy, decday))
+            D.routing(dt)
+        if on(st.RUN_ALT):
+            D.active_layer_update(al.rollover(doy, decday))
+        if on(st.RUN_ACCUM):
+            D.accum_update()
+        if on(st.RUN_HISTORY):
             D.history_accumulate()
-    return np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)
+        if per_step is not None:
+            per_step[0].append(per_step[1](D))
+    out = StepRows((np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)))
+    out.bal, out.qirr = bal, qirr
+    return out
 
 
 def upload_series(D, rec, forc_slots=None):
@@ -126,6 +177,20 @@ def assert_same_state(A, B, cols):
             assert same(B[name], np.ascontiguousarray(cols[name], dtype=B[name].dtype)), f"series input {name} of the run context against the upload"
         else:
             assert same(A[name], B[name]), f"field {name} of the stepwise context against the run context"
+
+
+def snapshot(D, **rows):
+    """Every non-series field and, under each keyword, the rows the caller read beside them."""
+    out = {k: D[k] for k in D.fields if k not in SERIES}
+    out.update(rows)
+    return out
+
+
+def assert_same(a, b, skip=()):
+    """Two snapshots bit for bit, key by key."""
+    assert a.keys() == b.keys()
+    for k, v in a.items():
+        assert k in skip or same(v, b[k]), k
 
 
 def assert_same_rows(got, want):

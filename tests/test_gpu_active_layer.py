@@ -225,18 +225,6 @@ def _context(base, graph, entries=False):
     return D, out
 
 
-def _stepwise(D, rec, steps, entries=False):
-    rows = []
-    for s in range(len(steps)):
-        c, o, b = stepwise(D, rec, steps[s:s + 1])
-        D.active_layer_update(al.rollover(int(steps[s]["doy"]), float(steps[s]["decday"])))
-        if entries:
-            D.accum_update()
-            D.history_accumulate()
-        rows.append((c[0], o[0], b[0]))
-    return [np.array([r[i] for r in rows]) for i in range(3)]
-
-
 def _snapshot(D, entries=None):
     out = {k: D[k] for k in D.fields if k not in SERIES}
     for w in ROWS:
@@ -261,7 +249,7 @@ def stepwise_result(base):
     out = {}
     for entries in (False, True):
         A, e = _context(base, False, entries)
-        diag = _stepwise(A, base[5], new_year_schedule(), entries)
+        diag = stepwise(A, base[5], new_year_schedule(), st.RUN_ALT | ((st.RUN_ACCUM | st.RUN_HISTORY) if entries else 0))
         out[entries] = (diag, _snapshot(A, e))
         A.close()
     return out

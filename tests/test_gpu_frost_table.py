@@ -11,9 +11,9 @@ from elmkernels_amd import _lib as L
 from elmkernels_amd import hydrology as hy
 from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
-from tests.hydrology_cases import (BRANCHES, CHAIN_STEPS, FROST_BRANCHES, Count, _new, _new_frost, _physics, _stepwise, add_frost, clear_snow,
+from tests.hydrology_cases import (BRANCHES, CHAIN_STEPS, FROST_BRANCHES, Count, _new, _new_frost, _physics, add_frost, clear_snow,
                                    generated_frost, prepare)
-from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, upload_series
+from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
@@ -132,7 +132,7 @@ def _assert_same(a, b):
 @pytest.fixture(scope="module")
 def stepwise_result(base):
     A = _context(base, False)
-    diag = _stepwise(A, base[0][5], schedule(NSTEPS))
+    diag = stepwise(A, base[0][5], schedule(NSTEPS), st.RUN_HYDROLOGY)
     out = (diag, _snapshot(A))
     A.close()
     return out
@@ -169,7 +169,7 @@ def test_the_captured_run_step_follows_the_extension(base, graph):
             elif turn == "enabled again":
                 D.soil_hydrology_frost_enable(2.0 * frost[hy.Q_PERCH_MAX])
         liq0 = A["h2osoi_liq"]
-        diag = _stepwise(A, b[5], S[s:s + 1])
+        diag = stepwise(A, b[5], S[s:s + 1], st.RUN_HYDROLOGY)
         B.run(DT, S[s:s + 1], st.RUN_HYDROLOGY)
         for g, w in zip(B.run_diagnostics(), diag):
             assert same(g, w), turn

@@ -11,7 +11,7 @@ from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests.parity_cases import WETLAND
-from tests.hydrology_cases import (BRANCHES, CHAIN_STEPS, CLOSURE_BOUND, CLOSURE_FIELDS, CLOSURE_MEASURED, _new, _physics, _stepwise, clear_snow,
+from tests.hydrology_cases import (BRANCHES, CHAIN_STEPS, CLOSURE_BOUND, CLOSURE_FIELDS, CLOSURE_MEASURED, _new, _physics, clear_snow,
                                    closure, generated, host_chain, prepare)
 from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, run_demo
@@ -162,7 +162,7 @@ def _assert_same(a, b):
 @pytest.fixture(scope="module")
 def stepwise_result(base):
     A = _context(base, False)
-    diag = _stepwise(A, base[0][5], schedule(NSTEPS))
+    diag = stepwise(A, base[0][5], schedule(NSTEPS), st.RUN_HYDROLOGY)
     out = (diag, _snapshot(A))
     A.close()
     return out

@@ -15,8 +15,8 @@ from elmkernels_amd import hydrology as hy
 from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests import parity_cases as P
-from tests.hydrology_cases import EDGE_CLASS_NAMES, _new, _new_frost, _stepwise, edge_columns, prepare
-from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests.hydrology_cases import EDGE_CLASS_NAMES, _new, _new_frost, edge_columns, prepare
+from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, stepwise, upload_series
 
 pytestmark = pytest.mark.gpu
 
@@ -158,7 +158,7 @@ def test_run_equals_stepwise_on_the_edge_tier(frost, lib_path):
     """elmk_run with ELMK_RUN_HYDROLOGY over two steps on the edge tier, graph on and graph off, against the stepwise calls: the
     diagnostics rows, every state field and every row, bit for bit (the device against itself: NaN for NaN)."""
     A, rec = _run_context(frost, lib_path, False)
-    want_diag = _stepwise(A, rec, schedule(NSTEPS))
+    want_diag = stepwise(A, rec, schedule(NSTEPS), st.RUN_HYDROLOGY)
     want = _snapshot(A, frost)
     A.close()
     for graph in (True, False):

@@ -17,7 +17,7 @@ from tests import helpers as H
 from tests.hydrology_cases import _new, clear_snow, prepare
 from tests.irrigation_cases import CHAIN_STEPS, chain_tod, generated, smpso_of
 from tests.parity_cases import WETLAND
-from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, upload_series
+from tests.run_cases import DT, NREC, SERIES, _inputs, assert_same, device, same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
@@ -155,42 +155,6 @@ def _context(base, graph, lib_path=None, irrig=True, wb=True, tape=False):
     return D
 
 
-def _stepwise(D, rec, steps, history=False, irrig=True):
-    """The stand-alone calls in elmk_run's order, with the split form of the physics: W0, the fused seven, the stage at the step's time
-    of day, soil temperature, snow hydrology, surface fluxes, the soil hydrology, conservation, the flag summary, W1 - W8."""
-    cons, fo, fb, bal, qirr = [], [], [], [], []
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        if irrig:
-            st.timestep7_fused(D, DT)
-            D.irrigation(DT, ir.time_of_day(float(p["decday"]), int(p["doy"])))
-            st.kokkos_soil_temperature(D, DT)
-            st.kokkos_snow_hydrology(D, DT)
-            st.kokkos_surface_fluxes(D, DT)
-        else:
-            st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        cons.append(st.kokkos_evaluate_conservation(D, DT))
-        flags, first = D.error_summary()
-        fo.append(flags)
-        fb.append(first)
-        bal.append(D.water_balance(DT))
-        if irrig:
-            qirr.append(D.irrigation_read(ir.QFLX_IRRIG))
-        if history:
-            D.history_accumulate()
-    return (np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)), bal, qirr
-
-
 def _snapshot(D, irrig=True):
     out = {k: D[k] for k in D.fields if k not in SERIES}
     out["hyd"], out["wb"] = D.soil_hydrology_rows(), D.water_balance_rows()
@@ -199,17 +163,11 @@ def _snapshot(D, irrig=True):
     return out
 
 
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert same(v, b[k]), k
-
-
 @pytest.fixture(scope="module")
 def stepwise_result(base):
     A = _context(base, False)
-    diag, bal, qirr = _stepwise(A, base[0][5], schedule(NSTEPS))
-    out = (diag, bal, qirr, _snapshot(A))
+    r = stepwise(A, base[0][5], schedule(NSTEPS), FLAGS)
+    out = (tuple(r), r.bal, r.qirr, _snapshot(A))
     A.close()
     return out
 
@@ -230,7 +188,7 @@ def test_run_equals_stepwise(base, stepwise_result, graph):
     for s, (wm, wn, wf) in enumerate(want_bal):
         assert bits(mms[s]) == bits(wm) and (int(nbad[s]), int(first[s])) == (wn, wf), s
     got = _snapshot(B)
-    _assert_same(got, want)
+    assert_same(got, want)
     q = got["irr"][ir.QFLX_IRRIG]
     assert (q > 0.0).sum() > NCOL // 10 and (got["irr"][ir.NLEFT] > 0.0).any() and (np.array(qirr) > 0.0).any(axis=1).sum() >= NSTEPS - 1
     f = {k: B[k] for k in WB_FIELDS}
@@ -255,7 +213,7 @@ def test_an_unflagged_run_never_irrigates(base):
         D.run(DT, steps, FLAGS & ~st.RUN_IRRIGATION)
     assert bits(B.irrigation_rows()) == bits(rows0)
     # (B's budget takes the term of the untouched QFLX_IRRIG row, +0.0: the same bits)
-    _assert_same(_snapshot(A, irrig=False), _snapshot(B, irrig=False))
+    assert_same(_snapshot(A, irrig=False), _snapshot(B, irrig=False))
     B.run(DT, steps[:1], FLAGS)
     assert (B.irrigation_read(ir.NLEFT) <= 3.0).any() and (B.irrigation_read(ir.QFLX_IRRIG) > 0.0).any()
     A.close()
@@ -311,7 +269,7 @@ def test_restart_4_plus_4_equals_8(base):
         Cx = _context(base, True, tape=True)
         Cx.restart_load(image)
         Cx.run(DT, S8[4:], flags)
-        _assert_same(_snapshot(Cx), want)
+        assert_same(_snapshot(Cx), want)
         assert bits(Cx.history_read(Cx._tape)) == bits(want_tape)
         Cx.close()
 
@@ -338,7 +296,7 @@ def test_refusals_change_nothing(base):
             *(lambda s=s: D.irrigation_enable(s) for s in bad_sched))
     D.irrigation_clear()  # nothing to free: OK
     assert D.device_bytes == bytes0 and D.restart_size() == size0
-    _assert_same(_snapshot(D, irrig=False), before)
+    assert_same(_snapshot(D, irrig=False), before)
     # a stream being captured
     with captured(D) as cap:
         s32 = np.ascontiguousarray(sched, dtype=np.int32)
@@ -361,24 +319,24 @@ def test_refusals_change_nothing(base):
             lambda: D.irrigation_read(0, col0=NCOL - 1, n=2), lambda: D.irrigation_read(0, col0=-1, n=1),
             lambda: D.run(DT + 0.5, S1, FLAGS), lambda: D.history_add_row(0, "irrigation", 3, "avg"))
     assert D.device_bytes == bytes1 and D.restart_size() == size1
-    _assert_same(_snapshot(D), state1)
+    assert_same(_snapshot(D), state1)
     # a row entry of the family bars the clear
     D.history_add_row(0, "irrigation", ir.QFLX_IRRIG, "avg")
     size_e, bytes_e = D.restart_size(), D.device_bytes
     refused(D.irrigation_clear, match="elmk_history_clear first")
     assert D.device_bytes == bytes_e and D.restart_size() == size_e
-    _assert_same(_snapshot(D), state1)
+    assert_same(_snapshot(D), state1)
     D.history_clear()
     assert D.restart_size() == size1
     # a land unit that is not soil or crop: nothing is enqueued
     D.set_land(**WETLAND)
     D.irrigation(DT, 0)
-    _assert_same(_snapshot(D), state1)
+    assert_same(_snapshot(D), state1)
     D.set_land(**synth.TEST_LAND)
     # the following step
     for X in (D, W):
         X.run(DT, S1, FLAGS)
-    _assert_same(_snapshot(D), _snapshot(W))
+    assert_same(_snapshot(D), _snapshot(W))
     assert (D.irrigation_read(ir.QFLX_IRRIG) == 1.0e-4).all()
     D.irrigation_clear()
     refused(lambda: D.irrigation_read(0), match="not enabled")

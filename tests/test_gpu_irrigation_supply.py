@@ -14,7 +14,7 @@ from elmkernels_amd import state as st
 from tests.hydrology_cases import _new, clear_snow, prepare
 from tests.irrigation_cases import generated, smpso_of
 from tests.irrigation_supply_cases import CASES, INF, NAN, cell_map, cell_values, census
-from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests.run_cases import DT, NREC, SERIES, _inputs, assert_same, same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
@@ -140,32 +140,6 @@ def _context(base, graph, lib_path=None, thr=THR):
     return D
 
 
-def _stepwise(D, rec, steps):
-    """The stand-alone calls in elmk_run's order: W0, the fused seven, elmk_irrigation at the step's time of day (the limit's launch
-    follows it while the limit is on), the rest of the physics, the soil hydrology, conservation, the flag summary, W1 - W8, the routing."""
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        st.timestep7_fused(D, DT)
-        D.irrigation(DT, ir.time_of_day(float(p["decday"]), int(p["doy"])))
-        st.kokkos_soil_temperature(D, DT)
-        st.kokkos_snow_hydrology(D, DT)
-        st.kokkos_surface_fluxes(D, DT)
-        D.soil_hydrology(DT)
-        st.kokkos_evaluate_conservation(D, DT)
-        D.error_summary()
-        D.water_balance(DT)
-        D.routing(DT)
-
-
 def _snapshot(D, limit=True):
     out = {k: D[k] for k in D.fields if k not in SERIES}
     out["hyd"], out["wb"], out["irr"] = D.soil_hydrology_rows(), D.water_balance_rows(), D.irrigation_rows()
@@ -173,12 +147,6 @@ def _snapshot(D, limit=True):
     if limit:
         out["sup"] = _sup_rows(D)
     return out
-
-
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert same(v, b[k]), k
 
 
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "nograph"])
@@ -190,10 +158,10 @@ def test_run_equals_stepwise_and_the_key_follows_the_switch(base, graph):
     steps = schedule(2 * NSTEPS)
     rec = base[0][5]
     A, B = _context(base, False), _context(base, graph)
-    _stepwise(A, rec, steps[:NSTEPS])
+    stepwise(A, rec, steps[:NSTEPS], FLAGS)
     B.run(DT, steps[:NSTEPS], FLAGS)
     a = _snapshot(A)
-    _assert_same(_snapshot(B), a)
+    assert_same(_snapshot(B), a)
     assert (a["sup"][ir.UNMET_SUM] > 0.0).any() and (a["irr"][ir.NLEFT] > 0.0).any()
     P = _context(base, graph, thr=None)  # never limited
     P.run(DT, steps[:NSTEPS], FLAGS)
@@ -204,17 +172,17 @@ def test_run_equals_stepwise_and_the_key_follows_the_switch(base, graph):
     unmet = a["sup"][ir.UNMET_SUM]
     for D in (A, B):
         D.irrigation_supply_clear()
-    _stepwise(A, rec, steps[NSTEPS:])
+    stepwise(A, rec, steps[NSTEPS:], FLAGS)
     B.run(DT, steps[NSTEPS:], FLAGS)
-    _assert_same(_snapshot(B, limit=False), _snapshot(A, limit=False))
+    assert_same(_snapshot(B, limit=False), _snapshot(A, limit=False))
     # on again
     for D in (A, B):
         D.irrigation_supply_enable(THR)
         D.irrigation_supply_init(unmet)
-    _stepwise(A, rec, steps[:NSTEPS])
+    stepwise(A, rec, steps[:NSTEPS], FLAGS)
     B.run(DT, steps[:NSTEPS], FLAGS)
     a = _snapshot(A)
-    _assert_same(_snapshot(B), a)
+    assert_same(_snapshot(B), a)
     assert (a["sup"][ir.UNMET_SUM] >= unmet).all()
     for D in (A, B, P):
         D.close()
@@ -245,7 +213,7 @@ def test_restart_3_plus_3_equals_6(base, lib_path):
     Cx.routing_init(volr, qsum, count)
     Cx.irrigation_supply_init(unmet)
     Cx.run(DT, steps[3:], FLAGS)
-    _assert_same(_snapshot(Cx), want)
+    assert_same(_snapshot(Cx), want)
     Cx.close()
 
 
@@ -281,7 +249,7 @@ def test_refusals_and_interlocks_change_nothing(base):
     refused(*(lambda v=v: D.irrigation_supply_enable(v) for v in (-0.1, 1.0, 1.5, NAN, INF, -INF)), match="threshold")
     refused(lambda: D.irrigation_supply_enable(THR), match=f"column {int(m[1][7])} is in more than one cell")
     assert D.device_bytes == bytes0 and D.restart_size() == size0
-    _assert_same(_snapshot(D, limit=False), before)
+    assert_same(_snapshot(D, limit=False), before)
     # the map the tests use: every column once
     D.routing_set_withdrawal(False)
     D.routing_clear()
@@ -311,13 +279,13 @@ def test_refusals_and_interlocks_change_nothing(base):
     D.routing_kinematic_enable(params)
     D.routing_kinematic_clear()
     assert D.device_bytes == bytes1 and D.restart_size() == size0
-    _assert_same(_snapshot(D), state1)
+    assert_same(_snapshot(D), state1)
     # the following step is the step of a context that met no refusal
     W = _context(base, True)
     W.irrigation_supply_init(np.full(NCELL, 7.0))
     for X in (D, W):
         X.run(DT, S1, FLAGS)
-    _assert_same(_snapshot(D), _snapshot(W))
+    assert_same(_snapshot(D), _snapshot(W))
     # the clear: the figures from before the enable, the existing refusals in their old words
     D.irrigation_supply_clear()
     refused(lambda: D.irrigation_supply_read(0), match="not enabled")
@@ -342,7 +310,7 @@ def test_a_context_without_the_limit_is_what_it_was(base):
     assert (B.device_bytes, B.restart_size()) == figures
     for D in (A, B):
         D.run(DT, steps, FLAGS)
-    _assert_same(_snapshot(A, limit=False), _snapshot(B, limit=False))
+    assert_same(_snapshot(A, limit=False), _snapshot(B, limit=False))
     assert bits(A.restart_save()) == bits(B.restart_save()) and (A.device_bytes, A.restart_size()) == (B.device_bytes, B.restart_size())
     # the step after, stepwise, against irrigation.step alone
     p = schedule(4)[3:]

@@ -152,7 +152,7 @@ def test_gridded_history_stepwise_and_run_equal_the_host_fold(graph):
     names = sorted({f for _, f, _ in GRIDDED})
     steps = GR.schedule()
     for s in range(NSTEPS):
-        GR.stepwise(A, rec, steps[s:s + 1], history=True)
+        GR.stepwise(A, rec, steps[s:s + 1], st.RUN_HISTORY)
         ref.fold({k: host_aggregate(A, k, ptr, col, w) for k in names})
     for D in (B, Cc):
         D.run_reserve(NREC, NSTEPS)
@@ -353,7 +353,7 @@ def test_fp32_state_library():
     ref = CellTapes(entries, np.diff(ptr) == 0)
     steps = GR.schedule(4)
     for s in range(4):
-        GR.stepwise(D, rec, steps[s:s + 1], history=True)
+        GR.stepwise(D, rec, steps[s:s + 1], st.RUN_HISTORY)
         ref.fold({f: host_aggregate(D, f, ptr, col, w) for _, f, _ in entries})
     t = D["t_grnd"]
     assert np.array_equal(t, t.astype(np.float32).astype(np.float64))

@@ -84,17 +84,17 @@ def test_ers_stepwise(base, lib_path):
     sch = schedule()
     A = device(base, lib_path=lib_path)
     ids = _history(A)
-    stepwise(A, rec, sch, history=True)
+    stepwise(A, rec, sch, st.RUN_HISTORY)
     B = device(base, lib_path=lib_path)
     _history(B)
-    stepwise(B, rec, sch[:N], history=True)
+    stepwise(B, rec, sch[:N], st.RUN_HISTORY)
     img = B.restart_save()
     B.close()
     R.verify(img)
     Cx, ids_c = _fresh(base, lib_path=lib_path)
     Cx.restart_load(img)
     assert [Cx.history_count(t) for t in range(4)] == [N, N, 0, 0]
-    stepwise(Cx, rec, sch[N:], history=True)
+    stepwise(Cx, rec, sch[N:], st.RUN_HISTORY)
     # the series inputs hold the last step's records in both
     _assert_same(_snapshot(A, ids), _snapshot(Cx, ids_c))
     A.close()
@@ -137,7 +137,7 @@ def test_decomposition_change(base):
     sch = schedule()
     A = device(base)
     ids = _history(A, gridded=False)
-    stepwise(A, rec, sch, history=True)
+    stepwise(A, rec, sch, st.RUN_HISTORY)
     want = _snapshot(A, ids)
     A.close()
     halves = [(0, 1400), (1400, n - 1400)]
@@ -145,7 +145,7 @@ def test_decomposition_change(base):
     for c0, m in halves:
         half = device(_sub(base, c0, m))
         _history(half, gridded=False)
-        stepwise(half, _sub(base, c0, m)[5], sch[:N], history=True)
+        stepwise(half, _sub(base, c0, m)[5], sch[:N], st.RUN_HISTORY)
         imgs.append(half.restart_save(c0))
         half.close()
     full = R.merge(imgs[::-1])
@@ -154,7 +154,7 @@ def test_decomposition_change(base):
         sub = _sub(base, c0, m)
         D, ids_d = _fresh(sub, gridded=False)
         D.restart_load(part, c0)
-        stepwise(D, sub[5], sch[N:], history=True)
+        stepwise(D, sub[5], sch[N:], st.RUN_HISTORY)
         got = _snapshot(D, ids_d)
         for k in D.fields:
             assert same(got[k], want[k][c0:c0 + m]), k
@@ -188,7 +188,7 @@ def test_refusals_leave_the_context_as_it_was(base):
     sch = schedule()
     B = device(base)
     _history(B)
-    stepwise(B, rec, sch[:N], history=True)
+    stepwise(B, rec, sch[:N], st.RUN_HISTORY)
     img = B.restart_save()
     B.close()
     D, ids = _fresh(base)
@@ -238,8 +238,8 @@ def test_refusals_leave_the_context_as_it_was(base):
     # the context still gives the bits of a clean one
     Cx, ids_c = _fresh(base)
     Cx.restart_load(img)
-    stepwise(D, rec, sch[N:N + 1], history=True)
-    stepwise(Cx, rec, sch[N:N + 1], history=True)
+    stepwise(D, rec, sch[N:N + 1], st.RUN_HISTORY)
+    stepwise(Cx, rec, sch[N:N + 1], st.RUN_HISTORY)
     _assert_same(_snapshot(D, ids), _snapshot(Cx, ids_c))
     D.close()
     Cx.close()

@@ -3,6 +3,7 @@ routing.qin_from_rows) bit for bit on every row, in both builds, over ten chaine
 the edge values in cells and columns of their own; the withdrawal on and off; the stage inside elmk_run against the stepwise calls,
 graph on and off; restarts through read / count / init; the budget; every refusal and interlock; a context that never enables it."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -12,15 +13,17 @@ from elmkernels_amd import hydrology as hy
 from elmkernels_amd import irrigation as ir
 from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
-from tests.hydrology_cases import _new, clear_snow, prepare
+from tests import river_cases as rv
+from tests.hydrology_cases import _new, prepare
 from tests.irrigation_cases import generated
-from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests.river_cases import NCELL, NSTEPS, TOL, read_rows, river_snapshot, set_runoff
+from tests.routing_kinematic_cases import cell_map, networks
+from tests.run_cases import DT, assert_same, schedule, stepwise
 from tests.support import bits, captured
 
 pytestmark = pytest.mark.gpu
 
 NCOLS = 1001
-TOL = 1.0e-9
 ROWS = (rt.VOLR, rt.QIN, rt.QOUT, rt.QOUT_SUM)
 NAN, INF = float("nan"), float("inf")
 
@@ -28,27 +31,7 @@ NAN, INF = float("nan"), float("inf")
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def base():
-    b = _inputs(NCOLS, 611)
-    clear_snow(b[0])
-    return b, prepare(b[0], 612)
-
-
-def cell_map(ncells, seed):
-    """A CSR map with 0 .. 5 columns per cell over NCOLS columns (a column may serve several cells, as the output grid allows), weights
-    that are no partition of one; column 5 (negative runoff) and column 9 (NaN runoff) are the single column of a cell each where there
-    are cells enough, and cell 0 of a grid of more than one cell has no columns."""
-    rng = np.random.default_rng(seed)
-    cnt = rng.integers(0, 6, ncells)
-    if ncells > 1:
-        cnt[0] = 0
-    if ncells >= 8:
-        cnt[3] = cnt[6] = 1
-    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    col = rng.integers(0, NCOLS, int(ptr[-1])).astype(np.int32)
-    col[(col == 5) | (col == 9)] = 11
-    if ncells >= 8:
-        col[ptr[3]], col[ptr[6]] = 5, 9
-    return ptr, col, rng.uniform(0.05, 1.5, col.size)
+    return rv.base()
 
 
 def runoff(call, lib_path):
@@ -60,35 +43,9 @@ def runoff(call, lib_path):
     return q
 
 
-def networks(n, seed):
-    """The issue's network shapes at n cells: name -> down."""
-    idx = np.arange(n)
-    nets = {"outlets": np.full(n, -1, np.int32), "chain": np.append(idx[1:], -1).astype(np.int32), "reverse": (idx - 1).astype(np.int32)}
-    if n >= 3:
-        # eight cells (fewer on a small grid) at indices 0, 255, 256, 511 and the last four drain into one cell; the rest is a chain
-        # into the same cell's neighbour
-        t = n // 2
-        srcs = sorted({i for i in (0, 255, 256, 511, n - 4, n - 3, n - 2, n - 1) if 0 <= i < n and i != t})[:8]
-        d = np.full(n, -1, np.int32)
-        d[srcs] = t
-        nets["eight"] = d
-        rng = np.random.default_rng(seed)
-        d = np.full(n, -1, np.int32)
-        deg = np.zeros(n, np.int64)
-        perm = rng.permutation(n)  # the forest runs along a random order of the cells, so upstream cells lie on both sides
-        for i in range(n - 1):
-            if rng.random() < 0.05:
-                continue
-            j = int(perm[rng.integers(i + 1, min(i + 1 + 30, n))])
-            if deg[j] < 8:
-                d[perm[i]] = j
-                deg[j] += 1
-        nets["forest"] = d
-    return nets
-
-
 def cell_values(n, seed):
-    """ddist, area and the initial VOLR with each edge value in a cell of its own where there are cells enough."""
+    """ddist, area and the initial VOLR with each edge value in a cell of its own where there are cells enough.  Not
+    routing_kinematic_cases.cell_values: that one draws the scheme's parameters before VOLR and has no capped reaches (ddist 19 .. 21)."""
     rng = np.random.default_rng(seed)
     ddist = np.exp(rng.uniform(np.log(500.0), np.log(60000.0), n))
     area = rng.uniform(0.5e8, 2.5e8, n)
@@ -104,28 +61,10 @@ def cell_values(n, seed):
     return ddist, area, volr
 
 
-def _ctx(base, lib_path, ncells, seed=3):
-    b, rows = base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.water_balance_enable(TOL)
-    ptr, col, w = cell_map(ncells, seed)
-    D.set_output_grid(ptr, col, w, fill=NAN)
-    D._map = (ptr, col, w)
-    return D
-
-
-def set_runoff(D, q):
-    D.upload("qflx_snwcp_liq", q)
-    D.water_balance(DT)
-    got = D.water_balance_read(hy.WB_QRUNOFF)
-    return got
-
-
-def read_rows(D):
-    return [D.routing_read(w) for w in ROWS]
-
-
 NSUBS, DTS = (1, 2, 7, 64), (1.0, 1800.0, 86400.0)
+
+
+_ctx = functools.partial(rv.context, hydrology=False)  # (the hydrology has not stepped: its runoff terms are zero)
 
 
 # ---- 1. the stage against the restatement -------------------------------------------------------------------------------------------
@@ -151,7 +90,7 @@ def test_ten_chained_calls_equal_the_restatement(base, ncells, lib_path):
             cld = (ncells + 63) // 64 * 64
             npad = rt.npad_of(up)
             assert D.device_bytes - bytes0 >= (6 * 8 + 8 + 8 + 4 * npad + 4) * cld
-            assert not any(r.any() for r in read_rows(D)) and D.routing_count() == 0
+            assert not any(r.any() for r in read_rows(D, ROWS)) and D.routing_count() == 0
             D.routing_init(volr0)
             volr, qsum = volr0.copy(), np.zeros(ncells)
             for c in range(10):
@@ -163,7 +102,7 @@ def test_ten_chained_calls_equal_the_restatement(base, ncells, lib_path):
                 volr, qout = rt.call(volr, qin, kout, up, dt, nsub)
                 with np.errstate(all="ignore"):
                     qsum = rt._canon(qsum + qout)
-                got = read_rows(D)
+                got = read_rows(D, ROWS)
                 for g, want, what in zip(got, (volr, qin, qout, qsum), ("VOLR", "QIN", "QOUT", "QOUT_SUM")):
                     assert bits(g) == bits(want), (name, nsub, dt, c, what, np.nonzero(g.view(np.uint64) != want.view(np.uint64))[0][:5])
                 assert D.routing_count() == c + 1
@@ -189,7 +128,7 @@ def test_the_edge_values_do_what_the_statement_says(base):
     D.routing_init(volr0)
     set_runoff(D, runoff(0, None))
     D.routing(1800.0)
-    v, qin, qout, _ = read_rows(D)
+    v, qin, qout, _ = read_rows(D, ROWS)
     assert (qout[[1, 3, 5, 11, 15]] == 0.0).all()  # 0, -0, negative, NaN, -inf
     assert qout[13] == INF and np.isnan(v[13]) and v[14] == INF
     assert qout[9] == rt.flow(np.array([1e300]), rt.EFFVEL / ddist[9], 1800.0)[0] and qout[9] > 1e290
@@ -246,7 +185,7 @@ def test_withdrawal_on_and_off(lib_path):
         for D, on in ((A, False), (B, True)):
             qin = rt.qin_from_rows(ptr, col, w, q, area, qflx_irrig=qi if on else None)
             volr[on], qout = rt.call(volr[on], qin, kout, up, DT, 2)
-            got = read_rows(D)
+            got = read_rows(D, ROWS)
             assert bits(got[0]) == bits(volr[on]) and bits(got[1]) == bits(qin) and bits(got[2]) == bits(qout), (s, on)
     assert (volr[True] < 0.0).any() and bits(volr[True]) != bits(volr[False])
     assert (B.routing_read(rt.QOUT)[volr[True] < 0.0] >= 0.0).all()
@@ -256,7 +195,7 @@ def test_withdrawal_on_and_off(lib_path):
     B.routing_init(volr[False], A.routing_read(rt.QOUT_SUM), A.routing_count())
     for D in ctxs:
         D.routing(DT)
-    for g, h in zip(read_rows(A), read_rows(B)):
+    for g, h in zip(read_rows(A, ROWS), read_rows(B, ROWS)):
         assert bits(g) == bits(h)
     with pytest.raises(L.ElmkError, match="irrigation is not enabled"):
         B.routing_set_withdrawal(True)
@@ -265,71 +204,18 @@ def test_withdrawal_on_and_off(lib_path):
 
 
 # ---- 3. the run ----------------------------------------------------------------------------------------------------------------------
-NCOL, NCELL, NSTEPS = 193, 65, 6
 FLAGS = st.RUN_HYDROLOGY | st.RUN_WATER_BALANCE | st.RUN_ROUTING
 
 
 @pytest.fixture(scope="module")
 def run_base():
-    b = _inputs(NCOL, 531)
-    clear_snow(b[0])
-    rows = prepare(b[0], 532)
-    rng = np.random.default_rng(77)
-    cnt = rng.integers(0, 6, NCELL)
-    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    col = rng.integers(0, NCOL, int(ptr[-1])).astype(np.int32)
-    ddist, area, _ = cell_values(NCELL, 78)
-    return b, rows, (ptr, col, rng.uniform(0.1, 1.0, col.size)), networks(NCELL, 79)["forest"], ddist, area
+    G = rv.run_case()
+    G["ddist"] = cell_values(NCELL, 78)[0]  # (this module's cell_values: with the capped cells' short reaches)
+    return G
 
 
-def _run_context(run_base, graph, lib_path=None, routing=True, nsub=3):
-    b, rows, m, down, ddist, area = run_base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.set_graph(graph)
-    D.run_reserve(NREC, 2 * NSTEPS)
-    upload_series(D, b[5])
-    D.water_balance_enable(TOL)
-    D.set_output_grid(*m, fill=NAN)
-    if routing:
-        D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
-    return D
-
-
-def _stepwise(D, rec, steps, routing=True):
-    """The stand-alone calls in elmk_run's order, with elmk_routing after the water balance."""
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        st.kokkos_evaluate_conservation(D, DT)
-        D.error_summary()
-        D.water_balance(DT)
-        if routing:
-            D.routing(DT)
-
-
-def _snapshot(D, routing=True):
-    out = {k: D[k] for k in D.fields if k not in SERIES}
-    out["hyd"], out["wb"] = D.soil_hydrology_rows(), D.water_balance_rows()
-    if routing:
-        out["route"] = np.stack(read_rows(D))
-        out["count"] = np.array(D.routing_count())
-    return out
-
-
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert same(v, b[k]), k
+# (the linear scheme alone, its rows left at zero)
+_run_context = functools.partial(rv.run_context, parts=("routing",), init=False)
 
 
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "nograph"])
@@ -338,34 +224,34 @@ def test_run_equals_stepwise(run_base, graph):
     when the graph is on) against six more stepwise steps; the host restatement follows the same rows; the count advances by nsteps."""
     steps = schedule(2 * NSTEPS)
     A, B = _run_context(run_base, False), _run_context(run_base, graph)
-    _stepwise(A, run_base[0][5], steps[:NSTEPS])
+    stepwise(A, run_base["rec"], steps[:NSTEPS], FLAGS)
     B.run(DT, steps[:NSTEPS], FLAGS)
     assert B.routing_count() == NSTEPS
-    a = _snapshot(A)
-    _assert_same(_snapshot(B), a)
+    a = river_snapshot(A, ROWS)
+    assert_same(river_snapshot(B, ROWS), a)
     assert (a["route"][rt.QOUT] > 0.0).any() and (a["wb"][hy.WB_QRUNOFF] != 0.0).any()
     # the last call's rows from the restatement, given the storages before it
-    ptr, col, w = run_base[2]
-    _stepwise(A, run_base[0][5], steps[NSTEPS:NSTEPS + 1])
-    qin = rt.qin_from_rows(ptr, col, w, A.water_balance_read(hy.WB_QRUNOFF), run_base[5])
-    v, qout = rt.call(a["route"][rt.VOLR], qin, rt.EFFVEL / run_base[4], rt.upstream_map(run_base[3]), DT, 3)
+    ptr, col, w = run_base["map"]
+    stepwise(A, run_base["rec"], steps[NSTEPS:NSTEPS + 1], FLAGS)
+    qin = rt.qin_from_rows(ptr, col, w, A.water_balance_read(hy.WB_QRUNOFF), run_base["area"])
+    v, qout = rt.call(a["route"][rt.VOLR], qin, rt.EFFVEL / run_base["ddist"], rt.upstream_map(run_base["down"]), DT, 3)
     assert bits(A.routing_read(rt.VOLR)) == bits(v) and bits(A.routing_read(rt.QOUT)) == bits(qout)
-    _stepwise(A, run_base[0][5], steps[NSTEPS + 1:])
+    stepwise(A, run_base["rec"], steps[NSTEPS + 1:], FLAGS)
     B.run(DT, steps[NSTEPS:], FLAGS)
-    _assert_same(_snapshot(B), _snapshot(A))
+    assert_same(river_snapshot(B, ROWS), river_snapshot(A, ROWS))
     assert B.routing_count() == 2 * NSTEPS
     # without the flag the rows stay put, and the run is the run of a context without the feature
-    P = _run_context(run_base, graph, routing=False)
+    P = _run_context(run_base, graph, parts=())
     P.run(DT, steps[:NSTEPS], FLAGS & ~st.RUN_ROUTING)
     P.run(DT, steps[NSTEPS:], FLAGS & ~st.RUN_ROUTING)
-    before = np.stack(read_rows(B))
+    before = np.stack(read_rows(B, ROWS))
     B2 = _run_context(run_base, graph)
     B2.run(DT, steps[:NSTEPS], FLAGS & ~st.RUN_ROUTING)
     B2.run(DT, steps[NSTEPS:], FLAGS & ~st.RUN_ROUTING)
-    assert not np.stack(read_rows(B2)).any() and B2.routing_count() == 0
-    _assert_same(_snapshot(B2, routing=False), _snapshot(P, routing=False))
-    _assert_same(_snapshot(B, routing=False), _snapshot(P, routing=False))
-    assert bits(np.stack(read_rows(B))) == bits(before)
+    assert not np.stack(read_rows(B2, ROWS)).any() and B2.routing_count() == 0
+    assert_same(river_snapshot(B2, ()), river_snapshot(P, ()))
+    assert_same(river_snapshot(B, ()), river_snapshot(P, ()))
+    assert bits(np.stack(read_rows(B, ROWS))) == bits(before)
     for D in (A, B, B2, P):
         D.close()
 
@@ -378,7 +264,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     steps = schedule(NSTEPS)
     A = _run_context(run_base, True, lib_path)
     A.run(DT, steps, FLAGS)
-    want = _snapshot(A)
+    want = river_snapshot(A, ROWS)
     size_a = A.restart_size()
     A.close()
     B = _run_context(run_base, True, lib_path)
@@ -390,8 +276,8 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     Cx.restart_load(img)
     Cx.routing_init(volr, qsum, count)
     Cx.run(DT, steps[3:], FLAGS)
-    got = _snapshot(Cx)
-    _assert_same(got, want)
+    got = river_snapshot(Cx, ROWS)
+    assert_same(got, want)
     assert Cx.routing_count() == NSTEPS
     with np.errstate(all="ignore"):
         assert bits(got["route"][rt.QOUT_SUM] / Cx.routing_count()) == bits(want["route"][rt.QOUT_SUM] / NSTEPS)
@@ -415,7 +301,7 @@ def test_budget_equals_the_restatement(base, ncells):
     set_runoff(D, q)
     for _ in range(2):
         D.routing(1800.0)
-    v, qin, qout, _ = read_rows(D)
+    v, qin, qout, _ = read_rows(D, ROWS)
     got, want = D.routing_budget(), rt.budget(v, qin, qout, down)
     assert np.isfinite(want).all() and want[2] > 0.0
     assert bits(got) == bits(want)
@@ -425,7 +311,7 @@ def test_budget_equals_the_restatement(base, ncells):
 
 # ---- 6. refusals and interlocks ------------------------------------------------------------------------------------------------------
 def test_refusals_and_interlocks_change_nothing(run_base):
-    b, rows, m, down, ddist, area = run_base
+    b, rows, m, down, ddist, area = (run_base[k] for k in ("b", "rows", "map", "down", "ddist", "area"))
     S1 = schedule(1)
 
     def refused(*calls, match=None):
@@ -433,9 +319,9 @@ def test_refusals_and_interlocks_change_nothing(run_base):
             with pytest.raises(L.ElmkError, match=match):
                 call()
 
-    D = _run_context(run_base, True, routing=False)
+    D = _run_context(run_base, True, parts=())
     bytes0, size0 = D.device_bytes, D.restart_size()
-    before = _snapshot(D, routing=False)
+    before = river_snapshot(D, ())
     refused(lambda: D.routing(DT), D.routing_init, lambda: D.routing_read(0), D.routing_count, D.routing_reset_mean, D.routing_budget,
             lambda: D.routing_set_withdrawal(True), match="not enabled")
     refused(lambda: D.run(DT, S1, FLAGS), match="without the runoff routing enabled")
@@ -469,7 +355,7 @@ def test_refusals_and_interlocks_change_nothing(run_base):
         assert rc == -1 and b"captured" in D.lib.elmk_last_error(D.ctx)
     D.routing_clear()  # nothing to free: OK
     assert D.device_bytes == bytes0 and D.restart_size() == size0
-    _assert_same(_snapshot(D, routing=False), before)
+    assert_same(river_snapshot(D, ()), before)
     # what the feature needs
     N = _new(b[0], b[1], b[2], rows, None, b[3], b[4])
     refused(lambda: N.routing_enable(down, ddist, area), match="no output grid")
@@ -481,7 +367,7 @@ def test_refusals_and_interlocks_change_nothing(run_base):
     bytes1 = D.device_bytes
     assert D.restart_size() == size0  # the image is what it was
     D.routing_init(np.full(NCELL, 5.0e4))
-    state1 = _snapshot(D)
+    state1 = river_snapshot(D, ROWS)
     refused(lambda: D.routing_enable(down, ddist, area), match="already enabled")
     refused(*(lambda dt=dt: D.routing(dt) for dt in (0.0, -1800.0, NAN, INF)), match="dt must be finite and positive")
     refused(lambda: D.routing_read(4), lambda: D.routing_read(-1), lambda: D.routing_read(0, cell0=NCELL, n=1),
@@ -490,13 +376,13 @@ def test_refusals_and_interlocks_change_nothing(run_base):
     refused(lambda: D.set_output_grid(*m, fill=0.0), D.clear_output_grid, D.water_balance_clear, D.soil_hydrology_clear,
             match="elmk_routing_clear first")
     assert D.device_bytes == bytes1 and D.restart_size() == size0
-    _assert_same(_snapshot(D), state1)
+    assert_same(river_snapshot(D, ROWS), state1)
     # the following step is the step of a context that met no refusal
     W = _run_context(run_base, True, nsub=2)
     W.routing_init(np.full(NCELL, 5.0e4))
     for X in (D, W):
         X.run(DT, S1, FLAGS)
-    _assert_same(_snapshot(D), _snapshot(W))
+    assert_same(river_snapshot(D, ROWS), river_snapshot(W, ROWS))
     D.routing_clear()
     refused(lambda: D.routing_read(0), match="not enabled")
     assert D.device_bytes == bytes0 and D.restart_size() == size0
@@ -511,7 +397,7 @@ def test_a_context_without_the_feature_is_what_it_was(run_base):
     context of the process has enabled, run and cleared it, the same as a fresh context's afterwards, and the same through an enable
     and a clear of its own."""
     steps = schedule(2)
-    A = _run_context(run_base, True, routing=False)
+    A = _run_context(run_base, True, parts=())
     A.run(DT, steps, FLAGS & ~st.RUN_ROUTING)
     figures = (A.device_bytes, A.restart_size(), bits(A.restart_save()))
     B = _run_context(run_base, True)
@@ -521,10 +407,10 @@ def test_a_context_without_the_feature_is_what_it_was(run_base):
     assert B.device_bytes == figures[0]
     B.close()
     assert (A.device_bytes, A.restart_size(), bits(A.restart_save())) == figures
-    F = _run_context(run_base, True, routing=False)
+    F = _run_context(run_base, True, parts=())
     F.run(DT, steps, FLAGS & ~st.RUN_ROUTING)
     assert (F.device_bytes, F.restart_size(), bits(F.restart_save())) == figures
-    F.routing_enable(run_base[3], run_base[4], run_base[5])
+    F.routing_enable(run_base["down"], run_base["ddist"], run_base["area"])
     F.routing_clear()
     assert (F.device_bytes, F.restart_size(), bits(F.restart_save())) == figures
     A.close()

@@ -4,24 +4,24 @@ builds, over five chained calls on every network shape, size and nsub, the withd
 their own; the stage inside elmk_run against the stepwise calls, graph on and off; restarts through _read and _init and through a
 version-8 image; a row on a history tape; the clear; every refusal and interlock; the budget; the example."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from elmkernels_amd import _lib as L
 from elmkernels_amd import history as hs
-from elmkernels_amd import hydrology as hy
-from elmkernels_amd import irrigation as ir
 from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
 from tests import heat_cases as hc
-from tests.hydrology_cases import _new, clear_snow, prepare
-from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests import river_cases as rv
+from tests.hydrology_cases import _new
+from tests.river_cases import NCELL, NCOL, NSTEPS, TOL, differing, finite, host_inputs, read_rows, river_snapshot, set_runoff
+from tests.run_cases import DT, NREC, assert_same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1.0e-9
 KW_ROWS = (rt.VOLR, rt.QIN, rt.QOUT, rt.QOUT_SUM, rt.WH, rt.WT, rt.QSUR)
 HEAT_ROWS = (rt.TT, rt.TR, rt.HEAT, rt.HIN, rt.HSRF, rt.HADJ, rt.HOUT)
 ROWS = KW_ROWS + HEAT_ROWS
@@ -32,38 +32,7 @@ NAN, INF = hc.NAN, hc.INF
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def base():
-    b = _inputs(hc.NCOLS, 611)
-    clear_snow(b[0])
-    return b, prepare(b[0], 612)
-
-
-def _ctx(base, lib_path, ncells, seed=3, withdraw=False):
-    """The prepared context with the water balance, an output grid of ncells cells (heat_cases.heat_map), and the hydrology stepped once
-    so that its surface rows hold values.  withdraw: the irrigation enabled with no irrigated column and a rate that applies for the
-    whole test, stepped once so that its QFLX_IRRIG row holds it."""
-    b, rows = base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.water_balance_enable(TOL)
-    ptr, col, w = hc.heat_map(ncells, seed)
-    D.set_output_grid(ptr, col, w, fill=NAN)
-    D._map = (ptr, col, w)
-    D._qirr = None
-    if withdraw:
-        D.irrigation_enable(np.full(hc.NCOLS, ir.NOT_IRRIGATED, np.int32))
-        rate = np.where(np.arange(hc.NCOLS) % 2 == 0, np.random.default_rng(9).uniform(0.0, 3.0e-5, hc.NCOLS), 0.0)
-        D.irrigation_init(rate, np.full(hc.NCOLS, 1000.0))
-        D.irrigation(DT, 0)
-        D._qirr = D.irrigation_read(ir.QFLX_IRRIG)
-        assert (D._qirr > 0.0).any()
-    D.soil_hydrology(DT)
-    D._surf = (D.soil_hydrology_read(hy.QFLX_SURF), D.soil_hydrology_read(hy.QFLX_H2OSFC_SURF))
-    return D
-
-
-def set_runoff(D, q):
-    D.upload("qflx_snwcp_liq", q)
-    D.water_balance(DT)
-    return D.water_balance_read(hy.WB_QRUNOFF)
+    return rv.base()
 
 
 def set_columns(D, call, ncols=hc.NCOLS):
@@ -73,25 +42,15 @@ def set_columns(D, call, ncols=hc.NCOLS):
     return {k: np.asarray(D[k], np.float64) for k in hc.FIELDS}
 
 
-def read_rows(D, rows):
-    return [D.routing_read(w) for w in rows]
-
-
-def host_inputs(D, qrunoff, area):
-    ptr, col, w = D._map
-    return rt.qin_from_rows(ptr, col, w, qrunoff, area, qflx_irrig=D._qirr), rt.qsur_from_rows(ptr, col, w, D._surf[0], D._surf[1], area)
-
-
-def differing(g, want):
-    return np.nonzero(g.view(np.uint64) != want.view(np.uint64))[0][:5]
-
-
 def enable_all(D, down, ddist, area, p, nsub, shade, withdraw=False):
     D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
     if withdraw:
         D.routing_set_withdrawal(True)
     D.routing_kinematic_enable(p)
     D.routing_heat_enable(hc.SUBLEV, shade)
+
+
+_ctx = functools.partial(rv.context, cell_map=hc.heat_map)
 
 
 # ---- 1. the stage against the restatement -------------------------------------------------------------------------------------------
@@ -138,7 +97,7 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, withdraw, lib_pa
                 D.water_balance(DT)
                 set_columns(D, c % 3)
                 D.routing(dt)
-                qin, qsur = hosts[c % 3]
+                qin, qsur, _ = hosts[c % 3]
                 census = {} if census_case else None
                 heat = {"tab": tab, "prep": preps[c % 3], "tt": tt, "tr": tr, "census": census}
                 out = rt.kinematic_call(wh, wt, volr, qin, qsur, area, p, up, dt, nsub, heat=heat)
@@ -176,7 +135,7 @@ def test_the_edge_values_do_what_the_statement_says(base):
     D.routing_kinematic_init(wh0, wt0)
     D.routing_heat_init(tt0, tr0)
     q = set_runoff(D, hc.snwcp(0))
-    qin, qsur = host_inputs(D, q, area)
+    qin, qsur, _ = host_inputs(D, q, area)
     prep = rt.heat_prep(*D._map, set_columns(D, 0), tab)
     D.routing(dt)
     out = rt.kinematic_call(wh0, wt0, volr0, qin, qsur, area, p, rt.upstream_map(down), dt, 1, heat={"tab": tab, "prep": prep, "tt": tt0, "tr": tr0})
@@ -215,83 +174,15 @@ def test_the_edge_values_do_what_the_statement_says(base):
 
 
 # ---- 2. the run ----------------------------------------------------------------------------------------------------------------------
-NCOL, NCELL, NSTEPS = 193, 65, 6
 FLAGS = st.RUN_HYDROLOGY | st.RUN_WATER_BALANCE | st.RUN_ROUTING
-
-
-def _finite(x):
-    return np.where(np.isfinite(x) & (np.abs(x) < 1e200), x, 7.0)
 
 
 @pytest.fixture(scope="module")
 def run_base():
-    b = _inputs(NCOL, 531)
-    clear_snow(b[0])
-    rows = prepare(b[0], 532)
-    rng = np.random.default_rng(77)
-    cnt = rng.integers(0, 6, NCELL)
-    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    col = rng.integers(0, NCOL, int(ptr[-1])).astype(np.int32)
-    ddist, area, p, volr0, wh0, wt0 = hc.cell_values(NCELL, 78)
-    shade, tt0, tr0 = hc.heat_values(NCELL, 81)
-    water = tuple(_finite(x) for x in (volr0, wh0, wt0))
-    temps = tuple(np.where((x > 200.0) & (x < 400.0), x, 280.0) for x in (tt0, tr0))
-    return b, rows, (ptr, col, rng.uniform(0.1, 1.0, col.size)), hc.networks(NCELL, 79)["forest"], ddist, area, p, water, shade, temps
+    return rv.run_case(heat=True)
 
 
-def _run_context(run_base, graph, lib_path=None, heat=True, nsub=3, init=True):
-    b, rows, m, down, ddist, area, p, (volr, wh, wt), shade, (tt, tr) = run_base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.set_graph(graph)
-    D.run_reserve(NREC, 2 * NSTEPS)
-    upload_series(D, b[5])
-    D.water_balance_enable(TOL)
-    D.set_output_grid(*m, fill=NAN)
-    D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
-    D.routing_kinematic_enable(p)
-    if heat:
-        D.routing_heat_enable(hc.SUBLEV, shade)
-    if init:
-        D.routing_init(volr)
-        D.routing_kinematic_init(wh, wt)
-        if heat:
-            D.routing_heat_init(tt, tr)
-    return D
-
-
-def _stepwise(D, rec, steps):
-    """The stand-alone calls in elmk_run's order, with elmk_routing after the water balance."""
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        st.kokkos_evaluate_conservation(D, DT)
-        D.error_summary()
-        D.water_balance(DT)
-        D.routing(DT)
-
-
-def _snapshot(D, rows):
-    out = {k: D[k] for k in D.fields if k not in SERIES}
-    out["hyd"], out["wb"] = D.soil_hydrology_rows(), D.water_balance_rows()
-    out["route"] = np.stack(read_rows(D, rows))
-    out["count"] = np.array(D.routing_count())
-    return out
-
-
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert same(v, b[k]), k
+_run_context = functools.partial(rv.run_context, parts=("routing", "kinematic", "heat"))
 
 
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "nograph"])
@@ -301,26 +192,26 @@ def test_run_equals_stepwise(run_base, graph):
     form without it, and on again."""
     steps = schedule(2 * NSTEPS)
     A, B = _run_context(run_base, False), _run_context(run_base, graph)
-    _stepwise(A, run_base[0][5], steps[:3])
+    stepwise(A, run_base["rec"], steps[:3], FLAGS)
     B.run(DT, steps[:3], FLAGS)
-    a = _snapshot(A, ROWS)
-    _assert_same(_snapshot(B, ROWS), a)
+    a = river_snapshot(A, ROWS)
+    assert_same(river_snapshot(B, ROWS), a)
     assert np.isfinite(a["route"]).all() and (a["route"][7] != rt.TFRZ).any() and a["route"][10].any() and a["route"][11].any()
-    _stepwise(A, run_base[0][5], steps[3:NSTEPS])
+    stepwise(A, run_base["rec"], steps[3:NSTEPS], FLAGS)
     B.run(DT, steps[3:NSTEPS], FLAGS)
-    _assert_same(_snapshot(B, ROWS), _snapshot(A, ROWS))
+    assert_same(river_snapshot(B, ROWS), river_snapshot(A, ROWS))
     tt, tr = A.routing_read(rt.TT), A.routing_read(rt.TR)
     for X in (A, B):
         X.routing_heat_clear()
-    _stepwise(A, run_base[0][5], steps[NSTEPS:NSTEPS + 2])
+    stepwise(A, run_base["rec"], steps[NSTEPS:NSTEPS + 2], FLAGS)
     B.run(DT, steps[NSTEPS:NSTEPS + 2], FLAGS)
-    _assert_same(_snapshot(B, KW_ROWS), _snapshot(A, KW_ROWS))
+    assert_same(river_snapshot(B, KW_ROWS), river_snapshot(A, KW_ROWS))
     for X in (A, B):
-        X.routing_heat_enable(hc.SUBLEV, run_base[8])
+        X.routing_heat_enable(hc.SUBLEV, run_base["shade"])
         X.routing_heat_init(tt, tr)
-    _stepwise(A, run_base[0][5], steps[NSTEPS + 2:NSTEPS + 5])
+    stepwise(A, run_base["rec"], steps[NSTEPS + 2:NSTEPS + 5], FLAGS)
     B.run(DT, steps[NSTEPS + 2:NSTEPS + 5], FLAGS)
-    _assert_same(_snapshot(B, ROWS), _snapshot(A, ROWS))
+    assert_same(river_snapshot(B, ROWS), river_snapshot(A, ROWS))
     for X in (A, B):
         X.close()
 
@@ -334,7 +225,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     steps = schedule(NSTEPS)
     A = _run_context(run_base, True, lib_path)
     A.run(DT, steps, FLAGS)
-    want = _snapshot(A, ROWS)
+    want = river_snapshot(A, ROWS)
     size_a = A.restart_size()
     A.close()
     B = _run_context(run_base, True, lib_path)
@@ -349,12 +240,12 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     Cx.routing_kinematic_init(wh, wt)
     Cx.routing_heat_init(tt, tr)
     Cx.run(DT, steps[3:], FLAGS)
-    _assert_same(_snapshot(Cx, ROWS), want)
+    assert_same(river_snapshot(Cx, ROWS), want)
     # heat_init leaves the other entries' rows alone, and without rows gives TT = TR = TFRZ and zero diagnostics
     Cx.routing_heat_init()
     assert bits(Cx.routing_read(rt.TT)) == bits(np.full(NCELL, rt.TFRZ)) == bits(Cx.routing_read(rt.TR))
     assert not any(Cx.routing_read(w).any() for w in HEAT_ROWS[2:]) and bits(Cx.routing_read(rt.VOLR)) == bits(want["route"][0])
-    N = _run_context(run_base, True, lib_path, heat=False)
+    N = _run_context(run_base, True, lib_path, parts=("routing", "kinematic"))
     assert N.restart_size() == size_a
     N.close()
     Cx.close()
@@ -370,10 +261,10 @@ def test_restart_3_plus_3_through_a_version_8_image(run_base):
     steps = schedule(NSTEPS)
     A = _run_context(run_base, True)
     A.run(DT, steps, FLAGS)
-    want = _snapshot(A, ROWS)
+    want = river_snapshot(A, ROWS)
     size_off = A.restart_size()
     A.close()
-    P = _run_context(run_base, True, heat=False)  # a context that never had the extension
+    P = _run_context(run_base, True, parts=("routing", "kinematic"))  # a context that never had the extension
     P.set_option(st.OPT_RESTART_CELLS, 1)
     P.run(DT, steps[:3], FLAGS)
     img_plain = P.restart_save()
@@ -395,21 +286,21 @@ def test_restart_3_plus_3_through_a_version_8_image(run_base):
     img6 = B.restart_save()
     assert int(R.verify(img6)["header"]["version"]) == R.VERSION_ROUTING and bits(img6) == bits(img_plain)
     B.close()
-    state_p = _snapshot(P, KW_ROWS)
+    state_p = river_snapshot(P, KW_ROWS)
     with pytest.raises(L.ElmkError, match="the stream temperature"):
         P.restart_load(img)  # version 8 into a context without the heat
-    _assert_same(_snapshot(P, KW_ROWS), state_p)
+    assert_same(river_snapshot(P, KW_ROWS), state_p)
     P.close()
     Cx = _run_context(run_base, True, init=False)
     Cx.set_option(st.OPT_RESTART_CELLS, 1)
-    state_c = _snapshot(Cx, ROWS)
+    state_c = river_snapshot(Cx, ROWS)
     with pytest.raises(L.ElmkError, match="the stream temperature"):
         Cx.restart_load(img6)  # version 6 into a context with it
-    _assert_same(_snapshot(Cx, ROWS), state_c)
+    assert_same(river_snapshot(Cx, ROWS), state_c)
     Cx.restart_load(img)
     assert Cx.routing_count() == 3 and not any(Cx.routing_read(w).any() for w in HEAT_ROWS[2:])
     Cx.run(DT, steps[3:], FLAGS)
-    _assert_same(_snapshot(Cx, ROWS), want)
+    assert_same(river_snapshot(Cx, ROWS), want)
     Cx.set_option(st.OPT_RESTART_CELLS, 0)
     assert Cx.restart_size() == size_off
     Cx.close()
@@ -499,7 +390,8 @@ def test_clear_returns_to_the_scheme_without_temperatures(base, lib_path):
 # ---- 5. refusals ---------------------------------------------------------------------------------------------------------------------
 def test_refusals_change_nothing(run_base):
     """Every refusal of the four entries and of the interlocks, in both directions, with nothing changed by any."""
-    b, rows_, m, down, ddist, area, p, (volr, wh, wt), shade, (tt, tr) = run_base
+    b, rows_, m, down, ddist, area, p, volr, wh, wt, shade = (run_base[k] for k in ("b", "rows", "map", "down", "ddist", "area", "p", "volr", "wh", "wt", "shade"))
+    tt, tr = run_base["temps"]
 
     def refused(*calls, match=None):
         for call in calls:
@@ -522,7 +414,7 @@ def test_refusals_change_nothing(run_base):
     D.routing_kinematic_enable(p)
     D.routing_kinematic_init(wh, wt)
     bytes1 = D.device_bytes
-    state1 = _snapshot(D, KW_ROWS)
+    state1 = river_snapshot(D, KW_ROWS)
     refused(D.routing_heat_init, D.routing_heat_budget, match="the extension is not on")
     refused(*(lambda w=w: D.routing_read(w) for w in HEAT_ROWS), lambda: D.routing_read(20), match="unknown row")
     refused(lambda: enable(sub=-1), lambda: enable(sub=15), match=r"elmk_routing_heat_enable: sublev outside 0 \.\. 14$")
@@ -549,13 +441,13 @@ def test_refusals_change_nothing(run_base):
     refused(enable, match="elmk_routing_heat_enable: the reservoirs are on .elmk_routing_reservoir_clear first.$")
     D.routing_reservoir_clear()
     assert D.device_bytes == bytes1 and D.restart_size() == size0
-    _assert_same(_snapshot(D, KW_ROWS), state1)
+    assert_same(river_snapshot(D, KW_ROWS), state1)
 
     enable()
     bytes2 = D.device_bytes
     assert bytes2 > bytes1 and D.restart_size() == size0  # the image is what it was
     D.routing_heat_init(tt, tr)
-    state2 = _snapshot(D, ROWS)
+    state2 = river_snapshot(D, ROWS)
     refused(enable, match="already on")
     refused(D.routing_kinematic_clear, match="elmk_routing_heat_clear first")
     # ... and the other way: the inundation's and the reservoirs' enables are refused while the heat is on
@@ -572,7 +464,7 @@ def test_refusals_change_nothing(run_base):
         cap_.end()
         assert rcs == (-1, -1, -1) and b"captured" in D.lib.elmk_last_error(D.ctx)
     assert D.device_bytes == bytes2 and D.restart_size() == size0
-    _assert_same(_snapshot(D, ROWS), state2)
+    assert_same(river_snapshot(D, ROWS), state2)
     # the following call is the call of a context that met no refusal
     W = _run_context(run_base, True, nsub=2)
     for X in (D, W):
@@ -595,7 +487,7 @@ def test_refusals_change_nothing(run_base):
 def test_budget_equals_the_restatement(base, ncells):
     D = _ctx(base, None, ncells)
     ddist, area, p, volr0, wh0, wt0 = hc.cell_values(ncells, 40 + ncells)
-    volr0, wh0, wt0 = (_finite(x) for x in (volr0, wh0, wt0))
+    volr0, wh0, wt0 = (finite(x) for x in (volr0, wh0, wt0))
     shade, tt0, tr0 = hc.heat_values(ncells, 90 + ncells)
     tt0, tr0 = (np.where((x > 200.0) & (x < 400.0), x, 280.0) for x in (tt0, tr0))
     down = hc.networks(ncells, 5)["forest" if ncells >= 3 else "outlets"]

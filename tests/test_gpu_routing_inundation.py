@@ -5,6 +5,7 @@ cells of their own; the edge values by value against a scalar reading of I1 - I4
 graph on and off, with the extension switched between runs; restarts; the clear; the interlocks; every refusal; the budget; the river
 supply limit; the example."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -16,14 +17,15 @@ from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
 from tests import inundation_cases as ic
 from tests import irrigation_supply_cases as sc
-from tests.hydrology_cases import _new, clear_snow, prepare
+from tests import river_cases as rv
+from tests.hydrology_cases import _new, prepare
 from tests.irrigation_cases import generated
-from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests.river_cases import NCELL, NSTEPS, TOL, differing, finite, host_inputs, read_rows, river_snapshot, set_runoff
+from tests.run_cases import DT, NREC, assert_same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1.0e-9
 ROWS = (rt.VOLR, rt.QIN, rt.QOUT, rt.QOUT_SUM, rt.WH, rt.WT, rt.QSUR, rt.WF, rt.FLOOD_DEPTH, rt.FLOOD_FRAC)
 NAMES = ("VOLR", "QIN", "QOUT", "QOUT_SUM", "WH", "WT", "QSUR", "WF", "FLOOD_DEPTH", "FLOOD_FRAC")
 NAN, INF = ic.NAN, ic.INF
@@ -32,38 +34,7 @@ NAN, INF = ic.NAN, ic.INF
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def base():
-    b = _inputs(ic.NCOLS, 611)
-    clear_snow(b[0])
-    return b, prepare(b[0], 612)
-
-
-def _ctx(base, lib_path, ncells, seed=3):
-    """The prepared context with the water balance, an output grid of ncells cells, and the hydrology stepped once so that its surface
-    rows hold values."""
-    b, rows = base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.water_balance_enable(TOL)
-    ptr, col, w = ic.cell_map(ncells, seed)
-    D.set_output_grid(ptr, col, w, fill=NAN)
-    D._map = (ptr, col, w)
-    D.soil_hydrology(DT)
-    D._surf = (D.soil_hydrology_read(hy.QFLX_SURF), D.soil_hydrology_read(hy.QFLX_H2OSFC_SURF))
-    return D
-
-
-def set_runoff(D, q):
-    D.upload("qflx_snwcp_liq", q)
-    D.water_balance(DT)
-    return D.water_balance_read(hy.WB_QRUNOFF)
-
-
-def read_rows(D, rows=ROWS):
-    return [D.routing_read(w) for w in rows]
-
-
-def host_inputs(D, qrunoff, area):
-    ptr, col, w = D._map
-    return rt.qin_from_rows(ptr, col, w, qrunoff, area), rt.qsur_from_rows(ptr, col, w, D._surf[0], D._surf[1], area)
+    return rv.base()
 
 
 def enable_all(D, down, ddist, area, p, rdepth, eprof, nsub):
@@ -72,8 +43,7 @@ def enable_all(D, down, ddist, area, p, rdepth, eprof, nsub):
     D.routing_inundation_enable(rdepth, eprof)
 
 
-def differing(g, want):
-    return np.nonzero(g.view(np.uint64) != want.view(np.uint64))[0][:5]
+_ctx = functools.partial(rv.context, cell_map=ic.cell_map)
 
 
 # ---- 1. the stage against the restatement -------------------------------------------------------------------------------------------
@@ -108,7 +78,7 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
             bytes2 = D.device_bytes
             D.routing_inundation_enable(rdepth, eprof)
             assert D.device_bytes - bytes2 >= (3 + 25) * 8 * cld
-            assert not any(r.any() for r in read_rows(D))
+            assert not any(r.any() for r in read_rows(D, ROWS))
             D.routing_init(volr)
             D.routing_kinematic_init(wh, wt)
             D.routing_inundation_init(wf)
@@ -117,7 +87,7 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
                 D.upload("qflx_snwcp_liq", ic.snwcp(c % 3))  # the row the call reads is the water balance's of this moment
                 D.water_balance(DT)
                 D.routing(dt)
-                qin, qsur = hosts[c % 3]
+                qin, qsur, _ = hosts[c % 3]
                 seen = ic.call_census(wh, wt, volr, wf, qin, qsur, area, p, up, dt, nsub, tab)
                 union |= seen.any(axis=0)
                 if ncells >= 257:
@@ -126,7 +96,7 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
                 wh, wt, volr, qout, wf, depth, frac = rt.kinematic_call(wh, wt, volr, qin, qsur, area, p, up, dt, nsub, flood=(tab, wf))
                 with np.errstate(all="ignore"):
                     qsum = rt._canon(qsum + qout)
-                for g, want, what in zip(read_rows(D), (volr, qin, qout, qsum, wh, wt, qsur, wf, depth, frac), NAMES):
+                for g, want, what in zip(read_rows(D, ROWS), (volr, qin, qout, qsum, wh, wt, qsur, wf, depth, frac), NAMES):
                     assert bits(g) == bits(want), (name, nsub, dt, c, what, differing(g, want))
                 assert D.routing_count() == c + 1
             if ncells > 1:
@@ -196,7 +166,7 @@ def test_the_edge_values_do_what_the_statement_says(base):
     D.routing_inundation_init(wf0)
     set_runoff(D, ic.snwcp(0))
     D.routing(dt)
-    v, _, qout, _, _, _, _, wf, depth, frac = read_rows(D)
+    v, _, qout, _, _, _, _, wf, depth, frac = read_rows(D, ROWS)
     ch, ct, cr = rt.kinematic_params(p)
     et0 = rt.channel_flow(wt0, p[rt.TLEN], p[rt.TWIDTH], ct, dt)
     er0 = rt.channel_flow(volr0, p[rt.RLEN], p[rt.RWIDTH], cr, dt)
@@ -232,83 +202,15 @@ def test_the_edge_values_do_what_the_statement_says(base):
 
 
 # ---- 3. the run ----------------------------------------------------------------------------------------------------------------------
-NCOL, NCELL, NSTEPS = 193, 65, 6
 FLAGS = st.RUN_HYDROLOGY | st.RUN_WATER_BALANCE | st.RUN_ROUTING
 
 
 @pytest.fixture(scope="module")
 def run_base():
-    b = _inputs(NCOL, 531)
-    clear_snow(b[0])
-    rows = prepare(b[0], 532)
-    rng = np.random.default_rng(77)
-    cnt = rng.integers(0, 6, NCELL)
-    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    col = rng.integers(0, NCOL, int(ptr[-1])).astype(np.int32)
-    ddist, area, p0, volr0, wh0, wt0 = ic.cell_values(NCELL, 78)
-    volr0, wh0, wt0 = (np.where(np.isfinite(x) & (x < 1e200), x, 7.0) for x in (volr0, wh0, wt0))
-    flood = ic.flood_values(NCELL, 80, area, p0, volr0, wh0, wt0, 3, DT)
-    return b, rows, (ptr, col, rng.uniform(0.1, 1.0, col.size)), ic.networks(NCELL, 79)["forest"], ddist, area, flood
+    return rv.run_case(flood=True)
 
 
-def _finite(x):
-    return np.where(np.isfinite(x) & (np.abs(x) < 1e200), x, 7.0)
-
-
-def _run_context(run_base, graph, lib_path=None, flood=True, nsub=3, init=True):
-    b, rows, m, down, ddist, area, (rdepth, eprof, p, volr, wh, wt, wf) = run_base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.set_graph(graph)
-    D.run_reserve(NREC, 2 * NSTEPS)
-    upload_series(D, b[5])
-    D.water_balance_enable(TOL)
-    D.set_output_grid(*m, fill=NAN)
-    D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
-    D.routing_kinematic_enable(p)
-    if flood:
-        D.routing_inundation_enable(rdepth, eprof)
-    if init:
-        D.routing_init(volr)
-        D.routing_kinematic_init(wh, wt)
-        if flood:
-            D.routing_inundation_init(_finite(wf))
-    return D
-
-
-def _stepwise(D, rec, steps):
-    """The stand-alone calls in elmk_run's order, with elmk_routing after the water balance."""
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        st.kokkos_evaluate_conservation(D, DT)
-        D.error_summary()
-        D.water_balance(DT)
-        D.routing(DT)
-
-
-def _snapshot(D, rows=ROWS):
-    out = {k: D[k] for k in D.fields if k not in SERIES}
-    out["hyd"], out["wb"] = D.soil_hydrology_rows(), D.water_balance_rows()
-    if rows:
-        out["route"] = np.stack(read_rows(D, rows))
-        out["count"] = np.array(D.routing_count())
-    return out
-
-
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert same(v, b[k]), k
+_run_context = functools.partial(rv.run_context, parts=("routing", "kinematic", "inundation"))
 
 
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "nograph"])
@@ -317,30 +219,30 @@ def test_run_equals_stepwise(run_base, graph):
     (on the captured step when the graph is on) against six more; the extension switched off between two runs, which drops the captured
     step and runs the plain form, and on again, which brings the flood form back; floodplains wet throughout."""
     steps = schedule(2 * NSTEPS)
-    rdepth, eprof = run_base[6][0], run_base[6][1]
+    rdepth, eprof = run_base["rdepth"], run_base["eprof"]
     A, B = _run_context(run_base, False), _run_context(run_base, graph)
-    _stepwise(A, run_base[0][5], steps[:NSTEPS])
+    stepwise(A, run_base["rec"], steps[:NSTEPS], FLAGS)
     B.run(DT, steps[:NSTEPS], FLAGS)
-    a = _snapshot(A)
-    _assert_same(_snapshot(B), a)
+    a = river_snapshot(A, ROWS)
+    assert_same(river_snapshot(B, ROWS), a)
     r = a["route"]
     assert (r[7] > 0.0).any() and (r[8] > 0.0).any() and (r[9] > 0.0).any() and (r[7] == 0.0).any() and B.routing_count() == NSTEPS
-    _stepwise(A, run_base[0][5], steps[NSTEPS:])
+    stepwise(A, run_base["rec"], steps[NSTEPS:], FLAGS)
     B.run(DT, steps[NSTEPS:], FLAGS)
-    _assert_same(_snapshot(B), _snapshot(A))
+    assert_same(river_snapshot(B, ROWS), river_snapshot(A, ROWS))
     wf = A.routing_read(rt.WF)
     for X in (A, B):
         X.routing_inundation_clear()
-    _stepwise(A, run_base[0][5], steps[:2])
+    stepwise(A, run_base["rec"], steps[:2], FLAGS)
     B.run(DT, steps[:2], FLAGS)
-    _assert_same(_snapshot(B, ROWS[:7]), _snapshot(A, ROWS[:7]))
+    assert_same(river_snapshot(B, ROWS[:7]), river_snapshot(A, ROWS[:7]))
     for X in (A, B):
         X.routing_inundation_enable(rdepth, eprof)
         X.routing_inundation_init(wf)
-    _stepwise(A, run_base[0][5], steps[2:4])
+    stepwise(A, run_base["rec"], steps[2:4], FLAGS)
     B.run(DT, steps[2:4], FLAGS)
-    a = _snapshot(A)
-    _assert_same(_snapshot(B), a)
+    a = river_snapshot(A, ROWS)
+    assert_same(river_snapshot(B, ROWS), a)
     assert (a["route"][7] > 0.0).any() and B.routing_count() == 2 * NSTEPS + 4
     for X in (A, B):
         X.close()
@@ -355,7 +257,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     steps = schedule(NSTEPS)
     A = _run_context(run_base, True, lib_path)
     A.run(DT, steps, FLAGS)
-    want = _snapshot(A)
+    want = river_snapshot(A, ROWS)
     size_a = A.restart_size()
     A.close()
     B = _run_context(run_base, True, lib_path)
@@ -370,7 +272,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     Cx.routing_kinematic_init(wh, wt)
     Cx.routing_inundation_init(wf)
     Cx.run(DT, steps[3:], FLAGS)
-    _assert_same(_snapshot(Cx), want)
+    assert_same(river_snapshot(Cx, ROWS), want)
     # each init leaves the other entries' rows alone; inundation_init without a row zero-fills
     Cx.routing_init(volr, qsum, 2)
     Cx.routing_kinematic_init(wh, wt)
@@ -378,7 +280,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     Cx.routing_inundation_init()
     assert not any(Cx.routing_read(w).any() for w in (rt.WF, rt.FLOOD_DEPTH, rt.FLOOD_FRAC))
     assert bits(Cx.routing_read(rt.VOLR)) == bits(volr) and bits(Cx.routing_read(rt.WH)) == bits(wh) and Cx.routing_count() == 2
-    N = _run_context(run_base, True, lib_path, flood=False)
+    N = _run_context(run_base, True, lib_path, parts=("routing", "kinematic"))
     assert N.restart_size() == size_a
     N.close()
     Cx.close()
@@ -409,12 +311,12 @@ def test_clear_returns_to_the_channel_without_banks(base, lib_path):
     A.routing_inundation_init(wf0)
     for _ in range(3):
         A.routing(1800.0)
-    rows = read_rows(A)
+    rows = read_rows(A, ROWS)
     assert (rows[7] > 0.0).any() and bits(rows[0]) != bits(volr0)
     with pytest.raises(L.ElmkError, match="elmk_routing_inundation_clear first"):
         A.routing_kinematic_clear()
     assert A.device_bytes == bytes_fp
-    for g, h in zip(read_rows(A), rows):
+    for g, h in zip(read_rows(A, ROWS), rows):
         assert bits(g) == bits(h)
     A.routing_inundation_clear()
     A.routing_inundation_clear()  # nothing to free: OK
@@ -425,7 +327,7 @@ def test_clear_returns_to_the_channel_without_banks(base, lib_path):
         A.routing_read(rt.WF)
     B.routing_init(rows[0], rows[3], 3)
     B.routing_kinematic_init(rows[4], rows[5])
-    qin, qsur = host_inputs(A, A.water_balance_read(hy.WB_QRUNOFF), area)
+    qin, qsur, _ = host_inputs(A, A.water_balance_read(hy.WB_QRUNOFF), area)
     wh, wt, v = rows[4], rows[5], rows[0]
     for _ in range(2):
         for D in (A, B):
@@ -450,8 +352,7 @@ def test_clear_returns_to_the_channel_without_banks(base, lib_path):
 def test_refusals_change_nothing(run_base):
     """Every refusal of the four entries and of the interlock, with nothing changed by any; elmk_device_bytes and elmk_restart_size
     return to their figures after the clear."""
-    b, rows, m, down, ddist, area, (rdepth, eprof, p, volr, wh, wt, wf) = run_base
-    wf = _finite(wf)
+    b, rows, m, down, ddist, area, rdepth, eprof, p, volr, wh, wt, wf = (run_base[k] for k in ("b", "rows", "map", "down", "ddist", "area", "rdepth", "eprof", "p", "volr", "wh", "wt", "wf"))
 
     def refused(*calls, match=None):
         for call in calls:
@@ -475,7 +376,7 @@ def test_refusals_change_nothing(run_base):
     D.routing_kinematic_enable(p)
     D.routing_kinematic_init(wh, wt)
     bytes1 = D.device_bytes
-    state1 = _snapshot(D, ROWS[:7])
+    state1 = river_snapshot(D, ROWS[:7])
     refused(D.routing_inundation_init, D.routing_inundation_budget, match="the extension is not on")
     refused(*(lambda w=w: D.routing_read(w) for w in ROWS[7:]), lambda: D.routing_read(10), match="unknown row")
     for v in (0.0, -0.0, -1.0, NAN, INF, -INF):
@@ -508,13 +409,13 @@ def test_refusals_change_nothing(run_base):
         with pytest.raises(ValueError):
             call()
     assert D.device_bytes == bytes1 and D.restart_size() == size0
-    _assert_same(_snapshot(D, ROWS[:7]), state1)
+    assert_same(river_snapshot(D, ROWS[:7]), state1)
 
     D.routing_inundation_enable(rdepth, eprof)
     bytes2 = D.device_bytes
     assert bytes2 > bytes1 and D.restart_size() == size0  # the image is what it was
     D.routing_inundation_init(wf)
-    state2 = _snapshot(D)
+    state2 = river_snapshot(D, ROWS)
     refused(lambda: D.routing_inundation_enable(rdepth, eprof), match="already on")
     refused(D.routing_kinematic_clear, match="elmk_routing_inundation_clear first")
     refused(lambda: D.routing_read(10), lambda: D.routing_read(-1), lambda: D.routing_read(rt.WF, cell0=NCELL, n=1))
@@ -527,12 +428,12 @@ def test_refusals_change_nothing(run_base):
         cap.end()
         assert rcs == (-1, -1, -1) and b"captured" in D.lib.elmk_last_error(D.ctx)
     assert D.device_bytes == bytes2 and D.restart_size() == size0
-    _assert_same(_snapshot(D), state2)
+    assert_same(river_snapshot(D, ROWS), state2)
     # the following step is the step of a context that met no refusal
     W = _run_context(run_base, True, nsub=2)
     for X in (D, W):
         X.run(DT, schedule(1), FLAGS)
-    _assert_same(_snapshot(D), _snapshot(W))
+    assert_same(river_snapshot(D, ROWS), river_snapshot(W, ROWS))
     D.routing_inundation_clear()
     assert D.device_bytes == bytes1 and D.restart_size() == size0
     D.routing_inundation_enable(rdepth, eprof)
@@ -548,9 +449,9 @@ def test_refusals_change_nothing(run_base):
 def test_budget_equals_the_restatement(base, ncells):
     D = _ctx(base, None, ncells)
     ddist, area, p0, volr0, wh0, wt0 = ic.cell_values(ncells, 40 + ncells)
-    volr0, wh0, wt0 = (_finite(x) for x in (volr0, wh0, wt0))
+    volr0, wh0, wt0 = (finite(x) for x in (volr0, wh0, wt0))
     rdepth, eprof, p, volr0, wh0, wt0, wf0 = ic.flood_values(ncells, 60 + ncells, area, p0, volr0, wh0, wt0, 2, 1800.0)
-    wf0 = _finite(wf0)
+    wf0 = finite(wf0)
     if ncells == 1:
         volr0, wf0 = volr0 + 1.0e8, wf0 + 1.0e6
     down = ic.networks(ncells, 5)["forest" if ncells >= 3 else "outlets"]
@@ -563,14 +464,14 @@ def test_budget_equals_the_restatement(base, ncells):
     set_runoff(D, q)
     for _ in range(2):
         D.routing(1800.0)
-    rows = read_rows(D)
+    rows = read_rows(D, ROWS)
     want, want_kw, want_fp = rt.budget(rows[0], rows[1], rows[2], down), rt.kinematic_budget(rows[4], rows[5]), rt.inundation_budget(rows[7])
     assert np.isfinite(want).all() and np.isfinite(want_kw).all() and np.isfinite(want_fp).all() and want_fp[0] > 0.0
     for _ in range(2):  # (in turn: the three share the reduction's scratch)
         assert bits(D.routing_inundation_budget()) == bits(want_fp)
         assert bits(D.routing_kinematic_budget()) == bits(want_kw)
         assert bits(D.routing_budget()) == bits(want)
-    for g, h in zip(read_rows(D), rows):
+    for g, h in zip(read_rows(D, ROWS), rows):
         assert bits(g) == bits(h)  # (the calls change no row)
     D.close()
 

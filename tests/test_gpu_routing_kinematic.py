@@ -4,6 +4,7 @@ calls on every network shape, size, nsub and dt with the edge values in cells of
 elmk_run against the stepwise calls, graph on and off; restarts through read / init / kinematic_init; switching back to the linear
 scheme; the withdrawal on and off with the scheme on; both budgets; every refusal; a context that never turns the scheme on."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -13,15 +14,16 @@ from elmkernels_amd import hydrology as hy
 from elmkernels_amd import irrigation as ir
 from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
-from tests.hydrology_cases import _new, clear_snow, prepare
+from tests import river_cases as rv
+from tests.hydrology_cases import _new, prepare
 from tests.irrigation_cases import generated
-from tests.routing_kinematic_cases import CASES, NCOLS, cell_map, cell_values, flow_census, networks, snwcp
-from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests.routing_kinematic_cases import CASES, cell_map, cell_values, flow_census, networks, snwcp
+from tests.river_cases import NCELL, NSTEPS, TOL, host_inputs, read_rows, river_snapshot, set_runoff
+from tests.run_cases import DT, assert_same, schedule, stepwise
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1.0e-9
 ROWS = (rt.VOLR, rt.QIN, rt.QOUT, rt.QOUT_SUM, rt.WH, rt.WT, rt.QSUR)
 NAMES = ("VOLR", "QIN", "QOUT", "QOUT_SUM", "WH", "WT", "QSUR")
 NAN, INF = float("nan"), float("inf")
@@ -30,38 +32,10 @@ NAN, INF = float("nan"), float("inf")
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def base():
-    b = _inputs(NCOLS, 611)
-    clear_snow(b[0])
-    return b, prepare(b[0], 612)
+    return rv.base()
 
 
-def _ctx(base, lib_path, ncells, seed=3):
-    """The prepared context with the water balance, an output grid of ncells cells, and the hydrology stepped once so that its surface
-    rows hold values."""
-    b, rows = base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.water_balance_enable(TOL)
-    ptr, col, w = cell_map(ncells, seed)
-    D.set_output_grid(ptr, col, w, fill=NAN)
-    D._map = (ptr, col, w)
-    D.soil_hydrology(DT)
-    D._surf = (D.soil_hydrology_read(hy.QFLX_SURF), D.soil_hydrology_read(hy.QFLX_H2OSFC_SURF))
-    return D
-
-
-def set_runoff(D, q):
-    D.upload("qflx_snwcp_liq", q)
-    D.water_balance(DT)
-    return D.water_balance_read(hy.WB_QRUNOFF)
-
-
-def read_rows(D, rows=ROWS):
-    return [D.routing_read(w) for w in rows]
-
-
-def host_inputs(D, qrunoff, area):
-    ptr, col, w = D._map
-    return rt.qin_from_rows(ptr, col, w, qrunoff, area), rt.qsur_from_rows(ptr, col, w, D._surf[0], D._surf[1], area)
+_ctx = rv.context
 
 
 # ---- 1. the stage against the restatement -------------------------------------------------------------------------------------------
@@ -86,7 +60,7 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
             bytes1 = D.device_bytes
             D.routing_kinematic_enable(p)
             assert D.device_bytes - bytes1 >= (6 + 7) * 8 * cld
-            assert not any(r.any() for r in read_rows(D)) and D.routing_count() == 0
+            assert not any(r.any() for r in read_rows(D, ROWS)) and D.routing_count() == 0
             D.routing_init(volr0)
             D.routing_kinematic_init(wh0, wt0)
             wh, wt, volr, qsum = wh0.copy(), wt0.copy(), volr0.copy(), np.zeros(ncells)
@@ -94,14 +68,14 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
                 D.upload("qflx_snwcp_liq", snwcp(c % 3))  # the row the call reads is the water balance's of this moment
                 D.water_balance(DT)
                 D.routing(dt)
-                qin, qsur = hosts[c % 3]
+                qin, qsur, _ = hosts[c % 3]
                 flow_census(seen, wh, wt, volr, area, p, dt / nsub)
                 wh, wt, volr, qout = rt.kinematic_call(wh, wt, volr, qin, qsur, area, p, up, dt, nsub)
                 with np.errstate(all="ignore"):
                     qsum = rt._canon(qsum + qout)
                     qsur_nonzero |= bool((qsur != 0.0).any())
                     qsub_negative |= bool((qin - qsur < 0.0).any())
-                for g, want, what in zip(read_rows(D), (volr, qin, qout, qsum, wh, wt, qsur), NAMES):
+                for g, want, what in zip(read_rows(D, ROWS), (volr, qin, qout, qsum, wh, wt, qsur), NAMES):
                     assert bits(g) == bits(want), (name, nsub, dt, c, what, np.nonzero(g.view(np.uint64) != want.view(np.uint64))[0][:5])
                 assert D.routing_count() == c + 1
             if ncells > 1:
@@ -131,7 +105,7 @@ def test_the_edge_values_do_what_the_statement_says(base):
     D.routing_kinematic_init(wh0, wt0)
     set_runoff(D, snwcp(0))
     D.routing(dt)
-    v, qin, qout, _, wh, wt, qsur = read_rows(D)
+    v, qin, qout, _, wh, wt, qsur = read_rows(D, ROWS)
     ch, ct, cr = rt.kinematic_params(p)
     et0 = rt.channel_flow(wt0, p[rt.TLEN], p[rt.TWIDTH], ct, dt)
     er0 = rt.channel_flow(volr0, p[rt.RLEN], p[rt.RWIDTH], cr, dt)
@@ -216,7 +190,7 @@ def test_withdrawal_on_and_off_with_the_scheme_on(lib_path):
             with np.errstate(all="ignore"):
                 qsum = rt._canon(qsum + qout)
             state[on] = (wh, wt, v, qsum)
-            for g, want, what in zip(read_rows(D), (v, qin, qout, qsum, wh, wt, qsur), NAMES):
+            for g, want, what in zip(read_rows(D, ROWS), (v, qin, qout, qsum, wh, wt, qsur), NAMES):
                 assert bits(g) == bits(want), (s, on, what, np.nonzero(g.view(np.uint64) != want.view(np.uint64))[0][:5])
         differs |= bits(A.routing_read(rt.QIN)) != bits(B.routing_read(rt.QIN))
         assert bits(A.routing_read(rt.QSUR)) == bits(B.routing_read(rt.QSUR))  # the withdrawal takes from QIN, and so from QSUB, alone
@@ -228,79 +202,23 @@ def test_withdrawal_on_and_off_with_the_scheme_on(lib_path):
     B.routing_kinematic_init(wh, wt)
     for D in ctxs:
         D.routing(DT)
-    for g, h in zip(read_rows(A), read_rows(B)):
+    for g, h in zip(read_rows(A, ROWS), read_rows(B, ROWS)):
         assert bits(g) == bits(h)
     for D in ctxs:
         D.close()
 
 
 # ---- 3. the run ----------------------------------------------------------------------------------------------------------------------
-NCOL, NCELL, NSTEPS = 193, 65, 6
 FLAGS = st.RUN_HYDROLOGY | st.RUN_WATER_BALANCE | st.RUN_ROUTING
 
 
 @pytest.fixture(scope="module")
 def run_base():
-    b = _inputs(NCOL, 531)
-    clear_snow(b[0])
-    rows = prepare(b[0], 532)
-    rng = np.random.default_rng(77)
-    cnt = rng.integers(0, 6, NCELL)
-    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    col = rng.integers(0, NCOL, int(ptr[-1])).astype(np.int32)
-    ddist, area, p = cell_values(NCELL, 78)[:3]
-    return b, rows, (ptr, col, rng.uniform(0.1, 1.0, col.size)), networks(NCELL, 79)["forest"], ddist, area, p
+    return rv.run_case()
 
 
-def _run_context(run_base, graph, lib_path=None, routing=True, kinematic=True, nsub=3):
-    b, rows, m, down, ddist, area, p = run_base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.set_graph(graph)
-    D.run_reserve(NREC, 2 * NSTEPS)
-    upload_series(D, b[5])
-    D.water_balance_enable(TOL)
-    D.set_output_grid(*m, fill=NAN)
-    if routing:
-        D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
-        if kinematic:
-            D.routing_kinematic_enable(p)
-    return D
-
-
-def _stepwise(D, rec, steps):
-    """The stand-alone calls in elmk_run's order, with elmk_routing after the water balance."""
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        st.kokkos_evaluate_conservation(D, DT)
-        D.error_summary()
-        D.water_balance(DT)
-        D.routing(DT)
-
-
-def _snapshot(D, rows=ROWS):
-    out = {k: D[k] for k in D.fields if k not in SERIES}
-    out["hyd"], out["wb"] = D.soil_hydrology_rows(), D.water_balance_rows()
-    if rows:
-        out["route"] = np.stack(read_rows(D, rows))
-        out["count"] = np.array(D.routing_count())
-    return out
-
-
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert same(v, b[k]), k
+# (the scheme on the linear routing, the rows left at zero)
+_run_context = functools.partial(rv.run_context, parts=("routing", "kinematic"), init=False)
 
 
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "nograph"])
@@ -309,32 +227,32 @@ def test_run_equals_stepwise(run_base, graph):
     the captured step when the graph is on) against six more stepwise steps; the host restatement follows the last call's rows."""
     steps = schedule(2 * NSTEPS)
     A, B = _run_context(run_base, False), _run_context(run_base, graph)
-    _stepwise(A, run_base[0][5], steps[:NSTEPS])
+    stepwise(A, run_base["rec"], steps[:NSTEPS], FLAGS)
     B.run(DT, steps[:NSTEPS], FLAGS)
     assert B.routing_count() == NSTEPS
-    a = _snapshot(A)
-    _assert_same(_snapshot(B), a)
+    a = river_snapshot(A, ROWS)
+    assert_same(river_snapshot(B, ROWS), a)
     r = a["route"]
     assert (r[2] > 0.0).any() and (r[4] > 0.0).any() and (r[5] > 0.0).any() and (r[6] != 0.0).any()
     # the next call's rows from the restatement, given the storages before it
-    ptr, col, w = run_base[2]
-    area, p = run_base[5], run_base[6]
-    _stepwise(A, run_base[0][5], steps[NSTEPS:NSTEPS + 1])
+    ptr, col, w = run_base["map"]
+    area, p = run_base["area"], run_base["p"]
+    stepwise(A, run_base["rec"], steps[NSTEPS:NSTEPS + 1], FLAGS)
     qin = rt.qin_from_rows(ptr, col, w, A.water_balance_read(hy.WB_QRUNOFF), area)
     qsur = rt.qsur_from_rows(ptr, col, w, A.soil_hydrology_read(hy.QFLX_SURF), A.soil_hydrology_read(hy.QFLX_H2OSFC_SURF), area)
-    wh, wt, v, qout = rt.kinematic_call(r[4], r[5], r[0], qin, qsur, area, p, rt.upstream_map(run_base[3]), DT, 3)
+    wh, wt, v, qout = rt.kinematic_call(r[4], r[5], r[0], qin, qsur, area, p, rt.upstream_map(run_base["down"]), DT, 3)
     for g, want in zip(read_rows(A, (rt.WH, rt.WT, rt.VOLR, rt.QOUT, rt.QSUR)), (wh, wt, v, qout, qsur)):
         assert bits(g) == bits(want)
-    _stepwise(A, run_base[0][5], steps[NSTEPS + 1:])
+    stepwise(A, run_base["rec"], steps[NSTEPS + 1:], FLAGS)
     B.run(DT, steps[NSTEPS:], FLAGS)
-    _assert_same(_snapshot(B), _snapshot(A))
+    assert_same(river_snapshot(B, ROWS), river_snapshot(A, ROWS))
     assert B.routing_count() == 2 * NSTEPS
     # the scheme turned off between two runs: the captured step is dropped and the linear scheme runs, as in the stepwise calls
     for X in (A, B):
         X.routing_kinematic_clear()
-    _stepwise(A, run_base[0][5], steps[:2])
+    stepwise(A, run_base["rec"], steps[:2], FLAGS)
     B.run(DT, steps[:2], FLAGS)
-    _assert_same(_snapshot(B, ROWS[:4]), _snapshot(A, ROWS[:4]))
+    assert_same(river_snapshot(B, ROWS[:4]), river_snapshot(A, ROWS[:4]))
     assert B.routing_count() == 2 * NSTEPS + 2
     for X in (A, B):
         X.close()
@@ -348,7 +266,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     steps = schedule(NSTEPS)
     A = _run_context(run_base, True, lib_path)
     A.run(DT, steps, FLAGS)
-    want = _snapshot(A)
+    want = river_snapshot(A, ROWS)
     size_a = A.restart_size()
     A.close()
     B = _run_context(run_base, True, lib_path)
@@ -362,7 +280,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     Cx.routing_init(volr, qsum, count)
     Cx.routing_kinematic_init(wh, wt)
     Cx.run(DT, steps[3:], FLAGS)
-    _assert_same(_snapshot(Cx), want)
+    assert_same(river_snapshot(Cx, ROWS), want)
     assert Cx.routing_count() == NSTEPS
     # routing_init leaves WH and WT alone; kinematic_init leaves VOLR, QOUT_SUM and the count alone
     Cx.routing_init(volr, qsum, 2)
@@ -421,7 +339,7 @@ def test_refusals_change_nothing(run_base):
     """Every refusal of the four entries, with nothing changed by any; elmk_device_bytes and elmk_restart_size return to their figures
     after the clear.  (The soil hydrology's absence cannot be reached through the entries: the routing needs the water balance, which
     needs it, and its clear is barred while the routing is enabled; the check stands behind them.)"""
-    b, rows, m, down, ddist, area, p = run_base
+    b, rows, m, down, ddist, area, p = (run_base[k] for k in ("b", "rows", "map", "down", "ddist", "area", "p"))
     S1 = schedule(1)
 
     def refused(*calls, match=None):
@@ -429,17 +347,17 @@ def test_refusals_change_nothing(run_base):
             with pytest.raises(L.ElmkError, match=match):
                 call()
 
-    D = _run_context(run_base, True, routing=False)
+    D = _run_context(run_base, True, parts=())
     bytes0, size0 = D.device_bytes, D.restart_size()
-    before = _snapshot(D, rows=())
+    before = river_snapshot(D, ())
     refused(lambda: D.routing_kinematic_enable(p), D.routing_kinematic_init, D.routing_kinematic_budget, match="not enabled")
     D.routing_kinematic_clear()  # nothing to free: OK
     assert D.device_bytes == bytes0 and D.restart_size() == size0
-    _assert_same(_snapshot(D, rows=()), before)
+    assert_same(river_snapshot(D, ()), before)
     D.routing_enable(down, ddist, area, rt.EFFVEL, 2)
     D.routing_init(np.full(NCELL, 5.0e4))
     bytes1 = D.device_bytes
-    state1 = _snapshot(D, ROWS[:4])
+    state1 = river_snapshot(D, ROWS[:4])
     refused(D.routing_kinematic_init, D.routing_kinematic_budget, match="the scheme is not on")
     refused(lambda: D.routing_read(rt.WH), lambda: D.routing_read(rt.QSUR), match="unknown row")
     for k, name in enumerate(rt.PARAM_NAMES):
@@ -454,13 +372,13 @@ def test_refusals_change_nothing(run_base):
         cap.end()
         assert rc == -1 and b"captured" in D.lib.elmk_last_error(D.ctx)
     assert D.device_bytes == bytes1 and D.restart_size() == size0
-    _assert_same(_snapshot(D, ROWS[:4]), state1)
+    assert_same(river_snapshot(D, ROWS[:4]), state1)
 
     D.routing_kinematic_enable(p)
     bytes2 = D.device_bytes
     assert bytes2 > bytes1 and D.restart_size() == size0  # the image is what it was
     D.routing_kinematic_init(np.full(NCELL, 2.0e5), np.full(NCELL, 1.0e5))
-    state2 = _snapshot(D)
+    state2 = river_snapshot(D, ROWS)
     refused(lambda: D.routing_kinematic_enable(p), match="already on")
     refused(lambda: D.routing_read(7), lambda: D.routing_read(-1), lambda: D.routing_read(rt.WH, cell0=NCELL, n=1))
     for call in (lambda: D.routing_kinematic_init(np.zeros(NCELL + 1)), lambda: D.routing_kinematic_enable(p[:, :-1])):
@@ -473,14 +391,14 @@ def test_refusals_change_nothing(run_base):
         assert rcs == (-1, -1) and b"captured" in D.lib.elmk_last_error(D.ctx)
     refused(D.soil_hydrology_clear, D.water_balance_clear, match="elmk_routing_clear first")
     assert D.device_bytes == bytes2 and D.restart_size() == size0
-    _assert_same(_snapshot(D), state2)
+    assert_same(river_snapshot(D, ROWS), state2)
     # the following step is the step of a context that met no refusal
     W = _run_context(run_base, True, nsub=2)
     W.routing_init(np.full(NCELL, 5.0e4))
     W.routing_kinematic_init(np.full(NCELL, 2.0e5), np.full(NCELL, 1.0e5))
     for X in (D, W):
         X.run(DT, S1, FLAGS)
-    _assert_same(_snapshot(D), _snapshot(W))
+    assert_same(river_snapshot(D, ROWS), river_snapshot(W, ROWS))
     D.routing_kinematic_clear()
     assert D.device_bytes == bytes1 and D.restart_size() == size0
     D.routing_kinematic_enable(p)
@@ -495,7 +413,7 @@ def test_a_context_without_the_scheme_is_what_it_was(run_base):
     """elmk_device_bytes, elmk_restart_size, the image and the routing's rows of a context that never turns the scheme on: the same
     before and after another context of the process has turned it on, run and cleared it, and the same as a fresh context's."""
     steps = schedule(2)
-    A = _run_context(run_base, True, kinematic=False)
+    A = _run_context(run_base, True, parts=("routing",))
     A.run(DT, steps, FLAGS)
     figures = (A.device_bytes, A.restart_size(), bits(A.restart_save()), bits(np.stack(read_rows(A, ROWS[:4]))))
     B = _run_context(run_base, True)
@@ -506,7 +424,7 @@ def test_a_context_without_the_scheme_is_what_it_was(run_base):
     assert B.device_bytes == figures[0]
     B.close()
     assert (A.device_bytes, A.restart_size(), bits(A.restart_save()), bits(np.stack(read_rows(A, ROWS[:4])))) == figures
-    F = _run_context(run_base, True, kinematic=False)
+    F = _run_context(run_base, True, parts=("routing",))
     F.run(DT, steps, FLAGS)
     assert (F.device_bytes, F.restart_size(), bits(F.restart_save()), bits(np.stack(read_rows(F, ROWS[:4])))) == figures
     A.close()
@@ -541,7 +459,7 @@ def test_budgets_equal_the_restatements(base, ncells):
     set_runoff(D, q)
     for _ in range(2):
         D.routing(1800.0)
-    v, qin, qout, _, wh, wt, _ = read_rows(D)
+    v, qin, qout, _, wh, wt, _ = read_rows(D, ROWS)
     want, want_kw = rt.budget(v, qin, qout, down), rt.kinematic_budget(wh, wt)
     assert np.isfinite(want).all() and np.isfinite(want_kw).all() and want[2] > 0.0 and (want_kw > 0.0).all()
     for _ in range(2):  # (in turn: the two share the reduction's scratch)

@@ -10,8 +10,8 @@ from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
 from tests import inundation_cases as ic
 from tests import reservoir_cases as rc
-from tests.hydrology_cases import _new, clear_snow, prepare
-from tests.run_cases import DT, _inputs
+from tests.river_cases import base, context, finite
+from tests.run_cases import DT
 from tests.support import bits
 
 pytestmark = pytest.mark.gpu
@@ -30,19 +30,10 @@ def part_bytes(part):
     return up(nrows * CLD * 8) + up(ntab * CLD * 8) + (up(CLD * 4) if part == "reservoir" else 0)
 
 
-def finite(x, fill=7.0):
-    return np.where(np.isfinite(x) & (np.abs(x) < 1e200), x, fill)
-
-
 @pytest.fixture(scope="module")
 def river():
     """The context with the base part on, and every part's inputs: finite, non-zero storages."""
-    b = _inputs(ic.NCOLS, 611)
-    clear_snow(b[0])
-    D = _new(b[0], b[1], b[2], prepare(b[0], 612), None, b[3], b[4])
-    D.water_balance_enable(1.0e-9)
-    D.set_output_grid(*ic.cell_map(NCELLS, 3), fill=np.nan)
-    D.soil_hydrology(DT)
+    D = context(base(), None, NCELLS, cell_map=ic.cell_map)
     D.upload("qflx_snwcp_liq", finite(ic.snwcp(0), 2.0e-5))  # (the budgets are to be numbers)
     D.water_balance(DT)
     ddist, area, p0, volr, wh, wt = ic.cell_values(NCELLS, 40 + NCELLS)

@@ -5,27 +5,27 @@ the stage inside elmk_run across a month boundary against the stepwise calls wit
 restarts through _read and _init and through a version-7 image; the rows on a history tape; the clear; the river supply limit's D7;
 every refusal; the budget; the example."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from elmkernels_amd import _lib as L
-from elmkernels_amd import hydrology as hy
 from elmkernels_amd import irrigation as ir
-from elmkernels_amd import regrid
 from elmkernels_amd import routing as rt
 from elmkernels_amd import state as st
 from tests import inundation_cases as ic
 from tests import irrigation_supply_cases as sc
 from tests import reservoir_cases as rc
-from tests.hydrology_cases import _new, clear_snow, prepare
+from tests import river_cases as rv
+from tests.hydrology_cases import _new, prepare
 from tests.irrigation_cases import generated, smpso_of
-from tests.run_cases import DT, NREC, SERIES, _inputs, same, schedule, upload_series
+from tests.river_cases import NCELL, NCOL, NSTEPS, TOL, differing, finite, host_inputs, read_rows, river_snapshot, set_runoff
+from tests.run_cases import DT, NREC, assert_same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, captured, run_demo
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1.0e-9
 KW_ROWS = (rt.VOLR, rt.QIN, rt.QOUT, rt.QOUT_SUM, rt.WH, rt.WT, rt.QSUR)
 FP_ROWS = (rt.WF, rt.FLOOD_DEPTH, rt.FLOOD_FRAC)
 DAM_ROWS = (rt.RES, rt.KRLS, rt.RES_TAKE)
@@ -41,56 +41,10 @@ def rows_of(flood):
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def base():
-    b = _inputs(ic.NCOLS, 611)
-    clear_snow(b[0])
-    return b, prepare(b[0], 612)
+    return rv.base()
 
 
-def _ctx(base, lib_path, ncells, seed=3, withdraw=False):
-    """The prepared context with the water balance, an output grid of ncells cells, and the hydrology stepped once so that its surface
-    rows hold values.  withdraw: the irrigation enabled with no irrigated column and a rate that applies for the whole test, stepped once
-    so that its QFLX_IRRIG row holds it."""
-    b, rows = base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.water_balance_enable(TOL)
-    ptr, col, w = ic.cell_map(ncells, seed)
-    D.set_output_grid(ptr, col, w, fill=NAN)
-    D._map = (ptr, col, w)
-    D._qirr = None
-    if withdraw:
-        D.irrigation_enable(np.full(ic.NCOLS, ir.NOT_IRRIGATED, np.int32))
-        rate = np.where(np.arange(ic.NCOLS) % 2 == 0, np.random.default_rng(9).uniform(0.0, 3.0e-5, ic.NCOLS), 0.0)
-        D.irrigation_init(rate, np.full(ic.NCOLS, 1000.0))
-        D.irrigation(DT, 0)
-        D._qirr = D.irrigation_read(ir.QFLX_IRRIG)
-        assert (D._qirr > 0.0).any()
-    D.soil_hydrology(DT)
-    D._surf = (D.soil_hydrology_read(hy.QFLX_SURF), D.soil_hydrology_read(hy.QFLX_H2OSFC_SURF))
-    return D
-
-
-def set_runoff(D, q):
-    D.upload("qflx_snwcp_liq", q)
-    D.water_balance(DT)
-    return D.water_balance_read(hy.WB_QRUNOFF)
-
-
-def read_rows(D, rows):
-    return [D.routing_read(w) for w in rows]
-
-
-def host_inputs(D, qrunoff, area):
-    """K1's QIN (the withdrawal included where it is on) and QSUR, and R1's two aggregates for D2."""
-    ptr, col, w = D._map
-    qin = rt.qin_from_rows(ptr, col, w, qrunoff, area, qflx_irrig=D._qirr)
-    wd = None
-    if D._qirr is not None:
-        wd = (regrid.apply_aggregate(ptr, col, w, qrunoff, 0.0), regrid.apply_aggregate(ptr, col, w, D._qirr, 0.0))
-    return qin, rt.qsur_from_rows(ptr, col, w, D._surf[0], D._surf[1], area), wd
-
-
-def differing(g, want):
-    return np.nonzero(g.view(np.uint64) != want.view(np.uint64))[0][:5]
+_ctx = functools.partial(rv.context, cell_map=ic.cell_map)
 
 
 # ---- 1. the stage against the restatement -------------------------------------------------------------------------------------------
@@ -216,7 +170,6 @@ def test_the_edge_values_do_what_the_statement_says(base):
 
 
 # ---- 2. the run ----------------------------------------------------------------------------------------------------------------------
-NCOL, NCELL, NSTEPS = 193, 65, 6
 FLAGS = st.RUN_HYDROLOGY | st.RUN_WATER_BALANCE | st.RUN_ROUTING
 
 
@@ -232,87 +185,10 @@ def month_schedule(nsteps):
 
 @pytest.fixture(scope="module")
 def run_base():
-    b = _inputs(NCOL, 531)
-    clear_snow(b[0])
-    rows = prepare(b[0], 532)
-    rng = np.random.default_rng(77)
-    cnt = rng.integers(0, 6, NCELL)
-    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    col = rng.integers(0, NCOL, int(ptr[-1])).astype(np.int32)
-    ddist, area, p0, volr0, wh0, wt0 = ic.cell_values(NCELL, 78)
-    volr0, wh0, wt0 = (_finite(x) for x in (volr0, wh0, wt0))
-    flood = ic.flood_values(NCELL, 80, area, p0, volr0, wh0, wt0, 3, DT)
-    cap, target, beta, mstart, res, krls = rc.dam_values(NCELL, 81)
-    dams = rc.dam_cells(NCELL)
-    target[1, dams] = 2.0 * target[0, dams] + 25.0  # February's targets are not January's
-    mstart[dams[::2]] = 1  # every other dam's year begins in February
-    res = _finite(res)
-    return b, rows, (ptr, col, rng.uniform(0.1, 1.0, col.size)), ic.networks(NCELL, 79)["forest"], ddist, area, flood, (cap, target, beta, mstart, res, krls)
+    return rv.run_case(dam=True)
 
 
-def _finite(x):
-    return np.where(np.isfinite(x) & (np.abs(x) < 1e200), x, 7.0)
-
-
-def _run_context(run_base, graph, lib_path=None, dam=True, flood=True, nsub=3, init=True):
-    b, rows, m, down, ddist, area, (rdepth, eprof, p, volr, wh, wt, wf), (cap, target, beta, mstart, res, krls) = run_base
-    D = _new(b[0], b[1], b[2], rows, lib_path, b[3], b[4])
-    D.set_graph(graph)
-    D.run_reserve(NREC, 2 * NSTEPS)
-    upload_series(D, b[5])
-    D.water_balance_enable(TOL)
-    D.set_output_grid(*m, fill=NAN)
-    D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
-    D.routing_kinematic_enable(p)
-    if flood:
-        D.routing_inundation_enable(rdepth, eprof)
-    if dam:
-        D.routing_reservoir_enable(cap, target, beta, mstart)
-    if init:
-        D.routing_init(volr)
-        D.routing_kinematic_init(wh, wt)
-        if flood:
-            D.routing_inundation_init(_finite(wf))
-        if dam:
-            D.routing_reservoir_init(res, krls)
-    return D
-
-
-def _stepwise(D, rec, steps, dam=True):
-    """The stand-alone calls in elmk_run's order, with elmk_routing after the water balance and the reservoirs' time before it."""
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        D.water_balance_begin()
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        st.kokkos_evaluate_conservation(D, DT)
-        D.error_summary()
-        D.water_balance(DT)
-        if dam:
-            D.routing_reservoir_time(rt.month_of_doy(int(p["doy"])), rt.month_begins(int(p["doy"]), float(p["decday"])))
-        D.routing(DT)
-
-
-def _snapshot(D, rows):
-    out = {k: D[k] for k in D.fields if k not in SERIES}
-    out["hyd"], out["wb"] = D.soil_hydrology_rows(), D.water_balance_rows()
-    out["route"] = np.stack(read_rows(D, rows))
-    out["count"] = np.array(D.routing_count())
-    return out
-
-
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert same(v, b[k]), k
+_run_context = functools.partial(rv.run_context, parts=("routing", "kinematic", "inundation", "reservoir"))
 
 
 @pytest.mark.parametrize("graph", [True, False], ids=["graph", "nograph"])
@@ -322,18 +198,18 @@ def test_run_equals_stepwise_across_a_month_boundary(run_base, graph):
     changes every dam's target.  Then a second run (on the captured step when the graph is on); the extension switched off between
     two runs, which drops the captured step and runs the form without it, and on again."""
     steps = month_schedule(2 * NSTEPS)
-    cap, target, beta, mstart, res0, krls0 = run_base[7]
+    cap, target, beta, mstart, res0, krls0 = run_base["dam"]
     rows = rows_of(True)
     A, B = _run_context(run_base, False), _run_context(run_base, graph)
-    _stepwise(A, run_base[0][5], steps[:3])
+    stepwise(A, run_base["rec"], steps[:3], FLAGS, reservoir_time=True)
     B.run(DT, steps[:3], FLAGS)
-    a = _snapshot(A, rows)
-    _assert_same(_snapshot(B, rows), a)
+    a = river_snapshot(A, rows)
+    assert_same(river_snapshot(B, rows), a)
     assert bits(a["route"][11]) == bits(krls0)  # January: no D1
-    _stepwise(A, run_base[0][5], steps[3:NSTEPS])
+    stepwise(A, run_base["rec"], steps[3:NSTEPS], FLAGS, reservoir_time=True)
     B.run(DT, steps[3:NSTEPS], FLAGS)
-    a = _snapshot(A, rows)
-    _assert_same(_snapshot(B, rows), a)
+    a = river_snapshot(A, rows)
+    assert_same(river_snapshot(B, rows), a)
     dams = rc.dam_cells(NCELL)
     moved = a["route"][11] != krls0
     assert moved[dams[::2]].all() and not moved[dams[1::2]].any() and B.routing_count() == NSTEPS
@@ -345,21 +221,21 @@ def test_run_equals_stepwise_across_a_month_boundary(run_base, graph):
         J.run(DT, steps_j, FLAGS)
     assert bits(J.routing_read(rt.RES)) != bits(a["route"][10]) and bits(J.routing_read(rt.KRLS)) == bits(krls0)
     J.close()
-    _stepwise(A, run_base[0][5], steps[NSTEPS:])
+    stepwise(A, run_base["rec"], steps[NSTEPS:], FLAGS, reservoir_time=True)
     B.run(DT, steps[NSTEPS:], FLAGS)
-    _assert_same(_snapshot(B, rows), _snapshot(A, rows))
+    assert_same(river_snapshot(B, rows), river_snapshot(A, rows))
     res, krls = A.routing_read(rt.RES), A.routing_read(rt.KRLS)
     for X in (A, B):
         X.routing_reservoir_clear()
-    _stepwise(A, run_base[0][5], steps[:2], dam=False)
+    stepwise(A, run_base["rec"], steps[:2], FLAGS)
     B.run(DT, steps[:2], FLAGS)
-    _assert_same(_snapshot(B, rows[:10]), _snapshot(A, rows[:10]))
+    assert_same(river_snapshot(B, rows[:10]), river_snapshot(A, rows[:10]))
     for X in (A, B):
         X.routing_reservoir_enable(cap, target, beta, mstart)
         X.routing_reservoir_init(res, krls)
-    _stepwise(A, run_base[0][5], steps[2:5])
+    stepwise(A, run_base["rec"], steps[2:5], FLAGS, reservoir_time=True)
     B.run(DT, steps[2:5], FLAGS)
-    _assert_same(_snapshot(B, rows), _snapshot(A, rows))
+    assert_same(river_snapshot(B, rows), river_snapshot(A, rows))
     for X in (A, B):
         X.close()
 
@@ -374,7 +250,7 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     rows = rows_of(True)
     A = _run_context(run_base, True, lib_path)
     A.run(DT, steps, FLAGS)
-    want = _snapshot(A, rows)
+    want = river_snapshot(A, rows)
     size_a = A.restart_size()
     A.close()
     B = _run_context(run_base, True, lib_path)
@@ -390,12 +266,12 @@ def test_restart_3_plus_3_equals_6(run_base, lib_path):
     Cx.routing_inundation_init(wf)
     Cx.routing_reservoir_init(res, krls)
     Cx.run(DT, steps[3:], FLAGS)
-    _assert_same(_snapshot(Cx, rows), want)
+    assert_same(river_snapshot(Cx, rows), want)
     # reservoir_init leaves the other entries' rows alone, and without rows gives RES 0, KRLS 1, RES_TAKE 0
     Cx.routing_reservoir_init()
     assert not Cx.routing_read(rt.RES).any() and not Cx.routing_read(rt.RES_TAKE).any() and bits(Cx.routing_read(rt.KRLS)) == bits(np.ones(NCELL))
     assert bits(Cx.routing_read(rt.VOLR)) == bits(want["route"][0]) and bits(Cx.routing_read(rt.WF)) == bits(want["route"][7])
-    N = _run_context(run_base, True, lib_path, dam=False)
+    N = _run_context(run_base, True, lib_path, parts=("routing", "kinematic", "inundation"))
     assert N.restart_size() == size_a
     N.close()
     Cx.close()
@@ -411,7 +287,7 @@ def test_restart_3_plus_3_through_a_version_7_image(run_base):
     rows = rows_of(True)
     A = _run_context(run_base, True)
     A.run(DT, steps, FLAGS)
-    want = _snapshot(A, rows)
+    want = river_snapshot(A, rows)
     size_off = A.restart_size()
     A.close()
     B = _run_context(run_base, True)
@@ -439,7 +315,7 @@ def test_restart_3_plus_3_through_a_version_7_image(run_base):
     Cx.restart_load(img)
     assert Cx.routing_count() == 3 and not Cx.routing_read(rt.RES_TAKE).any()
     Cx.run(DT, steps[3:], FLAGS)
-    _assert_same(_snapshot(Cx, rows), want)
+    assert_same(river_snapshot(Cx, rows), want)
     Cx.routing_reservoir_clear()
     with pytest.raises(L.ElmkError, match="the reservoirs"):
         Cx.restart_load(img)
@@ -451,7 +327,7 @@ def test_restart_3_plus_3_through_a_version_7_image(run_base):
 def test_the_rows_on_a_history_tape(run_base):
     """elmk_cell_history_add_row over RES, KRLS and RES_TAKE while the extension is on: the average of three calls is the mean of the
     rows read after each; while an entry exists elmk_routing_reservoir_clear is refused and changes nothing."""
-    D = _run_context(run_base, False, flood=False)
+    D = _run_context(run_base, False, parts=("routing", "kinematic", "reservoir"))
     ids = [D.cell_history_add_row(0, "routing", w, st.HIST_AVG) for w in DAM_ROWS]
     got = []
     for c in range(3):
@@ -620,7 +496,8 @@ def test_the_supply_limit_counts_the_reservoir(lib_path):
 # ---- 6. refusals ---------------------------------------------------------------------------------------------------------------------
 def test_refusals_change_nothing(run_base):
     """Every refusal of the five entries and of the interlocks, with nothing changed by any."""
-    b, rows_, m, down, ddist, area, (rdepth, eprof, p, volr, wh, wt, wf), (cap, target, beta, mstart, res, krls) = run_base
+    b, rows_, m, down, ddist, area, rdepth, eprof, p, volr, wh, wt, wf = (run_base[k] for k in ("b", "rows", "map", "down", "ddist", "area", "rdepth", "eprof", "p", "volr", "wh", "wt", "wf"))
+    cap, target, beta, mstart, res, krls = run_base["dam"]
     rows = rows_of(False)
 
     def refused(*calls, match=None):
@@ -644,7 +521,7 @@ def test_refusals_change_nothing(run_base):
     D.routing_kinematic_enable(p)
     D.routing_kinematic_init(wh, wt)
     bytes1 = D.device_bytes
-    state1 = _snapshot(D, KW_ROWS)
+    state1 = river_snapshot(D, KW_ROWS)
     refused(D.routing_reservoir_init, D.routing_reservoir_budget, lambda: D.routing_reservoir_time(0), match="the extension is not on")
     refused(*(lambda w=w: D.routing_read(w) for w in DAM_ROWS), lambda: D.routing_read(13), match="unknown row")
     for v in (-1.0, NAN, INF, -INF):
@@ -681,14 +558,14 @@ def test_refusals_change_nothing(run_base):
             call()
     refused(lambda: D.cell_history_add_row(0, st.CELL_ROWS_ROUTING, rt.RES, st.HIST_AVG), match="row out of range")
     assert D.device_bytes == bytes1 and D.restart_size() == size0
-    _assert_same(_snapshot(D, KW_ROWS), state1)
+    assert_same(river_snapshot(D, KW_ROWS), state1)
 
     enable()
     bytes2 = D.device_bytes
     assert bytes2 > bytes1 and D.restart_size() == size0  # the image is what it was
     D.routing_reservoir_init(res, krls)
     D.routing_reservoir_time(7, True)
-    state2 = _snapshot(D, rows)
+    state2 = river_snapshot(D, rows)
     refused(enable, match="already on")
     refused(D.routing_kinematic_clear, match="elmk_routing_reservoir_clear first")
     refused(lambda: D.routing_reservoir_time(-1), lambda: D.routing_reservoir_time(12), match="month outside 0 .. 11")
@@ -703,9 +580,9 @@ def test_refusals_change_nothing(run_base):
         cap_.end()
         assert rcs == (-1, -1, -1, -1) and b"captured" in D.lib.elmk_last_error(D.ctx)
     assert D.device_bytes == bytes2 and D.restart_size() == size0
-    _assert_same(_snapshot(D, rows), state2)
+    assert_same(river_snapshot(D, rows), state2)
     # the following call is the call of a context that met no refusal, in the month and with the `begins` that were set
-    W = _run_context(run_base, True, flood=False, nsub=2)
+    W = _run_context(run_base, True, parts=("routing", "kinematic", "reservoir"), nsub=2)
     W.routing_reservoir_time(7, True)
     for X in (D, W):
         set_runoff(X, ic.snwcp(0)[:NCOL])
@@ -727,9 +604,9 @@ def test_refusals_change_nothing(run_base):
 def test_budget_equals_the_restatement(base, ncells):
     D = _ctx(base, None, ncells, withdraw=True)
     ddist, area, p, volr0, wh0, wt0 = ic.cell_values(ncells, 40 + ncells)
-    volr0, wh0, wt0 = (_finite(x) for x in (volr0, wh0, wt0))
+    volr0, wh0, wt0 = (finite(x) for x in (volr0, wh0, wt0))
     cap, target, beta, mstart, res0, krls0 = rc.dam_values(ncells, 90 + ncells)
-    res0 = _finite(res0)
+    res0 = finite(res0)
     down = ic.networks(ncells, 5)["forest" if ncells >= 3 else "outlets"]
     D.routing_enable(down, ddist, area, rt.EFFVEL, 2)
     D.routing_set_withdrawal(True)

@@ -111,7 +111,7 @@ def test_history_option_equals_stepwise_accumulate(base):
     A, B = _pair(base)
     ids = [[D.history_add(t, f, op) for t, f, op in ENTRIES] for D in (A, B)]
     steps = schedule()
-    stepwise(A, rec, steps, history=True)
+    stepwise(A, rec, steps, st.RUN_HISTORY)
     B.run_reserve(NREC, NSTEPS)
     upload_series(B, rec)
     B.run(DT, steps, st.RUN_HISTORY)
@@ -130,7 +130,7 @@ def test_qbot_is_rh_option_equals_stepwise(base):
     rec["atm_qbot"] = np.clip(rec["atm_qbot"] * 5000.0, 5.0, 100.0)  # relative humidity, percent
     A, B = _pair(base)
     steps = schedule()
-    want = stepwise(A, rec, steps, qbot_is_rh=True)
+    want = stepwise(A, rec, steps, st.RUN_QBOT_IS_RH)
     B.run_reserve(NREC, NSTEPS)
     upload_series(B, rec)
     B.run(DT, steps, st.RUN_QBOT_IS_RH)

@@ -14,7 +14,7 @@ from elmkernels_amd import state as st
 from elmkernels_amd import synth
 from tests.hydrology_cases import _new, _new_frost, add_frost, clear_snow, generated_frost, prepare
 from tests.parity_cases import WETLAND
-from tests.run_cases import DT, NREC, SERIES, _inputs, device, same, schedule, stepwise, upload_series
+from tests.run_cases import DT, NREC, SERIES, _inputs, assert_same, device, same, schedule, stepwise, upload_series
 from tests.support import bits, build_demo, run_demo
 
 pytestmark = pytest.mark.gpu
@@ -159,38 +159,6 @@ def _context(base, graph, lib_path=None, features=True, wb=True, tol=TOL, wb_fir
     return D
 
 
-def _stepwise(D, rec, steps, wb=True, history=False, per_step=None):
-    """run_cases.stepwise with W0 after init_timestep, the hydrology after the physics, W1 - W8 after the flag summary, then the
-    active layer update and the history sample.  per_step: a list that receives a function's value after every step."""
-    cons, fo, fb, bal = [], [], [], []
-    for p in steps:
-        D.solar_geometry(DT, float(p["decday"]), int(p["doy"]))
-        f = int(p["forc_slot"])
-        for k in st.SERIES_FORCING:
-            D.upload(k, np.stack([rec[k][f], rec[k][f + 1]], axis=1))
-        for k in st.SERIES_PHENOLOGY:
-            D.upload(k, np.stack([rec[k][p["month1"]], rec[k][p["month2"]]], axis=1))
-        st.compute_phenology(D, float(p["month_wt1"]), float(p["month_wt2"]))
-        st.get_forcing(D, p["forc_wt1"], p["forc_wt2"], False)
-        st.kokkos_init_timestep(D)
-        if wb:
-            D.water_balance_begin()
-        st.advance_physics(D, DT)
-        D.soil_hydrology(DT)
-        cons.append(st.kokkos_evaluate_conservation(D, DT))
-        flags, first = D.error_summary()
-        fo.append(flags)
-        fb.append(first)
-        if wb:
-            bal.append(D.water_balance(DT))
-        D.active_layer_update(0)
-        if history:
-            D.history_accumulate()
-        if per_step is not None:
-            per_step[0].append(per_step[1](D))
-    return (np.array(cons), np.array(fo, np.uint32), np.array(fb, np.int64)), bal
-
-
 def _snapshot(D, wb=True):
     out = {k: D[k] for k in D.fields if k not in SERIES}
     out["rows"], out["frost"] = D.soil_hydrology_rows(), D.soil_hydrology_frost_rows()
@@ -200,17 +168,13 @@ def _snapshot(D, wb=True):
     return out
 
 
-def _assert_same(a, b, skip=()):
-    assert a.keys() == b.keys()
-    for k, v in a.items():
-        assert k in skip or same(v, b[k]), k
-
-
 @pytest.fixture(scope="module")
 def stepwise_result(base):
     A = _context(base, False)
-    diag, bal = _stepwise(A, base[0][5], schedule(NSTEPS))
-    out = (diag, bal, _snapshot(A))
+    # (FLAGS carries RUN_ALT: the shared restatement hands active_layer_update the step's rollover bits, which are 0 on every
+    # step of run_cases.schedule - checked on the host over 48 steps)
+    r = stepwise(A, base[0][5], schedule(NSTEPS), FLAGS)
+    out = (tuple(r), r.bal, _snapshot(A))
     A.close()
     return out
 
@@ -232,12 +196,12 @@ def test_run_equals_stepwise(base, stepwise_result, graph):
     print("nbad per step:", nbad.tolist(), "first:", first.tolist())
     assert nbad.max() > 0
     got = _snapshot(B)
-    _assert_same(got, want)
+    assert_same(got, want)
     assert np.isfinite(got["wb"]).all() and (got["wb"][hy.WB_ENDWB] > 4000.0).all()
     C = _context(base, graph, wb=False)
     C.run(DT, schedule(NSTEPS), FLAGS & ~st.RUN_WATER_BALANCE)
     assert C.run_water_balance()[0].shape[0] == 0  # (no ring rows: the run did not carry the flag)
-    _assert_same(_snapshot(C, wb=False), {k: v for k, v in got.items() if k != "wb"})
+    assert_same(_snapshot(C, wb=False), {k: v for k, v in got.items() if k != "wb"})
     B.close()
     C.close()
 
@@ -305,7 +269,7 @@ def test_tapes_over_feature_rows_equal_the_host_fold(base, graph):
         D.set_output_grid(*_out_map(), FILL)
     ids_a, ids_b = _add_row_entries(A), _add_row_entries(B)
     samples = []
-    _stepwise(A, base[0][5], schedule(NSTEPS), history=True, per_step=(samples, _read_sources))
+    stepwise(A, base[0][5], schedule(NSTEPS), FLAGS | st.RUN_HISTORY, per_step=(samples, _read_sources))
     assert len(samples) == NSTEPS and any(bits(samples[0][i]) != bits(samples[-1][i]) for i in range(4))
     B.run(DT, schedule(NSTEPS), FLAGS | st.RUN_HISTORY)
     _assert_tapes(A, ids_a, samples, "stepwise")
@@ -341,7 +305,7 @@ def test_restart_3_plus_3_equals_6(base):
     before = _snapshot(nohist)
     with pytest.raises(L.ElmkError, match="feature rows.*elmk_column_history_add_row"):
         nohist.restart_load(img)
-    _assert_same(_snapshot(nohist), before)
+    assert_same(_snapshot(nohist), before)
     nohist.close()
     B.close()
     halves = [R.slice(img, 0, 500), R.slice(img, 500, NCOL - 500)]
@@ -352,7 +316,7 @@ def test_restart_3_plus_3_equals_6(base):
         ids_c = _add_row_entries(C, gridded=False)
         C.restart_load(image)
         C.run(DT, S6[3:], flags)
-        _assert_same(_snapshot(C), want)
+        assert_same(_snapshot(C), want)
         for k, e in ids_c.items():
             assert bits(C.history_read(e)) == bits(want_tapes[k]), k
         C.close()
@@ -392,7 +356,7 @@ def test_refusals_change_nothing(base):
             lambda: D.water_balance_begin(), lambda: D.water_balance(DT), lambda: D.water_balance_read(hy.WB_ENDWB),
             lambda: D.run(DT, S1, FLAGS), lambda: D.history_add_row(0, "water_balance", hy.WB_QRUNOFF, "avg"))
     assert D.device_bytes == bytes1 and D.restart_size() == size1
-    _assert_same(_snapshot(D, wb=False), before)
+    assert_same(_snapshot(D, wb=False), before)
     _enable(D, TOL)
     bytes2 = D.device_bytes
     assert D.restart_size() == size1  # the balance rows are not in restart images
@@ -409,7 +373,7 @@ def test_refusals_change_nothing(base):
             lambda: D.history_add_row(0, "alt", -1, "avg"), lambda: D.history_add_row(4, "alt", 0, "avg"),
             lambda: D.history_add_row(0, "alt", 0, 9), lambda: D.gridded_history_add_row(0, "alt", 0, "avg"))  # no output grid
     assert D.device_bytes == bytes2 and D.restart_size() == size1
-    _assert_same(_snapshot(D), state0)
+    assert_same(_snapshot(D), state0)
 
     # a row entry of each family bars the clears of that family
     for fam, which, clears in (("water_balance", hy.WB_QRUNOFF, (D.water_balance_clear, D.soil_hydrology_clear)),
@@ -421,7 +385,7 @@ def test_refusals_change_nothing(base):
         size_e, bytes_e = D.restart_size(), D.device_bytes
         refused(*clears, match="elmk_history_clear first")
         assert D.device_bytes == bytes_e and D.restart_size() == size_e
-        _assert_same(_snapshot(D), state0)
+        assert_same(_snapshot(D), state0)
         D.history_clear()
         assert D.restart_size() == size1
     # a land unit that is not soil or crop: nothing is enqueued; what zero columns reduce to
@@ -429,14 +393,14 @@ def test_refusals_change_nothing(base):
     D.water_balance_begin()
     mms, nbad, first = D.water_balance(DT)
     assert mms.tolist() == [[np.inf, -np.inf, 0.0]] * 3 and (nbad, first) == (0, -1) and not np.signbit(mms[:, 2]).any()
-    _assert_same(_snapshot(D), state0, skip=())
+    assert_same(_snapshot(D), state0, skip=())
     D.set_land(**synth.TEST_LAND)
     # the following step
     for X in (D, W):
         X.run(DT, S1, FLAGS)
     for g, w in zip(D.run_water_balance(), W.run_water_balance()):
         assert same(g, w)
-    _assert_same(_snapshot(D), _snapshot(W))
+    assert_same(_snapshot(D), _snapshot(W))
     # on the other land unit the flagged run enqueues no stage and reports the identity
     D.set_land(**WETLAND)
     wb0 = D.water_balance_rows()
@@ -497,7 +461,7 @@ def test_a_context_without_the_feature_is_what_it_was(base):
     for D in (C, E):
         D.run(DT, S4, st.RUN_HYDROLOGY | st.RUN_ALT)
     assert bits(C.water_balance_rows()) == bits(wb_c)
-    _assert_same(_snapshot(C, wb=False), _snapshot(E, wb=False))
+    assert_same(_snapshot(C, wb=False), _snapshot(E, wb=False))
     for g, w in zip(C.run_diagnostics(), E.run_diagnostics()):
         assert same(g, w)
     assert bits(C.restart_save()) == bits(E.restart_save())

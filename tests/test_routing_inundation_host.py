@@ -457,5 +457,5 @@ def test_header_constants_and_bindings():
         assert f"elmk_routing_inundation_{name}(" in hpp, name
     # the kernel: a template parameter on the existing sub-step, no hint and no fence
     k = open(os.path.join(ROOT, "elmkernels_amd", "csrc", "k_routing.hip")).read()
-    sub_step = "template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM = false>\n__global__ __launch_bounds__(256) void k_kinematic_step("
+    sub_step = "template <int NPAD, bool FIRST, bool LAST, bool FLOOD, bool DAM = false, bool HEAT = false>\n__global__ __launch_bounds__(256) void k_kinematic_step("
     assert sub_step in k and "nontemporal_" not in k and "__threadfence" not in k
