@@ -3,66 +3,22 @@
 // for its acclimation terms.  The result is set against the loop this replaces - one run per step, and between two steps the host
 // downloads t_ref2m, applies the update and uploads t10 - and against a run that leaves t10 at its start-up value.  The demo prints
 // whether the first two are bit-identical (restart images, the accumulator and its step count) and how far t10 has moved.  Input:
-// the state.bin of examples/run_demo.cc (written by tests/test_gpu_run.py::test_run_demo and tests/test_gpu_accum.py::test_accum_demo).
+// the state.bin of examples/run_demo.cc (written by tests/test_gpu_run.py::test_run_demo and tests/test_gpu_accum.py::test_accum_demo);
+// examples/demo_io.h reads it and starts a context up.
 //
 //   g++ -std=c++17 -Iinclude examples/accum_demo.cc -Lelmkernels_amd -lelmk -Wl,-rpath,$PWD/elmkernels_amd -o accum_demo
 //   ./accum_demo state.bin
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <string>
 #include <vector>
 
-#include "elmk_interface.hpp"
+#include "demo_io.h"
 
-static std::vector<char> read_all(const char* path)
-{
-  FILE* f = std::fopen(path, "rb");
-  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<char> b((size_t)n);
-  if (std::fread(b.data(), 1, (size_t)n, f) != (size_t)n) throw std::runtime_error("short read");
-  std::fclose(f);
-  return b;
-}
-
-static const char* const FORCING[] = {"atm_tbot", "atm_pbot", "atm_qbot", "atm_flds", "atm_fsds", "atm_prec", "atm_wind"};
-static const char* const PHENOLOGY[] = {"mlai", "msai", "mhtop", "mhbot"};
+using namespace demo;
 constexpr int NREC = 25, NSTEPS = 48;
 constexpr int64_t PERIOD = 8;  // steps of the running mean (ELM: ten days)
-
-struct Inputs {
-  int64_t ncols;
-  std::map<std::string, const char*> fields, params;
-  std::map<std::string, int64_t> sizes;
-};
-
-// start-up: parameters and tables, the fields of the input file, geography, the run series
-static void start(elmk::ELMInterface& elm, Inputs& in)
-{
-  auto D = [&](const std::string& k) { return reinterpret_cast<const double*>(in.params.at(k)); };
-  auto I = [&](const char* k) { return reinterpret_cast<const int32_t*>(in.params.at(k)); };
-  elmk_snicar_tables t;
-  std::memset(&t, 0, sizeof t);
-  {
-    const double** slot = reinterpret_cast<const double**>(&t);  // the struct is 31 const double* members, in this order
-    for (int i = 0; i < (int)(sizeof t / sizeof(double*)); i++) slot[i] = D("snicar/" + std::to_string(i));
-  }
-  const int32_t* land = I("land");
-  const double* sc = D("scalars");
-  elm.setup(land[0], land[1], land[2], land[3], land[4], sc[0], (int)sc[1], sc[2], sc[3], D("pft_psn"), D("pft_alb"), D("z0mr"),
-            D("displar"), D("albsat"), D("albdry"), &t, D("age_tau"), D("age_kappa"), D("age_drdt0"));
-  for (const auto& kv : in.fields) elm.upload(kv.first.c_str(), kv.second);
-  elm.set_column_geography(D("lat"), D("lon"));
-  elm.reserve_run(NREC, NSTEPS);
-  for (const char* f : FORCING) elm.series_upload(f, 0, NREC, D(std::string("series/") + f));
-  for (const char* f : PHENOLOGY) elm.series_upload(f, 0, 12, D(std::string("series/") + f));
-}
 
 int main(int argc, char** argv)
 {
@@ -71,35 +27,15 @@ int main(int argc, char** argv)
     return 2;
   }
   try {
-    const std::vector<char> blob = read_all(argv[1]);
-    const char* p = blob.data();
-    const char* end = p + blob.size();
-    int64_t ncols;
-    std::memcpy(&ncols, p, 8);
-    p += 8;
-    Inputs in;
-    in.ncols = ncols;
-    while (p < end) {
-      char name[33] = {0};
-      std::memcpy(name, p, 32);
-      int32_t kind;
-      int64_t nbytes;
-      std::memcpy(&kind, p + 32, 4);
-      std::memcpy(&nbytes, p + 36, 8);
-      (kind == 0 ? in.fields : in.params)[name] = p + 44;
-      in.sizes[name] = nbytes;
-      p += 44 + nbytes;
-    }
-
-    if (in.sizes.at("steps") != (int64_t)(NSTEPS * sizeof(elmk_run_step))) throw std::runtime_error("steps: expected 48 rows");
-    std::vector<elmk_run_step> steps(NSTEPS);
-    std::memcpy(steps.data(), in.params.at("steps"), sizeof(elmk_run_step) * NSTEPS);
-    const double dt = reinterpret_cast<const double*>(in.params.at("scalars"))[4];
+    const Inputs in(argv[1]);
+    const int64_t ncols = in.ncols;
+    const std::vector<elmk_run_step> steps = run_steps(in, NSTEPS);
+    const double dt = in.dt();
     const size_t n = (size_t)ncols;
 
     // on the device: the value starts from the t10 that was uploaded, as a window that is already full
     elmk::ELMInterface device(ncols, 0);
-    start(device, in);
+    start(device, in, NREC, NSTEPS);
     const int entry = device.accum_add("t_ref2m", ELMK_ACCUM_RUNMEAN, PERIOD, "t10");
     device.accum_init(entry, nullptr, PERIOD);
     device.run(dt, steps, false, false, true);
@@ -108,7 +44,7 @@ int main(int argc, char** argv)
 
     // the loop it replaces: a round trip through the host after every step
     elmk::ELMInterface host(ncols, 0);
-    start(host, in);
+    start(host, in, NREC, NSTEPS);
     std::vector<double> t10(n), tref(n);
     host.download("t10", t10.data());
     for (int s = 0; s < NSTEPS; s++) {
@@ -125,7 +61,7 @@ int main(int argc, char** argv)
 
     // and t10 left alone
     elmk::ELMInterface frozen(ncols, 0);
-    start(frozen, in);
+    start(frozen, in, NREC, NSTEPS);
     frozen.run(dt, steps);
     std::vector<double> t10_frozen(n);
     frozen.download("t10", t10_frozen.data());

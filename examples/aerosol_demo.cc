@@ -5,48 +5,25 @@
 // the bracket (December, January) to (January, February) half way.  The result is set against the loop this replaces, one
 // update_aerosol() and one one-step run per step, and against a run that leaves aer_* at their start-up values.  The demo prints
 // mss_dst1 of a snow-covered column after each and exits non-zero unless the first two are bit-identical.  Input: the state.bin of
-// examples/run_demo.cc (written by tests/test_gpu_run.py::test_run_demo and tests/test_gpu_aerosol.py::test_aerosol_demo).
+// examples/run_demo.cc (written by tests/test_gpu_run.py::test_run_demo and tests/test_gpu_aerosol.py::test_aerosol_demo);
+// examples/demo_io.h reads it and starts a context up.
 //
 //   g++ -std=c++17 -Iinclude examples/aerosol_demo.cc -Lelmkernels_amd -lelmk -Wl,-rpath,$PWD/elmkernels_amd -o aerosol_demo
 //   ./aerosol_demo state.bin
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <string>
 #include <vector>
 
-#include "elmk_interface.hpp"
+#include "demo_io.h"
 
-static std::vector<char> read_all(const char* path)
-{
-  FILE* f = std::fopen(path, "rb");
-  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<char> b((size_t)n);
-  if (std::fread(b.data(), 1, (size_t)n, f) != (size_t)n) throw std::runtime_error("short read");
-  std::fclose(f);
-  return b;
-}
-
-static const char* const FORCING[] = {"atm_tbot", "atm_pbot", "atm_qbot", "atm_flds", "atm_fsds", "atm_prec", "atm_wind"};
-static const char* const PHENOLOGY[] = {"mlai", "msai", "mhtop", "mhbot"};
 static const char* const STREAMS[] = {"aer_bcphi",  "aer_bcpho",  "aer_bcdep",  "aer_dst1_1", "aer_dst1_2", "aer_dst2_1",
                                       "aer_dst2_2", "aer_dst3_1", "aer_dst3_2", "aer_dst4_1", "aer_dst4_2"};
 constexpr int NREC = 25, NSTEPS = 48, NSTREAM = 11, NMONTH = 12;
 constexpr int NLON = 144, NLAT = 96;  // the aerosol file's grid: cell = j * NLON + i, j from the south, i eastwards from 0 degrees
 constexpr int64_t NCELLS = (int64_t)NLON * NLAT;
 constexpr double PI = 3.14159265358979323846;
-
-struct Inputs {
-  int64_t ncols;
-  std::map<std::string, const char*> fields, params;
-  std::map<std::string, int64_t> sizes;
-};
 
 // the nearest-cell pick of the reference's aerosol reader (aerosol_data_old_impl.hh:32-55): one term of weight 1 per column
 static void nearest_map(const double* lat_r, const double* lon_r, int64_t n, std::vector<int32_t>& idx, std::vector<double>& w)
@@ -83,29 +60,13 @@ static std::vector<double> climatology()
   return x;
 }
 
-// start-up: parameters and tables, the fields of the input file, geography, the run series, the aerosol series and map
-static void start(elmk::ELMInterface& elm, Inputs& in, const std::vector<double>& clim)
+// start-up as every run demo's, then the aerosol series and map
+static void start(elmk::ELMInterface& elm, const demo::Inputs& in, const std::vector<double>& clim)
 {
-  auto D = [&](const std::string& k) { return reinterpret_cast<const double*>(in.params.at(k)); };
-  auto I = [&](const char* k) { return reinterpret_cast<const int32_t*>(in.params.at(k)); };
-  elmk_snicar_tables t;
-  std::memset(&t, 0, sizeof t);
-  {
-    const double** slot = reinterpret_cast<const double**>(&t);  // the struct is 31 const double* members, in this order
-    for (int i = 0; i < (int)(sizeof t / sizeof(double*)); i++) slot[i] = D("snicar/" + std::to_string(i));
-  }
-  const int32_t* land = I("land");
-  const double* sc = D("scalars");
-  elm.setup(land[0], land[1], land[2], land[3], land[4], sc[0], (int)sc[1], sc[2], sc[3], D("pft_psn"), D("pft_alb"), D("z0mr"),
-            D("displar"), D("albsat"), D("albdry"), &t, D("age_tau"), D("age_kappa"), D("age_drdt0"));
-  for (const auto& kv : in.fields) elm.upload(kv.first.c_str(), kv.second);
-  elm.set_column_geography(D("lat"), D("lon"));
-  elm.reserve_run(NREC, NSTEPS);
-  for (const char* f : FORCING) elm.series_upload(f, 0, NREC, D(std::string("series/") + f));
-  for (const char* f : PHENOLOGY) elm.series_upload(f, 0, 12, D(std::string("series/") + f));
+  demo::start(elm, in, NREC, NSTEPS);
   std::vector<int32_t> idx;
   std::vector<double> w;
-  nearest_map(D("lat"), D("lon"), in.ncols, idx, w);
+  nearest_map(in.D("lat"), in.D("lon"), in.ncols, idx, w);
   elm.aerosol_reserve(NCELLS, 1, idx.data(), w.data());
   for (int s = 0; s < NSTREAM; s++) elm.aerosol_upload(STREAMS[s], 0, NMONTH, clim.data() + (size_t)s * NMONTH * NCELLS);
 }
@@ -117,31 +78,11 @@ int main(int argc, char** argv)
     return 2;
   }
   try {
-    const std::vector<char> blob = read_all(argv[1]);
-    const char* p = blob.data();
-    const char* end = p + blob.size();
-    int64_t ncols;
-    std::memcpy(&ncols, p, 8);
-    p += 8;
-    Inputs in;
-    in.ncols = ncols;
-    while (p < end) {
-      char name[33] = {0};
-      std::memcpy(name, p, 32);
-      int32_t kind;
-      int64_t nbytes;
-      std::memcpy(&kind, p + 32, 4);
-      std::memcpy(&nbytes, p + 36, 8);
-      (kind == 0 ? in.fields : in.params)[name] = p + 44;
-      in.sizes[name] = nbytes;
-      p += 44 + nbytes;
-    }
-
-    if (in.sizes.at("steps") != (int64_t)(NSTEPS * sizeof(elmk_run_step))) throw std::runtime_error("steps: expected 48 rows");
-    std::vector<elmk_run_step> steps(NSTEPS);
-    std::memcpy(steps.data(), in.params.at("steps"), sizeof(elmk_run_step) * NSTEPS);
+    const demo::Inputs in(argv[1]);
+    const int64_t ncols = in.ncols;
+    const std::vector<elmk_run_step> steps = demo::run_steps(in, NSTEPS);
     if (steps.front().month1 == steps.back().month1) throw std::runtime_error("steps: the schedule stays inside one month bracket");
-    const double dt = reinterpret_cast<const double*>(in.params.at("scalars"))[4];
+    const double dt = in.dt();
     const size_t n = (size_t)ncols;
     const std::vector<double> clim = climatology();
 

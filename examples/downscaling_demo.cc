@@ -7,35 +7,16 @@
 // and the snowpack builds there.
 // The input is the flat binary file of examples/run_demo.cc with 25 hourly records in the atm_* series (identical for every column),
 // "topo" (each column's elevation, m), "hf" (the cell's surface height, m) and "steps" (48 elmk_run_step rows), written by
-// tests/test_gpu_downscaling.py::test_downscaling_demo.
+// tests/test_gpu_downscaling.py::test_downscaling_demo; examples/demo_io.h reads it.
 //
 //   g++ -std=c++17 -Iinclude examples/downscaling_demo.cc -Lelmkernels_amd -lelmk -Wl,-rpath,$PWD/elmkernels_amd -o downscaling_demo
 //   ./downscaling_demo state.bin
-#include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
 #include <vector>
 
-#include "elmk_interface.hpp"
+#include "demo_io.h"
 
-static std::vector<char> read_all(const char* path)
-{
-  FILE* f = std::fopen(path, "rb");
-  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<char> b((size_t)n);
-  if (std::fread(b.data(), 1, (size_t)n, f) != (size_t)n) throw std::runtime_error("short read");
-  std::fclose(f);
-  return b;
-}
-
-static const char* const FORCING[] = {"atm_tbot", "atm_pbot", "atm_qbot", "atm_flds", "atm_fsds", "atm_prec", "atm_wind"};
-static const char* const PHENOLOGY[] = {"mlai", "msai", "mhtop", "mhbot"};
+using namespace demo;
 constexpr int NREC = 25, NSTEPS = 48, WINDOW = 24;
 
 int main(int argc, char** argv)
@@ -45,35 +26,13 @@ int main(int argc, char** argv)
     return 2;
   }
   try {
-    const std::vector<char> blob = read_all(argv[1]);
-    const char* p = blob.data();
-    const char* end = p + blob.size();
-    int64_t ncols;
-    std::memcpy(&ncols, p, 8);
-    p += 8;
-    std::map<std::string, const char*> fields, params;
-    std::map<std::string, int64_t> sizes;
-    while (p < end) {
-      char name[33] = {0};
-      std::memcpy(name, p, 32);
-      int32_t kind;
-      int64_t nbytes;
-      std::memcpy(&kind, p + 32, 4);
-      std::memcpy(&nbytes, p + 36, 8);
-      (kind == 0 ? fields : params)[name] = p + 44;
-      sizes[name] = nbytes;
-      p += 44 + nbytes;
-    }
-    auto D = [&](const std::string& k) { return reinterpret_cast<const double*>(params.at(k)); };
-    auto I = [&](const char* k) { return reinterpret_cast<const int32_t*>(params.at(k)); };
-
-    if (sizes.at("steps") != (int64_t)(NSTEPS * sizeof(elmk_run_step))) throw std::runtime_error("steps: expected 48 rows");
-    std::vector<elmk_run_step> steps(NSTEPS);
-    std::memcpy(steps.data(), params.at("steps"), sizeof(elmk_run_step) * NSTEPS);
+    const Inputs in(argv[1]);
+    const int64_t ncols = in.ncols;
+    const std::vector<elmk_run_step> steps = run_steps(in, NSTEPS);
     const std::vector<elmk_run_step> first(steps.begin(), steps.begin() + WINDOW), second(steps.begin() + WINDOW, steps.end());
-    const double dt = D("scalars")[4];
-    const double* topo = D("topo");
-    const double hf_cell = D("hf")[0];
+    const double dt = in.dt();
+    const double* topo = in.D("topo");
+    const double hf_cell = in.D("hf")[0];
     // every column sees the one cell's surface height; one longwave group over the cell
     const std::vector<double> hf((size_t)ncols, hf_cell), gw((size_t)ncols, 1.0 / (double)ncols);
     const std::vector<int64_t> gptr = {0, ncols};
@@ -82,25 +41,15 @@ int main(int argc, char** argv)
 
     for (const int mode : {ELMK_DS_OFF, ELMK_DS_TOPO}) {
       elmk::ELMInterface elm(ncols, 0);
-      elmk_snicar_tables t;
-      std::memset(&t, 0, sizeof t);
-      {
-        const double** slot = reinterpret_cast<const double**>(&t);  // the struct is 31 const double* members, in this order
-        for (int i = 0; i < (int)(sizeof t / sizeof(double*)); i++) slot[i] = D("snicar/" + std::to_string(i));
-      }
-      const int32_t* land = I("land");
-      const double* sc = D("scalars");
-      elm.setup(land[0], land[1], land[2], land[3], land[4], sc[0], (int)sc[1], sc[2], sc[3], D("pft_psn"), D("pft_alb"), D("z0mr"),
-                D("displar"), D("albsat"), D("albdry"), &t, D("age_tau"), D("age_kappa"), D("age_drdt0"));
-      for (const auto& kv : fields) elm.upload(kv.first.c_str(), kv.second);
-      elm.set_column_geography(D("lat"), D("lon"));
+      setup(elm, in);
+      upload_fields(elm, in);
+      elm.set_column_geography(in.D("lat"), in.D("lon"));
       elm.set_column_elevation(topo, hf.data());
       elm.set_downscaling_groups(1, gptr.data(), gcol.data(), gw.data());
       elm.set_downscaling(mode);
       const int tbot = elm.history_add(0, "forc_tbot", ELMK_HIST_AVG);
       elm.reserve_run(NREC, WINDOW);
-      for (const char* f : FORCING) elm.series_upload(f, 0, NREC, D(std::string("series/") + f));
-      for (const char* f : PHENOLOGY) elm.series_upload(f, 0, 12, D(std::string("series/") + f));
+      upload_series(elm, in, NREC);
       elm.run(dt, first, true);
       elm.run(dt, second, true);
       std::vector<double> ta((size_t)ncols), sno((size_t)ncols);

@@ -2,34 +2,21 @@
 // of fluxes (average) and one of ground temperature extremes once, step a simulated day of half-hour steps (advance(), then
 // accumulate_history(): one kernel launch per step, nothing crosses the host link), read every entry once at the end.
 // The state and parameter arrays come from the flat binary file of examples/elm_interface_demo.cc (written by
-// tests/test_gpu_history.py::test_history_demo_runs): the demo has no file readers of its own, as the library has none.
+// tests/test_gpu_history.py::test_history_demo_runs); examples/demo_io.h reads it and makes the setup() call.
 //
 //   g++ -std=c++17 -Iinclude examples/history_demo.cc -Lelmkernels_amd -lelmk -Wl,-rpath,$PWD/elmkernels_amd -o history_demo
 //   ./history_demo state.bin [nsteps = 48] [out.bin]
 //
 // out.bin: the entries in the order of AVG_FIELDS, then t_grnd max, t_grnd min, each [ncols] doubles; then int64 sample counts of
 // tapes 0 and 1.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "elmk_interface.hpp"
-
-static std::vector<char> read_all(const char* path)
-{
-  FILE* f = std::fopen(path, "rb");
-  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<char> b((size_t)n);
-  if (std::fread(b.data(), 1, (size_t)n, f) != (size_t)n) throw std::runtime_error("short read");
-  std::fclose(f);
-  return b;
-}
+#include "demo_io.h"
 
 // single-level fluxes of the averaged tape
 static const char* const AVG_FIELDS[] = {"eflx_sh_tot", "eflx_lh_tot", "qflx_evap_tot", "eflx_soil_grnd", "fsa", "eflx_lwrad_out"};
@@ -42,39 +29,13 @@ int main(int argc, char** argv)
     return 2;
   }
   try {
-    const std::vector<char> blob = read_all(argv[1]);
+    const demo::Inputs in(argv[1]);
     const int nsteps = argc > 2 ? std::atoi(argv[2]) : 48;
-    const char* p = blob.data();
-    const char* end = p + blob.size();
-    int64_t ncols;
-    std::memcpy(&ncols, p, 8);
-    p += 8;
-    std::map<std::string, const char*> fields, params;
-    while (p < end) {
-      char name[33] = {0};
-      std::memcpy(name, p, 32);
-      int32_t kind;
-      int64_t nbytes;
-      std::memcpy(&kind, p + 32, 4);
-      std::memcpy(&nbytes, p + 36, 8);
-      (kind == 0 ? fields : params)[name] = p + 44;
-      p += 44 + nbytes;
-    }
-    auto D = [&](const char* k) { return reinterpret_cast<const double*>(params.at(k)); };
-    auto I = [&](const char* k) { return reinterpret_cast<const int32_t*>(params.at(k)); };
+    const int64_t ncols = in.ncols;
 
     elmk::ELMInterface elm(ncols, 0);
-    elmk_snicar_tables t;
-    std::memset(&t, 0, sizeof t);
-    {
-      const double** slot = reinterpret_cast<const double**>(&t);  // the struct is 31 const double* members, in this order
-      for (int i = 0; i < (int)(sizeof t / sizeof(double*)); i++) slot[i] = D(("snicar/" + std::to_string(i)).c_str());
-    }
-    const int32_t* land = I("land");
-    const double* sc = D("scalars");
-    elm.setup(land[0], land[1], land[2], land[3], land[4], sc[0], (int)sc[1], sc[2], sc[3], D("pft_psn"), D("pft_alb"), D("z0mr"),
-              D("displar"), D("albsat"), D("albdry"), &t, D("age_tau"), D("age_kappa"), D("age_drdt0"));
-    for (const auto& kv : fields) elm.upload(kv.first.c_str(), kv.second);
+    demo::setup(elm, in);
+    demo::upload_fields(elm, in);
 
     // tape 0: daily means of the fluxes; tape 1: daily extremes of the ground temperature
     std::vector<int> entries;
@@ -83,12 +44,12 @@ int main(int argc, char** argv)
     entries.push_back(elm.history_add(1, "t_grnd", ELMK_HIST_MIN));
 
     elmk::StepWeights w;
-    std::memcpy(w.forc_wt1, D("forc_wt1"), 64);
-    std::memcpy(w.forc_wt2, D("forc_wt2"), 64);
-    w.month_wt1 = D("month_wt")[0];
-    w.month_wt2 = D("month_wt")[1];
+    std::memcpy(w.forc_wt1, in.D("forc_wt1"), 64);
+    std::memcpy(w.forc_wt2, in.D("forc_wt2"), 64);
+    w.month_wt1 = in.D("month_wt")[0];
+    w.month_wt2 = in.D("month_wt")[1];
     w.qbot_is_relative_humidity = 0;
-    const double dt = sc[4];
+    const double dt = in.dt();
     for (int s = 0; s < nsteps; s++) {
       if (elm.advance(dt, w)) return 1;
       elm.accumulate_history();

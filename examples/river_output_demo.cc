@@ -6,38 +6,18 @@
 // elmk_routing_init, elmk_routing_kinematic_init or elmk_routing_inundation_init call.  Prints each cell's mean and peak discharge and
 // the largest flooded fraction of the whole run, and "identical" when the two runs agree in every bit of them.  The steps are the
 // stand-alone calls; in a model run elmk_run with ELMK_RUN_HYDROLOGY | ELMK_RUN_WATER_BALANCE | ELMK_RUN_ROUTING | ELMK_RUN_HISTORY
-// does the same on the device.
+// does the same on the device.  The columns, the cells and the kinematic scheme come from examples/demo_site.h.
 //
 //   g++ -std=c++17 -Iinclude examples/river_output_demo.cc -Lelmkernels_amd -lelmk -Wl,-rpath,$PWD/elmkernels_amd -o river_output_demo
 //   ./river_output_demo
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-#include "elmk.h"
+#include "demo_site.h"
 
-static void chk(elmk_ctx* ctx, int rc, const char* what)
-{
-  if (rc < 0) throw std::runtime_error(std::string(what) + ": " + elmk_last_error(ctx));
-}
-static int fid(const char* name)
-{
-  const int f = elmk_field_id(name);
-  if (f < 0) throw std::runtime_error(std::string("no field ") + name);
-  return f;
-}
-// one value per level for every column, [column][level]
-static void put(elmk_ctx* ctx, const char* name, int64_t n, const std::vector<double>& levels)
-{
-  std::vector<double> a((size_t)n * levels.size());
-  for (int64_t c = 0; c < n; c++)
-    for (size_t l = 0; l < levels.size(); l++) a[(size_t)c * levels.size() + l] = levels[l];
-  chk(ctx, elmk_upload(ctx, fid(name), a.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), name);
-}
-
+using namespace demo;
 static const int64_t N = 8;  // columns = cells: cell c drains into c + 1, the last is the outlet
 static const int NSUB = 4, NSTEPS = 48, STORM_STEPS = 12;
 static const double DT = 1800.0, STORM = 4.0e-3 /* mm/s: 14.4 mm/h */;
@@ -49,47 +29,14 @@ static elmk_ctx* make(bool fresh, int entry[NENTRY])
   elmk_ctx* ctx = nullptr;
   chk(ctx, elmk_create(N, 0, &ctx), "elmk_create");
   chk(ctx, elmk_set_land(ctx, 1 /* soil */, 1, 12, 0, 0), "elmk_set_land");
-  if (fresh) {
-    std::vector<double> zi(21, 0.0), dz(20, 0.0), z(20, 0.0);
-    for (int j = 0; j < 15; j++) z[5 + j] = 0.025 * (std::exp(0.5 * (j + 0.5)) - 1.0);
-    for (int j = 0; j < 15; j++) zi[6 + j] = j < 14 ? 0.5 * (z[5 + j] + z[6 + j]) : z[19] + 0.5 * (z[19] - z[18]);
-    for (int j = 0; j < 15; j++) dz[5 + j] = zi[6 + j] - zi[5 + j];
-    const double watsat = 0.45;
-    std::vector<double> liq(20, 0.0), ice(20, 0.0);
-    for (int j = 0; j < 15; j++) liq[5 + j] = 0.7 * watsat * dz[5 + j] * 1000.0;
-    put(ctx, "zisoi", N, zi);
-    put(ctx, "dz", N, dz);
-    put(ctx, "zsoi", N, z);
-    put(ctx, "h2osoi_liq", N, liq);
-    put(ctx, "h2osoi_ice", N, ice);
-    put(ctx, "watsat", N, std::vector<double>(15, watsat));
-    put(ctx, "sucsat", N, std::vector<double>(15, 200.0));
-    put(ctx, "bsw", N, std::vector<double>(15, 5.0));
-  }
-  chk(ctx, elmk_soil_hydrology_enable(ctx), "elmk_soil_hydrology_enable");
-  std::vector<double> hksat((size_t)ELMK_HYD_NLAYER * N, 2.0e-3), wtfact(N, 0.4), thresh(N, 5.0), k_wet(N, 0.035), rsub(N, 0.35);
-  chk(ctx, elmk_soil_hydrology_set_params(ctx, hksat.data(), wtfact.data(), thresh.data(), k_wet.data(), rsub.data()), "set_params");
-  if (fresh) {
-    std::vector<double> zwt0(N, 1.0), wa0(N, 4000.0);
-    chk(ctx, elmk_soil_hydrology_init(ctx, zwt0.data(), wa0.data()), "elmk_soil_hydrology_init");
-  }
+  if (fresh) loam_columns(ctx, N, 0.7);
+  hydrology_on(ctx, N, 2.0e-3);
+  if (fresh) hydrology_start(ctx, N, 1.0);
   chk(ctx, elmk_water_balance_enable(ctx, 1.0e-6), "elmk_water_balance_enable");
-  std::vector<int64_t> ptr(N + 1);
-  std::vector<int32_t> col(N), down(N);
-  std::vector<double> w(N, 1.0), ddist(N, 2.0e4), area(N, 1.0e8);
-  for (int64_t c = 0; c <= N; c++) ptr[c] = c;
-  for (int64_t c = 0; c < N; c++) {
-    col[c] = (int32_t)c;
-    down[c] = c + 1 < N ? (int32_t)(c + 1) : -1;
-  }
-  chk(ctx, elmk_set_output_grid(ctx, N, ptr.data(), col.data(), w.data(), 0.0), "elmk_set_output_grid");
-  chk(ctx, elmk_routing_enable(ctx, N, down.data(), ddist.data(), area.data(), 0.35, NSUB), "elmk_routing_enable");
+  river_cells(ctx, chain(N), NSUB);
   // kinematic_routing_demo.cc's cells under banks of 0.5 m and a floodplain that rises 0.2 m per tenth of the cell
   const double value[ELMK_KW_NPARAM] = {0.05, 0.1, 1.0e-3, 1.0e5, 10.0, 0.01, 0.05, 2.0e4, 100.0, 1.0e-3, 0.04};
-  std::vector<double> params((size_t)ELMK_KW_NPARAM * N);
-  for (int k = 0; k < ELMK_KW_NPARAM; k++)
-    for (int64_t c = 0; c < N; c++) params[(size_t)k * N + c] = value[k];
-  chk(ctx, elmk_routing_kinematic_enable(ctx, params.data()), "elmk_routing_kinematic_enable");
+  kinematic_on(ctx, N, value);
   std::vector<double> rdepth(N, 0.5), eprof((size_t)ELMK_FP_NPROF * N);
   for (int k = 0; k < ELMK_FP_NPROF; k++)
     for (int64_t c = 0; c < N; c++) eprof[(size_t)k * N + c] = 0.2 * k;

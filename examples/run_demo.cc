@@ -3,7 +3,8 @@
 // runs of 24; the records of the second window go up while the first run executes, and no step waits for the host.
 // The state and parameter arrays come from the flat binary file of examples/history_demo.cc, plus the geography ("lat", "lon"), the
 // series ("series/<field>": [records][ncols], 25 hourly records for atm_*, 12 months for mlai .. mhbot) and the schedule ("steps":
-// 48 elmk_run_step rows), written by tests/test_gpu_run.py::test_run_demo: the demo has no file readers or calendar of its own.
+// 48 elmk_run_step rows), written by tests/test_gpu_run.py::test_run_demo: the demo has no calendar of its own, and examples/demo_io.h
+// reads the file and sets the context up.
 //
 //   g++ -std=c++17 -Iinclude examples/run_demo.cc -Lelmkernels_amd -lelmk -Wl,-rpath,$PWD/elmkernels_amd -o run_demo
 //   ./run_demo state.bin [out.bin]
@@ -12,29 +13,12 @@
 // h2osoi_vol, h2ocan, h2osno, h2osfc, t_soisno, t_grnd, t_h2osfc, t_h2osfc_bef, nrad, dz, zsoi, zisoi), then the 48 conservation
 // rows [48][8][3] doubles.
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "elmk_interface.hpp"
+#include "demo_io.h"
 
-static std::vector<char> read_all(const char* path)
-{
-  FILE* f = std::fopen(path, "rb");
-  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-  std::fseek(f, 0, SEEK_END);
-  const long n = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<char> b((size_t)n);
-  if (std::fread(b.data(), 1, (size_t)n, f) != (size_t)n) throw std::runtime_error("short read");
-  std::fclose(f);
-  return b;
-}
-
-static const char* const FORCING[] = {"atm_tbot", "atm_pbot", "atm_qbot", "atm_flds", "atm_fsds", "atm_prec", "atm_wind"};
-static const char* const PHENOLOGY[] = {"mlai", "msai", "mhtop", "mhbot"};
+using namespace demo;
 constexpr int NREC = 25, NSTEPS = 48, WINDOW = 24;
 
 template <class T> static void put(FILE* o, const std::vector<T>& v) { std::fwrite(v.data(), sizeof(T), v.size(), o); }
@@ -46,56 +30,25 @@ int main(int argc, char** argv)
     return 2;
   }
   try {
-    const std::vector<char> blob = read_all(argv[1]);
-    const char* p = blob.data();
-    const char* end = p + blob.size();
-    int64_t ncols;
-    std::memcpy(&ncols, p, 8);
-    p += 8;
-    std::map<std::string, const char*> fields, params;
-    std::map<std::string, int64_t> sizes;
-    while (p < end) {
-      char name[33] = {0};
-      std::memcpy(name, p, 32);
-      int32_t kind;
-      int64_t nbytes;
-      std::memcpy(&kind, p + 32, 4);
-      std::memcpy(&nbytes, p + 36, 8);
-      (kind == 0 ? fields : params)[name] = p + 44;
-      sizes[name] = nbytes;
-      p += 44 + nbytes;
-    }
-    auto D = [&](const std::string& k) { return reinterpret_cast<const double*>(params.at(k)); };
-    auto I = [&](const char* k) { return reinterpret_cast<const int32_t*>(params.at(k)); };
-
+    const Inputs in(argv[1]);
+    const int64_t ncols = in.ncols;
     elmk::ELMInterface elm(ncols, 0);
-    elmk_snicar_tables t;
-    std::memset(&t, 0, sizeof t);
-    {
-      const double** slot = reinterpret_cast<const double**>(&t);  // the struct is 31 const double* members, in this order
-      for (int i = 0; i < (int)(sizeof t / sizeof(double*)); i++) slot[i] = D("snicar/" + std::to_string(i));
-    }
-    const int32_t* land = I("land");
-    const double* sc = D("scalars");
-    elm.setup(land[0], land[1], land[2], land[3], land[4], sc[0], (int)sc[1], sc[2], sc[3], D("pft_psn"), D("pft_alb"), D("z0mr"),
-              D("displar"), D("albsat"), D("albdry"), &t, D("age_tau"), D("age_kappa"), D("age_drdt0"));
-    for (const auto& kv : fields) elm.upload(kv.first.c_str(), kv.second);
-    elm.set_column_geography(D("lat"), D("lon"));
+    setup(elm, in);
+    upload_fields(elm, in);
+    elm.set_column_geography(in.D("lat"), in.D("lon"));
 
-    if (sizes.at("steps") != (int64_t)(NSTEPS * sizeof(elmk_run_step))) throw std::runtime_error("steps: expected 48 rows");
-    std::vector<elmk_run_step> steps(NSTEPS);
-    std::memcpy(steps.data(), params.at("steps"), sizeof(elmk_run_step) * NSTEPS);
+    const std::vector<elmk_run_step> steps = run_steps(in, NSTEPS);
     const std::vector<elmk_run_step> first(steps.begin(), steps.begin() + WINDOW), second(steps.begin() + WINDOW, steps.end());
-    const double dt = sc[4];
+    const double dt = in.dt();
 
     // all 25 forcing slots and the 12 months on the device; the first window's records (slots 0 .. 12) before the first run
     elm.reserve_run(NREC, WINDOW);
     const int split = first.back().forc_slot + 2;  // records the first run reads: 0 .. split - 1
-    for (const char* f : FORCING) elm.series_upload(f, 0, split, D(std::string("series/") + f));
-    for (const char* f : PHENOLOGY) elm.series_upload(f, 0, 12, D(std::string("series/") + f));
+    for (const char* f : FORCING) elm.series_upload(f, 0, split, in.D(std::string("series/") + f));
+    for (const char* f : PHENOLOGY) elm.series_upload(f, 0, 12, in.D(std::string("series/") + f));
     elm.enqueue_run(dt, first);
     // the second window goes up while the first run executes (it reads none of these records, so nothing waits)
-    for (const char* f : FORCING) elm.series_upload(f, split, NREC - split, D(std::string("series/") + f) + (size_t)split * ncols);
+    for (const char* f : FORCING) elm.series_upload(f, split, NREC - split, in.D(std::string("series/") + f) + (size_t)split * ncols);
     elm.finish_run();
     std::vector<double> cons = elm.run_conservation();
     elm.run(dt, second);

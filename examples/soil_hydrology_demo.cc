@@ -3,37 +3,18 @@
 // runs, so the fluxes the stage reads (qflx_top_soil, qflx_rootsoi) are simply uploaded once; in a model run elmk_advance_physics
 // writes them every step and elmk_run with ELMK_RUN_HYDROLOGY runs the stage after it.  Prints, per column, the water table, the
 // aquifer, the surface store and the soil water at the start and the end, with the day's budget: the change of the stores against
-// (rain - runoff - uptake - drainage) dt summed over the steps.
+// (rain - runoff - uptake - drainage) dt summed over the steps.  The columns come from examples/demo_site.h.
 //
 //   g++ -std=c++17 -Iinclude examples/soil_hydrology_demo.cc -Lelmkernels_amd -lelmk -Wl,-rpath,$PWD/elmkernels_amd -o soil_hydrology_demo
 //   ./soil_hydrology_demo
 #include <cmath>
 #include <cstdio>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-#include "elmk.h"
+#include "demo_site.h"
 
-static elmk_ctx* ctx;
-static void chk(int rc, const char* what)
-{
-  if (rc < 0) throw std::runtime_error(std::string(what) + ": " + elmk_last_error(ctx));
-}
-static int fid(const char* name)
-{
-  const int f = elmk_field_id(name);
-  if (f < 0) throw std::runtime_error(std::string("no field ") + name);
-  return f;
-}
-// one value per level for every column, [column][level]
-static void put(const char* name, int64_t n, const std::vector<double>& levels)
-{
-  std::vector<double> a((size_t)n * levels.size());
-  for (int64_t c = 0; c < n; c++)
-    for (size_t l = 0; l < levels.size(); l++) a[(size_t)c * levels.size() + l] = levels[l];
-  chk(elmk_upload(ctx, fid(name), a.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), name);
-}
+using namespace demo;
+
 static double soil_water(int64_t c, const std::vector<double>& liq)
 {
   double s = 0.0;
@@ -47,52 +28,37 @@ int main()
     const int64_t n = 6;
     const double dt = 1800.0, rain = 2.0e-3 /* mm/s: 7.2 mm/h */, uptake = 2.0e-5;
     const int nsteps = 48;
-    chk(elmk_create(n, 0, &ctx), "elmk_create");
-    chk(elmk_set_land(ctx, 1 /* soil */, 1, 12, 0, 0), "elmk_set_land");
-    // ELM's soil grid: 5 snow levels (unused here), 15 ground layers
-    std::vector<double> zi(21, 0.0), dz(20, 0.0), z(20, 0.0);
-    for (int j = 0; j < 15; j++) z[5 + j] = 0.025 * (std::exp(0.5 * (j + 0.5)) - 1.0);
-    for (int j = 0; j < 15; j++) zi[6 + j] = j < 14 ? 0.5 * (z[5 + j] + z[6 + j]) : z[19] + 0.5 * (z[19] - z[18]);
-    for (int j = 0; j < 15; j++) dz[5 + j] = zi[6 + j] - zi[5 + j];
-    const double watsat = 0.45;
-    std::vector<double> liq(20, 0.0), ice(20, 0.0), root(15, 0.0);
-    for (int j = 0; j < 15; j++) liq[5 + j] = 0.5 * watsat * dz[5 + j] * 1000.0;  // half saturated
+    elmk_ctx* ctx = nullptr;
+    chk(ctx, elmk_create(n, 0, &ctx), "elmk_create");
+    chk(ctx, elmk_set_land(ctx, 1 /* soil */, 1, 12, 0, 0), "elmk_set_land");
+    loam_columns(ctx, n, 0.5);  // half saturated
+    std::vector<double> root(15, 0.0);
     for (int j = 0; j < 5; j++) root[j] = uptake / 5.0;
-    put("zisoi", n, zi);
-    put("dz", n, dz);
-    put("zsoi", n, z);
-    put("h2osoi_liq", n, liq);
-    put("h2osoi_ice", n, ice);
-    put("watsat", n, std::vector<double>(15, watsat));
-    put("sucsat", n, std::vector<double>(15, 200.0));
-    put("bsw", n, std::vector<double>(15, 5.0));
-    put("qflx_rootsoi", n, root);
-    put("qflx_top_soil", n, {rain});
+    put(ctx, "qflx_rootsoi", n, root);
+    put(ctx, "qflx_top_soil", n, {rain});
     // (snl, h2osfc, frac_h2osfc, frac_sno_eff and the evaporation and dew terms stay at the zeros the context starts with)
 
-    chk(elmk_soil_hydrology_enable(ctx), "enable");
-    std::vector<double> hksat((size_t)ELMK_HYD_NLAYER * n, 5.0e-3), wtfact(n, 0.4), thresh(n, 5.0), k_wet(n, 0.035), rsub(n, 0.35);
-    chk(elmk_soil_hydrology_set_params(ctx, hksat.data(), wtfact.data(), thresh.data(), k_wet.data(), rsub.data()), "set_params");
+    hydrology_on(ctx, n, 5.0e-3);
     const double depth[n] = {0.05, 0.5, 1.5, 3.0, 6.0, 0.0 /* cold start */};
     std::vector<double> zwt0(depth, depth + n), wa0(n, 4000.0), cold(n);
-    chk(elmk_soil_hydrology_init(ctx, nullptr, nullptr), "init(cold start)");
-    chk(elmk_soil_hydrology_read(ctx, ELMK_HYD_ZWT, cold.data(), 0, n), "read");
+    chk(ctx, elmk_soil_hydrology_init(ctx, nullptr, nullptr), "init(cold start)");
+    chk(ctx, elmk_soil_hydrology_read(ctx, ELMK_HYD_ZWT, cold.data(), 0, n), "read");
     zwt0[n - 1] = cold[n - 1];
-    chk(elmk_soil_hydrology_init(ctx, zwt0.data(), wa0.data()), "init");
+    chk(ctx, elmk_soil_hydrology_init(ctx, zwt0.data(), wa0.data()), "init");
 
     std::vector<double> liq0((size_t)n * 20), liq1((size_t)n * 20), h2osfc(n), zwt(n), wa(n), row(n), out(n, 0.0);
-    chk(elmk_download(ctx, fid("h2osoi_liq"), liq0.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), "download");
+    chk(ctx, elmk_download(ctx, fid("h2osoi_liq"), liq0.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), "download");
     for (int s = 0; s < nsteps; s++) {
-      chk(elmk_soil_hydrology(ctx, dt), "elmk_soil_hydrology");
+      chk(ctx, elmk_soil_hydrology(ctx, dt), "elmk_soil_hydrology");
       for (int which : {ELMK_HYD_QFLX_SURF, ELMK_HYD_QFLX_H2OSFC_SURF, ELMK_HYD_QFLX_DRAIN}) {
-        chk(elmk_soil_hydrology_read(ctx, which, row.data(), 0, n), "read");
+        chk(ctx, elmk_soil_hydrology_read(ctx, which, row.data(), 0, n), "read");
         for (int64_t c = 0; c < n; c++) out[c] += row[c] * dt;
       }
     }
-    chk(elmk_download(ctx, fid("h2osoi_liq"), liq1.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), "download");
-    chk(elmk_download(ctx, fid("h2osfc"), h2osfc.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), "download");
-    chk(elmk_soil_hydrology_read(ctx, ELMK_HYD_ZWT, zwt.data(), 0, n), "read");
-    chk(elmk_soil_hydrology_read(ctx, ELMK_HYD_WA, wa.data(), 0, n), "read");
+    chk(ctx, elmk_download(ctx, fid("h2osoi_liq"), liq1.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), "download");
+    chk(ctx, elmk_download(ctx, fid("h2osfc"), h2osfc.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), "download");
+    chk(ctx, elmk_soil_hydrology_read(ctx, ELMK_HYD_ZWT, zwt.data(), 0, n), "read");
+    chk(ctx, elmk_soil_hydrology_read(ctx, ELMK_HYD_WA, wa.data(), 0, n), "read");
 
     std::printf("soil hydrology, %d steps of %.0f s, rain %.1f mm, uptake %.2f mm\n", nsteps, dt, rain * dt * nsteps, uptake * dt * nsteps);
     std::printf("%6s %9s %9s %10s %10s %9s %9s %10s %11s\n", "column", "zwt0 m", "zwt m", "soil0 mm", "soil mm", "h2osfc", "wa - wa0", "runoff mm", "budget mm");
@@ -104,7 +70,7 @@ int main()
       std::printf("%6lld %9.3f %9.3f %10.2f %10.2f %9.3f %9.3f %10.3f %11.2e\n", (long long)c, zwt0[c], zwt[c], soil_water(c, liq0),
                   soil_water(c, liq1), h2osfc[c], wa[c] - wa0[c], out[c], budget);
     }
-    chk(elmk_destroy(ctx), "elmk_destroy");
+    chk(ctx, elmk_destroy(ctx), "elmk_destroy");
     return worst < 1.0e-8 ? 0 : 1;
   } catch (const std::exception& e) {
     std::fprintf(stderr, "soil_hydrology_demo: %s\n", e.what());

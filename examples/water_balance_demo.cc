@@ -1,5 +1,5 @@
 // water_balance_demo.cc - the closed water budget of elmk.h ("water balance") and history entries over feature rows, through the C ABI:
-// a day of half-hour steps of steady rain and root uptake on the uniform loam columns of soil_hydrology_demo.cc.  Every step runs
+// a day of half-hour steps of steady rain and root uptake on the uniform loam columns of examples/demo_site.h.  Every step runs
 // elmk_init_timestep, elmk_water_balance_begin (W0), the soil hydrology stage and elmk_water_balance (W1 - W8), and samples a history
 // tape that averages two feature rows: total runoff QRUNOFF (a water-balance row) and the water table ZWT (a hydrology row).  Prints
 // the worst |ERRH2O| and the number of columns over the tolerance per step, then the tape means per column.  In a model run elmk_run
@@ -9,79 +9,45 @@
 //   ./water_balance_demo
 #include <cmath>
 #include <cstdio>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-#include "elmk.h"
+#include "demo_site.h"
 
-static elmk_ctx* ctx;
-static void chk(int rc, const char* what)
-{
-  if (rc < 0) throw std::runtime_error(std::string(what) + ": " + elmk_last_error(ctx));
-}
-static int fid(const char* name)
-{
-  const int f = elmk_field_id(name);
-  if (f < 0) throw std::runtime_error(std::string("no field ") + name);
-  return f;
-}
-// one value per level for every column, [column][level]
-static void put(const char* name, int64_t n, const std::vector<double>& levels)
-{
-  std::vector<double> a((size_t)n * levels.size());
-  for (int64_t c = 0; c < n; c++)
-    for (size_t l = 0; l < levels.size(); l++) a[(size_t)c * levels.size() + l] = levels[l];
-  chk(elmk_upload(ctx, fid(name), a.data(), 0, n, ELMK_LAYOUT_COL_MAJOR), name);
-}
+using namespace demo;
+
 int main()
 {
   try {
     const int64_t n = 6;
     const double dt = 1800.0, rain = 2.0e-3 /* mm/s: 7.2 mm/h */, uptake = 2.0e-5;
     const int nsteps = 48;
-    chk(elmk_create(n, 0, &ctx), "elmk_create");
-    chk(elmk_set_land(ctx, 1 /* soil */, 1, 12, 0, 0), "elmk_set_land");
-    // ELM's soil grid: 5 snow levels (unused here), 15 ground layers
-    std::vector<double> zi(21, 0.0), dz(20, 0.0), z(20, 0.0);
-    for (int j = 0; j < 15; j++) z[5 + j] = 0.025 * (std::exp(0.5 * (j + 0.5)) - 1.0);
-    for (int j = 0; j < 15; j++) zi[6 + j] = j < 14 ? 0.5 * (z[5 + j] + z[6 + j]) : z[19] + 0.5 * (z[19] - z[18]);
-    for (int j = 0; j < 15; j++) dz[5 + j] = zi[6 + j] - zi[5 + j];
-    const double watsat = 0.45;
-    std::vector<double> liq(20, 0.0), ice(20, 0.0), root(15, 0.0);
-    for (int j = 0; j < 15; j++) liq[5 + j] = 0.5 * watsat * dz[5 + j] * 1000.0;  // half saturated
+    elmk_ctx* ctx = nullptr;
+    chk(ctx, elmk_create(n, 0, &ctx), "elmk_create");
+    chk(ctx, elmk_set_land(ctx, 1 /* soil */, 1, 12, 0, 0), "elmk_set_land");
+    loam_columns(ctx, n, 0.5);  // half saturated
+    std::vector<double> root(15, 0.0);
     for (int j = 0; j < 5; j++) root[j] = uptake / 5.0;
-    put("zisoi", n, zi);
-    put("dz", n, dz);
-    put("zsoi", n, z);
-    put("h2osoi_liq", n, liq);
-    put("h2osoi_ice", n, ice);
-    put("watsat", n, std::vector<double>(15, watsat));
-    put("sucsat", n, std::vector<double>(15, 200.0));
-    put("bsw", n, std::vector<double>(15, 5.0));
-    put("qflx_rootsoi", n, root);
-    put("qflx_top_soil", n, {rain});
+    put(ctx, "qflx_rootsoi", n, root);
+    put(ctx, "qflx_top_soil", n, {rain});
     // what the budget sees of the same fluxes: the rain that reaches the ground and the uptake that leaves as transpiration
-    put("forc_rain", n, {rain});
-    put("qflx_evap_tot", n, {uptake});
+    put(ctx, "forc_rain", n, {rain});
+    put(ctx, "qflx_evap_tot", n, {uptake});
     // (snl, h2osfc, frac_h2osfc, frac_sno_eff and the evaporation and dew terms stay at the zeros the context starts with)
 
-    chk(elmk_soil_hydrology_enable(ctx), "enable");
-    std::vector<double> hksat((size_t)ELMK_HYD_NLAYER * n, 5.0e-3), wtfact(n, 0.4), thresh(n, 5.0), k_wet(n, 0.035), rsub(n, 0.35);
-    chk(elmk_soil_hydrology_set_params(ctx, hksat.data(), wtfact.data(), thresh.data(), k_wet.data(), rsub.data()), "set_params");
+    hydrology_on(ctx, n, 5.0e-3);
     const double depth[n] = {0.05, 0.5, 1.5, 3.0, 6.0, 0.0 /* cold start */};
     std::vector<double> zwt0(depth, depth + n), wa0(n, 4000.0), cold(n);
-    chk(elmk_soil_hydrology_init(ctx, nullptr, nullptr), "init(cold start)");
-    chk(elmk_soil_hydrology_read(ctx, ELMK_HYD_ZWT, cold.data(), 0, n), "read");
+    chk(ctx, elmk_soil_hydrology_init(ctx, nullptr, nullptr), "init(cold start)");
+    chk(ctx, elmk_soil_hydrology_read(ctx, ELMK_HYD_ZWT, cold.data(), 0, n), "read");
     zwt0[n - 1] = cold[n - 1];
-    chk(elmk_soil_hydrology_init(ctx, zwt0.data(), wa0.data()), "init");
+    chk(ctx, elmk_soil_hydrology_init(ctx, zwt0.data(), wa0.data()), "init");
 
     const double tol = 1.0e-8;  // mm
-    chk(elmk_water_balance_enable(ctx, tol), "elmk_water_balance_enable");
+    chk(ctx, elmk_water_balance_enable(ctx, tol), "elmk_water_balance_enable");
     const int e_runoff = elmk_column_history_add_row(ctx, 0, ELMK_ROWS_WATER_BALANCE, ELMK_WB_QRUNOFF, ELMK_HIST_AVG);
-    chk(e_runoff, "elmk_column_history_add_row(QRUNOFF)");
+    chk(ctx, e_runoff, "elmk_column_history_add_row(QRUNOFF)");
     const int e_zwt = elmk_column_history_add_row(ctx, 0, ELMK_ROWS_HYDROLOGY, ELMK_HYD_ZWT, ELMK_HIST_AVG);
-    chk(e_zwt, "elmk_column_history_add_row(ZWT)");
+    chk(ctx, e_zwt, "elmk_column_history_add_row(ZWT)");
 
     std::printf("water balance, %d steps of %.0f s, rain %.1f mm, uptake %.2f mm, tolerance %.1e mm\n", nsteps, dt, rain * dt * nsteps,
                 uptake * dt * nsteps, tol);
@@ -91,25 +57,25 @@ int main()
     for (int s = 0; s < nsteps; s++) {
       double mms[3][3];
       int64_t nbad = 0, first = -1;
-      chk(elmk_init_timestep(ctx), "elmk_init_timestep");
-      chk(elmk_water_balance_begin(ctx), "elmk_water_balance_begin");
-      chk(elmk_soil_hydrology(ctx, dt), "elmk_soil_hydrology");
-      chk(elmk_water_balance(ctx, dt, &mms[0][0], &nbad, &first), "elmk_water_balance");
-      chk(elmk_history_accumulate(ctx), "elmk_history_accumulate");
+      chk(ctx, elmk_init_timestep(ctx), "elmk_init_timestep");
+      chk(ctx, elmk_water_balance_begin(ctx), "elmk_water_balance_begin");
+      chk(ctx, elmk_soil_hydrology(ctx, dt), "elmk_soil_hydrology");
+      chk(ctx, elmk_water_balance(ctx, dt, &mms[0][0], &nbad, &first), "elmk_water_balance");
+      chk(ctx, elmk_history_accumulate(ctx), "elmk_history_accumulate");
       const double w = std::fmax(std::fabs(mms[0][0]), std::fabs(mms[0][1]));  // triple 0: (min, max, sum) of ERRH2O
       worst = std::fmax(worst, w);
       bad_total += nbad;
       std::printf("%4d %14.3e %6lld %10lld\n", s, w, (long long)nbad, (long long)first);
     }
     std::vector<double> runoff(n), zwt(n), tws(n);
-    chk(elmk_history_read(ctx, e_runoff, runoff.data(), 0, n, ELMK_LAYOUT_SOA), "elmk_history_read");
-    chk(elmk_history_read(ctx, e_zwt, zwt.data(), 0, n, ELMK_LAYOUT_SOA), "elmk_history_read");
-    chk(elmk_water_balance_read(ctx, ELMK_WB_ENDWB, tws.data(), 0, n), "elmk_water_balance_read");
+    chk(ctx, elmk_history_read(ctx, e_runoff, runoff.data(), 0, n, ELMK_LAYOUT_SOA), "elmk_history_read");
+    chk(ctx, elmk_history_read(ctx, e_zwt, zwt.data(), 0, n, ELMK_LAYOUT_SOA), "elmk_history_read");
+    chk(ctx, elmk_water_balance_read(ctx, ELMK_WB_ENDWB, tws.data(), 0, n), "elmk_water_balance_read");
     std::printf("%6s %9s %16s %12s %12s\n", "column", "zwt0 m", "mean QRUNOFF mm/s", "mean ZWT m", "TWS mm");
     for (int64_t c = 0; c < n; c++) std::printf("%6lld %9.3f %16.6e %12.4f %12.3f\n", (long long)c, zwt0[c], runoff[c], zwt[c], tws[c]);
-    chk(elmk_history_clear(ctx), "elmk_history_clear");
-    chk(elmk_water_balance_clear(ctx), "elmk_water_balance_clear");
-    chk(elmk_destroy(ctx), "elmk_destroy");
+    chk(ctx, elmk_history_clear(ctx), "elmk_history_clear");
+    chk(ctx, elmk_water_balance_clear(ctx), "elmk_water_balance_clear");
+    chk(ctx, elmk_destroy(ctx), "elmk_destroy");
     return (worst < tol && bad_total == 0) ? 0 : 1;
   } catch (const std::exception& e) {
     std::fprintf(stderr, "water_balance_demo: %s\n", e.what());

@@ -159,6 +159,22 @@ def test_cpp_interface_mirror_compiles_and_links():
         assert member in hdr, member
 
 
+EXAMPLES = sorted(f[:-3] for f in os.listdir(os.path.join(ROOT, "examples")) if f.endswith(".cc"))
+
+
+def test_every_example_is_listed():
+    """The programs of examples/ (the two shared headers, demo_io.h and demo_site.h, are not programs): an empty list would let
+    the parametrised test below pass with no case."""
+    assert len(EXAMPLES) >= 22 and "heat_demo" in EXAMPLES and "run_demo" in EXAMPLES
+
+
+@pytest.mark.parametrize("name", EXAMPLES)
+def test_example_compiles_and_links(name, tmp_path):
+    """Every examples/<name>.cc builds as the GPU tests build it (-Wall -Wextra -Werror, linked against libelmk): an edit to a
+    shared header cannot break a demo unseen on a machine without a GPU.  Nothing is run."""
+    assert os.path.isfile(build_demo(name, tmp_path))
+
+
 def test_solar_geometry_matches_the_reference_sources():
     """The host scalars kokkos_init_timestep computes before its kernels - step-averaged cos(zenith), day length, maximum day
     length (init_timestep_kokkos.cc:26-34) - as include/elmk_interface.hpp restates them, against the reference's own
