@@ -46,15 +46,18 @@ def placed_cells(n):
     return [(c, order[i], 0) for i, c in enumerate(free[:13])]
 
 
-def flood_values(n, seed, area, p, volr, wh, wt, nsub, dt):
+def flood_values(n, seed, area, p, volr, wh, wt, nsub, dt, rbank=1.0e4):
     """rdepth [n], eprof [11, n] and the initial VOLR, WH, WT, WF of one (nsub, dt) case, and the parameters with the placed cells'
     changed.  Cells without a place: banks of 0.3 .. 12 m, profile steps of 1 mm .. 5 m, every third floodplain wet.  Cells 2, 4 .. 16
     hold the edge values in WF.  A placed cell keeps its path through all five calls because it stands still: its Manning n is 400,
     so it releases next to nothing, its profile steps are 5 m, so a segment is wider than what five calls of inflow bring, and it
     starts in the middle of its segment (above the profile: at 1.5 VB_10; untouched: channel a third full under banks of 12 m).  A
-    returning cell is the opposite: a 40 m reach under banks of 1e4 m, which releases a fixed volume D per sub-step (what it holds, or
+    returning cell is the opposite: a 40 m reach under banks of rbank, which releases a fixed volume D per sub-step (what it holds, or
     Manning's rate where the sub-step is too short for the cap) that dwarfs its inflow; with the channel full and X = (m - 0.5) D on
-    the floodplain it returns in sub-step m, and m is the middle sub-step of its call."""
+    the floodplain it returns in sub-step m, and m is the middle sub-step of its call.  It returns there as long as what has flowed
+    in by then stays under D / 2.  Under banks of 1e4 m D is about 2.6e7 m3, which the 2e7 m3 of one wet floodplain straight above
+    the cell, or the stores of two such cells over a day, can reach; rbank = 1e6 m makes D a hundred times that, beyond what the
+    eight upstream cells a cell can have hold together, so that the paths hold on every network shape."""
     rng = np.random.default_rng(seed)
     p = p.copy()
     volr, wh, wt = volr.copy(), wh.copy(), wt.copy()
@@ -70,7 +73,7 @@ def flood_values(n, seed, area, p, volr, wh, wt, nsub, dt):
         eprof[:, c] = 5.0 * np.arange(11)
         wh[c] = wt[c] = 0.0
         if path == 1:
-            p[rt.RLEN, c], rdepth[c] = 40.0, 1.0e4
+            p[rt.RLEN, c], rdepth[c] = 40.0, rbank
         else:
             p[rt.NR, c], rdepth[c] = 400.0, 12.0
     tab = rt.inundation_tables(area, p, rdepth, eprof)

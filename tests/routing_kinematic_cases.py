@@ -39,7 +39,9 @@ def snwcp(call):
 
 def networks(n, seed):
     """The network shapes at n cells: name -> down (all outlets, a chain, a chain running backwards, eight cells into one, a forest
-    along a random order of the cells)."""
+    along a random order of the cells, a binary tree and a tree of four children per cell).  The widths of their upstream maps
+    (rt.npad_of) are 1, 1, 1, 8, 4 or 8 by the seed, 2 and 4; the two trees draw nothing from the generator, and from 257 cells on
+    their upstream cells lie in another workgroup than the cell."""
     idx = np.arange(n)
     nets = {"outlets": np.full(n, -1, np.int32), "chain": np.append(idx[1:], -1).astype(np.int32), "reverse": (idx - 1).astype(np.int32)}
     if n >= 3:
@@ -60,7 +62,22 @@ def networks(n, seed):
                 d[perm[i]] = j
                 deg[j] += 1
         nets["forest"] = d
+        nets["binary"] = tree(n, 2)
+    if n >= 5:
+        nets["quad"] = tree(n, 4)
     return nets
+
+
+def tree(n, k):
+    """down of the complete k-ary tree rooted in cell 0: the cells that flow into cell i are k * i + 1 .. k * i + k."""
+    d = ((np.arange(n) - 1) // k).astype(np.int32)
+    d[0] = -1
+    return d
+
+
+def widths(nets):
+    """The padded widths of the shapes' upstream maps, as routing_enable's launch picks its kernel by them."""
+    return {rt.npad_of(rt.upstream_map(down)) for down in nets.values()}
 
 
 def cell_values(n, seed):

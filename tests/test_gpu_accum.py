@@ -12,7 +12,7 @@ from elmkernels_amd import restart as R
 from elmkernels_amd import state as st
 from tests import helpers as H
 from tests.run_cases import DT, NREC, NSTEPS, SERIES, _inputs, demo_records, device, schedule, stepwise, upload_series
-from tests.support import bits, build_demo, captured, run_demo, same, state_blob
+from tests.support import bits, build_demo, captured, run_demo, same, same_nan, state_blob
 
 pytestmark = pytest.mark.gpu
 
@@ -110,6 +110,228 @@ def test_update_equals_the_restatement(n, lib_path):
     assert D.device_bytes == before
     D.accum_update()  # nothing to do
     D.sync()
+    D.close()
+
+
+# ---- pair and workgroup ends, every stored type, period and count edges ----------------------------------------------------------------
+def _fold_and_compare(D, entries, val, dst, seen, counts, what):
+    """After one accum_update: every entry's value (whole, and the last column alone), count and destination against accum.update of
+    the samples `seen`, NaNs equal.  val, dst and counts are advanced in place."""
+    f32 = D.lib.elmk_state_real_bytes() == 4
+    last = D.ncols - 1
+    for i, (src, kind, period, d) in enumerate(entries):
+        counts[i] += 1
+        val[i] = accum.update(val[i], seen[src], kind, period, counts[i])
+        got, cnt = D.accum_read(i)
+        assert cnt == counts[i], (what, i)
+        assert same_nan(got, val[i]), (what, i, entries[i])
+        tail, cnt = D.accum_read(i, col0=last, n=1)
+        assert cnt == counts[i] and same_nan(tail, val[i][..., last:]), (what, i, entries[i], "the last column")
+        if d:
+            if accum.writes_destination(kind, period, counts[i]):
+                with np.errstate(all="ignore"):  # state precision: rounded to fp32 in the fp32-state build
+                    dst[d] = (val[i].astype(np.float32).astype(np.float64) if f32 else val[i]).T
+            assert same_nan(D[d], dst[d]), (what, i, entries[i], d)
+
+
+END_SIZES = [(n, None) for n in (2, 3, 511, 512, 513, 1025)] + [(n, L.F32_LIB_PATH) for n in (513, 1025)]
+end_sizes = pytest.mark.parametrize("ncols,lib_path", END_SIZES, ids=lambda v: "f32" if v == L.F32_LIB_PATH else "f64" if v is None else None)
+# the three kinds on every stored type: F64 with one level and with 20, I32, U8 and U32; every kind meets every period of 1, 2, 3, 50
+END_ENTRIES = [("t_grnd", accum.RUNMEAN, 3, "t10"), ("t_soisno", accum.RUNMEAN, 50, None), ("snl", accum.RUNMEAN, 2, None),
+               ("veg_active", accum.RUNMEAN, 1, None), ("err_flags", accum.RUNMEAN, 50, None),
+               ("t_grnd", accum.TIMEAVG, 50, None), ("t_soisno", accum.TIMEAVG, 2, "csol"), ("snl", accum.TIMEAVG, 1, None),
+               ("veg_active", accum.TIMEAVG, 3, "n_melt"), ("err_flags", accum.TIMEAVG, 2, None),
+               ("t_grnd", accum.RUNACCUM, 1, None), ("t_soisno", accum.RUNACCUM, 3, None), ("snl", accum.RUNACCUM, 50, None),
+               ("veg_active", accum.RUNACCUM, 2, None), ("err_flags", accum.RUNACCUM, 3, "micro_sigma")]
+END_SOURCES = ("t_grnd", "t_soisno", "snl", "veg_active", "err_flags")
+
+
+@end_sizes
+def test_pair_and_workgroup_ends(ncols, lib_path):
+    """k_accum_update takes two columns per thread and 512 per workgroup: a pair, a pair and a half, a workgroup less one column, a
+    workgroup (the level stride unpadded), a workgroup and one column, two and one.  Fifteen entries, seven updates from freshly
+    uploaded samples; after every one the value (whole and for the last column alone), the count and the destination against
+    accum.update of the samples as downloaded; in both builds at 513 and 1025."""
+    assert len(END_ENTRIES) == accum.MAX_ENTRIES - 1 and {e[0] for e in END_ENTRIES} == set(END_SOURCES)
+    for kind in (accum.RUNMEAN, accum.TIMEAVG, accum.RUNACCUM):
+        assert {e[2] for e in END_ENTRIES if e[1] == kind} == {1, 2, 3, 50} and {e[0] for e in END_ENTRIES if e[1] == kind} == set(END_SOURCES)
+    D = st.ELMState(ncols, lib_path=lib_path)
+    assert (D.level_stride == ncols) == (ncols == 512)
+    assert [D.accum_add(*e) for e in END_ENTRIES] == list(range(len(END_ENTRIES)))
+    nlev = D.fields["t_soisno"][1]
+    rng = np.random.default_rng(60 + ncols)
+    for d in ("t10", "csol", "n_melt", "micro_sigma"):
+        D[d] = rng.standard_normal(D[d].shape)  # what a destination holds until its entry writes it
+    dst = {e[3]: D[e[3]] for e in END_ENTRIES if e[3]}
+    val = [np.zeros((nlev, ncols)) if e[0] == "t_soisno" else np.zeros(ncols) for e in END_ENTRIES]
+    counts = [0] * len(END_ENTRIES)
+    for step in range(1, 8):
+        t = rng.standard_normal(ncols) * 300.0
+        t[step % ncols] = -99999.0  # RUNACCUM's reset, in a column that moves by one (either side of a pair) with every update
+        t[(step + 1) % ncols] = 30000.0 * step  # ... and its upper clamp in the column beside it
+        if step == 4:
+            t[-1] = np.nan  # the last column, the one read alone
+        D["t_grnd"] = t
+        D["t_soisno"] = rng.standard_normal((ncols, nlev)) * 300.0
+        D["snl"] = rng.integers(0, 6, ncols).astype(np.int32)
+        D["veg_active"] = rng.integers(0, 256, ncols).astype(np.uint8)
+        flags = rng.integers(0, 1 << 32, ncols, dtype=np.uint64).astype(np.uint32)
+        flags[-1] |= np.uint32(1 << 31)  # (the last column: above 2^31, widened as unsigned)
+        D["err_flags"] = flags
+        assert same(D["err_flags"], flags)
+        seen = {k: _soa(D[k]) for k in END_SOURCES}
+        D.accum_update()
+        _fold_and_compare(D, END_ENTRIES, val, dst, seen, counts, (ncols, step))
+        for k in END_SOURCES:  # the sources are only read
+            assert same_nan(_soa(D[k]), seen[k]), k
+    # the samples did what they were chosen for
+    assert val[4][-1] >= 2.0 ** 31 and val[9][-1] >= 2.0 ** 31  # U32 widened as unsigned (a running mean and a period's mean of the flags)
+    assert np.isnan(val[0][-1]) and np.isnan(val[5][-1]) and not np.isnan(val[10]).any()  # RUNACCUM: t > 0 ? t : 0 drops a NaN
+    assert (val[14] == accum.RUNACCUM_MAX).all() and (val[10] == 0.0).any() and (val[10] == accum.RUNACCUM_MAX).any()
+    assert counts == [7] * len(END_ENTRIES)
+    D.close()
+
+
+@end_sizes
+def test_seeding_past_one_workgroup(ncols, lib_path):
+    """k_accum_seed at the same sizes, on one row and on twenty: accum_init without values leaves val = the destination widened and
+    the count given; the next update folds into it."""
+    D = st.ELMState(ncols, lib_path=lib_path)
+    entries = [("t_grnd", accum.RUNMEAN, 4, "t10"), ("t_soisno", accum.RUNMEAN, 4, "csol")]
+    ids = [D.accum_add(*e) for e in entries]
+    nlev = D.fields["t_soisno"][1]
+    rng = np.random.default_rng(70 + ncols)
+    D["t10"] = 280.0 + 15.0 * rng.standard_normal(ncols)
+    D["csol"] = 2.0e6 * (1.0 + rng.random((ncols, nlev)))
+    D["t_grnd"] = 270.0 + 10.0 * rng.standard_normal(ncols)
+    D["t_soisno"] = 270.0 + 10.0 * rng.standard_normal((ncols, nlev))
+    dst = {"t10": D["t10"], "csol": D["csol"]}
+    val, counts = [None, None], [0, 0]
+    for i, (e, k) in enumerate(zip(ids, (9, 2))):
+        D.accum_init(e, None, k)
+        val[i], counts[i] = _soa(dst[entries[i][3]]), k
+        got, cnt = D.accum_read(e)
+        assert cnt == k and same_nan(got, val[i]) and got.any(), (ncols, e)
+        tail, _ = D.accum_read(e, col0=ncols - 1, n=1)
+        assert same_nan(tail, val[i][..., ncols - 1:]), (ncols, e)
+    assert same_nan(D["t10"], dst["t10"]) and same_nan(D["csol"], dst["csol"])  # seeding reads the destination
+    D.accum_update()
+    _fold_and_compare(D, entries, val, dst, {k: _soa(D[k]) for k in ("t_grnd", "t_soisno")}, counts, (ncols, "after seeding"))
+    assert counts == [10, 3]
+    D.close()
+
+
+RESET_SAMPLES = (-99999.0, -99999.49, -99998.51, -99999.5, -99998.5, 2.0, 1.0e6)
+
+
+@pytest.mark.parametrize("lib_path", [None, L.F32_LIB_PATH], ids=["f64", "f32"])
+def test_runaccum_resets_by_the_rounded_sample(lib_path):
+    """RUNACCUM resets where rint(v) == -99999: -99999, -99999.49 and -99998.51 reset; the ties -99999.5 and -99998.5 round to the even
+    neighbours -100000 and -99998 and do not.  Seven samples over fourteen columns, so that each stands in an even and in an odd
+    column of a pair; an I32 source holds -99999 itself.  By value from a value at the upper clamp, and against accum.update."""
+    n = 2 * len(RESET_SAMPLES)
+    D = st.ELMState(n, lib_path=lib_path)
+    entries = [("t_ref2m", accum.RUNACCUM, 4, "micro_sigma"), ("altmax_indx", accum.RUNACCUM, 4, None)]
+    for e in entries:
+        D.accum_add(*e)
+    v = np.array(RESET_SAMPLES)[np.arange(n) % len(RESET_SAMPLES)]
+    k = np.array([-99999, -99998, -100000, 7, -99999, 0, 100000], np.int32)[np.arange(n) % 7]
+    assert all({int(c) % 2 for c in np.nonzero(v == s)[0]} == {0, 1} for s in RESET_SAMPLES)
+    val, dst, counts = [np.zeros(n), np.zeros(n)], {"micro_sigma": D["micro_sigma"]}, [0, 0]
+    for step, (t, a) in enumerate(((np.full(n, 1.0e6), np.full(n, 100000, np.int32)), (v, k), (v[::-1].copy(), k[::-1].copy()))):
+        D["t_ref2m"], D["altmax_indx"] = t, a
+        seen = {"t_ref2m": _soa(D["t_ref2m"]), "altmax_indx": _soa(D["altmax_indx"])}
+        if step == 1:  # as stored: the fp32-state build keeps the three inexact samples on their side of the ties
+            assert (np.rint(seen["t_ref2m"]) == np.rint(v)).all() and (seen["t_ref2m"][v % 0.5 == 0.0] == v[v % 0.5 == 0.0]).all()
+        D.accum_update()
+        _fold_and_compare(D, entries, val, dst, seen, counts, step)
+        if step == 0:
+            assert (val[0] == accum.RUNACCUM_MAX).all() and (val[1] == accum.RUNACCUM_MAX).all()
+        if step == 1:
+            reset = np.isin(v, (-99999.0, -99999.49, -99998.51))
+            assert (val[0][reset] == 0.0).all() and not np.signbit(val[0][reset]).any()
+            assert (val[0][v == -99998.5] == 0.5).all()  # not reset: 99999 - 99998.5
+            assert (val[0][v == -99999.5] == 0.0).all()  # not reset either, but 99999 - 99999.5 < 0 is clamped to the same +0.0
+            assert (val[0][v >= 2.0] == accum.RUNACCUM_MAX).all()
+            assert (val[1][k == -99999] == 0.0).all() and (val[1][k == -99998] == 1.0).all() and (val[1][k == -100000] == 0.0).all()
+            assert (val[1][k == 7] == accum.RUNACCUM_MAX).all()
+    D.close()
+
+
+def test_counts_and_periods_above_2_to_the_32():
+    """AccumRow.period and the counts are 64-bit: a running mean whose window of 2^33 + 5 steps is not full after 2^33, a period average
+    whose period of 2^33 steps ends with the next update (it divides by 2^33 and writes the destination) and starts anew with the one
+    after; two updates against accum.update, then an image into a fresh context with the same table keeps periods, counts and values."""
+    n, P0, P1 = 193, 2 ** 33 + 5, 2 ** 33
+    entries = [("t_ref2m", accum.RUNMEAN, P0, "n_melt"), ("t_grnd", accum.TIMEAVG, P1, "t10")]
+    rng = np.random.default_rng(91)
+    seed = [280.0 + 15.0 * rng.standard_normal(n), (2.0 ** 33 - 1.0) * (270.0 + 10.0 * rng.standard_normal(n))]
+    D = st.ELMState(n)
+    ids = [D.accum_add(*e) for e in entries]
+    D.accum_init(ids[0], seed[0], 2 ** 33)
+    D.accum_init(ids[1], seed[1], 2 ** 33 - 1)
+    val, counts = [seed[0].copy(), seed[1].copy()], [2 ** 33, 2 ** 33 - 1]
+    assert [D.accum_read(e)[1] for e in ids] == counts
+    dst = {"n_melt": D["n_melt"], "t10": D["t10"]}
+    for step in range(2):
+        D["t_ref2m"] = 280.0 + 15.0 * rng.standard_normal(n)
+        D["t_grnd"] = 270.0 + 10.0 * rng.standard_normal(n)
+        seen = {k: _soa(D[k]) for k in ("t_ref2m", "t_grnd")}
+        D.accum_update()
+        _fold_and_compare(D, entries, val, dst, seen, counts, step)
+        if step == 0:  # the period's end: the mean of 2^33 samples of about 270 K, written to t10
+            assert accum.writes_destination(accum.TIMEAVG, P1, counts[1]) and (np.abs(val[1] - 270.0) < 60.0).all() and same_nan(D["t10"], val[1])
+            assert not same_nan(val[0], accum.update(seed[0], seen["t_ref2m"], accum.RUNMEAN, P0 % 2 ** 32, 1))  # (what 32-bit words would give)
+        else:  # the first update of the next period: the sample itself
+            assert same_nan(val[1], seen["t_grnd"]) and not same_nan(D["t10"], val[1])
+    assert counts == [2 ** 33 + 2, 2 ** 33 + 1]
+    img = D.restart_save()
+    p = R.verify(img)
+    assert [int(x) for x in p["accum"]["period"]] == [P0, P1] and [int(x) for x in p["accum"]["nsteps"]] == counts
+    F = st.ELMState(n)
+    for e in entries:
+        F.accum_add(*e)
+    F.restart_load(img)
+    for i in ids:
+        got, cnt = F.accum_read(i)
+        assert cnt == counts[i] and same_nan(got, val[i]), i
+    assert same_nan(F["t10"], D["t10"]) and same_nan(F["n_melt"], D["n_melt"])
+    for X in (D, F):  # ... and both go on alike
+        X["t_ref2m"], X["t_grnd"] = seen["t_ref2m"][::-1].copy(), seen["t_grnd"][::-1].copy()
+        X.accum_update()
+    for i in ids:
+        assert F.accum_read(i)[1] == D.accum_read(i)[1] == counts[i] + 1 and same_nan(F.accum_read(i)[0], D.accum_read(i)[0])
+    D.close()
+    F.close()
+
+
+def test_a_period_of_one_step():
+    """P = 1 in every kind, four updates with a NaN and an infinite sample: RUNMEAN is (0.0 * val + v) / 1.0, so a NaN or infinite val
+    stays NaN; TIMEAVG zeroes, adds, divides by 1.0 and writes the destination on every update; RUNACCUM does not read its period."""
+    n = 193
+    D = st.ELMState(n)
+    entries = [("t_ref2m", accum.RUNMEAN, 1, "t10"), ("t_ref2m", accum.TIMEAVG, 1, "n_melt"), ("t_ref2m", accum.RUNACCUM, 1, "micro_sigma")]
+    for e in entries:
+        D.accum_add(*e)
+    c = np.arange(n) % 4
+    rng = np.random.default_rng(93)
+    val, counts = [np.zeros(n) for _ in entries], [0] * 3
+    dst = {e[3]: D[e[3]] for e in entries}
+    for step in range(1, 5):
+        t = 280.0 + 15.0 * rng.standard_normal(n)
+        if step == 2:
+            t[c == 1], t[c == 2], t[c == 3] = np.nan, np.inf, -0.0
+        D["t_ref2m"] = t
+        D.accum_update()
+        _fold_and_compare(D, entries, val, dst, {"t_ref2m": _soa(D["t_ref2m"])}, counts, step)
+        assert all(accum.writes_destination(e[1], 1, step) for e in entries)
+        finite = np.isfinite(t)
+        assert same_nan(val[1][finite & ~np.signbit(t)], t[finite & ~np.signbit(t)]) and same_nan(D["n_melt"], val[1])  # the sample itself
+        if step == 2:
+            assert np.isnan(val[0][c == 1]).all() and (val[0][c == 2] == np.inf).all() and (val[1][c == 2] == np.inf).all()
+            assert (val[1][c == 3] == 0.0).all() and not np.signbit(val[1][c == 3]).any()  # +0.0 + -0.0
+        if step >= 3:  # 0.0 * NaN and 0.0 * inf are NaN: the running mean never recovers; the period average does
+            assert np.isnan(val[0][(c == 1) | (c == 2)]).all() and np.isfinite(val[0][(c == 0) | (c == 3)]).all() and np.isfinite(val[1]).all()
     D.close()
 
 

@@ -23,13 +23,25 @@ CALLS = [(11, 0, 0.3, 0.7), (4, 4, 0.25, 0.75), (0, 1, 1.0, 0.0), (6, 7, 0.0, 1.
 
 
 def make_map(kind, n, ncells=NCELLS, seed=5):
-    """"col": per-column series; "n1": one term per column with a weight that is not 1; "n3": three rows with -1 padding in rows 1
-    and 2 (the library pads them to four)."""
+    """"col": per-column series (NPTS 0); "n1": one term per column with a weight that is not 1; "n3": three rows with -1 padding in
+    rows 1 and 2 (the library pads them to four); "n2": two rows, row 1 padding in about 40 % of the columns; "n5": five rows with
+    padding in rows 1 .. 4 (padded to eight); "n8": eight rows, full in most columns.  In all of them column 0 has padding in every
+    row but the first and column 3 has none, and the weights are no partition of one."""
     if kind == "col":
         return n, None, None
     rng = np.random.default_rng(seed)
     if kind == "n1":
         return ncells, rng.integers(0, ncells, (1, n)).astype(np.int32), rng.random((1, n)) + 0.5
+    if kind in ("n2", "n5", "n8"):
+        npts = int(kind[1:])
+        idx = rng.integers(0, ncells, (npts, n)).astype(np.int32)
+        w = rng.random((npts, n)) + 0.1
+        for k in range(1, npts):
+            idx[k, rng.random(n) < (0.1 if kind == "n8" else 0.4)] = -1
+        idx[1:, 0] = -1
+        if n > 3:
+            idx[1:, 3] = (2 + 3 * np.arange(npts - 1)) % ncells
+        return ncells, idx, w
     idx = rng.integers(0, ncells, (3, n)).astype(np.int32)
     w = rng.random((3, n)) + 0.1
     idx[1, rng.random(n) < 0.4] = -1
@@ -66,13 +78,23 @@ def stored(D, a):
 
 
 # ---- 1. the kernel equals the restatement ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("lib_path", [None, L.F32_LIB_PATH], ids=["fp64", "fp32state"])
-@pytest.mark.parametrize("kind", ["col", "n1", "n3"])
-@pytest.mark.parametrize("n", [1, N])
+KINDS = ("col", "n1", "n2", "n3", "n5", "n8")  # NPTS 0, 1, 2, 4, 8, 8
+# one thread per column, 256 per workgroup: one column, 193, a workgroup and one column in every width and both builds; the widths at
+# the ends, 0 and 8, also at one whole workgroup (the level stride unpadded) and at three with a partial last wave
+KERNEL_CASES = ([(n, k, p) for p in (None, L.F32_LIB_PATH) for k in KINDS for n in (1, N, 257)] +
+                [(n, k, None) for k in ("col", "n8") for n in (256, 600)])
+
+
+@pytest.mark.parametrize("n,kind,lib_path", KERNEL_CASES, ids=[f"{n}-{k}-{'fp32state' if p else 'fp64'}" for n, k, p in KERNEL_CASES])
 def test_kernel_equals_the_restatement(n, kind, lib_path):
+    """The stepwise call against aerosol.interpolate after every deposition, and what it must not touch: every other field.  (No read
+    that the wrapper offers reaches a row's padding past ncols.)"""
     cols, scal, soil, lat, lon, _ = _inputs(n, SEED)
     D = H.device_state(cols, scal, soil, lat=lat, lon=lon, lib_path=lib_path)
+    assert (D.level_stride == n) == (n == 256) and D.level_stride >= n
     ncells, idx, w = make_map(kind, n)
+    if idx is not None and n > 3:
+        assert (idx[1:, 0] == -1).all() and (idx[:, 3] >= 0).all()
     series = aerosol.synthetic_climatology(ncells, seed=3)
     for s in aerosol.STREAMS:
         series[s][8:11] = 0.0  # months 8 .. 10 are never uploaded: they read as zero
@@ -218,6 +240,54 @@ def test_run_equals_stepwise(base, mapped, flagged):
     assert (differs & snow).any()
     assert not same(got_state["aer_dst1_1"], Cx["aer_dst1_1"])
     Cx.close()
+
+
+# ---- 2b. the run form at every width: k_aerosol_deposition<NPTS, true> ---------------------------------------------------------------
+NW, WIDE_STEPS = 257, 4  # a workgroup and one column; four steps of the (11, 0) bracket, each with weights of its own
+
+
+@pytest.fixture(scope="module")
+def wide():
+    return _inputs(NW, SEED)
+
+
+@pytest.fixture(scope="module")
+def wide_unflagged(wide):
+    """The same steps without the flag (and without a series): every field but the series inputs."""
+    U = run_context(wide, None, False)
+    U.run(DT, schedule()[:WIDE_STEPS])
+    out = state_of(U)
+    U.close()
+    return out
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["nograph", "graph"])
+@pytest.mark.parametrize("kind", ["n1", "n2", "n8"])
+def test_run_deposits_the_last_steps_bracket_at_every_width(wide, wide_unflagged, kind, graph):
+    """No kernel of the step writes the eleven aer_* fields (class SURFACE), so after a flagged run they hold what the run's form of
+    the kernel wrote in the last step: aerosol.interpolate of that step's row of the schedule, at state precision.  test_run_equals_
+    stepwise has the width 4 (and test_history_accum_and_aerosol_flags_together no other)."""
+    ncells, idx, w = make_map(kind, NW)
+    series = aerosol.synthetic_climatology(ncells, seed=13)
+    steps = schedule()[:WIDE_STEPS]
+    last = steps[-1]
+    assert (int(last["month1"]), int(last["month2"])) == (11, 0) and 0.0 < float(last["month_wt1"]) < float(last["month_wt2"]) < 1.0
+    assert len({float(p["month_wt1"]) for p in steps}) == WIDE_STEPS  # (an earlier step's row would give other numbers)
+    assert all(st.field_class(f) == st.CLASS_SURFACE for f in AER)
+    D = run_context(wide, (ncells, idx, w, series), graph)
+    D.run(DT, steps, st.RUN_AEROSOL)
+    want = aerosol.interpolate(series, last["month1"], last["month2"], last["month_wt1"], last["month_wt2"], idx, w)
+    earlier = aerosol.interpolate(series, steps[-2]["month1"], steps[-2]["month2"], steps[-2]["month_wt1"], steps[-2]["month_wt2"], idx, w)
+    got = state_of(D)
+    for s in aerosol.STREAMS:
+        assert same(got["aer_" + s], stored(D, want[s])), (kind, graph, s)
+    D.close()
+    assert not same(want["dst1_1"], earlier["dst1_1"]) and want["dst1_1"].any()
+    # the run differed from the run without the flag: there aer_* stay what was uploaded
+    cols = wide[0]
+    for f in AER:
+        assert same(wide_unflagged[f], np.ascontiguousarray(cols[f], dtype=np.float64)), f
+        assert not same(got[f], wide_unflagged[f]), f
 
 
 # ---- 3. against a second device path --------------------------------------------------------------------------------------------------

@@ -81,9 +81,10 @@ def test_ten_chained_calls_equal_the_restatement(base, ncells, lib_path):
     bytes0 = D.device_bytes
     qs = [set_runoff(D, runoff(c, lib_path)) for c in range(3)]  # (three runoff rows serve the ten calls in turn)
     assert ncells < 8 or (qs[0][5] < 0.0 and np.isnan(qs[0][9]))
-    seen = set()
+    seen, widths = set(), set()
     for name, down in networks(ncells, 50 + ncells).items():
         up = rt.upstream_map(down)
+        widths.add(rt.npad_of(up))  # the NPAD the launch picks its kernel by
         for nsub, dt in ((n_, d_) for n_ in NSUBS for d_ in DTS):
             seen.add((nsub, dt))
             D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
@@ -113,6 +114,8 @@ def test_ten_chained_calls_equal_the_restatement(base, ncells, lib_path):
             D.routing_clear()
             assert D.device_bytes == bytes0
     assert seen == {(n, d) for n in NSUBS for d in DTS}
+    if ncells >= 63:
+        assert widths == {1, 2, 4, 8}, widths  # every instantiation with_npad can pick
     D.close()
 
 

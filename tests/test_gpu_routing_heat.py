@@ -58,7 +58,7 @@ _ctx = functools.partial(rv.context, cell_map=hc.heat_map)
 @pytest.mark.parametrize("withdraw", [False, True], ids=["nowithdrawal", "withdrawal"])
 @pytest.mark.parametrize("ncells", [1, 64, 65, 257, 1001])
 def test_five_chained_calls_equal_the_restatement(base, ncells, withdraw, lib_path):
-    """Per network shape (all five at 1001 cells, the forest below) and (nsub, dt) with nsub 1, 2 and 5: the scheme and the heat, init with
+    """Per network shape (all seven at 1001 cells, the forest below) and (nsub, dt) with nsub 1, 2 and 5: the scheme and the heat, init with
     the edge values, five calls with a new runoff row and new column fields before each; after every call all fourteen rows against
     routing.kinematic_call(heat=...) on what the device held before it, bit for bit.  At 1001 cells every branch of H1 - H5 is asserted
     on the restatement in every call of the forest's (5, 3600 s) case."""
@@ -75,8 +75,10 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, withdraw, lib_pa
     nets = hc.networks(ncells, 52 + ncells)
     if ncells != 1001:
         nets = {k: nets[k] for k in (("forest",) if ncells >= 3 else ("outlets",))}
+    widths = set()
     for name, down in nets.items():
         up = rt.upstream_map(down)
+        widths.add(rt.npad_of(up))  # the NPAD the launch picks its kernel by
         for nsub, dt in hc.CASES:
             bytes1 = None
             D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
@@ -113,6 +115,8 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, withdraw, lib_pa
                 assert D.routing_count() == c + 1
             D.routing_clear()  # frees everything
             assert D.device_bytes == bytes0
+    if ncells == 1001:  # (where every shape runs)
+        assert widths == {1, 2, 4, 8}, widths  # every instantiation with_npad can pick
     D.close()
 
 

@@ -66,12 +66,13 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
     qs = [set_runoff(D, ic.snwcp(c)) for c in range(3)]  # (three runoff rows serve the five calls in turn)
     hosts = [host_inputs(D, q, area) for q in qs]
     cld = (ncells + 63) // 64 * 64
-    union = np.zeros(len(ic.PATHS), bool)
+    union, widths = np.zeros(len(ic.PATHS), bool), set()
     lo, hi = ic.WINDOW[0], min(ncells, ic.WINDOW[1])
     for name, down in ic.networks(ncells, 52 + ncells).items():
         up = rt.upstream_map(down)
+        widths.add(rt.npad_of(up))  # the NPAD the launch picks its kernel by
         for nsub, dt in ic.CASES:
-            rdepth, eprof, p, volr, wh, wt, wf = ic.flood_values(ncells, 60 + ncells, area, p0, volr0, wh0, wt0, nsub, dt)
+            rdepth, eprof, p, volr, wh, wt, wf = ic.flood_values(ncells, 60 + ncells, area, p0, volr0, wh0, wt0, nsub, dt, rbank=1.0e6)
             tab = rt.inundation_tables(area, p, rdepth, eprof)
             D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
             D.routing_kinematic_enable(p)
@@ -106,6 +107,7 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
             assert D.device_bytes == bytes0
     if ncells >= 63:
         assert union.all(), [ic.PATHS[i] for i in np.nonzero(~union)[0]]
+        assert widths == {1, 2, 4, 8}, widths  # every instantiation with_npad can pick
     D.close()
 
 

@@ -51,10 +51,11 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
     qs = [set_runoff(D, snwcp(c)) for c in range(3)]  # (three runoff rows serve the five calls in turn)
     hosts = [host_inputs(D, q, area) for q in qs]
     assert ncells < 8 or (qs[0][5] < 0.0 and np.isnan(qs[0][9]))
-    seen, qsur_nonzero, qsub_negative = set(), False, False
+    seen, widths, qsur_nonzero, qsub_negative = set(), set(), False, False
     cld = (ncells + 63) // 64 * 64
     for name, down in networks(ncells, 50 + ncells).items():
         up = rt.upstream_map(down)
+        widths.add(rt.npad_of(up))  # the NPAD the launch picks its kernel by
         for nsub, dt in CASES:
             D.routing_enable(down, ddist, area, rt.EFFVEL, nsub)
             bytes1 = D.device_bytes
@@ -87,6 +88,7 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, lib_path):
     if ncells >= 63:
         assert seen == {(f, k) for f in ("eh", "et", "er") for k in ("capped", "uncapped")}, seen
         assert qsur_nonzero and qsub_negative
+        assert widths == {1, 2, 4, 8}, widths  # every instantiation with_npad can pick
     D.close()
 
 

@@ -66,9 +66,10 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, flood, withdraw,
     qs = [set_runoff(D, ic.snwcp(c)) for c in range(3)]  # (three runoff rows serve the five calls in turn)
     hosts = [host_inputs(D, q, area) for q in qs]
     cld = (ncells + 63) // 64 * 64
-    rows = rows_of(flood)
+    rows, widths = rows_of(flood), set()
     for name, down in ic.networks(ncells, 52 + ncells).items():
         up = rt.upstream_map(down)
+        widths.add(rt.npad_of(up))  # the NPAD the launch picks its kernel by
         for nsub, dt in ic.CASES:
             rdepth, eprof, p, volr, wh, wt, wf = ic.flood_values(ncells, 60 + ncells, area, p0, volr0, wh0, wt0, nsub, dt)
             ftab = rt.inundation_tables(area, p, rdepth, eprof) if flood else None
@@ -122,6 +123,8 @@ def test_five_chained_calls_equal_the_restatement(base, ncells, flood, withdraw,
                 assert (take[tab["DAM"]] > 0.0).any() and not take[~tab["DAM"]].any()
             D.routing_clear()  # frees everything
             assert D.device_bytes == bytes0
+    if ncells >= 63:
+        assert widths == {1, 2, 4, 8}, widths  # every instantiation with_npad can pick
     D.close()
 
 
