@@ -173,6 +173,10 @@ SIGNATURES = {
     "elmk_routing_heat_init": (C.c_int, [_P, _P, _P]),
     "elmk_routing_heat_budget": (C.c_int, [_P, _P]),
     "elmk_routing_heat_clear": (C.c_int, [_P]),
+    "elmk_floodplain_infiltration_enable": (C.c_int, [_P]),
+    "elmk_floodplain_infiltration_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_floodplain_infiltration_budget": (C.c_int, [_P, _P]),
+    "elmk_floodplain_infiltration_clear": (C.c_int, [_P]),
     "elmk_column_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_gridded_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_cell_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),

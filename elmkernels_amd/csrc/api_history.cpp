@@ -271,6 +271,7 @@ int elmk_set_output_grid(elmk_ctx* ctx, int64_t ncells, const int64_t* ptr, cons
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_set_output_grid: gridded history entries exist (elmk_history_clear first)");
   if (int rc = cellrows_hold(ctx, "elmk_set_output_grid")) return rc;  // (ncells is the grid's)
   if (int rc = irrsup_holds(ctx, "elmk_set_output_grid")) return rc;
+  if (int rc = land_holds(ctx, "elmk_set_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_set_output_grid")) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));  // (a gridded download may still read the old map)
   elmk_ctx::OGrid& O = ctx->ogrid;
@@ -290,6 +291,7 @@ int elmk_clear_output_grid(elmk_ctx* ctx)
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_clear_output_grid: gridded history entries exist (elmk_history_clear first)");
   if (int rc = cellrows_hold(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = irrsup_holds(ctx, "elmk_clear_output_grid")) return rc;
+  if (int rc = land_holds(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_clear_output_grid")) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->ogrid = elmk_ctx::OGrid{};

@@ -1,5 +1,5 @@
 // api_routing.cpp - the river stage (k_routing.hip; include/elmk.h "runoff routing", "kinematic-wave routing", "floodplain inundation",
-// "reservoirs", "stream temperature").  The stage has five parts, each with one allocation held exactly while the part is on (elmk_ctx.h: Routing): the
+// "reservoirs", "stream temperature", "floodplain infiltration").  The stage has six parts, each with one allocation held exactly while the part is on (elmk_ctx.h: Routing): the
 // base part, the kinematic-wave scheme on top of it, and that scheme's three extensions.  The table PARTS describes each part once - its
 // rows, its public row ids, what its budget reduces, what the restart image keeps of it, what it needs and how its refusals read - and
 // the part_* helpers below are what the five families of entry points share: how a call enters, how an enable, an init, a budget and a
@@ -9,7 +9,7 @@
 namespace {
 using Routing = elmk_ctx::Routing;
 
-enum { BASE, KW, FP, DAM, HEAT, NPARTS };
+enum { BASE, KW, FP, DAM, HEAT, LAND, NPARTS };
 struct PartDesc {
   Routing::Part Routing::*at;  // where the part is held (null: the base part, in Routing itself)
   int needs;                   // the part that has to be on before this one (-1: none)
@@ -41,7 +41,11 @@ constexpr PartDesc PARTS[NPARTS] = {
     // (the stream temperature's kernel is the scheme's; it excludes the two extensions before it: heat_excludes)
     {&Routing::heat, KW, HT_NROWS, ELMK_ROUTE_TT, 7, {HT_TT, HT_TR, HT_HEAT, HT_HIN, HT_HSRF, HT_HADJ, HT_HOUT}, 5, 2, {ELMK_ROUTE_TT, ELMK_ROUTE_TR},
      "stream temperature", "elmk_routing_heat_enable", "elmk_routing_heat_clear", "the extension is not on", "row out of range",
-     "the stream temperature is on"}};
+     "the stream temperature is on"},
+    // (the floodplain infiltration: its cell row QLAND; the three column rows and cellof lie behind it in the same allocation)
+    // (F1 reads FLOOD_FRAC as the last call left it, so with the extension on the image keeps that row as well: state)
+    {&Routing::land, FP, 1, ELMK_ROUTE_QLAND, 1, {0}, 1, 1, {ELMK_ROUTE_FLOOD_FRAC}, "floodplain infiltration", "elmk_floodplain_infiltration_enable",
+     "elmk_floodplain_infiltration_clear", "the extension is not on", "row out of range", "the floodplain infiltration is on"}};
 static_assert(ELMK_ROUTE_VOLR == 0 && ELMK_ROUTE_QIN == 1 && ELMK_ROUTE_QOUT == 2 && ELMK_ROUTE_QOUT_SUM == 3, "four rows");
 static_assert(ELMK_ROUTE_WH - 4 == KW_WH && ELMK_ROUTE_WT - 4 == KW_WT && ELMK_ROUTE_QSUR - 4 == KW_QSUR, "three rows");
 static_assert(ELMK_KW_NPARAM == KINEMATIC_NPARAM, "the parameter rows of elmk_maps.h");
@@ -51,8 +55,8 @@ static_assert(ELMK_ROUTE_RES == 10 && ELMK_ROUTE_KRLS == 11 && ELMK_ROUTE_RES_TA
 static_assert(DAM_NTAB == RESERVOIR_NTAB && DAM_TARGET + RESERVOIR_NMONTH == DAM_NTAB, "the tables of elmk_maps.h");
 static_assert(ELMK_ROUTE_TT == 13 && ELMK_ROUTE_HOUT == 19 && HT_HEAT == 0 && HT_HIN == 1 && HT_HSRF == 2 && HT_HADJ == 3 && HT_OUTLET == 4, "seven rows; H7's five lead");
 static_assert(HEAT_NSUBLEV == 15, "the soil layers of elmk_maps.h");
-// (the heat excludes the inundation and the reservoirs, so the image never holds more than the first four parts' rows)
-static_assert(PARTS[0].nstate + PARTS[1].nstate + PARTS[2].nstate + PARTS[3].nstate == elmk::ROUTE_STATE_MAX &&
+// (the heat excludes the inundation and the reservoirs, so the image never holds more than the rows of the first four parts and the last)
+static_assert(PARTS[0].nstate + PARTS[1].nstate + PARTS[2].nstate + PARTS[3].nstate + PARTS[5].nstate == elmk::ROUTE_STATE_MAX &&
                   PARTS[0].nstate + PARTS[1].nstate + PARTS[4].nstate <= elmk::ROUTE_STATE_MAX, "the rows of the image");
 
 const DevBuf<char>& part_mem(const Routing& T, const PartDesc& P) { return P.at ? (T.*P.at).mem : T.mem; }
@@ -78,6 +82,7 @@ void part_reset(Routing& T, int p)
   else T.*PARTS[p].at = Routing::Part{};
   if (p == DAM) T.dam_mstart = nullptr, T.dam_time = 0;
   if (p == HEAT) T.heat_sublev = 0;
+  if (p == LAND) T.land_cellof = nullptr;
 }
 
 // the heat and the scheme's two other extensions exclude each other: "<who>: <on> (<clear> first)" while part q is on
@@ -214,7 +219,7 @@ void route_launch(elmk_ctx* ctx, double dt, bool run)
                              DamArgs{T.dam.rows, T.dam.tab, T.dam_mstart, run ? ctx->run.table : nullptr, run ? ctx->run.cursor : nullptr,
                                      T.dam_time},
                              H, G, qrunoff, qirr, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
-                             ctx->stream);
+                             ctx->stream, LandArgs{T.land.mem ? T.land.tab + (size_t)ELMK_FPI_QFLX_DRAIN * ld : nullptr, T.land.rows});
   } else {
     launch_routing(route_args(ctx), G, qrunoff, qirr, dt, ctx->stream);
   }
@@ -228,6 +233,11 @@ const double* route_row(const elmk_ctx* ctx, int which, const char** why)
     if (which >= P.id0 && which < P.id0 + P.nids)
       return part_mem(T, P) ? part_rows(T, P) + (size_t)P.row_of[which - P.id0] * (size_t)T.cld : (*why = P.row_off, nullptr);
   return *why = "row out of range", nullptr;
+}
+
+int land_holds(elmk_ctx* ctx, const char* who)
+{
+  return ctx->route.land.mem ? part_excludes(ctx, LAND, who) : ELMK_OK;
 }
 
 int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal)
@@ -560,5 +570,63 @@ int elmk_routing_heat_init(elmk_ctx* ctx, const double* tt, const double* tr)
 int elmk_routing_heat_budget(elmk_ctx* ctx, double* sums) { return part_budget(ctx, HEAT, "elmk_routing_heat_budget", sums); }
 
 int elmk_routing_heat_clear(elmk_ctx* ctx) { return part_clear(ctx, HEAT, "elmk_routing_heat_clear"); }
+
+int elmk_floodplain_infiltration_enable(elmk_ctx* ctx)
+{
+  const char* who = "elmk_floodplain_infiltration_enable";
+  if (int rc = enter(ctx)) return rc;
+  if (!ctx->hyd_rows) return invalid(ctx, "elmk_floodplain_infiltration_enable: the soil hydrology is not enabled (elmk_soil_hydrology_enable)");
+  if (!ctx->wb_rows) return invalid(ctx, "elmk_floodplain_infiltration_enable: the water balance is not enabled (elmk_water_balance_enable)");
+  if (int rc = part_enter(ctx, FP, who)) return rc;  // (the routing, its kinematic-wave scheme, the inundation: each refusal says which)
+  Routing& T = ctx->route;
+  if (T.land.mem) return invalid(ctx, "elmk_floodplain_infiltration_enable: already on");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  // F0: the context keeps no host copy of the output grid's map, so from a download of its ptr and col
+  const CsrMap& M = ctx->ogrid.map;
+  std::vector<int64_t> ptr((size_t)M.nrows + 1);
+  std::vector<int32_t> col((size_t)M.nnz), cellof;
+  HIPCHK(hipMemcpyAsync(ptr.data(), M.ptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (M.nnz > 0) HIPCHK(hipMemcpyAsync(col.data(), M.col, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (const int64_t shared = csr_cellof(M.nrows, ctx->ncols, ptr.data(), col.data(), &cellof); shared != -1)
+    return invalid(ctx, (std::string(who) + ": column " + std::to_string(shared) +
+                         " is in more than one cell of the output grid (or twice in one)").c_str());
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the forms of its moment)
+  const size_t cld = (size_t)T.cld, ld = (size_t)ctx->ld;
+  return part_on(
+      ctx, LAND,
+      [&](Carve& L) {
+        L.take(T.land.rows, cld * sizeof(double));
+        L.take(T.land.tab, (size_t)ELMK_FPI_NROWS * ld * sizeof(double));
+        L.take(T.land_cellof, ld * sizeof(int32_t));
+      },
+      [&] {  // the padding columns of cellof -1, then the map's
+        return hip_fail(ctx, hipMemsetAsync(T.land_cellof, 0xFF, ld * sizeof(int32_t), ctx->stream), "hipMemset(floodplain infiltration cellof)") ||
+               (!cellof.empty() && upload(ctx, T.land_cellof, cellof.data(), cellof.size(), "hipMemcpy(floodplain infiltration cellof)"));
+      });
+}
+
+int elmk_floodplain_infiltration_read(elmk_ctx* ctx, int which, double* host, int64_t col0, int64_t n)
+{
+  const char* who = "elmk_floodplain_infiltration_read";
+  if (int rc = part_enter(ctx, LAND, who)) return rc;
+  if (which < 0 || which >= ELMK_FPI_NROWS) return invalid(ctx, "elmk_floodplain_infiltration_read: unknown row");
+  if (int rc = check_range(ctx, who, host, col0, n, ctx->ncols)) return rc;
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  if (n > 0)
+    HIPCHK(hipMemcpyAsync(host, ctx->route.land.tab + (size_t)which * (size_t)ctx->ld + (size_t)col0, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return synced(ctx);
+}
+
+int elmk_floodplain_infiltration_budget(elmk_ctx* ctx, double* sums) { return part_budget(ctx, LAND, "elmk_floodplain_infiltration_budget", sums); }
+
+int elmk_floodplain_infiltration_clear(elmk_ctx* ctx)
+{
+  const char* who = "elmk_floodplain_infiltration_clear";
+  if (int rc = enter(ctx)) return rc;
+  if (ctx->route.land.mem && hist_has_family(ctx, ELMK_ROWS_FLOODPLAIN))
+    return invalid(ctx, "elmk_floodplain_infiltration_clear: history entries over the floodplain infiltration rows exist (elmk_history_clear first)");
+  return part_clear(ctx, LAND, who);
+}
 
 }  // extern "C"

@@ -108,7 +108,15 @@ ActiveLayerArgs alt_args(const elmk_ctx* ctx)
 bool hyd_land(const elmk_ctx* ctx) { return ctx->h.land.ltype == istsoil || ctx->h.land.ltype == istcrop; }
 void hyd_launch(elmk_ctx* ctx, double dt)
 {
-  if (hyd_land(ctx)) launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, ctx->hydf_rows, dt, ctx->stream);
+  if (!hyd_land(ctx)) return;
+  const elmk_ctx::Routing& T = ctx->route;
+  if (T.land.mem) {  // the ROF form exactly while the floodplain infiltration is on
+    const size_t cld = (size_t)T.cld;
+    const RofArgs rof{T.land_cellof, T.fp.rows + FP_WF * cld, T.fp.rows + FP_FRAC * cld, T.area, T.land.tab};
+    launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, ctx->hydf_rows, dt, ctx->stream, &rof);
+  } else {
+    launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, ctx->hydf_rows, dt, ctx->stream);
+  }
 }
 void wb_begin_launch(elmk_ctx* ctx)
 {
@@ -120,7 +128,8 @@ void wb_launch(elmk_ctx* ctx, double dt, bool run)
   if (!hyd_land(ctx)) return;
   launch_water_balance(ctx->d, ctx->ncols, ctx->ld, ctx->hyd_rows, ctx->hydf_rows, ctx->wb_rows, dt, ctx->wb_tol, ctx->wb_part, ctx->wb_out,
                        run ? ctx->wb_ring_mms : nullptr, run ? ctx->wb_ring_census : ctx->wb_census, run ? ctx->run.cursor : nullptr,
-                       ctx->stream, ctx->irr_rows ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * (size_t)ctx->ld : nullptr);
+                       ctx->stream, ctx->irr_rows ? ctx->irr_rows + (size_t)ELMK_IRR_QFLX_IRRIG * (size_t)ctx->ld : nullptr,
+                       ctx->route.land.mem ? ctx->route.land.tab + (size_t)ELMK_FPI_QFLX_DRAIN * (size_t)ctx->ld : nullptr);
 }
 int wb_ring_alloc(elmk_ctx* ctx)
 {
@@ -146,6 +155,11 @@ int wb_ring_alloc(elmk_ctx* ctx)
 }
 const double* feature_row(const elmk_ctx* ctx, int family, int which, const char** why)
 {
+  if (family == ELMK_ROWS_FLOODPLAIN) {  // (the extension's column rows lie in the river stage's allocation)
+    if (!ctx->route.land.mem) return *why = "the family's feature is not enabled", nullptr;
+    if (which < 0 || which >= ELMK_FPI_NROWS) return *why = "unknown row", nullptr;
+    return ctx->route.land.tab + (size_t)which * (size_t)ctx->ld;
+  }
   if (family < 0 || family >= ELMK_ROWS_NFAMILY) return *why = "unknown row family", nullptr;
   const Rows& R = *FAMILY[family];
   if (!(ctx->*R.buf)) return *why = "the family's feature is not enabled", nullptr;
@@ -270,6 +284,7 @@ int elmk_soil_hydrology_clear(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, who)) return rc;
   for (const Rows* R : {&HYD, &HYDF, &WB})  // nothing changes unless all three may go
     if (int rc = rows_held(ctx, *R, who)) return rc;
+  if (int rc = land_holds(ctx, who)) return rc;  // (the hydrology's ROF form and the water balance's LAND form go with their rows)
   if (int rc = route_holds(ctx, who)) return rc;  // (the routing reads the water balance's QRUNOFF)
   if (int rc = elmk_water_balance_clear(ctx)) return rc;
   if (int rc = rows_clear(ctx, HYDF, who)) return rc;
@@ -364,8 +379,10 @@ int elmk_water_balance_read(elmk_ctx* ctx, int w, double* host, int64_t col0, in
 
 int elmk_water_balance_clear(elmk_ctx* ctx)
 {
-  if (ctx && ctx->wb_rows)
+  if (ctx && ctx->wb_rows) {
+    if (int rc = land_holds(ctx, "elmk_water_balance_clear")) return rc;
     if (int rc = route_holds(ctx, "elmk_water_balance_clear")) return rc;
+  }
   if (int rc = rows_clear(ctx, WB, "elmk_water_balance_clear")) return rc;
   if (!ctx->wb_rows) wb_release(ctx);  // (rows_clear has made the stream idle)
   return ELMK_OK;

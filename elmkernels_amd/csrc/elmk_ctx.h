@@ -165,10 +165,11 @@ struct StepKey {
   bool irr_supply = false;                   // the irrigation stage is in the step and the river supply limit's launch follows it
   bool route_dam = false;                    // the routing stage is in the step and takes the reservoirs' form (its time from the pad word)
   bool route_heat = false;                   // the routing stage is in the step and takes the stream temperature's form
+  bool land = false;                         // the floodplain infiltration is on: the hydrology, water balance and routing stages take its forms
   auto tie() const
   {
     return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw,
-                    irr_supply, route_dam, route_heat);
+                    irr_supply, route_dam, route_heat, land);
   }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
@@ -300,6 +301,8 @@ struct elmk_ctx {
   //   dam (elmk_routing_reservoir_*): the reservoirs' rows [DAM_NROWS][cld]; tab: the host's tables [DAM_NTAB][cld]; beside it, in
   //     the same allocation, MSTART [cld].  dam_time: the month | begins << 4 of elmk_routing_reservoir_time, what the stepwise calls read
   //   heat (elmk_routing_heat_*): the stream temperature's rows [HT_NROWS][cld]; tab: KSW [cld].  heat_sublev: the soil layer of H1
+  //   land (elmk_floodplain_infiltration_*): the cell row QLAND [1][cld]; tab: the three column rows [ELMK_FPI_NROWS][ld]; beside them, in
+  //     the same allocation, cellof [ld] (land_cellof; -1 in the padding columns)
   // route_launch takes the scheme and the forms whose memory is there.
   struct Routing {
     struct Part {
@@ -319,7 +322,8 @@ struct elmk_ctx {
     int32_t* down = nullptr;
     double* part = nullptr;
     double* out = nullptr;
-    Part kw, fp, dam, heat;
+    Part kw, fp, dam, heat, land;
+    int32_t* land_cellof = nullptr;
     int32_t* dam_mstart = nullptr;
     int32_t dam_time = 0;
     int heat_sublev = 0;
@@ -505,14 +509,17 @@ void route_launch(elmk_ctx* ctx, double dt, bool run = false);  // one call of t
 // "<who>: runoff routing is enabled (elmk_routing_clear first)" while it is - what the routing reads stays; with_withdrawal: only while
 // the withdrawal is on
 int route_holds(elmk_ctx* ctx, const char* who, bool with_withdrawal = false);
+// "<who>: the floodplain infiltration is on (elmk_floodplain_infiltration_clear first)" while it is - what its kernels' forms read stays
+int land_holds(elmk_ctx* ctx, const char* who);
 // row `which` (ELMK_ROUTE_*) of the river stages as elmk_routing_read finds it now, or null with *why set (not enabled, out of range, its
 // scheme or extension off)
 const double* route_row(const elmk_ctx* ctx, int which, const char** why);
 size_t route_bytes(const elmk_ctx* ctx);  // the device bytes of the parts that are on
 int route_zero_rows(elmk_ctx* ctx);       // every row of every part that is on zero (enqueued)
 // the routing state of the restart image (ELMK_OPT_RESTART_CELLS): the ELMK_ROUTE_* of the prognostic rows the parts hold at this
-// moment, in image order (VOLR, QOUT_SUM, WH, WT, WF, RES, KRLS, or TT, TR behind WT: the heat excludes the two before it); returns their number
-constexpr int ROUTE_STATE_MAX = 7;
+// moment, in image order (VOLR, QOUT_SUM, WH, WT, WF, RES, KRLS, or TT, TR behind WT: the heat excludes the two before it; with the
+// floodplain infiltration on FLOOD_FRAC, which its F1 reads before the next call rewrites it, comes last); returns their number
+constexpr int ROUTE_STATE_MAX = 8;
 int route_state_rows(const elmk_ctx* ctx, int* ids);
 constexpr int ALT_NROWS = 3;  // api_rows.cpp
 ActiveLayerArgs alt_args(const elmk_ctx* ctx);

@@ -273,8 +273,15 @@ void launch_irrigation_supply(int64_t ncols, double* irr_rows, int64_t ld, int i
 
 // soil hydrology (k_soil_hydrology.hip, elmk_soil_hydrology): one stage over every column; rows = the ELMK_HYD_NROWS fp64 rows of
 // the feature, [row][ld]; frost_rows = the ELMK_HYDF_NROWS rows of the frost-table extension, which select the F' form of the kernel, or
-// null for the plain one
-void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* frost_rows, double dt, hipStream_t st);
+// null for the plain one.  rof not null: the floodplain infiltration's form (F1 - F3): cellof [ld] the cell of every column or -1, wf / ff /
+// area the routing's WF, FLOOD_FRAC and area rows over the cells, out the extension's column rows [ELMK_FPI_NROWS][ld]
+struct RofArgs {
+  const int32_t* cellof;
+  const double *wf, *ff, *area;
+  double* out;
+};
+void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* frost_rows, double dt, hipStream_t st,
+                           const RofArgs* rof = nullptr);
 
 // water balance (k_water_balance.hip, elmk_water_balance_*): hyd_rows / frost_rows as launch_soil_hydrology's (frost_rows null: the
 // extension is off), wb_rows = the ELMK_WB_NROWS fp64 rows of the feature, [row][ld].
@@ -282,13 +289,14 @@ void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* f
 void launch_min_max_sum(const double* diag, int64_t ld, int64_t n, int ndiag, double* part, double* out, hipStream_t st);
 // W0: BEGWB
 void launch_wb_begin(const DevState* S, int64_t n, const double* hyd_rows, double* wb_rows, hipStream_t st);
-// qirr: the irrigation's QFLX_IRRIG row, which selects W4's form with the term, or null.
+// qirr: the irrigation's QFLX_IRRIG row, which selects W4's form with the term, or null.  qland: the floodplain infiltration's
+// QFLX_H2OROF_DRAIN row, which selects F4's form of W4, or null.
 // W1 - W8: the rows, the three triples into out[3][3] (part: 3 x ELMK_CONS_NPART x 3 doubles) and the census {nbad, first bad column or
 // INT64_MAX} into census[0 .. 2).  elmk_run (cursor not null): the triples are copied to ring + *cursor * 9 and the census goes to
 // census + *cursor * 2
 void launch_water_balance(const DevState* S, int64_t n, int64_t ld, const double* hyd_rows, const double* frost_rows, double* wb_rows,
                           double dt, double tol, double* part, double* out, double* ring, long long* census, const int32_t* cursor,
-                          hipStream_t st, const double* qirr = nullptr);
+                          hipStream_t st, const double* qirr = nullptr, const double* qland = nullptr);
 
 // runoff routing (k_routing.hip, elmk_routing_*): the feature's fp64 rows [ROUTE_NROWS][cld] over the output grid's cells, cld = ncells
 // rounded up to 64.  The first three rows are the ones launch_min_max_sum reduces for the budget; ROUTE_OUTLET (QOUT of the outlets,
@@ -365,10 +373,15 @@ void launch_routing_outlet_row(const int32_t* down, const double* src, double* d
 // one call: K1 (QIN as R1, QSUR from the hydrology's rows qsurf + qh2osfc, QSUB, the first er) as one launch, then nsub sub-step
 // launches that update WH, WT and VOLR in place; A.kout and ROUTE_VOLR_B are not read.  F.rows not null: the sub-steps take the flood
 // form (I1 - I5).  Dm.rows not null: every launch takes the DAM form (D1 - D4).  H.rows not null (F.rows and Dm.rows null): every
-// launch takes the HEAT form (H1 - H6)
+// launch takes the HEAT form (H1 - H6).  L.qland not null (F.rows not null, H.rows null): the K1 launch takes the LAND form (F5): it
+// aggregates the column row L.qdrain into the cell row L.qland and takes it out of WF
+struct LandArgs {
+  const double* qdrain;  // [ld]: the floodplain infiltration's QFLX_H2OROF_DRAIN
+  double* qland;         // [cld]
+};
 void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const HeatArgs& H, const OGridMap& M,
                               const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc, double dt,
-                              hipStream_t st);
+                              hipStream_t st, const LandArgs& L = LandArgs{nullptr, nullptr});
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

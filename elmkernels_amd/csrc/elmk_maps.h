@@ -83,6 +83,20 @@ inline int64_t csr_shared_column(int64_t ncols, int64_t nnz, const int32_t* col)
   return p == nnz ? -1 : repeat ? (int64_t)col[p] : -2;
 }
 
+// The cell of every column (elmk_floodplain_infiltration_enable; include/elmk.h "floodplain infiltration", F0), from an accepted CSR map by
+// cell: cellof[c] = the row whose span names column c, -1 for a column in no row.  Returns csr_shared_column's answer, and fills cellof
+// (ncols entries) only where that is -1: a column in two rows has no one cell.
+inline int64_t csr_cellof(int64_t nrows, int64_t ncols, const int64_t* ptr, const int32_t* col, std::vector<int32_t>* cellof)
+{
+  const int64_t nnz = nrows > 0 && ptr ? ptr[nrows] : 0;
+  const int64_t shared = csr_shared_column(ncols, nnz, col);
+  if (shared != -1) return shared;
+  cellof->assign((size_t)(ncols > 0 ? ncols : 0), -1);
+  for (int64_t r = 0; r < nrows && nnz > 0 && col; r++)
+    for (int64_t p = ptr[r]; p < ptr[r + 1]; p++) (*cellof)[(size_t)col[p]] = (int32_t)r;
+  return -1;
+}
+
 // River network (elmk_routing_enable; include/elmk.h "runoff routing"): every cell drains into one downstream cell down[c], or is an
 // outlet (-1).  ddist: metres to the downstream cell (> 0), area: square metres (>= 0).  Checks, in this order: the arguments; per cell
 // in index order the range of down, then a self-loop; the in-degree (at most ROUTE_MAXUP cells drain into one); cycles; ddist; area.

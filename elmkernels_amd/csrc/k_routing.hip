@@ -330,21 +330,34 @@ __device__ __forceinline__ double heat_settle(double h, double wn, double wmin, 
 }
 }  // namespace
 
+// ---- floodplain infiltration (include/elmk.h "floodplain infiltration", F5; elmkernels_amd/routing.py: kinematic_call's land) ----------
+// The LAND form of the K1 launch: one more sum in the CSR walk, 8 bytes per term; per cell WF read and written and QLAND written, 24 bytes.
+template <bool LAND>
+struct LandRows {};  // the plain form takes nothing: its kernel arguments, instructions and registers stay what they were
+template <>
+struct LandRows<true> {
+  gptr<const double> qdrain;  // [ld]: the column row QFLX_H2OROF_DRAIN
+  gptr<double> wf, qland;     // [cld]
+  double dt;
+};
+
 // K1: QIN as k_routing_qin, QSUR from the hydrology's two surface rows in the same order, QSUB, and the er of the first sub-step.
-// DAM: D1, D2 and the first sub-step's D3 for the dam cells.  HEAT: H1
-template <bool WITHDRAW, bool DAM = false, bool HEAT = false>
+// DAM: D1, D2 and the first sub-step's D3 for the dam cells.  HEAT: H1.  LAND: F5
+template <bool WITHDRAW, bool DAM = false, bool HEAT = false, bool LAND = false>
 __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
                                                         gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
                                                         gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
                                                         gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
                                                         gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<DAM> dm,
-                                                        HeatRows<HEAT> ht)
+                                                        HeatRows<HEAT> ht, LandRows<LAND> ln)
 {
   static_assert(!(HEAT && DAM), "the heat and the reservoirs exclude each other");
+  static_assert(!(HEAT && LAND), "the heat excludes the inundation, and the infiltration with it");
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncells) return;
   const int64_t p0 = ptr[c], p1 = ptr[c + 1];
   double r = 0.0, i = 0.0, s = 0.0;
+  [[maybe_unused]] double tl = 0.0;
   [[maybe_unused]] double ta = 0.0, pa = 0.0, qa = 0.0, lw = 0.0, ua = 0.0, sw = 0.0, tsur = 0.0, tsub = 0.0;
   for (int64_t p = p0; p < p1; p++) {
     const int32_t k = col[p];
@@ -357,6 +370,10 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
     }
     const double z = wp * (qsurf[k] + qh2osfc[k]);
     s = p == p0 ? z : s + z;
+    if constexpr (LAND) {
+      const double y = wp * ln.qdrain[k];
+      tl = p == p0 ? y : tl + y;
+    }
     if constexpr (HEAT) {  // H1's terms
       const bool first = p == p0;
       const int dt_ = ht.dtype;
@@ -382,6 +399,11 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
   if constexpr (WITHDRAW) r = r - i;
   const double ar = area[c];
   const double q = (r * 0.001) * ar, qs = (s * 0.001) * ar;
+  if constexpr (LAND) {  // F5
+    const double ql = (tl * 0.001) * ar;
+    route_st(ln.qland + c, ql);
+    route_st(ln.wf + c, ln.wf[c] - ql * ln.dt);
+  }
   if constexpr (DAM) {
     const double cap = dm.tab[DAM_CAP * cld + c];
     if (cap > 0.0) {  // D0
@@ -651,7 +673,7 @@ HeatRows<true> heat_rows(const HeatArgs& H, const double* hr_old, double* hr_new
 
 void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const HeatArgs& H,
                               const OGridMap& M, const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc,
-                              double dt, hipStream_t st)
+                              double dt, hipStream_t st, const LandArgs& Ln)
 {
   if (A.ncells <= 0) return;
   const double dts = dt / (double)A.nsub;  // K0
@@ -664,17 +686,22 @@ void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const 
   with_bool(Dm.rows != nullptr, [&](auto dam) {
     with_bool(qirr != nullptr, [&](auto withdraw) {
       with_bool(H.rows != nullptr, [&](auto heat) {
-        constexpr bool DAM = decltype(dam)::value, HEAT = decltype(heat)::value && !DAM;
-        DamRows<DAM> dm;
-        if constexpr (DAM) dm = dam_rows(Dm, dt);
-        HeatRows<HEAT> ht;
-        if constexpr (HEAT) ht = heat_rows(H, nullptr, hsrc);
-        hipLaunchKernelGGL((k_kinematic_prep<decltype(withdraw)::value, DAM, HEAT>), grid, block, 0, st, (gptr<const int64_t>)M.ptr,
-                           (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff, (gptr<const double>)qirr,
-                           (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
-                           (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
-                           (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
-                           (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts, dm, ht);
+        // (the LAND form exactly while the infiltration's rows and the floodplain's are there; the entry points keep it apart from the heat)
+        with_bool(Ln.qland != nullptr && F.rows != nullptr, [&](auto land) {
+          constexpr bool DAM = decltype(dam)::value, HEAT = decltype(heat)::value && !DAM, LAND = decltype(land)::value && !HEAT;
+          DamRows<DAM> dm;
+          if constexpr (DAM) dm = dam_rows(Dm, dt);
+          HeatRows<HEAT> ht;
+          if constexpr (HEAT) ht = heat_rows(H, nullptr, hsrc);
+          LandRows<LAND> ln;
+          if constexpr (LAND) ln = LandRows<true>{(gptr<const double>)Ln.qdrain, (gptr<double>)(F.rows + FP_WF * A.cld), (gptr<double>)Ln.qland, dt};
+          hipLaunchKernelGGL((k_kinematic_prep<decltype(withdraw)::value, DAM, HEAT, LAND>), grid, block, 0, st, (gptr<const int64_t>)M.ptr,
+                             (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff, (gptr<const double>)qirr,
+                             (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
+                             (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
+                             (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
+                             (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts, dm, ht, ln);
+        });
       });
     });
   });

@@ -33,11 +33,26 @@ __device__ __forceinline__ double hy_canon(double x) { return x != x ? __builtin
 
 // The rows a launch is handed: the feature's, and in the frost form the extension's.  The plain form keeps the kernel arguments it had
 // before the extension existed, so that its code is that kernel's, instruction for instruction.
-template <bool FROST> struct HydRows {
+template <bool FROST, bool ROF = false> struct HydRows {
   gptr<double> rows;
 };
-template <> struct HydRows<true> {
+template <> struct HydRows<true, false> {
   gptr<double> rows, frows;
+};
+// ROF: the floodplain infiltration (include/elmk.h "floodplain infiltration", F1 - F3): the column's cell, the routing's WF, FLOOD_FRAC and
+// area rows over the cells, and the extension's three column rows [ELMK_FPI_NROWS][ld]
+struct RofRows {
+  gptr<const int32_t> cellof;
+  gptr<const double> wf, ff, area;
+  gptr<double> out;
+};
+template <> struct HydRows<false, true> {
+  gptr<double> rows;
+  RofRows rof;
+};
+template <> struct HydRows<true, true> {
+  gptr<double> rows, frows;
+  RofRows rof;
 };
 
 // FROST: the F' form of the drainage (elmk_soil_hydrology_frost_enable), frows its ELMK_HYDF_NROWS rows.  It keeps nothing of its own
@@ -46,8 +61,10 @@ template <> struct HydRows<true> {
 // from them a second time, which frees their registers during the solve: with them carried the kernel spilled to scratch (DESIGN.md
 // section 20).  Branches A and B share one conductivity sum and one removal walk: they differ in the layers and in which table the
 // walk moves.
-template <bool FROST>
-__global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restrict__ S, HydRows<FROST> R, double dt)
+// ROF: F1 - F3 at the end of C.  The column's cell and the cell's three values are loaded there, through an index the compiler cannot
+// match with the loads at the top, and the three rows are stored there: nothing of the form is live into D.
+template <bool FROST, bool ROF>
+__global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restrict__ S, HydRows<FROST, ROF> R, double dt)
 {
   const gptr<double> rows = R.rows;
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -128,6 +145,28 @@ __global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restri
   }
   h2osfc = h2osfc - drain_sfc * dt;
   infl = infl + drain_sfc;
+  if constexpr (ROF) {  // F1 - F3
+    int64_t cr = c;
+    asm volatile("" : "+v"(cr));
+    const int32_t g = R.rof.cellof[cr];
+    double wf = 0.0, ff = 0.0, ar = 0.0;
+    if (g >= 0) {
+      wf = R.rof.wf[g];
+      ff = R.rof.ff[g];
+      ar = R.rof.area[g];
+    }
+    double hr = 0.0, d = 0.0, fr = 0.0;
+    if (g >= 0 && wf > 0.0 && ff > 0.0 && ar > 0.0) {
+      hr = (wf / ar) * 1000.0;
+      const double a = ff * qinmax, b = hr / dt;
+      d = a < b ? a : b;
+      fr = ff;
+    }
+    infl = infl + d;
+    R.rof.out[(int64_t)ELMK_FPI_H2OROF * ld + cr] = hy_canon(hr);
+    R.rof.out[(int64_t)ELMK_FPI_FRAC * ld + cr] = hy_canon(fr);
+    R.rof.out[(int64_t)ELMK_FPI_QFLX_DRAIN * ld + cr] = hy_canon(d);
+  }
 
   // D. soil water
   int jwt = HN;
@@ -542,15 +581,26 @@ __global__ __launch_bounds__(256) void k_soil_hydrology(const DevState* __restri
 
 // The plain form first in the unit's code object, where the kernel stood before the extension: with the frost form in front of it the
 // same instructions ran 1 % slower on the thawed tier.
-template __global__ void k_soil_hydrology<false>(const DevState* __restrict__, HydRows<false>, double);
-template __global__ void k_soil_hydrology<true>(const DevState* __restrict__, HydRows<true>, double);
+template __global__ void k_soil_hydrology<false, false>(const DevState* __restrict__, HydRows<false, false>, double);
+template __global__ void k_soil_hydrology<true, false>(const DevState* __restrict__, HydRows<true, false>, double);
+template __global__ void k_soil_hydrology<false, true>(const DevState* __restrict__, HydRows<false, true>, double);
+template __global__ void k_soil_hydrology<true, true>(const DevState* __restrict__, HydRows<true, true>, double);
 
-void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* frost_rows, double dt, hipStream_t st)
+void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* frost_rows, double dt, hipStream_t st, const RofArgs* rof)
 {
   if (n <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (frost_rows) hipLaunchKernelGGL(k_soil_hydrology<true>, grid, block, 0, st, S, HydRows<true>{(gptr<double>)rows, (gptr<double>)frost_rows}, dt);
-  else hipLaunchKernelGGL(k_soil_hydrology<false>, grid, block, 0, st, S, HydRows<false>{(gptr<double>)rows}, dt);
+  if (rof) {
+    const RofRows r{(gptr<const int32_t>)rof->cellof, (gptr<const double>)rof->wf, (gptr<const double>)rof->ff, (gptr<const double>)rof->area,
+                    (gptr<double>)rof->out};
+    if (frost_rows)
+      hipLaunchKernelGGL((k_soil_hydrology<true, true>), grid, block, 0, st, S, HydRows<true, true>{(gptr<double>)rows, (gptr<double>)frost_rows, r}, dt);
+    else hipLaunchKernelGGL((k_soil_hydrology<false, true>), grid, block, 0, st, S, HydRows<false, true>{(gptr<double>)rows, r}, dt);
+    return;
+  }
+  if (frost_rows)
+    hipLaunchKernelGGL((k_soil_hydrology<true, false>), grid, block, 0, st, S, HydRows<true, false>{(gptr<double>)rows, (gptr<double>)frost_rows}, dt);
+  else hipLaunchKernelGGL((k_soil_hydrology<false, false>), grid, block, 0, st, S, HydRows<false, false>{(gptr<double>)rows}, dt);
 }
 
 }  // namespace elmk

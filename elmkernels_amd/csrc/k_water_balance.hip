@@ -40,6 +40,9 @@ __device__ __forceinline__ void wb_st(gptr<double> p, double v)
   else *p = v;
 }
 __device__ __forceinline__ gptr<const double> wb_first(gptr<const double> p) { return p; }
+__device__ __forceinline__ gptr<const double> wb_first(gptr<const double> p, gptr<const double>) { return p; }
+__device__ __forceinline__ gptr<const double> wb_last(gptr<const double> p) { return p; }
+__device__ __forceinline__ gptr<const double> wb_last(gptr<const double>, gptr<const double> p) { return p; }
 }  // namespace
 
 #define LV(f, lev) S->f[(int64_t)(lev) * ld + c]
@@ -57,12 +60,13 @@ __global__ __launch_bounds__(256) void k_wb_begin(const DevState* __restrict__ S
 // W1 - W6.  FROST: QRUNOFF takes QFLX_DRAIN_PERCHED of the frost-table extension's rows hydf as well.  IRRIG: W4 takes the
 // irrigation's QFLX_IRRIG row as a term of the input (ELM's BalanceCheck; include/elmk.h "irrigation").  The row is one more kernel
 // argument, a pack that is empty without IRRIG, so that the two plain instantiations keep the kernel arguments, and with them every
-// instruction, they had before the term existed
-template <bool FROST, bool IRRIG, class... Q>
+// instruction, they had before the term existed.  LAND: W4 takes the floodplain infiltration's QFLX_H2OROF_DRAIN row as the last term of
+// the input (include/elmk.h "floodplain infiltration", F4); its row is one more member of the pack, behind the irrigation's
+template <bool FROST, bool IRRIG, bool LAND, class... Q>
 __global__ __launch_bounds__(256) void k_water_balance(const DevState* __restrict__ S, gptr<const double> hyd, gptr<const double> hydf,
                                                        gptr<double> wb, double dt, Q... qirr)
 {
-  static_assert(sizeof...(Q) == (IRRIG ? 1 : 0), "the QFLX_IRRIG row exactly with IRRIG");
+  static_assert(sizeof...(Q) == (IRRIG ? 1 : 0) + (LAND ? 1 : 0), "the QFLX_IRRIG row exactly with IRRIG, the QFLX_H2OROF_DRAIN row with LAND");
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t ld = S->ld;
   if (c >= S->ncols) return;
@@ -94,7 +98,11 @@ __global__ __launch_bounds__(256) void k_water_balance(const DevState* __restric
   // W4
   const double begwb = wb[(int64_t)ELMK_WB_BEGWB * ld + c];
   double errh2o;
-  if constexpr (IRRIG)
+  if constexpr (IRRIG && LAND)
+    errh2o = endwb - begwb - ((((S->forc_rain[c] + S->forc_snow[c]) + wb_first(qirr...)[c]) + wb_last(qirr...)[c]) - qrunoff - S->qflx_evap_tot[c] - S->qflx_snwcp_ice[c]) * dt;
+  else if constexpr (LAND)
+    errh2o = endwb - begwb - (((S->forc_rain[c] + S->forc_snow[c]) + wb_last(qirr...)[c]) - qrunoff - S->qflx_evap_tot[c] - S->qflx_snwcp_ice[c]) * dt;
+  else if constexpr (IRRIG)
     errh2o = endwb - begwb - (((S->forc_rain[c] + S->forc_snow[c]) + wb_first(qirr...)[c]) - qrunoff - S->qflx_evap_tot[c] - S->qflx_snwcp_ice[c]) * dt;
   else
     errh2o = endwb - begwb - (S->forc_rain[c] + S->forc_snow[c] - qrunoff - S->qflx_evap_tot[c] - S->qflx_snwcp_ice[c]) * dt;
@@ -169,7 +177,7 @@ void launch_wb_begin(const DevState* S, int64_t n, const double* hyd_rows, doubl
 
 void launch_water_balance(const DevState* S, int64_t n, int64_t ld, const double* hyd_rows, const double* frost_rows, double* wb_rows,
                           double dt, double tol, double* part, double* out, double* ring, long long* census, const int32_t* cursor,
-                          hipStream_t st, const double* qirr)
+                          hipStream_t st, const double* qirr, const double* qland)
 {
   if (n <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -177,9 +185,12 @@ void launch_water_balance(const DevState* S, int64_t n, int64_t ld, const double
     hipLaunchKernelGGL(kernel, grid, block, 0, st, S, (gptr<const double>)hyd_rows, (gptr<const double>)frost_rows, (gptr<double>)wb_rows,
                        dt, q...);
   };
-  const gptr<const double> q = (gptr<const double>)qirr;
-  if (qirr) frost_rows ? rows(k_water_balance<true, true, gptr<const double>>, q) : rows(k_water_balance<false, true, gptr<const double>>, q);
-  else frost_rows ? rows(k_water_balance<true, false>) : rows(k_water_balance<false, false>);
+  using P = gptr<const double>;
+  const P q = (P)qirr, ql = (P)qland;
+  if (qland && qirr) frost_rows ? rows(k_water_balance<true, true, true, P, P>, q, ql) : rows(k_water_balance<false, true, true, P, P>, q, ql);
+  else if (qland) frost_rows ? rows(k_water_balance<true, false, true, P>, ql) : rows(k_water_balance<false, false, true, P>, ql);
+  else if (qirr) frost_rows ? rows(k_water_balance<true, true, false, P>, q) : rows(k_water_balance<false, true, false, P>, q);
+  else frost_rows ? rows(k_water_balance<true, false, false>) : rows(k_water_balance<false, false, false>);
   static_assert(ELMK_WB_QRUNOFF == ELMK_WB_ERRH2O + 1 && ELMK_WB_ENDWB == ELMK_WB_ERRH2O + 2, "the reduced rows are adjacent");
   const double* diag = wb_rows + (size_t)ELMK_WB_ERRH2O * (size_t)ld;
   launch_min_max_sum(diag, ld, n, 3, part, out, st);

@@ -170,6 +170,19 @@ def column(c, dt, hit=None, probe=None):
         drain_sfc = _min(frac_h2osfc * qinmax, _div(h2osfc, dt))
     h2osfc = h2osfc - drain_sfc * dt
     infl = infl + drain_sfc
+    rof = c.get("rof")
+    if rof is not None:  # F1 - F3 ("floodplain infiltration"): rof = (in a cell, WF, FLOOD_FRAC, area of the cell)
+        in_cell, wf, ff, ar = rof
+        if in_cell and wf > 0.0 and ff > 0.0 and ar > 0.0:
+            hr = _div(wf, ar) * 1000.0
+            a, b = ff * qinmax, _div(hr, dt)
+            d = a if a < b else b
+            mark("rof_a" if a < b else "rof_b")
+            fr = ff
+        else:
+            mark("rof_guard")
+            hr = d = fr = 0.0
+        infl = infl + d
 
     # D. soil water
     jwt = _jwt(zwt, zi)
@@ -467,10 +480,16 @@ def column(c, dt, hit=None, probe=None):
          "qflx_rsub_sat": _canon(rsub_sat), "qcharge": _canon(qcharge), "fsat": _canon(fsat)}
     if frost:
         o["frost_table"], o["zwt_perched"], o["qflx_drain_perched"] = _canon(ft), _canon(zwp), _canon(qp)
+    if rof is not None:
+        o["h2orof"], o["frac_h2orof"], o["qflx_h2orof_drain"] = _canon(hr), _canon(fr), _canon(d)
     return o
 
 
-def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None):
+FPI_H2OROF, FPI_FRAC, FPI_QFLX_DRAIN = range(3)  # ELMK_FPI_*: the floodplain infiltration's column rows
+FPI_NROWS = 3
+
+
+def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None, rof=None):
     """One elmk_soil_hydrology on the host.
 
     fields: a dict of the state fields READS and h2osoi_vol as S[name] downloads them ([n] or [n, nlev], any float dtype: widened to
@@ -481,8 +500,13 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None):
     the results are rounded to it before they take the inputs' dtype.  frost: float64 [FROST_NROWS, n], the rows of the frost-table
     extension (Q_PERCH_MAX .. QFLX_DRAIN_PERCHED); with it the step takes the F' form, reads t_soisno as well and returns
     (out, rows_out, frost_out), frost_out the extension's rows after the step.  probes: a list that receives column()'s probe of every
-    column in turn."""
+    column in turn.  rof=(cellof, wf, flood_frac, area): the floodplain infiltration's form (include/elmk.h "floodplain infiltration",
+    F1 - F3): cellof int [n], the cell of every column or -1; wf, flood_frac, area float64 [ncells], the routing's rows as its last call
+    left them.  The result grows by fpi_out, float64 [FPI_NROWS, n]: H2OROF, FRAC, QFLX_H2OROF_DRAIN."""
     dt = float(dt)
+    if rof is not None:
+        r_cell = np.asarray(rof[0]).reshape(-1)
+        r_wf, r_ff, r_ar = (np.asarray(x, dtype=np.float64).reshape(-1) for x in rof[1:])
     f = {k: np.asarray(fields[k]) for k in READS + ("h2osoi_vol",) + (("t_soisno",) if frost is not None else ())}
     n = f["h2osfc"].shape[0]
     rows = np.asarray(rows, dtype=np.float64)
@@ -495,6 +519,9 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None):
         frost = np.asarray(frost, dtype=np.float64)
         assert frost.shape == (FROST_NROWS, n)
         frost_out = frost.copy()
+    if rof is not None:
+        assert r_cell.shape == (n,)
+        fpi_out = np.zeros((FPI_NROWS, n))
     s0, s1 = NLEVSNO, NLEVSNO + N
     for i in range(n):
         c = {"liq": w["h2osoi_liq"][i, s0:s1].tolist(), "ice": w["h2osoi_ice"][i, s0:s1].tolist(), "dz": w["dz"][i, s0:s1].tolist(),
@@ -509,6 +536,9 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None):
         c["k_wet"], c["rsub_top_max"] = float(rows[K_WET, i]), float(rows[RSUB_TOP_MAX, i])
         if frost is not None:
             c["t"], c["q_perch_max"] = w["t_soisno"][i, s0:s1].tolist(), float(frost[Q_PERCH_MAX, i])
+        if rof is not None:
+            g = int(r_cell[i])
+            c["rof"] = (True, float(r_wf[g]), float(r_ff[g]), float(r_ar[g])) if g >= 0 else (False, 0.0, 0.0, 0.0)
         if probes is None:
             o = column(c, dt, hit)
         else:
@@ -517,6 +547,8 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None):
         if frost is not None:
             frost_out[FROST_TABLE, i], frost_out[ZWT_PERCHED, i] = o["frost_table"], o["zwt_perched"]
             frost_out[QFLX_DRAIN_PERCHED, i] = o["qflx_drain_perched"]
+        if rof is not None:
+            fpi_out[:, i] = o["h2orof"], o["frac_h2orof"], o["qflx_h2orof_drain"]
         res["h2osoi_liq"][i, s0:s1] = o["liq"]
         res["h2osoi_ice"][i, s0] = o["ice0"]
         res["h2osoi_vol"][i, :N] = o["vol"]
@@ -533,7 +565,8 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None):
         out["h2osoi_ice"][:, s0] = rnd(res["h2osoi_ice"][:, s0], out["h2osoi_ice"])
         out["h2osoi_vol"][:, :N] = rnd(res["h2osoi_vol"][:, :N], out["h2osoi_vol"])
         out["h2osfc"][:] = rnd(res["h2osfc"], out["h2osfc"])
-    return (out, rows_out) if frost is None else (out, rows_out, frost_out)
+    ret = (out, rows_out) if frost is None else (out, rows_out, frost_out)
+    return ret if rof is None else ret + (fpi_out,)
 
 
 # ---- parameters -------------------------------------------------------------------------------------------------------------------
@@ -650,12 +683,13 @@ def water_balance_begin(fields, rows, wb=None):
     return out
 
 
-def water_balance_end(fields, rows, wb, dt, frost=None, snwcp_liq_term=True, qflx_irrig=None):
+def water_balance_end(fields, rows, wb, dt, frost=None, snwcp_liq_term=True, qflx_irrig=None, qflx_h2orof_drain=None):
     """W1 - W6 on the host, one numpy operation per IEEE operation in the header's order.  fields: the state fields WB_READS as S[name]
     downloads them; rows: the hydrology's rows after the step's soil_hydrology; wb: the rows of the feature, BEGWB from
     water_balance_begin; frost: the frost-table extension's rows [FROST_NROWS, n] where it is enabled.  Returns the rows after the
     stage (BEGWB unchanged).  snwcp_liq_term=False leaves W3's last term out (a measurement, not the stage).  qflx_irrig: the
-    irrigation's QFLX_IRRIG row [n] where that feature is enabled: W4 takes (forc_rain + forc_snow) + qflx_irrig as the input."""
+    irrigation's QFLX_IRRIG row [n] where that feature is enabled: W4 takes (forc_rain + forc_snow) + qflx_irrig as the input.
+    qflx_h2orof_drain: the floodplain infiltration's QFLX_H2OROF_DRAIN row [n] where that extension is on: the input's last term (F4)."""
     dt = float(dt)
     rows, wb = np.asarray(rows, dtype=np.float64), np.array(wb, dtype=np.float64)
     w = _wide(fields, WB_READS)
@@ -669,7 +703,13 @@ def water_balance_end(fields, rows, wb, dt, frost=None, snwcp_liq_term=True, qfl
         if frost is not None:
             q = q + np.asarray(frost, dtype=np.float64)[QFLX_DRAIN_PERCHED]
         qrunoff = q + w["qflx_snwcp_liq"] if snwcp_liq_term else q
-        if qflx_irrig is None:
+        if qflx_h2orof_drain is not None:
+            inp = w["forc_rain"] + w["forc_snow"]
+            if qflx_irrig is not None:
+                inp = inp + np.asarray(qflx_irrig, dtype=np.float64)
+            inp = inp + np.asarray(qflx_h2orof_drain, dtype=np.float64)
+            err = endwb - wb[WB_BEGWB] - (inp - qrunoff - w["qflx_evap_tot"] - w["qflx_snwcp_ice"]) * dt
+        elif qflx_irrig is None:
             err = endwb - wb[WB_BEGWB] - (w["forc_rain"] + w["forc_snow"] - qrunoff - w["qflx_evap_tot"] - w["qflx_snwcp_ice"]) * dt  # W4
         else:
             qi = np.asarray(qflx_irrig, dtype=np.float64)

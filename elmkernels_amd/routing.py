@@ -287,7 +287,15 @@ def qsur_from_rows(ptr, col, w, qflx_surf, qflx_h2osfc_surf, area):
         return _canon((s * 0.001) * np.asarray(area, dtype=np.float64).reshape(-1))
 
 
-def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True, flood=None, dam=None, heat=None):
+def land_from_rows(ptr, col, w, qflx_h2orof_drain):
+    """F5's t [ncells]: the column row QFLX_H2OROF_DRAIN (mm/s) through the output grid's CSR map, regrid.apply_aggregate's arithmetic with
+    +0.0 for a cell without terms - what kinematic_call takes as `land`."""
+    with np.errstate(all="ignore"):
+        return regrid.apply_aggregate(ptr, col, w, qflx_h2orof_drain, 0.0)
+
+
+def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place=False, cap=True, flood=None, dam=None, heat=None,
+                   land=None):
     """One elmk_routing with the scheme on, on the host: K0, K2 - K7.  wh, wt, volr, qin, qsur, area: float64 [ncells]; params
     [11, ncells]; up: upstream_map(down).  Returns (wh_new, wt_new, volr_new, qout).  in_place and cap are the wrong variants the host
     tests hold their checks against, as call's: in_place updates the cells one after another in index order, the upstream flows taken
@@ -300,7 +308,12 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
     (res_new, krls_new, res_take, qin_new) behind the flood rows, if any.
     heat: the HEAT form ("stream temperature", H1 - H6), a dict with "tab" (heat_tables), "prep" (heat_prep), "tt" and "tr" [ncells] and
     optionally "census", a dict that takes a bool row per branch of HEAT_BRANCHES; not together with flood or dam.  The result grows by
-    (tt_new, tr_new, heat, hin, hsrf, hadj, hout); the water rows keep their bits (H8)."""
+    (tt_new, tr_new, heat, hin, hsrf, hadj, hout); the water rows keep their bits (H8).
+    land: the LAND form of the K1 launch ("floodplain infiltration", F5), land_from_rows' aggregate of the column row
+    QFLX_H2OROF_DRAIN [ncells]; only with flood.  QLAND = (land * 0.001) * area leaves wf before the first sub-step, and the result
+    grows by (qland,) at its end."""
+    if land is not None and (flood is None or heat is not None):
+        raise ValueError("kinematic_call: land without flood, or with heat")
     if heat is not None:
         if flood is not None or dam is not None or in_place:
             raise ValueError("kinematic_call: heat with flood, dam or in_place")
@@ -329,6 +342,9 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
     safe = np.where(up >= 0, up, 0)
     ht = _HeatCall(heat, v.size) if heat is not None else None
     with np.errstate(all="ignore"):
+        if land is not None:  # F5
+            qland = _canon((np.asarray(land, dtype=np.float64).reshape(-1) * 0.001) * area)
+            wf = _canon(wf - qland * float(dt))
         qsub = qin - qsur
         for _ in range(nsub):
             eh = hillslope_flow(wh, area, ch, dts, cap)
@@ -371,6 +387,8 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
         out += (res, krls, take, qin)
     if ht is not None:
         out += ht.rows()
+    if land is not None:
+        out += (qland,)
     return out
 
 
@@ -471,6 +489,14 @@ def inundation_exchange(volr, wf, tab, area):
 def inundation_budget(wf):
     """I7: the sum of WF in the device reduction's order, float64 [1]."""
     return np.array([diagnostics.reduce_min_max_sum(wf)[2]])
+
+
+QLAND = 20  # ELMK_ROUTE_QLAND, readable while the floodplain infiltration is on
+
+
+def land_budget(qland):
+    """F6: the sum of QLAND in the device reduction's order, float64 [1]."""
+    return np.array([diagnostics.reduce_min_max_sum(qland)[2]])
 
 
 # ---- reservoirs (include/elmk.h "reservoirs", D0 - D8) -----------------------------------------------------------------------------------

@@ -44,8 +44,11 @@ ROUTE_RES, ROUTE_KRLS, ROUTE_RES_TAKE = 10, 11, 12  # ... while the reservoirs a
 ROUTE_TT, ROUTE_TR, ROUTE_HEAT, ROUTE_HIN, ROUTE_HSRF, ROUTE_HADJ, ROUTE_HOUT = range(13, 20)  # ... while the stream temperature is on (routing.TT .. routing.HOUT)
 WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB .. hydrology.WB_TOTSOILICE
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
+ROWS_FLOODPLAIN = 7  # ... and the floodplain infiltration's (ELMK_ROWS_FLOODPLAIN; which = FPI_*), past the cell-row families' numbers
+FPI_H2OROF, FPI_FRAC, FPI_QFLX_DRAIN = range(3)  # floodplain_infiltration_read (hydrology.FPI_*)
+ROUTE_QLAND = 20  # routing_read while the floodplain infiltration is on (routing.QLAND)
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
-                "irrigation": ROWS_IRRIGATION}
+                "irrigation": ROWS_IRRIGATION, "floodplain": ROWS_FLOODPLAIN}
 CELL_ROWS_ROUTING, CELL_ROWS_SUPPLY = range(2)  # cell_history_add_row: the cell-row families (ELMK_CELL_ROWS_*)
 CELL_ROW_FAMILIES = {"routing": CELL_ROWS_ROUTING, "supply": CELL_ROWS_SUPPLY}
 HYD_NROWS, HYD_NLAYER = 23, 10 # elmk_soil_hydrology_read: the row numbers are hydrology.ZWT .. hydrology.FSAT
@@ -728,6 +731,27 @@ class ELMState:
     def routing_heat_clear(self):
         """Back to the scheme without temperatures; TT and TR are dropped, the water stays."""
         self._chk(self.lib.elmk_routing_heat_clear(self.ctx), "routing_heat_clear")
+
+    # -- floodplain infiltration (include/elmk.h: elmk_floodplain_infiltration_enable ...; hydrology.step(rof=), water_balance_end(
+    #    qflx_h2orof_drain=) and routing.kinematic_call(land=) restate it) -------------------------------------------------------------
+    def floodplain_infiltration_enable(self):
+        """Let the floodplain's water infiltrate the soil columns of its cell: the soil hydrology, the water balance and the routing take
+        their forms with the term from here on.  Allocates the column rows FPI_H2OROF, FPI_FRAC, FPI_QFLX_DRAIN and the cell row
+        ROUTE_QLAND (zero-filled).  Needs soil_hydrology_enable, water_balance_enable, routing_kinematic_enable,
+        routing_inundation_enable and an output grid with every column in at most one cell."""
+        self._chk(self.lib.elmk_floodplain_infiltration_enable(self.ctx), "floodplain_infiltration_enable")
+
+    def floodplain_infiltration_read(self, which, col0=0, n=None):
+        """Row FPI_H2OROF, FPI_FRAC or FPI_QFLX_DRAIN of columns [col0, col0 + n): float64 [n].  Synchronises."""
+        return self._read_row("floodplain_infiltration_read", which, col0, n, self.ncols)
+
+    def floodplain_infiltration_budget(self):
+        """float64 [1]: the sum of QLAND (routing.land_budget).  Synchronises."""
+        return self._routing_budget("floodplain_infiltration_budget", 1)
+
+    def floodplain_infiltration_clear(self):
+        """Back to the stages without the term; WF stays."""
+        self._chk(self.lib.elmk_floodplain_infiltration_clear(self.ctx), "floodplain_infiltration_clear")
 
     # -- water balance (include/elmk.h: elmk_water_balance_enable ...; hydrology.water_balance_begin / _end restate the stage) -----
     def water_balance_enable(self, tol_mm):

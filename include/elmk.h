@@ -1434,6 +1434,66 @@ int elmk_routing_heat_init(elmk_ctx *ctx, const double *tt /*[ncells] or NULL: T
 int elmk_routing_heat_budget(elmk_ctx *ctx, double *sums /*[5]: H7, through R6's reduction kernels*/);
 int elmk_routing_heat_clear(elmk_ctx *ctx);
 
+/* ---- floodplain infiltration ------------------------------------------------------------------------
+ * The river-to-land coupling of the floodplain inundation (ELM's use_lnd_rof_two_way: the h2orof / frac_h2orof inputs of
+ * SoilHydrologyMod::Infiltration, with qflx_h2orof_drain going back to MOSART): the water standing on a flooded cell infiltrates the soil
+ * columns under it, and the routing takes what infiltrated out of the floodplain store.  An opt-in extension of the soil hydrology, the
+ * water balance and the kinematic-wave routing: template forms of their kernels, no run flag, no new launch.  The conventions are those of
+ * "soil hydrology" and "kinematic-wave routing": no contraction, left-associated + - *, `/` correctly rounded, plain IEEE comparisons,
+ * every row fp64 in both builds, a NaN stored into a row is the canonical quiet NaN.
+ * elmk_floodplain_infiltration_enable needs, and refuses with ELMK_E_INVALID and nothing changed otherwise (the text says which): the
+ * soil hydrology on, the water balance on, the kinematic-wave routing on, the floodplain inundation on, every column in at most one
+ * output cell (the refusal names the first shared column), no stream being captured, not already on.  The stream temperature is excluded
+ * through the inundation's own interlock; the reservoirs may be on.
+ *   F0 (host, once at enable) cellof[ncols], int32: the cell whose CSR span names column c, or -1 for a column in no cell; kept on the
+ *      device, owned by the extension and counted in elmk_device_bytes.
+ *   F1 (soil hydrology, section C, after qinmax is formed)
+ *        g = cellof[c];  if (g >= 0) { wf = WF[g]; ff = FLOOD_FRAC[g]; ar = area[g]; }
+ *        if (g >= 0 && wf > 0.0 && ff > 0.0 && ar > 0.0) {
+ *          hr = (wf / ar) * 1000.0                  mm over the cell's area
+ *          a = ff * qinmax;  b = hr / dt;  d = (a < b) ? a : b
+ *        } else { hr = 0.0; d = 0.0 }
+ *      WF and FLOOD_FRAC are read as the last routing call or elmk_routing_inundation_init left them: the previous step's end, the
+ *      convention of the supply limit's VOLR.  The guard keeps a NaN, zero or negative WF from producing a negative drain.
+ *   F2 (the last statement of section C, after infl = infl + drain_sfc)  infl = infl + d.  Sections D to H are unchanged; QFLX_INFL
+ *      carries the term.
+ *   F3 three fp64 column rows of the extension, each [elmk_level_stride], overwritten every step: ELMK_FPI_H2OROF = hr (mm),
+ *      ELMK_FPI_FRAC = ff where the guard passed, else 0.0, ELMK_FPI_QFLX_DRAIN = d (mm/s; ELM's qflx_h2orof_drain).
+ *   F4 (water balance, W4) (forc_rain + forc_snow) + QFLX_H2OROF_DRAIN takes the place of forc_rain + forc_snow; with the irrigation on
+ *      ((forc_rain + forc_snow) + QFLX_IRRIG) + QFLX_H2OROF_DRAIN.  W3 and QRUNOFF are unchanged.
+ *   F5 (routing, the K1 launch, once per call) t = the aggregate of w[p] * QFLX_DRAIN[col[p]] over the cell's terms in R1's order (the
+ *      first term assigned, the others added; a cell without terms takes 0.0);  QLAND = (t * 0.001) * area;  WF = WF - QLAND * dt.
+ *      ELMK_ROUTE_QLAND is a diagnostic cell row, m3/s.  WF may go slightly negative, as VOLR may with the withdrawal on; F1's guard and
+ *      I1 to I4 then do what they say literally.  I6 stands: this launch does no exchange.
+ *   F6 elmk_floodplain_infiltration_budget: sums[0] = the sum of QLAND through R6's reduction kernels.  The change of sum WH + sum WT +
+ *      sum VOLR + sum WF (+ sum RES) over a call becomes dt (sum QIN - sum outlet QOUT - sum QLAND) (- sum RES_TAKE).
+ *   F7 The two sides agree when the hydrology and the routing take the same dt and there is one routing call per hydrology call.
+ *      elmk_run guarantees both; stepwise it is the caller's contract, as it is for QRUNOFF and QFLX_IRRIG.
+ *   F8 Edge values do what F1 and F5 say literally.  NaN qinmax: a < b is false, so d = b.  WF = +inf: hr = +inf, d = a.  NaN area: the
+ *      guard fails.  A column in no cell: d = 0.0, and every other output keeps the bits of the plain stage.  A context in which no cell
+ *      is flooded keeps the bits of the stage without the extension on every existing row, column and cell.
+ * elmk_floodplain_infiltration_read copies columns [col0, col0 + n) of one of the three column rows; elmk_routing_read takes
+ * ELMK_ROUTE_QLAND only while the extension is on.  The three column rows and QLAND are diagnostics that the next step rewrites: there is
+ * no new prognostic row.  Restart: WF is in version 6 and later; F1 also reads FLOOD_FRAC as the last routing call left it, a
+ * diagnostic that a load leaves zero, so under ELMK_OPT_RESTART_CELLS a context with the extension on saves one more cell section,
+ * ELMK_ROUTE_FLOOD_FRAC, behind the others (the version stays what the other stages make it); such an image loads only into a context
+ * with the extension on, and 3 + 3 steps through it give the bits of 6.  Every other context saves byte for byte what it saved before.
+ * With the option off elmk_routing_inundation_init leaves FLOOD_FRAC zero, so the first step after such a restart drains nothing.
+ * While the extension is on elmk_routing_inundation_clear, elmk_soil_hydrology_clear, elmk_water_balance_clear, elmk_set_output_grid and
+ * elmk_clear_output_grid are refused with ELMK_E_INVALID ("elmk_floodplain_infiltration_clear first"); elmk_routing_clear frees it with
+ * the rest.  Enable and clear drop the captured run step.
+ * Tapes: ELMK_ROWS_FLOODPLAIN (which = ELMK_FPI_*) for elmk_column_history_add_row / elmk_gridded_history_add_row, and
+ * elmk_cell_history_add_row(ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_QLAND), both while the extension is on; while such an entry exists
+ * elmk_floodplain_infiltration_clear is refused ("elmk_history_clear first").
+ * A context that never enables it runs the kernels, launch sequences and graphs it ran before, allocates nothing more and saves the image
+ * it saved before.  Out of scope: evaporation from floodplain water, which needs an energy balance of its own. */
+enum { ELMK_FPI_H2OROF = 0, ELMK_FPI_FRAC = 1, ELMK_FPI_QFLX_DRAIN = 2, ELMK_FPI_NROWS = 3 };
+enum { ELMK_ROUTE_QLAND = 20 };
+int elmk_floodplain_infiltration_enable(elmk_ctx *ctx);
+int elmk_floodplain_infiltration_read(elmk_ctx *ctx, int which /*ELMK_FPI_**/, double *host, int64_t col0, int64_t n);
+int elmk_floodplain_infiltration_budget(elmk_ctx *ctx, double *sums /*[1]: the sum of QLAND, through R6's reduction kernels*/);
+int elmk_floodplain_infiltration_clear(elmk_ctx *ctx);
+
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.
  * These two entries register one such row, over the columns (elmk_column_history_add_row; the six elmk_history_* entries of "history"
@@ -1448,6 +1508,9 @@ int elmk_routing_heat_clear(elmk_ctx *ctx);
  * ELMK_RESTART_ROW_FIELD(family, which), a value no field id reaches, so a loader from before row entries refuses the image as a
  * history table other than its own.  Images of contexts without row entries are what they were. */
 enum { ELMK_ROWS_ALT = 0, ELMK_ROWS_HYDROLOGY = 1, ELMK_ROWS_FROST = 2, ELMK_ROWS_WATER_BALANCE = 3, ELMK_ROWS_IRRIGATION = 4, ELMK_ROWS_NFAMILY = 5 };
+/* the floodplain infiltration's three column rows (which = ELMK_FPI_*): the family's number lies past the cell-row families', which the
+ * restart image numbers from ELMK_ROWS_NFAMILY on, so that every image keeps the numbers it had */
+enum { ELMK_ROWS_FLOODPLAIN = 7 };
 #define ELMK_RESTART_ROW_BASE 0x40000000
 #define ELMK_RESTART_ROW_FIELD(family, which) (ELMK_RESTART_ROW_BASE + ((family) << 16) + (which))
 int elmk_column_history_add_row(elmk_ctx *ctx, int tape, int family, int which, int op);

@@ -445,6 +445,16 @@ class ELMInterface {
   void routing_heat_init(const double* tt = nullptr, const double* tr = nullptr) { ok(elmk_routing_heat_init(ctx_, tt, tr)); }
   void routing_heat_budget(double* sums) { ok(elmk_routing_heat_budget(ctx_, sums)); }
   void routing_heat_clear() { ok(elmk_routing_heat_clear(ctx_)); }
+  /* Floodplain infiltration (elmk.h "floodplain infiltration"): the floodplain's water infiltrates the soil columns of its cell, and the
+   * routing takes it out of WF.  floodplain_infiltration_enable() after soil_hydrology_enable, water_balance_enable,
+   * routing_kinematic_enable and routing_inundation_enable, over an output grid with every column in at most one cell; soil_hydrology,
+   * water_balance, routing and run() then take their forms with the term.  floodplain_infiltration_read() copies one of the column rows
+   * ELMK_FPI_* ([ncols]), routing_read() takes ELMK_ROUTE_QLAND as well, floodplain_infiltration_budget() fills sums[1];
+   * floodplain_infiltration_clear() returns to the stages without the term and keeps WF. */
+  void floodplain_infiltration_enable() { ok(elmk_floodplain_infiltration_enable(ctx_)); }
+  void floodplain_infiltration_read(int which, double* host) { ok(elmk_floodplain_infiltration_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
+  void floodplain_infiltration_budget(double* sums) { ok(elmk_floodplain_infiltration_budget(ctx_, sums)); }
+  void floodplain_infiltration_clear() { ok(elmk_floodplain_infiltration_clear(ctx_)); }
   /* History entries over one fp64 row of a feature (elmk.h "feature rows on history tapes"): family ELMK_ROWS_*, which the family's
    * row number; as history_add / gridded_history_add otherwise, one level.  While such an entry exists the family's clear is refused. */
   int history_add_row(int tape, int family, int which, int op)
