@@ -169,6 +169,9 @@ SIGNATURES = {
     "elmk_routing_reservoir_time": (C.c_int, [_P, C.c_int, C.c_int]),
     "elmk_routing_reservoir_budget": (C.c_int, [_P, _P]),
     "elmk_routing_reservoir_clear": (C.c_int, [_P]),
+    "elmk_routing_command_enable": (C.c_int, [_P, _P, _P, _P]),
+    "elmk_routing_command_budget": (C.c_int, [_P, _P]),
+    "elmk_routing_command_clear": (C.c_int, [_P]),
     "elmk_routing_heat_enable": (C.c_int, [_P, C.c_int, _P]),
     "elmk_routing_heat_init": (C.c_int, [_P, _P, _P]),
     "elmk_routing_heat_budget": (C.c_int, [_P, _P]),

@@ -16,7 +16,8 @@ static void irrsup_launch(elmk_ctx* ctx, int idt)
   const CsrMap& M = ctx->ogrid.map;
   launch_irrigation_supply(ctx->ncols, ctx->irr_rows, ctx->ld, idt, OGridMap{M.ptr, M.col, M.w, M.nrows, 0.0}, T.area,
                            T.rows + (size_t)ROUTE_VOLR * (size_t)T.cld, ctx->irrsup_thr, ctx->irrsup_rows, T.cld, ctx->stream, T.dam.rows,
-                           T.dam.tab);  // (D7 while the reservoirs are on)
+                           T.dam.tab,  // (D7 while the reservoirs are on)
+                           T.cmd.mem ? T.cmd_dam : nullptr, T.cmd.mem ? T.cmd.tab + (size_t)CMD_NDEP * (size_t)T.cld : nullptr);  // (C6)
 }
 
 void irr_run_launch(elmk_ctx* ctx, double dt)

@@ -1,5 +1,5 @@
 // api_routing.cpp - the river stage (k_routing.hip; include/elmk.h "runoff routing", "kinematic-wave routing", "floodplain inundation",
-// "reservoirs", "stream temperature", "floodplain infiltration").  The stage has six parts, each with one allocation held exactly while the part is on (elmk_ctx.h: Routing): the
+// "reservoirs", "stream temperature", "floodplain infiltration", "command areas").  The stage has seven parts, each with one allocation held exactly while the part is on (elmk_ctx.h: Routing): the
 // base part, the kinematic-wave scheme on top of it, and that scheme's three extensions.  The table PARTS describes each part once - its
 // rows, its public row ids, what its budget reduces, what the restart image keeps of it, what it needs and how its refusals read - and
 // the part_* helpers below are what the five families of entry points share: how a call enters, how an enable, an init, a budget and a
@@ -9,7 +9,7 @@
 namespace {
 using Routing = elmk_ctx::Routing;
 
-enum { BASE, KW, FP, DAM, HEAT, LAND, NPARTS };
+enum { BASE, KW, FP, DAM, HEAT, LAND, CMD, NPARTS };
 struct PartDesc {
   Routing::Part Routing::*at;  // where the part is held (null: the base part, in Routing itself)
   int needs;                   // the part that has to be on before this one (-1: none)
@@ -45,7 +45,10 @@ constexpr PartDesc PARTS[NPARTS] = {
     // (the floodplain infiltration: its cell row QLAND; the three column rows and cellof lie behind it in the same allocation)
     // (F1 reads FLOOD_FRAC as the last call left it, so with the extension on the image keeps that row as well: state)
     {&Routing::land, FP, 1, ELMK_ROUTE_QLAND, 1, {0}, 1, 1, {ELMK_ROUTE_FLOOD_FRAC}, "floodplain infiltration", "elmk_floodplain_infiltration_enable",
-     "elmk_floodplain_infiltration_clear", "the extension is not on", "row out of range", "the floodplain infiltration is on"}};
+     "elmk_floodplain_infiltration_clear", "the extension is not on", "row out of range", "the floodplain infiltration is on"},
+    // (the command areas: four diagnostic rows, nothing in the image; C5 reduces GIVE and TAKE, which lie first)
+    {&Routing::cmd, DAM, CMD_NROWS, ELMK_ROUTE_CMD_WANT, 4, {CMD_WANT, CMD_TAKE, CMD_GIVE, CMD_RATIO}, 2, 0, {0}, "command areas",
+     "elmk_routing_command_enable", "elmk_routing_command_clear", "the command areas are not on", "row out of range", "the command areas are on"}};
 static_assert(ELMK_ROUTE_VOLR == 0 && ELMK_ROUTE_QIN == 1 && ELMK_ROUTE_QOUT == 2 && ELMK_ROUTE_QOUT_SUM == 3, "four rows");
 static_assert(ELMK_ROUTE_WH - 4 == KW_WH && ELMK_ROUTE_WT - 4 == KW_WT && ELMK_ROUTE_QSUR - 4 == KW_QSUR, "three rows");
 static_assert(ELMK_KW_NPARAM == KINEMATIC_NPARAM, "the parameter rows of elmk_maps.h");
@@ -55,6 +58,8 @@ static_assert(ELMK_ROUTE_RES == 10 && ELMK_ROUTE_KRLS == 11 && ELMK_ROUTE_RES_TA
 static_assert(DAM_NTAB == RESERVOIR_NTAB && DAM_TARGET + RESERVOIR_NMONTH == DAM_NTAB, "the tables of elmk_maps.h");
 static_assert(ELMK_ROUTE_TT == 13 && ELMK_ROUTE_HOUT == 19 && HT_HEAT == 0 && HT_HIN == 1 && HT_HSRF == 2 && HT_HADJ == 3 && HT_OUTLET == 4, "seven rows; H7's five lead");
 static_assert(HEAT_NSUBLEV == 15, "the soil layers of elmk_maps.h");
+static_assert(ELMK_ROUTE_CMD_WANT == 21 && ELMK_ROUTE_CMD_RATIO == 24 && ELMK_CMD_NDEP == COMMAND_NDEP && CMD_NDEP == COMMAND_NDEP, "four rows, four slots");
+static_assert(PARTS[CMD].nstate == 0, "the command areas keep nothing in the image");
 // (the heat excludes the inundation and the reservoirs, so the image never holds more than the rows of the first four parts and the last)
 static_assert(PARTS[0].nstate + PARTS[1].nstate + PARTS[2].nstate + PARTS[3].nstate + PARTS[5].nstate == elmk::ROUTE_STATE_MAX &&
                   PARTS[0].nstate + PARTS[1].nstate + PARTS[4].nstate <= elmk::ROUTE_STATE_MAX, "the rows of the image");
@@ -83,6 +88,12 @@ void part_reset(Routing& T, int p)
   if (p == DAM) T.dam_mstart = nullptr, T.dam_time = 0;
   if (p == HEAT) T.heat_sublev = 0;
   if (p == LAND) T.land_cellof = nullptr;
+  if (p == CMD) {
+    T.cmd_ones = T.cmd_tshare = nullptr;
+    T.cmd_dam = T.cmd_dams = T.cmd_tcell = nullptr;
+    T.cmd_ptr = nullptr;
+    T.cmd_ndams = 0;
+  }
 }
 
 // the heat and the scheme's two other extensions exclude each other: "<who>: <on> (<clear> first)" while part q is on
@@ -130,6 +141,8 @@ int part_zero(elmk_ctx* ctx, int p)
 {
   const Routing& T = ctx->route;
   HIPCHK(hipMemsetAsync(part_rows(T, PARTS[p]), 0, (size_t)PARTS[p].nrows * (size_t)T.cld * sizeof(double), ctx->stream));
+  if (p == CMD)  // (RATIO's rest state is 1.0)
+    HIPCHK(hipMemcpyAsync(T.cmd.rows + (size_t)CMD_RATIO * (size_t)T.cld, T.cmd_ones, (size_t)T.cld * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   return ELMK_OK;
 }
 
@@ -219,7 +232,10 @@ void route_launch(elmk_ctx* ctx, double dt, bool run)
                              DamArgs{T.dam.rows, T.dam.tab, T.dam_mstart, run ? ctx->run.table : nullptr, run ? ctx->run.cursor : nullptr,
                                      T.dam_time},
                              H, G, qrunoff, qirr, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_SURF * ld, ctx->hyd_rows + (size_t)ELMK_HYD_QFLX_H2OSFC_SURF * ld, dt,
-                             ctx->stream, LandArgs{T.land.mem ? T.land.tab + (size_t)ELMK_FPI_QFLX_DRAIN * ld : nullptr, T.land.rows});
+                             ctx->stream, LandArgs{T.land.mem ? T.land.tab + (size_t)ELMK_FPI_QFLX_DRAIN * ld : nullptr, T.land.rows},
+                             T.cmd.mem ? CmdArgs{T.cmd.rows, T.cmd_dam, T.cmd.tab, T.cmd.tab + (size_t)CMD_NDEP * (size_t)T.cld, T.cmd_dams, T.cmd_ptr,
+                                                 T.cmd_tcell, T.cmd_tshare, T.cmd_ndams}
+                                       : CmdArgs{});
   } else {
     launch_routing(route_args(ctx), G, qrunoff, qirr, dt, ctx->stream);
   }
@@ -376,8 +392,10 @@ int elmk_routing_set_withdrawal(elmk_ctx* ctx, int on)
   const char* who = "elmk_routing_set_withdrawal";
   if (int rc = part_enter(ctx, BASE, who)) return rc;
   if (on && !ctx->irr_rows) return invalid(ctx, "elmk_routing_set_withdrawal: the irrigation is not enabled (elmk_irrigation_enable)");
-  if (!on)
+  if (!on) {
     if (int rc = irrsup_holds(ctx, who)) return rc;  // (the limit grants water that only the withdrawal takes out of VOLR)
+    if (int rc = part_excludes(ctx, CMD, who)) return rc;  // (C1 forms WANT from the withdrawal)
+  }
   if (int rc = refuse_capture(ctx, who)) return rc;
   ctx->route.withdraw = on != 0;  // (the captured run step is keyed by it)
   return ELMK_OK;
@@ -523,6 +541,57 @@ int elmk_routing_reservoir_time(elmk_ctx* ctx, int month, int begins)
 int elmk_routing_reservoir_budget(elmk_ctx* ctx, double* sums) { return part_budget(ctx, DAM, "elmk_routing_reservoir_budget", sums); }
 
 int elmk_routing_reservoir_clear(elmk_ctx* ctx) { return part_clear(ctx, DAM, "elmk_routing_reservoir_clear"); }
+
+int elmk_routing_command_enable(elmk_ctx* ctx, const int32_t* dam, const double* share, const double* claim)
+{
+  const char* who = "elmk_routing_command_enable";
+  if (int rc = part_enter(ctx, DAM, who)) return rc;  // (the routing, its kinematic-wave scheme, the reservoirs: each refusal says which)
+  Routing& T = ctx->route;
+  if (!T.withdraw) return invalid(ctx, "elmk_routing_command_enable: the routing's withdrawal is not on (elmk_routing_set_withdrawal)");
+  if (T.cmd.mem) return invalid(ctx, "elmk_routing_command_enable: already on");
+  if (!dam || !share || !claim) return invalid(ctx, "elmk_routing_command_enable: null argument");
+  if (int rc = refuse_capture(ctx, who)) return rc;
+  const size_t cld = (size_t)T.cld, n = (size_t)T.ncells;
+  // the check reads CAP: the device holds the only copy
+  std::vector<double> cap(n);
+  HIPCHK(hipMemcpyAsync(cap.data(), T.dam.tab + DAM_CAP * cld, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  CommandTables C;
+  int64_t cell = -1;
+  const char* const text = command_check(T.ncells, cap.data(), dam, share, claim, T.cld, &C, &cell);
+  if (int rc = invalid_at(ctx, who, text, cell)) return rc;
+  if (int rc = quiesce(ctx, false)) return rc;  // (the captured run step holds the launches of its moment)
+  const std::vector<double> one(cld, 1.0);
+  const size_t ndams = C.dams.size(), nnz = C.tcell.size();
+  T.cmd_ndams = (int64_t)ndams;
+  return part_on(
+      ctx, CMD,
+      [&](Carve& L) {
+        L.take(T.cmd.rows, (size_t)CMD_NROWS * cld * sizeof(double));
+        L.take(T.cmd.tab, (size_t)2 * CMD_NDEP * cld * sizeof(double));
+        L.take(T.cmd_ones, cld * sizeof(double));
+        L.take(T.cmd_dam, (size_t)CMD_NDEP * cld * sizeof(int32_t));
+        L.take(T.cmd_dams, (ndams + 1) * sizeof(int32_t));
+        L.take(T.cmd_ptr, (ndams + 1) * sizeof(int64_t));
+        L.take(T.cmd_tcell, (nnz + 1) * sizeof(int32_t));
+        L.take(T.cmd_tshare, (nnz + 1) * sizeof(double));
+      },
+      [&] {
+        return upload(ctx, T.cmd.tab, C.share.data(), C.share.size(), "hipMemcpy(command areas SHARE)") ||
+               upload(ctx, T.cmd.tab + CMD_NDEP * cld, C.claim.data(), C.claim.size(), "hipMemcpy(command areas CLAIM)") ||
+               upload(ctx, T.cmd_ones, one.data(), cld, "hipMemcpy(command areas ones)") ||
+               upload(ctx, T.cmd.rows + CMD_RATIO * cld, one.data(), cld, "hipMemcpy(command areas RATIO)") ||
+               upload(ctx, T.cmd_dam, C.dam.data(), C.dam.size(), "hipMemcpy(command areas DAM)") ||
+               (ndams && upload(ctx, T.cmd_dams, C.dams.data(), ndams, "hipMemcpy(command areas dams)")) ||
+               upload(ctx, T.cmd_ptr, C.ptr.data(), C.ptr.size(), "hipMemcpy(command areas ptr)") ||
+               (nnz && (upload(ctx, T.cmd_tcell, C.tcell.data(), nnz, "hipMemcpy(command areas terms)") ||
+                        upload(ctx, T.cmd_tshare, C.tshare.data(), nnz, "hipMemcpy(command areas terms' share)")));
+      });
+}
+
+int elmk_routing_command_budget(elmk_ctx* ctx, double* sums) { return part_budget(ctx, CMD, "elmk_routing_command_budget", sums); }
+
+int elmk_routing_command_clear(elmk_ctx* ctx) { return part_clear(ctx, CMD, "elmk_routing_command_clear"); }
 
 int elmk_routing_heat_enable(elmk_ctx* ctx, int sublev, const double* shade)
 {

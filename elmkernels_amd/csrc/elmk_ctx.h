@@ -166,10 +166,11 @@ struct StepKey {
   bool route_dam = false;                    // the routing stage is in the step and takes the reservoirs' form (its time from the pad word)
   bool route_heat = false;                   // the routing stage is in the step and takes the stream temperature's form
   bool land = false;                         // the floodplain infiltration is on: the hydrology, water balance and routing stages take its forms
+  bool route_cmd = false;                    // the command areas are on: the routing stage has their two launches, the supply limit their form
   auto tie() const
   {
     return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw,
-                    irr_supply, route_dam, route_heat, land);
+                    irr_supply, route_dam, route_heat, land, route_cmd);
   }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
@@ -291,7 +292,7 @@ struct elmk_ctx {
   // while the limit is on
   DevBuf<double> irrsup_rows;
   double irrsup_thr = 0.0;
-  // The river stage (elmk_routing_*) has five parts, each with one allocation held exactly while the part is on; api_routing.cpp's
+  // The river stage (elmk_routing_*) has seven parts, each with one allocation held exactly while the part is on; api_routing.cpp's
   // table PARTS says the rest about each (rows, public ids, budget, restart rows, refusals).
   //   base (elmk_routing_enable): `mem` holds the rows [ROUTE_NROWS][cld], KOUT and area [cld], the upstream map [npad][cld], down
   //     [cld] and the budgets' reduction partials [3][ELMK_CONS_NPART][3] and triples [3][3].  ncalls: the calls since the last
@@ -303,6 +304,9 @@ struct elmk_ctx {
   //   heat (elmk_routing_heat_*): the stream temperature's rows [HT_NROWS][cld]; tab: KSW [cld].  heat_sublev: the soil layer of H1
   //   land (elmk_floodplain_infiltration_*): the cell row QLAND [1][cld]; tab: the three column rows [ELMK_FPI_NROWS][ld]; beside them, in
   //     the same allocation, cellof [ld] (land_cellof; -1 in the padding columns)
+  //   cmd (elmk_routing_command_*): the command areas' rows [CMD_NROWS][cld]; tab: share and claim [2][CMD_NDEP][cld]; beside them, in
+  //     the same allocation, a row of 1.0 [cld] (what RATIO is reset from), the cells' dam row [CMD_NDEP][cld] (cmd_dam) and the inverse
+  //     map: cmd_dams [cmd_ndams], cmd_ptr [cmd_ndams + 1], cmd_tcell and cmd_tshare [terms]
   // route_launch takes the scheme and the forms whose memory is there.
   struct Routing {
     struct Part {
@@ -322,7 +326,11 @@ struct elmk_ctx {
     int32_t* down = nullptr;
     double* part = nullptr;
     double* out = nullptr;
-    Part kw, fp, dam, heat, land;
+    Part kw, fp, dam, heat, land, cmd;
+    double *cmd_ones = nullptr, *cmd_tshare = nullptr;
+    int32_t *cmd_dam = nullptr, *cmd_dams = nullptr, *cmd_tcell = nullptr;
+    int64_t* cmd_ptr = nullptr;
+    int64_t cmd_ndams = 0;
     int32_t* land_cellof = nullptr;
     int32_t* dam_mstart = nullptr;
     int32_t dam_time = 0;

@@ -267,9 +267,11 @@ void launch_irrigation_run(const DevState* S, int64_t n, double* rows, const int
 // supply limit", one launch behind launch_irrigation / launch_irrigation_run with the same idt.  irr_rows: the irrigation's rows [3][ld];
 // M: the output grid's map (every column in at most one cell); area, volr: the routing's [cld]; sup_rows: the limit's rows [4][cld];
 // dam_rows, dam_tab: the reservoirs' rows and tables (below: DAM_*) while they are on - S3 takes D7's form - else null
+// cmd_dam, cmd_claim: the command areas' ELL rows [CMD_NDEP][cld] while they are on (dam_rows not null) - S3 takes C6's form - else null
 void launch_irrigation_supply(int64_t ncols, double* irr_rows, int64_t ld, int idt, const OGridMap& M, const double* area,
                               const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st,
-                              const double* dam_rows = nullptr, const double* dam_tab = nullptr);
+                              const double* dam_rows = nullptr, const double* dam_tab = nullptr, const int32_t* cmd_dam = nullptr,
+                              const double* cmd_claim = nullptr);
 
 // soil hydrology (k_soil_hydrology.hip, elmk_soil_hydrology): one stage over every column; rows = the ELMK_HYD_NROWS fp64 rows of
 // the feature, [row][ld]; frost_rows = the ELMK_HYDF_NROWS rows of the frost-table extension, which select the F' form of the kernel, or
@@ -379,9 +381,27 @@ struct LandArgs {
   const double* qdrain;  // [ld]: the floodplain infiltration's QFLX_H2OROF_DRAIN
   double* qland;         // [cld]
 };
+// command areas (elmk_routing_command_*; include/elmk.h "command areas", C0 - C8): the part's fp64 rows [CMD_NROWS][cld] - the first two
+// are the ones launch_min_max_sum reduces for C5 - the cells' ELL rows dam (int32, -1 = empty), share and claim [CMD_NDEP][cld], and the
+// inverse map, a CSR over the dam list: dams [ndams] (the dam cells, ascending), ptr [ndams + 1], and the terms' cell and share in CSR
+// order.  rows not null (Dm.rows not null, qirr not null): the K1 launch takes the CMD form (C1) and k_command_allot (C2) and
+// k_command_take (C3) follow it before the first sub-step.
+enum { CMD_GIVE = 0, CMD_TAKE = 1, CMD_WANT = 2, CMD_RATIO = 3, CMD_NROWS = 4 };
+constexpr int CMD_NDEP = 4;
+struct CmdArgs {
+  double* rows = nullptr;
+  const int32_t* dam = nullptr;    // [CMD_NDEP][cld]
+  const double* share = nullptr;   // [CMD_NDEP][cld]
+  const double* claim = nullptr;   // [CMD_NDEP][cld]
+  const int32_t* dams = nullptr;   // [ndams]
+  const int64_t* ptr = nullptr;    // [ndams + 1]
+  const int32_t* tcell = nullptr;  // [nterms]
+  const double* tshare = nullptr;  // [nterms]
+  int64_t ndams = 0;
+};
 void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const HeatArgs& H, const OGridMap& M,
                               const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc, double dt,
-                              hipStream_t st, const LandArgs& L = LandArgs{nullptr, nullptr});
+                              hipStream_t st, const LandArgs& L = LandArgs{nullptr, nullptr}, const CmdArgs& C = CmdArgs{});
 
 // restart images (k_restart.hip, elmk_restart_*): one piece = n consecutive elements of one row, at dev (stored type sdtype, as
 // HistRow::dtype) and at chunk + img_off (image type adtype, an elmk_dtype); g0 = global column (or cell) of its first element

@@ -328,6 +328,110 @@ inline const char* heat_check(int64_t ncells, int sublev, const double* shade, i
   return nullptr;
 }
 
+// Command areas (elmk_routing_command_enable; include/elmk.h "command areas"): cap [ncells], the reservoirs' CAP (a dam: > 0.0), and
+// the cells' three ELL rows [COMMAND_NDEP][ncells]: dam, int32, the cell of a supplying dam or -1 for an empty slot, filled from slot 0
+// without gaps; share in (0, 1]; claim in [0, 1].  Checks, in this order: the arguments; per cell in index order and per slot in slot
+// order: the index in range, no filled slot behind an empty one, a cell with a reservoir, not the cell itself, not a dam of an earlier
+// slot, share, claim; behind the slots the cell's shares added in slot order; then per dam in the order of the dam list its claims
+// added in the order of its terms.  Returns the text, which names the row, and in *cell the first offending cell - for the claims' sum
+// the dam's cell - (-1 where the text is about no cell); the entry point puts " at cell <cell>" behind the text.  nullptr: accepted.
+// For accepted inputs and out not null, out holds what the device reads: the ELL rows [COMMAND_NDEP][ld] with ld >= ncells (padding
+// cells and empty slots: dam -1, share and claim 0.0) and the inverse map - dams: every cell with cap > 0.0 in ascending order, those
+// without dependents included; ptr [ndams + 1]; the terms (cell, slot) sorted by cell and then slot, with their share.  Linear time, no
+// recursion: one count per dam, a prefix sum, and one pass over the cells in index order.
+constexpr int COMMAND_NDEP = 4;
+struct CommandTables {
+  std::vector<int32_t> dam;          // [COMMAND_NDEP][ld]
+  std::vector<double> share, claim;  // [COMMAND_NDEP][ld]
+  std::vector<int32_t> dams;         // [ndams]
+  std::vector<int64_t> ptr;          // [ndams + 1]
+  std::vector<int32_t> tcell, tslot;  // [nterms]
+  std::vector<double> tshare;         // [nterms]
+};
+inline const char* command_check(int64_t ncells, const double* cap, const int32_t* dam, const double* share, const double* claim, int64_t ld,
+                                 CommandTables* out, int64_t* cell)
+{
+  if (cell) *cell = -1;
+  if (ncells < 1 || ncells > INT32_MAX) return "ncells outside 1 .. 2^31-1";
+  if (!cap || !dam || !share || !claim) return "null argument";
+  const size_t n = (size_t)ncells;
+  const auto at = [cell](const char* what, size_t c) {
+    if (cell) *cell = (int64_t)c;
+    return what;
+  };
+  std::vector<int64_t> count(n, 0);  // per cell: the terms of the dam that stands there
+  for (size_t c = 0; c < n; c++) {
+    bool empty = false;
+    double sum = 0.0;
+    for (int k = 0; k < COMMAND_NDEP; k++) {
+      const int64_t d = dam[(size_t)k * n + c];
+      if (d < -1 || d >= ncells) return at("DAM outside [-1, ncells)", c);
+      if (d < 0) {
+        empty = true;
+        continue;
+      }
+      if (empty) return at("DAM filled behind an empty slot", c);
+      if (!(cap[d] > 0.0)) return at("DAM names a cell without a reservoir", c);
+      if (d == (int64_t)c) return at("DAM names the cell itself", c);
+      for (int j = 0; j < k; j++)
+        if (dam[(size_t)j * n + c] == d) return at("DAM names one reservoir twice", c);
+      const double s = share[(size_t)k * n + c], q = claim[(size_t)k * n + c];
+      if (!(std::isfinite(s) && s > 0.0 && s <= 1.0)) return at("SHARE outside (0, 1]", c);
+      if (!(q >= 0.0 && q <= 1.0)) return at("CLAIM outside [0, 1]", c);
+      sum = k == 0 ? s : sum + s;
+      count[(size_t)d]++;
+    }
+    if (!(sum <= 1.0)) return at("SHARE sums to more than 1", c);
+  }
+  CommandTables T;
+  std::vector<int64_t> slot_of(n, -1);  // per cell: its place in the dam list
+  for (size_t c = 0; c < n; c++)
+    if (cap[c] > 0.0) {
+      slot_of[c] = (int64_t)T.dams.size();
+      T.dams.push_back((int32_t)c);
+    }
+  T.ptr.assign(T.dams.size() + 1, 0);
+  for (size_t j = 0; j < T.dams.size(); j++) T.ptr[j + 1] = T.ptr[j] + count[(size_t)T.dams[j]];
+  const size_t nnz = (size_t)T.ptr.back();
+  T.tcell.assign(nnz, 0);
+  T.tslot.assign(nnz, 0);
+  T.tshare.assign(nnz, 0.0);
+  std::vector<double> tclaim(nnz, 0.0);
+  std::vector<int64_t> fill(T.ptr.begin(), T.ptr.end() - 1);
+  for (size_t c = 0; c < n; c++)  // cells ascending, slots ascending: every dam's terms come out sorted by cell and then slot
+    for (int k = 0; k < COMMAND_NDEP; k++) {
+      const int64_t d = dam[(size_t)k * n + c];
+      if (d < 0) break;
+      const size_t p = (size_t)fill[(size_t)slot_of[(size_t)d]]++;
+      T.tcell[p] = (int32_t)c;
+      T.tslot[p] = k;
+      T.tshare[p] = share[(size_t)k * n + c];
+      tclaim[p] = claim[(size_t)k * n + c];
+    }
+  for (size_t j = 0; j < T.dams.size(); j++) {
+    double sum = 0.0;
+    for (int64_t p = T.ptr[j]; p < T.ptr[j + 1]; p++) sum = p == T.ptr[j] ? tclaim[(size_t)p] : sum + tclaim[(size_t)p];
+    if (!(sum <= 1.0)) return at("CLAIM sums to more than 1", (size_t)T.dams[j]);
+  }
+  if (out) {
+    if (ld < ncells) ld = ncells;
+    const size_t l = (size_t)ld;
+    T.dam.assign((size_t)COMMAND_NDEP * l, -1);
+    T.share.assign((size_t)COMMAND_NDEP * l, 0.0);
+    T.claim.assign((size_t)COMMAND_NDEP * l, 0.0);
+    for (size_t c = 0; c < n; c++)
+      for (int k = 0; k < COMMAND_NDEP; k++) {
+        const int32_t d = dam[(size_t)k * n + c];
+        if (d < 0) break;
+        T.dam[(size_t)k * l + c] = d;
+        T.share[(size_t)k * l + c] = share[(size_t)k * n + c];
+        T.claim[(size_t)k * l + c] = claim[(size_t)k * n + c];
+      }
+    *out = std::move(T);
+  }
+  return nullptr;
+}
+
 // The reservoirs' calendar, the reference's no-leap year: the month 0 .. 11 of day-of-year doy (0 = 1 January; any other doy is taken
 // modulo 365), and whether a step with (doy, decday) starts at 00:00 of the first day of its month: the active layer's rollover test,
 // decday == doy + 1.0, on the first doy of each month.

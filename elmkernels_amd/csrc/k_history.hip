@@ -387,12 +387,23 @@ struct SupDam<true> {
   gptr<const double> res, smin, cap;  // [cld] each
 };
 
+// C6 (include/elmk.h "command areas"): while the command areas are on too, a cell's claims on the usable storage of the dams that
+// supply it count as available as well; dam and claim are the cells' ELL rows [CMD_NDEP][cld]
+template <bool CMD>
+struct SupCmd {};  // the plain form takes nothing: its kernel arguments, instructions and registers stay what they were
+template <>
+struct SupCmd<true> {
+  gptr<const int32_t> dam;
+  gptr<const double> claim;
+};
+
 // grid (ceil(ncells / SUP_CELLS)); irr = the irrigation's rows [3][ld], sup = the limit's rows [4][cld]
-template <bool DAM = false>
+template <bool DAM = false, bool CMD = false>
 __global__ __launch_bounds__(SUP_THREADS) void k_irrigation_supply(gptr<double> irr, int64_t ld, int idt, int nspd, OGridMap M,
                                                                    gptr<const double> area, gptr<const double> volr, double thr,
-                                                                   gptr<double> sup, int64_t cld, SupDam<DAM> dm)
+                                                                   gptr<double> sup, int64_t cld, SupDam<DAM> dm, SupCmd<CMD> cm)
 {
+  static_assert(!CMD || DAM, "the command areas need the reservoirs");
   __shared__ double tile_d[SUP_TILE];
   __shared__ double tile_c[SUP_TILE];
   __shared__ double ratio_s[SUP_CELLS];
@@ -452,6 +463,24 @@ __global__ __launch_bounds__(SUP_THREADS) void k_irrigation_supply(gptr<double> 
         a = a + (r > 0.0 ? r : 0.0);
       }
     }
+    if constexpr (CMD) {  // C6: every slot's loads are issued before the sum; an empty slot reads the cell's own rows and adds nothing
+      int32_t d[CMD_NDEP];
+      double cl[CMD_NDEP], rs[CMD_NDEP], sm[CMD_NDEP];
+#pragma unroll
+      for (int k = 0; k < CMD_NDEP; k++) d[k] = cm.dam[(int64_t)k * cld + c];
+#pragma unroll
+      for (int k = 0; k < CMD_NDEP; k++) {
+        const int64_t j = d[k] >= 0 ? (int64_t)d[k] : c;
+        cl[k] = cm.claim[(int64_t)k * cld + c];
+        rs[k] = dm.res[j];
+        sm[k] = dm.smin[j];
+      }
+#pragma unroll
+      for (int k = 0; k < CMD_NDEP; k++) {
+        const double r = rs[k] - sm[k];
+        if (d[k] >= 0) a = a + cl[k] * (r > 0.0 ? r : 0.0);
+      }
+    }
     a = a - Vc;
     const double avail = a > 0.0 ? a : 0.0;
     const double ratio = Vd > avail ? avail / Vd : 1.0;  // S4
@@ -484,19 +513,25 @@ __global__ __launch_bounds__(SUP_THREADS) void k_irrigation_supply(gptr<double> 
 
 void launch_irrigation_supply(int64_t ncols, double* irr_rows, int64_t ld, int idt, const OGridMap& M, const double* area,
                               const double* volr, double thr, double* sup_rows, int64_t cld, hipStream_t st, const double* dam_rows,
-                              const double* dam_tab)
+                              const double* dam_tab, const int32_t* cmd_dam, const double* cmd_claim)
 {
   if (ncols <= 0 || M.ncells <= 0) return;
   const int nspd = (14400 + (idt - 1)) / idt;
   const dim3 grid((unsigned)((M.ncells + SUP_CELLS - 1) / SUP_CELLS));
-  if (dam_rows)
-    hipLaunchKernelGGL(k_irrigation_supply<true>, grid, dim3(SUP_THREADS), 0, st, (gptr<double>)irr_rows, ld, idt, nspd, M,
-                       (gptr<const double>)area, (gptr<const double>)volr, thr, (gptr<double>)sup_rows, cld,
-                       SupDam<true>{(gptr<const double>)(dam_rows + DAM_RES * cld), (gptr<const double>)(dam_tab + DAM_SMIN * cld),
-                                    (gptr<const double>)(dam_tab + DAM_CAP * cld)});
-  else
-    hipLaunchKernelGGL(k_irrigation_supply<false>, grid, dim3(SUP_THREADS), 0, st, (gptr<double>)irr_rows, ld, idt, nspd, M,
-                       (gptr<const double>)area, (gptr<const double>)volr, thr, (gptr<double>)sup_rows, cld, SupDam<false>{});
+  if (dam_rows) {
+    const SupDam<true> dm{(gptr<const double>)(dam_rows + DAM_RES * cld), (gptr<const double>)(dam_tab + DAM_SMIN * cld),
+                          (gptr<const double>)(dam_tab + DAM_CAP * cld)};
+    if (cmd_dam)
+      hipLaunchKernelGGL((k_irrigation_supply<true, true>), grid, dim3(SUP_THREADS), 0, st, (gptr<double>)irr_rows, ld, idt, nspd, M,
+                         (gptr<const double>)area, (gptr<const double>)volr, thr, (gptr<double>)sup_rows, cld, dm,
+                         SupCmd<true>{(gptr<const int32_t>)cmd_dam, (gptr<const double>)cmd_claim});
+    else
+      hipLaunchKernelGGL((k_irrigation_supply<true, false>), grid, dim3(SUP_THREADS), 0, st, (gptr<double>)irr_rows, ld, idt, nspd, M,
+                         (gptr<const double>)area, (gptr<const double>)volr, thr, (gptr<double>)sup_rows, cld, dm, SupCmd<false>{});
+  } else {
+    hipLaunchKernelGGL((k_irrigation_supply<false, false>), grid, dim3(SUP_THREADS), 0, st, (gptr<double>)irr_rows, ld, idt, nspd, M,
+                       (gptr<const double>)area, (gptr<const double>)volr, thr, (gptr<double>)sup_rows, cld, SupDam<false>{}, SupCmd<false>{});
+  }
 }
 
 }  // namespace elmk

@@ -341,18 +341,30 @@ struct LandRows<true> {
   double dt;
 };
 
+// ---- command areas (include/elmk.h "command areas", C0 - C8; elmkernels_amd/routing.py: command_allot, command_take) -------------------
+// The CMD form of the K1 launch (k_kinematic_prep_cmd): a cell with a filled slot (dam[0] >= 0: slots fill from slot 0) reads 4 bytes more and writes WANT.
+template <bool CMD>
+struct CmdRows {};  // the plain form takes nothing: its kernel arguments, instructions and registers stay what they were
+template <>
+struct CmdRows<true> {
+  gptr<const int32_t> dam0;  // [cld]: slot 0 of the cells' ELL row
+  gptr<double> want;         // [cld]
+};
+
 // K1: QIN as k_routing_qin, QSUR from the hydrology's two surface rows in the same order, QSUB, and the er of the first sub-step.
-// DAM: D1, D2 and the first sub-step's D3 for the dam cells.  HEAT: H1.  LAND: F5
-template <bool WITHDRAW, bool DAM = false, bool HEAT = false, bool LAND = false>
-__global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
-                                                        gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
-                                                        gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
-                                                        gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
-                                                        gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<DAM> dm,
-                                                        HeatRows<HEAT> ht, LandRows<LAND> ln)
+// DAM: D1, D2 and the first sub-step's D3 for the dam cells.  HEAT: H1.  LAND: F5.  CMD: C1.  The body of both kernels below.
+namespace {
+template <bool WITHDRAW, bool DAM, bool HEAT, bool LAND, bool CMD>
+__device__ __forceinline__ void kinematic_prep(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
+                                               gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
+                                               gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
+                                               gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
+                                               gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<DAM> dm,
+                                               HeatRows<HEAT> ht, LandRows<LAND> ln, CmdRows<CMD> cm)
 {
   static_assert(!(HEAT && DAM), "the heat and the reservoirs exclude each other");
   static_assert(!(HEAT && LAND), "the heat excludes the inundation, and the infiltration with it");
+  static_assert(!CMD || (WITHDRAW && DAM), "the command areas need the withdrawal and the reservoirs");
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncells) return;
   const int64_t p0 = ptr[c], p1 = ptr[c + 1];
@@ -422,6 +434,12 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
         take = want > avail ? avail : want;
         res = res - take;
         qd = (rn * 0.001) * ar - (iv - take / dm.dt);
+        if constexpr (CMD) {  // C1: what the own dam did not cover
+          if (cm.dam0[c] >= 0) {
+            const double rest = iv - take / dm.dt;
+            cm.want[c] = rest > 0.0 ? rest * dm.dt : 0.0;
+          }
+        }
       }
       route_st(dm.rows + (DAM_TAKE * cld + c), take);
       route_st(qin + c, qd);
@@ -435,6 +453,12 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
   route_st(qin + c, q);
   route_st(qsur + c, qs);
   route_st(qsub + c, q - qs);
+  if constexpr (CMD) {  // C1
+    if (cm.dam0[c] >= 0) {
+      const double rest = (i * 0.001) * ar;
+      cm.want[c] = rest > 0.0 ? rest * dm.dt : 0.0;
+    }
+  }
   const double e0 = kw_chan(volr[c], par[KW_RLEN * cld + c], par[KW_RWIDTH * cld + c], par[KW_CR * cld + c], dts);
   er[c] = e0;
   if constexpr (HEAT) {  // H1
@@ -462,6 +486,31 @@ __global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr,
     ht.rows[HT_HOUT * cld + c] = 0.0;
     route_st(ht.hr_new + c, e0 * ht.rows[HT_TR * cld + c]);
   }
+}
+}  // namespace
+
+template <bool WITHDRAW, bool DAM = false, bool HEAT = false, bool LAND = false>
+__global__ __launch_bounds__(256) void k_kinematic_prep(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
+                                                        gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
+                                                        gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
+                                                        gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
+                                                        gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<DAM> dm,
+                                                        HeatRows<HEAT> ht, LandRows<LAND> ln)
+{
+  kinematic_prep<WITHDRAW, DAM, HEAT, LAND, false>(ptr, col, w, qrunoff, qirr, qsurf, qh2osfc, area, volr, par, qin, qsur, qsub, er, ncells, cld,
+                                                   dts, dm, ht, ln, CmdRows<false>{});
+}
+// the CMD form of the K1 launch (C1): the withdrawal and the reservoirs are on
+template <bool LAND>
+__global__ __launch_bounds__(256) void k_kinematic_prep_cmd(gptr<const int64_t> ptr, gptr<const int32_t> col, gptr<const double> w,
+                                                            gptr<const double> qrunoff, gptr<const double> qirr, gptr<const double> qsurf,
+                                                            gptr<const double> qh2osfc, gptr<const double> area, gptr<const double> volr,
+                                                            gptr<const double> par, gptr<double> qin, gptr<double> qsur, gptr<double> qsub,
+                                                            gptr<double> er, int64_t ncells, int64_t cld, double dts, DamRows<true> dm,
+                                                            LandRows<LAND> ln, CmdRows<true> cm)
+{
+  kinematic_prep<true, true, false, LAND, true>(ptr, col, w, qrunoff, qirr, qsurf, qh2osfc, area, volr, par, qin, qsur, qsub, er, ncells, cld, dts,
+                                                dm, HeatRows<false>{}, ln, cm);
 }
 
 // ---- floodplain inundation (include/elmk.h "floodplain inundation", I0 - I8; elmkernels_amd/routing.py: inundation_exchange) --------
@@ -639,6 +688,98 @@ __global__ __launch_bounds__(256) void k_kinematic_step(gptr<double> wh_row, gpt
   }
 }
 
+// C2: one sum per dam, over the inverse map - a CSR over the dam list whose terms (cell, share) lie in CSR order.  The shape is
+// k_irrigation_supply's: a workgroup takes CMD_DAMS consecutive dams, whose terms are one contiguous span.  It walks the span in tiles of
+// CMD_TILE terms; every thread forms the product share * WANT[cell] of its share of a tile - coalesced loads of the terms' cell and share,
+// a gather of WANT that is coalesced where a dam's dependents are neighbours - into an LDS tile, then lane t adds dam t's products out of
+// LDS in CSR order.  A product is one rounding whichever lane forms it and every sum is taken by one lane in term order: the numpy
+// restatement's bits, no atomics, and a dam with thousands of dependents has its loads spread over the workgroup.  CMD_DAMS = 64 and
+// CMD_TILE = 1024, SUP_CELLS' and SUP_TILE's reasons: a command area holds a handful of cells up to a few thousand, so a span of 64 dams
+// is mostly one or two tile passes, and the 8 KiB tile leaves the occupancy to the registers.  A dam without terms writes nothing (C0).
+namespace {
+constexpr int CMD_THREADS = 256, CMD_DAMS = 64, CMD_TILE = 1024;
+static_assert(CMD_DAMS < CMD_THREADS && CMD_TILE % CMD_THREADS == 0, "thread t <= CMD_DAMS loads ptr; whole passes over a tile");
+}  // namespace
+
+__global__ __launch_bounds__(CMD_THREADS) void k_command_allot(gptr<const int32_t> dams, gptr<const int64_t> ptr, gptr<const int32_t> tcell,
+                                                               gptr<const double> tshare, gptr<const double> want, gptr<double> res,
+                                                               gptr<const double> smin, gptr<double> give, gptr<double> ratio, int64_t ndams)
+{
+  __shared__ double tile[CMD_TILE];
+  __shared__ int64_t sp[CMD_DAMS + 1];
+  const int t = threadIdx.x;
+  const int64_t d0 = (int64_t)blockIdx.x * CMD_DAMS;
+  const int64_t d1 = d0 + CMD_DAMS < ndams ? d0 + CMD_DAMS : ndams;
+  const int nd = (int)(d1 - d0);
+  if (t <= nd) sp[t] = ptr[d0 + t];
+  __syncthreads();
+  const int64_t P0 = sp[0], P1 = sp[nd];
+  int64_t p0 = 0, p1 = 0;
+  if (t < nd) {
+    p0 = sp[t];
+    p1 = sp[t + 1];
+  }
+  double W = 0.0;
+  for (int64_t base = P0; base < P1; base += CMD_TILE) {
+    const int m = (int)(P1 - base < CMD_TILE ? P1 - base : CMD_TILE);
+#pragma unroll
+    for (int k = 0; k < CMD_TILE / CMD_THREADS; k++) {
+      const int q = k * CMD_THREADS + t;
+      if (q < m) tile[q] = tshare[base + q] * want[tcell[base + q]];
+    }
+    __syncthreads();
+    const int64_t lo = p0 > base ? p0 : base, hi = p1 < base + m ? p1 : base + m;
+    for (int64_t p = lo; p < hi; p++) {
+      const double x = tile[p - base];
+      W = p == p0 ? x : W + x;
+    }
+    __syncthreads();
+  }
+  if (t < nd && p1 > p0) {
+    const int64_t c = dams[d0 + t];
+    const double r = res[c];
+    const double a = r - smin[c];
+    const double avail = a > 0.0 ? a : 0.0;
+    const double rat = W > avail ? avail / W : 1.0;
+    const double G = W * rat;
+    route_st(res + c, r - G);
+    route_st(give + c, G);
+    route_st(ratio + c, rat);
+  }
+}
+
+// C3: one thread per cell, a plain gather over the cells' ELL rows; every slot's loads are issued before the sum, an empty slot reads the
+// cell's own RATIO and adds nothing.  A cell without a filled slot returns after its first load.
+__global__ __launch_bounds__(256) void k_command_take(gptr<const int32_t> dam, gptr<const double> share, gptr<const double> want,
+                                                      gptr<const double> ratio, gptr<double> take, gptr<double> qin, gptr<const double> qsur,
+                                                      gptr<double> qsub, int64_t ncells, int64_t cld, double dt)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncells) return;
+  int32_t d[CMD_NDEP];
+#pragma unroll
+  for (int k = 0; k < CMD_NDEP; k++) d[k] = dam[(int64_t)k * cld + c];
+  if (d[0] < 0) return;  // C0
+  const double wv = want[c];
+  double sh[CMD_NDEP], rt[CMD_NDEP];
+#pragma unroll
+  for (int k = 0; k < CMD_NDEP; k++) {
+    sh[k] = share[(int64_t)k * cld + c];
+    rt[k] = ratio[d[k] >= 0 ? (int64_t)d[k] : c];
+  }
+  double got = 0.0;
+#pragma unroll
+  for (int k = 0; k < CMD_NDEP; k++) {
+    const double x = (sh[k] * wv) * rt[k];
+    if (d[k] >= 0) got = k == 0 ? x : got + x;
+  }
+  route_st(take + c, got);
+  double q = qin[c] + got / dt;
+  if (q != q) q = __builtin_nan("");
+  qin[c] = q;
+  route_st(qsub + c, q - qsur[c]);
+}
+
 namespace {
 DamRows<true> dam_rows(const DamArgs& Dm, double dt)
 {
@@ -673,7 +814,7 @@ HeatRows<true> heat_rows(const HeatArgs& H, const double* hr_old, double* hr_new
 
 void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const FloodArgs& F, const DamArgs& Dm, const HeatArgs& H,
                               const OGridMap& M, const double* qrunoff, const double* qirr, const double* qsurf, const double* qh2osfc,
-                              double dt, hipStream_t st, const LandArgs& Ln)
+                              double dt, hipStream_t st, const LandArgs& Ln, const CmdArgs& Cm)
 {
   if (A.ncells <= 0) return;
   const double dts = dt / (double)A.nsub;  // K0
@@ -688,23 +829,46 @@ void launch_routing_kinematic(const RouteArgs& A, const KinematicArgs& K, const 
       with_bool(H.rows != nullptr, [&](auto heat) {
         // (the LAND form exactly while the infiltration's rows and the floodplain's are there; the entry points keep it apart from the heat)
         with_bool(Ln.qland != nullptr && F.rows != nullptr, [&](auto land) {
-          constexpr bool DAM = decltype(dam)::value, HEAT = decltype(heat)::value && !DAM, LAND = decltype(land)::value && !HEAT;
-          DamRows<DAM> dm;
-          if constexpr (DAM) dm = dam_rows(Dm, dt);
-          HeatRows<HEAT> ht;
-          if constexpr (HEAT) ht = heat_rows(H, nullptr, hsrc);
-          LandRows<LAND> ln;
-          if constexpr (LAND) ln = LandRows<true>{(gptr<const double>)Ln.qdrain, (gptr<double>)(F.rows + FP_WF * A.cld), (gptr<double>)Ln.qland, dt};
-          hipLaunchKernelGGL((k_kinematic_prep<decltype(withdraw)::value, DAM, HEAT, LAND>), grid, block, 0, st, (gptr<const int64_t>)M.ptr,
-                             (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff, (gptr<const double>)qirr,
-                             (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
-                             (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par,
-                             (gptr<double>)(A.rows + ROUTE_QIN * A.cld), (gptr<double>)(K.rows + KW_QSUR * A.cld),
-                             (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts, dm, ht, ln);
+          // (the CMD form exactly while the command areas' rows are there; the entry points keep them to the withdrawal and the reservoirs)
+          with_bool(Cm.rows != nullptr, [&](auto cmd) {
+            constexpr bool WITHDRAW = decltype(withdraw)::value;
+            constexpr bool DAM = decltype(dam)::value, HEAT = decltype(heat)::value && !DAM, LAND = decltype(land)::value && !HEAT;
+            constexpr bool CMD = decltype(cmd)::value && WITHDRAW && DAM;
+            DamRows<DAM> dm;
+            if constexpr (DAM) dm = dam_rows(Dm, dt);
+            HeatRows<HEAT> ht;
+            if constexpr (HEAT) ht = heat_rows(H, nullptr, hsrc);
+            LandRows<LAND> ln;
+            if constexpr (LAND) ln = LandRows<true>{(gptr<const double>)Ln.qdrain, (gptr<double>)(F.rows + FP_WF * A.cld), (gptr<double>)Ln.qland, dt};
+            const auto args = [&](auto&& launch) {
+              launch((gptr<const int64_t>)M.ptr, (gptr<const int32_t>)M.col, (gptr<const double>)M.w, (gptr<const double>)qrunoff,
+                     (gptr<const double>)qirr, (gptr<const double>)qsurf, (gptr<const double>)qh2osfc, (gptr<const double>)A.area,
+                     (gptr<const double>)(A.rows + ROUTE_VOLR * A.cld), (gptr<const double>)K.par, (gptr<double>)(A.rows + ROUTE_QIN * A.cld),
+                     (gptr<double>)(K.rows + KW_QSUR * A.cld), (gptr<double>)(K.rows + KW_QSUB * A.cld), (gptr<double>)src, A.ncells, A.cld, dts);
+            };
+            if constexpr (CMD) {
+              const CmdRows<true> cm{(gptr<const int32_t>)Cm.dam, (gptr<double>)(Cm.rows + CMD_WANT * A.cld)};
+              args([&](auto... a) { hipLaunchKernelGGL((k_kinematic_prep_cmd<LAND>), grid, block, 0, st, a..., dm, ln, cm); });
+            } else {
+              args([&](auto... a) { hipLaunchKernelGGL((k_kinematic_prep<WITHDRAW, DAM, HEAT, LAND>), grid, block, 0, st, a..., dm, ht, ln); });
+            }
+          });
         });
       });
     });
   });
+  if (Cm.rows && Dm.rows && qirr) {  // C2, C3: between the K1 launch and the first sub-step
+    if (Cm.ndams > 0)
+      hipLaunchKernelGGL(k_command_allot, dim3((unsigned)((Cm.ndams + CMD_DAMS - 1) / CMD_DAMS)), dim3(CMD_THREADS), 0, st,
+                         (gptr<const int32_t>)Cm.dams, (gptr<const int64_t>)Cm.ptr, (gptr<const int32_t>)Cm.tcell, (gptr<const double>)Cm.tshare,
+                         (gptr<const double>)(Cm.rows + CMD_WANT * A.cld), (gptr<double>)(Dm.rows + DAM_RES * A.cld),
+                         (gptr<const double>)(Dm.tab + DAM_SMIN * A.cld), (gptr<double>)(Cm.rows + CMD_GIVE * A.cld),
+                         (gptr<double>)(Cm.rows + CMD_RATIO * A.cld), Cm.ndams);
+    hipLaunchKernelGGL(k_command_take, grid, block, 0, st, (gptr<const int32_t>)Cm.dam, (gptr<const double>)Cm.share,
+                       (gptr<const double>)(Cm.rows + CMD_WANT * A.cld), (gptr<const double>)(Cm.rows + CMD_RATIO * A.cld),
+                       (gptr<double>)(Cm.rows + CMD_TAKE * A.cld), (gptr<double>)(A.rows + ROUTE_QIN * A.cld),
+                       (gptr<const double>)(K.rows + KW_QSUR * A.cld), (gptr<double>)(K.rows + KW_QSUB * A.cld), A.ncells, A.cld, dt);
+  }
   for (int s = 0; s < A.nsub; s++) {
     const auto args = [&](auto&& launch) {
       launch((gptr<double>)(K.rows + KW_WH * A.cld), (gptr<double>)(K.rows + KW_WT * A.cld), (gptr<double>)(A.rows + ROUTE_VOLR * A.cld),

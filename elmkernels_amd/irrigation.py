@@ -181,7 +181,7 @@ def _canon(v):
     return np.where(v != v, _NAN, v)
 
 
-def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx_irrig=None, dam=None):
+def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx_irrig=None, dam=None, command=None):
     """S0 - S6 on the host: the launch that follows elmk_irrigation while the limit is on.
 
     ptr, col, w: the output grid's CSR map (every column in at most one cell); area, volr: the routing's [ncells]; rate, nleft: the
@@ -189,7 +189,8 @@ def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx
     [ncells], the prognostic row; qflx_irrig: the irrigation's QFLX_IRRIG row of this step ([ncols]; None: zeros) - the water applied
     in this step, which the routing has not yet taken out of volr (S2's y).  dam = (tab, res): the reservoirs are on (include/elmk.h
     "reservoirs", D7; tab: routing.reservoir_tables, res: the RES row [ncells]) - a dam cell's storage above SMIN counts as available
-    beside the channel's; None: S3 as it is.  Returns (rate_out, rows): rate_out float64 [ncols], rows float64 [SUPPLY_NROWS, ncells] in the order
+    beside the channel's; None: S3 as it is.  command: routing.command_tables' dict, the command areas are on too ("command areas", C6;
+    needs dam) - per filled slot in order, the cell's claim times the named dam's storage above SMIN counts as well.  Returns (rate_out, rows): rate_out float64 [ncols], rows float64 [SUPPLY_NROWS, ncells] in the order
     DEMAND, COMMITTED, RATIO, UNMET_SUM.  Nothing is changed in place."""
     from . import regrid
 
@@ -204,6 +205,8 @@ def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx
     unmet_sum = np.asarray(unmet_sum, dtype=np.float64).reshape(-1)
     thr = float(thr)
     ncells = ptr.size - 1
+    if command is not None and dam is None:
+        raise ValueError("supply_limit: command without dam")
     assert area.shape == volr.shape == unmet_sum.shape == (ncells,) and rate.shape == nleft.shape
     with np.errstate(all="ignore"):
         checks = nleft == float(nspd)                                # S0
@@ -217,6 +220,11 @@ def supply_limit(ptr, col, w, area, volr, rate, nleft, idt, thr, unmet_sum, qflx
         if dam is not None:  # D7
             r = np.asarray(dam[1], dtype=np.float64).reshape(-1) - dam[0]["SMIN"]
             a = np.where(dam[0]["DAM"], a + np.where(r > 0.0, r, 0.0), a)
+            if command is not None:  # C6
+                for k in range(command["DAM"].shape[0]):
+                    on = command["DAM"][k] >= 0
+                    rk = r[np.where(on, command["DAM"][k], 0)]
+                    a = np.where(on, a + command["CLAIM"][k] * np.where(rk > 0.0, rk, 0.0), a)
         a = a - Vc
         avail = np.where(a > 0.0, a, 0.0)
         ratio = np.where(Vd > avail, avail / np.where(Vd > avail, Vd, 1.0), 1.0)  # S4 (the division only where it is taken)

@@ -44,6 +44,16 @@ Its reservoirs (include/elmk.h "reservoirs"; the DAM form of both kernels), afte
     dam = {"tab": reservoir_tables(cap, target, beta, mstart), "res": res, "krls": krls, "month": m, "begins": b}
     wh, wt, volr, qout, res, krls, take, qin = kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, dam=dam)
 
+Its command areas (include/elmk.h "command areas"; k_kinematic_prep_cmd, k_command_allot, k_command_take), after
+S.routing_reservoir_enable and S.routing_set_withdrawal(True):
+
+    S.routing_command_enable(dam, share, claim)                         # [4, ncells] each: check_command says what they must hold
+    ... S.routing(dt) and S.run(..., RUN_ROUTING) now let the dams supply the cells that hang on them ...
+    take, give = S.routing_read(CMD_TAKE), S.routing_read(CMD_GIVE)
+
+    dam["command"] = command_tables(cap, dam_rows, share, claim)
+    ..., res, krls, take, qin, cmd_want, cmd_take, cmd_give, cmd_ratio = kinematic_call(..., dam=dam)
+
 Its stream temperature (include/elmk.h "stream temperature"; the HEAT form of both kernels), after S.routing_kinematic_enable and
 without the two extensions above:
 
@@ -305,7 +315,11 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
     dam: the DAM form ("reservoirs", D0 - D5), a dict with "tab" (reservoir_tables), "res" and "krls" [ncells], "month" (0 .. 11) and
     "begins"; optional "withdrawal" = (rn, i), R1's aggregates of QRUNOFF and QFLX_IRRIG [ncells] (the routing's withdrawal is on: D2;
     qin is then K1's QIN with the withdrawal), and "variant", one of the wrong variants of DAM_VARIANTS.  The result grows by
-    (res_new, krls_new, res_take, qin_new) behind the flood rows, if any.
+    (res_new, krls_new, res_take, qin_new) behind the flood rows, if any.  "command": the command areas ("command areas", C1 - C3;
+    needs "withdrawal"), a dict of command_tables' entries plus optionally "take", "give" and "ratio" [ncells], the rows as the device
+    holds them (the cells C0 leaves alone keep them; None: 0.0, 0.0 and 1.0), "variant", one of CMD_VARIANTS, and "census" (command_allot);
+    C1 - C3 run after the first regulation and before the first sub-step's use of QSUB, qin_new is the credited QIN, and the result
+    grows by (want, take, give, ratio) behind it.
     heat: the HEAT form ("stream temperature", H1 - H6), a dict with "tab" (heat_tables), "prep" (heat_prep), "tt" and "tr" [ncells] and
     optionally "census", a dict that takes a bool row per branch of HEAT_BRANCHES; not together with flood or dam.  The result grows by
     (tt_new, tr_new, heat, hin, hsrf, hadj, hout); the water rows keep their bits (H8).
@@ -327,6 +341,20 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
                                               dam.get("withdrawal"), d1_last=dvar == "d1_after_d2")
         dmonth = int(dam["month"])
         dkw = {"spill": dvar != "no_spill", "smin": dvar != "no_smin"}
+        cmd = dam.get("command")
+        if cmd is not None:
+            if dam.get("withdrawal") is None:
+                raise ValueError("kinematic_call: command areas without the withdrawal")
+            cvar = cmd.get("variant")
+            if cvar is not None and cvar not in CMD_VARIANTS:
+                raise ValueError(f"kinematic_call: unknown variant {cvar!r}")
+            with np.errstate(all="ignore"):  # C1: what R1 and D2 left of the withdrawal
+                iv = (np.asarray(dam["withdrawal"][1], dtype=np.float64).reshape(-1) * 0.001) * np.asarray(area, dtype=np.float64).reshape(-1)
+                cwant = command_want(np.where(dtab["DAM"], iv - take / float(dt), iv), dt, cmd)
+            cres0 = np.asarray(dam["res"], dtype=np.float64).reshape(-1)
+            ctake, cgive, cratio = (np.array(cmd[k], dtype=np.float64).reshape(-1) if cmd.get(k) is not None else None for k in ("take", "give", "ratio"))
+    else:
+        cmd = None
     if flood is not None:
         tab, wf = flood
         wf = np.array(wf, dtype=np.float64).reshape(-1)
@@ -346,7 +374,7 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
             qland = _canon((np.asarray(land, dtype=np.float64).reshape(-1) * 0.001) * area)
             wf = _canon(wf - qland * float(dt))
         qsub = qin - qsur
-        for _ in range(nsub):
+        for sub in range(nsub):
             eh = hillslope_flow(wh, area, ch, dts, cap)
             et = channel_flow(wt, p[TLEN], p[TWIDTH], ct, dts, cap)
             er = channel_flow(v, p[RLEN], p[RWIDTH], cr, dts, cap)
@@ -355,6 +383,10 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
                 er, res = reservoir_regulate(en, res, krls, dtab, dmonth, dts, **dkw)
                 if dvar == "own_eo":
                     en = er
+                if cmd is not None and sub == 0:  # C2, C3: after the K1 launch's regulation, before the first sub-step's QSUB
+                    res, cgive, cratio = command_allot(cwant, res, dtab, cmd, cgive, cratio, variant=cvar, res_avail=cres0,
+                                                       census=cmd.get("census"))
+                    ctake, qin, qsub = command_take(cwant, cratio, qin, qsur, dt, cmd, ctake, variant=cvar)
             if ht is not None:
                 ht.before(wt, v, qsub, eh, et, er, up, safe, dts)
             if in_place:
@@ -385,6 +417,8 @@ def kinematic_call(wh, wt, volr, qin, qsur, area, params, up, dt, nsub, in_place
         out += (wf, depth, frac)
     if dam is not None:
         out += (res, krls, take, qin)
+        if cmd is not None:
+            out += (cwant, ctake, cgive, cratio)
     if ht is not None:
         out += ht.rows()
     if land is not None:
@@ -636,7 +670,9 @@ def reservoir_targets(mean_inflow, mean_demand, cap):
       c = cap / (im * 365 * 86400), the storage as a share of the annual inflow volume;  BETA = min(1, (c / 0.5) ** 2);
       MSTART = the first month with inflow < im that follows a month with inflow >= im (the operational year begins when the inflow
                falls below its mean; 0 where no month does).
-    Returns (target float64 [12, ncells], beta float64 [ncells], mstart int32 [ncells])."""
+    Returns (target float64 [12, ncells], beta float64 [ncells], mstart int32 [ncells]).
+    With the command areas on (check_command) a dam also supplies the cells that depend on it: mean_demand should then include the
+    command area's demand - the dependents' mean withdrawal times their share - beside the own cell's."""
     cap = np.atleast_1d(np.asarray(cap, dtype=np.float64)).reshape(-1)
     fi = np.asarray(mean_inflow, dtype=np.float64)
     fd = np.asarray(mean_demand, dtype=np.float64)
@@ -655,6 +691,177 @@ def reservoir_targets(mean_inflow, mean_demand, cap):
     falls = below & ~np.roll(below, 1, axis=0)
     mstart = np.where(falls.any(axis=0), falls.argmax(axis=0), 0).astype(np.int32)
     return target, beta, mstart
+
+
+# ---- command areas (include/elmk.h "command areas", C0 - C8) ------------------------------------------------------------------------------
+CMD_WANT, CMD_TAKE, CMD_GIVE, CMD_RATIO = 21, 22, 23, 24  # ELMK_ROUTE_CMD_*, readable while the part is on
+NDEP = 4  # ELMK_CMD_NDEP: the slots of a cell's dependency rows
+CMD_VARIANTS = ("reverse", "ratio_on_want", "no_smin", "before_d2", "no_credit")  # the wrong variants the host tests hold the statement against
+
+# the refusals of elmk_routing_command_enable's check (elmk_maps.h: command_check), in its order; each is followed by the cell
+E_CMD_RANGE = "DAM outside [-1, ncells)"
+E_CMD_GAP = "DAM filled behind an empty slot"
+E_CMD_NODAM = "DAM names a cell without a reservoir"
+E_CMD_SELF = "DAM names the cell itself"
+E_CMD_TWICE = "DAM names one reservoir twice"
+E_CMD_SHARE = "SHARE outside (0, 1]"
+E_CMD_CLAIM = "CLAIM outside [0, 1]"
+E_CMD_SHARE_SUM = "SHARE sums to more than 1"
+E_CMD_CLAIM_SUM = "CLAIM sums to more than 1"  # followed by the dam's cell
+
+
+def _command_terms(cap, dam):
+    """The inverse map of checked rows: (dams, ptr, cell, slot) - the dam list (every cell with cap > 0, ascending), the CSR over it, and
+    the terms (cell, slot) sorted by cell and then slot.  A counting sort: linear time."""
+    n = cap.size
+    dams = np.nonzero(cap > 0.0)[0]
+    place = np.full(n, -1, np.int64)
+    place[dams] = np.arange(dams.size)
+    cell = np.repeat(np.arange(n)[:, None], NDEP, axis=1).reshape(-1)  # cell-major, slot-minor: sorted by cell and then slot
+    slot = np.tile(np.arange(NDEP), n)
+    d = dam.T.reshape(-1)
+    filled = d >= 0
+    cell, slot, d = cell[filled], slot[filled], d[filled]
+    order = np.argsort(place[d], kind="stable")
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(place[d], minlength=dams.size))]).astype(np.int64)
+    return dams.astype(np.int32), ptr, cell[order].astype(np.int32), slot[order].astype(np.int32)
+
+
+def check_command(cap, dam, share, claim):
+    """The checks of elmk_routing_command_enable on cap [ncells] (the reservoirs' CAP) and the rows dam (int), share and claim
+    [4, ncells], in its order: per cell in index order and per slot in slot order the index, the gap, the reservoir, the cell itself,
+    the repeat, share, claim; behind a cell's slots its shares added in slot order; then per dam in ascending order its claims added
+    in term order.  Raises ValueError with the entry point's text."""
+    cap = np.asarray(cap, dtype=np.float64).reshape(-1)
+    dam, share, claim = np.asarray(dam), np.asarray(share, dtype=np.float64), np.asarray(claim, dtype=np.float64)
+    n = cap.size
+    if dam.shape != (NDEP, n) or share.shape != dam.shape or claim.shape != dam.shape:
+        raise ValueError("dam, share and claim must be [4, ncells]")
+    dam = dam.astype(np.int64)
+    code = np.zeros((NDEP, n), np.int64)  # per slot the first failing check, 0: none
+    filled = dam >= 0
+    safe = np.where(filled & (dam < n), dam, 0)
+    gap = np.zeros(n, bool)
+    with np.errstate(all="ignore"):
+        for k in range(NDEP):
+            twice = np.zeros(n, bool)
+            for j in range(k):
+                twice |= dam[j] == dam[k]
+            c = np.where((dam[k] < -1) | (dam[k] >= n), 1,
+                np.where(~filled[k], 0,
+                np.where(gap, 2,
+                np.where(~(cap[safe[k]] > 0.0), 3,
+                np.where(dam[k] == np.arange(n), 4,
+                np.where(twice, 5,
+                np.where(~(np.isfinite(share[k]) & (share[k] > 0.0) & (share[k] <= 1.0)), 6,
+                np.where(~((claim[k] >= 0.0) & (claim[k] <= 1.0)), 7, 0))))))))
+            code[k] = c
+            gap |= ~filled[k]
+        first = np.where(code.any(axis=0), np.take_along_axis(code, (code != 0).argmax(axis=0)[None], axis=0)[0], 0)
+        # the shares' sum is checked behind a cell's slots: only in a cell whose slots all pass
+        ok = filled & (code == 0)
+        total = np.zeros(n)
+        for k in range(NDEP):
+            total = np.where(ok[k], share[k] if k == 0 else total + share[k], total)
+        first = np.where((first == 0) & ~(total <= 1.0), 8, first)
+    if first.any():
+        c = int(np.nonzero(first)[0][0])
+        raise ValueError(e_cell((E_CMD_RANGE, E_CMD_GAP, E_CMD_NODAM, E_CMD_SELF, E_CMD_TWICE, E_CMD_SHARE, E_CMD_CLAIM, E_CMD_SHARE_SUM)[int(first[c]) - 1], c))
+    dams, ptr, cell, slot = _command_terms(cap, dam)
+    q = claim[slot, cell]
+    for j in range(dams.size):
+        total = 0.0
+        for p in range(int(ptr[j]), int(ptr[j + 1])):
+            total = float(q[p]) if p == ptr[j] else total + float(q[p])
+        if not total <= 1.0:
+            raise ValueError(e_cell(E_CMD_CLAIM_SUM, int(dams[j])))
+
+
+def command_tables(cap, dam, share, claim):
+    """The checked rows' tables as the host derives them, a dict: DAM int32 [4, ncells] (-1 in every empty slot), SHARE and CLAIM
+    float64 [4, ncells] (0.0 there), HAS bool [ncells] (a filled slot 0), and the inverse map "dams" [ndams], "ptr" [ndams + 1], "cell",
+    "slot" and "share" [nterms] in CSR order."""
+    check_command(cap, dam, share, claim)
+    cap = np.asarray(cap, dtype=np.float64).reshape(-1)
+    d = np.asarray(dam).astype(np.int32)
+    filled = d >= 0
+    dams, ptr, cell, slot = _command_terms(cap, d)
+    s = np.where(filled, np.asarray(share, dtype=np.float64), 0.0)
+    return {"DAM": np.where(filled, d, -1).astype(np.int32), "SHARE": s, "CLAIM": np.where(filled, np.asarray(claim, dtype=np.float64), 0.0),
+            "HAS": filled[0], "dams": dams, "ptr": ptr, "cell": cell, "slot": slot, "share": s[slot, cell]}
+
+
+def command_want(rest, dt, cmd):
+    """C1: WANT [ncells] from rest, what R1 and D2 left of the cells' withdrawal in m3/s; 0.0 in a cell without a filled slot."""
+    rest = np.asarray(rest, dtype=np.float64).reshape(-1)
+    with np.errstate(all="ignore"):
+        return np.where(cmd["HAS"] & (rest > 0.0), rest * float(dt), 0.0)
+
+
+def command_allot(want, res, tab, cmd, give=None, ratio=None, variant=None, res_avail=None, census=None):
+    """C2 for every dam with terms: want [ncells] (C1), res [ncells] as the K1 launch left it, tab: reservoir_tables, cmd:
+    command_tables.  Returns (res_new, give, ratio); a dam without terms keeps its res and the give and ratio handed in (None: 0.0 and
+    1.0).  variant: "reverse" adds a dam's terms last to first, "no_smin" forms avail without SMIN, "before_d2" forms avail from
+    res_avail, the RES before D2's take (wrong variants).  census: a dict that takes bool rows over the cells, "limited", "unlimited"
+    (W > 0), "W = 0", "no terms" and "at or below SMIN"."""
+    want, res = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (want, res))
+    n = res.size
+    give = np.zeros(n) if give is None else np.array(give, dtype=np.float64).reshape(-1)
+    ratio = np.ones(n) if ratio is None else np.array(ratio, dtype=np.float64).reshape(-1)
+    dams, ptr = cmd["dams"].astype(np.int64), cmd["ptr"]
+    nd = dams.size
+    cnt = np.diff(ptr)
+    with np.errstate(all="ignore"):
+        x = cmd["share"] * want[cmd["cell"]]
+        W = np.zeros(nd)
+        for k in range(int(cnt.max(initial=0))):  # the k-th term of every dam that has one, in CSR order (reverse: from the last)
+            on = cnt > k
+            p = np.where(on, (ptr[1:] - 1 - k) if variant == "reverse" else (ptr[:-1] + k), 0)
+            xk = x[p] if x.size else np.zeros(nd)
+            W = np.where(on, xk if k == 0 else W + xk, W)
+        base = np.asarray(res_avail, dtype=np.float64).reshape(-1) if variant == "before_d2" else res
+        a = base[dams] - (0.0 if variant == "no_smin" else tab["SMIN"][dams])
+        avail = np.where(a > 0.0, a, 0.0)
+        limited = W > avail
+        r = np.where(limited, avail / np.where(limited, W, 1.0), 1.0)
+        G = W * r
+        has = cnt > 0
+        res_new, give, ratio = res.copy(), give, ratio
+        res_new[dams[has]] = _canon(res[dams] - G)[has]
+        give[dams[has]] = _canon(G)[has]
+        ratio[dams[has]] = _canon(r)[has]
+    if census is not None:
+        def row(mask):
+            out = np.zeros(n, bool)
+            out[dams[mask]] = True
+            return out
+        census.update({"limited": row(has & limited), "unlimited": row(has & ~limited & (W > 0.0)), "W = 0": row(has & (W == 0.0)),
+                       "no terms": row(~has), "at or below SMIN": row(has & ~(a > 0.0))})
+    return res_new, give, ratio
+
+
+def command_take(want, ratio, qin, qsur, dt, cmd, take=None, variant=None):
+    """C3 for every cell with a filled slot: want (C1), ratio (C2's row), qin and qsur [ncells].  Returns (take, qin_new, qsub_new); a
+    cell without a filled slot keeps the take handed in (None: 0.0) and its qin.  variant: "ratio_on_want" forms share * (WANT * RATIO),
+    "no_credit" leaves QIN as it is (wrong variants)."""
+    want, ratio, qin, qsur = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (want, ratio, qin, qsur))
+    take = np.zeros(want.size) if take is None else np.asarray(take, dtype=np.float64).reshape(-1)
+    dam, has = cmd["DAM"], cmd["HAS"]
+    with np.errstate(all="ignore"):
+        got = np.zeros(want.size)
+        for k in range(NDEP):
+            on = dam[k] >= 0
+            rk = ratio[np.where(on, dam[k], 0)]
+            x = cmd["SHARE"][k] * (want * rk) if variant == "ratio_on_want" else (cmd["SHARE"][k] * want) * rk
+            got = np.where(on, x if k == 0 else got + x, got)
+        q = qin if variant == "no_credit" else _canon(qin + got / float(dt))
+        qin_new = np.where(has, q, qin)
+        return np.where(has, _canon(got), take), qin_new, qin_new - qsur
+
+
+def command_budget(give, take):
+    """C5: the sums of CMD_GIVE and CMD_TAKE in the device reduction's order."""
+    return np.array([diagnostics.reduce_min_max_sum(x)[2] for x in (give, take)])
 
 
 # ---- stream temperature (include/elmk.h "stream temperature", H0 - H9) -------------------------------------------------------------------

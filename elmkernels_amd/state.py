@@ -47,6 +47,8 @@ ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = rang
 ROWS_FLOODPLAIN = 7  # ... and the floodplain infiltration's (ELMK_ROWS_FLOODPLAIN; which = FPI_*), past the cell-row families' numbers
 FPI_H2OROF, FPI_FRAC, FPI_QFLX_DRAIN = range(3)  # floodplain_infiltration_read (hydrology.FPI_*)
 ROUTE_QLAND = 20  # routing_read while the floodplain infiltration is on (routing.QLAND)
+ROUTE_CMD_WANT, ROUTE_CMD_TAKE, ROUTE_CMD_GIVE, ROUTE_CMD_RATIO = 21, 22, 23, 24  # ... while the command areas are on (routing.CMD_WANT ..)
+ROUTE_CMD_NDEP = 4  # ELMK_CMD_NDEP: the slots of a cell's dependency rows
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
                 "irrigation": ROWS_IRRIGATION, "floodplain": ROWS_FLOODPLAIN}
 CELL_ROWS_ROUTING, CELL_ROWS_SUPPLY = range(2)  # cell_history_add_row: the cell-row families (ELMK_CELL_ROWS_*)
@@ -605,7 +607,8 @@ class ELMState:
     def routing_read(self, which, cell0=0, n=None):
         """Row ROUTE_VOLR, ROUTE_QIN, ROUTE_QOUT or ROUTE_QOUT_SUM (with the kinematic-wave scheme on also ROUTE_WH, ROUTE_WT, ROUTE_QSUR,
         with its floodplain inundation on also ROUTE_WF, ROUTE_FLOOD_DEPTH, ROUTE_FLOOD_FRAC, with its reservoirs on also ROUTE_RES,
-        ROUTE_KRLS, ROUTE_RES_TAKE, with its stream temperature on also ROUTE_TT .. ROUTE_HOUT)
+        ROUTE_KRLS, ROUTE_RES_TAKE, with its stream temperature on also ROUTE_TT .. ROUTE_HOUT, with the command areas on also
+        ROUTE_CMD_WANT .. ROUTE_CMD_RATIO)
         of cells [cell0, cell0 + n): float64 [n].  Synchronises."""
         return self._read_row("routing_read", which, cell0, n, getattr(self, "routing_ncells", 0), clamp=True)
 
@@ -708,6 +711,30 @@ class ELMState:
     def routing_reservoir_clear(self):
         """Back to the free-flowing channel; RES is dropped, VOLR stays."""
         self._chk(self.lib.elmk_routing_reservoir_clear(self.ctx), "routing_reservoir_clear")
+
+    # -- command areas (include/elmk.h: elmk_routing_command_enable ...; routing.kinematic_call(dam={..., "command": cmd}) restates them) ---
+    def routing_command_enable(self, dam, share, claim):
+        """Let the dams supply the cells that depend on them: dam int32 [ROUTE_CMD_NDEP, ncells], the cell of a supplying dam or -1 for an
+        empty slot (filled from slot 0 without gaps), share float64 [ROUTE_CMD_NDEP, ncells] in (0, 1], the fraction of the cell's remaining
+        withdrawal asked of that dam, claim float64 [ROUTE_CMD_NDEP, ncells] in [0, 1], the cell's right to the dam's usable storage at
+        the supply limit's daily check (routing.check_command says the rest).  Allocates the rows ROUTE_CMD_WANT, _TAKE, _GIVE
+        (zero-filled) and _RATIO (1.0); routing_read takes them from here on.  Needs routing_reservoir_enable and
+        routing_set_withdrawal(True)."""
+        d = np.ascontiguousarray(dam, dtype=np.int32)
+        s = np.ascontiguousarray(share, dtype=np.float64)
+        c = np.ascontiguousarray(claim, dtype=np.float64)
+        n = getattr(self, "routing_ncells", d.shape[-1] if d.ndim == 2 else 0)
+        if d.shape != (ROUTE_CMD_NDEP, n) or s.shape != d.shape or c.shape != d.shape:
+            raise ValueError(f"routing_command_enable: dam, share and claim must be [{ROUTE_CMD_NDEP}, {n}]")
+        self._chk(self.lib.elmk_routing_command_enable(self.ctx, _p(d), _p(s), _p(c)), "routing_command_enable")
+
+    def routing_command_budget(self):
+        """float64 [2]: the sums of CMD_GIVE and CMD_TAKE (routing.command_budget).  Synchronises."""
+        return self._routing_budget("routing_command_budget", 2)
+
+    def routing_command_clear(self):
+        """Back to dams that serve their own cell only; RES stays."""
+        self._chk(self.lib.elmk_routing_command_clear(self.ctx), "routing_command_clear")
 
     # -- stream temperature (include/elmk.h: elmk_routing_heat_enable ...; routing.kinematic_call(heat=) restates it) ------------------------
     def routing_heat_enable(self, sublev=0, shade=None):

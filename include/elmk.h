@@ -1494,6 +1494,88 @@ int elmk_floodplain_infiltration_read(elmk_ctx *ctx, int which /*ELMK_FPI_**/, d
 int elmk_floodplain_infiltration_budget(elmk_ctx *ctx, double *sums /*[1]: the sum of QLAND, through R6's reduction kernels*/);
 int elmk_floodplain_infiltration_clear(elmk_ctx *ctx);
 
+/* ---- command areas ----------------------------------------------------------------------------------
+ * An opt-in part of the river stage on top of "reservoirs", after MOSART-WM's dependency database (Voisin et al., Hydrol. Earth Syst.
+ * Sci. 17, 2013): a dam supplies the cells that depend on it, not only the cell it stands in.  What the own dam (D2) has not covered
+ * of a cell's withdrawal is asked of up to ELMK_CMD_NDEP dams, each dam allots what it can among its dependents in proportion, and
+ * the cells' QIN is credited with what they received.  It needs the kinematic scheme, the reservoirs and the routing's withdrawal.  No
+ * run flag and no new call in the step: while it is on, elmk_routing and the ELMK_RUN_ROUTING stage enqueue two more launches between
+ * the K1 launch and the first sub-step (k_routing.hip: k_command_allot, k_command_take), the K1 launch takes its CMD form, and with the
+ * river supply limit also on k_irrigation_supply takes its CMD form.  elmkernels_amd/routing.py: check_command(), command_tables(),
+ * command_allot(), command_take() and kinematic_call(..., dam={..., "command": cmd}) restate it on the host.
+ *
+ * Conventions of "reservoirs": no contraction, left-associated + - *, `/` correctly rounded, plain IEEE comparisons, every row fp64 in
+ * both builds, a NaN stored as the canonical quiet NaN.
+ *
+ * Inputs, given once: three ELL rows [ELMK_CMD_NDEP][ncells].  dam: int32, the cell index of a supplying dam, -1 for an empty slot; the
+ * slots are filled from slot 0 without gaps.  share: the fraction of the cell's remaining withdrawal that it asks of that dam.  claim:
+ * the cell's fixed right to that dam's usable storage at the daily check of the river supply limit (C6).  The host checks them, per
+ * cell in index order and per slot in slot order: the index inside [-1, ncells); no filled slot behind an empty one; the named cell has
+ * CAP > 0.0; it is not the cell itself (D2 serves the own cell); it is not named by an earlier slot; share finite and in (0, 1]; claim
+ * finite and in [0, 1]; then the cell's shares, added in slot order, <= 1.0.  Then the host builds the inverse map: the dam list is
+ * every cell with CAP > 0.0 in ascending order (a dam without dependents has an empty span), and a CSR over that list holds the terms
+ * (cell, slot) sorted by cell and then slot; every dam's claims, added in term order, must be <= 1.0.  Linear time, no recursion.  Dam
+ * indices are a context's own cells: with several ranks a context allots among the cells it holds.
+ *
+ * Rows, all fp64 diagnostics that every call overwrites, zero after the enable except RATIO, which is 1.0: ELMK_ROUTE_CMD_WANT (m3, what
+ * a dependent cell asks for in total), ELMK_ROUTE_CMD_TAKE (m3, what it received), and at a dam's cell ELMK_ROUTE_CMD_GIVE (m3, what
+ * the dam gave) and ELMK_ROUTE_CMD_RATIO (the dam's ratio).  elmk_routing_read accepts the four only while the part is on.  There is no
+ * prognostic row: no image version changes, and with ELMK_OPT_RESTART_CELLS a context with the part on saves the version-7 image byte
+ * for byte (a load leaves WANT, TAKE and GIVE zero and RATIO 1.0).
+ *
+ * C0. A cell with no filled slot, and a dam with no terms, keep every bit of the form without the part; such a cell's WANT and TAKE and
+ *     such a dam's GIVE and RATIO are not written.
+ * C1. (K1 launch, k_kinematic_prep_cmd, the CMD form of the K1 launch, which exists only with the withdrawal and the reservoirs) a cell with a filled
+ *     slot forms, after R1 and D2, with iv = (i * 0.001) * area: for a dam cell rest = iv - t / dt (D2's t), for any other cell
+ *     rest = iv;  WANT = rest > 0.0 ? rest * dt : 0.0.  QIN, QSUB, D1 - D3 and the first er are what they are without the part.
+ * C2. (k_command_allot, one sum per dam with terms) RES here is what the K1 launch left: after D1, D2 and the first D3.
+ *     W = the sum over the dam's terms in CSR order of x = share * WANT[cell], the first term assigned and the rest added;
+ *     a = RES - SMIN;  avail = a > 0.0 ? a : 0.0;  ratio = W > avail ? avail / W : 1.0;  G = W * ratio;  RES = RES - G;  GIVE = G;
+ *     RATIO = ratio.
+ * C3. (k_command_take, one thread per cell) a cell with a filled slot forms got = the sum in slot order of (share * WANT) * RATIO[dam] -
+ *     the product x of C2, one rounding, then the ratio; the first slot assigned and the rest added;  TAKE = got;
+ *     QIN = QIN + got / dt;  QSUB = QIN - QSUR.
+ * C4. The sub-steps run unchanged; D3 of the later sub-steps sees the reduced RES.
+ * C5. (elmk_routing_command_budget) sums[0] = the sum of CMD_GIVE, sums[1] = the sum of CMD_TAKE, through R6's reduction kernels.  The
+ *     change of sum WH + sum WT + sum VOLR (+ sum WF) + sum RES over a call = dt (sum QIN - sum outlet QOUT) - sum RES_TAKE - sum
+ *     CMD_GIVE, and sum CMD_GIVE and sum CMD_TAKE agree but for the roundings: every term x * ratio is rounded once where it is taken,
+ *     G once per dam, and each sum once per addition.
+ * C6. (river supply limit, k_irrigation_supply<DAM, CMD>; elmkernels_amd/irrigation.py: supply_limit(command=)) S3 for a cell with
+ *     filled slots: after D7's own-dam term and before `- Vc`, for each slot in order r = RES[dam] - SMIN[dam], taken as 0.0 unless
+ *     > 0.0, and a = a + claim * r.  Every other cell keeps D7 / S3, and so does every cell with the part off.
+ * C7. Guaranteed: the claims of a dam sum to at most 1, so one check never promises more than the dam's usable storage.  Not
+ *     guaranteed: storage that is drawn down between a grant and its withdrawal - by D3's releases, by D2, by other cells' takes.  C2's
+ *     ratio catches that: what the dam cannot give leaves the channel, as in R1.
+ * C8. Edge values do what C1 - C3 say literally.  A NaN RES gives a = NaN, avail = 0.0: ratio = 0.0 for W > 0 (G = 0.0, RES stays NaN),
+ *     1.0 for W = 0.  RES = +inf gives everything asked (ratio 1.0) and stays +inf; RES = -inf, a negative RES and any RES <= SMIN
+ *     have avail = 0.0 and give nothing (ratio 0.0 for W > 0: G = W * 0.0 = 0.0).  WANT = +inf in a term makes W = +inf: with a finite
+ *     avail ratio = 0.0 and G = inf * 0.0 = NaN, so RES, GIVE and every dependent's TAKE and QIN are NaN; with avail = +inf too, W > avail
+ *     fails, ratio = 1.0 and G = +inf, RES = NaN.  W = 0 with terms fails W > avail: ratio = 1.0, G = 0.0, and RES - 0.0 keeps RES
+ *     (but -0.0 stays -0.0).  A NaN i makes rest NaN, which fails rest > 0.0: WANT = 0.0, nothing is asked, while QIN is NaN as it
+ *     is without the part.
+ *
+ *   elmk_routing_command_enable  checks the rows, builds the inverse map, allocates and uploads everything (one owner, counted in
+ *                           elmk_device_bytes) and drops the captured run step.  ELMK_E_INVALID, nothing changed: the kinematic
+ *                           scheme, the reservoirs or the routing's withdrawal off; already on; a null argument; a bad value (the
+ *                           text names the row and the first offending cell - for a dam's claims the dam's cell - as in
+ *                           "elmk_routing_command_enable: SHARE outside (0, 1] at cell 17"); a stream being captured.
+ *   elmk_routing_command_budget  C5; synchronises.
+ *   elmk_routing_command_clear   back to dams that serve their own cell; frees what enable allocated and drops the captured run
+ *                           step.  From then on every row takes the bits of a context that never had the part, given the same RES.
+ * While the part is on elmk_routing_reservoir_clear and elmk_routing_set_withdrawal(ctx, 0) are refused with ELMK_E_INVALID
+ * ("elmk_routing_command_clear first"); elmk_routing_clear frees everything.  The river supply limit may be enabled and cleared in
+ * either order relative to the part.
+ * Tapes: elmk_cell_history_add_row(ELMK_CELL_ROWS_ROUTING, ELMK_ROUTE_CMD_*) works while the part is on, and while such an entry exists
+ * elmk_routing_command_clear is refused ("elmk_history_clear first").
+ * A context that never enables it runs the kernels, launch sequences and graphs it ran before, allocates nothing more and saves the image
+ * it saved before. */
+enum { ELMK_CMD_NDEP = 4 };
+enum { ELMK_ROUTE_CMD_WANT = 21, ELMK_ROUTE_CMD_TAKE = 22, ELMK_ROUTE_CMD_GIVE = 23, ELMK_ROUTE_CMD_RATIO = 24 };
+int elmk_routing_command_enable(elmk_ctx *ctx, const int32_t *dam /*[4][ncells]*/, const double *share /*[4][ncells]*/,
+                                const double *claim /*[4][ncells]*/);
+int elmk_routing_command_budget(elmk_ctx *ctx, double *sums /*[2]: the sums of CMD_GIVE and CMD_TAKE, through R6's reduction kernels*/);
+int elmk_routing_command_clear(elmk_ctx *ctx);
+
 /* ---- feature rows on history tapes --------------------------------------------------------------
  * elmk_history_add and elmk_gridded_history_add take state fields; what the features above produce lives in fp64 rows beside the state.
  * These two entries register one such row, over the columns (elmk_column_history_add_row; the six elmk_history_* entries of "history"
