@@ -183,6 +183,20 @@ SIGNATURES = {
     "elmk_column_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_gridded_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "elmk_cell_history_add_row": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "elmk_points_set": (C.c_int, [_P, C.c_int, C.c_int64, _P]),
+    "elmk_points_add_field": (C.c_int, [_P, C.c_int, C.c_int]),
+    "elmk_points_add_row": (C.c_int, [_P, C.c_int, C.c_int]),
+    "elmk_points_add_cell_row": (C.c_int, [_P, C.c_int, C.c_int]),
+    "elmk_points_add_gridded_field": (C.c_int, [_P, C.c_int, C.c_int]),
+    "elmk_points_add_gridded_row": (C.c_int, [_P, C.c_int, C.c_int]),
+    "elmk_points_reserve": (C.c_int, [_P, C.c_int]),
+    "elmk_points_record": (C.c_int, [_P, C.c_double]),
+    "elmk_points_set_run": (C.c_int, [_P, C.c_int]),
+    "elmk_points_count": (C.c_int, [_P, _P, _P]),
+    "elmk_points_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_points_stamps": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
+    "elmk_points_reset": (C.c_int, [_P]),
+    "elmk_points_clear": (C.c_int, [_P]),
 }
 
 # ELM::SnicarData member order as laid out in elmk_snicar_tables (include/elmk.h)

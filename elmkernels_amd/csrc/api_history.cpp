@@ -20,7 +20,10 @@ bool has_gridded_entries(const elmk_ctx* ctx) { return !ctx->hist_crows.empty();
 
 bool tape_ok(int tape) { return tape >= 0 && tape < ELMK_HIST_MAX_TAPES; }
 
-// the rows of a cell-row family (ELMK_CELL_ROWS_*) for a history entry: the device row `which` over the routing's cells, or null with
+}  // namespace
+
+namespace elmk {
+// the rows of a cell-row family (ELMK_CELL_ROWS_*) for a history or point-series entry: the device row `which` over the routing's cells, or null with
 // *why set - exactly the rows elmk_routing_read / elmk_irrigation_supply_read accept at this moment
 const double* cell_row(const elmk_ctx* ctx, int family, int which, const char** why)
 {
@@ -30,9 +33,7 @@ const double* cell_row(const elmk_ctx* ctx, int family, int which, const char** 
   if (which < ELMK_IRRSUP_DEMAND || which > ELMK_IRRSUP_UNMET_SUM) return *why = "row out of range", nullptr;
   return ctx->irrsup_rows + (size_t)which * (size_t)ctx->route.cld;
 }
-}  // namespace
 
-namespace elmk {
 unsigned long long* hist_counts(elmk_ctx* ctx) { return (unsigned long long*)((char*)(HistRow*)ctx->hist_table + HIST_COUNTS_OFF); }
 
 unsigned hist_tape_mask(const elmk_ctx* ctx)
@@ -58,7 +59,7 @@ int cellrows_hold(elmk_ctx* ctx, const char* who, int family, int which0, int wh
     if (family < 0 || (e.family == ELMK_ROWS_NFAMILY + family && which >= which0 && which <= which1))
       return invalid(ctx, (std::string(who) + ": cell-row history entries exist on its rows (elmk_history_clear first)").c_str());
   }
-  return ELMK_OK;
+  return points_hold_cellrows(ctx, who, family, which0, which1);
 }
 
 void mark_sampled(elmk_ctx* ctx, unsigned mask)
@@ -270,6 +271,7 @@ int elmk_set_output_grid(elmk_ctx* ctx, int64_t ncells, const int64_t* ptr, cons
   if (int rc = refuse_capture(ctx, "elmk_set_output_grid")) return rc;
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_set_output_grid: gridded history entries exist (elmk_history_clear first)");
   if (int rc = cellrows_hold(ctx, "elmk_set_output_grid")) return rc;  // (ncells is the grid's)
+  if (int rc = points_hold_grid(ctx, "elmk_set_output_grid")) return rc;
   if (int rc = irrsup_holds(ctx, "elmk_set_output_grid")) return rc;
   if (int rc = land_holds(ctx, "elmk_set_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_set_output_grid")) return rc;
@@ -290,6 +292,7 @@ int elmk_clear_output_grid(elmk_ctx* ctx)
   if (int rc = refuse_capture(ctx, "elmk_clear_output_grid")) return rc;
   if (has_gridded_entries(ctx)) return invalid(ctx, "elmk_clear_output_grid: gridded history entries exist (elmk_history_clear first)");
   if (int rc = cellrows_hold(ctx, "elmk_clear_output_grid")) return rc;
+  if (int rc = points_hold_grid(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = irrsup_holds(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = land_holds(ctx, "elmk_clear_output_grid")) return rc;
   if (int rc = route_holds(ctx, "elmk_clear_output_grid")) return rc;

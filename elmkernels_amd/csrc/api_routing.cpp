@@ -695,6 +695,8 @@ int elmk_floodplain_infiltration_clear(elmk_ctx* ctx)
   if (int rc = enter(ctx)) return rc;
   if (ctx->route.land.mem && hist_has_family(ctx, ELMK_ROWS_FLOODPLAIN))
     return invalid(ctx, "elmk_floodplain_infiltration_clear: history entries over the floodplain infiltration rows exist (elmk_history_clear first)");
+  if (ctx->route.land.mem)
+    if (int rc = points_hold_family(ctx, who, ELMK_ROWS_FLOODPLAIN)) return rc;
   return part_clear(ctx, LAND, who);
 }
 

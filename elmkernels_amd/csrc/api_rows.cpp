@@ -16,7 +16,7 @@ namespace elmk {
 // while a history entry reads the family's rows they stay: "<who>: history entries over the rows exist (elmk_history_clear first)"
 int rows_held(elmk_ctx* ctx, const Rows& R, const char* who)
 {
-  if (!hist_has_family(ctx, R.family)) return ELMK_OK;
+  if (!hist_has_family(ctx, R.family)) return points_hold_family(ctx, who, R.family);
   return invalid(ctx, (std::string(who) + ": history entries over the " + R.label + " rows exist (elmk_history_clear first)").c_str());
 }
 

@@ -94,6 +94,10 @@ void run_history(elmk_ctx* ctx, double)
 {
   if ((ctx->run.flags & ELMK_RUN_HISTORY) && !ctx->hist.empty()) hist_accumulate_launch(ctx);
 }
+void run_points(elmk_ctx* ctx, double)
+{
+  if (ctx->pts.run_on) points_run_launch(ctx);
+}
 void run_next(elmk_ctx* ctx, double) { launch_run_next(ctx->run.cursor, ctx->stream); }
 
 bool aerosol_field(int f) { return f >= ELMK_FIELD_aer_bcphi && f <= ELMK_FIELD_aer_dst4_2; }
@@ -119,11 +123,13 @@ bool all_finite(const double* a, int64_t n)
 // the water balance's begin (ELMK_RUN_WATER_BALANCE), advance_physics' stages (one stage here: launch_advance, with the irrigation stage
 // in front of soil_temperature under ELMK_RUN_IRRIGATION), soil hydrology
 // (ELMK_RUN_HYDROLOGY), conservation -> ring row, flag summary -> ring row, water balance -> its ring rows, runoff routing
-// (ELMK_RUN_ROUTING), active layer thickness (ELMK_RUN_ALT), accumulated fields, history, next row
+// (ELMK_RUN_ROUTING), active layer thickness (ELMK_RUN_ALT), accumulated fields, history, the point series' record (while
+// elmk_points_set_run is in force), next row
 constexpr Stage RUN_STEP[] = {{run_solar_geometry, nullptr}, {run_phenology, nullptr},     {run_forcing, nullptr},        {run_aerosol, nullptr},
                               {run_init_timestep, nullptr},  {run_wb_begin, nullptr},      {launch_advance, nullptr},     {run_soil_hydrology, nullptr},
                               {run_conservation, nullptr},   {run_flag_reduce, nullptr},   {run_water_balance, nullptr},  {run_routing, nullptr},
-                              {run_active_layer, nullptr},   {run_accum, nullptr},         {run_history, nullptr},        {run_next, nullptr}};
+                              {run_active_layer, nullptr},   {run_accum, nullptr},         {run_history, nullptr},        {run_points, nullptr},
+                              {run_next, nullptr}};
 }  // namespace
 
 namespace elmk {
@@ -284,6 +290,7 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
     hi = std::max(hi, (int)p.forc_slot + 1);
     months |= (1u << p.month1) | (1u << p.month2);
   }
+  if (int rc = points_run_check(ctx)) return rc;
   if (int rc = refuse_capture(ctx, "elmk_run")) return rc;
 
   if (int rc = set_col_dayl(ctx, true)) return rc;  // per-column mode, as the first elmk_solar_geometry enters it
@@ -324,6 +331,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
   const int row0 = buf * R.max_steps;
   HIPCHK(hipMemcpyAsync(R.table + row0, rows, (size_t)nsteps * sizeof(RunRow), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetD32Async((hipDeviceptr_t)R.cursor, row0, 1, ctx->stream));
+  if (ctx->pts.run_on)
+    if (int rc = points_run_begin(ctx, buf, steps, nsteps)) return rc;
   R.flags = flags;
   R.live[buf] = true;  // (from here on an upload of these records waits for the run's end event)
   R.slot_lo[buf] = lo;
@@ -343,7 +352,7 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
                     (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows, (flags & ELMK_RUN_ROUTING) && ctx->route.withdraw,
                     (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx) && (bool)ctx->irrsup_rows,
                     (flags & ELMK_RUN_ROUTING) && (bool)ctx->route.dam.mem, (flags & ELMK_RUN_ROUTING) && (bool)ctx->route.heat.mem,
-                    (bool)ctx->route.land.mem, (bool)ctx->route.cmd.mem};
+                    (bool)ctx->route.land.mem, (bool)ctx->route.cmd.mem, points_key(ctx)};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;

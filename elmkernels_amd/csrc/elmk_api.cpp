@@ -643,7 +643,8 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
              ctx->run.mem.bytes() + ctx->grid.mem.bytes() + ctx->ogrid.mem.bytes() + ctx->sw.czf.bytes() + ctx->run.rec.bytes() +
              ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes() + ctx->alt_rows.bytes() +
              ctx->hyd_rows.bytes() + ctx->hydf_rows.bytes() + ctx->wb_rows.bytes() + ctx->wb_red.bytes() + ctx->wb_ring.bytes() +
-             ctx->irr_rows.bytes() + route_bytes(ctx) + ctx->irrsup_rows.bytes();
+             ctx->irr_rows.bytes() + route_bytes(ctx) + ctx->irrsup_rows.bytes() + ctx->pts.mem.bytes() + ctx->pts.ring.bytes() +
+             ctx->pts.stamps.bytes();
   // the cell rows of gridded history entries (not the column rows) and the accumulators' values: whole rows of ld or cld doubles,
   // both multiples of 64, so every size is a multiple of 256 already
   for (const elmk_ctx::HistEntry& e : ctx->hist) n += e.cells || e.cellrow ? e.acc.bytes() : 0;  // (a cell-row entry's are cell rows too)

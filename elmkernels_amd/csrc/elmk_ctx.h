@@ -154,7 +154,7 @@ enum GraphId { GRAPH_TS7, GRAPH_FUSED, GRAPH_ADVANCE, GRAPH_RUN_STEP, GRAPH_N };
 // shortwave modes, whether the soil hydrology stage is in the step (its flag is set and the land unit is soil or crop), whether that
 // stage takes the frost-table form, the history and accumulator tables' versions, whether the irrigation stage is in the step (its flag
 // is set and the land unit is soil or crop), whether the water balance takes its term, whether the routing stage takes the withdrawal and
-// whether the irrigation stage has the river supply limit's launch behind it;
+// whether the irrigation stage has the river supply limit's launch behind it, and whether the point series' record follows the history;
 // the other sequences have none (StepKey{}).
 struct StepKey {
   int flags = 0;
@@ -167,10 +167,11 @@ struct StepKey {
   bool route_heat = false;                   // the routing stage is in the step and takes the stream temperature's form
   bool land = false;                         // the floodplain infiltration is on: the hydrology, water balance and routing stages take its forms
   bool route_cmd = false;                    // the command areas are on: the routing stage has their two launches, the supply limit their form
+  uint64_t points_version = 0;               // the point series is armed: its launch follows the history's (its version; 0: not armed)
   auto tie() const
   {
     return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw,
-                    irr_supply, route_dam, route_heat, land, route_cmd);
+                    irr_supply, route_dam, route_heat, land, route_cmd, points_version);
   }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
@@ -416,6 +417,35 @@ struct elmk_ctx {
     bool step_live = false;
   } aer;
   hipEvent_t aer_step_done = nullptr;  // the end of the last stepwise elmk_aerosol_deposition (created by the first reservation)
+  // point series (elmk_points_*; api_points.cpp): the entries and the two lists as the host holds them; `mem` holds the device table
+  // k_points_record reads, the run's base word and the two lists [ELMK_POINTS_MAX_POINTS] each; `ring` the records [max_records][stride],
+  // stride = POINTS_HEAD + the entries' points, each entry padded to 8 doubles; `stamps` the decday of every row of the run's two step
+  // tables (with its pinned host copy, allocated by the first armed elmk_run of a reservation).  total: the records since the last
+  // reset, known on the host when a record is enqueued.  version: counts every change of what a captured run step holds of the part;
+  // the step's key takes it while the part is armed (run_on) and 0 otherwise.
+  struct Points {
+    struct Entry {
+      int kind, a, b;  // POINTS_* of api_points.cpp and the source's two ids (field, level; family, which)
+      const void* src;
+      int dtype;
+    };
+    std::vector<Entry> entries;
+    std::vector<int64_t> list[ELMK_POINTS_NKIND];
+    DevBuf<char> mem;
+    PointsTable* table = nullptr;
+    int32_t* base = nullptr;
+    int64_t* dlist[ELMK_POINTS_NKIND] = {};
+    DevBuf<double> ring;
+    int max_records = 0;
+    int64_t stride = 0;
+    int nwaves = 0;
+    DevBuf<double> stamps;
+    DevBuf<double, true> stamps_host;
+    int stamps_steps = 0;
+    int64_t total = 0;
+    bool run_on = false;
+    uint64_t version = 0;
+  } pts;
   std::string err;
 };
 
@@ -543,6 +573,21 @@ int hist_has_family(const elmk_ctx* ctx, int family);  // a row entry of the fam
 // "<who>: cell-row history entries exist on its rows (elmk_history_clear first)" while an entry of elmk_cell_history_add_row samples row
 // which0 .. which1 of the cell-row family (family < 0: any family, any row)
 int cellrows_hold(elmk_ctx* ctx, const char* who, int family = -1, int which0 = 0, int which1 = 0);
+// the rows of a cell-row family (ELMK_CELL_ROWS_*) for a history or point-series entry: the device row `which` over the routing's cells, or
+// null with *why set - exactly the rows elmk_routing_read / elmk_irrigation_supply_read accept at this moment (api_history.cpp)
+const double* cell_row(const elmk_ctx* ctx, int family, int which, const char** why);
+// point series (api_points.cpp).  The interlocks of P7, each "<who>: point-series entries ... (elmk_points_clear first)": an entry over
+// the rows of a feature family; an entry over row which0 .. which1 of a cell-row family (family < 0: any cell-row entry); a gridded or
+// cell-row entry or a cells list, which hold the output grid's map and its ncells
+int points_hold_family(elmk_ctx* ctx, const char* who, int family);
+int points_hold_cellrows(elmk_ctx* ctx, const char* who, int family, int which0, int which1);
+int points_hold_grid(elmk_ctx* ctx, const char* who);
+// elmk_run with the part armed: the refusals (before anything is enqueued), then the stamps and the base word of the run on buffer buf,
+// enqueued; the run step's stage; the armed part's key
+int points_run_check(elmk_ctx* ctx);
+int points_run_begin(elmk_ctx* ctx, int buf, const elmk_run_step* steps, int nsteps);
+void points_run_launch(elmk_ctx* ctx);
+inline uint64_t points_key(const elmk_ctx* ctx) { return ctx->pts.run_on ? ctx->pts.version : 0; }
 // downscaling TOPO mode: the forcing kernels' parameters (ds_topo false: OFF, the kernels as they were); api_run.cpp
 inline bool ds_topo(const elmk_ctx* ctx) { return ctx->ds.mode == ELMK_DS_TOPO; }
 DsParams ds_params(const elmk_ctx* ctx);

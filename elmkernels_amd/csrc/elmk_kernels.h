@@ -420,4 +420,30 @@ struct RstPiece {
 void launch_restart_pieces(int mode, const RstPiece* pieces, int npieces, int nbx, char* chunk, uint64_t* part, uint64_t* sums,
                            hipStream_t st);
 
+// point series (k_points.hip, elmk_points_*; include/elmk.h "point series", P0 - P9): one entry = one source sampled at the points of its
+// list.  src: the source row (one level of a state field, stored element type `dtype` as HistRow::dtype; a feature row or a cell row, fp64);
+// list: the entry's points, columns or cells, every index checked by elmk_points_set; out: where its n doubles start inside a record's
+// values.  gridded != 0: the list holds cells and the sample is the aggregate of src over the cell's terms of the output grid's map.
+// wave0: the first wave of the entry in the launch - a gather entry takes ceil(n / 64) waves, a gridded entry n - so a wave serves one entry.
+struct PointsEntry {
+  const void* src;
+  const int64_t* list;
+  int64_t out;
+  int32_t n;
+  int32_t dtype;
+  int32_t gridded;
+  int32_t wave0;
+};
+struct PointsTable {
+  PointsEntry e[ELMK_POINTS_MAX_ENTRIES];
+  int32_t nentries;
+  int32_t nwaves;
+};
+constexpr int POINTS_HEAD = 8;  // doubles in front of a record's values: the stamp, then padding to 64 bytes
+// One record into slot `slot` of ring [max_records][stride] with stamp `stamp` (cursor null: the stepwise call), or, inside elmk_run's
+// step, into slot (*base + *cursor) % max_records with stamp stamps[*cursor]: the slot of a replayed graph comes from device words.
+// nwaves = T.nwaves as the host knows it (> 0).
+void launch_points_record(const PointsTable* T, int nwaves, const OGridMap& M, double* ring, int64_t stride, int max_records, int slot,
+                          double stamp, const int32_t* cursor, const int32_t* base, const double* stamps, hipStream_t st);
+
 }  // namespace elmk

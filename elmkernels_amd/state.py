@@ -139,6 +139,7 @@ class ELMState:
         self.land = dict(ltype=1, ctype=0, vtype=2, urbpoi=0, lakpoi=0)
         self._hist_nlev = {}  # history entry id -> levels of its field
         self._hist_cells = set()  # ids of gridded history entries (their results are cell-shaped)
+        self._points_n, self._points_kind = [0, 0], {}  # point series: the two lists' sizes, entry id -> the list it samples
         self.output_ncells = None  # cells of the output grid (set_output_grid)
         self._accum_nlev = {}  # accumulator entry id -> levels of its source field
 
@@ -1095,6 +1096,91 @@ class ELMState:
         self._hist_nlev[entry] = 1
         self._hist_cells.add(entry)  # (the routing's cells are the output grid's)
         return entry
+
+    # -- point series (include/elmk.h "point series"; elmkernels_amd/points.py restates a record and the ring's order) ---------
+    def points_set(self, kind, idx):
+        """The list of `kind` ("columns" / "cells" or ELMK_POINTS_*): int64 indices in any order, duplicates allowed, at most 4096;
+        copied.  Every index is checked against ncols, or the output grid's ncells.  Only before the first record or after
+        points_reset."""
+        k = {"columns": 0, "cells": 1}[kind] if isinstance(kind, str) else int(kind)
+        a = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        self._chk(self.lib.elmk_points_set(self.ctx, k, a.size, _p(a)), f"points_set({kind})")
+        self._points_n[k] = a.size
+
+    def _points_added(self, entry, k):
+        self._points_kind[entry] = k
+        return entry
+
+    def points_add_field(self, name, level=0):
+        """One level of a state field at the columns list; returns the entry id."""
+        fid = self.fields[name][0] if isinstance(name, str) else int(name)
+        return self._points_added(self._chk(self.lib.elmk_points_add_field(self.ctx, fid, int(level)), f"points_add_field({name}, {level})"), 0)
+
+    def points_add_row(self, family, which):
+        """One feature row (history_add_row's families) at the columns list; returns the entry id."""
+        fam = ROW_FAMILIES[family] if isinstance(family, str) else int(family)
+        return self._points_added(self._chk(self.lib.elmk_points_add_row(self.ctx, fam, int(which)), f"points_add_row({family}, {which})"), 0)
+
+    def points_add_cell_row(self, family, which):
+        """One cell row of the river stages (cell_history_add_row's families) at the cells list; returns the entry id."""
+        fam = CELL_ROW_FAMILIES[family] if isinstance(family, str) else int(family)
+        return self._points_added(self._chk(self.lib.elmk_points_add_cell_row(self.ctx, fam, int(which)), f"points_add_cell_row({family}, {which})"), 1)
+
+    def points_add_gridded_field(self, name, level=0):
+        """One level of a state field aggregated through the output grid's map at the cells list; returns the entry id."""
+        fid = self.fields[name][0] if isinstance(name, str) else int(name)
+        return self._points_added(self._chk(self.lib.elmk_points_add_gridded_field(self.ctx, fid, int(level)),
+                                            f"points_add_gridded_field({name}, {level})"), 1)
+
+    def points_add_gridded_row(self, family, which):
+        """One feature row aggregated through the output grid's map at the cells list; returns the entry id."""
+        fam = ROW_FAMILIES[family] if isinstance(family, str) else int(family)
+        return self._points_added(self._chk(self.lib.elmk_points_add_gridded_row(self.ctx, fam, int(which)),
+                                            f"points_add_gridded_row({family}, {which})"), 1)
+
+    def points_reserve(self, max_records):
+        """The ring: max_records records of the present entries, device-resident."""
+        self._chk(self.lib.elmk_points_reserve(self.ctx, int(max_records)), "points_reserve")
+
+    def points_record(self, stamp):
+        """One record of every (entry, point) pair with time stamp `stamp`: one launch, stream-ordered, no synchronisation."""
+        self._chk(self.lib.elmk_points_record(self.ctx, float(stamp)), "points_record")
+
+    def points_set_run(self, on=True):
+        """While on, every step of run() records once after the history stage, stamped with the step's decday."""
+        self._chk(self.lib.elmk_points_set_run(self.ctx, 1 if on else 0), "points_set_run")
+
+    def points_count(self):
+        """(total, held): the records since the last reset and how many of them the ring still holds.  Does not synchronise."""
+        t, h = C.c_int64(), C.c_int64()
+        self._chk(self.lib.elmk_points_count(self.ctx, C.byref(t), C.byref(h)), "points_count")
+        return t.value, h.value
+
+    def points_read(self, entry, rec0=0, nrec=None):
+        """float64 [nrec, npoints] of one entry: held records rec0 .. rec0 + nrec - 1, oldest first (nrec None: to the newest).
+        Synchronises."""
+        if nrec is None:
+            nrec = self.points_count()[1] - int(rec0)
+        out = np.empty((max(int(nrec), 0), self._points_n[self._points_kind.get(int(entry), 0)]), dtype=np.float64)
+        self._chk(self.lib.elmk_points_read(self.ctx, int(entry), _p(out), int(rec0), int(nrec)), f"points_read({entry})")
+        return out
+
+    def points_stamps(self, rec0=0, nrec=None):
+        """float64 [nrec]: the stamps of the same records.  Synchronises."""
+        if nrec is None:
+            nrec = self.points_count()[1] - int(rec0)
+        out = np.empty(max(int(nrec), 0), dtype=np.float64)
+        self._chk(self.lib.elmk_points_stamps(self.ctx, _p(out), int(rec0), int(nrec)), "points_stamps")
+        return out
+
+    def points_reset(self):
+        """total back to 0 and the run's recording off; entries, lists and the reservation stay."""
+        self._chk(self.lib.elmk_points_reset(self.ctx), "points_reset")
+
+    def points_clear(self):
+        """Free the part: entries, lists, reservation."""
+        self._chk(self.lib.elmk_points_clear(self.ctx), "points_clear")
+        self._points_n, self._points_kind = [0, 0], {}
 
     # -- restart images (include/elmk.h "restart"; elmkernels_amd/restart.py reads and rewrites them on the host) -------------
     def field_class(self, name):

@@ -1624,6 +1624,77 @@ int elmk_gridded_history_add_row(elmk_ctx *ctx, int tape, int family, int which,
 enum { ELMK_CELL_ROWS_ROUTING = 0, ELMK_CELL_ROWS_SUPPLY = 1, ELMK_CELL_ROWS_NFAMILY = 2 };
 int elmk_cell_history_add_row(elmk_ctx *ctx, int tape, int family, int which, int op);
 
+/* ---- point series -----------------------------------------------------------------------------------
+ * Per-step records of chosen columns and river cells: the series at a flux-tower site (latent heat, t_grnd, ZWT every half hour), the
+ * hydrograph at a gauge cell (QOUT, VOLR, TR, RES every step), a site's gridcell mean - what the tapes of "history" average away and
+ * what "cell rows on history tapes" named as its later change.  An opt-in part: a driver names a few points and a few sources once;
+ * every record is ONE launch that gathers the current value of every (source, point) pair into a device-resident ring
+ * [max_records][values] with a time stamp per record, and the records are read back in bulk whenever the driver likes.  A context that
+ * never calls these entry points enqueues the launches it did and saves the images it did.  elmkernels_amd/points.py restates P1 - P3
+ * in numpy (record(), ring()).
+ *   P0  sources and entries.  An entry is one source; its points are the list of its kind: the columns list (ELMK_POINTS_COLUMNS) for
+ *       elmk_points_add_field and _add_row, the cells list (ELMK_POINTS_CELLS, the output grid's cells, which are the routing's) for
+ *       _add_cell_row, _add_gridded_field and _add_gridded_row.  The sources accepted are exactly those the history entry points accept
+ *       at the moment of the call - elmk_history_add for one level, elmk_column_history_add_row, elmk_cell_history_add_row,
+ *       elmk_gridded_history_add / _add_row for one level - with the same refusals: an unknown field, a level out of range, a family
+ *       that is not enabled, `which` out of range, no output grid.  Entries and lists may change only while total == 0: before the first
+ *       record or after elmk_points_reset.  A list is copied, in any order, duplicates allowed.
+ *   P1  sample.  The stored value widened to fp64 exactly as "history" widens it: F64 as stored (fp32 widened in libelmk_f32.so), I32, U8
+ *       and U32 exactly, rows as their fp64 value.  NaN payloads, infinities and -0.0 arrive bit for bit.
+ *   P2  gridded sample.  elmk_download_gridded's value for that one cell: fill where ptr[i] == ptr[i+1], else v = w[p0] * x[col[p0]], then
+ *       v = v + w[p] * x[col[p]] in term order, no contraction, one lane taking the sum.
+ *   P3  record.  Record number r (0-based since the last reset) lands in slot r % max_records.  A slot holds the stamp and, per entry,
+ *       npoints doubles in list order (entries padded so that one wave never straddles two).  held = min(total, max_records);
+ *       elmk_points_read and _stamps index the held records oldest first, rec0 + nrec <= held.  A record writes nothing but its slot.
+ *   P4  stepwise.  elmk_points_record(ctx, stamp) is ONE launch on the context's stream: no host memory, no synchronisation.  Refused,
+ *       nothing enqueued: without a reservation, without entries, with an entry whose list is empty, on a stream being captured.
+ *   P5  in a run.  While elmk_points_set_run(ctx, 1) is in force every step of elmk_run records once, after the history stage and before
+ *       the cursor moves: the sample of step s is what the step left, the routing's result included; the stamp is the step's decday.  No
+ *       run flag and no member of elmk_run_step: one more launch is enqueued behind the history's, and a captured step is keyed by it.
+ *       Record numbers continue across runs and across stepwise records in between; run k+1 enqueued while run k executes gives the same
+ *       series.  An armed elmk_run is refused, nothing enqueued, where P4 refuses a record.
+ *   P6  counting.  The number of records is known on the host when a record is enqueued: no device counter.  In a replayed graph the
+ *       slot is not baked into the captured arguments: the kernel derives it from the run's step cursor and a base word that elmk_run
+ *       writes on the stream before the run's first step.  elmk_points_count does not synchronise; _read and _stamps do.
+ *   P7  interlocks.  While an entry exists, a call that would free or resize what it reads is refused with ELMK_E_INVALID
+ *       ("elmk_points_clear first") and changes nothing: the clears that row, cell-row and gridded history entries guard, and
+ *       elmk_set_output_grid / elmk_clear_output_grid under gridded or cell-row entries or a cells list.  elmk_points_set checks every
+ *       index against ncols, or against the output grid's ncells; the refusal names the first offending position and value.
+ *   P8  memory.  Everything is counted in elmk_device_bytes and returned by elmk_points_clear.  The restart image does not change in any
+ *       version: the series is output, not state; a driver reads it before it saves.
+ *   P9  untouched contexts.  A context without a reservation runs the kernels, launch sequences and graphs it ran before;
+ *       elmk_points_set_run(ctx, 0), _reset and _clear give back the launch sequence of a context that never had the part.
+ *
+ *   elmk_points_set         the list of `kind` (n <= ELMK_POINTS_MAX_POINTS; n = 0 empties it).  The cells list needs the output grid.
+ *   elmk_points_add_*       one entry; returns its id (>= 0, in order of registration), at most ELMK_POINTS_MAX_ENTRIES.
+ *   elmk_points_reserve     the ring: max_records in 1 .. 2^24 records of the present entries (resized with them while total == 0).
+ *   elmk_points_record      P4.
+ *   elmk_points_set_run     P5; switching it on needs a reservation.
+ *   elmk_points_count       total (records since the last reset) and held; either pointer may be NULL.
+ *   elmk_points_read        host[nrec][npoints] of one entry, held records rec0 .. rec0 + nrec - 1; synchronises.
+ *   elmk_points_stamps      host[nrec], the same records' stamps; synchronises.
+ *   elmk_points_reset       total back to 0 (the next record lands in slot 0) and the run's recording off; entries, lists and the
+ *                           reservation stay.  Synchronises.
+ *   elmk_points_clear       frees everything: entries, lists, reservation, the armed state.
+ * All but elmk_points_record and _count are refused on a stream being captured. */
+enum { ELMK_POINTS_COLUMNS = 0, ELMK_POINTS_CELLS = 1, ELMK_POINTS_NKIND = 2 };
+#define ELMK_POINTS_MAX_ENTRIES 64
+#define ELMK_POINTS_MAX_POINTS 4096 /* per kind */
+int elmk_points_set(elmk_ctx *ctx, int kind, int64_t n, const int64_t *idx /*[n]*/);
+int elmk_points_add_field(elmk_ctx *ctx, int field, int level);
+int elmk_points_add_row(elmk_ctx *ctx, int family, int which);
+int elmk_points_add_cell_row(elmk_ctx *ctx, int family, int which);
+int elmk_points_add_gridded_field(elmk_ctx *ctx, int field, int level);
+int elmk_points_add_gridded_row(elmk_ctx *ctx, int family, int which);
+int elmk_points_reserve(elmk_ctx *ctx, int max_records);
+int elmk_points_record(elmk_ctx *ctx, double stamp);
+int elmk_points_set_run(elmk_ctx *ctx, int on);
+int elmk_points_count(elmk_ctx *ctx, int64_t *total, int64_t *held);
+int elmk_points_read(elmk_ctx *ctx, int entry, double *host /*[nrec][npoints]*/, int64_t rec0, int64_t nrec);
+int elmk_points_stamps(elmk_ctx *ctx, double *host /*[nrec]*/, int64_t rec0, int64_t nrec);
+int elmk_points_reset(elmk_ctx *ctx);
+int elmk_points_clear(elmk_ctx *ctx);
+
 /* ---- restart ---------------------------------------------------------------------------------
  * Exact restarts (E3SM's ERS test: 2N steps give the bits of N steps, a restart, N more steps).  A context saves its column state
  * and history into a self-describing byte buffer, the image, and another context - in another process, or with another column

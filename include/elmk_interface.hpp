@@ -479,6 +479,30 @@ class ELMInterface {
     ok(e < 0 ? e : ELMK_OK);
     return e;
   }
+  /* Point series (elmk.h "point series"): per-step records of chosen columns and river cells - a tower's series, a gauge's
+   * hydrograph - in a device-resident ring.  points_set names the columns (ELMK_POINTS_COLUMNS) or the cells (ELMK_POINTS_CELLS),
+   * points_add_* one source each (what the history entry points of the same kind accept), points_reserve the ring; then either
+   * points_record(stamp) after a step, one launch, or points_set_run(true) and every step of run() records with its decday.
+   * points_read gives one entry's [nrec][npoints], points_stamps the records' stamps, both oldest first. */
+  void points_set(int kind, const std::vector<int64_t>& idx) { ok(elmk_points_set(ctx_, kind, (int64_t)idx.size(), idx.data())); }
+  int points_add_field(const char* field, int level) { return entry(elmk_points_add_field(ctx_, id(field), level)); }
+  int points_add_row(int family, int which) { return entry(elmk_points_add_row(ctx_, family, which)); }
+  int points_add_cell_row(int family, int which) { return entry(elmk_points_add_cell_row(ctx_, family, which)); }
+  int points_add_gridded_field(const char* field, int level) { return entry(elmk_points_add_gridded_field(ctx_, id(field), level)); }
+  int points_add_gridded_row(int family, int which) { return entry(elmk_points_add_gridded_row(ctx_, family, which)); }
+  void points_reserve(int max_records) { ok(elmk_points_reserve(ctx_, max_records)); }
+  void points_record(double stamp) { ok(elmk_points_record(ctx_, stamp)); }
+  void points_set_run(bool on) { ok(elmk_points_set_run(ctx_, on ? 1 : 0)); }
+  int64_t points_count(int64_t* held = nullptr)
+  {
+    int64_t total = 0;
+    ok(elmk_points_count(ctx_, &total, held));
+    return total;
+  }
+  void points_read(int entry, double* host, int64_t rec0, int64_t nrec) { ok(elmk_points_read(ctx_, entry, host, rec0, nrec)); }
+  void points_stamps(double* host, int64_t rec0, int64_t nrec) { ok(elmk_points_stamps(ctx_, host, rec0, nrec)); }
+  void points_reset() { ok(elmk_points_reset(ctx_)); }
+  void points_clear() { ok(elmk_points_clear(ctx_)); }
   /* ELMK_OPT_RESTART_CELLS (elmk.h "restart", version 6): saveRestart() / loadRestart() carry the river stages' state - VOLR, QOUT_SUM
    * and the call count, WH, WT, WF, UNMET_SUM - so that a restart needs no routing_init / ..._init call. */
   void restart_cells(bool on = true) { ok(elmk_set_option(ctx_, ELMK_OPT_RESTART_CELLS, on ? 1 : 0)); }
@@ -654,6 +678,11 @@ class ELMInterface {
   void ok(int rc)
   {
     if (rc != ELMK_OK) throw std::runtime_error(elmk_last_error(ctx_));
+  }
+  int entry(int e)  // an entry id, or a negative code
+  {
+    ok(e < 0 ? e : ELMK_OK);
+    return e;
   }
   int id(const char* field)
   {
