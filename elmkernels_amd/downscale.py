@@ -2,7 +2,7 @@
 restated in the device's operation order, so that the tests can compare the TOPO forcing kernels bit for bit.  numpy only.
 
 exp is math.exp per element: glibc's exp is what the device's elmk_exp restates bit for bit, np.exp is not guaranteed to be.  qsat is
-the caller's (the tests use the reference's own, oracle.Reference().qsat): a function (T, p) -> qs over float64 arrays.  The group
+the caller's (the tests use oracle.qsat, pinned bit for bit to the reference's own): a function (T, p) -> qs over float64 arrays.  The group
 sums go through regrid.apply_aggregate, the host statement of the device's aggregation.
 """
 import math

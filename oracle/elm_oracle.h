@@ -322,6 +322,7 @@ void elmo_timestep7(elmo_state *S, double dt);            /* elm_kokkos_interfac
 
 /* ---- L2 physics, one column (elmo_physics.c) ---- */
 void elmo_qsat(double T, double p, double *es, double *esdT, double *qs, double *qsdT);
+void elmo_qsat_vec(int64_t n, const double *T, const double *p, double *es, double *esdT, double *qs, double *qsdT); /* oracle.qsat */
 double elmo_derive_forc_vp(double forc_qbot, double forc_pbot);
 double elmo_derive_forc_rho(double forc_pbot, double forc_qbot, double forc_tbot);
 double elmo_derive_forc_po2(double forc_pbot);

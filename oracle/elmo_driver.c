@@ -670,6 +670,12 @@ void elmo_pdma(int64_t n, const int *snl, const double *lhs, double *rhs)
   }
 }
 
+/* elmo_qsat elementwise over n values (oracle.qsat): one call of it per element */
+void elmo_qsat_vec(int64_t n, const double *T, const double *p, double *es, double *esdT, double *qs, double *qsdT)
+{
+  for (int64_t i = 0; i < n; i++) elmo_qsat(T[i], p[i], &es[i], &esdT[i], &qs[i], &qsdT[i]);
+}
+
 void elmo_phase_change(elmo_state *S, double dt, const double *dhsdT, const double *c_h2osfc)
 {
   for (int64_t c = 0; c < S->ncols; c++) {

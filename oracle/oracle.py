@@ -86,7 +86,9 @@ class _Lib:
         L.elmo_evaluate_conservation.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.elmo_pdma.argtypes = [C.c_int64] + [C.c_void_p] * 3
         L.elmo_phase_change.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
-        self.ref = _load(os.path.join(HERE, "_ref", "libelmref.so"))
+        L.elmo_qsat_vec.argtypes = [C.c_int64] + [C.c_void_p] * 6
+        L.elmo_qsat_vec.restype = None
+        self.ref =_load(os.path.join(HERE, "_ref", "libelmref.so"))
         if self.ref is not None:
             R = self.ref
             for n in ("frac_wet", "surface_radiation", "canopy_temperature", "bareground_fluxes", "soil_moist_stress"):
@@ -393,6 +395,17 @@ def pdma(snl, lhs, rhs, lib=None):
     fn = globals()["lib"]().lib.elmo_pdma if lib is None else lib.elmref_pdma
     fn(snl.shape[0], snl.ctypes.data, lhs.ctypes.data, sol.ctypes.data)
     return sol
+
+
+def qsat(T, p):
+    """elmo_qsat (qsat_impl.hh:7-78) elementwise over equally shaped float64 arrays -> [es, esdT, qs, qsdT], as Reference.qsat gives
+    the reference's own (tests/test_oracle_vs_ref.py pins the two bit for bit).  Needs no oracle/_ref."""
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    assert T.shape == p.shape
+    out = [np.zeros_like(T) for _ in range(4)]
+    lib().lib.elmo_qsat_vec(T.size, T.ctypes.data, p.ctypes.data, *[o.ctypes.data for o in out])
+    return out
 
 
 def set_pft_tables(psn, alb, z0mr, displar, pft):

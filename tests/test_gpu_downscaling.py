@@ -1,5 +1,5 @@
 """Downscaling of coarse-grid forcing to column elevation on the device (include/elmk.h "downscaling"): equal elevations give the
-bits of OFF, elmk_get_forcing in TOPO mode against elmkernels_amd/downscale.py (with the reference's own qsat), elmk_run against the
+bits of OFF, elmk_get_forcing in TOPO mode against elmkernels_amd/downscale.py (with the oracle's qsat), elmk_run against the
 stepwise calls (per-column series and a forcing grid, graph on and off), the physical properties of the adjusted fields, the snow a
 mountain column keeps, the refusals, an exact restart and the demo; and the longwave renormalisation on its own (k_ds_lw_norm) on
 every group shape of tests/output_map_cases.py, in both builds."""
@@ -33,13 +33,23 @@ def base():
 
 
 def _qsat():
-    """The reference's qsat (qsat_impl.hh) through oracle/_ref: (T, p) -> qs."""
+    """The oracle's qsat (elmo_qsat, the reference's qsat_impl.hh restated and pinned to it bit for bit): (T, p) -> qs."""
+    from oracle import oracle as O
+
+    return lambda T, p: O.qsat(T, p)[2]
+
+
+def test_oracle_qsat_is_the_references():
+    """Where oracle/_ref is built: the qsat these tests use has the bits of the reference's own, over both clamps of td."""
     from oracle import oracle as O
 
     if not O.have_ref():
         pytest.skip("oracle/_ref/libelmref.so not built (build() makes it where the reference is mounted)")
-    R = O.Reference()
-    return lambda T, p: R.qsat(T, p)[2]
+    rng = np.random.default_rng(7)
+    T = rng.uniform(180.0, 390.0, 20000)
+    p = rng.uniform(4.0e4, 1.05e5, 20000)
+    for a, b in zip(O.qsat(T, p), O.Reference().qsat(T, p)):
+        assert same(a, b)
 
 
 def _elevations(n, seed):
