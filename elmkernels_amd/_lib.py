@@ -131,6 +131,10 @@ SIGNATURES = {
     "elmk_soil_hydrology_frost_enable": (C.c_int, [_P, _P]),
     "elmk_soil_hydrology_frost_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
     "elmk_soil_hydrology_frost_clear": (C.c_int, [_P]),
+    "elmk_hillslope_enable": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double]),
+    "elmk_hillslope_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "elmk_hillslope_budget": (C.c_int, [_P, _P]),
+    "elmk_hillslope_clear": (C.c_int, [_P]),
     "elmk_water_balance_enable": (C.c_int, [_P, C.c_double]),
     "elmk_water_balance_begin": (C.c_int, [_P]),
     "elmk_water_balance": (C.c_int, [_P, C.c_double, _P, _P, _P]),

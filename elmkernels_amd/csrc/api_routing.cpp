@@ -649,6 +649,7 @@ int elmk_floodplain_infiltration_enable(elmk_ctx* ctx)
   if (int rc = part_enter(ctx, FP, who)) return rc;  // (the routing, its kinematic-wave scheme, the inundation: each refusal says which)
   Routing& T = ctx->route;
   if (T.land.mem) return invalid(ctx, "elmk_floodplain_infiltration_enable: already on");
+  if (int rc = hs_excludes(ctx, who)) return rc;  // (the LAT and ROF forms of the hydrology kernel do not combine yet)
   if (int rc = refuse_capture(ctx, who)) return rc;
   // F0: the context keeps no host copy of the output grid's map, so from a download of its ptr and col
   const CsrMap& M = ctx->ogrid.map;

@@ -110,6 +110,13 @@ void hyd_launch(elmk_ctx* ctx, double dt)
 {
   if (!hyd_land(ctx)) return;
   const elmk_ctx::Routing& T = ctx->route;
+  if (ctx->hs.mem) {  // L1 and L2, then the LAT form, exactly while the hillslope lateral flow is on (it excludes the two forms below)
+    const elmk_ctx::Hillslope& H = ctx->hs;
+    launch_hillslope(ctx->d, ctx->ncols, ctx->ld, ctx->hyd_rows, HillslopeArgs{H.rows, H.geom, H.down, H.up, H.npad, H.k_aniso}, ctx->stream);
+    const LatArgs lat{H.rows + (size_t)ELMK_HS_QLAT_NET * (size_t)ctx->ld, H.down};
+    launch_soil_hydrology(ctx->d, ctx->ncols, ctx->hyd_rows, nullptr, dt, ctx->stream, nullptr, &lat);
+    return;
+  }
   if (T.land.mem) {  // the ROF form exactly while the floodplain infiltration is on
     const size_t cld = (size_t)T.cld;
     const RofArgs rof{T.land_cellof, T.fp.rows + FP_WF * cld, T.fp.rows + FP_FRAC * cld, T.area, T.land.tab};
@@ -159,6 +166,11 @@ const double* feature_row(const elmk_ctx* ctx, int family, int which, const char
     if (!ctx->route.land.mem) return *why = "the family's feature is not enabled", nullptr;
     if (which < 0 || which >= ELMK_FPI_NROWS) return *why = "unknown row", nullptr;
     return ctx->route.land.tab + (size_t)which * (size_t)ctx->ld;
+  }
+  if (family == ELMK_ROWS_HILLSLOPE) {  // (the extension's rows lie in its own allocation)
+    if (!ctx->hs.mem) return *why = "the family's feature is not enabled", nullptr;
+    if (which < 0 || which >= ELMK_HS_NROWS) return *why = "unknown row", nullptr;
+    return ctx->hs.rows + (size_t)which * (size_t)ctx->ld;
   }
   if (family < 0 || family >= ELMK_ROWS_NFAMILY) return *why = "unknown row family", nullptr;
   const Rows& R = *FAMILY[family];
@@ -286,8 +298,13 @@ int elmk_soil_hydrology_clear(elmk_ctx* ctx)
     if (int rc = rows_held(ctx, *R, who)) return rc;
   if (int rc = land_holds(ctx, who)) return rc;  // (the hydrology's ROF form and the water balance's LAND form go with their rows)
   if (int rc = route_holds(ctx, who)) return rc;  // (the routing reads the water balance's QRUNOFF)
+  if (int rc = hs_held(ctx, who)) return rc;
   if (int rc = elmk_water_balance_clear(ctx)) return rc;
   if (int rc = rows_clear(ctx, HYDF, who)) return rc;
+  if (ctx->hs.mem) {  // the hillslope lateral flow goes with the stage it extends
+    if (int rc = quiesce(ctx, false)) return rc;
+    hs_release(ctx);
+  }
   const int rc = rows_clear(ctx, HYD, who);
   if (rc == ELMK_OK) ctx->hyd_params = false;
   return rc;
@@ -299,6 +316,7 @@ int elmk_soil_hydrology_frost_enable(elmk_ctx* ctx, const double* q_perch_max)
   const char* who = "elmk_soil_hydrology_frost_enable";
   if (int rc = rows_enter(ctx, HYD, who)) return rc;
   if (!q_perch_max) return invalid(ctx, "elmk_soil_hydrology_frost_enable: null argument");
+  if (int rc = hs_excludes(ctx, who)) return rc;  // (F'.A skips F.1 and F.2, which would drop a flux the neighbours have booked)
   if (int rc = rows_held(ctx, HYDF, who)) return rc;  // (a second enable: refused under row entries as the clear is)
   if (int rc = rows_enable(ctx, HYDF, who)) return rc;  // (zero-filled: the diagnostics)
   const size_t n = (size_t)ctx->ncols;

@@ -352,7 +352,8 @@ int elmk_run(elmk_ctx* ctx, double dt, const elmk_run_step* steps, int nsteps, i
                     (flags & ELMK_RUN_WATER_BALANCE) && (bool)ctx->irr_rows, (flags & ELMK_RUN_ROUTING) && ctx->route.withdraw,
                     (flags & ELMK_RUN_IRRIGATION) && hyd_land(ctx) && (bool)ctx->irrsup_rows,
                     (flags & ELMK_RUN_ROUTING) && (bool)ctx->route.dam.mem, (flags & ELMK_RUN_ROUTING) && (bool)ctx->route.heat.mem,
-                    (bool)ctx->route.land.mem, (bool)ctx->route.cmd.mem, points_key(ctx)};
+                    (bool)ctx->route.land.mem, (bool)ctx->route.cmd.mem, points_key(ctx),
+                    (flags & ELMK_RUN_HYDROLOGY) && hyd_land(ctx) && (bool)ctx->hs.mem};
   if (cz) {  // the run's czf replaces the stepwise record time's
     ctx->sw.step_time = false;
     ctx->sw.czf_ready = true;

@@ -642,7 +642,7 @@ int64_t elmk_device_bytes(const elmk_ctx* ctx)
   size_t n = ctx->arena.bytes() + ctx->staging.bytes() + ctx->scratch.bytes() + ctx->snicar.bytes() + ctx->snowage.bytes() + ctx->d.bytes() +
              ctx->run.mem.bytes() + ctx->grid.mem.bytes() + ctx->ogrid.mem.bytes() + ctx->sw.czf.bytes() + ctx->run.rec.bytes() +
              ctx->ds.topo.bytes() + ctx->ds.gmem.bytes() + ctx->accum_table.bytes() + ctx->aer.mem.bytes() + ctx->alt_rows.bytes() +
-             ctx->hyd_rows.bytes() + ctx->hydf_rows.bytes() + ctx->wb_rows.bytes() + ctx->wb_red.bytes() + ctx->wb_ring.bytes() +
+             ctx->hyd_rows.bytes() + ctx->hydf_rows.bytes() + ctx->hs.mem.bytes() + ctx->wb_rows.bytes() + ctx->wb_red.bytes() + ctx->wb_ring.bytes() +
              ctx->irr_rows.bytes() + route_bytes(ctx) + ctx->irrsup_rows.bytes() + ctx->pts.mem.bytes() + ctx->pts.ring.bytes() +
              ctx->pts.stamps.bytes();
   // the cell rows of gridded history entries (not the column rows) and the accumulators' values: whole rows of ld or cld doubles,

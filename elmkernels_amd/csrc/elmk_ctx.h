@@ -168,10 +168,11 @@ struct StepKey {
   bool land = false;                         // the floodplain infiltration is on: the hydrology, water balance and routing stages take its forms
   bool route_cmd = false;                    // the command areas are on: the routing stage has their two launches, the supply limit their form
   uint64_t points_version = 0;               // the point series is armed: its launch follows the history's (its version; 0: not armed)
+  bool hyd_lat = false;                      // the hydrology stage is in the step and takes the hillslope lateral flow's form and launches
   auto tie() const
   {
     return std::tie(flags, ds_topo, ds_groups, coszen, hyd_stage, hyd_frost, hist_version, accum_version, irr_stage, wb_irrig, route_withdraw,
-                    irr_supply, route_dam, route_heat, land, route_cmd, points_version);
+                    irr_supply, route_dam, route_heat, land, route_cmd, points_version, hyd_lat);
   }
   bool operator==(const StepKey& o) const { return tie() == o.tie(); }
 };
@@ -271,6 +272,20 @@ struct elmk_ctx {
   bool hyd_params = false;  // elmk_soil_hydrology_set_params has been called since the enable
   // its frost-table extension (elmk_soil_hydrology_frost_*): the ELMK_HYDF_NROWS fp64 rows [row][ld], held while the extension is enabled
   DevBuf<double> hydf_rows;
+  // its hillslope lateral flow (elmk_hillslope_*; api_hillslope.cpp): one allocation `mem` holds the ELMK_HS_NROWS fp64 rows [row][ld],
+  // the geometry dist, width, area, elev [HS_NGEOM][ld], down [ld] (-2 in the padding columns), the uphill map [npad][ld] and the
+  // budget's reduction partials [ELMK_CONS_NPART][3] and triple [3]; held exactly while the extension is on
+  struct Hillslope {
+    DevBuf<char> mem;
+    double* rows = nullptr;
+    double* geom = nullptr;
+    int32_t* down = nullptr;
+    int32_t* up = nullptr;
+    double* part = nullptr;
+    double* out = nullptr;
+    int npad = 0;
+    double k_aniso = 0.0;
+  } hs;
   // water balance (elmk_water_balance_*): the ELMK_WB_NROWS fp64 rows [row][ld] and, in wb_red, the reduction's stage-1 partials
   // [3][ELMK_CONS_NPART][3], its triples [3][3] and the census {nbad, first bad column}; held exactly while the feature is enabled.
   // wb_ring: the run's ring rows, per buffer b and step the triples (wb_ring_mms: rows b * max_steps .., 9 doubles each) and the census
@@ -563,6 +578,12 @@ constexpr int ALT_NROWS = 3;  // api_rows.cpp
 ActiveLayerArgs alt_args(const elmk_ctx* ctx);
 bool hyd_land(const elmk_ctx* ctx);
 void hyd_launch(elmk_ctx* ctx, double dt);
+// the hillslope lateral flow (api_hillslope.cpp): "<who>: the hillslope lateral flow is on (elmk_hillslope_clear first)" while it is;
+// "<who>: history entries over the hillslope rows exist (elmk_history_clear first)" or the point series' text while an entry reads its
+// rows; the release (the stream is idle)
+int hs_excludes(elmk_ctx* ctx, const char* who);
+int hs_held(elmk_ctx* ctx, const char* who);
+void hs_release(elmk_ctx* ctx);
 int wb_ring_alloc(elmk_ctx* ctx);  // the water balance's ring rows of the current reservation, if the feature is enabled (the stream is idle)
 void wb_begin_launch(elmk_ctx* ctx);
 void wb_launch(elmk_ctx* ctx, double dt, bool run);

@@ -282,8 +282,28 @@ struct RofArgs {
   const double *wf, *ff, *area;
   double* out;
 };
+// lat not null: the hillslope lateral flow's form (L3; frost_rows and rof are then null): qnet the extension's QLAT_NET row [ld], down [ld]
+struct LatArgs {
+  const double* qnet;
+  const int32_t* down;
+};
 void launch_soil_hydrology(const DevState* S, int64_t n, double* rows, double* frost_rows, double dt, hipStream_t st,
-                           const RofArgs* rof = nullptr);
+                           const RofArgs* rof = nullptr, const LatArgs* lat = nullptr);
+
+// hillslope lateral flow (k_hillslope.hip, elmk_hillslope_*; include/elmk.h "hillslope lateral flow"): the two launches in front of the
+// hydrology kernel's LAT form.  rows: the extension's fp64 rows [ELMK_HS_NROWS][ld]; geom: dist, width, area, elev [HS_NGEOM][ld];
+// down [ld] (-2 in the padding columns); up [npad][ld], the uphill columns of each column in ascending order, -1 = none
+enum { HS_DIST = 0, HS_WIDTH = 1, HS_AREA = 2, HS_ELEV = 3, HS_NGEOM = 4 };
+struct HillslopeArgs {
+  double* rows;
+  const double* geom;
+  const int32_t* down;
+  const int32_t* up;
+  int npad;
+  double k_aniso;
+};
+// L1 (HEAD, TRANS from the hydrology's rows and the state), then L2 (the four flux rows)
+void launch_hillslope(const DevState* S, int64_t n, int64_t ld, const double* hyd_rows, const HillslopeArgs& A, hipStream_t st);
 
 // water balance (k_water_balance.hip, elmk_water_balance_*): hyd_rows / frost_rows as launch_soil_hydrology's (frost_rows null: the
 // extension is off), wb_rows = the ELMK_WB_NROWS fp64 rows of the feature, [row][ld].

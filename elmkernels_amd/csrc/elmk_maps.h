@@ -147,6 +147,66 @@ inline const char* route_check(int64_t ncells, const int32_t* down, const double
   return nullptr;
 }
 
+// Hillslopes (elmk_hillslope_enable; include/elmk.h "hillslope lateral flow"): every column drains into one downhill column down[c],
+// into the stream (-1), or is on no hillslope (-2).  Checks, in this order: the arguments; per column in index order the range of down;
+// a self-loop; a column draining into a -2 column; the in-degree (at most ROUTE_MAXUP); cycles, by route_check's linear two-mark walk
+// (nothing recurses); then over the hillslope columns (down != -2) in index order, row by row: dist, width, area finite and > 0, elev
+// finite; k_aniso finite and > 0.  Returns the text, which names the row, and in *col the first offending column (-1 where the text is
+// about no column); the entry point puts " at column <col>" behind the text.  nullptr: accepted.
+// For an accepted hillslope set *nup is the largest in-degree (0 .. 8) and up the uphill map as the device reads it: row p of
+// ell_npad(*nup) rows of ld >= ncols entries each holds, for column c, the p-th column u with down[u] == c in ascending u, else -1.
+inline const char* hillslope_check(int64_t ncols, const int32_t* down, const double* dist, const double* width, const double* area,
+                                   const double* elev, double k_aniso, int64_t ld, int* nup, std::vector<int32_t>* up, int64_t* col)
+{
+  if (col) *col = -1;
+  if (ncols < 1 || ncols > INT32_MAX) return "ncols outside 1 .. 2^31-1";
+  if (!down || !dist || !width || !area || !elev) return "null argument";
+  const auto at = [col](const char* what, int64_t c) {
+    if (col) *col = c;
+    return what;
+  };
+  for (int64_t c = 0; c < ncols; c++)
+    if (down[c] < -2 || down[c] >= ncols) return at("down outside {-2, -1} and [0, ncols)", c);
+  for (int64_t c = 0; c < ncols; c++)
+    if (down[c] == c) return at("down equals its own index", c);
+  for (int64_t c = 0; c < ncols; c++)
+    if (down[c] >= 0 && down[c] != c && down[down[c]] == -2) return at("down names a column on no hillslope", c);
+  std::vector<char> deg((size_t)ncols, 0);
+  int most = 0;
+  for (int64_t c = 0; c < ncols; c++) {
+    if (down[c] < 0) continue;
+    char& d = deg[(size_t)down[c]];
+    if (d == ROUTE_MAXUP) return at("more than 8 uphill columns drain into one column", c);
+    d++;
+    if (d > most) most = d;
+  }
+  std::vector<char> mark((size_t)ncols, 0);
+  for (int64_t c = 0; c < ncols; c++) {
+    if (mark[(size_t)c]) continue;
+    int64_t j = c;
+    for (; j >= 0 && mark[(size_t)j] == 0; j = down[j]) mark[(size_t)j] = 1;
+    if (j >= 0 && mark[(size_t)j] == 1) return at("the hillslope has a cycle", c);
+    for (j = c; j >= 0 && mark[(size_t)j] == 1; j = down[j]) mark[(size_t)j] = 2;
+  }
+  const double* const rows[3] = {dist, width, area};
+  static const char* const bad[3] = {"dist not finite and > 0", "width not finite and > 0", "area not finite and > 0"};
+  for (int k = 0; k < 3; k++)
+    for (int64_t c = 0; c < ncols; c++)
+      if (down[c] != -2 && !(std::isfinite(rows[k][c]) && rows[k][c] > 0.0)) return at(bad[k], c);
+  for (int64_t c = 0; c < ncols; c++)
+    if (down[c] != -2 && !std::isfinite(elev[c])) return at("elev not finite", c);
+  if (!(std::isfinite(k_aniso) && k_aniso > 0.0)) return "k_aniso not finite and > 0";
+  if (nup) *nup = most;
+  if (up) {
+    if (ld < ncols) ld = ncols;
+    up->assign((size_t)ell_npad(most) * (size_t)ld, -1);
+    deg.assign((size_t)ncols, 0);
+    for (int64_t u = 0; u < ncols; u++)  // ascending u: each column's slots fill in ascending order
+      if (down[u] >= 0) (*up)[(size_t)deg[(size_t)down[u]]++ * (size_t)ld + (size_t)down[u]] = (int32_t)u;
+  }
+  return nullptr;
+}
+
 // Kinematic-wave routing parameters (elmk_routing_kinematic_enable; include/elmk.h "kinematic-wave routing"): params as
 // [KINEMATIC_NPARAM][ncells] in the order of ELMK_KW_*, every value finite and > 0.  Checks row by row, in row order; the text names
 // the first failing row.  For accepted parameters dev holds the seven rows the device keeps, [7][ld] with ld >= ncells in the order CH,

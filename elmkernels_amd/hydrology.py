@@ -9,6 +9,8 @@ text is the specification and `step` is its host truth.
     advance_physics(S, dt); S.soil_hydrology(dt)    # or S.run(dt, steps, RUN_HYDROLOGY)
     S.soil_hydrology_frost_enable(q_perch_max(slope))   # optional: the frost table and the perched water table (the header's F');
                                                         # step(..., frost=rows) is that form on the host
+    S.hillslope_enable(down, dist, width, area, elev, k_aniso)  # optional: lateral flow along hillslopes (the header's L1 - L3);
+                                                                # step(..., lat=(down, dist, width, area, elev, k_aniso)) on the host
 
 pow, exp and erf are math.pow / math.exp / math.erf per element (glibc), which the device's elmk_pow / elmk_exp restate bit for bit;
 np.power and np.exp are not guaranteed to.  min(a, b) and max(a, b) are (b < a ? b : a) and (a < b ? b : a), written out.
@@ -95,6 +97,20 @@ def _jwt(zwt, zi):
         if zwt <= zi[j + 1]:
             return j
     return N
+
+
+def _lat_rise(rt, zwt, jwt, liq, zi, watsat, sucsat, bsw):
+    """L3's rising walk ("hillslope lateral flow"): E's with rt for qt and the water into every visited layer of liq (changed in place).
+    Returns (what is left of rt, the water table, the layers visited, whether the walk ended inside a layer)."""
+    for j in range(jwt, -1, -1):
+        sy = _sy(zwt, watsat[j], sucsat[j], bsw[j])
+        ql = _max(0.0, _min(rt, sy * (zwt - zi[j]) * 1.0e3))
+        liq[j] = liq[j] + ql
+        zwt = zwt - _div(_div(ql, sy), 1000.0)
+        rt = rt - ql
+        if rt <= 0.0:
+            return rt, zwt, jwt - j + 1, True
+    return rt, zwt, jwt + 1, False
 
 
 def column(c, dt, hit=None, probe=None):
@@ -402,14 +418,26 @@ def column(c, dt, hit=None, probe=None):
             sd = sd + dzmm[j]
         imp = _pow(10.0, -E_ICE * _div(si, sd))
         rsub_top = imp * c["rsub_top_max"] * _exp(-FFF_D * zwt)
+        lat = c.get("lat")  # L3 ("hillslope lateral flow"): QLAT_NET of a column on a hillslope, in the place of the baseflow
+        if lat is not None:
+            rsub_top = lat
         rt = -rsub_top * dt
         if jwt == N:
             mark("drain_aquifer")
+            if lat is not None:
+                mark("lat_aquifer_inflow" if rt > 0.0 else "lat_aquifer")
             wa = wa + rt
             zwt = zwt - _div(_div(rt, 1000.0), rous)
             liq[L] = liq[L] + _max(0.0, wa - AQUIFER_MAX)
             wa = _min(wa, AQUIFER_MAX)
+        elif lat is not None and rt > 0.0:
+            rt, zwt, visited, ended = _lat_rise(rt, zwt, jwt, liq, zi, watsat, sucsat, bsw)
+            walks["L_rise"] = (visited, not ended)
+            mark("lat_rise_in_layer" if ended else "lat_rise_surface")
+            liq[0] = liq[0] + rt
         else:
+            if lat is not None:
+                mark("lat_fall")
             mark("drain_soil")
             walks["F_drain"] = (N - jwt, True)
             for j in range(jwt, N):
@@ -489,7 +517,7 @@ FPI_H2OROF, FPI_FRAC, FPI_QFLX_DRAIN = range(3)  # ELMK_FPI_*: the floodplain in
 FPI_NROWS = 3
 
 
-def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None, rof=None):
+def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None, rof=None, lat=None):
     """One elmk_soil_hydrology on the host.
 
     fields: a dict of the state fields READS and h2osoi_vol as S[name] downloads them ([n] or [n, nlev], any float dtype: widened to
@@ -502,8 +530,17 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None, rof=N
     (out, rows_out, frost_out), frost_out the extension's rows after the step.  probes: a list that receives column()'s probe of every
     column in turn.  rof=(cellof, wf, flood_frac, area): the floodplain infiltration's form (include/elmk.h "floodplain infiltration",
     F1 - F3): cellof int [n], the cell of every column or -1; wf, flood_frac, area float64 [ncells], the routing's rows as its last call
-    left them.  The result grows by fpi_out, float64 [FPI_NROWS, n]: H2OROF, FRAC, QFLX_H2OROF_DRAIN."""
+    left them.  The result grows by fpi_out, float64 [FPI_NROWS, n]: H2OROF, FRAC, QFLX_H2OROF_DRAIN.
+    lat=(down, dist, width, area, elev, k_aniso): the hillslope lateral flow's form (include/elmk.h "hillslope lateral flow"): L1 and L2
+    from the inputs (hillslope_head, hillslope_flow), then every column with L3.  The result grows by hs_out, float64 [HS_NROWS, n].  It
+    excludes frost and rof, as the device does."""
     dt = float(dt)
+    if lat is not None:
+        assert frost is None and rof is None
+        l_down = np.asarray(lat[0]).reshape(-1)
+        hs_out = np.zeros((HS_NROWS, l_down.size))
+        hs_out[HS_HEAD], hs_out[HS_TRANS] = hillslope_head(fields, rows, l_down, lat[4], lat[5])
+        hs_out[HS_QLAT_OUT:] = hillslope_flow(hs_out[HS_HEAD], hs_out[HS_TRANS], l_down, lat[1], lat[2], lat[3], hit=hit)
     if rof is not None:
         r_cell = np.asarray(rof[0]).reshape(-1)
         r_wf, r_ff, r_ar = (np.asarray(x, dtype=np.float64).reshape(-1) for x in rof[1:])
@@ -539,6 +576,10 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None, rof=N
         if rof is not None:
             g = int(r_cell[i])
             c["rof"] = (True, float(r_wf[g]), float(r_ff[g]), float(r_ar[g])) if g >= 0 else (False, 0.0, 0.0, 0.0)
+        if lat is not None and int(l_down[i]) != -2:
+            c["lat"] = float(hs_out[HS_QLAT_NET, i])
+        elif lat is not None and hit is not None:
+            hit.add("lat_off_hillslope")
         if probes is None:
             o = column(c, dt, hit)
         else:
@@ -566,7 +607,186 @@ def step(fields, rows, dt, hit=None, stored=None, frost=None, probes=None, rof=N
         out["h2osoi_vol"][:, :N] = rnd(res["h2osoi_vol"][:, :N], out["h2osoi_vol"])
         out["h2osfc"][:] = rnd(res["h2osfc"], out["h2osfc"])
     ret = (out, rows_out) if frost is None else (out, rows_out, frost_out)
+    if lat is not None:
+        return ret + (hs_out,)
     return ret if rof is None else ret + (fpi_out,)
+
+
+# ---- hillslope lateral flow (include/elmk.h "hillslope lateral flow"; k_hillslope.hip, elmk_maps.h: hillslope_check) --------------
+HS_HEAD, HS_TRANS, HS_QLAT_OUT, HS_QLAT_IN, HS_QLAT_NET, HS_QSTREAM = range(6)  # ELMK_HS_*
+HS_NROWS = 6
+HS_MAXUP = 8
+
+
+def hillslope_check(down, dist, width, area, elev, k_aniso):
+    """elmk_maps.h: hillslope_check on the host, the same checks in the same order with the same texts: returns (text, col) - the
+    refusal and the first offending column, -1 where the text is about no column - or (None, -1) for an accepted set.  The entry point's
+    message is "elmk_hillslope_enable: <text> at column <col>"."""
+    if any(v is None for v in (down, dist, width, area, elev)):
+        return "null argument", -1
+    down = np.asarray(down).reshape(-1)
+    n = down.size
+    if n < 1 or n > 2 ** 31 - 1:
+        return "ncols outside 1 .. 2^31-1", -1
+    d = down.astype(np.int64)
+    rows = [np.asarray(v, dtype=np.float64).reshape(-1) for v in (dist, width, area, elev)]
+
+    def first(mask):
+        idx = np.nonzero(mask)[0]
+        return int(idx[0]) if idx.size else -1
+
+    c = first((d < -2) | (d >= n))
+    if c >= 0:
+        return "down outside {-2, -1} and [0, ncols)", c
+    c = first(d == np.arange(n))
+    if c >= 0:
+        return "down equals its own index", c
+    c = first((d >= 0) & (d[np.maximum(d, 0)] == -2))
+    if c >= 0:
+        return "down names a column on no hillslope", c
+    deg = [0] * n
+    for c in range(n):
+        if d[c] >= 0:
+            if deg[d[c]] == HS_MAXUP:
+                return "more than 8 uphill columns drain into one column", c
+            deg[d[c]] += 1
+    mark = [0] * n
+    dl = d.tolist()
+    for c in range(n):
+        if mark[c]:
+            continue
+        j = c
+        while j >= 0 and mark[j] == 0:
+            mark[j] = 1
+            j = dl[j]
+        if j >= 0 and mark[j] == 1:
+            return "the hillslope has a cycle", c
+        j = c
+        while j >= 0 and mark[j] == 1:
+            mark[j] = 2
+            j = dl[j]
+    on = d != -2
+    with np.errstate(invalid="ignore"):
+        for name, row in zip(("dist", "width", "area"), rows):
+            c = first(on & ~(np.isfinite(row) & (row > 0.0)))
+            if c >= 0:
+                return name + " not finite and > 0", c
+        c = first(on & ~np.isfinite(rows[3]))
+    if c >= 0:
+        return "elev not finite", c
+    k = float(k_aniso)
+    if not (math.isfinite(k) and k > 0.0):
+        return "k_aniso not finite and > 0", -1
+    return None, -1
+
+
+def hillslope_map(down):
+    """The uphill map of an accepted set as the device reads it: int32 [npad, n], npad = 1, 2, 4 or 8 rows; row p holds, for column c,
+    the p-th column u with down[u] == c in ascending u, else -1."""
+    d = np.asarray(down).reshape(-1).astype(np.int64)
+    n = d.size
+    slots = [[] for _ in range(n)]
+    for u in range(n):
+        if d[u] >= 0:
+            slots[d[u]].append(u)
+    most = max((len(v) for v in slots), default=0)
+    npad = 1 if most <= 1 else 2 if most <= 2 else 4 if most <= 4 else 8
+    up = np.full((npad, n), -1, dtype=np.int32)
+    for c, v in enumerate(slots):
+        up[:len(v), c] = v
+    return up
+
+
+def hillslope_head(fields, rows, down, elev, k_aniso):
+    """L1 on the host: (HEAD [n], TRANS [n]) from the state fields (h2osoi_ice, dz, zisoi, watsat as S[name] downloads them) and the
+    hydrology's rows [NROWS, n] at the start of the stage."""
+    rows = np.asarray(rows, dtype=np.float64)
+    down = np.asarray(down).reshape(-1)
+    n = down.size
+    elev = np.broadcast_to(np.asarray(elev, dtype=np.float64), (n,))
+    k_aniso = float(k_aniso)
+    w = {k: np.asarray(fields[k]).astype(np.float64) for k in ("h2osoi_ice", "dz", "zisoi", "watsat")}
+    head, trans = np.zeros(n), np.zeros(n)
+    s0, s1 = NLEVSNO, NLEVSNO + N
+    for c in range(n):
+        if int(down[c]) == -2:
+            continue
+        zwt = float(rows[ZWT, c])
+        ice, dz = w["h2osoi_ice"][c, s0:s1].tolist(), w["dz"][c, s0:s1].tolist()
+        zi, watsat = w["zisoi"][c, s0:s1 + 1].tolist(), w["watsat"][c, :N].tolist()
+        hksat = rows[HKSAT:HKSAT + N, c].tolist()
+        jwt = _jwt(zwt, zi)
+        t = 0.0
+        if jwt < N:
+            si, sd = 0.0, 0.0
+            for j in range(_max(jwt - 1, 0), N):
+                vol_ice = _min(watsat[j], _div(ice[j], dz[j] * DENICE))
+                icefrac = _min(1.0, _div(vol_ice, watsat[j]))
+                dzmm = dz[j] * 1.0e3
+                si = si + icefrac * dzmm
+                sd = sd + dzmm
+            imp = _pow(10.0, -E_ICE * _div(si, sd))
+            for j in range(jwt, N):
+                t = t + hksat[j] * (zi[j + 1] - zwt if j == jwt else dz[j])
+            t = imp * t * 1.0e-3 * k_aniso
+        head[c] = _canon(float(elev[c]) - zwt)
+        trans[c] = _canon(t)
+    return head, trans
+
+
+def _hs_vol(d, hu, tu, hd, td, dist, width, hit=None):
+    """L2: the flux of the edge out of a column, m3/s; d its down (-1: the stream), hd and td HEAD and TRANS of d."""
+    if d == -1:
+        g = _max(_div(hu, dist), 0.0)
+        if hit is not None:
+            hit.add("lat_stream_clamp" if not hu > 0.0 else "lat_stream")
+    else:
+        g = _div(hu - hd, dist)
+    if hit is not None:
+        if g < -2.0:
+            hit.add("lat_clamp_lo")
+        if g > 2.0:
+            hit.add("lat_clamp_hi")
+        if d != -1 and g > 0.0:
+            hit.add("lat_g_pos")
+        if d != -1 and g < 0.0:
+            hit.add("lat_g_neg")
+    g = _min(_max(g, -2.0), 2.0)
+    t = td if (d != -1 and g < 0.0) else tu
+    return t * width * g
+
+
+def hillslope_flow(head, trans, down, dist, width, area, up=None, hit=None):
+    """L2 on the host: float64 [4, n], QLAT_OUT, QLAT_IN, QLAT_NET, QSTREAM.  up: hillslope_map(down), or None to build it."""
+    head, trans = (np.asarray(v, dtype=np.float64).tolist() for v in (head, trans))
+    down = np.asarray(down).reshape(-1).astype(np.int64).tolist()
+    n = len(down)
+    dist, width, area = (np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)).tolist() for v in (dist, width, area))
+    up = hillslope_map(down) if up is None else np.asarray(up)
+    out = np.zeros((4, n))
+    for c in range(n):
+        d = down[c]
+        if d == -2:
+            continue
+        hd, td = (head[d], trans[d]) if d >= 0 else (0.0, 0.0)
+        vol = _hs_vol(d, head[c], trans[c], hd, td, dist[c], width[c], hit)
+        qo = _div(1.0e3 * vol, area[c])
+        qi = 0.0
+        for p in range(up.shape[0]):
+            u = int(up[p, c])
+            if u >= 0:
+                qi = qi + _div(1.0e3 * _hs_vol(c, head[u], trans[u], head[c], trans[c], dist[u], width[u]), area[c])
+        out[:, c] = _canon(qo), _canon(qi), _canon(qo - qi), _canon(vol if d == -1 else 0.0)
+    return out
+
+
+def hillslope_budget(qstream):
+    """elmk_hillslope_budget on the host: float64 [1], the sum of QSTREAM in the device reduction's order
+    (diagnostics.reduce_min_max_sum)."""
+    from .diagnostics import reduce_min_max_sum
+
+    q = np.asarray(qstream, dtype=np.float64).reshape(-1)
+    return np.array([reduce_min_max_sum(q)[2] if q.size else 0.0])
 
 
 # ---- parameters -------------------------------------------------------------------------------------------------------------------

@@ -46,11 +46,14 @@ WB_NROWS = 7  # elmk_water_balance_read: the row numbers are hydrology.WB_BEGWB 
 ROWS_ALT, ROWS_HYDROLOGY, ROWS_FROST, ROWS_WATER_BALANCE, ROWS_IRRIGATION = range(5)  # history_add_row: the feature families (ELMK_ROWS_*)
 ROWS_FLOODPLAIN = 7  # ... and the floodplain infiltration's (ELMK_ROWS_FLOODPLAIN; which = FPI_*), past the cell-row families' numbers
 FPI_H2OROF, FPI_FRAC, FPI_QFLX_DRAIN = range(3)  # floodplain_infiltration_read (hydrology.FPI_*)
+ROWS_HILLSLOPE = 8  # ... and the hillslope lateral flow's (ELMK_ROWS_HILLSLOPE; which = HS_*)
+HS_HEAD, HS_TRANS, HS_QLAT_OUT, HS_QLAT_IN, HS_QLAT_NET, HS_QSTREAM = range(6)  # hillslope_read (hydrology.HS_*)
+HS_NROWS = 6
 ROUTE_QLAND = 20  # routing_read while the floodplain infiltration is on (routing.QLAND)
 ROUTE_CMD_WANT, ROUTE_CMD_TAKE, ROUTE_CMD_GIVE, ROUTE_CMD_RATIO = 21, 22, 23, 24  # ... while the command areas are on (routing.CMD_WANT ..)
 ROUTE_CMD_NDEP = 4  # ELMK_CMD_NDEP: the slots of a cell's dependency rows
 ROW_FAMILIES = {"alt": ROWS_ALT, "hydrology": ROWS_HYDROLOGY, "frost": ROWS_FROST, "water_balance": ROWS_WATER_BALANCE,
-                "irrigation": ROWS_IRRIGATION, "floodplain": ROWS_FLOODPLAIN}
+                "irrigation": ROWS_IRRIGATION, "floodplain": ROWS_FLOODPLAIN, "hillslope": ROWS_HILLSLOPE}
 CELL_ROWS_ROUTING, CELL_ROWS_SUPPLY = range(2)  # cell_history_add_row: the cell-row families (ELMK_CELL_ROWS_*)
 CELL_ROW_FAMILIES = {"routing": CELL_ROWS_ROUTING, "supply": CELL_ROWS_SUPPLY}
 HYD_NROWS, HYD_NLAYER = 23, 10 # elmk_soil_hydrology_read: the row numbers are hydrology.ZWT .. hydrology.FSAT
@@ -889,6 +892,38 @@ class ELMState:
     def soil_hydrology_frost_clear(self):
         """Free the extension's rows only: the stage is the plain one again."""
         self._chk(self.lib.elmk_soil_hydrology_frost_clear(self.ctx), "soil_hydrology_frost_clear")
+
+    # -- hillslope lateral flow (include/elmk.h: elmk_hillslope_enable ...; hydrology.hillslope_head / hillslope_flow / step(lat=)) ------
+    def hillslope_enable(self, down, dist, width, area, elev, k_aniso):
+        """Order the columns along hillslopes (include/elmk.h, L1 - L3): down int32 [ncols] (>= 0 the downhill column, -1 the stream,
+        -2 on no hillslope), dist, width, area, elev float64 [ncols] (scalars are broadcast), k_aniso the ratio of horizontal to vertical
+        conductivity.  From here on soil_hydrology and run(..., RUN_HYDROLOGY) pass groundwater downhill.  Refused without the hydrology,
+        when already on, for a refusal of hydrology.hillslope_check, with the frost table or the floodplain infiltration on."""
+        d = None if down is None else np.ascontiguousarray(down, dtype=np.int32).reshape(-1)
+        if d is not None and d.size != self.ncols:
+            raise ValueError(f"hillslope_enable: {d.size} values of down for {self.ncols} columns")
+        a = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.ncols,)))
+             for v in (dist, width, area, elev)]
+        self._chk(self.lib.elmk_hillslope_enable(self.ctx, None if d is None else _p(d), *(None if v is None else _p(v) for v in a),
+                                                 float(k_aniso)), "hillslope_enable")
+
+    def hillslope_read(self, which, col0=0, n=None):
+        """Row `which` (HS_HEAD .. HS_QSTREAM) of columns [col0, col0 + n): float64 [n].  Synchronises."""
+        return self._read_row("hillslope_read", which, col0, n, self.ncols)
+
+    def hillslope_rows(self):
+        """Every row of the extension: float64 [HS_NROWS, ncols], the hs_out of hydrology.step(lat=)."""
+        return np.stack([self.hillslope_read(w) for w in range(HS_NROWS)])
+
+    def hillslope_budget(self):
+        """float64 [1]: the sum of QSTREAM, m3/s (hydrology.hillslope_budget).  Synchronises."""
+        sums = np.zeros(1)
+        self._chk(self.lib.elmk_hillslope_budget(self.ctx, _p(sums)), "hillslope_budget")
+        return sums
+
+    def hillslope_clear(self):
+        """Free the extension: the stage drains every column by its own baseflow again."""
+        self._chk(self.lib.elmk_hillslope_clear(self.ctx), "hillslope_clear")
 
     # -- aerosol deposition (include/elmk.h: elmk_aerosol_reserve ...; elmkernels_amd/aerosol.py restates the kernel) ----------
     def aerosol_reserve(self, ncells=None, idx=None, w=None):

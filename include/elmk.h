@@ -664,7 +664,7 @@ int elmk_active_layer_clear(elmk_ctx *ctx);
  * with the h2osfc store, the Zeng-Decker Richards solve with the aquifer as an extra row, the water-table update and drainage.  The
  * reference has none of it: its conservation row hardwires hydrology_source_sink = 0.0 (driver/kokkos/conserved_quantity_kokkos.cc:22)
  * and it expects an external subsurface model, so without this stage no kernel applies qflx_top_soil, qflx_rootsoi or the ground
- * evaporation terms to the soil layers.  Out of scope: lateral flow, VSFM, lakes, wetlands, urban (irrigation: the section of that name below).
+ * evaporation terms to the soil layers.  Out of scope: VSFM, lakes, wetlands, urban (lateral flow and irrigation: the sections of those names below).
  * This text is the specification; elmkernels_amd/hydrology.py: column() is the same operation on the host, and where an evaluation
  * order is not spelled out here that function fixes it (k_soil_hydrology.hip follows it statement by statement, bit for bit).
  *
@@ -820,6 +820,70 @@ enum { ELMK_HYDF_Q_PERCH_MAX = 0, ELMK_HYDF_FROST_TABLE = 1, ELMK_HYDF_ZWT_PERCH
 int elmk_soil_hydrology_frost_enable(elmk_ctx *ctx, const double *q_perch_max /*[ncols]*/);
 int elmk_soil_hydrology_frost_read(elmk_ctx *ctx, int which, double *host, int64_t col0, int64_t n);
 int elmk_soil_hydrology_frost_clear(elmk_ctx *ctx);
+
+/* ---- hillslope lateral flow ------------------------------------------------------------------------
+ * The hillslope hydrology of CLM5 / CTSM (Swenson et al. 2019; SubsurfaceLateralFlow with use_hillslope): columns ordered along a
+ * hillslope, Darcy flow between neighbours driven by the head difference, the lowest column discharging to the stream.  An opt-in
+ * extension of the soil hydrology stage with no run flag and no restart-image change: while it is on, elmk_soil_hydrology and the
+ * ELMK_RUN_HYDROLOGY stage enqueue two small launches (L1, L2) in front of the hydrology kernel and run its LAT form (L3).  The net
+ * lateral flux takes the place of F.1's rsub_top, so QFLX_DRAIN, QRUNOFF and ERRH2O carry it as they are; the water balance and the
+ * routing are unchanged.  The conventions are those of "soil hydrology": no contraction, elmk_pow, left association, that section's min
+ * and max; zi[j] is the bottom of layer j.  elmkernels_amd/hydrology.py: hillslope_head, hillslope_flow and column() fix any evaluation
+ * order this text leaves open.
+ * The geometry, all [ncols]: down[c] >= 0 the downhill column; -1: the column's lower edge is the stream; -2: the column is on no
+ * hillslope and keeps F.1's baseflow and the bits of the stage without the extension in every output.  dist: metres from the column's
+ * centre to its downhill neighbour's centre, or to the stream; width: metres of the lower edge; area: square metres; elev: metres of
+ * the surface above the stream's water surface.  k_aniso: the ratio of horizontal to vertical conductivity.
+ * Host checks (elmk_maps.h: hillslope_check), in this order; on refusal nothing is changed and the message names the row and the first
+ * offending column: the arguments; down in {-2, -1} or [0, ncols); no self-loop; no column draining into a -2 column; at most 8 columns
+ * drain into one; no cycle (the linear two-mark walk of the river network's check, nothing recursive); dist, width, area finite and > 0
+ * on hillslope columns; elev finite on hillslope columns; k_aniso finite and > 0.  The host builds the uphill map the device reads:
+ * 1, 2, 4 or 8 rows, ascending uphill index per slot, -1 padding.
+ *   L1 (launch 1, per column, from the values at the start of the stage: ZWT as stored, h2osoi_ice, dz, watsat, HKSAT, zi)
+ *      down == -2: HEAD = 0; TRANS = 0.  Else icefrac as in A and jwt as in D.1;
+ *      jwt == N: T = 0.  Else si, sd and imp = pow(10, -e_ice * (si / sd)) over j = max(jwt-1, 0) .. N-1 as in F.1;
+ *        T = 0.0; for j = jwt .. N-1 ascending: T = T + hksat[j] * (j == jwt ? zi[j] - zwt : dz[j]);  T = imp * T * 1e-3 * k_aniso.
+ *      HEAD = elev - zwt (m); TRANS = T (m2/s).
+ *   L2 (launch 2, per column c).  The flux of the edge from u to d = down[u], m3/s:
+ *        d == -1: g = max(HEAD[u] / dist[u], 0)  - the stream gives the land no water: there is no stream store yet;
+ *        else     g = (HEAD[u] - HEAD[d]) / dist[u];
+ *        g = min(max(g, -2), 2);  Td = (d != -1 && g < 0) ? TRANS[d] : TRANS[u];  vol(u) = Td * width[u] * g.
+ *      QLAT_OUT[c] = 1e3 * vol(c) / area[c];  QLAT_IN[c] = the sum from 0.0, in slot order, of 1e3 * vol(u) / area[c] over the uphill
+ *      slots, each vol(u) recomputed by c from the operands its owner uses, so both ends hold the same bits;  QLAT_NET = OUT - IN;
+ *      QSTREAM = vol(c) where down == -1, else 0.  down == -2: all four 0.  A NaN is stored as the canonical quiet NaN.
+ *   L3 (the hydrology kernel, columns with down != -2, in the place of F.1's rsub_top; rous as in F.1)
+ *      rsub_top = QLAT_NET[c]; rt = -rsub_top * dt.  jwt == N: F.2 as it is.  Else, if rt > 0: E's rising walk with rt for qt and
+ *      liq[j] = liq[j] + ql in every visited layer; afterwards liq[0] = liq[0] + rt with what is left; wa is untouched and rous is not
+ *      applied.  Otherwise (a NaN included): F.2's falling walk as it is.  F.3 - F.8, G and H are unchanged; QFLX_DRAIN is then the net
+ *      flux and may be negative.
+ * Three consequences: a context whose columns are all -2 has the bits of a context without the extension in every field and row; a flat
+ * hillslope (equal HEAD, the stream column's HEAD <= 0) has QLAT_* = 0 everywhere; over any hillslope sum(area * QLAT_NET) * 1e-3 equals
+ * sum(QSTREAM) up to the roundings of L2's divisions and products.
+ * The extension owns ELMK_HS_NROWS fp64 column rows [level stride], all recomputed every step: HEAD (m), TRANS (m2/s), QLAT_OUT, QLAT_IN,
+ * QLAT_NET (mm/s), QSTREAM (m3/s, non-zero only where down == -1); beside them the geometry, down and the uphill map, all counted in
+ * elmk_device_bytes.  Nothing of it is prognostic: the restart image of a context with the extension is byte for byte that of one
+ * without, and N + N steps across a restart equal 2N once the driver has enabled the extension again.
+ *   elmk_hillslope_enable   checks, allocates, uploads; drops the captured run step.  ELMK_E_INVALID, nothing changed: the hydrology
+ *                           is not enabled; already on; a null argument; a refusal of the checks; a stream being captured; the frost
+ *                           table is on (elmk_soil_hydrology_frost_clear first: F'.A skips F.1 and F.2, which would drop a flux the
+ *                           neighbours have booked); the floodplain infiltration is on (elmk_floodplain_infiltration_clear first).
+ *                           While the extension is on elmk_soil_hydrology_frost_enable and elmk_floodplain_infiltration_enable are
+ *                           refused ("elmk_hillslope_clear first").
+ *   elmk_hillslope_read     row `which` (ELMK_HS_*) of columns [col0, col0 + n) as doubles; synchronises.
+ *   elmk_hillslope_budget   sums[0] = the sum of QSTREAM through the conservation's reduction kernels; synchronises.
+ *   elmk_hillslope_clear    frees everything of the extension and drops the captured run step: the stage is F again.  Refused while a
+ *                           history or point-series entry reads its rows ("elmk_history_clear first").  elmk_soil_hydrology_clear
+ *                           frees the extension too.
+ * Tapes: ELMK_ROWS_HILLSLOPE (which = ELMK_HS_*) for elmk_column_history_add_row, elmk_gridded_history_add_row and the point series.
+ * A context that never enables it runs the kernels, launch sequences and graphs it ran before, allocates nothing more and saves the image
+ * it saved before.  Out of scope, later changes: a stream store coupled to the routing's channel depth (losing streams); the frost-table
+ * and floodplain-infiltration combinations; per-layer ice impedance in the transmissivity; hillslope-dependent forcing. */
+enum { ELMK_HS_HEAD = 0, ELMK_HS_TRANS = 1, ELMK_HS_QLAT_OUT = 2, ELMK_HS_QLAT_IN = 3, ELMK_HS_QLAT_NET = 4, ELMK_HS_QSTREAM = 5, ELMK_HS_NROWS = 6 };
+int elmk_hillslope_enable(elmk_ctx *ctx, const int32_t *down /*[ncols]*/, const double *dist /*[ncols]*/, const double *width /*[ncols]*/,
+                          const double *area /*[ncols]*/, const double *elev /*[ncols]*/, double k_aniso);
+int elmk_hillslope_read(elmk_ctx *ctx, int which /*ELMK_HS_**/, double *host, int64_t col0, int64_t n);
+int elmk_hillslope_budget(elmk_ctx *ctx, double *sums /*[1]: the sum of QSTREAM*/);
+int elmk_hillslope_clear(elmk_ctx *ctx);
 
 /* ---- water balance ---------------------------------------------------------------------------------
  * The closed column water budget of a step that runs the soil hydrology, and ELM's standard hydrology outputs.  The conservation row of
@@ -1593,6 +1657,8 @@ enum { ELMK_ROWS_ALT = 0, ELMK_ROWS_HYDROLOGY = 1, ELMK_ROWS_FROST = 2, ELMK_ROW
 /* the floodplain infiltration's three column rows (which = ELMK_FPI_*): the family's number lies past the cell-row families', which the
  * restart image numbers from ELMK_ROWS_NFAMILY on, so that every image keeps the numbers it had */
 enum { ELMK_ROWS_FLOODPLAIN = 7 };
+/* the hillslope lateral flow's six column rows (which = ELMK_HS_*): the next number no family and no image uses */
+enum { ELMK_ROWS_HILLSLOPE = 8 };
 #define ELMK_RESTART_ROW_BASE 0x40000000
 #define ELMK_RESTART_ROW_FIELD(family, which) (ELMK_RESTART_ROW_BASE + ((family) << 16) + (which))
 int elmk_column_history_add_row(elmk_ctx *ctx, int tape, int family, int which, int op);

@@ -358,6 +358,21 @@ class ELMInterface {
   void soil_hydrology_frost_enable(const double* q_perch_max) { ok(elmk_soil_hydrology_frost_enable(ctx_, q_perch_max)); }
   void soil_hydrology_frost_read(int which, double* host) { ok(elmk_soil_hydrology_frost_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
   void soil_hydrology_frost_clear() { ok(elmk_soil_hydrology_frost_clear(ctx_)); }
+  /* Its hillslope lateral flow (elmk.h "hillslope lateral flow", L1 - L3): from hillslope_enable(down, dist, width, area, elev [ncols]
+   * each, k_aniso) on the stage passes groundwater downhill along down[] (-1: the stream, -2: on no hillslope) and the lowest column
+   * discharges to the stream; hillslope_read() fills [ncols] of row ELMK_HS_*, hillslope_budget() sums[1] with the stream discharge
+   * (m3/s); hillslope_clear() returns to every column's own baseflow.  It excludes the frost table and the floodplain infiltration. */
+  void hillslope_enable(const int32_t* down, const double* dist, const double* width, const double* area, const double* elev, double k_aniso)
+  {
+    ok(elmk_hillslope_enable(ctx_, down, dist, width, area, elev, k_aniso));
+  }
+  void hillslope_read(int which, double* host) { ok(elmk_hillslope_read(ctx_, which, host, 0, host ? ncols_ : 0)); }
+  void hillslope_rows(double* host /*[ELMK_HS_NROWS][ncols]*/)
+  {
+    for (int w = 0; w < ELMK_HS_NROWS; w++) hillslope_read(w, host + (size_t)w * (size_t)ncols_);
+  }
+  void hillslope_budget(double* sums) { ok(elmk_hillslope_budget(ctx_, sums)); }
+  void hillslope_clear() { ok(elmk_hillslope_clear(ctx_)); }
 
   /* Water balance (elmk.h "water balance"): the closed column water budget of a step that runs the soil hydrology, with total runoff
    * QRUNOFF, total water storage ENDWB (ELM's TWS) and the soil-water rows.  water_balance_enable(tol_mm) allocates the rows;
